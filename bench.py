@@ -10,13 +10,27 @@ With --gpus P > 1 the same problem (strong scaling) is factored over P ranks
 with 1-D block-cyclic block columns and an RCCL broadcast of every factored
 panel (gaussian_processes_amd/multi_gpu.py).
 
-Prints ONE JSON line (rank 0) with the driver's contract plus
+Prints ONE JSON line (rank 0) with the driver's contract (metric, value, unit,
+higher_is_better, dtype, ms_per_step).  On one GPU a plain run does only that:
+set-up, warm-up, the --steps timed steps (no per-launch events), the outputs
+when --dump-outputs DIR is given, the line.  --full adds, on one GPU:
   roofline      -- the dominant kernel (fp64 MFMA gemm_nt: SYRK/GEMM updates of the
                    factorisation), achieved = sum of algorithmic flops of its
                    launches / sum of their HIP-event durations in the timed region
+                   (the timed steps then carry the per-launch events; --no-prof drops them)
+  check         -- K alpha = y on sampled rows of the timed result
+  secondary     -- the other BASELINE configs, sizes and precisions, the gp.GP API path
+                   (--no-secondary drops them)
   cpu_baseline  -- the oracle (CPU restatement of the reference's stage sequence)
                    timed on this host on a bounded sample and scaled stage by
-                   stage (N^3 / N^2 / N) to the workload; N=1, rank 0 only.
+                   stage (N^3 / N^2 / N) to the workload; N=1, rank 0 only
+                   (--no-cpu-baseline drops it).
+
+--dump-outputs DIR writes what the last timed step computed, as a caller of the
+handle path receives it: DIR/log_lh.npy (float64, shape (1,)), DIR/alpha.npy
+(K^-1 y, float64, shape (N,)) and DIR/mean.npy (posterior mean at the m test
+points, in the run's dtype).  The inputs are seeded: the same arguments give the
+same inputs in every run.
 """
 import argparse
 import ctypes
@@ -59,7 +73,17 @@ def parse_args():
                     help="skip the side measurements (configs[1], [2], [4] and the gp.GP API path)")
     ap.add_argument("--launch-check", action="store_true",
                     help="rendezvous only (gloo, no GPU work): proves that `bench.py --gpus P` starts P ranks")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="one GPU: also the roofline (per-launch events in the timed steps), the residual check, the secondary "
+                         "measurements and the CPU baseline; a plain run times the headline steps and nothing else")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's results (log_lh, alpha, mean) to DIR/<name>.npy (one GPU only)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and (args.gpus > 1 or os.environ.get("GPX_MG_REHEARSE") or os.environ.get("GPX_BENCH_FORCE_DIST")):
+        ap.error("--dump-outputs is implemented for the single-GPU run only")
+    return args
 
 
 def synth(N, d, m, npdt):
@@ -399,7 +423,10 @@ def main():
 
     # ---- single GPU: everything through the gpx_gp handle, inputs resident in HBM ----
     result = measure_single(args, lib, _lib, N, d, m, dtid, npdt, args.steps, args.warmup, local_rank,
-                            prof_on=not args.no_prof)
+                            prof_on=args.full and not args.no_prof, check=args.full, dump_dir=args.dump_outputs)
+    if not args.full:
+        print(json.dumps(result))
+        return
     if not args.no_secondary and (N, d) != (8192, 8):
         result["secondary"] = secondary_measurements(args, lib, _lib, local_rank, result)
     if not args.no_cpu_baseline:
@@ -568,7 +595,7 @@ def measure_api(headline):
             "api_over_handle": round(sec / headline["value"], 4), "log_lh": llh}
 
 
-def measure_single(args, lib, _lib, N, d, m, dtid, npdt, steps, warmup, local_rank, prof_on):
+def measure_single(args, lib, _lib, N, d, m, dtid, npdt, steps, warmup, local_rank, prof_on, check=True, dump_dir=None):
     from gaussian_processes_amd.device import DeviceBuffer, sync
     dtype_name = "f64" if dtid == _lib.F64 else "f32"
     h, w, s = 1.0, 0.5 * np.sqrt(d), 1.0
@@ -620,16 +647,28 @@ def measure_single(args, lib, _lib, N, d, m, dtid, npdt, steps, warmup, local_ra
             prof[nm] = {"launches": a.value, "ms": b.value, "work": c.value}
         _lib.check(lib.gpx_prof_enable(0))
 
-    mean_host = dmean.to_host().astype(np.float64)
+    mean_out = dmean.to_host()
+    mean_host = mean_out.astype(np.float64)
     info = ctypes.c_int(0)
     _lib.check(lib.gpx_gp_info(handle, ctypes.byref(info)))
     assert info.value == 0 and np.isfinite(llh) and np.isfinite(mean_host).all()
-    # the timed result itself is checked: K alpha = y on sampled rows, outside the timed region
-    alpha_host = np.empty(N, dtype=np.float64)
-    _lib.check(lib.gpx_gp_get_alpha(handle, _lib.dptr(alpha_host)))
-    residual, nres = sampled_row_residual(X, y, alpha_host, h, w, s)
-    res_tol = 1e-9 if dtype_name == "f64" else 2e-3
-    assert residual < res_tol, "sampled-row residual %.3e exceeds %.1e" % (residual, res_tol)
+    if check or dump_dir:
+        alpha_host = np.empty(N, dtype=np.float64)
+        _lib.check(lib.gpx_gp_get_alpha(handle, _lib.dptr(alpha_host)))
+    check_out = None
+    if check:
+        # the timed result itself is checked: K alpha = y on sampled rows, outside the timed region
+        residual, nres = sampled_row_residual(X, y, alpha_host, h, w, s)
+        res_tol = 1e-9 if dtype_name == "f64" else 2e-3
+        assert residual < res_tol, "sampled-row residual %.3e exceeds %.1e" % (residual, res_tol)
+        check_out = {"sampled_rows": nres, "max_abs_residual_K_alpha_minus_y_over_max_y": residual,
+                     "tolerance": res_tol}
+    if dump_dir:
+        # the last timed step's results as the handle path hands them to its caller
+        os.makedirs(dump_dir, exist_ok=True)
+        np.save(os.path.join(dump_dir, "log_lh.npy"), np.array([llh], dtype=np.float64))
+        np.save(os.path.join(dump_dir, "alpha.npy"), alpha_host)
+        np.save(os.path.join(dump_dir, "mean.npy"), mean_out)
 
     peak = FP64_MFMA_PEAK_TFLOPS if dtype_name == "f64" else FP32_MFMA_PEAK_TFLOPS
     roofline = None
@@ -702,8 +741,7 @@ def measure_single(args, lib, _lib, N, d, m, dtid, npdt, steps, warmup, local_ra
         "potrf_tflops": round(potrf_tflops, 3) if potrf_tflops else None,
         "potrf_frac_of_peak": round(potrf_tflops / peak, 4) if potrf_tflops else None,
         "log_lh": llh,
-        "check": {"sampled_rows": nres, "max_abs_residual_K_alpha_minus_y_over_max_y": residual,
-                  "tolerance": res_tol},
+        "check": check_out,
         "roofline": roofline,
         "kernels": {k: {"launches_per_step": v["launches"] / steps,
                         "ms_per_step": round(v["ms"] / steps, 3)} for k, v in prof.items()},

@@ -7,10 +7,10 @@ ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 OUT=$ROOT/gpurun_out/$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_f32 -o bench -- python3 $ROOT/bench.py --problem-n 32768 --problem-d 16 --dtype f32 --no-cpu-baseline --no-secondary > $OUT/bench_n32768_f32.json 2> $OUT/f32.err || exit 1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_f32 -o bench -- python3 $ROOT/bench.py --full --problem-n 32768 --problem-d 16 --dtype f32 --no-cpu-baseline --no-secondary > $OUT/bench_n32768_f32.json 2> $OUT/f32.err || exit 1
 rm -f $OUT/stats_f32/*kernel_trace.csv
 echo "f32 done"
-python3 $ROOT/bench.py --problem-n 8192 --problem-d 8 --problem-m 1024 --no-cpu-baseline --no-secondary > $OUT/bench_n8192.json 2> $OUT/n8192.err || exit 1
+python3 $ROOT/bench.py --full --problem-n 8192 --problem-d 8 --problem-m 1024 --no-cpu-baseline --no-secondary > $OUT/bench_n8192.json 2> $OUT/n8192.err || exit 1
 python3 $ROOT/bench.py --problem-n 8192 --problem-d 8 --problem-m 1024 --no-cpu-baseline --no-secondary --no-prof --steps 10 --warmup 3 > $OUT/bench_n8192_noprof.json 2>> $OUT/n8192.err || exit 1
 echo "n8192 done"
 cd $ROOT
