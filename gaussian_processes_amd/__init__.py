@@ -14,10 +14,11 @@ import logging
 
 from . import ext
 from .gp import GP
+from .dist_gp import DistributedGP
 from .kernels import Kernel, GaussianKernel, PeriodicKernel
 from . import kernels
 
-__all__ = ["ext", "GP", "Kernel", "PeriodicKernel", "GaussianKernel"]
+__all__ = ["ext", "GP", "DistributedGP", "Kernel", "PeriodicKernel", "GaussianKernel"]
 
 logger = logging.getLogger("gp")
 logger.setLevel("INFO")

@@ -143,6 +143,7 @@ _SIGNATURES = {
     "gpx_mg_set_data": (c_int, [c_void_p, c_double_p, c_double_p]),
     "gpx_mg_fit": (c_int, [c_void_p, c_double_p, c_double, c_double_p, c_int_p]),
     "gpx_mg_mean": (c_int, [c_void_p, c_double_p, c_double_p, c_int64, c_double_p]),
+    "gpx_mg_cov": (c_int, [c_void_p, c_double_p, c_double_p, c_int64, c_double_p]),
     "gpx_mg_get_alpha": (c_int, [c_void_p, c_double_p]),
     "gpx_mg_scalars": (c_int, [c_void_p, c_double_p, c_double_p, c_int_p]),
     "gpx_mg_timing": (c_int, [c_void_p, c_double_p]),

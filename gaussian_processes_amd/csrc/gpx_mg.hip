@@ -23,6 +23,7 @@
 // (gpx_mg_create_cb): the same C schedule over any transport -- the tests run it with several ranks on
 // ONE GPU over gloo, which RCCL cannot do.
 #include "gpx_common.h"
+#include "gpx_gp_internal.h"   // DevBuf
 #include <dlfcn.h>
 #include <climits>
 #include <cmath>
@@ -200,6 +201,7 @@ struct gpx_mg {
     // device state
     void *A = nullptr, *pbuf[2] = {nullptr, nullptr}, *x = nullptr, *y = nullptr, *alpha = nullptr, *tmp = nullptr;
     double *scal = nullptr;                       // scal: [0] logdet block [1] y^T alpha [2] logdet acc [3] spare
+                                                  // [4, 12) gpx_mg_cov's agreement vector (mg_cov_agree)
     int *info = nullptr;                          // [0] info [1] reduction key
     hipStream_t S = nullptr, Q = nullptr, B = nullptr;   // main (updates, solves) / panel (factor, pack) / panel broadcasts
     hipStream_t O = nullptr;                      // lowest priority: the diagonal blocks' solve operators, off the panel chain
@@ -686,7 +688,7 @@ static int mg_alloc(gpx_mg *g)
     MG_ALLOC(y, (size_t)n * es);
     MG_ALLOC(alpha, (size_t)n * es);
     MG_ALLOC(tmp, (size_t)g->nb * es);
-    MG_ALLOC(scal, 4 * sizeof(double));
+    MG_ALLOC(scal, 12 * sizeof(double));
     MG_ALLOC(info, 4 * sizeof(int));
 #undef MG_ALLOC
     GPX_HIP(hipMemset(g->info, 0, 4 * sizeof(int)));
@@ -733,6 +735,119 @@ static int mg_new(gpx_mg **out, int dtype, int kernel, int64_t n, int d, int64_t
     if (tune().mg_bcast_set) g->bcast_sag = tune().mg_bcast_sag;
     g->owner_first = tune().mg_owner_first_set ? (tune().mg_owner_first != 0) : (world >= 2);
     *out = g;
+    return GPX_OK;
+}
+
+// ---- posterior covariance (gpx_mg_cov) ------------------------------------------------------------------------------
+// cov = Kxoxo - X X^T with X = Kxox L^-T, L left where the fit put it.  The forward solve is a FAN-IN over the block
+// columns: every rank holds an m x n accumulator B, block-major (block j: m x nb at j m nb, row-major, ld nb -- so that
+// the reduction of one block is one contiguous collective), which starts as Kxox on its own blocks and zero elsewhere.
+// Per block j: B_j is sum-reduced over the ranks; its owner solves X_j = B_j L_jj^-T in place and subtracts
+// X_j L[rows of block j', block column j]^T from every later block j' (block j + 1 first, so that its reduction overlaps
+// the rest of the update) and X_j X_j^T from its share of C.  Rank 0's C starts as Kxoxo, the others' at zero; one
+// all-reduce of C at the end.  Traffic: n m elements reduced (m nb per block) plus m ldc for C.
+
+// FNV-1a over the bytes of a host array, folded to 52 bits -- exact as a double, so that one F64 MAX all-reduce of
+// (h, -h) tells every rank whether all ranks passed the same bytes
+static double mg_hash(const void *p, size_t bytes)
+{
+    uint64_t h = 1469598103934665603ull;
+    const unsigned char *c = (const unsigned char *)p;
+    for (size_t i = 0; i < bytes; ++i) { h ^= c[i]; h *= 1099511628211ull; }
+    return (double)(h >> 12);
+}
+
+// the handle's sync-event pool holds at least `count` events (created up front: nothing fails half way through a run)
+static int mg_events_reserve(gpx_mg *g, size_t count)
+{
+    while (g->ev.size() < count) {
+        hipEvent_t x;
+        GPX_HIP(hipEventCreateWithFlags(&x, hipEventDisableTiming));
+        g->ev.push_back(x);
+    }
+    return GPX_OK;
+}
+
+// Every rank's local verdict and arguments, one F64 MAX all-reduce, the same status on every rank.  v (host, 8 values):
+// [0] a local allocation failed [1] a local argument is bad [2] m [3] -m [4] hash(xo) [5] -hash(xo) [6] hash(params)
+// [7] -hash(params); (x, -x) agree on every rank iff max(x) == -max(-x).
+static int mg_cov_agree(gpx_mg *g, double v[8])
+{
+    double *dv = g->scal + 4;
+    GPX_HIP(hipMemcpyAsync(dv, v, 8 * sizeof(double), hipMemcpyHostToDevice, g->S));
+    GPX_TRY(mg_allreduce(g, dv, 8, GPX_F64, 1, g->S));
+    GPX_HIP(hipMemcpyAsync(v, dv, 8 * sizeof(double), hipMemcpyDeviceToHost, g->S));
+    GPX_HIP(hipStreamSynchronize(g->S));
+    if (v[0] != 0) { set_error("gpx_mg_cov: a device allocation failed on at least one rank"); return GPX_ERR_NOMEM; }
+    if (v[1] != 0) { set_error("gpx_mg_cov: bad arguments on at least one rank (m < 0 or a NULL pointer)"); return GPX_ERR_ARG; }
+    if (v[2] != -v[3]) { set_error("gpx_mg_cov: the ranks called with different m (%.0f .. %.0f)", -v[3], v[2]); return GPX_ERR_ARG; }
+    if (v[4] != -v[5]) { set_error("gpx_mg_cov: the ranks called with different xo"); return GPX_ERR_ARG; }
+    if (v[6] != -v[7]) { set_error("gpx_mg_cov: the ranks called with different params"); return GPX_ERR_ARG; }
+    return GPX_OK;
+}
+
+// B_{j'} -= X_j L[rows of block j', block column j]^T for the blocks j' in [a, b): one launch -- a batch over blocks that
+// are all nb wide, or a single block of any width.  Rows stop short of the rider row n.
+static int mg_cov_update(gpx_mg *g, int64_t j, int64_t a, int64_t b, char *Bm, int64_t m, hipStream_t st)
+{
+    if (b <= a) return GPX_OK;
+    const size_t es = g->es;
+    const int64_t nb = g->nb, blk = m * nb, cl = g->local_col(j), kb = g->kb(j);
+    const char *X = Bm + (size_t)j * blk * es;
+    if (b - a == 1)
+        return gemm_nt(g->dtype, m, g->kb(a), kb, X, nb, g->Aat(g->k0(a), cl), g->ld, Bm + (size_t)a * blk * es, nb, -1.0,
+                       GPX_FULL, 0, 0, st);
+    Batch bt;
+    bt.count = (int)(b - a); bt.sA = 0; bt.sB = nb * g->ld; bt.sC = blk;
+    return gemm_nt(g->dtype, m, nb, kb, X, nb, g->Aat(g->k0(a), cl), g->ld, Bm + (size_t)a * blk * es, nb, -1.0, GPX_FULL,
+                   0, 0, st, 0, 0, &bt);
+}
+
+// The schedule, per owned block j: the chain -- in-block solve, then the look-ahead update of block j + 1 -- on Q (the
+// fit's high-priority panel stream), the rest of the update on S, where it overlaps the next block's solve; B (the
+// panel-broadcast stream of the fit) carries the block reductions in block order on every rank; O accumulates X_j X_j^T
+// into C off the chain.  A look-ahead waits for the earlier rest updates (they reach block j + 1 too).
+// dxo: m x d on the device; Bm, C: this call's buffers.
+static int mg_cov_run(gpx_mg *g, const double *params, const void *dxo, int64_t m, char *Bm, void *C, int64_t ldc)
+{
+    hipStream_t S = g->S, Q = g->Q, R = g->B, O = g->O;
+    const size_t es = g->es;
+    const int64_t nb = g->nb, blk = m * nb, nblk = g->nblk, last = nblk - 1;
+    const int64_t full_end = g->kb(last) == nb ? nblk : last;      // blocks [0, full_end) are nb wide
+    auto Bj = [&](int64_t j) { return Bm + (size_t)j * blk * es; };
+    GPX_HIP(hipMemsetAsync(Bm, 0, (size_t)nblk * blk * es, S));
+    GPX_HIP(hipMemsetAsync(C, 0, (size_t)m * ldc * es, S));
+    for (int64_t j : g->my_blocks)
+        GPX_TRY(kmat(g->dtype, g->kernel, GPX_K, dxo, m, (const char *)g->x + (size_t)g->k0(j) * g->d * es, g->kb(j), g->d,
+                     params, 0.0, GPX_FULL, Bj(j), nb, S));
+    if (g->rank == 0)
+        GPX_TRY(kmat(g->dtype, g->kernel, GPX_K, dxo, m, dxo, m, g->d, params, 0.0, GPX_FULL, C, ldc, S));
+    GPX_TRY(mg_order(g, S, R));
+    for (int64_t j = 0; j < nblk; ++j) {
+        // (R already waits for every local update of block j: see the mg_order(S, R) calls below)
+        GPX_TRY(mg_allreduce(g, Bj(j), (size_t)blk, g->dtype, 0, R));
+        if (g->owner(j) != g->rank) {
+            if (j < last) GPX_TRY(mg_order(g, S, R));            // this rank's contributions to block j + 1 are all on S
+            continue;
+        }
+        const int64_t k0 = g->k0(j), kb = g->kb(j), cl = g->local_col(j);
+        GPX_TRY(mg_order(g, R, Q));
+        GPX_TRY(trsm_right_lt(g->dtype, g->Aat(k0, cl), kb, g->ld, Bj(j), m, nb, Q, 0, &g->ops[(size_t)(j / g->world)]));
+        GPX_TRY(mg_order(g, Q, O));
+        GPX_TRY(gemm_nt(g->dtype, m, m, kb, Bj(j), nb, Bj(j), nb, C, ldc, -1.0, GPX_FULL, 0, 0, O));
+        if (j == last) break;
+        GPX_TRY(mg_order(g, Q, S));                               // X_j is final: the rest of the update may use it
+        GPX_TRY(mg_order(g, S, Q));                               // (the earlier rest updates reach block j + 1)
+        GPX_TRY(mg_cov_update(g, j, j + 1, j + 2, Bm, m, Q));     // look-ahead: block j + 1 ...
+        GPX_TRY(mg_order(g, Q, R));                               // ... whose reduction may start now
+        GPX_TRY(mg_cov_update(g, j, j + 2, full_end, Bm, m, S));  // the rest, one batched launch
+        if (full_end == last && last >= j + 2) GPX_TRY(mg_cov_update(g, j, last, nblk, Bm, m, S));   // a ragged last block
+    }
+    GPX_TRY(mg_order(g, S, R));
+    GPX_TRY(mg_order(g, Q, R));
+    GPX_TRY(mg_order(g, O, R));
+    GPX_TRY(mg_allreduce(g, C, (size_t)m * ldc, g->dtype, 0, R));
+    GPX_TRY(mg_order(g, R, S));
     return GPX_OK;
 }
 
@@ -1056,6 +1171,59 @@ int gpx_mg_mean(gpx_mg_t *g, const double *params, const double *xo, int64_t m, 
     (void)hipStreamSynchronize(g->S);
     (void)hipFree(dxo); (void)hipFree(dout);
     return rc;
+}
+
+int gpx_mg_cov(gpx_mg_t *g, const double *params, const double *xo, int64_t m, double *out)
+{
+    MG_ENTER(g);
+    if (g->rehearse) { set_error("gpx_mg_cov: a rehearsal handle holds one rank's share without a communicator"); return GPX_ERR_UNSUPPORTED; }
+    GPX_ARG(g->fitted, "mg is not fitted");                       // (the same on every rank: fit is collective)
+    if (g->info_host != 0) {                                      // (the reduced info word: the same on every rank)
+        set_error("gpx_mg_cov: the factor is not positive definite (info = %d)", g->info_host);
+        return GPX_ERR_ARG;
+    }
+    const size_t es = g->es;
+    const bool args_ok = m >= 0 && params && (m == 0 || (xo && out));
+    double v[8] = {0.0, args_ok ? 0.0 : 1.0, (double)m, -(double)m, 0.0, 0.0, 0.0, 0.0};
+    if (args_ok) {
+        v[4] = mg_hash(xo, (size_t)m * g->d * sizeof(double));
+        v[6] = mg_hash(params, (g->kernel == GPX_KERNEL_PERIODIC ? 3 : 2) * sizeof(double));
+    }
+    v[5] = -v[4]; v[7] = -v[6];
+    // everything this call allocates, before anything that depends on m is enqueued
+    const int64_t ldc = round_up(std::max<int64_t>(m, 1), 16);
+    DevBuf dxo, Bm, C;
+    if (args_ok && m > 0) {
+        const bool ok = dxo.alloc((size_t)m * g->d * es) == GPX_OK && Bm.alloc((size_t)g->nblk * m * g->nb * es) == GPX_OK &&
+                        C.alloc((size_t)m * ldc * es) == GPX_OK && mg_events_reserve(g, (size_t)(6 * g->nblk + 8)) == GPX_OK;
+        if (!ok) { (void)hipGetLastError(); v[0] = 1.0; }
+    }
+    GPX_TRY(mg_cov_agree(g, v));
+    if (m == 0) return GPX_OK;
+    struct Drain {                                                // every stream idle before the buffers above are freed
+        gpx_mg *g;
+        ~Drain() { for (hipStream_t st : {g->S, g->Q, g->B, g->O}) (void)hipStreamSynchronize(st); }
+    } drain{g};
+    g->ev_next = 0;                                               // (the fit drained every stream: its events are free)
+    if (g->dtype == GPX_F64) {
+        GPX_HIP(hipMemcpy(dxo.p, xo, (size_t)m * g->d * 8, hipMemcpyHostToDevice));
+    } else {
+        std::vector<float> h((size_t)m * g->d);
+        for (size_t i = 0; i < h.size(); ++i) h[i] = (float)xo[i];
+        GPX_HIP(hipMemcpy(dxo.p, h.data(), h.size() * 4, hipMemcpyHostToDevice));
+    }
+    GPX_TRY(mg_cov_run(g, params, dxo.p, m, (char *)Bm.p, C.p, ldc));
+    if (g->dtype == GPX_F64) {
+        GPX_HIP(hipMemcpy2DAsync(out, (size_t)m * 8, C.p, (size_t)ldc * 8, (size_t)m * 8, (size_t)m, hipMemcpyDeviceToHost, g->S));
+        GPX_HIP(hipStreamSynchronize(g->S));
+    } else {
+        std::vector<float> h((size_t)m * ldc);
+        GPX_HIP(hipMemcpyAsync(h.data(), C.p, h.size() * 4, hipMemcpyDeviceToHost, g->S));
+        GPX_HIP(hipStreamSynchronize(g->S));
+        for (int64_t i = 0; i < m; ++i)
+            for (int64_t k = 0; k < m; ++k) out[i * m + k] = (double)h[(size_t)(i * ldc + k)];
+    }
+    return GPX_OK;
 }
 
 int gpx_mg_get_alpha(gpx_mg_t *g, double *out)

@@ -75,6 +75,10 @@ def default_nb(n, world=8):
 
 
 # ------------------------------------------------- the C schedule (gpx_mg_*, RCCL) --
+class RankMismatchError(_lib.GpxError, ValueError):
+    """A collective call whose ranks did not agree on their arguments (gpx_mg_cov): raised on every rank."""
+
+
 class GlooCallbacks(object):
     """Host-side collectives for gpx_mg_create_cb: device pointer -> host staging -> torch.distributed
     (any CPU backend) -> device.  Slow by construction; it exists so that the C schedule can be run with
@@ -88,6 +92,7 @@ class GlooCallbacks(object):
         self.torch, self.dist = torch, dist
         self.group = _cpu_group(dist)          # host buffers: never over an nccl default group
         self.rank = dist.get_rank()
+        self.world = dist.get_world_size()
         self.lib = _lib.load()
         self.error = None
         self.bcast = _lib.MG_BCAST_FN(self._bcast)
@@ -236,6 +241,21 @@ class NativeDistributedGP(object):
         xo = np.ascontiguousarray(np.asarray(xo, dtype=np.float64).reshape(-1, self.d))
         out = np.empty(xo.shape[0], dtype=np.float64)
         self._check(self.lib.gpx_mg_mean(self.h, _lib.dptr(p), _lib.dptr(xo), xo.shape[0], _lib.dptr(out)))
+        return out
+
+    def cov(self, params, xo):
+        """Posterior covariance at xo, (m, m), on every rank (gpx_mg_cov: L stays distributed).  Collective: every rank
+        calls it with the same params and xo after the same fit.  The ranks agree before any work, so a disagreement (m,
+        xo or params differ between ranks) raises `RankMismatchError` on every rank instead of hanging."""
+        if self.info:                          # the reduced info word of the fit: the same on every rank
+            raise _lib.lapack_info_error(self.info)
+        p = np.ascontiguousarray(params, dtype=np.float64)
+        xo = np.ascontiguousarray(np.asarray(xo, dtype=np.float64).reshape(-1, self.d))
+        out = np.empty((xo.shape[0], xo.shape[0]), dtype=np.float64)
+        rc = self.lib.gpx_mg_cov(self.h, _lib.dptr(p), _lib.dptr(xo), xo.shape[0], _lib.dptr(out))
+        if rc == _lib.ERR_ARG and (self._cb is None or self._cb.error is None):
+            raise RankMismatchError(_lib.last_error())    # (well-formed here, shaped above: the ranks disagreed)
+        self._check(rc)
         return out
 
     @property

@@ -469,6 +469,13 @@ int gpx_mg_set_data(gpx_mg_t *mg, const double *x, const double *y);
 int gpx_mg_fit(gpx_mg_t *mg, const double *params, double s, double *log_lh, int *info);
 /* posterior mean at xo (m, d) HOST float64 -> out (m,) on every rank (each evaluates a slice) */
 int gpx_mg_mean(gpx_mg_t *mg, const double *params, const double *xo, int64_t m, double *out);
+/* posterior covariance at xo (m, d) HOST float64 -> out (m, m) HOST float64 on every rank: Kxoxo - X X^T with
+ * X = Kxox L^-T, L left distributed (a fan-in forward solve over the block columns: one all-reduce of m nb elements
+ * per block, one of m x m at the end).  Collective: every rank calls it with the same arguments after the same
+ * gpx_mg_fit.  The ranks agree on their local checks and allocations before any work: all go on, or all return the
+ * same status (GPX_ERR_ARG when m, xo or params differ between ranks, GPX_ERR_NOMEM when an allocation failed on one).
+ * GPX_ERR_ARG after a fit that was not positive definite; GPX_ERR_UNSUPPORTED on a rehearsal handle. */
+int gpx_mg_cov(gpx_mg_t *mg, const double *params, const double *xo, int64_t m, double *out);
 int gpx_mg_get_alpha(gpx_mg_t *mg, double *out);
 int gpx_mg_scalars(gpx_mg_t *mg, double *logdet, double *yta, int *info);
 /* this rank's times of the last fit, ms (HIP events): [0] kernel build [1] factorisation [2] solves
