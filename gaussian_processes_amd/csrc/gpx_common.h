@@ -107,18 +107,9 @@ struct DeviceGuard {
     ~DeviceGuard() { if (switched && prev >= 0) (void)hipSetDevice(prev); }
 };
 
-// Everything a host thread enqueues through this library shares that thread's grow-only scratch buffers (block inverses and
-// operators of the solves, the panels' hand-off blocks, reduction scratch ...).  Calls on ONE stream are ordered by the stream;
-// a call on ANOTHER stream first waits for the work of the call before it: handles fitted asynchronously back to back from
-// one thread (each on its own stream) would otherwise race on those buffers (seen once as a wrong log_lh in the four-handle
-// test of tests/test_gpu_configs.py, when faster panels changed the overlap).  One event record per API call; nothing is
-// recorded or waited for while a stream is being captured.
-void stream_epoch_bump();          // call before destroying any stream (see TurnState, gpx_runtime.hip)
-struct StreamTurn {
-    hipStream_t st;
-    explicit StreamTurn(hipStream_t s);
-    ~StreamTurn();
-};
+}  // namespace gpx
+#include "gpx_mem.h"   // who owns which device memory; StreamTurn
+namespace gpx {
 
 // parameters of a kernel-matrix member, precomputed on the host in f64
 struct KParams {
@@ -175,7 +166,7 @@ bool panel_res_fold(int64_t rows, int64_t kpre, int64_t kb, size_t es, int64_t l
 // Per-factor block operators of the single-right-hand-side solves (gpx_solve.hip, "operator form"): owned by
 // whoever owns the factor; `valid` must be cleared whenever the factor changes.  nullptr: built per call.
 struct TrsvOps {
-    void *buf = nullptr; size_t bytes = 0;
+    GrowBuf mem;                 // trsv_ops_bytes(dtype, n) of the factor; a view into a larger block never release()s
     bool valid = false;          // all blocks of the CURRENT factor have their operators
     int64_t built = 0;           // leading 512-blocks of the current factor that have them (trsv_ops_build_upto)
     void invalidate() { valid = false; built = 0; }   // a new factor: every owner calls this, never `valid = false` alone

@@ -54,16 +54,12 @@ static int upload_f64(int dtype, void *dst, const double *src, int64_t count, hi
         GPX_HIP(hipStreamSynchronize(st));
         return GPX_OK;
     }
-    double *tmp = nullptr;
-    GPX_HIP(hipMalloc((void **)&tmp, count * 8));
-    hipError_t e = hipMemcpyAsync(tmp, src, count * 8, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL((cvt_from_f64<float>), dim3((unsigned)cdiv(count, 256)), dim3(256), 0, st,
-                           tmp, (float *)dst, count);
-        e = hipStreamSynchronize(st);
-    }
-    (void)hipFree(tmp);
-    if (e != hipSuccess) return hip_fail(e, "upload_f64", __FILE__, __LINE__);
+    DevBuf tmp;
+    GPX_TRY(tmp.alloc(count * 8));
+    GPX_HIP(hipMemcpyAsync(tmp.p, src, count * 8, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL((cvt_from_f64<float>), dim3((unsigned)cdiv(count, 256)), dim3(256), 0, st,
+                       (const double *)tmp.p, (float *)dst, count);
+    GPX_HIP(hipStreamSynchronize(st));
     return GPX_OK;
 }
 
@@ -73,8 +69,9 @@ static int download_f64(int dtype, double *dst, int64_t ldh, const void *src, in
 {
     if (rows <= 0 || cols <= 0) return GPX_OK;
     if (cols == 1 && lds == 1 && ldh == 1) { cols = rows; rows = 1; lds = cols; ldh = cols; }   // vector
-    double *tmp = nullptr;
-    GPX_HIP(hipMalloc((void **)&tmp, (size_t)rows * cols * 8));
+    DevBuf buf;
+    GPX_TRY(buf.alloc((size_t)rows * cols * 8));
+    double *tmp = (double *)buf.p;
     dim3 grid((unsigned)cdiv(cols, 256), (unsigned)std::min<int64_t>(rows, 32768)), block(256);
     if (dtype == GPX_F64)
         hipLaunchKernelGGL((cvt_to_f64_2d<double>), grid, block, 0, st, (const double *)src, lds, tmp,
@@ -82,11 +79,9 @@ static int download_f64(int dtype, double *dst, int64_t ldh, const void *src, in
     else
         hipLaunchKernelGGL((cvt_to_f64_2d<float>), grid, block, 0, st, (const float *)src, lds, tmp, cols,
                            rows, cols, lower_only);
-    hipError_t e = hipMemcpy2DAsync(dst, (size_t)ldh * 8, tmp, (size_t)cols * 8, (size_t)cols * 8,
-                                    (size_t)rows, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    (void)hipFree(tmp);
-    if (e != hipSuccess) return hip_fail(e, "download_f64", __FILE__, __LINE__);
+    GPX_HIP(hipMemcpy2DAsync(dst, (size_t)ldh * 8, tmp, (size_t)cols * 8, (size_t)cols * 8,
+                             (size_t)rows, hipMemcpyDeviceToHost, st));
+    GPX_HIP(hipStreamSynchronize(st));
     return GPX_OK;
 }
 
@@ -191,11 +186,7 @@ int gpx_gp_create(gpx_gp_t **out, int dtype, int kernel, int64_t n, int d)
     const size_t es = esize(dtype);
     int rc = GPX_OK;
     hipError_t e;
-#define GP_ALLOC(field, bytes)                                                        \
-    if (rc == GPX_OK) {                                                               \
-        e = hipMalloc((void **)&g->field, (bytes));                                   \
-        if (e != hipSuccess) rc = hip_fail(e, "hipMalloc " #field, __FILE__, __LINE__); \
-    }
+#define GP_ALLOC(field, bytes) if (rc == GPX_OK) rc = dev_alloc((void **)&g->field, (bytes), "hipMalloc " #field)
     GP_ALLOC(x, (size_t)n * d * es);
     GP_ALLOC(y, (size_t)n * es);
     GP_ALLOC(A, (size_t)(n + 1) * g->lda * es);          // (+ one row: the right-hand side rides along in the factorisation)
@@ -225,8 +216,8 @@ int gpx_gp_destroy(gpx_gp_t *g)
     stream_epoch_bump();                                       // (StreamTurn: a later stream at this one's address is a different stream)
     if (g->st_ops) { (void)hipStreamSynchronize(g->st_ops); (void)hipStreamDestroy(g->st_ops); }
     if (g->ev_ops) (void)hipEventDestroy(g->ev_ops);
-    void *bufs[] = {g->x, g->y, g->A, g->alpha, g->t0, g->t1, g->scal, g->bw, g->ops.buf, g->gw, g->bops.buf};
-    for (void *b : bufs) if (b) (void)hipFree(b);
+    for (void *b : {g->x, g->y, g->A, g->alpha, g->t0, g->t1, (void *)g->scal}) dev_free(b);    // gpx_gp_create's fixed-size fields
+    for (GrowBuf *b : {&g->bw, &g->gw, &g->ops.mem, &g->bops.mem}) b->release();
     for (int i = 0; i < 6; ++i) if (g->ev[i]) (void)hipEventDestroy(g->ev[i]);
     if (g->st) (void)hipStreamDestroy(g->st);
     delete g;
@@ -355,12 +346,7 @@ int gpx_gp_fit(gpx_gp_t *g, int *info)
             GPX_HIP(hipStreamCreateWithPriority(&g->st_ops, hipStreamNonBlocking, least));
             GPX_HIP(hipEventCreateWithFlags(&g->ev_ops, hipEventDisableTiming));
         }
-        const size_t need = trsv_ops_bytes(g->dtype, g->n);
-        if (!g->ops.buf || g->ops.bytes < need) {             // (here, not inside the factorisation's launch loop)
-            if (g->ops.buf) { GPX_HIP(hipStreamSynchronize(st)); (void)hipFree(g->ops.buf); g->ops.buf = nullptr; g->ops.bytes = 0; }
-            GPX_HIP(hipMalloc(&g->ops.buf, need));
-            g->ops.bytes = need;
-        }
+        GPX_TRY(g->ops.mem.reserve(trsv_ops_bytes(g->dtype, g->n), st));   // (here, not inside the factorisation's launch loop)
         // (the operator buffer may still be read by solves of the factor before this one, queued on st)
         GPX_HIP(hipEventRecord(g->ev_ops, st));
         GPX_HIP(hipStreamWaitEvent(g->st_ops, g->ev_ops, 0));
@@ -668,14 +654,10 @@ static int fit_batch_impl(gpx_gp_t *g, const double *thetas, int64_t B, double *
         size_t freeg = 0, totalg = 0;
         GPX_HIP(hipMemGetInfo(&freeg, &totalg));
         const size_t per_row = 2 * nl + (group_ok ? trsv_ops_bytes(g->dtype, g->n) : 0);
-        int G = group_ok ? (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(8, B), (int64_t)((double)(freeg + g->gw_bytes) / 6.0 / (double)per_row))) : 1;
-        if (g->gw_cap >= G && g->gw) G = g->gw_cap;
+        int G = group_ok ? (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(8, B), (int64_t)((double)(freeg + g->gw.bytes) / 6.0 / (double)per_row))) : 1;
+        if (g->gw_cap >= G && g->gw.p) G = g->gw_cap;
         const size_t gneed = (size_t)G * per_row + (size_t)(1024 * 4 + 8) * sizeof(double) + 256;
-        if (g->gw_bytes < gneed) {
-            if (g->gw) { GPX_HIP(hipStreamSynchronize(g->st)); (void)hipFree(g->gw); g->gw = nullptr; g->gw_bytes = 0; g->gw_cap = 0; }
-            GPX_HIP(hipMalloc(&g->gw, gneed));
-            g->gw_bytes = gneed;
-        }
+        GPX_TRY(g->gw.reserve(gneed, g->st));
         g->gw_cap = G;
     }
     if (!g->x_finite || !g->y_finite) { set_error("%s (%s)", NONFINITE_MSG, g->x_finite ? "y" : "x"); return GPX_ERR_ARG; }
@@ -690,20 +672,18 @@ static int fit_batch_impl(gpx_gp_t *g, const double *thetas, int64_t B, double *
     int64_t Bc = (int64_t)((double)freeb * 0.85 / (double)(per + 4 * (size_t)n * es + 64));
     if (tune().batch_max_set) Bc = std::min<int64_t>(Bc, std::max<int64_t>(1, tune().batch_max));
     Bc = std::max<int64_t>(1, std::min<int64_t>(Bc, B));
-    if (!g->bw && (double)per > (double)freeb * 0.85) { set_error("fit_batch: not even one more n x n matrix fits in HBM"); return GPX_ERR_NOMEM; }
+    if (!g->bw.p && (double)per > (double)freeb * 0.85) { set_error("fit_batch: not even one more n x n matrix fits in HBM"); return GPX_ERR_NOMEM; }
     // one block, kept in the handle between calls (an ML-II loop calls this once per sweep; a fresh
     // hipMalloc of tens of GB costs more than the factorisations)
     const size_t vec = ((size_t)n * es + 255) / 256 * 256;
-    if (g->bw && g->bw_cap >= Bc) Bc = std::min<int64_t>(g->bw_cap, B);
+    if (g->bw.p && g->bw_cap >= Bc) Bc = std::min<int64_t>(g->bw_cap, B);
     const size_t need = (size_t)Bc * (per + 3 * vec) + (size_t)Bc * 2 * sizeof(double) + (size_t)Bc * sizeof(int) + 1024;
-    if (g->bw_bytes < need) {
-        if (g->bw) { GPX_HIP(hipStreamSynchronize(g->st)); (void)hipFree(g->bw); g->bw = nullptr; g->bw_bytes = 0; g->bw_cap = 0; }
-        GPX_HIP(hipMalloc(&g->bw, need));
-        g->bw_bytes = need; g->bw_cap = Bc;
-    }
+    bool grew = false;
+    GPX_TRY(g->bw.reserve(need, g->st, &grew));
+    if (grew) g->bw_cap = Bc;
     struct Ptr { void *p; } Ab, t0, t1, al, sc, inf;
     {
-        char *w = (char *)g->bw;
+        char *w = (char *)g->bw.p;
         Ab.p = w; w += (size_t)Bc * per;
         t0.p = w; w += (size_t)Bc * vec;
         t1.p = w; w += (size_t)Bc * vec;
@@ -763,7 +743,7 @@ static int fit_batch_impl(gpx_gp_t *g, const double *thetas, int64_t B, double *
             // is not positive definite (gp/gp.py:424-428) or that the reference would have refused (ValueError).
             const size_t nl = (size_t)n * lda * es;
             const int G = (int)g->gw_cap;
-            char *Xs = (char *)g->gw, *Ws = Xs + (size_t)G * nl;
+            char *Xs = (char *)g->gw.p, *Ws = Xs + (size_t)G * nl;
             const size_t obytes = G > 1 ? trsv_ops_bytes(g->dtype, n) : 0;
             char *Os = Ws + (size_t)G * nl;
             double *part = (double *)(((uintptr_t)(Os + (size_t)G * obytes) + 255) / 256 * 256);
@@ -782,7 +762,7 @@ static int fit_batch_impl(gpx_gp_t *g, const double *thetas, int64_t B, double *
                         else hipLaunchKernelGGL((eye_kernel<float>), grid, block, 0, st, (float *)(Xs + (size_t)i * nl), n, lda);
                         GPX_LAUNCH_CHECK();
                         TrsvOps o;                                   // (a view into the group's operator block: not owned, not freed)
-                        o.buf = Os + (size_t)i * obytes; o.bytes = obytes;
+                        o.mem.p = Os + (size_t)i * obytes; o.mem.bytes = obytes;
                         GPX_TRY(trsv_ops_build_upto(g->dtype, L0 + (size_t)i * per, n, lda, &o, n / 512, st));
                     }
                     GPX_HIP(hipMemsetAsync(Ws, 0, (size_t)gc * nl, st));
@@ -932,7 +912,7 @@ int gpx_gemm_nt_host(double *C, const double *A, const double *B, int64_t M, int
 int gpx_cholesky(double *L, const double *A, int64_t n, int *info)
 {
     GPX_TRY(ensure_device());
-    gpx::StreamTurn turn__(nullptr);                           // (this thread's scratch buffers: one stream at a time, gpx_common.h)
+    gpx::StreamTurn turn__(nullptr);                           // (this thread's scratch buffers: one stream at a time, gpx_mem.h)
     GPX_ARG(n >= 0 && info, "bad arguments");
     *info = 0;
     if (n == 0) return GPX_OK;
@@ -953,7 +933,7 @@ int gpx_cholesky(double *L, const double *A, int64_t n, int *info)
 int gpx_cho_solve(const double *L, int64_t n, double *b)
 {
     GPX_TRY(ensure_device());
-    gpx::StreamTurn turn__(nullptr);                           // (this thread's scratch buffers: one stream at a time, gpx_common.h)
+    gpx::StreamTurn turn__(nullptr);                           // (this thread's scratch buffers: one stream at a time, gpx_mem.h)
     GPX_ARG(n >= 0, "n < 0");
     if (n == 0) return GPX_OK;
     GPX_ARG(L && b, "NULL pointer");

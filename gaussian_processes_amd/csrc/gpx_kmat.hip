@@ -399,22 +399,7 @@ __global__ void mean_reduce_kernel(const double *__restrict__ partial, int nslic
     out[i] = (T)sum;
 }
 
-// grow-only device scratch for the slice partial sums (one per host thread)
-struct MeanScratch { void *p = nullptr; size_t bytes = 0; int device = -1; };
-static thread_local MeanScratch g_mean_scr;
-static int mean_scratch(size_t bytes, void **out)
-{
-    int dev = 0;
-    GPX_HIP(hipGetDevice(&dev));
-    if (g_mean_scr.device != dev || g_mean_scr.bytes < bytes) {
-        if (g_mean_scr.p && g_mean_scr.device == dev) { GPX_HIP(hipDeviceSynchronize()); (void)hipFree(g_mean_scr.p); }
-        g_mean_scr.p = nullptr; g_mean_scr.bytes = 0; g_mean_scr.device = dev;
-        GPX_HIP(hipMalloc(&g_mean_scr.p, bytes));
-        g_mean_scr.bytes = bytes;
-    }
-    *out = g_mean_scr.p;
-    return GPX_OK;
-}
+static thread_local ThreadScratch g_mean_scr;   // the slice partial sums
 
 template <typename T>
 static int launch_mean(int kernel, const void *xo, int64_t m, const void *x, int64_t n, int d,
@@ -433,7 +418,7 @@ static int launch_mean(int kernel, const void *xo, int64_t m, const void *x, int
     double *partial = nullptr;
     if (nslice > 1) {
         void *scr = nullptr;
-        GPX_TRY(mean_scratch((size_t)nslice * m * sizeof(double), &scr));
+        GPX_TRY(g_mean_scr.get((size_t)nslice * m * sizeof(double), &scr));
         partial = (double *)scr;
     }
     dim3 grid((unsigned)gx, (unsigned)nslice), block(256);
@@ -634,7 +619,7 @@ int gpx_d_kmat(int dtype, int kernel, int member, const void *x1, int64_t n, con
 int gpx_d_mean_member(int dtype, int kernel, int member, const void *xo, int64_t m, const void *x,
                       int64_t n, int d, const double *params, const void *alpha, void *out, void *stream)
 {
-    gpx::StreamTurn turn__((hipStream_t)stream);     // (this thread's scratch buffers: one stream at a time, gpx_common.h)
+    gpx::StreamTurn turn__((hipStream_t)stream);     // (this thread's scratch buffers: one stream at a time, gpx_mem.h)
     GPX_TRY(ensure_device());
     GPX_ARG(dtype == GPX_F64 || dtype == GPX_F32, "dtype must be GPX_F64 or GPX_F32");
     GPX_ARG(n >= 0 && m >= 0 && d >= 1, "need n, m >= 0 and d >= 1");
@@ -649,7 +634,7 @@ int gpx_d_mean_member(int dtype, int kernel, int member, const void *xo, int64_t
 int gpx_d_mean(int dtype, int kernel, const void *xo, int64_t m, const void *x, int64_t n, int d,
                const double *params, const void *alpha, void *out, void *stream)
 {
-    gpx::StreamTurn turn__((hipStream_t)stream);     // (this thread's scratch buffers: one stream at a time, gpx_common.h)
+    gpx::StreamTurn turn__((hipStream_t)stream);     // (this thread's scratch buffers: one stream at a time, gpx_mem.h)
     return gpx_d_mean_member(dtype, kernel, GPX_K, xo, m, x, n, d, params, alpha, out, stream);
 }
 

@@ -23,7 +23,6 @@
 // (gpx_mg_create_cb): the same C schedule over any transport -- the tests run it with several ranks on
 // ONE GPU over gloo, which RCCL cannot do.
 #include "gpx_common.h"
-#include "gpx_gp_internal.h"   // DevBuf
 #include <dlfcn.h>
 #include <climits>
 #include <cmath>
@@ -196,7 +195,7 @@ struct gpx_mg {
     int owner_first = 0;                          // the owner of the next panel factors it BEFORE it starts its own trailing update
                                                   // (gpx_mg_set_owner_first / GPX_MG_OWNER_FIRST; see mg_factor)
     hipEvent_t last_panel_ev = nullptr;           // behind the last panel this rank factored (stream Q)
-    void *sag_tmp = nullptr; size_t sag_tmp_bytes = 0;   // callback back-end only: where a rank drops pieces that are not its own
+    gpx::GrowBuf sag_tmp;                          // callback back-end only: where a rank drops pieces that are not its own
     int debug_info = 0;                           // gpx_debug_mg_inject_info: written into the device info word after the factorisation
     // device state
     void *A = nullptr, *pbuf[2] = {nullptr, nullptr}, *x = nullptr, *y = nullptr, *alpha = nullptr, *tmp = nullptr;
@@ -406,16 +405,10 @@ static int mg_bcast_panel(gpx_mg *g, void *dev_ptr, size_t count, int root, hipS
     auto at = [&](int i) { return (char *)dev_ptr + off(i) * g->es; };
     if (g->cb_bcast) {
         const size_t need = (count - off(P - 1)) * g->es;
-        if (g->sag_tmp_bytes < need) {
-            GPX_HIP(hipStreamSynchronize(st));
-            if (g->sag_tmp) (void)hipFree(g->sag_tmp);
-            g->sag_tmp = nullptr; g->sag_tmp_bytes = 0;
-            GPX_HIP(hipMalloc(&g->sag_tmp, need));
-            g->sag_tmp_bytes = need;
-        }
+        GPX_TRY(g->sag_tmp.reserve(need, st));
         for (int i = 0; i < P; ++i) {                             // phase 1: root -> rank i
             if (i == root) continue;
-            void *dst = (me == root || me == i) ? (void *)at(i) : g->sag_tmp;
+            void *dst = (me == root || me == i) ? (void *)at(i) : g->sag_tmp.p;
             const int rc = g->cb_bcast(g->cb_user, dst, len(i) * g->es, root, (void *)st);
             if (rc != 0) { set_error("broadcast callback failed (%d)", rc); return GPX_ERR_HIP; }
         }
@@ -680,7 +673,7 @@ static int mg_alloc(gpx_mg *g)
 {
     const size_t es = g->es;
     const int64_t n = g->n;
-#define MG_ALLOC(field, bytes) GPX_HIP(hipMalloc((void **)&g->field, (bytes) ? (bytes) : 16))
+#define MG_ALLOC(field, bytes) GPX_TRY(dev_alloc((void **)&g->field, (bytes) ? (bytes) : 16))
     MG_ALLOC(A, (size_t)g->nr * g->ld * es);
     MG_ALLOC(pbuf[0], (size_t)g->nr * g->nb * es);
     MG_ALLOC(pbuf[1], (size_t)g->nr * g->nb * es);
@@ -703,9 +696,7 @@ static int mg_alloc(gpx_mg *g)
     for (size_t jl = 0; jl < g->my_blocks.size(); ++jl) {
         const int64_t kb = g->kb(g->my_blocks[jl]);
         if (kb < 512 || kb % 512 != 0) continue;                  // (the step route: trsv_ops_build declines these)
-        const size_t need = trsv_ops_bytes(g->dtype, kb);
-        GPX_HIP(hipMalloc(&g->ops[jl].buf, need));
-        g->ops[jl].bytes = need;
+        GPX_TRY(g->ops[jl].mem.reserve(trsv_ops_bytes(g->dtype, kb), g->O));
     }
     return GPX_OK;
 }
@@ -853,12 +844,57 @@ static int mg_cov_run(gpx_mg *g, const double *params, const void *dxo, int64_t 
 
 }  // namespace gpx
 
+// The caller's host arrays are double whatever the handle's dtype; an fp32 handle rounds ON THE HOST (the single-GPU
+// handle converts on the device, gpx_gp.hip).  Both are synchronous.
+// `count` contiguous values, host -> device
+static int mg_upload(const gpx_mg *g, void *dst, const double *src, size_t count)
+{
+    if (g->dtype == GPX_F64) {
+        GPX_HIP(hipMemcpy(dst, src, count * 8, hipMemcpyHostToDevice));
+        return GPX_OK;
+    }
+    std::vector<float> h(src, src + count);
+    GPX_HIP(hipMemcpy(dst, h.data(), count * 4, hipMemcpyHostToDevice));
+    return GPX_OK;
+}
+
+// rows x cols, device (leading dimension lds) -> host (leading dimension ldh), behind the work queued on S
+static int mg_download(const gpx_mg *g, double *dst, int64_t ldh, const void *src, int64_t lds, int64_t rows, int64_t cols)
+{
+    if (g->dtype == GPX_F64) {
+        GPX_HIP(hipMemcpy2DAsync(dst, (size_t)ldh * 8, src, (size_t)lds * 8, (size_t)cols * 8, (size_t)rows, hipMemcpyDeviceToHost, g->S));
+        GPX_HIP(hipStreamSynchronize(g->S));
+        return GPX_OK;
+    }
+    std::vector<float> h((size_t)rows * lds);
+    GPX_HIP(hipMemcpyAsync(h.data(), src, h.size() * 4, hipMemcpyDeviceToHost, g->S));
+    GPX_HIP(hipStreamSynchronize(g->S));
+    for (int64_t i = 0; i < rows; ++i)
+        for (int64_t k = 0; k < cols; ++k) dst[i * ldh + k] = (double)h[(size_t)(i * lds + k)];
+    return GPX_OK;
+}
+
+static int mg_mean_run(gpx_mg *g, const double *params, const double *xo, int64_t m, double *out, void *dxo, void *dout)
+{
+    const size_t es = g->es;
+    GPX_TRY(mg_upload(g, dxo, xo, (size_t)m * g->d));
+    // every rank evaluates a slice of the test points, one all-reduce assembles the vector
+    const int64_t per = cdiv(m, g->world);
+    const int64_t m0 = std::min(m, g->rank * per), m1 = std::min(m, (g->rank + 1) * per);
+    GPX_HIP(hipMemsetAsync(dout, 0, (size_t)m * es, g->S));
+    if (m1 > m0)
+        GPX_TRY(gpx_d_mean(g->dtype, g->kernel, (char *)dxo + (size_t)m0 * g->d * es, m1 - m0, g->x, g->n, g->d, params, g->alpha,
+                           (char *)dout + (size_t)m0 * es, (void *)g->S));
+    GPX_TRY(mg_allreduce(g, dout, (size_t)m, g->dtype, 0, g->S));
+    return mg_download(g, out, m, dout, m, 1, m);
+}
+
 #define MG_ENTER(g)                                                          \
     GPX_ARG((g) != nullptr, "mg is NULL");                                   \
     gpx::tune_refresh();                                                     \
     gpx::DeviceGuard guard__((g)->device);                                   \
     if (guard__.rc != GPX_OK) return guard__.rc;                             \
-    gpx::StreamTurn turn__((g)->S)      /* this thread's scratch buffers: one stream at a time (gpx_common.h) */
+    gpx::StreamTurn turn__((g)->S)      /* this thread's scratch buffers: one stream at a time (gpx_mem.h) */
 
 extern "C" {
 
@@ -882,9 +918,9 @@ int gpx_mg_destroy(gpx_mg_t *g)
     if (g->B) (void)hipStreamSynchronize(g->B);
     if (g->O) (void)hipStreamSynchronize(g->O);
     if (g->comm && g_rccl.CommDestroy) (void)g_rccl.CommDestroy(g->comm);
-    void *bufs[] = {g->A, g->pbuf[0], g->pbuf[1], g->x, g->y, g->alpha, g->tmp, g->scal, g->info, g->sag_tmp};
-    for (void *b : bufs) if (b) (void)hipFree(b);
-    for (gpx::TrsvOps &o : g->ops) if (o.buf) (void)hipFree(o.buf);
+    for (void *b : {g->A, g->pbuf[0], g->pbuf[1], g->x, g->y, g->alpha, g->tmp, (void *)g->scal, (void *)g->info}) dev_free(b);   // mg_alloc's
+    g->sag_tmp.release();
+    for (gpx::TrsvOps &o : g->ops) o.mem.release();
     for (hipEvent_t e : g->ev) (void)hipEventDestroy(e);
     for (hipEvent_t e : g->tev) (void)hipEventDestroy(e);
     stream_epoch_bump();
@@ -1075,16 +1111,8 @@ int gpx_mg_set_data(gpx_mg_t *g, const double *x, const double *y)
         if (!std::isfinite(x[i])) { set_error("array must not contain infs or NaNs (x)"); return GPX_ERR_ARG; }
     for (int64_t i = 0; i < n; ++i)
         if (!std::isfinite(y[i])) { set_error("array must not contain infs or NaNs (y)"); return GPX_ERR_ARG; }
-    if (g->dtype == GPX_F64) {
-        GPX_HIP(hipMemcpy(g->x, x, (size_t)n * g->d * 8, hipMemcpyHostToDevice));
-        GPX_HIP(hipMemcpy(g->y, y, (size_t)n * 8, hipMemcpyHostToDevice));
-    } else {
-        std::vector<float> hx((size_t)n * g->d), hy((size_t)n);
-        for (size_t i = 0; i < hx.size(); ++i) hx[i] = (float)x[i];
-        for (size_t i = 0; i < hy.size(); ++i) hy[i] = (float)y[i];
-        GPX_HIP(hipMemcpy(g->x, hx.data(), hx.size() * 4, hipMemcpyHostToDevice));
-        GPX_HIP(hipMemcpy(g->y, hy.data(), hy.size() * 4, hipMemcpyHostToDevice));
-    }
+    GPX_TRY(mg_upload(g, g->x, x, (size_t)n * g->d));
+    GPX_TRY(mg_upload(g, g->y, y, (size_t)n));
     g->have_data = true; g->fitted = false;
     return GPX_OK;
 }
@@ -1137,39 +1165,11 @@ int gpx_mg_mean(gpx_mg_t *g, const double *params, const double *xo, int64_t m, 
     GPX_ARG(g->fitted && params, "mg is not fitted");
     GPX_ARG(m >= 0 && (m == 0 || (xo && out)), "bad arguments");
     if (m == 0) return GPX_OK;
-    const size_t es = g->es;
-    void *dxo = nullptr, *dout = nullptr;
-    GPX_HIP(hipMalloc(&dxo, (size_t)m * g->d * es));
-    hipError_t e = hipMalloc(&dout, (size_t)m * es);
-    if (e != hipSuccess) { (void)hipFree(dxo); return hip_fail(e, "hipMalloc", __FILE__, __LINE__); }
-    int rc = GPX_OK;
-    {
-        if (g->dtype == GPX_F64) e = hipMemcpy(dxo, xo, (size_t)m * g->d * 8, hipMemcpyHostToDevice);
-        else {
-            std::vector<float> h((size_t)m * g->d);
-            for (size_t i = 0; i < h.size(); ++i) h[i] = (float)xo[i];
-            e = hipMemcpy(dxo, h.data(), h.size() * 4, hipMemcpyHostToDevice);
-        }
-        if (e != hipSuccess) rc = hip_fail(e, "hipMemcpy", __FILE__, __LINE__);
-    }
-    // every rank evaluates a slice of the test points, one all-reduce assembles the vector
-    const int64_t per = cdiv(m, g->world);
-    const int64_t m0 = std::min(m, g->rank * per), m1 = std::min(m, (g->rank + 1) * per);
-    if (rc == GPX_OK && hipMemsetAsync(dout, 0, (size_t)m * es, g->S) != hipSuccess) rc = GPX_ERR_HIP;
-    if (rc == GPX_OK && m1 > m0)
-        rc = gpx_d_mean(g->dtype, g->kernel, (char *)dxo + (size_t)m0 * g->d * es, m1 - m0, g->x, g->n, g->d, params, g->alpha,
-                        (char *)dout + (size_t)m0 * es, (void *)g->S);
-    if (rc == GPX_OK) rc = mg_allreduce(g, dout, (size_t)m, g->dtype, 0, g->S);
-    if (rc == GPX_OK) {
-        if (g->dtype == GPX_F64) e = hipMemcpyAsync(out, dout, (size_t)m * 8, hipMemcpyDeviceToHost, g->S);
-        std::vector<float> h;
-        if (g->dtype != GPX_F64) { h.resize((size_t)m); e = hipMemcpyAsync(h.data(), dout, (size_t)m * 4, hipMemcpyDeviceToHost, g->S); }
-        if (e == hipSuccess) e = hipStreamSynchronize(g->S);
-        if (e != hipSuccess) rc = hip_fail(e, "mean copy-out", __FILE__, __LINE__);
-        else if (g->dtype != GPX_F64) for (int64_t i = 0; i < m; ++i) out[i] = (double)h[(size_t)i];
-    }
-    (void)hipStreamSynchronize(g->S);
-    (void)hipFree(dxo); (void)hipFree(dout);
+    DevBuf dxo, dout;
+    GPX_TRY(dxo.alloc((size_t)m * g->d * g->es));
+    GPX_TRY(dout.alloc((size_t)m * g->es));
+    const int rc = mg_mean_run(g, params, xo, m, out, dxo.p, dout.p);
+    (void)hipStreamSynchronize(g->S);                             // (idle before the two buffers are freed, whatever happened)
     return rc;
 }
 
@@ -1205,39 +1205,16 @@ int gpx_mg_cov(gpx_mg_t *g, const double *params, const double *xo, int64_t m, d
         ~Drain() { for (hipStream_t st : {g->S, g->Q, g->B, g->O}) (void)hipStreamSynchronize(st); }
     } drain{g};
     g->ev_next = 0;                                               // (the fit drained every stream: its events are free)
-    if (g->dtype == GPX_F64) {
-        GPX_HIP(hipMemcpy(dxo.p, xo, (size_t)m * g->d * 8, hipMemcpyHostToDevice));
-    } else {
-        std::vector<float> h((size_t)m * g->d);
-        for (size_t i = 0; i < h.size(); ++i) h[i] = (float)xo[i];
-        GPX_HIP(hipMemcpy(dxo.p, h.data(), h.size() * 4, hipMemcpyHostToDevice));
-    }
+    GPX_TRY(mg_upload(g, dxo.p, xo, (size_t)m * g->d));
     GPX_TRY(mg_cov_run(g, params, dxo.p, m, (char *)Bm.p, C.p, ldc));
-    if (g->dtype == GPX_F64) {
-        GPX_HIP(hipMemcpy2DAsync(out, (size_t)m * 8, C.p, (size_t)ldc * 8, (size_t)m * 8, (size_t)m, hipMemcpyDeviceToHost, g->S));
-        GPX_HIP(hipStreamSynchronize(g->S));
-    } else {
-        std::vector<float> h((size_t)m * ldc);
-        GPX_HIP(hipMemcpyAsync(h.data(), C.p, h.size() * 4, hipMemcpyDeviceToHost, g->S));
-        GPX_HIP(hipStreamSynchronize(g->S));
-        for (int64_t i = 0; i < m; ++i)
-            for (int64_t k = 0; k < m; ++k) out[i * m + k] = (double)h[(size_t)(i * ldc + k)];
-    }
-    return GPX_OK;
+    return mg_download(g, out, m, C.p, ldc, m, m);
 }
 
 int gpx_mg_get_alpha(gpx_mg_t *g, double *out)
 {
     MG_ENTER(g);
     GPX_ARG(g->fitted && out, "bad arguments");
-    if (g->dtype == GPX_F64) {
-        GPX_HIP(hipMemcpy(out, g->alpha, (size_t)g->n * 8, hipMemcpyDeviceToHost));
-    } else {
-        std::vector<float> h((size_t)g->n);
-        GPX_HIP(hipMemcpy(h.data(), g->alpha, h.size() * 4, hipMemcpyDeviceToHost));
-        for (int64_t i = 0; i < g->n; ++i) out[i] = (double)h[(size_t)i];
-    }
-    return GPX_OK;
+    return mg_download(g, out, g->n, g->alpha, g->n, 1, g->n);
 }
 
 int gpx_mg_scalars(gpx_mg_t *g, double *logdet, double *yta, int *info)

@@ -568,31 +568,27 @@ static int g_res_stamp_at = -1;
 // the caller's stream, gpx_d_potrf_panel on any stream, the multi-GPU schedule's panel stream, an asynchronous
 // gpx_gp_fit followed by another handle's) the new launch waits for the previous one through `ev`.
 struct ResScratch {
-    void *p = nullptr; size_t bytes = 0; int nbatch = 0; int serial = 0;
+    GrowBuf mem; int nbatch = 0; int serial = 0;
     hipEvent_t ev = nullptr;        // after the last launch that was NOT on the look-ahead stream / recorded on demand on it
     hipStream_t last = nullptr; bool have_last = false, last_on_side = false;
 };
-constexpr int RES_MAXDEV = 16;
-static thread_local ResScratch g_res_dev[RES_MAXDEV];       // one per device: a thread that alternates between GPUs keeps both
+static thread_local PerDevice<ResScratch> g_res_dev;
 #define RES_TRACE(...) do { if (tune().trace) { fprintf(stderr, "[gpx] " __VA_ARGS__); fputc('\n', stderr); fflush(stderr); } } while (0)
 static int res_scratch(int nbatch, size_t es, void **pub, int **flags, ResScratch **out)
 {
-    int dev = 0;
-    GPX_HIP(hipGetDevice(&dev));
-    if (dev < 0 || dev >= RES_MAXDEV) { set_error("resident panel: device index %d out of range", dev); return GPX_ERR_ARG; }
-    ResScratch &g = g_res_dev[dev];
+    ResScratch *cur = nullptr;
+    GPX_TRY(g_res_dev.current(&cur));
+    ResScratch &g = *cur;
     if (g.nbatch < nbatch) {
-        RES_TRACE("res_scratch: grow %d -> %d matrices (device %d, old %p)", g.nbatch, nbatch, dev, g.p);
-        if (g.p) { GPX_HIP(hipDeviceSynchronize()); (void)hipFree(g.p); }
-        g.p = nullptr; g.bytes = 0; g.nbatch = 0;
+        RES_TRACE("res_scratch: grow %d -> %d matrices (old %p)", g.nbatch, nbatch, g.mem.p);
+        g.nbatch = 0;
         const size_t fbytes = ((size_t)nbatch * RES_FLAGS * sizeof(int) + 255) / 256 * 256;
         const size_t region = (size_t)nbatch * RES_SLOTS * IB * IB * 8;
         const size_t need = fbytes + region + region / 2;
-        GPX_HIP(hipMalloc(&g.p, need));
-        GPX_HIP(hipMemset(g.p, 0, need));
+        GPX_TRY(g.mem.reserve_device(need));
+        GPX_HIP(hipMemset(g.mem.p, 0, need));
         GPX_HIP(hipDeviceSynchronize());
-        RES_TRACE("res_scratch: new block %p, %zu bytes, cleared", g.p, need);
-        g.bytes = need;
+        RES_TRACE("res_scratch: new block %p, %zu bytes, cleared", g.mem.p, need);
         g.nbatch = nbatch;
         g.serial = 0;
     }
@@ -605,12 +601,12 @@ static int res_scratch(int nbatch, size_t es, void **pub, int **flags, ResScratc
         // the flags hold the serial of the launch that raised them; long before the counter could wrap, start over
         // (everything that used the block has to be done first)
         GPX_HIP(hipDeviceSynchronize());
-        GPX_HIP(hipMemset(g.p, 0, fbytes));
+        GPX_HIP(hipMemset(g.mem.p, 0, fbytes));
         GPX_HIP(hipDeviceSynchronize());
         g.serial = 0;
     }
-    *flags = (int *)g.p;
-    *pub = (char *)g.p + fbytes + (es == 8 ? 0 : region);
+    *flags = (int *)g.mem.p;
+    *pub = (char *)g.mem.p + fbytes + (es == 8 ? 0 : region);
     *out = &g;
     return GPX_OK;
 }
@@ -632,8 +628,8 @@ int64_t panel_res_max()
 // the process and says so on stderr (gpx_debug_leaf_selfcheck: 1 passed, 2 failed -> fallback, 0 not run yet).
 static thread_local int g_leaf_force = 0;                      // the self-check's own launches: 1 / 4 / 5, no check
 static std::mutex g_leaf_mu;
-static int g_leaf_state[RES_MAXDEV] = {};                      // 0 unknown, 1 ok, 2 failed, 3 never verified (guarded by g_leaf_mu)
-static int g_leaf_tries[RES_MAXDEV] = {};                      // attempts that could not run (guarded by g_leaf_mu)
+static int g_leaf_state[MAX_DEVICES] = {};                      // 0 unknown, 1 ok, 2 failed, 3 never verified (guarded by g_leaf_mu)
+static int g_leaf_tries[MAX_DEVICES] = {};                      // attempts that could not run (guarded by g_leaf_mu)
 constexpr int LEAF_CHECK_TRIES = 3;
 static int leaf_selfcheck_run(int dev, hipStream_t st);
 // true: the asm-scheduled leaf may be used on the current device.  While the check has not PASSED the compiler-scheduled
@@ -645,7 +641,7 @@ static bool leaf_asm_ok(hipStream_t st = nullptr)
 {
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); return false; }
-    if (dev < 0 || dev >= RES_MAXDEV) return false;
+    if (dev < 0 || dev >= MAX_DEVICES) return false;
     std::lock_guard<std::mutex> lk(g_leaf_mu);
     if (g_leaf_state[dev] == 0) {
         ++g_prof_mute;
@@ -824,20 +820,20 @@ static int leaf_selfcheck_run(int dev, hipStream_t st)
             hA[i * LD + j] = hA[j * LD + i] = acc / 8.0 + (i == j ? 2.0 : 0.0);
         }
     std::vector<float> hAf(hA.begin(), hA.end());
-    void *dA = nullptr, *dG = nullptr, *dC = nullptr; int *dinfo = nullptr;
+    DevBuf bA, bG, bC, binfo;                                     // (freed on every exit, after `cleanup` has drained the streams)
     hipStream_t s1 = nullptr, s2 = nullptr;
     int verdict = 0;
     auto cleanup = [&]() {
         stream_epoch_bump();
         if (s1) { (void)hipStreamSynchronize(s1); (void)hipStreamDestroy(s1); }
         if (s2) { (void)hipStreamSynchronize(s2); (void)hipStreamDestroy(s2); }
-        (void)hipFree(dA); (void)hipFree(dG); (void)hipFree(dC); (void)hipFree(dinfo);
     };
-#define GPX_SC(call) do { if ((call) != hipSuccess) { (void)hipGetLastError(); cleanup(); return 0; } } while (0)
-    GPX_SC(hipMalloc(&dA, (size_t)N * LD * 8));
-    GPX_SC(hipMalloc(&dG, (size_t)GM * GK * 8));
-    GPX_SC(hipMalloc(&dC, (size_t)GM * GM * 8));
-    GPX_SC(hipMalloc((void **)&dinfo, sizeof(int)));
+#define GPX_SC(call) do { if ((call) != 0) { (void)hipGetLastError(); cleanup(); return 0; } } while (0)
+    GPX_SC(bA.alloc((size_t)N * LD * 8));                        // (GPX_OK == hipSuccess == 0)
+    GPX_SC(bG.alloc((size_t)GM * GK * 8));
+    GPX_SC(bC.alloc((size_t)GM * GM * 8));
+    GPX_SC(binfo.alloc(sizeof(int)));
+    void *const dA = bA.p, *const dG = bG.p, *const dC = bC.p; int *const dinfo = (int *)binfo.p;
     GPX_SC(hipMemset(dG, 0, (size_t)GM * GK * 8));
     GPX_SC(hipMemset(dC, 0, (size_t)GM * GM * 8));
     GPX_SC(hipStreamCreateWithFlags(&s1, hipStreamNonBlocking));
@@ -913,7 +909,7 @@ extern "C" int gpx_debug_leaf_selfcheck(int run_now, int *state)
     int dev = 0;
     GPX_HIP(hipGetDevice(&dev));
     std::lock_guard<std::mutex> lk(gpx::g_leaf_mu);
-    *state = (dev >= 0 && dev < gpx::RES_MAXDEV) ? gpx::g_leaf_state[dev] : 0;
+    *state = (dev >= 0 && dev < gpx::MAX_DEVICES) ? gpx::g_leaf_state[dev] : 0;
     return GPX_OK;
 }
 

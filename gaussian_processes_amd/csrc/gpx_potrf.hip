@@ -206,26 +206,9 @@ static int64_t outer_block(int64_t n, bool batched = false)
     return 1024;
 }
 
-// one 64 x 64 scratch block per host thread and device for the leaf's inverse (leaves of a
-// panel are stream-ordered, so one block is enough)
-struct LeafScratch { void *p = nullptr; size_t bytes = 0; int device = -1; };
-static thread_local LeafScratch g_leaf;
-static int leaf_scratch(size_t bytes, void **out)
-{
-    int dev = 0;
-    GPX_HIP(hipGetDevice(&dev));
-    if (g_leaf.device != dev || g_leaf.bytes < bytes) {
-        // growing on the same device: the old block may still be in use by queued leaves (a previous device's
-        // block is left to that context)
-        if (g_leaf.p && g_leaf.device == dev) { GPX_HIP(hipDeviceSynchronize()); (void)hipFree(g_leaf.p); }
-        g_leaf.p = nullptr;
-        GPX_HIP(hipMalloc(&g_leaf.p, std::max<size_t>(bytes, IB * IB * 8)));
-        g_leaf.bytes = std::max<size_t>(bytes, IB * IB * 8);
-        g_leaf.device = dev;
-    }
-    *out = g_leaf.p;
-    return GPX_OK;
-}
+// one 64 x 64 scratch block per matrix of a batch for the leaf's inverse (leaves of a panel are stream-ordered, so one
+// block is enough); never smaller than one fp64 block
+static thread_local ThreadScratch g_leaf;
 
 // ---- panel: rows [r0, n) x columns [c0, c0 + kb), diagonal block at (r0, c0) ----
 // Panels of up to 256 columns (a multiple of 64) are ONE launch of the resident panel kernel (gpx_panel.hip).
@@ -261,7 +244,7 @@ static int potrf_panel_t(T *A, int64_t lda, int64_t n, int64_t r0, int64_t c0, i
         T *inv = nullptr;
         if (via_inverse) {
             void *p = nullptr;
-            GPX_TRY(leaf_scratch((size_t)nbatch * IB * IB * sizeof(T), &p));
+            GPX_TRY(g_leaf.get(std::max<size_t>((size_t)nbatch * IB * IB * sizeof(T), IB * IB * 8), &p));
             inv = (T *)p;
         }
         {
@@ -554,7 +537,7 @@ extern "C" {
 
 int gpx_d_potrf(int dtype, void *A, int64_t n, int64_t lda, int *info_dev, void *stream)
 {
-    gpx::StreamTurn turn__((hipStream_t)stream);     // (this thread's scratch buffers: one stream at a time, gpx_common.h)
+    gpx::StreamTurn turn__((hipStream_t)stream);     // (this thread's scratch buffers: one stream at a time, gpx_mem.h)
     GPX_TRY(ensure_device());
     GPX_ARG(dtype == GPX_F64 || dtype == GPX_F32, "dtype must be GPX_F64 or GPX_F32");
     GPX_ARG(n >= 0, "n < 0");
@@ -582,7 +565,7 @@ int gpx_d_tril(int dtype, void *A, int64_t n, int64_t lda, void *stream)
 extern "C" int gpx_d_potrf_panel(int dtype, void *A, int64_t lda, int64_t n, int64_t r0, int64_t c0,
                                  int64_t kb, int *info_dev, void *stream)
 {
-    gpx::StreamTurn turn__((hipStream_t)stream);     // (this thread's scratch buffers: one stream at a time, gpx_common.h)
+    gpx::StreamTurn turn__((hipStream_t)stream);     // (this thread's scratch buffers: one stream at a time, gpx_mem.h)
     GPX_TRY(ensure_device());
     GPX_ARG(dtype == GPX_F64 || dtype == GPX_F32, "dtype must be GPX_F64 or GPX_F32");
     GPX_ARG(n >= 0 && r0 >= 0 && c0 >= 0 && kb >= 0 && r0 + kb <= n, "bad dimensions");

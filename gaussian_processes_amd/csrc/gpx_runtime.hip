@@ -231,7 +231,7 @@ extern "C" int gpx_debug_roctx_ranges(int64_t *count)
     return GPX_OK;
 }
 
-// ---- StreamTurn (gpx_common.h): one turn at a time for the streams a host thread drives ----
+// ---- StreamTurn (gpx_mem.h): one turn at a time for the streams a host thread drives ----
 namespace gpx {
 // `last` is compared together with the stream EPOCH at which it was recorded: the library bumps the epoch whenever it
 // destroys a stream (gpx_stream_destroy, a handle's own streams), so a new stream that happens to get a destroyed one's

@@ -62,22 +62,7 @@ __global__ __launch_bounds__(256) void inv64_kernel(const T *__restrict__ L, int
         }
 }
 
-// grow-only device scratch for the block inverses (one per host thread)
-struct SolveScratch { void *p = nullptr; size_t bytes = 0; int device = -1; };
-static thread_local SolveScratch g_scr;
-static int scratch(size_t bytes, void **out)
-{
-    int dev = 0;
-    GPX_HIP(hipGetDevice(&dev));
-    if (g_scr.device != dev || g_scr.bytes < bytes) {
-        if (g_scr.p && g_scr.device == dev) { GPX_HIP(hipDeviceSynchronize()); (void)hipFree(g_scr.p); }
-        g_scr.p = nullptr; g_scr.bytes = 0; g_scr.device = dev;
-        GPX_HIP(hipMalloc(&g_scr.p, bytes));
-        g_scr.bytes = bytes;
-    }
-    *out = g_scr.p;
-    return GPX_OK;
-}
+static thread_local ThreadScratch g_scr;        // the block inverses
 
 // ---- fused block steps of the single-right-hand-side solves ----------------
 // The solve advances in blocks of TB = 512 columns, ONE launch per block (the chain
@@ -532,22 +517,7 @@ __global__ __launch_bounds__(TBT) void trsv_op_kernel(const T *__restrict__ Wk, 
     if (part == 0) x[k0 + row] = acc;
 }
 
-// thread-local, grow-only home of the operators when the caller brings no cache of its own
-struct OpsScratch { void *p = nullptr; size_t bytes = 0; int device = -1; };
-static thread_local OpsScratch g_ops;
-static int ops_scratch(size_t bytes, void **out)
-{
-    int dev = 0;
-    GPX_HIP(hipGetDevice(&dev));
-    if (g_ops.device != dev || g_ops.bytes < bytes) {
-        if (g_ops.p && g_ops.device == dev) { GPX_HIP(hipDeviceSynchronize()); (void)hipFree(g_ops.p); }
-        g_ops.p = nullptr; g_ops.bytes = 0; g_ops.device = dev;
-        GPX_HIP(hipMalloc(&g_ops.p, bytes));
-        g_ops.bytes = bytes;
-    }
-    *out = g_ops.p;
-    return GPX_OK;
-}
+static thread_local ThreadScratch g_ops;        // home of the operators when the caller brings no cache of its own
 
 size_t trsv_ops_bytes(int dtype, int64_t n)
 {
@@ -642,18 +612,18 @@ static int trsv_t(const T *L, int64_t n, int64_t ldl, T *b, T *x, int transpose,
     const int64_t nblk = cdiv(ncols, SB);
     const int64_t sLinv = nblk * SB * SB;
     void *scr = nullptr;
-    GPX_TRY(scratch((size_t)nbt * sLinv * sizeof(T), &scr));
+    GPX_TRY(g_scr.get((size_t)nbt * sLinv * sizeof(T), &scr));
     T *Linv = (T *)scr;
     const int aligned = (((uintptr_t)L) % (2 * sizeof(T)) == 0) && (ldl % 2 == 0);
     const int ablate = 0;                          // (timing-only ablations of the step kernels: compile-time edits now)
     const int64_t nb = cdiv(ncols, TB);
     auto width = [&](int64_t blk) { return (int)std::min<int64_t>(TB, ncols - blk * TB); };
     // operator form: square systems of at least two full blocks, aligned rows, one system
-    const bool prebuilt = ops && ops->valid && ops->buf && n % OB == 0 && ops->bytes >= trsv_ops_bytes(dtype, n);
+    const bool prebuilt = ops && ops->valid && ops->mem.p && n % OB == 0 && ops->mem.bytes >= trsv_ops_bytes(dtype, n);
     // operators of the LEADING blocks only (built beside the factorisation, gpx_gp_fit; the caller has ordered `st` behind
     // them): a backward sweep takes the trailing blocks by steps and switches to one launch per block where they begin
-    const int64_t kpart = (ops && !ops->valid && ops->buf && ops->built > 0 && n % OB == 0 && transpose && !bt && ncols == n &&
-                           ops->bytes >= trsv_ops_bytes(dtype, n) && trsv_ops_enabled() && aligned &&
+    const int64_t kpart = (ops && !ops->valid && ops->mem.p && ops->built > 0 && n % OB == 0 && transpose && !bt && ncols == n &&
+                           ops->mem.bytes >= trsv_ops_bytes(dtype, n) && trsv_ops_enabled() && aligned &&
                            ldl % (16 / (int64_t)sizeof(T)) == 0 && ((uintptr_t)L) % 16 == 0) ? std::min(ops->built, n / OB) : 0;
     if (kpart == 0 && trsv_ops_enabled() && !bt && ncols == n && (n >= trsv_ops_min_n() || prebuilt) && aligned &&
         ldl % (16 / (int64_t)sizeof(T)) == 0 && ((uintptr_t)L) % 16 == 0) {
@@ -662,16 +632,13 @@ static int trsv_t(const T *L, int64_t n, int64_t ldl, T *b, T *x, int transpose,
         void *buf = nullptr;
         bool fresh = true;
         if (ops) {                                                   // the caller's cache (one factor, many solves)
-            if (!ops->buf || ops->bytes < trsv_ops_bytes(dtype, n)) {
-                if (ops->buf) { GPX_HIP(hipStreamSynchronize(st)); (void)hipFree(ops->buf); ops->buf = nullptr; }
-                GPX_HIP(hipMalloc(&ops->buf, trsv_ops_bytes(dtype, n)));
-                ops->bytes = trsv_ops_bytes(dtype, n);
-                ops->invalidate();
-            }
-            buf = ops->buf;
+            bool grew = false;
+            GPX_TRY(ops->mem.reserve(trsv_ops_bytes(dtype, n), st, &grew));
+            if (grew) ops->invalidate();
+            buf = ops->mem.p;
             fresh = !ops->valid;
         } else {
-            GPX_TRY(ops_scratch(trsv_ops_bytes(dtype, n), &buf));
+            GPX_TRY(g_ops.get(trsv_ops_bytes(dtype, n), &buf));
         }
         // (a factor whose leading blocks already have their operators: only the rest)
         if (fresh) GPX_TRY(trsv_ops_prepare<T>(L, n, ldl, buf, st, dtype, ops ? std::min(ops->built, nfull) : 0, nfull));
@@ -754,7 +721,7 @@ static int trsv_t(const T *L, int64_t n, int64_t ldl, T *b, T *x, int transpose,
         if (kpart > 0) {
             route_hit(RT_TRSV_OPS);
             const int64_t nfull = n / OB, BS = (int64_t)OB * OB;
-            const T *W = (const T *)ops->buf, *Wt = W + nfull * BS, *Tb = Wt + 3 * nfull * BS;
+            const T *W = (const T *)ops->mem.p, *Wt = W + nfull * BS, *Tb = Wt + 3 * nfull * BS;
             const int NCH = OB / (TBT / 32);
             for (int64_t k = kpart - 1; k >= 0; --k) {
                 const int64_t k0 = k * OB, q0 = k0 + OB;
@@ -780,15 +747,10 @@ int trsv_ops_build(int dtype, const void *L, int64_t n, int64_t ldl, TrsvOps *op
 {
     if (!ops || n < OB || n % OB != 0 || !trsv_ops_enabled() || ldl % (16 / (int64_t)esize(dtype)) != 0 || ((uintptr_t)L) % 16 != 0)
         return GPX_OK;                                               // not eligible: the solve takes the step route
-    const size_t need = trsv_ops_bytes(dtype, n);
-    if (!ops->buf || ops->bytes < need) {
-        if (ops->buf) { GPX_HIP(hipStreamSynchronize(st)); (void)hipFree(ops->buf); ops->buf = nullptr; }
-        GPX_HIP(hipMalloc(&ops->buf, need));
-        ops->bytes = need;
-    }
+    GPX_TRY(ops->mem.reserve(trsv_ops_bytes(dtype, n), st));
     ops->invalidate();
-    if (dtype == GPX_F64) GPX_TRY(trsv_ops_prepare<double>((const double *)L, n, ldl, ops->buf, st, dtype));
-    else GPX_TRY(trsv_ops_prepare<float>((const float *)L, n, ldl, ops->buf, st, dtype));
+    if (dtype == GPX_F64) GPX_TRY(trsv_ops_prepare<double>((const double *)L, n, ldl, ops->mem.p, st, dtype));
+    else GPX_TRY(trsv_ops_prepare<float>((const float *)L, n, ldl, ops->mem.p, st, dtype));
     ops->valid = true;
     ops->built = n / OB;
     return GPX_OK;
@@ -805,18 +767,13 @@ int trsv_ops_build_upto(int dtype, const void *L, int64_t n, int64_t ldl, TrsvOp
     if (!ops || !trsv_ops_ahead_ok(dtype, L, n, ldl)) return GPX_OK;
     const int64_t nfull = n / OB;
     kend = std::min(kend, nfull);
-    const size_t need = trsv_ops_bytes(dtype, n);
     if (ops->built == 0) {
-        if (!ops->buf || ops->bytes < need) {
-            if (ops->buf) { GPX_HIP(hipDeviceSynchronize()); (void)hipFree(ops->buf); ops->buf = nullptr; }
-            GPX_HIP(hipMalloc(&ops->buf, need));
-            ops->bytes = need;
-        }
+        GPX_TRY(ops->mem.reserve_device(trsv_ops_bytes(dtype, n)));
         ops->valid = false;
     }
-    if (kend <= ops->built || !ops->buf) return GPX_OK;
-    if (dtype == GPX_F64) GPX_TRY(trsv_ops_prepare<double>((const double *)L, n, ldl, ops->buf, st, dtype, ops->built, kend));
-    else GPX_TRY(trsv_ops_prepare<float>((const float *)L, n, ldl, ops->buf, st, dtype, ops->built, kend));
+    if (kend <= ops->built || !ops->mem.p) return GPX_OK;
+    if (dtype == GPX_F64) GPX_TRY(trsv_ops_prepare<double>((const double *)L, n, ldl, ops->mem.p, st, dtype, ops->built, kend));
+    else GPX_TRY(trsv_ops_prepare<float>((const float *)L, n, ldl, ops->mem.p, st, dtype, ops->built, kend));
     ops->built = kend;
     if (kend == nfull) ops->valid = true;
     return GPX_OK;
@@ -894,22 +851,7 @@ int panel_gemv_t(int dtype, const void *Lp, int64_t ldl, int64_t rows, int64_t n
 // x_upper: X is upper triangular on entry (the identity, when L^-T itself is wanted): rows beyond
 // the current block are still zero in its columns, so every step works on the leading k0 + kb rows
 // only -- a third of the flops.
-// grow-only device scratch of trsm_right_lt's operator route: one m x 512 block of X (one per host thread)
-struct TrsmScratch { void *p = nullptr; size_t bytes = 0; int device = -1; };
-static thread_local TrsmScratch g_trsm_scr;
-static int trsm_scratch(size_t bytes, void **out)
-{
-    int dev = 0;
-    GPX_HIP(hipGetDevice(&dev));
-    if (g_trsm_scr.device != dev || g_trsm_scr.bytes < bytes) {
-        if (g_trsm_scr.p && g_trsm_scr.device == dev) { GPX_HIP(hipDeviceSynchronize()); (void)hipFree(g_trsm_scr.p); }
-        g_trsm_scr.p = nullptr; g_trsm_scr.bytes = 0; g_trsm_scr.device = dev;
-        GPX_HIP(hipMalloc(&g_trsm_scr.p, bytes));
-        g_trsm_scr.bytes = bytes;
-    }
-    *out = g_trsm_scr.p;
-    return GPX_OK;
-}
+static thread_local ThreadScratch g_trsm_scr;   // trsm_right_lt's operator route: one m x 512 block of X
 
 int trsm_right_lt(int dtype, const void *L, int64_t n, int64_t ldl, void *X, int64_t m, int64_t ldx,
                   hipStream_t st, int x_upper, TrsvOps *ops)
@@ -925,11 +867,11 @@ int trsm_right_lt(int dtype, const void *L, int64_t n, int64_t ldl, void *X, int
         ((uintptr_t)X) % 16 == 0) {
         const int64_t nfull = n / OB, BS = (int64_t)OB * OB;
         if (!ops->valid) GPX_TRY(trsv_ops_build_upto(dtype, L, n, ldl, ops, nfull, st));
-        if (ops->valid && ops->buf) {
+        if (ops->valid && ops->mem.p) {
             route_hit(RT_TRSM_OPS);
             void *scr = nullptr;
-            GPX_TRY(trsm_scratch((size_t)m * OB * es, &scr));
-            const char *W = (const char *)ops->buf;
+            GPX_TRY(g_trsm_scr.get((size_t)m * OB * es, &scr));
+            const char *W = (const char *)ops->mem.p;
             for (int64_t k = 0; k < nfull; ++k) {
                 const int64_t k0 = k * OB, r = k0 + OB;
                 const int64_t me = x_upper ? std::min(m, r) : m;
@@ -978,7 +920,7 @@ int trsm_right_lt_batch(int dtype, const void *L, int64_t sL, int64_t n, int64_t
     route_hit(RT_TRSM_OPS);
     const int64_t nfull = n / OB, BS = (int64_t)OB * OB, sS = m * OB;
     void *scr = nullptr;
-    GPX_TRY(trsm_scratch((size_t)count * sS * es, &scr));
+    GPX_TRY(g_trsm_scr.get((size_t)count * sS * es, &scr));
     for (int64_t k = 0; k < nfull; ++k) {
         const int64_t k0 = k * OB, r = k0 + OB;
         const int64_t me = x_upper ? std::min(m, r) : m;
@@ -1061,7 +1003,7 @@ extern "C" {
 int gpx_d_trsv_lower(int dtype, const void *L, int64_t n, int64_t ldl, void *b, void *x,
                      int transpose, void *stream)
 {
-    gpx::StreamTurn turn__((hipStream_t)stream);     // (this thread's scratch buffers: one stream at a time, gpx_common.h)
+    gpx::StreamTurn turn__((hipStream_t)stream);     // (this thread's scratch buffers: one stream at a time, gpx_mem.h)
     GPX_TRY(ensure_device());
     GPX_ARG(dtype == GPX_F64 || dtype == GPX_F32, "dtype must be GPX_F64 or GPX_F32");
     GPX_ARG(n >= 0, "n < 0");
@@ -1074,7 +1016,7 @@ int gpx_d_trsv_lower(int dtype, const void *L, int64_t n, int64_t ldl, void *b, 
 int gpx_d_trsm_right_lt(int dtype, const void *L, int64_t n, int64_t ldl, void *X, int64_t m,
                         int64_t ldx, void *stream)
 {
-    gpx::StreamTurn turn__((hipStream_t)stream);     // (this thread's scratch buffers: one stream at a time, gpx_common.h)
+    gpx::StreamTurn turn__((hipStream_t)stream);     // (this thread's scratch buffers: one stream at a time, gpx_mem.h)
     GPX_TRY(ensure_device());
     GPX_ARG(dtype == GPX_F64 || dtype == GPX_F32, "dtype must be GPX_F64 or GPX_F32");
     GPX_ARG(n >= 0 && m >= 0, "negative dimension");
@@ -1109,7 +1051,7 @@ extern "C" {
 int gpx_d_trsv_lower_cols(int dtype, const void *L, int64_t n, int64_t ldl, int64_t ncols, void *b,
                           void *x, void *stream)
 {
-    gpx::StreamTurn turn__((hipStream_t)stream);     // (this thread's scratch buffers: one stream at a time, gpx_common.h)
+    gpx::StreamTurn turn__((hipStream_t)stream);     // (this thread's scratch buffers: one stream at a time, gpx_mem.h)
     GPX_TRY(ensure_device());
     GPX_ARG(dtype == GPX_F64 || dtype == GPX_F32, "dtype must be GPX_F64 or GPX_F32");
     GPX_ARG(n >= 0 && ncols >= 0 && ncols <= n, "need 0 <= ncols <= n");

@@ -69,6 +69,26 @@ def test_library_never_calls_getenv():
     assert b.value == a.value + 1
 
 
+def test_device_memory_has_one_owner():
+    """Every allocation and release of device memory inside the library goes through csrc/gpx_mem.h (DevBuf, GrowBuf,
+    ThreadScratch, dev_alloc / dev_free): before that header there were about fifty hand-written sites in seven units,
+    and the copies had drifted apart (five thread-local scratch allocators leaked a block at every device switch).  The
+    only other callers of the HIP allocator are the ABI's gpx_malloc / gpx_free, whose memory belongs to the caller."""
+    csrc = os.path.join(ROOT, "gaussian_processes_amd", "csrc")
+    call = re.compile(r"\bhip(?:Malloc|Free)\w*\s*\(")
+    for f in sorted(os.listdir(csrc)):
+        if not f.endswith((".hip", ".h")) or f == "gpx_mem.h":
+            continue
+        src = open(os.path.join(csrc, f)).read()
+        if f == "gpx_runtime.hip":
+            for name in ("gpx_malloc", "gpx_free"):           # drop the bodies of the two ABI functions
+                m = re.search(r"^int %s\(.*?^}\n" % name, src, re.S | re.M)
+                assert m and len(call.findall(m.group(0))) == 1, name
+                src = src.replace(m.group(0), "")
+        assert not call.search(src), (f, call.findall(src))
+    assert len(call.findall(open(os.path.join(csrc, "gpx_mem.h")).read())) == 2
+
+
 def test_no_cpu_fallback_without_gpu():
     if _lib.device_count() > 0:
         pytest.skip("a GPU is present")
