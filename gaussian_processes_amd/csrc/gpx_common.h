@@ -165,19 +165,25 @@ bool kernel_values_finite(int kernel, const double *p, double s, int dtype);   /
 bool panel_res_fold(int64_t rows, int64_t kpre, int64_t kb, size_t es, int64_t lda, const void *base);
 // Per-factor block operators of the single-right-hand-side solves (gpx_solve.hip, "operator form"): owned by
 // whoever owns the factor; `valid` must be cleared whenever the factor changes.  nullptr: built per call.
+constexpr int TRSV_OPS_BLOCK = 512;          // columns of an operator block: the one copy outside gpx_solve.hip
+static inline int64_t trsv_ops_nblocks(int64_t n) { return n / TRSV_OPS_BLOCK; }            // full blocks of n columns
+static inline bool trsv_ops_whole_blocks(int64_t n) { return n >= TRSV_OPS_BLOCK && n % TRSV_OPS_BLOCK == 0; }
 struct TrsvOps {
-    GrowBuf mem;                 // trsv_ops_bytes(dtype, n) of the factor; a view into a larger block never release()s
+    GrowBuf mem;                 // trsv_ops_bytes(dtype, n) of the factor; a view() never release()s
     bool valid = false;          // all blocks of the CURRENT factor have their operators
-    int64_t built = 0;           // leading 512-blocks of the current factor that have them (trsv_ops_build_upto)
+    int64_t built = 0;           // leading blocks of the current factor that have them (trsv_ops_build_upto)
     void invalidate() { valid = false; built = 0; }   // a new factor: every owner calls this, never `valid = false` alone
+    // no operators yet, in `bytes` of somebody else's block (not owned, not freed)
+    static TrsvOps view(void *p, size_t bytes) { TrsvOps o; o.mem.p = p; o.mem.bytes = bytes; return o; }
 };
-// Build the operators of an n x n factor (n a multiple of 512) ahead of time on `st`; a later trsv_lower with these ops
+// Build the operators of an n x n factor (whole blocks only) ahead of time on `st`; a later trsv_lower with these ops
 // takes the operator route whatever n is (the distributed solve prepares each diagonal block right after its panel).
 int trsv_ops_build(int dtype, const void *L, int64_t n, int64_t ldl, TrsvOps *ops, hipStream_t st);
-// The same in instalments, while the factorisation is still running: the operators of the 512-blocks [ops->built, kend) --
-// which need nothing but block columns < kend of L -- on `st`; ops->valid once kend reaches n / 512.  n % 512 == 0 only
-// (trsv_ops_ahead_ok); the first call of a factor passes ops->built == 0.
+// The same in instalments, while the factorisation is still running: the operators of the blocks [ops->built, kend) --
+// which need nothing but block columns < kend of L -- on `st`; ops->valid once kend reaches trsv_ops_nblocks(n).  At
+// least two whole blocks only (trsv_ops_ahead_ok); the first call of a factor passes ops->built == 0.
 bool trsv_ops_ahead_ok(int dtype, const void *L, int64_t n, int64_t ldl);
+bool trsm_ops_ok(int dtype, const void *L, int64_t n, int64_t ldl);   // ... and trsm_right_lt would use them (GPX_TRSM_OPS)
 size_t trsv_ops_bytes(int dtype, int64_t n);
 int trsv_ops_build_upto(int dtype, const void *L, int64_t n, int64_t ldl, TrsvOps *ops, int64_t kend, hipStream_t st);
 // potrf() progress hook of the calling host thread (null: none): called with the number of leading columns that are final
@@ -189,8 +195,11 @@ int trsv_lower(int dtype, const void *L, int64_t n, int64_t ldl, void *b, void *
                TrsvOps *ops = nullptr);
 int trsm_right_lt(int dtype, const void *L, int64_t n, int64_t ldl, void *X, int64_t m, int64_t ldx,
                   hipStream_t st, int x_upper = 0, TrsvOps *ops = nullptr);   // ops: this factor's block operators (completed here if need be): in-block substitution = one product with inv(L_kk)
-int trsm_right_lt_batch(int dtype, const void *L, int64_t sL, int64_t n, int64_t ldl, void *X, int64_t sX, int64_t m, int64_t ldx,
-                        hipStream_t st, int x_upper, const void *ops_base, int64_t sO, int count);   // `count` systems in lock-step (operator route)
+// K^-1 = L^-T L^-1 from a factor: X <- L^-T (the identity through trsm_right_lt), W <- X X^T, tri = GPX_FULL or GPX_LOWER (the
+// other half cleared).  X, W: n x ldl each.  count == 1: `ops` are the factor's own.  count > 1: a LOCK-STEP group (trsm_ops_ok
+// only): factors sL elements apart, X and W blocks n * ldl apart, operators built here into group_ops (count * trsv_ops_bytes).
+int inv_from_factor(int dtype, const void *L, int64_t n, int64_t ldl, void *X, void *W, int tri, hipStream_t st,
+                    TrsvOps *ops, int count = 1, int64_t sL = 0, void *group_ops = nullptr);
 int logdet_chol(int dtype, const void *L, int64_t n, int64_t ldl, double *out_dev, hipStream_t st, int count = 1,
                 int64_t sL = 0, int64_t so = 0);
 int dot(int dtype, const void *a, const void *b, int64_t n, double *out_dev, hipStream_t st, int count = 1,

@@ -182,14 +182,6 @@ __global__ void scale_copy_kernel(const T *__restrict__ src, T *__restrict__ dst
     if (i < n) dst[i] = (T)((double)src[i] * f);
 }
 
-template <typename T>
-__global__ void eye_fill_kernel(T *__restrict__ X, int64_t n, int64_t ld)
-{
-    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= ld) return;
-    for (int64_t r = blockIdx.y; r < n; r += gridDim.y) X[r * ld + c] = (c == r) ? (T)1 : (T)0;
-}
-
 // out (m) <- a (m) - b (m)
 template <typename T>
 __global__ void sub_kernel(const T *__restrict__ a, const T *__restrict__ b, T *__restrict__ out, int64_t n, double fb)
@@ -311,14 +303,7 @@ static int d2lh_t(gpx_gp *g, double *dlh_out, double *d2lh_out, double *d2loglh_
     GPX_TRY(X.alloc((size_t)n * lda * sizeof(T)));
     GPX_TRY(D.scal.alloc(64 * sizeof(double)));
     GPX_TRY(D.part.alloc((size_t)DR_BLOCKS * 2 * DR_MAXM * sizeof(double)));
-    {
-        dim3 grid((unsigned)cdiv(lda, 256), (unsigned)std::min<int64_t>(n, 32768)), block(256);
-        hipLaunchKernelGGL((eye_fill_kernel<T>), grid, block, 0, st, (T *)X.p, n, lda);
-        GPX_LAUNCH_CHECK();
-        GPX_HIP(hipMemsetAsync(D.W.p, 0, (size_t)n * lda * sizeof(T), st));
-        GPX_TRY(trsm_right_lt(g->dtype, g->A, n, lda, X.p, n, lda, st, 1, &g->ops));
-        GPX_TRY(gemm_nt(g->dtype, n, n, n, X.p, lda, X.p, lda, D.W.p, lda, 1.0, GPX_FULL, 0, 0, st, 0, 1));
-    }
+    GPX_TRY(inv_from_factor(g->dtype, g->A, n, lda, X.p, D.W.p, GPX_FULL, st, &g->ops));
     // a_i = alpha . v_i ; vu_ij = v_j . u_i   (device dots, one launch each: count = 1)
     std::vector<double> a(P), tr(P), vu((size_t)P * P), q((size_t)P * P, 0.0), hh((size_t)P * P, 0.0), T2((size_t)P * P, 0.0);
     double *sc = (double *)D.scal.p;

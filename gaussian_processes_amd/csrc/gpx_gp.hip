@@ -37,14 +37,6 @@ __global__ void cvt_to_f64_2d(const T *__restrict__ src, int64_t lds, double *__
     }
 }
 
-template <typename T>
-__global__ void eye_kernel(T *__restrict__ X, int64_t n, int64_t ld)
-{
-    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= ld) return;
-    for (int64_t r = blockIdx.y; r < n; r += gridDim.y) X[r * ld + c] = (c == r) ? (T)1 : (T)0;
-}
-
 // upload a host f64 array into a device buffer of dtype (via a temporary when f32)
 static int upload_f64(int dtype, void *dst, const double *src, int64_t count, hipStream_t st)
 {
@@ -291,7 +283,7 @@ static int ops_ahead_step(void *user, int64_t cols_done, hipEvent_t panel_done)
 {
     OpsAhead *o = (OpsAhead *)user;
     gpx_gp *g = o->g;
-    const int64_t ready = std::min(cols_done / 512, o->last);   // (the trailing blocks are left to the sweep's own steps)
+    const int64_t ready = std::min(trsv_ops_nblocks(cols_done), o->last);   // (the trailing blocks are left to the sweep's own steps)
     if (ready - g->ops.built < o->group) return GPX_OK;
     GPX_HIP(hipStreamWaitEvent(g->st_ops, panel_done, 0));
     return trsv_ops_build_upto(g->dtype, g->A, g->n, g->lda, &g->ops, ready, g->st_ops);
@@ -335,7 +327,7 @@ int gpx_gp_fit(gpx_gp_t *g, int *info)
     // blocks (~0.6 ms whatever their number), so instalments of 4 blocks cost the factorisation what the solve saves
     // (n = 8192: fit 6.71 -> 6.73 ms with groups of 4, 6.62 with one; n = 12288: 15.57 -> 15.04; n = 4096: no gain), and
     // the last blocks' operators would only be waited for: the backward sweep takes those blocks by steps
-    const int64_t nfull = g->n / 512, tail = tune().fit_ops_tail;
+    const int64_t nfull = trsv_ops_nblocks(g->n), tail = tune().fit_ops_tail;
     const int64_t group = std::max<int64_t>(1, std::min(nfull, nfull - tail));
     OpsAhead oa = {g, group, std::max<int64_t>(0, nfull - tail)};
     PotrfHook hook = {ops_ahead_step, &oa};
@@ -556,14 +548,7 @@ int gpx_gp_get_inv_Kxx(gpx_gp_t *g, double *out, int64_t ld)
     DevBuf X, C;
     GPX_TRY(X.alloc((size_t)n * lda * es));
     GPX_TRY(C.alloc((size_t)n * lda * es));
-    dim3 grid((unsigned)cdiv(lda, 256), (unsigned)std::min<int64_t>(n, 32768)), block(256);
-    if (g->dtype == GPX_F64) hipLaunchKernelGGL((eye_kernel<double>), grid, block, 0, g->st, (double *)X.p, n, lda);
-    else hipLaunchKernelGGL((eye_kernel<float>), grid, block, 0, g->st, (float *)X.p, n, lda);
-    GPX_LAUNCH_CHECK();
-    GPX_HIP(hipMemsetAsync(C.p, 0, (size_t)n * lda * es, g->st));
-    // X = I L^-T = L^-T ; K^-1 = L^-T L^-1 = X X^T   (gp/gp.py:311-312)
-    GPX_TRY(trsm_right_lt(g->dtype, g->A, n, lda, X.p, n, lda, g->st, 1, &g->ops));
-    GPX_TRY(gemm_nt(g->dtype, n, n, n, X.p, lda, X.p, lda, C.p, lda, 1.0, GPX_FULL, 0, 0, g->st, 0, 1));
+    GPX_TRY(inv_from_factor(g->dtype, g->A, n, lda, X.p, C.p, GPX_FULL, g->st, &g->ops));   // gp/gp.py:311-312
     return download_f64(g->dtype, out, ld, C.p, lda, n, n, 0, g->st);
 }
 
@@ -592,15 +577,7 @@ static int grad_reduce(gpx_gp *g, const void *alpha, const double *params, doubl
 static int grad_from_factor(gpx_gp *g, const void *L, int64_t lda, const void *alpha, const double *params, double s_noise,
                             void *X, void *W, double *part, TrsvOps *ops, double *out)
 {
-    const size_t es = esize(g->dtype);
-    const int64_t n = g->n;
-    dim3 grid((unsigned)cdiv(lda, 256), (unsigned)std::min<int64_t>(n, 32768)), block(256);
-    if (g->dtype == GPX_F64) hipLaunchKernelGGL((eye_kernel<double>), grid, block, 0, g->st, (double *)X, n, lda);
-    else hipLaunchKernelGGL((eye_kernel<float>), grid, block, 0, g->st, (float *)X, n, lda);
-    GPX_LAUNCH_CHECK();
-    GPX_HIP(hipMemsetAsync(W, 0, (size_t)n * lda * es, g->st));
-    GPX_TRY(trsm_right_lt(g->dtype, L, n, lda, X, n, lda, g->st, 1, ops));
-    GPX_TRY(gemm_nt(g->dtype, n, n, n, X, lda, X, lda, W, lda, 1.0, GPX_LOWER, 0, 0, g->st, 0, 1));
+    GPX_TRY(inv_from_factor(g->dtype, L, g->n, lda, X, W, GPX_LOWER, g->st, ops));
     return grad_reduce(g, alpha, params, s_noise, W, lda, part, out);
 }
 
@@ -650,7 +627,7 @@ static int fit_batch_impl(gpx_gp_t *g, const double *thetas, int64_t B, double *
         // at a time (the group's TRSM and SYRK run in lock-step: at n = 8192 one system's far update is 1 - 2 rounds of
         // tiles), as many as a sixth of free HBM holds, + their block operators
         const size_t nl = (size_t)g->n * g->lda * esize(g->dtype);
-        const bool group_ok = trsv_ops_ahead_ok(g->dtype, g->A, g->n, g->lda) && tune().trsm_ops != 0;
+        const bool group_ok = trsm_ops_ok(g->dtype, g->A, g->n, g->lda);
         size_t freeg = 0, totalg = 0;
         GPX_HIP(hipMemGetInfo(&freeg, &totalg));
         const size_t per_row = 2 * nl + (group_ok ? trsv_ops_bytes(g->dtype, g->n) : 0);
@@ -755,21 +732,8 @@ static int fit_batch_impl(gpx_gp_t *g, const double *thetas, int64_t B, double *
                 if (lock_step) {
                     // the group's K^-1 in lock-step: X = L^-T (operators of every row built first), W = X X^T lower.  Rows that are
                     // invalid or not positive definite take part (their factor is garbage; nothing of theirs is read back).
-                    const char *L0 = (const char *)Ab.p + (size_t)i0 * per;
-                    dim3 grid((unsigned)cdiv(lda, 256), (unsigned)std::min<int64_t>(n, 32768)), block(256);
-                    for (int i = 0; i < gc; ++i) {
-                        if (g->dtype == GPX_F64) hipLaunchKernelGGL((eye_kernel<double>), grid, block, 0, st, (double *)(Xs + (size_t)i * nl), n, lda);
-                        else hipLaunchKernelGGL((eye_kernel<float>), grid, block, 0, st, (float *)(Xs + (size_t)i * nl), n, lda);
-                        GPX_LAUNCH_CHECK();
-                        TrsvOps o;                                   // (a view into the group's operator block: not owned, not freed)
-                        o.mem.p = Os + (size_t)i * obytes; o.mem.bytes = obytes;
-                        GPX_TRY(trsv_ops_build_upto(g->dtype, L0 + (size_t)i * per, n, lda, &o, n / 512, st));
-                    }
-                    GPX_HIP(hipMemsetAsync(Ws, 0, (size_t)gc * nl, st));
-                    GPX_TRY(trsm_right_lt_batch(g->dtype, L0, (int64_t)(per / es), n, lda, Xs, (int64_t)(nl / es), n, lda, st, 1, Os,
-                                                (int64_t)(obytes / es), gc));
-                    Batch bw; bw.count = gc; bw.sA = bw.sB = bw.sC = (int64_t)(nl / es);
-                    GPX_TRY(gemm_nt(g->dtype, n, n, n, Xs, lda, Xs, lda, Ws, lda, 1.0, GPX_LOWER, 0, 0, st, 0, 1, &bw));
+                    GPX_TRY(inv_from_factor(g->dtype, (const char *)Ab.p + (size_t)i0 * per, n, lda, Xs, Ws, GPX_LOWER, st, nullptr, gc,
+                                            (int64_t)(per / es), Os));
                 }
                 for (int i = i0; i < i0 + gc; ++i) {
                     double *o = dloglh + (b0 + i) * (np + 1);

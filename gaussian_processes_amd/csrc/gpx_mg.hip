@@ -695,7 +695,7 @@ static int mg_alloc(gpx_mg *g)
     // (~21 MB per 1024-wide fp64 block: 1.3 GB at N = 65536 on one rank -- part of this handle's HBM budget)
     for (size_t jl = 0; jl < g->my_blocks.size(); ++jl) {
         const int64_t kb = g->kb(g->my_blocks[jl]);
-        if (kb < 512 || kb % 512 != 0) continue;                  // (the step route: trsv_ops_build declines these)
+        if (!trsv_ops_whole_blocks(kb)) continue;                 // (the step route: trsv_ops_build declines these)
         GPX_TRY(g->ops[jl].mem.reserve(trsv_ops_bytes(g->dtype, kb), g->O));
     }
     return GPX_OK;

@@ -8,14 +8,16 @@
 // Roofline: HBM read bandwidth -- a single-right-hand-side solve reads the
 // lower triangle of L once per direction (n^2/2 * sizeof(T) bytes, 2 n^2 flop for
 // both directions together).  The 64 x 64 diagonal blocks are inverted up front in
-// ONE batched launch (trinv64_kernel); the solve then advances 512 columns per
-// launch (trsv_fwd_fused / trsv_bwd_fused below).
+// ONE batched launch (inv64_kernel); the solve then advances 512 columns per launch:
+// trsv_fwd_fused / trsv_bwd_fused (steps), or trsv_op_kernel with per-block operators
+// built once per factor ("operator form" below; who may use them: ops_usable).
 #include "gpx_common.h"
 #include "gpx_leaf.h"
 
 namespace gpx {
 
-constexpr int SB = 64;
+constexpr int SB = 64;                 // the diagonal blocks that are inverted directly
+constexpr int OB = TRSV_OPS_BLOCK;     // columns of an operator block ("operator form" below)
 
 // ---- batched inverse of the 64 x 64 diagonal blocks --------------------------
 // One 256-thread workgroup per block (all blocks in one launch): the register-resident 4 x 4-tile sweep of the
@@ -48,9 +50,9 @@ __global__ __launch_bounds__(256) void inv64_kernel(const T *__restrict__ L, int
         }
     factor64<T, true, true>(a, x, jb, 0, nullptr);
     T *o = out ? out + (int64_t)blockIdx.y * bsOut + (int64_t)blockIdx.x * (SB * SB) : nullptr;
-    const int64_t kb = blockIdx.x >> 3, pp = blockIdx.x & 7;
-    T *w = W ? W + kb * (int64_t)(512 * 512) + pp * SB * (512 + 1) : nullptr;
-    T *wt = Wt ? Wt + kb * (int64_t)(512 * 512) + pp * SB * (512 + 1) : nullptr;
+    const int64_t kb = blockIdx.x / (OB / SB), pp = blockIdx.x % (OB / SB);
+    T *w = W ? W + kb * (int64_t)(OB * OB) + pp * SB * (OB + 1) : nullptr;
+    T *wt = Wt ? Wt + kb * (int64_t)(OB * OB) + pp * SB * (OB + 1) : nullptr;
 #pragma unroll
     for (int r = 0; r < 4; ++r)
 #pragma unroll
@@ -58,7 +60,7 @@ __global__ __launch_bounds__(256) void inv64_kernel(const T *__restrict__ L, int
             const int row = 4 * tr + r, col = 4 * tc + c;
             const T v = (col <= row) ? x[r][c] : (T)0;
             if (o) o[transposed ? col * SB + row : row * SB + col] = v;
-            if (w) { w[(int64_t)row * 512 + col] = v; wt[(int64_t)col * 512 + row] = v; }
+            if (w) { w[(int64_t)row * OB + col] = v; wt[(int64_t)col * OB + row] = v; }
         }
 }
 
@@ -228,7 +230,7 @@ template <typename T>
 __global__ __launch_bounds__(TBT) void trsv_fwd_fused(const T *__restrict__ L, int64_t ldl,
                                                       const T *__restrict__ Linv, T *__restrict__ b,
                                                       T *__restrict__ x, int64_t n, int64_t k0, int jb,
-                                                      int64_t p0, int pjb, int64_t far0, int aligned_i, int ablate,
+                                                      int64_t p0, int pjb, int64_t far0, int aligned_i,
                                                       int64_t bsL, int64_t bsLinv, int64_t bsv)
 {
     L += (int64_t)blockIdx.y * bsL; Linv += (int64_t)blockIdx.y * bsLinv;    // batched: system blockIdx.y
@@ -241,7 +243,7 @@ __global__ __launch_bounds__(TBT) void trsv_fwd_fused(const T *__restrict__ L, i
     const bool aligned = aligned_i != 0;
 
     if (blockIdx.x != 0) {
-        if (pjb <= 0 || (ablate & 4)) return;
+        if (pjb <= 0) return;
         far_fwd<T>(L, ldl, b, x, n, p0, pjb, far0, (int)blockIdx.x - 1, aligned, szp);
         return;
     }
@@ -264,7 +266,7 @@ __global__ __launch_bounds__(TBT) void trsv_fwd_fused(const T *__restrict__ L, i
     T l0[CG][4], l1[CG][4];
     __syncthreads();
     for (int s = 0; s < ns; ++s) {
-        if (s > 0 && !(ablate & 2)) {
+        if (s > 0) {
             T acc = (T)0;
 #pragma unroll
             for (int t = 0; t < CG; ++t) {
@@ -284,14 +286,12 @@ __global__ __launch_bounds__(TBT) void trsv_fwd_fused(const T *__restrict__ L, i
             const T *Li = Li0 + (s + 1) * (int64_t)(SB * SB);
 #pragma unroll
             for (int cc = 0; cc < 8; ++cc) ln[cc] = Li[(wave * 8 + cc) * SB + lane];
-            if (!(ablate & 2)) {
-                const T *rp = Lblk + (int64_t)min((s + 1) * SB + row, jb - 1) * ldl + 2 * j8;
+            const T *rp = Lblk + (int64_t)min((s + 1) * SB + row, jb - 1) * ldl + 2 * j8;
 #pragma unroll
-                for (int t = 0; t < CG; ++t) {
-                    if (t <= s) {
+            for (int t = 0; t < CG; ++t) {
+                if (t <= s) {
 #pragma unroll
-                        for (int m = 0; m < 4; ++m) load2(rp + t * SB + m * 16, aligned, l0[t][m], l1[t][m]);
-                    }
+                    for (int m = 0; m < 4; ++m) load2(rp + t * SB + m * 16, aligned, l0[t][m], l1[t][m]);
                 }
             }
         }
@@ -358,7 +358,7 @@ template <typename T, int CW>
 __global__ __launch_bounds__(TBT) void trsv_bwd_fused(const T *__restrict__ L, int64_t ldl,
                                                       const T *__restrict__ Linv, T *__restrict__ b,
                                                       T *__restrict__ x, int64_t k0, int jb, int64_t q0,
-                                                      int qjb, int64_t c0, int64_t c1, int aligned_i, int ablate,
+                                                      int qjb, int64_t c0, int64_t c1, int aligned_i,
                                                       int64_t bsL, int64_t bsLinv, int64_t bsv)
 {
     L += (int64_t)blockIdx.y * bsL; Linv += (int64_t)blockIdx.y * bsLinv;
@@ -371,7 +371,7 @@ __global__ __launch_bounds__(TBT) void trsv_bwd_fused(const T *__restrict__ L, i
     const bool aligned = aligned_i != 0;
 
     if (blockIdx.x != 0) {
-        if (qjb <= 0 || (ablate & 4)) return;
+        if (qjb <= 0) return;
         far_bwd<T, CW>(L, ldl, b, x, q0, qjb, c0, c1, (int)blockIdx.x - 1, aligned, sa, red);
         return;
     }
@@ -394,7 +394,7 @@ __global__ __launch_bounds__(TBT) void trsv_bwd_fused(const T *__restrict__ L, i
 #pragma unroll
         for (int cc = 0; cc < 8; ++cc) li[cc] = Li[(wave * 8 + cc) * SB + lane];
         T l0[32], l1[32];
-        const bool act = 2 * cpair < ncol && !(ablate & 2);     // ncol is a multiple of 64: always a pair
+        const bool act = 2 * cpair < ncol;       // ncol is a multiple of 64: always a pair
         if (act) {
             const T *col = L + (k0 + s * SB) * ldl + k0 + 2 * cpair;
 #pragma unroll
@@ -432,13 +432,11 @@ __global__ __launch_bounds__(TBT) void trsv_bwd_fused(const T *__restrict__ L, i
 //     W_k  = inv(L_kk)             (512 x 512, from the 64 x 64 inverses by recursive doubling, batched over k)
 //     Tf_k = W_k L_{k,k-1}         forward :  x_k = W_k  w_k - Tf_k x_{k-1}
 //     Tb_k = W_k^T L_{k+1,k}^T     backward:  a_k = W_k^T z_k - Tb_k a_{k+1}
-// a block step is ONE launch with no dependency inside it: 8 workgroups do the two 512-wide mat-vecs of block k
-// (64 rows each, 8 lanes per row, whole 128-byte lines), all others stream the far panel of the neighbour block
+// a block step is ONE launch with no dependency inside it: 32 workgroups do the two 512-wide mat-vecs of block k
+// (16 rows each, 32 lanes per row, whole 128-byte lines), all others stream the far panel of the neighbour block
 // exactly as before.  w_k / z_k already hold every far contribution (blocks two or more away were streamed by
 // earlier launches); the neighbour's contribution comes through Tf / Tb.  A ragged last block (n % 512) keeps
 // the old kernels.  Cost of the operators: 2 (n / 512) products of 512^3 + the doubling, ~1.3 ms at n = 65536.
-constexpr int OB = 512;
-
 // LT_k[j][m] = L[(OB k + m), OB (k - 1) + j]   for k = 1 .. nfull - 1  (grid: (OB / 64)^2 tiles, k - 1)
 template <typename T>
 __global__ __launch_bounds__(256) void transpose_subdiag_kernel(const T *__restrict__ L, int64_t ldl, T *__restrict__ LT)
@@ -459,10 +457,11 @@ __global__ __launch_bounds__(256) void transpose_subdiag_kernel(const T *__restr
     }
 }
 
-// one block step: workgroups [0, nchain) solve block k (rows k0 ..), the others stream the neighbour's far panel
-// PARTS lanes per row: 8 (64 rows per workgroup, 8 workgroups a block) or 32 (16 rows, 32 workgroups -- a workgroup
-// streams 128 KB of operators instead of 512: the block's two mat-vecs are bound by what ONE CU can pull)
-template <typename T, bool FWD, int PARTS>
+// one block step: workgroups [0, nchain) solve block k (rows k0 ..), the others stream the neighbour's far panel.
+// OPL = 32 lanes per row: 16 rows a workgroup, 32 workgroups a block -- a workgroup streams 128 KB of operators (with 8
+// lanes a row and 8 workgroups it was 512: the block's two mat-vecs are bound by what ONE CU can pull)
+constexpr int OPL = 32;
+template <typename T, bool FWD>
 __global__ __launch_bounds__(TBT) void trsv_op_kernel(const T *__restrict__ Wk, const T *__restrict__ Tk,
                                                       const T *__restrict__ L, int64_t ldl, T *__restrict__ rhs,
                                                       T *__restrict__ x, int64_t n, int64_t k0, int64_t p0, int pjb,
@@ -484,8 +483,8 @@ __global__ __launch_bounds__(TBT) void trsv_op_kernel(const T *__restrict__ Wk, 
         szp[i] = (Tk && i < pjb) ? x[p0 + i] : (T)0;
     }
     __syncthreads();
-    constexpr int ROWS = TBT / PARTS;                 // rows per workgroup
-    const int r = tid / PARTS, part = tid % PARTS;
+    constexpr int ROWS = TBT / OPL;                   // rows per workgroup
+    const int r = tid / OPL, part = tid % OPL;
     const int row = ROWS * (int)blockIdx.x + r;
     const T *wrow = Wk + (int64_t)row * OB, *trow = Tk ? Tk + (int64_t)row * OB : nullptr;
     T acc = (T)0;
@@ -493,8 +492,8 @@ __global__ __launch_bounds__(TBT) void trsv_op_kernel(const T *__restrict__ Wk, 
     // the loads cannot be batched and every iteration pays a memory round trip (measured 30 us instead of 8)
     if (trow) {
 #pragma unroll 8
-        for (int i = 0; i < OB / (2 * PARTS); ++i) {
-            const int c = 2 * PARTS * i + 2 * part;
+        for (int i = 0; i < OB / (2 * OPL); ++i) {
+            const int c = 2 * OPL * i + 2 * part;
             T w0, w1, t0, t1;
             load2(wrow + c, true, w0, w1);
             load2(trow + c, true, t0, t1);
@@ -505,45 +504,59 @@ __global__ __launch_bounds__(TBT) void trsv_op_kernel(const T *__restrict__ Wk, 
         }
     } else {
 #pragma unroll 8
-        for (int i = 0; i < OB / (2 * PARTS); ++i) {
-            const int c = 2 * PARTS * i + 2 * part;
+        for (int i = 0; i < OB / (2 * OPL); ++i) {
+            const int c = 2 * OPL * i + 2 * part;
             T w0, w1;
             load2(wrow + c, true, w0, w1);
             acc = fma(w0, sv[c], acc);
             acc = fma(w1, sv[c + 1], acc);
         }
     }
-    acc = PARTS == 8 ? lanes8_sum(acc) : lanes32_sum(acc);
+    acc = lanes32_sum(acc);
     if (part == 0) x[k0 + row] = acc;
 }
 
 static thread_local ThreadScratch g_ops;        // home of the operators when the caller brings no cache of its own
 
-size_t trsv_ops_bytes(int dtype, int64_t n)
-{
-    const int64_t nfull = n / OB;
-    return (size_t)(5 * nfull * (int64_t)OB * OB + nfull * 8 * (int64_t)SB * SB) * esize(dtype) + 256;
-}
+// The operator buffer of a factor with nfull = n / OB full blocks: five runs of nfull blocks of OB x OB elements,
+//     W_k | Wt_k = W_k^T | P_k (work space of the build; L_{k,k-1}^T in the end) | Tf_k | Tb_k,
+// then TAIL elements a block that nothing reads (the size of that block's 64 x 64 inverses, which live in g_scr) and
+// 256 bytes.  bytes() is what fit_batch_grad sizes its groups from and what the multi-GPU handle reserves per panel:
+// it stays as it is until the tail is dropped in a change of its own.
+template <typename T>
+struct OpsView {
+    static constexpr int64_t BS = (int64_t)OB * OB, TAIL = (int64_t)(OB / SB) * SB * SB;
+    T *base; int64_t nfull;
+    OpsView(const void *buf, int64_t n) : base((T *)buf), nfull(n / OB) {}
+    T *run(int r, int64_t k) const { return base + (r * nfull + k) * BS; }
+    T *W(int64_t k) const { return run(0, k); }
+    T *Wt(int64_t k) const { return run(1, k); }
+    T *P(int64_t k) const { return run(2, k); }
+    T *Tf(int64_t k) const { return run(3, k); }
+    T *Tb(int64_t k) const { return run(4, k); }
+    static size_t bytes(int64_t n) { return (size_t)((n / OB) * (5 * BS + TAIL)) * sizeof(T) + 256; }
+};
 
-// build W, Wt, Tf, Tb of the 512-blocks [kbeg, kend) of L into `buf` (trsv_ops_bytes): everything is batched over the
+size_t trsv_ops_bytes(int dtype, int64_t n) { return dtype == GPX_F64 ? OpsView<double>::bytes(n) : OpsView<float>::bytes(n); }
+
+// build W, Wt, Tf, Tb of the blocks [kbeg, kend) of L into `buf` (trsv_ops_bytes): everything is batched over the
 // blocks of the range with the pointers moved to its first block.  Block k needs L_kk, L_{k,k-1} and L_{k+1,k}: block
 // columns <= k of the factor.  kbeg = 0 also clears the triangular operators' zero halves for ALL blocks, so ranges go
 // out in increasing order.
 template <typename T>
-static int trsv_ops_prepare(const T *L, int64_t n, int64_t ldl, void *buf, hipStream_t st, int dtype, int64_t kbeg = 0,
-                            int64_t kend = -1)
+static int trsv_ops_prepare(const T *L, int64_t n, int64_t ldl, void *buf, hipStream_t st, int64_t kbeg = 0, int64_t kend = -1)
 {
-    const int64_t nfull = n / OB, rag = n - nfull * OB;
+    constexpr int dtype = sizeof(T) == 8 ? GPX_F64 : GPX_F32;
+    const OpsView<T> V(buf, n);
+    const int64_t nfull = V.nfull, rag = n - nfull * OB, BS = V.BS;
     if (kend < 0 || kend > nfull) kend = nfull;
     const int64_t cnt = kend - kbeg;
-    const int64_t BS = (int64_t)OB * OB;
-    T *W = (T *)buf, *Wt = W + nfull * BS, *P = Wt + nfull * BS, *Tf = P + nfull * BS, *Tb = Tf + nfull * BS;
-    if (kbeg == 0) GPX_HIP(hipMemsetAsync(W, 0, (size_t)2 * nfull * BS * sizeof(T), st));
+    if (kbeg == 0) GPX_HIP(hipMemsetAsync(V.W(0), 0, (size_t)(V.P(0) - V.W(0)) * sizeof(T), st));   // every W and Wt
     if (cnt <= 0) return GPX_OK;
     const int64_t dLk = (int64_t)OB * (ldl + 1);                     // L_kk -> L_{k+1,k+1}
     const T *Lk = L + kbeg * dLk;
-    T *Wk = W + kbeg * BS, *Wtk = Wt + kbeg * BS, *Pk = P + kbeg * BS;
-    hipLaunchKernelGGL((inv64_kernel<T>), dim3((unsigned)(cnt * 8)), dim3(256), 0, st, Lk, ldl, cnt * OB, (T *)nullptr, 0,
+    T *Wk = V.W(kbeg), *Wtk = V.Wt(kbeg), *Pk = V.P(kbeg);
+    hipLaunchKernelGGL((inv64_kernel<T>), dim3((unsigned)(cnt * (OB / SB))), dim3(256), 0, st, Lk, ldl, cnt * OB, (T *)nullptr, 0,
                        Wk, Wtk, (int64_t)0, (int64_t)0);
     GPX_LAUNCH_CHECK();
     for (int64_t s2 = SB; s2 < OB; s2 *= 2) {
@@ -562,172 +575,197 @@ static int trsv_ops_prepare(const T *L, int64_t n, int64_t ldl, void *buf, hipSt
     const int64_t ka = std::max<int64_t>(kbeg, 1);                   // Tf_k = W_k L_{k,k-1} = W_k LT_k^T,  k = ka .. kend - 1
     if (kend > ka) {
         // (the transpose kernel numbers its blocks from 1 relative to the base it is given)
-        hipLaunchKernelGGL((transpose_subdiag_kernel<T>), dim3(64, (unsigned)(kend - ka)), dim3(256), 0, st, L + (ka - 1) * dLk, ldl,
-                           P + (ka - 1) * BS);
+        hipLaunchKernelGGL((transpose_subdiag_kernel<T>), dim3((OB / SB) * (OB / SB), (unsigned)(kend - ka)), dim3(256), 0, st,
+                           L + (ka - 1) * dLk, ldl, V.P(ka - 1));
         GPX_LAUNCH_CHECK();
         Batch b;
         b.count = (int)(kend - ka);
         b.sA = BS; b.sB = BS; b.sC = BS;
-        GPX_TRY(gemm_nt(dtype, OB, OB, OB, W + ka * BS, OB, P + ka * BS, OB, Tf + ka * BS, OB, 1.0, GPX_FULL, 0, 0, st, 1, 0, &b));
+        GPX_TRY(gemm_nt(dtype, OB, OB, OB, V.W(ka), OB, V.P(ka), OB, V.Tf(ka), OB, 1.0, GPX_FULL, 0, 0, st, 1, 0, &b));
     }
     const int64_t kb_end = std::min(kend, nfull - 1);                // Tb_k = W_k^T L_{k+1,k}^T,  k = kbeg .. kb_end - 1
     if (kb_end > kbeg) {
         Batch b;
         b.count = (int)(kb_end - kbeg);
         b.sA = BS; b.sB = dLk; b.sC = BS;
-        GPX_TRY(gemm_nt(dtype, OB, OB, OB, Wtk, OB, Lk + (int64_t)OB * ldl, ldl, Tb + kbeg * BS, OB, 1.0, GPX_FULL, 0, 0, st, 1, 0, &b));
+        GPX_TRY(gemm_nt(dtype, OB, OB, OB, Wtk, OB, Lk + (int64_t)OB * ldl, ldl, V.Tb(kbeg), OB, 1.0, GPX_FULL, 0, 0, st, 1, 0, &b));
     }
     if (rag > 0 && kend == nfull) {                                  // the last full block against the ragged one
-        T *tb = Tb + (nfull - 1) * BS;
+        T *tb = V.Tb(nfull - 1);
         GPX_HIP(hipMemsetAsync(tb, 0, (size_t)BS * sizeof(T), st));
-        GPX_TRY(gemm_nt(dtype, OB, rag, OB, Wt + (nfull - 1) * BS, OB, L + nfull * OB * ldl + (nfull - 1) * OB, ldl, tb, OB,
+        GPX_TRY(gemm_nt(dtype, OB, rag, OB, V.Wt(nfull - 1), OB, L + nfull * OB * ldl + (nfull - 1) * OB, ldl, tb, OB,
                         1.0, GPX_FULL, 0, 0, st, 1, 0));
     }
     return GPX_OK;
 }
 
-static bool trsv_ops_enabled()
+// ---- who may use the operators: two tests, and what each caller asks on top of them --------------------
+//   ops_usable(dtype, L, ldl)   GPX_TRSV_OPS on, L on a 16-byte boundary, ldl % (16 / es) == 0
+//   trsv_ops_whole_blocks(n)    n % OB == 0 and n >= OB   (gpx_common.h)
+//   trsv_ops_build        usable, whole blocks (n == OB too: the multi-GPU fit's 512-wide panels)
+//   trsv_ops_ahead_ok     usable, whole blocks, n >= 2 OB   (gpx_gp_fit, trsv_ops_build_upto)
+//   trsm_ops_ok           trsv_ops_ahead_ok, GPX_TRSM_OPS on; trsm_right_lt: + the factor's TrsvOps, X and ldx as L and ldl
+//   trsv_t, operators     usable, one square system; n >= trsv_ops_min_n() -- ANY such n, the last block may be ragged --
+//                         or the caller's operators are complete (whole blocks)
+//   trsv_t, mixed         usable, one square system, backward; the caller's operators cover 0 < built leading blocks
+// The 16-byte pair implies the step kernels' `aligned` (L % (2 es) == 0, ldl % 2 == 0: two elements in one load), so the
+// operator sweeps pass aligned = 1:
+static bool ops_usable(int dtype, const void *L, int64_t ldl)
 {
-    return tune().trsv_ops != 0;
+    static_assert(16 % (2 * sizeof(double)) == 0 && 16 % (2 * sizeof(float)) == 0, "16 is a multiple of 2 es");
+    static_assert((16 / sizeof(double)) % 2 == 0 && (16 / sizeof(float)) % 2 == 0, "16 / es is even");
+    return tune().trsv_ops != 0 && ((uintptr_t)L) % 16 == 0 && ldl % (16 / (int64_t)esize(dtype)) == 0;
 }
 // below this the ~0.7 ms of operator products (11 under-filled launches) costs what the shorter steps save
 // (n = 8192: 1.17 vs 1.10 ms for both sweeps; n = 16384: 1.78 vs 2.49; n = 65536: 9.7 vs 12.1)
-static int64_t trsv_ops_min_n()
+static int64_t trsv_ops_min_n() { return std::max<int64_t>(2 * OB, tune().trsv_ops_min); }
+bool trsv_ops_ahead_ok(int dtype, const void *L, int64_t n, int64_t ldl) { return n >= 2 * OB && trsv_ops_whole_blocks(n) && ops_usable(dtype, L, ldl); }
+bool trsm_ops_ok(int dtype, const void *L, int64_t n, int64_t ldl) { return trsv_ops_ahead_ok(dtype, L, n, ldl) && tune().trsm_ops != 0; }
+
+// ---- the sweeps: what the launches of one solve share -----------------------------------------------------
+template <typename T>
+struct Sweep {
+    const T *L; int64_t n, ldl, ncols; T *b, *x; hipStream_t st;
+    unsigned nbt; int64_t sL, sv;      // systems solved by the same launches; strides of L, of b and x
+    T *Linv; int64_t sLinv;            // the 64 x 64 inverses of the diagonal (g_scr), stride per system
+    int aligned;                       // step kernels: two elements in one load
+    int64_t nb() const { return cdiv(ncols, TB); }
+    int width(int64_t blk) const { return (int)std::min<int64_t>(TB, ncols - blk * TB); }
+};
+
+// the inverses of the diagonal 64-blocks from `first` on, laid out for the forward (transposed = 1) / backward sweep
+template <typename T>
+static void inv64_blocks(const Sweep<T> &S, int64_t first, int transposed)
 {
-    return std::max<int64_t>(2 * OB, tune().trsv_ops_min);
+    hipLaunchKernelGGL((inv64_kernel<T>), dim3((unsigned)(cdiv(S.ncols, SB) - first), S.nbt), dim3(256), 0, S.st,
+                       S.L + first * SB * (S.ldl + 1), S.ldl, S.ncols - first * SB, S.Linv + first * SB * SB, transposed,
+                       (T *)nullptr, (T *)nullptr, S.sL, S.sLinv);
+}
+
+// Step sweeps over the blocks [kfirst, nb).  Per block two launches: (N) the 512 x 512 tile that carries the previous
+// block's solution into this block's rows/columns, spread over 8-16 workgroups; (F) workgroup 0 solves the block while
+// the other workgroups stream the previous block's far panel.
+template <typename T>
+static void steps_fwd(const Sweep<T> &S, int64_t kfirst)
+{
+    const int64_t n = S.n, nb = S.nb();
+    auto launch = [&](int64_t far_rows, int64_t nn, int64_t k0, int jb, int64_t p0, int pjb, int64_t far0) {
+        hipLaunchKernelGGL((trsv_fwd_fused<T>), dim3((unsigned)(1 + cdiv(far_rows, 64)), S.nbt), dim3(TBT), 0, S.st, S.L, S.ldl,
+                           S.Linv, S.b, S.x, nn, k0, jb, p0, pjb, far0, S.aligned, S.sL, S.sLinv, S.sv);
+    };
+    for (int64_t blk = kfirst; blk < nb; ++blk) {
+        const int64_t k0 = blk * TB, p0 = std::max<int64_t>(blk - 1, 0) * TB;
+        const int jb = S.width(blk), pjb = blk > 0 ? TB : 0;
+        if (blk > 0) launch(jb, k0 + jb, k0, 0, p0, pjb, k0);                               // (N)
+        launch(blk > 0 ? n - (k0 + jb) : 0, n, k0, jb, p0, pjb, k0 + jb);                   // (F)
+    }
+    // trapezoid: the last block's panel below the triangle
+    if (n > S.ncols) launch(n - S.ncols, n, S.ncols, 0, (nb - 1) * TB, S.width(nb - 1), S.ncols);
+}
+
+template <typename T>
+static void steps_bwd(const Sweep<T> &S, int64_t kfirst)
+{
+    const int64_t nb = S.nb();
+    for (int64_t blk = nb - 1; blk >= kfirst; --blk) {
+        const int64_t k0 = blk * TB, q0 = k0 + TB;
+        const int jb = S.width(blk), qjb = blk + 1 < nb ? S.width(blk + 1) : 0;
+        if (qjb > 0)
+            hipLaunchKernelGGL((trsv_bwd_fused<T, 32>), dim3((unsigned)(1 + cdiv(jb, 32)), S.nbt), dim3(TBT), 0, S.st, S.L,
+                               S.ldl, S.Linv, S.b, S.x, k0, 0, q0, qjb, k0, k0 + jb, S.aligned, S.sL, S.sLinv, S.sv);
+        hipLaunchKernelGGL((trsv_bwd_fused<T, 128>), dim3((unsigned)(1 + (qjb > 0 ? cdiv(k0, 128) : 0)), S.nbt),
+                           dim3(TBT), 0, S.st, S.L, S.ldl, S.Linv, S.b, S.x, k0, jb, q0, qjb, (int64_t)0, k0, S.aligned,
+                           S.sL, S.sLinv, S.sv);
+    }
+}
+
+// Operator sweeps (one system, square): one launch per full block.  A ragged last block is left to the step sweeps.
+constexpr int NCH = OB / (TBT / OPL);      // chain workgroups of a block
+
+template <typename T>
+static void ops_fwd(const Sweep<T> &S, const OpsView<T> &V)
+{
+    for (int64_t k = 0; k < V.nfull; ++k) {
+        const int64_t k0 = k * OB, far0 = k0 + OB;
+        const int64_t nfar = k > 0 ? cdiv(S.n - far0, 64) : 0;
+        hipLaunchKernelGGL((trsv_op_kernel<T, true>), dim3((unsigned)(NCH + nfar)), dim3(TBT), 0, S.st, V.W(k),
+                           k > 0 ? V.Tf(k) : (const T *)nullptr, S.L, S.ldl, S.b, S.x, S.n, k0, k0 - OB, k > 0 ? OB : 0, far0, S.n, NCH, 1);
+    }
+}
+
+// blocks kend - 1 .. 0; block kend (steps, or the ragged one) is solved already
+template <typename T>
+static void ops_bwd(const Sweep<T> &S, const OpsView<T> &V, int64_t kend)
+{
+    for (int64_t k = kend - 1; k >= 0; --k) {
+        const int64_t k0 = k * OB, q0 = k0 + OB;
+        const int qjb = (k + 1 < V.nfull) ? OB : (int)(S.n - q0);
+        const int64_t nfar = qjb > 0 ? cdiv(k0, 128) : 0;
+        hipLaunchKernelGGL((trsv_op_kernel<T, false>), dim3((unsigned)(NCH + nfar)), dim3(TBT), 0, S.st, V.Wt(k),
+                           qjb > 0 ? V.Tb(k) : (const T *)nullptr, S.L, S.ldl, S.b, S.x, S.n, k0, q0, qjb, (int64_t)0, k0, NCH, 1);
+    }
 }
 
 template <typename T>
 static int trsv_t(const T *L, int64_t n, int64_t ldl, T *b, T *x, int transpose, hipStream_t st,
-                  int64_t ncols = -1, const Batch *bt = nullptr, TrsvOps *ops = nullptr, int dtype = GPX_F64)
+                  int64_t ncols = -1, const Batch *bt = nullptr, TrsvOps *ops = nullptr)
 {
-    // bt: bt->count systems solved by the same launches; sA = stride of L, sB = stride of b and x
-    const unsigned nbt = (unsigned)(bt ? bt->count : 1);
-    const int64_t sL = bt ? bt->sA : 0, sv = bt ? bt->sB : 0;
+    constexpr int dtype = sizeof(T) == 8 ? GPX_F64 : GPX_F32;
     // ncols < n (forward only): the matrix is a trapezoid -- an ncols x ncols lower
     // triangle on top of (n - ncols) further rows; x[0:ncols] is solved and the
     // remaining right-hand side b[ncols:n] is reduced by L[ncols:n, 0:ncols] x.
     if (ncols < 0 || ncols > n) ncols = n;
-    ProfScope prof(PC_TRSV, ((double)n * ncols - 0.5 * (double)ncols * (ncols - 1)) * sizeof(T) * nbt, st);
-    const int64_t nblk = cdiv(ncols, SB);
-    const int64_t sLinv = nblk * SB * SB;
+    Sweep<T> S;
+    S.L = L; S.n = n; S.ldl = ldl; S.ncols = ncols; S.b = b; S.x = x; S.st = st;
+    // bt: bt->count systems solved by the same launches; sA = stride of L, sB = stride of b and x
+    S.nbt = (unsigned)(bt ? bt->count : 1); S.sL = bt ? bt->sA : 0; S.sv = bt ? bt->sB : 0;
+    ProfScope prof(PC_TRSV, ((double)n * ncols - 0.5 * (double)ncols * (ncols - 1)) * sizeof(T) * S.nbt, st);
+    S.sLinv = cdiv(ncols, SB) * SB * SB;
     void *scr = nullptr;
-    GPX_TRY(g_scr.get((size_t)nbt * sLinv * sizeof(T), &scr));
-    T *Linv = (T *)scr;
-    const int aligned = (((uintptr_t)L) % (2 * sizeof(T)) == 0) && (ldl % 2 == 0);
-    const int ablate = 0;                          // (timing-only ablations of the step kernels: compile-time edits now)
-    const int64_t nb = cdiv(ncols, TB);
-    auto width = [&](int64_t blk) { return (int)std::min<int64_t>(TB, ncols - blk * TB); };
-    // operator form: square systems of at least two full blocks, aligned rows, one system
-    const bool prebuilt = ops && ops->valid && ops->mem.p && n % OB == 0 && ops->mem.bytes >= trsv_ops_bytes(dtype, n);
+    GPX_TRY(g_scr.get((size_t)S.nbt * S.sLinv * sizeof(T), &scr));
+    S.Linv = (T *)scr;
+    S.aligned = (((uintptr_t)L) % (2 * sizeof(T)) == 0) && (ldl % 2 == 0);
+    // the route (table above)
+    const bool usable = !bt && ncols == n && ops_usable(dtype, L, ldl);
+    const bool cached = ops && ops->mem.p && n % OB == 0 && ops->mem.bytes >= trsv_ops_bytes(dtype, n);
+    const bool prebuilt = cached && ops->valid;
     // operators of the LEADING blocks only (built beside the factorisation, gpx_gp_fit; the caller has ordered `st` behind
     // them): a backward sweep takes the trailing blocks by steps and switches to one launch per block where they begin
-    const int64_t kpart = (ops && !ops->valid && ops->mem.p && ops->built > 0 && n % OB == 0 && transpose && !bt && ncols == n &&
-                           ops->mem.bytes >= trsv_ops_bytes(dtype, n) && trsv_ops_enabled() && aligned &&
-                           ldl % (16 / (int64_t)sizeof(T)) == 0 && ((uintptr_t)L) % 16 == 0) ? std::min(ops->built, n / OB) : 0;
-    if (kpart == 0 && trsv_ops_enabled() && !bt && ncols == n && (n >= trsv_ops_min_n() || prebuilt) && aligned &&
-        ldl % (16 / (int64_t)sizeof(T)) == 0 && ((uintptr_t)L) % 16 == 0) {
-        const int64_t nfull = n / OB, rag = n - nfull * OB, BS = (int64_t)OB * OB;
+    const int64_t kpart = (usable && cached && !ops->valid && ops->built > 0 && transpose) ? std::min(ops->built, n / OB) : 0;
+    if (kpart == 0 && usable && (n >= trsv_ops_min_n() || prebuilt)) {
         route_hit(RT_TRSV_OPS);
         void *buf = nullptr;
-        bool fresh = true;
         if (ops) {                                                   // the caller's cache (one factor, many solves)
             bool grew = false;
             GPX_TRY(ops->mem.reserve(trsv_ops_bytes(dtype, n), st, &grew));
             if (grew) ops->invalidate();
             buf = ops->mem.p;
-            fresh = !ops->valid;
         } else {
             GPX_TRY(g_ops.get(trsv_ops_bytes(dtype, n), &buf));
         }
+        const OpsView<T> V(buf, n);
         // (a factor whose leading blocks already have their operators: only the rest)
-        if (fresh) GPX_TRY(trsv_ops_prepare<T>(L, n, ldl, buf, st, dtype, ops ? std::min(ops->built, nfull) : 0, nfull));
-        if (ops) { ops->valid = true; ops->built = nfull; }
-        const T *W = (const T *)buf, *Wt = W + nfull * BS, *Tf = Wt + 2 * nfull * BS, *Tb = Tf + nfull * BS;
-        const int NCH = OB / (TBT / 32);        // 32 lanes per row (the 8-lane form was measured slower and went in round 6)
+        if (!ops || !ops->valid) GPX_TRY(trsv_ops_prepare<T>(L, n, ldl, buf, st, ops ? std::min(ops->built, V.nfull) : 0, V.nfull));
+        if (ops) { ops->valid = true; ops->built = V.nfull; }
+        const bool ragged = n > V.nfull * OB;
         if (!transpose) {
-            for (int64_t k = 0; k < nfull; ++k) {
-                const int64_t k0 = k * OB, far0 = k0 + OB;
-                const int64_t nfar = k > 0 ? cdiv(n - far0, 64) : 0;
-                hipLaunchKernelGGL((trsv_op_kernel<T, true, 32>), dim3((unsigned)(NCH + nfar)), dim3(TBT), 0, st, W + k * BS,
-                                       k > 0 ? Tf + k * BS : (const T *)nullptr, L, ldl, b, x, n, k0, k0 - OB, k > 0 ? OB : 0, far0, n,
-                                       NCH, aligned);
-            }
-            if (rag > 0) {                                           // ragged last block: the near tile, then the old chain
-                const int64_t k0 = nfull * OB, p0 = k0 - OB;
-                hipLaunchKernelGGL((inv64_kernel<T>), dim3((unsigned)nblk, nbt), dim3(256), 0, st, L, ldl, ncols, Linv, 1,
-                                   (T *)nullptr, (T *)nullptr, sL, sLinv);
-                hipLaunchKernelGGL((trsv_fwd_fused<T>), dim3((unsigned)(1 + cdiv(rag, 64))), dim3(TBT), 0, st, L, ldl, Linv, b, x,
-                                   n, k0, 0, p0, OB, k0, aligned, ablate, sL, sLinv, sv);
-                hipLaunchKernelGGL((trsv_fwd_fused<T>), dim3(1), dim3(TBT), 0, st, L, ldl, Linv, b, x, n, k0, (int)rag, p0, OB, n,
-                                   aligned, ablate, sL, sLinv, sv);
-            }
+            ops_fwd(S, V);
+            if (ragged) { inv64_blocks(S, 0, 1); steps_fwd(S, V.nfull); }
         } else {
-            if (rag > 0) {
-                const int64_t k0 = nfull * OB;
-                hipLaunchKernelGGL((inv64_kernel<T>), dim3((unsigned)nblk, nbt), dim3(256), 0, st, L, ldl, ncols, Linv, 0,
-                                   (T *)nullptr, (T *)nullptr, sL, sLinv);
-                hipLaunchKernelGGL((trsv_bwd_fused<T, 128>), dim3(1), dim3(TBT), 0, st, L, ldl, Linv, b, x, k0, (int)rag, k0 + OB, 0,
-                                   (int64_t)0, k0, aligned, ablate, sL, sLinv, sv);
-            }
-            for (int64_t k = nfull - 1; k >= 0; --k) {
-                const int64_t k0 = k * OB, q0 = k0 + OB;
-                const int qjb = (k + 1 < nfull) ? OB : (int)rag;
-                const int64_t nfar = qjb > 0 ? cdiv(k0, 128) : 0;
-                hipLaunchKernelGGL((trsv_op_kernel<T, false, 32>), dim3((unsigned)(NCH + nfar)), dim3(TBT), 0, st, Wt + k * BS,
-                                       qjb > 0 ? Tb + k * BS : (const T *)nullptr, L, ldl, b, x, n, k0, q0, qjb, (int64_t)0, k0, NCH,
-                                       aligned);
-            }
+            if (ragged) { inv64_blocks(S, 0, 0); steps_bwd(S, V.nfull); }
+            ops_bwd(S, V, V.nfull);
         }
-        GPX_LAUNCH_CHECK();
-        return GPX_OK;
-    }
-    // Per block two launches: (N) the 512 x 512 tile that carries the previous block's
-    // solution into this block's rows/columns, spread over 8-16 workgroups; (F) workgroup 0
-    // solves the block while the other workgroups stream the previous block's far panel.
-    route_hit(RT_TRSV_STEPS);
-    if (!transpose) {
-        hipLaunchKernelGGL((inv64_kernel<T>), dim3((unsigned)nblk, nbt), dim3(256), 0, st, L, ldl, ncols, Linv, 1,
-                           (T *)nullptr, (T *)nullptr, sL, sLinv);
-        for (int64_t blk = 0; blk < nb; ++blk) {
-            const int64_t k0 = blk * TB, p0 = std::max<int64_t>(blk - 1, 0) * TB;
-            const int jb = width(blk), pjb = blk > 0 ? TB : 0;
-            if (blk > 0)
-                hipLaunchKernelGGL((trsv_fwd_fused<T>), dim3((unsigned)(1 + cdiv(jb, 64)), nbt), dim3(TBT), 0, st, L, ldl,
-                                   Linv, b, x, k0 + jb, k0, 0, p0, pjb, k0, aligned, ablate, sL, sLinv, sv);
-            const int64_t far = blk > 0 ? n - (k0 + jb) : 0;
-            hipLaunchKernelGGL((trsv_fwd_fused<T>), dim3((unsigned)(1 + cdiv(far, 64)), nbt), dim3(TBT), 0, st, L, ldl,
-                               Linv, b, x, n, k0, jb, p0, pjb, k0 + jb, aligned, ablate, sL, sLinv, sv);
-        }
-        if (n > ncols)          // trapezoid: the last block's panel below the triangle
-            hipLaunchKernelGGL((trsv_fwd_fused<T>), dim3((unsigned)(1 + cdiv(n - ncols, 64)), nbt), dim3(TBT), 0, st, L,
-                               ldl, Linv, b, x, n, ncols, 0, (nb - 1) * TB, width(nb - 1), ncols, aligned, ablate,
-                               sL, sLinv, sv);
-    } else {
-        // (kpart > 0: blocks [kpart, nb) here, the leading kpart blocks by their operators below)
-        const int64_t b64 = kpart * (OB / SB);
-        hipLaunchKernelGGL((inv64_kernel<T>), dim3((unsigned)(nblk - b64), nbt), dim3(256), 0, st, L + b64 * SB * (ldl + 1), ldl,
-                           ncols - b64 * SB, Linv + b64 * SB * SB, 0, (T *)nullptr, (T *)nullptr, sL, sLinv);
-        for (int64_t blk = nb - 1; blk >= kpart; --blk) {
-            const int64_t k0 = blk * TB, q0 = k0 + TB;
-            const int jb = width(blk), qjb = blk + 1 < nb ? width(blk + 1) : 0;
-            if (qjb > 0)
-                hipLaunchKernelGGL((trsv_bwd_fused<T, 32>), dim3((unsigned)(1 + cdiv(jb, 32)), nbt), dim3(TBT), 0, st, L,
-                                   ldl, Linv, b, x, k0, 0, q0, qjb, k0, k0 + jb, aligned, ablate, sL, sLinv, sv);
-            hipLaunchKernelGGL((trsv_bwd_fused<T, 128>), dim3((unsigned)(1 + (qjb > 0 ? cdiv(k0, 128) : 0)), nbt),
-                               dim3(TBT), 0, st, L, ldl, Linv, b, x, k0, jb, q0, qjb, (int64_t)0, k0, aligned,
-                               ablate, sL, sLinv, sv);
-        }
+    } else if (!transpose) {
+        route_hit(RT_TRSV_STEPS);
+        inv64_blocks(S, 0, 1);
+        steps_fwd(S, 0);
+    } else {                                   // steps for the blocks [kpart, nb); the mixed sweep (kpart > 0): then operators
+        route_hit(RT_TRSV_STEPS);
+        inv64_blocks(S, kpart * (OB / SB), 0);
+        steps_bwd(S, kpart);
         if (kpart > 0) {
             route_hit(RT_TRSV_OPS);
-            const int64_t nfull = n / OB, BS = (int64_t)OB * OB;
-            const T *W = (const T *)ops->mem.p, *Wt = W + nfull * BS, *Tb = Wt + 3 * nfull * BS;
-            const int NCH = OB / (TBT / 32);
-            for (int64_t k = kpart - 1; k >= 0; --k) {
-                const int64_t k0 = k * OB, q0 = k0 + OB;
-                hipLaunchKernelGGL((trsv_op_kernel<T, false, 32>), dim3((unsigned)(NCH + cdiv(k0, 128))), dim3(TBT), 0, st, Wt + k * BS,
-                                       Tb + k * BS, L, ldl, b, x, n, k0, q0, OB, (int64_t)0, k0, NCH, aligned);
-            }
+            ops_bwd(S, OpsView<T>(ops->mem.p, n), kpart);
         }
     }
     GPX_LAUNCH_CHECK();
@@ -739,27 +777,20 @@ int trsv_lower(int dtype, const void *L, int64_t n, int64_t ldl, void *b, void *
 {
     if (n <= 0) return GPX_OK;
     if (dtype == GPX_F64)
-        return trsv_t<double>((const double *)L, n, ldl, (double *)b, (double *)x, transpose, st, -1, bt, ops, dtype);
-    return trsv_t<float>((const float *)L, n, ldl, (float *)b, (float *)x, transpose, st, -1, bt, ops, dtype);
+        return trsv_t<double>((const double *)L, n, ldl, (double *)b, (double *)x, transpose, st, -1, bt, ops);
+    return trsv_t<float>((const float *)L, n, ldl, (float *)b, (float *)x, transpose, st, -1, bt, ops);
 }
 
 int trsv_ops_build(int dtype, const void *L, int64_t n, int64_t ldl, TrsvOps *ops, hipStream_t st)
 {
-    if (!ops || n < OB || n % OB != 0 || !trsv_ops_enabled() || ldl % (16 / (int64_t)esize(dtype)) != 0 || ((uintptr_t)L) % 16 != 0)
-        return GPX_OK;                                               // not eligible: the solve takes the step route
+    if (!ops || !trsv_ops_whole_blocks(n) || !ops_usable(dtype, L, ldl)) return GPX_OK;   // the solve takes the step route
     GPX_TRY(ops->mem.reserve(trsv_ops_bytes(dtype, n), st));
     ops->invalidate();
-    if (dtype == GPX_F64) GPX_TRY(trsv_ops_prepare<double>((const double *)L, n, ldl, ops->mem.p, st, dtype));
-    else GPX_TRY(trsv_ops_prepare<float>((const float *)L, n, ldl, ops->mem.p, st, dtype));
+    if (dtype == GPX_F64) GPX_TRY(trsv_ops_prepare<double>((const double *)L, n, ldl, ops->mem.p, st));
+    else GPX_TRY(trsv_ops_prepare<float>((const float *)L, n, ldl, ops->mem.p, st));
     ops->valid = true;
     ops->built = n / OB;
     return GPX_OK;
-}
-
-bool trsv_ops_ahead_ok(int dtype, const void *L, int64_t n, int64_t ldl)
-{
-    return n >= 2 * OB && n % OB == 0 && trsv_ops_enabled() && ldl % (16 / (int64_t)esize(dtype)) == 0 && ((uintptr_t)L) % 16 == 0 &&
-           ((uintptr_t)L) % (2 * esize(dtype)) == 0 && ldl % 2 == 0;
 }
 
 int trsv_ops_build_upto(int dtype, const void *L, int64_t n, int64_t ldl, TrsvOps *ops, int64_t kend, hipStream_t st)
@@ -772,8 +803,8 @@ int trsv_ops_build_upto(int dtype, const void *L, int64_t n, int64_t ldl, TrsvOp
         ops->valid = false;
     }
     if (kend <= ops->built || !ops->mem.p) return GPX_OK;
-    if (dtype == GPX_F64) GPX_TRY(trsv_ops_prepare<double>((const double *)L, n, ldl, ops->mem.p, st, dtype, ops->built, kend));
-    else GPX_TRY(trsv_ops_prepare<float>((const float *)L, n, ldl, ops->mem.p, st, dtype, ops->built, kend));
+    if (dtype == GPX_F64) GPX_TRY(trsv_ops_prepare<double>((const double *)L, n, ldl, ops->mem.p, st, ops->built, kend));
+    else GPX_TRY(trsv_ops_prepare<float>((const float *)L, n, ldl, ops->mem.p, st, ops->built, kend));
     ops->built = kend;
     if (kend == nfull) ops->valid = true;
     return GPX_OK;
@@ -784,8 +815,8 @@ int trsv_lower_cols(int dtype, const void *L, int64_t n, int64_t ldl, int64_t nc
 {
     if (n <= 0 || ncols <= 0) return GPX_OK;
     if (dtype == GPX_F64)
-        return trsv_t<double>((const double *)L, n, ldl, (double *)b, (double *)x, 0, st, ncols, nullptr, nullptr, dtype);
-    return trsv_t<float>((const float *)L, n, ldl, (float *)b, (float *)x, 0, st, ncols, nullptr, nullptr, dtype);
+        return trsv_t<double>((const double *)L, n, ldl, (double *)b, (double *)x, 0, st, ncols);
+    return trsv_t<float>((const float *)L, n, ldl, (float *)b, (float *)x, 0, st, ncols);
 }
 
 // y[c] -= sum_r Lp[r, c] * x[r]   (c < ncols <= 1024, r < rows): the transposed
@@ -842,6 +873,43 @@ int panel_gemv_t(int dtype, const void *Lp, int64_t ldl, int64_t rows, int64_t n
     return GPX_OK;
 }
 
+static thread_local ThreadScratch g_trsm_scr;   // the operator route: one m x 512 block of X per system
+
+// Operator route of X <- X L^-T for `count` systems in LOCK-STEP (whole blocks, every system's block operators complete in
+// ops_base + i * sO): the substitution inside a 512-block,
+//   X[:, blk] <- X[:, blk] inv(L_kk)^T,
+// is ONE product with W_k = inv(L_kk) (into a scratch block, copied back) instead of eight 64-wide substitutions with
+// seven small products between them -- 16 latency-bound launches a block, which were most of a posterior covariance
+// (n = 8192, m = 1024: cov 11.0 -> see DESIGN 3.3).  Every launch covers all systems -- at n = 8192 a single system's far
+// update is 1 - 2 rounds of tiles (32 x 32 at most), eight of them fill the chip.  L, X, the operators and the scratch
+// block are sL / sX / sO / (m * 512) elements apart.
+static int trsm_right_lt_ops(int dtype, const void *L, int64_t sL, int64_t n, int64_t ldl, void *X, int64_t sX, int64_t m, int64_t ldx,
+                             hipStream_t st, int x_upper, const void *ops_base, int64_t sO, int count)
+{
+    route_hit(RT_TRSM_OPS);
+    const size_t es = esize(dtype);
+    const int64_t sS = m * OB;
+    void *scr = nullptr;
+    GPX_TRY(g_trsm_scr.get((size_t)count * sS * es, &scr));
+    for (int64_t k = 0; k < n / OB; ++k) {
+        const int64_t k0 = k * OB, r = k0 + OB;
+        const int64_t me = x_upper ? std::min(m, r) : m;
+        char *Xk = (char *)X + k0 * es;
+        const void *Wk = dtype == GPX_F64 ? (void *)OpsView<double>(ops_base, n).W(k) : (void *)OpsView<float>(ops_base, n).W(k);
+        Batch b1; b1.count = count; b1.sA = sX; b1.sB = sO; b1.sC = sS;
+        GPX_TRY(gemm_nt(dtype, me, OB, OB, Xk, ldx, Wk, OB, scr, OB, 1.0, GPX_FULL, 0, 0, st, 1, 0, &b1));
+        for (int i = 0; i < count; ++i)
+            GPX_HIP(hipMemcpy2DAsync(Xk + (size_t)i * sX * es, (size_t)ldx * es, (const char *)scr + (size_t)i * sS * es, (size_t)OB * es,
+                                     (size_t)OB * es, (size_t)me, hipMemcpyDeviceToDevice, st));
+        if (r < n) {
+            Batch b2; b2.count = count; b2.sA = sX; b2.sB = sL; b2.sC = sX;
+            GPX_TRY(gemm_nt(dtype, me, n - r, OB, Xk, ldx, (const char *)L + (r * ldl + k0) * es, ldl, (char *)X + r * es, ldx,
+                            -1.0, GPX_FULL, 0, 0, st, 0, 0, &b2));
+        }
+    }
+    return GPX_OK;
+}
+
 // X (m x n) <- X * L^-T, blocked and RIGHT-looking: after the columns of a block are
 // solved they are applied at once to every remaining column,
 //   X[:, r:] -= X[:, blk] * L[r:, blk]^T      (m x (n - r) output, K = block width),
@@ -851,40 +919,15 @@ int panel_gemv_t(int dtype, const void *Lp, int64_t ldl, int64_t rows, int64_t n
 // x_upper: X is upper triangular on entry (the identity, when L^-T itself is wanted): rows beyond
 // the current block are still zero in its columns, so every step works on the leading k0 + kb rows
 // only -- a third of the flops.
-static thread_local ThreadScratch g_trsm_scr;   // trsm_right_lt's operator route: one m x 512 block of X
-
 int trsm_right_lt(int dtype, const void *L, int64_t n, int64_t ldl, void *X, int64_t m, int64_t ldx,
                   hipStream_t st, int x_upper, TrsvOps *ops)
 {
     if (n <= 0 || m <= 0) return GPX_OK;
     const size_t es = esize(dtype);
-    // Operator route (the caller's TrsvOps of THIS factor, n a multiple of 512): the substitution inside a 512-block,
-    //   X[:, blk] <- X[:, blk] inv(L_kk)^T,
-    // is ONE product with W_k = inv(L_kk) (into a scratch block, copied back) instead of eight 64-wide substitutions with
-    // seven small products between them -- 16 latency-bound launches a block, which were most of a posterior covariance
-    // (n = 8192, m = 1024: cov 11.0 -> see DESIGN 3.3).  The operators are completed here if the factor has only some.
-    if (ops && trsv_ops_ahead_ok(dtype, L, n, ldl) && tune().trsm_ops != 0 && ldx % (16 / (int64_t)es) == 0 &&
-        ((uintptr_t)X) % 16 == 0) {
-        const int64_t nfull = n / OB, BS = (int64_t)OB * OB;
-        if (!ops->valid) GPX_TRY(trsv_ops_build_upto(dtype, L, n, ldl, ops, nfull, st));
-        if (ops->valid && ops->mem.p) {
-            route_hit(RT_TRSM_OPS);
-            void *scr = nullptr;
-            GPX_TRY(g_trsm_scr.get((size_t)m * OB * es, &scr));
-            const char *W = (const char *)ops->mem.p;
-            for (int64_t k = 0; k < nfull; ++k) {
-                const int64_t k0 = k * OB, r = k0 + OB;
-                const int64_t me = x_upper ? std::min(m, r) : m;
-                char *Xk = (char *)X + k0 * es;
-                GPX_TRY(gemm_nt(dtype, me, OB, OB, Xk, ldx, W + (size_t)k * BS * es, OB, scr, OB, 1.0, GPX_FULL, 0, 0, st, 1));
-                GPX_HIP(hipMemcpy2DAsync(Xk, (size_t)ldx * es, scr, (size_t)OB * es, (size_t)OB * es, (size_t)me,
-                                         hipMemcpyDeviceToDevice, st));
-                if (r < n)
-                    GPX_TRY(gemm_nt(dtype, me, n - r, OB, Xk, ldx, (const char *)L + (r * ldl + k0) * es, ldl, (char *)X + r * es, ldx,
-                                    -1.0, GPX_FULL, 0, 0, st));
-            }
-            return GPX_OK;
-        }
+    // Operator route (the caller's TrsvOps of THIS factor): completed here if the factor has only some.
+    if (ops && trsm_ops_ok(dtype, L, n, ldl) && ldx % (16 / (int64_t)es) == 0 && ((uintptr_t)X) % 16 == 0) {
+        if (!ops->valid) GPX_TRY(trsv_ops_build_upto(dtype, L, n, ldl, ops, n / OB, st));
+        if (ops->valid && ops->mem.p) return trsm_right_lt_ops(dtype, L, 0, n, ldl, X, 0, m, ldx, st, x_upper, ops->mem.p, 0, 1);
     }
     const int64_t NB = n >= 8192 ? 512 : 256;
     auto Lp = [&](int64_t r, int64_t c) { return (const char *)L + (r * ldl + c) * es; };
@@ -907,36 +950,37 @@ int trsm_right_lt(int dtype, const void *L, int64_t n, int64_t ldl, void *X, int
     return GPX_OK;
 }
 
-// X <- X L^-T for `count` systems in LOCK-STEP (operator route only: n a multiple of 512, every system's block operators
-// complete in ops_base + i * sO): every launch covers all systems -- at n = 8192 a single system's far update is 1 - 2 rounds
-// of tiles (32 x 32 at most), eight of them fill the chip.  L, X, the operators and the scratch block are sL / sX / sO / (m * 512)
-// elements apart.  Same products, same order per system as trsm_right_lt.
-int trsm_right_lt_batch(int dtype, const void *L, int64_t sL, int64_t n, int64_t ldl, void *X, int64_t sX, int64_t m, int64_t ldx,
-                        hipStream_t st, int x_upper, const void *ops_base, int64_t sO, int count)
+template <typename T>
+__global__ void eye_kernel(T *__restrict__ X, int64_t n, int64_t ld)
 {
-    if (n <= 0 || m <= 0 || count <= 0) return GPX_OK;
-    const size_t es = esize(dtype);
-    if (n % OB != 0 || !trsv_ops_ahead_ok(dtype, L, n, ldl)) { set_error("trsm_right_lt_batch: n must be a multiple of %d", OB); return GPX_ERR_ARG; }
-    route_hit(RT_TRSM_OPS);
-    const int64_t nfull = n / OB, BS = (int64_t)OB * OB, sS = m * OB;
-    void *scr = nullptr;
-    GPX_TRY(g_trsm_scr.get((size_t)count * sS * es, &scr));
-    for (int64_t k = 0; k < nfull; ++k) {
-        const int64_t k0 = k * OB, r = k0 + OB;
-        const int64_t me = x_upper ? std::min(m, r) : m;
-        char *Xk = (char *)X + k0 * es;
-        Batch b1; b1.count = count; b1.sA = sX; b1.sB = sO; b1.sC = sS;
-        GPX_TRY(gemm_nt(dtype, me, OB, OB, Xk, ldx, (const char *)ops_base + (size_t)k * BS * es, OB, scr, OB, 1.0, GPX_FULL, 0, 0, st, 1, 0, &b1));
-        for (int i = 0; i < count; ++i)
-            GPX_HIP(hipMemcpy2DAsync(Xk + (size_t)i * sX * es, (size_t)ldx * es, (const char *)scr + (size_t)i * sS * es, (size_t)OB * es,
-                                     (size_t)OB * es, (size_t)me, hipMemcpyDeviceToDevice, st));
-        if (r < n) {
-            Batch b2; b2.count = count; b2.sA = sX; b2.sB = sL; b2.sC = sX;
-            GPX_TRY(gemm_nt(dtype, me, n - r, OB, Xk, ldx, (const char *)L + (r * ldl + k0) * es, ldl, (char *)X + r * es, ldx,
-                            -1.0, GPX_FULL, 0, 0, st, 0, 0, &b2));
+    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= ld) return;
+    for (int64_t r = blockIdx.y; r < n; r += gridDim.y) X[r * ld + c] = (c == r) ? (T)1 : (T)0;
+}
+
+// X = I L^-T = L^-T ; K^-1 = L^-T L^-1 = X X^T   (gp/gp.py:311-312; gpx_common.h for the arguments)
+int inv_from_factor(int dtype, const void *L, int64_t n, int64_t ldl, void *X, void *W, int tri, hipStream_t st,
+                    TrsvOps *ops, int count, int64_t sL, void *group_ops)
+{
+    const size_t es = esize(dtype), nl = (size_t)n * ldl * es, ob = trsv_ops_bytes(dtype, n);
+    if (count > 1 && !trsm_ops_ok(dtype, L, n, ldl)) { set_error("inv_from_factor: a lock-step group needs the operator route"); return GPX_ERR_ARG; }
+    dim3 grid((unsigned)cdiv(ldl, 256), (unsigned)std::min<int64_t>(n, 32768)), block(256);
+    for (int i = 0; i < count; ++i) {
+        void *Xi = (char *)X + (size_t)i * nl;
+        if (dtype == GPX_F64) hipLaunchKernelGGL((eye_kernel<double>), grid, block, 0, st, (double *)Xi, n, ldl);
+        else hipLaunchKernelGGL((eye_kernel<float>), grid, block, 0, st, (float *)Xi, n, ldl);
+        GPX_LAUNCH_CHECK();
+        if (count > 1) {
+            TrsvOps o = TrsvOps::view((char *)group_ops + (size_t)i * ob, ob);
+            GPX_TRY(trsv_ops_build_upto(dtype, (const char *)L + (size_t)i * sL * es, n, ldl, &o, n / OB, st));
         }
     }
-    return GPX_OK;
+    GPX_HIP(hipMemsetAsync(W, 0, (size_t)count * nl, st));
+    const int64_t sX = (int64_t)(nl / es);
+    if (count > 1) GPX_TRY(trsm_right_lt_ops(dtype, L, sL, n, ldl, X, sX, n, ldl, st, 1, group_ops, (int64_t)(ob / es), count));
+    else GPX_TRY(trsm_right_lt(dtype, L, n, ldl, X, n, ldl, st, 1, ops));
+    Batch bw; bw.count = count; bw.sA = bw.sB = bw.sC = sX;
+    return gemm_nt(dtype, n, n, n, X, ldl, X, ldl, W, ldl, 1.0, tri, 0, 0, st, 0, 1, count > 1 ? &bw : nullptr);
 }
 
 // ---- reductions (single workgroup, fixed order => deterministic) ----------
@@ -1043,10 +1087,6 @@ int gpx_d_dot(int dtype, const void *a, const void *b, int64_t n, double *out_de
     GPX_ARG(n >= 0 && out_dev && (n == 0 || (a && b)), "bad arguments");
     return dot(dtype, a, b, n, out_dev, S(stream));
 }
-
-}  // extern "C"
-
-extern "C" {
 
 int gpx_d_trsv_lower_cols(int dtype, const void *L, int64_t n, int64_t ldl, int64_t ncols, void *b,
                           void *x, void *stream)

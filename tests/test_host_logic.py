@@ -89,6 +89,30 @@ def test_device_memory_has_one_owner():
     assert len(call.findall(open(os.path.join(csrc, "gpx_mem.h")).read())) == 2
 
 
+def test_solve_operators_keep_one_launch_site_and_one_block_width():
+    """The block operators of the triangular solves (csrc/gpx_solve.hip, "operator form") are on the path of every
+    solve, covariance and derivative call.  Two things a later edit could undo without any result changing at once:
+    the operator step is launched from ONE forward and ONE backward sweep (the mixed backward sweep and the ragged last
+    block call the same pieces; there used to be a second copy of the backward loop), and the width of an operator
+    block is known to gpx_solve.hip and the one constant of gpx_common.h -- the units that use the operators ask
+    trsv_ops_nblocks / trsv_ops_whole_blocks instead of dividing by a literal."""
+    csrc = os.path.join(ROOT, "gaussian_processes_amd", "csrc")
+
+    def code(f):        # without comments and string literals
+        src = open(os.path.join(csrc, f)).read()
+        return re.sub(r'"(?:\\.|[^"\\])*"', '""', re.sub(r"//[^\n]*", "", src))
+    solve = code("gpx_solve.hip")
+    assert len(re.findall(r"hipLaunchKernelGGL\(\(trsv_op_kernel<T, true>\)", solve)) == 1
+    assert len(re.findall(r"hipLaunchKernelGGL\(\(trsv_op_kernel<T, false>\)", solve)) == 1
+    assert len(re.findall(r"\btrsv_op_kernel<", solve)) == 2
+    assert len(re.findall(r"\bTRSV_OPS_BLOCK\s*=\s*512\b", code("gpx_common.h"))) == 1
+    users = [f for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".h")) and f not in ("gpx_solve.hip", "gpx_common.h")
+             and re.search(r"\b(?:TrsvOps|trsv_ops_\w+|trsm_ops_ok)\b", code(f))]
+    assert "gpx_gp.hip" in users and "gpx_mg.hip" in users
+    for f in users:
+        assert not re.search(r"\b512\b", code(f)), f
+
+
 def test_no_cpu_fallback_without_gpu():
     if _lib.device_count() > 0:
         pytest.skip("a GPU is present")
