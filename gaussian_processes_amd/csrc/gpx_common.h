@@ -6,6 +6,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <math.h>
+#include <vector>
 
 #include "../../include/gpx.h"
 #include "gpx_tune.h"
@@ -59,6 +60,32 @@ static inline hipStream_t S(void *s) { return (hipStream_t)s; }
 static inline size_t esize(int dtype) { return dtype == GPX_F64 ? 8 : 4; }
 static inline int64_t round_up(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
 static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+// a "now" on `to` after everything enqueued so far on `from`, through an event the caller owns
+static inline int order(hipEvent_t e, hipStream_t from, hipStream_t to)
+{
+    GPX_HIP(hipEventRecord(e, from));
+    GPX_HIP(hipStreamWaitEvent(to, e, 0));
+    return GPX_OK;
+}
+// Sync events (no timing) handed out in order, created on demand and reused after rewind().  ONE owner each (a thread's
+// look-ahead slot, a multi-GPU handle), who rewinds only when nothing that waits for an event of the round before is pending.
+struct EventPool {
+    std::vector<hipEvent_t> ev; size_t next = 0;
+    int reserve(size_t count)
+    {
+        while (ev.size() < count) {
+            hipEvent_t x;
+            GPX_HIP(hipEventCreateWithFlags(&x, hipEventDisableTiming));
+            ev.push_back(x);
+        }
+        return GPX_OK;
+    }
+    int get(hipEvent_t *e) { GPX_TRY(reserve(next + 1)); *e = ev[next++]; return GPX_OK; }
+    void rewind() { next = 0; }
+    void destroy() { for (hipEvent_t e : ev) (void)hipEventDestroy(e); ev.clear(); next = 0; }
+    int order(hipStream_t from, hipStream_t to) { hipEvent_t e; GPX_TRY(get(&e)); return gpx::order(e, from, to); }
+};
 
 // ---- live per-kernel-class timing (HIP events around each launch; off by default) ----
 enum ProfClass { PC_KMAT = 0, PC_GEMM = 1, PC_POTRF_DIAG = 2, PC_TRSM_ROWS = 3, PC_TRSV = 4,
@@ -142,21 +169,30 @@ int trsm_rows(int dtype, void *X, int64_t ldx, int64_t rows, const void *Ljj, in
 int syrk_bc(int dtype, int64_t n, int64_t row_begin, void *Cloc, int64_t ldc, int64_t cl0, int64_t cl1,
             const void *Pb, int64_t ldp, int64_t k0, int64_t kb, int64_t nb, int P, int rank,
             hipStream_t st, const int *abort_flag = nullptr, const Batch *bt = nullptr);
+// What potrf()'s schedule knows about ONE panel and the launch cannot see, by value down to the resident launch (gpx_panel.hip).
+// idle_chip: the panel's FIRST launch will find the chip idle (it is ordered behind the update before it and ahead of the
+// one that runs beside it) and may claim whole CUs (GPX_PANEL_EXCL_ROWS); later launches of the same panel (the right half
+// of a wide one) start on a chip that the update has filled meanwhile: they must not wait for empty CUs.
+// leaf_force: the leaf self-check's own launches: 1 / 4 / 5, no check (0: the leaf is chosen as usual)
+struct PanelHints { bool idle_chip = false; int leaf_force = 0; };
+// potrf() progress hook (null: none): called with the number of leading columns that are final once `panel_done` has
+// fired; single matrices with more than one outer block only.  (gpx_gp_fit builds the solves' block operators while the
+// factorisation runs.)
+struct PotrfHook { int (*fn)(void *user, int64_t cols_done, hipEvent_t panel_done); void *user; };
 // factor rows [r0, n) x columns [c0, c0 + kb) of A whose diagonal block sits at (r0, c0)
 // done: an event recorded behind the panel's last launch
 int potrf_panel(int dtype, void *A, int64_t lda, int64_t n, int64_t r0, int64_t c0, int64_t kb,
                 int *info_dev, hipStream_t st, const Batch *bt = nullptr, int64_t kpre = 0,   // kpre: see potrf_panel_res
-                hipEvent_t done = nullptr);
+                hipEvent_t done = nullptr, PanelHints hints = {});
 int potrf(int dtype, void *A, int64_t n, int64_t lda, int *info_dev, hipStream_t st, const Batch *bt = nullptr,
           int64_t xrows = 0,       // xrows: extra rows below the matrix that ride along (A has n + xrows rows)
-          bool may_block = false); // may_block: the caller allows the host to pace the panel launches (hipEventSynchronize
+          bool may_block = false,  // may_block: the caller allows the host to pace the panel launches (hipEventSynchronize
                                    // inside the call); false: a pure enqueue (gpx_d_potrf, anything under stream capture)
+          const PotrfHook *hook = nullptr);
 // the same panel in ONE launch (gpx_panel.hip): kb a multiple of 64, at most panel_res_max()
 int potrf_panel_res(int dtype, void *A, int64_t lda, int64_t n, int64_t r0, int64_t c0, int64_t kb, int *info_dev,
-                    hipStream_t st, const Batch *bt = nullptr, int64_t kpre = 0, hipEvent_t done = nullptr);
+                    hipStream_t st, const Batch *bt = nullptr, int64_t kpre = 0, hipEvent_t done = nullptr, PanelHints hints = {});
 int64_t panel_res_max();
-// set by potrf()'s loop for the one panel launch that will find the chip idle; reading it clears it (gpx_potrf.hip)
-bool potrf_take_idle_chip_hint();
 // this host thread's look-ahead stream of the blocked factorisation on the current device (nullptr before the first
 // one): it lives as long as the thread, so an event may be recorded on it at any time
 hipStream_t potrf_side_stream();
@@ -186,10 +222,6 @@ bool trsv_ops_ahead_ok(int dtype, const void *L, int64_t n, int64_t ldl);
 bool trsm_ops_ok(int dtype, const void *L, int64_t n, int64_t ldl);   // ... and trsm_right_lt would use them (GPX_TRSM_OPS)
 size_t trsv_ops_bytes(int dtype, int64_t n);
 int trsv_ops_build_upto(int dtype, const void *L, int64_t n, int64_t ldl, TrsvOps *ops, int64_t kend, hipStream_t st);
-// potrf() progress hook of the calling host thread (null: none): called with the number of leading columns that are final
-// once `panel_done` has fired; single matrices with more than one outer block only.
-struct PotrfHook { int (*fn)(void *user, int64_t cols_done, hipEvent_t panel_done); void *user; };
-void potrf_set_hook(const PotrfHook *hook);
 int trsv_lower(int dtype, const void *L, int64_t n, int64_t ldl, void *b, void *x, int transpose,
                hipStream_t st, const Batch *bt = nullptr,   // bt: sA = stride of L, sB = stride of b / x
                TrsvOps *ops = nullptr);

@@ -340,18 +340,13 @@ int gpx_gp_fit(gpx_gp_t *g, int *info)
         }
         GPX_TRY(g->ops.mem.reserve(trsv_ops_bytes(g->dtype, g->n), st));   // (here, not inside the factorisation's launch loop)
         // (the operator buffer may still be read by solves of the factor before this one, queued on st)
-        GPX_HIP(hipEventRecord(g->ev_ops, st));
-        GPX_HIP(hipStreamWaitEvent(g->st_ops, g->ev_ops, 0));
-        potrf_set_hook(&hook);
+        GPX_TRY(order(g->ev_ops, st, g->st_ops));
     }
-    const int prc = potrf(g->dtype, g->A, g->n, g->lda, info_dev, st, nullptr, ride ? 1 : 0, /*may_block=*/true);
-    potrf_set_hook(nullptr);
-    GPX_TRY(prc);
+    GPX_TRY(potrf(g->dtype, g->A, g->n, g->lda, info_dev, st, nullptr, ride ? 1 : 0, /*may_block=*/true, ahead ? &hook : nullptr));
     if (ahead) {
         // the solves wait for the operator stream.  The backward sweep takes the blocks that have no operators yet by
         // steps; a forward sweep (n > ride_max) and every later solve of this factor complete the set first (trsv_lower)
-        GPX_HIP(hipEventRecord(g->ev_ops, g->st_ops));
-        GPX_HIP(hipStreamWaitEvent(st, g->ev_ops, 0));
+        GPX_TRY(order(g->ev_ops, g->st_ops, st));
         if (g->ops.built > 0) route_hit(RT_FIT_OPS_AHEAD);
     }
     GPX_HIP(hipEventRecord(g->ev[2], st));

@@ -204,8 +204,7 @@ struct gpx_mg {
     int *info = nullptr;                          // [0] info [1] reduction key
     hipStream_t S = nullptr, Q = nullptr, B = nullptr;   // main (updates, solves) / panel (factor, pack) / panel broadcasts
     hipStream_t O = nullptr;                      // lowest priority: the diagonal blocks' solve operators, off the panel chain
-    std::vector<hipEvent_t> ev;                   // sync events (no timing), reused round-robin per fit
-    size_t ev_next = 0;
+    gpx::EventPool ev;                            // sync events (no timing), reused round-robin per fit
     std::vector<hipEvent_t> tev;                  // timing events (pairs)
     std::vector<int> tcls;                        // class of each timing pair
     std::vector<int64_t> tpan;                    // the panel it belongs to (-1: none)
@@ -243,27 +242,6 @@ namespace gpx {
 
 enum { T_BUILD = 0, T_FACTOR = 1, T_SOLVE = 2, T_REDUCE = 3, T_PANEL = 4, T_PACK = 5, T_BCAST = 6, T_UPDATE = 7,
        T_WAIT = 8 };   // T_WAIT: the update stream sat idle in front of a panel (chunk) that had not arrived: EXPOSED chain time
-
-static int mg_event(gpx_mg *g, hipEvent_t *e)
-{
-    if (g->ev_next == g->ev.size()) {
-        hipEvent_t x;
-        GPX_HIP(hipEventCreateWithFlags(&x, hipEventDisableTiming));
-        g->ev.push_back(x);
-    }
-    *e = g->ev[g->ev_next++];
-    return GPX_OK;
-}
-
-// record a "now" on `to` after everything enqueued so far on `from`
-static int mg_order(gpx_mg *g, hipStream_t from, hipStream_t to)
-{
-    hipEvent_t e;
-    GPX_TRY(mg_event(g, &e));
-    GPX_HIP(hipEventRecord(e, from));
-    GPX_HIP(hipStreamWaitEvent(to, e, 0));
-    return GPX_OK;
-}
 
 struct MgTimer {
     gpx_mg *g; hipStream_t st; size_t idx; bool on;
@@ -469,15 +447,15 @@ static int mg_factor_and_bcast(gpx_mg *g, int64_t j, void *buf, hipEvent_t buf_f
     if (g->owner(j) == g->rank) {
         const int64_t cl = g->local_col(j);
         { MgTimer t(g, T_PANEL, Q, j); GPX_TRY(potrf_panel(g->dtype, g->A, g->ld, g->nr, r0, cl, kb, g->info, Q)); }
-        GPX_TRY(mg_event(g, &g->last_panel_ev));
+        GPX_TRY(g->ev.get(&g->last_panel_ev));
         GPX_HIP(hipEventRecord(g->last_panel_ev, Q));
         if (buf_free) GPX_HIP(hipStreamWaitEvent(Q, buf_free, 0));
         { MgTimer t(g, T_PACK, Q, j); GPX_TRY(mg_pack(g, r0, cl, rows, kb, buf, Q)); }
-        GPX_TRY(mg_order(g, Q, B));
+        GPX_TRY(g->ev.order(Q, B));
         // the inverse of this diagonal block for the backward solve: ~11 small launches, on a low-priority stream of
         // their own ordered after the pack (round 4; they used to sit on Q, where with world <= 2 the owner's next panel
         // queued right behind them; their buffers come from mg_alloc, nothing is allocated inside this loop)
-        GPX_TRY(mg_order(g, Q, g->O));
+        GPX_TRY(g->ev.order(Q, g->O));
         GPX_TRY(trsv_ops_build(g->dtype, g->Aat(r0, cl), kb, g->ld, &g->ops[(size_t)(j / g->world)], g->O));
     } else {
         if (buf_free) GPX_HIP(hipStreamWaitEvent(B, buf_free, 0));
@@ -506,7 +484,7 @@ static int mg_factor_and_bcast(gpx_mg *g, int64_t j, void *buf, hipEvent_t buf_f
         done = end;
         if (chunk_ev) {
             hipEvent_t e;
-            GPX_TRY(mg_event(g, &e));
+            GPX_TRY(g->ev.get(&e));
             GPX_HIP(hipEventRecord(e, B));
             chunk_ev->push_back(e);
             chunk_end->push_back(end);
@@ -537,7 +515,7 @@ static int mg_factor(gpx_mg *g)
 {
     hipStream_t S = g->S, Q = g->Q;
     MgTimer tf(g, T_FACTOR, S);
-    GPX_TRY(mg_order(g, S, Q));                                   // the kernel build is done
+    GPX_TRY(g->ev.order(S, Q));                                   // the kernel build is done
     std::vector<hipEvent_t> cev; std::vector<int64_t> cend;
     GPX_TRY(mg_factor_and_bcast(g, 0, g->pbuf[0], nullptr, &cev, &cend));
     hipEvent_t readers_done[2] = {nullptr, nullptr};              // last update that read pbuf[i]
@@ -565,7 +543,7 @@ static int mg_factor(gpx_mg *g)
                 }
                 lo = std::max(lo, hi);
             }
-            GPX_TRY(mg_order(g, S, Q));
+            GPX_TRY(g->ev.order(S, Q));
             jl_first = g->first_local_block_after(nxt);
         } else {
             { MgTimer tw(g, T_WAIT, S); GPX_HIP(hipStreamWaitEvent(S, cev.back(), 0)); }   // the whole panel k is here
@@ -585,14 +563,14 @@ static int mg_factor(gpx_mg *g)
                             g->world, g->rank, S));
         }
         hipEvent_t e;
-        GPX_TRY(mg_event(g, &e));
+        GPX_TRY(g->ev.get(&e));
         GPX_HIP(hipEventRecord(e, S));
         readers_done[k % 2] = e;
         cev.swap(nev); cend.swap(nend);
     }
-    GPX_TRY(mg_order(g, Q, S));
-    GPX_TRY(mg_order(g, g->B, S));
-    GPX_TRY(mg_order(g, g->O, S));                                // the solve reads the operators
+    GPX_TRY(g->ev.order(Q, S));
+    GPX_TRY(g->ev.order(g->B, S));
+    GPX_TRY(g->ev.order(g->O, S));                                // the solve reads the operators
     if (g->debug_info != 0) {                                     // test hook: as if a resident panel launch had failed
         GPX_HIP(hipMemcpyAsync(g->info, &g->debug_info, sizeof(int), hipMemcpyHostToDevice, S));
         GPX_HIP(hipStreamSynchronize(S));
@@ -748,17 +726,6 @@ static double mg_hash(const void *p, size_t bytes)
     return (double)(h >> 12);
 }
 
-// the handle's sync-event pool holds at least `count` events (created up front: nothing fails half way through a run)
-static int mg_events_reserve(gpx_mg *g, size_t count)
-{
-    while (g->ev.size() < count) {
-        hipEvent_t x;
-        GPX_HIP(hipEventCreateWithFlags(&x, hipEventDisableTiming));
-        g->ev.push_back(x);
-    }
-    return GPX_OK;
-}
-
 // Every rank's local verdict and arguments, one F64 MAX all-reduce, the same status on every rank.  v (host, 8 values):
 // [0] a local allocation failed [1] a local argument is bad [2] m [3] -m [4] hash(xo) [5] -hash(xo) [6] hash(params)
 // [7] -hash(params); (x, -x) agree on every rank iff max(x) == -max(-x).
@@ -813,32 +780,32 @@ static int mg_cov_run(gpx_mg *g, const double *params, const void *dxo, int64_t 
                      params, 0.0, GPX_FULL, Bj(j), nb, S));
     if (g->rank == 0)
         GPX_TRY(kmat(g->dtype, g->kernel, GPX_K, dxo, m, dxo, m, g->d, params, 0.0, GPX_FULL, C, ldc, S));
-    GPX_TRY(mg_order(g, S, R));
+    GPX_TRY(g->ev.order(S, R));
     for (int64_t j = 0; j < nblk; ++j) {
-        // (R already waits for every local update of block j: see the mg_order(S, R) calls below)
+        // (R already waits for every local update of block j: see the order(S, R) calls below)
         GPX_TRY(mg_allreduce(g, Bj(j), (size_t)blk, g->dtype, 0, R));
         if (g->owner(j) != g->rank) {
-            if (j < last) GPX_TRY(mg_order(g, S, R));            // this rank's contributions to block j + 1 are all on S
+            if (j < last) GPX_TRY(g->ev.order(S, R));            // this rank's contributions to block j + 1 are all on S
             continue;
         }
         const int64_t k0 = g->k0(j), kb = g->kb(j), cl = g->local_col(j);
-        GPX_TRY(mg_order(g, R, Q));
+        GPX_TRY(g->ev.order(R, Q));
         GPX_TRY(trsm_right_lt(g->dtype, g->Aat(k0, cl), kb, g->ld, Bj(j), m, nb, Q, 0, &g->ops[(size_t)(j / g->world)]));
-        GPX_TRY(mg_order(g, Q, O));
+        GPX_TRY(g->ev.order(Q, O));
         GPX_TRY(gemm_nt(g->dtype, m, m, kb, Bj(j), nb, Bj(j), nb, C, ldc, -1.0, GPX_FULL, 0, 0, O));
         if (j == last) break;
-        GPX_TRY(mg_order(g, Q, S));                               // X_j is final: the rest of the update may use it
-        GPX_TRY(mg_order(g, S, Q));                               // (the earlier rest updates reach block j + 1)
+        GPX_TRY(g->ev.order(Q, S));                               // X_j is final: the rest of the update may use it
+        GPX_TRY(g->ev.order(S, Q));                               // (the earlier rest updates reach block j + 1)
         GPX_TRY(mg_cov_update(g, j, j + 1, j + 2, Bm, m, Q));     // look-ahead: block j + 1 ...
-        GPX_TRY(mg_order(g, Q, R));                               // ... whose reduction may start now
+        GPX_TRY(g->ev.order(Q, R));                               // ... whose reduction may start now
         GPX_TRY(mg_cov_update(g, j, j + 2, full_end, Bm, m, S));  // the rest, one batched launch
         if (full_end == last && last >= j + 2) GPX_TRY(mg_cov_update(g, j, last, nblk, Bm, m, S));   // a ragged last block
     }
-    GPX_TRY(mg_order(g, S, R));
-    GPX_TRY(mg_order(g, Q, R));
-    GPX_TRY(mg_order(g, O, R));
+    GPX_TRY(g->ev.order(S, R));
+    GPX_TRY(g->ev.order(Q, R));
+    GPX_TRY(g->ev.order(O, R));
     GPX_TRY(mg_allreduce(g, C, (size_t)m * ldc, g->dtype, 0, R));
-    GPX_TRY(mg_order(g, R, S));
+    GPX_TRY(g->ev.order(R, S));
     return GPX_OK;
 }
 
@@ -921,7 +888,7 @@ int gpx_mg_destroy(gpx_mg_t *g)
     for (void *b : {g->A, g->pbuf[0], g->pbuf[1], g->x, g->y, g->alpha, g->tmp, (void *)g->scal, (void *)g->info}) dev_free(b);   // mg_alloc's
     g->sag_tmp.release();
     for (gpx::TrsvOps &o : g->ops) o.mem.release();
-    for (hipEvent_t e : g->ev) (void)hipEventDestroy(e);
+    g->ev.destroy();
     for (hipEvent_t e : g->tev) (void)hipEventDestroy(e);
     stream_epoch_bump();
     if (g->S) (void)hipStreamDestroy(g->S);
@@ -1124,7 +1091,7 @@ int gpx_mg_fit(gpx_mg_t *g, const double *params, double s, double *log_lh, int 
     GPX_ARG(!(s < 0), "invalid value for s");
     if (!kernel_values_finite(g->kernel, params, s, g->dtype)) { set_error("array must not contain infs or NaNs"); return GPX_ERR_ARG; }
     g->fitted = false;
-    g->ev_next = 0; g->tev_next = 0;
+    g->ev.rewind(); g->tev_next = 0;
     GPX_HIP(hipMemsetAsync(g->info, 0, 4 * sizeof(int), g->S));
     GPX_TRY(mg_build(g, params, s));
     GPX_TRY(mg_factor(g));
@@ -1195,7 +1162,7 @@ int gpx_mg_cov(gpx_mg_t *g, const double *params, const double *xo, int64_t m, d
     DevBuf dxo, Bm, C;
     if (args_ok && m > 0) {
         const bool ok = dxo.alloc((size_t)m * g->d * es) == GPX_OK && Bm.alloc((size_t)g->nblk * m * g->nb * es) == GPX_OK &&
-                        C.alloc((size_t)m * ldc * es) == GPX_OK && mg_events_reserve(g, (size_t)(6 * g->nblk + 8)) == GPX_OK;
+                        C.alloc((size_t)m * ldc * es) == GPX_OK && g->ev.reserve((size_t)(6 * g->nblk + 8)) == GPX_OK;   // (events up front: nothing fails half way through a run)
         if (!ok) { (void)hipGetLastError(); v[0] = 1.0; }
     }
     GPX_TRY(mg_cov_agree(g, v));
@@ -1204,7 +1171,7 @@ int gpx_mg_cov(gpx_mg_t *g, const double *params, const double *xo, int64_t m, d
         gpx_mg *g;
         ~Drain() { for (hipStream_t st : {g->S, g->Q, g->B, g->O}) (void)hipStreamSynchronize(st); }
     } drain{g};
-    g->ev_next = 0;                                               // (the fit drained every stream: its events are free)
+    g->ev.rewind();                                               // (the fit drained every stream: its events are free)
     GPX_TRY(mg_upload(g, dxo.p, xo, (size_t)m * g->d));
     GPX_TRY(mg_cov_run(g, params, dxo.p, m, (char *)Bm.p, C.p, ldc));
     return mg_download(g, out, m, C.p, ldc, m, m);

@@ -626,7 +626,6 @@ int64_t panel_res_max()
 // thresholds moved under contention), and the result is compared with the compiler-scheduled MFMA leaf (LV = 1, whose
 // hazards hipcc handles) on the same input: agreement to 1e-12 relative or the library falls back to LV = 1 for the rest of
 // the process and says so on stderr (gpx_debug_leaf_selfcheck: 1 passed, 2 failed -> fallback, 0 not run yet).
-static thread_local int g_leaf_force = 0;                      // the self-check's own launches: 1 / 4 / 5, no check
 static std::mutex g_leaf_mu;
 static int g_leaf_state[MAX_DEVICES] = {};                      // 0 unknown, 1 ok, 2 failed, 3 never verified (guarded by g_leaf_mu)
 static int g_leaf_tries[MAX_DEVICES] = {};                      // attempts that could not run (guarded by g_leaf_mu)
@@ -662,7 +661,7 @@ static bool leaf_asm_ok(hipStream_t st = nullptr)
 
 template <typename T>
 static int panel_res_t(T *A, int64_t lda, int64_t n, int64_t r0, int64_t c0, int64_t kb, int *info_dev, hipStream_t st,
-                       const Batch *bt, int64_t kpre, hipEvent_t done)
+                       const Batch *bt, int64_t kpre, hipEvent_t done, PanelHints hints)
 {
     const int nbatch = bt ? bt->count : 1;
     void *pub = nullptr; int *flags = nullptr;
@@ -676,10 +675,8 @@ static int panel_res_t(T *A, int64_t lda, int64_t n, int64_t r0, int64_t c0, int
     const hipStream_t side = potrf_side_stream();
     if (!scr->ev) GPX_HIP(hipEventCreateWithFlags(&scr->ev, hipEventDisableTiming));
     if (scr->have_last && scr->last != st) {
-        if (scr->last_on_side) {
-            if (side == scr->last) GPX_HIP(hipEventRecord(scr->ev, side));     // everything queued there so far
-            else GPX_HIP(hipDeviceSynchronize());                               // (that stream went away with its device context)
-        }
+        // (`last` is then this device's side stream still: both slots are per device, and a side stream never changes once made)
+        if (scr->last_on_side) GPX_HIP(hipEventRecord(scr->ev, side));         // everything queued there so far
         GPX_HIP(hipStreamWaitEvent(st, scr->ev, 0));
     }
     unsigned long long *stamps = (g_res_stamps && g_res_stamp_at-- == 0) ? g_res_stamps : (unsigned long long *)nullptr;
@@ -712,8 +709,7 @@ static int panel_res_t(T *A, int64_t lda, int64_t n, int64_t r0, int64_t c0, int
     // LDS -- which a single matrix's panels never notice (at most 256 workgroups per launch) but a lock-step batch's would:
     // batches keep 1.)
     const int64_t excl_rows = tune().panel_excl_rows;
-    const bool idle_chip = potrf_take_idle_chip_hint();        // (always taken: a hint is for ONE launch)
-    const bool excl = !bt && idle_chip && rows <= excl_rows;
+    const bool excl = !bt && hints.idle_chip && rows <= excl_rows;   // (potrf_panel_t hands the hint to ONE launch)
     // (panels of up to GPX_LEAF4_ROWS rows take the LV = 4 instantiation beside an update too: n = 8192 5.94 -> 5.79 ms; taller
     //  ones lose more CUs to its one-workgroup-per-CU footprint than the leaf gives back: n = 16384 27.85 -> 28.4 ms)
     // (Several host threads factoring at once -- 4 x 128 one-per-CU workgroups wanting 256 CUs -- cannot deadlock: inside a
@@ -722,8 +718,8 @@ static int panel_res_t(T *A, int64_t lda, int64_t n, int64_t r0, int64_t c0, int
     //  tests/test_gpu_round5.py::test_four_host_threads_factor_n8192_concurrently holds it: 24 fits, no -7, bit-identical.)
     const int64_t leaf_dflt = (excl || (!bt && rows <= tune().leaf4_rows[F64 ? 0 : 1])) ? 4 : 1;
     // (the asm-scheduled leaf only where it has passed its self-check on this device; the check's own launches force a level)
-    const bool asm_ok = g_leaf_force != 0 || leaf_asm_ok(st);
-    const int64_t leaf_want = g_leaf_force ? g_leaf_force : (tune().leaf_set ? tune().leaf : -1);
+    const bool asm_ok = hints.leaf_force != 0 || leaf_asm_ok(st);
+    const int64_t leaf_want = hints.leaf_force ? hints.leaf_force : (tune().leaf_set ? tune().leaf : -1);
     const bool v4 = asm_ok && (leaf_want >= 0 ? leaf_want : leaf_dflt) == 4;   // (fp32: N = 32768 94.5 -> 94.2 ms with 5120)
     // A CU of its own for every workgroup of a SHORT panel (single matrix, rows <= GPX_PANEL_EXCL_ROWS).  Per-step stamps
     // of every leaf variant say the same thing (profiles/r04_leaf_steps_*.log): a leaf step takes 3 - 4 times longer while
@@ -786,10 +782,10 @@ static int panel_res_t(T *A, int64_t lda, int64_t n, int64_t r0, int64_t c0, int
 // kpre (a multiple of 64, <= c0): that many columns immediately to the left of the panel, rows [r0, n), are applied to
 // it first (P -= R R_d^T); the caller then omits that update
 int potrf_panel_res(int dtype, void *A, int64_t lda, int64_t n, int64_t r0, int64_t c0, int64_t kb, int *info_dev,
-                    hipStream_t st, const Batch *bt, int64_t kpre, hipEvent_t done)
+                    hipStream_t st, const Batch *bt, int64_t kpre, hipEvent_t done, PanelHints hints)
 {
-    if (dtype == GPX_F64) return panel_res_t<double>((double *)A, lda, n, r0, c0, kb, info_dev, st, bt, kpre, done);
-    return panel_res_t<float>((float *)A, lda, n, r0, c0, kb, info_dev, st, bt, kpre, done);
+    if (dtype == GPX_F64) return panel_res_t<double>((double *)A, lda, n, r0, c0, kb, info_dev, st, bt, kpre, done, hints);
+    return panel_res_t<float>((float *)A, lda, n, r0, c0, kb, info_dev, st, bt, kpre, done, hints);
 }
 
 // 1 passed, 2 failed, 0 could not run (see leaf_asm_ok).  Called under g_leaf_mu.
@@ -845,9 +841,8 @@ static int leaf_selfcheck_run(int dev, hipStream_t st)
         if (contended)                                           // ~1 ms of products on every matrix pipe of the chip
             for (int r = 0; r < 3; ++r)
                 if (gemm_nt(GPX_F64, GM, GM, GK, dG, GK, dG, GK, dC, GM, 1.0, GPX_FULL, 0, 0, s2) != GPX_OK) return false;
-        g_leaf_force = level;
-        const int rc = potrf_panel_res(dtype, dA, LD, N, 0, 0, N, dinfo, s1, nullptr, 0, nullptr);
-        g_leaf_force = 0;
+        // (leaf_force: the launch takes that leaf and never re-enters leaf_asm_ok, whose mutex this thread holds)
+        const int rc = potrf_panel_res(dtype, dA, LD, N, 0, 0, N, dinfo, s1, nullptr, 0, nullptr, PanelHints{false, level});
         if (rc != GPX_OK) return false;
         if (hipStreamSynchronize(s1) != hipSuccess || hipStreamSynchronize(s2) != hipSuccess) return false;
         int info = -1;

@@ -221,14 +221,15 @@ static thread_local ThreadScratch g_leaf;
 // "fused" (one launch per 64 columns, left-looking) and "lean" (leaf + one row kernel per 64 columns).
 template <typename T>
 static int potrf_panel_t(T *A, int64_t lda, int64_t n, int64_t r0, int64_t c0, int64_t kb, int *info_dev,
-                         hipStream_t st, int dtype, const Batch *bt, int64_t kpre = 0, hipEvent_t done = nullptr)
+                         hipStream_t st, int dtype, const Batch *bt, int64_t kpre = 0, hipEvent_t done = nullptr,
+                         PanelHints hints = {})
 {
     const int nbatch = bt ? bt->count : 1;
     const int64_t sM = bt ? bt->sA : 0;              // stride between the matrices of a batch
     // (c0 is a LOCAL column for a rank of the multi-GPU schedule: r0 != c0 there)
     if (kb % IB == 0 && kb <= panel_res_max()) {
         route_hit(RT_PANEL_RES);
-        return potrf_panel_res(dtype, A, lda, n, r0, c0, kb, info_dev, st, bt, kpre, done);
+        return potrf_panel_res(dtype, A, lda, n, r0, c0, kb, info_dev, st, bt, kpre, done, hints);
     }
     if (kpre != 0) { set_error("potrf_panel: a folded update needs the resident panel route"); return GPX_ERR_ARG; }
     if (kb <= IB) {
@@ -274,125 +275,184 @@ static int potrf_panel_t(T *A, int64_t lda, int64_t n, int64_t r0, int64_t c0, i
     }
     // wide panels of short matrices: a blocked factorisation of their own, with its own look-ahead (round 4)
     const int64_t h = ((kb / IB + 1) / 2) * IB;          // left half, a multiple of 64
-    GPX_TRY(potrf_panel_t<T>(A, lda, n, r0, c0, h, info_dev, st, dtype, bt));
+    GPX_TRY(potrf_panel_t<T>(A, lda, n, r0, c0, h, info_dev, st, dtype, bt, 0, nullptr, hints));
+    hints.idle_chip = false;                              // (the hint is for the panel's FIRST launch: the leftmost leaf, never a right half)
     T *R = A + (r0 + h) * lda + c0;                       // rows below the left half's diagonal block
     // the right half takes the left half's update itself when it is one resident-kernel launch over few rows
     if (panel_res_fold(n - (r0 + h), h, kb - h, sizeof(T), lda, A))
-        return potrf_panel_t<T>(A, lda, n, r0 + h, c0 + h, kb - h, info_dev, st, dtype, bt, h, done);
+        return potrf_panel_t<T>(A, lda, n, r0 + h, c0 + h, kb - h, info_dev, st, dtype, bt, h, done, hints);
     GPX_TRY(gemm_nt(dtype, n - (r0 + h), kb - h, h, R, lda, R, lda, R + h, lda, -1.0, GPX_LOWER, 0, 0, st, 0, 0, bt));
-    return potrf_panel_t<T>(A, lda, n, r0 + h, c0 + h, kb - h, info_dev, st, dtype, bt, 0, done);
+    return potrf_panel_t<T>(A, lda, n, r0 + h, c0 + h, kb - h, info_dev, st, dtype, bt, 0, done, hints);
 }
 
 int potrf_panel(int dtype, void *A, int64_t lda, int64_t n, int64_t r0, int64_t c0, int64_t kb,
-                int *info_dev, hipStream_t st, const Batch *bt, int64_t kpre, hipEvent_t done)
+                int *info_dev, hipStream_t st, const Batch *bt, int64_t kpre, hipEvent_t done, PanelHints hints)
 {
     if (dtype == GPX_F64)
-        return potrf_panel_t<double>((double *)A, lda, n, r0, c0, kb, info_dev, st, dtype, bt, kpre, done);
-    return potrf_panel_t<float>((float *)A, lda, n, r0, c0, kb, info_dev, st, dtype, bt, kpre, done);
+        return potrf_panel_t<double>((double *)A, lda, n, r0, c0, kb, info_dev, st, dtype, bt, kpre, done, hints);
+    return potrf_panel_t<float>((float *)A, lda, n, r0, c0, kb, info_dev, st, dtype, bt, kpre, done, hints);
 }
 
-// side stream + event pool for the look-ahead (one set per host thread and device)
-struct LookAhead {
-    int device = -1;
-    hipStream_t q = nullptr;
-    std::vector<hipEvent_t> ev;
-    size_t next = 0;
-    int get(hipEvent_t *e)
-    {
-        if (next == ev.size()) {
-            hipEvent_t x;
-            GPX_HIP(hipEventCreateWithFlags(&x, hipEventDisableTiming));
-            ev.push_back(x);
-        }
-        *e = ev[next++];
-        return GPX_OK;
-    }
-};
-static thread_local LookAhead g_la;
-
-// progress hook of this host thread (gpx_gp_fit builds the solves' block operators while the factorisation runs)
-static thread_local const PotrfHook *g_hook = nullptr;
-void potrf_set_hook(const PotrfHook *hook) { g_hook = hook; }
+// side stream + event pool for the look-ahead: one set per host thread and device (a thread that comes back to a device
+// finds its stream again; like all thread scratch the slot is not destroyed at thread or process exit, gpx_mem.h)
+struct LookAhead { hipStream_t q = nullptr; EventPool ev; };
+static thread_local PerDevice<LookAhead> g_la;
 
 hipStream_t potrf_side_stream()
 {
-    int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-    return g_la.device == dev ? g_la.q : nullptr;
+    LookAhead *la = nullptr;
+    return g_la.current(&la) == GPX_OK ? la->q : nullptr;
 }
 
-static int lookahead_setup()
+static int lookahead_setup(LookAhead **out)
 {
-    int dev = 0;
-    GPX_HIP(hipGetDevice(&dev));
-    if (g_la.device != dev) {
-        g_la.q = nullptr; g_la.ev.clear();
-        g_la.device = dev;
+    LookAhead *la = nullptr;
+    GPX_TRY(g_la.current(&la));
+    if (!la->q) {
         // the panel is on the critical path of the NEXT step: give its stream the highest
         // priority so that its workgroups get the CUs that trailing-update workgroups free up
         int least = 0, greatest = 0;
         GPX_HIP(hipDeviceGetStreamPriorityRange(&least, &greatest));
-        GPX_HIP(hipStreamCreateWithPriority(&g_la.q, hipStreamNonBlocking, greatest));
+        GPX_HIP(hipStreamCreateWithPriority(&la->q, hipStreamNonBlocking, greatest));
     }
-    g_la.next = 0;
+    la->ev.rewind();
+    *out = la;
     return GPX_OK;
 }
 
-// potrf()'s loop sets this right before a panel whose FIRST launch will find the chip idle (it is ordered behind the update
-// before it and ahead of the one that runs beside it); the resident panel launch that takes the hint may claim whole CUs
-// (gpx_panel.hip, GPX_PANEL_EXCL_ROWS).  Later launches of the same panel (the right half of a wide one) start on a chip that
-// the update has filled meanwhile: they must not wait for empty CUs.
-static thread_local bool g_idle_chip = false;
-bool potrf_take_idle_chip_hint() { const bool v = g_idle_chip; g_idle_chip = false; return v; }
+// What never changes during ONE factorisation (potrf() below); the three schedules share it and nothing else but the
+// "panel in flight" (k0, kb, ep, e_rest) that the pair phase hands to the look-ahead loop.
+struct PotrfCtx {
+    int dtype; void *A; int64_t n, N, lda; size_t es; int64_t nb; int *info_dev; const Batch *bt;
+    hipStream_t st, q;              // the caller's stream (updates) / this thread's look-ahead stream (panels); q, ev: null without look-ahead
+    EventPool *ev;
+    const PotrfHook *hook;          // single matrices only (null for a lock-step batch)
+    bool taper;
+    char *at(int64_t r, int64_t c) const { return (char *)A + (r * lda + c) * es; }
+    // Tapered outer block: the width that suits a factorisation of the rows that are LEFT (wide while the trailing
+    // update is the longer of the two, narrow once the step is bound by the panel chain); widths only ever shrink
+    // and each divides the one before, so every panel stays aligned to its own width.  Lock-step batches and a
+    // forced GPX_POTRF_NB keep one width.
+    int64_t nominal(int64_t k0) const { return (taper && !bt) ? std::min(nb, outer_block(n - k0)) : nb; }
+    // rows [row_begin, N) x columns [c0, c1) -= the block columns [k0, k0 + depth) of L (w: the width they were factored with)
+    int update(int64_t row_begin, int64_t c0, int64_t c1, int64_t k0, int64_t depth, int64_t w, hipStream_t s) const
+    {
+        return syrk_bc(dtype, N, row_begin, A, lda, c0, c1, at(k0, k0), lda, k0, depth, w, /*P=*/1, /*rank=*/0, s, info_dev, bt);
+    }
+    // panel [r, r + kb) on `s`; *done (from the pool) fires behind its last launch
+    int panel(int64_t r, int64_t kb, int64_t kpre, bool idle_chip, hipStream_t s, hipEvent_t *done) const
+    {
+        GPX_TRY(ev->get(done));
+        return potrf_panel(dtype, A, lda, N, r, r, kb, info_dev, s, bt, kpre, *done, PanelHints{idle_chip});
+    }
+    int progress(int64_t cols_done, hipEvent_t panel_done) const { return hook ? hook->fn(hook->user, cols_done, panel_done) : GPX_OK; }
+};
+
+static int potrf_no_lookahead(const PotrfCtx &c)
+{
+    for (int64_t k0 = 0; k0 < c.n; k0 += c.nb) {
+        const int64_t kb = std::min(c.nb, c.n - k0), r = k0 + kb;
+        GPX_TRY(potrf_panel(c.dtype, c.A, c.lda, c.N, k0, k0, kb, c.info_dev, c.st, c.bt));
+        if (r < c.n) GPX_TRY(c.update(r, r, c.n, k0, kb, c.nb, c.st));
+    }
+    return GPX_OK;
+}
+
+// ---- PAIR phase (round 6; OPT-IN: GPX_POTRF_PAIR_ROWS = rows that must lie beyond a pair, e.g. 20480; default 0 = never).
+// While many rows are left, the far trailing matrix is updated once per TWO 1024-wide panels with ONE product of depth
+// K = 2048 -- the operand is simply both block columns of L side by side -- instead of two of depth 1024, and both panels
+// of the NEXT pair are factored on the side stream while that product runs:
+//   invariant: panels A = [k0, k0 + 1024) and B = [k0 + 1024, k0 + 2048) are factored / in flight (epA, epB); everything
+//   before A has been applied everywhere; A has been applied to B's block column only.
+//     st: U_a  block column C <- (A | B), K = 2048         q: panel C   (after U_a)
+//     st: U_b  block column D <- (A | B), K = 2048         q: V = D <- C, K = 1024 (after U_b and panel C); panel D
+//     st: U_c  columns beyond D <- (A | B), K = 2048       (the long one: both panels and V hide under it)
+// MEASURED at N = 65536 fp64 (profiles/r06_ab_pair_phase.log, r06_timeline_n65536_{pair,nopair}.txt): the step gets 0.2 ... 0.6 %
+// SHORTER on the final build (1.334 -> 1.326 - 1.331 s; 0.9 ... 1.4 % on the round's earlier build; log_lh identical to the
+// last digit) because a fit has 60 long trailing launches instead of 81 -- fewer ramps, tails and cross-stream hand-offs --
+// and the trailing updates' C traffic halves.  But the update kernel's own figure gets worse (class fraction 0.88 against
+// 0.893; per tile 0.916 of peak against 0.921): the panel stream works two panels and V back to back beside ONE launch.
+// A slightly shorter step for a lower roofline fraction of the kernel this project is measured by: not the default; the
+// route is kept, tested, for larger N.  fp32 at N = 32768 (three pairs at most): 96.5 vs 96.4 ms.
+// In: panel [*k0, *k0 + *kb) in flight on q (*ep).  Out, when the phase ran (RT_POTRF_PAIR): the last panel B of the phase in
+// flight the same way, and *e_rest behind the last update -- exactly what a step of potrf()'s loop leaves behind.
+static int potrf_pair_phase(const PotrfCtx &c, int64_t *k0_io, int64_t *kb_io, hipEvent_t *ep_io, hipEvent_t *e_rest)
+{
+    const int64_t n = c.n;
+    const hipStream_t st = c.st, q = c.q;
+    const int64_t pair_rows = (c.bt || c.nb != 1024 || c.N - n > 1) ? 0 : tune().pair_rows[c.dtype == GPX_F64 ? 0 : 1];
+    // (every panel of the phase is 1024 wide: with the taper on, the widths shrink once <= 12288 rows are left)
+    auto pair_ok = [&](int64_t k) { return pair_rows > 0 && n - (k + 4 * 1024) >= pair_rows && c.nominal(k + 1024) == 1024 &&
+                                           c.nominal(k + 2048) == 1024 && c.nominal(k + 3072) == 1024; };
+    int64_t k0 = *k0_io;
+    if (*kb_io != 1024 || !pair_ok(k0)) return GPX_OK;
+    // entry: B's block column <- A, then panel B (the only panel of the phase that no update hides)
+    const int64_t rB = k0 + 1024;
+    hipEvent_t epA = *ep_io, epB;
+    GPX_HIP(hipStreamWaitEvent(st, epA, 0));
+    GPX_TRY(c.update(rB, rB, rB + 1024, k0, 1024, 1024, st));
+    GPX_TRY(c.ev->order(st, q));
+    GPX_TRY(c.panel(rB, 1024, 0, false, q, &epB));
+    GPX_TRY(c.progress(rB, epA));
+    route_hit(RT_POTRF_PAIR);
+    while (pair_ok(k0)) {
+        const int64_t rC = k0 + 2048, rD = rC + 1024, rE = rD + 1024;
+        GPX_HIP(hipStreamWaitEvent(st, epB, 0));            // A and B are factored (B follows A on q)
+        GPX_TRY(c.update(rC, rC, rD, k0, 2048, 1024, st));  // U_a
+        GPX_TRY(c.ev->order(st, q));
+        hipEvent_t epC, epD;
+        GPX_TRY(c.panel(rC, 1024, 0, false, q, &epC));
+        GPX_TRY(c.update(rD, rD, rE, k0, 2048, 1024, st));  // U_b
+        GPX_TRY(c.ev->order(st, q));
+        // V: a panel-class product on the panel stream (it is part of the chain to panel D and runs beside U_c)
+        GPX_TRY(gemm_nt(c.dtype, c.N - rD, 1024, 1024, c.at(rD, rC), c.lda, c.at(rD, rC), c.lda, c.at(rD, rD), c.lda, -1.0, GPX_LOWER, rD, rD, q));
+        GPX_TRY(c.panel(rD, 1024, 0, false, q, &epD));
+        if (rE < n) GPX_TRY(c.update(rE, rE, n, k0, 2048, 1024, st));   // U_c
+        GPX_TRY(c.progress(rC, epB));
+        GPX_TRY(c.progress(rD, epC));
+        k0 = rC; epA = epC; epB = epD;
+    }
+    // exit: A <- everything beyond B (K = 1024); then potrf()'s loop carries on with B as "the panel in flight"
+    const int64_t rC2 = k0 + 2048;
+    GPX_HIP(hipStreamWaitEvent(st, epA, 0));
+    if (rC2 < n) GPX_TRY(c.update(rC2, rC2, n, k0, 1024, 1024, st));
+    GPX_TRY(c.ev->get(e_rest));
+    GPX_HIP(hipEventRecord(*e_rest, st));
+    *k0_io = k0 + 1024; *kb_io = 1024; *ep_io = epB;
+    return GPX_OK;
+}
+
 // Right-looking blocked Cholesky with one-panel look-ahead: while the main stream
 // applies panel k to the block columns beyond k + 1, the side stream already
 // factors panel k + 1 (whose block column was updated first).
 // bt != null: bt->count matrices sA elements apart are factored in lock-step (every launch covers all of
 // them; info_dev then holds one word per matrix).
-int potrf(int dtype, void *A, int64_t n, int64_t lda, int *info_dev, hipStream_t st, const Batch *bt, int64_t xrows, bool may_block)
+int potrf(int dtype, void *A, int64_t n, int64_t lda, int *info_dev, hipStream_t st, const Batch *bt, int64_t xrows, bool may_block,
+          const PotrfHook *hook)
 {
     // xrows extra rows below the n x n matrix take part in every panel and update as rows, never as columns: on
     // return row n + i holds L^-1 applied to what was stored there (a right-hand side rides along: gpx_gp_fit)
     const int64_t N = n + xrows;
     GPX_HIP(hipMemsetAsync(info_dev, 0, sizeof(int) * (bt ? bt->count : 1), st));
     const int64_t nb = outer_block(n, bt != nullptr);
-    const int64_t nblk = cdiv(n, nb);
-    const size_t es = esize(dtype);
-    const bool no_la = tune().no_lookahead;
-    if (nblk <= 1) return potrf_panel(dtype, A, lda, N, 0, 0, n, info_dev, st, bt);
-    auto at = [&](int64_t r, int64_t c) { return (char *)A + (r * lda + c) * es; };
-    if (no_la) {
-        for (int64_t k0 = 0; k0 < n; k0 += nb) {
-            const int64_t kb = std::min(nb, n - k0), r = k0 + kb;
-            GPX_TRY(potrf_panel(dtype, A, lda, N, k0, k0, kb, info_dev, st, bt));
-            if (r < n) GPX_TRY(syrk_bc(dtype, N, r, A, lda, r, n, at(k0, k0), lda, k0, kb, nb, 1, 0, st, info_dev, bt));
-        }
-        return GPX_OK;
-    }
-    GPX_TRY(lookahead_setup());
-    hipStream_t q = g_la.q;
-    hipEvent_t e, ep;
-    GPX_TRY(g_la.get(&e));
-    GPX_HIP(hipEventRecord(e, st));
-    GPX_HIP(hipStreamWaitEvent(q, e, 0));
-    // Tapered outer block: the width that suits a factorisation of the rows that are LEFT (wide while the trailing
-    // update is the longer of the two, narrow once the step is bound by the panel chain); widths only ever shrink
-    // and each divides the one before, so every panel stays aligned to its own width.  Lock-step batches and a
-    // forced GPX_POTRF_NB keep one width.
-    const bool taper = tune().taper != 0 && !tune().potrf_nb_set;
-    auto nominal = [&](int64_t k0) -> int64_t { return (taper && !bt) ? std::min(nb, outer_block(n - k0)) : nb; };
+    if (cdiv(n, nb) <= 1) return potrf_panel(dtype, A, lda, N, 0, 0, n, info_dev, st, bt);
+    PotrfCtx c = {dtype, A, n, N, lda, esize(dtype), nb, info_dev, bt, st, nullptr, nullptr, bt ? nullptr : hook,
+                  tune().taper != 0 && !tune().potrf_nb_set};
+    if (tune().no_lookahead) return potrf_no_lookahead(c);
+    LookAhead *la = nullptr;
+    GPX_TRY(lookahead_setup(&la));
+    const hipStream_t q = c.q = la->q;
+    c.ev = &la->ev;
+    GPX_TRY(c.ev->order(st, q));
     // (Round 4 also built a "pair phase" here -- while many rows are left, the far trailing matrix updated once per TWO 256-wide
     //  panels with one K = 512 product, the panels in between applying their predecessors themselves, 512 / 256 columns deep --
     //  correct, and no faster: n = 8192 5.67 - 5.97 ms against 5.58 (profiles/r04_ab_pair_phase_dropped.log).  The K = 512 update
     //  does run at 60 TF/s, but the second panel of every pair starts on a chip the update has filled and takes 280 - 470 us
     //  instead of 115 (profiles/r04_timeline_n8192_pair_phase_dropped.txt): one panel per update, dispatched ahead of it, is
     //  the schedule this machine rewards.  Removed again.)
-    int64_t k0 = 0, kb = std::min(nominal(0), n);
-    GPX_TRY(g_la.get(&ep));
-    g_idle_chip = !bt;
-    GPX_TRY(potrf_panel(dtype, A, lda, N, 0, 0, kb, info_dev, q, bt, 0, ep));
-    g_idle_chip = false;
-    hipEvent_t e_rest = nullptr;                                // fires when the trailing update of the step before is done
+    int64_t k0 = 0, kb = std::min(c.nominal(0), n);
+    hipEvent_t ep, e_rest = nullptr;                            // e_rest fires when the trailing update of the step before is done
+    GPX_TRY(c.panel(0, kb, 0, /*idle_chip=*/!bt, q, &ep));
     // host pacing blocks the calling thread inside the loop: only where the caller said it may (the handle's gpx_gp_fit,
     // documented in include/gpx.h; gpx_d_potrf stays a pure enqueue) and never while the stream is being captured
     bool host_paced = may_block && !bt && n <= tune().host_paced;
@@ -401,99 +461,30 @@ int potrf(int dtype, void *A, int64_t n, int64_t lda, int *info_dev, hipStream_t
         if (hipStreamIsCapturing(st, &cs) != hipSuccess) (void)hipGetLastError();
         else if (cs != hipStreamCaptureStatusNone) host_paced = false;
     }
-    // ---- PAIR phase (round 6; OPT-IN: GPX_POTRF_PAIR_ROWS = rows that must lie beyond a pair, e.g. 20480; default 0 = never).
-    // While many rows are left, the far trailing matrix is updated once per TWO 1024-wide panels with ONE product of depth
-    // K = 2048 -- the operand is simply both block columns of L side by side -- instead of two of depth 1024, and both panels
-    // of the NEXT pair are factored on the side stream while that product runs:
-    //   invariant: panels A = [k0, k0 + 1024) and B = [k0 + 1024, k0 + 2048) are factored / in flight (epA, epB); everything
-    //   before A has been applied everywhere; A has been applied to B's block column only.
-    //     st: U_a  block column C <- (A | B), K = 2048         q: panel C   (after U_a)
-    //     st: U_b  block column D <- (A | B), K = 2048         q: V = D <- C, K = 1024 (after U_b and panel C); panel D
-    //     st: U_c  columns beyond D <- (A | B), K = 2048       (the long one: both panels and V hide under it)
-    // MEASURED at N = 65536 fp64 (profiles/r06_ab_pair_phase.log, r06_timeline_n65536_{pair,nopair}.txt): the step gets 0.2 ... 0.6 %
-    // SHORTER on the final build (1.334 -> 1.326 - 1.331 s; 0.9 ... 1.4 % on the round's earlier build; log_lh identical to the
-    // last digit) because a fit has 60 long trailing launches instead of 81 -- fewer ramps, tails and cross-stream hand-offs --
-    // and the trailing updates' C traffic halves.  But the update kernel's own figure gets worse (class fraction 0.88 against
-    // 0.893; per tile 0.916 of peak against 0.921): the panel stream works two panels and V back to back beside ONE launch.
-    // A slightly shorter step for a lower roofline fraction of the kernel this project is measured by: not the default; the
-    // route is kept, tested, for larger N.  fp32 at N = 32768 (three pairs at most): 96.5 vs 96.4 ms.
-    const int64_t pair_rows = (bt || nb != 1024 || xrows > 1) ? 0 : tune().pair_rows[dtype == GPX_F64 ? 0 : 1];
-    // (every panel of the phase is 1024 wide: with the taper on, the widths shrink once <= 12288 rows are left)
-    auto pair_ok = [&](int64_t k) { return pair_rows > 0 && n - (k + 4 * 1024) >= pair_rows && nominal(k + 1024) == 1024 &&
-                                           nominal(k + 2048) == 1024 && nominal(k + 3072) == 1024; };
-    if (kb == 1024 && pair_ok(k0)) {
-        // entry: B's block column <- A, then panel B (the only panel of the phase that no update hides)
-        const int64_t rB = k0 + 1024;
-        hipEvent_t epA = ep, epB;
-        GPX_HIP(hipStreamWaitEvent(st, epA, 0));
-        GPX_TRY(syrk_bc(dtype, N, rB, A, lda, rB, rB + 1024, at(k0, k0), lda, k0, 1024, 1024, 1, 0, st, info_dev, nullptr));
-        GPX_TRY(g_la.get(&e));
-        GPX_HIP(hipEventRecord(e, st));
-        GPX_HIP(hipStreamWaitEvent(q, e, 0));
-        GPX_TRY(g_la.get(&epB));
-        GPX_TRY(potrf_panel(dtype, A, lda, N, rB, rB, 1024, info_dev, q, nullptr, 0, epB));
-        if (g_hook) GPX_TRY(g_hook->fn(g_hook->user, rB, epA));
-        route_hit(RT_POTRF_PAIR);
-        while (pair_ok(k0)) {
-            const int64_t rC = k0 + 2048, rD = rC + 1024, rE = rD + 1024;
-            GPX_HIP(hipStreamWaitEvent(st, epB, 0));            // A and B are factored (B follows A on q)
-            GPX_TRY(syrk_bc(dtype, N, rC, A, lda, rC, rD, at(k0, k0), lda, k0, 2048, 1024, 1, 0, st, info_dev, nullptr));   // U_a
-            GPX_TRY(g_la.get(&e));
-            GPX_HIP(hipEventRecord(e, st));
-            GPX_HIP(hipStreamWaitEvent(q, e, 0));
-            hipEvent_t epC, epD;
-            GPX_TRY(g_la.get(&epC));
-            GPX_TRY(potrf_panel(dtype, A, lda, N, rC, rC, 1024, info_dev, q, nullptr, 0, epC));
-            GPX_TRY(syrk_bc(dtype, N, rD, A, lda, rD, rE, at(k0, k0), lda, k0, 2048, 1024, 1, 0, st, info_dev, nullptr));   // U_b
-            GPX_TRY(g_la.get(&e));
-            GPX_HIP(hipEventRecord(e, st));
-            GPX_HIP(hipStreamWaitEvent(q, e, 0));
-            // V: a panel-class product on the panel stream (it is part of the chain to panel D and runs beside U_c)
-            GPX_TRY(gemm_nt(dtype, N - rD, 1024, 1024, at(rD, rC), lda, at(rD, rC), lda, at(rD, rD), lda, -1.0, GPX_LOWER, rD, rD, q));
-            GPX_TRY(g_la.get(&epD));
-            GPX_TRY(potrf_panel(dtype, A, lda, N, rD, rD, 1024, info_dev, q, nullptr, 0, epD));
-            if (rE < n)
-                GPX_TRY(syrk_bc(dtype, N, rE, A, lda, rE, n, at(k0, k0), lda, k0, 2048, 1024, 1, 0, st, info_dev, nullptr)); // U_c
-            if (g_hook) {
-                GPX_TRY(g_hook->fn(g_hook->user, rC, epB));
-                GPX_TRY(g_hook->fn(g_hook->user, rD, epC));
-            }
-            k0 = rC; epA = epC; epB = epD;
-        }
-        // exit: A <- everything beyond B (K = 1024); then the loop below carries on with B as "the panel in flight"
-        const int64_t rB2 = k0 + 1024, rC2 = k0 + 2048;
-        GPX_HIP(hipStreamWaitEvent(st, epA, 0));
-        if (rC2 < n)
-            GPX_TRY(syrk_bc(dtype, N, rC2, A, lda, rC2, n, at(k0, k0), lda, k0, 1024, 1024, 1, 0, st, info_dev, nullptr));
-        GPX_TRY(g_la.get(&e_rest));
-        GPX_HIP(hipEventRecord(e_rest, st));
-        k0 = rB2; kb = 1024; ep = epB;
-    }
+    GPX_TRY(potrf_pair_phase(c, &k0, &kb, &ep, &e_rest));
     while (true) {
         const int64_t r = k0 + kb;
         GPX_HIP(hipStreamWaitEvent(st, ep, 0));                 // panel k is factored
         if (r >= n) {
-            if (g_hook && !bt) GPX_TRY(g_hook->fn(g_hook->user, n, ep));
+            GPX_TRY(c.progress(n, ep));
             break;
         }
         const hipEvent_t ep_k = ep;
-        const int64_t w1 = nominal(r), kb1 = std::min(w1, n - r);
+        const int64_t w1 = c.nominal(r), kb1 = std::min(w1, n - r);
         // block column k + 1 first, so that its panel can start ... (small n: the panel kernel applies panel k to its
         // own columns itself -- it then only waits for the trailing update of step k - 1, not for this stream's turn)
-        const bool fold = panel_res_fold(N - r, kb, kb1, es, lda, A);
+        const bool fold = panel_res_fold(N - r, kb, kb1, c.es, lda, A);
         hipEvent_t e_gate = nullptr;
         if (!fold) {
-            GPX_TRY(syrk_bc(dtype, N, r, A, lda, r, r + kb1, at(k0, k0), lda, k0, kb, w1, 1, 0, st, info_dev, bt));
-            GPX_TRY(g_la.get(&e));
-            GPX_HIP(hipEventRecord(e, st));
-            GPX_HIP(hipStreamWaitEvent(q, e, 0));
+            GPX_TRY(c.update(r, r, r + kb1, k0, kb, w1, st));
+            GPX_TRY(c.ev->order(st, q));
             // The panel has to get onto the chip BEFORE the rest of the update: that one follows the block-column update
             // directly in its stream, while the panel sits behind a cross-stream wait -- it used to start ~6 us late, found
             // every CU slot taken and ran for as long as the update did (n = 8192 with 512-wide blocks: the left half 504 us
             // beside a 441 us update, the right half 107 us after it; profiles/r04_timeline_n8192_nb512_before_gate.txt).
             // An event recorded on the panel's stream right behind its wait gates the rest of the update.
             if (!bt && N - r <= tune().gate_rows) {
-                GPX_TRY(g_la.get(&e_gate));
+                GPX_TRY(c.ev->get(&e_gate));
                 GPX_HIP(hipEventRecord(e_gate, q));
             }
         } else if (e_rest) {
@@ -511,19 +502,17 @@ int potrf(int dtype, void *A, int64_t n, int64_t lda, int *info_dev, hipStream_t
             if (host_paced) GPX_HIP(hipEventSynchronize(e_rest));   // (polling hipEventQuery instead: no faster, r04_ab_*_host_spin.log)
             GPX_HIP(hipStreamWaitEvent(q, e_rest, 0));
         }
-        GPX_TRY(g_la.get(&ep));
-        g_idle_chip = !bt && (e_gate != nullptr || (fold && (host_paced || !e_rest)));
-        GPX_TRY(potrf_panel(dtype, A, lda, N, r, r, kb1, info_dev, q, bt, fold ? kb : 0, ep));
-        g_idle_chip = false;
+        const bool idle_chip = !bt && (e_gate != nullptr || (fold && (host_paced || !e_rest)));
+        GPX_TRY(c.panel(r, kb1, fold ? kb : 0, idle_chip, q, &ep));
         // ... while the rest of the trailing matrix is updated underneath it
         if (r + kb1 < n) {
             if (e_gate) GPX_HIP(hipStreamWaitEvent(st, e_gate, 0));
-            GPX_TRY(syrk_bc(dtype, N, r, A, lda, r + kb1, n, at(k0, k0), lda, k0, kb, w1, 1, 0, st, info_dev, bt));
+            GPX_TRY(c.update(r, r + kb1, n, k0, kb, w1, st));
         }
-        GPX_TRY(g_la.get(&e_rest));
+        GPX_TRY(c.ev->get(&e_rest));
         GPX_HIP(hipEventRecord(e_rest, st));
         // (after the next panel and this step's update are on their way: the hook's launches never delay the chain)
-        if (g_hook && !bt) GPX_TRY(g_hook->fn(g_hook->user, r, ep_k));
+        GPX_TRY(c.progress(r, ep_k));
         k0 = r; kb = kb1;
     }
     return GPX_OK;

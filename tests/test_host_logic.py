@@ -113,6 +113,31 @@ def test_solve_operators_keep_one_launch_site_and_one_block_width():
         assert not re.search(r"\b512\b", code(f)), f
 
 
+def test_cholesky_schedule_state_is_explicit():
+    """The host schedule of the blocked Cholesky (csrc/gpx_potrf.hip) passes what a panel launch has to know
+    as ARGUMENTS (PanelHints, the PotrfHook pointer): three thread-local side channels used to carry them across
+    translation units, consumed by whichever launch came first.  What is thread-local in the factorisation's two units
+    is a per-device resource and nothing else; sync events come from an EventPool (gpx_common.h), and the trailing
+    update's seventeen positional arguments are written out once."""
+    csrc = os.path.join(ROOT, "gaussian_processes_amd", "csrc")
+
+    def code(f):        # without comments and string literals
+        src = open(os.path.join(csrc, f)).read()
+        return re.sub(r'"(?:\\.|[^"\\])*"', '""', re.sub(r"//[^\n]*", "", src))
+    gone = re.compile(r"\b(?:potrf_set_hook|potrf_take_idle_chip_hint|g_idle_chip|g_hook|g_leaf_force)\b")
+    for f in sorted(os.listdir(csrc)):
+        if f.endswith((".hip", ".h")):
+            assert not gone.search(code(f)), (f, gone.findall(code(f)))
+    for f in ("gpx_potrf.hip", "gpx_panel.hip"):
+        decls = [l.strip() for l in code(f).splitlines() if re.search(r"\bthread_local\b", l)]
+        assert decls, f
+        for l in decls:
+            assert re.match(r"static thread_local (?:ThreadScratch|PerDevice<\w+>) \w+;", l), (f, l)
+    for f in ("gpx_potrf.hip", "gpx_mg.hip"):
+        assert "hipEventCreateWithFlags" not in code(f), f
+    assert 1 <= len(re.findall(r"\bsyrk_bc\s*\(", code("gpx_potrf.hip"))) <= 2
+
+
 def test_no_cpu_fallback_without_gpu():
     if _lib.device_count() > 0:
         pytest.skip("a GPU is present")
