@@ -18,7 +18,7 @@ OK = 0
 ERR_ARG, ERR_HIP, ERR_NO_DEVICE, ERR_NOMEM, ERR_UNSUPPORTED, ERR_INTERNAL = -1, -2, -3, -4, -5, -6
 (ROUTE_TRSV_OPS, ROUTE_TRSV_STEPS, ROUTE_PANEL_RES, ROUTE_PANEL_CHAIN, ROUTE_FIT_RIDE, ROUTE_FIT_TWO_SOLVES,
  ROUTE_GEMM_FAST, ROUTE_GEMM_GENERIC, ROUTE_SYRK_EXACT, ROUTE_SYRK_PATCH, ROUTE_MG_BCAST_ONE, ROUTE_MG_BCAST_SAG,
- ROUTE_FIT_OPS_AHEAD, ROUTE_TRSM_OPS, ROUTE_POTRF_PAIR) = range(15)
+ ROUTE_FIT_OPS_AHEAD, ROUTE_TRSM_OPS, ROUTE_POTRF_PAIR, ROUTE_VAR_CHUNK) = range(16)
 F64, F32 = 0, 1
 KERNEL_GAUSSIAN, KERNEL_PERIODIC = 0, 1
 FULL, LOWER = 0, 1
@@ -93,6 +93,8 @@ _SIGNATURES = {
                                     c_void_p]),
     "gpx_d_logdet_chol": (c_int, [c_int, c_void_p, c_int64, c_int64, c_void_p, c_void_p]),
     "gpx_d_dot": (c_int, [c_int, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+    "gpx_d_var_rows": (c_int, [c_int, c_int, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int, c_double_p, c_void_p,
+                               c_void_p, c_void_p]),
     "gpx_gp_create": (c_int, [POINTER(c_void_p), c_int, c_int, c_int64, c_int]),
     "gpx_gp_destroy": (c_int, [c_void_p]),
     "gpx_gp_set_data": (c_int, [c_void_p, c_double_p, c_double_p]),
@@ -107,6 +109,10 @@ _SIGNATURES = {
     "gpx_gp_cov": (c_int, [c_void_p, c_double_p, c_int64, c_double_p]),
     "gpx_gp_mean_from_K": (c_int, [c_void_p, c_double_p, c_int64, c_double_p]),
     "gpx_gp_cov_from_K": (c_int, [c_void_p, c_double_p, c_double_p, c_int64, c_double_p]),
+    "gpx_gp_var": (c_int, [c_void_p, c_double_p, c_int64, c_int64, c_double_p]),
+    "gpx_gp_var_from_K": (c_int, [c_void_p, c_double_p, c_double_p, c_int64, c_int64, c_double_p]),
+    "gpx_debug_var_plan": (c_int, [c_int, c_int64, c_int64, c_int64, c_size_t, POINTER(c_int64), POINTER(c_int64),
+                                   POINTER(c_size_t)]),
     "gpx_gp_get_Kxx": (c_int, [c_void_p, c_double_p, c_int64]),
     "gpx_gp_get_Lxx": (c_int, [c_void_p, c_double_p, c_int64]),
     "gpx_gp_get_alpha": (c_int, [c_void_p, c_double_p]),
@@ -144,6 +150,7 @@ _SIGNATURES = {
     "gpx_mg_fit": (c_int, [c_void_p, c_double_p, c_double, c_double_p, c_int_p]),
     "gpx_mg_mean": (c_int, [c_void_p, c_double_p, c_double_p, c_int64, c_double_p]),
     "gpx_mg_cov": (c_int, [c_void_p, c_double_p, c_double_p, c_int64, c_double_p]),
+    "gpx_mg_var": (c_int, [c_void_p, c_double_p, c_double_p, c_int64, c_int64, c_double_p]),
     "gpx_mg_get_alpha": (c_int, [c_void_p, c_double_p]),
     "gpx_mg_scalars": (c_int, [c_void_p, c_double_p, c_double_p, c_int_p]),
     "gpx_mg_timing": (c_int, [c_void_p, c_double_p]),
@@ -259,6 +266,17 @@ def mem_free():
     f, t = c_size_t(0), c_size_t(0)
     check(load().gpx_mem_info(ctypes.byref(f), ctypes.byref(t)))
     return int(f.value)
+
+
+def var_plan(dtype_id, n, m, chunk_rows=0, free_bytes=None):
+    """The row chunking gpx_gp_var would use: (rows per chunk, chunks, device bytes per chunk).  Host arithmetic; only the
+    default `free_bytes` (the current device's free HBM) needs a GPU."""
+    if free_bytes is None:
+        free_bytes = mem_free()
+    rows, chunks, nbytes = c_int64(0), c_int64(0), c_size_t(0)
+    check(load().gpx_debug_var_plan(int(dtype_id), int(n), int(m), int(chunk_rows), int(free_bytes), ctypes.byref(rows),
+                                    ctypes.byref(chunks), ctypes.byref(nbytes)))
+    return rows.value, chunks.value, int(nbytes.value)
 
 
 def route_count(route):

@@ -48,7 +48,7 @@ int  ensure_device();   // GPX_OK when a GPU is usable
 // point of decision.  Tests that force a route through an environment switch assert it here.
 enum Route { RT_TRSV_OPS = 0, RT_TRSV_STEPS = 1, RT_PANEL_RES = 2, RT_PANEL_CHAIN = 3, RT_FIT_RIDE = 4,
              RT_FIT_TWO_SOLVES = 5, RT_GEMM_FAST = 6, RT_GEMM_GENERIC = 7, RT_SYRK_EXACT = 8, RT_SYRK_PATCH = 9,
-             RT_MG_BCAST_ONE = 10, RT_MG_BCAST_SAG = 11, RT_FIT_OPS_AHEAD = 12, RT_TRSM_OPS = 13, RT_POTRF_PAIR = 14, RT_COUNT = 15 };
+             RT_MG_BCAST_ONE = 10, RT_MG_BCAST_SAG = 11, RT_FIT_OPS_AHEAD = 12, RT_TRSM_OPS = 13, RT_POTRF_PAIR = 14, RT_VAR_CHUNK = 15, RT_COUNT = 16 };
 void route_hit(int route);
 
 // LAPACK-style info of a factorisation as the host sees it: > 0 "not positive definite" (the caller's business),
@@ -237,6 +237,17 @@ int logdet_chol(int dtype, const void *L, int64_t n, int64_t ldl, double *out_de
 int dot(int dtype, const void *a, const void *b, int64_t n, double *out_dev, hipStream_t st, int count = 1,
         int64_t sa = 0, int64_t sb = 0, int64_t so = 0);
 int tril(int dtype, void *A, int64_t n, int64_t lda, hipStream_t st);
+// Predictive variance (gpx_solve.hip).  var_rows: out_dev[i] = kdiag(i) - sum_j X[i, j]^2 over a solved rows x n chunk
+// (gpx_d_var_rows' arguments), or with accumulate != 0: out_dev[i] += sum_j X[i, j]^2 (no kdiag; the distributed form adds
+// its blocks' sums in block order).  var_finish: out_dev[i] = k(xo_i, xo_i) - acc_dev[i].  Sums and outputs are f64.
+int var_rows(int dtype, int kernel, const void *X, int64_t rows, int64_t n, int64_t ldx, const void *xo, int d,
+             const double *params, const double *kdiag_dev, int accumulate, double *out_dev, hipStream_t st);
+int var_finish(int dtype, int kernel, const void *xo, int d, const double *params, const double *acc_dev, int64_t rows,
+               double *out_dev, hipStream_t st);
+// The row chunking of a predictive-variance call (gpx_gp.hip; host arithmetic): *rows per chunk, *chunks, *bytes of device
+// memory one chunk needs.  chunk_rows 0: the largest multiple of 128 (at most var_chunk_cap) whose buffers fit a quarter
+// of free_bytes.  GPX_ERR_ARG / GPX_ERR_NOMEM as gpx_debug_var_plan documents.
+int var_plan(int dtype, int64_t n, int64_t m, int64_t chunk_rows, size_t free_bytes, int64_t *rows, int64_t *chunks, size_t *bytes);
 int dloglh_reduce(int dtype, int kernel, const void *x, int64_t n, int d, const double *params,
                   const void *alpha, const void *W, int64_t ldw, double *partial_dev, double *out4,
                   hipStream_t st);

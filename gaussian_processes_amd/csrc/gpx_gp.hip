@@ -149,6 +149,41 @@ bool kernel_values_finite(int kernel, const double *p, double s, int dtype)
     return dtype == GPX_F32 ? kernel_values_finite_t<float>(kernel, p, s) : kernel_values_finite_t<double>(kernel, p, s);
 }
 
+// ---- predictive variance: the row chunking -------------------------------------------------------------------------
+// Rows per chunk without an explicit request: capped, because a chunk beyond a few thousand rows buys nothing (the TRSM's
+// far updates already fill the chip; DESIGN 4 has the measurement behind the figure) and costs HBM.
+constexpr int64_t VAR_CHUNK_ALIGN = 128, VAR_CHUNK_CAP = 4096;
+
+// One chunk's device memory: the rows x lda chunk of Kxox that is solved in place, and the rows x TRSV_OPS_BLOCK block the
+// operator route of the solve stages its in-block product in.  (xo and the result are O(m d) and O(m): not chunked.)
+int var_plan(int dtype, int64_t n, int64_t m, int64_t chunk_rows, size_t free_bytes, int64_t *rows, int64_t *chunks, size_t *bytes)
+{
+    if (!(dtype == GPX_F64 || dtype == GPX_F32)) { set_error("var plan: dtype must be GPX_F64 or GPX_F32"); return GPX_ERR_ARG; }
+    if (n < 1 || m < 0) { set_error("var plan: need n >= 1 and m >= 0"); return GPX_ERR_ARG; }
+    if (chunk_rows < 0 || chunk_rows % VAR_CHUNK_ALIGN != 0) {
+        set_error("var plan: chunk_rows must be 0 (automatic) or a multiple of %d (got %lld)", (int)VAR_CHUNK_ALIGN, (long long)chunk_rows);
+        return GPX_ERR_ARG;
+    }
+    const size_t per_row = (size_t)(round_up(n, 16) + TRSV_OPS_BLOCK) * esize(dtype), budget = free_bytes / 4;
+    const int64_t fit = (int64_t)std::min<size_t>(budget / per_row, (size_t)1 << 40) / VAR_CHUNK_ALIGN * VAR_CHUNK_ALIGN;
+    if (fit < VAR_CHUNK_ALIGN) {
+        set_error("var plan: not even %d rows of %lld columns fit a quarter of the free device memory (%zu bytes free)",
+                  (int)VAR_CHUNK_ALIGN, (long long)n, free_bytes);
+        return GPX_ERR_NOMEM;
+    }
+    int64_t r = chunk_rows ? chunk_rows : std::min(fit, VAR_CHUNK_CAP);
+    if (m > 0 && m <= r) r = m;                            // one chunk: exactly the rows there are
+    if ((size_t)r * per_row > budget) {
+        set_error("var plan: chunk_rows = %lld needs %zu bytes, more than a quarter of the free device memory (%zu bytes free)",
+                  (long long)chunk_rows, (size_t)r * per_row, free_bytes);
+        return GPX_ERR_NOMEM;
+    }
+    if (rows) *rows = r;
+    if (chunks) *chunks = cdiv(m, r);
+    if (bytes) *bytes = (size_t)r * per_row;
+    return GPX_OK;
+}
+
 static const char *NONFINITE_MSG = "array must not contain infs or NaNs";      // scipy's text (gp/gp.py:294, 332-334)
 
 #define GP_NEED_FINITE_Y(g)                                                    \
@@ -505,6 +540,79 @@ int gpx_gp_cov_from_K(gpx_gp_t *g, const double *Kxox, const double *Kxoxo, int6
     GPX_TRY(trsm_right_lt(g->dtype, g->A, n, g->lda, X.p, m, ldx, g->st, 0, &g->ops));
     GPX_TRY(gemm_nt(g->dtype, m, m, n, X.p, ldx, X.p, ldx, C.p, ldc, -1.0, GPX_FULL, 0, 0, g->st));
     return download_f64(g->dtype, out, m, C.p, ldc, m, m, 0, g->st);
+}
+
+// Predictive variance, diag of RW06 eq. 2.24, in row chunks: X = K(xo_c, x) (or the caller's rows of Kxox), X <- X L^-T
+// where gpx_gp_cov runs it (the same operators), out_c = kdiag_c - rowsumsq(X).  One chunk buffer, one double[m] of results,
+// one download; nothing m x m exists anywhere.  Kxox != NULL: the plugin form (kdiag is then the caller's too).
+static int gp_var_impl(gpx_gp *g, const double *xo, const double *Kxox, const double *kdiag, int64_t m, int64_t chunk_rows, double *out)
+{
+    const size_t es = esize(g->dtype);
+    const int64_t n = g->n, ldx = g->lda;
+    size_t freeb = 0, totalb = 0;
+    GPX_HIP(hipMemGetInfo(&freeb, &totalb));
+    int64_t rows = 0, chunks = 0;
+    GPX_TRY(var_plan(g->dtype, n, m, chunk_rows, freeb, &rows, &chunks, nullptr));
+    DevBuf dxo, X, dvar, dk, stage;
+    GPX_TRY(X.alloc((size_t)rows * ldx * es));
+    GPX_TRY(dvar.alloc((size_t)m * sizeof(double)));
+    if (Kxox) {
+        GPX_TRY(dk.alloc((size_t)m * sizeof(double)));
+        GPX_HIP(hipMemcpyAsync(dk.p, kdiag, (size_t)m * sizeof(double), hipMemcpyHostToDevice, g->st));
+        if (g->dtype == GPX_F32) GPX_TRY(stage.alloc((size_t)rows * n * sizeof(double)));
+    } else {
+        GPX_TRY(dxo.alloc((size_t)m * g->d * es));
+        GPX_TRY(upload_f64(g->dtype, dxo.p, xo, m * g->d, g->st));
+    }
+    for (int64_t c = 0; c < chunks; ++c) {
+        const int64_t r0 = c * rows, rc = std::min(rows, m - r0);
+        route_hit(RT_VAR_CHUNK);
+        const void *xo_c = nullptr;
+        if (!Kxox) {
+            xo_c = (const char *)dxo.p + (size_t)r0 * g->d * es;
+            GPX_TRY(kmat(g->dtype, g->kernel, GPX_K, xo_c, rc, g->x, n, g->d, g->params, 0.0, GPX_FULL, X.p, ldx, g->st));
+        } else if (g->dtype == GPX_F64) {
+            GPX_HIP(hipMemcpy2DAsync(X.p, (size_t)ldx * 8, Kxox + r0 * n, (size_t)n * 8, (size_t)n * 8, (size_t)rc, hipMemcpyHostToDevice, g->st));
+        } else {
+            GPX_HIP(hipMemcpyAsync(stage.p, Kxox + r0 * n, (size_t)rc * n * 8, hipMemcpyHostToDevice, g->st));
+            for (int64_t r = 0; r < rc; ++r)
+                hipLaunchKernelGGL((cvt_from_f64<float>), dim3((unsigned)cdiv(n, 256)), dim3(256), 0, g->st,
+                                   (const double *)stage.p + r * n, (float *)X.p + r * ldx, n);
+            GPX_LAUNCH_CHECK();
+        }
+        GPX_TRY(trsm_right_lt(g->dtype, g->A, n, g->lda, X.p, rc, ldx, g->st, 0, &g->ops));
+        GPX_TRY(var_rows(g->dtype, g->kernel, X.p, rc, n, ldx, xo_c, g->d, g->params, Kxox ? (const double *)dk.p + r0 : nullptr, 0,
+                         (double *)dvar.p + r0, g->st));
+    }
+    GPX_HIP(hipMemcpyAsync(out, dvar.p, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, g->st));
+    GPX_HIP(hipStreamSynchronize(g->st));
+    return GPX_OK;
+}
+
+int gpx_gp_var(gpx_gp_t *g, const double *xo, int64_t m, int64_t chunk_rows, double *out)
+{
+    GP_ENTER(g);
+    GPX_ARG(g && g->fitted, "gp is not fitted");
+    GPX_ARG(m >= 0 && (m == 0 || (xo && out)), "bad arguments");
+    GPX_ARG(chunk_rows >= 0 && chunk_rows % VAR_CHUNK_ALIGN == 0, "chunk_rows must be 0 (automatic) or a multiple of 128");
+    if (m == 0) return GPX_OK;
+    return gp_var_impl(g, xo, nullptr, nullptr, m, chunk_rows, out);
+}
+
+int gpx_gp_var_from_K(gpx_gp_t *g, const double *Kxox, const double *kdiag, int64_t m, int64_t chunk_rows, double *out)
+{
+    GP_ENTER(g);
+    GPX_ARG(g && g->fitted, "gp is not fitted");
+    GPX_ARG(m >= 0 && (m == 0 || (Kxox && kdiag && out)), "bad arguments");
+    GPX_ARG(chunk_rows >= 0 && chunk_rows % VAR_CHUNK_ALIGN == 0, "chunk_rows must be 0 (automatic) or a multiple of 128");
+    if (m == 0) return GPX_OK;
+    return gp_var_impl(g, nullptr, Kxox, kdiag, m, chunk_rows, out);
+}
+
+int gpx_debug_var_plan(int dtype, int64_t n, int64_t m, int64_t chunk_rows, size_t free_bytes,
+                       int64_t *rows_per_chunk, int64_t *chunks, size_t *bytes_per_chunk)
+{
+    return var_plan(dtype, n, m, chunk_rows, free_bytes, rows_per_chunk, chunks, bytes_per_chunk);
 }
 
 int gpx_gp_get_Kxx(gpx_gp_t *g, double *out, int64_t ld)

@@ -200,7 +200,7 @@ struct gpx_mg {
     // device state
     void *A = nullptr, *pbuf[2] = {nullptr, nullptr}, *x = nullptr, *y = nullptr, *alpha = nullptr, *tmp = nullptr;
     double *scal = nullptr;                       // scal: [0] logdet block [1] y^T alpha [2] logdet acc [3] spare
-                                                  // [4, 12) gpx_mg_cov's agreement vector (mg_cov_agree)
+                                                  // [4, 15) gpx_mg_cov's / gpx_mg_var's agreement vector (mg_cov_agree)
     int *info = nullptr;                          // [0] info [1] reduction key
     hipStream_t S = nullptr, Q = nullptr, B = nullptr;   // main (updates, solves) / panel (factor, pack) / panel broadcasts
     hipStream_t O = nullptr;                      // lowest priority: the diagonal blocks' solve operators, off the panel chain
@@ -659,7 +659,7 @@ static int mg_alloc(gpx_mg *g)
     MG_ALLOC(y, (size_t)n * es);
     MG_ALLOC(alpha, (size_t)n * es);
     MG_ALLOC(tmp, (size_t)g->nb * es);
-    MG_ALLOC(scal, 12 * sizeof(double));
+    MG_ALLOC(scal, 16 * sizeof(double));
     MG_ALLOC(info, 4 * sizeof(int));
 #undef MG_ALLOC
     GPX_HIP(hipMemset(g->info, 0, 4 * sizeof(int)));
@@ -726,21 +726,27 @@ static double mg_hash(const void *p, size_t bytes)
     return (double)(h >> 12);
 }
 
-// Every rank's local verdict and arguments, one F64 MAX all-reduce, the same status on every rank.  v (host, 8 values):
+// Every rank's local verdict and arguments, one F64 MAX all-reduce, the same status on every rank.  v (host, nv values):
 // [0] a local allocation failed [1] a local argument is bad [2] m [3] -m [4] hash(xo) [5] -hash(xo) [6] hash(params)
-// [7] -hash(params); (x, -x) agree on every rank iff max(x) == -max(-x).
-static int mg_cov_agree(gpx_mg *g, double v[8])
+// [7] -hash(params); (x, -x) agree on every rank iff max(x) == -max(-x).  gpx_mg_var (nv = MG_VAR_AGREE) adds
+// [8] chunk_rows [9] -chunk_rows [10] -(rows per chunk this rank's free memory allows): -max = the smallest of them.
+constexpr int MG_COV_AGREE = 8, MG_VAR_AGREE = 11;
+static int mg_cov_agree(gpx_mg *g, double *v, int nv = MG_COV_AGREE, const char *who = "gpx_mg_cov")
 {
     double *dv = g->scal + 4;
-    GPX_HIP(hipMemcpyAsync(dv, v, 8 * sizeof(double), hipMemcpyHostToDevice, g->S));
-    GPX_TRY(mg_allreduce(g, dv, 8, GPX_F64, 1, g->S));
-    GPX_HIP(hipMemcpyAsync(v, dv, 8 * sizeof(double), hipMemcpyDeviceToHost, g->S));
+    GPX_HIP(hipMemcpyAsync(dv, v, nv * sizeof(double), hipMemcpyHostToDevice, g->S));
+    GPX_TRY(mg_allreduce(g, dv, nv, GPX_F64, 1, g->S));
+    GPX_HIP(hipMemcpyAsync(v, dv, nv * sizeof(double), hipMemcpyDeviceToHost, g->S));
     GPX_HIP(hipStreamSynchronize(g->S));
-    if (v[0] != 0) { set_error("gpx_mg_cov: a device allocation failed on at least one rank"); return GPX_ERR_NOMEM; }
-    if (v[1] != 0) { set_error("gpx_mg_cov: bad arguments on at least one rank (m < 0 or a NULL pointer)"); return GPX_ERR_ARG; }
-    if (v[2] != -v[3]) { set_error("gpx_mg_cov: the ranks called with different m (%.0f .. %.0f)", -v[3], v[2]); return GPX_ERR_ARG; }
-    if (v[4] != -v[5]) { set_error("gpx_mg_cov: the ranks called with different xo"); return GPX_ERR_ARG; }
-    if (v[6] != -v[7]) { set_error("gpx_mg_cov: the ranks called with different params"); return GPX_ERR_ARG; }
+    if (v[0] != 0) { set_error("%s: a device allocation failed on at least one rank", who); return GPX_ERR_NOMEM; }
+    if (v[1] != 0) {
+        set_error("%s: bad arguments on at least one rank (m < 0 or a NULL pointer%s)", who, nv > MG_COV_AGREE ? ", or a chunk_rows that is not a multiple of 128" : "");
+        return GPX_ERR_ARG;
+    }
+    if (v[2] != -v[3]) { set_error("%s: the ranks called with different m (%.0f .. %.0f)", who, -v[3], v[2]); return GPX_ERR_ARG; }
+    if (v[4] != -v[5]) { set_error("%s: the ranks called with different xo", who); return GPX_ERR_ARG; }
+    if (v[6] != -v[7]) { set_error("%s: the ranks called with different params", who); return GPX_ERR_ARG; }
+    if (nv > MG_COV_AGREE && v[8] != -v[9]) { set_error("%s: the ranks called with different chunk_rows (%.0f .. %.0f)", who, -v[9], v[8]); return GPX_ERR_ARG; }
     return GPX_OK;
 }
 
@@ -766,7 +772,10 @@ static int mg_cov_update(gpx_mg *g, int64_t j, int64_t a, int64_t b, char *Bm, i
 // panel-broadcast stream of the fit) carries the block reductions in block order on every rank; O accumulates X_j X_j^T
 // into C off the chain.  A look-ahead waits for the earlier rest updates (they reach block j + 1 too).
 // dxo: m x d on the device; Bm, C: this call's buffers.
-static int mg_cov_run(gpx_mg *g, const double *params, const void *dxo, int64_t m, char *Bm, void *C, int64_t ldc)
+// What becomes of a solved block X_j: C != NULL (gpx_mg_cov): C -= X_j X_j^T, C (m x ldc) starts as Kxoxo on rank 0 and is
+// sum-reduced at the end.  C == NULL (gpx_mg_var, m = one row chunk): acc[i] += sum_c X_j[i, c]^2 in f64 -- on O, which
+// takes a rank's blocks in block order -- and acc (m doubles) is sum-reduced at the end.
+static int mg_cov_run(gpx_mg *g, const double *params, const void *dxo, int64_t m, char *Bm, void *C, int64_t ldc, double *acc = nullptr)
 {
     hipStream_t S = g->S, Q = g->Q, R = g->B, O = g->O;
     const size_t es = g->es;
@@ -774,11 +783,12 @@ static int mg_cov_run(gpx_mg *g, const double *params, const void *dxo, int64_t 
     const int64_t full_end = g->kb(last) == nb ? nblk : last;      // blocks [0, full_end) are nb wide
     auto Bj = [&](int64_t j) { return Bm + (size_t)j * blk * es; };
     GPX_HIP(hipMemsetAsync(Bm, 0, (size_t)nblk * blk * es, S));
-    GPX_HIP(hipMemsetAsync(C, 0, (size_t)m * ldc * es, S));
+    if (C) GPX_HIP(hipMemsetAsync(C, 0, (size_t)m * ldc * es, S));
+    else GPX_HIP(hipMemsetAsync(acc, 0, (size_t)m * sizeof(double), S));
     for (int64_t j : g->my_blocks)
         GPX_TRY(kmat(g->dtype, g->kernel, GPX_K, dxo, m, (const char *)g->x + (size_t)g->k0(j) * g->d * es, g->kb(j), g->d,
                      params, 0.0, GPX_FULL, Bj(j), nb, S));
-    if (g->rank == 0)
+    if (C && g->rank == 0)
         GPX_TRY(kmat(g->dtype, g->kernel, GPX_K, dxo, m, dxo, m, g->d, params, 0.0, GPX_FULL, C, ldc, S));
     GPX_TRY(g->ev.order(S, R));
     for (int64_t j = 0; j < nblk; ++j) {
@@ -792,7 +802,8 @@ static int mg_cov_run(gpx_mg *g, const double *params, const void *dxo, int64_t 
         GPX_TRY(g->ev.order(R, Q));
         GPX_TRY(trsm_right_lt(g->dtype, g->Aat(k0, cl), kb, g->ld, Bj(j), m, nb, Q, 0, &g->ops[(size_t)(j / g->world)]));
         GPX_TRY(g->ev.order(Q, O));
-        GPX_TRY(gemm_nt(g->dtype, m, m, kb, Bj(j), nb, Bj(j), nb, C, ldc, -1.0, GPX_FULL, 0, 0, O));
+        if (C) GPX_TRY(gemm_nt(g->dtype, m, m, kb, Bj(j), nb, Bj(j), nb, C, ldc, -1.0, GPX_FULL, 0, 0, O));
+        else GPX_TRY(var_rows(g->dtype, g->kernel, Bj(j), m, kb, nb, nullptr, g->d, nullptr, nullptr, 1, acc, O));
         if (j == last) break;
         GPX_TRY(g->ev.order(Q, S));                               // X_j is final: the rest of the update may use it
         GPX_TRY(g->ev.order(S, Q));                               // (the earlier rest updates reach block j + 1)
@@ -804,7 +815,8 @@ static int mg_cov_run(gpx_mg *g, const double *params, const void *dxo, int64_t 
     GPX_TRY(g->ev.order(S, R));
     GPX_TRY(g->ev.order(Q, R));
     GPX_TRY(g->ev.order(O, R));
-    GPX_TRY(mg_allreduce(g, C, (size_t)m * ldc, g->dtype, 0, R));
+    if (C) GPX_TRY(mg_allreduce(g, C, (size_t)m * ldc, g->dtype, 0, R));
+    else GPX_TRY(mg_allreduce(g, acc, (size_t)m, GPX_F64, 0, R));
     GPX_TRY(g->ev.order(R, S));
     return GPX_OK;
 }
@@ -1175,6 +1187,64 @@ int gpx_mg_cov(gpx_mg_t *g, const double *params, const double *xo, int64_t m, d
     GPX_TRY(mg_upload(g, dxo.p, xo, (size_t)m * g->d));
     GPX_TRY(mg_cov_run(g, params, dxo.p, m, (char *)Bm.p, C.p, ldc));
     return mg_download(g, out, m, C.p, ldc, m, m);
+}
+
+// Predictive variance over the distributed factor: gpx_mg_cov's fan-in forward solve per row chunk of xo (Bm is m_c x n,
+// not m x n), the owners' row sums of squares instead of the SYRK, one F64 all-reduce of m_c values per chunk, then
+// k(xo_i, xo_i) - acc_i on every rank.  The ranks agree on the arguments AND on the chunking (the smallest of what their
+// free memories allow) before anything is enqueued; every rank allocates for its own figure, which is at least that.
+int gpx_mg_var(gpx_mg_t *g, const double *params, const double *xo, int64_t m, int64_t chunk_rows, double *out)
+{
+    MG_ENTER(g);
+    if (g->rehearse) { set_error("gpx_mg_var: a rehearsal handle holds one rank's share without a communicator"); return GPX_ERR_UNSUPPORTED; }
+    GPX_ARG(g->fitted, "mg is not fitted");                       // (the same on every rank: fit is collective)
+    if (g->info_host != 0) {                                      // (the reduced info word: the same on every rank)
+        set_error("gpx_mg_var: the factor is not positive definite (info = %d)", g->info_host);
+        return GPX_ERR_ARG;
+    }
+    const size_t es = g->es;
+    const int64_t ncols = g->nblk * g->nb;                        // columns of the block-major accumulator
+    size_t freeb = 0, totalb = 0;
+    GPX_HIP(hipMemGetInfo(&freeb, &totalb));
+    int64_t rows = 0;
+    const int plan_rc = m >= 0 ? var_plan(g->dtype, ncols, m, chunk_rows, freeb, &rows, nullptr, nullptr) : GPX_ERR_ARG;
+    const bool args_ok = m >= 0 && params && (m == 0 || (xo && out)) && plan_rc != GPX_ERR_ARG;
+    double v[MG_VAR_AGREE] = {plan_rc == GPX_ERR_NOMEM ? 1.0 : 0.0, args_ok ? 0.0 : 1.0, (double)m, -(double)m, 0.0, 0.0, 0.0, 0.0,
+                              (double)chunk_rows, -(double)chunk_rows, -(double)rows};
+    if (args_ok) {
+        v[4] = mg_hash(xo, (size_t)m * g->d * sizeof(double));
+        v[6] = mg_hash(params, (g->kernel == GPX_KERNEL_PERIODIC ? 3 : 2) * sizeof(double));
+    }
+    v[5] = -v[4]; v[7] = -v[6];
+    // everything this call allocates, before anything that depends on m is enqueued
+    DevBuf dxo, Bm, acc, dvar;
+    if (args_ok && m > 0 && plan_rc == GPX_OK) {
+        const bool ok = dxo.alloc((size_t)m * g->d * es) == GPX_OK && Bm.alloc((size_t)ncols * rows * es) == GPX_OK &&
+                        acc.alloc((size_t)rows * sizeof(double)) == GPX_OK && dvar.alloc((size_t)m * sizeof(double)) == GPX_OK &&
+                        g->ev.reserve((size_t)(6 * g->nblk + 8)) == GPX_OK;
+        if (!ok) { (void)hipGetLastError(); v[0] = 1.0; }
+    }
+    GPX_TRY(mg_cov_agree(g, v, MG_VAR_AGREE, "gpx_mg_var"));
+    if (m == 0) return GPX_OK;
+    rows = (int64_t)(-v[10]);                                     // the chunking every rank can hold
+    struct Drain {                                                // every stream idle before the buffers above are freed
+        gpx_mg *g;
+        ~Drain() { for (hipStream_t st : {g->S, g->Q, g->B, g->O}) (void)hipStreamSynchronize(st); }
+    } drain{g};
+    GPX_TRY(mg_upload(g, dxo.p, xo, (size_t)m * g->d));
+    for (int64_t r0 = 0; r0 < m; r0 += rows) {
+        const int64_t rc = std::min(rows, m - r0);
+        const void *xo_c = (const char *)dxo.p + (size_t)r0 * g->d * es;
+        route_hit(RT_VAR_CHUNK);
+        // (the chunk before has drained every stream: its events are free, and so is the accumulator)
+        for (hipStream_t st : {g->S, g->Q, g->B, g->O}) GPX_HIP(hipStreamSynchronize(st));
+        g->ev.rewind();
+        GPX_TRY(mg_cov_run(g, params, xo_c, rc, (char *)Bm.p, nullptr, 0, (double *)acc.p));
+        GPX_TRY(var_finish(g->dtype, g->kernel, xo_c, g->d, params, (const double *)acc.p, rc, (double *)dvar.p + r0, g->S));
+    }
+    GPX_HIP(hipMemcpyAsync(out, dvar.p, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, g->S));
+    GPX_HIP(hipStreamSynchronize(g->S));
+    return GPX_OK;
 }
 
 int gpx_mg_get_alpha(gpx_mg_t *g, double *out)

@@ -11,7 +11,9 @@
 // ONE batched launch (inv64_kernel); the solve then advances 512 columns per launch:
 // trsv_fwd_fused / trsv_bwd_fused (steps), or trsv_op_kernel with per-block operators
 // built once per factor ("operator form" below; who may use them: ops_usable).
+// var_rows_kernel (the predictive variance's finishing pass) reads a solved m x n chunk once: rows n sizeof(T) bytes.
 #include "gpx_common.h"
+#include "gpx_kernels_dev.h"
 #include "gpx_leaf.h"
 
 namespace gpx {
@@ -1038,11 +1040,143 @@ int dot(int dtype, const void *a, const void *b, int64_t n, double *out_dev, hip
     return GPX_OK;
 }
 
+// ---- predictive variance: the finishing pass over a solved chunk X = K(xo_c, x) L^-T ---------------------------------
+// k(xo_i, xo_i) as gpx_d_kmat builds it on its diagonal: the same accumulation of the distance (every term a_k - a_k:
+// 0 for finite points, NaN otherwise) through the same entry functions, in the handle's dtype.
+template <typename T>
+__device__ __forceinline__ T kdiag_entry(const KParams &kp, const T *__restrict__ a, int d)
+{
+    T acc = (T)0;
+    if (kp.kernel == GPX_KERNEL_GAUSSIAN) {
+        for (int k = 0; k < d; ++k) { const T t = a[k] - a[k]; acc = fma(t, t, acc); }
+        return gaussian_entry<T, 0>(acc, (T)kp.c[0], (T)kp.c[1], (T)kp.c[2], (T)kp.c[3]);
+    }
+    for (int k = 0; k < d; ++k) { const T sn = sin((T)0.5 * (a[k] - a[k]) / (T)kp.c[2]); acc = fma(sn, sn, acc); }
+    const T h = (T)kp.c[0], w = (T)kp.c[1];
+    return (h * h) * dev_exp<T>((T)-2.0 * acc / (w * w));
+}
+
+// One workgroup per row (grid-stride over rows): out[i] = kdiag(i) - sum_j X[i, j]^2, or out[i] += sum_j X[i, j]^2.
+// Bandwidth bound (rows n es bytes, read once): 16-byte loads, four in flight per lane; every lane sums its elements in
+// f64 in index order, the wave is folded by lanes64_sum, the four waves through LDS in wave order -- no atomics, the
+// same bits every time.  MODE 0: kdiag from kdiag_dev   1: kdiag from the kernel family at xo   2: accumulate.
+template <typename T, int MODE>
+__global__ __launch_bounds__(256) void var_rows_kernel(const T *__restrict__ X, int64_t rows, int64_t n, int64_t ldx,
+                                                       int aligned, const T *__restrict__ xo, int d, KParams kp,
+                                                       const double *__restrict__ kdiag, double *__restrict__ out)
+{
+    constexpr int VEC = Vec<T>::N;
+    typedef typename Vec<T>::type VT;
+    __shared__ double red[4];
+    const int tid = threadIdx.x;
+    const int64_t nv = aligned ? n / VEC : 0;              // whole 16-byte vectors of a row; the rest is the scalar tail
+    for (int64_t row = blockIdx.x; row < rows; row += gridDim.x) {
+        const T *__restrict__ xr = X + row * ldx;
+        const VT *__restrict__ xv = reinterpret_cast<const VT *>(xr);
+        double acc = 0.0;
+        int64_t v = tid;
+        for (; v + 3 * 256 < nv; v += 4 * 256) {
+            VT t[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) t[u] = xv[v + u * 256];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const T *e = reinterpret_cast<const T *>(&t[u]);
+#pragma unroll
+                for (int q = 0; q < VEC; ++q) acc = fma((double)e[q], (double)e[q], acc);
+            }
+        }
+        for (; v < nv; v += 256) {
+            const VT t = xv[v];
+            const T *e = reinterpret_cast<const T *>(&t);
+#pragma unroll
+            for (int q = 0; q < VEC; ++q) acc = fma((double)e[q], (double)e[q], acc);
+        }
+        for (int64_t c = nv * VEC + tid; c < n; c += 256) acc = fma((double)xr[c], (double)xr[c], acc);
+        acc = lanes64_sum(acc);
+        __syncthreads();                                   // (the row before: red[] has been read)
+        if ((tid & 63) == 0) red[tid >> 6] = acc;
+        __syncthreads();
+        if (tid == 0) {
+            const double s = ((red[0] + red[1]) + red[2]) + red[3];
+            if (MODE == 2) out[row] += s;
+            else if (MODE == 0) out[row] = kdiag[row] - s;
+            else out[row] = (double)kdiag_entry<T>(kp, xo + row * d, d) - s;
+        }
+    }
+}
+
+// out[i] = k(xo_i, xo_i) - acc[i]: the distributed form's last step, after the ranks' row sums have been added up
+template <typename T>
+__global__ void var_finish_kernel(const T *__restrict__ xo, int d, KParams kp, const double *__restrict__ acc, int64_t rows,
+                                  double *__restrict__ out)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < rows) out[i] = (double)kdiag_entry<T>(kp, xo + i * d, d) - acc[i];
+}
+
+template <typename T>
+static int launch_var_rows(const void *X, int64_t rows, int64_t n, int64_t ldx, const void *xo, int d, const KParams &kp,
+                           const double *kdiag_dev, int accumulate, double *out_dev, hipStream_t st)
+{
+    const int aligned = (ldx * (int64_t)sizeof(T)) % 16 == 0 && ((uintptr_t)X) % 16 == 0;
+    const dim3 grid((unsigned)std::min<int64_t>(rows, 1 << 20)), block(256);
+    ProfScope prof(PC_REDUCE, (double)rows * (double)n * sizeof(T), st);
+#define GPX_VAR_LAUNCH(MODE)                                                                                   \
+    hipLaunchKernelGGL((var_rows_kernel<T, MODE>), grid, block, 0, st, (const T *)X, rows, n, ldx, aligned,   \
+                       (const T *)xo, d, kp, kdiag_dev, out_dev)
+    if (accumulate) GPX_VAR_LAUNCH(2);
+    else if (kdiag_dev) GPX_VAR_LAUNCH(0);
+    else GPX_VAR_LAUNCH(1);
+#undef GPX_VAR_LAUNCH
+    GPX_LAUNCH_CHECK();
+    return GPX_OK;
+}
+
+int var_rows(int dtype, int kernel, const void *X, int64_t rows, int64_t n, int64_t ldx, const void *xo, int d,
+             const double *params, const double *kdiag_dev, int accumulate, double *out_dev, hipStream_t st)
+{
+    if (rows <= 0) return GPX_OK;
+    KParams kp;
+    memset(&kp, 0, sizeof(kp));
+    if (!accumulate && !kdiag_dev) GPX_TRY(make_kparams(kernel, GPX_K, params, 0.0, &kp));
+    if (dtype == GPX_F64) return launch_var_rows<double>(X, rows, n, ldx, xo, d, kp, kdiag_dev, accumulate, out_dev, st);
+    return launch_var_rows<float>(X, rows, n, ldx, xo, d, kp, kdiag_dev, accumulate, out_dev, st);
+}
+
+int var_finish(int dtype, int kernel, const void *xo, int d, const double *params, const double *acc_dev, int64_t rows,
+               double *out_dev, hipStream_t st)
+{
+    if (rows <= 0) return GPX_OK;
+    KParams kp;
+    GPX_TRY(make_kparams(kernel, GPX_K, params, 0.0, &kp));
+    const dim3 grid((unsigned)cdiv(rows, 256)), block(256);
+    if (dtype == GPX_F64)
+        hipLaunchKernelGGL((var_finish_kernel<double>), grid, block, 0, st, (const double *)xo, d, kp, acc_dev, rows, out_dev);
+    else
+        hipLaunchKernelGGL((var_finish_kernel<float>), grid, block, 0, st, (const float *)xo, d, kp, acc_dev, rows, out_dev);
+    GPX_LAUNCH_CHECK();
+    return GPX_OK;
+}
+
 }  // namespace gpx
 
 using namespace gpx;
 
 extern "C" {
+
+int gpx_d_var_rows(int dtype, int kernel, const void *X, int64_t rows, int64_t n, int64_t ldx, const void *xo, int d,
+                   const double *params, const double *kdiag_dev, double *out_dev, void *stream)
+{
+    GPX_ARG(dtype == GPX_F64 || dtype == GPX_F32, "dtype must be GPX_F64 or GPX_F32");
+    GPX_ARG(rows >= 0 && n >= 0 && ldx >= n, "need rows, n >= 0 and ldx >= n");
+    if (rows == 0) return GPX_OK;
+    GPX_ARG(out_dev && (n == 0 || X), "NULL pointer");
+    GPX_ARG(kdiag_dev || (xo && params && d >= 1), "need kdiag_dev, or xo, params and d >= 1");
+    GPX_ARG(kdiag_dev || kernel == GPX_KERNEL_GAUSSIAN || kernel == GPX_KERNEL_PERIODIC, "unknown kernel family");
+    GPX_TRY(ensure_device());
+    return var_rows(dtype, kernel, X, rows, n, ldx, xo, d, params, kdiag_dev, 0, out_dev, S(stream));
+}
 
 int gpx_d_trsv_lower(int dtype, const void *L, int64_t n, int64_t ldl, void *b, void *x,
                      int transpose, void *stream)

@@ -1,7 +1,7 @@
 """DistributedGP -- the drop-in `GP` interface on the multi-GPU fit.
 
 At the sizes the multi-GPU path exists for (K and its factor no longer fit one GPU's HBM), a user gets the same
-object as `gp.GP` -- ``log_lh``, ``lh``, ``inv_Kxx_y``, ``mean(xo)``, ``cov(xo)``, the setters, ``params`` /
+object as `gp.GP` -- ``log_lh``, ``lh``, ``inv_Kxx_y``, ``mean(xo)``, ``cov(xo)``, ``var(xo)``, ``predict(xo)``, the setters, ``params`` /
 ``set_param`` and the memoisation rules -- on top of one rank's `multi_gpu.NativeDistributedGP` handle:
 
     g = gp.DistributedGP(gp.GaussianKernel(1.0, 0.5), x, y, s=1.0, dist=dist)      # backend="rccl"
@@ -172,6 +172,22 @@ class DistributedGP(GP):
         xo, m = self._xo(xo)
         mg = self._fit_pd()
         return mg.cov(np.ascontiguousarray(self.K.params, dtype=DTYPE), xo.reshape(m, self._d))
+
+    def var(self, xo, noise=False, chunk_rows=0):
+        r"""Predictive variance at xo, ``(m,)`` on every rank (collective: gpx_mg_var, row chunks of xo over the
+        distributed factor; any m).  ``noise=True`` adds :math:`s^2`.  Not clamped at zero, as `GP.var`.  Ranks that
+        disagree on xo or chunk_rows raise `multi_gpu.RankMismatchError` together."""
+        xo, m = self._xo(xo)
+        mg = self._fit_pd()
+        out = mg.var(np.ascontiguousarray(self.K.params, dtype=DTYPE), xo.reshape(m, self._d), chunk_rows=chunk_rows)
+        if noise:
+            out += self._s ** 2
+        return out
+
+    def predict(self, xo, noise=False):
+        r"""``(mean(xo), var(xo, noise))`` (two collectives)."""
+        xo, _ = self._xo(xo)
+        return self.mean(xo), self.var(xo, noise=noise)
 
     def fit_timing(self):
         """This rank's stage times of the last fit, ms (`NativeDistributedGP.timing`)."""

@@ -490,6 +490,43 @@ class GP(object):
                                              _lib.dptr(out)))
         return out
 
+    #: plugin kernels: the host evaluates Kxox for `var` in row chunks of at most this many bytes
+    _VAR_HOST_CHUNK_BYTES = 256 << 20
+
+    def var(self, xo, noise=False, chunk_rows=0):
+        r"""Predictive variance, the diagonal of `cov(xo)` (RW06 eq. 2.24), ``(m,)`` -- at any `m`: the test points go
+        through the device in row chunks (:math:`X = K(x^*_c, x) L^{-\top}`, then
+        :math:`k(x^*_i, x^*_i) - \sum_j X_{ij}^2`), so nothing ``(m, m)`` and no whole ``(m, n)`` matrix exists on the
+        device, on the host or in between.  ``noise=True`` adds :math:`s^2` (the variance of a new observation).
+        ``chunk_rows``: rows per device chunk, 0 (automatic) or a multiple of 128.  Like the diagonal of `cov`, the
+        result is NOT clamped at zero: where the posterior variance is below the rounding error of the two terms it
+        may come out slightly negative."""
+        xo, m = self._xo(xo)                         # a bad shape raises before the library is touched
+        chunk_rows = int(chunk_rows)
+        if chunk_rows < 0 or chunk_rows % 128:
+            raise ValueError("invalid value for chunk_rows: %d (0, or a multiple of 128)" % chunk_rows)
+        st = self._fit_pd()
+        out = np.empty(m, dtype=DTYPE)
+        lib = _lib.load()
+        if getattr(self.K, "_native_kernel", None) is not None:
+            _lib.check(lib.gpx_gp_var(st.handle, _lib.dptr(xo), m, chunk_rows, _lib.dptr(out)))
+        else:
+            step = max(1, self._VAR_HOST_CHUNK_BYTES // (8 * self._n))
+            for r0 in range(0, m, step):
+                xc = xo[r0:r0 + step]
+                Kxox = np.ascontiguousarray(self.Kxox(xc), dtype=DTYPE)
+                kdiag = np.ascontiguousarray(self.K.diag(xc), dtype=DTYPE)
+                _lib.check(lib.gpx_gp_var_from_K(st.handle, _lib.dptr(Kxox), _lib.dptr(kdiag), xc.shape[0], chunk_rows,
+                                                 _lib.dptr(out[r0:r0 + step])))
+        if noise:
+            out += self._s ** 2
+        return out
+
+    def predict(self, xo, noise=False):
+        r"""``(mean(xo), var(xo, noise))``: the predictive mean and its error bar, both ``(m,)``."""
+        xo, _ = self._xo(xo)
+        return self.mean(xo), self.var(xo, noise=noise)
+
     def dm_dtheta(self, xo):
         r"""Derivative of the predictive mean w.r.t. the parameters, ``(n_p, m)``
         (gp/gp.py:627-662, gp_c.pyx:114-131)."""

@@ -40,6 +40,15 @@ def member_matrix(kernel_id, member, params, x1, x2, out):
     return out
 
 
+def self_distance(x):
+    """(n,) of x_i - x_i summed over the coordinates: 0 for a finite point, NaN for one that holds a NaN or an infinity
+    -- what the kernel-matrix build puts on the diagonal of K(x, x), so a closed-form `diag` keeps its NaNs."""
+    x, n, d = points(np.ascontiguousarray(x, dtype=DTYPE))
+    x = x.reshape(n, d)
+    with np.errstate(invalid="ignore"):
+        return (x - x).sum(axis=1)
+
+
 def positive_param(name, val):
     """Reference rule: a parameter below machine epsilon is invalid (gaussian.py:62-69)."""
     if val < EPS:

@@ -50,6 +50,15 @@ class Kernel(object):
     def __call__(self, x1, x2, out=None):
         return self.K(x1, x2, out=out)
 
+    def diag(self, x):
+        r"""``k(x_i, x_i)`` for every point of `x`, an ``(n,)`` array: the diagonal of ``K(x, x)`` without the matrix
+        (what `GP.var` needs of :math:`K(x^*, x^*)`).  The default evaluates ``K`` one point at a time; kernels with a
+        closed form override it."""
+        import numpy as np
+        x = np.asarray(x)
+        return np.array([np.asarray(self.K(x[i:i + 1], x[i:i + 1])).reshape(()) for i in range(x.shape[0])],
+                        dtype=np.float64)
+
     def jacobian(self, x1, x2, out=None):
         r"""(n_p, n, m) array of first parameter derivatives of the kernel matrix."""
         raise NotImplementedError

@@ -258,6 +258,21 @@ class NativeDistributedGP(object):
         self._check(rc)
         return out
 
+    def var(self, params, xo, chunk_rows=0):
+        """Posterior variance at xo, (m,), on every rank (gpx_mg_var: the fan-in solve of `cov` per row chunk of xo, row
+        sums of squares instead of the (m, m) product -- any m).  Collective, and the ranks agree first: m, xo, params or
+        chunk_rows that differ between ranks raise `RankMismatchError` on every rank."""
+        if self.info:                          # the reduced info word of the fit: the same on every rank
+            raise _lib.lapack_info_error(self.info)
+        p = np.ascontiguousarray(params, dtype=np.float64)
+        xo = np.ascontiguousarray(np.asarray(xo, dtype=np.float64).reshape(-1, self.d))
+        out = np.empty(xo.shape[0], dtype=np.float64)
+        rc = self.lib.gpx_mg_var(self.h, _lib.dptr(p), _lib.dptr(xo), xo.shape[0], int(chunk_rows), _lib.dptr(out))
+        if rc == _lib.ERR_ARG and (self._cb is None or self._cb.error is None):
+            raise RankMismatchError(_lib.last_error())    # (well-formed here, shaped above: the ranks disagreed)
+        self._check(rc)
+        return out
+
     @property
     def alpha(self):
         out = np.empty(self.n, dtype=np.float64)

@@ -187,6 +187,7 @@ int gpx_prof_read(int cls, double *launches, double *total_ms, double *total_wor
 #define GPX_ROUTE_FIT_OPS_AHEAD  12   /* gpx_gp_fit: block operators of the solves built beside the factorisation */
 #define GPX_ROUTE_TRSM_OPS       13   /* X L^-T (posterior covariance, inverse): in-block step as one product with inv(L_kk) */
 #define GPX_ROUTE_POTRF_PAIR     14   /* a factorisation that entered the pair phase: far trailing updates of depth K = 2048, one per two panels */
+#define GPX_ROUTE_VAR_CHUNK      15   /* predictive variance (gpx_gp_var, gpx_gp_var_from_K, gpx_mg_var): one hit per row chunk */
 int gpx_debug_route_count(int route, int64_t *count);
 /* roctx ranges pushed so far (GPX_ROCTX=1: every gpx_gp_* call and every launch class below it is a nested host range for
  * `rocprofv3 --marker-trace`; libroctx64.so is loaded on first use; 0 while the switch is off) */
@@ -299,6 +300,15 @@ int gpx_d_trsm_right_lt(int dtype, const void *L, int64_t n, int64_t ldl, void *
 int gpx_d_logdet_chol(int dtype, const void *L, int64_t n, int64_t ldl,
                       double *out_dev, void *stream);
 
+/* out_dev[i] = kdiag(i) - sum_j X[i, j]^2   for i < rows, j < n;  X: rows x n, ldx, handle dtype;  out_dev: DOUBLE
+ * kdiag(i): kdiag_dev[i] (double) when kdiag_dev != NULL, else K(xo[i,:], xo[i,:]) of the kernel family, evaluated by
+ * the same device function gpx_d_kmat uses (so it equals the diagonal of gpx_d_kmat(xo, xo) in that dtype).
+ * f64 accumulation for both dtypes, fixed summation order, no atomics: bitwise repeatable. */
+int gpx_d_var_rows(int dtype, int kernel, const void *X, int64_t rows, int64_t n, int64_t ldx, const void *xo, int d,
+                   const double *params, const double *kdiag_dev, double *out_dev, void *stream);
+/* (The finishing pass of the predictive variance, on a chunk X = K(xo_c, x) L^-T: rows n sizeof(T) bytes read once;
+ * 16-byte loads when ldx and X are 16-byte aligned, scalar loads otherwise.  GPX_PROF_REDUCE.) */
+
 /* out_dev[0] = sum_i a[i] * b[i]  (f64 accumulation).  np.dot(y, Kiy), gp_c.pyx:26 */
 int gpx_d_dot(int dtype, const void *a, const void *b, int64_t n, double *out_dev,
               void *stream);
@@ -344,6 +354,19 @@ int gpx_gp_cov(gpx_gp_t *gp, const double *xo, int64_t m, double *out);
 int gpx_gp_mean_from_K(gpx_gp_t *gp, const double *Kxox, int64_t m, double *out);
 int gpx_gp_cov_from_K(gpx_gp_t *gp, const double *Kxox, const double *Kxoxo, int64_t m,
                       double *out);
+/* diag of the posterior covariance at xo (m, d) HOST float64 -> out (m,) HOST float64, in row chunks:
+ * per chunk X = K(xo_c, x) (m_c x n), X <- X L^-T, out_c = k(xo_c, xo_c) - rowsumsq(X).  Device memory: one chunk
+ * (m_c x lda) whatever m.  chunk_rows: 0 = automatic, else a multiple of 128.  Same preconditions and errors as gpx_gp_cov. */
+int gpx_gp_var(gpx_gp_t *gp, const double *xo, int64_t m, int64_t chunk_rows, double *out);
+/* plugin kernels: the caller supplies Kxox (m, n) and kdiag (m,) = k(xo_i, xo_i), HOST float64 */
+int gpx_gp_var_from_K(gpx_gp_t *gp, const double *Kxox, const double *kdiag, int64_t m, int64_t chunk_rows, double *out);
+/* host arithmetic only (no GPU): the chunking of a call -- rows per chunk, number of chunks, device bytes per chunk */
+int gpx_debug_var_plan(int dtype, int64_t n, int64_t m, int64_t chunk_rows, size_t free_bytes,
+                       int64_t *rows_per_chunk, int64_t *chunks, size_t *bytes_per_chunk);
+/* The automatic rule: the largest multiple of 128 rows, at most 4096, whose buffers -- the chunk itself and the solve's
+ * staging block, (lda + 512) elements a row -- fit a quarter of free_bytes; m itself when all of m fits one chunk.
+ * GPX_ERR_ARG: chunk_rows < 0 or not a multiple of 128, m < 0, n < 1.  GPX_ERR_NOMEM: 128 rows (or the chunk asked for)
+ * do not fit.  The variance is not clamped at zero (neither is the diagonal of gpx_gp_cov). */
 /* copy-outs to HOST float64: Kxx is rebuilt (full, + s^2 I); L has zero upper */
 int gpx_gp_get_Kxx(gpx_gp_t *gp, double *out, int64_t ld);
 int gpx_gp_get_Lxx(gpx_gp_t *gp, double *out, int64_t ld);
@@ -476,6 +499,13 @@ int gpx_mg_mean(gpx_mg_t *mg, const double *params, const double *xo, int64_t m,
  * same status (GPX_ERR_ARG when m, xo or params differ between ranks, GPX_ERR_NOMEM when an allocation failed on one).
  * GPX_ERR_ARG after a fit that was not positive definite; GPX_ERR_UNSUPPORTED on a rehearsal handle. */
 int gpx_mg_cov(gpx_mg_t *mg, const double *params, const double *xo, int64_t m, double *out);
+/* Predictive variance at xo over the distributed factor -> out (m,) HOST float64 on every rank, the same bits everywhere.
+ * Collective.  gpx_mg_cov's fan-in forward solve per row chunk of xo (the accumulator is m_c x n instead of m x n), the
+ * block owners' row sums of squares (f64, block order) instead of the m x m product, ONE F64 sum all-reduce of m_c values
+ * per chunk.  chunk_rows as in gpx_gp_var; 0: the smallest of the ranks' automatic figures.  The ranks agree on m, xo,
+ * params and chunk_rows before any work (statuses as gpx_mg_cov: GPX_ERR_ARG when they differ or after a fit that was
+ * not positive definite, GPX_ERR_NOMEM when an allocation failed on one, GPX_ERR_UNSUPPORTED on a rehearsal handle). */
+int gpx_mg_var(gpx_mg_t *mg, const double *params, const double *xo, int64_t m, int64_t chunk_rows, double *out);
 int gpx_mg_get_alpha(gpx_mg_t *mg, double *out);
 int gpx_mg_scalars(gpx_mg_t *mg, double *logdet, double *yta, int *info);
 /* this rank's times of the last fit, ms (HIP events): [0] kernel build [1] factorisation [2] solves
