@@ -15,10 +15,10 @@ import logging
 from . import ext
 from .gp import GP
 from .dist_gp import DistributedGP
-from .kernels import Kernel, GaussianKernel, PeriodicKernel
+from .kernels import Kernel, GaussianKernel, PeriodicKernel, GaussianARDKernel
 from . import kernels
 
-__all__ = ["ext", "GP", "DistributedGP", "Kernel", "PeriodicKernel", "GaussianKernel"]
+__all__ = ["ext", "GP", "DistributedGP", "Kernel", "PeriodicKernel", "GaussianKernel", "GaussianARDKernel"]
 
 logger = logging.getLogger("gp")
 logger.setLevel("INFO")

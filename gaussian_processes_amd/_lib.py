@@ -20,7 +20,8 @@ ERR_ARG, ERR_HIP, ERR_NO_DEVICE, ERR_NOMEM, ERR_UNSUPPORTED, ERR_INTERNAL = -1, 
  ROUTE_GEMM_FAST, ROUTE_GEMM_GENERIC, ROUTE_SYRK_EXACT, ROUTE_SYRK_PATCH, ROUTE_MG_BCAST_ONE, ROUTE_MG_BCAST_SAG,
  ROUTE_FIT_OPS_AHEAD, ROUTE_TRSM_OPS, ROUTE_POTRF_PAIR, ROUTE_VAR_CHUNK) = range(16)
 F64, F32 = 0, 1
-KERNEL_GAUSSIAN, KERNEL_PERIODIC = 0, 1
+KERNEL_GAUSSIAN, KERNEL_PERIODIC, KERNEL_GAUSSIAN_ARD = 0, 1, 2
+ARD_MAX_D = 64
 FULL, LOWER = 0, 1
 (K, DK_DH, DK_DW, DK_DP, D2K_DHDH, D2K_DHDW, D2K_DHDP, D2K_DWDW, D2K_DWDP, D2K_DPDP) = range(10)
 MIN_LOG = -705.6238298100243
@@ -70,6 +71,7 @@ _SIGNATURES = {
     "gpx_prof_read": (c_int, [c_int, c_double_p, c_double_p, c_double_p]),
     "gpx_d_kmat": (c_int, [c_int, c_int, c_int, c_void_p, c_int64, c_void_p, c_int64, c_int,
                            c_double_p, c_double, c_int, c_void_p, c_int64, c_void_p]),
+    "gpx_d_scale_points": (c_int, [c_int, c_void_p, c_int64, c_int, c_double_p, c_void_p, c_void_p]),
     "gpx_d_mean": (c_int, [c_int, c_int, c_void_p, c_int64, c_void_p, c_int64, c_int, c_double_p,
                            c_void_p, c_void_p, c_void_p]),
     "gpx_d_mean_member": (c_int, [c_int, c_int, c_int, c_void_p, c_int64, c_void_p, c_int64, c_int, c_double_p,
@@ -100,6 +102,7 @@ _SIGNATURES = {
     "gpx_gp_set_data": (c_int, [c_void_p, c_double_p, c_double_p]),
     "gpx_gp_set_data_device": (c_int, [c_void_p, c_void_p, c_void_p]),
     "gpx_gp_set_params": (c_int, [c_void_p, c_double_p, c_double]),
+    "gpx_gp_get_params": (c_int, [c_void_p, c_double_p, c_int, c_int_p]),
     "gpx_gp_set_K": (c_int, [c_void_p, c_double_p, c_int64]),
     "gpx_gp_fit": (c_int, [c_void_p, c_int_p]),
     "gpx_gp_log_lh": (c_int, [c_void_p, c_double_p]),

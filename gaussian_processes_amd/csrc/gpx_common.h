@@ -251,6 +251,15 @@ int var_plan(int dtype, int64_t n, int64_t m, int64_t chunk_rows, size_t free_by
 int dloglh_reduce(int dtype, int kernel, const void *x, int64_t n, int d, const double *params,
                   const void *alpha, const void *W, int64_t ldw, double *partial_dev, double *out4,
                   hipStream_t st);
+// The Gaussian ARD family (gpx_kmat.hip): out <- x / w (w_host: d doubles; out may be x); the gradient's pass over W = K^-1
+// on the scaled points xs with iso = (h / sqrt(wbar), 1): out (host, d + 2) = [S_0, S_1 .. S_d, trace W].
+// dloglh_partial_doubles: the DEVICE doubles either reduction needs for its per-workgroup partial sums.
+int scale_points(int dtype, const void *x, int64_t n, int d, const double *w_host, void *out, hipStream_t st);
+// (h / sqrt(wbar), 1) of ARD parameters (h, w_1 ... w_d): wbar = exp(sum log w_k / d) in the host's double arithmetic
+void ard_iso(const double *params, int d, double *iso2);
+size_t dloglh_partial_doubles(int kernel, int d);
+int dloglh_reduce_ard(int dtype, const void *xs, int64_t n, int d, const double *iso, const void *alpha, const void *W,
+                      int64_t ldw, double *partial_dev, double *out, hipStream_t st);
 int kmat(int dtype, int kernel, int member, const void *x1, int64_t n, const void *x2, int64_t m,
          int d, const double *params, double diag_add, int tri, void *out, int64_t ld, hipStream_t st);
 

@@ -765,6 +765,10 @@ extern "C" {
 
 static int deriv_supported(gpx_gp_t *g)
 {
+    if (g->kernel == GPX_KERNEL_GAUSSIAN_ARD) {
+        set_error("second derivatives and dm_dtheta are not implemented for the ARD family (gpx_gp_dloglh_dtheta is)");
+        return GPX_ERR_UNSUPPORTED;
+    }
     if (g->kernel == GPX_KERNEL_PERIODIC && g->d != 1) {
         set_error("periodic derivative members need d == 1 (got %d)", g->d);
         return GPX_ERR_UNSUPPORTED;

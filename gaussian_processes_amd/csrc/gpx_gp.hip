@@ -83,7 +83,21 @@ int kmat(int dtype, int kernel, int member, const void *x1, int64_t n, const voi
     return gpx_d_kmat(dtype, kernel, member, x1, n, x2, m, d, params, diag_add, tri, out, ld, (void *)st);
 }
 
-static int nparams_of(int kernel) { return kernel == GPX_KERNEL_PERIODIC ? 3 : 2; }
+// ARD: the scaled points and the isotropic constants follow every change of x or of the widths
+int gp_rescale(gpx_gp *g)
+{
+    if (g->kernel != GPX_KERNEL_GAUSSIAN_ARD || !g->have_data || !g->have_params) return GPX_OK;
+    ard_iso(g->params, g->d, g->iso);
+    return scale_points(g->dtype, g->x, g->n, g->d, g->params + 1, g->xs, g->st);
+}
+
+// test points of a call: uploaded in the handle's dtype and, for the ARD family, scaled like the training points
+static int upload_points(gpx_gp *g, void *dst, const double *xo, int64_t m)
+{
+    GPX_TRY(upload_f64(g->dtype, dst, xo, m * g->d, g->st));
+    if (g->kernel == GPX_KERNEL_GAUSSIAN_ARD) GPX_TRY(scale_points(g->dtype, dst, m, g->d, g->params + 1, dst, g->st));
+    return GPX_OK;
+}
 
 int check_internal_info(int info)
 {
@@ -202,19 +216,21 @@ int gpx_gp_create(gpx_gp_t **out, int dtype, int kernel, int64_t n, int d)
     GPX_ARG(out, "gp is NULL");
     *out = nullptr;
     GPX_ARG(dtype == GPX_F64 || dtype == GPX_F32, "dtype must be GPX_F64 or GPX_F32");
-    GPX_ARG(kernel == GPX_KERNEL_GAUSSIAN || kernel == GPX_KERNEL_PERIODIC, "unknown kernel family");
+    GPX_ARG(kernel == GPX_KERNEL_GAUSSIAN || kernel == GPX_KERNEL_PERIODIC || kernel == GPX_KERNEL_GAUSSIAN_ARD, "unknown kernel family");
     GPX_ARG(n >= 1 && d >= 1, "need n >= 1 and d >= 1");
+    GPX_ARG(kernel != GPX_KERNEL_GAUSSIAN_ARD || d <= GPX_ARD_MAX_D, "the ARD family needs d <= GPX_ARD_MAX_D");
     gpx_gp *g = new gpx_gp();
     memset(g, 0, sizeof(*g));
     g->dtype = dtype; g->kernel = kernel; g->n = n; g->d = d;
     if (hipGetDevice(&g->device) != hipSuccess) { (void)hipGetLastError(); g->device = 0; }
-    g->nparams = nparams_of(kernel);
+    g->nparams = nparams_of(kernel, d);
     g->lda = round_up(n, 16);
     const size_t es = esize(dtype);
     int rc = GPX_OK;
     hipError_t e;
 #define GP_ALLOC(field, bytes) if (rc == GPX_OK) rc = dev_alloc((void **)&g->field, (bytes), "hipMalloc " #field)
     GP_ALLOC(x, (size_t)n * d * es);
+    if (kernel == GPX_KERNEL_GAUSSIAN_ARD) GP_ALLOC(xs, (size_t)n * d * es);
     GP_ALLOC(y, (size_t)n * es);
     GP_ALLOC(A, (size_t)(n + 1) * g->lda * es);          // (+ one row: the right-hand side rides along in the factorisation)
     GP_ALLOC(alpha, (size_t)n * es);
@@ -243,7 +259,7 @@ int gpx_gp_destroy(gpx_gp_t *g)
     stream_epoch_bump();                                       // (StreamTurn: a later stream at this one's address is a different stream)
     if (g->st_ops) { (void)hipStreamSynchronize(g->st_ops); (void)hipStreamDestroy(g->st_ops); }
     if (g->ev_ops) (void)hipEventDestroy(g->ev_ops);
-    for (void *b : {g->x, g->y, g->A, g->alpha, g->t0, g->t1, (void *)g->scal}) dev_free(b);    // gpx_gp_create's fixed-size fields
+    for (void *b : {g->x, g->xs, g->y, g->A, g->alpha, g->t0, g->t1, (void *)g->scal}) dev_free(b);    // gpx_gp_create's fixed-size fields
     for (GrowBuf *b : {&g->bw, &g->gw, &g->ops.mem, &g->bops.mem}) b->release();
     for (int i = 0; i < 6; ++i) if (g->ev[i]) (void)hipEventDestroy(g->ev[i]);
     if (g->st) (void)hipStreamDestroy(g->st);
@@ -258,6 +274,7 @@ int gpx_gp_set_data(gpx_gp_t *g, const double *x, const double *y)
     GPX_TRY(upload_f64(g->dtype, g->x, x, g->n * g->d, g->st));
     GPX_TRY(upload_f64(g->dtype, g->y, y, g->n, g->st));
     g->have_data = true; g->fitted = false;
+    GPX_TRY(gp_rescale(g));
     return gp_scan_finite(g);
 }
 
@@ -270,6 +287,7 @@ int gpx_gp_set_data_device(gpx_gp_t *g, const void *x_dev, const void *y_dev)
     GPX_HIP(hipMemcpyAsync(g->y, y_dev, (size_t)g->n * es, hipMemcpyDeviceToDevice, g->st));
     GPX_HIP(hipStreamSynchronize(g->st));      // the caller may free or overwrite the sources on return
     g->have_data = true; g->fitted = false;
+    GPX_TRY(gp_rescale(g));
     return gp_scan_finite(g);
 }
 
@@ -281,6 +299,16 @@ int gpx_gp_set_params(gpx_gp_t *g, const double *params, double s)
     for (int i = 0; i < g->nparams; ++i) g->params[i] = params[i];
     g->s = s;
     g->have_params = true; g->fitted = false; g->have_K = false;
+    return gp_rescale(g);
+}
+
+int gpx_gp_get_params(gpx_gp_t *g, double *params, int cap, int *count)
+{
+    GP_ENTER(g);
+    GPX_ARG(g->have_params, "no kernel parameters in the handle");
+    GPX_ARG(cap >= 0 && (cap == 0 || params), "bad arguments");
+    if (count) *count = g->nparams;
+    for (int i = 0; i < g->nparams && i < cap; ++i) params[i] = g->params[i];
     return GPX_OK;
 }
 
@@ -332,7 +360,8 @@ int gpx_gp_fit(gpx_gp_t *g, int *info)
             "set_data and set_params (or set_K) must be called before fit");
     // scipy.linalg.cholesky(Kxx, check_finite=True), gp/gp.py:294: a kernel matrix with NaN / inf entries is a
     // ValueError, not "not positive definite".  K is finite iff x, the kernel's constants and s^2 are.
-    if (!g->have_K && (!g->x_finite || !kernel_values_finite(g->kernel, g->params, g->s, g->dtype))) {
+    const GpView v = gp_view(g);
+    if (!g->have_K && (!g->x_finite || !kernel_values_finite(v.kernel, v.params, g->s, g->dtype))) {
         set_error("%s (%s)", NONFINITE_MSG, g->x_finite ? "kernel parameters or s" : "x");
         return GPX_ERR_ARG;
     }
@@ -342,7 +371,7 @@ int gpx_gp_fit(gpx_gp_t *g, int *info)
     GPX_HIP(hipEventRecord(g->ev[0], st));
     // Kxx = K(x, x) + s^2 I, lower triangle only (gp/gp.py:263-266)
     if (!g->have_K)
-        GPX_TRY(kmat(g->dtype, g->kernel, GPX_K, g->x, g->n, g->x, g->n, g->d, g->params, g->s * g->s,
+        GPX_TRY(kmat(g->dtype, v.kernel, GPX_K, v.x, g->n, v.x, g->n, g->d, v.params, g->s * g->s,
                      GPX_LOWER, g->A, g->lda, st));
     g->have_K = false;   // the factor overwrites it
     GPX_HIP(hipEventRecord(g->ev[1], st));
@@ -462,8 +491,9 @@ int gpx_gp_mean(gpx_gp_t *g, const double *xo, int64_t m, double *out)
     DevBuf dxo, dout;
     GPX_TRY(dxo.alloc((size_t)m * g->d * es));
     GPX_TRY(dout.alloc((size_t)m * es));
-    GPX_TRY(upload_f64(g->dtype, dxo.p, xo, m * g->d, g->st));
-    GPX_TRY(gpx_d_mean(g->dtype, g->kernel, dxo.p, m, g->x, g->n, g->d, g->params, g->alpha, dout.p,
+    GPX_TRY(upload_points(g, dxo.p, xo, m));
+    const GpView v = gp_view(g);
+    GPX_TRY(gpx_d_mean(g->dtype, v.kernel, dxo.p, m, v.x, g->n, g->d, v.params, g->alpha, dout.p,
                        (void *)g->st));
     return download_f64(g->dtype, out, 1, dout.p, 1, m, 1, 0, g->st);
 }
@@ -480,12 +510,13 @@ int gpx_gp_cov(gpx_gp_t *g, const double *xo, int64_t m, double *out)
     GPX_TRY(dxo.alloc((size_t)m * g->d * es));
     GPX_TRY(X.alloc((size_t)m * ldx * es));
     GPX_TRY(C.alloc((size_t)m * ldc * es));
-    GPX_TRY(upload_f64(g->dtype, dxo.p, xo, m * g->d, g->st));
+    GPX_TRY(upload_points(g, dxo.p, xo, m));
+    const GpView v = gp_view(g);
     // X = Kxox (m x n); V^T = X L^-T; cov = Kxoxo - V^T V   (gp/gp.py:622-625 without K^-1)
-    GPX_TRY(kmat(g->dtype, g->kernel, GPX_K, dxo.p, m, g->x, g->n, g->d, g->params, 0.0, GPX_FULL, X.p,
+    GPX_TRY(kmat(g->dtype, v.kernel, GPX_K, dxo.p, m, v.x, g->n, g->d, v.params, 0.0, GPX_FULL, X.p,
                  ldx, g->st));
     GPX_TRY(trsm_right_lt(g->dtype, g->A, g->n, g->lda, X.p, m, ldx, g->st, 0, &g->ops));
-    GPX_TRY(kmat(g->dtype, g->kernel, GPX_K, dxo.p, m, dxo.p, m, g->d, g->params, 0.0, GPX_FULL, C.p,
+    GPX_TRY(kmat(g->dtype, v.kernel, GPX_K, dxo.p, m, dxo.p, m, g->d, v.params, 0.0, GPX_FULL, C.p,
                  ldc, g->st));
     GPX_TRY(gemm_nt(g->dtype, m, m, g->n, X.p, ldx, X.p, ldx, C.p, ldc, -1.0, GPX_FULL, 0, 0, g->st));
     return download_f64(g->dtype, out, m, C.p, ldc, m, m, 0, g->st);
@@ -562,15 +593,16 @@ static int gp_var_impl(gpx_gp *g, const double *xo, const double *Kxox, const do
         if (g->dtype == GPX_F32) GPX_TRY(stage.alloc((size_t)rows * n * sizeof(double)));
     } else {
         GPX_TRY(dxo.alloc((size_t)m * g->d * es));
-        GPX_TRY(upload_f64(g->dtype, dxo.p, xo, m * g->d, g->st));
+        GPX_TRY(upload_points(g, dxo.p, xo, m));
     }
+    const GpView v = gp_view(g);
     for (int64_t c = 0; c < chunks; ++c) {
         const int64_t r0 = c * rows, rc = std::min(rows, m - r0);
         route_hit(RT_VAR_CHUNK);
         const void *xo_c = nullptr;
         if (!Kxox) {
             xo_c = (const char *)dxo.p + (size_t)r0 * g->d * es;
-            GPX_TRY(kmat(g->dtype, g->kernel, GPX_K, xo_c, rc, g->x, n, g->d, g->params, 0.0, GPX_FULL, X.p, ldx, g->st));
+            GPX_TRY(kmat(g->dtype, v.kernel, GPX_K, xo_c, rc, v.x, n, g->d, v.params, 0.0, GPX_FULL, X.p, ldx, g->st));
         } else if (g->dtype == GPX_F64) {
             GPX_HIP(hipMemcpy2DAsync(X.p, (size_t)ldx * 8, Kxox + r0 * n, (size_t)n * 8, (size_t)n * 8, (size_t)rc, hipMemcpyHostToDevice, g->st));
         } else {
@@ -581,7 +613,7 @@ static int gp_var_impl(gpx_gp *g, const double *xo, const double *Kxox, const do
             GPX_LAUNCH_CHECK();
         }
         GPX_TRY(trsm_right_lt(g->dtype, g->A, n, g->lda, X.p, rc, ldx, g->st, 0, &g->ops));
-        GPX_TRY(var_rows(g->dtype, g->kernel, X.p, rc, n, ldx, xo_c, g->d, g->params, Kxox ? (const double *)dk.p + r0 : nullptr, 0,
+        GPX_TRY(var_rows(g->dtype, v.kernel, X.p, rc, n, ldx, xo_c, g->d, v.params, Kxox ? (const double *)dk.p + r0 : nullptr, 0,
                          (double *)dvar.p + r0, g->st));
     }
     GPX_HIP(hipMemcpyAsync(out, dvar.p, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, g->st));
@@ -622,7 +654,8 @@ int gpx_gp_get_Kxx(gpx_gp_t *g, double *out, int64_t ld)
     const size_t es = esize(g->dtype);
     DevBuf K;
     GPX_TRY(K.alloc((size_t)g->n * g->lda * es));
-    GPX_TRY(kmat(g->dtype, g->kernel, GPX_K, g->x, g->n, g->x, g->n, g->d, g->params, g->s * g->s,
+    const GpView v = gp_view(g);
+    GPX_TRY(kmat(g->dtype, v.kernel, GPX_K, v.x, g->n, v.x, g->n, g->d, v.params, g->s * g->s,
                  GPX_FULL, K.p, g->lda, g->st));
     return download_f64(g->dtype, out, ld, K.p, g->lda, g->n, g->n, 0, g->st);
 }
@@ -657,14 +690,28 @@ int gpx_gp_get_inv_Kxx(gpx_gp_t *g, double *out, int64_t ld)
 
 // the reduction half of the gradient: W = K^-1 (lower triangle, n x ldw) is in HBM; one fused pass of (alpha alpha^T - W)
 // against the kernel derivatives evaluated on the fly (gp_c.pyx:34-49).  Synchronises g->st.
-static int grad_reduce(gpx_gp *g, const void *alpha, const double *params, double s_noise, const void *W, int64_t ldw, double *part,
-                       double *out)
+// pts: the points that go with `params` -- g->x, or for the ARD family x / w for THESE widths (the handle's xs, a batch row's copy)
+static int grad_reduce(gpx_gp *g, const void *pts, const void *alpha, const double *params, double s_noise, const void *W, int64_t ldw,
+                       double *part, double *out)
 {
     const int64_t n = g->n;
-    double *aa = part + 1024 * 4;
+    double *aa = part + dloglh_partial_doubles(g->kernel, g->d);
     GPX_TRY(dot(g->dtype, alpha, alpha, n, aa, g->st));
+    if (g->kernel == GPX_KERNEL_GAUSSIAN_ARD) {
+        // S_0, S_1 .. S_d, tr W from the device; dh = S_0 / h, dw_k = (S_k / w_k - S_0 / (d w_k)) / 2
+        const int d = g->d;
+        double iso[2], S[GPX_ARD_MAX_D + 2], ata = 0.0;
+        ard_iso(params, d, iso);
+        GPX_TRY(dloglh_reduce_ard(g->dtype, pts, n, d, iso, alpha, W, ldw, part, S, g->st));
+        GPX_HIP(hipMemcpyAsync(&ata, aa, sizeof(double), hipMemcpyDeviceToHost, g->st));
+        GPX_HIP(hipStreamSynchronize(g->st));
+        out[0] = S[0] / params[0];
+        for (int k = 0; k < d; ++k) out[1 + k] = 0.5 * (S[1 + k] / params[1 + k] - S[0] / ((double)d * params[1 + k]));
+        out[d + 1] = s_noise * (ata - S[d + 1]);
+        return GPX_OK;
+    }
     double p4[4];
-    GPX_TRY(dloglh_reduce(g->dtype, g->kernel, g->x, n, g->d, params, alpha, W, ldw, part, p4, g->st));
+    GPX_TRY(dloglh_reduce(g->dtype, g->kernel, pts, n, g->d, params, alpha, W, ldw, part, p4, g->st));
     double ata = 0.0;
     GPX_HIP(hipMemcpyAsync(&ata, aa, sizeof(double), hipMemcpyDeviceToHost, g->st));
     GPX_HIP(hipStreamSynchronize(g->st));
@@ -676,12 +723,12 @@ static int grad_reduce(gpx_gp *g, const void *alpha, const double *params, doubl
 // d log_lh / d(kernel params..., s) from a factor L (n x n, lower, in HBM) and alpha = K^-1 y: X = L^-T by the blocked
 // right-looking TRSM, W = K^-1 = X X^T (lower triangle, triangular k-loop) on the MFMA kernel, then ONE fused pass
 // reduces (alpha alpha^T - W) against the kernel derivatives evaluated on the fly.  X, W: n x lda scratch; part:
-// 1024 * 4 + 8 doubles; ops: the block operators of THIS factor (completed here).  Synchronises `g->st`.
-static int grad_from_factor(gpx_gp *g, const void *L, int64_t lda, const void *alpha, const double *params, double s_noise,
+// dloglh_partial_doubles() + 8 doubles; ops: the block operators of THIS factor (completed here).  Synchronises `g->st`.
+static int grad_from_factor(gpx_gp *g, const void *pts, const void *L, int64_t lda, const void *alpha, const double *params, double s_noise,
                             void *X, void *W, double *part, TrsvOps *ops, double *out)
 {
     GPX_TRY(inv_from_factor(g->dtype, L, g->n, lda, X, W, GPX_LOWER, g->st, ops));
-    return grad_reduce(g, alpha, params, s_noise, W, lda, part, out);
+    return grad_reduce(g, pts, alpha, params, s_noise, W, lda, part, out);
 }
 
 // Gradient of the log marginal likelihood w.r.t. (kernel params..., s), RW06 eq. 5.9
@@ -708,8 +755,8 @@ int gpx_gp_dloglh_dtheta(gpx_gp_t *g, double *out)
     DevBuf X, W, part;
     GPX_TRY(X.alloc((size_t)n * lda * es));
     GPX_TRY(W.alloc((size_t)n * lda * es));
-    GPX_TRY(part.alloc((size_t)1024 * 4 * sizeof(double) + 64));
-    return grad_from_factor(g, g->A, lda, g->alpha, g->params, g->s, X.p, W.p, (double *)part.p, &g->ops, out);
+    GPX_TRY(part.alloc(dloglh_partial_doubles(g->kernel, g->d) * sizeof(double) + 64));
+    return grad_from_factor(g, gp_view(g).x, g->A, lda, g->alpha, g->params, g->s, X.p, W.p, (double *)part.p, &g->ops, out);
 }
 
 // Batched ML-II step (BASELINE config 5; the reference's inner step "set params -> read log_lh",
@@ -736,7 +783,7 @@ static int fit_batch_impl(gpx_gp_t *g, const double *thetas, int64_t B, double *
         const size_t per_row = 2 * nl + (group_ok ? trsv_ops_bytes(g->dtype, g->n) : 0);
         int G = group_ok ? (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(8, B), (int64_t)((double)(freeg + g->gw.bytes) / 6.0 / (double)per_row))) : 1;
         if (g->gw_cap >= G && g->gw.p) G = g->gw_cap;
-        const size_t gneed = (size_t)G * per_row + (size_t)(1024 * 4 + 8) * sizeof(double) + 256;
+        const size_t gneed = (size_t)G * per_row + (dloglh_partial_doubles(g->kernel, g->d) + 8) * sizeof(double) + 256;
         GPX_TRY(g->gw.reserve(gneed, g->st));
         g->gw_cap = G;
     }
@@ -747,9 +794,12 @@ static int fit_batch_impl(gpx_gp_t *g, const double *thetas, int64_t B, double *
     const int64_t ride_max = tune().fit_ride_max;
     const bool ride = n <= ride_max;                      // y rides along as row n of every matrix (see gpx_gp_fit)
     const size_t per = (size_t)(n + (ride ? 1 : 0)) * lda * es;
+    // ARD: every row of a chunk has its own widths, so its own scaled copy of x (n x d) beside its matrix
+    const bool ard = g->kernel == GPX_KERNEL_GAUSSIAN_ARD;
+    const size_t xsz = ard ? ((size_t)n * g->d * es + 255) / 256 * 256 : 0;
     size_t freeb = 0, totalb = 0;
     GPX_HIP(hipMemGetInfo(&freeb, &totalb));
-    int64_t Bc = (int64_t)((double)freeb * 0.85 / (double)(per + 4 * (size_t)n * es + 64));
+    int64_t Bc = (int64_t)((double)freeb * 0.85 / (double)(per + xsz + 4 * (size_t)n * es + 64));
     if (tune().batch_max_set) Bc = std::min<int64_t>(Bc, std::max<int64_t>(1, tune().batch_max));
     Bc = std::max<int64_t>(1, std::min<int64_t>(Bc, B));
     if (!g->bw.p && (double)per > (double)freeb * 0.85) { set_error("fit_batch: not even one more n x n matrix fits in HBM"); return GPX_ERR_NOMEM; }
@@ -757,14 +807,15 @@ static int fit_batch_impl(gpx_gp_t *g, const double *thetas, int64_t B, double *
     // hipMalloc of tens of GB costs more than the factorisations)
     const size_t vec = ((size_t)n * es + 255) / 256 * 256;
     if (g->bw.p && g->bw_cap >= Bc) Bc = std::min<int64_t>(g->bw_cap, B);
-    const size_t need = (size_t)Bc * (per + 3 * vec) + (size_t)Bc * 2 * sizeof(double) + (size_t)Bc * sizeof(int) + 1024;
+    const size_t need = (size_t)Bc * (per + xsz + 3 * vec) + (size_t)Bc * 2 * sizeof(double) + (size_t)Bc * sizeof(int) + 1024;
     bool grew = false;
     GPX_TRY(g->bw.reserve(need, g->st, &grew));
     if (grew) g->bw_cap = Bc;
-    struct Ptr { void *p; } Ab, t0, t1, al, sc, inf;
+    struct Ptr { void *p; } Ab, xb, t0, t1, al, sc, inf;
     {
         char *w = (char *)g->bw.p;
         Ab.p = w; w += (size_t)Bc * per;
+        xb.p = w; w += (size_t)Bc * xsz;
         t0.p = w; w += (size_t)Bc * vec;
         t1.p = w; w += (size_t)Bc * vec;
         al.p = w; w += (size_t)Bc * vec;
@@ -784,10 +835,20 @@ static int fit_batch_impl(gpx_gp_t *g, const double *thetas, int64_t B, double *
             bool ok = th[np] >= 0 && std::isfinite(th[np]);
             for (int k = 0; k < np; ++k) ok = ok && std::isfinite(th[k]) && !(th[k] < eps);
             valid[i] = ok;
-            const double safe[3] = {1.0, 1.0, 1.0};      // an invalid row still takes part in the lock-step
+            double safe[1 + GPX_ARD_MAX_D];              // an invalid row still takes part in the lock-step
+            for (int k = 0; k < np; ++k) safe[k] = 1.0;
             const double *prm = ok ? th : safe;
             const double s = ok ? th[np] : 1.0;
-            GPX_TRY(kmat(g->dtype, g->kernel, GPX_K, g->x, n, g->x, n, g->d, prm, s * s, GPX_LOWER,
+            int kern = g->kernel;
+            const void *pts = g->x;
+            double iso[2];
+            if (ard) {
+                void *xi = (char *)xb.p + (size_t)i * xsz;
+                GPX_TRY(scale_points(g->dtype, g->x, n, g->d, prm + 1, xi, st));
+                ard_iso(prm, g->d, iso);
+                kern = GPX_KERNEL_GAUSSIAN; pts = xi; prm = iso;
+            }
+            GPX_TRY(kmat(g->dtype, kern, GPX_K, pts, n, pts, n, g->d, prm, s * s, GPX_LOWER,
                          (char *)Ab.p + (size_t)i * per, lda, st));
             char *rhs = ride ? (char *)Ab.p + (size_t)i * per + (size_t)n * lda * es : (char *)t0.p + (size_t)i * vec;
             GPX_HIP(hipMemcpyAsync(rhs, g->y, (size_t)n * es, hipMemcpyDeviceToDevice, st));
@@ -843,11 +904,12 @@ static int fit_batch_impl(gpx_gp_t *g, const double *thetas, int64_t B, double *
                     if (!valid[i] || hi[i] != 0) { for (int k = 0; k <= np; ++k) o[k] = NAN; continue; }
                     const double *th = thetas + (b0 + i) * (np + 1);
                     const void *alpha_i = (char *)al.p + (size_t)i * vec;
+                    const void *pts_i = ard ? (const void *)((char *)xb.p + (size_t)i * xsz) : (const void *)g->x;
                     if (lock_step) {
-                        GPX_TRY(grad_reduce(g, alpha_i, th, th[np], Ws + (size_t)(i - i0) * nl, lda, part, o));
+                        GPX_TRY(grad_reduce(g, pts_i, alpha_i, th, th[np], Ws + (size_t)(i - i0) * nl, lda, part, o));
                     } else {
                         g->bops.invalidate();
-                        GPX_TRY(grad_from_factor(g, (char *)Ab.p + (size_t)i * per, lda, alpha_i, th, th[np], Xs, Ws, part, &g->bops, o));
+                        GPX_TRY(grad_from_factor(g, pts_i, (char *)Ab.p + (size_t)i * per, lda, alpha_i, th, th[np], Xs, Ws, part, &g->bops, o));
                     }
                 }
             }

@@ -7,10 +7,12 @@ struct gpx_gp {
     int dtype, kernel, d, nparams;
     int64_t n, lda;
     void *x, *y, *A, *alpha, *t0, *t1;
+    void *xs;          // GPX_KERNEL_GAUSSIAN_ARD only: x / w, (n, d) in the handle's dtype (gp_rescale); null otherwise
     double *scal;      // device: [0] logdet [1] y^T alpha [2] spare ; int info at scal + 3
     hipStream_t st;
     hipEvent_t ev[6];
-    double params[3];
+    double params[1 + GPX_ARD_MAX_D];
+    double iso[2];     // GPX_KERNEL_GAUSSIAN_ARD: (h / sqrt(wbar), 1), the isotropic constants that go with xs
     double s;
     bool have_data, have_params, fitted, have_K;
     bool x_finite, y_finite;   // scipy's check_finite=True (gp/gp.py:294, 332-334): one O(n d) device reduction per set_data
@@ -30,6 +32,18 @@ struct gpx_gp {
 namespace gpx {
 // x_finite / y_finite of the handle from its device arrays (one O(n d) reduction; synchronous)
 int gp_scan_finite(gpx_gp *g);
+// kernel parameters of a family at dimension d
+static inline int nparams_of(int kernel, int d) { return kernel == GPX_KERNEL_GAUSSIAN_ARD ? 1 + d : (kernel == GPX_KERNEL_PERIODIC ? 3 : 2); }
+// The points and the two isotropic constants this handle's launches use: its own (x, params), or for the ARD family the
+// scaled points and (h / sqrt(wbar), 1) as GPX_KERNEL_GAUSSIAN  --  k_ard(a, b; h, w) = k_gaussian(a / w, b / w; h / sqrt(wbar), 1)
+struct GpView { int kernel; const void *x; const double *params; };
+static inline GpView gp_view(const gpx_gp *g)
+{
+    if (g->kernel == GPX_KERNEL_GAUSSIAN_ARD) return {GPX_KERNEL_GAUSSIAN, g->xs, g->iso};
+    return {g->kernel, g->x, g->params};
+}
+// ARD: xs <- x / w and iso, enqueued on the handle's stream, once data and parameters are both there (no-op otherwise)
+int gp_rescale(gpx_gp *g);
 }
 
 // every gpx_gp_* entry: the handle's device becomes current for the duration of the call, and the handle's stream takes

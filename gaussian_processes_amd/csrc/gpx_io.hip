@@ -68,6 +68,7 @@ static bool expected_file_bytes(const FactorHeader &hd, size_t es, unsigned long
 {
     const unsigned long long n = (unsigned long long)hd.n, d = (unsigned long long)hd.d, R = (unsigned long long)hd.block_rows;
     unsigned long long total = sizeof(FactorHeader) + 8ull * (n * d + 2 * n);
+    if (hd.kernel == GPX_KERNEL_GAUSSIAN_ARD && hd.nparams > 0) total += 8ull * d;          // the d widths behind the header
     for (unsigned long long r0 = 0; r0 < n; r0 += R) {
         const unsigned long long r1 = std::min(n, r0 + R);
         total += (r1 - r0) * r1 * es;
@@ -145,7 +146,9 @@ int gpx_gp_save(gpx_gp_t *g, const char *path)
     hd.nparams = g->have_params ? g->nparams : 0;          // 0: fitted from an uploaded matrix (plugin kernel)
     memcpy(&hd.info, &h4[3], sizeof(int));
     hd.n = n; hd.block_rows = io_block_rows(n, es);
-    for (int i = 0; i < 3; ++i) hd.params[i] = g->have_params ? g->params[i] : 0.0;
+    // (ARD: h in the header, its d widths right behind it; the other families' files are what they always were)
+    const bool ard = g->kernel == GPX_KERNEL_GAUSSIAN_ARD;
+    for (int i = 0; i < 3; ++i) hd.params[i] = (g->have_params && !(ard && i > 0)) ? g->params[i] : 0.0;
     hd.s = g->s; hd.logdet = h4[0]; hd.yta = h4[1];
     // written under a temporary name and renamed when complete: a failure never leaves a truncated checkpoint
     // under the final name
@@ -175,6 +178,7 @@ int gpx_gp_save(gpx_gp_t *g, const char *path)
     fp.f = fdopen(tfd, "wb");
     if (!fp.f) { (void)close(tfd); set_error("gpx_gp_save: cannot open %s for writing", tmp_path.c_str()); return GPX_ERR_ARG; }
     bool ok = fwrite(&hd, sizeof(hd), 1, fp.f) == 1;
+    if (ard && g->have_params) ok = ok && fwrite(g->params + 1, 8, (size_t)g->d, fp.f) == (size_t)g->d;
     std::vector<double> v;
     GPX_TRY(vec_d2h_f64(g, g->x, n * g->d, v)); ok = ok && fwrite(v.data(), 8, v.size(), fp.f) == v.size();
     GPX_TRY(vec_d2h_f64(g, g->y, n, v));        ok = ok && fwrite(v.data(), 8, v.size(), fp.f) == v.size();
@@ -241,12 +245,13 @@ int gpx_gp_load(gpx_gp_t **out, const char *path)
     // the header is not trusted: every field is checked, and the sizes it implies against the size of the file,
     // before anything is allocated from it
     const bool dtype_ok = hd.dtype == GPX_F64 || hd.dtype == GPX_F32;
-    const bool kernel_ok = hd.kernel == GPX_KERNEL_GAUSSIAN || hd.kernel == GPX_KERNEL_PERIODIC;
-    const int np_expected = hd.kernel == GPX_KERNEL_PERIODIC ? 3 : 2;
+    const bool ard = hd.kernel == GPX_KERNEL_GAUSSIAN_ARD;
+    const bool kernel_ok = hd.kernel == GPX_KERNEL_GAUSSIAN || hd.kernel == GPX_KERNEL_PERIODIC || (ard && hd.d >= 1 && hd.d <= GPX_ARD_MAX_D);
+    const int np_expected = kernel_ok ? nparams_of(hd.kernel, hd.d) : 0;
     bool fields_ok = dtype_ok && kernel_ok && hd.n >= 1 && hd.n <= ((int64_t)1 << 24) && hd.d >= 1 && hd.d <= 65536 &&
                      hd.block_rows >= 1 && hd.block_rows <= hd.n && (hd.nparams == 0 || hd.nparams == np_expected) &&
                      hd.info >= 0 && std::isfinite(hd.s) && hd.s >= 0;
-    for (int i = 0; i < hd.nparams && fields_ok; ++i) fields_ok = std::isfinite(hd.params[i]);
+    for (int i = 0; i < std::min(hd.nparams, ard ? 1 : 3) && fields_ok; ++i) fields_ok = std::isfinite(hd.params[i]);
     if (!fields_ok) { set_error("gpx_gp_load: %s has a corrupt header", path); return GPX_ERR_ARG; }
     {
         struct stat sb;
@@ -263,6 +268,12 @@ int gpx_gp_load(gpx_gp_t **out, const char *path)
     const int64_t n = g->n, lda = g->lda;
     const size_t es = esize(g->dtype);
     std::vector<double> v;
+    if (ard && hd.nparams > 0) {
+        g->params[0] = hd.params[0];
+        bool wok = fread(g->params + 1, 8, (size_t)hd.d, fp.f) == (size_t)hd.d;
+        for (int k = 0; k < hd.d && wok; ++k) wok = std::isfinite(g->params[1 + k]);
+        if (!wok) { set_error("gpx_gp_load: %s is truncated or holds corrupt widths", path); return GPX_ERR_ARG; }
+    }
     auto rd = [&](void *dev, int64_t count) -> int {
         v.resize((size_t)count);
         if (fread(v.data(), 8, v.size(), fp.f) != v.size()) { set_error("gpx_gp_load: %s is truncated", path); return GPX_ERR_ARG; }
@@ -300,9 +311,11 @@ int gpx_gp_load(gpx_gp_t **out, const char *path)
     double h4[4] = {hd.logdet, hd.yta, 0.0, 0.0};
     memcpy(&h4[3], &hd.info, sizeof(int));
     GPX_HIP(hipMemcpy(g->scal, h4, sizeof(h4), hipMemcpyHostToDevice));
-    for (int i = 0; i < 3; ++i) g->params[i] = hd.params[i];
+    if (!ard) for (int i = 0; i < 3; ++i) g->params[i] = hd.params[i];
     g->s = hd.s;
     g->have_data = true; g->have_params = hd.nparams > 0; g->fitted = true; g->have_K = false;
+    GPX_TRY(gp_rescale(g));                            // (ARD: the scaled points are not in the file)
+    GPX_HIP(hipStreamSynchronize(g->st));
     g->ops.invalidate();
     guard.g = nullptr;
     *out = g;
@@ -316,7 +329,7 @@ int gpx_gp_describe(gpx_gp_t *g, int *dtype, int *kernel, int64_t *n, int *d, do
     if (kernel) *kernel = g->kernel;
     if (n) *n = g->n;
     if (d) *d = g->d;
-    if (params3) for (int i = 0; i < 3; ++i) params3[i] = g->params[i];
+    if (params3) for (int i = 0; i < 3; ++i) params3[i] = (g->kernel == GPX_KERNEL_GAUSSIAN_ARD && i > 0) ? NAN : g->params[i];
     if (s) *s = g->s;
     return GPX_OK;
 }
@@ -353,6 +366,17 @@ int gpx_kmat_host(int kernel, int member, double *out, const double *x1, int64_t
         GPX_TRY(b.alloc((size_t)m * d * 8));
         GPX_HIP(hipMemcpy(b.p, x2, (size_t)m * d * 8, hipMemcpyHostToDevice));
         bp = b.p;
+    }
+    // ARD: both point sets scaled once, in place, then the isotropic build on (x1 / w, x2 / w; h / sqrt(wbar), 1)
+    double iso[2];
+    if (kernel == GPX_KERNEL_GAUSSIAN_ARD) {
+        if (member != GPX_K) { set_error("the ARD family has no member %d (GPX_K only)", member); return GPX_ERR_UNSUPPORTED; }
+        GPX_ARG(d <= GPX_ARD_MAX_D, "the ARD family needs d <= GPX_ARD_MAX_D");
+        GPX_TRY(scale_points(GPX_F64, a.p, n, d, params + 1, a.p, nullptr));
+        if (bp != a.p) GPX_TRY(scale_points(GPX_F64, b.p, m, d, params + 1, b.p, nullptr));
+        GPX_HIP(hipStreamSynchronize(nullptr));
+        ard_iso(params, d, iso);
+        kernel = GPX_KERNEL_GAUSSIAN; params = iso;
     }
     const int64_t npan = cdiv(n, R);
     GPX_TRY(o[0].alloc((size_t)R * ld * 8));

@@ -287,6 +287,44 @@ static int launch_kmat(const void *x1, int64_t n, const void *x2, int64_t m, int
 }
 
 // ---------------------------------------------------------------------------
+// Gaussian ARD (GPX_KERNEL_GAUSSIAN_ARD): k(a, b; h, w) = k_gaussian(a / w, b / w; h / sqrt(wbar), 1), so every build and
+// every prediction of the family runs the kernels above on SCALED points.  scale_points_kernel makes them: one thread per
+// point, the widths as a kernel argument read with a wave-uniform index (scalar loads), a true division (the fp64 result
+// is the correctly rounded quotient, numpy's x / w bit for bit).  In place is fine: a thread reads an element before
+// it writes it and nobody else touches it.
+// ---------------------------------------------------------------------------
+struct ArdWidths { double w[GPX_ARD_MAX_D]; };
+
+template <typename T>
+__global__ __launch_bounds__(256) void scale_points_kernel(const T *x, int64_t n, int d, ArdWidths aw, T *out)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    for (int k = 0; k < d; ++k) out[i * d + k] = x[i * d + k] / (T)aw.w[k];
+}
+
+void ard_iso(const double *params, int d, double *iso2)
+{
+    double sl = 0.0;
+    for (int k = 0; k < d; ++k) sl += log(params[1 + k]);
+    iso2[0] = params[0] / sqrt(exp(sl / (double)d));
+    iso2[1] = 1.0;
+}
+
+int scale_points(int dtype, const void *x, int64_t n, int d, const double *w_host, void *out, hipStream_t st)
+{
+    if (d < 1 || d > GPX_ARD_MAX_D) { set_error("scale_points: need 1 <= d <= %d (got %d)", GPX_ARD_MAX_D, d); return GPX_ERR_ARG; }
+    if (n <= 0) return GPX_OK;
+    ArdWidths aw;
+    for (int k = 0; k < GPX_ARD_MAX_D; ++k) aw.w[k] = k < d ? w_host[k] : 1.0;
+    const dim3 grid((unsigned)cdiv(n, 256)), block(256);
+    if (dtype == GPX_F64) hipLaunchKernelGGL((scale_points_kernel<double>), grid, block, 0, st, (const double *)x, n, d, aw, (double *)out);
+    else hipLaunchKernelGGL((scale_points_kernel<float>), grid, block, 0, st, (const float *)x, n, d, aw, (float *)out);
+    GPX_LAUNCH_CHECK();
+    return GPX_OK;
+}
+
+// ---------------------------------------------------------------------------
 // fused posterior mean: out[i] = sum_j K(xo[i], x[j]) * alpha[j]   (gp/gp.py:597)
 // Workgroup (bx, by) owns MP test points and the by-th slice of the training set,
 // which streams through LDS in chunks of 256 points (one per thread, transposed and
@@ -400,6 +438,7 @@ __global__ void mean_reduce_kernel(const double *__restrict__ partial, int nslic
 }
 
 static thread_local ThreadScratch g_mean_scr;   // the slice partial sums
+static thread_local ThreadScratch g_ard_scr;    // gpx_d_kmat on the ARD family: the scaled copies of its two point sets
 
 template <typename T>
 static int launch_mean(int kernel, const void *xo, int64_t m, const void *x, int64_t n, int d,
@@ -568,6 +607,8 @@ int dloglh_reduce(int dtype, int kernel, const void *x, int64_t n, int d, const 
     const int64_t ntr = cdiv(n, GR_T);
     const int blocks = (int)std::min<int64_t>(GR_BLOCKS, ntr * (ntr + 1) / 2);
     GPX_HIP(hipMemsetAsync(partial_dev, 0, (size_t)GR_BLOCKS * 4 * sizeof(double), st));
+    {
+    ProfScope prof(PC_REDUCE, 0.5 * (double)n * (double)(n + 1) * (double)es, st);      // the lower triangle of W, read once
     if (dtype == GPX_F64) {
         if (smem > 48 * 1024)
             GPX_HIP(hipFuncSetAttribute((const void *)dloglh_reduce_kernel<double>,
@@ -582,6 +623,7 @@ int dloglh_reduce(int dtype, int kernel, const void *x, int64_t n, int d, const 
                            (const float *)alpha, (const float *)W, ldw, gpar, ntr, partial_dev);
     }
     GPX_LAUNCH_CHECK();
+    }
     std::vector<double> host((size_t)GR_BLOCKS * 4);
     GPX_HIP(hipMemcpyAsync(host.data(), partial_dev, host.size() * sizeof(double), hipMemcpyDeviceToHost, st));
     GPX_HIP(hipStreamSynchronize(st));
@@ -589,6 +631,176 @@ int dloglh_reduce(int dtype, int kernel, const void *x, int64_t n, int d, const 
         double v = 0.0;
         for (int b = 0; b < GR_BLOCKS; ++b) v += host[(size_t)b * 4 + q];
         out4[q] = v;
+    }
+    return GPX_OK;
+}
+
+// ---------------------------------------------------------------------------
+// The same pass for the Gaussian ARD family (d + 1 kernel parameters): with t_k = (a_k - b_k) / w_k (the difference of the
+// SCALED points) and c_ab = wt (alpha_a alpha_b - W_ab) k_ab it accumulates
+//   S_0 = sum c_ab,   S_k = sum c_ab t_k^2  (k = 1 .. d),   tr W
+// from which the host forms dh = S_0 / h and dw_k = (S_k - S_0 / d) / (2 w_k)  (dk/dh = 2k/h, dk/dw_k = k (t_k^2 - 1/d) / w_k).
+// One read of W, nothing n x n x d anywhere, no atomics; the same fixed grid, tile walk and host summation as above, f64
+// sums for both dtypes: bitwise repeatable.
+// Per tile a thread (one column, 16 rows) first forms its 16 weights c_ab -- squared distance in T as the matrix build
+// forms it, one exp each -- and keeps them in registers, then walks the dimensions once more: S_k += sum_i c_i t_ik^2.
+// d is a run-time value and d accumulators indexed by a loop variable would live in scratch memory, so the kernel is
+// compiled for DMAX = 8, 16, 32, 64 accumulators and that loop is unrolled over DMAX with a uniform `k < d` guard: every
+// acc[k] is a register (no scratch: see DESIGN 3.4 for the compiler's resource line).  The staged points are zero beyond d.
+// ---------------------------------------------------------------------------
+template <typename T, int DMAX>
+__global__ __launch_bounds__(256) void dloglh_reduce_ard_kernel(const T *__restrict__ xs, int64_t n, int d,
+                                                                const T *__restrict__ alpha,
+                                                                const T *__restrict__ W, int64_t ldw, double c2,
+                                                                int64_t ntiles_r, double *__restrict__ partial)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    T *s1 = reinterpret_cast<T *>(smem_raw);          // [GR_T][DMAX]   rows
+    T *s2 = s1 + (size_t)GR_T * DMAX;                 // [DMAX][GR_T]   columns, transposed
+    T *sa1 = s2 + (size_t)GR_T * DMAX;                // alpha rows
+    T *sa2 = sa1 + GR_T;                              // alpha cols
+    __shared__ double red[4][DMAX + 2];
+    const int tid = threadIdx.x, col = tid & 63;
+    const int rg = __builtin_amdgcn_readfirstlane(tid >> 6);      // (the wave's index: uniform, so the row reads broadcast)
+    double acc[DMAX];
+#pragma unroll
+    for (int k = 0; k < DMAX; ++k) acc[k] = 0.0;
+    double acc0 = 0.0, acctr = 0.0;
+    const int64_t total = ntiles_r * (ntiles_r + 1) / 2;
+    for (int64_t t = blockIdx.x; t < total; t += gridDim.x) {
+        int64_t tr = (int64_t)((sqrt(8.0 * (double)t + 1.0) - 1.0) * 0.5);
+        while ((tr + 1) * (tr + 2) / 2 <= t) ++tr;
+        while (tr * (tr + 1) / 2 > t) --tr;
+        const int64_t tc = t - tr * (tr + 1) / 2;
+        const int64_t r0 = tr * GR_T, c0 = tc * GR_T;
+        __syncthreads();
+        for (int idx = tid; idx < GR_T * DMAX; idx += 256) {
+            const int r = idx / DMAX, k = idx - r * DMAX;
+            s1[idx] = (k < d && r0 + r < n) ? xs[(r0 + r) * d + k] : (T)0;
+            s2[(size_t)k * GR_T + r] = (k < d && c0 + r < n) ? xs[(c0 + r) * d + k] : (T)0;
+        }
+        if (tid < GR_T) {
+            sa1[tid] = (r0 + tid < n) ? alpha[r0 + tid] : (T)0;
+            sa2[tid] = (c0 + tid < n) ? alpha[c0 + tid] : (T)0;
+        }
+        __syncthreads();
+        const int64_t gc = c0 + col;
+        // the squared distances of this thread's 16 entries, accumulated as kmat_kernel accumulates them
+        T r2[16];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) r2[i] = (T)0;
+#pragma unroll 2
+        for (int k = 0; k < d; ++k) {
+            const T b = s2[(size_t)k * GR_T + col];
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                const T tt = s1[(rg + 4 * i) * DMAX + k] - b;
+                r2[i] = fma(tt, tt, r2[i]);
+            }
+        }
+        // the weights c_ab (0 for an entry outside the matrix or above the diagonal: W is only read inside the lower triangle)
+        double c[16];
+        const double ak = (double)sa2[col];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const int r = rg + 4 * i;
+            const int64_t gr = r0 + r;
+            double ci = 0.0;
+            if (gr < n && gc <= gr) {
+                const double wjk = (double)W[gr * ldw + gc];
+                const double coef = ((gc == gr) ? 1.0 : 2.0) * ((double)sa1[r] * ak - wjk);
+                if (gc == gr) acctr += wjk;
+                const double e = -0.5 * (double)r2[i];
+                if (!(e < GPX_MIN_LOG)) ci = coef * (c2 * exp(e));
+            }
+            c[i] = ci;
+            acc0 += ci;
+        }
+#pragma unroll
+        for (int k = 0; k < DMAX; ++k) {
+            if (k < d) {
+                const T b = s2[(size_t)k * GR_T + col];
+                double a = 0.0;
+#pragma unroll
+                for (int i = 0; i < 16; ++i) {
+                    const double tt = (double)(s1[(rg + 4 * i) * DMAX + k] - b);
+                    a = fma(c[i], tt * tt, a);
+                }
+                acc[k] += a;
+            }
+        }
+    }
+    // wave reduction (64 lanes), then across the 4 waves in a fixed order; slot 0: S_0, 1 .. DMAX: S_k, DMAX + 1: tr W
+    const bool lane0 = (tid & 63) == 0;
+    {
+        double v = acc0;
+        for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+        if (lane0) red[rg][0] = v;
+        v = acctr;
+        for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+        if (lane0) red[rg][DMAX + 1] = v;
+    }
+#pragma unroll
+    for (int k = 0; k < DMAX; ++k) {
+        double v = acc[k];
+        for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+        if (lane0) red[rg][1 + k] = v;
+    }
+    __syncthreads();
+    if (tid < d + 2) {
+        const int q = tid <= d ? tid : DMAX + 1;
+        partial[(int64_t)blockIdx.x * (d + 2) + tid] = ((red[0][q] + red[1][q]) + red[2][q]) + red[3][q];
+    }
+}
+
+template <typename T, int DMAX>
+static int launch_reduce_ard(const void *xs, int64_t n, int d, const void *alpha, const void *W, int64_t ldw, double c2,
+                             int64_t ntr, int blocks, double *partial_dev, hipStream_t st)
+{
+    const size_t smem = ((size_t)2 * GR_T * DMAX + 2 * GR_T) * sizeof(T);
+    if (smem > 48 * 1024)
+        GPX_HIP(hipFuncSetAttribute((const void *)dloglh_reduce_ard_kernel<T, DMAX>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+    hipLaunchKernelGGL((dloglh_reduce_ard_kernel<T, DMAX>), dim3(blocks), dim3(256), smem, st, (const T *)xs, n, d, (const T *)alpha,
+                       (const T *)W, ldw, c2, ntr, partial_dev);
+    GPX_LAUNCH_CHECK();
+    return GPX_OK;
+}
+
+template <typename T>
+static int launch_reduce_ard_d(const void *xs, int64_t n, int d, const void *alpha, const void *W, int64_t ldw, double c2,
+                               int64_t ntr, int blocks, double *partial_dev, hipStream_t st)
+{
+    if (d <= 8) return launch_reduce_ard<T, 8>(xs, n, d, alpha, W, ldw, c2, ntr, blocks, partial_dev, st);
+    if (d <= 16) return launch_reduce_ard<T, 16>(xs, n, d, alpha, W, ldw, c2, ntr, blocks, partial_dev, st);
+    if (d <= 32) return launch_reduce_ard<T, 32>(xs, n, d, alpha, W, ldw, c2, ntr, blocks, partial_dev, st);
+    return launch_reduce_ard<T, 64>(xs, n, d, alpha, W, ldw, c2, ntr, blocks, partial_dev, st);
+}
+
+size_t dloglh_partial_doubles(int kernel, int d) { return (size_t)GR_BLOCKS * (kernel == GPX_KERNEL_GAUSSIAN_ARD ? d + 2 : 4); }
+
+// xs: the SCALED points; iso: (h / sqrt(wbar), 1); partial_dev: dloglh_partial_doubles() of DEVICE memory;
+// out: host, d + 2 values [S_0, S_1 .. S_d, trace W]
+int dloglh_reduce_ard(int dtype, const void *xs, int64_t n, int d, const double *iso, const void *alpha, const void *W,
+                      int64_t ldw, double *partial_dev, double *out, hipStream_t st)
+{
+    if (d < 1 || d > GPX_ARD_MAX_D) { set_error("ARD gradient needs 1 <= d <= %d (got %d)", GPX_ARD_MAX_D, d); return GPX_ERR_ARG; }
+    const double c2 = 0.5 * sqrt(2.0 / M_PI) * iso[0] * iso[0] / iso[1];          // make_kparams, GPX_K
+    const int64_t ntr = cdiv(n, GR_T);
+    const int blocks = (int)std::min<int64_t>(GR_BLOCKS, ntr * (ntr + 1) / 2);
+    const size_t count = (size_t)GR_BLOCKS * (d + 2);
+    GPX_HIP(hipMemsetAsync(partial_dev, 0, count * sizeof(double), st));
+    {
+        ProfScope prof(PC_REDUCE, 0.5 * (double)n * (double)(n + 1) * (double)esize(dtype), st);
+        if (dtype == GPX_F64) GPX_TRY((launch_reduce_ard_d<double>(xs, n, d, alpha, W, ldw, c2, ntr, blocks, partial_dev, st)));
+        else GPX_TRY((launch_reduce_ard_d<float>(xs, n, d, alpha, W, ldw, c2, ntr, blocks, partial_dev, st)));
+    }
+    std::vector<double> host(count);
+    GPX_HIP(hipMemcpyAsync(host.data(), partial_dev, count * sizeof(double), hipMemcpyDeviceToHost, st));
+    GPX_HIP(hipStreamSynchronize(st));
+    for (int q = 0; q < d + 2; ++q) {
+        double v = 0.0;
+        for (int b = 0; b < GR_BLOCKS; ++b) v += host[(size_t)b * (d + 2) + q];
+        out[q] = v;
     }
     return GPX_OK;
 }
@@ -610,10 +822,37 @@ int gpx_d_kmat(int dtype, int kernel, int member, const void *x1, int64_t n, con
     GPX_ARG(tri == GPX_FULL || tri == GPX_LOWER, "tri must be GPX_FULL or GPX_LOWER");
     if (n == 0 || m == 0) return GPX_OK;
     GPX_ARG(x1 && x2 && out, "NULL pointer");
+    if (kernel == GPX_KERNEL_GAUSSIAN_ARD) {
+        // scale both point sets into this thread's scratch, then the isotropic build on (x1 / w, x2 / w; h / sqrt(wbar), 1)
+        if (member != GPX_K) { set_error("the ARD family has no member %d (GPX_K only)", member); return GPX_ERR_UNSUPPORTED; }
+        GPX_ARG(params, "params is NULL");
+        GPX_ARG(d <= GPX_ARD_MAX_D, "the ARD family needs d <= GPX_ARD_MAX_D");
+        gpx::StreamTurn turn__((hipStream_t)stream);     // (this thread's scratch buffers: one stream at a time, gpx_mem.h)
+        const size_t es = esize(dtype), b1 = ((size_t)n * d * es + 255) / 256 * 256;
+        const bool same = x2 == x1 && m == n;
+        void *scr = nullptr;
+        GPX_TRY(g_ard_scr.get(b1 + (same ? 0 : (size_t)m * d * es), &scr));
+        void *s1 = scr, *s2 = same ? scr : (void *)((char *)scr + b1);
+        GPX_TRY(scale_points(dtype, x1, n, d, params + 1, s1, S(stream)));
+        if (!same) GPX_TRY(scale_points(dtype, x2, m, d, params + 1, s2, S(stream)));
+        double iso[2];
+        ard_iso(params, d, iso);
+        return gpx_d_kmat(dtype, GPX_KERNEL_GAUSSIAN, member, s1, n, s2, m, d, iso, diag_add, tri, out, ld, stream);
+    }
     KParams kp;
     GPX_TRY(make_kparams(kernel, member, params, diag_add, &kp));
     if (dtype == GPX_F64) return launch_kmat<double>(x1, n, x2, m, d, kp, tri, out, ld, S(stream));
     return launch_kmat<float>(x1, n, x2, m, d, kp, tri, out, ld, S(stream));
+}
+
+int gpx_d_scale_points(int dtype, const void *x, int64_t n, int d, const double *w_host, void *out, void *stream)
+{
+    GPX_TRY(ensure_device());
+    GPX_ARG(dtype == GPX_F64 || dtype == GPX_F32, "dtype must be GPX_F64 or GPX_F32");
+    GPX_ARG(n >= 0 && d >= 1 && d <= GPX_ARD_MAX_D, "need n >= 0 and 1 <= d <= GPX_ARD_MAX_D");
+    if (n == 0) return GPX_OK;
+    GPX_ARG(x && w_host && out, "NULL pointer");
+    return scale_points(dtype, x, n, d, w_host, out, S(stream));
 }
 
 int gpx_d_mean_member(int dtype, int kernel, int member, const void *xo, int64_t m, const void *x,

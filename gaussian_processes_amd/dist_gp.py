@@ -36,6 +36,9 @@ def _native_kernel_id(K):
     if kid is None:
         raise TypeError("DistributedGP needs a built-in kernel (GaussianKernel or PeriodicKernel); %s is a Python "
                         "kernel plugin, which gp.GP supports on one GPU" % type(K).__name__)
+    if kid == _lib.KERNEL_GAUSSIAN_ARD:
+        raise NotImplementedError("DistributedGP does not support %s: the multi-GPU fit knows GaussianKernel and "
+                                  "PeriodicKernel only; gp.GP has the ARD family on one GPU" % type(K).__name__)
     return kid
 
 

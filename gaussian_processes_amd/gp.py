@@ -245,8 +245,13 @@ class GP(object):
     def _d(self):
         return 1 if self._x.ndim == 1 else self._x.shape[1]
 
+    def _is_ard(self):
+        return getattr(self.K, "_native_kernel", None) == _lib.KERNEL_GAUSSIAN_ARD
+
     def _state(self):
         kid = getattr(self.K, "_native_kernel", None)
+        if kid == _lib.KERNEL_GAUSSIAN_ARD and self._d != self.K.d:
+            raise ValueError("x has %d dimension(s), the kernel has %d width(s)" % (self._d, self.K.d))
         key = (self._dtype, _lib.KERNEL_GAUSSIAN if kid is None else kid, self._n, self._d,
                self._device)
         if self._dev is None or self._dev.key != key:
@@ -380,7 +385,7 @@ class GP(object):
         is never materialised); plugin kernels: the reference's formula with device products."""
         npar = len(self.params)
         native = getattr(self.K, "_native_kernel", None) is not None
-        if native and (self._d == 1 or self.K._native_kernel == _lib.KERNEL_GAUSSIAN):
+        if native and (self._d == 1 or self.K._native_kernel in (_lib.KERNEL_GAUSSIAN, _lib.KERNEL_GAUSSIAN_ARD)):
             st = self._fit()
             out = np.empty(npar, dtype=DTYPE)
             _lib.check(_lib.load().gpx_gp_dloglh_dtheta(st.handle, _lib.dptr(out)))
@@ -393,12 +398,16 @@ class GP(object):
     def _native_derivs(self):
         """True when the derivative stack can stay on the device (built-in kernel; periodic: 1-D)."""
         kid = getattr(self.K, "_native_kernel", None)
-        return kid is not None and (self._d == 1 or kid == _lib.KERNEL_GAUSSIAN)
+        return kid is not None and kid != _lib.KERNEL_GAUSSIAN_ARD and (self._d == 1 or kid == _lib.KERNEL_GAUSSIAN)
+
+    def _no_ard(self, name):
+        if self._is_ard():
+            raise NotImplementedError("%s is not implemented for GaussianARDKernel (dloglh_dtheta and dlh_dtheta are)" % name)
 
     @memoprop
     def dlh_dtheta(self):
         r"""Gradient of the marginal likelihood (gp/gp.py:435-465).  Native kernels: device resident."""
-        if self._native_derivs():
+        if self._native_derivs() or self._is_ard():
             # gp_c.pyx:52-67 is lh times gp_c.pyx:34-49 term by term: 0.5 lh (y^T K^-1 dK K^-1 y - tr(K^-1 dK))
             return np.asarray(self.lh * self.dloglh_dtheta, dtype=DTYPE)
         out, Ki = self._nan_or(len(self.params))
@@ -410,6 +419,7 @@ class GP(object):
     def d2lh_dtheta2(self):
         r"""Hessian of the marginal likelihood (gp/gp.py:467-502).  Native kernels: device resident
         (K^-1, the K^-1 dK_i products and all traces / quadratic forms stay in HBM)."""
+        self._no_ard("d2lh_dtheta2")
         if self._native_derivs():
             st = self._fit()
             npar = len(self.params)
@@ -431,6 +441,7 @@ class GP(object):
         the reference only offers the lh-scaled `d2lh_dtheta2`, which is identically zero once
         ``log_lh < MIN`` (any n beyond a few hundred).  ``d2lh / lh - (dlh / lh)(dlh / lh)^T`` from the
         same device pass (csrc/gpx_deriv.hip); native kernels only.  NaN when `Kxx` is not PD."""
+        self._no_ard("d2loglh_dtheta2")
         if not self._native_derivs():
             raise NotImplementedError("d2loglh_dtheta2 needs a built-in kernel (periodic: 1-D inputs)")
         st = self._fit()
@@ -530,6 +541,7 @@ class GP(object):
     def dm_dtheta(self, xo):
         r"""Derivative of the predictive mean w.r.t. the parameters, ``(n_p, m)``
         (gp/gp.py:627-662, gp_c.pyx:114-131)."""
+        self._no_ard("dm_dtheta")
         if self._native_derivs():
             st = self._fit_pd()                      # LinAlgError when not PD, as inv_Kxx raises in the reference
             xo, m = self._xo(xo)
@@ -572,9 +584,14 @@ class GP(object):
             y = np.empty(n.value, dtype=DTYPE)
             _lib.check(lib.gpx_gp_get_xy(h, _lib.dptr(x), _lib.dptr(y)))
             if K is None:
-                from .kernels import GaussianKernel, PeriodicKernel
-                K = GaussianKernel(*prm[:2]) if kid.value == _lib.KERNEL_GAUSSIAN else PeriodicKernel(*prm[:3])
-            obj = cls(K, x.ravel() if d.value == 1 else x, y, s=s.value,
+                from .kernels import GaussianKernel, PeriodicKernel, GaussianARDKernel
+                if kid.value == _lib.KERNEL_GAUSSIAN_ARD:
+                    full, cnt = np.zeros(1 + _lib.ARD_MAX_D), ctypes.c_int(0)
+                    _lib.check(lib.gpx_gp_get_params(h, _lib.dptr(full), full.size, ctypes.byref(cnt)))
+                    K = GaussianARDKernel(full[0], full[1:cnt.value])
+                else:
+                    K = GaussianKernel(*prm[:2]) if kid.value == _lib.KERNEL_GAUSSIAN else PeriodicKernel(*prm[:3])
+            obj = cls(K, x.ravel() if (d.value == 1 and kid.value != _lib.KERNEL_GAUSSIAN_ARD) else x, y, s=s.value,
                       dtype="float64" if dt.value == _lib.F64 else "float32", device=device)
             key = (obj._dtype, kid.value, obj._n, obj._d, obj._device)
             st = _DeviceState.adopt(h, key)

@@ -2,5 +2,6 @@
 from .base import Kernel
 from .periodic import PeriodicKernel
 from .gaussian import GaussianKernel
+from .gaussian_ard import GaussianARDKernel
 
-__all__ = ["Kernel", "PeriodicKernel", "GaussianKernel"]
+__all__ = ["Kernel", "PeriodicKernel", "GaussianKernel", "GaussianARDKernel"]

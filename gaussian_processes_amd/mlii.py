@@ -19,7 +19,19 @@ from . import _lib
 
 __all__ = ["log_lh_batch", "best_restart", "BatchEvaluator", "optimize"]
 
-_KERNEL_IDS = {"gaussian": (_lib.KERNEL_GAUSSIAN, 2), "periodic": (_lib.KERNEL_PERIODIC, 3)}
+_KERNEL_IDS = {"gaussian": (_lib.KERNEL_GAUSSIAN, 2), "periodic": (_lib.KERNEL_PERIODIC, 3),
+               "gaussian_ard": (_lib.KERNEL_GAUSSIAN_ARD, None)}     # None: (h, w_1 ... w_d), the count comes from x
+
+
+def _kernel_id(kernel, x):
+    """(GPX_KERNEL_* id, number of kernel parameters) of a family name for inputs x: (n,) or (n, d)."""
+    kid, nkp = _KERNEL_IDS[kernel]
+    if nkp is None:
+        d = 1 if x.ndim == 1 else x.shape[1]
+        if not 1 <= d <= _lib.ARD_MAX_D:
+            raise ValueError("kernel %r needs between 1 and %d input dimensions (got %d)" % (kernel, _lib.ARD_MAX_D, d))
+        nkp = d + 1
+    return kid, nkp
 
 
 class BatchEvaluator(object):
@@ -28,8 +40,8 @@ class BatchEvaluator(object):
     tens-of-GB workspace allocation once.  ``ev(thetas)`` -> log_lh of every row."""
 
     def __init__(self, x, y, kernel="gaussian", dtype="float64", device=None):
-        self.kid, self.nkp = _KERNEL_IDS[kernel]
         x = np.ascontiguousarray(x, dtype=np.float64)
+        self.kid, self.nkp = _kernel_id(kernel, x)
         y = np.ascontiguousarray(y, dtype=np.float64)
         n = x.shape[0]
         d = 1 if x.ndim == 1 else x.shape[1]
@@ -117,8 +129,8 @@ def log_lh_batch(x, y, thetas, kernel="gaussian", dtype="float64", dist=None, de
     (tools/mlii_bench.py): 13.0 ms per restart with 1 handle, 10.7 ms with 4, worse with 2 or 8 --
     the factorisation of a matrix this small is a chain of dependent launches, not throughput.
     """
-    kid, nkp = _KERNEL_IDS[kernel]
     x = np.ascontiguousarray(x, dtype=np.float64)
+    kid, nkp = _kernel_id(kernel, x)
     y = np.ascontiguousarray(y, dtype=np.float64)
     thetas = np.atleast_2d(np.asarray(thetas, dtype=np.float64))
     if thetas.shape[1] != nkp + 1:

@@ -93,6 +93,11 @@ extern "C" {
 /* kernel families (gp/kernels/gaussian.py, gp/kernels/periodic.py) */
 #define GPX_KERNEL_GAUSSIAN 0   /* params = (h, w)    */
 #define GPX_KERNEL_PERIODIC 1   /* params = (h, w, p) */
+/* Gaussian with one length-scale per input dimension (ARD, RW06 eq. 5.1; an extension: the reference has none):
+ *   k(a, b) = h^2 / sqrt(2 pi wbar^2) * exp(-1/2 sum_k ((a_k - b_k) / w_k)^2),   wbar = (prod_k w_k)^(1/d)
+ * -- at equal widths exactly GPX_KERNEL_GAUSSIAN on (n, d) inputs.  Only the function itself is a member (GPX_K). */
+#define GPX_KERNEL_GAUSSIAN_ARD 2   /* params = (h, w_1 ... w_d), 1 <= d <= GPX_ARD_MAX_D */
+#define GPX_ARD_MAX_D 64
 
 /* members of a kernel family: the function and its parameter derivatives.
  * Gaussian: gaussian_c.pyx:18-164.  Periodic: periodic_c.pyx:18-235. */
@@ -212,10 +217,17 @@ int gpx_debug_leaf_selfcheck(int run_now, int *state);
  * params: HOST array (h, w[, p]) as doubles.  tri = GPX_LOWER skips tiles that
  * lie strictly above the diagonal (only meaningful for x1 == x2).
  * d > 1 (an extension: the reference is 1-D) uses r2 = sum_k (x1[i,k]-x2[j,k])^2;
- * periodic members other than GPX_K require d == 1. */
+ * periodic members other than GPX_K require d == 1.
+ * GPX_KERNEL_GAUSSIAN_ARD: params = (h, w_1 ... w_d), member GPX_K only (others: GPX_ERR_UNSUPPORTED); both point sets
+ * are scaled into this host thread's scratch (gpx_d_scale_points), then built as GPX_KERNEL_GAUSSIAN. */
 int gpx_d_kmat(int dtype, int kernel, int member, const void *x1, int64_t n,
                const void *x2, int64_t m, int d, const double *params,
                double diag_add, int tri, void *out, int64_t ld, void *stream);
+
+/* out[i, k] = x[i, k] / w[k] for i < n, k < d, in `dtype` (a true division: the fp64 result is numpy's x / w bit for
+ * bit).  x, out: DEVICE (n, d) densely packed, out may equal x; w_host: HOST d doubles, 1 <= d <= GPX_ARD_MAX_D.
+ * The identity behind GPX_KERNEL_GAUSSIAN_ARD:  k_ard(a, b; h, w) = k_gaussian(a / w, b / w; h / sqrt(wbar), 1). */
+int gpx_d_scale_points(int dtype, const void *x, int64_t n, int d, const double *w_host, void *out, void *stream);
 
 /* Fused posterior mean  out[i] = sum_j K(xo[i], x[j]) * alpha[j]   (gp/gp.py:597
  * without materialising Kxox).  xo: (m, d), x: (n, d), alpha: (n,), out: (m,). */
@@ -328,8 +340,10 @@ int gpx_gp_set_data(gpx_gp_t *gp, const double *x, const double *y);
  * have completed (synchronise the producing stream first).  Returns after the copies are
  * done, so the sources may be freed or overwritten at once. */
 int gpx_gp_set_data_device(gpx_gp_t *gp, const void *x_dev, const void *y_dev);
-/* params = (h, w[, p]); s = noise standard deviation (gp/gp.py:190-197) */
+/* params = (h, w[, p]), or (h, w_1 ... w_d) for GPX_KERNEL_GAUSSIAN_ARD; s = noise standard deviation (gp/gp.py:190-197) */
 int gpx_gp_set_params(gpx_gp_t *gp, const double *params, double s);
+/* the kernel parameters the handle holds: *count of them (any family), the first min(cap, *count) written to params */
+int gpx_gp_get_params(gpx_gp_t *gp, double *params, int cap, int *count);
 /* Plugin kernels (any gp.kernels.Kernel subclass without a native id):
  * the host evaluates its own K(x, x) + s^2 I (gp/gp.py:263-266) and hands the
  * full (n, n) HOST float64 matrix over; gpx_gp_fit then skips the kernel build. */
@@ -376,7 +390,10 @@ int gpx_gp_get_inv_Kxx(gpx_gp_t *gp, double *out, int64_t ld);
 /* d log_lh / d(theta): out[n_params + 1] HOST float64, order (kernel params..., s).  RW06 eq. 5.9
  * (gp/gp.py:398-433, gp_c.pyx:34-49) computed on the device: K^-1 by TRSM + SYRK on the MFMA
  * kernel, then one fused pass against kernel derivatives evaluated on the fly.  All NaN when the
- * factorisation failed (gp/gp.py:424-428).  Periodic kernel: d == 1 only. */
+ * factorisation failed (gp/gp.py:424-428).  Periodic kernel: d == 1 only.
+ * GPX_KERNEL_GAUSSIAN_ARD: d + 2 values (h, w_1 ... w_d, s); K^-1 as above, then one pass over its lower triangle that
+ * accumulates S_0 = sum c_ab, S_k = sum c_ab t_k^2 (c_ab = (alpha_a alpha_b - W_ab) k_ab, t_k = (a_k - b_k) / w_k) and
+ * tr W in f64 with a fixed summation order (bitwise repeatable); dh = S_0 / h, dw_k = (S_k - S_0 / d) / (2 w_k). */
 int gpx_gp_dloglh_dtheta(gpx_gp_t *gp, double *out);
 /* dlh / d(theta) (gp/gp.py:435-465, gp_c.pyx:52-67) and d2lh / d(theta)^2 (gp/gp.py:467-502,
  * gp_c.pyx:70-111), both HOST float64: dlh[n_params + 1], d2lh[(n_params + 1)^2] row-major, parameter
@@ -386,7 +403,8 @@ int gpx_gp_dloglh_dtheta(gpx_gp_t *gp, double *out);
  * return.  All NaN when the factorisation failed (gp/gp.py:458-462,493-497).  Native kernels only
  * (periodic: d == 1).  d2loglh (extension, may be NULL): the Hessian of the LOG marginal likelihood,
  * d2lh / lh - (dlh / lh)(dlh / lh)^T, from the same pass; it stays finite where lh underflows to 0
- * (log_lh < MIN, i.e. any n beyond a few hundred) and the reference's lh-scaled Hessian is all zeros. */
+ * (log_lh < MIN, i.e. any n beyond a few hundred) and the reference's lh-scaled Hessian is all zeros.
+ * GPX_KERNEL_GAUSSIAN_ARD: GPX_ERR_UNSUPPORTED (this entry and gpx_gp_dm_dtheta). */
 int gpx_gp_dlh_d2lh(gpx_gp_t *gp, double *dlh, double *d2lh, double *d2loglh);
 /* d mean(xo) / d(theta) -> out (n_params + 1, m) HOST float64 (gp/gp.py:627-662, gp_c.pyx:114-131):
  * dK_i(xo, x) alpha - K(xo, x) K^-1 dK_i alpha with fused on-the-fly mat-vecs and two triangular
@@ -394,7 +412,8 @@ int gpx_gp_dlh_d2lh(gpx_gp_t *gp, double *dlh, double *d2lh, double *d2loglh);
 int gpx_gp_dm_dtheta(gpx_gp_t *gp, const double *xo, int64_t m, double *out);
 /* Batched ML-II step (BASELINE config 5; the reference's inner step "set params -> read log_lh",
  * gp/gp.py:216-223,337-367, for a table of restarts on the handle's data set).
- * thetas: HOST (B, n_params + 1) row-major, rows (kernel params..., s); log_lh: HOST B doubles;
+ * thetas: HOST (B, n_params + 1) row-major, rows (kernel params..., s) -- d + 2 values a row for
+ * GPX_KERNEL_GAUSSIAN_ARD, whose rows each get a scaled copy of x (n d elements) in the workspace; log_lh: HOST B doubles;
  * info: HOST B ints or NULL (potrf info per row; -1 for a row with invalid parameters).
  * A row whose parameters the reference rejects with ValueError (kernel parameter < EPS, s < 0,
  * non-finite) yields NaN; a non-positive-definite row or logdet < MIN yields -inf.
@@ -420,7 +439,9 @@ int gpx_gp_fit_batch_grad(gpx_gp_t *gp, const double *thetas, int64_t B, double 
  * gpx_gp_load creates a NEW handle on the current device, fitted, without recomputing anything. */
 int gpx_gp_save(gpx_gp_t *gp, const char *path);
 int gpx_gp_load(gpx_gp_t **gp, const char *path);
-/* what a handle holds (any pointer may be NULL); x: (n, d), y: (n,) HOST float64 */
+/* what a handle holds (any pointer may be NULL); x: (n, d), y: (n,) HOST float64.  params3: (h, NaN, NaN) for
+ * GPX_KERNEL_GAUSSIAN_ARD (gpx_gp_get_params has them all); x is what set_data gave, never the scaled copy.
+ * Checkpoints of GPX_KERNEL_GAUSSIAN_ARD carry the d widths behind the header; the other families' files are unchanged. */
 int gpx_gp_describe(gpx_gp_t *gp, int *dtype, int *kernel, int64_t *n, int *d, double *params3, double *s);
 int gpx_gp_get_xy(gpx_gp_t *gp, double *x, double *y);
 /* timing of the last fit, milliseconds per stage (HIP events on the handle's
