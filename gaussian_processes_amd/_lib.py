@@ -18,7 +18,7 @@ OK = 0
 ERR_ARG, ERR_HIP, ERR_NO_DEVICE, ERR_NOMEM, ERR_UNSUPPORTED, ERR_INTERNAL = -1, -2, -3, -4, -5, -6
 (ROUTE_TRSV_OPS, ROUTE_TRSV_STEPS, ROUTE_PANEL_RES, ROUTE_PANEL_CHAIN, ROUTE_FIT_RIDE, ROUTE_FIT_TWO_SOLVES,
  ROUTE_GEMM_FAST, ROUTE_GEMM_GENERIC, ROUTE_SYRK_EXACT, ROUTE_SYRK_PATCH, ROUTE_MG_BCAST_ONE, ROUTE_MG_BCAST_SAG,
- ROUTE_FIT_OPS_AHEAD, ROUTE_TRSM_OPS, ROUTE_POTRF_PAIR, ROUTE_VAR_CHUNK) = range(16)
+ ROUTE_FIT_OPS_AHEAD, ROUTE_TRSM_OPS, ROUTE_POTRF_PAIR, ROUTE_VAR_CHUNK, ROUTE_LOO_CHUNK) = range(17)
 F64, F32 = 0, 1
 KERNEL_GAUSSIAN, KERNEL_PERIODIC, KERNEL_GAUSSIAN_ARD = 0, 1, 2
 ARD_MAX_D = 64
@@ -97,6 +97,8 @@ _SIGNATURES = {
     "gpx_d_dot": (c_int, [c_int, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
     "gpx_d_var_rows": (c_int, [c_int, c_int, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int, c_double_p, c_void_p,
                                c_void_p, c_void_p]),
+    "gpx_d_loo_rows": (c_int, [c_int, c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                               c_void_p, c_void_p, c_void_p]),
     "gpx_gp_create": (c_int, [POINTER(c_void_p), c_int, c_int, c_int64, c_int]),
     "gpx_gp_destroy": (c_int, [c_void_p]),
     "gpx_gp_set_data": (c_int, [c_void_p, c_double_p, c_double_p]),
@@ -114,6 +116,8 @@ _SIGNATURES = {
     "gpx_gp_cov_from_K": (c_int, [c_void_p, c_double_p, c_double_p, c_int64, c_double_p]),
     "gpx_gp_var": (c_int, [c_void_p, c_double_p, c_int64, c_int64, c_double_p]),
     "gpx_gp_var_from_K": (c_int, [c_void_p, c_double_p, c_double_p, c_int64, c_int64, c_double_p]),
+    "gpx_gp_inv_diag": (c_int, [c_void_p, c_int64, c_double_p]),
+    "gpx_gp_loo": (c_int, [c_void_p, c_int64, c_double_p, c_double_p, c_double_p, c_double_p]),
     "gpx_debug_var_plan": (c_int, [c_int, c_int64, c_int64, c_int64, c_size_t, POINTER(c_int64), POINTER(c_int64),
                                    POINTER(c_size_t)]),
     "gpx_gp_get_Kxx": (c_int, [c_void_p, c_double_p, c_int64]),

@@ -48,7 +48,7 @@ int  ensure_device();   // GPX_OK when a GPU is usable
 // point of decision.  Tests that force a route through an environment switch assert it here.
 enum Route { RT_TRSV_OPS = 0, RT_TRSV_STEPS = 1, RT_PANEL_RES = 2, RT_PANEL_CHAIN = 3, RT_FIT_RIDE = 4,
              RT_FIT_TWO_SOLVES = 5, RT_GEMM_FAST = 6, RT_GEMM_GENERIC = 7, RT_SYRK_EXACT = 8, RT_SYRK_PATCH = 9,
-             RT_MG_BCAST_ONE = 10, RT_MG_BCAST_SAG = 11, RT_FIT_OPS_AHEAD = 12, RT_TRSM_OPS = 13, RT_POTRF_PAIR = 14, RT_VAR_CHUNK = 15, RT_COUNT = 16 };
+             RT_MG_BCAST_ONE = 10, RT_MG_BCAST_SAG = 11, RT_FIT_OPS_AHEAD = 12, RT_TRSM_OPS = 13, RT_POTRF_PAIR = 14, RT_VAR_CHUNK = 15, RT_LOO_CHUNK = 16, RT_COUNT = 17 };
 void route_hit(int route);
 
 // LAPACK-style info of a factorisation as the host sees it: > 0 "not positive definite" (the caller's business),
@@ -226,7 +226,8 @@ int trsv_lower(int dtype, const void *L, int64_t n, int64_t ldl, void *b, void *
                hipStream_t st, const Batch *bt = nullptr,   // bt: sA = stride of L, sB = stride of b / x
                TrsvOps *ops = nullptr);
 int trsm_right_lt(int dtype, const void *L, int64_t n, int64_t ldl, void *X, int64_t m, int64_t ldx,
-                  hipStream_t st, int x_upper = 0, TrsvOps *ops = nullptr);   // ops: this factor's block operators (completed here if need be): in-block substitution = one product with inv(L_kk)
+                  hipStream_t st, int x_upper = 0, TrsvOps *ops = nullptr,    // ops: this factor's block operators (completed here if need be): in-block substitution = one product with inv(L_kk)
+                  int64_t c0 = 0);   // c0 > 0 (x_upper, a multiple of 64): X is rows [c0, c0 + m) of the identity; the sweep begins at c0 (operator route: at c0's block)
 // K^-1 = L^-T L^-1 from a factor: X <- L^-T (the identity through trsm_right_lt), W <- X X^T, tri = GPX_FULL or GPX_LOWER (the
 // other half cleared).  X, W: n x ldl each.  count == 1: `ops` are the factor's own.  count > 1: a LOCK-STEP group (trsm_ops_ok
 // only): factors sL elements apart, X and W blocks n * ldl apart, operators built here into group_ops (count * trsv_ops_bytes).
@@ -244,6 +245,15 @@ int var_rows(int dtype, int kernel, const void *X, int64_t rows, int64_t n, int6
              const double *params, const double *kdiag_dev, int accumulate, double *out_dev, hipStream_t st);
 int var_finish(int dtype, int kernel, const void *xo, int d, const double *params, const double *acc_dev, int64_t rows,
                double *out_dev, hipStream_t st);
+// Leave-one-out from the factor (gpx_solve.hip).  eye_rows: X (rows x ld) <- rows [c0, c0 + rows) of the identity, columns
+// [cz, ld) only.  loo_rows: gpx_d_loo_rows' arguments, over the chunk solved from that seed.  loo_points: the same per-point
+// quantities from a diagonal kii that is already there.  sum_f64: out_dev[0] = sum a[i], one workgroup, fixed order.
+int eye_rows(int dtype, void *X, int64_t rows, int64_t ld, int64_t c0, int64_t cz, hipStream_t st);
+int loo_rows(int dtype, const void *X, int64_t rows, int64_t n, int64_t ldx, int64_t c0, const void *y, const void *alpha,
+             double *kii, double *mean, double *var, double *logp, hipStream_t st);
+int loo_points(int dtype, const double *kii, const void *y, const void *alpha, int64_t n, double *mean, double *var, double *logp,
+               hipStream_t st);
+int sum_f64(const double *a, int64_t n, double *out_dev, hipStream_t st);
 // The row chunking of a predictive-variance call (gpx_gp.hip; host arithmetic): *rows per chunk, *chunks, *bytes of device
 // memory one chunk needs.  chunk_rows 0: the largest multiple of 128 (at most var_chunk_cap) whose buffers fit a quarter
 // of free_bytes.  GPX_ERR_ARG / GPX_ERR_NOMEM as gpx_debug_var_plan documents.

@@ -259,7 +259,7 @@ int gpx_gp_destroy(gpx_gp_t *g)
     stream_epoch_bump();                                       // (StreamTurn: a later stream at this one's address is a different stream)
     if (g->st_ops) { (void)hipStreamSynchronize(g->st_ops); (void)hipStreamDestroy(g->st_ops); }
     if (g->ev_ops) (void)hipEventDestroy(g->ev_ops);
-    for (void *b : {g->x, g->xs, g->y, g->A, g->alpha, g->t0, g->t1, (void *)g->scal}) dev_free(b);    // gpx_gp_create's fixed-size fields
+    for (void *b : {g->x, g->xs, g->y, g->A, g->alpha, g->t0, g->t1, (void *)g->scal, (void *)g->kii}) dev_free(b);    // gpx_gp_create's fixed-size fields, and kii (n doubles, on first use)
     for (GrowBuf *b : {&g->bw, &g->gw, &g->ops.mem, &g->bops.mem}) b->release();
     for (int i = 0; i < 6; ++i) if (g->ev[i]) (void)hipEventDestroy(g->ev[i]);
     if (g->st) (void)hipStreamDestroy(g->st);
@@ -273,7 +273,7 @@ int gpx_gp_set_data(gpx_gp_t *g, const double *x, const double *y)
     GPX_ARG(g && x && y, "NULL argument");
     GPX_TRY(upload_f64(g->dtype, g->x, x, g->n * g->d, g->st));
     GPX_TRY(upload_f64(g->dtype, g->y, y, g->n, g->st));
-    g->have_data = true; g->fitted = false;
+    g->have_data = true; g->fitted = false; g->have_kii = false;
     GPX_TRY(gp_rescale(g));
     return gp_scan_finite(g);
 }
@@ -286,7 +286,7 @@ int gpx_gp_set_data_device(gpx_gp_t *g, const void *x_dev, const void *y_dev)
     GPX_HIP(hipMemcpyAsync(g->x, x_dev, (size_t)g->n * g->d * es, hipMemcpyDeviceToDevice, g->st));
     GPX_HIP(hipMemcpyAsync(g->y, y_dev, (size_t)g->n * es, hipMemcpyDeviceToDevice, g->st));
     GPX_HIP(hipStreamSynchronize(g->st));      // the caller may free or overwrite the sources on return
-    g->have_data = true; g->fitted = false;
+    g->have_data = true; g->fitted = false; g->have_kii = false;
     GPX_TRY(gp_rescale(g));
     return gp_scan_finite(g);
 }
@@ -298,7 +298,7 @@ int gpx_gp_set_params(gpx_gp_t *g, const double *params, double s)
     GPX_ARG(!(s < 0), "invalid value for s");                  // gp/gp.py:192-193 (`val < 0`: a NaN passes, as in the reference; gpx_gp_fit then rejects it as non-finite)
     for (int i = 0; i < g->nparams; ++i) g->params[i] = params[i];
     g->s = s;
-    g->have_params = true; g->fitted = false; g->have_K = false;
+    g->have_params = true; g->fitted = false; g->have_K = false; g->have_kii = false;
     return gp_rescale(g);
 }
 
@@ -332,7 +332,7 @@ int gpx_gp_set_K(gpx_gp_t *g, const double *Kxx, int64_t ld)
                                (const double *)tmp.p + r * n, (float *)g->A + r * g->lda, n);
         GPX_HIP(hipStreamSynchronize(g->st));
     }
-    g->have_K = true; g->fitted = false;
+    g->have_K = true; g->fitted = false; g->have_kii = false;
     return GPX_OK;
 }
 
@@ -374,6 +374,7 @@ int gpx_gp_fit(gpx_gp_t *g, int *info)
         GPX_TRY(kmat(g->dtype, v.kernel, GPX_K, v.x, g->n, v.x, g->n, g->d, v.params, g->s * g->s,
                      GPX_LOWER, g->A, g->lda, st));
     g->have_K = false;   // the factor overwrites it
+    g->have_kii = false; // ... and diag(K^-1) went with the factor before
     GPX_HIP(hipEventRecord(g->ev[1], st));
     // Lxx (gp/gp.py:294), in place
     // Small and mid sizes: y rides along as row n of the matrix -- every panel substitutes it, every update reduces it,
@@ -639,6 +640,87 @@ int gpx_gp_var_from_K(gpx_gp_t *g, const double *Kxox, const double *kdiag, int6
     GPX_ARG(chunk_rows >= 0 && chunk_rows % VAR_CHUNK_ALIGN == 0, "chunk_rows must be 0 (automatic) or a multiple of 128");
     if (m == 0) return GPX_OK;
     return gp_var_impl(g, nullptr, Kxox, kdiag, m, chunk_rows, out);
+}
+
+// Leave-one-out, RW06 eq. 5.10 - 5.12: everything but diag(K^-1) is in HBM after a fit, and (K^-1)_ii = |L^-1 e_i|^2.  In row
+// chunks of the identity (var_plan, as gpx_gp_var): X = E_c L^-T by the sweep that begins at the chunk's own column --
+// L^-1 e_i is zero above row i -- then the row sums of squares (loo_rows).  n^3 / 3 flops, one chunk buffer, nothing n x n.
+// The diagonal stays in the handle (g->kii) until the factor changes.  mean / var / logp (device, n doubles each; all or
+// none): the per-point quantities are written by the same pass.
+static int gp_loo_sweep(gpx_gp *g, int64_t chunk_rows, double *mean, double *var, double *logp)
+{
+    const size_t es = esize(g->dtype);
+    const int64_t n = g->n, ldx = g->lda;
+    size_t freeb = 0, totalb = 0;
+    GPX_HIP(hipMemGetInfo(&freeb, &totalb));
+    int64_t rows = 0, chunks = 0;
+    GPX_TRY(var_plan(g->dtype, n, n, chunk_rows, freeb, &rows, &chunks, nullptr));
+    if (!g->kii) GPX_TRY(dev_alloc((void **)&g->kii, (size_t)n * sizeof(double), "hipMalloc kii"));
+    DevBuf X;
+    GPX_TRY(X.alloc((size_t)rows * ldx * es));
+    for (int64_t c = 0; c < chunks; ++c) {
+        const int64_t c0 = c * rows, rc = std::min(rows, n - c0);
+        route_hit(RT_LOO_CHUNK);
+        GPX_TRY(eye_rows(g->dtype, X.p, rc, ldx, c0, c0 / TRSV_OPS_BLOCK * TRSV_OPS_BLOCK, g->st));
+        GPX_TRY(trsm_right_lt(g->dtype, g->A, n, g->lda, X.p, rc, ldx, g->st, 1, &g->ops, c0));
+        GPX_TRY(loo_rows(g->dtype, X.p, rc, n, ldx, c0, mean ? (const char *)g->y + c0 * es : nullptr,
+                         mean ? (const char *)g->alpha + c0 * es : nullptr, g->kii + c0, mean ? mean + c0 : nullptr,
+                         mean ? var + c0 : nullptr, mean ? logp + c0 : nullptr, g->st));
+    }
+    g->have_kii = true;
+    return GPX_OK;
+}
+
+// what gpx_gp_inv_diag and gpx_gp_loo ask of the handle beyond "fitted": a factor that exists
+static int gp_need_factor(gpx_gp *g)
+{
+    double h4[4];
+    GPX_HIP(hipMemcpyAsync(h4, g->scal, sizeof(h4), hipMemcpyDeviceToHost, g->st));
+    GPX_HIP(hipStreamSynchronize(g->st));
+    int info;
+    memcpy(&info, &h4[3], sizeof(int));
+    GPX_TRY(check_internal_info(info));
+    if (info != 0) { set_error("Kxx is not positive definite (info = %d): there is no factor to take diag(K^-1) from", info); return GPX_ERR_ARG; }
+    return GPX_OK;
+}
+
+int gpx_gp_inv_diag(gpx_gp_t *g, int64_t chunk_rows, double *out)
+{
+    GP_ENTER(g);
+    GPX_ARG(g->fitted, "gp is not fitted");
+    GPX_ARG(out, "out is NULL");
+    GPX_ARG(chunk_rows >= 0 && chunk_rows % VAR_CHUNK_ALIGN == 0, "chunk_rows must be 0 (automatic) or a multiple of 128");
+    GPX_TRY(gp_need_factor(g));
+    if (!g->have_kii) GPX_TRY(gp_loo_sweep(g, chunk_rows, nullptr, nullptr, nullptr));
+    GPX_HIP(hipMemcpyAsync(out, g->kii, (size_t)g->n * sizeof(double), hipMemcpyDeviceToHost, g->st));
+    GPX_HIP(hipStreamSynchronize(g->st));
+    return GPX_OK;
+}
+
+int gpx_gp_loo(gpx_gp_t *g, int64_t chunk_rows, double *mean, double *var, double *log_p, double *log_p_sum)
+{
+    GP_ENTER(g);
+    GPX_ARG(g->fitted, "gp is not fitted");
+    GP_NEED_FINITE_Y(g);
+    GPX_ARG(chunk_rows >= 0 && chunk_rows % VAR_CHUNK_ALIGN == 0, "chunk_rows must be 0 (automatic) or a multiple of 128");
+    GPX_TRY(gp_need_factor(g));
+    const int64_t n = g->n;
+    if (!mean && !var && !log_p && !log_p_sum) {           // nothing asked for: the diagonal, for the calls to come
+        if (!g->have_kii) GPX_TRY(gp_loo_sweep(g, chunk_rows, nullptr, nullptr, nullptr));
+        return GPX_OK;
+    }
+    DevBuf o;                                              // mean | var | logp | sum of logp
+    GPX_TRY(o.alloc((size_t)(3 * n + 1) * sizeof(double)));
+    double *dm = (double *)o.p, *dv = dm + n, *dl = dv + n, *ds = dl + n;
+    if (!g->have_kii) GPX_TRY(gp_loo_sweep(g, chunk_rows, dm, dv, dl));
+    else GPX_TRY(loo_points(g->dtype, g->kii, g->y, g->alpha, n, dm, dv, dl, g->st));
+    GPX_TRY(sum_f64(dl, n, ds, g->st));                    // one workgroup, fixed order: not a host sum
+    if (mean) GPX_HIP(hipMemcpyAsync(mean, dm, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, g->st));
+    if (var) GPX_HIP(hipMemcpyAsync(var, dv, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, g->st));
+    if (log_p) GPX_HIP(hipMemcpyAsync(log_p, dl, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, g->st));
+    if (log_p_sum) GPX_HIP(hipMemcpyAsync(log_p_sum, ds, sizeof(double), hipMemcpyDeviceToHost, g->st));
+    GPX_HIP(hipStreamSynchronize(g->st));
+    return GPX_OK;
 }
 
 int gpx_debug_var_plan(int dtype, int64_t n, int64_t m, int64_t chunk_rows, size_t free_bytes,

@@ -25,6 +25,8 @@ struct gpx_gp {
     // the block operators of the row being differentiated
     gpx::GrowBuf gw; int64_t gw_cap;   // gw_cap: rows per lock-step gradient group the block holds
     gpx::TrsvOps bops;
+    double *kii;          // device, n doubles from the first leave-one-out call on: diag(K^-1) of the CURRENT factor when
+    bool have_kii;        // have_kii (cleared wherever `fitted` is, and by a new fit)
     hipStream_t st_ops;   // lazily created: where gpx_gp_fit builds `ops` while the factorisation is still running
     hipEvent_t ev_ops;
 };

@@ -885,17 +885,19 @@ static thread_local ThreadScratch g_trsm_scr;   // the operator route: one m x 5
 // (n = 8192, m = 1024: cov 11.0 -> see DESIGN 3.3).  Every launch covers all systems -- at n = 8192 a single system's far
 // update is 1 - 2 rounds of tiles (32 x 32 at most), eight of them fill the chip.  L, X, the operators and the scratch
 // block are sL / sX / sO / (m * 512) elements apart.
+// c0 (x_upper only; 0: the whole sweep): row i of X is zero before column c0 + i -- rows [c0, c0 + m) of the identity.  The
+// sweep begins at the block that holds column c0, and a block that ends at column r works on the rows c0 + i < r.
 static int trsm_right_lt_ops(int dtype, const void *L, int64_t sL, int64_t n, int64_t ldl, void *X, int64_t sX, int64_t m, int64_t ldx,
-                             hipStream_t st, int x_upper, const void *ops_base, int64_t sO, int count)
+                             hipStream_t st, int x_upper, const void *ops_base, int64_t sO, int count, int64_t c0 = 0)
 {
     route_hit(RT_TRSM_OPS);
     const size_t es = esize(dtype);
     const int64_t sS = m * OB;
     void *scr = nullptr;
     GPX_TRY(g_trsm_scr.get((size_t)count * sS * es, &scr));
-    for (int64_t k = 0; k < n / OB; ++k) {
+    for (int64_t k = c0 / OB; k < n / OB; ++k) {
         const int64_t k0 = k * OB, r = k0 + OB;
-        const int64_t me = x_upper ? std::min(m, r) : m;
+        const int64_t me = x_upper ? std::min(m, r - c0) : m;
         char *Xk = (char *)X + k0 * es;
         const void *Wk = dtype == GPX_F64 ? (void *)OpsView<double>(ops_base, n).W(k) : (void *)OpsView<float>(ops_base, n).W(k);
         Batch b1; b1.count = count; b1.sA = sX; b1.sB = sO; b1.sC = sS;
@@ -921,16 +923,22 @@ static int trsm_right_lt_ops(int dtype, const void *L, int64_t sL, int64_t n, in
 // x_upper: X is upper triangular on entry (the identity, when L^-T itself is wanted): rows beyond
 // the current block are still zero in its columns, so every step works on the leading k0 + kb rows
 // only -- a third of the flops.
+// c0 > 0 (x_upper, a multiple of 64): X holds rows [c0, c0 + m) of the identity, zero before column c0 + i in row i, so the
+// sweep is the trailing sub-system from c0 on (the operator route: from the start of c0's block); nothing left of it is touched.
+// (64 elements are 256 or 512 bytes: L + c0 (ldl + 1) and X + c0 sit on whatever 16-byte boundary L and X sit on.)
 int trsm_right_lt(int dtype, const void *L, int64_t n, int64_t ldl, void *X, int64_t m, int64_t ldx,
-                  hipStream_t st, int x_upper, TrsvOps *ops)
+                  hipStream_t st, int x_upper, TrsvOps *ops, int64_t c0)
 {
     if (n <= 0 || m <= 0) return GPX_OK;
     const size_t es = esize(dtype);
+    if (c0 < 0 || c0 >= n || c0 % SB != 0 || (c0 > 0 && !x_upper)) { set_error("trsm_right_lt: bad first column %lld", (long long)c0); return GPX_ERR_ARG; }
     // Operator route (the caller's TrsvOps of THIS factor): completed here if the factor has only some.
     if (ops && trsm_ops_ok(dtype, L, n, ldl) && ldx % (16 / (int64_t)es) == 0 && ((uintptr_t)X) % 16 == 0) {
         if (!ops->valid) GPX_TRY(trsv_ops_build_upto(dtype, L, n, ldl, ops, n / OB, st));
-        if (ops->valid && ops->mem.p) return trsm_right_lt_ops(dtype, L, 0, n, ldl, X, 0, m, ldx, st, x_upper, ops->mem.p, 0, 1);
+        if (ops->valid && ops->mem.p) return trsm_right_lt_ops(dtype, L, 0, n, ldl, X, 0, m, ldx, st, x_upper, ops->mem.p, 0, 1, c0);
     }
+    if (c0 > 0)                                            // the 64-wide route on the trailing sub-system
+        return trsm_right_lt(dtype, (const char *)L + c0 * (ldl + 1) * es, n - c0, ldl, (char *)X + c0 * es, m, ldx, st, 1, nullptr, 0);
     const int64_t NB = n >= 8192 ? 512 : 256;
     auto Lp = [&](int64_t r, int64_t c) { return (const char *)L + (r * ldl + c) * es; };
     auto Xp = [&](int64_t c) { return (char *)X + c * es; };
@@ -960,6 +968,25 @@ __global__ void eye_kernel(T *__restrict__ X, int64_t n, int64_t ld)
     for (int64_t r = blockIdx.y; r < n; r += gridDim.y) X[r * ld + c] = (c == r) ? (T)1 : (T)0;
 }
 
+// eye_kernel for a row chunk: X (rows x ld) <- rows [c0, c0 + rows) of the identity, columns [cz, ld) only (cz <= c0)
+template <typename T>
+__global__ void eye_rows_kernel(T *__restrict__ X, int64_t rows, int64_t ld, int64_t c0, int64_t cz)
+{
+    const int64_t c = cz + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= ld) return;
+    for (int64_t r = blockIdx.y; r < rows; r += gridDim.y) X[r * ld + c] = (c == c0 + r) ? (T)1 : (T)0;
+}
+
+int eye_rows(int dtype, void *X, int64_t rows, int64_t ld, int64_t c0, int64_t cz, hipStream_t st)
+{
+    if (rows <= 0 || cz >= ld) return GPX_OK;
+    const dim3 grid((unsigned)cdiv(ld - cz, 256), (unsigned)std::min<int64_t>(rows, 32768)), block(256);
+    if (dtype == GPX_F64) hipLaunchKernelGGL((eye_rows_kernel<double>), grid, block, 0, st, (double *)X, rows, ld, c0, cz);
+    else hipLaunchKernelGGL((eye_rows_kernel<float>), grid, block, 0, st, (float *)X, rows, ld, c0, cz);
+    GPX_LAUNCH_CHECK();
+    return GPX_OK;
+}
+
 // X = I L^-T = L^-T ; K^-1 = L^-T L^-1 = X X^T   (gp/gp.py:311-312; gpx_common.h for the arguments)
 int inv_from_factor(int dtype, const void *L, int64_t n, int64_t ldl, void *X, void *W, int tri, hipStream_t st,
                     TrsvOps *ops, int count, int64_t sL, void *group_ops)
@@ -986,7 +1013,7 @@ int inv_from_factor(int dtype, const void *L, int64_t n, int64_t ldl, void *X, v
 }
 
 // ---- reductions (single workgroup, fixed order => deterministic) ----------
-template <typename T, int MODE>   // MODE 0: sum a[i]*b[i]   1: 2*sum log a[i*stride]
+template <typename T, int MODE>   // MODE 0: sum a[i]*b[i]   1: 2*sum log a[i*stride]   2: sum a[i]
 __global__ __launch_bounds__(1024) void reduce_kernel(const T *__restrict__ a, const T *__restrict__ b,
                                                       int64_t n, int64_t stride, double *__restrict__ out,
                                                       int64_t sa, int64_t sb, int64_t so)
@@ -1000,7 +1027,8 @@ __global__ __launch_bounds__(1024) void reduce_kernel(const T *__restrict__ a, c
     double acc = 0.0;
     for (int64_t i = tid; i < n; i += 1024) {
         if (MODE == 0) acc = fma((double)a[i], (double)b[i], acc);
-        else acc += log((double)a[i * stride]);
+        else if (MODE == 1) acc += log((double)a[i * stride]);
+        else acc += (double)a[i];
     }
     for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
     if ((tid & 63) == 0) red[tid >> 6] = acc;
@@ -1008,7 +1036,7 @@ __global__ __launch_bounds__(1024) void reduce_kernel(const T *__restrict__ a, c
     if (tid == 0) {
         double s = 0.0;
         for (int w = 0; w < 16; ++w) s += red[w];
-        out[0] = (MODE == 0) ? s : 2.0 * s;
+        out[0] = (MODE == 1) ? 2.0 * s : s;
     }
 }
 
@@ -1036,6 +1064,14 @@ int dot(int dtype, const void *a, const void *b, int64_t n, double *out_dev, hip
     else
         hipLaunchKernelGGL((reduce_kernel<float, 0>), dim3(count), dim3(1024), 0, st, (const float *)a,
                            (const float *)b, n, 1, out_dev, sa, sb, so);
+    GPX_LAUNCH_CHECK();
+    return GPX_OK;
+}
+
+int sum_f64(const double *a, int64_t n, double *out_dev, hipStream_t st)
+{
+    hipLaunchKernelGGL((reduce_kernel<double, 2>), dim3(1), dim3(1024), 0, st, a, (const double *)nullptr, n, 1, out_dev,
+                       (int64_t)0, (int64_t)0, (int64_t)0);
     GPX_LAUNCH_CHECK();
     return GPX_OK;
 }
@@ -1159,11 +1195,119 @@ int var_finish(int dtype, int kernel, const void *xo, int d, const double *param
     return GPX_OK;
 }
 
+// ---- leave-one-out: the finishing pass over a solved chunk X = E_c L^-T (rows [c0, c0 + rows) of the identity) --------
+// RW06 eq. 5.10 - 5.12 from k = (K^-1)_ii, a = alpha_i and y_i: the left-out mean and variance, and log p(y_i | the others)
+__device__ __forceinline__ void loo_point(double k, double a, double y, int64_t i, double *__restrict__ mean,
+                                          double *__restrict__ var, double *__restrict__ logp)
+{
+#pragma clang fp contract(off)                             // (both callers round alike: the fused pass and the cached one give the same bits)
+    if (mean) mean[i] = y - a / k;
+    if (var) var[i] = 1.0 / k;
+    if (logp) logp[i] = 0.5 * log(k) - 0.5 * a * a / k - 0.9189385332046727;      // log(2 pi) / 2
+}
+
+// One workgroup per row (grid-stride over rows), var_rows_kernel's reduction: kii[i] = sum_j X[i, j]^2 over j in [c0 + i, n)
+// -- row i of X is column c0 + i of L^-1, zero (and never written by the sweep) before that column.  The row is read from
+// c0 + i rounded down to the 16-byte vector; the columns before c0 + i are masked, nothing outside [that vector, n) is
+// loaded.  With y and alpha (the chunk's own rows, handle dtype) the leave-one-out quantities of the row are written too.
+template <typename T>
+__global__ __launch_bounds__(256) void loo_rows_kernel(const T *__restrict__ X, int64_t rows, int64_t n, int64_t ldx, int64_t c0,
+                                                       int aligned, const T *__restrict__ y, const T *__restrict__ alpha,
+                                                       double *__restrict__ kii, double *__restrict__ mean,
+                                                       double *__restrict__ var, double *__restrict__ logp)
+{
+    constexpr int VEC = Vec<T>::N;
+    typedef typename Vec<T>::type VT;
+    __shared__ double red[4];
+    const int tid = threadIdx.x;
+    const int64_t nv = aligned ? n / VEC : 0;              // whole 16-byte vectors of a row; the rest is the scalar tail
+    for (int64_t row = blockIdx.x; row < rows; row += gridDim.x) {
+        const T *__restrict__ xr = X + row * ldx;
+        const VT *__restrict__ xv = reinterpret_cast<const VT *>(xr);
+        const int64_t first = c0 + row;                    // the row's first column
+        double acc = 0.0;
+#pragma unroll 4
+        for (int64_t v = first / VEC + tid; v < nv; v += 256) {
+            const VT t = xv[v];
+            const T *e = reinterpret_cast<const T *>(&t);
+#pragma unroll
+            for (int q = 0; q < VEC; ++q) {
+                const double x = (v * VEC + q >= first) ? (double)e[q] : 0.0;
+                acc = fma(x, x, acc);
+            }
+        }
+        for (int64_t c = max(nv * VEC, first) + tid; c < n; c += 256) acc = fma((double)xr[c], (double)xr[c], acc);
+        acc = lanes64_sum(acc);
+        __syncthreads();                                   // (the row before: red[] has been read)
+        if ((tid & 63) == 0) red[tid >> 6] = acc;
+        __syncthreads();
+        if (tid == 0) {
+            const double k = ((red[0] + red[1]) + red[2]) + red[3];
+            if (kii) kii[row] = k;
+            if (y) loo_point(k, (double)alpha[row], (double)y[row], row, mean, var, logp);
+        }
+    }
+}
+
+// the same quantities from a diagonal that is already there
+template <typename T>
+__global__ void loo_point_kernel(const double *__restrict__ kii, const T *__restrict__ y, const T *__restrict__ alpha, int64_t n,
+                                 double *__restrict__ mean, double *__restrict__ var, double *__restrict__ logp)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) loo_point(kii[i], (double)alpha[i], (double)y[i], i, mean, var, logp);
+}
+
+int loo_rows(int dtype, const void *X, int64_t rows, int64_t n, int64_t ldx, int64_t c0, const void *y, const void *alpha,
+             double *kii, double *mean, double *var, double *logp, hipStream_t st)
+{
+    if (rows <= 0) return GPX_OK;
+    const size_t es = esize(dtype);
+    const int aligned = (ldx * (int64_t)es) % 16 == 0 && ((uintptr_t)X) % 16 == 0;
+    const dim3 grid((unsigned)std::min<int64_t>(rows, 1 << 20)), block(256);
+    ProfScope prof(PC_REDUCE, ((double)rows * (double)(n - c0) - 0.5 * (double)rows * (double)rows) * es, st);
+    if (dtype == GPX_F64)
+        hipLaunchKernelGGL((loo_rows_kernel<double>), grid, block, 0, st, (const double *)X, rows, n, ldx, c0, aligned,
+                           (const double *)y, (const double *)alpha, kii, mean, var, logp);
+    else
+        hipLaunchKernelGGL((loo_rows_kernel<float>), grid, block, 0, st, (const float *)X, rows, n, ldx, c0, aligned,
+                           (const float *)y, (const float *)alpha, kii, mean, var, logp);
+    GPX_LAUNCH_CHECK();
+    return GPX_OK;
+}
+
+int loo_points(int dtype, const double *kii, const void *y, const void *alpha, int64_t n, double *mean, double *var, double *logp,
+               hipStream_t st)
+{
+    if (n <= 0) return GPX_OK;
+    const dim3 grid((unsigned)cdiv(n, 256)), block(256);
+    if (dtype == GPX_F64)
+        hipLaunchKernelGGL((loo_point_kernel<double>), grid, block, 0, st, kii, (const double *)y, (const double *)alpha, n, mean, var, logp);
+    else
+        hipLaunchKernelGGL((loo_point_kernel<float>), grid, block, 0, st, kii, (const float *)y, (const float *)alpha, n, mean, var, logp);
+    GPX_LAUNCH_CHECK();
+    return GPX_OK;
+}
+
 }  // namespace gpx
 
 using namespace gpx;
 
 extern "C" {
+
+int gpx_d_loo_rows(int dtype, const void *X, int64_t rows, int64_t n, int64_t ldx, int64_t c0, const void *y, const void *alpha,
+                   double *kii_dev, double *mean_dev, double *var_dev, double *logp_dev, void *stream)
+{
+    GPX_ARG(dtype == GPX_F64 || dtype == GPX_F32, "dtype must be GPX_F64 or GPX_F32");
+    GPX_ARG(rows >= 0 && n >= 0 && ldx >= n && c0 >= 0, "need rows, n, c0 >= 0 and ldx >= n");
+    GPX_ARG(c0 + rows <= n, "rows [c0, c0 + rows) must lie within n");
+    if (rows == 0) return GPX_OK;
+    GPX_ARG(X && (kii_dev || y), "NULL pointer");
+    GPX_ARG((y != nullptr) == (alpha != nullptr), "y and alpha go together");
+    GPX_ARG(y || !(mean_dev || var_dev || logp_dev), "mean / var / logp need y and alpha");
+    GPX_TRY(ensure_device());
+    return loo_rows(dtype, X, rows, n, ldx, c0, y, alpha, kii_dev, mean_dev, var_dev, logp_dev, S(stream));
+}
 
 int gpx_d_var_rows(int dtype, int kernel, const void *X, int64_t rows, int64_t n, int64_t ldx, const void *xo, int d,
                    const double *params, const double *kdiag_dev, double *out_dev, void *stream)

@@ -9,7 +9,8 @@ object as `gp.GP` -- ``log_lh``, ``lh``, ``inv_Kxx_y``, ``mean(xo)``, ``cov(xo)`
 
 Every rank builds the same object with the same data and calls the same members in the same order: a fit, a mean
 and a cov are collective.  The factor never leaves the ranks' HBM, so what needs an n x n host copy (`Kxx`, `Lxx`,
-`inv_Kxx`, the derivative stack, `dm_dtheta`) and what would have to carry a handle or a communicator to another
+`inv_Kxx`, the derivative stack, `dm_dtheta`), leave-one-out (`loo`, `inv_Kxx_diag`: not implemented over the distributed
+factor) and what would have to carry a handle or a communicator to another
 process (`save_fitted`, copy, pickle) raises NotImplementedError: `GP` has them.
 """
 import numpy as np
@@ -20,9 +21,9 @@ from .gp import GP, DTYPE, memoprop
 __all__ = ["DistributedGP"]
 
 
-def _unsupported(name):
-    msg = ("DistributedGP.%s is not available (it needs an n x n host copy of a matrix that stays distributed, or a "
-           "handle and communicator that do not travel): use gp.GP for it" % name)
+def _unsupported(name, why="it needs an n x n host copy of a matrix that stays distributed, or a handle and communicator "
+                           "that do not travel"):
+    msg = "DistributedGP.%s is not available (%s): use gp.GP for it" % (name, why)
 
     def f(*args, **kwargs):
         raise NotImplementedError(msg)
@@ -207,6 +208,12 @@ class DistributedGP(GP):
     d2lh_dtheta2 = property(_unsupported("d2lh_dtheta2"))
     d2loglh_dtheta2 = property(_unsupported("d2loglh_dtheta2"))
     dm_dtheta = _unsupported("dm_dtheta")
+    _NO_LOO = "leave-one-out over the distributed factor is not implemented; one GPU has it"
+    inv_Kxx_diag = property(_unsupported("inv_Kxx_diag", _NO_LOO))
+    loo_mean = property(_unsupported("loo_mean", _NO_LOO))
+    loo_var = property(_unsupported("loo_var", _NO_LOO))
+    loo_log_lh = property(_unsupported("loo_log_lh", _NO_LOO))
+    loo = _unsupported("loo", _NO_LOO)
     save_fitted = _unsupported("save_fitted")
     load_fitted = classmethod(_unsupported("load_fitted"))
     _state = _unsupported("_state")

@@ -538,6 +538,54 @@ class GP(object):
         xo, _ = self._xo(xo)
         return self.mean(xo), self.var(xo, noise=noise)
 
+    # ---- leave-one-out cross-validation (extension; RW06 section 5.4.2) ----
+    @memoprop
+    def inv_Kxx_diag(self):
+        r"""Diagonal of :math:`K_{xx}^{-1}`, ``(n,)``, without the inverse: :math:`(K^{-1})_{ii} = \|L^{-1} e_i\|^2` from
+        the resident factor in row chunks (one :math:`n^3/3` sweep, nothing ``(n, n)`` beside the factor, an ``O(n)``
+        download).  Raises numpy.linalg.LinAlgError when `Kxx` is not positive definite, as `inv_Kxx` does."""
+        st = self._fit_pd()
+        out = np.empty(self._n, dtype=DTYPE)
+        _lib.check(_lib.load().gpx_gp_inv_diag(st.handle, 0, _lib.dptr(out)))
+        return out
+
+    def loo(self, chunk_rows=0):
+        r"""Leave-one-out predictions ``(mean, var, log_p)``, each ``(n,)``, in one device call (RW06 eq. 5.10 - 5.12):
+        with :math:`\alpha = K^{-1} y` and :math:`k_i = (K^{-1})_{ii}`,
+        :math:`\mu_i = y_i - \alpha_i / k_i`, :math:`\sigma_i^2 = 1 / k_i` and
+        :math:`\log p_i = \tfrac12 \log k_i - \tfrac12 \alpha_i^2 / k_i - \tfrac12 \log 2\pi`.
+        :math:`\sigma_i^2` is the variance of the left-out OBSERVATION, noise included: ``var(x_i, noise=True)`` of the GP
+        fitted without point i.  Fills `loo_mean`, `loo_var` and `loo_log_lh`.  ``chunk_rows`` as for `var`."""
+        chunk_rows = int(chunk_rows)
+        if chunk_rows < 0 or chunk_rows % 128:
+            raise ValueError("invalid value for chunk_rows: %d (0, or a multiple of 128)" % chunk_rows)
+        st = self._fit_pd()
+        mean, var, log_p = (np.empty(self._n, dtype=DTYPE) for _ in range(3))
+        total = ctypes.c_double(0.0)
+        _lib.check(_lib.load().gpx_gp_loo(st.handle, chunk_rows, _lib.dptr(mean), _lib.dptr(var), _lib.dptr(log_p),
+                                          ctypes.byref(total)))
+        self._memoized.update(loo_mean=mean, loo_var=var, loo_log_lh=DTYPE(total.value))
+        return mean, var, log_p
+
+    @memoprop
+    def loo_mean(self):
+        r"""Leave-one-out predictive mean at every training point, ``(n,)`` (see `loo`)."""
+        return self.loo()[0]
+
+    @memoprop
+    def loo_var(self):
+        r"""Leave-one-out predictive variance of every observation, noise included, ``(n,)`` (see `loo`)."""
+        return self.loo()[1]
+
+    @memoprop
+    def loo_log_lh(self):
+        r"""Leave-one-out log pseudo-likelihood :math:`\sum_i \log p(y_i \mid y_{-i})`, RW06 eq. 5.11 (summed on the
+        device in a fixed order); ``-inf`` when `Kxx` is not positive definite, as `log_lh`."""
+        if self._fit().info != 0:
+            return -np.inf
+        self.loo()
+        return self._memoized["loo_log_lh"]
+
     def dm_dtheta(self, xo):
         r"""Derivative of the predictive mean w.r.t. the parameters, ``(n_p, m)``
         (gp/gp.py:627-662, gp_c.pyx:114-131)."""

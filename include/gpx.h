@@ -193,6 +193,7 @@ int gpx_prof_read(int cls, double *launches, double *total_ms, double *total_wor
 #define GPX_ROUTE_TRSM_OPS       13   /* X L^-T (posterior covariance, inverse): in-block step as one product with inv(L_kk) */
 #define GPX_ROUTE_POTRF_PAIR     14   /* a factorisation that entered the pair phase: far trailing updates of depth K = 2048, one per two panels */
 #define GPX_ROUTE_VAR_CHUNK      15   /* predictive variance (gpx_gp_var, gpx_gp_var_from_K, gpx_mg_var): one hit per row chunk */
+#define GPX_ROUTE_LOO_CHUNK      16   /* leave-one-out (gpx_gp_inv_diag, gpx_gp_loo): one hit per row chunk of the identity swept; none when the handle still has the diagonal */
 int gpx_debug_route_count(int route, int64_t *count);
 /* roctx ranges pushed so far (GPX_ROCTX=1: every gpx_gp_* call and every launch class below it is a nested host range for
  * `rocprofv3 --marker-trace`; libroctx64.so is loaded on first use; 0 while the switch is off) */
@@ -321,6 +322,19 @@ int gpx_d_var_rows(int dtype, int kernel, const void *X, int64_t rows, int64_t n
 /* (The finishing pass of the predictive variance, on a chunk X = K(xo_c, x) L^-T: rows n sizeof(T) bytes read once;
  * 16-byte loads when ldx and X are 16-byte aligned, scalar loads otherwise.  GPX_PROF_REDUCE.) */
 
+/* The finishing pass of leave-one-out, on a chunk X = E_c L^-T (rows [c0, c0 + rows) of the identity, solved): row i is
+ * column c0 + i of L^-1, and kii_dev[i] = sum_j X[i, j]^2 over j in [c0 + i, n) = (K^-1)_{c0+i, c0+i}.  X: rows x n, ldx, handle
+ * dtype, c0 + rows <= n.  Row i is read from column c0 + i rounded down to the 16-byte vector (from c0 + i itself when X or
+ * ldx is not 16-byte aligned); the columns before c0 + i are masked, whatever they hold, and nothing outside
+ * [that column, n) is loaded.  With y and alpha (DEVICE, handle dtype, the chunk's own rows: y[i] goes with row i; both or
+ * neither) the leave-one-out quantities of RW06 eq. 5.10 - 5.12 are written by the same pass, each pointer optional,
+ * with k = kii[i], a = alpha[i]:   mean_dev[i] = y[i] - a / k    var_dev[i] = 1 / k
+ *                                  logp_dev[i] = log(k) / 2 - a^2 / (2 k) - log(2 pi) / 2
+ * All outputs DOUBLE; f64 accumulation for both dtypes, fixed summation order, no atomics: bitwise repeatable.
+ * One 256-thread workgroup per row; GPX_PROF_REDUCE. */
+int gpx_d_loo_rows(int dtype, const void *X, int64_t rows, int64_t n, int64_t ldx, int64_t c0, const void *y, const void *alpha,
+                   double *kii_dev, double *mean_dev, double *var_dev, double *logp_dev, void *stream);
+
 /* out_dev[0] = sum_i a[i] * b[i]  (f64 accumulation).  np.dot(y, Kiy), gp_c.pyx:26 */
 int gpx_d_dot(int dtype, const void *a, const void *b, int64_t n, double *out_dev,
               void *stream);
@@ -381,6 +395,17 @@ int gpx_debug_var_plan(int dtype, int64_t n, int64_t m, int64_t chunk_rows, size
  * staging block, (lda + 512) elements a row -- fit a quarter of free_bytes; m itself when all of m fits one chunk.
  * GPX_ERR_ARG: chunk_rows < 0 or not a multiple of 128, m < 0, n < 1.  GPX_ERR_NOMEM: 128 rows (or the chunk asked for)
  * do not fit.  The variance is not clamped at zero (neither is the diagonal of gpx_gp_cov). */
+/* Leave-one-out cross-validation from the fitted factor (RW06 section 5.4.2).  diag(K^-1) -> out (n,) HOST float64:
+ * (K^-1)_ii = |L^-1 e_i|^2, in row chunks of the identity: X = E_c L^-T by a sweep that begins at the chunk's own column
+ * (L^-1 e_i is zero above row i), then gpx_d_loo_rows.  n^3 / 3 flops; device memory one chunk (as gpx_gp_var: the same
+ * chunk_rows, rule, cap and errors, with m = n) plus n doubles that stay in the handle: a second call on the same fit
+ * sweeps nothing.  set_data, set_params, set_K and fit drop them.  Preconditions and statuses of gpx_gp_cov, and
+ * GPX_ERR_ARG when the last fit was not positive definite (there is no factor). */
+int gpx_gp_inv_diag(gpx_gp_t *gp, int64_t chunk_rows, double *out);
+/* mean[i], var[i]: the prediction for y_i -- noise included -- of the GP fitted without point i (eq. 5.12); log_p[i] its log
+ * density at y_i (eq. 5.10); *log_p_sum their sum (eq. 5.11), reduced on the device in a fixed order.  (n,) HOST float64
+ * each; any pointer may be NULL.  As gpx_gp_inv_diag, and y must be finite. */
+int gpx_gp_loo(gpx_gp_t *gp, int64_t chunk_rows, double *mean, double *var, double *log_p, double *log_p_sum);
 /* copy-outs to HOST float64: Kxx is rebuilt (full, + s^2 I); L has zero upper */
 int gpx_gp_get_Kxx(gpx_gp_t *gp, double *out, int64_t ld);
 int gpx_gp_get_Lxx(gpx_gp_t *gp, double *out, int64_t ld);
