@@ -18,7 +18,8 @@ OK = 0
 ERR_ARG, ERR_HIP, ERR_NO_DEVICE, ERR_NOMEM, ERR_UNSUPPORTED, ERR_INTERNAL = -1, -2, -3, -4, -5, -6
 (ROUTE_TRSV_OPS, ROUTE_TRSV_STEPS, ROUTE_PANEL_RES, ROUTE_PANEL_CHAIN, ROUTE_FIT_RIDE, ROUTE_FIT_TWO_SOLVES,
  ROUTE_GEMM_FAST, ROUTE_GEMM_GENERIC, ROUTE_SYRK_EXACT, ROUTE_SYRK_PATCH, ROUTE_MG_BCAST_ONE, ROUTE_MG_BCAST_SAG,
- ROUTE_FIT_OPS_AHEAD, ROUTE_TRSM_OPS, ROUTE_POTRF_PAIR, ROUTE_VAR_CHUNK, ROUTE_LOO_CHUNK) = range(17)
+ ROUTE_FIT_OPS_AHEAD, ROUTE_TRSM_OPS, ROUTE_POTRF_PAIR, ROUTE_VAR_CHUNK, ROUTE_LOO_CHUNK, ROUTE_TRSM_L_OPS,
+ ROUTE_GRAD_CHUNK) = range(19)
 F64, F32 = 0, 1
 KERNEL_GAUSSIAN, KERNEL_PERIODIC, KERNEL_GAUSSIAN_ARD = 0, 1, 2
 ARD_MAX_D = 64
@@ -93,6 +94,10 @@ _SIGNATURES = {
                                    c_void_p, c_void_p]),
     "gpx_d_trsm_right_lt": (c_int, [c_int, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64,
                                     c_void_p]),
+    "gpx_d_trsm_right_l": (c_int, [c_int, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64,
+                                   c_void_p]),
+    "gpx_d_pred_grad": (c_int, [c_int, c_int, c_void_p, c_int64, c_void_p, c_int64, c_int, c_double_p, c_void_p, c_void_p,
+                                c_int64, c_double, c_void_p, c_void_p]),
     "gpx_d_logdet_chol": (c_int, [c_int, c_void_p, c_int64, c_int64, c_void_p, c_void_p]),
     "gpx_d_dot": (c_int, [c_int, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
     "gpx_d_var_rows": (c_int, [c_int, c_int, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int, c_double_p, c_void_p,
@@ -116,6 +121,8 @@ _SIGNATURES = {
     "gpx_gp_cov_from_K": (c_int, [c_void_p, c_double_p, c_double_p, c_int64, c_double_p]),
     "gpx_gp_var": (c_int, [c_void_p, c_double_p, c_int64, c_int64, c_double_p]),
     "gpx_gp_var_from_K": (c_int, [c_void_p, c_double_p, c_double_p, c_int64, c_int64, c_double_p]),
+    "gpx_gp_mean_grad": (c_int, [c_void_p, c_double_p, c_int64, c_double_p]),
+    "gpx_gp_var_grad": (c_int, [c_void_p, c_double_p, c_int64, c_int64, c_double_p, c_double_p]),
     "gpx_gp_inv_diag": (c_int, [c_void_p, c_int64, c_double_p]),
     "gpx_gp_loo": (c_int, [c_void_p, c_int64, c_double_p, c_double_p, c_double_p, c_double_p]),
     "gpx_debug_var_plan": (c_int, [c_int, c_int64, c_int64, c_int64, c_size_t, POINTER(c_int64), POINTER(c_int64),

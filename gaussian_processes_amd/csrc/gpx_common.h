@@ -48,7 +48,8 @@ int  ensure_device();   // GPX_OK when a GPU is usable
 // point of decision.  Tests that force a route through an environment switch assert it here.
 enum Route { RT_TRSV_OPS = 0, RT_TRSV_STEPS = 1, RT_PANEL_RES = 2, RT_PANEL_CHAIN = 3, RT_FIT_RIDE = 4,
              RT_FIT_TWO_SOLVES = 5, RT_GEMM_FAST = 6, RT_GEMM_GENERIC = 7, RT_SYRK_EXACT = 8, RT_SYRK_PATCH = 9,
-             RT_MG_BCAST_ONE = 10, RT_MG_BCAST_SAG = 11, RT_FIT_OPS_AHEAD = 12, RT_TRSM_OPS = 13, RT_POTRF_PAIR = 14, RT_VAR_CHUNK = 15, RT_LOO_CHUNK = 16, RT_COUNT = 17 };
+             RT_MG_BCAST_ONE = 10, RT_MG_BCAST_SAG = 11, RT_FIT_OPS_AHEAD = 12, RT_TRSM_OPS = 13, RT_POTRF_PAIR = 14, RT_VAR_CHUNK = 15, RT_LOO_CHUNK = 16,
+             RT_TRSM_L_OPS = 17, RT_GRAD_CHUNK = 18, RT_COUNT = 19 };
 void route_hit(int route);
 
 // LAPACK-style info of a factorisation as the host sees it: > 0 "not positive definite" (the caller's business),
@@ -90,7 +91,7 @@ struct EventPool {
 // ---- live per-kernel-class timing (HIP events around each launch; off by default) ----
 enum ProfClass { PC_KMAT = 0, PC_GEMM = 1, PC_POTRF_DIAG = 2, PC_TRSM_ROWS = 3, PC_TRSV = 4,
                  PC_MEAN = 5, PC_REDUCE = 6, PC_GEMM_SKINNY = 7, PC_GEMM_GENERIC = 8, PC_GEMM_PANEL = 9, PC_GEMM_N64 = 10,
-                 PC_COUNT = 11 };
+                 PC_TRANSPOSE = 11, PC_PRED_GRAD = 12, PC_COUNT = 13 };
 extern bool g_prof_on;
 // the registry is shared by all host threads (mutex inside); a scope ends its OWN record
 int  prof_begin(int cls, double work, hipStream_t st);    // record index, -1 when nothing was recorded
@@ -228,6 +229,15 @@ int trsv_lower(int dtype, const void *L, int64_t n, int64_t ldl, void *b, void *
 int trsm_right_lt(int dtype, const void *L, int64_t n, int64_t ldl, void *X, int64_t m, int64_t ldx,
                   hipStream_t st, int x_upper = 0, TrsvOps *ops = nullptr,    // ops: this factor's block operators (completed here if need be): in-block substitution = one product with inv(L_kk)
                   int64_t c0 = 0);   // c0 > 0 (x_upper, a multiple of 64): X is rows [c0, c0 + m) of the identity; the sweep begins at c0 (operator route: at c0's block)
+// X (m x n, ldx) <- X * L^-1, in place (gpx_solve.hip): the mirror of trsm_right_lt, block columns from the last to the first.
+// ops: this factor's block operators (completed here if need be): in-block solve = one product with Wt_k.  Without them
+// (or where trsm_ops_ok says no) the 64-wide route.  Scratch: the transposed row panels of L, at most n x TRSV_OPS_BLOCK.
+int trsm_right_l(int dtype, const void *L, int64_t n, int64_t ldl, void *X, int64_t m, int64_t ldx, hipStream_t st,
+                 TrsvOps *ops = nullptr);
+// Input-space gradient pass (gpx_kmat.hip): gpx_d_pred_grad's arguments on GPX_KERNEL_GAUSSIAN / GPX_KERNEL_PERIODIC points;
+// col_div (HOST, d doubles, or null): column k of the result is divided by col_div[k] (the ARD family on scaled points).
+int pred_grad(int dtype, int kernel, const void *xo, int64_t m, const void *x, int64_t n, int d, const double *params,
+              const void *alpha, const void *B, int64_t ldb, double scale, const double *col_div, double *out_dev, hipStream_t st);
 // K^-1 = L^-T L^-1 from a factor: X <- L^-T (the identity through trsm_right_lt), W <- X X^T, tri = GPX_FULL or GPX_LOWER (the
 // other half cleared).  X, W: n x ldl each.  count == 1: `ops` are the factor's own.  count > 1: a LOCK-STEP group (trsm_ops_ok
 // only): factors sL elements apart, X and W blocks n * ldl apart, operators built here into group_ops (count * trsv_ops_bytes).

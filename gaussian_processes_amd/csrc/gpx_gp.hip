@@ -642,6 +642,69 @@ int gpx_gp_var_from_K(gpx_gp_t *g, const double *Kxox, const double *kdiag, int6
     return gp_var_impl(g, nullptr, Kxox, kdiag, m, chunk_rows, out);
 }
 
+// Input-space gradients of the prediction.  The mean's is one fused pass with w = alpha.  The variance's,
+//   dvar_i/dxo_i = -2 sum_j beta_ij dk(xo_i, x_j)/dxo_i,   beta_i = K^-1 k_i = L^-T (L^-1 k_i),
+// goes through gpx_gp_var's chunks and buffer: X = K(xo_c, x), X <- X L^-T (the variance falls out here: var_rows), X <- X L^-1
+// (trsm_right_l, the handle's operators), then the same fused pass with w = X.  Nothing n x n beside the factor; one
+// download at the end.  ARD: everything on the scaled points, column k of the result divided by w_k.
+static const double *gp_col_div(const gpx_gp *g) { return g->kernel == GPX_KERNEL_GAUSSIAN_ARD ? g->params + 1 : nullptr; }
+
+int gpx_gp_mean_grad(gpx_gp_t *g, const double *xo, int64_t m, double *grad)
+{
+    GP_ENTER(g);
+    GPX_ARG(g && g->fitted, "gp is not fitted");
+    GP_NEED_FINITE_Y(g);
+    GPX_ARG(m >= 0 && (m == 0 || (xo && grad)), "bad arguments");
+    if (m == 0) return GPX_OK;
+    DevBuf dxo, dout;
+    GPX_TRY(dxo.alloc((size_t)m * g->d * esize(g->dtype)));
+    GPX_TRY(dout.alloc((size_t)m * g->d * sizeof(double)));
+    GPX_TRY(upload_points(g, dxo.p, xo, m));
+    const GpView v = gp_view(g);
+    GPX_TRY(pred_grad(g->dtype, v.kernel, dxo.p, m, v.x, g->n, g->d, v.params, g->alpha, nullptr, 0, 1.0, gp_col_div(g),
+                      (double *)dout.p, g->st));
+    GPX_HIP(hipMemcpyAsync(grad, dout.p, (size_t)m * g->d * sizeof(double), hipMemcpyDeviceToHost, g->st));
+    GPX_HIP(hipStreamSynchronize(g->st));
+    return GPX_OK;
+}
+
+int gpx_gp_var_grad(gpx_gp_t *g, const double *xo, int64_t m, int64_t chunk_rows, double *var, double *grad)
+{
+    GP_ENTER(g);
+    GPX_ARG(g && g->fitted, "gp is not fitted");
+    GPX_ARG(m >= 0 && (m == 0 || (xo && grad)), "bad arguments");
+    GPX_ARG(chunk_rows >= 0 && chunk_rows % VAR_CHUNK_ALIGN == 0, "chunk_rows must be 0 (automatic) or a multiple of 128");
+    if (m == 0) return GPX_OK;
+    const size_t es = esize(g->dtype);
+    const int64_t n = g->n, ldx = g->lda, d = g->d;
+    size_t freeb = 0, totalb = 0;
+    GPX_HIP(hipMemGetInfo(&freeb, &totalb));
+    int64_t rows = 0, chunks = 0;
+    GPX_TRY(var_plan(g->dtype, n, m, chunk_rows, freeb, &rows, &chunks, nullptr));
+    DevBuf dxo, X, dout;                                   // dout: grad (m, d) | var (m)
+    GPX_TRY(X.alloc((size_t)rows * ldx * es));
+    GPX_TRY(dout.alloc((size_t)m * (d + 1) * sizeof(double)));
+    GPX_TRY(dxo.alloc((size_t)m * d * es));
+    GPX_TRY(upload_points(g, dxo.p, xo, m));
+    double *dgrad = (double *)dout.p, *dvar = dgrad + m * d;
+    const GpView v = gp_view(g);
+    for (int64_t c = 0; c < chunks; ++c) {
+        const int64_t r0 = c * rows, rc = std::min(rows, m - r0);
+        route_hit(RT_GRAD_CHUNK);
+        const void *xo_c = (const char *)dxo.p + (size_t)r0 * d * es;
+        GPX_TRY(kmat(g->dtype, v.kernel, GPX_K, xo_c, rc, v.x, n, g->d, v.params, 0.0, GPX_FULL, X.p, ldx, g->st));
+        GPX_TRY(trsm_right_lt(g->dtype, g->A, n, g->lda, X.p, rc, ldx, g->st, 0, &g->ops));
+        if (var) GPX_TRY(var_rows(g->dtype, v.kernel, X.p, rc, n, ldx, xo_c, g->d, v.params, nullptr, 0, dvar + r0, g->st));
+        GPX_TRY(trsm_right_l(g->dtype, g->A, n, g->lda, X.p, rc, ldx, g->st, &g->ops));
+        GPX_TRY(pred_grad(g->dtype, v.kernel, xo_c, rc, v.x, n, g->d, v.params, nullptr, X.p, ldx, -2.0, gp_col_div(g),
+                          dgrad + r0 * d, g->st));
+    }
+    GPX_HIP(hipMemcpyAsync(grad, dgrad, (size_t)m * d * sizeof(double), hipMemcpyDeviceToHost, g->st));
+    if (var) GPX_HIP(hipMemcpyAsync(var, dvar, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, g->st));
+    GPX_HIP(hipStreamSynchronize(g->st));
+    return GPX_OK;
+}
+
 // Leave-one-out, RW06 eq. 5.10 - 5.12: everything but diag(K^-1) is in HBM after a fit, and (K^-1)_ii = |L^-1 e_i|^2.  In row
 // chunks of the identity (var_plan, as gpx_gp_var): X = E_c L^-T by the sweep that begins at the chunk's own column --
 // L^-1 e_i is zero above row i -- then the row sums of squares (loo_rows).  n^3 / 3 flops, one chunk buffer, nothing n x n.

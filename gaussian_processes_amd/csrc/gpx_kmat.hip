@@ -490,6 +490,225 @@ static int launch_mean(int kernel, const void *xo, int64_t m, const void *x, int
     return GPX_OK;
 }
 
+// ---------------------------------------------------------------------------
+// Fused input-space gradient of a prediction:
+//   out[i, k] = scale * sum_j w_ij * dk(xo_i, x_j)/dxo_ik,    w_ij = alpha[j]  (the mean)  or  B[i * ldb + j]  (a solved chunk)
+//   gaussian  dk/da_k = -(a_k - b_k) / w^2 * k           periodic  dk/da_k = -sin((a_k - b_k) / p) / (p w^2) * k
+// mean_kernel's shape: workgroup (bx, by, bz) owns PTS test points, the by-th slice of the training set -- streamed through
+// LDS in chunks of 256 points, one per lane -- and the bz-th window of DP dimensions.  Per pair the lane forms the
+// distance over ALL d dimensions once, k_ij once (the entry function of kmat_kernel, clamp included: a clamped pair adds
+// exactly 0), g = w_ij k_ij in f64, and then for each dimension of the window the difference a_k - b_k itself (never
+// xo_ik sum_j g - sum_j g x_jk, which cancels far from the origin) times g into one of PTS x DP f64 accumulators: that per-lane
+// state is what the brackets bound, PTS * DP = PG_ACC = 16 -- d <= 4: DP = 4, 4 points; else DP = 16, 1 point; d > 16 takes cdiv(d, 16) windows,
+// each of which evaluates k again.  For the distance the test points are wave-uniform SGPR operands (scalar cache).  Lanes are
+// added by shuffles, waves through LDS, slices by pred_grad_reduce_kernel, all in a fixed order: no atomics, bitwise repeatable.
+// ---------------------------------------------------------------------------
+constexpr int PG_ACC = 16;         // f64 accumulators per lane
+template <typename T> __device__ __forceinline__ void dev_sincos(T x, T *s, T *c);
+template <> __device__ __forceinline__ void dev_sincos<double>(double x, double *s, double *c) { sincos(x, s, c); }
+template <> __device__ __forceinline__ void dev_sincos<float>(float x, float *s, float *c) { sincosf(x, s, c); }
+
+template <typename T, int KIND, int DP>
+__global__ __launch_bounds__(256) void pred_grad_kernel(const T *__restrict__ xo, int64_t m, const T *__restrict__ x, int64_t n,
+                                                        int d, KParams kp, const T *__restrict__ alpha, const T *__restrict__ B,
+                                                        int64_t ldb, int64_t slice_len, double *__restrict__ partial)
+{
+    constexpr int PTS = PG_ACC / DP;
+    constexpr int KU = KIND == GPX_KERNEL_GAUSSIAN ? 2 : 1;   // unrolling of the distance loop (periodic: ONE inlined sincos)
+    static_assert(KIND == GPX_KERNEL_GAUSSIAN || PTS == 1, "the periodic pass reuses the lane's slot of the chunk");
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    T *sx = reinterpret_cast<T *>(smem_raw);            // [d][MCP] chunk of x, transposed
+    __shared__ double red[4][PTS * DP];
+
+    const int tid = threadIdx.x;
+    const int64_t p0 = (int64_t)blockIdx.x * PTS;
+    const int kbeg = (int)blockIdx.z * DP;              // this workgroup's window of dimensions
+    double acc[PTS][DP];
+#pragma unroll
+    for (int pp = 0; pp < PTS; ++pp)
+#pragma unroll
+        for (int kk = 0; kk < DP; ++kk) acc[pp][kk] = 0.0;
+    const T *brow[PTS];
+#pragma unroll
+    for (int pp = 0; pp < PTS; ++pp) brow[pp] = B ? B + min(p0 + pp, m - 1) * ldb : alpha;   // (alpha: the same weights for every point)
+
+    // this window's coordinates of the test points live in VECTOR registers (staged through LDS): as SGPR operands like the
+    // rest of the point they are PG_ACC loop invariants on top of the pointers and constants, more than the scalar file holds
+    T *sa = sx + (size_t)d * MCP;                       // [PTS][d]
+    for (int idx = tid; idx < PTS * d; idx += 256) {
+        const int pp = PTS == 1 ? 0 : idx / d;
+        sa[idx] = xo[min(p0 + pp, m - 1) * d + (idx - pp * d)];
+    }
+    __syncthreads();
+    T av[PTS][DP];
+#pragma unroll
+    for (int pp = 0; pp < PTS; ++pp)
+#pragma unroll
+        for (int kk = 0; kk < DP; ++kk) av[pp][kk] = (kbeg + kk < d) ? sa[pp * d + kbeg + kk] : (T)0;
+
+    // gaussian: c1, c2 of gaussian_entry; periodic: h^2, -2 / w^2, p
+    const T c1 = KIND == GPX_KERNEL_GAUSSIAN ? (T)kp.c[0] : (T)kp.c[0] * (T)kp.c[0];
+    const T c2 = KIND == GPX_KERNEL_GAUSSIAN ? (T)kp.c[1] : (T)-2.0 / ((T)kp.c[1] * (T)kp.c[1]);
+    const T per = (T)kp.c[2];
+    const int qd = 256 / d, rd = 256 - qd * d;          // idx += 256  <=>  (c, k) += (qd, rd) with carry
+    const int cst = tid / d, kst = tid - cst * d;
+    const int64_t jbeg = (int64_t)blockIdx.y * slice_len, jend = min(n, jbeg + slice_len);
+    for (int64_t j0 = jbeg; j0 < jend; j0 += 256) {
+        __syncthreads();
+        {
+            const int64_t lim = (jend - j0) * d;
+            const T *g = x + j0 * d;
+            int c = cst, k = kst;
+            for (int idx = tid; idx < 256 * d; idx += 256) {
+                sx[(size_t)k * MCP + c] = (idx < lim) ? g[idx] : (T)0;
+                c += qd; k += rd;
+                if (k >= d) { k -= d; ++c; }
+            }
+        }
+        __syncthreads();
+        const int64_t j = j0 + tid;
+        if (j < jend) {
+            T r[PTS];
+#pragma unroll
+            for (int pp = 0; pp < PTS; ++pp) r[pp] = (T)0;
+#pragma unroll KU
+            for (int k = 0; k < d; ++k) {
+                const T b = sx[(size_t)k * MCP + tid];
+#pragma unroll
+                for (int pp = 0; pp < PTS; ++pp) {
+                    const T a = sa[pp * d + k];
+                    if (KIND == GPX_KERNEL_GAUSSIAN) {
+                        const T t = a - b;
+                        r[pp] = fma(t, t, r[pp]);
+                    } else {
+                        // PTS == 1: the lane's slot of the chunk is its own from here on, and takes sin((a - b) / p) =
+                        // 2 sin cos of the half angle for the pass below -- one sincos per pair and dimension
+                        T sn, cs;
+                        dev_sincos<T>((T)0.5 * (a - b) / per, &sn, &cs);
+                        r[pp] = fma(sn, sn, r[pp]);
+                        sx[(size_t)k * MCP + tid] = (T)2.0 * sn * cs;
+                    }
+                }
+            }
+            double g[PTS];
+#pragma unroll
+            for (int pp = 0; pp < PTS; ++pp) {
+                const T kv = KIND == GPX_KERNEL_GAUSSIAN ? gaussian_entry<T, 0>(r[pp], c1, c2, (T)0, (T)0)
+                                                          : c1 * dev_exp<T>(c2 * r[pp]);
+                const T wv = brow[pp][j];
+                g[pp] = (double)kv * (double)wv;
+            }
+#pragma unroll
+            for (int kk = 0; kk < DP; ++kk) {
+                if (kbeg + kk < d) {                                      // (uniform: d and the window are scalars)
+                    const T b = sx[(size_t)(kbeg + kk) * MCP + tid];
+#pragma unroll
+                    for (int pp = 0; pp < PTS; ++pp) {
+                        const T f = KIND == GPX_KERNEL_GAUSSIAN ? av[pp][kk] - b : b;
+                        acc[pp][kk] = fma(g[pp], (double)f, acc[pp][kk]);
+                    }
+                }
+            }
+        }
+    }
+    // wave reduction (64 lanes), then across the 4 waves in a fixed order
+#pragma unroll
+    for (int pp = 0; pp < PTS; ++pp)
+#pragma unroll
+        for (int kk = 0; kk < DP; ++kk) {
+            double v = acc[pp][kk];
+            for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+            if ((tid & 63) == 0) red[tid >> 6][pp * DP + kk] = v;
+        }
+    __syncthreads();
+    if (tid < PTS * DP) {
+        const int pp = tid / DP, kk = tid - pp * DP;
+        if (p0 + pp < m && kbeg + kk < d)
+            partial[((int64_t)blockIdx.y * m + p0 + pp) * d + kbeg + kk] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
+    }
+}
+
+// out[i, k] = factor * sum over the slices (in slice order) [/ div.w[k]]
+template <bool DIV>
+__global__ void pred_grad_reduce_kernel(const double *__restrict__ partial, int nslice, int64_t md, int d, double factor,
+                                        ArdWidths div, double *__restrict__ out)
+{
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= md) return;
+    double sum = 0.0;
+    for (int y = 0; y < nslice; ++y) sum += partial[(int64_t)y * md + e];
+    sum *= factor;
+    if (DIV) sum /= div.w[e % d];
+    out[e] = sum;
+}
+
+static thread_local ThreadScratch g_pgrad_scr;  // the slice partial sums of the gradient pass
+
+template <typename T>
+static int launch_pred_grad(int kernel, const void *xo, int64_t m, const void *x, int64_t n, int d, const KParams &kp,
+                            const void *alpha, const void *B, int64_t ldb, double scale, const double *col_div, double *out,
+                            hipStream_t st)
+{
+    if ((size_t)d * MCP * sizeof(T) > 96 * 1024) {        // launch_mean's range of d
+        set_error("pred_grad: d = %d too large", d);
+        return GPX_ERR_UNSUPPORTED;
+    }
+    if (col_div && d > GPX_ARD_MAX_D) { set_error("pred_grad: column divisors need d <= %d (got %d)", GPX_ARD_MAX_D, d); return GPX_ERR_ARG; }
+    const int DP = (d <= 4 && kernel == GPX_KERNEL_GAUSSIAN) ? 4 : 16, PTS = PG_ACC / DP;   // (periodic: one point a workgroup)
+    const size_t smem = (size_t)d * (MCP + PTS) * sizeof(T);   // the chunk of x and the group's test points
+    const int64_t gx = cdiv(m, PTS), gz = cdiv(d, DP);
+    // enough workgroups to fill the chip: slices of the training set when m alone is too small (launch_mean's rule)
+    int64_t nslice = std::max<int64_t>(1, std::min<int64_t>(cdiv(2048, gx * gz), cdiv(n, 256)));
+    const int64_t slice_len = cdiv(cdiv(n, nslice), 256) * 256;
+    nslice = cdiv(n, slice_len);
+    void *scr = nullptr;
+    GPX_TRY(g_pgrad_scr.get((size_t)nslice * m * d * sizeof(double), &scr));
+    double *partial = (double *)scr;
+    // the derivative's constant: gaussian -1 / w^2 = 2 c1, periodic -1 / (p w^2)
+    const double factor = scale * (kernel == GPX_KERNEL_GAUSSIAN ? 2.0 * kp.c[0] : -1.0 / (kp.c[2] * kp.c[1] * kp.c[1]));
+    ArdWidths aw;
+    for (int k = 0; k < GPX_ARD_MAX_D; ++k) aw.w[k] = (col_div && k < d) ? col_div[k] : 1.0;
+    dim3 grid((unsigned)gx, (unsigned)nslice, (unsigned)gz), block(256);
+    ProfScope prof(PC_PRED_GRAD, (double)m * n * gz, st);
+#define GPX_PGRAD_LAUNCH(KIND, DPV)                                                                       \
+    do {                                                                                                  \
+        if (smem > 48 * 1024)                                                                             \
+            GPX_HIP(hipFuncSetAttribute((const void *)pred_grad_kernel<T, KIND, DPV>,                     \
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));          \
+        hipLaunchKernelGGL((pred_grad_kernel<T, KIND, DPV>), grid, block, smem, st, (const T *)xo, m,     \
+                           (const T *)x, n, d, kp, (const T *)alpha, (const T *)B, ldb, slice_len, partial); \
+    } while (0)
+#define GPX_PGRAD_KIND(KIND)                                                                              \
+    do {                                                                                                  \
+        if (DP == 4) GPX_PGRAD_LAUNCH(KIND, 4);                                                           \
+        else GPX_PGRAD_LAUNCH(KIND, 16);                                                                  \
+    } while (0)
+    if (kernel == GPX_KERNEL_GAUSSIAN) GPX_PGRAD_KIND(GPX_KERNEL_GAUSSIAN);
+    else GPX_PGRAD_LAUNCH(GPX_KERNEL_PERIODIC, 16);
+#undef GPX_PGRAD_KIND
+#undef GPX_PGRAD_LAUNCH
+    GPX_LAUNCH_CHECK();
+    const int64_t md = m * d;
+    if (col_div)
+        hipLaunchKernelGGL((pred_grad_reduce_kernel<true>), dim3((unsigned)cdiv(md, 256)), dim3(256), 0, st, partial, (int)nslice, md, d, factor, aw, out);
+    else
+        hipLaunchKernelGGL((pred_grad_reduce_kernel<false>), dim3((unsigned)cdiv(md, 256)), dim3(256), 0, st, partial, (int)nslice, md, d, factor, aw, out);
+    GPX_LAUNCH_CHECK();
+    return GPX_OK;
+}
+
+int pred_grad(int dtype, int kernel, const void *xo, int64_t m, const void *x, int64_t n, int d, const double *params,
+              const void *alpha, const void *B, int64_t ldb, double scale, const double *col_div, double *out_dev, hipStream_t st)
+{
+    if (m <= 0) return GPX_OK;
+    if (kernel != GPX_KERNEL_GAUSSIAN && kernel != GPX_KERNEL_PERIODIC) { set_error("pred_grad: unknown kernel family %d", kernel); return GPX_ERR_ARG; }
+    if (n <= 0) { GPX_HIP(hipMemsetAsync(out_dev, 0, (size_t)m * d * sizeof(double), st)); return GPX_OK; }
+    KParams kp;
+    GPX_TRY(make_kparams(kernel, GPX_K, params, 0.0, &kp));
+    if (dtype == GPX_F64) return launch_pred_grad<double>(kernel, xo, m, x, n, d, kp, alpha, B, ldb, scale, col_div, out_dev, st);
+    return launch_pred_grad<float>(kernel, xo, m, x, n, d, kp, alpha, B, ldb, scale, col_div, out_dev, st);
+}
+
 
 // ---------------------------------------------------------------------------
 // Fused gradient reduction (gp/ext/gp_c.pyx:34-49 without its dense products):
@@ -875,6 +1094,33 @@ int gpx_d_mean(int dtype, int kernel, const void *xo, int64_t m, const void *x, 
 {
     gpx::StreamTurn turn__((hipStream_t)stream);     // (this thread's scratch buffers: one stream at a time, gpx_mem.h)
     return gpx_d_mean_member(dtype, kernel, GPX_K, xo, m, x, n, d, params, alpha, out, stream);
+}
+
+int gpx_d_pred_grad(int dtype, int kernel, const void *xo, int64_t m, const void *x, int64_t n, int d, const double *params,
+                    const void *alpha, const void *B, int64_t ldb, double scale, double *out_dev, void *stream)
+{
+    gpx::StreamTurn turn__((hipStream_t)stream);     // (this thread's scratch buffers: one stream at a time, gpx_mem.h)
+    GPX_TRY(ensure_device());
+    GPX_ARG(dtype == GPX_F64 || dtype == GPX_F32, "dtype must be GPX_F64 or GPX_F32");
+    GPX_ARG(n >= 0 && m >= 0 && d >= 1, "need n, m >= 0 and d >= 1");
+    GPX_ARG((alpha != nullptr) != (B != nullptr) || n == 0, "exactly one of alpha / B");
+    if (m == 0) return GPX_OK;
+    GPX_ARG(xo && out_dev && params && (n == 0 || x), "NULL pointer");
+    GPX_ARG(!B || ldb >= n, "ldb < n");
+    if (kernel == GPX_KERNEL_GAUSSIAN_ARD) {
+        // as gpx_d_kmat: the isotropic pass on (xo / w, x / w; h / sqrt(wbar), 1), column k divided by w_k
+        GPX_ARG(d <= GPX_ARD_MAX_D, "the ARD family needs d <= GPX_ARD_MAX_D");
+        const size_t es = esize(dtype), b1 = ((size_t)m * d * es + 255) / 256 * 256;
+        void *scr = nullptr;
+        GPX_TRY(g_ard_scr.get(b1 + (size_t)n * d * es, &scr));
+        void *s1 = scr, *s2 = (char *)scr + b1;
+        GPX_TRY(scale_points(dtype, xo, m, d, params + 1, s1, S(stream)));
+        GPX_TRY(scale_points(dtype, x, n, d, params + 1, s2, S(stream)));
+        double iso[2];
+        ard_iso(params, d, iso);
+        return pred_grad(dtype, GPX_KERNEL_GAUSSIAN, s1, m, s2, n, d, iso, alpha, B, ldb, scale, params + 1, out_dev, S(stream));
+    }
+    return pred_grad(dtype, kernel, xo, m, x, n, d, params, alpha, B, ldb, scale, nullptr, out_dev, S(stream));
 }
 
 }  // extern "C"

@@ -960,6 +960,161 @@ int trsm_right_lt(int dtype, const void *L, int64_t n, int64_t ldl, void *X, int
     return GPX_OK;
 }
 
+// ---- X <- X L^-1: the backward sweep over many right-hand sides -------------------------------------------
+// dst (cols x rows, ldd) <- src (rows x cols, lds)^T through 64 x 64 LDS tiles (transpose_subdiag_kernel's pattern for any
+// shape): loads and stores both run along a row, every index is checked against rows / cols.
+template <typename T>
+__global__ __launch_bounds__(256) void transpose_kernel(const T *__restrict__ src, int64_t lds, int64_t rows, int64_t cols,
+                                                        T *__restrict__ dst, int64_t ldd)
+{
+    __shared__ T tile[64][65];
+    const int64_t r0 = (int64_t)blockIdx.y * 64, c0 = (int64_t)blockIdx.x * 64;
+    for (int idx = threadIdx.x; idx < 64 * 64; idx += 256) {
+        const int r = idx >> 6, c = idx & 63;
+        if (r0 + r < rows && c0 + c < cols) tile[r][c] = src[(r0 + r) * lds + c0 + c];
+    }
+    __syncthreads();
+    for (int idx = threadIdx.x; idx < 64 * 64; idx += 256) {
+        const int c = idx >> 6, r = idx & 63;
+        if (r0 + r < rows && c0 + c < cols) dst[(c0 + c) * ldd + r0 + r] = tile[r][c];
+    }
+}
+
+static int transpose(int dtype, const void *src, int64_t lds, int64_t rows, int64_t cols, void *dst, int64_t ldd, hipStream_t st)
+{
+    if (rows <= 0 || cols <= 0) return GPX_OK;
+    const dim3 grid((unsigned)cdiv(cols, 64), (unsigned)cdiv(rows, 64)), block(256);
+    ProfScope prof(PC_TRANSPOSE, 2.0 * (double)rows * cols * esize(dtype), st);
+    if (dtype == GPX_F64) hipLaunchKernelGGL((transpose_kernel<double>), grid, block, 0, st, (const double *)src, lds, rows, cols, (double *)dst, ldd);
+    else hipLaunchKernelGGL((transpose_kernel<float>), grid, block, 0, st, (const float *)src, lds, rows, cols, (float *)dst, ldd);
+    GPX_LAUNCH_CHECK();
+    return GPX_OK;
+}
+
+// X[r, 0:jb] <- X[r, 0:jb] * Ljj^-1 for rows r < rows: trsm_rows (gpx_potrf.hip) mirrored, one lane per row, backward
+// substitution along the row:  x_c = (a_c - sum_{t > c} x_t L[t, c]) / L[c, c],  c = jb - 1 .. 0.  All lanes read the same
+// element of the staged block at the same time (an LDS broadcast).
+template <typename T, bool FULL64>
+__global__ __launch_bounds__(256) void trsm_rows_l_kernel(T *__restrict__ X, int64_t ldx, int64_t rows,
+                                                          const T *__restrict__ Ljj, int64_t ldl, int jb)
+{
+    __shared__ T sL[SB * (SB + 1)];
+    const int tid = threadIdx.x;
+    for (int idx = tid; idx < jb * jb; idx += 256) {
+        const int i = idx / jb, c = idx - i * jb;
+        sL[i * (SB + 1) + c] = (c <= i) ? Ljj[(int64_t)i * ldl + c] : (T)0;
+    }
+    __syncthreads();
+    const int64_t r = (int64_t)blockIdx.x * 256 + tid;
+    if (r >= rows) return;
+    T *xr = X + r * ldx;
+    if (FULL64) {
+        T x[SB];
+        constexpr int CH = 16 / sizeof(T);
+#pragma unroll
+        for (int c = 0; c < SB; c += CH) {
+            struct alignas(16) V { T e[CH]; } v = *reinterpret_cast<const V *>(xr + c);
+#pragma unroll
+            for (int e = 0; e < CH; ++e) x[c + e] = v.e[e];
+        }
+#pragma unroll
+        for (int c = SB - 1; c >= 0; --c) {
+            T v = x[c];
+#pragma unroll
+            for (int t = SB - 1; t > c; --t) v = fma(-x[t], sL[t * (SB + 1) + c], v);
+            x[c] = v / sL[c * (SB + 1) + c];
+        }
+#pragma unroll
+        for (int c = 0; c < SB; c += CH) {
+            struct alignas(16) V { T e[CH]; } v;
+#pragma unroll
+            for (int e = 0; e < CH; ++e) v.e[e] = x[c + e];
+            *reinterpret_cast<V *>(xr + c) = v;
+        }
+    } else {
+        for (int c = jb - 1; c >= 0; --c) {
+            T v = xr[c];
+            for (int t = jb - 1; t > c; --t) v = fma(-xr[t], sL[t * (SB + 1) + c], v);
+            xr[c] = v / sL[c * (SB + 1) + c];
+        }
+    }
+}
+
+template <typename T>
+static int trsm_rows_l(void *X, int64_t ldx, int64_t rows, const void *Ljj, int64_t ldl, int jb, hipStream_t st)
+{
+    if (rows <= 0 || jb <= 0) return GPX_OK;
+    const dim3 grid((unsigned)cdiv(rows, 256)), block(256);
+    const bool vec_ok = jb == SB && ldx % (16 / (int64_t)sizeof(T)) == 0 && ((uintptr_t)X) % 16 == 0;
+    ProfScope prof(PC_TRSM_ROWS, (double)rows * jb * jb, st);
+    if (vec_ok) hipLaunchKernelGGL((trsm_rows_l_kernel<T, true>), grid, block, 0, st, (T *)X, ldx, rows, (const T *)Ljj, ldl, jb);
+    else hipLaunchKernelGGL((trsm_rows_l_kernel<T, false>), grid, block, 0, st, (T *)X, ldx, rows, (const T *)Ljj, ldl, jb);
+    GPX_LAUNCH_CHECK();
+    return GPX_OK;
+}
+
+static thread_local ThreadScratch g_trsml_scr;  // X L^-1: the transposed row panel of L of the block being applied
+
+// X (m x n) <- X * L^-1, blocked and RIGHT-looking, block columns from the LAST to the first: after the columns of a block
+// are solved they are applied at once to every column before them,
+//   X[:, 0:k0] -= X[:, blk] * L[blk, 0:k0]      (m x k0 output, K = block width).
+// gemm_nt wants both operands K-contiguous and this one is a ROW panel of L read along its rows, so the panel is staged
+// transposed (LT[c][t] = L[k0 + t, c], ld = block width rounded up to 16) in thread scratch first: n^2 / 2 elements moved per sweep.
+// Operator route (the caller's TrsvOps of THIS factor, trsm_ops_ok, X and ldx aligned as L and ldl): the in-block solve is ONE
+// product with Wt_k = inv(L_kk)^T -- gemm_nt(X_k, Wt_k) = X_k inv(L_kk) -- into the scratch block trsm_right_lt_ops uses,
+// copied back.  64-wide route (everything else): two levels as in trsm_right_lt (outer 256 / 512, inner 64); the transposed
+// panel includes the outer block's own columns, so the left-looking products inside the block read it too, and a 64 x 64
+// diagonal block is solved by substitution along the rows (trsm_rows_l_kernel).
+int trsm_right_l(int dtype, const void *L, int64_t n, int64_t ldl, void *X, int64_t m, int64_t ldx, hipStream_t st, TrsvOps *ops)
+{
+    if (n <= 0 || m <= 0) return GPX_OK;
+    const size_t es = esize(dtype);
+    auto Lp = [&](int64_t r, int64_t c) { return (const char *)L + (r * ldl + c) * es; };
+    auto Xp = [&](int64_t c) { return (char *)X + c * es; };
+    if (ops && trsm_ops_ok(dtype, L, n, ldl) && ldx % (16 / (int64_t)es) == 0 && ((uintptr_t)X) % 16 == 0) {
+        if (!ops->valid) GPX_TRY(trsv_ops_build_upto(dtype, L, n, ldl, ops, n / OB, st));
+        if (ops->valid && ops->mem.p) {
+            route_hit(RT_TRSM_L_OPS);
+            void *scr = nullptr, *LT = nullptr;
+            GPX_TRY(g_trsm_scr.get((size_t)m * OB * es, &scr));
+            GPX_TRY(g_trsml_scr.get((size_t)(n - OB) * OB * es, &LT));
+            for (int64_t k = n / OB - 1; k >= 0; --k) {
+                const int64_t k0 = k * OB;
+                const void *Wtk = dtype == GPX_F64 ? (void *)OpsView<double>(ops->mem.p, n).Wt(k) : (void *)OpsView<float>(ops->mem.p, n).Wt(k);
+                GPX_TRY(gemm_nt(dtype, m, OB, OB, Xp(k0), ldx, Wtk, OB, scr, OB, 1.0, GPX_FULL, 0, 0, st, 1));
+                GPX_HIP(hipMemcpy2DAsync(Xp(k0), (size_t)ldx * es, scr, (size_t)OB * es, (size_t)OB * es, (size_t)m, hipMemcpyDeviceToDevice, st));
+                if (k0 > 0) {
+                    GPX_TRY(transpose(dtype, Lp(k0, 0), ldl, OB, k0, LT, OB, st));
+                    GPX_TRY(gemm_nt(dtype, m, k0, OB, Xp(k0), ldx, LT, OB, X, ldx, -1.0, GPX_FULL, 0, 0, st));
+                }
+            }
+            return GPX_OK;
+        }
+    }
+    const int64_t NB = n >= 8192 ? OB : 256;
+    const int64_t ldt = std::min<int64_t>(NB, round_up(n, 16));
+    void *LTv = nullptr;
+    GPX_TRY(g_trsml_scr.get((size_t)n * ldt * es, &LTv));
+    const char *LT = (const char *)LTv;
+    for (int64_t k0 = (n - 1) / NB * NB; k0 >= 0; k0 -= NB) {
+        const int64_t kb = std::min(NB, n - k0), ke = k0 + kb;
+        // LT[c][t] = L[k0 + t, c] for c < ke, t < kb (the block's own columns too: only what lies below a diagonal block is read)
+        GPX_TRY(transpose(dtype, Lp(k0, 0), ldl, kb, ke, LTv, ldt, st));
+        for (int64_t j0 = k0 + (kb - 1) / SB * SB; j0 >= k0; j0 -= SB) {
+            const int jb = (int)std::min<int64_t>(SB, ke - j0);
+            const int64_t je = j0 + jb;
+            if (je < ke)
+                GPX_TRY(gemm_nt(dtype, m, jb, ke - je, Xp(je), ldx, LT + (j0 * ldt + (je - k0)) * es, ldt, Xp(j0), ldx, -1.0,
+                                GPX_FULL, 0, 0, st));
+            if (dtype == GPX_F64) GPX_TRY(trsm_rows_l<double>(Xp(j0), ldx, m, Lp(j0, j0), ldl, jb, st));
+            else GPX_TRY(trsm_rows_l<float>(Xp(j0), ldx, m, Lp(j0, j0), ldl, jb, st));
+        }
+        if (k0 > 0)
+            GPX_TRY(gemm_nt(dtype, m, k0, kb, Xp(k0), ldx, LT, ldt, X, ldx, -1.0, GPX_FULL, 0, 0, st));
+    }
+    return GPX_OK;
+}
+
 template <typename T>
 __global__ void eye_kernel(T *__restrict__ X, int64_t n, int64_t ld)
 {
@@ -1348,6 +1503,21 @@ int gpx_d_trsm_right_lt(int dtype, const void *L, int64_t n, int64_t ldl, void *
     GPX_ARG(ldl % 16 == 0 && ldx % 16 == 0, "ldl/ldx must be multiples of 16 elements");
     GPX_ARG(((uintptr_t)L) % 16 == 0 && ((uintptr_t)X) % 16 == 0, "L/X must be 16-byte aligned");
     return trsm_right_lt(dtype, L, n, ldl, X, m, ldx, S(stream));
+}
+
+int gpx_d_trsm_right_l(int dtype, const void *L, int64_t n, int64_t ldl, void *X, int64_t m,
+                       int64_t ldx, void *stream)
+{
+    gpx::StreamTurn turn__((hipStream_t)stream);     // (this thread's scratch buffers: one stream at a time, gpx_mem.h)
+    GPX_TRY(ensure_device());
+    GPX_ARG(dtype == GPX_F64 || dtype == GPX_F32, "dtype must be GPX_F64 or GPX_F32");
+    GPX_ARG(n >= 0 && m >= 0, "negative dimension");
+    if (n == 0 || m == 0) return GPX_OK;
+    GPX_ARG(L && X, "NULL pointer");
+    GPX_ARG(ldl >= n && ldx >= n, "leading dimension too small");
+    GPX_ARG(ldl % 16 == 0 && ldx % 16 == 0, "ldl/ldx must be multiples of 16 elements");
+    GPX_ARG(((uintptr_t)L) % 16 == 0 && ((uintptr_t)X) % 16 == 0, "L/X must be 16-byte aligned");
+    return trsm_right_l(dtype, L, n, ldl, X, m, ldx, S(stream));
 }
 
 int gpx_d_logdet_chol(int dtype, const void *L, int64_t n, int64_t ldl, double *out_dev, void *stream)

@@ -538,6 +538,51 @@ class GP(object):
         xo, _ = self._xo(xo)
         return self.mean(xo), self.var(xo, noise=noise)
 
+    # ---- input-space gradients of the prediction (extension) ----
+    def _grad_args(self, xo, chunk_rows, name):
+        """(xo, m, chunk_rows, the fitted state) of a gradient call; every refusal comes before the library is touched."""
+        xo, m = self._xo(xo)
+        chunk_rows = int(chunk_rows)
+        if chunk_rows < 0 or chunk_rows % 128:
+            raise ValueError("invalid value for chunk_rows: %d (0, or a multiple of 128)" % chunk_rows)
+        if getattr(self.K, "_native_kernel", None) is None:
+            raise NotImplementedError("%s needs a built-in kernel: the kernel plugin contract (K, jacobian, hessian) has no "
+                                      "derivative with respect to the inputs, dk/dx" % name)
+        return xo, m, chunk_rows, self._fit_pd()
+
+    def dmean_dx(self, xo):
+        r"""Gradient of the predictive mean with respect to the test point,
+        :math:`\partial m(x^*_i) / \partial x^*_i = \sum_j \alpha_j \, \partial k(x^*_i, x_j) / \partial x^*_i`, float64 in the
+        shape of `xo` (``(m,)`` for 1-D inputs, ``(m, d)`` otherwise).  One fused device pass; no ``(m, n)`` matrix exists."""
+        xo, m, _, st = self._grad_args(xo, 0, "dmean_dx")
+        out = np.empty(xo.shape, dtype=DTYPE)
+        _lib.check(_lib.load().gpx_gp_mean_grad(st.handle, _lib.dptr(xo), m, _lib.dptr(out)))
+        return out
+
+    def _var_grad(self, xo, chunk_rows, name, want_var):
+        xo, m, chunk_rows, st = self._grad_args(xo, chunk_rows, name)
+        grad = np.empty(xo.shape, dtype=DTYPE)
+        var = np.empty(m, dtype=DTYPE) if want_var else None
+        _lib.check(_lib.load().gpx_gp_var_grad(st.handle, _lib.dptr(xo), m, chunk_rows,
+                                               _lib.dptr(var) if want_var else None, _lib.dptr(grad)))
+        return var, grad
+
+    def dvar_dx(self, xo, chunk_rows=0):
+        r"""Gradient of the predictive variance `var(xo)` with respect to the test point,
+        :math:`-2 \sum_j \beta_{ij} \, \partial k(x^*_i, x_j) / \partial x^*_i` with
+        :math:`\beta_i = K_{xx}^{-1} k(x, x^*_i)`, float64 in the shape of `xo`.  Row chunks as `var`: per chunk
+        :math:`X = K(x^*_c, x)`, :math:`X \leftarrow X L^{-\top}`, :math:`X \leftarrow X L^{-1}`, then one fused pass; no
+        :math:`K^{-1}` is formed.  The noise term of ``var(xo, noise=True)`` does not depend on `xo`."""
+        return self._var_grad(xo, chunk_rows, "dvar_dx", False)[1]
+
+    def predict_grad(self, xo, noise=False, chunk_rows=0):
+        r"""``(mean, var, dmean_dx, dvar_dx)`` at `xo`: what an acquisition function and its optimiser need.  The variance
+        comes out of the first sweep of the chunk pass that yields its gradient."""
+        var, dvar = self._var_grad(xo, chunk_rows, "predict_grad", True)
+        if noise:
+            var += self._s ** 2
+        return self.mean(xo), var, self.dmean_dx(xo), dvar
+
     # ---- leave-one-out cross-validation (extension; RW06 section 5.4.2) ----
     @memoprop
     def inv_Kxx_diag(self):

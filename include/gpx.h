@@ -170,6 +170,8 @@ int gpx_stream_wait_event(void *stream, void *event);
 #define GPX_PROF_GEMM_GENERIC 8 /* gemm_nt_kernel<T> (unaligned / K-tail shapes); flops */
 #define GPX_PROF_GEMM_PANEL   9 /* gemm_nt_fast_kernel<T,128,0>: panel / covariance products; flops */
 #define GPX_PROF_GEMM_N64    10 /* gemm_nt_fast_kernel<T,64,1>: trailing updates of few tiles on 128 x 64 tiles; flops */
+#define GPX_PROF_TRANSPOSE   11 /* transpose_kernel: the row panels of L staged for X L^-1; bytes read + written */
+#define GPX_PROF_PRED_GRAD   12 /* pred_grad_kernel + its slice reduction; kernel evaluations m*n per window of dimensions */
 int gpx_prof_enable(int on);    /* also clears the registry */
 int gpx_prof_read(int cls, double *launches, double *total_ms, double *total_work);
 
@@ -194,6 +196,8 @@ int gpx_prof_read(int cls, double *launches, double *total_ms, double *total_wor
 #define GPX_ROUTE_POTRF_PAIR     14   /* a factorisation that entered the pair phase: far trailing updates of depth K = 2048, one per two panels */
 #define GPX_ROUTE_VAR_CHUNK      15   /* predictive variance (gpx_gp_var, gpx_gp_var_from_K, gpx_mg_var): one hit per row chunk */
 #define GPX_ROUTE_LOO_CHUNK      16   /* leave-one-out (gpx_gp_inv_diag, gpx_gp_loo): one hit per row chunk of the identity swept; none when the handle still has the diagonal */
+#define GPX_ROUTE_TRSM_L_OPS     17   /* X L^-1 (gpx_gp_var_grad): in-block step as one product with inv(L_kk); one hit per sweep */
+#define GPX_ROUTE_GRAD_CHUNK     18   /* input-space gradient of the variance (gpx_gp_var_grad): one hit per row chunk */
 int gpx_debug_route_count(int route, int64_t *count);
 /* roctx ranges pushed so far (GPX_ROCTX=1: every gpx_gp_* call and every launch class below it is a nested host range for
  * `rocprofv3 --marker-trace`; libroctx64.so is loaded on first use; 0 while the switch is off) */
@@ -241,6 +245,18 @@ int gpx_d_mean(int dtype, int kernel, const void *xo, int64_t m, const void *x,
  * Periodic members other than GPX_K need d == 1. */
 int gpx_d_mean_member(int dtype, int kernel, int member, const void *xo, int64_t m, const void *x,
                       int64_t n, int d, const double *params, const void *alpha, void *out, void *stream);
+
+/* Fused input-space gradient  out_dev[i, k] = scale * sum_j w_ij * dk(xo_i, x_j)/dxo_ik  for i < m, k < d, never
+ * materialising dK.  w_ij = alpha[j] (B == NULL: with alpha = K^-1 y and scale = 1 the gradient of the posterior mean) or
+ * B[i * ldb + j] (alpha == NULL: a solved chunk B = Kxox K^-1 and scale = -2 give the gradient of the posterior variance);
+ * exactly one of the two.  xo: (m, d), x: (n, d), alpha: (n,), B: (m, n) ldb, all DEVICE in `dtype`; out_dev: DEVICE DOUBLE
+ * (m, d) dense.  All three families (ARD: computed on x / w, column k divided by w_k); every d gpx_d_mean takes for the
+ * dtype, GPX_ERR_UNSUPPORTED beyond.  The differences a_k - b_k are formed directly; a pair the kernel's underflow clamp
+ * zeroes adds exactly 0.  f64 accumulation for both dtypes, fixed summation order, no atomics: bitwise repeatable.
+ * GPX_PROF_PRED_GRAD. */
+int gpx_d_pred_grad(int dtype, int kernel, const void *xo, int64_t m, const void *x, int64_t n, int d,
+                    const double *params, const void *alpha, const void *B, int64_t ldb, double scale,
+                    double *out_dev, void *stream);
 
 /* C (M x N, ldc) += alpha * A (M x K, lda) * B (N x K, ldb)^T -- the MFMA work-horse.
  * tri = GPX_LOWER: only tiles with some row >= col are touched and elements
@@ -307,6 +323,13 @@ int gpx_d_panel_gemv_t(int dtype, const void *Lp, int64_t ldl, int64_t rows, int
  * V = L^-1 Kxxo, the factor of the posterior covariance (gp/gp.py:622-625). */
 int gpx_d_trsm_right_lt(int dtype, const void *L, int64_t n, int64_t ldl, void *X,
                         int64_t m, int64_t ldx, void *stream);
+
+/* X (m x n, ldx) <- X * L^-1, in place: the mirror of gpx_d_trsm_right_lt (block columns from the last to the first,
+ * right-looking; the row panel of L that a far update multiplies by is staged transposed in per-thread scratch, at most
+ * n x 512 elements).  After gpx_d_trsm_right_lt on X = Kxox this yields the rows of Kxox K^-1.  Same argument checks;
+ * brings no block operators, so the 64-wide route.  Deterministic (no atomics, fixed order). */
+int gpx_d_trsm_right_l(int dtype, const void *L, int64_t n, int64_t ldl, void *X,
+                       int64_t m, int64_t ldx, void *stream);
 
 /* out_dev[0] = 2 * sum_i log L[i,i]  (f64 accumulation for both dtypes).
  * Replaces the LU-based np.linalg.slogdet(K) of gp_c.pyx:21 given L. */
@@ -406,6 +429,14 @@ int gpx_gp_inv_diag(gpx_gp_t *gp, int64_t chunk_rows, double *out);
  * density at y_i (eq. 5.10); *log_p_sum their sum (eq. 5.11), reduced on the device in a fixed order.  (n,) HOST float64
  * each; any pointer may be NULL.  As gpx_gp_inv_diag, and y must be finite. */
 int gpx_gp_loo(gpx_gp_t *gp, int64_t chunk_rows, double *mean, double *var, double *log_p, double *log_p_sum);
+/* Input-space gradients of the prediction at xo (m, d) HOST float64 -> grad (m, d) HOST float64; m = 0 is legal.
+ * gpx_gp_mean_grad: d mean(xo_i) / d xo_i, one fused pass (gpx_d_pred_grad with alpha); needs finite y, as gpx_gp_mean.
+ * gpx_gp_var_grad: d var(xo_i) / d xo_i = -2 sum_j beta_ij dk(xo_i, x_j)/dxo_i with beta_i = K^-1 k(x, xo_i), in the row
+ * chunks of gpx_gp_var (same chunk_rows, rule, buffer and errors): X = K(xo_c, x), X <- X L^-T, X <- X L^-1, then
+ * gpx_d_pred_grad with B = X and scale = -2.  var (m,) HOST float64, optional: the variance itself, taken from the first
+ * sweep of the same pass (what gpx_gp_var returns).  Nothing n x n beside the factor exists; one download at the end. */
+int gpx_gp_mean_grad(gpx_gp_t *gp, const double *xo, int64_t m, double *grad);
+int gpx_gp_var_grad(gpx_gp_t *gp, const double *xo, int64_t m, int64_t chunk_rows, double *var, double *grad);
 /* copy-outs to HOST float64: Kxx is rebuilt (full, + s^2 I); L has zero upper */
 int gpx_gp_get_Kxx(gpx_gp_t *gp, double *out, int64_t ld);
 int gpx_gp_get_Lxx(gpx_gp_t *gp, double *out, int64_t ld);
