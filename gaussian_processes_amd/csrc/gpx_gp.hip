@@ -38,7 +38,7 @@ __global__ void cvt_to_f64_2d(const T *__restrict__ src, int64_t lds, double *__
 }
 
 // upload a host f64 array into a device buffer of dtype (via a temporary when f32)
-static int upload_f64(int dtype, void *dst, const double *src, int64_t count, hipStream_t st)
+int upload_f64(int dtype, void *dst, const double *src, int64_t count, hipStream_t st)
 {
     if (count <= 0) return GPX_OK;
     if (dtype == GPX_F64) {

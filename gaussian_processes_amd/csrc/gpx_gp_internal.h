@@ -34,6 +34,8 @@ struct gpx_gp {
 namespace gpx {
 // x_finite / y_finite of the handle from its device arrays (one O(n d) reduction; synchronous)
 int gp_scan_finite(gpx_gp *g);
+// upload a host f64 array into a device buffer of dtype (gpx_gp.hip); returns when `src` may be reused
+int upload_f64(int dtype, void *dst, const double *src, int64_t count, hipStream_t st);
 // kernel parameters of a family at dimension d
 static inline int nparams_of(int kernel, int d) { return kernel == GPX_KERNEL_GAUSSIAN_ARD ? 1 + d : (kernel == GPX_KERNEL_PERIODIC ? 3 : 2); }
 // The points and the two isotropic constants this handle's launches use: its own (x, params), or for the ARD family the

@@ -699,6 +699,55 @@ class GP(object):
         obj._dev = st
         return obj
 
+    # ---- growing a fitted GP (extension) ----
+    def extend(self, x_new, y_new):
+        r"""A new, fitted `GP` on the data of this one plus `k` further observations, without refactoring: the Cholesky
+        factor of the bordered matrix is the old factor with `k` rows appended,
+        :math:`X = K(x_{new}, x) L^{-\top}` and the factor of :math:`K(x_{new}, x_{new}) + s^2 I - X X^\top`.  One
+        triangular sweep over `k` right-hand sides (:math:`O(n^2 k)`) and two solves for the new :math:`K^{-1} y`
+        (:math:`O(n^2)`), against :math:`n^3/3` for ``g.x = ...; g.y = ...``.  ``x_new``: ``(k,)`` for 1-D inputs or
+        ``(k, d)``; ``y_new``: ``(k,)``; ``k >= 1``.  The result carries a deep copy of `K` and the same `s`, `dtype` and
+        `device`; this object and its device state are unchanged.  Raises numpy.linalg.LinAlgError when this GP's
+        `Kxx` is not positive definite; when the extended matrix is not, the result behaves like any GP whose fit
+        failed (``log_lh == -inf``, `Lxx` raises).
+
+        Memory: source and result coexist, so TWO factors are resident in HBM (:math:`n^2 + (n + k)^2` elements)
+        until the source is dropped; ``g = g.extend(xn, yn)`` releases it."""
+        x_new = np.ascontiguousarray(x_new, dtype=DTYPE)       # every refusal comes before the library is touched
+        y_new = np.ascontiguousarray(y_new, dtype=DTYPE)
+        if x_new.ndim != self._x.ndim or (x_new.ndim == 2 and x_new.shape[1] != self._d):
+            raise ValueError("invalid shape for x_new: %s" % str(x_new.shape))
+        k = x_new.shape[0]
+        if k < 1:
+            raise ValueError("extend needs at least one new point (k = %d)" % k)
+        if y_new.shape != (k,):
+            raise ValueError("invalid shape for y_new: %s" % str(y_new.shape))
+        st = self._fit_pd()
+        lib = _lib.load()
+        h, info = ctypes.c_void_p(), ctypes.c_int(0)
+        if getattr(self.K, "_native_kernel", None) is not None:
+            _lib.check(lib.gpx_gp_extend(st.handle, _lib.dptr(x_new), _lib.dptr(y_new), k, ctypes.byref(h), ctypes.byref(info)))
+        else:
+            Kno = np.ascontiguousarray(self.K(x_new, self._x), dtype=DTYPE)
+            Knn = np.array(self.K(x_new, x_new), dtype=DTYPE, order="C")
+            Knn[np.diag_indices_from(Knn)] += self._s ** 2
+            _check_finite(Kno)
+            _check_finite(Knn)
+            _lib.check(lib.gpx_gp_extend_from_K(st.handle, _lib.dptr(x_new), _lib.dptr(y_new), k, _lib.dptr(Kno),
+                                                _lib.dptr(Knn), ctypes.byref(h), ctypes.byref(info)))
+        try:
+            obj = type(self)(deepcopy(self.K), np.concatenate([self._x, x_new]), np.concatenate([self._y, y_new]),
+                             s=self._s, dtype="float64" if self._dtype == _lib.F64 else "float32", device=self._device)
+            new =_DeviceState.adopt(h, (obj._dtype, st.key[1], obj._n, obj._d, obj._device))
+        except Exception:
+            lib.gpx_gp_destroy(h)
+            raise
+        new.info = info.value
+        new.data_version = obj._data_version
+        new.params_version = new.fit_version = obj._version
+        obj._dev = new
+        return obj
+
     def fit_timing(self):
         """Milliseconds of the last device fit: kernel build, potrf, solve, reductions, total
         (HIP events on the handle's stream)."""

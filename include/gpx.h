@@ -172,6 +172,7 @@ int gpx_stream_wait_event(void *stream, void *event);
 #define GPX_PROF_GEMM_N64    10 /* gemm_nt_fast_kernel<T,64,1>: trailing updates of few tiles on 128 x 64 tiles; flops */
 #define GPX_PROF_TRANSPOSE   11 /* transpose_kernel: the row panels of L staged for X L^-1; bytes read + written */
 #define GPX_PROF_PRED_GRAD   12 /* pred_grad_kernel + its slice reduction; kernel evaluations m*n per window of dimensions */
+#define GPX_PROF_EXTEND      13 /* copy_lower_kernel + schur_reduce_kernel (gpx_gp_extend): bytes read + written */
 int gpx_prof_enable(int on);    /* also clears the registry */
 int gpx_prof_read(int cls, double *launches, double *total_ms, double *total_work);
 
@@ -198,6 +199,7 @@ int gpx_prof_read(int cls, double *launches, double *total_ms, double *total_wor
 #define GPX_ROUTE_LOO_CHUNK      16   /* leave-one-out (gpx_gp_inv_diag, gpx_gp_loo): one hit per row chunk of the identity swept; none when the handle still has the diagonal */
 #define GPX_ROUTE_TRSM_L_OPS     17   /* X L^-1 (gpx_gp_var_grad): in-block step as one product with inv(L_kk); one hit per sweep */
 #define GPX_ROUTE_GRAD_CHUNK     18   /* input-space gradient of the variance (gpx_gp_var_grad): one hit per row chunk */
+#define GPX_ROUTE_EXTEND         19   /* gpx_gp_extend / gpx_gp_extend_from_K: one hit per call                        */
 int gpx_debug_route_count(int route, int64_t *count);
 /* roctx ranges pushed so far (GPX_ROCTX=1: every gpx_gp_* call and every launch class below it is a nested host range for
  * `rocprofv3 --marker-trace`; libroctx64.so is loaded on first use; 0 while the switch is off) */
@@ -362,6 +364,20 @@ int gpx_d_loo_rows(int dtype, const void *X, int64_t rows, int64_t n, int64_t ld
 int gpx_d_dot(int dtype, const void *a, const void *b, int64_t n, double *out_dev,
               void *stream);
 
+/* dst[i, j] = src[i, j] for j <= i < n (lower trapezoid, re-pitched lds -> ldd); 16-byte vectors where both sides allow.
+ * Elements of dst to the right of the 16-byte vector that holds the diagonal are not written.
+ * (Both bases and both pitches 16-byte aligned: row i moves whole vectors up to the one that holds column i, which stays
+ * inside the pitch; otherwise exactly columns [0, i], one element at a time.  n^2 / 2 elements each way, where a strided
+ * memcpy of the square moves n^2.  GPX_PROF_EXTEND.) */
+int gpx_d_copy_lower(int dtype, const void *src, int64_t lds, void *dst, int64_t ldd, int64_t n, void *stream);
+/* S[i, j] -= sum_c B[i, c] B[j, c]  for j <= i < k, c < n  (B: k x n, ldb; S: k x k, lds; strict upper untouched).
+ * Split over column slices of B so that few rows still fill the chip; the slices' partial products are summed in f64
+ * in ascending slice order and rounded once: no atomics, bitwise repeatable.
+ * (The partial products are MFMA products in `dtype` into this host thread's scratch; any base / pitch is accepted, the
+ * aligned ones take the fast product kernel.  When all n columns fit ONE slice there are no partials: one product
+ * S -= B B^T on the lower tiles, accumulated by the product kernel in `dtype`.) */
+int gpx_d_schur_lower(int dtype, const void *B, int64_t k, int64_t n, int64_t ldb, void *S, int64_t lds, void *stream);
+
 /* ------------------------------------------------ fitted-GP device handle -- */
 /* One handle = one GP resident in HBM: x, y, the kernel matrix / its factor
  * (in place), alpha = K^-1 y, logdet, y^T alpha.  Mirrors the memoised
@@ -437,6 +453,24 @@ int gpx_gp_loo(gpx_gp_t *gp, int64_t chunk_rows, double *mean, double *var, doub
  * sweep of the same pass (what gpx_gp_var returns).  Nothing n x n beside the factor exists; one download at the end. */
 int gpx_gp_mean_grad(gpx_gp_t *gp, const double *xo, int64_t m, double *grad);
 int gpx_gp_var_grad(gpx_gp_t *gp, const double *xo, int64_t m, int64_t chunk_rows, double *var, double *grad);
+/* Growing a fitted GP by k observations without refactoring.  The factor of the bordered matrix is the old factor with k
+ * rows appended:  K' = [K B^T; B C],  L' = [L 0; X Ls],  X = B L^-T (k x n),  Ls Ls^T = C - X X^T (k x k),
+ * B = K(x_new, x), C = K(x_new, x_new) + s^2 I:  one triangular sweep over k right-hand sides (n^2 k flops), a k x k
+ * Schur complement and its factorisation, two single-rhs solves for the new alpha.
+ * A NEW fitted handle for the n + k points (x; x_new), (y; y_new), same dtype / kernel / params / s as `gp`, whose factor is
+ * the factor of `gp` with k rows appended -- no kernel matrix of the old points is rebuilt, nothing n x n is factored.
+ * `gp` must be fitted and positive definite (else GPX_ERR_ARG) and is left untouched and usable; k >= 1.
+ * x_new (k, d), y_new (k,) HOST float64.  *info (HOST, may not be NULL): 0, or n + j (1-based) when the j-th pivot of the
+ * Schur complement is not positive -- exactly what potrf of the whole (n + k) matrix would report; the handle is then
+ * "fitted, not PD" like one from gpx_gp_fit.  Synchronous.  On any failure *out = NULL and `gp` is intact.
+ * The one thing of `gp` the call may change: block operators of the solves that `gp` has not built yet are completed (on the
+ * new handle's stream, which is synchronised before the call returns or the new handle is destroyed), as by any gpx_gp_cov.
+ * Source and result coexist: two factors are resident until the caller destroys one.  gpx_gp_last_timing of the new handle:
+ * [0] rows of K [1] copy + sweep + Schur + potrf [2] solves [3] reductions [4] total. */
+int gpx_gp_extend(gpx_gp_t *gp, const double *x_new, const double *y_new, int64_t k, gpx_gp_t **out, int *info);
+/* plugin kernels: the caller supplies B = K(x_new, x) (k, n) and C = K(x_new, x_new) + s^2 I (k, k; lower read), HOST float64 */
+int gpx_gp_extend_from_K(gpx_gp_t *gp, const double *x_new, const double *y_new, int64_t k,
+                         const double *Knew_old, const double *Knew_new, gpx_gp_t **out, int *info);
 /* copy-outs to HOST float64: Kxx is rebuilt (full, + s^2 I); L has zero upper */
 int gpx_gp_get_Kxx(gpx_gp_t *gp, double *out, int64_t ld);
 int gpx_gp_get_Lxx(gpx_gp_t *gp, double *out, int64_t ld);
