@@ -261,13 +261,10 @@ static int deriv_vectors(DerivState &D)
 
 static int read_info(gpx_gp *g, int *info, double *logdet, double *yta)
 {
-    double h4[4];
-    GPX_HIP(hipMemcpyAsync(h4, g->scal, sizeof(h4), hipMemcpyDeviceToHost, g->st));
-    GPX_HIP(hipStreamSynchronize(g->st));
-    memcpy(info, &h4[3], sizeof(int));
-    GPX_TRY(check_internal_info(*info));
+    GpScal sc;
+    GPX_TRY(gp_read_scal(g, &sc));
     if (!g->y_finite) { set_error("array must not contain infs or NaNs (y)"); return GPX_ERR_ARG; }   // gp/gp.py:332-334
-    *logdet = h4[0]; *yta = h4[1];
+    *info = sc.info; *logdet = sc.logdet; *yta = sc.yta;
     return GPX_OK;
 }
 
@@ -426,13 +423,7 @@ static int dm_t(gpx_gp *g, const double *xo, int64_t m, double *out)
     GPX_TRY(o1.alloc((size_t)m * sizeof(T)));
     GPX_TRY(o2.alloc((size_t)m * sizeof(T)));
     GPX_TRY(res.alloc((size_t)P * m * sizeof(T)));
-    {
-        // upload the test points (host f64 -> dtype)
-        std::vector<T> h((size_t)m * g->d);
-        for (size_t i = 0; i < h.size(); ++i) h[i] = (T)xo[i];
-        GPX_HIP(hipMemcpyAsync(dxo.p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, st));
-        GPX_HIP(hipStreamSynchronize(st));
-    }
+    GPX_TRY(upload_f64(g->dtype, dxo.p, m * g->d, xo, m * g->d, 1, m * g->d, st));
     const int *jm = jac_members(g->kernel);
     const unsigned mb = (unsigned)cdiv(m, 256);
     for (int i = 0; i < P; ++i) {
@@ -446,11 +437,7 @@ static int dm_t(gpx_gp *g, const double *xo, int64_t m, double *out)
                            (const T *)o2.p, (T *)res.p + (size_t)i * m, m, 1.0);
         GPX_LAUNCH_CHECK();
     }
-    std::vector<T> h((size_t)P * m);
-    GPX_HIP(hipMemcpyAsync(h.data(), res.p, h.size() * sizeof(T), hipMemcpyDeviceToHost, st));
-    GPX_HIP(hipStreamSynchronize(st));
-    for (size_t i = 0; i < h.size(); ++i) out[i] = (double)h[i];
-    return GPX_OK;
+    return download_f64(g->dtype, out, P * m, res.p, P * m, 1, P * m, 0, st);
 }
 
 
@@ -532,9 +519,7 @@ struct Glue {
     int upload(DevBuf &b, const double *h, int64_t rows, int64_t cols, int64_t ldd)
     {
         if (!b.p) GPX_TRY(b.alloc((size_t)rows * ldd * 8));
-        GPX_HIP(hipMemcpy2DAsync(b.p, (size_t)ldd * 8, h, (size_t)cols * 8, (size_t)cols * 8, (size_t)rows, hipMemcpyHostToDevice, st));
-        GPX_HIP(hipStreamSynchronize(st));           // (the host buffer is the caller's: done with it on return)
-        return GPX_OK;
+        return upload_f64(GPX_F64, b.p, ldd, h, cols, rows, cols, st);   // (the host buffer is the caller's: done with it on return)
     }
     int vec(DevBuf &b, int64_t len) { return b.alloc((size_t)round_up(len, 16) * 8); }
     // out (rows) = M (rows x cols, ldm) v (cols)

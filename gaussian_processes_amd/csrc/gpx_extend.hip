@@ -143,33 +143,6 @@ int schur_lower(int dtype, const void *B, int64_t k, int64_t n, int64_t ldb, voi
 }
 
 // ---- the handle ---------------------------------------------------------------------------------------------------------
-// dst (rows x cols, ldd, dtype T) <- src (rows x cols, dense, f64)
-template <typename T>
-__global__ void cvt_rows_kernel(const double *__restrict__ src, T *__restrict__ dst, int64_t ldd, int64_t rows, int64_t cols)
-{
-    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= cols) return;
-    for (int64_t r = blockIdx.y; r < rows; r += gridDim.y) dst[r * ldd + c] = (T)src[r * cols + c];
-}
-
-// a HOST f64 (rows x cols) array into a pitched device matrix of the handle's dtype (the caller's B and C; vectors go
-// through upload_f64); returns when `src` may be reused
-static int upload_rows(int dtype, void *dst, int64_t ldd, const double *src, int64_t rows, int64_t cols, hipStream_t st)
-{
-    if (rows <= 0 || cols <= 0) return GPX_OK;
-    DevBuf stage;
-    GPX_TRY(stage.alloc((size_t)rows * cols * sizeof(double)));
-    GPX_HIP(hipMemcpyAsync(stage.p, src, (size_t)rows * cols * sizeof(double), hipMemcpyHostToDevice, st));
-    const dim3 grid((unsigned)cdiv(cols, 256), (unsigned)std::min<int64_t>(rows, 32768)), block(256);
-    if (dtype == GPX_F64)
-        hipLaunchKernelGGL((cvt_rows_kernel<double>), grid, block, 0, st, (const double *)stage.p, (double *)dst, ldd, rows, cols);
-    else
-        hipLaunchKernelGGL((cvt_rows_kernel<float>), grid, block, 0, st, (const double *)stage.p, (float *)dst, ldd, rows, cols);
-    GPX_LAUNCH_CHECK();
-    GPX_HIP(hipStreamSynchronize(st));
-    return GPX_OK;
-}
-
 // potrf of the Schur complement reports its j-th pivot; the whole (n + k) matrix would have reported n + j
 __global__ void info_shift_kernel(int *info, int shift)
 {
@@ -182,15 +155,7 @@ static int extend_impl(gpx_gp *g, const double *x_new, const double *y_new, int6
 {
     const int64_t n = g->n, n2 = n + k, d = g->d, lda = g->lda;
     const size_t es = esize(g->dtype);
-    {   // a factor that exists
-        double h4[4];
-        GPX_HIP(hipMemcpyAsync(h4, g->scal, sizeof(h4), hipMemcpyDeviceToHost, g->st));
-        GPX_HIP(hipStreamSynchronize(g->st));
-        int info0;
-        memcpy(&info0, &h4[3], sizeof(int));
-        GPX_TRY(check_internal_info(info0));
-        if (info0 != 0) { set_error("Kxx is not positive definite (info = %d): there is no factor to extend", info0); return GPX_ERR_ARG; }
-    }
+    GPX_TRY(gp_need_factor(g, "to extend"));
     route_hit(RT_EXTEND);
     gpx_gp_t *g2 = nullptr;
     GPX_TRY(gpx_gp_create(&g2, g->dtype, g->kernel, n2, g->d));
@@ -202,8 +167,8 @@ static int extend_impl(gpx_gp *g, const double *x_new, const double *y_new, int6
     // 1. the data: the old points device to device, the new ones uploaded behind them
     GPX_HIP(hipMemcpyAsync(g2->x, g->x, (size_t)n * d * es, hipMemcpyDeviceToDevice, st));
     GPX_HIP(hipMemcpyAsync(g2->y, g->y, (size_t)n * es, hipMemcpyDeviceToDevice, st));
-    GPX_TRY(upload_f64(g->dtype, (char *)g2->x + (size_t)n * d * es, x_new, k * d, st));
-    GPX_TRY(upload_f64(g->dtype, (char *)g2->y + (size_t)n * es, y_new, k, st));
+    GPX_TRY(upload_f64(g->dtype, (char *)g2->x + (size_t)n * d * es, k * d, x_new, k * d, 1, k * d, st));
+    GPX_TRY(upload_f64(g->dtype, (char *)g2->y + (size_t)n * es, k, y_new, k, 1, k, st));
     memcpy(g2->params, g->params, sizeof(g->params));
     g2->s = g->s;
     g2->have_data = true; g2->have_params = g->have_params;
@@ -213,10 +178,10 @@ static int extend_impl(gpx_gp *g, const double *x_new, const double *y_new, int6
     const GpView v = gp_view(g2);
     const char *xn = (const char *)v.x + (size_t)n * d * es;
     char *A2 = (char *)g2->A, *X = A2 + (size_t)n * lda2 * es;     // rows [n, n2): 16-byte aligned, lda2 is a multiple of 16
-    int *info_dev = (int *)(g2->scal + 3);
+    int *info_dev = &g2->scal->info;
     GPX_HIP(hipEventRecord(g2->ev[0], st));
     // 2. B = K(x_new, x) into rows [n, n2) x columns [0, n)
-    if (Kno) GPX_TRY(upload_rows(g->dtype, X, lda2, Kno, k, n, st));
+    if (Kno) GPX_TRY(upload_f64(g->dtype, X, lda2, Kno, n, k, n, st));
     else GPX_TRY(kmat(g->dtype, v.kernel, GPX_K, xn, k, v.x, n, g->d, v.params, 0.0, GPX_FULL, X, lda2, st));
     GPX_HIP(hipEventRecord(g2->ev[1], st));
     // 3. the old factor, re-pitched
@@ -228,7 +193,7 @@ static int extend_impl(gpx_gp *g, const double *x_new, const double *y_new, int6
     const int64_t ldc = round_up(k, 16);
     DevBuf C;
     GPX_TRY(C.alloc((size_t)k * ldc * es));
-    if (Knn) GPX_TRY(upload_rows(g->dtype, C.p, ldc, Knn, k, k, st));
+    if (Knn) GPX_TRY(upload_f64(g->dtype, C.p, ldc, Knn, k, k, k, st));
     else GPX_TRY(kmat(g->dtype, v.kernel, GPX_K, xn, k, xn, k, g->d, v.params, g->s * g->s, GPX_LOWER, C.p, ldc, st));
     GPX_TRY(schur_lower(g->dtype, X, k, n, lda2, C.p, ldc, st));
     GPX_TRY(potrf(g->dtype, C.p, k, ldc, info_dev, st));
@@ -236,20 +201,10 @@ static int extend_impl(gpx_gp *g, const double *x_new, const double *y_new, int6
     GPX_LAUNCH_CHECK();
     GPX_TRY(copy_lower(g->dtype, C.p, ldc, A2 + ((size_t)n * lda2 + n) * es, lda2, k, st));
     GPX_HIP(hipEventRecord(g2->ev[2], st));
-    // 6. alpha by the two sweeps of gpx_gp_fit's non-riding branch; the new factor's operators are built lazily
+    // 6. the tail of gpx_gp_fit, both sweeps; the new factor's operators are built lazily.  (It waits for the stream: the
+    // scratch block C is free to go)
     g2->ops.invalidate();
-    g2->have_K = false; g2->have_kii = false;
-    GPX_HIP(hipMemcpyAsync(g2->t0, g2->y, (size_t)n2 * es, hipMemcpyDeviceToDevice, st));
-    GPX_TRY(trsv_lower(g->dtype, g2->A, n2, lda2, g2->t0, g2->t1, 0, st, nullptr, &g2->ops));
-    GPX_TRY(trsv_lower(g->dtype, g2->A, n2, lda2, g2->t1, g2->alpha, 1, st, nullptr, &g2->ops));
-    GPX_HIP(hipEventRecord(g2->ev[3], st));
-    GPX_TRY(logdet_chol(g->dtype, g2->A, n2, lda2, g2->scal + 0, st));
-    GPX_TRY(dot(g->dtype, g2->y, g2->alpha, n2, g2->scal + 1, st));
-    GPX_HIP(hipEventRecord(g2->ev[4], st));
-    g2->fitted = true;
-    GPX_HIP(hipMemcpyAsync(info, info_dev, sizeof(int), hipMemcpyDeviceToHost, st));
-    GPX_HIP(hipStreamSynchronize(st));                     // (also: the scratch block C is free to go)
-    GPX_TRY(check_internal_info(*info));
+    GPX_TRY(gp_finish_fit(g2, false, info));
     guard.g = nullptr;
     *out = g2;
     return GPX_OK;

@@ -9,7 +9,7 @@
 //   A      (n, lda) row-major, lda = round_up(n, 16): lower triangle holds K, then L
 //   alpha  (n,)    K^-1 y
 //   t0,t1  (n,)    solve scratch
-//   scal   3 doubles (logdet, y^T alpha, spare) + 1 int (potrf info)
+//   scal   GpScal (gpx_gp_internal.h): logdet, y^T alpha, the non-finite flags, potrf's info
 #include "gpx_common.h"
 #include <cmath>
 #include <vector>
@@ -18,11 +18,14 @@
 
 namespace gpx {
 
+// ---- the staging pair: host float64 <-> device arrays of a handle's dtype ---------------------------------------------------
+// Both kernels: grid (column blocks of 256, rows up to 32768), a row loop for what lies beyond.  (T)double rounds to nearest.
 template <typename T>
-__global__ void cvt_from_f64(const double *__restrict__ src, T *__restrict__ dst, int64_t n)
+__global__ void cvt_from_f64_2d(const double *__restrict__ src, int64_t lds, T *__restrict__ dst, int64_t ldd, int64_t rows, int64_t cols)
 {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) dst[i] = (T)src[i];
+    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= cols) return;
+    for (int64_t r = blockIdx.y; r < rows; r += gridDim.y) dst[r * ldd + c] = (T)src[r * lds + c];
 }
 
 template <typename T>
@@ -37,30 +40,37 @@ __global__ void cvt_to_f64_2d(const T *__restrict__ src, int64_t lds, double *__
     }
 }
 
-// upload a host f64 array into a device buffer of dtype (via a temporary when f32)
-int upload_f64(int dtype, void *dst, const double *src, int64_t count, hipStream_t st)
+// a (rows x cols) block of float64 from host to device or back: a vector by a plain copy, a matrix by a pitched one -- also
+// where both sides are dense (n = 8192: the plain copy of 512 MiB took 9.50 ms, the pitched one 9.35)
+static int copy_rows(void *dst, int64_t ldd, const void *src, int64_t lds, int64_t rows, int64_t cols, hipMemcpyKind kind, hipStream_t st)
 {
-    if (count <= 0) return GPX_OK;
+    if (rows == 1) GPX_HIP(hipMemcpyAsync(dst, src, (size_t)cols * 8, kind, st));
+    else GPX_HIP(hipMemcpy2DAsync(dst, (size_t)ldd * 8, src, (size_t)lds * 8, (size_t)cols * 8, (size_t)rows, kind, st));
+    return GPX_OK;
+}
+
+int upload_f64(int dtype, void *dst, int64_t ldd, const double *src, int64_t lds, int64_t rows, int64_t cols, hipStream_t st, DevBuf *stage)
+{
+    if (rows <= 0 || cols <= 0) return GPX_OK;
     if (dtype == GPX_F64) {
-        GPX_HIP(hipMemcpyAsync(dst, src, count * 8, hipMemcpyHostToDevice, st));
-        GPX_HIP(hipStreamSynchronize(st));
-        return GPX_OK;
+        GPX_TRY(copy_rows(dst, ldd, src, lds, rows, cols, hipMemcpyHostToDevice, st));
+    } else {
+        DevBuf mine;
+        if (!stage) stage = &mine;
+        if (!stage->p) GPX_TRY(stage->alloc((size_t)rows * cols * 8));
+        GPX_TRY(copy_rows(stage->p, cols, src, lds, rows, cols, hipMemcpyHostToDevice, st));
+        const dim3 grid((unsigned)cdiv(cols, 256), (unsigned)std::min<int64_t>(rows, 32768)), block(256);
+        hipLaunchKernelGGL((cvt_from_f64_2d<float>), grid, block, 0, st, (const double *)stage->p, cols, (float *)dst, ldd, rows, cols);
+        GPX_LAUNCH_CHECK();
     }
-    DevBuf tmp;
-    GPX_TRY(tmp.alloc(count * 8));
-    GPX_HIP(hipMemcpyAsync(tmp.p, src, count * 8, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL((cvt_from_f64<float>), dim3((unsigned)cdiv(count, 256)), dim3(256), 0, st,
-                       (const double *)tmp.p, (float *)dst, count);
     GPX_HIP(hipStreamSynchronize(st));
     return GPX_OK;
 }
 
-// download a device (rows x cols, lds) matrix of dtype into host f64 (ldh)
-static int download_f64(int dtype, double *dst, int64_t ldh, const void *src, int64_t lds, int64_t rows,
-                        int64_t cols, int lower_only, hipStream_t st)
+int download_f64(int dtype, double *dst, int64_t ldh, const void *src, int64_t lds, int64_t rows, int64_t cols, int lower_only,
+                 hipStream_t st)
 {
     if (rows <= 0 || cols <= 0) return GPX_OK;
-    if (cols == 1 && lds == 1 && ldh == 1) { cols = rows; rows = 1; lds = cols; ldh = cols; }   // vector
     DevBuf buf;
     GPX_TRY(buf.alloc((size_t)rows * cols * 8));
     double *tmp = (double *)buf.p;
@@ -71,8 +81,8 @@ static int download_f64(int dtype, double *dst, int64_t ldh, const void *src, in
     else
         hipLaunchKernelGGL((cvt_to_f64_2d<float>), grid, block, 0, st, (const float *)src, lds, tmp, cols,
                            rows, cols, lower_only);
-    GPX_HIP(hipMemcpy2DAsync(dst, (size_t)ldh * 8, tmp, (size_t)cols * 8, (size_t)cols * 8,
-                             (size_t)rows, hipMemcpyDeviceToHost, st));
+    GPX_LAUNCH_CHECK();
+    GPX_TRY(copy_rows(dst, ldh, tmp, cols, rows, cols, hipMemcpyDeviceToHost, st));
     GPX_HIP(hipStreamSynchronize(st));
     return GPX_OK;
 }
@@ -94,8 +104,23 @@ int gp_rescale(gpx_gp *g)
 // test points of a call: uploaded in the handle's dtype and, for the ARD family, scaled like the training points
 static int upload_points(gpx_gp *g, void *dst, const double *xo, int64_t m)
 {
-    GPX_TRY(upload_f64(g->dtype, dst, xo, m * g->d, g->st));
+    GPX_TRY(upload_f64(g->dtype, dst, m * g->d, xo, m * g->d, 1, m * g->d, g->st));
     if (g->kernel == GPX_KERNEL_GAUSSIAN_ARD) GPX_TRY(scale_points(g->dtype, dst, m, g->d, g->params + 1, dst, g->st));
+    return GPX_OK;
+}
+
+int gp_read_scal(gpx_gp *g, GpScal *host)
+{
+    GPX_HIP(hipMemcpyAsync(host, g->scal, sizeof(GpScal), hipMemcpyDeviceToHost, g->st));
+    GPX_HIP(hipStreamSynchronize(g->st));
+    return check_internal_info(host->info);
+}
+
+int gp_need_factor(gpx_gp *g, const char *what_for)
+{
+    GpScal sc;
+    GPX_TRY(gp_read_scal(g, &sc));
+    if (sc.info != 0) { set_error("Kxx is not positive definite (info = %d): there is no factor %s", sc.info, what_for); return GPX_ERR_ARG; }
     return GPX_OK;
 }
 
@@ -105,6 +130,32 @@ int check_internal_info(int info)
     set_error("internal failure inside the factorisation (info = %d: a hand-off between workgroups of the resident "
               "panel kernel timed out); the factor is not valid -- this is NOT a statement about the matrix", info);
     return GPX_ERR_INTERNAL;
+}
+
+int gp_finish_fit(gpx_gp *g, bool rhs_is_row_n, int *info)
+{
+    const size_t es = esize(g->dtype);
+    hipStream_t st = g->st;
+    // inv_Kxx_y = cho_solve((L, True), y) (gp/gp.py:332-334)
+    if (rhs_is_row_n) {
+        GPX_TRY(trsv_lower(g->dtype, g->A, g->n, g->lda, (char *)g->A + (size_t)g->n * g->lda * es, g->alpha, 1, st, nullptr, &g->ops));
+    } else {
+        GPX_HIP(hipMemcpyAsync(g->t0, g->y, (size_t)g->n * es, hipMemcpyDeviceToDevice, st));
+        GPX_TRY(trsv_lower(g->dtype, g->A, g->n, g->lda, g->t0, g->t1, 0, st, nullptr, &g->ops));
+        GPX_TRY(trsv_lower(g->dtype, g->A, g->n, g->lda, g->t1, g->alpha, 1, st, nullptr, &g->ops));
+    }
+    GPX_HIP(hipEventRecord(g->ev[3], st));
+    // logdet (replaces slogdet(K), gp_c.pyx:21) and y^T alpha (gp_c.pyx:26)
+    GPX_TRY(logdet_chol(g->dtype, g->A, g->n, g->lda, &g->scal->logdet, st));
+    GPX_TRY(dot(g->dtype, g->y, g->alpha, g->n, &g->scal->yta, st));
+    GPX_HIP(hipEventRecord(g->ev[4], st));
+    g->fitted = true;
+    if (info) {
+        GPX_HIP(hipMemcpyAsync(info, &g->scal->info, sizeof(int), hipMemcpyDeviceToHost, st));
+        GPX_HIP(hipStreamSynchronize(st));
+        GPX_TRY(check_internal_info(*info));
+    }
+    return GPX_OK;
 }
 
 // flag[0] |= 1 when v holds a NaN or an infinity (scipy's asarray_chkfinite on the device, O(n))
@@ -120,7 +171,7 @@ __global__ void nonfinite_kernel(const T *__restrict__ v, int64_t n, int *__rest
 // x_finite / y_finite of the handle from its device arrays (synchronous)
 int gp_scan_finite(gpx_gp *g)
 {
-    int *flags = (int *)(g->scal + 2);                    // two spare words of the scalar block
+    int *flags = &g->scal->x_bad;                          // x_bad, y_bad
     GPX_HIP(hipMemsetAsync(flags, 0, 2 * sizeof(int), g->st));
     const int64_t nx = g->n * g->d, ny = g->n;
     const unsigned bx = (unsigned)std::min<int64_t>(cdiv(nx, 256), 1024), by = (unsigned)std::min<int64_t>(cdiv(ny, 256), 1024);
@@ -198,6 +249,29 @@ int var_plan(int dtype, int64_t n, int64_t m, int64_t chunk_rows, size_t free_by
     return GPX_OK;
 }
 
+// The row chunks of one call and their buffer: gpx_gp_var / var_from_K / var_grad over the test points, the leave-one-out
+// sweep over the rows of the identity.  init refuses a bad chunk_rows in the caller's name (`who`), then -- m = 0: nothing to
+// do, nothing allocated -- sizes the chunks from the free device memory (var_plan) and allocates X, rows x lda in g's dtype.
+struct RowChunks {
+    int64_t m = 0, rows = 0, chunks = 0;
+    DevBuf X;
+    int init(gpx_gp *g, int64_t m_, int64_t chunk_rows, const char *who)
+    {
+        if (chunk_rows < 0 || chunk_rows % VAR_CHUNK_ALIGN != 0) {
+            set_error("%s: chunk_rows must be 0 (automatic) or a multiple of 128", who);
+            return GPX_ERR_ARG;
+        }
+        m = m_;
+        if (m == 0) return GPX_OK;
+        size_t freeb = 0, totalb = 0;
+        GPX_HIP(hipMemGetInfo(&freeb, &totalb));
+        GPX_TRY(var_plan(g->dtype, g->n, m, chunk_rows, freeb, &rows, &chunks, nullptr));
+        return X.alloc((size_t)rows * g->lda * esize(g->dtype));
+    }
+    int64_t r0(int64_t c) const { return c * rows; }                        // first row of chunk c
+    int64_t rc(int64_t c) const { return std::min(rows, m - c * rows); }    // ... and how many it has
+};
+
 static const char *NONFINITE_MSG = "array must not contain infs or NaNs";      // scipy's text (gp/gp.py:294, 332-334)
 
 #define GP_NEED_FINITE_Y(g)                                                    \
@@ -271,9 +345,9 @@ int gpx_gp_set_data(gpx_gp_t *g, const double *x, const double *y)
 {
     GP_ENTER(g);
     GPX_ARG(g && x && y, "NULL argument");
-    GPX_TRY(upload_f64(g->dtype, g->x, x, g->n * g->d, g->st));
-    GPX_TRY(upload_f64(g->dtype, g->y, y, g->n, g->st));
-    g->have_data = true; g->fitted = false; g->have_kii = false;
+    GPX_TRY(upload_f64(g->dtype, g->x, g->n * g->d, x, g->n * g->d, 1, g->n * g->d, g->st));
+    GPX_TRY(upload_f64(g->dtype, g->y, g->n, y, g->n, 1, g->n, g->st));
+    g->have_data = true; gp_unfit(g);
     GPX_TRY(gp_rescale(g));
     return gp_scan_finite(g);
 }
@@ -286,7 +360,7 @@ int gpx_gp_set_data_device(gpx_gp_t *g, const void *x_dev, const void *y_dev)
     GPX_HIP(hipMemcpyAsync(g->x, x_dev, (size_t)g->n * g->d * es, hipMemcpyDeviceToDevice, g->st));
     GPX_HIP(hipMemcpyAsync(g->y, y_dev, (size_t)g->n * es, hipMemcpyDeviceToDevice, g->st));
     GPX_HIP(hipStreamSynchronize(g->st));      // the caller may free or overwrite the sources on return
-    g->have_data = true; g->fitted = false; g->have_kii = false;
+    g->have_data = true; gp_unfit(g);
     GPX_TRY(gp_rescale(g));
     return gp_scan_finite(g);
 }
@@ -298,7 +372,7 @@ int gpx_gp_set_params(gpx_gp_t *g, const double *params, double s)
     GPX_ARG(!(s < 0), "invalid value for s");                  // gp/gp.py:192-193 (`val < 0`: a NaN passes, as in the reference; gpx_gp_fit then rejects it as non-finite)
     for (int i = 0; i < g->nparams; ++i) g->params[i] = params[i];
     g->s = s;
-    g->have_params = true; g->fitted = false; g->have_K = false; g->have_kii = false;
+    g->have_params = true; g->have_K = false; gp_unfit(g);
     return gp_rescale(g);
 }
 
@@ -316,23 +390,8 @@ int gpx_gp_set_K(gpx_gp_t *g, const double *Kxx, int64_t ld)
 {
     GP_ENTER(g);
     GPX_ARG(g && Kxx && ld >= g->n, "bad arguments");
-    const int64_t n = g->n;
-    if (g->dtype == GPX_F64) {
-        GPX_HIP(hipMemcpy2DAsync(g->A, (size_t)g->lda * 8, Kxx, (size_t)ld * 8, (size_t)n * 8, (size_t)n,
-                                 hipMemcpyHostToDevice, g->st));
-        GPX_HIP(hipStreamSynchronize(g->st));
-    } else {
-        // stage as f64, convert row by row into the padded f32 matrix
-        DevBuf tmp;
-        GPX_TRY(tmp.alloc((size_t)n * n * 8));
-        GPX_HIP(hipMemcpy2DAsync(tmp.p, (size_t)n * 8, Kxx, (size_t)ld * 8, (size_t)n * 8, (size_t)n,
-                                 hipMemcpyHostToDevice, g->st));
-        for (int64_t r = 0; r < n; ++r)
-            hipLaunchKernelGGL((cvt_from_f64<float>), dim3((unsigned)cdiv(n, 256)), dim3(256), 0, g->st,
-                               (const double *)tmp.p + r * n, (float *)g->A + r * g->lda, n);
-        GPX_HIP(hipStreamSynchronize(g->st));
-    }
-    g->have_K = true; g->fitted = false; g->have_kii = false;
+    GPX_TRY(upload_f64(g->dtype, g->A, g->lda, Kxx, ld, g->n, g->n, g->st));
+    g->have_K = true; gp_unfit(g);
     return GPX_OK;
 }
 
@@ -366,7 +425,6 @@ int gpx_gp_fit(gpx_gp_t *g, int *info)
         return GPX_ERR_ARG;
     }
     const size_t es = esize(g->dtype);
-    int *info_dev = (int *)(g->scal + 3);
     hipStream_t st = g->st;
     GPX_HIP(hipEventRecord(g->ev[0], st));
     // Kxx = K(x, x) + s^2 I, lower triangle only (gp/gp.py:263-266)
@@ -383,8 +441,7 @@ int gpx_gp_fit(gpx_gp_t *g, int *info)
     const int64_t ride_max = tune().fit_ride_max;
     const bool ride = g->n <= ride_max;
     route_hit(ride ? RT_FIT_RIDE : RT_FIT_TWO_SOLVES);
-    char *row_n = (char *)g->A + (size_t)g->n * g->lda * es;
-    if (ride) GPX_HIP(hipMemcpyAsync(row_n, g->y, (size_t)g->n * es, hipMemcpyDeviceToDevice, st));
+    if (ride) GPX_HIP(hipMemcpyAsync((char *)g->A + (size_t)g->n * g->lda * es, g->y, (size_t)g->n * es, hipMemcpyDeviceToDevice, st));
     g->ops.invalidate();                                  // a new factor: its block operators are rebuilt once
     const bool ahead = tune().fit_ops_ahead != 0 && g->n >= tune().fit_ops_ahead_min &&
                        trsv_ops_ahead_ok(g->dtype, g->A, g->n, g->lda);
@@ -407,7 +464,7 @@ int gpx_gp_fit(gpx_gp_t *g, int *info)
         // (the operator buffer may still be read by solves of the factor before this one, queued on st)
         GPX_TRY(order(g->ev_ops, st, g->st_ops));
     }
-    GPX_TRY(potrf(g->dtype, g->A, g->n, g->lda, info_dev, st, nullptr, ride ? 1 : 0, /*may_block=*/true, ahead ? &hook : nullptr));
+    GPX_TRY(potrf(g->dtype, g->A, g->n, g->lda, &g->scal->info, st, nullptr, ride ? 1 : 0, /*may_block=*/true, ahead ? &hook : nullptr));
     if (ahead) {
         // the solves wait for the operator stream.  The backward sweep takes the blocks that have no operators yet by
         // steps; a forward sweep (n > ride_max) and every later solve of this factor complete the set first (trsv_lower)
@@ -415,41 +472,18 @@ int gpx_gp_fit(gpx_gp_t *g, int *info)
         if (g->ops.built > 0) route_hit(RT_FIT_OPS_AHEAD);
     }
     GPX_HIP(hipEventRecord(g->ev[2], st));
-    // inv_Kxx_y = cho_solve((L, True), y) (gp/gp.py:332-334)
-    if (ride) {
-        GPX_TRY(trsv_lower(g->dtype, g->A, g->n, g->lda, row_n, g->alpha, 1, st, nullptr, &g->ops));
-    } else {
-        GPX_HIP(hipMemcpyAsync(g->t0, g->y, (size_t)g->n * es, hipMemcpyDeviceToDevice, st));
-        GPX_TRY(trsv_lower(g->dtype, g->A, g->n, g->lda, g->t0, g->t1, 0, st, nullptr, &g->ops));
-        GPX_TRY(trsv_lower(g->dtype, g->A, g->n, g->lda, g->t1, g->alpha, 1, st, nullptr, &g->ops));
-    }
-    GPX_HIP(hipEventRecord(g->ev[3], st));
-    // logdet (replaces slogdet(K), gp_c.pyx:21) and y^T alpha (gp_c.pyx:26)
-    GPX_TRY(logdet_chol(g->dtype, g->A, g->n, g->lda, g->scal + 0, st));
-    GPX_TRY(dot(g->dtype, g->y, g->alpha, g->n, g->scal + 1, st));
-    GPX_HIP(hipEventRecord(g->ev[4], st));
-    g->fitted = true;
-    if (info) {
-        GPX_HIP(hipMemcpyAsync(info, info_dev, sizeof(int), hipMemcpyDeviceToHost, st));
-        GPX_HIP(hipStreamSynchronize(st));
-        GPX_TRY(check_internal_info(*info));
-    }
-    return GPX_OK;
+    return gp_finish_fit(g, ride, info);
 }
 
 static int gp_scalars(gpx_gp_t *g, double *logdet, double *yta, int *info)
 {
     GP_ENTER(g);
     GPX_ARG(g && g->fitted, "gp is not fitted");
-    double h[4];
-    GPX_HIP(hipMemcpyAsync(h, g->scal, sizeof(h), hipMemcpyDeviceToHost, g->st));
-    GPX_HIP(hipStreamSynchronize(g->st));
-    int inf;
-    memcpy(&inf, &h[3], sizeof(int));
-    GPX_TRY(check_internal_info(inf));
-    if (logdet) *logdet = h[0];
-    if (yta) *yta = h[1];
-    if (info) *info = inf;
+    GpScal sc;
+    GPX_TRY(gp_read_scal(g, &sc));
+    if (logdet) *logdet = sc.logdet;
+    if (yta) *yta = sc.yta;
+    if (info) *info = sc.info;
     return GPX_OK;
 }
 
@@ -496,7 +530,7 @@ int gpx_gp_mean(gpx_gp_t *g, const double *xo, int64_t m, double *out)
     const GpView v = gp_view(g);
     GPX_TRY(gpx_d_mean(g->dtype, v.kernel, dxo.p, m, v.x, g->n, g->d, v.params, g->alpha, dout.p,
                        (void *)g->st));
-    return download_f64(g->dtype, out, 1, dout.p, 1, m, 1, 0, g->st);
+    return download_f64(g->dtype, out, m, dout.p, m, 1, m, 0, g->st);
 }
 
 int gpx_gp_cov(gpx_gp_t *g, const double *xo, int64_t m, double *out)
@@ -536,15 +570,9 @@ int gpx_gp_mean_from_K(gpx_gp_t *g, const double *Kxox, int64_t m, double *out)
     GPX_TRY(X.alloc((size_t)m * ldx * es));
     GPX_TRY(o.alloc((size_t)m * es));
     GPX_HIP(hipMemsetAsync(o.p, 0, (size_t)m * es, g->st));
-    if (g->dtype == GPX_F64) {
-        GPX_HIP(hipMemcpy2DAsync(X.p, (size_t)ldx * 8, Kxox, (size_t)n * 8, (size_t)n * 8, (size_t)m,
-                                 hipMemcpyHostToDevice, g->st));
-    } else {
-        for (int64_t r = 0; r < m; ++r)
-            GPX_TRY(upload_f64(g->dtype, (float *)X.p + r * ldx, Kxox + r * n, n, g->st));
-    }
+    GPX_TRY(upload_f64(g->dtype, X.p, ldx, Kxox, n, m, n, g->st));
     GPX_TRY(gemm_nt(g->dtype, m, 1, n, X.p, ldx, g->alpha, ldx, o.p, 1, 1.0, GPX_FULL, 0, 0, g->st));
-    return download_f64(g->dtype, out, 1, o.p, 1, m, 1, 0, g->st);
+    return download_f64(g->dtype, out, m, o.p, m, 1, m, 0, g->st);
 }
 
 int gpx_gp_cov_from_K(gpx_gp_t *g, const double *Kxox, const double *Kxoxo, int64_t m, double *out)
@@ -558,17 +586,8 @@ int gpx_gp_cov_from_K(gpx_gp_t *g, const double *Kxox, const double *Kxoxo, int6
     DevBuf X, C;
     GPX_TRY(X.alloc((size_t)m * ldx * es));
     GPX_TRY(C.alloc((size_t)m * ldc * es));
-    if (g->dtype == GPX_F64) {
-        GPX_HIP(hipMemcpy2DAsync(X.p, (size_t)ldx * 8, Kxox, (size_t)n * 8, (size_t)n * 8, (size_t)m,
-                                 hipMemcpyHostToDevice, g->st));
-        GPX_HIP(hipMemcpy2DAsync(C.p, (size_t)ldc * 8, Kxoxo, (size_t)m * 8, (size_t)m * 8, (size_t)m,
-                                 hipMemcpyHostToDevice, g->st));
-    } else {
-        for (int64_t r = 0; r < m; ++r) {
-            GPX_TRY(upload_f64(g->dtype, (float *)X.p + r * ldx, Kxox + r * n, n, g->st));
-            GPX_TRY(upload_f64(g->dtype, (float *)C.p + r * ldc, Kxoxo + r * m, m, g->st));
-        }
-    }
+    GPX_TRY(upload_f64(g->dtype, X.p, ldx, Kxox, n, m, n, g->st));
+    GPX_TRY(upload_f64(g->dtype, C.p, ldc, Kxoxo, m, m, m, g->st));
     GPX_TRY(trsm_right_lt(g->dtype, g->A, n, g->lda, X.p, m, ldx, g->st, 0, &g->ops));
     GPX_TRY(gemm_nt(g->dtype, m, m, n, X.p, ldx, X.p, ldx, C.p, ldc, -1.0, GPX_FULL, 0, 0, g->st));
     return download_f64(g->dtype, out, m, C.p, ldc, m, m, 0, g->st);
@@ -577,41 +596,30 @@ int gpx_gp_cov_from_K(gpx_gp_t *g, const double *Kxox, const double *Kxoxo, int6
 // Predictive variance, diag of RW06 eq. 2.24, in row chunks: X = K(xo_c, x) (or the caller's rows of Kxox), X <- X L^-T
 // where gpx_gp_cov runs it (the same operators), out_c = kdiag_c - rowsumsq(X).  One chunk buffer, one double[m] of results,
 // one download; nothing m x m exists anywhere.  Kxox != NULL: the plugin form (kdiag is then the caller's too).
-static int gp_var_impl(gpx_gp *g, const double *xo, const double *Kxox, const double *kdiag, int64_t m, int64_t chunk_rows, double *out)
+static int gp_var_impl(gpx_gp *g, const double *xo, const double *Kxox, const double *kdiag, const RowChunks &ch, double *out)
 {
     const size_t es = esize(g->dtype);
-    const int64_t n = g->n, ldx = g->lda;
-    size_t freeb = 0, totalb = 0;
-    GPX_HIP(hipMemGetInfo(&freeb, &totalb));
-    int64_t rows = 0, chunks = 0;
-    GPX_TRY(var_plan(g->dtype, n, m, chunk_rows, freeb, &rows, &chunks, nullptr));
-    DevBuf dxo, X, dvar, dk, stage;
-    GPX_TRY(X.alloc((size_t)rows * ldx * es));
+    const int64_t n = g->n, ldx = g->lda, m = ch.m;
+    const DevBuf &X = ch.X;
+    DevBuf dxo, dvar, dk, stage;                           // stage: upload_f64's, one for all chunks
     GPX_TRY(dvar.alloc((size_t)m * sizeof(double)));
     if (Kxox) {
         GPX_TRY(dk.alloc((size_t)m * sizeof(double)));
         GPX_HIP(hipMemcpyAsync(dk.p, kdiag, (size_t)m * sizeof(double), hipMemcpyHostToDevice, g->st));
-        if (g->dtype == GPX_F32) GPX_TRY(stage.alloc((size_t)rows * n * sizeof(double)));
     } else {
         GPX_TRY(dxo.alloc((size_t)m * g->d * es));
         GPX_TRY(upload_points(g, dxo.p, xo, m));
     }
     const GpView v = gp_view(g);
-    for (int64_t c = 0; c < chunks; ++c) {
-        const int64_t r0 = c * rows, rc = std::min(rows, m - r0);
+    for (int64_t c = 0; c < ch.chunks; ++c) {
+        const int64_t r0 = ch.r0(c), rc = ch.rc(c);
         route_hit(RT_VAR_CHUNK);
         const void *xo_c = nullptr;
         if (!Kxox) {
             xo_c = (const char *)dxo.p + (size_t)r0 * g->d * es;
             GPX_TRY(kmat(g->dtype, v.kernel, GPX_K, xo_c, rc, v.x, n, g->d, v.params, 0.0, GPX_FULL, X.p, ldx, g->st));
-        } else if (g->dtype == GPX_F64) {
-            GPX_HIP(hipMemcpy2DAsync(X.p, (size_t)ldx * 8, Kxox + r0 * n, (size_t)n * 8, (size_t)n * 8, (size_t)rc, hipMemcpyHostToDevice, g->st));
         } else {
-            GPX_HIP(hipMemcpyAsync(stage.p, Kxox + r0 * n, (size_t)rc * n * 8, hipMemcpyHostToDevice, g->st));
-            for (int64_t r = 0; r < rc; ++r)
-                hipLaunchKernelGGL((cvt_from_f64<float>), dim3((unsigned)cdiv(n, 256)), dim3(256), 0, g->st,
-                                   (const double *)stage.p + r * n, (float *)X.p + r * ldx, n);
-            GPX_LAUNCH_CHECK();
+            GPX_TRY(upload_f64(g->dtype, X.p, ldx, Kxox + r0 * n, n, rc, n, g->st, &stage));
         }
         GPX_TRY(trsm_right_lt(g->dtype, g->A, n, g->lda, X.p, rc, ldx, g->st, 0, &g->ops));
         GPX_TRY(var_rows(g->dtype, v.kernel, X.p, rc, n, ldx, xo_c, g->d, v.params, Kxox ? (const double *)dk.p + r0 : nullptr, 0,
@@ -627,9 +635,10 @@ int gpx_gp_var(gpx_gp_t *g, const double *xo, int64_t m, int64_t chunk_rows, dou
     GP_ENTER(g);
     GPX_ARG(g && g->fitted, "gp is not fitted");
     GPX_ARG(m >= 0 && (m == 0 || (xo && out)), "bad arguments");
-    GPX_ARG(chunk_rows >= 0 && chunk_rows % VAR_CHUNK_ALIGN == 0, "chunk_rows must be 0 (automatic) or a multiple of 128");
+    RowChunks ch;
+    GPX_TRY(ch.init(g, m, chunk_rows, __func__));
     if (m == 0) return GPX_OK;
-    return gp_var_impl(g, xo, nullptr, nullptr, m, chunk_rows, out);
+    return gp_var_impl(g, xo, nullptr, nullptr, ch, out);
 }
 
 int gpx_gp_var_from_K(gpx_gp_t *g, const double *Kxox, const double *kdiag, int64_t m, int64_t chunk_rows, double *out)
@@ -637,9 +646,10 @@ int gpx_gp_var_from_K(gpx_gp_t *g, const double *Kxox, const double *kdiag, int6
     GP_ENTER(g);
     GPX_ARG(g && g->fitted, "gp is not fitted");
     GPX_ARG(m >= 0 && (m == 0 || (Kxox && kdiag && out)), "bad arguments");
-    GPX_ARG(chunk_rows >= 0 && chunk_rows % VAR_CHUNK_ALIGN == 0, "chunk_rows must be 0 (automatic) or a multiple of 128");
+    RowChunks ch;
+    GPX_TRY(ch.init(g, m, chunk_rows, __func__));
     if (m == 0) return GPX_OK;
-    return gp_var_impl(g, nullptr, Kxox, kdiag, m, chunk_rows, out);
+    return gp_var_impl(g, nullptr, Kxox, kdiag, ch, out);
 }
 
 // Input-space gradients of the prediction.  The mean's is one fused pass with w = alpha.  The variance's,
@@ -673,23 +683,20 @@ int gpx_gp_var_grad(gpx_gp_t *g, const double *xo, int64_t m, int64_t chunk_rows
     GP_ENTER(g);
     GPX_ARG(g && g->fitted, "gp is not fitted");
     GPX_ARG(m >= 0 && (m == 0 || (xo && grad)), "bad arguments");
-    GPX_ARG(chunk_rows >= 0 && chunk_rows % VAR_CHUNK_ALIGN == 0, "chunk_rows must be 0 (automatic) or a multiple of 128");
+    RowChunks ch;
+    GPX_TRY(ch.init(g, m, chunk_rows, __func__));
     if (m == 0) return GPX_OK;
     const size_t es = esize(g->dtype);
     const int64_t n = g->n, ldx = g->lda, d = g->d;
-    size_t freeb = 0, totalb = 0;
-    GPX_HIP(hipMemGetInfo(&freeb, &totalb));
-    int64_t rows = 0, chunks = 0;
-    GPX_TRY(var_plan(g->dtype, n, m, chunk_rows, freeb, &rows, &chunks, nullptr));
-    DevBuf dxo, X, dout;                                   // dout: grad (m, d) | var (m)
-    GPX_TRY(X.alloc((size_t)rows * ldx * es));
+    const DevBuf &X = ch.X;
+    DevBuf dxo, dout;                                      // dout: grad (m, d) | var (m)
     GPX_TRY(dout.alloc((size_t)m * (d + 1) * sizeof(double)));
     GPX_TRY(dxo.alloc((size_t)m * d * es));
     GPX_TRY(upload_points(g, dxo.p, xo, m));
     double *dgrad = (double *)dout.p, *dvar = dgrad + m * d;
     const GpView v = gp_view(g);
-    for (int64_t c = 0; c < chunks; ++c) {
-        const int64_t r0 = c * rows, rc = std::min(rows, m - r0);
+    for (int64_t c = 0; c < ch.chunks; ++c) {
+        const int64_t r0 = ch.r0(c), rc = ch.rc(c);
         route_hit(RT_GRAD_CHUNK);
         const void *xo_c = (const char *)dxo.p + (size_t)r0 * d * es;
         GPX_TRY(kmat(g->dtype, v.kernel, GPX_K, xo_c, rc, v.x, n, g->d, v.params, 0.0, GPX_FULL, X.p, ldx, g->st));
@@ -710,19 +717,14 @@ int gpx_gp_var_grad(gpx_gp_t *g, const double *xo, int64_t m, int64_t chunk_rows
 // L^-1 e_i is zero above row i -- then the row sums of squares (loo_rows).  n^3 / 3 flops, one chunk buffer, nothing n x n.
 // The diagonal stays in the handle (g->kii) until the factor changes.  mean / var / logp (device, n doubles each; all or
 // none): the per-point quantities are written by the same pass.
-static int gp_loo_sweep(gpx_gp *g, int64_t chunk_rows, double *mean, double *var, double *logp)
+static int gp_loo_sweep(gpx_gp *g, const RowChunks &ch, double *mean, double *var, double *logp)
 {
     const size_t es = esize(g->dtype);
     const int64_t n = g->n, ldx = g->lda;
-    size_t freeb = 0, totalb = 0;
-    GPX_HIP(hipMemGetInfo(&freeb, &totalb));
-    int64_t rows = 0, chunks = 0;
-    GPX_TRY(var_plan(g->dtype, n, n, chunk_rows, freeb, &rows, &chunks, nullptr));
+    const DevBuf &X = ch.X;
     if (!g->kii) GPX_TRY(dev_alloc((void **)&g->kii, (size_t)n * sizeof(double), "hipMalloc kii"));
-    DevBuf X;
-    GPX_TRY(X.alloc((size_t)rows * ldx * es));
-    for (int64_t c = 0; c < chunks; ++c) {
-        const int64_t c0 = c * rows, rc = std::min(rows, n - c0);
+    for (int64_t c = 0; c < ch.chunks; ++c) {
+        const int64_t c0 = ch.r0(c), rc = ch.rc(c);
         route_hit(RT_LOO_CHUNK);
         GPX_TRY(eye_rows(g->dtype, X.p, rc, ldx, c0, c0 / TRSV_OPS_BLOCK * TRSV_OPS_BLOCK, g->st));
         GPX_TRY(trsm_right_lt(g->dtype, g->A, n, g->lda, X.p, rc, ldx, g->st, 1, &g->ops, c0));
@@ -734,27 +736,17 @@ static int gp_loo_sweep(gpx_gp *g, int64_t chunk_rows, double *mean, double *var
     return GPX_OK;
 }
 
-// what gpx_gp_inv_diag and gpx_gp_loo ask of the handle beyond "fitted": a factor that exists
-static int gp_need_factor(gpx_gp *g)
-{
-    double h4[4];
-    GPX_HIP(hipMemcpyAsync(h4, g->scal, sizeof(h4), hipMemcpyDeviceToHost, g->st));
-    GPX_HIP(hipStreamSynchronize(g->st));
-    int info;
-    memcpy(&info, &h4[3], sizeof(int));
-    GPX_TRY(check_internal_info(info));
-    if (info != 0) { set_error("Kxx is not positive definite (info = %d): there is no factor to take diag(K^-1) from", info); return GPX_ERR_ARG; }
-    return GPX_OK;
-}
-
+// (both entry points: the sweep has no chunks when the diagonal is already in the handle, and a bad chunk_rows is refused
+// before the factor is asked for)
 int gpx_gp_inv_diag(gpx_gp_t *g, int64_t chunk_rows, double *out)
 {
     GP_ENTER(g);
     GPX_ARG(g->fitted, "gp is not fitted");
     GPX_ARG(out, "out is NULL");
-    GPX_ARG(chunk_rows >= 0 && chunk_rows % VAR_CHUNK_ALIGN == 0, "chunk_rows must be 0 (automatic) or a multiple of 128");
-    GPX_TRY(gp_need_factor(g));
-    if (!g->have_kii) GPX_TRY(gp_loo_sweep(g, chunk_rows, nullptr, nullptr, nullptr));
+    RowChunks ch;
+    GPX_TRY(ch.init(g, g->have_kii ? 0 : g->n, chunk_rows, __func__));
+    GPX_TRY(gp_need_factor(g, "to take diag(K^-1) from"));
+    if (!g->have_kii) GPX_TRY(gp_loo_sweep(g, ch, nullptr, nullptr, nullptr));
     GPX_HIP(hipMemcpyAsync(out, g->kii, (size_t)g->n * sizeof(double), hipMemcpyDeviceToHost, g->st));
     GPX_HIP(hipStreamSynchronize(g->st));
     return GPX_OK;
@@ -765,17 +757,18 @@ int gpx_gp_loo(gpx_gp_t *g, int64_t chunk_rows, double *mean, double *var, doubl
     GP_ENTER(g);
     GPX_ARG(g->fitted, "gp is not fitted");
     GP_NEED_FINITE_Y(g);
-    GPX_ARG(chunk_rows >= 0 && chunk_rows % VAR_CHUNK_ALIGN == 0, "chunk_rows must be 0 (automatic) or a multiple of 128");
-    GPX_TRY(gp_need_factor(g));
+    RowChunks ch;
+    GPX_TRY(ch.init(g, g->have_kii ? 0 : g->n, chunk_rows, __func__));
+    GPX_TRY(gp_need_factor(g, "to take diag(K^-1) from"));
     const int64_t n = g->n;
     if (!mean && !var && !log_p && !log_p_sum) {           // nothing asked for: the diagonal, for the calls to come
-        if (!g->have_kii) GPX_TRY(gp_loo_sweep(g, chunk_rows, nullptr, nullptr, nullptr));
+        if (!g->have_kii) GPX_TRY(gp_loo_sweep(g, ch, nullptr, nullptr, nullptr));
         return GPX_OK;
     }
     DevBuf o;                                              // mean | var | logp | sum of logp
     GPX_TRY(o.alloc((size_t)(3 * n + 1) * sizeof(double)));
     double *dm = (double *)o.p, *dv = dm + n, *dl = dv + n, *ds = dl + n;
-    if (!g->have_kii) GPX_TRY(gp_loo_sweep(g, chunk_rows, dm, dv, dl));
+    if (!g->have_kii) GPX_TRY(gp_loo_sweep(g, ch, dm, dv, dl));
     else GPX_TRY(loo_points(g->dtype, g->kii, g->y, g->alpha, n, dm, dv, dl, g->st));
     GPX_TRY(sum_f64(dl, n, ds, g->st));                    // one workgroup, fixed order: not a host sum
     if (mean) GPX_HIP(hipMemcpyAsync(mean, dm, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, g->st));
@@ -817,7 +810,7 @@ int gpx_gp_get_alpha(gpx_gp_t *g, double *out)
     GP_ENTER(g);
     GPX_ARG(g && g->fitted && out, "bad arguments");
     GP_NEED_FINITE_Y(g);                                  // cho_solve(..., check_finite=True), gp/gp.py:332-334
-    return download_f64(g->dtype, out, 1, g->alpha, 1, g->n, 1, 0, g->st);
+    return download_f64(g->dtype, out, g->n, g->alpha, g->n, 1, g->n, 0, g->st);
 }
 
 int gpx_gp_get_inv_Kxx(gpx_gp_t *g, double *out, int64_t ld)
@@ -887,13 +880,9 @@ int gpx_gp_dloglh_dtheta(gpx_gp_t *g, double *out)
     GP_NEED_FINITE_Y(g);
     const size_t es = esize(g->dtype);
     const int64_t n = g->n, lda = g->lda;
-    double h4[4];
-    GPX_HIP(hipMemcpyAsync(h4, g->scal, sizeof(h4), hipMemcpyDeviceToHost, g->st));
-    GPX_HIP(hipStreamSynchronize(g->st));
-    int info;
-    memcpy(&info, &h4[3], sizeof(int));
-    GPX_TRY(check_internal_info(info));
-    if (info != 0) {                                   // gp/gp.py:424-428: NaN when K is not PD
+    GpScal sc;
+    GPX_TRY(gp_read_scal(g, &sc));
+    if (sc.info != 0) {                                 // gp/gp.py:424-428: NaN when K is not PD
         for (int i = 0; i <= g->nparams; ++i) out[i] = NAN;
         return GPX_OK;
     }

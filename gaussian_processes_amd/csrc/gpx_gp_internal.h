@@ -1,6 +1,18 @@
 // gpx_gp_internal.h -- the fitted-GP handle, shared by gpx_gp.hip and gpx_deriv.hip (not part of the ABI).
 #pragma once
 #include "gpx_common.h"
+#include <cstddef>
+
+// The handle's scalars in HBM: what a fit leaves behind, and the two flags of gp_scan_finite.  32 bytes at these offsets
+// since the first version (logdet, yta, spare, info as four 8-byte slots); nothing outside this struct spells them out.
+struct GpScal {
+    double logdet;     // log det K from the factor's diagonal (logdet_chol)
+    double yta;        // y^T alpha (dot)
+    int x_bad, y_bad;  // gp_scan_finite: non-zero when x / y holds a NaN or an infinity
+    int info;          // potrf: 0, the failing pivot (1-based), or < 0 for an internal failure (check_internal_info)
+    int pad;
+};
+static_assert(sizeof(GpScal) == 32 && offsetof(GpScal, x_bad) == 16 && offsetof(GpScal, info) == 24, "GpScal layout");
 
 struct gpx_gp {
     int device;        // the HIP device the handle lives on; every entry point makes it current
@@ -8,7 +20,7 @@ struct gpx_gp {
     int64_t n, lda;
     void *x, *y, *A, *alpha, *t0, *t1;
     void *xs;          // GPX_KERNEL_GAUSSIAN_ARD only: x / w, (n, d) in the handle's dtype (gp_rescale); null otherwise
-    double *scal;      // device: [0] logdet [1] y^T alpha [2] spare ; int info at scal + 3
+    GpScal *scal;      // device
     hipStream_t st;
     hipEvent_t ev[6];
     double params[1 + GPX_ARD_MAX_D];
@@ -16,7 +28,6 @@ struct gpx_gp {
     double s;
     bool have_data, have_params, fitted, have_K;
     bool x_finite, y_finite;   // scipy's check_finite=True (gp/gp.py:294, 332-334): one O(n d) device reduction per set_data
-    float ms[5];
     // fit_batch workspace (grow-only, freed with the handle): the matrices of one chunk + their vectors
     gpx::GrowBuf bw; int64_t bw_cap;        // bw_cap: matrices per chunk the block holds
     // block operators of the triangular solves (built once per factor, reused by every later solve)
@@ -26,7 +37,7 @@ struct gpx_gp {
     gpx::GrowBuf gw; int64_t gw_cap;   // gw_cap: rows per lock-step gradient group the block holds
     gpx::TrsvOps bops;
     double *kii;          // device, n doubles from the first leave-one-out call on: diag(K^-1) of the CURRENT factor when
-    bool have_kii;        // have_kii (cleared wherever `fitted` is, and by a new fit)
+    bool have_kii;        // have_kii: cleared by a new fit, and with `fitted`, which gp_unfit alone clears
     hipStream_t st_ops;   // lazily created: where gpx_gp_fit builds `ops` while the factorisation is still running
     hipEvent_t ev_ops;
 };
@@ -34,8 +45,25 @@ struct gpx_gp {
 namespace gpx {
 // x_finite / y_finite of the handle from its device arrays (one O(n d) reduction; synchronous)
 int gp_scan_finite(gpx_gp *g);
-// upload a host f64 array into a device buffer of dtype (gpx_gp.hip); returns when `src` may be reused
-int upload_f64(int dtype, void *dst, const double *src, int64_t count, hipStream_t st);
+// The one staging pair between host float64 and device arrays of a handle's dtype (gpx_gp.hip).  A vector is rows = 1.
+// host f64 (rows x cols, lds) -> device dtype (rows x cols, ldd); returns when `src` may be reused.  fp32 goes through a
+// float64 staging copy on the device and one conversion launch: `stage`, when given, is that copy's buffer, allocated by
+// the first call and kept by the caller (a chunked caller's first chunk is its largest); fp64 is copied straight across
+int upload_f64(int dtype, void *dst, int64_t ldd, const double *src, int64_t lds, int64_t rows, int64_t cols, hipStream_t st,
+               DevBuf *stage = nullptr);
+// device dtype (rows x cols, lds) -> host f64 (rows x cols, ldh); lower_only: zeros above the diagonal
+int download_f64(int dtype, double *dst, int64_t ldh, const void *src, int64_t lds, int64_t rows, int64_t cols, int lower_only,
+                 hipStream_t st);
+// the scalar block on the host: a copy on the handle's stream, a wait for it, and GPX_ERR_INTERNAL for info < 0
+int gp_read_scal(gpx_gp *g, GpScal *host);
+// ... and for callers that need a factor that exists: GPX_ERR_ARG "... there is no factor <what_for>" when info != 0
+int gp_need_factor(gpx_gp *g, const char *what_for);
+// whatever changes the data, the parameters or the matrix: no fit any more, and no diag(K^-1) of one
+static inline void gp_unfit(gpx_gp *g) { g->fitted = false; g->have_kii = false; }
+// The tail of a fit on g->st, behind a factor in g->A: alpha (rhs_is_row_n: L^-1 y rode along as row n of A and only the
+// backward sweep is left; otherwise both sweeps from y), logdet, y^T alpha, ev[3], ev[4], fitted.  info (may be null):
+// waits for all of it and takes potrf's verdict to the host
+int gp_finish_fit(gpx_gp *g, bool rhs_is_row_n, int *info);
 // kernel parameters of a family at dimension d
 static inline int nparams_of(int kernel, int d) { return kernel == GPX_KERNEL_GAUSSIAN_ARD ? 1 + d : (kernel == GPX_KERNEL_PERIODIC ? 3 : 2); }
 // The points and the two isotropic constants this handle's launches use: its own (x, params), or for the ARD family the

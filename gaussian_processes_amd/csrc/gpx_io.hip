@@ -84,46 +84,6 @@ static int64_t io_block_rows(int64_t n, size_t es)
     return std::max<int64_t>(1, std::min<int64_t>(r, n));
 }
 
-template <typename T>
-__global__ void vec_to_f64(const T *__restrict__ src, double *__restrict__ dst, int64_t n)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) dst[i] = (double)src[i];
-}
-template <typename T>
-__global__ void vec_from_f64(const double *__restrict__ src, T *__restrict__ dst, int64_t n)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) dst[i] = (T)src[i];
-}
-
-static int vec_d2h_f64(gpx_gp *g, const void *dev, int64_t count, std::vector<double> &out)
-{
-    out.resize((size_t)count);
-    DevBuf tmp;
-    GPX_TRY(tmp.alloc((size_t)count * 8));
-    const unsigned nb = (unsigned)cdiv(count, 256);
-    if (g->dtype == GPX_F64) hipLaunchKernelGGL((vec_to_f64<double>), dim3(nb), dim3(256), 0, g->st, (const double *)dev, (double *)tmp.p, count);
-    else hipLaunchKernelGGL((vec_to_f64<float>), dim3(nb), dim3(256), 0, g->st, (const float *)dev, (double *)tmp.p, count);
-    GPX_LAUNCH_CHECK();
-    GPX_HIP(hipMemcpyAsync(out.data(), tmp.p, (size_t)count * 8, hipMemcpyDeviceToHost, g->st));
-    GPX_HIP(hipStreamSynchronize(g->st));
-    return GPX_OK;
-}
-
-static int vec_h2d_f64(gpx_gp *g, void *dev, int64_t count, const std::vector<double> &in)
-{
-    DevBuf tmp;
-    GPX_TRY(tmp.alloc((size_t)count * 8));
-    GPX_HIP(hipMemcpyAsync(tmp.p, in.data(), (size_t)count * 8, hipMemcpyHostToDevice, g->st));
-    const unsigned nb = (unsigned)cdiv(count, 256);
-    if (g->dtype == GPX_F64) hipLaunchKernelGGL((vec_from_f64<double>), dim3(nb), dim3(256), 0, g->st, (const double *)tmp.p, (double *)dev, count);
-    else hipLaunchKernelGGL((vec_from_f64<float>), dim3(nb), dim3(256), 0, g->st, (const double *)tmp.p, (float *)dev, count);
-    GPX_LAUNCH_CHECK();
-    GPX_HIP(hipStreamSynchronize(g->st));
-    return GPX_OK;
-}
-
 }  // namespace gpx
 
 using namespace gpx;
@@ -136,20 +96,19 @@ int gpx_gp_save(gpx_gp_t *g, const char *path)
     GPX_ARG(path && g->fitted, "gp is not fitted / path is NULL");
     const int64_t n = g->n, lda = g->lda;
     const size_t es = esize(g->dtype);
-    double h4[4];
-    GPX_HIP(hipMemcpyAsync(h4, g->scal, sizeof(h4), hipMemcpyDeviceToHost, g->st));
-    GPX_HIP(hipStreamSynchronize(g->st));
+    GpScal sc;
+    GPX_TRY(gp_read_scal(g, &sc));
     FactorHeader hd;
     memset(&hd, 0, sizeof(hd));
     memcpy(hd.magic, "GPXFACT1", 8);
     hd.version = 1; hd.dtype = g->dtype; hd.kernel = g->kernel; hd.d = g->d;
     hd.nparams = g->have_params ? g->nparams : 0;          // 0: fitted from an uploaded matrix (plugin kernel)
-    memcpy(&hd.info, &h4[3], sizeof(int));
+    hd.info = sc.info;
     hd.n = n; hd.block_rows = io_block_rows(n, es);
     // (ARD: h in the header, its d widths right behind it; the other families' files are what they always were)
     const bool ard = g->kernel == GPX_KERNEL_GAUSSIAN_ARD;
     for (int i = 0; i < 3; ++i) hd.params[i] = (g->have_params && !(ard && i > 0)) ? g->params[i] : 0.0;
-    hd.s = g->s; hd.logdet = h4[0]; hd.yta = h4[1];
+    hd.s = g->s; hd.logdet = sc.logdet; hd.yta = sc.yta;
     // written under a temporary name and renamed when complete: a failure never leaves a truncated checkpoint
     // under the final name
     // (a UNIQUE temporary in the target's directory so that two saves to the same path, e.g. every rank of a multi-rank
@@ -180,9 +139,15 @@ int gpx_gp_save(gpx_gp_t *g, const char *path)
     bool ok = fwrite(&hd, sizeof(hd), 1, fp.f) == 1;
     if (ard && g->have_params) ok = ok && fwrite(g->params + 1, 8, (size_t)g->d, fp.f) == (size_t)g->d;
     std::vector<double> v;
-    GPX_TRY(vec_d2h_f64(g, g->x, n * g->d, v)); ok = ok && fwrite(v.data(), 8, v.size(), fp.f) == v.size();
-    GPX_TRY(vec_d2h_f64(g, g->y, n, v));        ok = ok && fwrite(v.data(), 8, v.size(), fp.f) == v.size();
-    GPX_TRY(vec_d2h_f64(g, g->alpha, n, v));    ok = ok && fwrite(v.data(), 8, v.size(), fp.f) == v.size();
+    auto wr = [&](const void *dev, int64_t count) -> int {
+        v.resize((size_t)count);
+        GPX_TRY(download_f64(g->dtype, v.data(), count, dev, count, 1, count, 0, g->st));
+        ok = ok && fwrite(v.data(), 8, v.size(), fp.f) == v.size();
+        return GPX_OK;
+    };
+    GPX_TRY(wr(g->x, n * g->d));
+    GPX_TRY(wr(g->y, n));
+    GPX_TRY(wr(g->alpha, n));
     // the lower trapezoid of L, row block [r0, r1): columns [0, r1), packed row-major, two staging buffers
     const int64_t R = hd.block_rows;
     Pinned stage[2];
@@ -277,7 +242,7 @@ int gpx_gp_load(gpx_gp_t **out, const char *path)
     auto rd = [&](void *dev, int64_t count) -> int {
         v.resize((size_t)count);
         if (fread(v.data(), 8, v.size(), fp.f) != v.size()) { set_error("gpx_gp_load: %s is truncated", path); return GPX_ERR_ARG; }
-        return vec_h2d_f64(g, dev, count, v);
+        return upload_f64(g->dtype, dev, count, v.data(), count, 1, count, g->st);
     };
     GPX_TRY(rd(g->x, n * g->d));
     GPX_TRY(rd(g->y, n));
@@ -308,9 +273,8 @@ int gpx_gp_load(gpx_gp_t **out, const char *path)
     (void)hipStreamSynchronize(g->st);
     if (rc != GPX_OK) return rc;
     GPX_TRY(gp_scan_finite(g));
-    double h4[4] = {hd.logdet, hd.yta, 0.0, 0.0};
-    memcpy(&h4[3], &hd.info, sizeof(int));
-    GPX_HIP(hipMemcpy(g->scal, h4, sizeof(h4), hipMemcpyHostToDevice));
+    GpScal sc = {hd.logdet, hd.yta, 0, 0, hd.info, 0};   // (the flags: gp_scan_finite has them in the handle by now)
+    GPX_HIP(hipMemcpy(g->scal, &sc, sizeof(sc), hipMemcpyHostToDevice));
     if (!ard) for (int i = 0; i < 3; ++i) g->params[i] = hd.params[i];
     g->s = hd.s;
     g->have_data = true; g->have_params = hd.nparams > 0; g->fitted = true; g->have_K = false;
@@ -338,9 +302,8 @@ int gpx_gp_get_xy(gpx_gp_t *g, double *x, double *y)
 {
     GP_ENTER(g);
     GPX_ARG(g->have_data, "no data in the handle");
-    std::vector<double> v;
-    if (x) { GPX_TRY(vec_d2h_f64(g, g->x, g->n * g->d, v)); memcpy(x, v.data(), v.size() * 8); }
-    if (y) { GPX_TRY(vec_d2h_f64(g, g->y, g->n, v)); memcpy(y, v.data(), v.size() * 8); }
+    if (x) GPX_TRY(download_f64(g->dtype, x, g->n * g->d, g->x, g->n * g->d, 1, g->n * g->d, 0, g->st));
+    if (y) GPX_TRY(download_f64(g->dtype, y, g->n, g->y, g->n, 1, g->n, 0, g->st));
     return GPX_OK;
 }
 
