@@ -19,7 +19,8 @@ ERR_ARG, ERR_HIP, ERR_NO_DEVICE, ERR_NOMEM, ERR_UNSUPPORTED, ERR_INTERNAL = -1, 
 (ROUTE_TRSV_OPS, ROUTE_TRSV_STEPS, ROUTE_PANEL_RES, ROUTE_PANEL_CHAIN, ROUTE_FIT_RIDE, ROUTE_FIT_TWO_SOLVES,
  ROUTE_GEMM_FAST, ROUTE_GEMM_GENERIC, ROUTE_SYRK_EXACT, ROUTE_SYRK_PATCH, ROUTE_MG_BCAST_ONE, ROUTE_MG_BCAST_SAG,
  ROUTE_FIT_OPS_AHEAD, ROUTE_TRSM_OPS, ROUTE_POTRF_PAIR, ROUTE_VAR_CHUNK, ROUTE_LOO_CHUNK, ROUTE_TRSM_L_OPS,
- ROUTE_GRAD_CHUNK, ROUTE_EXTEND) = range(20)
+ ROUTE_GRAD_CHUNK, ROUTE_EXTEND, ROUTE_SAMPLE) = range(21)
+PROF_RANDN = 14
 F64, F32 = 0, 1
 KERNEL_GAUSSIAN, KERNEL_PERIODIC, KERNEL_GAUSSIAN_ARD = 0, 1, 2
 ARD_MAX_D = 64
@@ -106,6 +107,9 @@ _SIGNATURES = {
                                c_void_p, c_void_p, c_void_p]),
     "gpx_d_copy_lower": (c_int, [c_int, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p]),
     "gpx_d_schur_lower": (c_int, [c_int, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p]),
+    "gpx_d_randn": (c_int, [c_int, c_void_p, c_int64, c_int64, c_int64, c_uint64, c_uint64, c_uint64, c_void_p]),
+    "gpx_d_mvn_sample": (c_int, [c_int, c_void_p, c_int64, c_int64, c_void_p, c_double, c_int64, c_uint64, c_uint64, c_void_p,
+                                 c_int64, c_void_p, c_int64, c_void_p, c_void_p]),
     "gpx_gp_create": (c_int, [POINTER(c_void_p), c_int, c_int, c_int64, c_int]),
     "gpx_gp_destroy": (c_int, [c_void_p]),
     "gpx_gp_set_data": (c_int, [c_void_p, c_double_p, c_double_p]),
@@ -129,6 +133,9 @@ _SIGNATURES = {
     "gpx_gp_loo": (c_int, [c_void_p, c_int64, c_double_p, c_double_p, c_double_p, c_double_p]),
     "gpx_gp_extend": (c_int, [c_void_p, c_double_p, c_double_p, c_int64, POINTER(c_void_p), c_int_p]),
     "gpx_gp_extend_from_K": (c_int, [c_void_p, c_double_p, c_double_p, c_int64, c_double_p, c_double_p, POINTER(c_void_p),
+                                     c_int_p]),
+    "gpx_gp_sample": (c_int, [c_void_p, c_double_p, c_int64, c_int64, c_uint64, c_int, c_double, c_double_p, c_int_p]),
+    "gpx_gp_sample_from_K": (c_int, [c_void_p, c_double_p, c_double_p, c_int64, c_int64, c_uint64, c_int, c_double, c_double_p,
                                      c_int_p]),
     "gpx_debug_var_plan": (c_int, [c_int, c_int64, c_int64, c_int64, c_size_t, POINTER(c_int64), POINTER(c_int64),
                                    POINTER(c_size_t)]),

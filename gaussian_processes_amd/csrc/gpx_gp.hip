@@ -277,6 +277,47 @@ static const char *NONFINITE_MSG = "array must not contain infs or NaNs";      /
 #define GP_NEED_FINITE_Y(g)                                                    \
     do { if (!(g)->y_finite) { set_error("%s (y)", NONFINITE_MSG); return GPX_ERR_ARG; } } while (0)
 
+// The posterior covariance at m test points, left on the device:  C (m x m, ldc) = Kxoxo - V^T V,  V^T = Kxox L^-T
+// (gp/gp.py:622-625 without K^-1).  xo: the test points (built-in families), or Kxox / Kxoxo: the caller's matrices (plugin
+// kernels).  mean_dev (may be null; m elements, handle dtype): the posterior mean at the same points, as gpx_gp_mean /
+// gpx_gp_mean_from_K compute it -- from Kxox before the sweep overwrites it.  Everything is enqueued on the handle's stream.
+struct CovBlock { DevBuf dxo, X, C; int64_t ldc = 0; };
+static int gp_cov_device(gpx_gp *g, const double *xo, const double *Kxox, const double *Kxoxo, int64_t m, CovBlock *b, void *mean_dev)
+{
+    const size_t es = esize(g->dtype);
+    const int64_t n = g->n, ldx = g->lda, ldc = round_up(m, 16);
+    b->ldc = ldc;
+    if (xo) GPX_TRY(b->dxo.alloc((size_t)m * g->d * es));
+    GPX_TRY(b->X.alloc((size_t)m * ldx * es));
+    GPX_TRY(b->C.alloc((size_t)m * ldc * es));
+    if (xo) {
+        GPX_TRY(upload_points(g, b->dxo.p, xo, m));
+        const GpView v = gp_view(g);
+        if (mean_dev)
+            GPX_TRY(gpx_d_mean(g->dtype, v.kernel, b->dxo.p, m, v.x, n, g->d, v.params, g->alpha, mean_dev, (void *)g->st));
+        GPX_TRY(kmat(g->dtype, v.kernel, GPX_K, b->dxo.p, m, v.x, n, g->d, v.params, 0.0, GPX_FULL, b->X.p, ldx, g->st));
+        GPX_TRY(trsm_right_lt(g->dtype, g->A, n, g->lda, b->X.p, m, ldx, g->st, 0, &g->ops));
+        GPX_TRY(kmat(g->dtype, v.kernel, GPX_K, b->dxo.p, m, b->dxo.p, m, g->d, v.params, 0.0, GPX_FULL, b->C.p, ldc, g->st));
+    } else {
+        GPX_TRY(upload_f64(g->dtype, b->X.p, ldx, Kxox, n, m, n, g->st));
+        GPX_TRY(upload_f64(g->dtype, b->C.p, ldc, Kxoxo, m, m, m, g->st));
+        if (mean_dev) {
+            GPX_HIP(hipMemsetAsync(mean_dev, 0, (size_t)m * es, g->st));
+            GPX_TRY(gemm_nt(g->dtype, m, 1, n, b->X.p, ldx, g->alpha, ldx, mean_dev, 1, 1.0, GPX_FULL, 0, 0, g->st));
+        }
+        GPX_TRY(trsm_right_lt(g->dtype, g->A, n, g->lda, b->X.p, m, ldx, g->st, 0, &g->ops));
+    }
+    return gemm_nt(g->dtype, m, m, n, b->X.p, ldx, b->X.p, ldx, b->C.p, ldc, -1.0, GPX_FULL, 0, 0, g->st);
+}
+
+// k(0) of the handle's family from its parameters: the prior variance the automatic jitter of gpx_gp_sample scales with
+static double gp_prior_var(const gpx_gp *g)
+{
+    const GpView v = gp_view(g);
+    if (v.kernel == GPX_KERNEL_PERIODIC) return v.params[0] * v.params[0];                // periodic_c.pyx:30 at distance zero
+    return 0.5 * sqrt(2.0 / M_PI) * v.params[0] * v.params[0] / v.params[1];              // gaussian_c.pyx:28
+}
+
 }  // namespace gpx
 
 using namespace gpx;
@@ -539,22 +580,9 @@ int gpx_gp_cov(gpx_gp_t *g, const double *xo, int64_t m, double *out)
     GPX_ARG(g && g->fitted, "gp is not fitted");
     GPX_ARG(m >= 0 && (m == 0 || (xo && out)), "bad arguments");
     if (m == 0) return GPX_OK;
-    const size_t es = esize(g->dtype);
-    const int64_t ldx = g->lda, ldc = round_up(m, 16);
-    DevBuf dxo, X, C;
-    GPX_TRY(dxo.alloc((size_t)m * g->d * es));
-    GPX_TRY(X.alloc((size_t)m * ldx * es));
-    GPX_TRY(C.alloc((size_t)m * ldc * es));
-    GPX_TRY(upload_points(g, dxo.p, xo, m));
-    const GpView v = gp_view(g);
-    // X = Kxox (m x n); V^T = X L^-T; cov = Kxoxo - V^T V   (gp/gp.py:622-625 without K^-1)
-    GPX_TRY(kmat(g->dtype, v.kernel, GPX_K, dxo.p, m, v.x, g->n, g->d, v.params, 0.0, GPX_FULL, X.p,
-                 ldx, g->st));
-    GPX_TRY(trsm_right_lt(g->dtype, g->A, g->n, g->lda, X.p, m, ldx, g->st, 0, &g->ops));
-    GPX_TRY(kmat(g->dtype, v.kernel, GPX_K, dxo.p, m, dxo.p, m, g->d, v.params, 0.0, GPX_FULL, C.p,
-                 ldc, g->st));
-    GPX_TRY(gemm_nt(g->dtype, m, m, g->n, X.p, ldx, X.p, ldx, C.p, ldc, -1.0, GPX_FULL, 0, 0, g->st));
-    return download_f64(g->dtype, out, m, C.p, ldc, m, m, 0, g->st);
+    CovBlock b;
+    GPX_TRY(gp_cov_device(g, xo, nullptr, nullptr, m, &b, nullptr));
+    return download_f64(g->dtype, out, m, b.C.p, b.ldc, m, m, 0, g->st);
 }
 
 int gpx_gp_mean_from_K(gpx_gp_t *g, const double *Kxox, int64_t m, double *out)
@@ -581,16 +609,64 @@ int gpx_gp_cov_from_K(gpx_gp_t *g, const double *Kxox, const double *Kxoxo, int6
     GPX_ARG(g && g->fitted, "gp is not fitted");
     GPX_ARG(m >= 0 && (m == 0 || (Kxox && Kxoxo && out)), "bad arguments");
     if (m == 0) return GPX_OK;
+    CovBlock b;
+    GPX_TRY(gp_cov_device(g, nullptr, Kxox, Kxoxo, m, &b, nullptr));
+    return download_f64(g->dtype, out, m, b.C.p, b.ldc, m, m, 0, g->st);
+}
+
+// Joint posterior samples at m test points: the covariance block of gpx_gp_cov (the very matrix it would download), the
+// mean of gpx_gp_mean, then mvn_sample (gpx_sample.hip) with stream 0: out (S x m) = 1 mean^T + Z Lc^T,
+// Lc Lc^T = cov + (jitter [+ s^2]) I.  One download of S x m; nothing m x m leaves the device.
+static int gp_sample_impl(gpx_gp *g, const double *xo, const double *Kxox, const double *Kxoxo, int64_t m, int64_t S, uint64_t seed,
+                          int noise, double jitter, double *out, int *info)
+{
+    *info = 0;
+    GPX_TRY(gp_need_factor(g, "to sample from"));
+    route_hit(RT_SAMPLE);
+    if (m == 0 || S == 0) return GPX_OK;
     const size_t es = esize(g->dtype);
-    const int64_t n = g->n, ldx = g->lda, ldc = round_up(m, 16);
-    DevBuf X, C;
-    GPX_TRY(X.alloc((size_t)m * ldx * es));
-    GPX_TRY(C.alloc((size_t)m * ldc * es));
-    GPX_TRY(upload_f64(g->dtype, X.p, ldx, Kxox, n, m, n, g->st));
-    GPX_TRY(upload_f64(g->dtype, C.p, ldc, Kxoxo, m, m, m, g->st));
-    GPX_TRY(trsm_right_lt(g->dtype, g->A, n, g->lda, X.p, m, ldx, g->st, 0, &g->ops));
-    GPX_TRY(gemm_nt(g->dtype, m, m, n, X.p, ldx, X.p, ldx, C.p, ldc, -1.0, GPX_FULL, 0, 0, g->st));
-    return download_f64(g->dtype, out, m, C.p, ldc, m, m, 0, g->st);
+    if (jitter < 0.0) jitter = sqrt(g->dtype == GPX_F64 ? 2.220446049250313e-16 : 1.1920928955078125e-07) * gp_prior_var(g);
+    const double diag_add = jitter + (noise ? g->s * g->s : 0.0);
+    GPX_ARG(diag_add <= 1.79769313486231570e308, "jitter must be finite");          // (NaN fails it too)
+    const int64_t ldz = round_up(m, 16);
+    CovBlock b;
+    DevBuf mean, Z, smp, dinfo;
+    GPX_TRY(mean.alloc((size_t)m * es));
+    GPX_TRY(Z.alloc((size_t)S * ldz * es));
+    GPX_TRY(smp.alloc((size_t)S * ldz * es));
+    GPX_TRY(dinfo.alloc(sizeof(int)));
+    GPX_TRY(gp_cov_device(g, xo, Kxox, Kxoxo, m, &b, mean.p));
+    GPX_TRY(mvn_sample(g->dtype, b.C.p, m, b.ldc, mean.p, diag_add, S, seed, 0, Z.p, ldz, smp.p, ldz, (int *)dinfo.p, g->st));
+    int host_info = 0;
+    GPX_HIP(hipMemcpyAsync(&host_info, dinfo.p, sizeof(int), hipMemcpyDeviceToHost, g->st));
+    GPX_HIP(hipStreamSynchronize(g->st));
+    GPX_TRY(check_internal_info(host_info));
+    *info = host_info;
+    if (host_info != 0) return GPX_OK;                     // the caller's matrix, the caller's verdict: out is not written
+    return download_f64(g->dtype, out, m, smp.p, ldz, S, m, 0, g->st);
+}
+
+int gpx_gp_sample(gpx_gp_t *g, const double *xo, int64_t m, int64_t S, uint64_t seed, int noise, double jitter, double *out, int *info)
+{
+    GP_ENTER(g);
+    GPX_ARG(g->fitted && g->have_data && g->have_params, "gp is not fitted (from kernel parameters: a handle fitted from set_K samples with gpx_gp_sample_from_K)");
+    GP_NEED_FINITE_Y(g);
+    GPX_ARG(info, "info is NULL");
+    GPX_ARG(m >= 0 && S >= 0 && (m == 0 || S == 0 || (xo && out)), "bad arguments");
+    GPX_ARG(jitter == jitter, "jitter is NaN");
+    return gp_sample_impl(g, xo, nullptr, nullptr, m, S, seed, noise, jitter, out, info);
+}
+
+int gpx_gp_sample_from_K(gpx_gp_t *g, const double *Kxox, const double *Kxoxo, int64_t m, int64_t S, uint64_t seed, int noise,
+                         double jitter, double *out, int *info)
+{
+    GP_ENTER(g);
+    GPX_ARG(g->fitted, "gp is not fitted");
+    GP_NEED_FINITE_Y(g);
+    GPX_ARG(info, "info is NULL");
+    GPX_ARG(m >= 0 && S >= 0 && (m == 0 || S == 0 || (Kxox && Kxoxo && out)), "bad arguments");
+    GPX_ARG(jitter >= 0.0, "jitter must be >= 0 (the automatic value needs kernel parameters: gpx_gp_sample)");
+    return gp_sample_impl(g, nullptr, Kxox, Kxoxo, m, S, seed, noise, jitter, out, info);
 }
 
 // Predictive variance, diag of RW06 eq. 2.24, in row chunks: X = K(xo_c, x) (or the caller's rows of Kxox), X <- X L^-T

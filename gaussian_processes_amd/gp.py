@@ -699,6 +699,73 @@ class GP(object):
         obj._dev = st
         return obj
 
+    # ---- joint posterior samples (extension) ----
+    def _auto_jitter(self, xo, Kxoxo=None):
+        """``sqrt(eps_dtype) * k(0)``: the prior variance from the kernel's closed form, or -- a plugin kernel -- the largest
+        diagonal entry of the `Kxoxo` it evaluated."""
+        eps = np.finfo(np.float64 if self._dtype == _lib.F64 else np.float32).eps
+        k0 = np.max(self.K.diag(xo[:1])) if Kxoxo is None else np.max(np.diag(Kxoxo))
+        return float(np.sqrt(eps) * k0)
+
+    def sample(self, xo, size=None, seed=None, noise=False, jitter=None):
+        r"""Draws from the joint posterior of the function values at `xo`, on the device:
+        :math:`f = m(x^*) + L_c z` with :math:`L_c L_c^\top = \mathrm{cov}(x^*) + \epsilon I` and `z` standard normal --
+        the covariance is the matrix `cov(xo)` returns, factored where it was built, and only the samples come back.
+        Float64, ``(m,)`` for ``size=None`` and ``(size, m)`` for an int ``size >= 0``; ``sample(xo, seed=k)`` is
+        ``sample(xo, size=1, seed=k)[0]``.
+
+        ``seed``: an int in ``[0, 2**64)`` -- the same seed gives the same bits, on any device and for any `size` prefix
+        of rows; ``None`` takes one from numpy's global state (``np.random.randint``), so ``np.random.seed`` governs it.
+        The normal numbers are the counter-based sequence of ``gpx_d_randn`` (include/gpx.h), stream 0: row `s`, point `i`
+        is element ``s * m + i``.  ``noise=True`` adds :math:`s^2` to the diagonal: the draw is of new observations.
+        ``jitter``: :math:`\epsilon \ge 0`; ``None`` is ``sqrt(eps_dtype) * k(0)`` with `k(0)` the kernel's prior variance
+        (a plugin kernel: the largest diagonal entry of ``Kxoxo(xo)``).  A posterior covariance is singular to rounding
+        wherever `xo` comes close to the data or to itself; when the factorisation still fails, numpy.linalg.LinAlgError
+        names the pivot and the jitter -- nothing is retried with a larger one.  Memory: ``(m, n)``, ``(m, m)`` and two
+        ``(size, m)`` blocks on the device; `m` is bounded by HBM."""
+        xo, m = self._xo(xo)                         # every refusal comes before the library is touched
+        if size is None:
+            S = 1
+        else:
+            if isinstance(size, bool) or not isinstance(size, (int, np.integer)) or size < 0:
+                raise ValueError("invalid value for size: %r (None, or an int >= 0)" % (size,))
+            S = int(size)
+        if seed is None:
+            seed = int(np.random.randint(0, 2 ** 32)) << 32 | int(np.random.randint(0, 2 ** 32))
+        elif isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 2 ** 64:
+            raise ValueError("invalid value for seed: %r (None, or an int in [0, 2**64))" % (seed,))
+        seed = int(seed)
+        if jitter is not None:
+            try:
+                jitter = float(jitter)
+            except (TypeError, ValueError):
+                raise ValueError("invalid value for jitter: %r (None, or a float >= 0)" % (jitter,))
+            if not (np.isfinite(jitter) and jitter >= 0):
+                raise ValueError("invalid value for jitter: %r (None, or a finite float >= 0)" % (jitter,))
+        st = self._fit_pd()
+        lib = _lib.load()
+        out = np.empty((S, m), dtype=DTYPE)
+        info = ctypes.c_int(0)
+        if getattr(self.K, "_native_kernel", None) is not None:
+            _lib.check(lib.gpx_gp_sample(st.handle, _lib.dptr(xo), m, S, seed, int(bool(noise)), -1.0 if jitter is None else jitter,
+                                         _lib.dptr(out), ctypes.byref(info)))
+            if info.value != 0 and jitter is None:
+                jitter = self._auto_jitter(xo)
+        else:
+            # (no K() of an empty point set; and the handle of a plugin kernel was fitted from an uploaded matrix: it holds
+            # no s, so s^2 rides in the jitter)
+            Kxox = np.ascontiguousarray(self.Kxox(xo), dtype=DTYPE) if m else None
+            Kxoxo = np.ascontiguousarray(self.Kxoxo(xo), dtype=DTYPE) if m else None
+            if jitter is None:
+                jitter = self._auto_jitter(xo, Kxoxo) if m else 0.0
+            _lib.check(lib.gpx_gp_sample_from_K(st.handle, _lib.dptr(Kxox) if m else None, _lib.dptr(Kxoxo) if m else None, m, S,
+                                                seed, 0, jitter + (float(self._s) ** 2 if noise else 0.0), _lib.dptr(out),
+                                                ctypes.byref(info)))
+        if info.value != 0:
+            raise np.linalg.LinAlgError("the posterior covariance at xo plus jitter %.3e is not positive definite: pivot %d of %d "
+                                        "is not positive (pass a larger jitter)" % (jitter, info.value, m))
+        return out[0] if size is None else out
+
     # ---- growing a fitted GP (extension) ----
     def extend(self, x_new, y_new):
         r"""A new, fitted `GP` on the data of this one plus `k` further observations, without refactoring: the Cholesky

@@ -173,6 +173,7 @@ int gpx_stream_wait_event(void *stream, void *event);
 #define GPX_PROF_TRANSPOSE   11 /* transpose_kernel: the row panels of L staged for X L^-1; bytes read + written */
 #define GPX_PROF_PRED_GRAD   12 /* pred_grad_kernel + its slice reduction; kernel evaluations m*n per window of dimensions */
 #define GPX_PROF_EXTEND      13 /* copy_lower_kernel + schur_reduce_kernel (gpx_gp_extend): bytes read + written */
+#define GPX_PROF_RANDN       14 /* randn_kernel (gpx_d_randn): bytes written */
 int gpx_prof_enable(int on);    /* also clears the registry */
 int gpx_prof_read(int cls, double *launches, double *total_ms, double *total_work);
 
@@ -200,6 +201,7 @@ int gpx_prof_read(int cls, double *launches, double *total_ms, double *total_wor
 #define GPX_ROUTE_TRSM_L_OPS     17   /* X L^-1 (gpx_gp_var_grad): in-block step as one product with inv(L_kk); one hit per sweep */
 #define GPX_ROUTE_GRAD_CHUNK     18   /* input-space gradient of the variance (gpx_gp_var_grad): one hit per row chunk */
 #define GPX_ROUTE_EXTEND         19   /* gpx_gp_extend / gpx_gp_extend_from_K: one hit per call                        */
+#define GPX_ROUTE_SAMPLE         20   /* gpx_gp_sample / gpx_gp_sample_from_K: one hit per call                        */
 int gpx_debug_route_count(int route, int64_t *count);
 /* roctx ranges pushed so far (GPX_ROCTX=1: every gpx_gp_* call and every launch class below it is a nested host range for
  * `rocprofv3 --marker-trace`; libroctx64.so is loaded on first use; 0 while the switch is off) */
@@ -378,6 +380,34 @@ int gpx_d_copy_lower(int dtype, const void *src, int64_t lds, void *dst, int64_t
  * S -= B B^T on the lower tiles, accumulated by the product kernel in `dtype`.) */
 int gpx_d_schur_lower(int dtype, const void *B, int64_t k, int64_t n, int64_t ldb, void *S, int64_t lds, void *stream);
 
+/* Normal numbers, counter based.
+ * out[i, j] = z(seed, stream, offset + i * cols + j)  for i < rows, j < cols;  out: rows x cols, ld >= cols, in `dtype`.
+ * Elements in the padding [cols, ld) are not written.  GPX_PROF_RANDN (bytes written).
+ * z(seed, stream, e) is a pure function of its three arguments -- not of the grid, of ld, or of how a caller splits a matrix
+ * into calls (two calls that split a matrix by rows, the second with offset = rows_1 * cols, give the bits of one call):
+ *   q = e >> 1
+ *   (w0, w1, w2, w3) = Philox4x32-10, counter (q & 0xffffffff, q >> 32, stream & 0xffffffff, stream >> 32),
+ *                      key (seed & 0xffffffff, seed >> 32); constants and rounds of Random123: multipliers 0xD2511F53 (on c0)
+ *                      and 0xCD9E8D57 (on c2), key increments 0x9E3779B9 and 0xBB67AE85 after every round, one round
+ *                      c <- (hi(M1 c2) ^ c1 ^ k0, lo(M1 c2), hi(M0 c0) ^ c3 ^ k1, lo(M0 c0))
+ *   u1 = (2 (((w0 << 32) | w1) >> 12) + 1) 2^-53, u2 likewise from (w2, w3): exact in fp64, in [2^-53, 1 - 2^-53], so
+ *        log u1 is finite and |z| <= sqrt(106 ln 2) = 8.572
+ *   r = sqrt(-2 ln u1);  even e: r cos(2 pi u2), odd e: r sin(2 pi u2)   (sincospi(2 u2): the angle is never rounded)
+ * computed in fp64 for both dtypes and rounded once to `dtype`.  One thread per Philox call; the two elements of a pair may
+ * lie in different rows (odd cols), and the first or last element of a call may be half a pair (odd offset). */
+int gpx_d_randn(int dtype, void *out, int64_t rows, int64_t cols, int64_t ld,
+                uint64_t seed, uint64_t stream, uint64_t offset, void *hipstream);
+
+/* out (S x m, ldo) = 1 mean^T + Z Lc^T  with  Lc Lc^T = C + jitter I  and  Z = randn(S x m; seed, stream, offset 0).
+ * C: m x m, ldc, lower triangle read, DESTROYED (on return it holds Lc with a zero upper triangle).  mean: (m,) or NULL (zero).
+ * Z: S x ldz work block.  info_dev as gpx_d_potrf; when it is non-zero, out is unspecified.  A pure enqueue.
+ * (jitter onto the diagonal, gpx_d_potrf, gpx_d_tril, gpx_d_randn into Z, mean into every row of out, then one
+ * gpx_d_gemm_nt: out[s, i] += sum_k Z[s, k] Lc[i, k].  C as gpx_d_potrf wants it: 16-byte aligned, ldc a multiple of 16;
+ * jitter finite and >= 0.) */
+int gpx_d_mvn_sample(int dtype, void *C, int64_t m, int64_t ldc, const void *mean, double jitter, int64_t S,
+                     uint64_t seed, uint64_t stream, void *Z, int64_t ldz, void *out, int64_t ldo,
+                     int *info_dev, void *hipstream);
+
 /* ------------------------------------------------ fitted-GP device handle -- */
 /* One handle = one GP resident in HBM: x, y, the kernel matrix / its factor
  * (in place), alpha = K^-1 y, logdet, y^T alpha.  Mirrors the memoised
@@ -471,6 +501,25 @@ int gpx_gp_extend(gpx_gp_t *gp, const double *x_new, const double *y_new, int64_
 /* plugin kernels: the caller supplies B = K(x_new, x) (k, n) and C = K(x_new, x_new) + s^2 I (k, k; lower read), HOST float64 */
 int gpx_gp_extend_from_K(gpx_gp_t *gp, const double *x_new, const double *y_new, int64_t k,
                          const double *Knew_old, const double *Knew_new, gpx_gp_t **out, int *info);
+/* Joint posterior samples at xo (m, d) HOST float64 -> out (S, m) HOST float64: row s is one draw of the function values
+ * at the m points, mean(xo) + Lc z_s with Lc Lc^T = cov(xo) + (jitter [+ s^2]) I.  The covariance is built exactly as
+ * gpx_gp_cov builds it (the matrix that is factored is bit for bit the one it would download), the mean is gpx_gp_mean's, then
+ * gpx_d_mvn_sample with stream = 0 on the device: one download of S x m, nothing m x m leaves the device.
+ * noise != 0: s^2 is added to the diagonal -- the draw is of new OBSERVATIONS.
+ * jitter >= 0: absolute.  jitter < 0: automatic, sqrt(eps_dtype) * k(0) with k(0) the family's prior variance, from the
+ * handle's parameters on the host (h^2 / (w sqrt(2 pi)), h^2 for the periodic family, the isotropic constants for ARD).
+ * *info (HOST, may not be NULL): 0, or the 1-based failing pivot of the m x m factorisation -- the status is GPX_OK and out is
+ * not written; there is no retry with a larger jitter.  m == 0 or S == 0 is legal and writes nothing.
+ * Preconditions and statuses of gpx_gp_cov, finite y as gpx_gp_mean, GPX_ERR_ARG when the last fit was not positive definite
+ * (there is no factor), GPX_ERR_NOMEM when X (m x lda), C (m x m), Z and the samples (S x m each) do not fit: m is bounded by
+ * HBM, nothing is chunked.  GPX_ROUTE_SAMPLE: one hit per call.  gpx_gp_last_timing is untouched. */
+int gpx_gp_sample(gpx_gp_t *gp, const double *xo, int64_t m, int64_t S, uint64_t seed, int noise, double jitter,
+                  double *out /* (S, m) HOST float64 */, int *info);
+/* plugin kernels: the caller supplies Kxox (m, n) and Kxoxo (m, m), HOST float64; jitter >= 0 (no parameters to derive one
+ * from).  noise adds the s of gpx_gp_set_params: a handle fitted from gpx_gp_set_K alone has none (its caller folds s^2 into
+ * jitter). */
+int gpx_gp_sample_from_K(gpx_gp_t *gp, const double *Kxox, const double *Kxoxo, int64_t m, int64_t S, uint64_t seed,
+                         int noise, double jitter, double *out, int *info);
 /* copy-outs to HOST float64: Kxx is rebuilt (full, + s^2 I); L has zero upper */
 int gpx_gp_get_Kxx(gpx_gp_t *gp, double *out, int64_t ld);
 int gpx_gp_get_Lxx(gpx_gp_t *gp, double *out, int64_t ld);
