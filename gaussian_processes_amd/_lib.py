@@ -19,8 +19,8 @@ ERR_ARG, ERR_HIP, ERR_NO_DEVICE, ERR_NOMEM, ERR_UNSUPPORTED, ERR_INTERNAL = -1, 
 (ROUTE_TRSV_OPS, ROUTE_TRSV_STEPS, ROUTE_PANEL_RES, ROUTE_PANEL_CHAIN, ROUTE_FIT_RIDE, ROUTE_FIT_TWO_SOLVES,
  ROUTE_GEMM_FAST, ROUTE_GEMM_GENERIC, ROUTE_SYRK_EXACT, ROUTE_SYRK_PATCH, ROUTE_MG_BCAST_ONE, ROUTE_MG_BCAST_SAG,
  ROUTE_FIT_OPS_AHEAD, ROUTE_TRSM_OPS, ROUTE_POTRF_PAIR, ROUTE_VAR_CHUNK, ROUTE_LOO_CHUNK, ROUTE_TRSM_L_OPS,
- ROUTE_GRAD_CHUNK, ROUTE_EXTEND, ROUTE_SAMPLE) = range(21)
-PROF_RANDN = 14
+ ROUTE_GRAD_CHUNK, ROUTE_EXTEND, ROUTE_SAMPLE, ROUTE_KAPPLY_FUSED, ROUTE_KAPPLY_GEMM) = range(23)
+PROF_RANDN, PROF_RFF, PROF_KAPPLY = 14, 15, 16
 F64, F32 = 0, 1
 KERNEL_GAUSSIAN, KERNEL_PERIODIC, KERNEL_GAUSSIAN_ARD = 0, 1, 2
 ARD_MAX_D = 64
@@ -110,6 +110,9 @@ _SIGNATURES = {
     "gpx_d_randn": (c_int, [c_int, c_void_p, c_int64, c_int64, c_int64, c_uint64, c_uint64, c_uint64, c_void_p]),
     "gpx_d_mvn_sample": (c_int, [c_int, c_void_p, c_int64, c_int64, c_void_p, c_double, c_int64, c_uint64, c_uint64, c_void_p,
                                  c_int64, c_void_p, c_int64, c_void_p, c_void_p]),
+    "gpx_d_rff_features": (c_int, [c_int, c_void_p, c_int64, c_int, c_void_p, c_int64, c_double, c_void_p, c_int64, c_void_p]),
+    "gpx_d_kmat_apply": (c_int, [c_int, c_int, c_void_p, c_int64, c_void_p, c_int64, c_int, c_double_p, c_void_p, c_int64, c_int64,
+                                 c_void_p, c_int64, c_void_p]),
     "gpx_gp_create": (c_int, [POINTER(c_void_p), c_int, c_int, c_int64, c_int]),
     "gpx_gp_destroy": (c_int, [c_void_p]),
     "gpx_gp_set_data": (c_int, [c_void_p, c_double_p, c_double_p]),
@@ -137,6 +140,13 @@ _SIGNATURES = {
     "gpx_gp_sample": (c_int, [c_void_p, c_double_p, c_int64, c_int64, c_uint64, c_int, c_double, c_double_p, c_int_p]),
     "gpx_gp_sample_from_K": (c_int, [c_void_p, c_double_p, c_double_p, c_int64, c_int64, c_uint64, c_int, c_double, c_double_p,
                                      c_int_p]),
+    "gpx_gp_paths_create": (c_int, [c_void_p, c_int64, c_int64, c_uint64, POINTER(c_void_p)]),
+    "gpx_paths_eval": (c_int, [c_void_p, c_double_p, c_int64, c_int64, c_double_p]),
+    "gpx_paths_get": (c_int, [c_void_p, c_double_p, c_double_p, c_double_p]),
+    "gpx_paths_describe": (c_int, [c_void_p, c_int_p, c_int_p, POINTER(c_int64), c_int_p, POINTER(c_int64), POINTER(c_int64),
+                                   POINTER(c_uint64)]),
+    "gpx_debug_paths_timing": (c_int, [c_void_p, POINTER(c_float)]),
+    "gpx_paths_destroy": (c_int, [c_void_p]),
     "gpx_debug_var_plan": (c_int, [c_int, c_int64, c_int64, c_int64, c_size_t, POINTER(c_int64), POINTER(c_int64),
                                    POINTER(c_size_t)]),
     "gpx_gp_get_Kxx": (c_int, [c_void_p, c_double_p, c_int64]),
@@ -158,6 +168,7 @@ _SIGNATURES = {
     "gpx_debug_route_count": (c_int, [c_int, POINTER(c_int64)]),
     "gpx_debug_roctx_ranges": (c_int, [POINTER(c_int64)]),
     "gpx_debug_tune_refreshes": (c_int, [POINTER(c_int64)]),
+    "gpx_debug_kapply_fused_max": (c_int, [c_int64, POINTER(c_int64)]),
     "gpx_debug_leaf_selfcheck": (c_int, [c_int, POINTER(c_int)]),
     "gpx_debug_route_reset": (c_int, []),
     "gpx_debug_mg_inject_info": (c_int, [c_void_p, c_int]),
@@ -314,6 +325,15 @@ def route_count(route):
 
 def route_reset():
     check(load().gpx_debug_route_reset())
+
+
+def kapply_fused_max(value=-1):
+    """Set GPX_KAPPLY_FUSED_MAX -- the largest number of weight vectors for which `gpx_d_kmat_apply` takes its fused route --
+    for the whole process and both dtypes, and return the value that was in force (-1: the per-dtype defaults of
+    csrc/gpx_tune.h); a negative `value` restores the defaults."""
+    prev = c_int64(0)
+    check(load().gpx_debug_kapply_fused_max(int(value), ctypes.byref(prev)))
+    return prev.value
 
 
 def lapack_info_error(info):

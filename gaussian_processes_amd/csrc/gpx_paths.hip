@@ -1,0 +1,550 @@
+// gpx_paths.hip -- posterior function samples by pathwise conditioning (Matheron's rule; Wilson et al. 2020):
+//   f_s(a) = phi(a) . Theta_s + sum_j k(a, x_j) V[s, j],     V_s = alpha - Kxx^-1 (Phi(x) Theta_s + sigma E_s)
+// a random-feature draw of the prior plus an exact, data-dependent update.  Two device primitives -- the feature map
+// (gpx_d_rff_features) and the kernel matrix applied to several weight vectors at once without materialising it
+// (gpx_d_kmat_apply) -- and the handle that owns one set of paths (gpx_gp_paths_create, gpx_paths_*).  include/gpx.h has the
+// definition of every random input; tests/_paths_helpers.py restates it in numpy.
+#include "gpx_common.h"
+#include "gpx_kernels_dev.h"
+#include "gpx_gp_internal.h"
+#include <algorithm>
+
+struct gpx_paths {
+    int device, dtype, kernel, d;      // kernel: the family of the GP the paths came from
+    int64_t n, S, F, ldv, ldt;         // ldv: pitch of V (the source's lda); ldt: pitch of theta, round_up(2F, 16)
+    uint64_t seed;
+    double *omega;                     // (F, d) dense, DOUBLE for both dtypes
+    void *theta, *V, *pts;             // (S, 2F) ldt; (S, n) ldv; (n, d): the view's points (x, or x / w for ARD)
+    double iso[2];                     // the view's isotropic constants (h_v, w_v)
+    double w[GPX_ARD_MAX_D];           // ARD: the widths test points are divided by
+    double scale;                      // sqrt(k0 / F)
+    float ms[4];                       // gpx_debug_paths_timing: how long the creation took, by stage
+    gpx::GrowBuf ws;                   // gpx_paths_eval's chunk buffers (grow-only, freed with the handle): points, features, values, staging
+    hipStream_t st;
+};
+
+namespace gpx {
+
+// ---------------------------------------------------------------------------
+// Feature map: out[i, f] = scale cos(omega_f . p_i), out[i, F + f] = scale sin(omega_f . p_i).  One thread per (point,
+// frequency), frequencies along the lanes (both stores coalesced; a point's coordinates are wave-uniform), a row loop beyond
+// 32768 points.  The projection and the sincos are fp64 for both dtypes; the one rounding to fp32 is the store.
+// ---------------------------------------------------------------------------
+template <typename T>
+__global__ __launch_bounds__(256) void rff_features_kernel(const T *__restrict__ pts, int64_t m, int d, const double *__restrict__ omega,
+                                                           int64_t F, double scale, T *__restrict__ out, int64_t ld)
+{
+    const int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (f >= F) return;
+    const double *w = omega + f * d;
+    for (int64_t i = blockIdx.y; i < m; i += gridDim.y) {
+        const T *p = pts + i * d;
+        double t = 0.0;
+        for (int k = 0; k < d; ++k) t = fma(w[k], (double)p[k], t);
+        double sn, cs;
+        sincos(t, &sn, &cs);
+        out[i * ld + f] = (T)(scale * cs);
+        out[i * ld + F + f] = (T)(scale * sn);
+    }
+}
+
+int rff_features(int dtype, const void *pts, int64_t m, int d, const double *omega_dev, int64_t F, double scale, void *out, int64_t ld,
+                 hipStream_t st)
+{
+    if (m <= 0 || F <= 0) return GPX_OK;
+    const dim3 grid((unsigned)cdiv(F, 256), (unsigned)std::min<int64_t>(m, 32768)), block(256);
+    ProfScope prof(PC_RFF, 2.0 * (double)m * (double)F * (double)esize(dtype), st);
+    if (dtype == GPX_F64)
+        hipLaunchKernelGGL((rff_features_kernel<double>), grid, block, 0, st, (const double *)pts, m, d, omega_dev, F, scale, (double *)out, ld);
+    else
+        hipLaunchKernelGGL((rff_features_kernel<float>), grid, block, 0, st, (const float *)pts, m, d, omega_dev, F, scale, (float *)out, ld);
+    GPX_LAUNCH_CHECK();
+    return GPX_OK;
+}
+
+// ---------------------------------------------------------------------------
+// K(xo, x) applied to S weight vectors, fused:  partial[slice][s][i] = sum_{j in slice} k(xo_i, x_j) V[s, j].
+// mean_kernel's shape (gpx_kmat.hip): workgroup (bx, by, bz) owns KA_MP test points, the by-th slice of the training set --
+// streamed through LDS in chunks of 256 points, one per lane, transposed and padded -- and the bz-th group of KA_SV weight
+// vectors.  Per chunk a lane loads its KA_SV weights V[s0 .. s0 + KA_SV, j] once (coalesced across the lanes, zero beyond S),
+// forms each k(xo_p, x_j) once -- the distance as kmat_kernel accumulates it, the entry function of kmat_kernel, underflow
+// clamp included: the value is the element gpx_d_kmat would store -- and adds it into KA_MP x KA_SV f64 sums.  Only a new group
+// of vectors (gridDim.z) evaluates the kernel again.  Lanes are added by shuffles, waves through LDS, slices by
+// kapply_reduce_kernel in ascending order: no atomics, bitwise repeatable.
+// KA_MP x KA_SV <= 32 f64 accumulators are at most 64 VGPRs of the lane's state; DESIGN "Posterior paths" has the compiler's count.
+// ---------------------------------------------------------------------------
+constexpr int KA_CP = 257;         // padded chunk row (mean_kernel's MCP)
+constexpr int KA_LDS_MAX = 96 * 1024;   // the largest chunk of x the fused kernel is launched with (kapply_fused_fits).  set_max_lds sets a
+                                        // kernel's limit ONCE per device, so it gets this constant, never the d-dependent size of one call
+
+// The register block by the number of weight vectors: (test points per workgroup, vectors per lane).  One vector is
+// mean_kernel's own shape; up to four keep its 8 points -- the chunk's staging pass and its two barriers are shared by twice
+// the pairs -- and from five on the block is 4 x 8.  (Measured with 4 x 8 alone, DESIGN "Posterior paths": S = 1 took 1.7 times
+// gpx_d_mean in fp64 and 2.6 times in fp32, where seven of the eight f64 FMAs per kernel value multiplied zeros.)
+struct KaShape { int mp, sv; };
+static inline KaShape kapply_shape(int64_t S) { return S == 1 ? KaShape{8, 1} : (S <= 4 ? KaShape{8, 4} : KaShape{4, 8}); }
+
+// KIND: GPX_KERNEL_GAUSSIAN or GPX_KERNEL_PERIODIC (member GPX_K, any d); KA_MP x KA_SV: the register block
+template <typename T, int KIND, int KA_MP, int KA_SV>
+__global__ __launch_bounds__(256) void kapply_fused_kernel(const T *__restrict__ xo, int64_t m, const T *__restrict__ x, int64_t n, int d,
+                                                           KParams kp, const T *__restrict__ V, int64_t ldv, int64_t S,
+                                                           int64_t slice_len, double *__restrict__ partial)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    T *sx = reinterpret_cast<T *>(smem_raw);            // [d][KA_CP] chunk of x, transposed
+    __shared__ double red[4][KA_MP * KA_SV];
+
+    const int tid = threadIdx.x;
+    const int64_t p0 = (int64_t)blockIdx.x * KA_MP;
+    const int64_t s0 = (int64_t)blockIdx.z * KA_SV;
+    double acc[KA_MP][KA_SV];
+#pragma unroll
+    for (int pp = 0; pp < KA_MP; ++pp)
+#pragma unroll
+        for (int sv = 0; sv < KA_SV; ++sv) acc[pp][sv] = 0.0;
+    const T *orow[KA_MP];
+#pragma unroll
+    for (int pp = 0; pp < KA_MP; ++pp) orow[pp] = xo + min(p0 + pp, m - 1) * d;
+
+    const T c1 = (T)kp.c[0], c2 = (T)kp.c[1];
+    const int qd = 256 / d, rd = 256 - qd * d;          // idx += 256  <=>  (c, k) += (qd, rd) with carry
+    const int cst = tid / d, kst = tid - cst * d;
+    const int64_t jbeg = (int64_t)blockIdx.y * slice_len, jend = min(n, jbeg + slice_len);
+    for (int64_t j0 = jbeg; j0 < jend; j0 += 256) {
+        __syncthreads();
+        {
+            const int64_t lim = (jend - j0) * d;
+            const T *g = x + j0 * d;
+            int c = cst, k = kst;
+            for (int idx = tid; idx < 256 * d; idx += 256) {
+                sx[(size_t)k * KA_CP + c] = (idx < lim) ? g[idx] : (T)0;
+                c += qd; k += rd;
+                if (k >= d) { k -= d; ++c; }
+            }
+        }
+        __syncthreads();
+        const int64_t j = j0 + tid;
+        if (j < jend) {
+            double vj[KA_SV];
+#pragma unroll
+            for (int sv = 0; sv < KA_SV; ++sv) vj[sv] = (s0 + sv < S) ? (double)V[(s0 + sv) * ldv + j] : 0.0;
+            T r[KA_MP];
+#pragma unroll
+            for (int pp = 0; pp < KA_MP; ++pp) r[pp] = (T)0;
+            // (the test points are the same for every lane: SGPR operands through the scalar cache, as in kmat_kernel)
+            for (int k = 0; k < d; ++k) {
+                const T b = sx[(size_t)k * KA_CP + tid];
+#pragma unroll
+                for (int pp = 0; pp < KA_MP; ++pp) {
+                    const T a = orow[pp][k];
+                    if (KIND == GPX_KERNEL_GAUSSIAN) {
+                        const T t = a - b;
+                        r[pp] = fma(t, t, r[pp]);
+                    } else {
+                        const T sn = sin((T)0.5 * (a - b) / (T)kp.c[2]);
+                        r[pp] = fma(sn, sn, r[pp]);
+                    }
+                }
+            }
+#pragma unroll
+            for (int pp = 0; pp < KA_MP; ++pp) {
+                T kv;
+                if (KIND == GPX_KERNEL_GAUSSIAN) {
+                    kv = gaussian_entry<T, 0>(r[pp], c1, c2, (T)0, (T)0);
+                } else {
+                    const T h = (T)kp.c[0], w = (T)kp.c[1];
+                    kv = (h * h) * dev_exp<T>((T)-2.0 * r[pp] / (w * w));
+                }
+                const double kd = (double)kv;
+#pragma unroll
+                for (int sv = 0; sv < KA_SV; ++sv) acc[pp][sv] = fma(kd, vj[sv], acc[pp][sv]);
+            }
+        }
+    }
+    // wave reduction (64 lanes), then across the 4 waves in a fixed order
+#pragma unroll
+    for (int pp = 0; pp < KA_MP; ++pp)
+#pragma unroll
+        for (int sv = 0; sv < KA_SV; ++sv) {
+            double v = acc[pp][sv];
+            for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+            if ((tid & 63) == 0) red[tid >> 6][pp * KA_SV + sv] = v;
+        }
+    __syncthreads();
+    if (tid < KA_MP * KA_SV) {
+        const int pp = tid / KA_SV, sv = tid - pp * KA_SV;
+        if (p0 + pp < m && s0 + sv < S)
+            partial[((int64_t)blockIdx.y * S + s0 + sv) * m + p0 + pp] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
+    }
+}
+
+// out[s, i] += sum over the slices, in slice order; one rounding to T
+template <typename T>
+__global__ __launch_bounds__(256) void kapply_reduce_kernel(const double *__restrict__ partial, int nslice, int64_t S, int64_t m,
+                                                            T *__restrict__ out, int64_t ldo)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= m) return;
+    for (int64_t s = blockIdx.y; s < S; s += gridDim.y) {
+        double sum = 0.0;
+        for (int y = 0; y < nslice; ++y) sum += partial[((int64_t)y * S + s) * m + i];
+        out[s * ldo + i] = (T)((double)out[s * ldo + i] + sum);
+    }
+}
+
+static thread_local ThreadScratch g_kapply_scr;   // fused route: the slice partial sums; product route: the chunk of K(xo, x)
+
+// does the fused kernel take this (d, S)?  launch_mean's range of d (the chunk of x in LDS), one grid z per vector group
+static bool kapply_fused_fits(int dtype, int d, int64_t S)
+{
+    return (size_t)d * KA_CP * esize(dtype) <= (size_t)KA_LDS_MAX && cdiv(S, kapply_shape(S).sv) <= 65535;
+}
+
+template <typename T, int KA_MP, int KA_SV>
+static int launch_kapply_fused(int kernel, const void *xo, int64_t m, const void *x, int64_t n, int d, const KParams &kp, const void *V,
+                               int64_t ldv, int64_t S, void *out, int64_t ldo, hipStream_t st)
+{
+    const size_t smem = (size_t)d * KA_CP * sizeof(T);
+    const int64_t gx = cdiv(m, KA_MP), gz = cdiv(S, KA_SV);
+    // enough workgroups to fill the chip: slices of the training set when m and the vector groups alone are too few (launch_mean's rule)
+    int64_t nslice = std::max<int64_t>(1, std::min<int64_t>(cdiv(2048, gx * gz), cdiv(n, 256)));
+    const int64_t slice_len = cdiv(cdiv(n, nslice), 256) * 256;
+    nslice = cdiv(n, slice_len);
+    void *scr = nullptr;
+    GPX_TRY(g_kapply_scr.get((size_t)nslice * S * m * sizeof(double), &scr));
+    double *partial = (double *)scr;
+    const dim3 grid((unsigned)gx, (unsigned)nslice, (unsigned)gz), block(256);
+    ProfScope prof(PC_KAPPLY, (double)m * (double)n * (double)gz, st);
+#define GPX_KAPPLY_LAUNCH(KIND)                                                                                                    \
+    do {                                                                                                                           \
+        if (smem > 48 * 1024) GPX_TRY(set_max_lds((const void *)kapply_fused_kernel<T, KIND, KA_MP, KA_SV>, KA_LDS_MAX));           \
+        hipLaunchKernelGGL((kapply_fused_kernel<T, KIND, KA_MP, KA_SV>), grid, block, smem, st, (const T *)xo, m, (const T *)x, n, \
+                           d, kp, (const T *)V, ldv, S, slice_len, partial);                                                       \
+    } while (0)
+    if (kernel == GPX_KERNEL_GAUSSIAN) GPX_KAPPLY_LAUNCH(GPX_KERNEL_GAUSSIAN);
+    else GPX_KAPPLY_LAUNCH(GPX_KERNEL_PERIODIC);
+#undef GPX_KAPPLY_LAUNCH
+    GPX_LAUNCH_CHECK();
+    const dim3 rgrid((unsigned)cdiv(m, 256), (unsigned)std::min<int64_t>(S, 32768));
+    hipLaunchKernelGGL((kapply_reduce_kernel<T>), rgrid, block, 0, st, partial, (int)nslice, S, m, (T *)out, ldo);
+    GPX_LAUNCH_CHECK();
+    return GPX_OK;
+}
+
+template <typename T>
+static int kapply_fused(int kernel, const void *xo, int64_t m, const void *x, int64_t n, int d, const KParams &kp, const void *V,
+                        int64_t ldv, int64_t S, void *out, int64_t ldo, hipStream_t st)
+{
+    const KaShape sh = kapply_shape(S);
+    if (sh.sv == 1) return launch_kapply_fused<T, 8, 1>(kernel, xo, m, x, n, d, kp, V, ldv, S, out, ldo, st);
+    if (sh.sv == 4) return launch_kapply_fused<T, 8, 4>(kernel, xo, m, x, n, d, kp, V, ldv, S, out, ldo, st);
+    return launch_kapply_fused<T, 4, 8>(kernel, xo, m, x, n, d, kp, V, ldv, S, out, ldo, st);
+}
+
+// the product route's chunk of K(xo, x): a multiple of 128 rows (the shifted C pointer of the product stays aligned), at most
+// 4096, within KAPPLY_CHUNK_BYTES
+constexpr size_t KAPPLY_CHUNK_BYTES = (size_t)256 << 20;
+
+int kmat_apply(int dtype, int kernel, const void *xo, int64_t m, const void *x, int64_t n, int d, const double *params, const void *V,
+               int64_t ldv, int64_t S, void *out, int64_t ldo, hipStream_t st)
+{
+    if (m <= 0 || S <= 0 || n <= 0) return GPX_OK;
+    if (kernel != GPX_KERNEL_GAUSSIAN && kernel != GPX_KERNEL_PERIODIC) {
+        set_error("kmat_apply: kernel family %d is not supported (GPX_KERNEL_GAUSSIAN or GPX_KERNEL_PERIODIC; the ARD family on scaled points)", kernel);
+        return GPX_ERR_UNSUPPORTED;
+    }
+    const size_t es = esize(dtype);
+    if (S <= tune().kapply_fused_max[dtype] && kapply_fused_fits(dtype, d, S)) {
+        KParams kp;
+        GPX_TRY(make_kparams(kernel, GPX_K, params, 0.0, &kp));
+        route_hit(RT_KAPPLY_FUSED);
+        if (dtype == GPX_F64) return kapply_fused<double>(kernel, xo, m, x, n, d, kp, V, ldv, S, out, ldo, st);
+        return kapply_fused<float>(kernel, xo, m, x, n, d, kp, V, ldv, S, out, ldo, st);
+    }
+    // (any base and pitch of V: gemm_nt takes its generic kernel where the LDS-DMA one needs 16-byte alignment)
+    const int64_t ldk = round_up(n, 16);
+    const int64_t fit = (int64_t)(KAPPLY_CHUNK_BYTES / ((size_t)ldk * es)) / 128 * 128;
+    const int64_t rows = std::min<int64_t>(m, std::max<int64_t>(128, std::min<int64_t>(fit, 4096)));
+    void *Kc = nullptr;
+    GPX_TRY(g_kapply_scr.get((size_t)rows * ldk * es, &Kc));
+    for (int64_t r0 = 0; r0 < m; r0 += rows) {
+        const int64_t rc = std::min(rows, m - r0);
+        route_hit(RT_KAPPLY_GEMM);
+        GPX_TRY(kmat(dtype, kernel, GPX_K, (const char *)xo + (size_t)r0 * d * es, rc, x, n, d, params, 0.0, GPX_FULL, Kc, ldk, st));
+        GPX_TRY(gemm_nt(dtype, S, rc, n, V, ldv, Kc, ldk, (char *)out + (size_t)r0 * es, ldo, 1.0, GPX_FULL, 0, 0, st));
+    }
+    return GPX_OK;
+}
+
+// ---- the handle's small kernels --------------------------------------------------------------------------------------
+// a[i] = a[i] / div for i < count (a true division: Omega = z / w_v as numpy divides)
+__global__ void paths_div_kernel(double *__restrict__ a, int64_t count, double div)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < count) a[i] = a[i] / div;
+}
+
+// R[s, j] = mul * R[s, j]  (alpha == null)   or   R[s, j] = alpha[j] - R[s, j];   grid (column blocks of 256, rows up to 32768)
+template <typename T>
+__global__ void paths_rows_kernel(T *__restrict__ R, int64_t ld, int64_t rows, int64_t cols, T mul, const T *__restrict__ alpha)
+{
+    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= cols) return;
+    for (int64_t r = blockIdx.y; r < rows; r += gridDim.y) R[r * ld + c] = alpha ? alpha[c] - R[r * ld + c] : mul * R[r * ld + c];
+}
+
+static int paths_rows(int dtype, void *R, int64_t ld, int64_t rows, int64_t cols, double mul, const void *alpha, hipStream_t st)
+{
+    const dim3 grid((unsigned)cdiv(cols, 256), (unsigned)std::min<int64_t>(rows, 32768)), block(256);
+    if (dtype == GPX_F64) hipLaunchKernelGGL((paths_rows_kernel<double>), grid, block, 0, st, (double *)R, ld, rows, cols, mul, (const double *)alpha);
+    else hipLaunchKernelGGL((paths_rows_kernel<float>), grid, block, 0, st, (float *)R, ld, rows, cols, (float)mul, (const float *)alpha);
+    GPX_LAUNCH_CHECK();
+    return GPX_OK;
+}
+
+// rows of a feature chunk: a multiple of 128 (the shifted C pointer of R += Theta Phi_c^T stays aligned), at most 4096, within
+// 128 MiB of features
+static int64_t paths_feature_rows(int dtype, int64_t ldphi)
+{
+    const int64_t fit = (int64_t)(((size_t)128 << 20) / ((size_t)ldphi * esize(dtype))) / 128 * 128;
+    return std::max<int64_t>(128, std::min<int64_t>(fit, 4096));
+}
+
+// the five stage marks of one creation, destroyed on scope exit
+struct StageEvents {
+    hipEvent_t e[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    int create() { for (hipEvent_t &x : e) GPX_HIP(hipEventCreate(&x)); return GPX_OK; }
+    ~StageEvents() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
+};
+
+// everything gpx_gp_paths_create enqueues on the source's stream, into a handle whose fields are allocated
+static int paths_build(gpx_gp *g, gpx_paths *p)
+{
+    const GpView v = gp_view(g);
+    const int dtype = g->dtype, d = g->d;
+    const int64_t n = g->n, S = p->S, F = p->F;
+    const size_t es = esize(dtype);
+    hipStream_t st = g->st;
+    StageEvents ev;                                         // start | generators, copy | features + products | sweeps | V = alpha - R
+    GPX_TRY(ev.create());
+    GPX_HIP(hipEventRecord(ev.e[0], st));
+    GPX_HIP(hipMemcpyAsync(p->pts, v.x, (size_t)n * d * es, hipMemcpyDeviceToDevice, st));
+    // Omega = z(seed, 1, .) / w_v
+    GPX_TRY(randn(GPX_F64, p->omega, F, d, d, p->seed, 1, 0, st));
+    hipLaunchKernelGGL(paths_div_kernel, dim3((unsigned)cdiv(F * d, 256)), dim3(256), 0, st, p->omega, F * d, p->iso[1]);
+    GPX_LAUNCH_CHECK();
+    if (S == 0) { GPX_HIP(hipStreamSynchronize(st)); return GPX_OK; }
+    GPX_HIP(hipMemsetAsync(p->theta, 0, (size_t)S * p->ldt * es, st));
+    GPX_HIP(hipMemsetAsync(p->V, 0, (size_t)S * p->ldv * es, st));
+    GPX_TRY(randn(dtype, p->theta, S, 2 * F, p->ldt, p->seed, 2, 0, st));
+    // R = sigma E, then R += Theta Phi(x)^T in row chunks of x: a full n x 2F never exists
+    void *R = p->V;
+    GPX_TRY(randn(dtype, R, S, n, p->ldv, p->seed, 3, 0, st));
+    GPX_TRY(paths_rows(dtype, R, p->ldv, S, n, g->s, nullptr, st));
+    const int64_t ldphi = p->ldt, rows = std::min(n, paths_feature_rows(dtype, ldphi));
+    DevBuf phi;
+    GPX_TRY(phi.alloc((size_t)rows * ldphi * es));
+    GPX_HIP(hipEventRecord(ev.e[1], st));
+    for (int64_t r0 = 0; r0 < n; r0 += rows) {
+        const int64_t rc = std::min(rows, n - r0);
+        GPX_TRY(rff_features(dtype, (const char *)p->pts + (size_t)r0 * d * es, rc, d, p->omega, F, p->scale, phi.p, ldphi, st));
+        GPX_TRY(gemm_nt(dtype, S, rc, 2 * F, p->theta, p->ldt, phi.p, ldphi, (char *)R + (size_t)r0 * es, p->ldv, 1.0, GPX_FULL, 0, 0, st));
+    }
+    GPX_HIP(hipEventRecord(ev.e[2], st));
+    // R <- R Kxx^-1 (rows are right-hand sides: two sweeps over the factor), V = alpha - R
+    GPX_TRY(trsm_right_lt(dtype, g->A, n, g->lda, R, S, p->ldv, st, 0, &g->ops));
+    GPX_TRY(trsm_right_l(dtype, g->A, n, g->lda, R, S, p->ldv, st, &g->ops));
+    GPX_HIP(hipEventRecord(ev.e[3], st));
+    GPX_TRY(paths_rows(dtype, R, p->ldv, S, n, 0.0, g->alpha, st));
+    GPX_HIP(hipEventRecord(ev.e[4], st));
+    GPX_HIP(hipStreamSynchronize(st));                      // (phi is freed on return)
+    GPX_HIP(hipEventElapsedTime(&p->ms[0], ev.e[1], ev.e[2]));
+    GPX_HIP(hipEventElapsedTime(&p->ms[1], ev.e[2], ev.e[3]));
+    GPX_HIP(hipEventElapsedTime(&p->ms[3], ev.e[0], ev.e[4]));
+    p->ms[2] = p->ms[3] - p->ms[0] - p->ms[1];
+    return GPX_OK;
+}
+
+}  // namespace gpx
+
+using namespace gpx;
+
+// upload_f64 takes its staging copy as a DevBuf; this one looks at memory the handle owns and frees nothing
+struct StageView {
+    gpx::DevBuf buf;
+    explicit StageView(void *p) { buf.p = p; }
+    ~StageView() { buf.p = nullptr; }
+};
+
+// every gpx_paths_* entry: GP_ENTER's steps for a paths handle
+#define PATHS_ENTER(p)                                                       \
+    GPX_ARG((p) != nullptr, "paths is NULL");                                \
+    gpx::tune_refresh();                                                     \
+    gpx::DeviceGuard guard__((p)->device);                                   \
+    if (guard__.rc != GPX_OK) return guard__.rc;                             \
+    gpx::StreamTurn turn__((p)->st);                                         \
+    gpx::RoctxRange api_range__(__func__)
+
+extern "C" {
+
+int gpx_d_rff_features(int dtype, const void *pts, int64_t m, int d, const double *omega_dev, int64_t F, double scale, void *out,
+                       int64_t ld, void *stream)
+{
+    GPX_TRY(ensure_device());
+    GPX_ARG(dtype == GPX_F64 || dtype == GPX_F32, "dtype must be GPX_F64 or GPX_F32");
+    GPX_ARG(m >= 0 && F >= 0 && d >= 1, "need m, F >= 0 and d >= 1");
+    if (m == 0 || F == 0) return GPX_OK;
+    GPX_ARG(pts && omega_dev && out, "NULL pointer");
+    GPX_ARG(F <= INT64_MAX / 2 && ld >= 2 * F, "ld < 2 F");
+    GPX_ARG(m <= INT64_MAX / ld && F <= INT64_MAX / d, "m * ld overflows");
+    GPX_ARG(cdiv(F, 256) <= 0x7fffffff, "F is more than one launch covers");
+    return rff_features(dtype, pts, m, d, omega_dev, F, scale, out, ld, S(stream));
+}
+
+int gpx_d_kmat_apply(int dtype, int kernel, const void *xo, int64_t m, const void *x, int64_t n, int d, const double *params,
+                     const void *V, int64_t ldv, int64_t Sn, void *out, int64_t ldo, void *stream)
+{
+    gpx::StreamTurn turn__((hipStream_t)stream);     // (this thread's scratch buffers: one stream at a time, gpx_mem.h)
+    GPX_TRY(ensure_device());
+    GPX_ARG(dtype == GPX_F64 || dtype == GPX_F32, "dtype must be GPX_F64 or GPX_F32");
+    GPX_ARG(n >= 0 && m >= 0 && Sn >= 0 && d >= 1, "need n, m, S >= 0 and d >= 1");
+    if (m == 0 || Sn == 0 || n == 0) return GPX_OK;
+    GPX_ARG(xo && x && V && out && params, "NULL pointer");
+    GPX_ARG(ldv >= n && ldo >= m, "leading dimension too small");
+    GPX_ARG(Sn <= INT64_MAX / ldv && Sn <= INT64_MAX / ldo && cdiv(m, 4) <= 0x7fffffff, "S * ld overflows, or m is more than one launch covers");   // (cdiv(m, 4): the most workgroups along x)
+    return kmat_apply(dtype, kernel, xo, m, x, n, d, params, V, ldv, Sn, out, ldo, S(stream));
+}
+
+int gpx_paths_destroy(gpx_paths_t *p)
+{
+    if (!p) return GPX_OK;
+    gpx::DeviceGuard guard__(p->device);
+    if (p->st) (void)hipStreamSynchronize(p->st);
+    stream_epoch_bump();                                       // (StreamTurn: a later stream at this one's address is a different stream)
+    for (void *b : {(void *)p->omega, p->theta, p->V, p->pts}) dev_free(b);
+    p->ws.release();
+    if (p->st) (void)hipStreamDestroy(p->st);
+    delete p;
+    return GPX_OK;
+}
+
+int gpx_gp_paths_create(gpx_gp_t *g, int64_t Sn, int64_t F, uint64_t seed, gpx_paths_t **out)
+{
+    GPX_ARG(out, "paths is NULL");
+    *out = nullptr;
+    GP_ENTER(g);
+    if (g->kernel == GPX_KERNEL_PERIODIC) {
+        set_error("gpx_gp_paths_create: the periodic family is not supported (GPX_KERNEL_GAUSSIAN and GPX_KERNEL_GAUSSIAN_ARD are)");
+        return GPX_ERR_UNSUPPORTED;
+    }
+    GPX_ARG(Sn >= 0 && F >= 1, "need S >= 0 and F >= 1");
+    GPX_ARG(g->fitted && g->have_data, "gp is not fitted");
+    if (!g->have_params) {
+        set_error("gpx_gp_paths_create: a handle fitted from gpx_gp_set_K has no kernel parameters to draw a prior from");
+        return GPX_ERR_UNSUPPORTED;
+    }
+    if (!g->y_finite) { set_error("array must not contain infs or NaNs (y)"); return GPX_ERR_ARG; }
+    GPX_ARG(F <= (INT64_MAX / 4) / std::max<int64_t>(Sn, g->d) && Sn <= INT64_MAX / (g->lda * 8), "S * F, F * d or S * n overflows");
+    GPX_TRY(gp_need_factor(g, "to condition the paths on"));
+    const GpView v = gp_view(g);
+    const size_t es = esize(g->dtype);
+    gpx_paths *p = new gpx_paths();
+    memset(p, 0, sizeof(*p));
+    p->device = g->device; p->dtype = g->dtype; p->kernel = g->kernel; p->d = g->d;
+    p->n = g->n; p->S = Sn; p->F = F; p->seed = seed;
+    p->ldv = g->lda; p->ldt = round_up(2 * F, 16);
+    p->iso[0] = v.params[0]; p->iso[1] = v.params[1];
+    for (int k = 0; k < GPX_ARD_MAX_D; ++k) p->w[k] = (g->kernel == GPX_KERNEL_GAUSSIAN_ARD && k < g->d) ? g->params[1 + k] : 1.0;
+    const double k0 = 0.5 * sqrt(2.0 / M_PI) * p->iso[0] * p->iso[0] / p->iso[1];     // gp_prior_var: h_v^2 / (w_v sqrt(2 pi))
+    p->scale = sqrt(k0 / (double)F);
+    int rc = GPX_OK;
+#define PATHS_ALLOC(field, bytes) if (rc == GPX_OK) rc = dev_alloc((void **)&p->field, (bytes) ? (bytes) : 16, "hipMalloc " #field)
+    PATHS_ALLOC(omega, (size_t)F * g->d * sizeof(double));
+    PATHS_ALLOC(theta, (size_t)Sn * p->ldt * es);
+    PATHS_ALLOC(V, (size_t)Sn * p->ldv * es);
+    PATHS_ALLOC(pts, (size_t)g->n * g->d * es);
+#undef PATHS_ALLOC
+    if (rc == GPX_OK) {
+        hipError_t e = hipStreamCreateWithFlags(&p->st, hipStreamNonBlocking);
+        if (e != hipSuccess) rc = hip_fail(e, "hipStreamCreate", __FILE__, __LINE__);
+    }
+    if (rc == GPX_OK) rc = paths_build(g, p);
+    if (rc == GPX_OK) {
+        hipError_t e = hipStreamSynchronize(g->st);
+        if (e != hipSuccess) rc = hip_fail(e, "hipStreamSynchronize", __FILE__, __LINE__);
+    }
+    if (rc != GPX_OK) { (void)hipStreamSynchronize(g->st); gpx_paths_destroy(p); return rc; }
+    *out = p;
+    return GPX_OK;
+}
+
+int gpx_paths_eval(gpx_paths_t *p, const double *xo, int64_t m, int64_t chunk_rows, double *out)
+{
+    PATHS_ENTER(p);
+    GPX_ARG(m >= 0 && (m == 0 || p->S == 0 || (xo && out)), "bad arguments");
+    if (chunk_rows < 0 || chunk_rows % 128 != 0) {
+        set_error("gpx_paths_eval: chunk_rows must be 0 (automatic) or a multiple of 128");
+        return GPX_ERR_ARG;
+    }
+    if (m == 0 || p->S == 0) return GPX_OK;
+    const int dtype = p->dtype, d = p->d;
+    const int64_t S = p->S, F = p->F;
+    const size_t es = esize(dtype);
+    GPX_ARG(m <= INT64_MAX / (8 * std::max<int64_t>(S, d)), "S * m overflows");
+    int64_t rows = chunk_rows ? chunk_rows : paths_feature_rows(dtype, p->ldt);
+    if (m <= rows) rows = m;                              // one chunk: exactly the rows there are
+    const int64_t ldo = round_up(rows, 16);
+    // One chunk's buffers, carved out of the handle's grow-only block: a loop that evaluates round after round allocates once.
+    const auto pad = [](size_t b) { return (b + 255) / 256 * 256; };
+    const size_t b_xo = pad((size_t)rows * d * es), b_phi = pad((size_t)rows * p->ldt * es), b_out = pad((size_t)S * ldo * es);
+    const size_t b_stage = dtype == GPX_F64 ? 0 : pad((size_t)rows * d * sizeof(double));   // upload_f64's float64 copy (fp32 only)
+    GPX_TRY(p->ws.reserve(b_xo + b_phi + b_out + b_stage, p->st));
+    char *base = (char *)p->ws.p;
+    void *dxo = base, *phi = base + b_xo, *outc = base + b_xo + b_phi;
+    StageView stage(b_stage ? base + b_xo + b_phi + b_out : nullptr);
+    for (int64_t r0 = 0; r0 < m; r0 += rows) {
+        const int64_t rc = std::min(rows, m - r0);
+        GPX_TRY(upload_f64(dtype, dxo, rc * d, xo + r0 * d, rc * d, 1, rc * d, p->st, b_stage ? &stage.buf : nullptr));
+        if (p->kernel == GPX_KERNEL_GAUSSIAN_ARD) GPX_TRY(scale_points(dtype, dxo, rc, d, p->w, dxo, p->st));
+        GPX_TRY(rff_features(dtype, dxo, rc, d, p->omega, F, p->scale, phi, p->ldt, p->st));
+        GPX_HIP(hipMemsetAsync(outc, 0, (size_t)S * ldo * es, p->st));
+        GPX_TRY(gemm_nt(dtype, S, rc, 2 * F, p->theta, p->ldt, phi, p->ldt, outc, ldo, 1.0, GPX_FULL, 0, 0, p->st));
+        GPX_TRY(kmat_apply(dtype, GPX_KERNEL_GAUSSIAN, dxo, rc, p->pts, p->n, d, p->iso, p->V, p->ldv, S, outc, ldo, p->st));
+        GPX_TRY(download_f64(dtype, out + r0, m, outc, ldo, S, rc, 0, p->st));
+    }
+    return GPX_OK;
+}
+
+int gpx_paths_get(gpx_paths_t *p, double *omega, double *theta, double *V)
+{
+    PATHS_ENTER(p);
+    if (omega) {
+        GPX_HIP(hipMemcpyAsync(omega, p->omega, (size_t)p->F * p->d * sizeof(double), hipMemcpyDeviceToHost, p->st));
+        GPX_HIP(hipStreamSynchronize(p->st));
+    }
+    if (theta) GPX_TRY(download_f64(p->dtype, theta, 2 * p->F, p->theta, p->ldt, p->S, 2 * p->F, 0, p->st));
+    if (V) GPX_TRY(download_f64(p->dtype, V, p->n, p->V, p->ldv, p->S, p->n, 0, p->st));
+    return GPX_OK;
+}
+
+int gpx_debug_paths_timing(gpx_paths_t *p, float *ms4)
+{
+    GPX_ARG(p != nullptr && ms4 != nullptr, "NULL argument");
+    for (int i = 0; i < 4; ++i) ms4[i] = p->ms[i];
+    return GPX_OK;
+}
+
+int gpx_paths_describe(gpx_paths_t *p, int *dtype, int *kernel, int64_t *n, int *d, int64_t *Sn, int64_t *F, uint64_t *seed)
+{
+    GPX_ARG(p != nullptr, "paths is NULL");
+    if (dtype) *dtype = p->dtype;
+    if (kernel) *kernel = p->kernel;
+    if (n) *n = p->n;
+    if (d) *d = p->d;
+    if (Sn) *Sn = p->S;
+    if (F) *F = p->F;
+    if (seed) *seed = p->seed;
+    return GPX_OK;
+}
+
+}  // extern "C"

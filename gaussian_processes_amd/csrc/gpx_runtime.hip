@@ -54,6 +54,7 @@ extern "C" char **environ;
 namespace gpx {
 static thread_local Tune g_tune;
 static std::atomic<long long> g_tune_refreshes{0};
+static std::atomic<long long> g_kapply_fused_max{-1};   // gpx_debug_kapply_fused_max: < 0 = the per-dtype defaults
 const Tune &tune() { return g_tune; }
 int64_t tune_refresh_count() { return (int64_t)g_tune_refreshes.load(std::memory_order_relaxed); }
 
@@ -100,10 +101,19 @@ void tune_refresh()
             break;
         }
     }
+    const long long kfm = g_kapply_fused_max.load(std::memory_order_relaxed);
+    if (kfm >= 0) t.kapply_fused_max[0] = t.kapply_fused_max[1] = (int64_t)kfm;
     g_tune = t;
     g_tune_refreshes.fetch_add(1, std::memory_order_relaxed);
 }
 }  // namespace gpx
+
+extern "C" int gpx_debug_kapply_fused_max(int64_t value, int64_t *previous)
+{
+    const long long old = gpx::g_kapply_fused_max.exchange(value < 0 ? -1LL : (long long)value);
+    if (previous) *previous = (int64_t)old;
+    return GPX_OK;
+}
 
 extern "C" int gpx_debug_tune_refreshes(int64_t *count)
 {
@@ -194,7 +204,7 @@ const char *prof_class_name(int cls)
 {
     static const char *names[PC_COUNT] = {"gpx:kernel_matrix", "gpx:gemm_trailing_update", "gpx:potrf_panel", "gpx:trsm_rows", "gpx:trsv",
                                           "gpx:mean", "gpx:reduce", "gpx:gemm_skinny", "gpx:gemm_generic", "gpx:gemm_panel", "gpx:gemm_n64",
-                                          "gpx:transpose", "gpx:pred_grad", "gpx:extend", "gpx:randn"};
+                                          "gpx:transpose", "gpx:pred_grad", "gpx:extend", "gpx:randn", "gpx:rff_features", "gpx:kmat_apply"};
     return (cls >= 0 && cls < PC_COUNT) ? names[cls] : "gpx:other";
 }
 bool roctx_push(const char *name)

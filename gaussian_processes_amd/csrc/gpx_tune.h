@@ -68,6 +68,13 @@ namespace gpx {
     /* ---- diagnostics (gpx_runtime.hip) ---- */                                                                      \
     XF(roctx, "GPX_ROCTX")
 
+// GPX_KAPPLY_FUSED_MAX: gpx_d_kmat_apply takes its fused route up to this many weight vectors; keyed by dtype like the X2
+// entries (DESIGN "Posterior paths" has the measurement: the fp32 product is four times as fast as the fp64 one, the fused
+// kernel's f64 sums are not).  Not in the list above: it is set by a call (gpx_debug_kapply_fused_max: one value for both
+// dtypes), not by the environment, and every refresh copies the process-wide value into the snapshot.
+constexpr int64_t GPX_KAPPLY_FUSED_MAX_F64 = 32;
+constexpr int64_t GPX_KAPPLY_FUSED_MAX_F32 = 8;
+
 struct Tune {
 #define GPX_T_X(f, e, d) int64_t f = (d);
 #define GPX_T_XF(f, e) bool f = false;
@@ -82,6 +89,7 @@ struct Tune {
     long long potrf_widths[3] = {1, 8192, 12288};      // GPX_POTRF_WIDTHS = "rows128,rows256,rows512": outer-block taper
     bool mg_bcast_set = false, mg_bcast_sag = false;   // GPX_MG_BCAST ("sag": scatter + all-gather)
     char rccl_lib[256] = {0};                          // GPX_RCCL_LIB
+    int64_t kapply_fused_max[2] = {GPX_KAPPLY_FUSED_MAX_F64, GPX_KAPPLY_FUSED_MAX_F32};   // gpx_debug_kapply_fused_max
 };
 
 // the calling host thread's snapshot (defaults until its first refresh)

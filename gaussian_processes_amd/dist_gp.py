@@ -10,7 +10,7 @@ object as `gp.GP` -- ``log_lh``, ``lh``, ``inv_Kxx_y``, ``mean(xo)``, ``cov(xo)`
 Every rank builds the same object with the same data and calls the same members in the same order: a fit, a mean
 and a cov are collective.  The factor never leaves the ranks' HBM, so what needs an n x n host copy (`Kxx`, `Lxx`,
 `inv_Kxx`, the derivative stack, `dm_dtheta`), leave-one-out, the input-space gradients, growing the fit and joint samples (`loo`, `inv_Kxx_diag`, `dmean_dx`, `dvar_dx`,
-`predict_grad`, `extend`, `sample`: not implemented over the distributed factor) and what would have to carry a handle or a communicator to another
+`predict_grad`, `extend`, `sample`, `sample_paths`: not implemented over the distributed factor) and what would have to carry a handle or a communicator to another
 process (`save_fitted`, copy, pickle) raises NotImplementedError: `GP` has them.
 """
 import numpy as np
@@ -220,6 +220,7 @@ class DistributedGP(GP):
     predict_grad = _unsupported("predict_grad", _NO_XGRAD)
     extend = _unsupported("extend", "appending rows to the distributed factor is not implemented; one GPU has it")
     sample = _unsupported("sample", "joint samples over the distributed factor are not implemented; one GPU has them")
+    sample_paths = _unsupported("sample_paths", "posterior paths over the distributed factor are not implemented; one GPU has them")
     save_fitted = _unsupported("save_fitted")
     load_fitted = classmethod(_unsupported("load_fitted"))
     _state = _unsupported("_state")

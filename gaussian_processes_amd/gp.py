@@ -766,6 +766,45 @@ class GP(object):
                                         "is not positive (pass a larger jitter)" % (jitter, info.value, m))
         return out[0] if size is None else out
 
+    # ---- posterior function samples (extension) ----
+    def sample_paths(self, size, seed=None, features=1024):
+        r"""`size` draws of the posterior FUNCTION as a `PosteriorPaths` object that is evaluated at any number of points
+        afterwards, ``paths(xo) -> (size, m)``: pathwise conditioning (Matheron's rule),
+        :math:`f_s(a) = \phi(a)^\top \Theta_s + k(a, x) K_{xx}^{-1} (y - \Phi(x) \Theta_s - s\,\epsilon_s)` -- a
+        random-feature draw of the prior (`features` frequencies, cos / sin pairs) plus an exact, data-dependent update.
+        Where `sample` factors an ``(m, m)`` covariance for one fixed point set, a path costs ``O(m n)`` per evaluation and
+        can be optimised over many candidates (Thompson sampling).  `gaussian_processes_amd.paths` has the definition of
+        every random input; the object is a pure function of ``(seed, size, features)`` and this fitted GP.
+
+        ``size``: an int ``>= 0``.  ``seed``: as in `sample` (an int in ``[0, 2**64)``; ``None`` draws one from numpy's
+        global state); row `s` depends on `s` alone, so ``sample_paths(3, seed)`` is a prefix of ``sample_paths(9, seed)``.
+        ``features``: an int ``>= 1``; the prior's covariance error is ``O(k0 / sqrt(features))`` with `k0` the prior
+        variance, the data update is exact.  The draws are of the latent function: observation noise is not added.
+        Memory held on the device until the object is closed or collected: ``size x n`` weights (plus ``size x 2 features``
+        and a copy of `x`).  The result does not refer to this GP again.
+
+        `GaussianKernel` and `GaussianARDKernel` only: NotImplementedError for `PeriodicKernel` and for plugin kernels.
+        Raises numpy.linalg.LinAlgError when `Kxx` is not positive definite.  Not offered: gradients of a path with respect
+        to the input, `DistributedGP`, persistence of paths."""
+        from .paths import PosteriorPaths
+        if isinstance(size, bool) or not isinstance(size, (int, np.integer)) or size < 0:    # every refusal comes before the library is touched
+            raise ValueError("invalid value for size: %r (an int >= 0)" % (size,))
+        if isinstance(features, bool) or not isinstance(features, (int, np.integer)) or features < 1:
+            raise ValueError("invalid value for features: %r (an int >= 1)" % (features,))
+        if seed is None:
+            seed = int(np.random.randint(0, 2 ** 32)) << 32 | int(np.random.randint(0, 2 ** 32))
+        elif isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 2 ** 64:
+            raise ValueError("invalid value for seed: %r (None, or an int in [0, 2**64))" % (seed,))
+        kid = getattr(self.K, "_native_kernel", None)
+        if kid not in (_lib.KERNEL_GAUSSIAN, _lib.KERNEL_GAUSSIAN_ARD):
+            raise NotImplementedError("sample_paths supports GaussianKernel and GaussianARDKernel (a random-feature prior needs "
+                                      "the kernel's spectral density); %s is not supported" % type(self.K).__name__)
+        size, features, seed = int(size), int(features), int(seed)
+        st = self._fit_pd()
+        h = ctypes.c_void_p()
+        _lib.check(_lib.load().gpx_gp_paths_create(st.handle, size, features, seed, ctypes.byref(h)))
+        return PosteriorPaths(h, size, features, seed, self._n, self._d, self._x.ndim)
+
     # ---- growing a fitted GP (extension) ----
     def extend(self, x_new, y_new):
         r"""A new, fitted `GP` on the data of this one plus `k` further observations, without refactoring: the Cholesky

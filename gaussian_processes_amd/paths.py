@@ -1,0 +1,103 @@
+r"""PosteriorPaths -- draws of the posterior FUNCTION, to be evaluated at any number of points (`GP.sample_paths`).
+
+Pathwise conditioning (Matheron's rule; Wilson et al. 2020): a draw is a function,
+
+    f_s(a) = phi(a) . Theta_s + sum_j k(a, x_j) V[s, j],      V_s = alpha - Kxx^-1 (Phi(x) Theta_s + s E_s)
+
+-- a random-feature draw of the prior plus an exact, data-dependent update -- stored as one weight vector per path in HBM.
+Evaluating `size` paths at `m` points costs O(m n) kernel evaluations and O(m n size) multiply-adds; nothing ``(m, m)`` is
+ever formed, so a Thompson-sampling round can draw once and then optimise the draw over tens of thousands of candidates.
+
+The whole object is a pure function of ``(seed, size, features)`` and the fitted GP.  With `z(seed, stream, e)` the
+counter-based sequence of ``gpx_d_randn`` (include/gpx.h; stream 0 stays `GP.sample`'s), `p` the points `x` (Gaussian) or
+`x / w` (ARD), ``(h_v, w_v)`` the isotropic constants ``(h, w)`` or ``(h / sqrt(wbar), 1)``, ``k0 = h_v^2 / (w_v sqrt(2 pi))``
+and `F` = `features`:
+
+    Omega[f, k] = z(seed, 1, f d + k) / w_v          spectral frequencies (float64 for both dtypes)
+    Theta[s, q] = z(seed, 2, s 2F + q)               feature weights
+    E[s, j]     = z(seed, 3, s n + j)                the observation-noise draw
+    phi(a)      = sqrt(k0 / F) [cos(Omega a); sin(Omega a)]
+
+Row `s` of `Theta` and `E` depends on `s` alone: the random inputs of ``size=3`` are a prefix of those of ``size=9``.
+The approximation lies in the prior only -- its covariance error is ``O(k0 / sqrt(F))`` -- the data update is exact.
+The draws are of the LATENT function: observation noise is not added to the values.  Memory held: ``size x n`` weights,
+``size x 2F`` feature weights, ``F x d`` frequencies and a copy of the ``n x d`` points, all on the device.
+
+Out of scope: gradients of a path with respect to the input, the periodic family (an exact Fourier-series prior exists for
+it), plugin kernels, `DistributedGP`, and persistence -- a paths object is regenerated from its seed, not copied or pickled.
+"""
+import ctypes
+
+import numpy as np
+
+from . import _lib
+
+__all__ = ["PosteriorPaths"]
+
+DTYPE = np.float64
+
+
+class PosteriorPaths(object):
+    """`size` posterior function draws of a fitted `GP` (made by `GP.sample_paths`); call it with test points.
+
+    Attributes: ``size``, ``features``, ``seed``, ``n``, ``d``.  The object owns its device state and does not refer to the
+    `GP` again: the GP may be modified, refitted or deleted."""
+
+    def __init__(self, handle, size, features, seed, n, d, ndim):
+        self._handle = handle
+        self.size, self.features, self.seed, self.n, self.d = size, features, seed, n, d
+        self._ndim = ndim              # of the GP's x: 1 -> xo is (m,), 2 -> (m, d)
+
+    def __call__(self, xo, chunk_rows=0):
+        """The draws at `xo` (``(m,)`` for 1-D inputs or ``(m, d)``): ``(size, m)`` float64.  ``chunk_rows``: test points per
+        device chunk, 0 (automatic) or a multiple of 128."""
+        xo = np.ascontiguousarray(xo, dtype=DTYPE)             # every refusal comes before the library is touched
+        d = 1 if xo.ndim == 1 else xo.shape[1] if xo.ndim == 2 else -1
+        if xo.ndim not in (1, 2) or d != self.d or (xo.ndim == 1 and self._ndim == 2):
+            raise ValueError("invalid shape for xo: %s" % str(xo.shape))
+        if isinstance(chunk_rows, bool) or not isinstance(chunk_rows, (int, np.integer)) or chunk_rows < 0 or chunk_rows % 128:
+            raise ValueError("invalid value for chunk_rows: %r (0, or a multiple of 128)" % (chunk_rows,))
+        if not self._handle:
+            raise ValueError("the paths have been closed")
+        m = xo.shape[0]
+        out = np.empty((self.size, m), dtype=DTYPE)
+        _lib.check(_lib.load().gpx_paths_eval(self._handle, _lib.dptr(xo), m, int(chunk_rows), _lib.dptr(out)))
+        return out
+
+    def state(self):
+        """Diagnostic: ``(Omega (F, d), Theta (size, 2F), V (size, n))`` as float64 host copies (``gpx_paths_get``; the tests pin
+        the definition with it)."""
+        if not self._handle:
+            raise ValueError("the paths have been closed")
+        omega = np.empty((self.features, self.d), dtype=DTYPE)
+        theta = np.empty((self.size, 2 * self.features), dtype=DTYPE)
+        V = np.empty((self.size, self.n), dtype=DTYPE)
+        _lib.check(_lib.load().gpx_paths_get(self._handle, _lib.dptr(omega), _lib.dptr(theta), _lib.dptr(V)))
+        return omega, theta, V
+
+    def create_timing(self):
+        """Diagnostic (tools/paths_probe.py): milliseconds the creation took on the device -- features + products, the two
+        sweeps, the rest, total."""
+        if not self._handle:
+            raise ValueError("the paths have been closed")
+        ms = (ctypes.c_float * 4)()
+        _lib.check(_lib.load().gpx_debug_paths_timing(self._handle, ms))
+        return dict(zip(("features_products", "sweeps", "rest", "total"), list(ms)))
+
+    def close(self):
+        """Release the device state now (`__del__` does it otherwise)."""
+        if self._handle:
+            _lib.load().gpx_paths_destroy(self._handle)
+            self._handle = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:   # interpreter shutdown
+            pass
+
+    def _no_copy(self, *args, **kwargs):
+        raise NotImplementedError("PosteriorPaths holds device state and is not copied or pickled: regenerate it from the seed, "
+                                  "gp.sample_paths(%d, seed=%d, features=%d)" % (self.size, self.seed, self.features))
+
+    __copy__ = __deepcopy__ = __reduce_ex__ = __getstate__ = _no_copy

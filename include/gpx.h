@@ -174,6 +174,8 @@ int gpx_stream_wait_event(void *stream, void *event);
 #define GPX_PROF_PRED_GRAD   12 /* pred_grad_kernel + its slice reduction; kernel evaluations m*n per window of dimensions */
 #define GPX_PROF_EXTEND      13 /* copy_lower_kernel + schur_reduce_kernel (gpx_gp_extend): bytes read + written */
 #define GPX_PROF_RANDN       14 /* randn_kernel (gpx_d_randn): bytes written */
+#define GPX_PROF_RFF         15 /* rff_features_kernel (gpx_d_rff_features): bytes written */
+#define GPX_PROF_KAPPLY      16 /* kapply_fused_kernel + its slice reduction (gpx_d_kmat_apply, fused route): kernel evaluations m*n per group of weight vectors */
 int gpx_prof_enable(int on);    /* also clears the registry */
 int gpx_prof_read(int cls, double *launches, double *total_ms, double *total_work);
 
@@ -202,6 +204,8 @@ int gpx_prof_read(int cls, double *launches, double *total_ms, double *total_wor
 #define GPX_ROUTE_GRAD_CHUNK     18   /* input-space gradient of the variance (gpx_gp_var_grad): one hit per row chunk */
 #define GPX_ROUTE_EXTEND         19   /* gpx_gp_extend / gpx_gp_extend_from_K: one hit per call                        */
 #define GPX_ROUTE_SAMPLE         20   /* gpx_gp_sample / gpx_gp_sample_from_K: one hit per call                        */
+#define GPX_ROUTE_KAPPLY_FUSED   21   /* gpx_d_kmat_apply: K(xo, x) V^T by the fused kernel, K never materialised; one hit per chunk */
+#define GPX_ROUTE_KAPPLY_GEMM    22   /* gpx_d_kmat_apply: gpx_d_kmat into scratch, then gpx_d_gemm_nt; one hit per row chunk of xo  */
 int gpx_debug_route_count(int route, int64_t *count);
 /* roctx ranges pushed so far (GPX_ROCTX=1: every gpx_gp_* call and every launch class below it is a nested host range for
  * `rocprofv3 --marker-trace`; libroctx64.so is loaded on first use; 0 while the switch is off) */
@@ -211,6 +215,12 @@ int gpx_debug_route_reset(void);
  * (one pass over `environ`; csrc/gpx_tune.h is the table of all of them); nothing below an entry point reads the
  * environment -- libgpx.so does not import getenv. */
 int gpx_debug_tune_refreshes(int64_t *count);
+/* GPX_KAPPLY_FUSED_MAX: the largest number of weight vectors S for which gpx_d_kmat_apply takes its fused route (defaults per
+ * dtype: csrc/gpx_tune.h, measured: DESIGN "Posterior paths").  The one switch that is a call and not an environment variable:
+ * value >= 0 sets it for the whole process and both dtypes (0: always the product route), value < 0 restores the defaults;
+ * *previous (may be NULL) receives the value that was in force, -1 for the defaults.  Like every switch it enters the calling
+ * thread's snapshot at the next entry point. */
+int gpx_debug_kapply_fused_max(int64_t value, int64_t *previous);
 /* The asm-scheduled MFMA leaf of the panel kernel (csrc/gpx_leaf.h) carries wait states measured on gfx950; before a process
  * first uses it on a device it is checked there against the compiler-scheduled leaf (full-mantissa 256 x 256 panel, alone and
  * beside a product that loads every matrix pipe).  *state: 0 not run yet, 1 passed, 2 failed -- the library then uses the
@@ -408,6 +418,31 @@ int gpx_d_mvn_sample(int dtype, void *C, int64_t m, int64_t ldc, const void *mea
                      uint64_t seed, uint64_t stream, void *Z, int64_t ldz, void *out, int64_t ldo,
                      int *info_dev, void *hipstream);
 
+/* Random Fourier features of a point set:  out[i, f] = scale cos(omega_f . p_i),  out[i, F + f] = scale sin(omega_f . p_i)
+ * for i < m, f < F.  pts: (m, d) densely packed in `dtype`; omega_dev: DEVICE DOUBLE (F, d) densely packed, for both dtypes;
+ * out: (m, 2F) with ld >= 2F in `dtype`; the padding [2F, ld) is not written.  The projection and the sincos are fp64 for
+ * both dtypes (the point as stored, converted exactly), the result is rounded once on the store.  One launch;
+ * GPX_PROF_RFF (bytes written). */
+int gpx_d_rff_features(int dtype, const void *pts, int64_t m, int d, const double *omega_dev, int64_t F, double scale,
+                       void *out, int64_t ld, void *stream);
+
+/* out[s, i] += sum_j K(xo_i, x_j) V[s, j]   for s < S, i < m:  the kernel matrix applied to S weight vectors at once,
+ * accumulated INTO out.  xo: (m, d), x: (n, d) densely packed; V: (S, n) ldv; out: (S, m) ldo; all DEVICE in `dtype`.
+ * Member GPX_K of GPX_KERNEL_GAUSSIAN and GPX_KERNEL_PERIODIC (any d gpx_d_mean takes); GPX_KERNEL_GAUSSIAN_ARD callers pass
+ * scaled points and the isotropic constants (gpx_d_scale_points).  Two routes:
+ *   fused (GPX_ROUTE_KAPPLY_FUSED; S <= GPX_KAPPLY_FUSED_MAX and d within gpx_d_mean's range): K(xo, x) is never
+ *     materialised.  A workgroup owns 4 test points and a slice of x streamed through LDS, every lane one training point and
+ *     a register block of 8 weight vectors (8 points and 1 or 4 vectors for S = 1 and S <= 4); each k(xo_i, x_j) -- the entry
+ *     function of gpx_d_kmat, underflow clamp included -- is formed once per group of vectors; f64 sums, slices added in ascending order by a second launch: no atomics,
+ *     bitwise repeatable.  GPX_PROF_KAPPLY.
+ *   product (GPX_ROUTE_KAPPLY_GEMM): row chunks of xo (a multiple of 128 rows): gpx_d_kmat into this host thread's scratch,
+ *     then gpx_d_gemm_nt(S, m_c, n, 1, V, ldv, K_c, ., out + r0, ldo).
+ * Both routes take any base and pitch of V and out (the product route's fast kernel wants V 16-byte aligned with ldv a multiple of
+ * 16 bytes and takes the generic one otherwise).
+ * m == 0, S == 0 or n == 0 leaves out as it is. */
+int gpx_d_kmat_apply(int dtype, int kernel, const void *xo, int64_t m, const void *x, int64_t n, int d,
+                     const double *params, const void *V, int64_t ldv, int64_t S, void *out, int64_t ldo, void *stream);
+
 /* ------------------------------------------------ fitted-GP device handle -- */
 /* One handle = one GP resident in HBM: x, y, the kernel matrix / its factor
  * (in place), alpha = K^-1 y, logdet, y^T alpha.  Mirrors the memoised
@@ -593,6 +628,44 @@ int gpx_gp_last_timing(gpx_gp_t *gp, float *ms5);
  * elements (row n is the handle's work row, see gpx_gp_last_timing) */
 int gpx_gp_device_ptrs(gpx_gp_t *gp, void **A, int64_t *lda, void **x, void **y,
                        void **alpha, void **stream);
+
+/* ------------------------------------------------------- posterior paths -- */
+/* S draws of the posterior FUNCTION (pathwise conditioning: Matheron's rule; Wilson et al. 2020), each one weight vector
+ * resident in HBM, to be evaluated at any number of points afterwards:
+ *   f_s(a) = phi(a) . Theta_s + sum_j k(a, x_j) V[s, j],    V_s = alpha - Kxx^-1 (Phi(x) Theta_s + sigma E_s)
+ * GPX_KERNEL_GAUSSIAN and GPX_KERNEL_GAUSSIAN_ARD only.  On the handle's view -- points p = x (Gaussian) or x / w (ARD),
+ * isotropic constants (h_v, w_v) = (h, w) or (h / sqrt(wbar), 1), k0 = h_v^2 / (w_v sqrt(2 pi)) -- and with z the sequence
+ * of gpx_d_randn (stream 0 stays gpx_gp_sample's):
+ *   Omega[f, k] = z(seed, 1, f d + k) / w_v     f < F, k < d    spectral frequencies, DOUBLE for both dtypes
+ *   Theta[s, q] = z(seed, 2, s 2F + q)          s < S, q < 2F   feature weights, handle dtype
+ *   E[s, j]     = z(seed, 3, s n + j)           j < n           the observation-noise draw; sigma = the GP's s
+ *   phi(a)      = sqrt(k0 / F) [cos(Omega a); sin(Omega a)]     (gpx_d_rff_features; no phase term)
+ * Row s of Theta and E depends on s alone: the random inputs of S' < S paths are a prefix of those of S.  The approximation
+ * lies in the prior only (covariance error O(k0 / sqrt(F))); the data update is exact.  The draws are of the LATENT function:
+ * observation noise is not added to the values.
+ * gpx_gp_paths_create: on the handle's stream -- Omega, Theta; R = sigma E; R += Theta Phi(x)^T in row chunks of x (a multiple
+ * of 128 rows: gpx_d_rff_features, then gpx_d_gemm_nt); R <- R L^-T; R <- R L^-1; V = alpha - R.  Synchronous.  The result
+ * owns Omega, Theta, V (S x lda), a copy of the view's points and the constants and never refers to `gp` again: `gp` may
+ * be refitted or destroyed, and is itself unchanged except for block operators completed as by any gpx_gp_cov.
+ * Preconditions and statuses of gpx_gp_sample (fitted, positive definite, finite y); GPX_ERR_UNSUPPORTED for the periodic
+ * family and for a handle fitted from gpx_gp_set_K; GPX_ERR_ARG for S < 0 or F < 1.  On failure *paths = NULL. */
+typedef struct gpx_paths gpx_paths_t;
+int gpx_gp_paths_create(gpx_gp_t *gp, int64_t S, int64_t F, uint64_t seed, gpx_paths_t **paths);
+/* f_s(xo_i) -> out (S, m) HOST float64, xo (m, d) HOST float64, in row chunks of xo (chunk_rows: 0 = automatic, else a
+ * multiple of 128; gpx_gp_var's contract).  Per chunk: upload (ARD: gpx_d_scale_points), gpx_d_rff_features,
+ * out_c = Theta Phi_c^T by gpx_d_gemm_nt into a zeroed block, gpx_d_kmat_apply, one download.  m == 0 and S == 0 are legal.
+ * The chunk's device buffers belong to the paths handle and only ever grow: repeated evaluations allocate once.  One host thread
+ * at a time per paths handle. */
+int gpx_paths_eval(gpx_paths_t *paths, const double *xo, int64_t m, int64_t chunk_rows, double *out);
+/* the state as HOST float64: omega (F, d), theta (S, 2F), V (S, n); any pointer may be NULL */
+int gpx_paths_get(gpx_paths_t *paths, double *omega, double *theta, double *V);
+/* any pointer may be NULL; kernel: the family of the GP the paths came from */
+int gpx_paths_describe(gpx_paths_t *paths, int *dtype, int *kernel, int64_t *n, int *d, int64_t *S, int64_t *F, uint64_t *seed);
+/* diagnostic (tools/paths_probe.py): how long gpx_gp_paths_create took, milliseconds (HIP events on the source's stream): [0]
+ * features + products (R += Theta Phi(x)^T) [1] the two sweeps [2] the rest (generators, the copy of the points, V = alpha - R)
+ * [3] total; zeros for S == 0 */
+int gpx_debug_paths_timing(gpx_paths_t *paths, float *ms4);
+int gpx_paths_destroy(gpx_paths_t *paths);
 
 /* ------------------------------------------------------------- multi-GPU -- */
 /* One GP spread over the GPUs of a node, one PROCESS per GPU (north-star; SURVEY 8e -- the reference has
