@@ -116,8 +116,14 @@ struct ProfScope {
     ~ProfScope() { if (rec >= 0) prof_end(rec, st); }
 };
 
-// hipFuncAttributeMaxDynamicSharedMemorySize, once per (kernel, device); thread-safe
+// hipFuncAttributeMaxDynamicSharedMemorySize, once per (kernel, device); thread-safe.  Once: so `bytes` is a constant of the
+// kernel, never the size one call happens to need -- LDS_CHUNK_MAX for the kernels that stage a chunk of points and refuse a
+// d beyond it (kmat, the streamed kernels), LDS_TILE_MAX for the tile reductions, which do not: the CU's 160 KiB less 4 KiB
+// for their static reduction slots (the limit counts dynamic bytes only; a launch beyond it is a HIP launch error).  Through a
+// fitted handle kmat's own range of d keeps them below 48 KiB; called with a larger d, fp64 d = 156 .. 158 would have launched
+// with the call's exact size as the limit and does not with this constant
 int set_max_lds(const void *fn, int bytes);
+constexpr int LDS_CHUNK_MAX = 96 * 1024, LDS_TILE_MAX = 156 * 1024;
 
 // Makes `device` current for the calling host thread and restores the previous one on scope
 // exit (HIP's current device is per host thread; handles remember the device they live on).
@@ -234,7 +240,7 @@ int trsm_right_lt(int dtype, const void *L, int64_t n, int64_t ldl, void *X, int
 // (or where trsm_ops_ok says no) the 64-wide route.  Scratch: the transposed row panels of L, at most n x TRSV_OPS_BLOCK.
 int trsm_right_l(int dtype, const void *L, int64_t n, int64_t ldl, void *X, int64_t m, int64_t ldx, hipStream_t st,
                  TrsvOps *ops = nullptr);
-// Input-space gradient pass (gpx_kmat.hip): gpx_d_pred_grad's arguments on GPX_KERNEL_GAUSSIAN / GPX_KERNEL_PERIODIC points;
+// Input-space gradient pass (gpx_stream.hip): gpx_d_pred_grad's arguments on GPX_KERNEL_GAUSSIAN / GPX_KERNEL_PERIODIC points;
 // col_div (HOST, d doubles, or null): column k of the result is divided by col_div[k] (the ARD family on scaled points).
 int pred_grad(int dtype, int kernel, const void *xo, int64_t m, const void *x, int64_t n, int d, const double *params,
               const void *alpha, const void *B, int64_t ldb, double scale, const double *col_div, double *out_dev, hipStream_t st);
@@ -272,7 +278,11 @@ int randn(int dtype, void *out, int64_t rows, int64_t cols, int64_t ld, uint64_t
 int mvn_sample(int dtype, void *C, int64_t m, int64_t ldc, const void *mean, double jitter, int64_t S, uint64_t seed, uint64_t stream,
                void *Z, int64_t ldz, void *out, int64_t ldo, int *info_dev, hipStream_t st);
 // Posterior paths (gpx_paths.hip).  rff_features: gpx_d_rff_features' arguments.  kmat_apply: gpx_d_kmat_apply's (the caller
-// holds the StreamTurn: both routes use this host thread's scratch).
+// holds the StreamTurn: both routes use this host thread's scratch).  kapply_fused: its fused route (gpx_stream.hip) for a
+// (d, S) that kapply_fused_fits takes; kp: member GPX_K of GPX_KERNEL_GAUSSIAN or GPX_KERNEL_PERIODIC.
+bool kapply_fused_fits(int dtype, int d, int64_t S);
+int kapply_fused(int dtype, const void *xo, int64_t m, const void *x, int64_t n, int d, const KParams &kp, const void *V, int64_t ldv,
+                 int64_t S, void *out, int64_t ldo, hipStream_t st);
 int rff_features(int dtype, const void *pts, int64_t m, int d, const double *omega_dev, int64_t F, double scale, void *out, int64_t ld,
                  hipStream_t st);
 int kmat_apply(int dtype, int kernel, const void *xo, int64_t m, const void *x, int64_t n, int d, const double *params, const void *V,
@@ -287,7 +297,9 @@ int dloglh_reduce(int dtype, int kernel, const void *x, int64_t n, int d, const 
 // The Gaussian ARD family (gpx_kmat.hip): out <- x / w (w_host: d doubles; out may be x); the gradient's pass over W = K^-1
 // on the scaled points xs with iso = (h / sqrt(wbar), 1): out (host, d + 2) = [S_0, S_1 .. S_d, trace W].
 // dloglh_partial_doubles: the DEVICE doubles either reduction needs for its per-workgroup partial sums.
+struct ArdWidths { double w[GPX_ARD_MAX_D]; };   // the widths as a kernel argument
 int scale_points(int dtype, const void *x, int64_t n, int d, const double *w_host, void *out, hipStream_t st);
+int ard_scratch(size_t bytes, void **p);         // this host thread's block for the scaled copies of a call's two point sets
 // (h / sqrt(wbar), 1) of ARD parameters (h, w_1 ... w_d): wbar = exp(sum log w_k / d) in the host's double arithmetic
 void ard_iso(const double *params, int d, double *iso2);
 size_t dloglh_partial_doubles(int kernel, int d);

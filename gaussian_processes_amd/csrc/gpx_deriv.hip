@@ -67,10 +67,8 @@ __global__ __launch_bounds__(256) void member_quad_trace_kernel(const T *__restr
     for (int p = 0; p < DR_MAXM; ++p) { accq[p] = 0.0; acch[p] = 0.0; }
     const int64_t total = ntiles * (ntiles + 1) / 2;
     for (int64_t t = blockIdx.x; t < total; t += gridDim.x) {
-        int64_t tr = (int64_t)((sqrt(8.0 * (double)t + 1.0) - 1.0) * 0.5);
-        while ((tr + 1) * (tr + 2) / 2 <= t) ++tr;
-        while (tr * (tr + 1) / 2 > t) --tr;
-        const int64_t tc = t - tr * (tr + 1) / 2;
+        int64_t tr, tc;
+        tri_tile(t, &tr, &tc);
         const int64_t r0 = tr * DR_T, c0 = tc * DR_T;
         __syncthreads();
         for (int idx = tid; idx < DR_T * d; idx += 256) {
@@ -112,6 +110,7 @@ __global__ __launch_bounds__(256) void member_quad_trace_kernel(const T *__restr
             }
         }
     }
+    // (block_sum_fixed's text with a member's two sums interleaved, as written before the helper: 22 fewer instructions)
 #pragma unroll
     for (int p = 0; p < DR_MAXM; ++p) {
         double vq = accq[p], vh = acch[p];
@@ -119,8 +118,7 @@ __global__ __launch_bounds__(256) void member_quad_trace_kernel(const T *__restr
         if ((tid & 63) == 0) { red[tid >> 6][2 * p] = vq; red[tid >> 6][2 * p + 1] = vh; }
     }
     __syncthreads();
-    if (tid < 2 * DR_MAXM)
-        partial[(int64_t)blockIdx.x * (2 * DR_MAXM) + tid] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
+    if (tid < 2 * DR_MAXM) partial[(int64_t)blockIdx.x * (2 * DR_MAXM) + tid] = block_sum_final(red, tid);
 }
 
 // sum_ab A[a, b] * B[b, a] = trace(A B) for two n x n matrices: 64 x 64 tiles, B's tile transposed
@@ -131,7 +129,7 @@ __global__ __launch_bounds__(256) void trace_prod_kernel(const T *__restrict__ A
                                                          int64_t ntiles, double *__restrict__ partial)
 {
     __shared__ T sB[DR_T][DR_T + 1];
-    __shared__ double red[4];
+    __shared__ double red[4][1];
     const int tid = threadIdx.x, col = tid & 63, rg = tid >> 6;
     double acc = 0.0;
     const int64_t total = ntiles * ntiles;
@@ -150,10 +148,10 @@ __global__ __launch_bounds__(256) void trace_prod_kernel(const T *__restrict__ A
                 acc = fma((double)A[(a0 + r) * lda + b0 + col], (double)sB[col][r], acc);
         }
     }
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
-    if ((tid & 63) == 0) red[tid >> 6] = acc;
+    const double acc1[1] = {acc};
+    block_sum_fixed(acc1, red, tid);
     __syncthreads();
-    if (tid == 0) partial[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
+    if (tid == 0) partial[blockIdx.x] = block_sum_final(red, 0);
 }
 
 // out[0] = sum_i a[i * stride]  (trace of a matrix: stride = ld + 1); single workgroup, fixed order
@@ -366,9 +364,7 @@ static int d2lh_t(gpx_gp *g, double *dlh_out, double *d2lh_out, double *d2loglh_
         const int64_t ntr = ntl;
         const int blocks = (int)std::min<int64_t>(DR_BLOCKS, ntr * (ntr + 1) / 2);
         const size_t smem = ((size_t)2 * DR_T * g->d + 2 * DR_T) * sizeof(T);
-        if (smem > 48 * 1024)
-            GPX_HIP(hipFuncSetAttribute((const void *)member_quad_trace_kernel<T>,
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+        if (smem > 48 * 1024) GPX_TRY(set_max_lds((const void *)member_quad_trace_kernel<T>, LDS_TILE_MAX));
         hipLaunchKernelGGL((member_quad_trace_kernel<T>), dim3(blocks), dim3(256), smem, st, (const T *)g->x, n, g->d,
                            (const T *)g->alpha, (const T *)D.W.p, lda, ml, ntr, (double *)D.part.p);
         GPX_LAUNCH_CHECK();

@@ -1,4 +1,4 @@
-// gpx_kmat.hip -- pairwise kernel-matrix build and fused posterior mean (gfx950).
+// gpx_kmat.hip -- pairwise kernel-matrix build, ARD scaling and the hyper-parameter gradient reductions (gfx950).
 //
 // Replaces the O(n*m) double loops of gp/ext/gaussian_c.pyx:18-164 and
 // gp/ext/periodic_c.pyx:18-235 (one exp per entry, single CPU thread) and the
@@ -79,6 +79,7 @@ __global__ __launch_bounds__(256) void kmat_kernel(const T *__restrict__ x1, int
     // rblk: row blocks of KM_ROWS per workgroup.  The column points are staged (transposed) ONCE and serve rblk row
     // blocks (round 6: one block per workgroup paid the 32 KB staging pass and its barrier per 64 rows, and half of
     // the 524 k workgroups of a lower-only N = 65536 build existed only to find themselves above the diagonal)
+    constexpr int KIND = MODE == 3 ? GPX_KERNEL_PERIODIC : GPX_KERNEL_GAUSSIAN;   // the pair term (MODE 4 forms none)
     constexpr int VEC = Vec<T>::N;
     constexpr int TN = 64 * VEC;
     constexpr int TNP = TN + VEC;                     // padded row of s2: the transposing stores below
@@ -102,13 +103,9 @@ __global__ __launch_bounds__(256) void kmat_kernel(const T *__restrict__ x1, int
             for (int idx = tid; idx < KM_ROWS * d; idx += 256) s1[idx] = (idx < lim1) ? g1[idx] : (T)0;
         const int64_t lim2 = (m - col0) * d;
         const T *g2 = x2 + col0 * d;
-        const int qd = 256 / d, rd = 256 - qd * d;    // idx += 256  <=>  (c, k) += (qd, rd) with carry
-        int c = tid / d, k = tid - c * d;
-        for (int idx = tid; idx < TN * d; idx += 256) {
-            s2[(size_t)k * TNP + c] = (idx < lim2) ? g2[idx] : (T)0;
-            c += qd; k += rd;
-            if (k >= d) { k -= d; ++c; }
-        }
+        const int qd = 256 / d, rd = 256 - qd * d;
+        const int cst = tid / d, kst = tid - cst * d;
+        GPX_STAGE_POINTS_TRANSPOSED(s2, TNP, g2, TN * d, lim2, d, tid, qd, rd, cst, kst);
     }
     __syncthreads();
 
@@ -159,15 +156,7 @@ __global__ __launch_bounds__(256) void kmat_kernel(const T *__restrict__ x1, int
                 for (int r = 0; r < KM_RB; ++r) {
                     const T a = arow[r][k];
 #pragma unroll
-                    for (int v = 0; v < VEC; ++v) {
-                        if (MODE == 3) {
-                            const T sn = sin((T)0.5 * (a - b[v]) / (T)kp.c[2]);
-                            acc[r][v] = fma(sn, sn, acc[r][v]);
-                        } else {
-                            const T t = a - b[v];
-                            acc[r][v] = fma(t, t, acc[r][v]);
-                        }
-                    }
+                    for (int v = 0; v < VEC; ++v) acc[r][v] = pair_term<T, KIND>(a, b[v], (T)kp.c[2], acc[r][v]);
                 }
             }
         }
@@ -185,8 +174,7 @@ __global__ __launch_bounds__(256) void kmat_kernel(const T *__restrict__ x1, int
                     if (MODE <= 2) {
                         pv[v] = gaussian_entry<T, MODE>(acc[r][v], c1, c2, c3, c4);
                     } else if (MODE == 3) {
-                        const T h = (T)kp.c[0], w = (T)kp.c[1];
-                        pv[v] = (h * h) * dev_exp<T>((T)-2.0 * acc[r][v] / (w * w));
+                        pv[v] = periodic_k<T>(acc[r][v], (T)kp.c[0], (T)kp.c[1]);
                     } else {
                         pv[v] = periodic_entry<T>(kp.member, acc[r][v], (T)kp.c[0], (T)kp.c[1], (T)kp.c[2]);
                     }
@@ -206,8 +194,7 @@ __global__ __launch_bounds__(256) void kmat_kernel(const T *__restrict__ x1, int
                 if (MODE <= 2) {
                     x = gaussian_entry<T, MODE>(acc[r][v], c1, c2, c3, c4);
                 } else if (MODE == 3) {
-                    const T h = (T)kp.c[0], w = (T)kp.c[1];
-                    x = (h * h) * dev_exp<T>((T)-2.0 * acc[r][v] / (w * w));
+                    x = periodic_k<T>(acc[r][v], (T)kp.c[0], (T)kp.c[1]);
                 } else {
                     x = periodic_entry<T>(kp.member, acc[r][v], (T)kp.c[0], (T)kp.c[1], (T)kp.c[2]);
                 }
@@ -243,7 +230,7 @@ static int launch_kmat(const void *x1, int64_t n, const void *x2, int64_t m, int
         return GPX_ERR_UNSUPPORTED;
     }
     const size_t smem = ((mode == 4 ? (size_t)KM_ROWS * d : (size_t)0) + (size_t)d * (TN + VEC)) * sizeof(T);
-    if (smem > 96 * 1024) {
+    if (smem > (size_t)LDS_CHUNK_MAX) {
         set_error("kmat: d = %d too large for the LDS-staged tile (96 KiB of column points)", d);
         return GPX_ERR_UNSUPPORTED;
     }
@@ -268,9 +255,7 @@ static int launch_kmat(const void *x1, int64_t n, const void *x2, int64_t m, int
     ProfScope prof(PC_KMAT, bytes, st);
 #define GPX_KM_LAUNCH(MODE)                                                                   \
     do {                                                                                      \
-        if (smem > 48 * 1024)                                                                 \
-            GPX_HIP(hipFuncSetAttribute((const void *)kmat_kernel<T, MODE>,                   \
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem)); \
+        if (smem > 48 * 1024) GPX_TRY(set_max_lds((const void *)kmat_kernel<T, MODE>, LDS_CHUNK_MAX)); \
         hipLaunchKernelGGL((kmat_kernel<T, MODE>), grid, block, smem, st, a, n, b, m, d, kp,  \
                            tri, aligned, o, ld, rblk);                                        \
     } while (0)
@@ -293,8 +278,6 @@ static int launch_kmat(const void *x1, int64_t n, const void *x2, int64_t m, int
 // is the correctly rounded quotient, numpy's x / w bit for bit).  In place is fine: a thread reads an element before
 // it writes it and nobody else touches it.
 // ---------------------------------------------------------------------------
-struct ArdWidths { double w[GPX_ARD_MAX_D]; };
-
 template <typename T>
 __global__ __launch_bounds__(256) void scale_points_kernel(const T *x, int64_t n, int d, ArdWidths aw, T *out)
 {
@@ -324,391 +307,8 @@ int scale_points(int dtype, const void *x, int64_t n, int d, const double *w_hos
     return GPX_OK;
 }
 
-// ---------------------------------------------------------------------------
-// fused posterior mean: out[i] = sum_j K(xo[i], x[j]) * alpha[j]   (gp/gp.py:597)
-// Workgroup (bx, by) owns MP test points and the by-th slice of the training set,
-// which streams through LDS in chunks of 256 points (one per thread, transposed and
-// padded so both the staging stores and the reads are conflict-free).  Sums are
-// kept in f64; a slice's partial sums go to `partial[by][i]` and a second launch
-// adds the slices in a fixed order (deterministic: no atomics).
-// ---------------------------------------------------------------------------
-constexpr int MP = 8;
-constexpr int MCP = 257;           // padded chunk row
-
-// KIND: kernel family; FORM: gaussian member form 0..2 (see gaussian_entry), or for the periodic family
-// 0 = K for any d, 1 = any member at d == 1 (kp.member) -- out = member(xo, x) @ alpha.
-template <typename T, int KIND, int FORM>
-__global__ __launch_bounds__(256) void mean_kernel(const T *__restrict__ xo, int64_t m,
-                                                   const T *__restrict__ x, int64_t n, int d,
-                                                   KParams kp, const T *__restrict__ alpha,
-                                                   int64_t slice_len, double *__restrict__ partial,
-                                                   T *__restrict__ out)
-{
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    T *sx = reinterpret_cast<T *>(smem_raw);            // [d][MCP] chunk of x, transposed
-    __shared__ double red[4][MP];
-
-    const int tid = threadIdx.x;
-    const int64_t p0 = (int64_t)blockIdx.x * MP;
-    double acc[MP];
-#pragma unroll
-    for (int pp = 0; pp < MP; ++pp) acc[pp] = 0.0;
-    const T *orow[MP];
-#pragma unroll
-    for (int pp = 0; pp < MP; ++pp) orow[pp] = xo + min(p0 + pp, m - 1) * d;
-
-    const T c1 = (T)kp.c[0], c2 = (T)kp.c[1], c3 = (T)kp.c[2], c4 = (T)kp.c[3];
-    const int qd = 256 / d, rd = 256 - qd * d;          // idx += 256  <=>  (c, k) += (qd, rd) with carry
-    const int cst = tid / d, kst = tid - cst * d;
-    const int64_t jbeg = (int64_t)blockIdx.y * slice_len, jend = min(n, jbeg + slice_len);
-    for (int64_t j0 = jbeg; j0 < jend; j0 += 256) {
-        __syncthreads();
-        {
-            const int64_t lim = (jend - j0) * d;
-            const T *g = x + j0 * d;
-            int c = cst, k = kst;
-            for (int idx = tid; idx < 256 * d; idx += 256) {
-                sx[(size_t)k * MCP + c] = (idx < lim) ? g[idx] : (T)0;
-                c += qd; k += rd;
-                if (k >= d) { k -= d; ++c; }
-            }
-        }
-        __syncthreads();
-        const int64_t j = j0 + tid;
-        if (j < jend) {
-            const T aj = alpha[j];
-            T r[MP];
-#pragma unroll
-            for (int pp = 0; pp < MP; ++pp) r[pp] = (T)0;
-            // (the test points are the same for every lane: SGPR operands through the scalar cache, as in kmat_kernel)
-            for (int k = 0; k < d; ++k) {
-                const T b = sx[(size_t)k * MCP + tid];
-#pragma unroll
-                for (int pp = 0; pp < MP; ++pp) {
-                    const T a = orow[pp][k];
-                    if (KIND == GPX_KERNEL_GAUSSIAN) {
-                        const T t = a - b;
-                        r[pp] = fma(t, t, r[pp]);
-                    } else if (FORM == 1) {
-                        r[pp] = a - b;                                // d == 1: the signed difference
-                    } else {
-                        const T sn = sin((T)0.5 * (a - b) / (T)kp.c[2]);
-                        r[pp] = fma(sn, sn, r[pp]);
-                    }
-                }
-            }
-#pragma unroll
-            for (int pp = 0; pp < MP; ++pp) {
-                T kv;
-                if (KIND == GPX_KERNEL_GAUSSIAN) {
-                    kv = gaussian_entry<T, FORM>(r[pp], c1, c2, c3, c4);
-                } else if (FORM == 1) {
-                    kv = periodic_entry<T>(kp.member, r[pp], (T)kp.c[0], (T)kp.c[1], (T)kp.c[2]);
-                } else {
-                    const T h = (T)kp.c[0], w = (T)kp.c[1];
-                    kv = (h * h) * dev_exp<T>((T)-2.0 * r[pp] / (w * w));
-                }
-                acc[pp] += (double)kv * (double)aj;
-            }
-        }
-    }
-    // wave reduction (64 lanes), then across the 4 waves in a fixed order
-#pragma unroll
-    for (int pp = 0; pp < MP; ++pp) {
-        double v = acc[pp];
-        for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-        if ((tid & 63) == 0) red[tid >> 6][pp] = v;
-    }
-    __syncthreads();
-    if (tid < MP && p0 + tid < m) {
-        const double sum = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
-        if (partial) partial[(int64_t)blockIdx.y * m + p0 + tid] = sum;
-        else out[p0 + tid] = (T)sum;
-    }
-}
-
-template <typename T>
-__global__ void mean_reduce_kernel(const double *__restrict__ partial, int nslice, int64_t m, T *__restrict__ out)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= m) return;
-    double sum = 0.0;
-    for (int y = 0; y < nslice; ++y) sum += partial[(int64_t)y * m + i];
-    out[i] = (T)sum;
-}
-
-static thread_local ThreadScratch g_mean_scr;   // the slice partial sums
-static thread_local ThreadScratch g_ard_scr;    // gpx_d_kmat on the ARD family: the scaled copies of its two point sets
-
-template <typename T>
-static int launch_mean(int kernel, const void *xo, int64_t m, const void *x, int64_t n, int d,
-                       const KParams &kp, const void *alpha, void *out, hipStream_t st)
-{
-    const size_t smem = (size_t)d * MCP * sizeof(T);
-    if (smem > 96 * 1024) {
-        set_error("mean: d = %d too large", d);
-        return GPX_ERR_UNSUPPORTED;
-    }
-    // enough workgroups to fill the chip: slices of the training set when m alone is too small
-    const int64_t gx = cdiv(m, MP);
-    int64_t nslice = std::max<int64_t>(1, std::min<int64_t>(cdiv(2048, gx), cdiv(n, 256)));
-    const int64_t slice_len = cdiv(cdiv(n, nslice), 256) * 256;
-    nslice = cdiv(n, slice_len);
-    double *partial = nullptr;
-    if (nslice > 1) {
-        void *scr = nullptr;
-        GPX_TRY(g_mean_scr.get((size_t)nslice * m * sizeof(double), &scr));
-        partial = (double *)scr;
-    }
-    dim3 grid((unsigned)gx, (unsigned)nslice), block(256);
-    ProfScope prof(PC_MEAN, (double)m * n, st);
-#define GPX_MEAN_LAUNCH(KIND, FORM)                                                                 \
-    do {                                                                                            \
-        if (smem > 48 * 1024)                                                                       \
-            GPX_HIP(hipFuncSetAttribute((const void *)mean_kernel<T, KIND, FORM>,                   \
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));    \
-        hipLaunchKernelGGL((mean_kernel<T, KIND, FORM>), grid, block, smem, st, (const T *)xo, m,   \
-                           (const T *)x, n, d, kp, (const T *)alpha, slice_len, partial, (T *)out); \
-    } while (0)
-    if (kernel == GPX_KERNEL_GAUSSIAN) {
-        switch ((int)kp.c[4]) {
-        case 0: GPX_MEAN_LAUNCH(GPX_KERNEL_GAUSSIAN, 0); break;
-        case 1: GPX_MEAN_LAUNCH(GPX_KERNEL_GAUSSIAN, 1); break;
-        default: GPX_MEAN_LAUNCH(GPX_KERNEL_GAUSSIAN, 2); break;
-        }
-    } else if (kp.member == GPX_K) {
-        GPX_MEAN_LAUNCH(GPX_KERNEL_PERIODIC, 0);
-    } else {
-        if (d != 1) { set_error("periodic derivative members need d == 1 (got %d)", d); return GPX_ERR_UNSUPPORTED; }
-        GPX_MEAN_LAUNCH(GPX_KERNEL_PERIODIC, 1);
-    }
-#undef GPX_MEAN_LAUNCH
-    if (partial)
-        hipLaunchKernelGGL((mean_reduce_kernel<T>), dim3((unsigned)cdiv(m, 256)), dim3(256), 0, st, partial,
-                           (int)nslice, m, (T *)out);
-    GPX_LAUNCH_CHECK();
-    return GPX_OK;
-}
-
-// ---------------------------------------------------------------------------
-// Fused input-space gradient of a prediction:
-//   out[i, k] = scale * sum_j w_ij * dk(xo_i, x_j)/dxo_ik,    w_ij = alpha[j]  (the mean)  or  B[i * ldb + j]  (a solved chunk)
-//   gaussian  dk/da_k = -(a_k - b_k) / w^2 * k           periodic  dk/da_k = -sin((a_k - b_k) / p) / (p w^2) * k
-// mean_kernel's shape: workgroup (bx, by, bz) owns PTS test points, the by-th slice of the training set -- streamed through
-// LDS in chunks of 256 points, one per lane -- and the bz-th window of DP dimensions.  Per pair the lane forms the
-// distance over ALL d dimensions once, k_ij once (the entry function of kmat_kernel, clamp included: a clamped pair adds
-// exactly 0), g = w_ij k_ij in f64, and then for each dimension of the window the difference a_k - b_k itself (never
-// xo_ik sum_j g - sum_j g x_jk, which cancels far from the origin) times g into one of PTS x DP f64 accumulators: that per-lane
-// state is what the brackets bound, PTS * DP = PG_ACC = 16 -- d <= 4: DP = 4, 4 points; else DP = 16, 1 point; d > 16 takes cdiv(d, 16) windows,
-// each of which evaluates k again.  For the distance the test points are wave-uniform SGPR operands (scalar cache).  Lanes are
-// added by shuffles, waves through LDS, slices by pred_grad_reduce_kernel, all in a fixed order: no atomics, bitwise repeatable.
-// ---------------------------------------------------------------------------
-constexpr int PG_ACC = 16;         // f64 accumulators per lane
-template <typename T> __device__ __forceinline__ void dev_sincos(T x, T *s, T *c);
-template <> __device__ __forceinline__ void dev_sincos<double>(double x, double *s, double *c) { sincos(x, s, c); }
-template <> __device__ __forceinline__ void dev_sincos<float>(float x, float *s, float *c) { sincosf(x, s, c); }
-
-template <typename T, int KIND, int DP>
-__global__ __launch_bounds__(256) void pred_grad_kernel(const T *__restrict__ xo, int64_t m, const T *__restrict__ x, int64_t n,
-                                                        int d, KParams kp, const T *__restrict__ alpha, const T *__restrict__ B,
-                                                        int64_t ldb, int64_t slice_len, double *__restrict__ partial)
-{
-    constexpr int PTS = PG_ACC / DP;
-    constexpr int KU = KIND == GPX_KERNEL_GAUSSIAN ? 2 : 1;   // unrolling of the distance loop (periodic: ONE inlined sincos)
-    static_assert(KIND == GPX_KERNEL_GAUSSIAN || PTS == 1, "the periodic pass reuses the lane's slot of the chunk");
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    T *sx = reinterpret_cast<T *>(smem_raw);            // [d][MCP] chunk of x, transposed
-    __shared__ double red[4][PTS * DP];
-
-    const int tid = threadIdx.x;
-    const int64_t p0 = (int64_t)blockIdx.x * PTS;
-    const int kbeg = (int)blockIdx.z * DP;              // this workgroup's window of dimensions
-    double acc[PTS][DP];
-#pragma unroll
-    for (int pp = 0; pp < PTS; ++pp)
-#pragma unroll
-        for (int kk = 0; kk < DP; ++kk) acc[pp][kk] = 0.0;
-    const T *brow[PTS];
-#pragma unroll
-    for (int pp = 0; pp < PTS; ++pp) brow[pp] = B ? B + min(p0 + pp, m - 1) * ldb : alpha;   // (alpha: the same weights for every point)
-
-    // this window's coordinates of the test points live in VECTOR registers (staged through LDS): as SGPR operands like the
-    // rest of the point they are PG_ACC loop invariants on top of the pointers and constants, more than the scalar file holds
-    T *sa = sx + (size_t)d * MCP;                       // [PTS][d]
-    for (int idx = tid; idx < PTS * d; idx += 256) {
-        const int pp = PTS == 1 ? 0 : idx / d;
-        sa[idx] = xo[min(p0 + pp, m - 1) * d + (idx - pp * d)];
-    }
-    __syncthreads();
-    T av[PTS][DP];
-#pragma unroll
-    for (int pp = 0; pp < PTS; ++pp)
-#pragma unroll
-        for (int kk = 0; kk < DP; ++kk) av[pp][kk] = (kbeg + kk < d) ? sa[pp * d + kbeg + kk] : (T)0;
-
-    // gaussian: c1, c2 of gaussian_entry; periodic: h^2, -2 / w^2, p
-    const T c1 = KIND == GPX_KERNEL_GAUSSIAN ? (T)kp.c[0] : (T)kp.c[0] * (T)kp.c[0];
-    const T c2 = KIND == GPX_KERNEL_GAUSSIAN ? (T)kp.c[1] : (T)-2.0 / ((T)kp.c[1] * (T)kp.c[1]);
-    const T per = (T)kp.c[2];
-    const int qd = 256 / d, rd = 256 - qd * d;          // idx += 256  <=>  (c, k) += (qd, rd) with carry
-    const int cst = tid / d, kst = tid - cst * d;
-    const int64_t jbeg = (int64_t)blockIdx.y * slice_len, jend = min(n, jbeg + slice_len);
-    for (int64_t j0 = jbeg; j0 < jend; j0 += 256) {
-        __syncthreads();
-        {
-            const int64_t lim = (jend - j0) * d;
-            const T *g = x + j0 * d;
-            int c = cst, k = kst;
-            for (int idx = tid; idx < 256 * d; idx += 256) {
-                sx[(size_t)k * MCP + c] = (idx < lim) ? g[idx] : (T)0;
-                c += qd; k += rd;
-                if (k >= d) { k -= d; ++c; }
-            }
-        }
-        __syncthreads();
-        const int64_t j = j0 + tid;
-        if (j < jend) {
-            T r[PTS];
-#pragma unroll
-            for (int pp = 0; pp < PTS; ++pp) r[pp] = (T)0;
-#pragma unroll KU
-            for (int k = 0; k < d; ++k) {
-                const T b = sx[(size_t)k * MCP + tid];
-#pragma unroll
-                for (int pp = 0; pp < PTS; ++pp) {
-                    const T a = sa[pp * d + k];
-                    if (KIND == GPX_KERNEL_GAUSSIAN) {
-                        const T t = a - b;
-                        r[pp] = fma(t, t, r[pp]);
-                    } else {
-                        // PTS == 1: the lane's slot of the chunk is its own from here on, and takes sin((a - b) / p) =
-                        // 2 sin cos of the half angle for the pass below -- one sincos per pair and dimension
-                        T sn, cs;
-                        dev_sincos<T>((T)0.5 * (a - b) / per, &sn, &cs);
-                        r[pp] = fma(sn, sn, r[pp]);
-                        sx[(size_t)k * MCP + tid] = (T)2.0 * sn * cs;
-                    }
-                }
-            }
-            double g[PTS];
-#pragma unroll
-            for (int pp = 0; pp < PTS; ++pp) {
-                const T kv = KIND == GPX_KERNEL_GAUSSIAN ? gaussian_entry<T, 0>(r[pp], c1, c2, (T)0, (T)0)
-                                                          : c1 * dev_exp<T>(c2 * r[pp]);
-                const T wv = brow[pp][j];
-                g[pp] = (double)kv * (double)wv;
-            }
-#pragma unroll
-            for (int kk = 0; kk < DP; ++kk) {
-                if (kbeg + kk < d) {                                      // (uniform: d and the window are scalars)
-                    const T b = sx[(size_t)(kbeg + kk) * MCP + tid];
-#pragma unroll
-                    for (int pp = 0; pp < PTS; ++pp) {
-                        const T f = KIND == GPX_KERNEL_GAUSSIAN ? av[pp][kk] - b : b;
-                        acc[pp][kk] = fma(g[pp], (double)f, acc[pp][kk]);
-                    }
-                }
-            }
-        }
-    }
-    // wave reduction (64 lanes), then across the 4 waves in a fixed order
-#pragma unroll
-    for (int pp = 0; pp < PTS; ++pp)
-#pragma unroll
-        for (int kk = 0; kk < DP; ++kk) {
-            double v = acc[pp][kk];
-            for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-            if ((tid & 63) == 0) red[tid >> 6][pp * DP + kk] = v;
-        }
-    __syncthreads();
-    if (tid < PTS * DP) {
-        const int pp = tid / DP, kk = tid - pp * DP;
-        if (p0 + pp < m && kbeg + kk < d)
-            partial[((int64_t)blockIdx.y * m + p0 + pp) * d + kbeg + kk] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
-    }
-}
-
-// out[i, k] = factor * sum over the slices (in slice order) [/ div.w[k]]
-template <bool DIV>
-__global__ void pred_grad_reduce_kernel(const double *__restrict__ partial, int nslice, int64_t md, int d, double factor,
-                                        ArdWidths div, double *__restrict__ out)
-{
-    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= md) return;
-    double sum = 0.0;
-    for (int y = 0; y < nslice; ++y) sum += partial[(int64_t)y * md + e];
-    sum *= factor;
-    if (DIV) sum /= div.w[e % d];
-    out[e] = sum;
-}
-
-static thread_local ThreadScratch g_pgrad_scr;  // the slice partial sums of the gradient pass
-
-template <typename T>
-static int launch_pred_grad(int kernel, const void *xo, int64_t m, const void *x, int64_t n, int d, const KParams &kp,
-                            const void *alpha, const void *B, int64_t ldb, double scale, const double *col_div, double *out,
-                            hipStream_t st)
-{
-    if ((size_t)d * MCP * sizeof(T) > 96 * 1024) {        // launch_mean's range of d
-        set_error("pred_grad: d = %d too large", d);
-        return GPX_ERR_UNSUPPORTED;
-    }
-    if (col_div && d > GPX_ARD_MAX_D) { set_error("pred_grad: column divisors need d <= %d (got %d)", GPX_ARD_MAX_D, d); return GPX_ERR_ARG; }
-    const int DP = (d <= 4 && kernel == GPX_KERNEL_GAUSSIAN) ? 4 : 16, PTS = PG_ACC / DP;   // (periodic: one point a workgroup)
-    const size_t smem = (size_t)d * (MCP + PTS) * sizeof(T);   // the chunk of x and the group's test points
-    const int64_t gx = cdiv(m, PTS), gz = cdiv(d, DP);
-    // enough workgroups to fill the chip: slices of the training set when m alone is too small (launch_mean's rule)
-    int64_t nslice = std::max<int64_t>(1, std::min<int64_t>(cdiv(2048, gx * gz), cdiv(n, 256)));
-    const int64_t slice_len = cdiv(cdiv(n, nslice), 256) * 256;
-    nslice = cdiv(n, slice_len);
-    void *scr = nullptr;
-    GPX_TRY(g_pgrad_scr.get((size_t)nslice * m * d * sizeof(double), &scr));
-    double *partial = (double *)scr;
-    // the derivative's constant: gaussian -1 / w^2 = 2 c1, periodic -1 / (p w^2)
-    const double factor = scale * (kernel == GPX_KERNEL_GAUSSIAN ? 2.0 * kp.c[0] : -1.0 / (kp.c[2] * kp.c[1] * kp.c[1]));
-    ArdWidths aw;
-    for (int k = 0; k < GPX_ARD_MAX_D; ++k) aw.w[k] = (col_div && k < d) ? col_div[k] : 1.0;
-    dim3 grid((unsigned)gx, (unsigned)nslice, (unsigned)gz), block(256);
-    ProfScope prof(PC_PRED_GRAD, (double)m * n * gz, st);
-#define GPX_PGRAD_LAUNCH(KIND, DPV)                                                                       \
-    do {                                                                                                  \
-        if (smem > 48 * 1024)                                                                             \
-            GPX_HIP(hipFuncSetAttribute((const void *)pred_grad_kernel<T, KIND, DPV>,                     \
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));          \
-        hipLaunchKernelGGL((pred_grad_kernel<T, KIND, DPV>), grid, block, smem, st, (const T *)xo, m,     \
-                           (const T *)x, n, d, kp, (const T *)alpha, (const T *)B, ldb, slice_len, partial); \
-    } while (0)
-#define GPX_PGRAD_KIND(KIND)                                                                              \
-    do {                                                                                                  \
-        if (DP == 4) GPX_PGRAD_LAUNCH(KIND, 4);                                                           \
-        else GPX_PGRAD_LAUNCH(KIND, 16);                                                                  \
-    } while (0)
-    if (kernel == GPX_KERNEL_GAUSSIAN) GPX_PGRAD_KIND(GPX_KERNEL_GAUSSIAN);
-    else GPX_PGRAD_LAUNCH(GPX_KERNEL_PERIODIC, 16);
-#undef GPX_PGRAD_KIND
-#undef GPX_PGRAD_LAUNCH
-    GPX_LAUNCH_CHECK();
-    const int64_t md = m * d;
-    if (col_div)
-        hipLaunchKernelGGL((pred_grad_reduce_kernel<true>), dim3((unsigned)cdiv(md, 256)), dim3(256), 0, st, partial, (int)nslice, md, d, factor, aw, out);
-    else
-        hipLaunchKernelGGL((pred_grad_reduce_kernel<false>), dim3((unsigned)cdiv(md, 256)), dim3(256), 0, st, partial, (int)nslice, md, d, factor, aw, out);
-    GPX_LAUNCH_CHECK();
-    return GPX_OK;
-}
-
-int pred_grad(int dtype, int kernel, const void *xo, int64_t m, const void *x, int64_t n, int d, const double *params,
-              const void *alpha, const void *B, int64_t ldb, double scale, const double *col_div, double *out_dev, hipStream_t st)
-{
-    if (m <= 0) return GPX_OK;
-    if (kernel != GPX_KERNEL_GAUSSIAN && kernel != GPX_KERNEL_PERIODIC) { set_error("pred_grad: unknown kernel family %d", kernel); return GPX_ERR_ARG; }
-    if (n <= 0) { GPX_HIP(hipMemsetAsync(out_dev, 0, (size_t)m * d * sizeof(double), st)); return GPX_OK; }
-    KParams kp;
-    GPX_TRY(make_kparams(kernel, GPX_K, params, 0.0, &kp));
-    if (dtype == GPX_F64) return launch_pred_grad<double>(kernel, xo, m, x, n, d, kp, alpha, B, ldb, scale, col_div, out_dev, st);
-    return launch_pred_grad<float>(kernel, xo, m, x, n, d, kp, alpha, B, ldb, scale, col_div, out_dev, st);
-}
-
+static thread_local ThreadScratch g_ard_scr;    // gpx_d_kmat and gpx_d_pred_grad on the ARD family: the scaled copies of their two point sets
+int ard_scratch(size_t bytes, void **p) { return g_ard_scr.get(bytes, p); }
 
 // ---------------------------------------------------------------------------
 // Fused gradient reduction (gp/ext/gp_c.pyx:34-49 without its dense products):
@@ -746,10 +346,8 @@ __global__ __launch_bounds__(256) void dloglh_reduce_kernel(const T *__restrict_
     double acc[4] = {0.0, 0.0, 0.0, 0.0};             // up to 3 kernel params + trace
     const int64_t total = ntiles_r * (ntiles_r + 1) / 2;
     for (int64_t t = blockIdx.x; t < total; t += gridDim.x) {
-        int64_t tr = (int64_t)((sqrt(8.0 * (double)t + 1.0) - 1.0) * 0.5);
-        while ((tr + 1) * (tr + 2) / 2 <= t) ++tr;
-        while (tr * (tr + 1) / 2 > t) --tr;
-        const int64_t tc = t - tr * (tr + 1) / 2;
+        int64_t tr, tc;
+        tri_tile(t, &tr, &tc);
         const int64_t r0 = tr * GR_T, c0 = tc * GR_T;
         __syncthreads();
         for (int idx = tid; idx < GR_T * d; idx += 256) {
@@ -792,14 +390,9 @@ __global__ __launch_bounds__(256) void dloglh_reduce_kernel(const T *__restrict_
             }
         }
     }
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        double v = acc[q];
-        for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-        if ((tid & 63) == 0) red[tid >> 6][q] = v;
-    }
+    block_sum_fixed(acc, red, tid);
     __syncthreads();
-    if (tid < 4) partial[(int64_t)blockIdx.x * 4 + tid] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
+    if (tid < 4) partial[(int64_t)blockIdx.x * 4 + tid] = block_sum_final(red, tid);
 }
 
 // partial: GR_BLOCKS * 4 doubles of DEVICE memory; out4: host, [P0, P1, P2, trace W]
@@ -829,15 +422,11 @@ int dloglh_reduce(int dtype, int kernel, const void *x, int64_t n, int d, const 
     {
     ProfScope prof(PC_REDUCE, 0.5 * (double)n * (double)(n + 1) * (double)es, st);      // the lower triangle of W, read once
     if (dtype == GPX_F64) {
-        if (smem > 48 * 1024)
-            GPX_HIP(hipFuncSetAttribute((const void *)dloglh_reduce_kernel<double>,
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+        if (smem > 48 * 1024) GPX_TRY(set_max_lds((const void *)dloglh_reduce_kernel<double>, LDS_TILE_MAX));
         hipLaunchKernelGGL((dloglh_reduce_kernel<double>), dim3(blocks), dim3(256), smem, st, (const double *)x, n,
                            d, (const double *)alpha, (const double *)W, ldw, gpar, ntr, partial_dev);
     } else {
-        if (smem > 48 * 1024)
-            GPX_HIP(hipFuncSetAttribute((const void *)dloglh_reduce_kernel<float>,
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+        if (smem > 48 * 1024) GPX_TRY(set_max_lds((const void *)dloglh_reduce_kernel<float>, LDS_TILE_MAX));
         hipLaunchKernelGGL((dloglh_reduce_kernel<float>), dim3(blocks), dim3(256), smem, st, (const float *)x, n, d,
                            (const float *)alpha, (const float *)W, ldw, gpar, ntr, partial_dev);
     }
@@ -887,10 +476,8 @@ __global__ __launch_bounds__(256) void dloglh_reduce_ard_kernel(const T *__restr
     double acc0 = 0.0, acctr = 0.0;
     const int64_t total = ntiles_r * (ntiles_r + 1) / 2;
     for (int64_t t = blockIdx.x; t < total; t += gridDim.x) {
-        int64_t tr = (int64_t)((sqrt(8.0 * (double)t + 1.0) - 1.0) * 0.5);
-        while ((tr + 1) * (tr + 2) / 2 <= t) ++tr;
-        while (tr * (tr + 1) / 2 > t) --tr;
-        const int64_t tc = t - tr * (tr + 1) / 2;
+        int64_t tr, tc;
+        tri_tile(t, &tr, &tc);
         const int64_t r0 = tr * GR_T, c0 = tc * GR_T;
         __syncthreads();
         for (int idx = tid; idx < GR_T * DMAX; idx += 256) {
@@ -950,6 +537,8 @@ __global__ __launch_bounds__(256) void dloglh_reduce_ard_kernel(const T *__restr
         }
     }
     // wave reduction (64 lanes), then across the 4 waves in a fixed order; slot 0: S_0, 1 .. DMAX: S_k, DMAX + 1: tr W
+    // (block_sum_fixed's text, written out: through the helper every instantiation takes two more VGPRs and <float, 32> falls
+    // from three to two waves a SIMD)
     const bool lane0 = (tid & 63) == 0;
     {
         double v = acc0;
@@ -966,10 +555,7 @@ __global__ __launch_bounds__(256) void dloglh_reduce_ard_kernel(const T *__restr
         if (lane0) red[rg][1 + k] = v;
     }
     __syncthreads();
-    if (tid < d + 2) {
-        const int q = tid <= d ? tid : DMAX + 1;
-        partial[(int64_t)blockIdx.x * (d + 2) + tid] = ((red[0][q] + red[1][q]) + red[2][q]) + red[3][q];
-    }
+    if (tid < d + 2) partial[(int64_t)blockIdx.x * (d + 2) + tid] = block_sum_final(red, tid <= d ? tid : DMAX + 1);
 }
 
 template <typename T, int DMAX>
@@ -977,8 +563,7 @@ static int launch_reduce_ard(const void *xs, int64_t n, int d, const void *alpha
                              int64_t ntr, int blocks, double *partial_dev, hipStream_t st)
 {
     const size_t smem = ((size_t)2 * GR_T * DMAX + 2 * GR_T) * sizeof(T);
-    if (smem > 48 * 1024)
-        GPX_HIP(hipFuncSetAttribute((const void *)dloglh_reduce_ard_kernel<T, DMAX>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+    if (smem > 48 * 1024) GPX_TRY(set_max_lds((const void *)dloglh_reduce_ard_kernel<T, DMAX>, LDS_TILE_MAX));
     hipLaunchKernelGGL((dloglh_reduce_ard_kernel<T, DMAX>), dim3(blocks), dim3(256), smem, st, (const T *)xs, n, d, (const T *)alpha,
                        (const T *)W, ldw, c2, ntr, partial_dev);
     GPX_LAUNCH_CHECK();
@@ -1072,55 +657,6 @@ int gpx_d_scale_points(int dtype, const void *x, int64_t n, int d, const double 
     if (n == 0) return GPX_OK;
     GPX_ARG(x && w_host && out, "NULL pointer");
     return scale_points(dtype, x, n, d, w_host, out, S(stream));
-}
-
-int gpx_d_mean_member(int dtype, int kernel, int member, const void *xo, int64_t m, const void *x,
-                      int64_t n, int d, const double *params, const void *alpha, void *out, void *stream)
-{
-    gpx::StreamTurn turn__((hipStream_t)stream);     // (this thread's scratch buffers: one stream at a time, gpx_mem.h)
-    GPX_TRY(ensure_device());
-    GPX_ARG(dtype == GPX_F64 || dtype == GPX_F32, "dtype must be GPX_F64 or GPX_F32");
-    GPX_ARG(n >= 0 && m >= 0 && d >= 1, "need n, m >= 0 and d >= 1");
-    if (m == 0) return GPX_OK;
-    GPX_ARG(xo && out && (n == 0 || (x && alpha)), "NULL pointer");
-    KParams kp;
-    GPX_TRY(make_kparams(kernel, member, params, 0.0, &kp));
-    if (dtype == GPX_F64) return launch_mean<double>(kernel, xo, m, x, n, d, kp, alpha, out, S(stream));
-    return launch_mean<float>(kernel, xo, m, x, n, d, kp, alpha, out, S(stream));
-}
-
-int gpx_d_mean(int dtype, int kernel, const void *xo, int64_t m, const void *x, int64_t n, int d,
-               const double *params, const void *alpha, void *out, void *stream)
-{
-    gpx::StreamTurn turn__((hipStream_t)stream);     // (this thread's scratch buffers: one stream at a time, gpx_mem.h)
-    return gpx_d_mean_member(dtype, kernel, GPX_K, xo, m, x, n, d, params, alpha, out, stream);
-}
-
-int gpx_d_pred_grad(int dtype, int kernel, const void *xo, int64_t m, const void *x, int64_t n, int d, const double *params,
-                    const void *alpha, const void *B, int64_t ldb, double scale, double *out_dev, void *stream)
-{
-    gpx::StreamTurn turn__((hipStream_t)stream);     // (this thread's scratch buffers: one stream at a time, gpx_mem.h)
-    GPX_TRY(ensure_device());
-    GPX_ARG(dtype == GPX_F64 || dtype == GPX_F32, "dtype must be GPX_F64 or GPX_F32");
-    GPX_ARG(n >= 0 && m >= 0 && d >= 1, "need n, m >= 0 and d >= 1");
-    GPX_ARG((alpha != nullptr) != (B != nullptr) || n == 0, "exactly one of alpha / B");
-    if (m == 0) return GPX_OK;
-    GPX_ARG(xo && out_dev && params && (n == 0 || x), "NULL pointer");
-    GPX_ARG(!B || ldb >= n, "ldb < n");
-    if (kernel == GPX_KERNEL_GAUSSIAN_ARD) {
-        // as gpx_d_kmat: the isotropic pass on (xo / w, x / w; h / sqrt(wbar), 1), column k divided by w_k
-        GPX_ARG(d <= GPX_ARD_MAX_D, "the ARD family needs d <= GPX_ARD_MAX_D");
-        const size_t es = esize(dtype), b1 = ((size_t)m * d * es + 255) / 256 * 256;
-        void *scr = nullptr;
-        GPX_TRY(g_ard_scr.get(b1 + (size_t)n * d * es, &scr));
-        void *s1 = scr, *s2 = (char *)scr + b1;
-        GPX_TRY(scale_points(dtype, xo, m, d, params + 1, s1, S(stream)));
-        GPX_TRY(scale_points(dtype, x, n, d, params + 1, s2, S(stream)));
-        double iso[2];
-        ard_iso(params, d, iso);
-        return pred_grad(dtype, GPX_KERNEL_GAUSSIAN, s1, m, s2, n, d, iso, alpha, B, ldb, scale, params + 1, out_dev, S(stream));
-    }
-    return pred_grad(dtype, kernel, xo, m, x, n, d, params, alpha, B, ldb, scale, nullptr, out_dev, S(stream));
 }
 
 }  // extern "C"

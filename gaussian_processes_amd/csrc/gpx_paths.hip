@@ -63,183 +63,10 @@ int rff_features(int dtype, const void *pts, int64_t m, int d, const double *ome
 }
 
 // ---------------------------------------------------------------------------
-// K(xo, x) applied to S weight vectors, fused:  partial[slice][s][i] = sum_{j in slice} k(xo_i, x_j) V[s, j].
-// mean_kernel's shape (gpx_kmat.hip): workgroup (bx, by, bz) owns KA_MP test points, the by-th slice of the training set --
-// streamed through LDS in chunks of 256 points, one per lane, transposed and padded -- and the bz-th group of KA_SV weight
-// vectors.  Per chunk a lane loads its KA_SV weights V[s0 .. s0 + KA_SV, j] once (coalesced across the lanes, zero beyond S),
-// forms each k(xo_p, x_j) once -- the distance as kmat_kernel accumulates it, the entry function of kmat_kernel, underflow
-// clamp included: the value is the element gpx_d_kmat would store -- and adds it into KA_MP x KA_SV f64 sums.  Only a new group
-// of vectors (gridDim.z) evaluates the kernel again.  Lanes are added by shuffles, waves through LDS, slices by
-// kapply_reduce_kernel in ascending order: no atomics, bitwise repeatable.
-// KA_MP x KA_SV <= 32 f64 accumulators are at most 64 VGPRs of the lane's state; DESIGN "Posterior paths" has the compiler's count.
+// K(xo, x) applied to S weight vectors: the fused route is the streamed apply kernel (gpx_stream.hip); beyond its range of
+// (d, S) the product route builds K(xo, x) in row chunks and multiplies.
 // ---------------------------------------------------------------------------
-constexpr int KA_CP = 257;         // padded chunk row (mean_kernel's MCP)
-constexpr int KA_LDS_MAX = 96 * 1024;   // the largest chunk of x the fused kernel is launched with (kapply_fused_fits).  set_max_lds sets a
-                                        // kernel's limit ONCE per device, so it gets this constant, never the d-dependent size of one call
-
-// The register block by the number of weight vectors: (test points per workgroup, vectors per lane).  One vector is
-// mean_kernel's own shape; up to four keep its 8 points -- the chunk's staging pass and its two barriers are shared by twice
-// the pairs -- and from five on the block is 4 x 8.  (Measured with 4 x 8 alone, DESIGN "Posterior paths": S = 1 took 1.7 times
-// gpx_d_mean in fp64 and 2.6 times in fp32, where seven of the eight f64 FMAs per kernel value multiplied zeros.)
-struct KaShape { int mp, sv; };
-static inline KaShape kapply_shape(int64_t S) { return S == 1 ? KaShape{8, 1} : (S <= 4 ? KaShape{8, 4} : KaShape{4, 8}); }
-
-// KIND: GPX_KERNEL_GAUSSIAN or GPX_KERNEL_PERIODIC (member GPX_K, any d); KA_MP x KA_SV: the register block
-template <typename T, int KIND, int KA_MP, int KA_SV>
-__global__ __launch_bounds__(256) void kapply_fused_kernel(const T *__restrict__ xo, int64_t m, const T *__restrict__ x, int64_t n, int d,
-                                                           KParams kp, const T *__restrict__ V, int64_t ldv, int64_t S,
-                                                           int64_t slice_len, double *__restrict__ partial)
-{
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    T *sx = reinterpret_cast<T *>(smem_raw);            // [d][KA_CP] chunk of x, transposed
-    __shared__ double red[4][KA_MP * KA_SV];
-
-    const int tid = threadIdx.x;
-    const int64_t p0 = (int64_t)blockIdx.x * KA_MP;
-    const int64_t s0 = (int64_t)blockIdx.z * KA_SV;
-    double acc[KA_MP][KA_SV];
-#pragma unroll
-    for (int pp = 0; pp < KA_MP; ++pp)
-#pragma unroll
-        for (int sv = 0; sv < KA_SV; ++sv) acc[pp][sv] = 0.0;
-    const T *orow[KA_MP];
-#pragma unroll
-    for (int pp = 0; pp < KA_MP; ++pp) orow[pp] = xo + min(p0 + pp, m - 1) * d;
-
-    const T c1 = (T)kp.c[0], c2 = (T)kp.c[1];
-    const int qd = 256 / d, rd = 256 - qd * d;          // idx += 256  <=>  (c, k) += (qd, rd) with carry
-    const int cst = tid / d, kst = tid - cst * d;
-    const int64_t jbeg = (int64_t)blockIdx.y * slice_len, jend = min(n, jbeg + slice_len);
-    for (int64_t j0 = jbeg; j0 < jend; j0 += 256) {
-        __syncthreads();
-        {
-            const int64_t lim = (jend - j0) * d;
-            const T *g = x + j0 * d;
-            int c = cst, k = kst;
-            for (int idx = tid; idx < 256 * d; idx += 256) {
-                sx[(size_t)k * KA_CP + c] = (idx < lim) ? g[idx] : (T)0;
-                c += qd; k += rd;
-                if (k >= d) { k -= d; ++c; }
-            }
-        }
-        __syncthreads();
-        const int64_t j = j0 + tid;
-        if (j < jend) {
-            double vj[KA_SV];
-#pragma unroll
-            for (int sv = 0; sv < KA_SV; ++sv) vj[sv] = (s0 + sv < S) ? (double)V[(s0 + sv) * ldv + j] : 0.0;
-            T r[KA_MP];
-#pragma unroll
-            for (int pp = 0; pp < KA_MP; ++pp) r[pp] = (T)0;
-            // (the test points are the same for every lane: SGPR operands through the scalar cache, as in kmat_kernel)
-            for (int k = 0; k < d; ++k) {
-                const T b = sx[(size_t)k * KA_CP + tid];
-#pragma unroll
-                for (int pp = 0; pp < KA_MP; ++pp) {
-                    const T a = orow[pp][k];
-                    if (KIND == GPX_KERNEL_GAUSSIAN) {
-                        const T t = a - b;
-                        r[pp] = fma(t, t, r[pp]);
-                    } else {
-                        const T sn = sin((T)0.5 * (a - b) / (T)kp.c[2]);
-                        r[pp] = fma(sn, sn, r[pp]);
-                    }
-                }
-            }
-#pragma unroll
-            for (int pp = 0; pp < KA_MP; ++pp) {
-                T kv;
-                if (KIND == GPX_KERNEL_GAUSSIAN) {
-                    kv = gaussian_entry<T, 0>(r[pp], c1, c2, (T)0, (T)0);
-                } else {
-                    const T h = (T)kp.c[0], w = (T)kp.c[1];
-                    kv = (h * h) * dev_exp<T>((T)-2.0 * r[pp] / (w * w));
-                }
-                const double kd = (double)kv;
-#pragma unroll
-                for (int sv = 0; sv < KA_SV; ++sv) acc[pp][sv] = fma(kd, vj[sv], acc[pp][sv]);
-            }
-        }
-    }
-    // wave reduction (64 lanes), then across the 4 waves in a fixed order
-#pragma unroll
-    for (int pp = 0; pp < KA_MP; ++pp)
-#pragma unroll
-        for (int sv = 0; sv < KA_SV; ++sv) {
-            double v = acc[pp][sv];
-            for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-            if ((tid & 63) == 0) red[tid >> 6][pp * KA_SV + sv] = v;
-        }
-    __syncthreads();
-    if (tid < KA_MP * KA_SV) {
-        const int pp = tid / KA_SV, sv = tid - pp * KA_SV;
-        if (p0 + pp < m && s0 + sv < S)
-            partial[((int64_t)blockIdx.y * S + s0 + sv) * m + p0 + pp] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
-    }
-}
-
-// out[s, i] += sum over the slices, in slice order; one rounding to T
-template <typename T>
-__global__ __launch_bounds__(256) void kapply_reduce_kernel(const double *__restrict__ partial, int nslice, int64_t S, int64_t m,
-                                                            T *__restrict__ out, int64_t ldo)
-{
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= m) return;
-    for (int64_t s = blockIdx.y; s < S; s += gridDim.y) {
-        double sum = 0.0;
-        for (int y = 0; y < nslice; ++y) sum += partial[((int64_t)y * S + s) * m + i];
-        out[s * ldo + i] = (T)((double)out[s * ldo + i] + sum);
-    }
-}
-
-static thread_local ThreadScratch g_kapply_scr;   // fused route: the slice partial sums; product route: the chunk of K(xo, x)
-
-// does the fused kernel take this (d, S)?  launch_mean's range of d (the chunk of x in LDS), one grid z per vector group
-static bool kapply_fused_fits(int dtype, int d, int64_t S)
-{
-    return (size_t)d * KA_CP * esize(dtype) <= (size_t)KA_LDS_MAX && cdiv(S, kapply_shape(S).sv) <= 65535;
-}
-
-template <typename T, int KA_MP, int KA_SV>
-static int launch_kapply_fused(int kernel, const void *xo, int64_t m, const void *x, int64_t n, int d, const KParams &kp, const void *V,
-                               int64_t ldv, int64_t S, void *out, int64_t ldo, hipStream_t st)
-{
-    const size_t smem = (size_t)d * KA_CP * sizeof(T);
-    const int64_t gx = cdiv(m, KA_MP), gz = cdiv(S, KA_SV);
-    // enough workgroups to fill the chip: slices of the training set when m and the vector groups alone are too few (launch_mean's rule)
-    int64_t nslice = std::max<int64_t>(1, std::min<int64_t>(cdiv(2048, gx * gz), cdiv(n, 256)));
-    const int64_t slice_len = cdiv(cdiv(n, nslice), 256) * 256;
-    nslice = cdiv(n, slice_len);
-    void *scr = nullptr;
-    GPX_TRY(g_kapply_scr.get((size_t)nslice * S * m * sizeof(double), &scr));
-    double *partial = (double *)scr;
-    const dim3 grid((unsigned)gx, (unsigned)nslice, (unsigned)gz), block(256);
-    ProfScope prof(PC_KAPPLY, (double)m * (double)n * (double)gz, st);
-#define GPX_KAPPLY_LAUNCH(KIND)                                                                                                    \
-    do {                                                                                                                           \
-        if (smem > 48 * 1024) GPX_TRY(set_max_lds((const void *)kapply_fused_kernel<T, KIND, KA_MP, KA_SV>, KA_LDS_MAX));           \
-        hipLaunchKernelGGL((kapply_fused_kernel<T, KIND, KA_MP, KA_SV>), grid, block, smem, st, (const T *)xo, m, (const T *)x, n, \
-                           d, kp, (const T *)V, ldv, S, slice_len, partial);                                                       \
-    } while (0)
-    if (kernel == GPX_KERNEL_GAUSSIAN) GPX_KAPPLY_LAUNCH(GPX_KERNEL_GAUSSIAN);
-    else GPX_KAPPLY_LAUNCH(GPX_KERNEL_PERIODIC);
-#undef GPX_KAPPLY_LAUNCH
-    GPX_LAUNCH_CHECK();
-    const dim3 rgrid((unsigned)cdiv(m, 256), (unsigned)std::min<int64_t>(S, 32768));
-    hipLaunchKernelGGL((kapply_reduce_kernel<T>), rgrid, block, 0, st, partial, (int)nslice, S, m, (T *)out, ldo);
-    GPX_LAUNCH_CHECK();
-    return GPX_OK;
-}
-
-template <typename T>
-static int kapply_fused(int kernel, const void *xo, int64_t m, const void *x, int64_t n, int d, const KParams &kp, const void *V,
-                        int64_t ldv, int64_t S, void *out, int64_t ldo, hipStream_t st)
-{
-    const KaShape sh = kapply_shape(S);
-    if (sh.sv == 1) return launch_kapply_fused<T, 8, 1>(kernel, xo, m, x, n, d, kp, V, ldv, S, out, ldo, st);
-    if (sh.sv == 4) return launch_kapply_fused<T, 8, 4>(kernel, xo, m, x, n, d, kp, V, ldv, S, out, ldo, st);
-    return launch_kapply_fused<T, 4, 8>(kernel, xo, m, x, n, d, kp, V, ldv, S, out, ldo, st);
-}
+static thread_local ThreadScratch g_kapply_scr;   // product route: the chunk of K(xo, x) (live across a kmat call, so not the streamed passes' block)
 
 // the product route's chunk of K(xo, x): a multiple of 128 rows (the shifted C pointer of the product stays aligned), at most
 // 4096, within KAPPLY_CHUNK_BYTES
@@ -258,8 +85,7 @@ int kmat_apply(int dtype, int kernel, const void *xo, int64_t m, const void *x, 
         KParams kp;
         GPX_TRY(make_kparams(kernel, GPX_K, params, 0.0, &kp));
         route_hit(RT_KAPPLY_FUSED);
-        if (dtype == GPX_F64) return kapply_fused<double>(kernel, xo, m, x, n, d, kp, V, ldv, S, out, ldo, st);
-        return kapply_fused<float>(kernel, xo, m, x, n, d, kp, V, ldv, S, out, ldo, st);
+        return kapply_fused(dtype, xo, m, x, n, d, kp, V, ldv, S, out, ldo, st);
     }
     // (any base and pitch of V: gemm_nt takes its generic kernel where the LDS-DMA one needs 16-byte alignment)
     const int64_t ldk = round_up(n, 16);

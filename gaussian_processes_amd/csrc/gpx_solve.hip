@@ -1243,8 +1243,7 @@ __device__ __forceinline__ T kdiag_entry(const KParams &kp, const T *__restrict_
         return gaussian_entry<T, 0>(acc, (T)kp.c[0], (T)kp.c[1], (T)kp.c[2], (T)kp.c[3]);
     }
     for (int k = 0; k < d; ++k) { const T sn = sin((T)0.5 * (a[k] - a[k]) / (T)kp.c[2]); acc = fma(sn, sn, acc); }
-    const T h = (T)kp.c[0], w = (T)kp.c[1];
-    return (h * h) * dev_exp<T>((T)-2.0 * acc / (w * w));
+    return periodic_k<T>(acc, (T)kp.c[0], (T)kp.c[1]);
 }
 
 // One workgroup per row (grid-stride over rows): out[i] = kdiag(i) - sum_j X[i, j]^2, or out[i] += sum_j X[i, j]^2.

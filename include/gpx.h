@@ -175,7 +175,7 @@ int gpx_stream_wait_event(void *stream, void *event);
 #define GPX_PROF_EXTEND      13 /* copy_lower_kernel + schur_reduce_kernel (gpx_gp_extend): bytes read + written */
 #define GPX_PROF_RANDN       14 /* randn_kernel (gpx_d_randn): bytes written */
 #define GPX_PROF_RFF         15 /* rff_features_kernel (gpx_d_rff_features): bytes written */
-#define GPX_PROF_KAPPLY      16 /* kapply_fused_kernel + its slice reduction (gpx_d_kmat_apply, fused route): kernel evaluations m*n per group of weight vectors */
+#define GPX_PROF_KAPPLY      16 /* stream_apply_kernel + its slice reduction (gpx_d_kmat_apply, fused route): kernel evaluations m*n per group of weight vectors */
 int gpx_prof_enable(int on);    /* also clears the registry */
 int gpx_prof_read(int cls, double *launches, double *total_ms, double *total_work);
 

@@ -138,6 +138,50 @@ def test_cholesky_schedule_state_is_explicit():
     assert 1 <= len(re.findall(r"\bsyrk_bc\s*\(", code("gpx_potrf.hip"))) <= 2
 
 
+def test_streamed_reductions_keep_one_copy_of_each_piece():
+    """The kernels that stream the training set through LDS (csrc/gpx_stream.hip, DESIGN "Streamed reductions") and the tile
+    reductions were grown by copying one another: the transposed chunk staging existed four times, the fixed-order block
+    sum seven, the triangular tile walk and the host's slice plan three each, and seven launch sites raised the dynamic-LDS
+    limit on their own with a size that depended on the call.  Each of these now has ONE definition (csrc/gpx_kernels_dev.h,
+    slice_plan, set_max_lds); a new kernel on this path that brings a copy of its own fails here."""
+    csrc = os.path.join(ROOT, "gaussian_processes_amd", "csrc")
+
+    def code(f):        # without comments and string literals
+        src = open(os.path.join(csrc, f)).read()
+        return re.sub(r'"(?:\\.|[^"\\])*"', '""', re.sub(r"//[^\n]*", "", src))
+    files = [f for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".h"))]
+    assert "gpx_stream.hip" in files
+
+    def sites(pattern):
+        return {f: len(re.findall(pattern, code(f))) for f in files if re.search(pattern, code(f))}
+    # the dynamic-LDS limit: set_max_lds (once per kernel and device, a constant) and nobody else
+    assert sites(r"\bhipFuncSetAttribute\b") == {"gpx_runtime.hip": 1}
+    for f in ("gpx_kmat.hip", "gpx_deriv.hip", "gpx_stream.hip"):
+        for arg in re.findall(r"\bset_max_lds\(\(const void \*\)[^;]*?,\s*([^,;]+?)\)\);", code(f)):
+            assert arg in ("LDS_CHUNK_MAX", "LDS_TILE_MAX"), (f, arg)
+        assert "set_max_lds" in code(f), f
+    # the carry loop of the transposed staging, the triangular index inversion, the slice plan
+    assert sites(r"k -= \(?d\)?;\s*\+\+c") == {"gpx_kernels_dev.h": 1}
+    assert sites(r"sqrt\(8\.0 \* \(double\)t") == {"gpx_kernels_dev.h": 1}
+    assert sites(r"\bcdiv\(2048,") == {"gpx_stream.hip": 1}
+    # the 64-lane shuffle-down sum: the helper, the two sums that are no four-wave block sum (the 16-wave strided_sum_kernel
+    # and the one-value sum of gpx_solve.hip), and the two kernels that keep the text written out because the helper changes
+    # their code: dloglh_reduce_ard_kernel's three (two more VGPRs, <float, 32> loses a wave per SIMD) and
+    # member_quad_trace_kernel's interleaved pair (22 more instructions) -- DESIGN "Streamed reductions"
+    assert sites(r"off = 32; off > 0; off >>= 1") == {"gpx_kernels_dev.h": 1, "gpx_deriv.hip": 2, "gpx_solve.hip": 1, "gpx_kmat.hip": 3}
+    for f in ("gpx_kmat.hip", "gpx_deriv.hip", "gpx_stream.hip", "gpx_paths.hip"):
+        assert "((red[0]" not in code(f), f
+    # one partial-sum scratch for the streamed passes; the mean and the apply kernel have one launch site each, behind one
+    # launcher that owns the slice plan, the scratch, the LDS limit and the slices' reduction
+    stream = code("gpx_stream.hip")
+    assert re.findall(r"static thread_local ThreadScratch (\w+);", stream) == ["g_partial_scr"]
+    for k in ("stream_mean_kernel", "stream_apply_kernel", "apply_reduce_kernel", "pred_grad_kernel"):
+        assert len(re.findall(r"hipLaunchKernelGGL\(\(%s<" % k, stream)) == 1, k
+    assert len(re.findall(r"\bslice_plan\(", stream)) == 3          # the definition, the apply launcher, pred_grad
+    for f in files:
+        assert not re.search(r"\b(?:mean_kernel|kapply_fused_kernel|g_mean_scr|g_pgrad_scr)\b", code(f)), f
+
+
 def test_no_cpu_fallback_without_gpu():
     if _lib.device_count() > 0:
         pytest.skip("a GPU is present")
