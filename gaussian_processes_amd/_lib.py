@@ -19,8 +19,8 @@ ERR_ARG, ERR_HIP, ERR_NO_DEVICE, ERR_NOMEM, ERR_UNSUPPORTED, ERR_INTERNAL = -1, 
 (ROUTE_TRSV_OPS, ROUTE_TRSV_STEPS, ROUTE_PANEL_RES, ROUTE_PANEL_CHAIN, ROUTE_FIT_RIDE, ROUTE_FIT_TWO_SOLVES,
  ROUTE_GEMM_FAST, ROUTE_GEMM_GENERIC, ROUTE_SYRK_EXACT, ROUTE_SYRK_PATCH, ROUTE_MG_BCAST_ONE, ROUTE_MG_BCAST_SAG,
  ROUTE_FIT_OPS_AHEAD, ROUTE_TRSM_OPS, ROUTE_POTRF_PAIR, ROUTE_VAR_CHUNK, ROUTE_LOO_CHUNK, ROUTE_TRSM_L_OPS,
- ROUTE_GRAD_CHUNK, ROUTE_EXTEND, ROUTE_SAMPLE, ROUTE_KAPPLY_FUSED, ROUTE_KAPPLY_GEMM) = range(23)
-PROF_RANDN, PROF_RFF, PROF_KAPPLY = 14, 15, 16
+ ROUTE_GRAD_CHUNK, ROUTE_EXTEND, ROUTE_SAMPLE, ROUTE_KAPPLY_FUSED, ROUTE_KAPPLY_GEMM, ROUTE_PATHS_GRAD_CHUNK) = range(24)
+PROF_RANDN, PROF_RFF, PROF_KAPPLY, PROF_KAPPLY_GRAD = 14, 15, 16, 17
 F64, F32 = 0, 1
 KERNEL_GAUSSIAN, KERNEL_PERIODIC, KERNEL_GAUSSIAN_ARD = 0, 1, 2
 ARD_MAX_D = 64
@@ -113,6 +113,10 @@ _SIGNATURES = {
     "gpx_d_rff_features": (c_int, [c_int, c_void_p, c_int64, c_int, c_void_p, c_int64, c_double, c_void_p, c_int64, c_void_p]),
     "gpx_d_kmat_apply": (c_int, [c_int, c_int, c_void_p, c_int64, c_void_p, c_int64, c_int, c_double_p, c_void_p, c_int64, c_int64,
                                  c_void_p, c_int64, c_void_p]),
+    "gpx_d_rff_features_grad": (c_int, [c_int, c_void_p, c_int64, c_int, c_void_p, c_int64, c_double, c_double_p, c_void_p, c_int64,
+                                        c_void_p]),
+    "gpx_d_kmat_apply_grad": (c_int, [c_int, c_int, c_void_p, c_int64, c_void_p, c_int64, c_int, c_double_p, c_double_p, c_void_p,
+                                      c_int64, c_int64, c_void_p, c_int64, c_void_p]),
     "gpx_gp_create": (c_int, [POINTER(c_void_p), c_int, c_int, c_int64, c_int]),
     "gpx_gp_destroy": (c_int, [c_void_p]),
     "gpx_gp_set_data": (c_int, [c_void_p, c_double_p, c_double_p]),
@@ -142,6 +146,7 @@ _SIGNATURES = {
                                      c_int_p]),
     "gpx_gp_paths_create": (c_int, [c_void_p, c_int64, c_int64, c_uint64, POINTER(c_void_p)]),
     "gpx_paths_eval": (c_int, [c_void_p, c_double_p, c_int64, c_int64, c_double_p]),
+    "gpx_paths_grad": (c_int, [c_void_p, c_double_p, c_int64, c_int64, c_double_p, c_double_p]),
     "gpx_paths_get": (c_int, [c_void_p, c_double_p, c_double_p, c_double_p]),
     "gpx_paths_describe": (c_int, [c_void_p, c_int_p, c_int_p, POINTER(c_int64), c_int_p, POINTER(c_int64), POINTER(c_int64),
                                    POINTER(c_uint64)]),

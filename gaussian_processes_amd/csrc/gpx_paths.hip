@@ -1,8 +1,9 @@
 // gpx_paths.hip -- posterior function samples by pathwise conditioning (Matheron's rule; Wilson et al. 2020):
 //   f_s(a) = phi(a) . Theta_s + sum_j k(a, x_j) V[s, j],     V_s = alpha - Kxx^-1 (Phi(x) Theta_s + sigma E_s)
-// a random-feature draw of the prior plus an exact, data-dependent update.  Two device primitives -- the feature map
-// (gpx_d_rff_features) and the kernel matrix applied to several weight vectors at once without materialising it
-// (gpx_d_kmat_apply) -- and the handle that owns one set of paths (gpx_gp_paths_create, gpx_paths_*).  include/gpx.h has the
+// a random-feature draw of the prior plus an exact, data-dependent update.  The device primitives -- the feature map and its
+// derivative (gpx_d_rff_features, gpx_d_rff_features_grad) and the kernel matrix applied to several weight vectors at once
+// without materialising it (gpx_d_kmat_apply; its input-space gradient gpx_d_kmat_apply_grad is gpx_stream.hip's) -- and the
+// handle that owns one set of paths (gpx_gp_paths_create, gpx_paths_*).  include/gpx.h has the
 // definition of every random input; tests/_paths_helpers.py restates it in numpy.
 #include "gpx_common.h"
 #include "gpx_kernels_dev.h"
@@ -19,7 +20,7 @@ struct gpx_paths {
     double w[GPX_ARD_MAX_D];           // ARD: the widths test points are divided by
     double scale;                      // sqrt(k0 / F)
     float ms[4];                       // gpx_debug_paths_timing: how long the creation took, by stage
-    gpx::GrowBuf ws;                   // gpx_paths_eval's chunk buffers (grow-only, freed with the handle): points, features, values, staging
+    gpx::GrowBuf ws;                   // gpx_paths_eval's and gpx_paths_grad's chunk buffers (grow-only, freed with the handle): points, features, values, staging
     hipStream_t st;
 };
 
@@ -58,6 +59,52 @@ int rff_features(int dtype, const void *pts, int64_t m, int d, const double *ome
         hipLaunchKernelGGL((rff_features_kernel<double>), grid, block, 0, st, (const double *)pts, m, d, omega_dev, F, scale, (double *)out, ld);
     else
         hipLaunchKernelGGL((rff_features_kernel<float>), grid, block, 0, st, (const float *)pts, m, d, omega_dev, F, scale, (float *)out, ld);
+    GPX_LAUNCH_CHECK();
+    return GPX_OK;
+}
+
+// ---------------------------------------------------------------------------
+// The feature map's derivative with respect to the point, row i d + k = d phi(p_i) / d p_ik:
+//   out[i d + k, f] = -(scale / div_k) omega[f, k] sin(omega_f . p_i),   out[i d + k, F + f] = (scale / div_k) omega[f, k] cos(omega_f . p_i)
+// rff_features_kernel's shape and conventions -- one thread per (point, frequency), frequencies along the lanes, fp64
+// projection and sincos, one rounding on the store -- with the sincos formed ONCE for the d rows it feeds.  sd: scale / div_k,
+// divided on the host (DIV), else `scale` for every k.
+// ---------------------------------------------------------------------------
+template <typename T, bool DIV>
+__global__ __launch_bounds__(256) void rff_features_grad_kernel(const T *__restrict__ pts, int64_t m, int d, const double *__restrict__ omega,
+                                                                int64_t F, double scale, ArdWidths sd, T *__restrict__ out, int64_t ld)
+{
+    const int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (f >= F) return;
+    const double *w = omega + f * d;
+    for (int64_t i = blockIdx.y; i < m; i += gridDim.y) {
+        const T *p = pts + i * d;
+        double t = 0.0;
+        for (int k = 0; k < d; ++k) t = fma(w[k], (double)p[k], t);
+        double sn, cs;
+        sincos(t, &sn, &cs);
+        T *row = out + i * d * ld;
+        for (int k = 0; k < d; ++k) {
+            const double c = (DIV ? sd.w[k] : scale) * w[k];
+            row[k * ld + f] = (T)(-(c * sn));
+            row[k * ld + F + f] = (T)(c * cs);
+        }
+    }
+}
+
+int rff_features_grad(int dtype, const void *pts, int64_t m, int d, const double *omega_dev, int64_t F, double scale, const double *col_div,
+                      void *out, int64_t ld, hipStream_t st)
+{
+    if (m <= 0 || F <= 0) return GPX_OK;
+    if (col_div && d > GPX_ARD_MAX_D) { set_error("rff_features_grad: column divisors need d <= %d (got %d)", GPX_ARD_MAX_D, d); return GPX_ERR_ARG; }
+    ArdWidths sd;
+    for (int k = 0; k < GPX_ARD_MAX_D; ++k) sd.w[k] = (col_div && k < d) ? scale / col_div[k] : scale;
+    const dim3 grid((unsigned)cdiv(F, 256), (unsigned)std::min<int64_t>(m, 32768)), block(256);
+    ProfScope prof(PC_RFF, 2.0 * (double)m * (double)d * (double)F * (double)esize(dtype), st);
+#define GPX_RFFG_LAUNCH(T, DIV) hipLaunchKernelGGL((rff_features_grad_kernel<T, DIV>), grid, block, 0, st, (const T *)pts, m, d, omega_dev, F, scale, sd, (T *)out, ld)
+    if (dtype == GPX_F64) { if (col_div) GPX_RFFG_LAUNCH(double, true); else GPX_RFFG_LAUNCH(double, false); }
+    else { if (col_div) GPX_RFFG_LAUNCH(float, true); else GPX_RFFG_LAUNCH(float, false); }
+#undef GPX_RFFG_LAUNCH
     GPX_LAUNCH_CHECK();
     return GPX_OK;
 }
@@ -133,6 +180,14 @@ static int paths_rows(int dtype, void *R, int64_t ld, int64_t rows, int64_t cols
 static int64_t paths_feature_rows(int dtype, int64_t ldphi)
 {
     const int64_t fit = (int64_t)(((size_t)128 << 20) / ((size_t)ldphi * esize(dtype))) / 128 * 128;
+    return std::max<int64_t>(128, std::min<int64_t>(fit, 4096));
+}
+
+// rows of a gradient chunk (gpx_paths_grad): a multiple of 128, at most 4096, whose feature blocks -- rows (d + 1) ldt elements:
+// the derivative's rows d and the map's own -- fit 512 MiB; never fewer than 128
+static int64_t paths_grad_rows(int dtype, int d, int64_t ldt)
+{
+    const int64_t fit = (int64_t)(((size_t)512 << 20) / ((size_t)(d + 1) * ldt * esize(dtype))) / 128 * 128;
     return std::max<int64_t>(128, std::min<int64_t>(fit, 4096));
 }
 
@@ -225,6 +280,20 @@ int gpx_d_rff_features(int dtype, const void *pts, int64_t m, int d, const doubl
     GPX_ARG(m <= INT64_MAX / ld && F <= INT64_MAX / d, "m * ld overflows");
     GPX_ARG(cdiv(F, 256) <= 0x7fffffff, "F is more than one launch covers");
     return rff_features(dtype, pts, m, d, omega_dev, F, scale, out, ld, S(stream));
+}
+
+int gpx_d_rff_features_grad(int dtype, const void *pts, int64_t m, int d, const double *omega_dev, int64_t F, double scale,
+                            const double *col_div, void *out, int64_t ld, void *stream)
+{
+    GPX_TRY(ensure_device());
+    GPX_ARG(dtype == GPX_F64 || dtype == GPX_F32, "dtype must be GPX_F64 or GPX_F32");
+    GPX_ARG(m >= 0 && F >= 0 && d >= 1, "need m, F >= 0 and d >= 1");
+    if (m == 0 || F == 0) return GPX_OK;
+    GPX_ARG(pts && omega_dev && out, "NULL pointer");
+    GPX_ARG(F <= INT64_MAX / 2 && ld >= 2 * F, "ld < 2 F");
+    GPX_ARG(m <= INT64_MAX / d && m * d <= INT64_MAX / ld && F <= INT64_MAX / d, "m * d * ld overflows");
+    GPX_ARG(cdiv(F, 256) <= 0x7fffffff, "F is more than one launch covers");
+    return rff_features_grad(dtype, pts, m, d, omega_dev, F, scale, col_div, out, ld, S(stream));
 }
 
 int gpx_d_kmat_apply(int dtype, int kernel, const void *xo, int64_t m, const void *x, int64_t n, int d, const double *params,
@@ -337,6 +406,55 @@ int gpx_paths_eval(gpx_paths_t *p, const double *xo, int64_t m, int64_t chunk_ro
         GPX_TRY(gemm_nt(dtype, S, rc, 2 * F, p->theta, p->ldt, phi, p->ldt, outc, ldo, 1.0, GPX_FULL, 0, 0, p->st));
         GPX_TRY(kmat_apply(dtype, GPX_KERNEL_GAUSSIAN, dxo, rc, p->pts, p->n, d, p->iso, p->V, p->ldv, S, outc, ldo, p->st));
         GPX_TRY(download_f64(dtype, out + r0, m, outc, ldo, S, rc, 0, p->st));
+    }
+    return GPX_OK;
+}
+
+int gpx_paths_grad(gpx_paths_t *p, const double *xo, int64_t m, int64_t chunk_rows, double *values, double *grad)
+{
+    PATHS_ENTER(p);
+    GPX_ARG(m >= 0 && (m == 0 || p->S == 0 || (xo && grad)), "bad arguments");
+    if (chunk_rows < 0 || chunk_rows % 128 != 0) {
+        set_error("gpx_paths_grad: chunk_rows must be 0 (automatic) or a multiple of 128");
+        return GPX_ERR_ARG;
+    }
+    if (m == 0 || p->S == 0) return GPX_OK;
+    const int dtype = p->dtype, d = p->d;
+    const int64_t S = p->S, F = p->F;
+    const size_t es = esize(dtype);
+    const bool ard = p->kernel == GPX_KERNEL_GAUSSIAN_ARD;
+    GPX_ARG(m <= (INT64_MAX / 8) / (std::max<int64_t>(S, 1) * d), "S * m * d overflows");
+    int64_t rows = chunk_rows ? chunk_rows : paths_grad_rows(dtype, d, p->ldt);
+    if (m <= rows) rows = m;                              // one chunk: exactly the rows there are
+    const int64_t ldo = round_up(rows, 16), ldg = round_up(rows * d, 16);
+    // One chunk's buffers, carved out of the handle's grow-only block as gpx_paths_eval's are: points, the derivative's
+    // features, the gradient block, and with values the map's own features and the value block
+    const auto pad = [](size_t b) { return (b + 255) / 256 * 256; };
+    const size_t b_xo = pad((size_t)rows * d * es), b_psi = pad((size_t)rows * d * p->ldt * es), b_g = pad((size_t)S * ldg * es);
+    const size_t b_phi = values ? pad((size_t)rows * p->ldt * es) : 0, b_out = values ? pad((size_t)S * ldo * es) : 0;
+    const size_t b_stage = dtype == GPX_F64 ? 0 : pad((size_t)rows * d * sizeof(double));   // upload_f64's float64 copy (fp32 only)
+    GPX_TRY(p->ws.reserve(b_xo + b_psi + b_g + b_phi + b_out + b_stage, p->st));
+    char *base = (char *)p->ws.p;
+    void *dxo = base, *psi = base + b_xo, *gc = base + b_xo + b_psi, *phi = base + b_xo + b_psi + b_g, *outc = base + b_xo + b_psi + b_g + b_phi;
+    StageView stage(b_stage ? base + b_xo + b_psi + b_g + b_phi + b_out : nullptr);
+    const double *col_div = ard ? p->w : nullptr;
+    for (int64_t r0 = 0; r0 < m; r0 += rows) {
+        const int64_t rc = std::min(rows, m - r0);
+        route_hit(RT_PATHS_GRAD_CHUNK);
+        GPX_TRY(upload_f64(dtype, dxo, rc * d, xo + r0 * d, rc * d, 1, rc * d, p->st, b_stage ? &stage.buf : nullptr));
+        if (ard) GPX_TRY(scale_points(dtype, dxo, rc, d, p->w, dxo, p->st));
+        GPX_TRY(rff_features_grad(dtype, dxo, rc, d, p->omega, F, p->scale, col_div, psi, p->ldt, p->st));
+        GPX_HIP(hipMemsetAsync(gc, 0, (size_t)S * ldg * es, p->st));
+        GPX_TRY(gemm_nt(dtype, S, rc * d, 2 * F, p->theta, p->ldt, psi, p->ldt, gc, ldg, 1.0, GPX_FULL, 0, 0, p->st));
+        GPX_TRY(kapply_grad(dtype, dxo, rc, p->pts, p->n, d, p->iso, col_div, p->V, p->ldv, S, gc, ldg, p->st));
+        GPX_TRY(download_f64(dtype, grad + r0 * d, m * d, gc, ldg, S, rc * d, 0, p->st));
+        if (values) {                                     // gpx_paths_eval's steps on the same uploaded chunk
+            GPX_TRY(rff_features(dtype, dxo, rc, d, p->omega, F, p->scale, phi, p->ldt, p->st));
+            GPX_HIP(hipMemsetAsync(outc, 0, (size_t)S * ldo * es, p->st));
+            GPX_TRY(gemm_nt(dtype, S, rc, 2 * F, p->theta, p->ldt, phi, p->ldt, outc, ldo, 1.0, GPX_FULL, 0, 0, p->st));
+            GPX_TRY(kmat_apply(dtype, GPX_KERNEL_GAUSSIAN, dxo, rc, p->pts, p->n, d, p->iso, p->V, p->ldv, S, outc, ldo, p->st));
+            GPX_TRY(download_f64(dtype, values + r0, m, outc, ldo, S, rc, 0, p->st));
+        }
     }
     return GPX_OK;
 }

@@ -1,9 +1,9 @@
 // gpx_stream.hip -- the streamed reductions over the training set (gfx950): a few test points against ALL of x, which
 // passes through LDS in chunks of 256 points.  The fused posterior mean (stream_mean_kernel: gpx_d_mean, gpx_d_mean_member),
-// the fused route of gpx_d_kmat_apply (stream_apply_kernel) and the fused input-space gradient (pred_grad_kernel:
-// gpx_d_pred_grad) -- three kernels from the same pieces -- with the slice plan, the partial-sum scratch and the sliced
-// launcher they share.  The pieces (chunk staging, pair term, entry functions, block sum) are gpx_kernels_dev.h's; DESIGN
-// "Streamed reductions".
+// the fused route of gpx_d_kmat_apply (stream_apply_kernel), the fused input-space gradient (pred_grad_kernel:
+// gpx_d_pred_grad) and that gradient for several weight vectors at once (stream_apply_grad_kernel: gpx_d_kmat_apply_grad) --
+// four kernels from the same pieces -- with the slice plan, the partial-sum scratch and the sliced launcher they share.  The
+// pieces (chunk staging, pair term, entry functions, block sum) are gpx_kernels_dev.h's; DESIGN "Streamed reductions".
 #include "gpx_common.h"
 #include "gpx_kernels_dev.h"
 #include <algorithm>
@@ -26,8 +26,8 @@ static SlicePlan slice_plan(int64_t groups, int64_t n)
 
 // The slices' partial sums of every launcher below.  A block is this host thread's on one device, and every entry that
 // reaches it holds a StreamTurn: the thread's calls use it one after another on ONE stream at a time, so a pass's partial
-// sums are consumed by its reduce kernel before the next pass on that stream writes them (mean, pred_grad and the fused
-// kmat_apply never nest: none of them calls another).  The product route of kmat_apply keeps a block of its own
+// sums are consumed by its reduce kernel before the next pass on that stream writes them (mean, pred_grad, the fused
+// kmat_apply and kmat_apply_grad never nest: none of them calls another).  The product route of kmat_apply keeps a block of its own
 // (gpx_paths.hip): that one is live across a gpx_d_kmat call.
 static thread_local ThreadScratch g_partial_scr;
 
@@ -213,18 +213,17 @@ __global__ __launch_bounds__(256) void apply_reduce_kernel(const double *__restr
     }
 }
 
-// the launch both kernels share: the slice plan over `groups` workgroups, the partial sums (always == false: only when there is
-// more than one slice), the LDS limit, and the slices' reduction
-template <typename T, bool ADD, typename Launch>
-static int launch_sliced(int64_t groups, int64_t n, int d, int64_t S, int64_t m, bool always, const void *kernel_fn, void *out, int64_t ldo,
-                         hipStream_t st, Launch launch)
+// the launch every sliced kernel but pred_grad's shares: the slice plan over `groups` workgroups, the partial sums -- `cols` doubles
+// a slice; always == false: only when there is more than one slice --, the LDS limit, and the slices' reduction
+template <typename Launch, typename Reduce>
+static int launch_sliced_with(int64_t groups, int64_t n, size_t smem, size_t cols, bool always, const void *kernel_fn, Launch launch,
+                              Reduce reduce)
 {
-    const size_t smem = (size_t)d * MCP * sizeof(T);
     const SlicePlan sp = slice_plan(groups, n);
     double *partial = nullptr;
     if (always || sp.nslice > 1) {
         void *scr = nullptr;
-        GPX_TRY(g_partial_scr.get((size_t)sp.nslice * S * m * sizeof(double), &scr));
+        GPX_TRY(g_partial_scr.get((size_t)sp.nslice * cols * sizeof(double), &scr));
         partial = (double *)scr;
     }
     // (set_max_lds sets a kernel's limit ONCE per device, so it gets the constant, never the d-dependent size of one call)
@@ -232,11 +231,21 @@ static int launch_sliced(int64_t groups, int64_t n, int d, int64_t S, int64_t m,
     launch(sp, smem, partial);
     GPX_LAUNCH_CHECK();
     if (partial) {
-        const dim3 rgrid((unsigned)cdiv(m, 256), (unsigned)std::min<int64_t>(S, 32768));
-        hipLaunchKernelGGL((apply_reduce_kernel<T, ADD>), rgrid, dim3(256), 0, st, partial, (int)sp.nslice, S, m, (T *)out, ldo);
+        reduce(partial, (int)sp.nslice);
         GPX_LAUNCH_CHECK();
     }
     return GPX_OK;
+}
+
+// ... for the two apply kernels: the chunk of x in LDS, S x m sums a slice, apply_reduce_kernel
+template <typename T, bool ADD, typename Launch>
+static int launch_sliced(int64_t groups, int64_t n, int d, int64_t S, int64_t m, bool always, const void *kernel_fn, void *out, int64_t ldo,
+                         hipStream_t st, Launch launch)
+{
+    return launch_sliced_with(groups, n, (size_t)d * MCP * sizeof(T), (size_t)S * m, always, kernel_fn, launch, [&](double *partial, int nslice) {
+        const dim3 rgrid((unsigned)cdiv(m, 256), (unsigned)std::min<int64_t>(S, 32768));
+        hipLaunchKernelGGL((apply_reduce_kernel<T, ADD>), rgrid, dim3(256), 0, st, partial, nslice, S, m, (T *)out, ldo);
+    });
 }
 
 template <typename T, typename EV>
@@ -517,6 +526,199 @@ int pred_grad(int dtype, int kernel, const void *xo, int64_t m, const void *x, i
     return launch_pred_grad<float>(kernel, xo, m, x, n, d, kp, alpha, B, ldb, scale, col_div, out_dev, st);
 }
 
+// ---------------------------------------------------------------------------
+// The input-space gradient of K(xo, x) applied to S weight vectors (gpx_d_kmat_apply_grad; gaussian only):
+//   out[s, i d + k] += (1 / div_k) sum_j V[s, j] dk(xo_i, x_j)/dxo_ik,        dk/da_k = -(a_k - b_k) / w^2 * k
+// pred_grad_kernel's pair loop with stream_apply_kernel's register block of weight vectors: workgroup (bx, by, bz) owns PTS
+// test points and the window of DP dimensions bx % W (windows are the fast index: neighbours share their points and slice),
+// the by-th slice of the training set and the bz-th group of SV weight vectors.  Per pair the lane forms the distance over ALL d
+// dimensions once and k_ij once (GaussianEval<T, 0>: the element gpx_d_kmat would store, clamp included: a clamped pair adds
+// exactly 0); per chunk it loads V[s0 .. s0 + SV, j] once (coalesced across the lanes, zero beyond S); g_s = k_ij V[s, j] in
+// f64, and for each dimension of the window the difference a_k - b_k itself times g_s into one of PTS x SV x DP <= KG_ACC f64
+// accumulators.  This window's coordinates of the test points live in vector registers, staged through LDS (pred_grad_kernel
+// says why).  Lanes are added by shuffles, waves through LDS, slices by apply_grad_reduce_kernel -- which also applies -1 / w^2,
+// the division, the += and the one rounding to T -- all in a fixed order: no atomics, bitwise repeatable.
+// ---------------------------------------------------------------------------
+constexpr int KG_ACC = 32;         // f64 accumulators per lane at most: stream_apply_kernel's budget
+
+template <typename T, int PTS, int SV, int DP>
+__global__ __launch_bounds__(256) void stream_apply_grad_kernel(const T *__restrict__ xo, int64_t m, const T *__restrict__ x, int64_t n,
+                                                                int d, int W, KParams kp, const T *__restrict__ V, int64_t ldv, int64_t S,
+                                                                int64_t slice_len, double *__restrict__ partial)
+{
+    static_assert(PTS * SV * DP <= KG_ACC, "the register block is at most KG_ACC f64 accumulators");
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    T *sx = reinterpret_cast<T *>(smem_raw);            // [d][MCP] chunk of x, transposed
+    __shared__ double red[4][PTS * SV * DP];
+
+    const int tid = threadIdx.x;
+    const int64_t pg = (int64_t)blockIdx.x / W;
+    const int64_t p0 = pg * PTS;
+    const int kbeg = (int)((int64_t)blockIdx.x - pg * W) * DP;   // this workgroup's window of dimensions
+    const int64_t s0 = (int64_t)blockIdx.z * SV;
+    double acc[PTS][SV][DP];
+#pragma unroll
+    for (int pp = 0; pp < PTS; ++pp)
+#pragma unroll
+        for (int sv = 0; sv < SV; ++sv)
+#pragma unroll
+            for (int kk = 0; kk < DP; ++kk) acc[pp][sv][kk] = 0.0;
+
+    T *sa = sx + (size_t)d * MCP;                       // [PTS][d]: the group's test points
+    for (int idx = tid; idx < PTS * d; idx += 256) {
+        const int pp = PTS == 1 ? 0 : idx / d;
+        sa[idx] = xo[min(p0 + pp, m - 1) * d + (idx - pp * d)];
+    }
+    __syncthreads();
+    T av[PTS][DP];
+#pragma unroll
+    for (int pp = 0; pp < PTS; ++pp)
+#pragma unroll
+        for (int kk = 0; kk < DP; ++kk) av[pp][kk] = (kbeg + kk < d) ? sa[pp * d + kbeg + kk] : (T)0;
+
+    const GaussianEval<T, 0> ev(kp);
+    const int qd = 256 / d, rd = 256 - qd * d;          // idx += 256  <=>  (c, k) += (qd, rd) with carry
+    const int cst = tid / d, kst = tid - cst * d;
+    const int64_t jbeg = (int64_t)blockIdx.y * slice_len, jend = min(n, jbeg + slice_len);
+    for (int64_t j0 = jbeg; j0 < jend; j0 += 256) {
+        __syncthreads();
+        {
+            const int64_t lim = (jend - j0) * d;
+            const T *g = x + j0 * d;
+            GPX_STAGE_POINTS_TRANSPOSED(sx, MCP, g, 256 * d, lim, d, tid, qd, rd, cst, kst);
+        }
+        __syncthreads();
+        const int64_t j = j0 + tid;
+        if (j < jend) {
+            double vj[SV];
+#pragma unroll
+            for (int sv = 0; sv < SV; ++sv) vj[sv] = (s0 + sv < S) ? (double)V[(s0 + sv) * ldv + j] : 0.0;
+            T r[PTS];
+#pragma unroll
+            for (int pp = 0; pp < PTS; ++pp) r[pp] = (T)0;
+#pragma unroll 2
+            for (int k = 0; k < d; ++k) {
+                const T b = sx[(size_t)k * MCP + tid];
+#pragma unroll
+                for (int pp = 0; pp < PTS; ++pp) { const T a = sa[pp * d + k]; r[pp] = ev.step(a, b, r[pp]); }
+            }
+            double g[PTS][SV];
+#pragma unroll
+            for (int pp = 0; pp < PTS; ++pp) {
+                const double kd = (double)ev.entry(r[pp]);
+#pragma unroll
+                for (int sv = 0; sv < SV; ++sv) g[pp][sv] = kd * vj[sv];
+            }
+#pragma unroll
+            for (int kk = 0; kk < DP; ++kk) {
+                if (kbeg + kk < d) {                                      // (uniform: d and the window are scalars)
+                    const T b = sx[(size_t)(kbeg + kk) * MCP + tid];
+#pragma unroll
+                    for (int pp = 0; pp < PTS; ++pp) {
+                        const double f = (double)(av[pp][kk] - b);
+#pragma unroll
+                        for (int sv = 0; sv < SV; ++sv) acc[pp][sv][kk] = fma(g[pp][sv], f, acc[pp][sv][kk]);
+                    }
+                }
+            }
+        }
+    }
+    // wave reduction (64 lanes), then across the 4 waves in a fixed order
+    block_sum_fixed(reinterpret_cast<const double (&)[PTS * SV * DP]>(acc), red, tid);          // (acc as [(pp * SV + sv) * DP + kk])
+    __syncthreads();
+    if (tid < PTS * SV * DP) {
+        const int ps = tid / DP, kk = tid - ps * DP, pp = ps / SV, sv = ps - pp * SV;
+        if (p0 + pp < m && s0 + sv < S && kbeg + kk < d)
+            partial[(((int64_t)blockIdx.y * S + s0 + sv) * m + p0 + pp) * d + kbeg + kk] = block_sum_final(red, tid);
+    }
+}
+
+// out[s, e] += factor * sum over the slices (in slice order) [/ div.w[e % d]], e = i d + k; one rounding to T
+template <typename T, bool DIV>
+__global__ __launch_bounds__(256) void apply_grad_reduce_kernel(const double *__restrict__ partial, int nslice, int64_t S, int64_t md, int d,
+                                                                double factor, ArdWidths div, T *__restrict__ out, int64_t ldo)
+{
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= md) return;
+    for (int64_t s = blockIdx.y; s < S; s += gridDim.y) {
+        double sum = 0.0;
+        for (int y = 0; y < nslice; ++y) sum += partial[((int64_t)y * S + s) * md + e];
+        sum *= factor;
+        if (DIV) sum /= div.w[e % d];
+        out[s * ldo + e] = (T)((double)out[s * ldo + e] + sum);
+    }
+}
+
+// The register block of kmat_apply_grad by S and d: (test points per workgroup, vectors per lane, dimensions per window), at
+// most KG_ACC accumulators.  d <= 4: one window of 4, and the points make up the budget -- 4 x 1 x 4 (pred_grad_kernel's block),
+// 4 x 2 x 4, 2 x 4 x 4.  d > 4: one point -- 1 x 1 x 16 (pred_grad_kernel's block), 1 x 2 x 16, 1 x 4 x 8.  One or two vectors get
+// a block of their own: the lesson of kapply_shape -- a block of 4 vectors at S = 1 multiplies zeros in three of its four
+// f64 FMAs per difference.  DESIGN "Posterior paths" has the table and the compiler's resources.
+struct KgShape { int pts, sv, dp; };
+static inline KgShape kapply_grad_shape(int64_t S, int d)
+{
+    if (d <= 4) return S == 1 ? KgShape{4, 1, 4} : (S == 2 ? KgShape{4, 2, 4} : KgShape{2, 4, 4});
+    return S == 1 ? KgShape{1, 1, 16} : (S == 2 ? KgShape{1, 2, 16} : KgShape{1, 4, 8});
+}
+
+template <typename T, int PTS, int SV, int DP>
+static int launch_apply_grad(const void *xo, int64_t m, const void *x, int64_t n, int d, const KParams &kp, const ArdWidths &aw, bool div,
+                             const void *V, int64_t ldv, int64_t S, void *out, int64_t ldo, hipStream_t st)
+{
+    const int64_t W = cdiv(d, DP), gx = cdiv(m, PTS) * W, gz = cdiv(S, SV), md = m * d;
+    const double factor = 2.0 * kp.c[0];                // the derivative's constant: -1 / w^2 = 2 c1
+    ProfScope prof(PC_KAPPLY_GRAD, (double)m * (double)n * (double)gz * (double)W, st);
+    // (LDS: the chunk of x and the group's test points; the largest d whose chunk fits leaves room for them: fp64 d = 47: 97008
+    // bytes, fp32 d = 95: 98040)
+    return launch_sliced_with(gx * gz, n, (size_t)d * (MCP + PTS) * sizeof(T), (size_t)S * md, true,
+                              (const void *)stream_apply_grad_kernel<T, PTS, SV, DP>,
+                              [&](const SlicePlan &sp, size_t smem, double *partial) {
+        hipLaunchKernelGGL((stream_apply_grad_kernel<T, PTS, SV, DP>), dim3((unsigned)gx, (unsigned)sp.nslice, (unsigned)gz), dim3(256), smem, st,
+                           (const T *)xo, m, (const T *)x, n, d, (int)W, kp, (const T *)V, ldv, S, sp.slice_len, partial);
+    }, [&](double *partial, int nslice) {
+        const dim3 rgrid((unsigned)cdiv(md, 256), (unsigned)std::min<int64_t>(S, 32768));
+        if (div) hipLaunchKernelGGL((apply_grad_reduce_kernel<T, true>), rgrid, dim3(256), 0, st, partial, nslice, S, md, d, factor, aw, (T *)out, ldo);
+        else hipLaunchKernelGGL((apply_grad_reduce_kernel<T, false>), rgrid, dim3(256), 0, st, partial, nslice, S, md, d, factor, aw, (T *)out, ldo);
+    });
+}
+
+template <typename T>
+static int kapply_grad_t(const void *xo, int64_t m, const void *x, int64_t n, int d, const KParams &kp, const double *col_div,
+                         const void *V, int64_t ldv, int64_t S, void *out, int64_t ldo, hipStream_t st)
+{
+    ArdWidths aw;
+    for (int k = 0; k < GPX_ARD_MAX_D; ++k) aw.w[k] = (col_div && k < d) ? col_div[k] : 1.0;
+    const KgShape sh = kapply_grad_shape(S, d);
+#define GPX_KGRAD_LAUNCH(P, V_, D) return launch_apply_grad<T, P, V_, D>(xo, m, x, n, d, kp, aw, col_div != nullptr, V, ldv, S, out, ldo, st)
+    if (sh.dp == 4) {
+        if (sh.sv == 1) GPX_KGRAD_LAUNCH(4, 1, 4);
+        if (sh.sv == 2) GPX_KGRAD_LAUNCH(4, 2, 4);
+        GPX_KGRAD_LAUNCH(2, 4, 4);
+    }
+    if (sh.sv == 1) GPX_KGRAD_LAUNCH(1, 1, 16);
+    if (sh.sv == 2) GPX_KGRAD_LAUNCH(1, 2, 16);
+    GPX_KGRAD_LAUNCH(1, 4, 8);
+#undef GPX_KGRAD_LAUNCH
+}
+
+int kapply_grad(int dtype, const void *xo, int64_t m, const void *x, int64_t n, int d, const double *params, const double *col_div,
+                const void *V, int64_t ldv, int64_t S, void *out, int64_t ldo, hipStream_t st)
+{
+    if (m <= 0 || S <= 0 || n <= 0) return GPX_OK;
+    if ((size_t)d * MCP * esize(dtype) > (size_t)LDS_CHUNK_MAX) {     // the mean's range of d
+        set_error("kmat_apply_grad: d = %d too large", d);
+        return GPX_ERR_UNSUPPORTED;
+    }
+    if (col_div && d > GPX_ARD_MAX_D) { set_error("kmat_apply_grad: column divisors need d <= %d (got %d)", GPX_ARD_MAX_D, d); return GPX_ERR_ARG; }
+    const KgShape sh = kapply_grad_shape(S, d);
+    if (cdiv(S, sh.sv) > 65535) { set_error("kmat_apply_grad: S = %lld is more groups of weight vectors than one launch covers", (long long)S); return GPX_ERR_ARG; }
+    if (cdiv(m, sh.pts) > 0x7fffffff / cdiv(d, sh.dp)) { set_error("kmat_apply_grad: m is more than one launch covers"); return GPX_ERR_ARG; }
+    KParams kp;
+    GPX_TRY(make_kparams(GPX_KERNEL_GAUSSIAN, GPX_K, params, 0.0, &kp));
+    if (dtype == GPX_F64) return kapply_grad_t<double>(xo, m, x, n, d, kp, col_div, V, ldv, S, out, ldo, st);
+    return kapply_grad_t<float>(xo, m, x, n, d, kp, col_div, V, ldv, S, out, ldo, st);
+}
+
 }  // namespace gpx
 
 using namespace gpx;
@@ -570,6 +772,24 @@ int gpx_d_pred_grad(int dtype, int kernel, const void *xo, int64_t m, const void
         return pred_grad(dtype, GPX_KERNEL_GAUSSIAN, s1, m, s2, n, d, iso, alpha, B, ldb, scale, params + 1, out_dev, S(stream));
     }
     return pred_grad(dtype, kernel, xo, m, x, n, d, params, alpha, B, ldb, scale, nullptr, out_dev, S(stream));
+}
+
+int gpx_d_kmat_apply_grad(int dtype, int kernel, const void *xo, int64_t m, const void *x, int64_t n, int d, const double *params,
+                          const double *col_div, const void *V, int64_t ldv, int64_t Sn, void *out, int64_t ldo, void *stream)
+{
+    gpx::StreamTurn turn__((hipStream_t)stream);     // (this thread's scratch buffers: one stream at a time, gpx_mem.h)
+    GPX_TRY(ensure_device());
+    GPX_ARG(dtype == GPX_F64 || dtype == GPX_F32, "dtype must be GPX_F64 or GPX_F32");
+    GPX_ARG(n >= 0 && m >= 0 && Sn >= 0 && d >= 1, "need n, m, S >= 0 and d >= 1");
+    if (kernel != GPX_KERNEL_GAUSSIAN) {
+        set_error("gpx_d_kmat_apply_grad: kernel family %d is not supported (GPX_KERNEL_GAUSSIAN; the ARD family on scaled points with col_div = w)", kernel);
+        return GPX_ERR_UNSUPPORTED;
+    }
+    if (m == 0 || Sn == 0 || n == 0) return GPX_OK;
+    GPX_ARG(xo && x && V && out && params, "NULL pointer");
+    GPX_ARG(m <= INT64_MAX / d && ldv >= n && ldo >= m * d, "leading dimension too small");
+    GPX_ARG(Sn <= INT64_MAX / ldv && Sn <= (INT64_MAX / 8) / ldo, "S * ld overflows");
+    return kapply_grad(dtype, xo, m, x, n, d, params, col_div, V, ldv, Sn, out, ldo, S(stream));
 }
 
 }  // extern "C"

@@ -784,8 +784,12 @@ class GP(object):
         and a copy of `x`).  The result does not refer to this GP again.
 
         `GaussianKernel` and `GaussianARDKernel` only: NotImplementedError for `PeriodicKernel` and for plugin kernels.
-        Raises numpy.linalg.LinAlgError when `Kxx` is not positive definite.  Not offered: gradients of a path with respect
-        to the input, `DistributedGP`, persistence of paths."""
+        Raises numpy.linalg.LinAlgError when `Kxx` is not positive definite.
+
+        The paths are differentiable in their input: ``paths.grad(xo) -> (size,) + xo.shape`` and
+        ``paths.value_and_grad(xo) -> (values, grad)`` give :math:`\partial f_s / \partial a_k` at every point from one
+        fused pass, so a draw can be maximised by a gradient-based multi-start optimiser rather than by central differences.
+        Not offered: second derivatives, `DistributedGP`, persistence of paths."""
         from .paths import PosteriorPaths
         if isinstance(size, bool) or not isinstance(size, (int, np.integer)) or size < 0:    # every refusal comes before the library is touched
             raise ValueError("invalid value for size: %r (an int >= 0)" % (size,))

@@ -23,8 +23,17 @@ The approximation lies in the prior only -- its covariance error is ``O(k0 / sqr
 The draws are of the LATENT function: observation noise is not added to the values.  Memory held: ``size x n`` weights,
 ``size x 2F`` feature weights, ``F x d`` frequencies and a copy of the ``n x d`` points, all on the device.
 
-Out of scope: gradients of a path with respect to the input, the periodic family (an exact Fourier-series prior exists for
-it), plugin kernels, `DistributedGP`, and persistence -- a paths object is regenerated from its seed, not copied or pickled.
+A path is differentiable in its input, and the derivative is as cheap as the value -- with `p` the view's points,
+
+    d f_s / d a_k (a) = sqrt(k0 / F) sum_f Omega[f, k] (Theta[s, F + f] cos(Omega_f . a) - Theta[s, f] sin(Omega_f . a))
+                        - 1 / w_v^2 sum_j V[s, j] (a_k - p_jk) k(a, p_j)
+
+(ARD: on ``a / w``, component `k` divided by ``w_k``) -- so a draw can be maximised by a gradient-based multi-start optimiser
+instead of central differences: `PosteriorPaths.grad` and `PosteriorPaths.value_and_grad` form every kernel value once per
+group of paths and window of dimensions, where ``2 d + 1`` calls of the paths form it ``2 d + 1`` times.
+
+Out of scope: second derivatives, the periodic family (an exact Fourier-series prior exists for it), plugin kernels,
+`DistributedGP`, and persistence -- a paths object is regenerated from its seed, not copied or pickled.
 """
 import ctypes
 
@@ -48,10 +57,10 @@ class PosteriorPaths(object):
         self.size, self.features, self.seed, self.n, self.d = size, features, seed, n, d
         self._ndim = ndim              # of the GP's x: 1 -> xo is (m,), 2 -> (m, d)
 
-    def __call__(self, xo, chunk_rows=0):
-        """The draws at `xo` (``(m,)`` for 1-D inputs or ``(m, d)``): ``(size, m)`` float64.  ``chunk_rows``: test points per
-        device chunk, 0 (automatic) or a multiple of 128."""
-        xo = np.ascontiguousarray(xo, dtype=DTYPE)             # every refusal comes before the library is touched
+    def _checked(self, xo, chunk_rows):
+        """`xo` as a contiguous float64 array and its number of points, after the refusals `__call__`, `grad` and
+        `value_and_grad` share -- every one of them comes before the library is touched."""
+        xo = np.ascontiguousarray(xo, dtype=DTYPE)
         d = 1 if xo.ndim == 1 else xo.shape[1] if xo.ndim == 2 else -1
         if xo.ndim not in (1, 2) or d != self.d or (xo.ndim == 1 and self._ndim == 2):
             raise ValueError("invalid shape for xo: %s" % str(xo.shape))
@@ -59,10 +68,31 @@ class PosteriorPaths(object):
             raise ValueError("invalid value for chunk_rows: %r (0, or a multiple of 128)" % (chunk_rows,))
         if not self._handle:
             raise ValueError("the paths have been closed")
-        m = xo.shape[0]
+        return xo, xo.shape[0]
+
+    def __call__(self, xo, chunk_rows=0):
+        """The draws at `xo` (``(m,)`` for 1-D inputs or ``(m, d)``): ``(size, m)`` float64.  ``chunk_rows``: test points per
+        device chunk, 0 (automatic) or a multiple of 128."""
+        xo, m = self._checked(xo, chunk_rows)
         out = np.empty((self.size, m), dtype=DTYPE)
         _lib.check(_lib.load().gpx_paths_eval(self._handle, _lib.dptr(xo), m, int(chunk_rows), _lib.dptr(out)))
         return out
+
+    def grad(self, xo, chunk_rows=0):
+        """The gradients of the draws with respect to the input at `xo`: ``(size,) + xo.shape`` float64 -- ``(size, m)`` for
+        1-D inputs, ``(size, m, d)`` otherwise; ``[s, i, k]`` is ``d f_s / d xo_ik``.  `xo` and ``chunk_rows`` as for a call."""
+        xo, m = self._checked(xo, chunk_rows)
+        grad = np.empty((self.size,) + xo.shape, dtype=DTYPE)
+        _lib.check(_lib.load().gpx_paths_grad(self._handle, _lib.dptr(xo), m, int(chunk_rows), None, _lib.dptr(grad)))
+        return grad
+
+    def value_and_grad(self, xo, chunk_rows=0):
+        """``(values (size, m), grad)``: what a call and `grad` return for the same arguments, bit for bit, from one upload of
+        the points -- what a gradient-based optimiser asks for at every step."""
+        xo, m = self._checked(xo, chunk_rows)
+        values, grad = np.empty((self.size, m), dtype=DTYPE), np.empty((self.size,) + xo.shape, dtype=DTYPE)
+        _lib.check(_lib.load().gpx_paths_grad(self._handle, _lib.dptr(xo), m, int(chunk_rows), _lib.dptr(values), _lib.dptr(grad)))
+        return values, grad
 
     def state(self):
         """Diagnostic: ``(Omega (F, d), Theta (size, 2F), V (size, n))`` as float64 host copies (``gpx_paths_get``; the tests pin

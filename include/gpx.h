@@ -176,6 +176,7 @@ int gpx_stream_wait_event(void *stream, void *event);
 #define GPX_PROF_RANDN       14 /* randn_kernel (gpx_d_randn): bytes written */
 #define GPX_PROF_RFF         15 /* rff_features_kernel (gpx_d_rff_features): bytes written */
 #define GPX_PROF_KAPPLY      16 /* stream_apply_kernel + its slice reduction (gpx_d_kmat_apply, fused route): kernel evaluations m*n per group of weight vectors */
+#define GPX_PROF_KAPPLY_GRAD 17 /* stream_apply_grad_kernel + its slice reduction (gpx_d_kmat_apply_grad): kernel evaluations m*n per group of weight vectors and window of dimensions */
 int gpx_prof_enable(int on);    /* also clears the registry */
 int gpx_prof_read(int cls, double *launches, double *total_ms, double *total_work);
 
@@ -206,6 +207,7 @@ int gpx_prof_read(int cls, double *launches, double *total_ms, double *total_wor
 #define GPX_ROUTE_SAMPLE         20   /* gpx_gp_sample / gpx_gp_sample_from_K: one hit per call                        */
 #define GPX_ROUTE_KAPPLY_FUSED   21   /* gpx_d_kmat_apply: K(xo, x) V^T by the fused kernel, K never materialised; one hit per chunk */
 #define GPX_ROUTE_KAPPLY_GEMM    22   /* gpx_d_kmat_apply: gpx_d_kmat into scratch, then gpx_d_gemm_nt; one hit per row chunk of xo  */
+#define GPX_ROUTE_PATHS_GRAD_CHUNK 23 /* gpx_paths_grad: one hit per row chunk of xo                                                   */
 int gpx_debug_route_count(int route, int64_t *count);
 /* roctx ranges pushed so far (GPX_ROCTX=1: every gpx_gp_* call and every launch class below it is a nested host range for
  * `rocprofv3 --marker-trace`; libroctx64.so is loaded on first use; 0 while the switch is off) */
@@ -426,6 +428,17 @@ int gpx_d_mvn_sample(int dtype, void *C, int64_t m, int64_t ldc, const void *mea
 int gpx_d_rff_features(int dtype, const void *pts, int64_t m, int d, const double *omega_dev, int64_t F, double scale,
                        void *out, int64_t ld, void *stream);
 
+/* The derivative of that feature map with respect to the point, as a matrix gpx_d_gemm_nt can consume -- row i d + k is
+ * d phi(p_i) / d p_ik:
+ *   out[i d + k, f]     = -(scale / div_k) omega[f, k] sin(omega_f . p_i)
+ *   out[i d + k, F + f] =  (scale / div_k) omega[f, k] cos(omega_f . p_i)        i < m, k < d, f < F
+ * out: (m d, 2F) with ld >= 2F in `dtype`; the padding [2F, ld) is not written.  col_div: HOST, d doubles
+ * (d <= GPX_ARD_MAX_D), or NULL for no division (the ARD family on scaled points: div = w).  gpx_d_rff_features'
+ * conventions otherwise: fp64 projection and sincos for both dtypes -- formed once per (i, f), not d times -- one
+ * rounding on the store, frequencies along the lanes.  One launch; GPX_PROF_RFF (bytes written). */
+int gpx_d_rff_features_grad(int dtype, const void *pts, int64_t m, int d, const double *omega_dev, int64_t F, double scale,
+                            const double *col_div, void *out, int64_t ld, void *stream);
+
 /* out[s, i] += sum_j K(xo_i, x_j) V[s, j]   for s < S, i < m:  the kernel matrix applied to S weight vectors at once,
  * accumulated INTO out.  xo: (m, d), x: (n, d) densely packed; V: (S, n) ldv; out: (S, m) ldo; all DEVICE in `dtype`.
  * Member GPX_K of GPX_KERNEL_GAUSSIAN and GPX_KERNEL_PERIODIC (any d gpx_d_mean takes); GPX_KERNEL_GAUSSIAN_ARD callers pass
@@ -442,6 +455,26 @@ int gpx_d_rff_features(int dtype, const void *pts, int64_t m, int d, const doubl
  * m == 0, S == 0 or n == 0 leaves out as it is. */
 int gpx_d_kmat_apply(int dtype, int kernel, const void *xo, int64_t m, const void *x, int64_t n, int d,
                      const double *params, const void *V, int64_t ldv, int64_t S, void *out, int64_t ldo, void *stream);
+
+/* out[s, i d + k] += (1 / div_k) sum_j V[s, j] dk(xo_i, x_j)/dxo_ik   for s < S, i < m, k < d:  the input-space gradient
+ * of the kernel matrix applied to S weight vectors at once, accumulated INTO out; dK is never materialised and each
+ * k(xo_i, x_j) is formed once per group of vectors and window of dimensions.  xo: (m, d), x: (n, d) densely packed; V: (S, n)
+ * ldv; out: (S, m d) ldo; all DEVICE in `dtype`, any base and pitch of V and out.  col_div: HOST, d doubles
+ * (d <= GPX_ARD_MAX_D), or NULL for no division.  GPX_KERNEL_GAUSSIAN only (dk/da_k = -(a_k - b_k) / w^2 k):
+ * GPX_KERNEL_GAUSSIAN_ARD callers pass scaled points, the isotropic constants and col_div = w; the periodic and ARD ids
+ * return GPX_ERR_UNSUPPORTED.  Every d gpx_d_mean takes for the dtype, GPX_ERR_UNSUPPORTED beyond; every S: groups of
+ * weight vectors go on the grid's z (more than 65535 groups: GPX_ERR_ARG).
+ * A workgroup owns a few test points, a slice of x streamed through LDS and a window of dimensions, every lane one training
+ * point and a register block of weight vectors (at most 32 f64 sums per lane; the block by S and d: DESIGN "Posterior
+ * paths").  Per pair the distance over all d dimensions and k_ij -- the entry function of gpx_d_kmat, underflow clamp
+ * included: a clamped pair adds exactly 0 -- are formed once, g_s = k_ij V[s, j] in f64, and every difference a_k - b_k
+ * directly.  f64 sums for both dtypes; lanes by shuffles, waves through LDS, slices in ascending order by a second launch,
+ * which also applies -1 / w^2, the division, the += and the one rounding to `dtype`: no atomics, bitwise repeatable.
+ * There is no product route (dK is d times the size of K).  GPX_PROF_KAPPLY_GRAD.
+ * m == 0, S == 0 or n == 0 leaves out as it is. */
+int gpx_d_kmat_apply_grad(int dtype, int kernel, const void *xo, int64_t m, const void *x, int64_t n, int d,
+                          const double *params, const double *col_div, const void *V, int64_t ldv, int64_t S, void *out,
+                          int64_t ldo, void *stream);
 
 /* ------------------------------------------------ fitted-GP device handle -- */
 /* One handle = one GP resident in HBM: x, y, the kernel matrix / its factor
@@ -657,6 +690,18 @@ int gpx_gp_paths_create(gpx_gp_t *gp, int64_t S, int64_t F, uint64_t seed, gpx_p
  * The chunk's device buffers belong to the paths handle and only ever grow: repeated evaluations allocate once.  One host thread
  * at a time per paths handle. */
 int gpx_paths_eval(gpx_paths_t *paths, const double *xo, int64_t m, int64_t chunk_rows, double *out);
+/* d f_s(xo_i) / d xo_ik -> grad (S, m, d) HOST float64, and with values != NULL also f_s(xo_i) -> values (S, m); xo (m, d)
+ * HOST float64.  On the handle's view (a = xo, or xo / w for ARD, whose component k is then divided by w_k):
+ *   d f_s / d a_k = sqrt(k0 / F) sum_f Omega[f, k] (Theta[s, F + f] cos(Omega_f . a) - Theta[s, f] sin(Omega_f . a))
+ *                   - 1 / w_v^2 sum_j V[s, j] (a_k - p_jk) k(a, p_j)
+ * gpx_paths_eval's contract: chunk_rows 0 (automatic) or a multiple of 128, m == 0 and S == 0 legal, the chunk's buffers
+ * carved from the handle's grow-only block, one host thread at a time per handle.  Per chunk (GPX_ROUTE_PATHS_GRAD_CHUNK,
+ * one hit each): upload (ARD: gpx_d_scale_points), gpx_d_rff_features_grad, the chunk's S x round_up(rows d, 16) block
+ * zeroed, Theta Psi_c^T into it by gpx_d_gemm_nt, gpx_d_kmat_apply_grad into the same block, one download.  With values the
+ * steps of gpx_paths_eval run on the same uploaded chunk: the values are bit for bit gpx_paths_eval's for the same
+ * chunk_rows.  Automatic chunk: the largest multiple of 128 rows, at most 4096, whose feature blocks -- rows (d + 1)
+ * round_up(2F, 16) elements -- fit 512 MiB, never fewer than 128; m <= that takes exactly one chunk. */
+int gpx_paths_grad(gpx_paths_t *paths, const double *xo, int64_t m, int64_t chunk_rows, double *values, double *grad);
 /* the state as HOST float64: omega (F, d), theta (S, 2F), V (S, n); any pointer may be NULL */
 int gpx_paths_get(gpx_paths_t *paths, double *omega, double *theta, double *V);
 /* any pointer may be NULL; kernel: the family of the GP the paths came from */
