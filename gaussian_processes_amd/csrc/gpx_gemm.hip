@@ -1131,13 +1131,17 @@ int syrk_bc(int dtype, int64_t n, int64_t row_begin, void *Cloc, int64_t ldc, in
     }
     // generic route: one launch per local block column
     for (int64_t c = cl0; c < cl1;) {
-        const int64_t w = std::min(nb - c % nb, cl1 - c), g = gcol(c);
+        const int64_t wb = std::min(nb - c % nb, cl1 - c), g = gcol(c);
         const int64_t rb = std::max(row_begin, g);
+        // Columns at global index n and beyond (the padding of a ragged last block column of the block-cyclic layout) have
+        // no row at or below them, and their rows of Pb do not exist: with the first panel they lie past the end of the
+        // panel buffer.  The product stops at column n.
+        const int64_t w = std::min(wb, n - g);
         if (rb < n)
             GPX_TRY(gemm_nt(dtype, n - rb, w, kb, (const char *)Pb + (rb - k0) * ldp * es, ldp,
                             (const char *)Pb + (g - k0) * ldp * es, ldp,
                             (char *)Cloc + (rb * ldc + c) * es, ldc, -1.0, GPX_LOWER, rb, g, st, 0, 0, bt));
-        c += w;
+        c += wb;
     }
     return GPX_OK;
 }

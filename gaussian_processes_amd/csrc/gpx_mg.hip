@@ -17,12 +17,14 @@
 // the backward substitution is right-looking over the block columns, one nb-vector broadcast per block.
 // logdet and the posterior mean are local sums plus one all-reduce.
 //
-// Communicator back-ends: (1) RCCL, loaded with dlopen at first use -- libgpx.so itself has no link-time
-// dependency on it, single-GPU users never load it; ranks are joined through an ncclUniqueId that the
+// Communicator kinds (MgComm, chosen once at creation): (1) RCCL, loaded with dlopen at first use -- libgpx.so itself
+// has no link-time dependency on it, single-GPU users never load it; ranks are joined through an ncclUniqueId that the
 // host distributes out of band (gpx_mg_unique_id on rank 0).  (2) host callbacks on DEVICE pointers
 // (gpx_mg_create_cb): the same C schedule over any transport -- the tests run it with several ranks on
-// ONE GPU over gloo, which RCCL cannot do.
+// ONE GPU over gloo, which RCCL cannot do.  (3) rehearsal (gpx_mg_create_rehearsal): no communication at all, one
+// rank's share beside stand-ins for what the others would send (MgRehearsal).
 #include "gpx_common.h"
+#include "gpx_gp_internal.h"   // upload_f64 / download_f64, nparams_of
 #include <dlfcn.h>
 #include <climits>
 #include <cmath>
@@ -175,9 +177,40 @@ __global__ void info_key_kernel(const int *__restrict__ info, int *__restrict__ 
 
 using namespace gpx;
 
-constexpr int GPX_MG_TIMING_N = 13;
 typedef int (*gpx_mg_bcast_fn)(void *user, void *dev_ptr, size_t bytes, int root, void *stream);
 typedef int (*gpx_mg_allreduce_fn)(void *user, void *dev_ptr, size_t count, int dtype, int op, void *stream);
+
+// Classes of the timing pairs, which are also the slots of gpx_mg::ms; from T_WAIT_MAX on, figures that gpx_mg_fit derives
+// (mg_harvest_timing).  multi_gpu.NativeDistributedGP.TIMING_KEYS_EX names the slots in this order.
+enum { T_BUILD = 0, T_FACTOR = 1, T_SOLVE = 2, T_REDUCE = 3, T_PANEL = 4, T_PACK = 5, T_BCAST = 6, T_UPDATE = 7,
+       T_WAIT = 8,          // the update stream sat idle in front of a panel (chunk) that had not arrived: EXPOSED chain time
+       T_WAIT_MAX = 9,      // the longest single such wait
+       T_WAITS_LONG = 10,   // the number of waits of more than 20 us
+       T_REH_MODEL = 11,    // rehearsal: the modelled transfer time the fit enqueued
+       T_REH_CHAIN = 12,    // rehearsal: the remote owners' chains it stood in for
+       GPX_MG_TIMING_N = 13 };
+
+// The communicator of a handle: its kind is chosen once, by the gpx_mg_create* that made the handle, and every collective
+// (mg_bcast, mg_allreduce, mg_bcast_panel) reads it here.
+enum MgCommKind { MG_COMM_RCCL, MG_COMM_CALLBACKS, MG_COMM_REHEARSAL };
+struct MgComm {
+    MgCommKind kind = MG_COMM_RCCL;
+    ncclComm_t rccl = nullptr;                    // RCCL: null before gpx_mg_connect and after gpx_mg_adopt_comm took it away
+    gpx_mg_bcast_fn cb_bcast = nullptr;           // callbacks
+    gpx_mg_allreduce_fn cb_allreduce = nullptr;
+    void *cb_user = nullptr;
+    gpx::GrowBuf sag_tmp;                         // callbacks, scatter + all-gather: where a rank drops pieces that are not its own
+};
+// REHEARSAL of one rank's share of a `world`-rank run in ONE process (gpx_mg_create_rehearsal): a panel this rank does not
+// own is copied out of a resident factor of the same matrix (L: n + 1 rows, the rider row included), an alpha block out of
+// the resident solution, and every broadcast is followed by a delay that models the transfer at GBps per xGMI link
+struct MgRehearsal {
+    const void *L = nullptr; int64_t ld = 0;
+    const void *alpha = nullptr;
+    double GBps = 100.0, lat_us = 20.0;
+    double model_ms = 0;                          // modelled transfer time enqueued by the last fit (all panel broadcasts)
+    double chain_ms = 0;                          // modelled remote-owner chain time enqueued by the last fit
+};
 
 struct gpx_mg {
     int device, dtype, kernel, d, world, rank;
@@ -185,17 +218,13 @@ struct gpx_mg {
     size_t es;
     std::vector<int64_t> my_blocks;
     std::vector<gpx::TrsvOps> ops;                // per owned block column: inverse of its diagonal block (backward solve)
-    // communicator
-    ncclComm_t comm = nullptr;
-    gpx_mg_bcast_fn cb_bcast = nullptr;
-    gpx_mg_allreduce_fn cb_allreduce = nullptr;
-    void *cb_user = nullptr;
+    MgComm comm;                                  // its kind is mg_new's argument and never changes
+    MgRehearsal reh;                             // comm.kind == MG_COMM_REHEARSAL only
     int bcast_chunks = 4;
     int bcast_sag = 0;                            // panel broadcast as scatter + all-gather (GPX_MG_BCAST=sag / gpx_mg_set_bcast)
     int owner_first = 0;                          // the owner of the next panel factors it BEFORE it starts its own trailing update
                                                   // (gpx_mg_set_owner_first / GPX_MG_OWNER_FIRST; see mg_factor)
     hipEvent_t last_panel_ev = nullptr;           // behind the last panel this rank factored (stream Q)
-    gpx::GrowBuf sag_tmp;                          // callback back-end only: where a rank drops pieces that are not its own
     int debug_info = 0;                           // gpx_debug_mg_inject_info: written into the device info word after the factorisation
     // device state
     void *A = nullptr, *pbuf[2] = {nullptr, nullptr}, *x = nullptr, *y = nullptr, *alpha = nullptr, *tmp = nullptr;
@@ -213,18 +242,9 @@ struct gpx_mg {
     bool have_data = false, fitted = false;
     double logdet = 0, yta = 0;
     int info_host = 0;
-    double ms[GPX_MG_TIMING_N] = {0};            // 0 .. 7: stages and chain (gpx_mg_timing); 8 .. 10: exposed waits (gpx_mg_timing_ex)
+    double ms[GPX_MG_TIMING_N] = {0};            // indexed by T_* (gpx_mg_timing: the first 8; gpx_mg_timing_ex: all)
     bool timing = true;
     bool wait_timing = false;                     // T_WAIT pairs around the update stream's waits (gpx_mg_set_wait_timing): opt-in
-    // REHEARSAL of one rank's share of a `world`-rank run in ONE process (gpx_mg_create_rehearsal): no communicator; a
-    // panel this rank does not own is copied out of a resident factor of the same matrix (reh_L: n + 1 rows, the rider row
-    // included), and every broadcast is followed by a delay that models the transfer at reh_GBps per xGMI link
-    bool rehearse = false;
-    const void *reh_L = nullptr; int64_t reh_ld = 0;
-    const void *reh_alpha = nullptr;
-    double reh_GBps = 100.0, reh_lat_us = 20.0;
-    double reh_model_ms = 0;                      // modelled transfer time enqueued by the last fit (all panel broadcasts)
-    double reh_chain_ms = 0;                      // modelled remote-owner chain time enqueued by the last fit
 
     int64_t owner(int64_t j) const { return j % world; }
     int64_t local_col(int64_t j) const { return (j / world) * nb; }
@@ -239,9 +259,6 @@ struct gpx_mg {
 };
 
 namespace gpx {
-
-enum { T_BUILD = 0, T_FACTOR = 1, T_SOLVE = 2, T_REDUCE = 3, T_PANEL = 4, T_PACK = 5, T_BCAST = 6, T_UPDATE = 7,
-       T_WAIT = 8 };   // T_WAIT: the update stream sat idle in front of a panel (chunk) that had not arrived: EXPOSED chain time
 
 struct MgTimer {
     gpx_mg *g; hipStream_t st; size_t idx; bool on;
@@ -262,18 +279,35 @@ struct MgTimer {
     ~MgTimer() { if (on) (void)hipEventRecord(g->tev[idx + 1], st); }
 };
 
-static ncclDataType_t nccl_type(int dtype) { return dtype == GPX_F64 ? ncclFloat64 : ncclFloat32; }
+static int mg_pack_from(gpx_mg *g, const void *src, int64_t ld, int64_t rows, int64_t kb, void *buf, hipStream_t st)
+{
+    if (rows <= 0) return GPX_OK;
+    const unsigned blocks = (unsigned)std::min<int64_t>(cdiv(rows * cdiv(kb, 2), 256), 4096);
+    if (g->dtype == GPX_F64)
+        hipLaunchKernelGGL((pack_panel_kernel<double>), dim3(blocks), dim3(256), 0, st, (const double *)src, ld,
+                           (double *)buf, g->nb, rows, (int)kb);
+    else
+        hipLaunchKernelGGL((pack_panel_kernel<float>), dim3(blocks), dim3(256), 0, st, (const float *)src, ld,
+                           (float *)buf, g->nb, rows, (int)kb);
+    GPX_LAUNCH_CHECK();
+    return GPX_OK;
+}
+static int mg_pack(gpx_mg *g, int64_t r0, int64_t cl, int64_t rows, int64_t kb, void *buf, hipStream_t st)
+{
+    return mg_pack_from(g, g->Aat(r0, cl), g->ld, rows, kb, buf, st);
+}
 
-// rehearsal: hold the stream for `ticks` of the 100 MHz real-time clock (one lane; a modelled transfer)
+// ---- rehearsal: what stands in for the other ranks (none of it is communication) ------------------------------------
+// hold the stream for `ticks` of the 100 MHz real-time clock (one lane; a modelled transfer)
 __global__ void mg_delay_kernel(unsigned long long ticks)
 {
     const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
     while (__builtin_amdgcn_s_memrealtime() - t0 < ticks) __builtin_amdgcn_s_sleep(32);
 }
-static int mg_delay(gpx_mg *g, double us, hipStream_t st)
+static int reh_delay(gpx_mg *g, double us, hipStream_t st)
 {
     if (us <= 0) return GPX_OK;
-    g->reh_model_ms += us * 1e-3;
+    g->reh.model_ms += us * 1e-3;
     hipLaunchKernelGGL(mg_delay_kernel, dim3(1), dim3(1), 0, st, (unsigned long long)(us * 100.0));
     GPX_LAUNCH_CHECK();
     return GPX_OK;
@@ -281,51 +315,101 @@ static int mg_delay(gpx_mg *g, double us, hipStream_t st)
 // the modelled duration of one panel-chunk broadcast of `bytes` (DESIGN section 5's assumptions, stated in the JSON the
 // rehearsal writes): a ring moves the payload through one link per hop, pipelined -- bytes / rate; scatter + all-gather puts
 // 1 / P of it on each of the root's links, twice -- 2 bytes / (P rate); one latency per collective call
-static double mg_model_us(const gpx_mg *g, size_t bytes, bool sag)
+static double reh_model_us(const gpx_mg *g, size_t bytes, bool sag)
 {
-    const double per_us = g->reh_GBps * 1e3;                      // bytes per microsecond
-    return sag ? 2.0 * (double)bytes / ((double)g->world * per_us) + 2.0 * g->reh_lat_us : (double)bytes / per_us + g->reh_lat_us;
+    const double per_us = g->reh.GBps * 1e3;                      // bytes per microsecond
+    return sag ? 2.0 * (double)bytes / ((double)g->world * per_us) + 2.0 * g->reh.lat_us : (double)bytes / per_us + g->reh.lat_us;
+}
+// `count` elements of alpha from element `off` on: a block this rank does not own comes out of the resident solution
+static int reh_alpha_block(gpx_mg *g, int64_t off, size_t count, int root, hipStream_t st)
+{
+    if (root == g->rank || !g->reh.alpha) return GPX_OK;
+    GPX_HIP(hipMemcpyAsync((char *)g->alpha + (size_t)off * g->es, (const char *)g->reh.alpha + (size_t)off * g->es, count * g->es,
+                           hipMemcpyDeviceToDevice, st));
+    return GPX_OK;
+}
+// rows [row0, row0 + rows) of panel j (relative to its first row) into buf: packed out of the resident factor when another
+// rank owns the panel, then the modelled transfer of `count` elements
+static int reh_panel(gpx_mg *g, void *buf, size_t count, int root, hipStream_t st, int64_t j, int64_t row0, int64_t rows, bool sag)
+{
+    if (root != g->rank) {
+        if (j < 0 || !g->reh.L) { set_error("rehearsal: a panel broadcast without its context"); return GPX_ERR_ARG; }
+        const int64_t k0 = g->k0(j), kb = g->kb(j);
+        GPX_TRY(mg_pack_from(g, (const char *)g->reh.L + ((size_t)(k0 + row0) * g->reh.ld + k0) * g->es, g->reh.ld, rows, kb, buf, st));
+    }
+    return reh_delay(g, reh_model_us(g, count * g->es, sag), st);
+}
+// the remote owner's chain of panel j behind the arrival of the panel before -- taken to be what THIS rank measured for the
+// nearest panel it owns in the fit before (symmetric ranks; nothing in the first fit)
+static int reh_remote_chain(gpx_mg *g, int64_t j, hipStream_t st)
+{
+    if (g->own_chain_ms.empty()) return GPX_OK;
+    double best = 0; int64_t dist = -1;
+    for (int64_t o : g->my_blocks) {
+        const int64_t dd = o > j ? o - j : j - o;
+        if ((size_t)o < g->own_chain_ms.size() && g->own_chain_ms[(size_t)o] > 0 && (dist < 0 || dd < dist)) { dist = dd; best = g->own_chain_ms[(size_t)o]; }
+    }
+    const double before = g->reh.model_ms;
+    GPX_TRY(reh_delay(g, best * 1e3, st));
+    g->reh.chain_ms += g->reh.model_ms - before;                  // (kept apart from the transfers)
+    g->reh.model_ms = before;
+    return GPX_OK;
+}
+
+// ---- the collectives: each consults g->comm, nothing else ------------------------------------------------------------
+static ncclDataType_t nccl_type(int dtype) { return dtype == GPX_F64 ? ncclFloat64 : (dtype == GPX_F32 ? ncclFloat32 : ncclInt32); }
+
+// Does a collective of `count` elements have anything to do right now?  One rank has nobody to talk to -- except over RCCL
+// when tune().force_collectives (read at call time: the tests set it per call) sends even that through the library.
+// The one refusal: an RCCL handle without its communicator.
+static int mg_comm_live(const gpx_mg *g, size_t count, bool *live)
+{
+    *live = count > 0 && (g->world > 1 || g->comm.kind == MG_COMM_REHEARSAL || (g->comm.kind == MG_COMM_RCCL && tune().force_collectives));
+    if (*live && g->comm.kind == MG_COMM_RCCL && !g->comm.rccl) {
+        set_error("this handle has no communicator (it was handed to another handle by gpx_mg_adopt_comm, or never connected)");
+        return GPX_ERR_ARG;
+    }
+    return GPX_OK;
+}
+// a host callback's return code (an exception on the Python side is parked there and comes back as non-zero)
+static int mg_cb_rc(int rc, const char *what)
+{
+    if (rc == 0) return GPX_OK;
+    set_error("%s callback failed (%d)", what, rc);
+    return GPX_ERR_HIP;
 }
 
 // broadcast `count` elements of the handle's dtype at dev_ptr from `root`, on stream st
 static int mg_bcast(gpx_mg *g, void *dev_ptr, size_t count, int root, hipStream_t st)
 {
-    if (count == 0) return GPX_OK;
-    if (g->rehearse) {
-        // (only alpha blocks travel this way: a block this rank does not own comes out of the resident solution)
-        if (root != g->rank && g->reh_alpha) {
-            const size_t off = (size_t)((const char *)dev_ptr - (const char *)g->alpha);
-            GPX_HIP(hipMemcpyAsync(dev_ptr, (const char *)g->reh_alpha + off, count * g->es, hipMemcpyDeviceToDevice, st));
-        }
-        return mg_delay(g, g->reh_lat_us, st);
+    bool live = false;
+    GPX_TRY(mg_comm_live(g, count, &live));
+    if (!live) return GPX_OK;
+    switch (g->comm.kind) {
+    case MG_COMM_REHEARSAL: return reh_delay(g, g->reh.lat_us, st);
+    case MG_COMM_CALLBACKS: return mg_cb_rc(g->comm.cb_bcast(g->comm.cb_user, dev_ptr, count * g->es, root, (void *)st), "broadcast");
+    case MG_COMM_RCCL: GPX_NCCL(g_rccl.Broadcast(dev_ptr, dev_ptr, count, nccl_type(g->dtype), root, g->comm.rccl, st)); break;
     }
-    if (g->cb_bcast) {
-        if (g->world == 1) return GPX_OK;
-        const int rc = g->cb_bcast(g->cb_user, dev_ptr, count * g->es, root, (void *)st);
-        if (rc != 0) { set_error("broadcast callback failed (%d)", rc); return GPX_ERR_HIP; }
-        return GPX_OK;
-    }
-    if (g->world == 1 && !tune().force_collectives) return GPX_OK;
-    if (!g->comm) { set_error("this handle has no communicator (it was handed to another handle by gpx_mg_adopt_comm, or never connected)"); return GPX_ERR_ARG; }
-    GPX_NCCL(g_rccl.Broadcast(dev_ptr, dev_ptr, count, nccl_type(g->dtype), root, g->comm, st));
     return GPX_OK;
+}
+// ... of alpha[off, off + count): the back substitution's block broadcast
+static int mg_bcast_alpha(gpx_mg *g, int64_t off, size_t count, int root, hipStream_t st)
+{
+    if (g->comm.kind == MG_COMM_REHEARSAL) GPX_TRY(reh_alpha_block(g, off, count, root, st));
+    return mg_bcast(g, (char *)g->alpha + (size_t)off * g->es, count, root, st);
 }
 
 // op 0: sum of `count` elements of dtype (GPX_F64 / GPX_F32 / 2 = int32); op 1: max
 static int mg_allreduce(gpx_mg *g, void *dev_ptr, size_t count, int dtype, int op, hipStream_t st)
 {
-    if (count == 0) return GPX_OK;
-    if (g->rehearse) return mg_delay(g, g->reh_lat_us, st);       // (local values only: the rehearsal's scalars are this rank's share)
-    if (g->cb_allreduce) {
-        if (g->world == 1) return GPX_OK;
-        const int rc = g->cb_allreduce(g->cb_user, dev_ptr, count, dtype, op, (void *)st);
-        if (rc != 0) { set_error("all-reduce callback failed (%d)", rc); return GPX_ERR_HIP; }
-        return GPX_OK;
+    bool live = false;
+    GPX_TRY(mg_comm_live(g, count, &live));
+    if (!live) return GPX_OK;
+    switch (g->comm.kind) {
+    case MG_COMM_REHEARSAL: return reh_delay(g, g->reh.lat_us, st);   // (local values only: the rehearsal's scalars are this rank's share)
+    case MG_COMM_CALLBACKS: return mg_cb_rc(g->comm.cb_allreduce(g->comm.cb_user, dev_ptr, count, dtype, op, (void *)st), "all-reduce");
+    case MG_COMM_RCCL: GPX_NCCL(g_rccl.AllReduce(dev_ptr, dev_ptr, count, nccl_type(dtype), op == 0 ? ncclSum : ncclMax, g->comm.rccl, st)); break;
     }
-    if (g->world == 1 && !tune().force_collectives) return GPX_OK;
-    if (!g->comm) { set_error("this handle has no communicator (it was handed to another handle by gpx_mg_adopt_comm, or never connected)"); return GPX_ERR_ARG; }
-    const ncclDataType_t t = dtype == GPX_F64 ? ncclFloat64 : (dtype == GPX_F32 ? ncclFloat32 : ncclInt32);
-    GPX_NCCL(g_rccl.AllReduce(dev_ptr, dev_ptr, count, t, op == 0 ? ncclSum : ncclMax, g->comm, st));
     return GPX_OK;
 }
 
@@ -359,79 +443,66 @@ static void mg_chunk_plan(int64_t rows, int64_t nb, int nch_req, std::vector<int
     }
 }
 
-static int mg_pack_from(gpx_mg *g, const void *src, int64_t ld, int64_t rows, int64_t kb, void *buf, hipStream_t st);
-// (j, row0, rows: which rows of which panel dev_ptr holds -- the rehearsal needs to know what it stands in for)
-static int mg_bcast_panel(gpx_mg *g, void *dev_ptr, size_t count, int root, hipStream_t st, int64_t j = -1, int64_t row0 = 0, int64_t rows = 0)
+// dev_ptr holds rows [row0, row0 + rows) of panel j, `count` elements (the rehearsal needs to know what it stands in for)
+static int mg_bcast_panel(gpx_mg *g, void *dev_ptr, size_t count, int root, hipStream_t st, int64_t j, int64_t row0, int64_t rows)
 {
     const int P = g->world, me = g->rank;
+    const MgComm &c = g->comm;
+    // (an RCCL handle without its communicator takes the plain route, where mg_bcast refuses it)
+    const bool sag = g->bcast_sag && mg_piece_sag_ok(count, P) && (c.kind != MG_COMM_RCCL || c.rccl);
+    route_hit(sag ? RT_MG_BCAST_SAG : RT_MG_BCAST_ONE);
+    if (c.kind == MG_COMM_REHEARSAL) return reh_panel(g, dev_ptr, count, root, st, j, row0, rows, sag);
+    if (!sag) return mg_bcast(g, dev_ptr, count, root, st);
     const size_t piece = mg_piece(count, P);                      // 32-element (128- / 256-byte) aligned pieces; the last one takes the rest
-    if (g->rehearse) {
-        const bool sag_m = g->bcast_sag && mg_piece_sag_ok(count, P);
-        route_hit(sag_m ? RT_MG_BCAST_SAG : RT_MG_BCAST_ONE);
-        if (root != me) {
-            if (j < 0 || !g->reh_L) { set_error("rehearsal: a panel broadcast without its context"); return GPX_ERR_ARG; }
-            const int64_t k0 = g->k0(j), kb = g->kb(j);
-            GPX_TRY(mg_pack_from(g, (const char *)g->reh_L + ((size_t)(k0 + row0) * g->reh_ld + k0) * g->es, g->reh_ld, rows, kb, dev_ptr, st));
-        }
-        return mg_delay(g, mg_model_us(g, count * g->es, sag_m), st);
-    }
-    const bool sag = g->bcast_sag && mg_piece_sag_ok(count, P) && (g->cb_bcast || g->comm);
-    if (!sag) { route_hit(RT_MG_BCAST_ONE); return mg_bcast(g, dev_ptr, count, root, st); }
-    route_hit(RT_MG_BCAST_SAG);
     auto off = [&](int i) { return (size_t)i * piece; };
     auto len = [&](int i) { return i + 1 == P ? count - off(i) : piece; };
     auto at = [&](int i) { return (char *)dev_ptr + off(i) * g->es; };
-    if (g->cb_bcast) {
-        const size_t need = (count - off(P - 1)) * g->es;
-        GPX_TRY(g->sag_tmp.reserve(need, st));
+    if (c.kind == MG_COMM_CALLBACKS) {
+        GPX_TRY(g->comm.sag_tmp.reserve(len(P - 1) * g->es, st));
         for (int i = 0; i < P; ++i) {                             // phase 1: root -> rank i
             if (i == root) continue;
-            void *dst = (me == root || me == i) ? (void *)at(i) : g->sag_tmp.p;
-            const int rc = g->cb_bcast(g->cb_user, dst, len(i) * g->es, root, (void *)st);
-            if (rc != 0) { set_error("broadcast callback failed (%d)", rc); return GPX_ERR_HIP; }
+            void *dst = (me == root || me == i) ? (void *)at(i) : c.sag_tmp.p;
+            GPX_TRY(mg_cb_rc(c.cb_bcast(c.cb_user, dst, len(i) * g->es, root, (void *)st), "broadcast"));
         }
-        for (int i = 0; i < P; ++i) {                             // phase 2: rank i -> everybody
-            const int rc = g->cb_bcast(g->cb_user, at(i), len(i) * g->es, i, (void *)st);
-            if (rc != 0) { set_error("broadcast callback failed (%d)", rc); return GPX_ERR_HIP; }
-        }
+        for (int i = 0; i < P; ++i)                               // phase 2: rank i -> everybody
+            GPX_TRY(mg_cb_rc(c.cb_bcast(c.cb_user, at(i), len(i) * g->es, i, (void *)st), "broadcast"));
         return GPX_OK;
     }
     const ncclDataType_t t = nccl_type(g->dtype);
     GPX_NCCL(g_rccl.GroupStart());
     if (me == root) {
         for (int i = 0; i < P; ++i)
-            if (i != root) GPX_NCCL(g_rccl.Send(at(i), len(i), t, i, g->comm, st));
+            if (i != root) GPX_NCCL(g_rccl.Send(at(i), len(i), t, i, c.rccl, st));
     } else {
-        GPX_NCCL(g_rccl.Recv(at(me), len(me), t, root, g->comm, st));
+        GPX_NCCL(g_rccl.Recv(at(me), len(me), t, root, c.rccl, st));
     }
     GPX_NCCL(g_rccl.GroupEnd());
     GPX_NCCL(g_rccl.GroupStart());
-    for (int j = 0; j < P; ++j) {
-        if (j == me) continue;
-        if (j != root) GPX_NCCL(g_rccl.Send(at(me), len(me), t, j, g->comm, st));      // (the root already holds every piece)
-        if (me != root) GPX_NCCL(g_rccl.Recv(at(j), len(j), t, j, g->comm, st));
+    for (int i = 0; i < P; ++i) {
+        if (i == me) continue;
+        if (i != root) GPX_NCCL(g_rccl.Send(at(me), len(me), t, i, c.rccl, st));      // (the root already holds every piece)
+        if (me != root) GPX_NCCL(g_rccl.Recv(at(i), len(i), t, i, c.rccl, st));
     }
     GPX_NCCL(g_rccl.GroupEnd());
     return GPX_OK;
 }
 
-static int mg_pack_from(gpx_mg *g, const void *src, int64_t ld, int64_t rows, int64_t kb, void *buf, hipStream_t st)
+// The one drain: waits for every stream the handle enqueues on (all four, also after one of them has failed) and
+// returns the first failure
+static int mg_drain(gpx_mg *g)
 {
-    if (rows <= 0) return GPX_OK;
-    const unsigned blocks = (unsigned)std::min<int64_t>(cdiv(rows * cdiv(kb, 2), 256), 4096);
-    if (g->dtype == GPX_F64)
-        hipLaunchKernelGGL((pack_panel_kernel<double>), dim3(blocks), dim3(256), 0, st, (const double *)src, ld,
-                           (double *)buf, g->nb, rows, (int)kb);
-    else
-        hipLaunchKernelGGL((pack_panel_kernel<float>), dim3(blocks), dim3(256), 0, st, (const float *)src, ld,
-                           (float *)buf, g->nb, rows, (int)kb);
-    GPX_LAUNCH_CHECK();
-    return GPX_OK;
+    int rc = GPX_OK;
+    for (hipStream_t st : {g->S, g->Q, g->B, g->O}) {
+        const hipError_t e = st ? hipStreamSynchronize(st) : hipSuccess;
+        if (e != hipSuccess && rc == GPX_OK) rc = hip_fail(e, "hipStreamSynchronize", __FILE__, __LINE__);
+    }
+    return rc;
 }
-static int mg_pack(gpx_mg *g, int64_t r0, int64_t cl, int64_t rows, int64_t kb, void *buf, hipStream_t st)
-{
-    return mg_pack_from(g, g->Aat(r0, cl), g->ld, rows, kb, buf, st);
-}
+// ... as a guard: idle before the buffers of the scope around it are freed, whatever happened in between
+struct MgDrain {
+    gpx_mg *g;
+    ~MgDrain() { (void)mg_drain(g); }
+};
 
 // Factor (owner, stream Q), pack (owner, Q) and broadcast (everybody, stream B) block column j into buf.  The
 // broadcasts have a stream of their own: all ranks issue them in panel order on B, and Q -- the panel chain -- never
@@ -459,19 +530,7 @@ static int mg_factor_and_bcast(gpx_mg *g, int64_t j, void *buf, hipEvent_t buf_f
         GPX_TRY(trsv_ops_build(g->dtype, g->Aat(r0, cl), kb, g->ld, &g->ops[(size_t)(j / g->world)], g->O));
     } else {
         if (buf_free) GPX_HIP(hipStreamWaitEvent(B, buf_free, 0));
-        // rehearsal: the remote owner's chain behind the arrival of the panel before -- taken to be what THIS rank measured
-        // for the nearest panel it owns in the fit before (symmetric ranks; nothing in the first fit)
-        if (g->rehearse && !g->own_chain_ms.empty()) {
-            double best = 0; int64_t dist = -1;
-            for (int64_t o : g->my_blocks) {
-                const int64_t dd = o > j ? o - j : j - o;
-                if ((size_t)o < g->own_chain_ms.size() && g->own_chain_ms[(size_t)o] > 0 && (dist < 0 || dd < dist)) { dist = dd; best = g->own_chain_ms[(size_t)o]; }
-            }
-            const double before = g->reh_model_ms;
-            GPX_TRY(mg_delay(g, best * 1e3, B));
-            g->reh_chain_ms += g->reh_model_ms - before;          // (kept apart from the transfers)
-            g->reh_model_ms = before;
-        }
+        if (g->comm.kind == MG_COMM_REHEARSAL) GPX_TRY(reh_remote_chain(g, j, B));
     }
     // row chunks (mg_chunk_plan)
     std::vector<int64_t> ends;
@@ -600,7 +659,7 @@ static int mg_solve(gpx_mg *g)
             GPX_TRY(trsv_lower(g->dtype, g->Aat(r0, cl), kb, g->ld, g->tmp, (char *)g->alpha + (size_t)r0 * g->es, 1, S, nullptr,
                                &g->ops[(size_t)(j / g->world)]));
         }
-        GPX_TRY(mg_bcast(g, (char *)g->alpha + (size_t)r0 * g->es, (size_t)kb, (int)g->owner(j), S));
+        GPX_TRY(mg_bcast_alpha(g, r0, (size_t)kb, (int)g->owner(j), S));
         int64_t before = 0;                                          // this rank's block columns left of block j
         for (int64_t b : g->my_blocks) if (b < j) ++before;
         const int64_t ncols = before * g->nb;
@@ -638,10 +697,7 @@ static int mg_reduce(gpx_mg *g)
     double h[4]; int hi[2];
     GPX_HIP(hipMemcpyAsync(h, g->scal, sizeof(h), hipMemcpyDeviceToHost, S));
     GPX_HIP(hipMemcpyAsync(hi, g->info, sizeof(hi), hipMemcpyDeviceToHost, S));
-    GPX_HIP(hipStreamSynchronize(S));
-    GPX_HIP(hipStreamSynchronize(g->Q));
-    GPX_HIP(hipStreamSynchronize(g->B));
-    GPX_HIP(hipStreamSynchronize(g->O));
+    GPX_TRY(mg_drain(g));
     g->logdet = h[2]; g->yta = h[1];
     g->info_host = hi[1] == 0 ? 0 : (hi[1] == INT_MAX ? -7 : (1 << 30) - hi[1]);
     return GPX_OK;
@@ -679,7 +735,7 @@ static int mg_alloc(gpx_mg *g)
     return GPX_OK;
 }
 
-static int mg_new(gpx_mg **out, int dtype, int kernel, int64_t n, int d, int64_t nb, int world, int rank)
+static int mg_new(gpx_mg **out, MgCommKind kind, int dtype, int kernel, int64_t n, int d, int64_t nb, int world, int rank)
 {
     GPX_TRY(ensure_device());
     GPX_ARG(out, "mg is NULL");
@@ -692,6 +748,7 @@ static int mg_new(gpx_mg **out, int dtype, int kernel, int64_t n, int d, int64_t
     gpx_mg *g = new gpx_mg();
     g->dtype = dtype; g->kernel = kernel; g->n = n; g->d = d; g->nb = nb; g->world = world; g->rank = rank;
     g->es = esize(dtype);
+    g->comm.kind = kind;
     if (hipGetDevice(&g->device) != hipSuccess) { (void)hipGetLastError(); g->device = 0; }
     g->nblk = cdiv(n, nb);
     for (int64_t j = rank; j < g->nblk; j += world) g->my_blocks.push_back(j);
@@ -731,7 +788,7 @@ static double mg_hash(const void *p, size_t bytes)
 // [7] -hash(params); (x, -x) agree on every rank iff max(x) == -max(-x).  gpx_mg_var (nv = MG_VAR_AGREE) adds
 // [8] chunk_rows [9] -chunk_rows [10] -(rows per chunk this rank's free memory allows): -max = the smallest of them.
 constexpr int MG_COV_AGREE = 8, MG_VAR_AGREE = 11;
-static int mg_cov_agree(gpx_mg *g, double *v, int nv = MG_COV_AGREE, const char *who = "gpx_mg_cov")
+static int mg_cov_agree(gpx_mg *g, double *v, int nv, const char *who)
 {
     double *dv = g->scal + 4;
     GPX_HIP(hipMemcpyAsync(dv, v, nv * sizeof(double), hipMemcpyHostToDevice, g->S));
@@ -749,6 +806,34 @@ static int mg_cov_agree(gpx_mg *g, double *v, int nv = MG_COV_AGREE, const char 
     if (nv > MG_COV_AGREE && v[8] != -v[9]) { set_error("%s: the ranks called with different chunk_rows (%.0f .. %.0f)", who, -v[9], v[8]); return GPX_ERR_ARG; }
     return GPX_OK;
 }
+
+// The opening of a collective prediction (`who`: gpx_mg_cov / gpx_mg_var), up to the point where every rank knows that all
+// of them go on.  The refusals first: they depend on the handle's state alone, which is the same on every rank.  Then
+// this rank's verdict goes into v[0, 8) (the caller has filled what lies beyond), `alloc` makes EVERYTHING THIS CALL
+// ALLOCATES, BEFORE ANYTHING THAT DEPENDS ON m IS ENQUEUED, and the ranks agree (mg_cov_agree): a rank whose arguments are
+// bad or whose allocation fails still gets there, and all ranks fail together.  plan_rc: the verdict of the caller's own
+// plan (GPX_ERR_ARG counts as a bad argument, GPX_ERR_NOMEM as a failed allocation).  After GPX_OK with m > 0 the caller
+// puts an MgDrain in front of its work: the buffers `alloc` made are freed on return.
+template <typename Alloc>
+static int mg_predict_open(gpx_mg *g, const char *who, double *v, int nv, const double *params, const double *xo, int64_t m,
+                           const double *out, int plan_rc, Alloc alloc)
+{
+    if (g->comm.kind == MG_COMM_REHEARSAL) { set_error("%s: a rehearsal handle holds one rank's share without a communicator", who); return GPX_ERR_UNSUPPORTED; }
+    if (!g->fitted) { set_error("%s: mg is not fitted", who); return GPX_ERR_ARG; }   // (the same on every rank: fit is collective)
+    if (g->info_host != 0) {                                      // (the reduced info word: the same on every rank)
+        set_error("%s: the factor is not positive definite (info = %d)", who, g->info_host);
+        return GPX_ERR_ARG;
+    }
+    const bool args_ok = m >= 0 && params && (m == 0 || (xo && out)) && plan_rc != GPX_ERR_ARG;
+    v[0] = plan_rc == GPX_ERR_NOMEM ? 1.0 : 0.0; v[1] = args_ok ? 0.0 : 1.0; v[2] = (double)m; v[3] = -(double)m;
+    v[4] = args_ok ? mg_hash(xo, (size_t)m * g->d * sizeof(double)) : 0.0;
+    v[6] = args_ok ? mg_hash(params, (size_t)nparams_of(g->kernel, g->d) * sizeof(double)) : 0.0;
+    v[5] = -v[4]; v[7] = -v[6];
+    if (args_ok && m > 0 && plan_rc == GPX_OK && !alloc()) { (void)hipGetLastError(); v[0] = 1.0; }
+    return mg_cov_agree(g, v, nv, who);
+}
+// upload_f64's float64 staging copy of `count` values, for callers that allocate before they agree (fp64: none)
+static int mg_stage_alloc(const gpx_mg *g, DevBuf *stage, size_t count) { return g->dtype == GPX_F64 ? GPX_OK : stage->alloc(count * sizeof(double)); }
 
 // B_{j'} -= X_j L[rows of block j', block column j]^T for the blocks j' in [a, b): one launch -- a batch over blocks that
 // are all nb wide, or a single block of any width.  Rows stop short of the rider row n.
@@ -823,40 +908,13 @@ static int mg_cov_run(gpx_mg *g, const double *params, const void *dxo, int64_t 
 
 }  // namespace gpx
 
-// The caller's host arrays are double whatever the handle's dtype; an fp32 handle rounds ON THE HOST (the single-GPU
-// handle converts on the device, gpx_gp.hip).  Both are synchronous.
-// `count` contiguous values, host -> device
-static int mg_upload(const gpx_mg *g, void *dst, const double *src, size_t count)
-{
-    if (g->dtype == GPX_F64) {
-        GPX_HIP(hipMemcpy(dst, src, count * 8, hipMemcpyHostToDevice));
-        return GPX_OK;
-    }
-    std::vector<float> h(src, src + count);
-    GPX_HIP(hipMemcpy(dst, h.data(), count * 4, hipMemcpyHostToDevice));
-    return GPX_OK;
-}
-
-// rows x cols, device (leading dimension lds) -> host (leading dimension ldh), behind the work queued on S
-static int mg_download(const gpx_mg *g, double *dst, int64_t ldh, const void *src, int64_t lds, int64_t rows, int64_t cols)
-{
-    if (g->dtype == GPX_F64) {
-        GPX_HIP(hipMemcpy2DAsync(dst, (size_t)ldh * 8, src, (size_t)lds * 8, (size_t)cols * 8, (size_t)rows, hipMemcpyDeviceToHost, g->S));
-        GPX_HIP(hipStreamSynchronize(g->S));
-        return GPX_OK;
-    }
-    std::vector<float> h((size_t)rows * lds);
-    GPX_HIP(hipMemcpyAsync(h.data(), src, h.size() * 4, hipMemcpyDeviceToHost, g->S));
-    GPX_HIP(hipStreamSynchronize(g->S));
-    for (int64_t i = 0; i < rows; ++i)
-        for (int64_t k = 0; k < cols; ++k) dst[i * ldh + k] = (double)h[(size_t)(i * lds + k)];
-    return GPX_OK;
-}
-
-static int mg_mean_run(gpx_mg *g, const double *params, const double *xo, int64_t m, double *out, void *dxo, void *dout)
+// Host arrays are float64 whatever the handle's dtype: they cross by the single-GPU handle's staging pair (upload_f64 /
+// download_f64, gpx_gp.hip) on S, which rounds fp32 on the device, to nearest even as the host would.
+// dxo, dout: m x d and m values in the handle's dtype; stage: upload_f64's staging copy (mg_stage_alloc)
+static int mg_mean_run(gpx_mg *g, const double *params, const double *xo, int64_t m, double *out, void *dxo, void *dout, DevBuf *stage)
 {
     const size_t es = g->es;
-    GPX_TRY(mg_upload(g, dxo, xo, (size_t)m * g->d));
+    GPX_TRY(upload_f64(g->dtype, dxo, m * g->d, xo, m * g->d, 1, m * g->d, g->S, stage));
     // every rank evaluates a slice of the test points, one all-reduce assembles the vector
     const int64_t per = cdiv(m, g->world);
     const int64_t m0 = std::min(m, g->rank * per), m1 = std::min(m, (g->rank + 1) * per);
@@ -865,7 +923,31 @@ static int mg_mean_run(gpx_mg *g, const double *params, const double *xo, int64_
         GPX_TRY(gpx_d_mean(g->dtype, g->kernel, (char *)dxo + (size_t)m0 * g->d * es, m1 - m0, g->x, g->n, g->d, params, g->alpha,
                            (char *)dout + (size_t)m0 * es, (void *)g->S));
     GPX_TRY(mg_allreduce(g, dout, (size_t)m, g->dtype, 0, g->S));
-    return mg_download(g, out, m, dout, m, 1, m);
+    // (download_f64 allocates its float64 temporary here, behind the call's last collective: a failure is this rank's alone)
+    return download_f64(g->dtype, out, m, dout, m, 1, m, 0, g->S);
+}
+
+// Stage and chain times of this rank after a fit (HIP events; every stream drained by mg_reduce) into g->ms, the chain
+// per owned panel into own_chain_ms, and the rehearsal's modelled delays, which start from zero for the next fit
+static void mg_harvest_timing(gpx_mg *g)
+{
+    for (double &v : g->ms) v = 0;
+    std::vector<double> chain_now((size_t)g->nblk, 0.0);
+    for (size_t i = 0; i + 1 < g->tev_next; i += 2) {
+        float t = 0.f;
+        if (hipEventElapsedTime(&t, g->tev[i], g->tev[i + 1]) != hipSuccess) { (void)hipGetLastError(); continue; }
+        const int cls = g->tcls[i / 2];
+        g->ms[cls] += t;
+        if (g->tpan[i / 2] >= 0 && (cls == T_PANEL || cls == T_PACK || cls == T_UPDATE)) chain_now[(size_t)g->tpan[i / 2]] += t;
+        if (cls == T_WAIT) {
+            g->ms[T_WAIT_MAX] = std::max(g->ms[T_WAIT_MAX], (double)t);
+            if (t > 0.02f) g->ms[T_WAITS_LONG] += 1.0;
+        }
+    }
+    g->own_chain_ms.swap(chain_now);
+    g->ms[T_REH_MODEL] = g->reh.model_ms;
+    g->ms[T_REH_CHAIN] = g->reh.chain_ms;
+    g->reh.model_ms = 0; g->reh.chain_ms = 0;
 }
 
 #define MG_ENTER(g)                                                          \
@@ -892,23 +974,25 @@ int gpx_mg_destroy(gpx_mg_t *g)
 {
     if (!g) return GPX_OK;
     gpx::DeviceGuard guard__(g->device);
-    if (g->S) (void)hipStreamSynchronize(g->S);
-    if (g->Q) (void)hipStreamSynchronize(g->Q);
-    if (g->B) (void)hipStreamSynchronize(g->B);
-    if (g->O) (void)hipStreamSynchronize(g->O);
-    if (g->comm && g_rccl.CommDestroy) (void)g_rccl.CommDestroy(g->comm);
+    (void)mg_drain(g);
+    if (g->comm.rccl && g_rccl.CommDestroy) (void)g_rccl.CommDestroy(g->comm.rccl);
     for (void *b : {g->A, g->pbuf[0], g->pbuf[1], g->x, g->y, g->alpha, g->tmp, (void *)g->scal, (void *)g->info}) dev_free(b);   // mg_alloc's
-    g->sag_tmp.release();
+    g->comm.sag_tmp.release();
     for (gpx::TrsvOps &o : g->ops) o.mem.release();
     g->ev.destroy();
     for (hipEvent_t e : g->tev) (void)hipEventDestroy(e);
     stream_epoch_bump();
-    if (g->S) (void)hipStreamDestroy(g->S);
-    if (g->Q) (void)hipStreamDestroy(g->Q);
-    if (g->B) (void)hipStreamDestroy(g->B);
-    if (g->O) (void)hipStreamDestroy(g->O);
+    for (hipStream_t st : {g->S, g->Q, g->B, g->O})
+        if (st) (void)hipStreamDestroy(st);
     delete g;
     return GPX_OK;
+}
+
+// the tail of every gpx_mg_create*: a handle that could not be completed is not handed out
+static int mg_created(gpx_mg_t **out, int rc)
+{
+    if (rc != GPX_OK) { gpx_mg_destroy(*out); *out = nullptr; }
+    return rc;
 }
 
 int gpx_mg_probe(void)
@@ -919,24 +1003,21 @@ int gpx_mg_probe(void)
 
 int gpx_mg_create_local(gpx_mg_t **out, int dtype, int kernel, int64_t n, int d, int64_t nb, int world, int rank)
 {
-    GPX_TRY(mg_new(out, dtype, kernel, n, d, nb, world, rank));
-    gpx_mg *g = *out;
-    int rc = rccl_load();
-    if (rc == GPX_OK) rc = mg_alloc(g);
-    if (rc != GPX_OK) { gpx_mg_destroy(g); *out = nullptr; }
-    return rc;
+    GPX_TRY(mg_new(out, MG_COMM_RCCL, dtype, kernel, n, d, nb, world, rank));
+    const int rc = rccl_load();
+    return mg_created(out, rc == GPX_OK ? mg_alloc(*out) : rc);
 }
 
 int gpx_mg_connect(gpx_mg_t *g, const void *id128)
 {
     MG_ENTER(g);
     GPX_ARG(id128, "the RCCL unique id is NULL");
-    GPX_ARG(!g->comm && !g->cb_bcast, "the handle already has a communicator");
+    GPX_ARG(g->comm.kind == MG_COMM_RCCL && !g->comm.rccl, "the handle already has a communicator");
     GPX_TRY(rccl_load());
     ncclUniqueId id;
     memcpy(&id, id128, sizeof(id));
-    ncclResult_t r = g_rccl.CommInitRank(&g->comm, g->world, id, g->rank);
-    if (r != ncclSuccess) { g->comm = nullptr; set_error("ncclCommInitRank failed: %s", g_rccl.GetErrorString(r)); return GPX_ERR_HIP; }
+    ncclResult_t r = g_rccl.CommInitRank(&g->comm.rccl, g->world, id, g->rank);
+    if (r != ncclSuccess) { g->comm.rccl = nullptr; set_error("ncclCommInitRank failed: %s", g_rccl.GetErrorString(r)); return GPX_ERR_HIP; }
     return GPX_OK;
 }
 
@@ -945,23 +1026,21 @@ int gpx_mg_create(gpx_mg_t **out, int dtype, int kernel, int64_t n, int d, int64
 {
     GPX_ARG(id128, "the RCCL unique id is NULL");
     GPX_TRY(gpx_mg_create_local(out, dtype, kernel, n, d, nb, world, rank));
-    const int rc = gpx_mg_connect(*out, id128);
-    if (rc != GPX_OK) { gpx_mg_destroy(*out); *out = nullptr; }
-    return rc;
+    return mg_created(out, gpx_mg_connect(*out, id128));
 }
 
 int gpx_mg_adopt_comm(gpx_mg_t *g, gpx_mg_t *from)
 {
     MG_ENTER(g);
     GPX_ARG(from != nullptr && from != g, "no handle to adopt the communicator from");
-    GPX_ARG(!g->comm && !g->cb_bcast && !g->rehearse, "the handle already has a communicator");
-    GPX_ARG(from->comm != nullptr, "the other handle has no RCCL communicator");
+    GPX_ARG(g->comm.kind == MG_COMM_RCCL && !g->comm.rccl, "the handle already has a communicator");
+    GPX_ARG(from->comm.rccl != nullptr, "the other handle has no RCCL communicator");
     GPX_ARG(from->world == g->world && from->rank == g->rank && from->device == g->device, "world / rank / device differ");
     // everything the other handle queued on the communicator has to be done before this one issues collectives on it
     if (from->B) GPX_HIP(hipStreamSynchronize(from->B));
     if (from->S) GPX_HIP(hipStreamSynchronize(from->S));
-    g->comm = from->comm;
-    from->comm = nullptr;                                         // (its destroy no longer touches the communicator)
+    g->comm.rccl = from->comm.rccl;
+    from->comm.rccl = nullptr;                                      // (its destroy no longer touches the communicator)
     return GPX_OK;
 }
 
@@ -969,11 +1048,11 @@ int gpx_mg_comm_info(gpx_mg_t *g, int *nranks, int *rank, int *device, int *bcas
 {
     MG_ENTER(g);
     if (bcast_sag) *bcast_sag = g->bcast_sag;
-    if (g->comm) {                                                // what RCCL itself says about the communicator
+    if (g->comm.rccl) {                                           // what RCCL itself says about the communicator
         int v = 0;
-        if (nranks) { GPX_NCCL(g_rccl.CommCount(g->comm, &v)); *nranks = v; }
-        if (rank) { GPX_NCCL(g_rccl.CommUserRank(g->comm, &v)); *rank = v; }
-        if (device) { GPX_NCCL(g_rccl.CommCuDevice(g->comm, &v)); *device = v; }
+        if (nranks) { GPX_NCCL(g_rccl.CommCount(g->comm.rccl, &v)); *nranks = v; }
+        if (rank) { GPX_NCCL(g_rccl.CommUserRank(g->comm.rccl, &v)); *rank = v; }
+        if (device) { GPX_NCCL(g_rccl.CommCuDevice(g->comm.rccl, &v)); *device = v; }
         return GPX_OK;
     }
     if (nranks) *nranks = 0;                                      // no RCCL communicator (callback back-end)
@@ -1026,14 +1105,11 @@ int gpx_mg_create_rehearsal(gpx_mg_t **out, int dtype, int kernel, int64_t n, in
 {
     GPX_ARG(L_dev && ldl >= n && alpha_dev, "the resident factor (n + 1 rows) and solution are needed");
     GPX_ARG(link_GBps > 0 && latency_us >= 0, "bad transfer model");
-    GPX_TRY(mg_new(out, dtype, kernel, n, d, nb, world, rank));
+    GPX_TRY(mg_new(out, MG_COMM_REHEARSAL, dtype, kernel, n, d, nb, world, rank));
     gpx_mg *g = *out;
-    g->rehearse = true;
-    g->reh_L = L_dev; g->reh_ld = ldl; g->reh_alpha = alpha_dev;
-    g->reh_GBps = link_GBps; g->reh_lat_us = latency_us;
-    const int rc = mg_alloc(g);
-    if (rc != GPX_OK) { gpx_mg_destroy(g); *out = nullptr; }
-    return rc;
+    g->reh.L = L_dev; g->reh.ld = ldl; g->reh.alpha = alpha_dev;
+    g->reh.GBps = link_GBps; g->reh.lat_us = latency_us;
+    return mg_created(out, mg_alloc(g));
 }
 
 int gpx_debug_mg_inject_info(gpx_mg_t *g, int value)
@@ -1069,14 +1145,10 @@ int gpx_mg_create_cb(gpx_mg_t **out, int dtype, int kernel, int64_t n, int d, in
                      gpx_mg_bcast_fn bcast, gpx_mg_allreduce_fn allreduce, void *user)
 {
     GPX_ARG(world == 1 || (bcast && allreduce), "callbacks are NULL");
-    GPX_TRY(mg_new(out, dtype, kernel, n, d, nb, world, rank));
+    GPX_TRY(mg_new(out, MG_COMM_CALLBACKS, dtype, kernel, n, d, nb, world, rank));
     gpx_mg *g = *out;
-    g->cb_bcast = bcast ? bcast : [](void *, void *, size_t, int, void *) { return 0; };
-    g->cb_allreduce = allreduce ? allreduce : [](void *, void *, size_t, int, int, void *) { return 0; };
-    g->cb_user = user;
-    const int rc = mg_alloc(g);
-    if (rc != GPX_OK) { gpx_mg_destroy(g); *out = nullptr; }
-    return rc;
+    g->comm.cb_bcast = bcast; g->comm.cb_allreduce = allreduce; g->comm.cb_user = user;   // (may be NULL for one rank: never called)
+    return mg_created(out, mg_alloc(g));
 }
 
 int gpx_mg_set_data(gpx_mg_t *g, const double *x, const double *y)
@@ -1090,8 +1162,8 @@ int gpx_mg_set_data(gpx_mg_t *g, const double *x, const double *y)
         if (!std::isfinite(x[i])) { set_error("array must not contain infs or NaNs (x)"); return GPX_ERR_ARG; }
     for (int64_t i = 0; i < n; ++i)
         if (!std::isfinite(y[i])) { set_error("array must not contain infs or NaNs (y)"); return GPX_ERR_ARG; }
-    GPX_TRY(mg_upload(g, g->x, x, (size_t)n * g->d));
-    GPX_TRY(mg_upload(g, g->y, y, (size_t)n));
+    GPX_TRY(upload_f64(g->dtype, g->x, n * g->d, x, n * g->d, 1, n * g->d, g->S));
+    GPX_TRY(upload_f64(g->dtype, g->y, n, y, n, 1, n, g->S));
     g->have_data = true; g->fitted = false;
     return GPX_OK;
 }
@@ -1111,24 +1183,7 @@ int gpx_mg_fit(gpx_mg_t *g, const double *params, double s, double *log_lh, int 
     GPX_TRY(mg_reduce(g));
     GPX_TRY(check_internal_info(g->info_host));                   // every rank sees the same reduced word: all fail together
     g->fitted = true;
-    // stage and chain times of this rank (HIP events, all streams drained by mg_reduce)
-    for (double &v : g->ms) v = 0;
-    std::vector<double> chain_now((size_t)g->nblk, 0.0);
-    for (size_t i = 0; i + 1 < g->tev_next; i += 2) {
-        float t = 0.f;
-        if (hipEventElapsedTime(&t, g->tev[i], g->tev[i + 1]) != hipSuccess) { (void)hipGetLastError(); continue; }
-        const int cls = g->tcls[i / 2];
-        g->ms[cls] += t;
-        if (g->tpan[i / 2] >= 0 && (cls == T_PANEL || cls == T_PACK || cls == T_UPDATE)) chain_now[(size_t)g->tpan[i / 2]] += t;
-        if (cls == T_WAIT) {                                      // [9] the longest single wait, [10] waits of more than 20 us
-            g->ms[9] = std::max(g->ms[9], (double)t);
-            if (t > 0.02f) g->ms[10] += 1.0;
-        }
-    }
-    g->own_chain_ms.swap(chain_now);
-    g->ms[11] = g->reh_model_ms;                                  // (rehearsal: the modelled transfer time this fit enqueued)
-    g->ms[12] = g->reh_chain_ms;                                  // (rehearsal: the remote owners' chains it stood in for)
-    g->reh_model_ms = 0; g->reh_chain_ms = 0;
+    mg_harvest_timing(g);
     if (info) *info = g->info_host;
     if (log_lh) {
         // gp/gp.py:362-365 and gp_c.pyx:22-29
@@ -1144,49 +1199,34 @@ int gpx_mg_mean(gpx_mg_t *g, const double *params, const double *xo, int64_t m, 
     GPX_ARG(g->fitted && params, "mg is not fitted");
     GPX_ARG(m >= 0 && (m == 0 || (xo && out)), "bad arguments");
     if (m == 0) return GPX_OK;
-    DevBuf dxo, dout;
+    DevBuf dxo, dout, stage;
     GPX_TRY(dxo.alloc((size_t)m * g->d * g->es));
     GPX_TRY(dout.alloc((size_t)m * g->es));
-    const int rc = mg_mean_run(g, params, xo, m, out, dxo.p, dout.p);
-    (void)hipStreamSynchronize(g->S);                             // (idle before the two buffers are freed, whatever happened)
+    GPX_TRY(mg_stage_alloc(g, &stage, (size_t)m * g->d));
+    const int rc = mg_mean_run(g, params, xo, m, out, dxo.p, dout.p, &stage);
+    (void)hipStreamSynchronize(g->S);                             // (idle before the buffers are freed, whatever happened)
     return rc;
 }
 
 int gpx_mg_cov(gpx_mg_t *g, const double *params, const double *xo, int64_t m, double *out)
 {
     MG_ENTER(g);
-    if (g->rehearse) { set_error("gpx_mg_cov: a rehearsal handle holds one rank's share without a communicator"); return GPX_ERR_UNSUPPORTED; }
-    GPX_ARG(g->fitted, "mg is not fitted");                       // (the same on every rank: fit is collective)
-    if (g->info_host != 0) {                                      // (the reduced info word: the same on every rank)
-        set_error("gpx_mg_cov: the factor is not positive definite (info = %d)", g->info_host);
-        return GPX_ERR_ARG;
-    }
     const size_t es = g->es;
-    const bool args_ok = m >= 0 && params && (m == 0 || (xo && out));
-    double v[8] = {0.0, args_ok ? 0.0 : 1.0, (double)m, -(double)m, 0.0, 0.0, 0.0, 0.0};
-    if (args_ok) {
-        v[4] = mg_hash(xo, (size_t)m * g->d * sizeof(double));
-        v[6] = mg_hash(params, (g->kernel == GPX_KERNEL_PERIODIC ? 3 : 2) * sizeof(double));
-    }
-    v[5] = -v[4]; v[7] = -v[6];
-    // everything this call allocates, before anything that depends on m is enqueued
     const int64_t ldc = round_up(std::max<int64_t>(m, 1), 16);
-    DevBuf dxo, Bm, C;
-    if (args_ok && m > 0) {
-        const bool ok = dxo.alloc((size_t)m * g->d * es) == GPX_OK && Bm.alloc((size_t)g->nblk * m * g->nb * es) == GPX_OK &&
-                        C.alloc((size_t)m * ldc * es) == GPX_OK && g->ev.reserve((size_t)(6 * g->nblk + 8)) == GPX_OK;   // (events up front: nothing fails half way through a run)
-        if (!ok) { (void)hipGetLastError(); v[0] = 1.0; }
-    }
-    GPX_TRY(mg_cov_agree(g, v));
+    double v[MG_COV_AGREE];
+    DevBuf dxo, stage, Bm, C;
+    GPX_TRY(mg_predict_open(g, "gpx_mg_cov", v, MG_COV_AGREE, params, xo, m, out, GPX_OK, [&] {
+        return dxo.alloc((size_t)m * g->d * es) == GPX_OK && mg_stage_alloc(g, &stage, (size_t)m * g->d) == GPX_OK &&
+               Bm.alloc((size_t)g->nblk * m * g->nb * es) == GPX_OK && C.alloc((size_t)m * ldc * es) == GPX_OK &&
+               g->ev.reserve((size_t)(6 * g->nblk + 8)) == GPX_OK;   // (events up front: nothing fails half way through a run)
+    }));
     if (m == 0) return GPX_OK;
-    struct Drain {                                                // every stream idle before the buffers above are freed
-        gpx_mg *g;
-        ~Drain() { for (hipStream_t st : {g->S, g->Q, g->B, g->O}) (void)hipStreamSynchronize(st); }
-    } drain{g};
+    MgDrain drain{g};
     g->ev.rewind();                                               // (the fit drained every stream: its events are free)
-    GPX_TRY(mg_upload(g, dxo.p, xo, (size_t)m * g->d));
+    GPX_TRY(upload_f64(g->dtype, dxo.p, m * g->d, xo, m * g->d, 1, m * g->d, g->S, &stage));
     GPX_TRY(mg_cov_run(g, params, dxo.p, m, (char *)Bm.p, C.p, ldc));
-    return mg_download(g, out, m, C.p, ldc, m, m);
+    // (download_f64 allocates its float64 temporary here, behind the call's last collective: a failure is this rank's alone)
+    return download_f64(g->dtype, out, m, C.p, ldc, m, m, 0, g->S);
 }
 
 // Predictive variance over the distributed factor: gpx_mg_cov's fan-in forward solve per row chunk of xo (Bm is m_c x n,
@@ -1196,48 +1236,29 @@ int gpx_mg_cov(gpx_mg_t *g, const double *params, const double *xo, int64_t m, d
 int gpx_mg_var(gpx_mg_t *g, const double *params, const double *xo, int64_t m, int64_t chunk_rows, double *out)
 {
     MG_ENTER(g);
-    if (g->rehearse) { set_error("gpx_mg_var: a rehearsal handle holds one rank's share without a communicator"); return GPX_ERR_UNSUPPORTED; }
-    GPX_ARG(g->fitted, "mg is not fitted");                       // (the same on every rank: fit is collective)
-    if (g->info_host != 0) {                                      // (the reduced info word: the same on every rank)
-        set_error("gpx_mg_var: the factor is not positive definite (info = %d)", g->info_host);
-        return GPX_ERR_ARG;
-    }
     const size_t es = g->es;
     const int64_t ncols = g->nblk * g->nb;                        // columns of the block-major accumulator
     size_t freeb = 0, totalb = 0;
     GPX_HIP(hipMemGetInfo(&freeb, &totalb));
     int64_t rows = 0;
     const int plan_rc = m >= 0 ? var_plan(g->dtype, ncols, m, chunk_rows, freeb, &rows, nullptr, nullptr) : GPX_ERR_ARG;
-    const bool args_ok = m >= 0 && params && (m == 0 || (xo && out)) && plan_rc != GPX_ERR_ARG;
-    double v[MG_VAR_AGREE] = {plan_rc == GPX_ERR_NOMEM ? 1.0 : 0.0, args_ok ? 0.0 : 1.0, (double)m, -(double)m, 0.0, 0.0, 0.0, 0.0,
-                              (double)chunk_rows, -(double)chunk_rows, -(double)rows};
-    if (args_ok) {
-        v[4] = mg_hash(xo, (size_t)m * g->d * sizeof(double));
-        v[6] = mg_hash(params, (g->kernel == GPX_KERNEL_PERIODIC ? 3 : 2) * sizeof(double));
-    }
-    v[5] = -v[4]; v[7] = -v[6];
-    // everything this call allocates, before anything that depends on m is enqueued
-    DevBuf dxo, Bm, acc, dvar;
-    if (args_ok && m > 0 && plan_rc == GPX_OK) {
-        const bool ok = dxo.alloc((size_t)m * g->d * es) == GPX_OK && Bm.alloc((size_t)ncols * rows * es) == GPX_OK &&
-                        acc.alloc((size_t)rows * sizeof(double)) == GPX_OK && dvar.alloc((size_t)m * sizeof(double)) == GPX_OK &&
-                        g->ev.reserve((size_t)(6 * g->nblk + 8)) == GPX_OK;
-        if (!ok) { (void)hipGetLastError(); v[0] = 1.0; }
-    }
-    GPX_TRY(mg_cov_agree(g, v, MG_VAR_AGREE, "gpx_mg_var"));
+    double v[MG_VAR_AGREE];
+    v[8] = (double)chunk_rows; v[9] = -(double)chunk_rows; v[10] = -(double)rows;
+    DevBuf dxo, stage, Bm, acc, dvar;
+    GPX_TRY(mg_predict_open(g, "gpx_mg_var", v, MG_VAR_AGREE, params, xo, m, out, plan_rc, [&] {
+        return dxo.alloc((size_t)m * g->d * es) == GPX_OK && mg_stage_alloc(g, &stage, (size_t)m * g->d) == GPX_OK &&
+               Bm.alloc((size_t)ncols * rows * es) == GPX_OK && acc.alloc((size_t)rows * sizeof(double)) == GPX_OK &&
+               dvar.alloc((size_t)m * sizeof(double)) == GPX_OK && g->ev.reserve((size_t)(6 * g->nblk + 8)) == GPX_OK;
+    }));
     if (m == 0) return GPX_OK;
     rows = (int64_t)(-v[10]);                                     // the chunking every rank can hold
-    struct Drain {                                                // every stream idle before the buffers above are freed
-        gpx_mg *g;
-        ~Drain() { for (hipStream_t st : {g->S, g->Q, g->B, g->O}) (void)hipStreamSynchronize(st); }
-    } drain{g};
-    GPX_TRY(mg_upload(g, dxo.p, xo, (size_t)m * g->d));
+    MgDrain drain{g};
+    GPX_TRY(upload_f64(g->dtype, dxo.p, m * g->d, xo, m * g->d, 1, m * g->d, g->S, &stage));
     for (int64_t r0 = 0; r0 < m; r0 += rows) {
         const int64_t rc = std::min(rows, m - r0);
         const void *xo_c = (const char *)dxo.p + (size_t)r0 * g->d * es;
         route_hit(RT_VAR_CHUNK);
-        // (the chunk before has drained every stream: its events are free, and so is the accumulator)
-        for (hipStream_t st : {g->S, g->Q, g->B, g->O}) GPX_HIP(hipStreamSynchronize(st));
+        GPX_TRY(mg_drain(g));                                     // (the chunk before is done: its events are free, and so is the accumulator)
         g->ev.rewind();
         GPX_TRY(mg_cov_run(g, params, xo_c, rc, (char *)Bm.p, nullptr, 0, (double *)acc.p));
         GPX_TRY(var_finish(g->dtype, g->kernel, xo_c, g->d, params, (const double *)acc.p, rc, (double *)dvar.p + r0, g->S));
@@ -1251,7 +1272,7 @@ int gpx_mg_get_alpha(gpx_mg_t *g, double *out)
 {
     MG_ENTER(g);
     GPX_ARG(g->fitted && out, "bad arguments");
-    return mg_download(g, out, g->n, g->alpha, g->n, 1, g->n);
+    return download_f64(g->dtype, out, g->n, g->alpha, g->n, 1, g->n, 0, g->S);
 }
 
 int gpx_mg_scalars(gpx_mg_t *g, double *logdet, double *yta, int *info)
@@ -1268,7 +1289,7 @@ int gpx_mg_timing(gpx_mg_t *g, double *ms8)
 {
     MG_ENTER(g);
     GPX_ARG(g->fitted && ms8, "bad arguments");
-    for (int i = 0; i < 8; ++i) ms8[i] = g->ms[i];
+    for (int i = 0; i < T_WAIT; ++i) ms8[i] = g->ms[i];            // T_BUILD .. T_UPDATE
     return GPX_OK;
 }
 
@@ -1292,7 +1313,7 @@ int gpx_mg_timing_ex(gpx_mg_t *g, double *ms, int count)
 {
     MG_ENTER(g);
     GPX_ARG(g->fitted && ms && count >= 0, "bad arguments");
-    for (int i = 0; i < count; ++i) ms[i] = i < GPX_MG_TIMING_N ? g->ms[i] : 0.0;
+    for (int i = 0; i < count; ++i) ms[i] = i < GPX_MG_TIMING_N ? g->ms[i] : 0.0;   // slot i = T_* of value i
     return GPX_OK;
 }
 

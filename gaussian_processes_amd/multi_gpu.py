@@ -79,51 +79,86 @@ class RankMismatchError(_lib.GpxError, ValueError):
     """A collective call whose ranks did not agree on their arguments (gpx_mg_cov): raised on every rank."""
 
 
-class GlooCallbacks(object):
-    """Host-side collectives for gpx_mg_create_cb: device pointer -> host staging -> torch.distributed
-    (any CPU backend) -> device.  Slow by construction; it exists so that the C schedule can be run with
-    several ranks on ONE GPU (RCCL cannot put two ranks on a device) and verified in tests/"""
+class HostStagedCallbacks(object):
+    """Host-side collectives for gpx_mg_create_cb (the interface `NativeDistributedGP(callbacks=...)` expects): wait for
+    the stream, device pointer -> host array, the exchange, host array -> device.  A subclass supplies the exchange --
+    `exchange_bcast`, `exchange_allreduce` -- and may say what else happens when this rank gives up (`rank_failed`).
+    Slow by construction; it exists so that the C schedule can be run with several ranks on ONE GPU (RCCL cannot put
+    two ranks on a device) and verified in tests/"""
 
     _NP = {_lib.F64: np.float64, _lib.F32: np.float32, 2: np.int32}
 
-    def __init__(self, dist):
-        import torch
-        from .mlii import _cpu_group
-        self.torch, self.dist = torch, dist
-        self.group = _cpu_group(dist)          # host buffers: never over an nccl default group
-        self.rank = dist.get_rank()
-        self.world = dist.get_world_size()
+    def __init__(self, rank, world):
+        self.rank, self.world = int(rank), int(world)
         self.lib = _lib.load()
-        self.error = None
+        self.error = None                       # what went wrong inside a callback; NativeDistributedGP._check raises it
         self.bcast = _lib.MG_BCAST_FN(self._bcast)
         self.allreduce = _lib.MG_ALLREDUCE_FN(self._allreduce)
+
+    def exchange_bcast(self, buf, root):
+        """`buf`: uint8, the payload's size, filled on `root`.  Returns the array that holds the root's bytes."""
+        raise NotImplementedError
+
+    def exchange_allreduce(self, buf, op):
+        """`buf`: this rank's values.  Returns the array of their sum (op 0) or maximum (op 1) over the ranks."""
+        raise NotImplementedError
+
+    def rank_failed(self, exc):
+        """Called once `exc` has stopped a callback of this rank, before the C side hears of it."""
+
+    def _d2h(self, buf, dev_ptr, stream):
+        _lib.check(self.lib.gpx_memcpy_d2h(buf.ctypes.data_as(ctypes.c_void_p), dev_ptr, buf.nbytes, stream))
+
+    def _h2d(self, dev_ptr, buf, stream):
+        _lib.check(self.lib.gpx_memcpy_h2d(dev_ptr, buf.ctypes.data_as(ctypes.c_void_p), buf.nbytes, stream))
+
+    def _fail(self, exc):                       # an exception must not unwind through the C frames: return code 1
+        self.error = exc
+        self.rank_failed(exc)
+        return 1
 
     def _bcast(self, user, dev_ptr, nbytes, root, stream):
         try:
             buf = np.empty(nbytes, dtype=np.uint8)
             _lib.check(self.lib.gpx_stream_sync(stream))
             if self.rank == root:
-                _lib.check(self.lib.gpx_memcpy_d2h(buf.ctypes.data_as(ctypes.c_void_p), dev_ptr, nbytes, stream))
-            self.dist.broadcast(self.torch.from_numpy(buf), src=root, group=self.group)
+                self._d2h(buf, dev_ptr, stream)
+            got = self.exchange_bcast(buf, root)
             if self.rank != root:
-                _lib.check(self.lib.gpx_memcpy_h2d(dev_ptr, buf.ctypes.data_as(ctypes.c_void_p), nbytes, stream))
+                self._h2d(dev_ptr, got, stream)
             return 0
-        except Exception as exc:       # an exception must not unwind through the C frames
-            self.error = exc
-            return 1
+        except Exception as exc:                # noqa: BLE001
+            return self._fail(exc)
 
     def _allreduce(self, user, dev_ptr, count, dtype, op, stream):
         try:
             buf = np.empty(count, dtype=self._NP[dtype])
             _lib.check(self.lib.gpx_stream_sync(stream))
-            _lib.check(self.lib.gpx_memcpy_d2h(buf.ctypes.data_as(ctypes.c_void_p), dev_ptr, buf.nbytes, stream))
-            self.dist.all_reduce(self.torch.from_numpy(buf),
-                                 op=self.dist.ReduceOp.SUM if op == 0 else self.dist.ReduceOp.MAX, group=self.group)
-            _lib.check(self.lib.gpx_memcpy_h2d(dev_ptr, buf.ctypes.data_as(ctypes.c_void_p), buf.nbytes, stream))
+            self._d2h(buf, dev_ptr, stream)
+            self._h2d(dev_ptr, self.exchange_allreduce(buf, op), stream)
             return 0
-        except Exception as exc:
-            self.error = exc
-            return 1
+        except Exception as exc:                # noqa: BLE001
+            return self._fail(exc)
+
+
+class GlooCallbacks(HostStagedCallbacks):
+    """The exchange over torch.distributed (any CPU backend)."""
+
+    def __init__(self, dist):
+        import torch
+        from .mlii import _cpu_group
+        self.torch, self.dist = torch, dist
+        self.group = _cpu_group(dist)          # host buffers: never over an nccl default group
+        HostStagedCallbacks.__init__(self, dist.get_rank(), dist.get_world_size())
+
+    def exchange_bcast(self, buf, root):
+        self.dist.broadcast(self.torch.from_numpy(buf), src=root, group=self.group)
+        return buf
+
+    def exchange_allreduce(self, buf, op):
+        self.dist.all_reduce(self.torch.from_numpy(buf), op=self.dist.ReduceOp.SUM if op == 0 else self.dist.ReduceOp.MAX,
+                             group=self.group)
+        return buf
 
 
 class NativeDistributedGP(object):
@@ -135,7 +170,9 @@ class NativeDistributedGP(object):
     TIMING_KEYS = ("kernel_build", "factor", "solve", "reduce", "chain_panel", "chain_pack", "chain_bcast",
                    "chain_update")
     # gpx_mg_timing_ex: how long the update stream sat idle in front of a panel (chunk) that had not arrived -- EXPOSED
-    # chain time, the longest single wait, the number of waits above 20 us; rehearsal: the modelled transfer time
+    # chain time, the longest single wait, the number of waits above 20 us; rehearsal: the modelled transfer time.
+    # Key i names slot i of the T_* enum of csrc/gpx_mg.hip (T_BUILD = 0 .. T_UPDATE = 7, then T_WAIT, T_WAIT_MAX,
+    # T_WAITS_LONG, T_REH_MODEL, T_REH_CHAIN = 12): a new slot is a new enumerator there and a new key here
     TIMING_KEYS_EX = TIMING_KEYS + ("exposed_wait", "exposed_wait_max", "exposed_waits_over_20us", "modelled_transfer",
                                     "modelled_remote_chain")
 
@@ -143,80 +180,76 @@ class NativeDistributedGP(object):
                  backend="rccl", device=0, callbacks=None, rehearsal=None, adopt_from=None):
         """`callbacks` (backend="callbacks" only): an object with ctypes function pointers `.bcast` / `.allreduce`
         (gpx_mg_bcast_fn / gpx_mg_allreduce_fn of include/gpx.h), an `.error` slot and `.rank` / `.world` -- any
-        transport for the host-callback data plane; default: `GlooCallbacks(dist)`."""
+        transport for the host-callback data plane (`HostStagedCallbacks`); default: `GlooCallbacks(dist)`.
+        `rehearsal`: ONE rank of a `world`-rank run in this process (gpx_mg_create_rehearsal): dict(rank, world, L_ptr,
+        ldl, alpha_ptr, link_GBps, latency_us) -- the resident factor / solution stand in for what other ranks send."""
         self.lib = _lib.load()
         self.n, self.d = int(n), int(d)
         if rehearsal is not None:
-            # ONE rank of a `world`-rank run in this process (gpx_mg_create_rehearsal): rehearsal = dict(rank, world, L_ptr,
-            # ldl, alpha_ptr, link_GBps, latency_us) -- the resident factor / solution stand in for what other ranks send
             self.rank, self.world = int(rehearsal["rank"]), int(rehearsal["world"])
-            self.nb = int(nb or default_nb(n, self.world))
-            _lib.check(self.lib.gpx_set_device(int(device)))
-            self.h = ctypes.c_void_p()
-            self._cb = None
-            _lib.check(self.lib.gpx_mg_create_rehearsal(
-                ctypes.byref(self.h), dtype_id, kernel_id, self.n, self.d, self.nb, self.world, self.rank,
-                ctypes.c_void_p(rehearsal["L_ptr"]), int(rehearsal["ldl"]), ctypes.c_void_p(rehearsal["alpha_ptr"]),
-                float(rehearsal.get("link_GBps", 100.0)), float(rehearsal.get("latency_us", 20.0))))
-            self.log_lh = None
-            self.info = None
-            return
-        if callbacks is not None:
+        elif callbacks is not None:
             self.rank, self.world = int(callbacks.rank), int(callbacks.world)
         else:
             self.rank, self.world = (dist.get_rank(), dist.get_world_size()) if dist is not None else (0, 1)
         self.nb = int(nb or default_nb(n, self.world))
         _lib.check(self.lib.gpx_set_device(int(device)))
-        self.h = ctypes.c_void_p()
-        self._cb = None
-        if backend == "rccl":
-            # two steps with an agreement in between: a rank whose local allocation fails (the local matrix and two
-            # panel buffers in HBM, three streams) must not leave the others blocked inside ncclCommInitRank
-            rc = self.lib.gpx_mg_create_local(ctypes.byref(self.h), dtype_id, kernel_id, self.n, self.d, self.nb,
-                                              self.world, self.rank)
-            err = _lib.last_error() if rc != 0 else ""
-            ident = np.zeros(_lib.MG_ID_BYTES, dtype=np.uint8)
-            if rc == 0 and self.rank == 0 and adopt_from is None:
-                rc = self.lib.gpx_mg_unique_id(ident.ctypes.data_as(ctypes.c_void_p))
-                err = _lib.last_error() if rc != 0 else ""
-            adopt = adopt_from is not None
-            if dist is not None and self.world > 1:
-                import torch
-                from .mlii import _cpu_group
-                cpu = _cpu_group(dist)           # CPU tensors: a gloo side group when the default group is nccl
-                ok = torch.tensor([1 if rc == 0 else 0], dtype=torch.int32)
-                dist.all_reduce(ok, op=dist.ReduceOp.MIN, group=cpu)
-                if int(ok.item()) == 0:
-                    self.close()
-                    raise _lib.GpxError("multi-GPU set-up failed on %s before the communicator was created%s"
-                                        % ("this rank" if rc != 0 else "another rank", (": " + err) if err else ""))
-                if not adopt:
-                    dist.broadcast(torch.from_numpy(ident), src=0, group=cpu)    # the ncclUniqueId travels out of band
-            else:
-                _lib.check(rc)
-            try:
-                if adopt:
-                    # ONE ncclCommInitRank per process: a handle of another width takes over the communicator (round 5: the
-                    # tuning pass tries several layouts; re-creating communicators in a running job is a risk nobody needs)
-                    _lib.check(self.lib.gpx_mg_adopt_comm(self.h, adopt_from.h))
-                else:
-                    _lib.check(self.lib.gpx_mg_connect(self.h, ident.ctypes.data_as(ctypes.c_void_p)))
-            except Exception:
-                self.close()
-                raise
+        self.h, self._cb = ctypes.c_void_p(), None
+        self.log_lh = self.info = None
+        shape = (dtype_id, kernel_id, self.n, self.d, self.nb, self.world, self.rank)   # what every gpx_mg_create* takes
+        if rehearsal is not None:
+            self._create_rehearsal(shape, rehearsal)
+        elif backend == "rccl":
+            self._create_rccl(shape, dist, adopt_from)
         elif backend == "callbacks":
-            if self.world > 1:
-                self._cb = callbacks if callbacks is not None else GlooCallbacks(dist)
-                b = ctypes.cast(self._cb.bcast, ctypes.c_void_p)
-                a = ctypes.cast(self._cb.allreduce, ctypes.c_void_p)
-            else:
-                b = a = None
-            _lib.check(self.lib.gpx_mg_create_cb(ctypes.byref(self.h), dtype_id, kernel_id, self.n, self.d, self.nb,
-                                                 self.world, self.rank, b, a, None))
+            self._create_callbacks(shape, dist, callbacks)
         else:
             raise ValueError("backend must be 'rccl' or 'callbacks'")
-        self.log_lh = None
-        self.info = None
+
+    def _create_rehearsal(self, shape, reh):
+        _lib.check(self.lib.gpx_mg_create_rehearsal(
+            ctypes.byref(self.h), *shape, ctypes.c_void_p(reh["L_ptr"]), int(reh["ldl"]), ctypes.c_void_p(reh["alpha_ptr"]),
+            float(reh.get("link_GBps", 100.0)), float(reh.get("latency_us", 20.0))))
+
+    def _create_rccl(self, shape, dist, adopt_from):
+        # two steps with an agreement in between: a rank whose local allocation fails (the local matrix and two
+        # panel buffers in HBM, three streams) must not leave the others blocked inside ncclCommInitRank
+        rc = self.lib.gpx_mg_create_local(ctypes.byref(self.h), *shape)
+        ident = np.zeros(_lib.MG_ID_BYTES, dtype=np.uint8)
+        if rc == 0 and self.rank == 0 and adopt_from is None:
+            rc = self.lib.gpx_mg_unique_id(ident.ctypes.data_as(ctypes.c_void_p))
+        err = _lib.last_error() if rc != 0 else ""      # (of whichever of the two calls failed)
+        if dist is not None and self.world > 1:
+            import torch
+            from .mlii import _cpu_group
+            cpu = _cpu_group(dist)           # CPU tensors: a gloo side group when the default group is nccl
+            ok = torch.tensor([1 if rc == 0 else 0], dtype=torch.int32)
+            dist.all_reduce(ok, op=dist.ReduceOp.MIN, group=cpu)
+            if int(ok.item()) == 0:
+                self.close()
+                raise _lib.GpxError("multi-GPU set-up failed on %s before the communicator was created%s"
+                                    % ("this rank" if rc != 0 else "another rank", (": " + err) if err else ""))
+            if adopt_from is None:
+                dist.broadcast(torch.from_numpy(ident), src=0, group=cpu)    # the ncclUniqueId travels out of band
+        else:
+            _lib.check(rc)
+        try:
+            if adopt_from is not None:
+                # ONE ncclCommInitRank per process: a handle of another width takes over the communicator (round 5: the
+                # tuning pass tries several layouts; re-creating communicators in a running job is a risk nobody needs)
+                _lib.check(self.lib.gpx_mg_adopt_comm(self.h, adopt_from.h))
+            else:
+                _lib.check(self.lib.gpx_mg_connect(self.h, ident.ctypes.data_as(ctypes.c_void_p)))
+        except Exception:
+            self.close()
+            raise
+
+    def _create_callbacks(self, shape, dist, callbacks):
+        b = a = None
+        if self.world > 1:
+            self._cb = callbacks if callbacks is not None else GlooCallbacks(dist)
+            b = ctypes.cast(self._cb.bcast, ctypes.c_void_p)
+            a = ctypes.cast(self._cb.allreduce, ctypes.c_void_p)
+        _lib.check(self.lib.gpx_mg_create_cb(ctypes.byref(self.h), *shape, b, a, None))
 
     def _check(self, rc):
         if rc != 0 and self._cb is not None and self._cb.error is not None:
@@ -224,54 +257,53 @@ class NativeDistributedGP(object):
             raise err
         _lib.check(rc)
 
+    @staticmethod
+    def _params(params):
+        return np.ascontiguousarray(params, dtype=np.float64)
+
+    def _points(self, xo):
+        return np.ascontiguousarray(np.asarray(xo, dtype=np.float64).reshape(-1, self.d))
+
     def set_data(self, x, y):
         x = np.ascontiguousarray(np.asarray(x, dtype=np.float64).reshape(self.n, self.d))
         y = np.ascontiguousarray(np.asarray(y, dtype=np.float64).reshape(self.n))
         self._check(self.lib.gpx_mg_set_data(self.h, _lib.dptr(x), _lib.dptr(y)))
 
     def fit(self, params, s):
-        p = np.ascontiguousarray(params, dtype=np.float64)
-        llh, info = ctypes.c_double(0.0), ctypes.c_int(0)
+        p, llh, info = self._params(params), ctypes.c_double(0.0), ctypes.c_int(0)
         self._check(self.lib.gpx_mg_fit(self.h, _lib.dptr(p), float(s), ctypes.byref(llh), ctypes.byref(info)))
         self.log_lh, self.info = llh.value, info.value
         return self.log_lh
 
     def mean(self, params, xo):
-        p = np.ascontiguousarray(params, dtype=np.float64)
-        xo = np.ascontiguousarray(np.asarray(xo, dtype=np.float64).reshape(-1, self.d))
+        p, xo = self._params(params), self._points(xo)
         out = np.empty(xo.shape[0], dtype=np.float64)
         self._check(self.lib.gpx_mg_mean(self.h, _lib.dptr(p), _lib.dptr(xo), xo.shape[0], _lib.dptr(out)))
+        return out
+
+    def _agreed(self, entry, params, xo, out_shape, *extra):
+        """A collective prediction whose ranks agree on their arguments first (gpx_mg_cov / gpx_mg_var)."""
+        if self.info:                          # the reduced info word of the fit: the same on every rank
+            raise _lib.lapack_info_error(self.info)
+        p, xo = self._params(params), self._points(xo)
+        out = np.empty(out_shape(xo.shape[0]), dtype=np.float64)
+        rc = entry(self.h, _lib.dptr(p), _lib.dptr(xo), xo.shape[0], *(extra + (_lib.dptr(out),)))
+        if rc == _lib.ERR_ARG and (self._cb is None or self._cb.error is None):
+            raise RankMismatchError(_lib.last_error())    # (well-formed here, shaped above: the ranks disagreed)
+        self._check(rc)
         return out
 
     def cov(self, params, xo):
         """Posterior covariance at xo, (m, m), on every rank (gpx_mg_cov: L stays distributed).  Collective: every rank
         calls it with the same params and xo after the same fit.  The ranks agree before any work, so a disagreement (m,
         xo or params differ between ranks) raises `RankMismatchError` on every rank instead of hanging."""
-        if self.info:                          # the reduced info word of the fit: the same on every rank
-            raise _lib.lapack_info_error(self.info)
-        p = np.ascontiguousarray(params, dtype=np.float64)
-        xo = np.ascontiguousarray(np.asarray(xo, dtype=np.float64).reshape(-1, self.d))
-        out = np.empty((xo.shape[0], xo.shape[0]), dtype=np.float64)
-        rc = self.lib.gpx_mg_cov(self.h, _lib.dptr(p), _lib.dptr(xo), xo.shape[0], _lib.dptr(out))
-        if rc == _lib.ERR_ARG and (self._cb is None or self._cb.error is None):
-            raise RankMismatchError(_lib.last_error())    # (well-formed here, shaped above: the ranks disagreed)
-        self._check(rc)
-        return out
+        return self._agreed(self.lib.gpx_mg_cov, params, xo, lambda m: (m, m))
 
     def var(self, params, xo, chunk_rows=0):
         """Posterior variance at xo, (m,), on every rank (gpx_mg_var: the fan-in solve of `cov` per row chunk of xo, row
         sums of squares instead of the (m, m) product -- any m).  Collective, and the ranks agree first: m, xo, params or
         chunk_rows that differ between ranks raise `RankMismatchError` on every rank."""
-        if self.info:                          # the reduced info word of the fit: the same on every rank
-            raise _lib.lapack_info_error(self.info)
-        p = np.ascontiguousarray(params, dtype=np.float64)
-        xo = np.ascontiguousarray(np.asarray(xo, dtype=np.float64).reshape(-1, self.d))
-        out = np.empty(xo.shape[0], dtype=np.float64)
-        rc = self.lib.gpx_mg_var(self.h, _lib.dptr(p), _lib.dptr(xo), xo.shape[0], int(chunk_rows), _lib.dptr(out))
-        if rc == _lib.ERR_ARG and (self._cb is None or self._cb.error is None):
-            raise RankMismatchError(_lib.last_error())    # (well-formed here, shaped above: the ranks disagreed)
-        self._check(rc)
-        return out
+        return self._agreed(self.lib.gpx_mg_var, params, xo, lambda m: m, int(chunk_rows))
 
     @property
     def alpha(self):
@@ -320,13 +352,10 @@ class NativeDistributedGP(object):
                 "panel_bcast": "scatter+allgather" if v[2].value else "one collective", "wait_timing": bool(v[3].value)}
 
     def timing(self, extended=False):
-        if extended:
-            ms = np.zeros(len(self.TIMING_KEYS_EX))
-            self._check(self.lib.gpx_mg_timing_ex(self.h, _lib.dptr(ms), ms.size))
-            return dict(zip(self.TIMING_KEYS_EX, [float(v) for v in ms]))
-        ms = np.zeros(8)
-        self._check(self.lib.gpx_mg_timing(self.h, _lib.dptr(ms)))
-        return dict(zip(self.TIMING_KEYS, [float(v) for v in ms]))
+        keys = self.TIMING_KEYS_EX if extended else self.TIMING_KEYS     # (the first 8 slots are gpx_mg_timing's)
+        ms = np.zeros(len(keys))
+        self._check(self.lib.gpx_mg_timing_ex(self.h, _lib.dptr(ms), ms.size))
+        return dict(zip(keys, [float(v) for v in ms]))
 
     def chain_by_panel(self):
         """ms per panel of the last fit that this rank spent on the owner's chain (factor + pack + the last chunk of the
@@ -417,9 +446,9 @@ def rehearse_rank(N, d, rank, world, X, y, params, s, dtype_id=_lib.F64, nb=None
     # the rider row: row n of the resident matrix <- L^-1 y (what rides through the distributed factorisation as one more
     # row of every panel; the single-GPU fit's own work row does not survive its backward solve)
     from .device import DeviceBuffer
-    es_ = 8 if dtype_id == _lib.F64 else 4
-    tmp = DeviceBuffer.from_host(np.ascontiguousarray(y, dtype=np.float64 if es_ == 8 else np.float32))
-    _lib.check(lib.gpx_d_trsv_lower(dtype_id, A, N, lda.value, tmp.ptr, ctypes.c_void_p(A.value + N * lda.value * es_), 0, None))
+    es, npdt = (8, np.float64) if dtype_id == _lib.F64 else (4, np.float32)
+    tmp = DeviceBuffer.from_host(np.ascontiguousarray(y, dtype=npdt))
+    _lib.check(lib.gpx_d_trsv_lower(dtype_id, A, N, lda.value, tmp.ptr, ctypes.c_void_p(A.value + N * lda.value * es), 0, None))
     _lib.check(lib.gpx_stream_sync(None))
     tmp.free()
     reh = {"rank": rank, "world": world, "L_ptr": A.value, "ldl": lda.value, "alpha_ptr": al.value,
@@ -436,18 +465,15 @@ def rehearse_rank(N, d, rank, world, X, y, params, s, dtype_id=_lib.F64, nb=None
         sched = mg.schedule_info()                      # what is IN EFFECT (the arguments may have been None)
         mg.set_data(X, y)
         runs = []
-        p = np.ascontiguousarray(params, dtype=np.float64)
         for i in range(fits):
             t0 = time.perf_counter()
-            mg.fit(p, s)
+            mg.fit(params, s)
             wall = time.perf_counter() - t0
             tm = mg.timing(extended=True)
             tm["wall_s"] = wall
             runs.append(tm)
         chain = mg.chain_by_panel()
         # the owned block columns against the resident factor (both in HBM: a few sampled rows of each owned panel)
-        es = 8 if dtype_id == _lib.F64 else 4
-        npdt = np.float64 if es == 8 else np.float32
         Aloc, ld_loc = ctypes.c_void_p(), ctypes.c_int64()
         _lib.check(lib.gpx_mg_device_ptrs(mg.h, ctypes.byref(Aloc), ctypes.byref(ld_loc)))
         worst = 0.0
@@ -470,8 +496,7 @@ def rehearse_rank(N, d, rank, world, X, y, params, s, dtype_id=_lib.F64, nb=None
         alpha_ref = np.array(g.inv_Kxx_y, dtype=np.float64)
         alpha_err = float(np.abs(alpha - alpha_ref).max() / max(1e-300, np.abs(alpha_ref).max()))
         last = runs[-1]
-        nblk = -(-N // nbv)
-        steps = nblk
+        steps = -(-N // nbv)
         own = chain[chain > 0]
         return {
             "what": "rehearsal of rank %d of %d on one GPU: measured compute, MODELLED transfer" % (rank, world),
@@ -580,7 +605,6 @@ def bench_distributed(args, X, y, Xo, params, s, dtype_id, residual_check=None):
     N, d, m = args.n, args.d, args.m
     # RCCL prints a version banner on stdout when its communicator is created; keep stdout clean for the
     # single JSON line (stderr still shows everything)
-    import sys
     sys.stdout.flush()
     saved_stdout = os.dup(1)
     os.dup2(2, 1)

@@ -4,11 +4,11 @@ A GPU box admits at most six processes on its card, so a world of eight -- the n
 rehearsed with one process per rank there.  The schedule itself does not care where its ranks live: every rank is a
 `gpx_mg` handle with its own streams, the library's per-thread state (look-ahead stream, published blocks of the
 resident panel kernel) is per host thread, and the host-callback data plane only needs a broadcast and an all-reduce.
-Here those rendezvous on a threading.Barrier and pass the payload through a shared host buffer -- the same two-hop
-staging as multi_gpu.GlooCallbacks, without the process boundary.  ctypes releases the GIL around every C call and a
+Here those rendezvous on a threading.Barrier and pass the payload through a shared host buffer -- the two-hop staging
+of multi_gpu.HostStagedCallbacks, which GlooCallbacks shares, without the process boundary.  ctypes releases the GIL around
+every C call and a
 Barrier wait releases it too, so the eight ranks really run their launches concurrently.
 """
-import ctypes
 import threading
 
 import numpy as np
@@ -25,57 +25,35 @@ class _Shared(object):
         self.slots = [None] * world
 
 
-class ThreadCallbacks(object):
-    """One rank's end of the in-process collectives (the interface NativeDistributedGP(callbacks=...) expects)."""
-
-    _NP = {_lib.F64: np.float64, _lib.F32: np.float32, 2: np.int32}
+class ThreadCallbacks(multi_gpu.HostStagedCallbacks):
+    """One rank's end of the in-process collectives: the exchange over a Barrier and shared host arrays."""
 
     def __init__(self, shared, rank):
-        self.shared, self.rank, self.world = shared, rank, shared.world
-        self.lib = _lib.load()
-        self.error = None
-        self.bcast = _lib.MG_BCAST_FN(self._bcast)
-        self.allreduce = _lib.MG_ALLREDUCE_FN(self._allreduce)
+        self.shared = shared
+        multi_gpu.HostStagedCallbacks.__init__(self, rank, shared.world)
 
-    def _fail(self, exc):
-        self.error = exc
+    def rank_failed(self, exc):
         self.shared.barrier.abort()          # nobody is left waiting for a rank that has given up
-        return 1
 
-    def _bcast(self, user, dev_ptr, nbytes, root, stream):
-        try:
-            sh = self.shared
-            _lib.check(self.lib.gpx_stream_sync(stream))
-            if self.rank == root:
-                buf = np.empty(nbytes, dtype=np.uint8)
-                _lib.check(self.lib.gpx_memcpy_d2h(buf.ctypes.data_as(ctypes.c_void_p), dev_ptr, nbytes, stream))
-                sh.buf = buf
-            sh.barrier.wait()
-            if self.rank != root:
-                src = sh.buf
-                assert src is not None and src.nbytes == nbytes, "broadcast size mismatch between ranks"
-                _lib.check(self.lib.gpx_memcpy_h2d(dev_ptr, src.ctypes.data_as(ctypes.c_void_p), nbytes, stream))
-            sh.barrier.wait()                # the root may reuse the buffer
-            return 0
-        except Exception as exc:             # noqa: BLE001 -- an exception must not unwind through the C frames
-            return self._fail(exc)
+    def exchange_bcast(self, buf, root):
+        sh = self.shared
+        if self.rank == root:
+            sh.buf = buf
+        sh.barrier.wait()
+        src = sh.buf
+        assert src is not None and src.nbytes == buf.nbytes, "broadcast size mismatch between ranks"
+        sh.barrier.wait()                    # everybody holds the root's array: the root may post its next one
+        return src
 
-    def _allreduce(self, user, dev_ptr, count, dtype, op, stream):
-        try:
-            sh = self.shared
-            buf = np.empty(count, dtype=self._NP[dtype])
-            _lib.check(self.lib.gpx_stream_sync(stream))
-            _lib.check(self.lib.gpx_memcpy_d2h(buf.ctypes.data_as(ctypes.c_void_p), dev_ptr, buf.nbytes, stream))
-            sh.slots[self.rank] = buf
-            sh.barrier.wait()
-            acc = sh.slots[0].copy()
-            for r in range(1, self.world):   # rank order: every rank forms the same sum
-                acc = acc + sh.slots[r] if op == 0 else np.maximum(acc, sh.slots[r])
-            _lib.check(self.lib.gpx_memcpy_h2d(dev_ptr, acc.ctypes.data_as(ctypes.c_void_p), acc.nbytes, stream))
-            sh.barrier.wait()
-            return 0
-        except Exception as exc:             # noqa: BLE001
-            return self._fail(exc)
+    def exchange_allreduce(self, buf, op):
+        sh = self.shared
+        sh.slots[self.rank] = buf
+        sh.barrier.wait()
+        acc = sh.slots[0].copy()
+        for r in range(1, self.world):       # rank order: every rank forms the same sum
+            acc = acc + sh.slots[r] if op == 0 else np.maximum(acc, sh.slots[r])
+        sh.barrier.wait()                    # everybody has read the slots: they may be filled again
+        return acc
 
 
 def run_thread_world(world, N, d, nb, m, dtype_id=0, s=1.0, sag=False, timeout=300):
