@@ -19,8 +19,9 @@ ERR_ARG, ERR_HIP, ERR_NO_DEVICE, ERR_NOMEM, ERR_UNSUPPORTED, ERR_INTERNAL = -1, 
 (ROUTE_TRSV_OPS, ROUTE_TRSV_STEPS, ROUTE_PANEL_RES, ROUTE_PANEL_CHAIN, ROUTE_FIT_RIDE, ROUTE_FIT_TWO_SOLVES,
  ROUTE_GEMM_FAST, ROUTE_GEMM_GENERIC, ROUTE_SYRK_EXACT, ROUTE_SYRK_PATCH, ROUTE_MG_BCAST_ONE, ROUTE_MG_BCAST_SAG,
  ROUTE_FIT_OPS_AHEAD, ROUTE_TRSM_OPS, ROUTE_POTRF_PAIR, ROUTE_VAR_CHUNK, ROUTE_LOO_CHUNK, ROUTE_TRSM_L_OPS,
- ROUTE_GRAD_CHUNK, ROUTE_EXTEND, ROUTE_SAMPLE, ROUTE_KAPPLY_FUSED, ROUTE_KAPPLY_GEMM, ROUTE_PATHS_GRAD_CHUNK) = range(24)
-PROF_RANDN, PROF_RFF, PROF_KAPPLY, PROF_KAPPLY_GRAD = 14, 15, 16, 17
+ ROUTE_GRAD_CHUNK, ROUTE_EXTEND, ROUTE_SAMPLE, ROUTE_KAPPLY_FUSED, ROUTE_KAPPLY_GEMM, ROUTE_PATHS_GRAD_CHUNK,
+ ROUTE_REMOVE) = range(25)
+PROF_RANDN, PROF_RFF, PROF_KAPPLY, PROF_KAPPLY_GRAD, PROF_CHOL_DELETE = 14, 15, 16, 17, 18
 F64, F32 = 0, 1
 KERNEL_GAUSSIAN, KERNEL_PERIODIC, KERNEL_GAUSSIAN_ARD = 0, 1, 2
 ARD_MAX_D = 64
@@ -107,6 +108,7 @@ _SIGNATURES = {
                                c_void_p, c_void_p, c_void_p]),
     "gpx_d_copy_lower": (c_int, [c_int, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p]),
     "gpx_d_schur_lower": (c_int, [c_int, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p]),
+    "gpx_d_chol_delete": (c_int, [c_int, c_void_p, c_int64, c_int64, POINTER(c_int64), c_int64, c_void_p, c_int64, c_void_p]),
     "gpx_d_randn": (c_int, [c_int, c_void_p, c_int64, c_int64, c_int64, c_uint64, c_uint64, c_uint64, c_void_p]),
     "gpx_d_mvn_sample": (c_int, [c_int, c_void_p, c_int64, c_int64, c_void_p, c_double, c_int64, c_uint64, c_uint64, c_void_p,
                                  c_int64, c_void_p, c_int64, c_void_p, c_void_p]),
@@ -141,6 +143,7 @@ _SIGNATURES = {
     "gpx_gp_extend": (c_int, [c_void_p, c_double_p, c_double_p, c_int64, POINTER(c_void_p), c_int_p]),
     "gpx_gp_extend_from_K": (c_int, [c_void_p, c_double_p, c_double_p, c_int64, c_double_p, c_double_p, POINTER(c_void_p),
                                      c_int_p]),
+    "gpx_gp_remove": (c_int, [c_void_p, POINTER(c_int64), c_int64, POINTER(c_void_p), c_int_p]),
     "gpx_gp_sample": (c_int, [c_void_p, c_double_p, c_int64, c_int64, c_uint64, c_int, c_double, c_double_p, c_int_p]),
     "gpx_gp_sample_from_K": (c_int, [c_void_p, c_double_p, c_double_p, c_int64, c_int64, c_uint64, c_int, c_double, c_double_p,
                                      c_int_p]),

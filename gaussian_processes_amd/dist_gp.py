@@ -9,8 +9,8 @@ object as `gp.GP` -- ``log_lh``, ``lh``, ``inv_Kxx_y``, ``mean(xo)``, ``cov(xo)`
 
 Every rank builds the same object with the same data and calls the same members in the same order: a fit, a mean
 and a cov are collective.  The factor never leaves the ranks' HBM, so what needs an n x n host copy (`Kxx`, `Lxx`,
-`inv_Kxx`, the derivative stack, `dm_dtheta`), leave-one-out, the input-space gradients, growing the fit and joint samples (`loo`, `inv_Kxx_diag`, `dmean_dx`, `dvar_dx`,
-`predict_grad`, `extend`, `sample`, `sample_paths`: not implemented over the distributed factor) and what would have to carry a handle or a communicator to another
+`inv_Kxx`, the derivative stack, `dm_dtheta`), leave-one-out, the input-space gradients, growing and shrinking the fit and joint samples (`loo`, `inv_Kxx_diag`, `dmean_dx`, `dvar_dx`,
+`predict_grad`, `extend`, `remove`, `sample`, `sample_paths`: not implemented over the distributed factor) and what would have to carry a handle or a communicator to another
 process (`save_fitted`, copy, pickle) raises NotImplementedError: `GP` has them.
 """
 import numpy as np
@@ -219,6 +219,7 @@ class DistributedGP(GP):
     dvar_dx = _unsupported("dvar_dx", _NO_XGRAD)
     predict_grad = _unsupported("predict_grad", _NO_XGRAD)
     extend = _unsupported("extend", "appending rows to the distributed factor is not implemented; one GPU has it")
+    remove = _unsupported("remove", "deleting rows of the distributed factor is not implemented; one GPU has it")
     sample = _unsupported("sample", "joint samples over the distributed factor are not implemented; one GPU has them")
     sample_paths = _unsupported("sample_paths", "posterior paths over the distributed factor are not implemented; one GPU has them")
     save_fitted = _unsupported("save_fitted")

@@ -858,6 +858,72 @@ class GP(object):
         obj._dev = new
         return obj
 
+    # ---- shrinking a fitted GP ----
+    def _removal_indices(self, idx):
+        """`idx` of `remove` as a sorted int64 array of distinct indices in [0, n), fewer than n of them; ValueError otherwise."""
+        n = self._n
+        a = np.asarray(idx)
+        if a.dtype == np.bool_:
+            if a.shape != (n,):
+                raise ValueError("invalid shape for a boolean mask: %s, expected (%d,)" % (str(a.shape), n))
+            a = np.flatnonzero(a)
+        else:
+            if a.ndim == 0:
+                a = a.reshape(1)
+            if a.ndim != 1:
+                raise ValueError("idx must be an int, a 1-D sequence of ints or a boolean mask of shape (n,)")
+            if a.size and not np.issubdtype(a.dtype, np.integer):
+                raise ValueError("idx must hold integers, not %s" % a.dtype)
+        if a.size == 0:
+            raise ValueError("remove needs at least one index")
+        a = a.astype(np.int64)
+        if ((a < -n) | (a >= n)).any():
+            raise ValueError("index out of range for %d points" % n)
+        a = np.sort(np.where(a < 0, a + n, a))
+        if (a[1:] == a[:-1]).any():
+            raise ValueError("idx holds an index more than once")
+        if a.size >= n:
+            raise ValueError("cannot remove all %d points" % n)
+        return np.ascontiguousarray(a)
+
+    def remove(self, idx):
+        r"""A new, fitted `GP` on the data of this one without the observations `idx`, without refactoring.  Deleting
+        row and column `i` of :math:`K = L L^\top` leaves the factor before `i` as it is; the part behind it takes the
+        rank-1 update :math:`L_{33}' L_{33}'^\top = L_{33} L_{33}^\top + l_{32} l_{32}^\top` by Givens rotations --
+        unconditionally stable, and no kernel is evaluated, so every family and every plugin kernel takes the same path.
+        Cost: :math:`O((n - r_0)^2 k)` for `k` indices of which :math:`r_0` is the smallest -- all `k` updates share ONE
+        pass, so the trailing triangle moves once -- and two solves for the new :math:`K^{-1} y` (:math:`O(n^2)`),
+        against :math:`n^3/3` for ``g.x = ...; g.y = ...``.
+
+        `idx`: an int, a 1-D sequence of ints (negative values count from the end; any order) or a boolean mask of
+        shape ``(n,)``.  ValueError for an empty `idx`, an index twice, an index out of range, all `n` points, or a
+        non-integer dtype.  The result has ``np.delete(x, idx, axis=0)`` and ``np.delete(y, idx)``, a deep copy of `K`
+        and the same `s`, `dtype` and `device`; this object and its device state are unchanged.  Raises
+        numpy.linalg.LinAlgError when this GP's `Kxx` is not positive definite.
+
+        Memory: source and result coexist, so TWO factors are resident in HBM (:math:`n^2 + (n - k)^2` elements) until
+        the source is dropped; ``g = g.remove(i)`` releases it.  A sliding window is
+        ``g = g.extend(xn, yn).remove(range(k))``."""
+        rm = self._removal_indices(idx)                        # every refusal comes before the library is touched
+        k = int(rm.size)
+        st = self._fit_pd()
+        lib = _lib.load()
+        h, info = ctypes.c_void_p(), ctypes.c_int(0)
+        _lib.check(lib.gpx_gp_remove(st.handle, rm.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), k, ctypes.byref(h),
+                                     ctypes.byref(info)))
+        try:
+            obj = type(self)(deepcopy(self.K), np.delete(self._x, rm, axis=0), np.delete(self._y, rm),
+                             s=self._s, dtype="float64" if self._dtype == _lib.F64 else "float32", device=self._device)
+            new = _DeviceState.adopt(h, (obj._dtype, st.key[1], obj._n, obj._d, obj._device))
+        except Exception:
+            lib.gpx_gp_destroy(h)
+            raise
+        new.info = info.value
+        new.data_version = obj._data_version
+        new.params_version = new.fit_version = obj._version
+        obj._dev = new
+        return obj
+
     def fit_timing(self):
         """Milliseconds of the last device fit: kernel build, potrf, solve, reductions, total
         (HIP events on the handle's stream)."""

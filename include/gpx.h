@@ -177,6 +177,7 @@ int gpx_stream_wait_event(void *stream, void *event);
 #define GPX_PROF_RFF         15 /* rff_features_kernel (gpx_d_rff_features): bytes written */
 #define GPX_PROF_KAPPLY      16 /* stream_apply_kernel + its slice reduction (gpx_d_kmat_apply, fused route): kernel evaluations m*n per group of weight vectors */
 #define GPX_PROF_KAPPLY_GRAD 17 /* stream_apply_grad_kernel + its slice reduction (gpx_d_kmat_apply_grad): kernel evaluations m*n per group of weight vectors and window of dimensions */
+#define GPX_PROF_CHOL_DELETE 18 /* del_copy_rows_kernel + del_block_kernel (gpx_d_chol_delete), ONE record per call around all of its launches: bytes read + written */
 int gpx_prof_enable(int on);    /* also clears the registry */
 int gpx_prof_read(int cls, double *launches, double *total_ms, double *total_work);
 
@@ -208,6 +209,7 @@ int gpx_prof_read(int cls, double *launches, double *total_ms, double *total_wor
 #define GPX_ROUTE_KAPPLY_FUSED   21   /* gpx_d_kmat_apply: K(xo, x) V^T by the fused kernel, K never materialised; one hit per chunk */
 #define GPX_ROUTE_KAPPLY_GEMM    22   /* gpx_d_kmat_apply: gpx_d_kmat into scratch, then gpx_d_gemm_nt; one hit per row chunk of xo  */
 #define GPX_ROUTE_PATHS_GRAD_CHUNK 23 /* gpx_paths_grad: one hit per row chunk of xo                                                   */
+#define GPX_ROUTE_REMOVE         24   /* gpx_gp_remove: one hit per call                                               */
 int gpx_debug_route_count(int route, int64_t *count);
 /* roctx ranges pushed so far (GPX_ROCTX=1: every gpx_gp_* call and every launch class below it is a nested host range for
  * `rocprofv3 --marker-trace`; libroctx64.so is loaded on first use; 0 while the switch is off) */
@@ -391,6 +393,18 @@ int gpx_d_copy_lower(int dtype, const void *src, int64_t lds, void *dst, int64_t
  * aligned ones take the fast product kernel.  When all n columns fit ONE slice there are no partials: one product
  * S -= B B^T on the lower tiles, accumulated by the product kernel in `dtype`.) */
 int gpx_d_schur_lower(int dtype, const void *B, int64_t k, int64_t n, int64_t ldb, void *S, int64_t lds, void *stream);
+/* The Cholesky factor without k of its rows and columns: out (n - k) x (n - k), ldo, lower triangle = the factor of K with
+ * rows and columns idx deleted, where L (n x n, ldl, lower, on the device, only read) is the factor of K.  The strict upper
+ * triangle of out is not written.  idx_host: k sorted distinct indices in [0, n) on the HOST, 1 <= k < n (it may be reused
+ * on return: the call waits for its upload, nothing else).  GPX_ERR_ARG for unsorted, repeated or out-of-range indices,
+ * k >= n, out == L or a pitch that is too small.
+ * Rows and columns before idx[0] are copied; behind each deleted column the factor takes a rank-1 UPDATE by Givens
+ * rotations (stable for any factor, no pivot can fail), all k of them in ONE pass: one launch per block of 32 columns from
+ * idx[0]'s block on, in stream order; the k update vectors (n x k in `dtype`) live in this host thread's scratch.
+ * O((n - idx[0])^2 k) flops, the factor read once and written once.  The arithmetic is `dtype`'s; no atomics and a fixed
+ * order: bitwise repeatable.  Any base / pitch is accepted: 16-byte loads where L's allow.  GPX_PROF_CHOL_DELETE. */
+int gpx_d_chol_delete(int dtype, const void *L, int64_t n, int64_t ldl, const int64_t *idx_host, int64_t k, void *out, int64_t ldo,
+                      void *stream);
 
 /* Normal numbers, counter based.
  * out[i, j] = z(seed, stream, offset + i * cols + j)  for i < rows, j < cols;  out: rows x cols, ld >= cols, in `dtype`.
@@ -569,6 +583,15 @@ int gpx_gp_extend(gpx_gp_t *gp, const double *x_new, const double *y_new, int64_
 /* plugin kernels: the caller supplies B = K(x_new, x) (k, n) and C = K(x_new, x_new) + s^2 I (k, k; lower read), HOST float64 */
 int gpx_gp_extend_from_K(gpx_gp_t *gp, const double *x_new, const double *y_new, int64_t k,
                          const double *Knew_old, const double *Knew_new, gpx_gp_t **out, int *info);
+/* Shrinking a fitted GP by k observations without refactoring (gpx_d_chol_delete on the handle's factor).
+ * A NEW fitted handle for the n - k kept points, in their order, same dtype / kernel / params / s as `gp`: x and y are
+ * gathered on the device, the factor is the source's with rows and columns idx deleted, alpha / logdet / y^T alpha come from
+ * the tail of gpx_gp_fit.  No kernel is evaluated: a handle fitted from gpx_gp_set_K (plugin kernels) takes the same entry.
+ * idx: k sorted distinct indices in [0, n), HOST, 1 <= k < n (else GPX_ERR_ARG).  `gp` must be fitted and positive definite
+ * (else GPX_ERR_ARG); it is never written and stays usable.  *info (HOST, may not be NULL): 0 -- the rotations cannot fail.
+ * Synchronous.  On any failure *out = NULL and `gp` is intact.  Source and result coexist: two factors are resident until
+ * the caller destroys one.  gpx_gp_last_timing of the new handle: [0] 0 [1] the deletion [2] solves [3] reductions [4] total. */
+int gpx_gp_remove(gpx_gp_t *gp, const int64_t *idx, int64_t k, gpx_gp_t **out, int *info);
 /* Joint posterior samples at xo (m, d) HOST float64 -> out (S, m) HOST float64: row s is one draw of the function values
  * at the m points, mean(xo) + Lc z_s with Lc Lc^T = cov(xo) + (jitter [+ s^2]) I.  The covariance is built exactly as
  * gpx_gp_cov builds it (the matrix that is factored is bit for bit the one it would download), the mean is gpx_gp_mean's, then
