@@ -140,6 +140,8 @@ _SIGNATURES = {
     "gpx_gp_var_grad": (c_int, [c_void_p, c_double_p, c_int64, c_int64, c_double_p, c_double_p]),
     "gpx_gp_inv_diag": (c_int, [c_void_p, c_int64, c_double_p]),
     "gpx_gp_loo": (c_int, [c_void_p, c_int64, c_double_p, c_double_p, c_double_p, c_double_p]),
+    "gpx_gp_loo_grad": (c_int, [c_void_p, c_double_p, c_double_p]),
+    "gpx_gp_loo_grad_weights": (c_int, [c_void_p, c_double_p, c_int64]),
     "gpx_gp_extend": (c_int, [c_void_p, c_double_p, c_double_p, c_int64, POINTER(c_void_p), c_int_p]),
     "gpx_gp_extend_from_K": (c_int, [c_void_p, c_double_p, c_double_p, c_int64, c_double_p, c_double_p, POINTER(c_void_p),
                                      c_int_p]),
@@ -166,6 +168,7 @@ _SIGNATURES = {
     "gpx_gp_dm_dtheta": (c_int, [c_void_p, c_double_p, c_int64, c_double_p]),
     "gpx_gp_fit_batch": (c_int, [c_void_p, c_double_p, c_int64, c_double_p, c_int_p]),
     "gpx_gp_fit_batch_grad": (c_int, [c_void_p, c_double_p, c_int64, c_double_p, c_double_p, c_double_p, c_int_p]),
+    "gpx_gp_fit_batch_loo": (c_int, [c_void_p, c_double_p, c_int64, c_double_p, c_double_p, c_int_p]),
     "gpx_gp_save": (c_int, [c_void_p, c_char_p]),
     "gpx_gp_load": (c_int, [POINTER(c_void_p), c_char_p]),
     "gpx_gp_describe": (c_int, [c_void_p, c_int_p, c_int_p, POINTER(c_int64), c_int_p, c_double_p, c_double_p]),

@@ -315,5 +315,30 @@ int dloglh_reduce_ard(int dtype, const void *xs, int64_t n, int d, const double 
                       int64_t ldw, double *partial_dev, double *out, hipStream_t st);
 int kmat(int dtype, int kernel, int member, const void *x1, int64_t n, const void *x2, int64_t m,
          int d, const double *params, double diag_add, int tri, void *out, int64_t ld, hipStream_t st);
+// The leave-one-out criterion's passes (gpx_kmat.hip): dloglh_reduce's and dloglh_reduce_ard's arguments with a second vector
+// r and Pm = K^-1 diag(c) K^-1 (lower triangle read) where those take W; the coefficient of an entry is
+// (r_a alpha_b + alpha_a r_b) / 2 - Pm_ab and the last value of `out` is trace Pm.  The same partial-sum block.
+int dloo_reduce(int dtype, int kernel, const void *x, int64_t n, int d, const double *params, const void *alpha, const void *r,
+                const void *Pm, int64_t ldp, double *partial_dev, double *out4, hipStream_t st);
+int dloo_reduce_ard(int dtype, const void *xs, int64_t n, int d, const double *iso, const void *alpha, const void *r, const void *Pm,
+                    int64_t ldp, double *partial_dev, double *out, hipStream_t st);
+// The ingredients of the leave-one-out gradient's weights G = (r alpha^T + alpha r^T) / 2 - Pm from a factor (gpx_loograd.hip).
+// One system's vectors, all in ONE block of loo_vec_bytes() that the caller owns (loo_vecs_at lays it out):
+struct LooVecs {
+    double *kii, *logp;          // n doubles each: diag(K^-1) and the per-point log p(y_i | the others)
+    double *sums;                // [0]: sum of logp (fixed order: sum_f64)   [1]: r . alpha
+    void *u, *sq, *t, *r;        // n each, the system's dtype: alpha / k, sqrt(c), solve scratch, r = K^-1 (alpha / k)
+};
+size_t loo_vec_bytes(int dtype, int64_t n);
+LooVecs loo_vecs_at(void *block, int dtype, int64_t n);
+// loo_weights_vectors: behind inv_from_factor(..., GPX_FULL, ...), X = L^-T and W = K^-1 in HBM.  k from the rows of X as
+// loo_rows sums them (kii_have != null: that diagonal instead, through loo_points), the criterion's value, c, r by two
+// sweeps with the factor, then Y = W diag(sqrt(c)) over X.  loo_weights_product: Pm = Y Y^T, lower triangle, over W, for
+// `count` systems n * ldl elements apart in lock-step.  loo_weights_from_factor: all of it for one system.
+int loo_weights_vectors(int dtype, const void *L, int64_t n, int64_t ldl, const void *y, const void *alpha, void *X, const void *W,
+                        const LooVecs &v, const double *kii_have, TrsvOps *ops, hipStream_t st);
+int loo_weights_product(int dtype, int64_t n, int64_t ldl, const void *Y, void *Pm, int count, hipStream_t st);
+int loo_weights_from_factor(int dtype, const void *L, int64_t n, int64_t ldl, const void *y, const void *alpha, void *X, void *W,
+                            const LooVecs &v, const double *kii_have, TrsvOps *ops, hipStream_t st);
 
 }  // namespace gpx

@@ -272,11 +272,6 @@ struct RowChunks {
     int64_t rc(int64_t c) const { return std::min(rows, m - c * rows); }    // ... and how many it has
 };
 
-static const char *NONFINITE_MSG = "array must not contain infs or NaNs";      // scipy's text (gp/gp.py:294, 332-334)
-
-#define GP_NEED_FINITE_Y(g)                                                    \
-    do { if (!(g)->y_finite) { set_error("%s (y)", NONFINITE_MSG); return GPX_ERR_ARG; } } while (0)
-
 // The posterior covariance at m test points, left on the device:  C (m x m, ldc) = Kxoxo - V^T V,  V^T = Kxox L^-T
 // (gp/gp.py:622-625 without K^-1).  xo: the test points (built-in families), or Kxox / Kxoxo: the caller's matrices (plugin
 // kernels).  mean_dev (may be null; m elements, handle dtype): the posterior mean at the same points, as gpx_gp_mean /
@@ -975,8 +970,11 @@ int gpx_gp_dloglh_dtheta(gpx_gp_t *g, double *out)
 // of the solves covers all of them (grid dimension y / x = matrix index), so the chain of small
 // dependent launches that bounds ONE n = 8192 factorisation is paid once per batch and the chip stays
 // filled by the trailing updates of all matrices.  Chunked when B matrices do not fit in free HBM.
+// loo != 0 (gpx_gp_fit_batch_loo): the criterion is the leave-one-out one.  The factorisation, the solves and the groups are
+// the same; a group's K^-1 is formed whole (GPX_FULL), each row's vectors follow (loo_weights_vectors), the group's Y Y^T
+// run in lock-step, and the row's value comes out of its gradient pass: `log_lh` and `dloglh` then hold L_LOO and its gradient.
 static int fit_batch_impl(gpx_gp_t *g, const double *thetas, int64_t B, double *log_lh, double *dloglh, double *logdet_yta,
-                          int *info)
+                          int *info, int loo = 0)
 {
     GPX_ARG(g->have_data, "set_data must be called before fit_batch");
     GPX_ARG(B >= 0 && (B == 0 || (thetas && log_lh)), "bad arguments");
@@ -993,7 +991,8 @@ static int fit_batch_impl(gpx_gp_t *g, const double *thetas, int64_t B, double *
         const size_t per_row = 2 * nl + (group_ok ? trsv_ops_bytes(g->dtype, g->n) : 0);
         int G = group_ok ? (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(8, B), (int64_t)((double)(freeg + g->gw.bytes) / 6.0 / (double)per_row))) : 1;
         if (g->gw_cap >= G && g->gw.p) G = g->gw_cap;
-        const size_t gneed = (size_t)G * per_row + (dloglh_partial_doubles(g->kernel, g->d) + 8) * sizeof(double) + 256;
+        const size_t gneed = (size_t)G * per_row + (dloglh_partial_doubles(g->kernel, g->d) + 8) * sizeof(double) + 256 +
+                             (loo ? (size_t)G * loo_vec_bytes(g->dtype, g->n) + 256 : 0);   // + a group's leave-one-out vectors
         GPX_TRY(g->gw.reserve(gneed, g->st));
         g->gw_cap = G;
     }
@@ -1082,6 +1081,7 @@ static int fit_batch_impl(gpx_gp_t *g, const double *thetas, int64_t B, double *
             const double logdet = hs[2 * i], yta = hs[2 * i + 1];
             double v;
             if (!valid[i]) v = NAN;                               // the reference raises ValueError for this row
+            else if (loo) v = hi[i] != 0 ? -INFINITY : NAN;       // (a row with a factor: its value comes with its gradient, below)
             else if (hi[i] != 0 || !(logdet >= GPX_MIN_LOG)) v = -INFINITY;     // gp/gp.py:362-365, gp_c.pyx:22-29
             else v = -0.5 * yta - 0.5 * logdet - 0.5 * (double)n * log(2 * M_PI);
             log_lh[b0 + i] = v;
@@ -1098,6 +1098,9 @@ static int fit_batch_impl(gpx_gp_t *g, const double *thetas, int64_t B, double *
             const size_t obytes = G > 1 ? trsv_ops_bytes(g->dtype, n) : 0;
             char *Os = Ws + (size_t)G * nl;
             double *part = (double *)(((uintptr_t)(Os + (size_t)G * obytes) + 255) / 256 * 256);
+            const size_t lvb = loo_vec_bytes(g->dtype, n);
+            char *Vs = (char *)(((uintptr_t)(part + dloglh_partial_doubles(g->kernel, g->d) + 8) + 255) / 256 * 256);   // loo: a group's vectors
+            const int tri = loo ? GPX_FULL : GPX_LOWER;
             for (int i0 = 0; i0 < cnt; i0 += G) {
                 const int gc = std::min(G, cnt - i0);
                 bool any = false;
@@ -1106,8 +1109,18 @@ static int fit_batch_impl(gpx_gp_t *g, const double *thetas, int64_t B, double *
                 if (lock_step) {
                     // the group's K^-1 in lock-step: X = L^-T (operators of every row built first), W = X X^T lower.  Rows that are
                     // invalid or not positive definite take part (their factor is garbage; nothing of theirs is read back).
-                    GPX_TRY(inv_from_factor(g->dtype, (const char *)Ab.p + (size_t)i0 * per, n, lda, Xs, Ws, GPX_LOWER, st, nullptr, gc,
+                    GPX_TRY(inv_from_factor(g->dtype, (const char *)Ab.p + (size_t)i0 * per, n, lda, Xs, Ws, tri, st, nullptr, gc,
                                             (int64_t)(per / es), Os));
+                    if (loo) {
+                        // every row's k, value, r and Y from its own K^-1, then the group's Pm = Y Y^T in lock-step
+                        for (int i = i0; i < i0 + gc; ++i) {
+                            if (!valid[i] || hi[i] != 0) continue;
+                            GPX_TRY(loo_weights_vectors(g->dtype, (char *)Ab.p + (size_t)i * per, n, lda, g->y, (char *)al.p + (size_t)i * vec,
+                                                        Xs + (size_t)(i - i0) * nl, Ws + (size_t)(i - i0) * nl,
+                                                        loo_vecs_at(Vs + (size_t)(i - i0) * lvb, g->dtype, n), nullptr, nullptr, st));
+                        }
+                        GPX_TRY(loo_weights_product(g->dtype, n, lda, Xs, Ws, gc, st));
+                    }
                 }
                 for (int i = i0; i < i0 + gc; ++i) {
                     double *o = dloglh + (b0 + i) * (np + 1);
@@ -1115,7 +1128,16 @@ static int fit_batch_impl(gpx_gp_t *g, const double *thetas, int64_t B, double *
                     const double *th = thetas + (b0 + i) * (np + 1);
                     const void *alpha_i = (char *)al.p + (size_t)i * vec;
                     const void *pts_i = ard ? (const void *)((char *)xb.p + (size_t)i * xsz) : (const void *)g->x;
-                    if (lock_step) {
+                    if (loo) {
+                        const LooVecs lv = loo_vecs_at(Vs + (size_t)(lock_step ? i - i0 : 0) * lvb, g->dtype, n);
+                        if (!lock_step) {
+                            g->bops.invalidate();
+                            GPX_TRY(loo_weights_from_factor(g->dtype, (char *)Ab.p + (size_t)i * per, n, lda, g->y, alpha_i, Xs, Ws, lv, nullptr,
+                                                            &g->bops, st));
+                        }
+                        GPX_TRY(loo_grad_reduce(g, pts_i, alpha_i, th, th[np], lv, Ws + (size_t)(lock_step ? i - i0 : 0) * nl, lda, part,
+                                                &log_lh[b0 + i], o));
+                    } else if (lock_step) {
                         GPX_TRY(grad_reduce(g, pts_i, alpha_i, th, th[np], Ws + (size_t)(i - i0) * nl, lda, part, o));
                     } else {
                         g->bops.invalidate();
@@ -1147,6 +1169,17 @@ int gpx_gp_fit_batch_grad(gpx_gp_t *g, const double *thetas, int64_t B, double *
     GPX_ARG(B == 0 || dloglh, "dloglh is NULL");
     GP_NEED_FINITE_Y(g);
     return fit_batch_impl(g, thetas, B, log_lh, dloglh, logdet_yta, info);
+}
+
+// The same table under the leave-one-out criterion: loo_log_lh (B) and dloo (B, n_params + 1) per row, from the row's factor
+// where the lock-step pass left it (fit_batch_impl, loo).  An invalid row: NaN and NaN; a row that is not positive
+// definite: -inf and NaN; info as gpx_gp_fit_batch_grad sets it.
+int gpx_gp_fit_batch_loo(gpx_gp_t *g, const double *thetas, int64_t B, double *loo_log_lh, double *dloo, int *info)
+{
+    GP_ENTER(g);
+    GPX_ARG(B == 0 || dloo, "dloo is NULL");
+    GP_NEED_FINITE_Y(g);
+    return fit_batch_impl(g, thetas, B, loo_log_lh, dloo, nullptr, info, 1);
 }
 
 int gpx_gp_last_timing(gpx_gp_t *g, float *ms5)

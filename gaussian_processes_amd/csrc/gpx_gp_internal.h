@@ -76,7 +76,17 @@ static inline GpView gp_view(const gpx_gp *g)
 }
 // ARD: xs <- x / w and iso, enqueued on the handle's stream, once data and parameters are both there (no-op otherwise)
 int gp_rescale(gpx_gp *g);
+// The reduction half of the leave-one-out gradient (gpx_loograd.hip): (alpha, v.r, Pm) of one system in HBM -> out
+// (n_params + 1, order (kernel params..., s)) and the criterion's value (may be null).  pts, params, s_noise, part: as
+// grad_reduce's in gpx_gp.hip.  Synchronises g->st.
+int loo_grad_reduce(gpx_gp *g, const void *pts, const void *alpha, const double *params, double s_noise, const LooVecs &v,
+                    const void *Pm, int64_t ldp, double *part, double *value, double *out);
 }
+
+static const char *const NONFINITE_MSG = "array must not contain infs or NaNs";      // scipy's text (gp/gp.py:294, 332-334)
+
+#define GP_NEED_FINITE_Y(g)                                                    \
+    do { if (!(g)->y_finite) { gpx::set_error("%s (y)", NONFINITE_MSG); return GPX_ERR_ARG; } } while (0)
 
 // every gpx_gp_* entry: the handle's device becomes current for the duration of the call, and the handle's stream takes
 // its turn among the streams this host thread drives (StreamTurn, gpx_mem.h); with GPX_ROCTX=1 the call is a roctx range

@@ -609,6 +609,269 @@ int dloglh_reduce_ard(int dtype, const void *xs, int64_t n, int d, const double 
     return GPX_OK;
 }
 
+// ---------------------------------------------------------------------------
+// The same two passes for the leave-one-out criterion (RW06 eq. 5.13 rearranged; gpx_loograd.hip has the derivation):
+//   P[p]    = sum_{j,k} G_jk dK_p(x_j, x_k),   G = (r alpha^T + alpha r^T) / 2 - Pm,   Pm = K^-1 diag(c) K^-1
+//   P[last] = trace(Pm)
+// Two vectors where the marginal-likelihood pass has one, and Pm's lower triangle where it reads W: the coefficient of an
+// entry is wt ((r_j alpha_k + alpha_j r_k) / 2 - Pm_jk).  Everything else -- the tile walk, the staging of the points, the
+// fixed-order sums, the per-workgroup partials the host adds in index order -- is the text above, in kernels of their own:
+// the marginal-likelihood kernels are not touched, their results cannot move.
+// ---------------------------------------------------------------------------
+template <typename T>
+__global__ __launch_bounds__(256) void dloo_reduce_kernel(const T *__restrict__ x, int64_t n, int d,
+                                                          const T *__restrict__ alpha, const T *__restrict__ rv,
+                                                          const T *__restrict__ Pm, int64_t ldp,
+                                                          GradParams gp, int64_t ntiles_r,
+                                                          double *__restrict__ partial)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    T *s1 = reinterpret_cast<T *>(smem_raw);          // [GR_T][d]   rows
+    T *s2 = s1 + (size_t)GR_T * d;                    // [d][GR_T]   columns, transposed
+    T *sa1 = s2 + (size_t)GR_T * d;                   // alpha rows
+    T *sa2 = sa1 + GR_T;                              // alpha cols
+    T *sr1 = sa2 + GR_T;                              // r rows
+    T *sr2 = sr1 + GR_T;                              // r cols
+    __shared__ double red[4][4];
+    const int tid = threadIdx.x, col = tid & 63, rg = tid >> 6;
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};             // up to 3 kernel params + trace
+    const int64_t total = ntiles_r * (ntiles_r + 1) / 2;
+    for (int64_t t = blockIdx.x; t < total; t += gridDim.x) {
+        int64_t tr, tc;
+        tri_tile(t, &tr, &tc);
+        const int64_t r0 = tr * GR_T, c0 = tc * GR_T;
+        __syncthreads();
+        for (int idx = tid; idx < GR_T * d; idx += 256) {
+            const int r = idx / d, k = idx - r * d;
+            s1[idx] = (r0 + r < n) ? x[(r0 + r) * d + k] : (T)0;
+            s2[(size_t)k * GR_T + r] = (c0 + r < n) ? x[(c0 + r) * d + k] : (T)0;
+        }
+        if (tid < GR_T) {
+            sa1[tid] = (r0 + tid < n) ? alpha[r0 + tid] : (T)0;
+            sa2[tid] = (c0 + tid < n) ? alpha[c0 + tid] : (T)0;
+            sr1[tid] = (r0 + tid < n) ? rv[r0 + tid] : (T)0;
+            sr2[tid] = (c0 + tid < n) ? rv[c0 + tid] : (T)0;
+        }
+        __syncthreads();
+        const int64_t gc = c0 + col;
+        const double ak = (double)sa2[col], rk = (double)sr2[col];
+        for (int i = 0; i < 16; ++i) {
+            const int r = rg + 4 * i;
+            const int64_t gr = r0 + r;
+            if (gr >= n || gc >= n || gc > gr) continue;
+            const double wt = (gc == gr) ? 1.0 : 2.0;
+            const double pjk = (double)Pm[gr * ldp + gc];
+            const double coef = wt * (0.5 * ((double)sr1[r] * ak + (double)sa1[r] * rk) - pjk);
+            if (gc == gr) acc[3] += pjk;
+            if (gp.kernel == GPX_KERNEL_GAUSSIAN) {
+                T d2 = (T)0;
+                for (int k = 0; k < d; ++k) {
+                    const T tt = s1[r * d + k] - s2[(size_t)k * GR_T + col];
+                    d2 = fma(tt, tt, d2);
+                }
+                const double e = gp.c1 * (double)d2;
+                if (!(e < GPX_MIN_LOG)) {
+                    const double ex = exp(e);
+                    acc[0] += coef * (gp.c2h * ex);
+                    acc[1] += coef * (ex * (gp.c3w * (double)d2 - gp.c2w));
+                }
+            } else {
+                const T dd = s1[r] - s2[col];          // d == 1
+                acc[0] += coef * (double)periodic_entry<T>(GPX_DK_DH, dd, (T)gp.h, (T)gp.w, (T)gp.p);
+                acc[1] += coef * (double)periodic_entry<T>(GPX_DK_DW, dd, (T)gp.h, (T)gp.w, (T)gp.p);
+                acc[2] += coef * (double)periodic_entry<T>(GPX_DK_DP, dd, (T)gp.h, (T)gp.w, (T)gp.p);
+            }
+        }
+    }
+    block_sum_fixed(acc, red, tid);
+    __syncthreads();
+    if (tid < 4) partial[(int64_t)blockIdx.x * 4 + tid] = block_sum_final(red, tid);
+}
+
+// the partial sums of `width` quantities per workgroup, added on the host in workgroup order
+static int sum_partials(const double *partial_dev, int width, double *out, hipStream_t st)
+{
+    std::vector<double> host((size_t)GR_BLOCKS * width);
+    GPX_HIP(hipMemcpyAsync(host.data(), partial_dev, host.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    GPX_HIP(hipStreamSynchronize(st));
+    for (int q = 0; q < width; ++q) {
+        double v = 0.0;
+        for (int b = 0; b < GR_BLOCKS; ++b) v += host[(size_t)b * width + q];
+        out[q] = v;
+    }
+    return GPX_OK;
+}
+
+// partial: GR_BLOCKS * 4 doubles of DEVICE memory; out4: host, [P0, P1, P2, trace Pm]
+int dloo_reduce(int dtype, int kernel, const void *x, int64_t n, int d, const double *params, const void *alpha, const void *r,
+                const void *Pm, int64_t ldp, double *partial_dev, double *out4, hipStream_t st)
+{
+    GradParams gpar;
+    memset(&gpar, 0, sizeof(gpar));
+    gpar.kernel = kernel;
+    if (kernel == GPX_KERNEL_GAUSSIAN) {
+        const double h = params[0], w = params[1], S = sqrt(2.0 / M_PI);
+        gpar.nkp = 2;
+        gpar.c1 = -0.5 / (w * w);
+        gpar.c2h = S * h / w;                          // gaussian_c.pyx:61
+        gpar.c2w = 0.5 * S * h * h / (w * w);          // :82
+        gpar.c3w = 0.5 * S * h * h / pow(w, 4);        // :83
+    } else {
+        if (d != 1) { set_error("periodic gradient needs d == 1"); return GPX_ERR_UNSUPPORTED; }
+        gpar.nkp = 3; gpar.h = params[0]; gpar.w = params[1]; gpar.p = params[2];
+    }
+    const size_t es = esize(dtype);
+    const size_t smem = ((size_t)2 * GR_T * d + 4 * GR_T) * es;
+    const int64_t ntr = cdiv(n, GR_T);
+    const int blocks = (int)std::min<int64_t>(GR_BLOCKS, ntr * (ntr + 1) / 2);
+    GPX_HIP(hipMemsetAsync(partial_dev, 0, (size_t)GR_BLOCKS * 4 * sizeof(double), st));
+    {
+    ProfScope prof(PC_REDUCE, 0.5 * (double)n * (double)(n + 1) * (double)es, st);      // the lower triangle of Pm, read once
+    if (dtype == GPX_F64) {
+        if (smem > 48 * 1024) GPX_TRY(set_max_lds((const void *)dloo_reduce_kernel<double>, LDS_TILE_MAX));
+        hipLaunchKernelGGL((dloo_reduce_kernel<double>), dim3(blocks), dim3(256), smem, st, (const double *)x, n, d,
+                           (const double *)alpha, (const double *)r, (const double *)Pm, ldp, gpar, ntr, partial_dev);
+    } else {
+        if (smem > 48 * 1024) GPX_TRY(set_max_lds((const void *)dloo_reduce_kernel<float>, LDS_TILE_MAX));
+        hipLaunchKernelGGL((dloo_reduce_kernel<float>), dim3(blocks), dim3(256), smem, st, (const float *)x, n, d,
+                           (const float *)alpha, (const float *)r, (const float *)Pm, ldp, gpar, ntr, partial_dev);
+    }
+    GPX_LAUNCH_CHECK();
+    }
+    return sum_partials(partial_dev, 4, out4, st);
+}
+
+// The ARD pass: c_ab = wt ((r_a alpha_b + alpha_a r_b) / 2 - Pm_ab) k_ab;  S_0 = sum c_ab,  S_k = sum c_ab t_k^2,  tr Pm.
+// DMAX accumulators in registers as in dloglh_reduce_ard_kernel, here in one array with S_0 and the trace so that the
+// block sum is the shared helper's; two more staged vectors.
+template <typename T, int DMAX>
+__global__ __launch_bounds__(256) void dloo_reduce_ard_kernel(const T *__restrict__ xs, int64_t n, int d,
+                                                              const T *__restrict__ alpha, const T *__restrict__ rv,
+                                                              const T *__restrict__ Pm, int64_t ldp, double c2,
+                                                              int64_t ntiles_r, double *__restrict__ partial)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    T *s1 = reinterpret_cast<T *>(smem_raw);          // [GR_T][DMAX]   rows
+    T *s2 = s1 + (size_t)GR_T * DMAX;                 // [DMAX][GR_T]   columns, transposed
+    T *sa1 = s2 + (size_t)GR_T * DMAX;                // alpha rows
+    T *sa2 = sa1 + GR_T;                              // alpha cols
+    T *sr1 = sa2 + GR_T;                              // r rows
+    T *sr2 = sr1 + GR_T;                              // r cols
+    __shared__ double red[4][DMAX + 2];
+    const int tid = threadIdx.x, col = tid & 63;
+    const int rg = __builtin_amdgcn_readfirstlane(tid >> 6);      // (the wave's index: uniform, so the row reads broadcast)
+    double acc[DMAX + 2];                             // slot 0: S_0, 1 .. DMAX: S_k, DMAX + 1: tr Pm
+#pragma unroll
+    for (int k = 0; k < DMAX + 2; ++k) acc[k] = 0.0;
+    const int64_t total = ntiles_r * (ntiles_r + 1) / 2;
+    for (int64_t t = blockIdx.x; t < total; t += gridDim.x) {
+        int64_t tr, tc;
+        tri_tile(t, &tr, &tc);
+        const int64_t r0 = tr * GR_T, c0 = tc * GR_T;
+        __syncthreads();
+        for (int idx = tid; idx < GR_T * DMAX; idx += 256) {
+            const int r = idx / DMAX, k = idx - r * DMAX;
+            s1[idx] = (k < d && r0 + r < n) ? xs[(r0 + r) * d + k] : (T)0;
+            s2[(size_t)k * GR_T + r] = (k < d && c0 + r < n) ? xs[(c0 + r) * d + k] : (T)0;
+        }
+        if (tid < GR_T) {
+            sa1[tid] = (r0 + tid < n) ? alpha[r0 + tid] : (T)0;
+            sa2[tid] = (c0 + tid < n) ? alpha[c0 + tid] : (T)0;
+            sr1[tid] = (r0 + tid < n) ? rv[r0 + tid] : (T)0;
+            sr2[tid] = (c0 + tid < n) ? rv[c0 + tid] : (T)0;
+        }
+        __syncthreads();
+        const int64_t gc = c0 + col;
+        // the squared distances of this thread's 16 entries, accumulated as kmat_kernel accumulates them
+        T r2[16];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) r2[i] = (T)0;
+#pragma unroll 2
+        for (int k = 0; k < d; ++k) {
+            const T b = s2[(size_t)k * GR_T + col];
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                const T tt = s1[(rg + 4 * i) * DMAX + k] - b;
+                r2[i] = fma(tt, tt, r2[i]);
+            }
+        }
+        // the weights c_ab (0 for an entry outside the matrix or above the diagonal: Pm is only read inside the lower triangle)
+        double c[16];
+        const double ak = (double)sa2[col], rk = (double)sr2[col];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const int r = rg + 4 * i;
+            const int64_t gr = r0 + r;
+            double ci = 0.0;
+            if (gr < n && gc <= gr) {
+                const double pjk = (double)Pm[gr * ldp + gc];
+                const double coef = ((gc == gr) ? 1.0 : 2.0) * (0.5 * ((double)sr1[r] * ak + (double)sa1[r] * rk) - pjk);
+                if (gc == gr) acc[DMAX + 1] += pjk;
+                const double e = -0.5 * (double)r2[i];
+                if (!(e < GPX_MIN_LOG)) ci = coef * (c2 * exp(e));
+            }
+            c[i] = ci;
+            acc[0] += ci;
+        }
+#pragma unroll
+        for (int k = 0; k < DMAX; ++k) {
+            if (k < d) {
+                const T b = s2[(size_t)k * GR_T + col];
+                double a = 0.0;
+#pragma unroll
+                for (int i = 0; i < 16; ++i) {
+                    const double tt = (double)(s1[(rg + 4 * i) * DMAX + k] - b);
+                    a = fma(c[i], tt * tt, a);
+                }
+                acc[1 + k] += a;
+            }
+        }
+    }
+    block_sum_fixed(acc, red, tid);
+    __syncthreads();
+    if (tid < d + 2) partial[(int64_t)blockIdx.x * (d + 2) + tid] = block_sum_final(red, tid <= d ? tid : DMAX + 1);
+}
+
+template <typename T, int DMAX>
+static int launch_loo_reduce_ard(const void *xs, int64_t n, int d, const void *alpha, const void *r, const void *Pm, int64_t ldp,
+                                 double c2, int64_t ntr, int blocks, double *partial_dev, hipStream_t st)
+{
+    const size_t smem = ((size_t)2 * GR_T * DMAX + 4 * GR_T) * sizeof(T);
+    if (smem > 48 * 1024) GPX_TRY(set_max_lds((const void *)dloo_reduce_ard_kernel<T, DMAX>, LDS_TILE_MAX));
+    hipLaunchKernelGGL((dloo_reduce_ard_kernel<T, DMAX>), dim3(blocks), dim3(256), smem, st, (const T *)xs, n, d, (const T *)alpha,
+                       (const T *)r, (const T *)Pm, ldp, c2, ntr, partial_dev);
+    GPX_LAUNCH_CHECK();
+    return GPX_OK;
+}
+
+template <typename T>
+static int launch_loo_reduce_ard_d(const void *xs, int64_t n, int d, const void *alpha, const void *r, const void *Pm, int64_t ldp,
+                                   double c2, int64_t ntr, int blocks, double *partial_dev, hipStream_t st)
+{
+    if (d <= 8) return launch_loo_reduce_ard<T, 8>(xs, n, d, alpha, r, Pm, ldp, c2, ntr, blocks, partial_dev, st);
+    if (d <= 16) return launch_loo_reduce_ard<T, 16>(xs, n, d, alpha, r, Pm, ldp, c2, ntr, blocks, partial_dev, st);
+    if (d <= 32) return launch_loo_reduce_ard<T, 32>(xs, n, d, alpha, r, Pm, ldp, c2, ntr, blocks, partial_dev, st);
+    return launch_loo_reduce_ard<T, 64>(xs, n, d, alpha, r, Pm, ldp, c2, ntr, blocks, partial_dev, st);
+}
+
+// xs: the SCALED points; iso: (h / sqrt(wbar), 1); partial_dev: dloglh_partial_doubles() of DEVICE memory;
+// out: host, d + 2 values [S_0, S_1 .. S_d, trace Pm]
+int dloo_reduce_ard(int dtype, const void *xs, int64_t n, int d, const double *iso, const void *alpha, const void *r, const void *Pm,
+                    int64_t ldp, double *partial_dev, double *out, hipStream_t st)
+{
+    if (d < 1 || d > GPX_ARD_MAX_D) { set_error("ARD gradient needs 1 <= d <= %d (got %d)", GPX_ARD_MAX_D, d); return GPX_ERR_ARG; }
+    const double c2 = 0.5 * sqrt(2.0 / M_PI) * iso[0] * iso[0] / iso[1];          // make_kparams, GPX_K
+    const int64_t ntr = cdiv(n, GR_T);
+    const int blocks = (int)std::min<int64_t>(GR_BLOCKS, ntr * (ntr + 1) / 2);
+    GPX_HIP(hipMemsetAsync(partial_dev, 0, (size_t)GR_BLOCKS * (d + 2) * sizeof(double), st));
+    {
+        ProfScope prof(PC_REDUCE, 0.5 * (double)n * (double)(n + 1) * (double)esize(dtype), st);
+        if (dtype == GPX_F64) GPX_TRY((launch_loo_reduce_ard_d<double>(xs, n, d, alpha, r, Pm, ldp, c2, ntr, blocks, partial_dev, st)));
+        else GPX_TRY((launch_loo_reduce_ard_d<float>(xs, n, d, alpha, r, Pm, ldp, c2, ntr, blocks, partial_dev, st)));
+    }
+    return sum_partials(partial_dev, d + 2, out, st);
+}
+
 }  // namespace gpx
 
 using namespace gpx;

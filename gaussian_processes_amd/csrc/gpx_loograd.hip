@@ -1,0 +1,222 @@
+// gpx_loograd.hip -- the gradient of the leave-one-out criterion (gpx_gp_loo_grad, gpx_gp_loo_grad_weights).
+//
+// With W = K^-1, alpha = W y and k_i = W_ii the criterion is  L = sum_i ( log k_i / 2 - alpha_i^2 / (2 k_i) - log(2 pi) / 2 )
+// (RW06 eq. 5.10 - 5.12; gpx_gp_loo sums it).  From dW = -W dK W:  dk_i = -(W dK W)_ii,  dalpha = -W dK alpha,  so
+//   dL = sum_i [ -c_i (W dK W)_ii + (alpha_i / k_i) (W dK alpha)_i ],      c_i = (1 + alpha_i^2 / k_i) / (2 k_i)  > 0
+//      = sum_ab dK_ab G_ab,      G = (r alpha^T + alpha r^T) / 2 - Pm,     r = W (alpha / k),    Pm = W diag(c) W
+// which is RW06 eq. 5.13 with the products regrouped: eq. 5.13 as printed takes one n^3 product W dK_j per parameter, this
+// form ONE for all of them -- Pm = Y Y^T with Y = W diag(sqrt(c)), a symmetric product, lower triangle only -- and then a
+// single fused pass of dloglh_reduce's shape over (alpha, r, Pm) against the kernel derivatives evaluated on the fly.
+// Noise: dK/ds = 2 s I, so dL/ds = 2 s tr G = 2 s (r . alpha - tr Pm).
+//
+// Memory: the two n x ldl blocks the marginal-likelihood gradient uses and no third.  X = L^-T is dead once k has been read
+// from its rows, so Y is written over it; W is dead once Y exists, so Pm is written over W.  No explicit G on this route
+// (gpx_gp_loo_grad_weights forms one, in float64, for the caller who asked for it).
+// k is read from the rows of X -- k_i = |row i of L^-T|^2, float64 sums, the very kernel gpx_gp_loo's sweep ends with --
+// rather than from the diagonal of W, so the value that comes out of this call is gpx_gp_loo's bit for bit, in fp32 too.
+#include "gpx_common.h"
+#include <cmath>
+
+#include "gpx_gp_internal.h"
+
+namespace gpx {
+
+// u = alpha / k and sqrt(c), in the system's dtype; one thread per point.  k > 0 for every factor that exists.
+template <typename T>
+__global__ void loo_weights_kernel(const double *__restrict__ kii, const T *__restrict__ alpha, int64_t n, T *__restrict__ u,
+                                   T *__restrict__ sq)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const double k = kii[i], a = (double)alpha[i];
+    const double c = 0.5 * (1.0 + a * a / k) / k;
+    u[i] = (T)(a / k);
+    sq[i] = (T)sqrt(c);
+}
+
+// Y[r, c] = W[r, c] sq[c]: eye_kernel's grid (column blocks of 256, rows up to 32768 and a row loop beyond); columns < n only
+template <typename T>
+__global__ void col_scale_kernel(const T *__restrict__ W, const T *__restrict__ sq, T *__restrict__ Y, int64_t n, int64_t ld)
+{
+    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= n) return;
+    const T s = sq[c];
+    for (int64_t r = blockIdx.y; r < n; r += gridDim.y) Y[r * ld + c] = W[r * ld + c] * s;
+}
+
+// G (n x n float64, dense) from alpha, r and the lower triangle of Pm: entry (a, b) and its mirror from the same
+// expression in the same order of operands, so G is symmetric bit for bit
+template <typename T>
+__global__ void loo_g_kernel(const T *__restrict__ alpha, const T *__restrict__ rv, const T *__restrict__ Pm, int64_t ldp,
+                             double *__restrict__ G, int64_t n)
+{
+    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= n) return;
+    const double ac = (double)alpha[c], rc = (double)rv[c];
+    for (int64_t r = blockIdx.y; r < n; r += gridDim.y) {
+        const int64_t hi = r > c ? r : c, lo = r > c ? c : r;
+        const double ah = r > c ? (double)alpha[r] : ac, rh = r > c ? (double)rv[r] : rc;
+        const double al = r > c ? ac : (double)alpha[r], rl = r > c ? rc : (double)rv[r];
+        G[r * n + c] = 0.5 * (rh * al + ah * rl) - (double)Pm[hi * ldp + lo];
+    }
+}
+
+static inline size_t pad256(size_t b) { return (b + 255) / 256 * 256; }
+
+size_t loo_vec_bytes(int dtype, int64_t n) { return 2 * pad256((size_t)n * 8) + 256 + 4 * pad256((size_t)n * esize(dtype)); }
+
+LooVecs loo_vecs_at(void *block, int dtype, int64_t n)
+{
+    char *p = (char *)block;
+    const size_t d8 = pad256((size_t)n * 8), dt = pad256((size_t)n * esize(dtype));
+    LooVecs v;
+    v.kii = (double *)p; p += d8;
+    v.logp = (double *)p; p += d8;
+    v.sums = (double *)p; p += 256;
+    v.u = p; p += dt;
+    v.sq = p; p += dt;
+    v.t = p; p += dt;
+    v.r = p;
+    return v;
+}
+
+int loo_weights_vectors(int dtype, const void *L, int64_t n, int64_t ldl, const void *y, const void *alpha, void *X, const void *W,
+                        const LooVecs &v, const double *kii_have, TrsvOps *ops, hipStream_t st)
+{
+    // k and the per-point terms; their sum in sum_f64's fixed order, as gpx_gp_loo takes it
+    const double *kii = kii_have ? kii_have : v.kii;
+    if (kii_have) GPX_TRY(loo_points(dtype, kii, y, alpha, n, nullptr, nullptr, v.logp, st));
+    else GPX_TRY(loo_rows(dtype, X, n, n, ldl, 0, y, alpha, v.kii, nullptr, nullptr, v.logp, st));
+    GPX_TRY(sum_f64(v.logp, n, v.sums, st));
+    const dim3 g1((unsigned)cdiv(n, 256)), block(256);
+    if (dtype == GPX_F64) hipLaunchKernelGGL((loo_weights_kernel<double>), g1, block, 0, st, kii, (const double *)alpha, n, (double *)v.u, (double *)v.sq);
+    else hipLaunchKernelGGL((loo_weights_kernel<float>), g1, block, 0, st, kii, (const float *)alpha, n, (float *)v.u, (float *)v.sq);
+    GPX_LAUNCH_CHECK();
+    // r = W (alpha / k) = L^-T (L^-1 u): two sweeps with the factor (its block operators where it has them), not a product with W
+    GPX_TRY(trsv_lower(dtype, L, n, ldl, v.u, v.t, 0, st, nullptr, ops));
+    GPX_TRY(trsv_lower(dtype, L, n, ldl, v.t, v.r, 1, st, nullptr, ops));
+    GPX_TRY(dot(dtype, v.r, alpha, n, v.sums + 1, st));
+    // Y = W diag(sqrt(c)) over X: X's rows have been read (k), nothing else needs L^-T
+    const dim3 g2((unsigned)cdiv(n, 256), (unsigned)std::min<int64_t>(n, 32768));
+    if (dtype == GPX_F64) hipLaunchKernelGGL((col_scale_kernel<double>), g2, block, 0, st, (const double *)W, (const double *)v.sq, (double *)X, n, ldl);
+    else hipLaunchKernelGGL((col_scale_kernel<float>), g2, block, 0, st, (const float *)W, (const float *)v.sq, (float *)X, n, ldl);
+    GPX_LAUNCH_CHECK();
+    return GPX_OK;
+}
+
+// Pm = Y Y^T, lower triangle, over W (dead: k and Y exist).  gemm_nt on its triangular route: the tiles above the diagonal
+// are not computed; cleared first because the route for an n that is no multiple of the k-step accumulates into C.
+int loo_weights_product(int dtype, int64_t n, int64_t ldl, const void *Y, void *Pm, int count, hipStream_t st)
+{
+    const int64_t sX = n * ldl;
+    GPX_HIP(hipMemsetAsync(Pm, 0, (size_t)count * sX * esize(dtype), st));
+    Batch bw; bw.count = count; bw.sA = bw.sB = bw.sC = sX;
+    return gemm_nt(dtype, n, n, n, Y, ldl, Y, ldl, Pm, ldl, 1.0, GPX_LOWER, 0, 0, st, 0, 0, count > 1 ? &bw : nullptr);
+}
+
+int loo_weights_from_factor(int dtype, const void *L, int64_t n, int64_t ldl, const void *y, const void *alpha, void *X, void *W,
+                            const LooVecs &v, const double *kii_have, TrsvOps *ops, hipStream_t st)
+{
+    GPX_TRY(inv_from_factor(dtype, L, n, ldl, X, W, GPX_FULL, st, ops));
+    GPX_TRY(loo_weights_vectors(dtype, L, n, ldl, y, alpha, X, W, v, kii_have, ops, st));
+    return loo_weights_product(dtype, n, ldl, X, W, 1, st);
+}
+
+// The reduction half, grad_reduce's counterpart: (alpha, r, Pm) are in HBM; one fused pass, then the host turns the sums
+// into (d/dh, d/dw ..., d/ds) -- no factor 1/2 here: dL = sum dK_ab G_ab.  ARD: dk/dh = 2 k / h, dk/dw_k = k (t_k^2 - 1 / d) / w_k
+// on the scaled points, grad_reduce's bookkeeping of S_0 .. S_d.  value (may be null): the criterion.  Synchronises g->st.
+int loo_grad_reduce(gpx_gp *g, const void *pts, const void *alpha, const double *params, double s_noise, const LooVecs &v,
+                    const void *Pm, int64_t ldp, double *part, double *value, double *out)
+{
+    const int64_t n = g->n;
+    double S[GPX_ARD_MAX_D + 2], sums[2] = {0.0, 0.0};
+    const bool ard = g->kernel == GPX_KERNEL_GAUSSIAN_ARD;
+    if (ard) {
+        double iso[2];
+        ard_iso(params, g->d, iso);
+        GPX_TRY(dloo_reduce_ard(g->dtype, pts, n, g->d, iso, alpha, v.r, Pm, ldp, part, S, g->st));
+    } else {
+        GPX_TRY(dloo_reduce(g->dtype, g->kernel, pts, n, g->d, params, alpha, v.r, Pm, ldp, part, S, g->st));
+    }
+    GPX_HIP(hipMemcpyAsync(sums, v.sums, sizeof(sums), hipMemcpyDeviceToHost, g->st));
+    GPX_HIP(hipStreamSynchronize(g->st));
+    if (ard) {
+        const int d = g->d;
+        out[0] = 2.0 * S[0] / params[0];
+        for (int k = 0; k < d; ++k) out[1 + k] = S[1 + k] / params[1 + k] - S[0] / ((double)d * params[1 + k]);
+        out[d + 1] = 2.0 * s_noise * (sums[1] - S[d + 1]);
+    } else {
+        for (int i = 0; i < g->nparams; ++i) out[i] = S[i];
+        out[g->nparams] = 2.0 * s_noise * (sums[1] - S[3]);    // dK/ds = 2 s I
+    }
+    if (value) *value = sums[0];
+    return GPX_OK;
+}
+
+// the handle's own factor: X, W, the vectors and the partial sums in one call's DevBufs; diag(K^-1) stays in the handle
+struct LooWork { DevBuf X, W, vec, part; LooVecs v; };
+static int loo_weights_of_handle(gpx_gp *g, LooWork *w)
+{
+    const size_t es = esize(g->dtype);
+    const int64_t n = g->n, lda = g->lda;
+    GPX_TRY(w->X.alloc((size_t)n * lda * es));
+    GPX_TRY(w->W.alloc((size_t)n * lda * es));
+    GPX_TRY(w->vec.alloc(loo_vec_bytes(g->dtype, n)));
+    w->v = loo_vecs_at(w->vec.p, g->dtype, n);
+    if (!g->kii) GPX_TRY(dev_alloc((void **)&g->kii, (size_t)n * sizeof(double), "hipMalloc kii"));
+    if (!g->have_kii) w->v.kii = g->kii;                   // written here, as the first gpx_gp_loo would have
+    GPX_TRY(loo_weights_from_factor(g->dtype, g->A, n, lda, g->y, g->alpha, w->X.p, w->W.p, w->v, g->have_kii ? g->kii : nullptr,
+                                    &g->ops, g->st));
+    g->have_kii = true;
+    return GPX_OK;
+}
+
+}  // namespace gpx
+
+using namespace gpx;
+
+extern "C" {
+
+int gpx_gp_loo_grad(gpx_gp_t *g, double *loo_log_lh, double *grad)
+{
+    GP_ENTER(g);
+    GPX_ARG(g->fitted && loo_log_lh && grad, "bad arguments");
+    GP_NEED_FINITE_Y(g);
+    if (g->kernel == GPX_KERNEL_PERIODIC && g->d != 1) { set_error("periodic gradient needs d == 1"); return GPX_ERR_UNSUPPORTED; }
+    GPX_ARG(g->have_data && g->have_params, "the handle was fitted from a matrix: no kernel to differentiate (gpx_gp_loo_grad_weights)");
+    GpScal sc;
+    GPX_TRY(gp_read_scal(g, &sc));
+    if (sc.info != 0) {                                    // no factor: the criterion is -inf, its gradient NaN (as gpx_gp_dloglh_dtheta)
+        *loo_log_lh = -INFINITY;
+        for (int i = 0; i <= g->nparams; ++i) grad[i] = NAN;
+        return GPX_OK;
+    }
+    LooWork w;
+    GPX_TRY(w.part.alloc(dloglh_partial_doubles(g->kernel, g->d) * sizeof(double) + 64));
+    GPX_TRY(loo_weights_of_handle(g, &w));
+    return loo_grad_reduce(g, gp_view(g).x, g->alpha, g->params, g->s, w.v, w.W.p, g->lda, (double *)w.part.p, loo_log_lh, grad);
+}
+
+int gpx_gp_loo_grad_weights(gpx_gp_t *g, double *G, int64_t ld)
+{
+    GP_ENTER(g);
+    GPX_ARG(g->fitted && G && ld >= g->n, "bad arguments");
+    GP_NEED_FINITE_Y(g);
+    GPX_TRY(gp_need_factor(g, "to take the leave-one-out weights from"));
+    const int64_t n = g->n;
+    LooWork w;
+    DevBuf Gd;
+    GPX_TRY(Gd.alloc((size_t)n * n * sizeof(double)));
+    GPX_TRY(loo_weights_of_handle(g, &w));
+    const dim3 grid((unsigned)cdiv(n, 256), (unsigned)std::min<int64_t>(n, 32768)), block(256);
+    if (g->dtype == GPX_F64)
+        hipLaunchKernelGGL((loo_g_kernel<double>), grid, block, 0, g->st, (const double *)g->alpha, (const double *)w.v.r,
+                           (const double *)w.W.p, g->lda, (double *)Gd.p, n);
+    else
+        hipLaunchKernelGGL((loo_g_kernel<float>), grid, block, 0, g->st, (const float *)g->alpha, (const float *)w.v.r,
+                           (const float *)w.W.p, g->lda, (double *)Gd.p, n);
+    GPX_LAUNCH_CHECK();
+    return download_f64(GPX_F64, G, ld, Gd.p, n, n, n, 0, g->st);
+}
+
+}  // extern "C"

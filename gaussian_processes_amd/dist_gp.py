@@ -9,7 +9,7 @@ object as `gp.GP` -- ``log_lh``, ``lh``, ``inv_Kxx_y``, ``mean(xo)``, ``cov(xo)`
 
 Every rank builds the same object with the same data and calls the same members in the same order: a fit, a mean
 and a cov are collective.  The factor never leaves the ranks' HBM, so what needs an n x n host copy (`Kxx`, `Lxx`,
-`inv_Kxx`, the derivative stack, `dm_dtheta`), leave-one-out, the input-space gradients, growing and shrinking the fit and joint samples (`loo`, `inv_Kxx_diag`, `dmean_dx`, `dvar_dx`,
+`inv_Kxx`, the derivative stack, `dm_dtheta`), leave-one-out, the input-space gradients, growing and shrinking the fit and joint samples (`loo`, `inv_Kxx_diag`, `dloo_dtheta`, `dmean_dx`, `dvar_dx`,
 `predict_grad`, `extend`, `remove`, `sample`, `sample_paths`: not implemented over the distributed factor) and what would have to carry a handle or a communicator to another
 process (`save_fitted`, copy, pickle) raises NotImplementedError: `GP` has them.
 """
@@ -214,6 +214,7 @@ class DistributedGP(GP):
     loo_var = property(_unsupported("loo_var", _NO_LOO))
     loo_log_lh = property(_unsupported("loo_log_lh", _NO_LOO))
     loo = _unsupported("loo", _NO_LOO)
+    dloo_dtheta = property(_unsupported("dloo_dtheta", _NO_LOO))
     _NO_XGRAD = "input-space gradients over the distributed factor are not implemented; one GPU has them"
     dmean_dx = _unsupported("dmean_dx", _NO_XGRAD)
     dvar_dx = _unsupported("dvar_dx", _NO_XGRAD)

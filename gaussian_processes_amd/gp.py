@@ -631,6 +631,47 @@ class GP(object):
         self.loo()
         return self._memoized["loo_log_lh"]
 
+    @memoprop
+    def dloo_dtheta(self):
+        r"""Gradient of `loo_log_lh` with respect to `params`, float64 ``(n_params + 1,)``: RW06 eq. 5.13, rearranged.
+        With :math:`W = K^{-1}`, :math:`\alpha = W y`, :math:`k_i = W_{ii}`,
+
+        .. math::
+            c_i = \tfrac12 (1 + \alpha_i^2 / k_i) / k_i, \quad r = W (\alpha / k), \quad P = W \,\mathrm{diag}(c)\, W, \quad
+            G = \tfrac12 (r \alpha^\top + \alpha r^\top) - P,
+
+        .. math::
+            \partial L_{LOO} / \partial \theta_j = \sum_{ab} (\partial K / \partial \theta_j)_{ab} G_{ab}, \qquad
+            \partial L_{LOO} / \partial s = 2 s \,(r \cdot \alpha - \mathrm{tr}\, P).
+
+        Eq. 5.13 as printed takes one :math:`n^3` product per parameter; this form takes ONE for all of them
+        (:math:`P = Y Y^\top`, :math:`Y = W \mathrm{diag}(\sqrt{c})`, lower triangle).  Cost: what `dloglh_dtheta` costs
+        (:math:`K^{-1}` from the factor, :math:`n^3`) plus that product (:math:`n^3`) and one fused pass over :math:`P`;
+        device memory the factor plus two ``(n, n)`` blocks, the same as `dloglh_dtheta`.  Native kernels (the
+        eligibility of `dloglh_dtheta`'s device route): everything on the device, :math:`r` by two triangular solves,
+        the kernel derivatives evaluated on the fly; `loo_log_lh` comes out of the same call and is filled when absent.
+        Every other kernel (plugin kernels, periodic at d > 1): :math:`G` is downloaded once and contracted with
+        `Kxx_J` on the host; it is not kept.  All NaN when `Kxx` is not positive definite, as `dloglh_dtheta`."""
+        npar = len(self.params)
+        st = self._fit()
+        out = np.empty(npar, dtype=DTYPE)
+        if st.info != 0:
+            out.fill(np.nan)
+            return out
+        native = getattr(self.K, "_native_kernel", None) is not None
+        if native and (self._d == 1 or self.K._native_kernel in (_lib.KERNEL_GAUSSIAN, _lib.KERNEL_GAUSSIAN_ARD)):
+            total = ctypes.c_double(0.0)
+            _lib.check(_lib.load().gpx_gp_loo_grad(st.handle, ctypes.byref(total), _lib.dptr(out)))
+            self._memoized.setdefault("loo_log_lh", DTYPE(total.value))
+            return out
+        G = np.empty((self._n, self._n), dtype=DTYPE)
+        _lib.check(_lib.load().gpx_gp_loo_grad_weights(st.handle, _lib.dptr(G), self._n))
+        J = self.Kxx_J
+        for j in range(npar - 1):
+            out[j] = np.sum(J[j] * G)
+        out[npar - 1] = 2.0 * self._s * np.trace(G)
+        return out
+
     def dm_dtheta(self, xo):
         r"""Derivative of the predictive mean w.r.t. the parameters, ``(n_p, m)``
         (gp/gp.py:627-662, gp_c.pyx:114-131)."""

@@ -34,6 +34,14 @@ def _kernel_id(kernel, x):
     return kid, nkp
 
 
+CRITERIA = ("log_lh", "loo")
+
+
+def _check_criterion(criterion):
+    if criterion not in CRITERIA:
+        raise ValueError("invalid value for criterion: %r (one of %s)" % (criterion, ", ".join(repr(c) for c in CRITERIA)))
+
+
 class BatchEvaluator(object):
     """One resident data set, many sweeps: keeps the ``gpx_gp`` handle (x, y and the lock-step
     workspace in HBM) alive between calls, so that an outer optimiser pays the upload and the
@@ -69,13 +77,17 @@ class BatchEvaluator(object):
             _lib.check(self.lib.gpx_gp_fit_batch(self.h, _lib.dptr(th), th.shape[0], _lib.dptr(res), None))
         return res
 
-    def value_and_grad(self, thetas, clamp=True):
+    def value_and_grad(self, thetas, clamp=True, criterion="log_lh"):
         """(log_lh, dloglh_dtheta) of every row: one ``gpx_gp_fit_batch_grad`` call -- the lock-step factorisation,
         then per row the reference's ``dloglh_dtheta`` (gp/gp.py:398-433, gp_c.pyx:34-49) from the row's own factor.
         ``clamp=False`` returns the log marginal likelihood WITHOUT the reference's ``logdet < MIN -> -inf`` clamp
         (gp_c.pyx:22-29) wherever the matrix is positive definite: -1/2 y^T a - 1/2 logdet - n/2 log 2 pi from the
         row's (logdet, y^T a) -- what an optimiser needs at n beyond a few thousand, where the clamped value is
-        -inf on most of the parameter space (an extension; the gradient is the reference's either way)."""
+        -inf on most of the parameter space (an extension; the gradient is the reference's either way).
+        ``criterion="loo"``: (loo_log_lh, dloo_dtheta) of every row instead, one ``gpx_gp_fit_batch_loo`` call -- the same
+        lock-step factorisation, then per row what ``GP.loo_log_lh`` and ``GP.dloo_dtheta`` return; the criterion has no
+        determinant and no clamp, `clamp` is ignored.  -inf and NaN for a row that is not positive definite."""
+        _check_criterion(criterion)
         th = np.ascontiguousarray(np.atleast_2d(np.asarray(thetas, dtype=np.float64)))
         if th.shape[1] != self.nkp + 1:
             raise ValueError("thetas must have %d columns (kernel params + s)" % (self.nkp + 1))
@@ -83,13 +95,19 @@ class BatchEvaluator(object):
         val = np.empty(B, dtype=np.float64)
         grad = np.empty((B, self.nkp + 1), dtype=np.float64)
         ldy = np.empty((B, 2), dtype=np.float64)
-        if B:
+        if B and criterion == "loo":
+            _lib.check(self.lib.gpx_gp_fit_batch_loo(self.h, _lib.dptr(th), B, _lib.dptr(val), _lib.dptr(grad), None))
+        elif B:
             _lib.check(self.lib.gpx_gp_fit_batch_grad(self.h, _lib.dptr(th), B, _lib.dptr(val), _lib.dptr(grad), _lib.dptr(ldy), None))
             if not clamp:
                 ok = np.isfinite(ldy).all(axis=1)
                 raw = -0.5 * ldy[:, 1] - 0.5 * ldy[:, 0] - 0.5 * self.n * np.log(2 * np.pi)
                 val = np.where(ok, raw, val)
         return val, grad
+
+    def loo(self, thetas):
+        """loo_log_lh of every row: the values of ``value_and_grad(thetas, criterion="loo")``, from the same call."""
+        return self.value_and_grad(thetas, criterion="loo")[0]
 
     def close(self):
         if self.h:
@@ -275,7 +293,7 @@ class _LockStep(object):
 
 
 def optimize(x, y, thetas0, kernel="gaussian", dtype="float64", device=None, bounds=None, maxiter=50, clamp=False,
-             options=None, evaluator=None):
+             options=None, evaluator=None, criterion="log_lh"):
     """ML-II by L-BFGS-B from every row of `thetas0` at once, all restarts in LOCK-STEP (what the reference's
     ``fit_MLII`` did one restart at a time before it was removed, CHANGELOG.md:19; its objective and gradient are
     ``GP.log_lh`` / ``GP.dloglh_dtheta``, gp/gp.py:337-367, 398-433).
@@ -292,7 +310,14 @@ def optimize(x, y, thetas0, kernel="gaussian", dtype="float64", device=None, bou
     likelihood (`BatchEvaluator.value_and_grad`); clamp=True keeps the reference's -inf plateau, on which an
     optimiser cannot move.  `evaluator`: an object with ``value_and_grad(thetas, clamp=...)`` to use instead of a new
     `BatchEvaluator` (tests; a caller that keeps its data set resident).  Returns a dict: theta (R, n_params + 1),
-    log_lh (R,), log_lh0 (R,), nit, nfev (R,), batched_calls, best (index of the largest final log_lh), messages."""
+    log_lh (R,), log_lh0 (R,), nit, nfev (R,), batched_calls, best (index of the largest final log_lh), messages,
+    criterion.
+
+    criterion="loo" maximises the leave-one-out criterion ``GP.loo_log_lh`` with gradient ``GP.dloo_dtheta`` (RW06 section
+    5.4.2: the choice when the model is misspecified) through the same machinery, one ``gpx_gp_fit_batch_loo`` call per
+    step; `log_lh` and `log_lh0` of the result then hold that criterion's values, and `clamp` has no meaning.  The
+    evaluator is then called as ``value_and_grad(thetas, clamp=..., criterion="loo")``."""
+    _check_criterion(criterion)
     import threading
     from scipy.optimize import minimize
     th0 = np.atleast_2d(np.asarray(thetas0, dtype=np.float64))
@@ -306,9 +331,10 @@ def optimize(x, y, thetas0, kernel="gaussian", dtype="float64", device=None, bou
     lb = list(zip(np.log(lo), np.log(hi)))
     big = 1e300
     ev = evaluator if evaluator is not None else BatchEvaluator(x, y, kernel=kernel, dtype=dtype, device=device)
+    kw = {"clamp": clamp} if criterion == "log_lh" else {"clamp": clamp, "criterion": criterion}
     try:
-        v0, _ = ev.value_and_grad(th0, clamp=clamp)
-        ls = _LockStep(lambda table: ev.value_and_grad(table, clamp=clamp), R)
+        v0, _ = ev.value_and_grad(th0, **kw)
+        ls = _LockStep(lambda table: ev.value_and_grad(table, **kw), R)
         out = [None] * R
 
         def run(i):
@@ -348,7 +374,7 @@ def optimize(x, y, thetas0, kernel="gaussian", dtype="float64", device=None, bou
             if isinstance(o, BaseException):
                 raise o
         theta = np.exp(np.array([o.x for o in out]))
-        final, _ = ev.value_and_grad(theta, clamp=clamp)
+        final, _ = ev.value_and_grad(theta, **kw)
     finally:
         if evaluator is None:
             ev.close()
@@ -359,4 +385,4 @@ def optimize(x, y, thetas0, kernel="gaussian", dtype="float64", device=None, bou
     ok = np.where(np.isfinite(final), final, -np.inf)
     return {"theta": theta, "log_lh": final, "log_lh0": v0, "nit": np.array([o.nit for o in out]),
             "nfev": np.array([o.nfev for o in out]), "batched_calls": ls.calls + 2, "best": int(np.argmax(ok)),
-            "messages": [str(o.message) for o in out]}
+            "messages": [str(o.message) for o in out], "criterion": criterion}

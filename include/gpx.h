@@ -557,6 +557,23 @@ int gpx_gp_inv_diag(gpx_gp_t *gp, int64_t chunk_rows, double *out);
  * density at y_i (eq. 5.10); *log_p_sum their sum (eq. 5.11), reduced on the device in a fixed order.  (n,) HOST float64
  * each; any pointer may be NULL.  As gpx_gp_inv_diag, and y must be finite. */
 int gpx_gp_loo(gpx_gp_t *gp, int64_t chunk_rows, double *mean, double *var, double *log_p, double *log_p_sum);
+/* The gradient of the leave-one-out criterion L = *log_p_sum above w.r.t. (kernel params..., s), RW06 eq. 5.13 rearranged so
+ * that ONE n^3 product serves every parameter.  With W = K^-1, k = diag W, c_i = (1 + alpha_i^2 / k_i) / (2 k_i),
+ * r = W (alpha / k) and Pm = W diag(c) W:   dL/dtheta_j = sum_ab (dK/dtheta_j)_ab G_ab,   G = (r alpha^T + alpha r^T) / 2 - Pm,
+ * dL/ds = 2 s (r . alpha - tr Pm).  On the device: W by TRSM + SYRK as gpx_gp_dloglh_dtheta forms it (whole, not its lower
+ * triangle), k from the rows of L^-T, r by two sweeps with the factor, Pm = Y Y^T (lower triangle) with Y = W diag(sqrt(c))
+ * written over L^-T and Pm over W, then one fused pass of (alpha, r, Pm) against the kernel derivatives evaluated on the fly:
+ * fixed summation order, f64 sums, bitwise repeatable.  Device memory: gpx_gp_dloglh_dtheta's two n x lda blocks.
+ * *loo_log_lh: the criterion itself from the same call, bit for bit gpx_gp_loo's *log_p_sum (the diagonal k stays in the
+ * handle, whichever of the two calls came first).  grad: n_params + 1 HOST float64.  GPX_ERR_ARG: NULL arguments, a handle
+ * that is not fitted or was fitted from gpx_gp_set_K (no kernel to differentiate), non-finite y.  -inf and an all-NaN gradient
+ * when the factorisation failed.  Periodic kernel: d == 1 only (GPX_ERR_UNSUPPORTED). */
+int gpx_gp_loo_grad(gpx_gp_t *gp, double *loo_log_lh, double *grad);            /* grad: n_params + 1, order (kernel params..., s) */
+/* The weights themselves, for callers who hold the kernel's derivatives (plugin kernels, periodic at d > 1): G (n, n) with
+ * leading dimension ld, float64, symmetric bit for bit -- formed in float64 from alpha, r and Pm's lower triangle in one
+ * more n x n float64 block on the device, then downloaded.  No kernel is evaluated: any fitted, positive definite handle.
+ * dL/dtheta_j = sum(dK_j * G); the noise's share is 2 s trace(G). */
+int gpx_gp_loo_grad_weights(gpx_gp_t *gp, double *G, int64_t ld);               /* HOST n x n float64, full symmetric G above */
 /* Input-space gradients of the prediction at xo (m, d) HOST float64 -> grad (m, d) HOST float64; m = 0 is legal.
  * gpx_gp_mean_grad: d mean(xo_i) / d xo_i, one fused pass (gpx_d_pred_grad with alpha); needs finite y, as gpx_gp_mean.
  * gpx_gp_var_grad: d var(xo_i) / d xo_i = -2 sum_j beta_ij dk(xo_i, x_j)/dxo_i with beta_i = K^-1 k(x, xo_i), in the row
@@ -661,6 +678,12 @@ int gpx_gp_fit_batch(gpx_gp_t *gp, const double *thetas, int64_t B, double *log_
  * thousand and leaves an optimiser nothing to follow (an extension; `log_lh` itself keeps the clamp). */
 int gpx_gp_fit_batch_grad(gpx_gp_t *gp, const double *thetas, int64_t B, double *log_lh, double *dloglh,
                           double *logdet_yta, int *info);
+/* The same table under the leave-one-out criterion: loo_log_lh HOST B doubles, dloo HOST (B, n_params + 1), what
+ * gpx_gp_loo_grad returns for a handle fitted at the row's parameters.  The lock-step factorisation and the groups of
+ * gpx_gp_fit_batch_grad; a group's K^-1 whole, its Y Y^T products in lock-step.  A row with invalid parameters: NaN and
+ * NaN; a row that is not positive definite: -inf and NaN (no logdet < MIN clamp: the criterion has no determinant);
+ * info as above. */
+int gpx_gp_fit_batch_loo(gpx_gp_t *gp, const double *thetas, int64_t B, double *loo_log_lh, double *dloo, int *info);
 /* Checkpoint of a fitted handle (the reference persists by pickling its memoised host arrays,
  * gp/gp.py:78-92; a 32 GiB factor cannot go that way).  File: header (dtype, kernel, n, d, params, s,
  * logdet, y^T alpha, info), x, y, alpha as float64, then the LOWER trapezoid of L in row blocks
