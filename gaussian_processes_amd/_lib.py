@@ -20,8 +20,8 @@ ERR_ARG, ERR_HIP, ERR_NO_DEVICE, ERR_NOMEM, ERR_UNSUPPORTED, ERR_INTERNAL = -1, 
  ROUTE_GEMM_FAST, ROUTE_GEMM_GENERIC, ROUTE_SYRK_EXACT, ROUTE_SYRK_PATCH, ROUTE_MG_BCAST_ONE, ROUTE_MG_BCAST_SAG,
  ROUTE_FIT_OPS_AHEAD, ROUTE_TRSM_OPS, ROUTE_POTRF_PAIR, ROUTE_VAR_CHUNK, ROUTE_LOO_CHUNK, ROUTE_TRSM_L_OPS,
  ROUTE_GRAD_CHUNK, ROUTE_EXTEND, ROUTE_SAMPLE, ROUTE_KAPPLY_FUSED, ROUTE_KAPPLY_GEMM, ROUTE_PATHS_GRAD_CHUNK,
- ROUTE_REMOVE) = range(25)
-PROF_RANDN, PROF_RFF, PROF_KAPPLY, PROF_KAPPLY_GRAD, PROF_CHOL_DELETE = 14, 15, 16, 17, 18
+ ROUTE_REMOVE, ROUTE_SPARSE_CHUNK) = range(26)
+PROF_RANDN, PROF_RFF, PROF_KAPPLY, PROF_KAPPLY_GRAD, PROF_CHOL_DELETE, PROF_SPARSE_GRAM = 14, 15, 16, 17, 18, 19
 F64, F32 = 0, 1
 KERNEL_GAUSSIAN, KERNEL_PERIODIC, KERNEL_GAUSSIAN_ARD = 0, 1, 2
 ARD_MAX_D = 64
@@ -159,6 +159,27 @@ _SIGNATURES = {
     "gpx_paths_destroy": (c_int, [c_void_p]),
     "gpx_debug_var_plan": (c_int, [c_int, c_int64, c_int64, c_int64, c_size_t, POINTER(c_int64), POINTER(c_int64),
                                    POINTER(c_size_t)]),
+    "gpx_sgp_create": (c_int, [POINTER(c_void_p), c_int, c_int, c_int64, c_int64, c_int]),
+    "gpx_sgp_destroy": (c_int, [c_void_p]),
+    "gpx_sgp_set_data": (c_int, [c_void_p, c_double_p, c_double_p, c_double_p]),
+    "gpx_sgp_fit": (c_int, [c_void_p, c_double_p, c_double, c_double, c_int64, c_int_p, c_int_p]),
+    "gpx_sgp_info": (c_int, [c_void_p, c_int_p, c_int_p]),
+    "gpx_sgp_elbo": (c_int, [c_void_p, c_double_p, c_double_p]),
+    "gpx_sgp_mean": (c_int, [c_void_p, c_double_p, c_int64, c_double_p]),
+    "gpx_sgp_var": (c_int, [c_void_p, c_double_p, c_int64, c_int64, c_double_p]),
+    "gpx_sgp_cov": (c_int, [c_void_p, c_double_p, c_int64, c_double_p]),
+    "gpx_sgp_get": (c_int, [c_void_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p]),
+    "gpx_sgp_last_timing": (c_int, [c_void_p, POINTER(c_float)]),
+    "gpx_sgp_set_split": (c_int, [c_void_p, c_int]),
+    "gpx_debug_sgp_plan": (c_int, [c_int, c_int64, c_int64, c_int64, c_int, c_size_t, POINTER(c_int64), POINTER(c_int64),
+                                   c_int_p, POINTER(c_int64)]),
+    "gpx_d_sum_slices_lower": (c_int, [c_int, c_void_p, c_int64, c_int64, c_int, c_int64, c_void_p, c_int64, c_void_p]),
+    "gpx_d_gemv_acc": (c_int, [c_int, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
+    "gpx_d_mirror_lower": (c_int, [c_int, c_void_p, c_int64, c_int64, c_void_p]),
+    "gpx_d_transpose": (c_int, [c_int, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p]),
+    "gpx_d_sgp_form_B": (c_int, [c_int, c_void_p, c_int64, c_int64, c_double, c_void_p, c_int64, c_void_p, c_void_p]),
+    "gpx_d_var_rows2": (c_int, [c_int, c_int, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int, c_double_p,
+                                c_void_p, c_void_p]),
     "gpx_gp_get_Kxx": (c_int, [c_void_p, c_double_p, c_int64]),
     "gpx_gp_get_Lxx": (c_int, [c_void_p, c_double_p, c_int64]),
     "gpx_gp_get_alpha": (c_int, [c_void_p, c_double_p]),

@@ -1,0 +1,804 @@
+// gpx_sparse.hip -- sparse GP regression on M inducing points (Titsias 2009, the collapsed bound): gpx_sgp_*.
+//
+//   Kuu = K(z, z) + eps I = Luu Luu^T      Phi = sum_c K(z, x_c) K(x_c, z)      b = sum_c K(z, x_c) y_c
+//   X = Luu^-1 Phi Luu^-T                  B = I + X / s^2 = LB LB^T            c = LB^-1 Luu^-1 b / s
+//   elbo = -sum log diag LB - N/2 log 2 pi - N log s - yy / (2 s^2) + c.c / (2 s^2) - (kff - tr X) / (2 s^2)
+//   mean(a) = k(a, z) w,  w = Luu^-T LB^-T c / s       var(a) = k(a, a) - |Luu^-1 k(z, a)|^2 + |LB^-1 Luu^-1 k(z, a)|^2
+// (Kuu + Phi / s^2 is never factored: log|A| - log|Kuu| cancels badly; B = I + X / s^2 is well conditioned.)
+//
+// The hot path is the Gram matrix Phi, 2 M^2 N flops: x goes by in column chunks, G = K(z, x_c) is MATERIALISED once per
+// chunk (M x c, the chunk's columns contiguous: both operands of G G^T are depth-contiguous, the NT product's layout) and
+// multiplied by the product kernel of gpx_gemm.hip on the lower tiles.  Fusing the kernel evaluation into the product
+// would re-evaluate each operand panel once per output tile column (M / 128 times) in a build that is VALU-bound.
+// Phi is small and the depth enormous -- the opposite of a trailing update -- so the depth of a chunk is split over the
+// product's batch dimension: slice p of every chunk adds to partial accumulator p, and sum_slices_lower_kernel adds the
+// partials in slice order at the end.  No atomics: a repeated fit gives the same bits.
+// Everything after that is M x M: potrf, the triangular sweeps and the reductions the library already owns, plus the small
+// kernels of this file (mirror / transpose, B and the trace, the two-block variance rows).
+//
+// Layout in HBM (dtype T, ldm = round_up(M, 16)):
+//   x (N, d)  y (N)  z (M, d)  [xs, zs: the ARD family's scaled copies]
+//   Luu, Phi, Xf, Xt, LB   M x ldm each     (Xf, Xt: work; X ends up in Xt)
+//   cvec, w, t0, t1        M each
+//   bacc                   M doubles
+//   work (grow-only)       G (M x cols) | the partial accumulators (slices x M x ldm)
+#include "gpx_common.h"
+#include <algorithm>
+#include <cmath>
+#include <vector>
+
+#include "gpx_gp_internal.h"
+
+// what a fit leaves behind on the device
+struct SgpScal {
+    double logdetB;    // 2 sum log diag LB (logdet_chol)
+    double yy;         // y . y
+    double cc;         // c . c
+    double k00;        // k(z_0, z_0), the kernel's value at distance zero in the handle's arithmetic
+    double trX;        // trace of X
+    double zero;       // stays 0: the row sum k(0) is `finished` against
+    int info1, info2;  // potrf of Kuu, of B
+};
+
+struct gpx_sgp {
+    int device, dtype, kernel, d, nparams;
+    int64_t n, m, ldm;
+    void *x, *y, *z, *xs, *zs;
+    void *Luu, *Phi, *Xf, *Xt, *LB;
+    void *cvec, *w, *t0, *t1;
+    double *bacc;
+    SgpScal *scal;
+    gpx::GrowBuf work;
+    hipStream_t st;
+    hipEvent_t ev[4];                  // start, Kuu done, chunks done, tail done
+    std::vector<hipEvent_t> cev;       // three per chunk: before the build, behind it, behind the products
+    int64_t chunks_timed;
+    double params[1 + GPX_ARD_MAX_D], iso[2];
+    double s, jitter;
+    bool have_x, have_y, have_z, fitted;
+    int stage, pivot, split;
+    SgpScal host;                      // the scalars of the last good fit
+};
+
+namespace gpx {
+
+constexpr int64_t SGP_CHUNK_ALIGN = 128, SGP_CHUNK_CAP = 16384, SGP_TARGET_WGS = 256, SGP_MIN_SLICES = 8, SGP_MAX_SLICES = 16,
+                  SGP_ACC_BYTES = (int64_t)2 << 30;
+
+// ---- the plan: columns per chunk, depth slices ---------------------------------------------------------------------------
+static int sgp_plan(int dtype, int64_t n, int64_t M, int64_t chunk_cols, int split, size_t free_bytes, int64_t *cols, int64_t *chunks,
+                    int *slices, int64_t *slice_cols)
+{
+    if (!(dtype == GPX_F64 || dtype == GPX_F32)) { set_error("sparse plan: dtype must be GPX_F64 or GPX_F32"); return GPX_ERR_ARG; }
+    if (n < 1 || M < 1) { set_error("sparse plan: need n >= 1 and m_inducing >= 1"); return GPX_ERR_ARG; }
+    if (chunk_cols < 0 || chunk_cols % SGP_CHUNK_ALIGN != 0) {
+        set_error("sparse plan: chunk_cols must be 0 (automatic) or a multiple of %d (got %lld)", (int)SGP_CHUNK_ALIGN, (long long)chunk_cols);
+        return GPX_ERR_ARG;
+    }
+    if (split < 0) { set_error("sparse plan: split must be >= 0"); return GPX_ERR_ARG; }
+    const size_t per_col = (size_t)M * esize(dtype), budget = free_bytes / 4;
+    const int64_t fit = (int64_t)std::min<size_t>(budget / per_col, (size_t)1 << 40) / SGP_CHUNK_ALIGN * SGP_CHUNK_ALIGN;
+    if (fit < SGP_CHUNK_ALIGN) {
+        set_error("sparse plan: not even %d columns of %lld rows fit a quarter of the free device memory (%zu bytes free)",
+                  (int)SGP_CHUNK_ALIGN, (long long)M, free_bytes);
+        return GPX_ERR_NOMEM;
+    }
+    int64_t c = chunk_cols ? chunk_cols : std::min(fit, SGP_CHUNK_CAP);
+    c = std::min(c, round_up(n, SGP_CHUNK_ALIGN));                     // one chunk: no wider than the data
+    if ((size_t)c * per_col > budget) {
+        set_error("sparse plan: chunk_cols = %lld needs %zu bytes, more than a quarter of the free device memory (%zu bytes free)",
+                  (long long)chunk_cols, (size_t)c * per_col, free_bytes);
+        return GPX_ERR_NOMEM;
+    }
+    // Depth slices: a function of (M, dtype) alone, so that results do not depend on the box.  Enough of them for the tiles
+    // of the lower triangle to cover the chip, and never fewer than SGP_MIN_SLICES: the product kernel runs a depth of
+    // 2048 columns per workgroup faster than one of 16384 whatever the tile count (fp64, d = 32, N = 2^20, chunk 16384,
+    // Gram product TF/s at P = 1 | 2 | 4 | 8 | 16:  M = 1024  4.7 | 9.3 | 18.3 | 35.6 | 38.6,  M = 2048  9.2 | 15.0 | 21.3 |
+    // 26.9 | 26.7,  M = 4096  37.0 | 41.5 | 44.5 | 55.3 | 54.5).  The partial accumulators together stay within
+    // SGP_ACC_BYTES.
+    const int64_t T = cdiv(M, 128), tiles = T * (T + 1) / 2;
+    const int64_t acc_fit = std::max<int64_t>(1, SGP_ACC_BYTES / ((int64_t)M * round_up(M, 16) * (int64_t)esize(dtype)));
+    const int64_t planned = std::min(acc_fit, std::min(SGP_MAX_SLICES, std::max(SGP_MIN_SLICES, cdiv(SGP_TARGET_WGS, tiles))));
+    const int64_t P = split > 0 ? split : planned;
+    const int64_t W = round_up(std::max(cdiv(c, P), SGP_CHUNK_ALIGN), SGP_CHUNK_ALIGN);
+    if (cols) *cols = c;
+    if (chunks) *chunks = cdiv(n, c);
+    if (slices) *slices = (int)cdiv(c, W);
+    if (slice_cols) *slice_cols = W;
+    return GPX_OK;
+}
+
+// ---- the kernels ---------------------------------------------------------------------------------------------------------
+// a 256-thread workgroup's sum, in a fixed order (a binary tree over the thread index); the result is valid in thread 0
+__device__ __forceinline__ double block256_sum(double v, double *red)
+{
+    const int tid = threadIdx.x;
+    __syncthreads();                                       // (a previous use of red[] has been read)
+    red[tid] = v;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (tid < s) red[tid] += red[tid + s];
+        __syncthreads();
+    }
+    return red[0];
+}
+
+// out[i, j] = sum_p P[p sP + i ldp + j], j <= i: the partial accumulators of the depth slices, p ascending, f64, one rounding
+template <typename T>
+__global__ __launch_bounds__(256) void sum_slices_lower_kernel(const T *__restrict__ P, int64_t ldp, int64_t sP, int slices, int64_t n,
+                                                               T *__restrict__ out, int64_t ldo)
+{
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    for (int64_t i = blockIdx.y; i < n; i += gridDim.y) {
+        if (j > i) continue;
+        const T *__restrict__ p = P + i * ldp + j;
+        double acc = 0.0;
+        for (int s = 0; s < slices; ++s) acc += (double)p[(int64_t)s * sP];
+        out[i * ldo + j] = (T)acc;
+    }
+}
+
+// acc[i] += sum_j G[i, j] y[j]: one workgroup per row (grid-stride), every lane its columns in index order, then the tree
+template <typename T>
+__global__ __launch_bounds__(256) void gemv_acc_kernel(const T *__restrict__ G, int64_t rows, int64_t cols, int64_t ldg,
+                                                       const T *__restrict__ y, double *__restrict__ acc)
+{
+    __shared__ double red[256];
+    for (int64_t i = blockIdx.x; i < rows; i += gridDim.x) {
+        const T *__restrict__ g = G + i * ldg;
+        double v = 0.0;
+        for (int64_t j = threadIdx.x; j < cols; j += 256) v = fma((double)g[j], (double)y[j], v);
+        const double t = block256_sum(v, red);
+        if (threadIdx.x == 0) acc[i] += t;
+    }
+}
+
+// out[j, i] = in[i, j] through a 32 x 32 tile in LDS.  mirror: in == out (no __restrict__), only the tiles at or below the
+// diagonal are read and only elements strictly above it are written -- nobody reads what another workgroup writes.
+template <typename T>
+__global__ __launch_bounds__(256) void transpose_kernel(const T *in, int64_t ldi, T *out, int64_t ldo, int64_t n, int mirror)
+{
+    __shared__ T tile[32][33];
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    const int64_t bi = blockIdx.y, bj = blockIdx.x;        // tile row / tile column of `in`
+    if (mirror && bj > bi) return;
+    for (int r = ty; r < 32; r += 8) {
+        const int64_t i = bi * 32 + r, j = bj * 32 + tx;
+        if (i < n && j < n) tile[r][tx] = in[i * ldi + j];
+    }
+    __syncthreads();
+    for (int r = ty; r < 32; r += 8) {
+        const int64_t oi = bj * 32 + r, oj = bi * 32 + tx; // out[oi, oj] = in[oj, oi] = tile[tx][r]
+        if (oi < n && oj < n && (!mirror || oj > oi)) out[oi * ldo + oj] = tile[tx][r];
+    }
+}
+
+// B[i, j] = (i == j) + X[i, j] / s^2 for j <= i; the workgroups of the extra grid row y == gridDim.y - 1 do not write B:
+// the first of them sums the diagonal of X in f64 in a fixed order
+template <typename T>
+__global__ __launch_bounds__(256) void form_B_kernel(const T *__restrict__ X, int64_t ldx, int64_t n, double s2, T *__restrict__ B,
+                                                     int64_t ldb, double *__restrict__ trace)
+{
+    __shared__ double red[256];
+    if (blockIdx.y == gridDim.y - 1) {
+        if (blockIdx.x != 0) return;
+        double v = 0.0;
+        for (int64_t i = threadIdx.x; i < n; i += 256) v += (double)X[i * ldx + i];
+        const double t = block256_sum(v, red);
+        if (threadIdx.x == 0) trace[0] = t;
+        return;
+    }
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    for (int64_t i = blockIdx.y; i < n; i += gridDim.y - 1) {
+        if (j > i) continue;
+        const double v = (double)X[i * ldx + j] / s2 + (i == j ? 1.0 : 0.0);
+        B[i * ldb + j] = (T)v;
+    }
+}
+
+// acc[i] = sum_j V[i, j]^2 - sum_j W[i, j]^2: the two solved blocks of the variance, f64, one workgroup per row
+template <typename T>
+__global__ __launch_bounds__(256) void rows2_kernel(const T *__restrict__ V, const T *__restrict__ W, int64_t rows, int64_t n, int64_t ldx,
+                                                    double *__restrict__ acc)
+{
+    __shared__ double red[256];
+    for (int64_t i = blockIdx.x; i < rows; i += gridDim.x) {
+        const T *__restrict__ v = V + i * ldx, *__restrict__ w = W + i * ldx;
+        double a = 0.0, b = 0.0;
+        for (int64_t j = threadIdx.x; j < n; j += 256) {
+            a = fma((double)v[j], (double)v[j], a);
+            b = fma((double)w[j], (double)w[j], b);
+        }
+        const double sa = block256_sum(a, red);
+        const double sb = block256_sum(b, red);
+        if (threadIdx.x == 0) acc[i] = sa - sb;
+    }
+}
+
+// dst[i] = (T)(src[i] / div), src DOUBLE;  v[i] = (T)(v[i] / div)
+template <typename T>
+__global__ void cvt_div_kernel(const double *__restrict__ src, T *__restrict__ dst, int64_t n, double div)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) dst[i] = (T)(src[i] / div);
+}
+template <typename T>
+__global__ void div_kernel(T *__restrict__ v, int64_t n, double div)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) v[i] = (T)((double)v[i] / div);
+}
+
+static int cvt_div(int dtype, const double *src, void *dst, int64_t n, double div, hipStream_t st)
+{
+    const dim3 grid((unsigned)cdiv(n, 256)), block(256);
+    if (dtype == GPX_F64) hipLaunchKernelGGL((cvt_div_kernel<double>), grid, block, 0, st, src, (double *)dst, n, div);
+    else hipLaunchKernelGGL((cvt_div_kernel<float>), grid, block, 0, st, src, (float *)dst, n, div);
+    GPX_LAUNCH_CHECK();
+    return GPX_OK;
+}
+static int div_vec(int dtype, void *v, int64_t n, double div, hipStream_t st)
+{
+    const dim3 grid((unsigned)cdiv(n, 256)), block(256);
+    if (dtype == GPX_F64) hipLaunchKernelGGL((div_kernel<double>), grid, block, 0, st, (double *)v, n, div);
+    else hipLaunchKernelGGL((div_kernel<float>), grid, block, 0, st, (float *)v, n, div);
+    GPX_LAUNCH_CHECK();
+    return GPX_OK;
+}
+
+static int sum_slices_lower(int dtype, const void *P, int64_t ldp, int64_t sP, int slices, int64_t n, void *out, int64_t ldo, hipStream_t st)
+{
+    if (n <= 0) return GPX_OK;
+    const dim3 grid((unsigned)cdiv(n, 256), (unsigned)std::min<int64_t>(n, 32768)), block(256);
+    if (dtype == GPX_F64)
+        hipLaunchKernelGGL((sum_slices_lower_kernel<double>), grid, block, 0, st, (const double *)P, ldp, sP, slices, n, (double *)out, ldo);
+    else
+        hipLaunchKernelGGL((sum_slices_lower_kernel<float>), grid, block, 0, st, (const float *)P, ldp, sP, slices, n, (float *)out, ldo);
+    GPX_LAUNCH_CHECK();
+    return GPX_OK;
+}
+
+static int gemv_acc(int dtype, const void *G, int64_t rows, int64_t cols, int64_t ldg, const void *y, double *acc, hipStream_t st)
+{
+    if (rows <= 0 || cols <= 0) return GPX_OK;
+    const dim3 grid((unsigned)std::min<int64_t>(rows, 1 << 20)), block(256);
+    if (dtype == GPX_F64)
+        hipLaunchKernelGGL((gemv_acc_kernel<double>), grid, block, 0, st, (const double *)G, rows, cols, ldg, (const double *)y, acc);
+    else
+        hipLaunchKernelGGL((gemv_acc_kernel<float>), grid, block, 0, st, (const float *)G, rows, cols, ldg, (const float *)y, acc);
+    GPX_LAUNCH_CHECK();
+    return GPX_OK;
+}
+
+static int transpose_sq(int dtype, const void *in, int64_t ldi, void *out, int64_t ldo, int64_t n, int mirror, hipStream_t st)
+{
+    if (n <= 0) return GPX_OK;
+    const int64_t t = cdiv(n, 32);
+    if (t > 65535) { set_error("transpose: n = %lld is beyond the grid", (long long)n); return GPX_ERR_ARG; }
+    const dim3 grid((unsigned)t, (unsigned)t), block(256);
+    ProfScope prof(PC_TRANSPOSE, (double)n * (double)n * (mirror ? 1.0 : 2.0) * (double)esize(dtype), st);
+    if (dtype == GPX_F64)
+        hipLaunchKernelGGL((transpose_kernel<double>), grid, block, 0, st, (const double *)in, ldi, (double *)out, ldo, n, mirror);
+    else
+        hipLaunchKernelGGL((transpose_kernel<float>), grid, block, 0, st, (const float *)in, ldi, (float *)out, ldo, n, mirror);
+    GPX_LAUNCH_CHECK();
+    return GPX_OK;
+}
+
+static int form_B(int dtype, const void *X, int64_t ldx, int64_t n, double s, void *B, int64_t ldb, double *trace_dev, hipStream_t st)
+{
+    if (n <= 0) return GPX_OK;
+    const dim3 grid((unsigned)cdiv(n, 256), (unsigned)std::min<int64_t>(n, 32768) + 1), block(256);
+    if (dtype == GPX_F64)
+        hipLaunchKernelGGL((form_B_kernel<double>), grid, block, 0, st, (const double *)X, ldx, n, s * s, (double *)B, ldb, trace_dev);
+    else
+        hipLaunchKernelGGL((form_B_kernel<float>), grid, block, 0, st, (const float *)X, ldx, n, s * s, (float *)B, ldb, trace_dev);
+    GPX_LAUNCH_CHECK();
+    return GPX_OK;
+}
+
+// out_dev[i] = kdiag(i) - sum V^2 + sum W^2: the row sums here (into acc_dev, rows doubles), kdiag and the subtraction by var_finish (gpx_solve.hip), which
+// evaluates k(xo_i, xo_i) as gpx_d_kmat does on its diagonal
+static int var_rows2(int dtype, int kernel, const void *V, const void *W, int64_t rows, int64_t n, int64_t ldx, const void *xo, int d,
+                     const double *params, double *acc_dev, double *out_dev, hipStream_t st)
+{
+    if (rows <= 0) return GPX_OK;
+    {
+        ProfScope prof(PC_REDUCE, 2.0 * (double)rows * (double)n * (double)esize(dtype), st);
+        const dim3 grid((unsigned)std::min<int64_t>(rows, 1 << 20)), block(256);
+        if (dtype == GPX_F64)
+            hipLaunchKernelGGL((rows2_kernel<double>), grid, block, 0, st, (const double *)V, (const double *)W, rows, n, ldx, acc_dev);
+        else
+            hipLaunchKernelGGL((rows2_kernel<float>), grid, block, 0, st, (const float *)V, (const float *)W, rows, n, ldx, acc_dev);
+        GPX_LAUNCH_CHECK();
+    }
+    return var_finish(dtype, kernel, xo, d, params, acc_dev, rows, out_dev, st);
+}
+
+// ---- the handle ----------------------------------------------------------------------------------------------------------
+struct SgpView { int kernel; const void *x, *z; const double *params; };
+static inline SgpView sgp_view(const gpx_sgp *g)
+{
+    if (g->kernel == GPX_KERNEL_GAUSSIAN_ARD) return {GPX_KERNEL_GAUSSIAN, g->xs, g->zs, g->iso};
+    return {g->kernel, g->x, g->z, g->params};
+}
+
+static int sgp_read_info(gpx_sgp *g, int which, int *info)
+{
+    GPX_HIP(hipMemcpyAsync(info, which == 1 ? &g->scal->info1 : &g->scal->info2, sizeof(int), hipMemcpyDeviceToHost, g->st));
+    GPX_HIP(hipStreamSynchronize(g->st));
+    return check_internal_info(*info);
+}
+
+static int sgp_chunk_events(gpx_sgp *g, int64_t chunks)
+{
+    while ((int64_t)g->cev.size() < 3 * chunks) {
+        hipEvent_t e;
+        GPX_HIP(hipEventCreate(&e));
+        g->cev.push_back(e);
+    }
+    return GPX_OK;
+}
+
+static int sgp_fit(gpx_sgp *g, int64_t chunk_cols)
+{
+    const int dtype = g->dtype;
+    const size_t es = esize(dtype);
+    const int64_t n = g->n, M = g->m, ldm = g->ldm;
+    hipStream_t st = g->st;
+    g->fitted = false; g->stage = 0; g->pivot = 0; g->chunks_timed = 0;
+    // the plan and its buffer, before anything is enqueued
+    size_t freeb = 0, totalb = 0;
+    GPX_HIP(hipMemGetInfo(&freeb, &totalb));
+    int64_t cols = 0, chunks = 0, W = 0;
+    int slices = 0;
+    GPX_TRY(sgp_plan(dtype, n, M, chunk_cols, g->split, freeb + g->work.bytes, &cols, &chunks, &slices, &W));
+    const int64_t sP = M * ldm;
+    const size_t g_bytes = (size_t)M * cols * es, p_bytes = (size_t)slices * sP * es;
+    GPX_TRY(g->work.reserve(g_bytes + p_bytes, st));
+    char *G = (char *)g->work.p, *Pacc = G + g_bytes;      // (g_bytes is a multiple of 128 es: Pacc is 16-byte aligned)
+    GPX_TRY(sgp_chunk_events(g, chunks));
+    if (g->kernel == GPX_KERNEL_GAUSSIAN_ARD) {
+        ard_iso(g->params, g->d, g->iso);
+        GPX_TRY(scale_points(dtype, g->x, n, g->d, g->params + 1, g->xs, st));
+        GPX_TRY(scale_points(dtype, g->z, M, g->d, g->params + 1, g->zs, st));
+    }
+    const SgpView v = sgp_view(g);
+    GPX_HIP(hipMemsetAsync(g->scal, 0, sizeof(SgpScal), st));
+    GPX_HIP(hipEventRecord(g->ev[0], st));
+    // 1. Kuu and its factor
+    GPX_TRY(kmat(dtype, v.kernel, GPX_K, v.z, M, v.z, M, g->d, v.params, g->jitter, GPX_LOWER, g->Luu, ldm, st));
+    GPX_TRY(potrf(dtype, g->Luu, M, ldm, &g->scal->info1, st));
+    GPX_TRY(tril(dtype, g->Luu, M, ldm, st));
+    GPX_HIP(hipEventRecord(g->ev[1], st));
+    int info = 0;
+    GPX_TRY(sgp_read_info(g, 1, &info));
+    if (info != 0) { g->stage = 1; g->pivot = info; g->fitted = true; return GPX_OK; }
+    // 2. the chunk loop: Phi's partials, b
+    GPX_HIP(hipMemsetAsync(Pacc, 0, p_bytes, st));
+    GPX_HIP(hipMemsetAsync(g->bacc, 0, (size_t)M * sizeof(double), st));
+    for (int64_t c = 0; c < chunks; ++c) {
+        const int64_t c0 = c * cols, cc = std::min(cols, n - c0);
+        route_hit(RT_SPARSE_CHUNK);
+        GPX_HIP(hipEventRecord(g->cev[3 * c], st));
+        GPX_TRY(kmat(dtype, v.kernel, GPX_K, v.z, M, (const char *)v.x + (size_t)c0 * g->d * es, cc, g->d, v.params, 0.0, GPX_FULL, G, cols, st));
+        GPX_HIP(hipEventRecord(g->cev[3 * c + 1], st));
+        const int64_t nfull = cc / W, tail = cc - nfull * W;
+        {
+            ProfScope prof(PC_SPARSE_GRAM, (double)cc * (double)M * (double)(M + 1), st);     // 2 cc flops per element of the lower triangle
+            if (nfull > 0) {
+                Batch bt; bt.count = (int)nfull; bt.sA = W; bt.sB = W; bt.sC = sP;
+                GPX_TRY(gemm_nt(dtype, M, M, W, G, cols, G, cols, Pacc, ldm, 1.0, GPX_LOWER, 0, 0, st, 0, 0, &bt));
+            }
+            if (tail > 0) {
+                const char *Gt = G + (size_t)nfull * W * es;
+                GPX_TRY(gemm_nt(dtype, M, M, tail, Gt, cols, Gt, cols, Pacc + (size_t)nfull * sP * es, ldm, 1.0, GPX_LOWER, 0, 0, st));
+            }
+        }
+        GPX_TRY(gemv_acc(dtype, G, M, cc, cols, (const char *)g->y + (size_t)c0 * es, g->bacc, st));
+        GPX_HIP(hipEventRecord(g->cev[3 * c + 2], st));
+    }
+    g->chunks_timed = chunks;
+    GPX_HIP(hipMemsetAsync(g->Phi, 0, (size_t)M * ldm * es, st));
+    GPX_TRY(sum_slices_lower(dtype, Pacc, ldm, sP, slices, M, g->Phi, ldm, st));
+    GPX_HIP(hipEventRecord(g->ev[2], st));
+    // 3. the M x M tail
+    GPX_TRY(dot(dtype, g->y, g->y, n, &g->scal->yy, st));
+    // k(0): the first inducing point against itself, through the variance's finishing pass with a zero sum
+    GPX_TRY(var_finish(dtype, v.kernel, v.z, g->d, v.params, &g->scal->zero, 1, &g->scal->k00, st));
+    GPX_HIP(hipMemcpyAsync(g->Xf, g->Phi, (size_t)M * ldm * es, hipMemcpyDeviceToDevice, st));
+    GPX_TRY(transpose_sq(dtype, g->Xf, ldm, g->Xf, ldm, M, 1, st));                 // mirror: Phi, full
+    GPX_TRY(trsm_right_lt(dtype, g->Luu, M, ldm, g->Xf, M, ldm, st));               // Phi Luu^-T
+    GPX_TRY(transpose_sq(dtype, g->Xf, ldm, g->Xt, ldm, M, 0, st));                 // Luu^-1 Phi
+    GPX_TRY(trsm_right_lt(dtype, g->Luu, M, ldm, g->Xt, M, ldm, st));               // X = Luu^-1 Phi Luu^-T
+    GPX_TRY(form_B(dtype, g->Xt, ldm, M, g->s, g->LB, ldm, &g->scal->trX, st));
+    GPX_TRY(potrf(dtype, g->LB, M, ldm, &g->scal->info2, st));
+    GPX_TRY(tril(dtype, g->LB, M, ldm, st));
+    GPX_TRY(sgp_read_info(g, 2, &info));
+    if (info != 0) {
+        GPX_HIP(hipEventRecord(g->ev[3], st));
+        GPX_HIP(hipStreamSynchronize(st));
+        g->stage = 2; g->pivot = info; g->fitted = true;
+        return GPX_OK;
+    }
+    // c = LB^-1 Luu^-1 b / s   (trsv_lower destroys its right-hand side)
+    GPX_TRY(cvt_div(dtype, g->bacc, g->t0, M, 1.0, st));
+    GPX_TRY(trsv_lower(dtype, g->Luu, M, ldm, g->t0, g->t1, 0, st));
+    GPX_TRY(trsv_lower(dtype, g->LB, M, ldm, g->t1, g->cvec, 0, st));
+    GPX_TRY(div_vec(dtype, g->cvec, M, g->s, st));
+    // w = Luu^-T LB^-T c / s
+    GPX_HIP(hipMemcpyAsync(g->t0, g->cvec, (size_t)M * es, hipMemcpyDeviceToDevice, st));
+    GPX_TRY(trsv_lower(dtype, g->LB, M, ldm, g->t0, g->t1, 1, st));
+    GPX_TRY(trsv_lower(dtype, g->Luu, M, ldm, g->t1, g->w, 1, st));
+    GPX_TRY(div_vec(dtype, g->w, M, g->s, st));
+    GPX_TRY(logdet_chol(dtype, g->LB, M, ldm, &g->scal->logdetB, st));
+    GPX_TRY(dot(dtype, g->cvec, g->cvec, M, &g->scal->cc, st));
+    GPX_HIP(hipEventRecord(g->ev[3], st));
+    GPX_HIP(hipMemcpyAsync(&g->host, g->scal, sizeof(SgpScal), hipMemcpyDeviceToHost, st));
+    GPX_HIP(hipStreamSynchronize(st));
+    g->fitted = true;
+    return GPX_OK;
+}
+
+static int sgp_upload_points(gpx_sgp *g, void *dst, const double *xo, int64_t m)
+{
+    GPX_TRY(upload_f64(g->dtype, dst, m * g->d, xo, m * g->d, 1, m * g->d, g->st));
+    if (g->kernel == GPX_KERNEL_GAUSSIAN_ARD) GPX_TRY(scale_points(g->dtype, dst, m, g->d, g->params + 1, dst, g->st));
+    return GPX_OK;
+}
+
+// V = K(xo_c, z) Luu^-T and W = V LB^-T of `rows` test points (rows x ldm each), enqueued on the handle's stream
+static int sgp_two_blocks(gpx_sgp *g, const void *xo_c, int64_t rows, void *V, void *W)
+{
+    const SgpView v = sgp_view(g);
+    const int64_t M = g->m, ldm = g->ldm;
+    GPX_TRY(kmat(g->dtype, v.kernel, GPX_K, xo_c, rows, v.z, M, g->d, v.params, 0.0, GPX_FULL, V, ldm, g->st));
+    GPX_TRY(trsm_right_lt(g->dtype, g->Luu, M, ldm, V, rows, ldm, g->st));
+    GPX_HIP(hipMemcpyAsync(W, V, (size_t)rows * ldm * esize(g->dtype), hipMemcpyDeviceToDevice, g->st));
+    return trsm_right_lt(g->dtype, g->LB, M, ldm, W, rows, ldm, g->st);
+}
+
+}  // namespace gpx
+
+using namespace gpx;
+
+#define SGP_ENTER(g)                                                         \
+    GPX_ARG((g) != nullptr, "handle is NULL");                               \
+    gpx::tune_refresh();                                                     \
+    gpx::DeviceGuard guard__((g)->device);                                   \
+    if (guard__.rc != GPX_OK) return guard__.rc;                             \
+    gpx::StreamTurn turn__((g)->st);                                         \
+    gpx::RoctxRange api_range__(__func__)
+
+#define SGP_NEED_FIT(g)                                                                                              \
+    do {                                                                                                             \
+        GPX_ARG((g)->fitted, "the sparse GP is not fitted");                                                         \
+        if ((g)->stage != 0) {                                                                                       \
+            gpx::set_error("%s: %s is not positive definite (stage %d, info = %d): there is nothing to predict from", __func__, \
+                           (g)->stage == 1 ? "Kuu" : "B", (g)->stage, (g)->pivot);                                   \
+            return GPX_ERR_ARG;                                                                                      \
+        }                                                                                                            \
+    } while (0)
+
+extern "C" {
+
+int gpx_sgp_create(gpx_sgp_t **out, int dtype, int kernel, int64_t n, int64_t m_inducing, int d)
+{
+    GPX_TRY(ensure_device());
+    GPX_ARG(out, "handle is NULL");
+    *out = nullptr;
+    GPX_ARG(dtype == GPX_F64 || dtype == GPX_F32, "dtype must be GPX_F64 or GPX_F32");
+    GPX_ARG(kernel == GPX_KERNEL_GAUSSIAN || kernel == GPX_KERNEL_PERIODIC || kernel == GPX_KERNEL_GAUSSIAN_ARD, "unknown kernel family");
+    GPX_ARG(n >= 1 && m_inducing >= 1 && d >= 1, "need n >= 1, m_inducing >= 1 and d >= 1");
+    GPX_ARG(kernel != GPX_KERNEL_GAUSSIAN_ARD || d <= GPX_ARD_MAX_D, "the ARD family needs d <= GPX_ARD_MAX_D");
+    gpx_sgp *g = new gpx_sgp();
+    g->dtype = dtype; g->kernel = kernel; g->n = n; g->m = m_inducing; g->d = d;
+    if (hipGetDevice(&g->device) != hipSuccess) { (void)hipGetLastError(); g->device = 0; }
+    g->nparams = nparams_of(kernel, d);
+    g->ldm = round_up(m_inducing, 16);
+    const size_t es = esize(dtype), mm = (size_t)m_inducing * g->ldm * es, mv = (size_t)g->ldm * es;
+    int rc = GPX_OK;
+    hipError_t e;
+#define SGP_ALLOC(field, bytes) if (rc == GPX_OK) rc = dev_alloc((void **)&g->field, (bytes), "hipMalloc " #field)
+    SGP_ALLOC(x, (size_t)n * d * es);
+    SGP_ALLOC(y, (size_t)n * es);
+    SGP_ALLOC(z, (size_t)m_inducing * d * es);
+    if (kernel == GPX_KERNEL_GAUSSIAN_ARD) { SGP_ALLOC(xs, (size_t)n * d * es); SGP_ALLOC(zs, (size_t)m_inducing * d * es); }
+    SGP_ALLOC(Luu, mm); SGP_ALLOC(Phi, mm); SGP_ALLOC(Xf, mm); SGP_ALLOC(Xt, mm); SGP_ALLOC(LB, mm);
+    SGP_ALLOC(cvec, mv); SGP_ALLOC(w, mv); SGP_ALLOC(t0, mv); SGP_ALLOC(t1, mv);
+    SGP_ALLOC(bacc, (size_t)m_inducing * sizeof(double));
+    SGP_ALLOC(scal, sizeof(SgpScal));
+#undef SGP_ALLOC
+    if (rc == GPX_OK) {
+        e = hipStreamCreateWithFlags(&g->st, hipStreamNonBlocking);
+        if (e != hipSuccess) rc = hip_fail(e, "hipStreamCreate", __FILE__, __LINE__);
+    }
+    for (int i = 0; i < 4 && rc == GPX_OK; ++i) {
+        e = hipEventCreate(&g->ev[i]);
+        if (e != hipSuccess) rc = hip_fail(e, "hipEventCreate", __FILE__, __LINE__);
+    }
+    if (rc != GPX_OK) { gpx_sgp_destroy(g); return rc; }
+    *out = g;
+    return GPX_OK;
+}
+
+int gpx_sgp_destroy(gpx_sgp_t *g)
+{
+    if (!g) return GPX_OK;
+    gpx::DeviceGuard guard__(g->device);
+    if (g->st) (void)hipStreamSynchronize(g->st);
+    stream_epoch_bump();                                       // (StreamTurn: a later stream at this one's address is a different stream)
+    for (void *b : {g->x, g->y, g->z, g->xs, g->zs, g->Luu, g->Phi, g->Xf, g->Xt, g->LB, g->cvec, g->w, g->t0, g->t1, (void *)g->bacc,
+                    (void *)g->scal})
+        dev_free(b);
+    g->work.release();
+    for (int i = 0; i < 4; ++i) if (g->ev[i]) (void)hipEventDestroy(g->ev[i]);
+    for (hipEvent_t e : g->cev) (void)hipEventDestroy(e);
+    if (g->st) (void)hipStreamDestroy(g->st);
+    delete g;
+    return GPX_OK;
+}
+
+int gpx_sgp_set_data(gpx_sgp_t *g, const double *x, const double *y, const double *z)
+{
+    SGP_ENTER(g);
+    g->fitted = false;
+    if (x) { GPX_TRY(upload_f64(g->dtype, g->x, g->n * g->d, x, g->n * g->d, 1, g->n * g->d, g->st)); g->have_x = true; }
+    if (y) { GPX_TRY(upload_f64(g->dtype, g->y, g->n, y, g->n, 1, g->n, g->st)); g->have_y = true; }
+    if (z) { GPX_TRY(upload_f64(g->dtype, g->z, g->m * g->d, z, g->m * g->d, 1, g->m * g->d, g->st)); g->have_z = true; }
+    return GPX_OK;
+}
+
+int gpx_sgp_fit(gpx_sgp_t *g, const double *params, double s, double jitter, int64_t chunk_cols, int *stage, int *pivot)
+{
+    SGP_ENTER(g);
+    GPX_ARG(params && stage && pivot, "NULL argument");
+    GPX_ARG(g->have_x && g->have_y && g->have_z, "no data in the handle (gpx_sgp_set_data)");
+    GPX_ARG(s > 0.0 && s <= 1.79769313486231570e308, "s must be positive and finite (the bound divides by s^2)");
+    GPX_ARG(jitter >= 0.0 && jitter <= 1.79769313486231570e308, "jitter must be >= 0 and finite");
+    GPX_ARG(chunk_cols >= 0 && chunk_cols % SGP_CHUNK_ALIGN == 0, "chunk_cols must be 0 (automatic) or a multiple of 128");
+    for (int i = 0; i < g->nparams; ++i) {
+        GPX_ARG(std::isfinite(params[i]), "array must not contain infs or NaNs (kernel parameters)");
+        g->params[i] = params[i];
+    }
+    g->s = s; g->jitter = jitter;
+    const int rc = sgp_fit(g, chunk_cols);
+    if (rc != GPX_OK) { g->fitted = false; return rc; }
+    *stage = g->stage; *pivot = g->pivot;
+    return GPX_OK;
+}
+
+int gpx_sgp_info(gpx_sgp_t *g, int *stage, int *pivot)
+{
+    GPX_ARG(g != nullptr && stage && pivot, "NULL argument");
+    GPX_ARG(g->fitted, "the sparse GP is not fitted");
+    *stage = g->stage; *pivot = g->pivot;
+    return GPX_OK;
+}
+
+int gpx_sgp_elbo(gpx_sgp_t *g, double *elbo, double *terms5)
+{
+    GPX_ARG(g != nullptr && elbo, "NULL argument");
+    GPX_ARG(g->fitted, "the sparse GP is not fitted");
+    double t[5];
+    if (g->stage != 0) {
+        for (double &v : t) v = NAN;
+        *elbo = -INFINITY;
+    } else {
+        const SgpScal &h = g->host;
+        const double s2 = g->s * g->s, N = (double)g->n;
+        t[0] = -0.5 * h.logdetB;
+        t[1] = -0.5 * N * log(2.0 * M_PI) - N * log(g->s);
+        t[2] = -0.5 * h.yy / s2;
+        t[3] = 0.5 * h.cc / s2;
+        t[4] = -0.5 * (N * h.k00 - h.trX) / s2;
+        *elbo = (((t[0] + t[1]) + t[2]) + t[3]) + t[4];
+    }
+    if (terms5) for (int i = 0; i < 5; ++i) terms5[i] = t[i];
+    return GPX_OK;
+}
+
+int gpx_sgp_mean(gpx_sgp_t *g, const double *xo, int64_t m, double *out)
+{
+    SGP_ENTER(g);
+    SGP_NEED_FIT(g);
+    GPX_ARG(m >= 0 && (m == 0 || (xo && out)), "bad arguments");
+    if (m == 0) return GPX_OK;
+    const size_t es = esize(g->dtype);
+    DevBuf dxo, dout;
+    GPX_TRY(dxo.alloc((size_t)m * g->d * es));
+    GPX_TRY(dout.alloc((size_t)m * es));
+    GPX_TRY(sgp_upload_points(g, dxo.p, xo, m));
+    const SgpView v = sgp_view(g);
+    GPX_TRY(gpx_d_mean(g->dtype, v.kernel, dxo.p, m, v.z, g->m, g->d, v.params, g->w, dout.p, (void *)g->st));
+    return download_f64(g->dtype, out, m, dout.p, m, 1, m, 0, g->st);
+}
+
+int gpx_sgp_var(gpx_sgp_t *g, const double *xo, int64_t m, int64_t chunk_rows, double *out)
+{
+    SGP_ENTER(g);
+    SGP_NEED_FIT(g);
+    GPX_ARG(m >= 0 && (m == 0 || (xo && out)), "bad arguments");
+    GPX_ARG(chunk_rows >= 0 && chunk_rows % 128 == 0, "chunk_rows must be 0 (automatic) or a multiple of 128");
+    if (m == 0) return GPX_OK;
+    const size_t es = esize(g->dtype);
+    size_t freeb = 0, totalb = 0;
+    GPX_HIP(hipMemGetInfo(&freeb, &totalb));
+    int64_t rows = 0, chunks = 0;
+    GPX_TRY(var_plan(g->dtype, g->m, m, chunk_rows, freeb / 2, &rows, &chunks, nullptr));      // two blocks a chunk
+    DevBuf dxo, V, W, dvar, dacc;
+    GPX_TRY(dxo.alloc((size_t)m * g->d * es));
+    GPX_TRY(V.alloc((size_t)rows * g->ldm * es));
+    GPX_TRY(W.alloc((size_t)rows * g->ldm * es));
+    GPX_TRY(dvar.alloc((size_t)m * sizeof(double)));
+    GPX_TRY(dacc.alloc((size_t)rows * sizeof(double)));
+    GPX_TRY(sgp_upload_points(g, dxo.p, xo, m));
+    const SgpView v = sgp_view(g);
+    for (int64_t c = 0; c < chunks; ++c) {
+        const int64_t r0 = c * rows, rc = std::min(rows, m - r0);
+        route_hit(RT_VAR_CHUNK);
+        const char *xo_c = (const char *)dxo.p + (size_t)r0 * g->d * es;
+        GPX_TRY(sgp_two_blocks(g, xo_c, rc, V.p, W.p));
+        GPX_TRY(var_rows2(g->dtype, v.kernel, V.p, W.p, rc, g->m, g->ldm, xo_c, g->d, v.params, (double *)dacc.p, (double *)dvar.p + r0, g->st));
+    }
+    GPX_HIP(hipMemcpyAsync(out, dvar.p, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, g->st));
+    GPX_HIP(hipStreamSynchronize(g->st));
+    return GPX_OK;
+}
+
+int gpx_sgp_cov(gpx_sgp_t *g, const double *xo, int64_t m, double *out)
+{
+    SGP_ENTER(g);
+    SGP_NEED_FIT(g);
+    GPX_ARG(m >= 0 && (m == 0 || (xo && out)), "bad arguments");
+    if (m == 0) return GPX_OK;
+    const size_t es = esize(g->dtype);
+    const int64_t ldc = round_up(m, 16), ldm = g->ldm;
+    DevBuf dxo, V, W, C;
+    GPX_TRY(dxo.alloc((size_t)m * g->d * es));
+    GPX_TRY(V.alloc((size_t)m * ldm * es));
+    GPX_TRY(W.alloc((size_t)m * ldm * es));
+    GPX_TRY(C.alloc((size_t)m * ldc * es));
+    GPX_TRY(sgp_upload_points(g, dxo.p, xo, m));
+    const SgpView v = sgp_view(g);
+    GPX_TRY(sgp_two_blocks(g, dxo.p, m, V.p, W.p));
+    GPX_TRY(kmat(g->dtype, v.kernel, GPX_K, dxo.p, m, dxo.p, m, g->d, v.params, 0.0, GPX_FULL, C.p, ldc, g->st));
+    GPX_TRY(gemm_nt(g->dtype, m, m, g->m, V.p, ldm, V.p, ldm, C.p, ldc, -1.0, GPX_FULL, 0, 0, g->st));
+    GPX_TRY(gemm_nt(g->dtype, m, m, g->m, W.p, ldm, W.p, ldm, C.p, ldc, 1.0, GPX_FULL, 0, 0, g->st));
+    return download_f64(g->dtype, out, m, C.p, ldc, m, m, 0, g->st);
+}
+
+int gpx_sgp_get(gpx_sgp_t *g, double *Luu, double *LB, double *c, double *Phi, double *b)
+{
+    SGP_ENTER(g);
+    GPX_ARG(g->fitted, "the sparse GP is not fitted");
+    const int64_t M = g->m, ldm = g->ldm;
+    if (Luu) GPX_TRY(download_f64(g->dtype, Luu, M, g->Luu, ldm, M, M, 1, g->st));
+    if (LB) GPX_TRY(download_f64(g->dtype, LB, M, g->LB, ldm, M, M, 1, g->st));
+    if (c) GPX_TRY(download_f64(g->dtype, c, M, g->cvec, M, 1, M, 0, g->st));
+    if (Phi) GPX_TRY(download_f64(g->dtype, Phi, M, g->Phi, ldm, M, M, 1, g->st));
+    if (b) {
+        GPX_HIP(hipMemcpyAsync(b, g->bacc, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, g->st));
+        GPX_HIP(hipStreamSynchronize(g->st));
+    }
+    return GPX_OK;
+}
+
+int gpx_sgp_last_timing(gpx_sgp_t *g, float *ms5)
+{
+    GPX_ARG(g != nullptr && ms5, "NULL argument");
+    GPX_ARG(g->fitted, "the sparse GP is not fitted");
+    gpx::DeviceGuard guard__(g->device);
+    if (guard__.rc != GPX_OK) return guard__.rc;
+    for (int i = 0; i < 5; ++i) ms5[i] = 0.0f;
+    GPX_HIP(hipEventElapsedTime(&ms5[0], g->ev[0], g->ev[1]));
+    if (g->stage == 1) { ms5[4] = ms5[0]; return GPX_OK; }
+    for (int64_t c = 0; c < g->chunks_timed; ++c) {
+        float a = 0.0f, b = 0.0f;
+        GPX_HIP(hipEventElapsedTime(&a, g->cev[3 * c], g->cev[3 * c + 1]));
+        GPX_HIP(hipEventElapsedTime(&b, g->cev[3 * c + 1], g->cev[3 * c + 2]));
+        ms5[1] += a; ms5[2] += b;
+    }
+    if (g->chunks_timed > 0) {
+        float r = 0.0f;
+        GPX_HIP(hipEventElapsedTime(&r, g->cev[3 * g->chunks_timed - 1], g->ev[2]));   // the slice sum
+        ms5[2] += r;
+    }
+    GPX_HIP(hipEventElapsedTime(&ms5[3], g->ev[2], g->ev[3]));
+    GPX_HIP(hipEventElapsedTime(&ms5[4], g->ev[0], g->ev[3]));
+    return GPX_OK;
+}
+
+int gpx_sgp_set_split(gpx_sgp_t *g, int slices)
+{
+    GPX_ARG(g != nullptr, "handle is NULL");
+    GPX_ARG(slices >= 0, "slices must be >= 0");
+    g->split = slices;
+    g->fitted = false;
+    return GPX_OK;
+}
+
+int gpx_debug_sgp_plan(int dtype, int64_t n, int64_t m_inducing, int64_t chunk_cols, int split, size_t free_bytes, int64_t *cols,
+                       int64_t *chunks, int *slices, int64_t *slice_cols)
+{
+    return sgp_plan(dtype, n, m_inducing, chunk_cols, split, free_bytes, cols, chunks, slices, slice_cols);
+}
+
+// ---- the building blocks ---------------------------------------------------------------------------------------------------
+#define SGP_D_ENTER()                                                                            \
+    gpx::tune_refresh();                                                                         \
+    GPX_ARG(dtype == GPX_F64 || dtype == GPX_F32, "dtype must be GPX_F64 or GPX_F32")
+
+int gpx_d_sum_slices_lower(int dtype, const void *P, int64_t ldp, int64_t sP, int slices, int64_t n, void *out, int64_t ldo, void *stream)
+{
+    SGP_D_ENTER();
+    GPX_ARG(n >= 0 && slices >= 1, "need n >= 0 and slices >= 1");
+    if (n == 0) return GPX_OK;
+    GPX_ARG(P && out && P != out, "NULL pointer or out == P");
+    GPX_ARG(ldp >= n && ldo >= n && sP >= 0, "leading dimension too small");
+    GPX_TRY(ensure_device());
+    return sum_slices_lower(dtype, P, ldp, sP, slices, n, out, ldo, S(stream));
+}
+
+int gpx_d_gemv_acc(int dtype, const void *G, int64_t rows, int64_t cols, int64_t ldg, const void *y, double *acc_dev, void *stream)
+{
+    SGP_D_ENTER();
+    GPX_ARG(rows >= 0 && cols >= 0, "negative dimension");
+    if (rows == 0 || cols == 0) return GPX_OK;
+    GPX_ARG(G && y && acc_dev, "NULL pointer");
+    GPX_ARG(ldg >= cols, "leading dimension too small");
+    GPX_TRY(ensure_device());
+    return gemv_acc(dtype, G, rows, cols, ldg, y, acc_dev, S(stream));
+}
+
+int gpx_d_mirror_lower(int dtype, void *A, int64_t n, int64_t lda, void *stream)
+{
+    SGP_D_ENTER();
+    GPX_ARG(n >= 0, "n < 0");
+    if (n == 0) return GPX_OK;
+    GPX_ARG(A && lda >= n, "NULL pointer or leading dimension too small");
+    GPX_TRY(ensure_device());
+    return transpose_sq(dtype, A, lda, A, lda, n, 1, S(stream));
+}
+
+int gpx_d_transpose(int dtype, const void *in, int64_t ldi, void *out, int64_t ldo, int64_t n, void *stream)
+{
+    SGP_D_ENTER();
+    GPX_ARG(n >= 0, "n < 0");
+    if (n == 0) return GPX_OK;
+    GPX_ARG(in && out && in != out, "NULL pointer or out == in");
+    GPX_ARG(ldi >= n && ldo >= n, "leading dimension too small");
+    GPX_TRY(ensure_device());
+    return transpose_sq(dtype, in, ldi, out, ldo, n, 0, S(stream));
+}
+
+int gpx_d_sgp_form_B(int dtype, const void *X, int64_t ldx, int64_t n, double s, void *B, int64_t ldb, double *trace_dev, void *stream)
+{
+    SGP_D_ENTER();
+    GPX_ARG(n >= 0, "n < 0");
+    if (n == 0) return GPX_OK;
+    GPX_ARG(X && B && trace_dev && X != B, "NULL pointer or B == X");
+    GPX_ARG(ldx >= n && ldb >= n, "leading dimension too small");
+    GPX_ARG(s > 0.0, "s must be positive");
+    GPX_TRY(ensure_device());
+    return form_B(dtype, X, ldx, n, s, B, ldb, trace_dev, S(stream));
+}
+
+int gpx_d_var_rows2(int dtype, int kernel, const void *V, const void *W, int64_t rows, int64_t n, int64_t ldx, const void *xo, int d,
+                    const double *params, double *out_dev, void *stream)
+{
+    SGP_D_ENTER();
+    GPX_ARG(rows >= 0 && n >= 0, "negative dimension");
+    if (rows == 0) return GPX_OK;
+    GPX_ARG(V && W && xo && params && out_dev && d >= 1, "NULL pointer or d < 1");
+    GPX_ARG(ldx >= n, "leading dimension too small");
+    GPX_ARG(kernel == GPX_KERNEL_GAUSSIAN || kernel == GPX_KERNEL_PERIODIC, "unknown kernel family (the ARD family: scaled points and the isotropic constants)");
+    GPX_TRY(ensure_device());
+    DevBuf acc;                                            // the row sums; the call waits for the stream before it frees them
+    GPX_TRY(acc.alloc((size_t)rows * sizeof(double)));
+    GPX_TRY(var_rows2(dtype, kernel, V, W, rows, n, ldx, xo, d, params, (double *)acc.p, out_dev, S(stream)));
+    GPX_HIP(hipStreamSynchronize(S(stream)));
+    return GPX_OK;
+}
+
+}  // extern "C"

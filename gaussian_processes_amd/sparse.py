@@ -1,0 +1,397 @@
+"""SparseGP -- GP regression on M inducing points (Titsias 2009, the collapsed bound; "SGPR") on MI355X.
+
+The dense `GP` factors an n x n matrix; this class never forms one.  With inducing inputs `z` (M, d)::
+
+    Kuu  = K(z, z) + jitter I = Luu Luu^T       Phi = K(z, x) K(x, z)        b = K(z, x) y
+    X    = Luu^-1 Phi Luu^-T                    B = I + X / s^2 = LB LB^T    c = LB^-1 Luu^-1 b / s
+    elbo = -sum log diag LB - N/2 log 2 pi - N log s - y.y / (2 s^2) + c.c / (2 s^2) - (sum_i k(x_i, x_i) - tr X) / (2 s^2)
+    mean(a) = k(a, z) Luu^-T LB^-T c / s
+    var(a)  = k(a, a) - |Luu^-1 k(z, a)|^2 + |LB^-1 Luu^-1 k(z, a)|^2
+
+O(N M^2) time, O(M^2 + M chunk) device memory: x passes through the device in column chunks (``gpx_sgp_fit``,
+include/gpx.h).  `elbo` is a LOWER BOUND on the log marginal likelihood of the dense GP, not that likelihood: there is no
+attribute called ``log_lh`` here, on purpose.
+"""
+import ctypes
+
+import numpy as np
+
+from . import _lib
+from .gp import DTYPE, _DTYPES
+
+__all__ = ["SparseGP"]
+
+ELBO_TERMS = ("logdet", "noise", "fit", "quad", "trace")
+_STAGE_NAMES = {1: "Kuu = K(z, z) + jitter I", 2: "B = I + Luu^-1 Phi Luu^-T / s^2"}
+
+
+class _SparseState(object):
+    """Owns the gpx_sgp handle of one SparseGP; rebuilt whenever a shape, the dtype or the kernel family changes."""
+
+    def __init__(self, dtype_id, kernel_id, n, m, d, device):
+        self.key = (dtype_id, kernel_id, n, m, d, device)
+        self.handle = ctypes.c_void_p()
+        self.data_version = -1
+        self.fit_version = -1
+        self.stage = self.pivot = None
+        lib = _lib.load()
+        if device is not None:
+            _lib.check(lib.gpx_set_device(int(device)))
+        _lib.check(lib.gpx_sgp_create(ctypes.byref(self.handle), dtype_id, kernel_id, n, m, d))
+
+    def close(self):
+        if self.handle:
+            _lib.load().gpx_sgp_destroy(self.handle)
+            self.handle = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:   # interpreter shutdown
+            pass
+
+
+def _changed(val, cur):
+    """Does `val` differ from the array `cur` (None: nothing there yet) in shape or in any element?"""
+    if cur is None:
+        return True
+    val = np.asarray(val)
+    return val.shape != cur.shape or bool(np.any(val != cur))
+
+
+def _chunk_arg(name, val):
+    val = int(val)
+    if val < 0 or val % 128:
+        raise ValueError("invalid value for %s: %d (0, or a multiple of 128)" % (name, val))
+    return val
+
+
+class SparseGP(object):
+    r"""Sparse GP regression on inducing points.
+
+    Parameters
+    ----------
+    K : one of the built-in kernels (`GaussianKernel`, `PeriodicKernel`, `GaussianARDKernel`)
+    x : ``(n,)`` or ``(n, d)`` input locations;  y : ``(n,)`` observations
+    s : standard deviation of the observation noise, ``> 0`` (the bound divides by :math:`s^2`)
+    z : ``(M,)`` or ``(M, d)`` inducing inputs, ``M >= 1`` (`subset_inducing` picks rows of `x`)
+    jitter : added to the diagonal of ``K(z, z)``; ``None`` is ``sqrt(eps_dtype) * k(0)``
+    chunk_cols : columns of `x` per device chunk of the fit, 0 (automatic) or a multiple of 128
+    """
+
+    def __init__(self, K, x, y, s, z, jitter=None, dtype="float64", device=None, chunk_cols=0):
+        if getattr(K, "_native_kernel", None) is None:
+            raise NotImplementedError("SparseGP needs a built-in kernel (GaussianKernel, PeriodicKernel, GaussianARDKernel): "
+                                      "plugin kernels are not supported")
+        self.K = K
+        self._x = self._y = self._z = self._s = None
+        self._dtype = _DTYPES[dtype]
+        self._device = device
+        self._dev = None
+        self._version = 0          # bumped by every invalidation
+        self._data_version = 0     # bumped when x, y or z change
+        self._memoized = {}
+        self._jitter = None
+        self._chunk_cols = 0
+        self.x = x
+        self.y = y
+        self.z = z
+        self.s = s
+        self.jitter = jitter
+        self.chunk_cols = chunk_cols
+
+    # ---- invalidation: GP's scheme ----
+    def _invalidate(self, data=False):
+        self._memoized = {}
+        self._version += 1
+        if data:
+            self._data_version += 1
+
+    @property
+    def x(self):
+        return self._x
+
+    @x.setter
+    def x(self, val):
+        if _changed(val, self._x):
+            arr = np.array(val, copy=True, dtype=DTYPE)
+            if arr.ndim not in (1, 2) or arr.shape[0] < 1:
+                raise ValueError("invalid shape for x: %s" % str(arr.shape))
+            _check_finite(arr)
+            self._invalidate(data=True)
+            self._x = arr
+            self._x.flags.writeable = False
+
+    @property
+    def y(self):
+        return self._y
+
+    @y.setter
+    def y(self, val):
+        if _changed(val, self._y):
+            arr = np.array(val, copy=True, dtype=DTYPE)
+            if arr.shape != (self._x.shape[0],):
+                raise ValueError("invalid shape for y: %s" % str(arr.shape))
+            _check_finite(arr)
+            self._invalidate(data=True)
+            self._y = arr
+            self._y.flags.writeable = False
+
+    @property
+    def z(self):
+        r"""Inducing inputs, read-only float64 copy, in the shape they were given."""
+        return self._z
+
+    @z.setter
+    def z(self, val):
+        if _changed(val, self._z):
+            arr = np.array(val, copy=True, dtype=DTYPE)
+            d = 1 if arr.ndim == 1 else (arr.shape[1] if arr.ndim == 2 else -1)
+            if arr.ndim not in (1, 2) or d != self._d:
+                raise ValueError("invalid shape for z: %s (x has %d dimension(s))" % (str(arr.shape), self._d))
+            if arr.shape[0] < 1:
+                raise ValueError("need at least one inducing point (M >= 1)")
+            _check_finite(arr)
+            self._invalidate(data=True)
+            self._z = arr
+            self._z.flags.writeable = False
+
+    @property
+    def s(self):
+        return self._s
+
+    @s.setter
+    def s(self, val):
+        if not (val > 0) or not np.isfinite(val):
+            raise ValueError("invalid value for s: %s (the bound divides by s^2: s > 0)" % val)
+        if val != self._s:
+            self._invalidate()
+            self._s = DTYPE(val)
+
+    @property
+    def jitter(self):
+        r"""The value in force: the one given, or ``sqrt(eps_dtype) * k(0)`` from the kernel's current parameters."""
+        return self._auto_jitter() if self._jitter is None else self._jitter
+
+    @jitter.setter
+    def jitter(self, val):
+        if val is not None:
+            val = float(val)
+            if not (val >= 0.0) or not np.isfinite(val):
+                raise ValueError("invalid value for jitter: %s (None, or a finite number >= 0)" % val)
+        if val != self._jitter:
+            self._invalidate()
+            self._jitter = val
+
+    @property
+    def chunk_cols(self):
+        return self._chunk_cols
+
+    @chunk_cols.setter
+    def chunk_cols(self, val):
+        val = _chunk_arg("chunk_cols", val)
+        if val != self._chunk_cols:
+            self._invalidate()
+            self._chunk_cols = val
+
+    @property
+    def params(self):
+        r"""``(kernel parameters..., s)``, as `GP.params`."""
+        kp = self.K.params
+        out = np.empty(kp.size + 1)
+        out[:-1] = kp
+        out[-1] = self._s
+        return out
+
+    @params.setter
+    def params(self, val):
+        if np.any(self.params != val):
+            self._invalidate()
+            self.K.params = val[:-1]
+            self.s = val[-1]
+
+    def set_param(self, name, val):
+        if name == "s":
+            self.s = val
+            return
+        if getattr(self.K, name) != val:
+            self._invalidate()
+            self.K.set_param(name, val)
+
+    @property
+    def n_inducing(self):
+        return self._z.shape[0]
+
+    @property
+    def _n(self):
+        return self._x.shape[0]
+
+    @property
+    def _d(self):
+        return 1 if self._x.ndim == 1 else self._x.shape[1]
+
+    def _auto_jitter(self):
+        eps = np.finfo(np.float64 if self._dtype == _lib.F64 else np.float32).eps
+        return float(np.sqrt(eps) * np.max(self.K.diag(self._z[:1])))
+
+    @staticmethod
+    def subset_inducing(x, M, seed=0):
+        r"""`M` distinct rows of `x`, in the order ``numpy.random.RandomState(seed).permutation(n)[:M]`` gives: a pure
+        function of ``(x.shape, M, seed)`` where the choice of rows is concerned."""
+        x = np.asarray(x)
+        M = int(M)
+        if x.ndim not in (1, 2):
+            raise ValueError("invalid shape for x: %s" % str(x.shape))
+        if M < 1 or M > x.shape[0]:
+            raise ValueError("invalid value for M: %d (1 .. %d)" % (M, x.shape[0]))
+        return np.array(x[np.random.RandomState(seed).permutation(x.shape[0])[:M]], dtype=DTYPE)
+
+    # ---- device plumbing ----
+    def _state(self):
+        kid = self.K._native_kernel
+        if kid == _lib.KERNEL_GAUSSIAN_ARD and self._d != self.K.d:
+            raise ValueError("x has %d dimension(s), the kernel has %d width(s)" % (self._d, self.K.d))
+        key = (self._dtype, kid, self._n, self.n_inducing, self._d, self._device)
+        if self._dev is None or self._dev.key != key:
+            if self._dev is not None:
+                self._dev.close()
+            self._dev = _SparseState(*key)
+        st = self._dev
+        if st.data_version != self._data_version:
+            xs, ys, zs = (np.ascontiguousarray(a, dtype=DTYPE) for a in (self._x, self._y, self._z))
+            _lib.check(_lib.load().gpx_sgp_set_data(st.handle, _lib.dptr(xs), _lib.dptr(ys), _lib.dptr(zs)))
+            st.data_version = self._data_version
+            st.fit_version = -1
+        return st
+
+    def _fit(self):
+        """Make the device state current: one device fit serves `elbo` and every prediction."""
+        st = self._state()
+        if st.fit_version == self._version:
+            return st
+        p = np.ascontiguousarray(self.K.params, dtype=DTYPE)
+        stage, pivot = ctypes.c_int(0), ctypes.c_int(0)
+        _lib.check(_lib.load().gpx_sgp_fit(st.handle, _lib.dptr(p), float(self._s), float(self.jitter), self._chunk_cols,
+                                           ctypes.byref(stage), ctypes.byref(pivot)))
+        st.stage, st.pivot = stage.value, pivot.value
+        st.fit_version = self._version
+        return st
+
+    def _fit_pd(self):
+        st = self._fit()
+        if st.stage != 0:
+            raise np.linalg.LinAlgError("stage %d of the sparse fit (%s): %d-th leading minor of the array is not positive definite"
+                                        % (st.stage, _STAGE_NAMES[st.stage], st.pivot))
+        return st
+
+    def _elbo_and_terms(self):
+        if "elbo" not in self._memoized:
+            st = self._fit()
+            if st.stage != 0:
+                self._memoized["elbo"] = (DTYPE(-np.inf), dict((k, DTYPE(np.nan)) for k in ELBO_TERMS))
+            else:
+                out, terms = ctypes.c_double(0.0), np.empty(5, dtype=DTYPE)
+                _lib.check(_lib.load().gpx_sgp_elbo(st.handle, ctypes.byref(out), _lib.dptr(terms)))
+                self._memoized["elbo"] = (DTYPE(out.value), dict(zip(ELBO_TERMS, terms)))
+        return self._memoized["elbo"]
+
+    @property
+    def elbo(self):
+        r"""Titsias' lower bound on the log marginal likelihood, float64; ``-inf`` when either factorisation fails."""
+        return self._elbo_and_terms()[0]
+
+    @property
+    def elbo_terms(self):
+        r"""The five terms of `elbo` (they sum to it): ``logdet`` :math:`-\sum \log \mathrm{diag} L_B`, ``noise``
+        :math:`-\frac N2 \log 2\pi - N \log s`, ``fit`` :math:`-y^\top y / 2s^2`, ``quad`` :math:`c^\top c / 2s^2`,
+        ``trace`` :math:`-(\sum_i k(x_i, x_i) - \mathrm{tr} X) / 2s^2`."""
+        return dict(self._elbo_and_terms()[1])
+
+    def _get(self, which):
+        if which not in self._memoized:
+            st = self._fit_pd()
+            M = self.n_inducing
+            out = np.empty(M if which in ("c", "b") else (M, M), dtype=DTYPE)
+            args = [_lib.dptr(out) if k == which else None for k in ("Luu", "LB", "c", "Phi", "b")]
+            _lib.check(_lib.load().gpx_sgp_get(st.handle, *args))
+            self._memoized[which] = out
+        return self._memoized[which]
+
+    @property
+    def Luu(self):
+        r"""Lower Cholesky factor of ``K(z, z) + jitter I``, ``(M, M)``."""
+        return self._get("Luu")
+
+    @property
+    def LB(self):
+        r"""Lower Cholesky factor of :math:`B = I + L_{uu}^{-1} \Phi L_{uu}^{-\top} / s^2`, ``(M, M)``."""
+        return self._get("LB")
+
+    @property
+    def c(self):
+        r""":math:`L_B^{-1} L_{uu}^{-1} K(z, x) y / s`, ``(M,)``."""
+        return self._get("c")
+
+    @property
+    def Phi(self):
+        r"""Lower triangle of :math:`K(z, x) K(x, z)`, ``(M, M)``, zero above the diagonal."""
+        return self._get("Phi")
+
+    @property
+    def b(self):
+        r""":math:`K(z, x) y`, ``(M,)``."""
+        return self._get("b")
+
+    # ---- predictions ----
+    def _xo(self, xo):
+        xo = np.ascontiguousarray(xo, dtype=DTYPE)
+        d = 1 if xo.ndim == 1 else (xo.shape[1] if xo.ndim == 2 else -1)
+        if xo.ndim not in (1, 2) or d != self._d:
+            raise ValueError("invalid shape for xo: %s" % str(xo.shape))
+        return xo, xo.shape[0]
+
+    def mean(self, xo):
+        r"""Predictive mean :math:`k(x^*, z) L_{uu}^{-\top} L_B^{-\top} c / s`, ``(m,)``: one fused device pass."""
+        xo, m = self._xo(xo)
+        st = self._fit_pd()
+        out = np.empty(m, dtype=DTYPE)
+        _lib.check(_lib.load().gpx_sgp_mean(st.handle, _lib.dptr(xo), m, _lib.dptr(out)))
+        return out
+
+    def var(self, xo, noise=False, chunk_rows=0):
+        r"""Predictive variance, the diagonal of `cov(xo)`, ``(m,)``, in row chunks of `xo` (``chunk_rows``: 0 or a
+        multiple of 128).  ``noise=True`` adds :math:`s^2`.  Not clamped at zero."""
+        xo, m = self._xo(xo)
+        chunk_rows = _chunk_arg("chunk_rows", chunk_rows)
+        st = self._fit_pd()
+        out = np.empty(m, dtype=DTYPE)
+        _lib.check(_lib.load().gpx_sgp_var(st.handle, _lib.dptr(xo), m, chunk_rows, _lib.dptr(out)))
+        if noise:
+            out += self._s ** 2
+        return out
+
+    def predict(self, xo, noise=False):
+        r"""``(mean(xo), var(xo, noise))``."""
+        xo, _ = self._xo(xo)
+        return self.mean(xo), self.var(xo, noise=noise)
+
+    def cov(self, xo):
+        r"""Predictive covariance :math:`K(x^*, x^*) - V_1^\top V_1 + V_2^\top V_2`, ``(m, m)``."""
+        xo, m = self._xo(xo)
+        st = self._fit_pd()
+        out = np.empty((m, m), dtype=DTYPE)
+        _lib.check(_lib.load().gpx_sgp_cov(st.handle, _lib.dptr(xo), m, _lib.dptr(out)))
+        return out
+
+    def fit_timing(self):
+        """Milliseconds of the last device fit (HIP events on the handle's stream): Kuu and its factor, the chunks' kernel
+        builds, the chunks' Gram products (with b and the slice sum), the M x M tail, total."""
+        st = self._fit()
+        ms = (ctypes.c_float * 5)()
+        _lib.check(_lib.load().gpx_sgp_last_timing(st.handle, ms))
+        return dict(zip(("kuu", "build", "gram", "tail", "total"), list(ms)))
+
+
+def _check_finite(a):
+    if not np.isfinite(a).all():
+        raise ValueError("array must not contain infs or NaNs")

@@ -178,6 +178,7 @@ int gpx_stream_wait_event(void *stream, void *event);
 #define GPX_PROF_KAPPLY      16 /* stream_apply_kernel + its slice reduction (gpx_d_kmat_apply, fused route): kernel evaluations m*n per group of weight vectors */
 #define GPX_PROF_KAPPLY_GRAD 17 /* stream_apply_grad_kernel + its slice reduction (gpx_d_kmat_apply_grad): kernel evaluations m*n per group of weight vectors and window of dimensions */
 #define GPX_PROF_CHOL_DELETE 18 /* del_copy_rows_kernel + del_block_kernel (gpx_d_chol_delete), ONE record per call around all of its launches: bytes read + written */
+#define GPX_PROF_SPARSE_GRAM 19 /* gpx_sgp_fit: the Gram product K(z, x_c) K(x_c, z) of ONE chunk, one record around all of its slice products; flops 2 c per element of the lower triangle.  (The product kernel's own launches are recorded under their classes as well.) */
 int gpx_prof_enable(int on);    /* also clears the registry */
 int gpx_prof_read(int cls, double *launches, double *total_ms, double *total_work);
 
@@ -210,6 +211,7 @@ int gpx_prof_read(int cls, double *launches, double *total_ms, double *total_wor
 #define GPX_ROUTE_KAPPLY_GEMM    22   /* gpx_d_kmat_apply: gpx_d_kmat into scratch, then gpx_d_gemm_nt; one hit per row chunk of xo  */
 #define GPX_ROUTE_PATHS_GRAD_CHUNK 23 /* gpx_paths_grad: one hit per row chunk of xo                                                   */
 #define GPX_ROUTE_REMOVE         24   /* gpx_gp_remove: one hit per call                                               */
+#define GPX_ROUTE_SPARSE_CHUNK   25   /* gpx_sgp_fit: one hit per column chunk of x                                   */
 int gpx_debug_route_count(int route, int64_t *count);
 /* roctx ranges pushed so far (GPX_ROCTX=1: every gpx_gp_* call and every launch class below it is a nested host range for
  * `rocprofv3 --marker-trace`; libroctx64.so is loaded on first use; 0 while the switch is off) */
@@ -757,6 +759,87 @@ int gpx_paths_describe(gpx_paths_t *paths, int *dtype, int *kernel, int64_t *n, 
  * [3] total; zeros for S == 0 */
 int gpx_debug_paths_timing(gpx_paths_t *paths, float *ms4);
 int gpx_paths_destroy(gpx_paths_t *paths);
+
+/* ------------------------------------------- sparse GP on inducing points -- */
+/* Titsias' collapsed bound (2009; "SGPR") on M inducing inputs z: O(N M^2) time, O(M^2 + M chunk) memory, nothing N x N.
+ * One formulation (DESIGN 3.3 "Sparse GP on inducing points"), s the noise standard deviation, eps the jitter:
+ *   Kuu = K(z, z) + eps I = Luu Luu^T        Phi = sum_c K(z, x_c) K(x_c, z)      b = sum_c K(z, x_c) y_c
+ *   X = Luu^-1 Phi Luu^-T                    B = I + X / s^2 = LB LB^T            c = LB^-1 Luu^-1 b / s
+ *   elbo = [-sum log diag LB] + [-N/2 log 2 pi - N log s] + [-yy / (2 s^2)] + [c.c / (2 s^2)] + [-(kff - tr X) / (2 s^2)]
+ *          terms5:  0 log-det        1 noise                  2 data fit        3 quadratic       4 trace
+ *   mean(a) = k(a, z) w,  w = Luu^-T LB^-T c / s
+ *   var(a)  = k(a, a) - |Luu^-1 k(z, a)|^2 + |LB^-1 Luu^-1 k(z, a)|^2      cov likewise with the two blocks' products
+ * Kuu + Phi / s^2 is never factored: log|A| - log|Kuu| cancels badly, B is well conditioned.
+ * The handle keeps x (N, d), y, z (M, d) in HBM in its dtype and makes its device current in every call, as gpx_gp_t does;
+ * every call is synchronous.  All three kernel families (the ARD family on points scaled by gpx_d_scale_points at fit time),
+ * every d gpx_d_kmat takes, both dtypes.  b, yy, kff, tr X and the scalars of the bound are DOUBLE for both dtypes. */
+typedef struct gpx_sgp gpx_sgp_t;
+int gpx_sgp_create(gpx_sgp_t **h, int dtype, int kernel, int64_t n, int64_t m_inducing, int d);
+int gpx_sgp_destroy(gpx_sgp_t *h);
+/* x: (n, d), y: (n,), z: (m_inducing, d), HOST float64 (converted on upload); any of them NULL: that array is kept.
+ * Forgets the fit. */
+int gpx_sgp_set_data(gpx_sgp_t *h, const double *x, const double *y, const double *z);
+/* The fit, on the handle's stream:
+ *   1. Kuu (gpx_d_kmat, lower, diag_add = jitter), gpx_d_potrf.  A non-zero info: *stage = 1, *pivot = it, and the call returns.
+ *   2. the chunk loop over columns of x, chunk_cols wide (0: automatic -- gpx_debug_sgp_plan; else a multiple of 128), one
+ *      GPX_ROUTE_SPARSE_CHUNK hit each:  G = K(z, x_c) (M x c, ld = the chunk width) by gpx_d_kmat;  G G^T on the lower tiles
+ *      by the product kernel's batched launch as a split over the depth (slices of the plan's width; slice p of every chunk
+ *      adds to partial accumulator p; the ragged last slice of the last chunk is a call of its own), GPX_PROF_SPARSE_GRAM
+ *      around each chunk's products;  b += G y_c (gpx_d_gemv_acc).  Then the partials are summed in slice order
+ *      (gpx_d_sum_slices_lower).  No atomics anywhere: a repeated fit gives the same bits.
+ *   3. the M x M tail: gpx_d_mirror_lower, gpx_d_trsm_right_lt, gpx_d_transpose, gpx_d_trsm_right_lt (X);
+ *      gpx_d_sgp_form_B (B lower and tr X); gpx_d_potrf (a non-zero info: *stage = 2); two gpx_d_trsv_lower for c, two
+ *      more for w; gpx_d_logdet_chol, gpx_d_dot.
+ * params as gpx_gp_set_params; s > 0; jitter >= 0, finite.  *stage = *pivot = 0 after a good fit.  The status is GPX_OK
+ * whether or not a factorisation failed (the matrix is the caller's); GPX_ERR_INTERNAL as gpx_gp_fit. */
+int gpx_sgp_fit(gpx_sgp_t *h, const double *params, double s, double jitter, int64_t chunk_cols, int *stage, int *pivot);
+/* stage and pivot of the last fit (both 0: fitted and positive definite) */
+int gpx_sgp_info(gpx_sgp_t *h, int *stage, int *pivot);
+/* the bound and its five terms (terms5 may be NULL); -inf and NaN terms when a factorisation failed */
+int gpx_sgp_elbo(gpx_sgp_t *h, double *elbo, double *terms5);
+/* predictions at xo (m, d) HOST float64 -> HOST float64.  GPX_ERR_ARG when the last fit's stage is non-zero.
+ * mean: one gpx_d_mean pass against z with w.  var (m,): row chunks as gpx_gp_var (chunk_rows 0 or a multiple of 128, one
+ * GPX_ROUTE_VAR_CHUNK hit each): V = K(xo_c, z), V <- V Luu^-T, W <- V LB^-T, gpx_d_var_rows2; not clamped at zero.
+ * cov (m, m): K(xo, xo) - V V^T + W W^T by gpx_d_gemm_nt. */
+int gpx_sgp_mean(gpx_sgp_t *h, const double *xo, int64_t m, double *out);
+int gpx_sgp_var(gpx_sgp_t *h, const double *xo, int64_t m, int64_t chunk_rows, double *out);
+int gpx_sgp_cov(gpx_sgp_t *h, const double *xo, int64_t m, double *out);
+/* the fit's state as HOST float64, for tests and inspection: Luu, LB (M x M dense, zero upper triangle), c (M), Phi (M x M,
+ * lower triangle, zero above), b (M); any pointer may be NULL.  After a stage-1 failure only Luu's leading columns mean
+ * anything; after stage 2 everything but LB and c. */
+int gpx_sgp_get(gpx_sgp_t *h, double *Luu, double *LB, double *c, double *Phi, double *b);
+/* milliseconds of the last fit (HIP events on the handle's stream): [0] Kuu + its factor [1] the chunks' kernel builds
+ * [2] the chunks' Gram products, b and the slice sum [3] the M x M tail [4] total */
+int gpx_sgp_last_timing(gpx_sgp_t *h, float *ms5);
+/* Depth slices per chunk for later fits of this handle: 0 = the plan's (the default), P >= 1 = exactly that many (1: one
+ * plain product per chunk).  For measurements (tools/sparse_bench.py); results differ in the last bits between values. */
+int gpx_sgp_set_split(gpx_sgp_t *h, int slices);
+/* host arithmetic only: the plan of a fit -- columns per chunk, chunks, depth slices per full chunk and their width.
+ * chunk_cols 0: the largest multiple of 128, at most 16384, whose M x c block fits a quarter of free_bytes; one chunk of
+ * round_up(n, 128) when n is within it.  slices: P = as many as make tiles x P cover 256 workgroups (tiles = the 128 x 128
+ * tiles of the lower triangle), at least 8, at most 16, and no more than keep the partial accumulators within 2 GiB -- a
+ * function of (m_inducing, dtype) alone; split > 0 replaces P.  No slice is narrower than 128 columns: the width is the
+ * chunk's share cols / P rounded up to 128, *slices = cdiv(cols, width) <= P. */
+int gpx_debug_sgp_plan(int dtype, int64_t n, int64_t m_inducing, int64_t chunk_cols, int split, size_t free_bytes,
+                       int64_t *cols, int64_t *chunks, int *slices, int64_t *slice_cols);
+/* The new kernels, one building block each (DEVICE pointers, `dtype` unless said otherwise; fixed order, no atomics).
+ * gpx_d_sum_slices_lower: out[i, j] = sum_p P[p sP + i ldp + j] for j <= i < n, p ascending, summed in f64, rounded once;
+ *   the strict upper triangle of out is not written.
+ * gpx_d_gemv_acc: acc[i] += sum_j G[i, j] y[j]  for i < rows, j < cols; acc DOUBLE; one workgroup per row, f64 sums.
+ * gpx_d_mirror_lower: A[j, i] = A[i, j] for j < i < n.
+ * gpx_d_transpose: out[j, i] = in[i, j] for i, j < n; out != in.
+ * gpx_d_sgp_form_B: B[i, j] = (i == j) + X[i, j] / s^2 for j <= i < n (upper not written); trace_dev[0] = sum_i X[i, i]
+ *   (DOUBLE, one workgroup, fixed order).
+ * gpx_d_var_rows2: out_dev[i] = kdiag(i) - sum_j V[i, j]^2 + sum_j W[i, j]^2 -- gpx_d_var_rows' contract (kdiag from the
+ *   kernel family at xo[i], f64 sums, out DOUBLE) with a second block of the same shape and pitch; not clamped.  The row sums
+ *   go through a block of `rows` doubles that the call allocates: it waits for the stream before it returns. */
+int gpx_d_sum_slices_lower(int dtype, const void *P, int64_t ldp, int64_t sP, int slices, int64_t n, void *out, int64_t ldo, void *stream);
+int gpx_d_gemv_acc(int dtype, const void *G, int64_t rows, int64_t cols, int64_t ldg, const void *y, double *acc_dev, void *stream);
+int gpx_d_mirror_lower(int dtype, void *A, int64_t n, int64_t lda, void *stream);
+int gpx_d_transpose(int dtype, const void *in, int64_t ldi, void *out, int64_t ldo, int64_t n, void *stream);
+int gpx_d_sgp_form_B(int dtype, const void *X, int64_t ldx, int64_t n, double s, void *B, int64_t ldb, double *trace_dev, void *stream);
+int gpx_d_var_rows2(int dtype, int kernel, const void *V, const void *W, int64_t rows, int64_t n, int64_t ldx, const void *xo, int d,
+                    const double *params, double *out_dev, void *stream);
 
 /* ------------------------------------------------------------- multi-GPU -- */
 /* One GP spread over the GPUs of a node, one PROCESS per GPU (north-star; SURVEY 8e -- the reference has

@@ -1,0 +1,179 @@
+"""GPU tests of SparseGP (gpx_sgp_*, csrc/gpx_sparse.hip) against the numpy restatement of tests/_sparse_helpers.py, which
+tests/test_sparse_cpu.py pins against the dense oracle.
+
+Tolerances.  fp64: ORACLE_TOL["float64"] of tests/test_gpu_var.py (rtol 1e-7, atol 1e-10) at jitter 1e-6 -- every case has
+cond(Kuu + eps I) <= 2e7 and cond(B) <= 100 (asserted on the CPU), so cond * eps is far inside it.  fp32: jitter=None and
+the project's fp32 ORACLE_TOL (rtol 1e-2, atol 5e-3); where the fp32 run of the restatement itself is further than that
+from the fp64 run, 4 * E32 (the device sums in another order than numpy).  With the cases as they stand no E32 exceeds the
+fp32 atol (the largest: LB 1.3e-3 and c 1.1e-3 of gaussian (777, 1, 24), LB 1.2e-3 and trace 1.5e-3 of periodic
+(777, 1, 64); tests/test_sparse_cpu.py prints all of them), so the floor decides nothing at present.
+Two device evaluations of one quantity are compared at 1e-10 * max|ref| (tests/_extend_helpers.close)."""
+import numpy as np
+import pytest
+
+import gaussian_processes_amd as gp
+from gaussian_processes_amd import _lib
+from test_gpu_var import ORACLE_TOL
+from _extend_helpers import close
+from _sparse_helpers import (CASES, CASE_IDS, E32, QUANTITIES, S_NOISE, TERMS, case_data, case_jitter, make_kernel, quantities,
+                             reference)
+
+pytestmark = pytest.mark.gpu
+
+NP_DTYPE = {"float64": np.float64, "float32": np.float32}
+
+
+def _chunks(N, chunk_cols):
+    return 1 if chunk_cols == 0 else -(-N // chunk_cols)          # automatic: every test case fits one chunk
+
+
+def _sparse(case, dtype="float64", chunk_cols=0, jitter="case"):
+    kind, N, d, M = case
+    _, x, y, z, _, _ = case_data(case)
+    if jitter == "case":
+        jitter = case_jitter(case, NP_DTYPE[dtype]) if dtype == "float64" else None
+    return gp.SparseGP(make_kernel(kind, d), x, y, S_NOISE, z, jitter=jitter, dtype=dtype, chunk_cols=chunk_cols)
+
+
+def _device_quantities(sg, xo):
+    out = {"elbo": sg.elbo, "Luu": sg.Luu, "LB": sg.LB, "c": sg.c, "mean": sg.mean(xo), "var": sg.var(xo), "cov": sg.cov(xo)}
+    out.update(sg.elbo_terms)
+    return {k: np.asarray(v, dtype=np.float64) for k, v in out.items()}
+
+
+@pytest.mark.parametrize("chunk_cols", [128, 0])
+@pytest.mark.parametrize("dtype", ["float64", "float32"])
+@pytest.mark.parametrize("case", CASES, ids=CASE_IDS)
+def test_parity_against_the_restatement(case, dtype, chunk_cols):
+    xo = case_data(case)[4]
+    sg = _sparse(case, dtype, chunk_cols)
+    assert np.isclose(sg.jitter, case_jitter(case, NP_DTYPE[dtype]), rtol=1e-6, atol=0.0)     # (k(0) from the kernel class / from the oracle)
+    _lib.route_reset()
+    got = _device_quantities(sg, xo)
+    assert _lib.route_count(_lib.ROUTE_SPARSE_CHUNK) == _chunks(case[1], chunk_cols)     # one fit, this many chunks
+    ref = quantities(reference(case, sg.jitter))
+    tol = ORACLE_TOL[dtype]
+    bad = []
+    for name in QUANTITIES:
+        g, r = got[name], ref[name]
+        assert g.shape == r.shape, name
+        err = np.abs(g - r)
+        bound = tol["atol"] + tol["rtol"] * np.abs(r)
+        floor = 4.0 * E32[case][name] if dtype == "float32" else 0.0
+        worst = float((err - np.maximum(bound, floor)).max())
+        print("%-6s max err %.3e  (max |ref| %.3e, 4 E32 %.3e)%s" % (name, err.max(), np.abs(r).max(), floor, "  <-- FAILS" if worst > 0 else ""))
+        if not worst <= 0:
+            bad.append(name)
+    assert not bad, "beyond tolerance: %s" % ", ".join(bad)
+    assert set(sg.elbo_terms) == set(TERMS)
+    assert abs(sum(sg.elbo_terms[k] for k in TERMS) - sg.elbo) <= 1e-12 * abs(sg.elbo)
+
+
+@pytest.mark.parametrize("case", CASES, ids=CASE_IDS)
+def test_var_is_the_diagonal_of_cov_and_chunks_agree(case):
+    _, _, _, _, xo, xo300 = case_data(case)
+    _lib.route_reset()
+    sg = _sparse(case)
+    cov = sg.cov(xo)
+    close(sg.var(xo), np.diag(cov))
+    assert _lib.route_count(_lib.ROUTE_VAR_CHUNK) == 1
+    whole = sg.var(xo300)
+    assert _lib.route_count(_lib.ROUTE_VAR_CHUNK) == 2
+    chunked = sg.var(xo300, chunk_rows=128)
+    assert _lib.route_count(_lib.ROUTE_VAR_CHUNK) == 2 + 3          # 128 + 128 + 44 rows
+    close(chunked, whole)
+    close(whole[:len(xo)], np.diag(cov))
+    assert np.array_equal(sg.var(xo, noise=True), sg.var(xo) + S_NOISE ** 2)
+    mean, var = sg.predict(xo, noise=True)
+    assert np.array_equal(mean, sg.mean(xo)) and np.array_equal(var, sg.var(xo, noise=True))
+    assert _lib.route_count(_lib.ROUTE_SPARSE_CHUNK) == 1            # all of it from one fit
+
+
+@pytest.mark.parametrize("case", CASES, ids=CASE_IDS)
+def test_chunking_does_not_change_the_model(case):
+    xo = case_data(case)[4]
+    a, b = _sparse(case, chunk_cols=128), _sparse(case, chunk_cols=0)
+    close(a.elbo, b.elbo)
+    close(a.c, b.c)
+    close(a.mean(xo), b.mean(xo))
+
+
+@pytest.mark.parametrize("dtype", ["float64", "float32"])
+@pytest.mark.parametrize("case,chunk_cols", [(CASES[1], 0), (CASES[2], 128)], ids=["gaussian-2000-auto", "ard-1000-128"])
+def test_repeated_fits_are_bitwise_identical(case, chunk_cols, dtype):
+    xo = case_data(case)[4]
+    a, b = _sparse(case, dtype, chunk_cols), _sparse(case, dtype, chunk_cols)
+    assert a.elbo == b.elbo
+    for name in ("Phi", "c", "b"):
+        assert np.array_equal(getattr(a, name), getattr(b, name)), name
+    assert np.array_equal(a.mean(xo), b.mean(xo))
+    assert np.array_equal(np.triu(a.Phi, 1), np.zeros_like(a.Phi))
+
+
+def test_inducing_points_at_the_data_give_the_dense_gp():
+    """z = x at jitter 1.5e-8 on (300, 3): the bound against the dense device GP's log_lh, within 1e-4 absolute (where that
+    number comes from: tests/test_sparse_cpu.py::test_z_equal_x_is_the_dense_gp)."""
+    case = CASES[5]
+    _, x, y, z, xo, _ = case_data(case)
+    sg = _sparse(case, jitter=1.5e-8)
+    dense = gp.GP(make_kernel(case[0], case[2]), x, y, s=S_NOISE)
+    print("elbo %.9f  dense log_lh %.9f" % (sg.elbo, dense.log_lh))
+    assert abs(sg.elbo - dense.log_lh) <= 1e-4
+    err = float(np.abs(sg.mean(xo) - dense.mean(xo)).max())
+    print("mean: max |sparse - dense| = %.3e" % err)
+    assert err <= 1e-4
+
+
+def test_failed_factorisation_is_reported_and_recovered_from():
+    case = CASES[4]
+    _, x, y, z, xo, _ = case_data(case)
+    zz = np.array(z)
+    zz[12:] = zz[:12]                # every inducing point twice: Kuu has rank 12 at jitter 0, and of the twelve pivots that
+                                     # are zero up to rounding the first that comes out <= 0 is reported (a tiny positive one
+                                     # only makes the next more negative)
+    sg = gp.SparseGP(make_kernel(case[0], case[2]), x, y, S_NOISE, zz, jitter=0.0)
+    assert sg.elbo == -np.inf
+    assert all(np.isnan(v) for v in sg.elbo_terms.values())
+    st = sg._fit()
+    assert st.stage == 1 and 13 <= st.pivot <= 24
+    for call in (sg.mean, sg.var, sg.cov):
+        with pytest.raises(np.linalg.LinAlgError, match=r"stage 1 .*%d-th leading minor" % st.pivot):
+            call(xo)
+    sg.z = z                                                         # a good fit on the same object
+    sg.jitter = case_jitter(case, np.float64)
+    fresh = _sparse(case)
+    assert sg.elbo == fresh.elbo and np.isfinite(sg.elbo)
+    assert np.array_equal(sg.mean(xo), fresh.mean(xo))
+
+
+def test_setters_refit_and_nothing_else_does():
+    case = CASES[0]
+    kind, N, d, M = case
+    params, x, y, z, xo, _ = case_data(case)
+    sg = _sparse(case)
+    _lib.route_reset()
+    sg.elbo, sg.mean(xo), sg.var(xo), sg.cov(xo), sg.Luu, sg.c, sg.elbo_terms, sg.fit_timing()
+    sg.s, sg.z, sg.params, sg.jitter = sg.s, sg.z.copy(), sg.params.copy(), sg.jitter      # nothing changes
+    sg.mean(xo), sg.elbo
+    assert _lib.route_count(_lib.ROUTE_SPARSE_CHUNK) == 1
+    jit = case_jitter(case, np.float64)
+
+    sg.s = 0.7
+    fresh = gp.SparseGP(make_kernel(kind, d), x, y, 0.7, z, jitter=jit)
+    assert sg.elbo == fresh.elbo and np.array_equal(sg.mean(xo), fresh.mean(xo))
+    assert _lib.route_count(_lib.ROUTE_SPARSE_CHUNK) == 3
+
+    p = sg.params
+    p[1] *= 1.25
+    sg.params = p
+    fresh = gp.SparseGP(gp.GaussianKernel(p[0], p[1]), x, y, 0.7, z, jitter=jit)
+    assert sg.elbo == fresh.elbo and np.array_equal(sg.mean(xo), fresh.mean(xo))
+
+    z2 = gp.SparseGP.subset_inducing(x, 77, seed=11)
+    sg.z = z2
+    fresh = gp.SparseGP(gp.GaussianKernel(p[0], p[1]), x, y, 0.7, z2, jitter=jit)
+    assert sg.n_inducing == 77 and sg.Luu.shape == (77, 77)
+    assert sg.elbo == fresh.elbo and np.array_equal(sg.mean(xo), fresh.mean(xo))
+    t = sg.fit_timing()
+    assert set(t) == {"kuu", "build", "gram", "tail", "total"} and all(v >= 0 for v in t.values())
+    assert t["total"] >= max(t["kuu"], t["build"], t["gram"], t["tail"])
