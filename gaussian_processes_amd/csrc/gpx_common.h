@@ -299,11 +299,19 @@ int kmat_apply(int dtype, int kernel, const void *xo, int64_t m, const void *x, 
 // memory one chunk needs.  chunk_rows 0: the largest multiple of 128 (at most var_chunk_cap) whose buffers fit a quarter
 // of free_bytes.  GPX_ERR_ARG / GPX_ERR_NOMEM as gpx_debug_var_plan documents.
 int var_plan(int dtype, int64_t n, int64_t m, int64_t chunk_rows, size_t free_bytes, int64_t *rows, int64_t *chunks, size_t *bytes);
-int dloglh_reduce(int dtype, int kernel, const void *x, int64_t n, int d, const double *params,
-                  const void *alpha, const void *W, int64_t ldw, double *partial_dev, double *out4,
-                  hipStream_t st);
-// The Gaussian ARD family (gpx_kmat.hip): out <- x / w (w_host: d doubles; out may be x); the gradient's pass over W = K^-1
-// on the scaled points xs with iso = (h / sqrt(wbar), 1): out (host, d + 2) = [S_0, S_1 .. S_d, trace W].
+// The fused hyper-parameter gradient pass (gpx_kmat.hip): sum_ab G_ab dK_p(x_a, x_b) with the kernel derivatives formed on
+// the fly, M's lower triangle read once; out4 (host) = [P0, P1, P2, trace M].  vec_b == nullptr: the marginal likelihood,
+// G = a a^T - M (a = alpha, M = K^-1); otherwise the leave-one-out criterion, G = (b a^T + a b^T) / 2 - M (b = r,
+// M = Pm = K^-1 diag(c) K^-1).  tile_reduce_ard: the same on the Gaussian ARD family's scaled points xs with
+// iso = (h / sqrt(wbar), 1): out (host, d + 2) = [S_0, S_1 .. S_d, trace M].
+// grad_from_sums: either pass's sums -> the gradient (kernel params ..., s); `factor` 1/2 (marginal likelihood) or 1 (LOO).
+int tile_reduce(int dtype, int kernel, const void *x, int64_t n, int d, const double *params, const void *vec_a, const void *vec_b,
+                const void *M, int64_t ldm, double *partial_dev, double *out4, hipStream_t st);
+int tile_reduce_ard(int dtype, const void *xs, int64_t n, int d, const double *iso, const void *vec_a, const void *vec_b, const void *M,
+                    int64_t ldm, double *partial_dev, double *out, hipStream_t st);
+void grad_from_sums(int kernel, int d, const double *params, const double *S, double quad, double noise_scale, double factor,
+                    double *out);
+// The Gaussian ARD family (gpx_kmat.hip): out <- x / w (w_host: d doubles; out may be x).
 // dloglh_partial_doubles: the DEVICE doubles either reduction needs for its per-workgroup partial sums.
 struct ArdWidths { double w[GPX_ARD_MAX_D]; };   // the widths as a kernel argument
 int scale_points(int dtype, const void *x, int64_t n, int d, const double *w_host, void *out, hipStream_t st);
@@ -311,17 +319,8 @@ int ard_scratch(size_t bytes, void **p);         // this host thread's block for
 // (h / sqrt(wbar), 1) of ARD parameters (h, w_1 ... w_d): wbar = exp(sum log w_k / d) in the host's double arithmetic
 void ard_iso(const double *params, int d, double *iso2);
 size_t dloglh_partial_doubles(int kernel, int d);
-int dloglh_reduce_ard(int dtype, const void *xs, int64_t n, int d, const double *iso, const void *alpha, const void *W,
-                      int64_t ldw, double *partial_dev, double *out, hipStream_t st);
 int kmat(int dtype, int kernel, int member, const void *x1, int64_t n, const void *x2, int64_t m,
          int d, const double *params, double diag_add, int tri, void *out, int64_t ld, hipStream_t st);
-// The leave-one-out criterion's passes (gpx_kmat.hip): dloglh_reduce's and dloglh_reduce_ard's arguments with a second vector
-// r and Pm = K^-1 diag(c) K^-1 (lower triangle read) where those take W; the coefficient of an entry is
-// (r_a alpha_b + alpha_a r_b) / 2 - Pm_ab and the last value of `out` is trace Pm.  The same partial-sum block.
-int dloo_reduce(int dtype, int kernel, const void *x, int64_t n, int d, const double *params, const void *alpha, const void *r,
-                const void *Pm, int64_t ldp, double *partial_dev, double *out4, hipStream_t st);
-int dloo_reduce_ard(int dtype, const void *xs, int64_t n, int d, const double *iso, const void *alpha, const void *r, const void *Pm,
-                    int64_t ldp, double *partial_dev, double *out, hipStream_t st);
 // The ingredients of the leave-one-out gradient's weights G = (r alpha^T + alpha r^T) / 2 - Pm from a factor (gpx_loograd.hip).
 // One system's vectors, all in ONE block of loo_vec_bytes() that the caller owns (loo_vecs_at lays it out):
 struct LooVecs {

@@ -906,26 +906,17 @@ static int grad_reduce(gpx_gp *g, const void *pts, const void *alpha, const doub
     const int64_t n = g->n;
     double *aa = part + dloglh_partial_doubles(g->kernel, g->d);
     GPX_TRY(dot(g->dtype, alpha, alpha, n, aa, g->st));
+    double S[GPX_ARD_MAX_D + 2], ata = 0.0;            // ARD: S_0, S_1 .. S_d, tr W; otherwise [P0, P1, P2, tr W]
     if (g->kernel == GPX_KERNEL_GAUSSIAN_ARD) {
-        // S_0, S_1 .. S_d, tr W from the device; dh = S_0 / h, dw_k = (S_k / w_k - S_0 / (d w_k)) / 2
-        const int d = g->d;
-        double iso[2], S[GPX_ARD_MAX_D + 2], ata = 0.0;
-        ard_iso(params, d, iso);
-        GPX_TRY(dloglh_reduce_ard(g->dtype, pts, n, d, iso, alpha, W, ldw, part, S, g->st));
-        GPX_HIP(hipMemcpyAsync(&ata, aa, sizeof(double), hipMemcpyDeviceToHost, g->st));
-        GPX_HIP(hipStreamSynchronize(g->st));
-        out[0] = S[0] / params[0];
-        for (int k = 0; k < d; ++k) out[1 + k] = 0.5 * (S[1 + k] / params[1 + k] - S[0] / ((double)d * params[1 + k]));
-        out[d + 1] = s_noise * (ata - S[d + 1]);
-        return GPX_OK;
+        double iso[2];
+        ard_iso(params, g->d, iso);
+        GPX_TRY(tile_reduce_ard(g->dtype, pts, n, g->d, iso, alpha, nullptr, W, ldw, part, S, g->st));
+    } else {
+        GPX_TRY(tile_reduce(g->dtype, g->kernel, pts, n, g->d, params, alpha, nullptr, W, ldw, part, S, g->st));
     }
-    double p4[4];
-    GPX_TRY(dloglh_reduce(g->dtype, g->kernel, pts, n, g->d, params, alpha, W, ldw, part, p4, g->st));
-    double ata = 0.0;
     GPX_HIP(hipMemcpyAsync(&ata, aa, sizeof(double), hipMemcpyDeviceToHost, g->st));
     GPX_HIP(hipStreamSynchronize(g->st));
-    for (int i = 0; i < g->nparams; ++i) out[i] = 0.5 * p4[i];
-    out[g->nparams] = s_noise * (ata - p4[3]);         // dK/ds = 2 s I  (gp_c.pyx:46)
+    grad_from_sums(g->kernel, g->d, params, S, ata, s_noise, 0.5, out);
     return GPX_OK;
 }
 

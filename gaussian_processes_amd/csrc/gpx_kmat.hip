@@ -312,13 +312,19 @@ int ard_scratch(size_t bytes, void **p) { return g_ard_scr.get(bytes, p); }
 
 // ---------------------------------------------------------------------------
 // Fused gradient reduction (gp/ext/gp_c.pyx:34-49 without its dense products):
-//   P[p]  = sum_{j,k} (alpha_j alpha_k - W[j,k]) * dK_p(x_j, x_k)      p < n_kp
-//   P[n_kp] = trace(W)
-// with W = K^-1 (lower triangle read; both W and dK_p are symmetric, so the sum runs over
-// the lower triangle with weight 2 off the diagonal).  The kernel derivatives are evaluated
-// on the fly from the squared distance (no n x n Jacobian is materialised).  Deterministic:
-// a fixed grid of workgroups walks the tiles in a fixed order, per-workgroup partial sums
-// are written out and added up by the host in index order.
+//   P[p]    = sum_{j,k} G_jk * dK_p(x_j, x_k)      p < n_kp
+//   P[last] = trace(M)
+// for a symmetric weight matrix G = (vectors) - M of which only M is in memory (lower triangle read; G and dK_p are
+// symmetric, so the sum runs over the lower triangle with weight 2 off the diagonal).  The kernel derivatives are
+// evaluated on the fly from the squared distance (no n x n Jacobian is materialised).  Deterministic: a fixed grid of
+// workgroups walks the tiles in a fixed order, per-workgroup partial sums are written out and added up by the host in
+// index order.  NV, the number of staged vector pairs, selects the criterion -- staging the second pair and the coefficient
+// are the ONLY text that differs, and each instantiation holds exactly one form of it:
+//   NV == 1  marginal likelihood:  G = a a^T - M,               a = alpha, M = W = K^-1
+//   NV == 2  leave-one-out (RW06 eq. 5.13 rearranged; gpx_loograd.hip has the derivation):
+//                                  G = (b a^T + a b^T) / 2 - M,  a = alpha, b = r, M = Pm = K^-1 diag(c) K^-1
+// (NV as a template parameter and not a __device__ helper around the shared text: the instantiations keep the resource
+// lines the four separate kernels had)
 // ---------------------------------------------------------------------------
 struct GradParams {
     double c1, c2h, c2w, c3w;      // gaussian: e = c1*d2 ; dK_dh = c2h*exp(e) ; dK_dw = exp(e)*(c3w*d2 - c2w)
@@ -329,309 +335,33 @@ struct GradParams {
 constexpr int GR_T = 64;           // tile edge
 constexpr int GR_BLOCKS = 1024;
 
-template <typename T>
-__global__ __launch_bounds__(256) void dloglh_reduce_kernel(const T *__restrict__ x, int64_t n, int d,
-                                                            const T *__restrict__ alpha,
-                                                            const T *__restrict__ W, int64_t ldw,
-                                                            GradParams gp, int64_t ntiles_r,
-                                                            double *__restrict__ partial)
+// The staged vectors as ONE kernel argument of NV pointers.  The NV == 1 kernels take no second pointer (and reserve no LDS
+// for one), so every instantiation has the argument layout of the kernel it replaced: with an unused `vec_b` in the list the
+// isotropic marginal-likelihood kernel was scheduled differently and measured 2 - 6 % slower.
+template <typename T, int NV> struct TileVecs { const T *a, *b; };
+template <typename T> struct TileVecs<T, 1> { const T *a; };
+template <typename T, int NV>
+static TileVecs<T, NV> tile_vecs(const void *vec_a, const void *vec_b)
 {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    T *s1 = reinterpret_cast<T *>(smem_raw);          // [GR_T][d]   rows
-    T *s2 = s1 + (size_t)GR_T * d;                    // [d][GR_T]   columns, transposed
-    T *sa1 = s2 + (size_t)GR_T * d;                   // alpha rows
-    T *sa2 = sa1 + GR_T;                              // alpha cols
-    __shared__ double red[4][4];
-    const int tid = threadIdx.x, col = tid & 63, rg = tid >> 6;
-    double acc[4] = {0.0, 0.0, 0.0, 0.0};             // up to 3 kernel params + trace
-    const int64_t total = ntiles_r * (ntiles_r + 1) / 2;
-    for (int64_t t = blockIdx.x; t < total; t += gridDim.x) {
-        int64_t tr, tc;
-        tri_tile(t, &tr, &tc);
-        const int64_t r0 = tr * GR_T, c0 = tc * GR_T;
-        __syncthreads();
-        for (int idx = tid; idx < GR_T * d; idx += 256) {
-            const int r = idx / d, k = idx - r * d;
-            s1[idx] = (r0 + r < n) ? x[(r0 + r) * d + k] : (T)0;
-            s2[(size_t)k * GR_T + r] = (c0 + r < n) ? x[(c0 + r) * d + k] : (T)0;
-        }
-        if (tid < GR_T) {
-            sa1[tid] = (r0 + tid < n) ? alpha[r0 + tid] : (T)0;
-            sa2[tid] = (c0 + tid < n) ? alpha[c0 + tid] : (T)0;
-        }
-        __syncthreads();
-        const int64_t gc = c0 + col;
-        const T ak = sa2[col];
-        for (int i = 0; i < 16; ++i) {
-            const int r = rg + 4 * i;
-            const int64_t gr = r0 + r;
-            if (gr >= n || gc >= n || gc > gr) continue;
-            const double wt = (gc == gr) ? 1.0 : 2.0;
-            const double wjk = (double)W[gr * ldw + gc];
-            const double coef = wt * ((double)sa1[r] * (double)ak - wjk);
-            if (gc == gr) acc[3] += wjk;
-            if (gp.kernel == GPX_KERNEL_GAUSSIAN) {
-                T d2 = (T)0;
-                for (int k = 0; k < d; ++k) {
-                    const T tt = s1[r * d + k] - s2[(size_t)k * GR_T + col];
-                    d2 = fma(tt, tt, d2);
-                }
-                const double e = gp.c1 * (double)d2;
-                if (!(e < GPX_MIN_LOG)) {
-                    const double ex = exp(e);
-                    acc[0] += coef * (gp.c2h * ex);
-                    acc[1] += coef * (ex * (gp.c3w * (double)d2 - gp.c2w));
-                }
-            } else {
-                const T dd = s1[r] - s2[col];          // d == 1
-                acc[0] += coef * (double)periodic_entry<T>(GPX_DK_DH, dd, (T)gp.h, (T)gp.w, (T)gp.p);
-                acc[1] += coef * (double)periodic_entry<T>(GPX_DK_DW, dd, (T)gp.h, (T)gp.w, (T)gp.p);
-                acc[2] += coef * (double)periodic_entry<T>(GPX_DK_DP, dd, (T)gp.h, (T)gp.w, (T)gp.p);
-            }
-        }
-    }
-    block_sum_fixed(acc, red, tid);
-    __syncthreads();
-    if (tid < 4) partial[(int64_t)blockIdx.x * 4 + tid] = block_sum_final(red, tid);
+    TileVecs<T, NV> v;
+    v.a = (const T *)vec_a;
+    if constexpr (NV == 2) v.b = (const T *)vec_b;
+    return v;
 }
 
-// partial: GR_BLOCKS * 4 doubles of DEVICE memory; out4: host, [P0, P1, P2, trace W]
-int dloglh_reduce(int dtype, int kernel, const void *x, int64_t n, int d, const double *params,
-                  const void *alpha, const void *W, int64_t ldw, double *partial_dev, double *out4,
-                  hipStream_t st)
-{
-    GradParams gpar;
-    memset(&gpar, 0, sizeof(gpar));
-    gpar.kernel = kernel;
-    if (kernel == GPX_KERNEL_GAUSSIAN) {
-        const double h = params[0], w = params[1], S = sqrt(2.0 / M_PI);
-        gpar.nkp = 2;
-        gpar.c1 = -0.5 / (w * w);
-        gpar.c2h = S * h / w;                          // gaussian_c.pyx:61
-        gpar.c2w = 0.5 * S * h * h / (w * w);          // :82
-        gpar.c3w = 0.5 * S * h * h / pow(w, 4);        // :83
-    } else {
-        if (d != 1) { set_error("periodic gradient needs d == 1"); return GPX_ERR_UNSUPPORTED; }
-        gpar.nkp = 3; gpar.h = params[0]; gpar.w = params[1]; gpar.p = params[2];
-    }
-    const size_t es = esize(dtype);
-    const size_t smem = ((size_t)2 * GR_T * d + 2 * GR_T) * es;
-    const int64_t ntr = cdiv(n, GR_T);
-    const int blocks = (int)std::min<int64_t>(GR_BLOCKS, ntr * (ntr + 1) / 2);
-    GPX_HIP(hipMemsetAsync(partial_dev, 0, (size_t)GR_BLOCKS * 4 * sizeof(double), st));
-    {
-    ProfScope prof(PC_REDUCE, 0.5 * (double)n * (double)(n + 1) * (double)es, st);      // the lower triangle of W, read once
-    if (dtype == GPX_F64) {
-        if (smem > 48 * 1024) GPX_TRY(set_max_lds((const void *)dloglh_reduce_kernel<double>, LDS_TILE_MAX));
-        hipLaunchKernelGGL((dloglh_reduce_kernel<double>), dim3(blocks), dim3(256), smem, st, (const double *)x, n,
-                           d, (const double *)alpha, (const double *)W, ldw, gpar, ntr, partial_dev);
-    } else {
-        if (smem > 48 * 1024) GPX_TRY(set_max_lds((const void *)dloglh_reduce_kernel<float>, LDS_TILE_MAX));
-        hipLaunchKernelGGL((dloglh_reduce_kernel<float>), dim3(blocks), dim3(256), smem, st, (const float *)x, n, d,
-                           (const float *)alpha, (const float *)W, ldw, gpar, ntr, partial_dev);
-    }
-    GPX_LAUNCH_CHECK();
-    }
-    std::vector<double> host((size_t)GR_BLOCKS * 4);
-    GPX_HIP(hipMemcpyAsync(host.data(), partial_dev, host.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-    GPX_HIP(hipStreamSynchronize(st));
-    for (int q = 0; q < 4; ++q) {
-        double v = 0.0;
-        for (int b = 0; b < GR_BLOCKS; ++b) v += host[(size_t)b * 4 + q];
-        out4[q] = v;
-    }
-    return GPX_OK;
-}
-
-// ---------------------------------------------------------------------------
-// The same pass for the Gaussian ARD family (d + 1 kernel parameters): with t_k = (a_k - b_k) / w_k (the difference of the
-// SCALED points) and c_ab = wt (alpha_a alpha_b - W_ab) k_ab it accumulates
-//   S_0 = sum c_ab,   S_k = sum c_ab t_k^2  (k = 1 .. d),   tr W
-// from which the host forms dh = S_0 / h and dw_k = (S_k - S_0 / d) / (2 w_k)  (dk/dh = 2k/h, dk/dw_k = k (t_k^2 - 1/d) / w_k).
-// One read of W, nothing n x n x d anywhere, no atomics; the same fixed grid, tile walk and host summation as above, f64
-// sums for both dtypes: bitwise repeatable.
-// Per tile a thread (one column, 16 rows) first forms its 16 weights c_ab -- squared distance in T as the matrix build
-// forms it, one exp each -- and keeps them in registers, then walks the dimensions once more: S_k += sum_i c_i t_ik^2.
-// d is a run-time value and d accumulators indexed by a loop variable would live in scratch memory, so the kernel is
-// compiled for DMAX = 8, 16, 32, 64 accumulators and that loop is unrolled over DMAX with a uniform `k < d` guard: every
-// acc[k] is a register (no scratch: see DESIGN 3.4 for the compiler's resource line).  The staged points are zero beyond d.
-// ---------------------------------------------------------------------------
-template <typename T, int DMAX>
-__global__ __launch_bounds__(256) void dloglh_reduce_ard_kernel(const T *__restrict__ xs, int64_t n, int d,
-                                                                const T *__restrict__ alpha,
-                                                                const T *__restrict__ W, int64_t ldw, double c2,
-                                                                int64_t ntiles_r, double *__restrict__ partial)
-{
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    T *s1 = reinterpret_cast<T *>(smem_raw);          // [GR_T][DMAX]   rows
-    T *s2 = s1 + (size_t)GR_T * DMAX;                 // [DMAX][GR_T]   columns, transposed
-    T *sa1 = s2 + (size_t)GR_T * DMAX;                // alpha rows
-    T *sa2 = sa1 + GR_T;                              // alpha cols
-    __shared__ double red[4][DMAX + 2];
-    const int tid = threadIdx.x, col = tid & 63;
-    const int rg = __builtin_amdgcn_readfirstlane(tid >> 6);      // (the wave's index: uniform, so the row reads broadcast)
-    double acc[DMAX];
-#pragma unroll
-    for (int k = 0; k < DMAX; ++k) acc[k] = 0.0;
-    double acc0 = 0.0, acctr = 0.0;
-    const int64_t total = ntiles_r * (ntiles_r + 1) / 2;
-    for (int64_t t = blockIdx.x; t < total; t += gridDim.x) {
-        int64_t tr, tc;
-        tri_tile(t, &tr, &tc);
-        const int64_t r0 = tr * GR_T, c0 = tc * GR_T;
-        __syncthreads();
-        for (int idx = tid; idx < GR_T * DMAX; idx += 256) {
-            const int r = idx / DMAX, k = idx - r * DMAX;
-            s1[idx] = (k < d && r0 + r < n) ? xs[(r0 + r) * d + k] : (T)0;
-            s2[(size_t)k * GR_T + r] = (k < d && c0 + r < n) ? xs[(c0 + r) * d + k] : (T)0;
-        }
-        if (tid < GR_T) {
-            sa1[tid] = (r0 + tid < n) ? alpha[r0 + tid] : (T)0;
-            sa2[tid] = (c0 + tid < n) ? alpha[c0 + tid] : (T)0;
-        }
-        __syncthreads();
-        const int64_t gc = c0 + col;
-        // the squared distances of this thread's 16 entries, accumulated as kmat_kernel accumulates them
-        T r2[16];
-#pragma unroll
-        for (int i = 0; i < 16; ++i) r2[i] = (T)0;
-#pragma unroll 2
-        for (int k = 0; k < d; ++k) {
-            const T b = s2[(size_t)k * GR_T + col];
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                const T tt = s1[(rg + 4 * i) * DMAX + k] - b;
-                r2[i] = fma(tt, tt, r2[i]);
-            }
-        }
-        // the weights c_ab (0 for an entry outside the matrix or above the diagonal: W is only read inside the lower triangle)
-        double c[16];
-        const double ak = (double)sa2[col];
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            const int r = rg + 4 * i;
-            const int64_t gr = r0 + r;
-            double ci = 0.0;
-            if (gr < n && gc <= gr) {
-                const double wjk = (double)W[gr * ldw + gc];
-                const double coef = ((gc == gr) ? 1.0 : 2.0) * ((double)sa1[r] * ak - wjk);
-                if (gc == gr) acctr += wjk;
-                const double e = -0.5 * (double)r2[i];
-                if (!(e < GPX_MIN_LOG)) ci = coef * (c2 * exp(e));
-            }
-            c[i] = ci;
-            acc0 += ci;
-        }
-#pragma unroll
-        for (int k = 0; k < DMAX; ++k) {
-            if (k < d) {
-                const T b = s2[(size_t)k * GR_T + col];
-                double a = 0.0;
-#pragma unroll
-                for (int i = 0; i < 16; ++i) {
-                    const double tt = (double)(s1[(rg + 4 * i) * DMAX + k] - b);
-                    a = fma(c[i], tt * tt, a);
-                }
-                acc[k] += a;
-            }
-        }
-    }
-    // wave reduction (64 lanes), then across the 4 waves in a fixed order; slot 0: S_0, 1 .. DMAX: S_k, DMAX + 1: tr W
-    // (block_sum_fixed's text, written out: through the helper every instantiation takes two more VGPRs and <float, 32> falls
-    // from three to two waves a SIMD)
-    const bool lane0 = (tid & 63) == 0;
-    {
-        double v = acc0;
-        for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-        if (lane0) red[rg][0] = v;
-        v = acctr;
-        for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-        if (lane0) red[rg][DMAX + 1] = v;
-    }
-#pragma unroll
-    for (int k = 0; k < DMAX; ++k) {
-        double v = acc[k];
-        for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-        if (lane0) red[rg][1 + k] = v;
-    }
-    __syncthreads();
-    if (tid < d + 2) partial[(int64_t)blockIdx.x * (d + 2) + tid] = block_sum_final(red, tid <= d ? tid : DMAX + 1);
-}
-
-template <typename T, int DMAX>
-static int launch_reduce_ard(const void *xs, int64_t n, int d, const void *alpha, const void *W, int64_t ldw, double c2,
-                             int64_t ntr, int blocks, double *partial_dev, hipStream_t st)
-{
-    const size_t smem = ((size_t)2 * GR_T * DMAX + 2 * GR_T) * sizeof(T);
-    if (smem > 48 * 1024) GPX_TRY(set_max_lds((const void *)dloglh_reduce_ard_kernel<T, DMAX>, LDS_TILE_MAX));
-    hipLaunchKernelGGL((dloglh_reduce_ard_kernel<T, DMAX>), dim3(blocks), dim3(256), smem, st, (const T *)xs, n, d, (const T *)alpha,
-                       (const T *)W, ldw, c2, ntr, partial_dev);
-    GPX_LAUNCH_CHECK();
-    return GPX_OK;
-}
-
-template <typename T>
-static int launch_reduce_ard_d(const void *xs, int64_t n, int d, const void *alpha, const void *W, int64_t ldw, double c2,
-                               int64_t ntr, int blocks, double *partial_dev, hipStream_t st)
-{
-    if (d <= 8) return launch_reduce_ard<T, 8>(xs, n, d, alpha, W, ldw, c2, ntr, blocks, partial_dev, st);
-    if (d <= 16) return launch_reduce_ard<T, 16>(xs, n, d, alpha, W, ldw, c2, ntr, blocks, partial_dev, st);
-    if (d <= 32) return launch_reduce_ard<T, 32>(xs, n, d, alpha, W, ldw, c2, ntr, blocks, partial_dev, st);
-    return launch_reduce_ard<T, 64>(xs, n, d, alpha, W, ldw, c2, ntr, blocks, partial_dev, st);
-}
-
-size_t dloglh_partial_doubles(int kernel, int d) { return (size_t)GR_BLOCKS * (kernel == GPX_KERNEL_GAUSSIAN_ARD ? d + 2 : 4); }
-
-// xs: the SCALED points; iso: (h / sqrt(wbar), 1); partial_dev: dloglh_partial_doubles() of DEVICE memory;
-// out: host, d + 2 values [S_0, S_1 .. S_d, trace W]
-int dloglh_reduce_ard(int dtype, const void *xs, int64_t n, int d, const double *iso, const void *alpha, const void *W,
-                      int64_t ldw, double *partial_dev, double *out, hipStream_t st)
-{
-    if (d < 1 || d > GPX_ARD_MAX_D) { set_error("ARD gradient needs 1 <= d <= %d (got %d)", GPX_ARD_MAX_D, d); return GPX_ERR_ARG; }
-    const double c2 = 0.5 * sqrt(2.0 / M_PI) * iso[0] * iso[0] / iso[1];          // make_kparams, GPX_K
-    const int64_t ntr = cdiv(n, GR_T);
-    const int blocks = (int)std::min<int64_t>(GR_BLOCKS, ntr * (ntr + 1) / 2);
-    const size_t count = (size_t)GR_BLOCKS * (d + 2);
-    GPX_HIP(hipMemsetAsync(partial_dev, 0, count * sizeof(double), st));
-    {
-        ProfScope prof(PC_REDUCE, 0.5 * (double)n * (double)(n + 1) * (double)esize(dtype), st);
-        if (dtype == GPX_F64) GPX_TRY((launch_reduce_ard_d<double>(xs, n, d, alpha, W, ldw, c2, ntr, blocks, partial_dev, st)));
-        else GPX_TRY((launch_reduce_ard_d<float>(xs, n, d, alpha, W, ldw, c2, ntr, blocks, partial_dev, st)));
-    }
-    std::vector<double> host(count);
-    GPX_HIP(hipMemcpyAsync(host.data(), partial_dev, count * sizeof(double), hipMemcpyDeviceToHost, st));
-    GPX_HIP(hipStreamSynchronize(st));
-    for (int q = 0; q < d + 2; ++q) {
-        double v = 0.0;
-        for (int b = 0; b < GR_BLOCKS; ++b) v += host[(size_t)b * (d + 2) + q];
-        out[q] = v;
-    }
-    return GPX_OK;
-}
-
-// ---------------------------------------------------------------------------
-// The same two passes for the leave-one-out criterion (RW06 eq. 5.13 rearranged; gpx_loograd.hip has the derivation):
-//   P[p]    = sum_{j,k} G_jk dK_p(x_j, x_k),   G = (r alpha^T + alpha r^T) / 2 - Pm,   Pm = K^-1 diag(c) K^-1
-//   P[last] = trace(Pm)
-// Two vectors where the marginal-likelihood pass has one, and Pm's lower triangle where it reads W: the coefficient of an
-// entry is wt ((r_j alpha_k + alpha_j r_k) / 2 - Pm_jk).  Everything else -- the tile walk, the staging of the points, the
-// fixed-order sums, the per-workgroup partials the host adds in index order -- is the text above, in kernels of their own:
-// the marginal-likelihood kernels are not touched, their results cannot move.
-// ---------------------------------------------------------------------------
-template <typename T>
-__global__ __launch_bounds__(256) void dloo_reduce_kernel(const T *__restrict__ x, int64_t n, int d,
-                                                          const T *__restrict__ alpha, const T *__restrict__ rv,
-                                                          const T *__restrict__ Pm, int64_t ldp,
+template <typename T, int NV>
+__global__ __launch_bounds__(256) void tile_reduce_kernel(const T *__restrict__ x, int64_t n, int d,
+                                                          TileVecs<T, NV> vec, const T *__restrict__ M, int64_t ldm,
                                                           GradParams gp, int64_t ntiles_r,
                                                           double *__restrict__ partial)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     T *s1 = reinterpret_cast<T *>(smem_raw);          // [GR_T][d]   rows
     T *s2 = s1 + (size_t)GR_T * d;                    // [d][GR_T]   columns, transposed
-    T *sa1 = s2 + (size_t)GR_T * d;                   // alpha rows
-    T *sa2 = sa1 + GR_T;                              // alpha cols
-    T *sr1 = sa2 + GR_T;                              // r rows
-    T *sr2 = sr1 + GR_T;                              // r cols
+    T *sa1 = s2 + (size_t)GR_T * d;                   // vec.a rows
+    T *sa2 = sa1 + GR_T;                              // vec.a cols
+    T *sb1 = sa2 + GR_T;                              // vec.b rows  (NV == 2)
+    T *sb2 = sb1 + GR_T;                              // vec.b cols
     __shared__ double red[4][4];
     const int tid = threadIdx.x, col = tid & 63, rg = tid >> 6;
     double acc[4] = {0.0, 0.0, 0.0, 0.0};             // up to 3 kernel params + trace
@@ -647,22 +377,26 @@ __global__ __launch_bounds__(256) void dloo_reduce_kernel(const T *__restrict__ 
             s2[(size_t)k * GR_T + r] = (c0 + r < n) ? x[(c0 + r) * d + k] : (T)0;
         }
         if (tid < GR_T) {
-            sa1[tid] = (r0 + tid < n) ? alpha[r0 + tid] : (T)0;
-            sa2[tid] = (c0 + tid < n) ? alpha[c0 + tid] : (T)0;
-            sr1[tid] = (r0 + tid < n) ? rv[r0 + tid] : (T)0;
-            sr2[tid] = (c0 + tid < n) ? rv[c0 + tid] : (T)0;
+            sa1[tid] = (r0 + tid < n) ? vec.a[r0 + tid] : (T)0;
+            sa2[tid] = (c0 + tid < n) ? vec.a[c0 + tid] : (T)0;
+            if constexpr (NV == 2) {
+                sb1[tid] = (r0 + tid < n) ? vec.b[r0 + tid] : (T)0;
+                sb2[tid] = (c0 + tid < n) ? vec.b[c0 + tid] : (T)0;
+            }
         }
         __syncthreads();
         const int64_t gc = c0 + col;
-        const double ak = (double)sa2[col], rk = (double)sr2[col];
+        const T ak = sa2[col];
+        const double bk = NV == 2 ? (double)sb2[col] : 0.0;
         for (int i = 0; i < 16; ++i) {
             const int r = rg + 4 * i;
             const int64_t gr = r0 + r;
             if (gr >= n || gc >= n || gc > gr) continue;
             const double wt = (gc == gr) ? 1.0 : 2.0;
-            const double pjk = (double)Pm[gr * ldp + gc];
-            const double coef = wt * (0.5 * ((double)sr1[r] * ak + (double)sa1[r] * rk) - pjk);
-            if (gc == gr) acc[3] += pjk;
+            const double mjk = (double)M[gr * ldm + gc];
+            const double coef = NV == 1 ? wt * ((double)sa1[r] * (double)ak - mjk)
+                                        : wt * (0.5 * ((double)sb1[r] * (double)ak + (double)sa1[r] * bk) - mjk);
+            if (gc == gr) acc[3] += mjk;
             if (gp.kernel == GPX_KERNEL_GAUSSIAN) {
                 T d2 = (T)0;
                 for (int k = 0; k < d; ++k) {
@@ -702,65 +436,90 @@ static int sum_partials(const double *partial_dev, int width, double *out, hipSt
     return GPX_OK;
 }
 
-// partial: GR_BLOCKS * 4 doubles of DEVICE memory; out4: host, [P0, P1, P2, trace Pm]
-int dloo_reduce(int dtype, int kernel, const void *x, int64_t n, int d, const double *params, const void *alpha, const void *r,
-                const void *Pm, int64_t ldp, double *partial_dev, double *out4, hipStream_t st)
+// the workgroups of a pass over n points, and the launch's lower triangle of M read once as its byte count
+static inline int grad_blocks(int64_t n) { const int64_t ntr = cdiv(n, GR_T); return (int)std::min<int64_t>(GR_BLOCKS, ntr * (ntr + 1) / 2); }
+static inline double grad_bytes(int dtype, int64_t n) { return 0.5 * (double)n * (double)(n + 1) * (double)esize(dtype); }
+
+static int make_grad_params(int kernel, int d, const double *params, GradParams *gpar)
 {
-    GradParams gpar;
-    memset(&gpar, 0, sizeof(gpar));
-    gpar.kernel = kernel;
+    memset(gpar, 0, sizeof(*gpar));
+    gpar->kernel = kernel;
     if (kernel == GPX_KERNEL_GAUSSIAN) {
         const double h = params[0], w = params[1], S = sqrt(2.0 / M_PI);
-        gpar.nkp = 2;
-        gpar.c1 = -0.5 / (w * w);
-        gpar.c2h = S * h / w;                          // gaussian_c.pyx:61
-        gpar.c2w = 0.5 * S * h * h / (w * w);          // :82
-        gpar.c3w = 0.5 * S * h * h / pow(w, 4);        // :83
+        gpar->nkp = 2;
+        gpar->c1 = -0.5 / (w * w);
+        gpar->c2h = S * h / w;                         // gaussian_c.pyx:61
+        gpar->c2w = 0.5 * S * h * h / (w * w);         // :82
+        gpar->c3w = 0.5 * S * h * h / pow(w, 4);       // :83
     } else {
         if (d != 1) { set_error("periodic gradient needs d == 1"); return GPX_ERR_UNSUPPORTED; }
-        gpar.nkp = 3; gpar.h = params[0]; gpar.w = params[1]; gpar.p = params[2];
+        gpar->nkp = 3; gpar->h = params[0]; gpar->w = params[1]; gpar->p = params[2];
     }
-    const size_t es = esize(dtype);
-    const size_t smem = ((size_t)2 * GR_T * d + 4 * GR_T) * es;
-    const int64_t ntr = cdiv(n, GR_T);
-    const int blocks = (int)std::min<int64_t>(GR_BLOCKS, ntr * (ntr + 1) / 2);
+    return GPX_OK;
+}
+
+template <typename T, int NV>
+static int launch_tile_reduce(const void *x, int64_t n, int d, const void *vec_a, const void *vec_b, const void *M, int64_t ldm,
+                              const GradParams &gpar, double *partial_dev, hipStream_t st)
+{
+    const size_t smem = ((size_t)2 * GR_T * d + 2 * NV * GR_T) * sizeof(T);
+    if (smem > 48 * 1024) GPX_TRY(set_max_lds((const void *)tile_reduce_kernel<T, NV>, LDS_TILE_MAX));
+    hipLaunchKernelGGL((tile_reduce_kernel<T, NV>), dim3(grad_blocks(n)), dim3(256), smem, st, (const T *)x, n, d,
+                       tile_vecs<T, NV>(vec_a, vec_b), (const T *)M, ldm, gpar, cdiv(n, GR_T), partial_dev);
+    GPX_LAUNCH_CHECK();
+    return GPX_OK;
+}
+
+// partial_dev: GR_BLOCKS * 4 doubles of DEVICE memory; out4: host, [P0, P1, P2, trace M]; vec_b == nullptr selects NV = 1
+int tile_reduce(int dtype, int kernel, const void *x, int64_t n, int d, const double *params, const void *vec_a, const void *vec_b,
+                const void *M, int64_t ldm, double *partial_dev, double *out4, hipStream_t st)
+{
+    GradParams gpar;
+    GPX_TRY(make_grad_params(kernel, d, params, &gpar));
     GPX_HIP(hipMemsetAsync(partial_dev, 0, (size_t)GR_BLOCKS * 4 * sizeof(double), st));
     {
-    ProfScope prof(PC_REDUCE, 0.5 * (double)n * (double)(n + 1) * (double)es, st);      // the lower triangle of Pm, read once
-    if (dtype == GPX_F64) {
-        if (smem > 48 * 1024) GPX_TRY(set_max_lds((const void *)dloo_reduce_kernel<double>, LDS_TILE_MAX));
-        hipLaunchKernelGGL((dloo_reduce_kernel<double>), dim3(blocks), dim3(256), smem, st, (const double *)x, n, d,
-                           (const double *)alpha, (const double *)r, (const double *)Pm, ldp, gpar, ntr, partial_dev);
-    } else {
-        if (smem > 48 * 1024) GPX_TRY(set_max_lds((const void *)dloo_reduce_kernel<float>, LDS_TILE_MAX));
-        hipLaunchKernelGGL((dloo_reduce_kernel<float>), dim3(blocks), dim3(256), smem, st, (const float *)x, n, d,
-                           (const float *)alpha, (const float *)r, (const float *)Pm, ldp, gpar, ntr, partial_dev);
-    }
-    GPX_LAUNCH_CHECK();
+        ProfScope prof(PC_REDUCE, grad_bytes(dtype, n), st);
+        if (dtype == GPX_F64) {
+            if (vec_b) GPX_TRY((launch_tile_reduce<double, 2>(x, n, d, vec_a, vec_b, M, ldm, gpar, partial_dev, st)));
+            else GPX_TRY((launch_tile_reduce<double, 1>(x, n, d, vec_a, vec_b, M, ldm, gpar, partial_dev, st)));
+        } else {
+            if (vec_b) GPX_TRY((launch_tile_reduce<float, 2>(x, n, d, vec_a, vec_b, M, ldm, gpar, partial_dev, st)));
+            else GPX_TRY((launch_tile_reduce<float, 1>(x, n, d, vec_a, vec_b, M, ldm, gpar, partial_dev, st)));
+        }
     }
     return sum_partials(partial_dev, 4, out4, st);
 }
 
-// The ARD pass: c_ab = wt ((r_a alpha_b + alpha_a r_b) / 2 - Pm_ab) k_ab;  S_0 = sum c_ab,  S_k = sum c_ab t_k^2,  tr Pm.
-// DMAX accumulators in registers as in dloglh_reduce_ard_kernel, here in one array with S_0 and the trace so that the
-// block sum is the shared helper's; two more staged vectors.
-template <typename T, int DMAX>
-__global__ __launch_bounds__(256) void dloo_reduce_ard_kernel(const T *__restrict__ xs, int64_t n, int d,
-                                                              const T *__restrict__ alpha, const T *__restrict__ rv,
-                                                              const T *__restrict__ Pm, int64_t ldp, double c2,
+// ---------------------------------------------------------------------------
+// The same pass for the Gaussian ARD family (d + 1 kernel parameters): with t_k = (a_k - b_k) / w_k (the difference of the
+// SCALED points) and c_ab = wt G_ab k_ab (G as above, by NV) it accumulates
+//   S_0 = sum c_ab,   S_k = sum c_ab t_k^2  (k = 1 .. d),   tr M
+// from which the host forms the gradient (dk/dh = 2k/h, dk/dw_k = k (t_k^2 - 1/d) / w_k: grad_from_sums).
+// One read of M, nothing n x n x d anywhere, no atomics; the same fixed grid, tile walk and host summation as above, f64
+// sums for both dtypes: bitwise repeatable.
+// Per tile a thread (one column, 16 rows) first forms its 16 weights c_ab -- squared distance in T as the matrix build
+// forms it, one exp each -- and keeps them in registers, then walks the dimensions once more: S_k += sum_i c_i t_ik^2.
+// d is a run-time value and d accumulators indexed by a loop variable would live in scratch memory, so the kernel is
+// compiled for DMAX = 8, 16, 32, 64 accumulators and that loop is unrolled over DMAX with a uniform `k < d` guard: every
+// acc[k] is a register (no scratch: see DESIGN 3.4 for the compiler's resource line).  The staged points are zero beyond d.
+// S_0, the S_k and the trace share ONE register array, so the block sum is the shared helper's.
+// ---------------------------------------------------------------------------
+template <typename T, int DMAX, int NV>
+__global__ __launch_bounds__(256) void tile_reduce_ard_kernel(const T *__restrict__ xs, int64_t n, int d,
+                                                              TileVecs<T, NV> vec, const T *__restrict__ M, int64_t ldm, double c2,
                                                               int64_t ntiles_r, double *__restrict__ partial)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     T *s1 = reinterpret_cast<T *>(smem_raw);          // [GR_T][DMAX]   rows
     T *s2 = s1 + (size_t)GR_T * DMAX;                 // [DMAX][GR_T]   columns, transposed
-    T *sa1 = s2 + (size_t)GR_T * DMAX;                // alpha rows
-    T *sa2 = sa1 + GR_T;                              // alpha cols
-    T *sr1 = sa2 + GR_T;                              // r rows
-    T *sr2 = sr1 + GR_T;                              // r cols
+    T *sa1 = s2 + (size_t)GR_T * DMAX;                // vec.a rows
+    T *sa2 = sa1 + GR_T;                              // vec.a cols
+    T *sb1 = sa2 + GR_T;                              // vec.b rows  (NV == 2)
+    T *sb2 = sb1 + GR_T;                              // vec.b cols
     __shared__ double red[4][DMAX + 2];
     const int tid = threadIdx.x, col = tid & 63;
     const int rg = __builtin_amdgcn_readfirstlane(tid >> 6);      // (the wave's index: uniform, so the row reads broadcast)
-    double acc[DMAX + 2];                             // slot 0: S_0, 1 .. DMAX: S_k, DMAX + 1: tr Pm
+    double acc[DMAX + 2];                             // slot 0: S_0, 1 .. DMAX: S_k, DMAX + 1: tr M
 #pragma unroll
     for (int k = 0; k < DMAX + 2; ++k) acc[k] = 0.0;
     const int64_t total = ntiles_r * (ntiles_r + 1) / 2;
@@ -775,10 +534,12 @@ __global__ __launch_bounds__(256) void dloo_reduce_ard_kernel(const T *__restric
             s2[(size_t)k * GR_T + r] = (k < d && c0 + r < n) ? xs[(c0 + r) * d + k] : (T)0;
         }
         if (tid < GR_T) {
-            sa1[tid] = (r0 + tid < n) ? alpha[r0 + tid] : (T)0;
-            sa2[tid] = (c0 + tid < n) ? alpha[c0 + tid] : (T)0;
-            sr1[tid] = (r0 + tid < n) ? rv[r0 + tid] : (T)0;
-            sr2[tid] = (c0 + tid < n) ? rv[c0 + tid] : (T)0;
+            sa1[tid] = (r0 + tid < n) ? vec.a[r0 + tid] : (T)0;
+            sa2[tid] = (c0 + tid < n) ? vec.a[c0 + tid] : (T)0;
+            if constexpr (NV == 2) {
+                sb1[tid] = (r0 + tid < n) ? vec.b[r0 + tid] : (T)0;
+                sb2[tid] = (c0 + tid < n) ? vec.b[c0 + tid] : (T)0;
+            }
         }
         __syncthreads();
         const int64_t gc = c0 + col;
@@ -795,18 +556,20 @@ __global__ __launch_bounds__(256) void dloo_reduce_ard_kernel(const T *__restric
                 r2[i] = fma(tt, tt, r2[i]);
             }
         }
-        // the weights c_ab (0 for an entry outside the matrix or above the diagonal: Pm is only read inside the lower triangle)
+        // the weights c_ab (0 for an entry outside the matrix or above the diagonal: M is only read inside the lower triangle)
         double c[16];
-        const double ak = (double)sa2[col], rk = (double)sr2[col];
+        const double ak = (double)sa2[col], bk = NV == 2 ? (double)sb2[col] : 0.0;
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
             const int r = rg + 4 * i;
             const int64_t gr = r0 + r;
             double ci = 0.0;
             if (gr < n && gc <= gr) {
-                const double pjk = (double)Pm[gr * ldp + gc];
-                const double coef = ((gc == gr) ? 1.0 : 2.0) * (0.5 * ((double)sr1[r] * ak + (double)sa1[r] * rk) - pjk);
-                if (gc == gr) acc[DMAX + 1] += pjk;
+                const double mjk = (double)M[gr * ldm + gc];
+                const double wt = (gc == gr) ? 1.0 : 2.0;
+                const double coef = NV == 1 ? wt * ((double)sa1[r] * ak - mjk)
+                                            : wt * (0.5 * ((double)sb1[r] * ak + (double)sa1[r] * bk) - mjk);
+                if (gc == gr) acc[DMAX + 1] += mjk;
                 const double e = -0.5 * (double)r2[i];
                 if (!(e < GPX_MIN_LOG)) ci = coef * (c2 * exp(e));
             }
@@ -832,44 +595,68 @@ __global__ __launch_bounds__(256) void dloo_reduce_ard_kernel(const T *__restric
     if (tid < d + 2) partial[(int64_t)blockIdx.x * (d + 2) + tid] = block_sum_final(red, tid <= d ? tid : DMAX + 1);
 }
 
-template <typename T, int DMAX>
-static int launch_loo_reduce_ard(const void *xs, int64_t n, int d, const void *alpha, const void *r, const void *Pm, int64_t ldp,
-                                 double c2, int64_t ntr, int blocks, double *partial_dev, hipStream_t st)
+template <typename T, int DMAX, int NV>
+static int launch_tile_reduce_ard(const void *xs, int64_t n, int d, const void *vec_a, const void *vec_b, const void *M, int64_t ldm,
+                                  double c2, double *partial_dev, hipStream_t st)
 {
-    const size_t smem = ((size_t)2 * GR_T * DMAX + 4 * GR_T) * sizeof(T);
-    if (smem > 48 * 1024) GPX_TRY(set_max_lds((const void *)dloo_reduce_ard_kernel<T, DMAX>, LDS_TILE_MAX));
-    hipLaunchKernelGGL((dloo_reduce_ard_kernel<T, DMAX>), dim3(blocks), dim3(256), smem, st, (const T *)xs, n, d, (const T *)alpha,
-                       (const T *)r, (const T *)Pm, ldp, c2, ntr, partial_dev);
+    const size_t smem = ((size_t)2 * GR_T * DMAX + 2 * NV * GR_T) * sizeof(T);
+    if (smem > 48 * 1024) GPX_TRY(set_max_lds((const void *)tile_reduce_ard_kernel<T, DMAX, NV>, LDS_TILE_MAX));
+    hipLaunchKernelGGL((tile_reduce_ard_kernel<T, DMAX, NV>), dim3(grad_blocks(n)), dim3(256), smem, st, (const T *)xs, n, d,
+                       tile_vecs<T, NV>(vec_a, vec_b), (const T *)M, ldm, c2, cdiv(n, GR_T), partial_dev);
     GPX_LAUNCH_CHECK();
     return GPX_OK;
 }
 
-template <typename T>
-static int launch_loo_reduce_ard_d(const void *xs, int64_t n, int d, const void *alpha, const void *r, const void *Pm, int64_t ldp,
-                                   double c2, int64_t ntr, int blocks, double *partial_dev, hipStream_t st)
+template <typename T, int NV>
+static int launch_tile_reduce_ard_d(const void *xs, int64_t n, int d, const void *vec_a, const void *vec_b, const void *M, int64_t ldm,
+                                    double c2, double *partial_dev, hipStream_t st)
 {
-    if (d <= 8) return launch_loo_reduce_ard<T, 8>(xs, n, d, alpha, r, Pm, ldp, c2, ntr, blocks, partial_dev, st);
-    if (d <= 16) return launch_loo_reduce_ard<T, 16>(xs, n, d, alpha, r, Pm, ldp, c2, ntr, blocks, partial_dev, st);
-    if (d <= 32) return launch_loo_reduce_ard<T, 32>(xs, n, d, alpha, r, Pm, ldp, c2, ntr, blocks, partial_dev, st);
-    return launch_loo_reduce_ard<T, 64>(xs, n, d, alpha, r, Pm, ldp, c2, ntr, blocks, partial_dev, st);
+    if (d <= 8) return launch_tile_reduce_ard<T, 8, NV>(xs, n, d, vec_a, vec_b, M, ldm, c2, partial_dev, st);
+    if (d <= 16) return launch_tile_reduce_ard<T, 16, NV>(xs, n, d, vec_a, vec_b, M, ldm, c2, partial_dev, st);
+    if (d <= 32) return launch_tile_reduce_ard<T, 32, NV>(xs, n, d, vec_a, vec_b, M, ldm, c2, partial_dev, st);
+    return launch_tile_reduce_ard<T, 64, NV>(xs, n, d, vec_a, vec_b, M, ldm, c2, partial_dev, st);
 }
 
+size_t dloglh_partial_doubles(int kernel, int d) { return (size_t)GR_BLOCKS * (kernel == GPX_KERNEL_GAUSSIAN_ARD ? d + 2 : 4); }
+
 // xs: the SCALED points; iso: (h / sqrt(wbar), 1); partial_dev: dloglh_partial_doubles() of DEVICE memory;
-// out: host, d + 2 values [S_0, S_1 .. S_d, trace Pm]
-int dloo_reduce_ard(int dtype, const void *xs, int64_t n, int d, const double *iso, const void *alpha, const void *r, const void *Pm,
-                    int64_t ldp, double *partial_dev, double *out, hipStream_t st)
+// out: host, d + 2 values [S_0, S_1 .. S_d, trace M]; vec_b == nullptr selects NV = 1
+int tile_reduce_ard(int dtype, const void *xs, int64_t n, int d, const double *iso, const void *vec_a, const void *vec_b, const void *M,
+                    int64_t ldm, double *partial_dev, double *out, hipStream_t st)
 {
     if (d < 1 || d > GPX_ARD_MAX_D) { set_error("ARD gradient needs 1 <= d <= %d (got %d)", GPX_ARD_MAX_D, d); return GPX_ERR_ARG; }
     const double c2 = 0.5 * sqrt(2.0 / M_PI) * iso[0] * iso[0] / iso[1];          // make_kparams, GPX_K
-    const int64_t ntr = cdiv(n, GR_T);
-    const int blocks = (int)std::min<int64_t>(GR_BLOCKS, ntr * (ntr + 1) / 2);
     GPX_HIP(hipMemsetAsync(partial_dev, 0, (size_t)GR_BLOCKS * (d + 2) * sizeof(double), st));
     {
-        ProfScope prof(PC_REDUCE, 0.5 * (double)n * (double)(n + 1) * (double)esize(dtype), st);
-        if (dtype == GPX_F64) GPX_TRY((launch_loo_reduce_ard_d<double>(xs, n, d, alpha, r, Pm, ldp, c2, ntr, blocks, partial_dev, st)));
-        else GPX_TRY((launch_loo_reduce_ard_d<float>(xs, n, d, alpha, r, Pm, ldp, c2, ntr, blocks, partial_dev, st)));
+        ProfScope prof(PC_REDUCE, grad_bytes(dtype, n), st);
+        if (dtype == GPX_F64) {
+            if (vec_b) GPX_TRY((launch_tile_reduce_ard_d<double, 2>(xs, n, d, vec_a, vec_b, M, ldm, c2, partial_dev, st)));
+            else GPX_TRY((launch_tile_reduce_ard_d<double, 1>(xs, n, d, vec_a, vec_b, M, ldm, c2, partial_dev, st)));
+        } else {
+            if (vec_b) GPX_TRY((launch_tile_reduce_ard_d<float, 2>(xs, n, d, vec_a, vec_b, M, ldm, c2, partial_dev, st)));
+            else GPX_TRY((launch_tile_reduce_ard_d<float, 1>(xs, n, d, vec_a, vec_b, M, ldm, c2, partial_dev, st)));
+        }
     }
     return sum_partials(partial_dev, d + 2, out, st);
+}
+
+// The host half of either gradient: the sums of a pass -> (d/d kernel params ..., d/ds).  factor: 1/2 for the marginal
+// likelihood (RW06 eq. 5.9), 1 for the leave-one-out criterion (dL = sum dK_ab G_ab); it enters only as a product by 1/2, 1 or
+// 2, all exact, so each output is bit for bit the expression its criterion always computed.  quad: the vectors' part of tr G (alpha .
+// alpha, r . alpha); noise_scale multiplies (quad - tr M)  (dK/ds = 2 s I, gp_c.pyx:46).
+// ARD: dk/dh = 2 k / h, dk/dw_k = k (t_k^2 - 1 / d) / w_k on the scaled points.
+void grad_from_sums(int kernel, int d, const double *params, const double *S, double quad, double noise_scale, double factor,
+                    double *out)
+{
+    if (kernel == GPX_KERNEL_GAUSSIAN_ARD) {
+        out[0] = (2.0 * factor) * S[0] / params[0];
+        for (int k = 0; k < d; ++k) out[1 + k] = factor * (S[1 + k] / params[1 + k] - S[0] / ((double)d * params[1 + k]));
+        out[d + 1] = noise_scale * (quad - S[d + 1]);
+        return;
+    }
+    const int nkp = kernel == GPX_KERNEL_GAUSSIAN ? 2 : 3;
+    for (int i = 0; i < nkp; ++i) out[i] = factor * S[i];
+    out[nkp] = noise_scale * (quad - S[3]);
 }
 
 }  // namespace gpx

@@ -6,7 +6,7 @@
 //      = sum_ab dK_ab G_ab,      G = (r alpha^T + alpha r^T) / 2 - Pm,     r = W (alpha / k),    Pm = W diag(c) W
 // which is RW06 eq. 5.13 with the products regrouped: eq. 5.13 as printed takes one n^3 product W dK_j per parameter, this
 // form ONE for all of them -- Pm = Y Y^T with Y = W diag(sqrt(c)), a symmetric product, lower triangle only -- and then a
-// single fused pass of dloglh_reduce's shape over (alpha, r, Pm) against the kernel derivatives evaluated on the fly.
+// single fused pass, tile_reduce (gpx_kmat.hip) with two vectors, over (alpha, r, Pm) against the kernel derivatives evaluated on the fly.
 // Noise: dK/ds = 2 s I, so dL/ds = 2 s tr G = 2 s (r . alpha - tr Pm).
 //
 // Memory: the two n x ldl blocks the marginal-likelihood gradient uses and no third.  X = L^-T is dead once k has been read
@@ -122,33 +122,24 @@ int loo_weights_from_factor(int dtype, const void *L, int64_t n, int64_t ldl, co
     return loo_weights_product(dtype, n, ldl, X, W, 1, st);
 }
 
-// The reduction half, grad_reduce's counterpart: (alpha, r, Pm) are in HBM; one fused pass, then the host turns the sums
-// into (d/dh, d/dw ..., d/ds) -- no factor 1/2 here: dL = sum dK_ab G_ab.  ARD: dk/dh = 2 k / h, dk/dw_k = k (t_k^2 - 1 / d) / w_k
-// on the scaled points, grad_reduce's bookkeeping of S_0 .. S_d.  value (may be null): the criterion.  Synchronises g->st.
+// The reduction half, grad_reduce's counterpart: (alpha, r, Pm) are in HBM; one fused pass (tile_reduce with two vectors),
+// then grad_from_sums turns the sums into (d/dh, d/dw ..., d/ds) -- factor 1, not 1/2: dL = sum dK_ab G_ab; noise:
+// 2 s (r . alpha - tr Pm).  value (may be null): the criterion.  Synchronises g->st.
 int loo_grad_reduce(gpx_gp *g, const void *pts, const void *alpha, const double *params, double s_noise, const LooVecs &v,
                     const void *Pm, int64_t ldp, double *part, double *value, double *out)
 {
     const int64_t n = g->n;
     double S[GPX_ARD_MAX_D + 2], sums[2] = {0.0, 0.0};
-    const bool ard = g->kernel == GPX_KERNEL_GAUSSIAN_ARD;
-    if (ard) {
+    if (g->kernel == GPX_KERNEL_GAUSSIAN_ARD) {
         double iso[2];
         ard_iso(params, g->d, iso);
-        GPX_TRY(dloo_reduce_ard(g->dtype, pts, n, g->d, iso, alpha, v.r, Pm, ldp, part, S, g->st));
+        GPX_TRY(tile_reduce_ard(g->dtype, pts, n, g->d, iso, alpha, v.r, Pm, ldp, part, S, g->st));
     } else {
-        GPX_TRY(dloo_reduce(g->dtype, g->kernel, pts, n, g->d, params, alpha, v.r, Pm, ldp, part, S, g->st));
+        GPX_TRY(tile_reduce(g->dtype, g->kernel, pts, n, g->d, params, alpha, v.r, Pm, ldp, part, S, g->st));
     }
     GPX_HIP(hipMemcpyAsync(sums, v.sums, sizeof(sums), hipMemcpyDeviceToHost, g->st));
     GPX_HIP(hipStreamSynchronize(g->st));
-    if (ard) {
-        const int d = g->d;
-        out[0] = 2.0 * S[0] / params[0];
-        for (int k = 0; k < d; ++k) out[1 + k] = S[1 + k] / params[1 + k] - S[0] / ((double)d * params[1 + k]);
-        out[d + 1] = 2.0 * s_noise * (sums[1] - S[d + 1]);
-    } else {
-        for (int i = 0; i < g->nparams; ++i) out[i] = S[i];
-        out[g->nparams] = 2.0 * s_noise * (sums[1] - S[3]);    // dK/ds = 2 s I
-    }
+    grad_from_sums(g->kernel, g->d, params, S, sums[1], 2.0 * s_noise, 1.0, out);
     if (value) *value = sums[0];
     return GPX_OK;
 }

@@ -165,10 +165,14 @@ def test_streamed_reductions_keep_one_copy_of_each_piece():
     assert sites(r"sqrt\(8\.0 \* \(double\)t") == {"gpx_kernels_dev.h": 1}
     assert sites(r"\bcdiv\(2048,") == {"gpx_stream.hip": 1}
     # the 64-lane shuffle-down sum: the helper, the two sums that are no four-wave block sum (the 16-wave strided_sum_kernel
-    # and the one-value sum of gpx_solve.hip), and the two kernels that keep the text written out because the helper changes
-    # their code: dloglh_reduce_ard_kernel's three (two more VGPRs, <float, 32> loses a wave per SIMD) and
-    # member_quad_trace_kernel's interleaved pair (22 more instructions) -- DESIGN "Streamed reductions"
-    assert sites(r"off = 32; off > 0; off >>= 1") == {"gpx_kernels_dev.h": 1, "gpx_deriv.hip": 2, "gpx_solve.hip": 1, "gpx_kmat.hip": 3}
+    # and the one-value sum of gpx_solve.hip), and the one kernel that keeps the text written out because the helper changes
+    # its code: member_quad_trace_kernel's interleaved pair (22 more instructions) -- DESIGN "Streamed reductions".  The
+    # tile reductions of gpx_kmat.hip all go through the helper (one register array for S_0, the S_k and the trace)
+    assert sites(r"off = 32; off > 0; off >>= 1") == {"gpx_kernels_dev.h": 1, "gpx_deriv.hip": 2, "gpx_solve.hip": 1}
+    # one tile walk for both hyper-parameter gradients: two kernels, one host summation of the partials
+    kmat = code("gpx_kmat.hip")
+    assert re.findall(r"__global__ __launch_bounds__\(256\) void (\w+_reduce\w*)\(", kmat) == ["tile_reduce_kernel", "tile_reduce_ard_kernel"]
+    assert len(re.findall(r"v \+= host\[", kmat)) == 1
     for f in ("gpx_kmat.hip", "gpx_deriv.hip", "gpx_stream.hip", "gpx_paths.hip"):
         assert "((red[0]" not in code(f), f
     # one partial-sum scratch for the streamed passes; the mean and the apply kernel have one launch site each, behind one

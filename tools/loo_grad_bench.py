@@ -1,14 +1,17 @@
 """tools/loo_grad_bench.py -- time GP.dloo_dtheta against GP.dloglh_dtheta (profiles/loo_grad_bench_*.json).
 
-    python tools/loo_grad_bench.py [--sizes 2048,8192,16384] [--d 8] [--dtypes float64,float32] [--repeats 7] [--batch-n 2048]
-                                   [--step-timeout 300] [--out profiles/loo_grad_bench_<date>.json]
+    python tools/loo_grad_bench.py [--sizes 2048,8192,16384] [--d 8[,32]] [--kernels gaussian[,ard]] [--dtypes float64,float32]
+                                   [--repeats 7] [--batch-n 2048] [--step-timeout 300] [--out profiles/loo_grad_bench_<date>.json]
 
-One process, one JSON object (stdout, and the file).  Gaussian kernel.  Per (n, dtype) ONE fitted handle; on it
+One process, one JSON object (stdout, and the file).  Per (kernel, n, d, dtype) ONE fitted handle; on it
 gpx_gp_loo_grad and gpx_gp_dloglh_dtheta ALTERNATE, so that both see the same state of the machine, after a warm-up of each.
 Both calls are synchronous (they end with a wait for the handle's stream and a host sum of the partials): the clock is the
 host's around the call.  The median of the repeats is reported beside min, max and every run.  Then, in a pass of its own,
-the gpx_prof split of one call each: HIP events around every launch, by launch class.  The flop count predicts one more n^3
-product for the leave-one-out gradient (K^-1 whole instead of its lower triangle, and P = Y Y^T): `loo_over_loglh`.
+the gpx_prof split of --repeats calls each, again alternating: HIP events around every launch, by launch class; the first
+call's split is reported whole, and the device time of the fused reduction (class `reduce`: tile_reduce_kernel /
+tile_reduce_ard_kernel alone) for every repeat as `reduce_*`.  To compare two builds of the library run the tool once per
+build, the builds alternating, and set the `reduce_*` medians of one against the run-to-run range of the other.
+The flop count predicts one more n^3 product for the leave-one-out gradient (K^-1 whole instead of its lower triangle, and P = Y Y^T): `loo_over_loglh`.
 Last, gpx_gp_fit_batch_loo against gpx_gp_fit_batch_grad for the same 8 rows at --batch-n.
 Every GPU step runs under a watchdog of its own (--step-timeout seconds): a step that overruns it ends the process with
 exit status 124, so nothing further is started on the device.
@@ -79,15 +82,19 @@ def data(n, d):
     return X, np.sin(X.sum(1) / np.sqrt(d)) + 0.1 * rng.randn(n)
 
 
-def one_size(n, d, dtype, args):
+def one_size(n, d, dtype, kernel, args):
     lib = _lib.load()
     X, y = data(n, d)
-    g = gp.GP(gp.GaussianKernel(1.0, 0.5 * np.sqrt(d)), X, y, s=1.0, dtype=dtype)
-    res = {"n": n, "d": d, "dtype": dtype}
+    if kernel == "ard":
+        k = gp.GaussianARDKernel(1.0, 0.5 * np.sqrt(d) * np.random.RandomState(7).uniform(0.5, 2.0, d))
+    else:
+        k = gp.GaussianKernel(1.0, 0.5 * np.sqrt(d))
+    g = gp.GP(k, X, y, s=1.0, dtype=dtype)
+    res = {"kernel": kernel, "n": n, "d": d, "dtype": dtype}
     with Step("fit n = %d %s" % (n, dtype), args.step_timeout):
         h = g._fit_pd().handle
         res["log_lh"] = float(g.log_lh)
-    out, val = np.empty(3), ctypes.c_double(0.0)
+    out, val = np.empty(len(g.params)), ctypes.c_double(0.0)
 
     def loo():
         t0 = time.perf_counter()
@@ -109,7 +116,13 @@ def one_size(n, d, dtype, args):
         res["loo_over_loglh"] = res["dloo_dtheta"]["median_ms"] / res["dloglh_dtheta"]["median_ms"]
         res["loo_log_lh"] = val.value
     with Step("gpx_prof split n = %d %s" % (n, dtype), args.step_timeout):
-        res["prof_dloo_dtheta"], res["prof_dloglh_dtheta"] = prof_of(loo), prof_of(llh)
+        a, b = [], []
+        for _ in range(args.repeats):
+            a.append(prof_of(loo))
+            b.append(prof_of(llh))
+        res["prof_dloo_dtheta"], res["prof_dloglh_dtheta"] = a[0], b[0]
+        res["reduce_dloo_dtheta"] = stats([p["reduce"]["ms"] for p in a])
+        res["reduce_dloglh_dtheta"] = stats([p["reduce"]["ms"] for p in b])
     g._dev.close()
     return res
 
@@ -138,22 +151,26 @@ def batch(n, d, args):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", default="2048,8192,16384")
-    ap.add_argument("--d", type=int, default=8)
+    ap.add_argument("--d", default="8", help="input dimensions, comma separated (the batch uses the first)")
+    ap.add_argument("--kernels", default="gaussian", help="gaussian,ard")
     ap.add_argument("--dtypes", default="float64,float32")
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--batch-n", type=int, default=2048)
     ap.add_argument("--step-timeout", type=int, default=300)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
-    res = {"device": _lib.device_info(0)["name"], "kernel": "gaussian", "s": 1.0, "repeats": args.repeats,
+    ds = [int(v) for v in args.d.split(",") if v]
+    res = {"device": _lib.device_info(0)["name"], "kernels": args.kernels, "s": 1.0, "repeats": args.repeats,
            "clock": "host perf_counter around the synchronous calls, the two gradients alternating on one fitted handle, after "
-                    "one warm-up call each; prof_*: gpx_prof, HIP events around each launch, in a pass of its own",
+                    "one warm-up call each; prof_*, reduce_*: gpx_prof, HIP events around each launch, in a pass of its own",
            "sizes": [], "batch": None}
-    for n in [int(v) for v in args.sizes.split(",") if v]:
-        for dtype in args.dtypes.split(","):
-            res["sizes"].append(one_size(n, args.d, dtype, args))
+    for kernel in args.kernels.split(","):
+        for n in [int(v) for v in args.sizes.split(",") if v]:
+            for d in ds:
+                for dtype in args.dtypes.split(","):
+                    res["sizes"].append(one_size(n, d, dtype, kernel, args))
     if args.batch_n > 0:
-        res["batch"] = batch(args.batch_n, args.d, args)
+        res["batch"] = batch(args.batch_n, ds[0], args)
     text = json.dumps(res)
     path = args.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
                                     "loo_grad_bench_%s.json" % datetime.date.today().isoformat())
