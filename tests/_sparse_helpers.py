@@ -27,6 +27,29 @@ CASES = [("gaussian", 1000, 3, 128), ("gaussian", 2000, 3, 256), ("ard", 1000, 3
          ("gaussian", 777, 1, 24), ("gaussian", 300, 3, 300)]
 CASE_IDS = ["%s-%d-%d-%d" % c for c in CASES]
 
+# Depth-slice plans of a fit beyond "one slice, many chunks" (chunk_cols = 128) and "one chunk, many slices" (automatic):
+# (chunk_cols, split) -> (chunks, slices, slice width, whole slices of the LAST chunk, columns of its tail product).
+# Host arithmetic (gpx_debug_sgp_plan): asserted on the CPU by tests/test_sparse_cpu.py and again where the GPU tests use them.
+PLANS_N1000 = {
+    (384, 0): (3, 3, 128, 1, 104),     # the last chunk is one whole slice and a tail: the third accumulator is untouched by it
+    (384, 2): (3, 2, 256, 0, 232),     # the last chunk goes through the tail product alone
+    (0, 1): (1, 1, 1024, 0, 1000),     # one unbatched product of depth 1000, on the generic kernel
+    (0, 3): (1, 3, 384, 2, 232),       # two batched slices and a tail
+}
+PLANS_N2000 = {(768, 0): (3, 6, 128, 3, 80)}                     # three chunks of six slices; the last: three whole slices and a tail
+# (case, (chunk_cols, split), expected figures)
+PLAN_CASES = ([(CASES[i], p, f) for i in (0, 2) for p, f in sorted(PLANS_N1000.items())]
+              + [(CASES[1], p, f) for p, f in sorted(PLANS_N2000.items())])
+PLAN_IDS = ["%s-%d-%d-%d-cols%d-split%d" % (c + p) for c, p, _ in PLAN_CASES]
+
+
+def plan_figures(plan4, N):
+    """(chunks, slices, slice width, whole slices of the last chunk, its tail columns) from gpx_debug_sgp_plan's
+    (cols, chunks, slices, width) -- the arithmetic of the chunk loop in csrc/gpx_sparse.hip."""
+    cols, chunks, slices, width = plan4
+    last = N - (chunks - 1) * cols
+    return chunks, slices, width, last // width, last % width
+
 
 def kernel_params(kind, d):
     if kind == "gaussian":
@@ -72,8 +95,8 @@ def auto_jitter(kind, params, dtype):
 
 
 def sgpr_reference(kind, params, x, y, z, s, jitter, dtype=np.float64):
-    """The bound, its five terms, Luu, LB, c, Phi, b and closures mean / var / cov, every array in `dtype` (kernel values are
-    evaluated in float64 by the oracle and cast)."""
+    """The bound, its five terms, Luu, LB, c, Phi, b, babs = |K(z, x)| |y| (the scale of b's rounding error) and closures
+    mean / var / cov, every array in `dtype` (kernel values are evaluated in float64 by the oracle and cast)."""
     okind, op, xv, zv = oracle_view(kind, params, x, z)
     T = dtype
     y = np.asarray(y, dtype=T)
@@ -118,7 +141,8 @@ def sgpr_reference(kind, params, x, y, z, s, jitter, dtype=np.float64):
         xov, _, V1, V2 = blocks(xo)
         return np.diag(K(xov, xov)) - (V1 * V1).sum(0) + (V2 * V2).sum(0)
 
-    return dict(elbo=elbo, terms=terms, Luu=Luu, LB=LB, c=c, Phi=np.tril(Phi), b=b, Kuu=Kuu, B=B, mean=mean, var=var, cov=cov)
+    return dict(elbo=elbo, terms=terms, Luu=Luu, LB=LB, c=c, Phi=np.tril(Phi), b=b, babs=np.abs(Kzx) @ np.abs(y), Kuu=Kuu, B=B,
+                mean=mean, var=var, cov=cov)
 
 
 _DATA, _REF = {}, {}

@@ -137,45 +137,74 @@ def test_gemm_nt_vs_numpy(dtype, M, N, K):
     np.testing.assert_allclose(got, ref, rtol=tol, atol=tol * np.sqrt(K))
 
 
-@pytest.mark.parametrize("M,K", [(300, 300), (300, 320), (1500, 64), (2304, 256), (4100, 128)])
-def test_gemm_nt_lower_mask(M, K):
+_NPDT = {"f64": np.float64, "f32": np.float32}
+_DID = {"f64": _lib.F64, "f32": _lib.F32}
+
+
+def _lower_tol(dtype, K):
+    """fp64: the lower-triangle tests' own pair; fp32: the pair of test_gemm_nt_vs_numpy."""
+    return dict(rtol=1e-12, atol=1e-10) if dtype == "f64" else dict(rtol=2e-4, atol=2e-4 * np.sqrt(K))
+
+
+def _with_dtype_alpha(cases, fmt):
+    """The fp64 / alpha = -1 cases under the ids they always had, then the other dtype and sign."""
+    out = [pytest.param(*c, "f64", -1.0, id=fmt % c) for c in cases]
+    for dtype, alpha in (("f64", 1.0), ("f32", -1.0), ("f32", 1.0)):
+        out += [pytest.param(*c, dtype, alpha, id="%s-%s-%+g" % (fmt % c, dtype, alpha)) for c in cases]
+    return out
+
+
+# (1100, 96): N just over 1024 -- a ragged second patch column, and the diagonal split on in both dtypes
+@pytest.mark.parametrize("M,K,dtype,alpha",
+                         _with_dtype_alpha([(300, 300), (300, 320), (1500, 64), (2304, 256), (4100, 128), (1100, 96)], "%d-%d"))
+def test_gemm_nt_lower_mask(M, K, dtype, alpha):
+    npdt = _NPDT[dtype]
     rng = np.random.RandomState(3)
     ld = ((max(M, K) + 15) // 16) * 16
-    A = np.zeros((M, ld)); A[:, :K] = rng.randn(M, K)
-    C = np.zeros((M, ld)); C[:, :M] = rng.randn(M, M)
+    A = np.zeros((M, ld), npdt); A[:, :K] = rng.randn(M, K)
+    C = np.zeros((M, ld), npdt); C[:, :M] = rng.randn(M, M)
+    A[:, K:] = 1e30                                        # poisoned padding, as in test_gemm_nt_vs_numpy: the K tail is masked
     dA, dC = DeviceBuffer.from_host(A), DeviceBuffer.from_host(C)
-    _lib.check(_lib.load().gpx_d_gemm_nt(_lib.F64, M, M, K, -1.0, dA.ptr, ld, dA.ptr, ld, dC.ptr, ld,
+    _lib.route_reset()
+    _lib.check(_lib.load().gpx_d_gemm_nt(_DID[dtype], M, M, K, alpha, dA.ptr, ld, dA.ptr, ld, dC.ptr, ld,
                                          _lib.LOWER, 0, 0, None))
     sync()
+    # K = 300 is no multiple of 128 bytes in either dtype: the generic kernel; every other depth here the fast one
+    generic = int(K == 300)
+    assert (_lib.route_count(_lib.ROUTE_GEMM_FAST), _lib.route_count(_lib.ROUTE_GEMM_GENERIC)) == (1 - generic, generic)
     got = dC.to_host()[:, :M]
-    full = C[:, :M] - A[:, :K] @ A[:, :K].T
+    A64 = A[:, :K].astype(np.float64)
+    full = C[:, :M].astype(np.float64) + alpha * (A64 @ A64.T)
     il, iu = np.tril_indices(M), np.triu_indices(M, 1)
-    np.testing.assert_allclose(got[il], full[il], rtol=1e-12, atol=1e-10)
+    np.testing.assert_allclose(got[il].astype(np.float64), full[il], **_lower_tol(dtype, K))
     assert np.array_equal(got[iu], C[:, :M][iu])           # strict upper untouched
 
 
-def test_gemm_nt_lower_with_offsets():
+@pytest.mark.parametrize("dtype,alpha", [("f64", -1.0), ("f64", 1.0), ("f32", -1.0), ("f32", 1.0)])
+def test_gemm_nt_lower_with_offsets(dtype, alpha):
     # panel-update geometry of the factorisation: tall C (M x 64) whose top 64 x 64 block is on
     # the diagonal, and a shifted triangle (row0 != col0)
+    npdt, tol = _NPDT[dtype], _lower_tol(dtype, 192)
     rng = np.random.RandomState(11)
     M, N, K = 900, 64, 192
-    A = rng.randn(M, K); C = rng.randn(M, 64)
+    A = rng.randn(M, K).astype(npdt); C = rng.randn(M, 64).astype(npdt)
     dA, dC = DeviceBuffer.from_host(A), DeviceBuffer.from_host(C)
-    _lib.check(_lib.load().gpx_d_gemm_nt(_lib.F64, M, N, K, -1.0, dA.ptr, K, dA.ptr, K, dC.ptr, 64,
+    _lib.check(_lib.load().gpx_d_gemm_nt(_DID[dtype], M, N, K, alpha, dA.ptr, K, dA.ptr, K, dC.ptr, 64,
                                          _lib.LOWER, 0, 0, None))
     sync()
     got = dC.to_host()
-    full = C - A @ A[:N].T
+    A64 = A.astype(np.float64)
+    full = C.astype(np.float64) + alpha * (A64 @ A64[:N].T)
     mask = np.arange(M)[:, None] >= np.arange(N)[None, :]
-    np.testing.assert_allclose(got[mask], full[mask], rtol=1e-12, atol=1e-10)
+    np.testing.assert_allclose(got[mask].astype(np.float64), full[mask], **tol)
     assert np.array_equal(got[~mask], C[~mask])
     dC2 = DeviceBuffer.from_host(C)
-    _lib.check(_lib.load().gpx_d_gemm_nt(_lib.F64, M, N, K, -1.0, dA.ptr, K, dA.ptr, K, dC2.ptr, 64,
+    _lib.check(_lib.load().gpx_d_gemm_nt(_DID[dtype], M, N, K, alpha, dA.ptr, K, dA.ptr, K, dC2.ptr, 64,
                                          _lib.LOWER, 10, 40, None))
     sync()
     got = dC2.to_host()
     mask = (10 + np.arange(M))[:, None] >= (40 + np.arange(N))[None, :]
-    np.testing.assert_allclose(got[mask], full[mask], rtol=1e-12, atol=1e-10)
+    np.testing.assert_allclose(got[mask].astype(np.float64), full[mask], **tol)
     assert np.array_equal(got[~mask], C[~mask])
 
 
@@ -439,21 +468,25 @@ def test_full_size_properties_config2():
 
 
 # ------------------------------------------- block-cyclic building blocks --
-@pytest.mark.parametrize("n,nb,P,k", [(2000, 256, 3, 1), (4096, 512, 2, 0), (3100, 128, 4, 5),
-                                      (2560, 256, 1, 2), (5000, 512, 8, 0)])
-def test_syrk_bc_block_cyclic_vs_numpy(n, nb, P, k):
+_SYRK_BC_CASES = [(2000, 256, 3, 1), (4096, 512, 2, 0), (3100, 128, 4, 5), (2560, 256, 1, 2), (5000, 512, 8, 0)]
+
+
+@pytest.mark.parametrize("n,nb,P,k,dtype", [pytest.param(*c, "f64", id="%d-%d-%d-%d" % c) for c in _SYRK_BC_CASES]
+                         + [pytest.param(*c, "f32", id="%d-%d-%d-%d-f32" % c) for c in _SYRK_BC_CASES])
+def test_syrk_bc_block_cyclic_vs_numpy(n, nb, P, k, dtype):
+    npdt = _NPDT[dtype]
     rng = np.random.RandomState(n + P)
     k0 = k * nb
     kb = nb
     row_begin = k0 + kb
-    panel = rng.randn(n - k0, kb)                      # row i = global row k0 + i
+    panel = rng.randn(n - k0, kb).astype(npdt)         # row i = global row k0 + i
     dP = DeviceBuffer.from_host(panel)
     nblk = (n + nb - 1) // nb
     for rank in range(P):
         gblocks = [j for j in range(nblk) if j % P == rank]
         ncl = len(gblocks) * nb
         ldc = ((ncl + 15) // 16) * 16
-        C = np.zeros((n, ldc)); C[:, :ncl] = rng.randn(n, ncl)
+        C = np.zeros((n, ldc), npdt); C[:, :ncl] = rng.randn(n, ncl)
         dC = DeviceBuffer.from_host(C)
         # local block columns whose global index is > k
         first = next((jl for jl, j in enumerate(gblocks) if j > k), None)
@@ -461,43 +494,55 @@ def test_syrk_bc_block_cyclic_vs_numpy(n, nb, P, k):
             continue
         cl0 = first * nb
         cl1 = min(ncl, ncl)
-        _lib.check(_lib.load().gpx_d_syrk_bc(_lib.F64, n, row_begin, dC.ptr, ldc, cl0, cl1, dP.ptr, kb,
+        _lib.check(_lib.load().gpx_d_syrk_bc(_DID[dtype], n, row_begin, dC.ptr, ldc, cl0, cl1, dP.ptr, kb,
                                              k0, kb, nb, P, rank, None))
         sync()
-        got = dC.to_host()
-        ref = C.copy()
+        got = dC.to_host().astype(np.float64)
+        ref = C.astype(np.float64)
+        panel64 = panel.astype(np.float64)
         rows_all = np.arange(row_begin, n)
         for jl, j in enumerate(gblocks):
             if jl < first:
                 continue
             gcols = j * nb + np.arange(nb)
             gcols = gcols[gcols < n]           # padding columns beyond the matrix: rows >= gc do not exist
-            upd = panel[rows_all - k0] @ panel[gcols - k0].T                    # one product per block column ...
+            upd = panel64[rows_all - k0] @ panel64[gcols - k0].T                # one product per block column ...
             upd[rows_all[:, None] < gcols[None, :]] = 0.0                       # ... masked to global row >= global column
             ref[row_begin:, jl * nb:jl * nb + gcols.size] -= upd
-        np.testing.assert_allclose(got, ref, rtol=1e-12, atol=1e-10)
+        np.testing.assert_allclose(got, ref, **_lower_tol(dtype, kb))
 
 
-def test_potrf_panel_device_api_matches_full_factor():
+@pytest.mark.parametrize("dtype", ["f64", "f32"])
+def test_potrf_panel_device_api_matches_full_factor(dtype):
+    """fp32: within 4 E32 of the fp64 factor, E32 = max |scipy's fp32 factor - scipy's fp64 factor| of the same matrix (the
+    reference's own fp32 error; the margin of tests/test_gpu_sparse.py for a device that sums in another order)."""
+    npdt = _NPDT[dtype]
     n, nb = 1500, 256
     A = _spd(n, 7)
     lda = ((n + 15) // 16) * 16
-    Ap = np.zeros((n, lda)); Ap[:, :n] = A
+    Ap = np.zeros((n, lda), npdt); Ap[:, :n] = A
     dA = DeviceBuffer.from_host(Ap)
     info = DeviceBuffer((4,), np.int32).zero()
     lib = _lib.load()
     for k0 in range(0, n, nb):
         kb = min(nb, n - k0)
-        _lib.check(lib.gpx_d_potrf_panel(_lib.F64, dA.ptr, lda, n, k0, k0, kb, info.ptr, None))
+        _lib.check(lib.gpx_d_potrf_panel(_DID[dtype], dA.ptr, lda, n, k0, k0, kb, info.ptr, None))
         r = k0 + kb
         if r < n:
-            off = ctypes.c_void_p(dA.ptr.value + (k0 * lda + k0) * 8)
-            _lib.check(lib.gpx_d_syrk_bc(_lib.F64, n, r, dA.ptr, lda, r, n, off, lda, k0, kb, nb, 1, 0,
+            off = ctypes.c_void_p(dA.ptr.value + (k0 * lda + k0) * Ap.itemsize)
+            _lib.check(lib.gpx_d_syrk_bc(_DID[dtype], n, r, dA.ptr, lda, r, n, off, lda, k0, kb, nb, 1, 0,
                                          None))
     sync()
     L = np.tril(dA.to_host()[:, :n])
     assert info.to_host()[0] == 0
-    np.testing.assert_allclose(L, scipy.linalg.cholesky(A, lower=True), rtol=1e-9, atol=1e-11)
+    ref = scipy.linalg.cholesky(A, lower=True)
+    if dtype == "f64":
+        np.testing.assert_allclose(L, ref, rtol=1e-9, atol=1e-11)
+        return
+    E32 = float(np.abs(scipy.linalg.cholesky(Ap[:, :n], lower=True).astype(np.float64) - ref).max())
+    err = float(np.abs(L.astype(np.float64) - ref).max())
+    print("fp32 panel factor: E32 = %.3e, max |device - fp64 factor| = %.3e (allowed 4 E32 = %.3e)" % (E32, err, 4 * E32))
+    assert err <= 4 * E32
 
 
 @pytest.mark.parametrize("dtype", ["f64", "f32"])

@@ -7,7 +7,10 @@ the project's fp32 ORACLE_TOL (rtol 1e-2, atol 5e-3); where the fp32 run of the 
 from the fp64 run, 4 * E32 (the device sums in another order than numpy).  With the cases as they stand no E32 exceeds the
 fp32 atol (the largest: LB 1.3e-3 and c 1.1e-3 of gaussian (777, 1, 24), LB 1.2e-3 and trace 1.5e-3 of periodic
 (777, 1, 64); tests/test_sparse_cpu.py prints all of them), so the floor decides nothing at present.
-Two device evaluations of one quantity are compared at 1e-10 * max|ref| (tests/_extend_helpers.close)."""
+Two device evaluations of one quantity are compared at 1e-10 * max|ref| (tests/_extend_helpers.close).
+The depth-slice plans of tests/_sparse_helpers.PLAN_CASES (several chunks of several slices, a last chunk that leaves the
+higher accumulators untouched or runs the tail product alone, one unbatched product) are set through gpx_sgp_set_split on
+the handle before the first fit; what they are held to between each other is derived in the test that does it."""
 import numpy as np
 import pytest
 
@@ -15,8 +18,9 @@ import gaussian_processes_amd as gp
 from gaussian_processes_amd import _lib
 from test_gpu_var import ORACLE_TOL
 from _extend_helpers import close
-from _sparse_helpers import (CASES, CASE_IDS, E32, QUANTITIES, S_NOISE, TERMS, case_data, case_jitter, make_kernel, quantities,
-                             reference)
+from _sparse_helpers import (CASES, CASE_IDS, E32, PLAN_CASES, PLAN_IDS, QUANTITIES, S_NOISE, TERMS, case_data, case_jitter,
+                             make_kernel, plan_figures, quantities, reference)
+from test_sparse_cpu import _plan
 
 pytestmark = pytest.mark.gpu
 
@@ -51,6 +55,11 @@ def test_parity_against_the_restatement(case, dtype, chunk_cols):
     _lib.route_reset()
     got = _device_quantities(sg, xo)
     assert _lib.route_count(_lib.ROUTE_SPARSE_CHUNK) == _chunks(case[1], chunk_cols)     # one fit, this many chunks
+    _assert_parity(case, dtype, sg, got)
+
+
+def _assert_parity(case, dtype, sg, got):
+    """Every quantity of a fit against the restatement: ORACLE_TOL, in fp32 with the floor 4 E32."""
     ref = quantities(reference(case, sg.jitter))
     tol = ORACLE_TOL[dtype]
     bad = []
@@ -108,6 +117,65 @@ def test_repeated_fits_are_bitwise_identical(case, chunk_cols, dtype):
         assert np.array_equal(getattr(a, name), getattr(b, name)), name
     assert np.array_equal(a.mean(xo), b.mean(xo))
     assert np.array_equal(np.triu(a.Phi, 1), np.zeros_like(a.Phi))
+
+
+# ---- depth-slice plans between the two extremes (tests/_sparse_helpers.PLAN_CASES) -----------------------------------------
+def _planned(case, dtype, plan):
+    """A SparseGP whose handle is told its depth split before the first fit (gpx_sgp_set_split, as tools/sparse_bench.py)."""
+    chunk_cols, split = plan
+    sg = _sparse(case, dtype, chunk_cols)
+    _lib.check(_lib.load().gpx_sgp_set_split(sg._state().handle, split))
+    return sg
+
+
+@pytest.mark.parametrize("dtype", ["float64", "float32"])
+@pytest.mark.parametrize("case,plan,figures", PLAN_CASES, ids=PLAN_IDS)
+def test_depth_slice_plans_parity_and_repeatability(case, plan, figures, dtype):
+    N, M = case[1], case[3]
+    did = _lib.F64 if dtype == "float64" else _lib.F32
+    assert plan_figures(_plan(N, M, plan[0], plan[1], free=_lib.mem_free(), dtype=did), N) == figures
+    xo = case_data(case)[4]
+    sg = _planned(case, dtype, plan)
+    _lib.route_reset()
+    got = _device_quantities(sg, xo)
+    assert _lib.route_count(_lib.ROUTE_SPARSE_CHUNK) == figures[0]
+    _assert_parity(case, dtype, sg, got)
+    again = _planned(case, dtype, plan)
+    assert again.elbo == sg.elbo
+    for name in ("Phi", "b", "c"):
+        assert np.array_equal(getattr(again, name), getattr(sg, name)), name
+    assert np.array_equal(np.triu(sg.Phi, 1), np.zeros_like(sg.Phi))
+
+
+_BASE = {}
+
+
+def _base_plan(case):
+    """The automatic plan's fit of a case in fp64 (one chunk, eight or sixteen slices), one per session."""
+    if case not in _BASE:
+        assert _plan(case[1], case[3], free=_lib.mem_free())[1] == 1
+        sg = _sparse(case)
+        _BASE[case] = dict(Phi=sg.Phi, b=sg.b, c=sg.c, elbo=sg.elbo, mean=sg.mean(case_data(case)[4]))
+    return _BASE[case]
+
+
+@pytest.mark.parametrize("case,plan,figures", PLAN_CASES, ids=PLAN_IDS)
+def test_depth_slice_plans_differ_in_summation_order_only(case, plan, figures):
+    """fp64, against the automatic plan.  Phi: every term is positive for these kernels, so two summation orders differ by at
+    most 2 gamma_N Phi (4e-13 Phi): `close`.  b cancels, so it is held to 4 N u (|G| |y|) componentwise (2 gamma_N (|G| |y|)
+    between two orders; G from the oracle).  Kuu's conditioning sits between these and elbo, c and the mean: those to the
+    parity tolerance only."""
+    N = case[1]
+    base, sg = _base_plan(case), _planned(case, "float64", plan)
+    close(sg.Phi, base["Phi"])
+    bound = 4.0 * N * 2.0 ** -53 * reference(case, sg.jitter)["babs"]
+    err = np.abs(sg.b - base["b"])
+    print("b: max |plan - automatic| / (4 N u |G| |y|) = %.3g" % float((err / bound).max()))
+    assert (err <= bound).all()
+    tol = ORACLE_TOL["float64"]
+    np.testing.assert_allclose(sg.elbo, base["elbo"], **tol)
+    np.testing.assert_allclose(sg.c, base["c"], **tol)
+    np.testing.assert_allclose(sg.mean(case_data(case)[4]), base["mean"], **tol)
 
 
 def test_inducing_points_at_the_data_give_the_dense_gp():

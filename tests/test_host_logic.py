@@ -38,6 +38,19 @@ def test_library_exports_every_declared_symbol():
     assert lib.gpx_version() == 100
 
 
+def test_every_device_block_is_named_in_a_gpu_test():
+    """Every exported gpx_d_* block occurs, as a word, in at least one tests/test_gpu_*.py: a block does not arrive without a
+    test that calls it by name (a text search of the test sources for the API's own names, nothing more)."""
+    tests = os.path.join(ROOT, "tests")
+    text = "\n".join(open(os.path.join(tests, f)).read() for f in sorted(os.listdir(tests))
+                     if f.startswith("test_gpu_") and f.endswith(".py"))
+    words = set(re.findall(r"\bgpx_d_[a-zA-Z0-9_]+\b", text))
+    blocks = [name for name in _lib.EXPORTED_SYMBOLS if name.startswith("gpx_d_")]
+    assert len(blocks) > 30
+    missing = [name for name in blocks if name not in words]
+    assert not missing, "exported device blocks that no tests/test_gpu_*.py names: %s" % ", ".join(missing)
+
+
 def test_library_never_calls_getenv():
     """Every GPX_* switch is read through ONE snapshot per API call (csrc/gpx_tune.h: a pass over `environ` at the entry
     point), never by a getenv at its point of use -- round 4 had 66 such sites, a dozen of them per panel launch.  The

@@ -12,8 +12,8 @@ import gaussian_processes_amd as gp
 from gaussian_processes_amd import _lib
 from oracle import gp_oracle as orc
 from conftest import ROOT
-from _sparse_helpers import (CASES, CASE_IDS, E32, JITTER64, QUANTITIES, S_NOISE, case_data, case_jitter, kernel_params,
-                             oracle_view, reference, sgpr_reference)
+from _sparse_helpers import (CASES, CASE_IDS, E32, JITTER64, PLAN_CASES, PLAN_IDS, QUANTITIES, S_NOISE, case_data, case_jitter,
+                             kernel_params, oracle_view, plan_figures, reference, sgpr_reference)
 
 c_double_p, c_int_p = POINTER(c_double), POINTER(c_int)
 
@@ -219,3 +219,12 @@ def test_plan_of_a_fit():
         _plan(1000, 4096, free=1 << 20)
     with pytest.raises(MemoryError):
         _plan(1 << 20, 4096, 16384, free=1 << 30)
+
+
+@pytest.mark.parametrize("dtype", [_lib.F64, _lib.F32], ids=["f64", "f32"])
+@pytest.mark.parametrize("case,plan,figures", PLAN_CASES, ids=PLAN_IDS)
+def test_depth_slice_plans_of_the_gpu_tests(case, plan, figures, dtype):
+    """The plans tests/test_gpu_sparse.py fits with are what tests/_sparse_helpers.py says they are, in both dtypes."""
+    _, N, _, M = case
+    assert plan_figures(_plan(N, M, plan[0], plan[1], dtype=dtype), N) == figures
+    assert _plan(N, M, dtype=dtype)[1] == 1                        # the plan they are compared with: one chunk
