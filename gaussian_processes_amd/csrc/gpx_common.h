@@ -249,10 +249,16 @@ int pred_grad(int dtype, int kernel, const void *xo, int64_t m, const void *x, i
 // only): factors sL elements apart, X and W blocks n * ldl apart, operators built here into group_ops (count * trsv_ops_bytes).
 int inv_from_factor(int dtype, const void *L, int64_t n, int64_t ldl, void *X, void *W, int tri, hipStream_t st,
                     TrsvOps *ops, int count = 1, int64_t sL = 0, void *group_ops = nullptr);
+// The small shared blocks (gpx_small.hip).  logdet_chol, dot, sum_f64, diag_sum: one workgroup, fixed order; count > 1: one
+// workgroup per matrix / pair.  diag_sum: out_dev[0] = sum A[i, i].  transpose: dst (cols x rows, ldd) <- src (rows x cols, lds)^T;
+// mirror != 0: src == dst allowed, only the tiles at or below the diagonal are read and only elements strictly above it are
+// written (the lower triangle mirrored into the upper one).  tril: the strict upper triangle <- 0.
 int logdet_chol(int dtype, const void *L, int64_t n, int64_t ldl, double *out_dev, hipStream_t st, int count = 1,
                 int64_t sL = 0, int64_t so = 0);
 int dot(int dtype, const void *a, const void *b, int64_t n, double *out_dev, hipStream_t st, int count = 1,
         int64_t sa = 0, int64_t sb = 0, int64_t so = 0);
+int diag_sum(int dtype, const void *A, int64_t n, int64_t lda, double *out_dev, hipStream_t st);
+int transpose(int dtype, const void *src, int64_t lds, int64_t rows, int64_t cols, void *dst, int64_t ldd, int mirror, hipStream_t st);
 int tril(int dtype, void *A, int64_t n, int64_t lda, hipStream_t st);
 // Predictive variance (gpx_solve.hip).  var_rows: out_dev[i] = kdiag(i) - sum_j X[i, j]^2 over a solved rows x n chunk
 // (gpx_d_var_rows' arguments), or with accumulate != 0: out_dev[i] += sum_j X[i, j]^2 (no kdiag; the distributed form adds
@@ -261,8 +267,8 @@ int var_rows(int dtype, int kernel, const void *X, int64_t rows, int64_t n, int6
              const double *params, const double *kdiag_dev, int accumulate, double *out_dev, hipStream_t st);
 int var_finish(int dtype, int kernel, const void *xo, int d, const double *params, const double *acc_dev, int64_t rows,
                double *out_dev, hipStream_t st);
-// Leave-one-out from the factor (gpx_solve.hip).  eye_rows: X (rows x ld) <- rows [c0, c0 + rows) of the identity, columns
-// [cz, ld) only.  loo_rows: gpx_d_loo_rows' arguments, over the chunk solved from that seed.  loo_points: the same per-point
+// Leave-one-out from the factor (gpx_solve.hip).  eye_rows (gpx_small.hip): X (rows x ld) <- rows [c0, c0 + rows) of the
+// identity, columns [cz, ld) only.  loo_rows: gpx_d_loo_rows' arguments, over the chunk solved from that seed.  loo_points: the same per-point
 // quantities from a diagonal kii that is already there.  sum_f64: out_dev[0] = sum a[i], one workgroup, fixed order.
 int eye_rows(int dtype, void *X, int64_t rows, int64_t ld, int64_t c0, int64_t cz, hipStream_t st);
 int loo_rows(int dtype, const void *X, int64_t rows, int64_t n, int64_t ldx, int64_t c0, const void *y, const void *alpha,
@@ -273,6 +279,10 @@ int sum_f64(const double *a, int64_t n, double *out_dev, hipStream_t st);
 // Growing a fitted handle (gpx_extend.hip).  copy_lower: gpx_d_copy_lower's arguments.  schur_lower: gpx_d_schur_lower's.
 int copy_lower(int dtype, const void *src, int64_t lds, void *dst, int64_t ldd, int64_t n, hipStream_t st);
 int schur_lower(int dtype, const void *B, int64_t k, int64_t n, int64_t ldb, void *S, int64_t lds, hipStream_t st);
+// The slices' partial sums folded (gpx_sparse.hip): gpx_d_sum_slices_lower's arguments; minus_from (n x ldo, or null; may be
+// out): the sum is subtracted from it instead
+int sum_slices_lower(int dtype, const void *P, int64_t ldp, int64_t sP, int slices, int64_t n, const void *minus_from, void *out, int64_t ldo,
+                     hipStream_t st);
 // Shrinking one (gpx_remove.hip).  chol_delete: gpx_d_chol_delete's arguments, already checked (the caller holds the StreamTurn).
 int chol_delete(int dtype, const void *L, int64_t n, int64_t ldl, const int64_t *idx_host, int64_t k, void *out, int64_t ldo, hipStream_t st);
 // Sampling (gpx_sample.hip).  randn: gpx_d_randn's arguments.  mvn_sample: gpx_d_mvn_sample's.

@@ -13,6 +13,7 @@
 //     d2lh_ij = 1/2 [ dlh_j (a_i - tr_i) + lh (-2 vu_ij + q_ij + T_ij - h_ij) ]
 //     dm_i    = dK_i(xo, x) alpha - K(xo, x) u_i                                        gp_c.pyx:114-131
 // Only the (n_p + 1)^2 scalars (or the (n_p + 1) x m matrix of dm) return to the host.
+#include "gpx_small.h"
 #include "gpx_gp_internal.h"
 #include "gpx_kernels_dev.h"
 #include <cmath>
@@ -154,38 +155,15 @@ __global__ __launch_bounds__(256) void trace_prod_kernel(const T *__restrict__ A
     if (tid == 0) partial[blockIdx.x] = block_sum_final(red, 0);
 }
 
-// out[0] = sum_i a[i * stride]  (trace of a matrix: stride = ld + 1); single workgroup, fixed order
-template <typename T>
-__global__ __launch_bounds__(1024) void strided_sum_kernel(const T *__restrict__ a, int64_t n, int64_t stride,
-                                                           double *__restrict__ out)
+// dst[i] = (T)(src[i] * f), the product in f64
+static int scale_copy(int dtype, const void *src, void *dst, int64_t n, double f, hipStream_t st)
 {
-    __shared__ double red[16];
-    const int tid = threadIdx.x;
-    double acc = 0.0;
-    for (int64_t i = tid; i < n; i += 1024) acc += (double)a[i * stride];
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
-    if ((tid & 63) == 0) red[tid >> 6] = acc;
-    __syncthreads();
-    if (tid == 0) {
-        double s = 0.0;
-        for (int w = 0; w < 16; ++w) s += red[w];
-        out[0] = s;
-    }
-}
-
-template <typename T>
-__global__ void scale_copy_kernel(const T *__restrict__ src, T *__restrict__ dst, int64_t n, double f)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) dst[i] = (T)((double)src[i] * f);
-}
-
-// out (m) <- a (m) - b (m)
-template <typename T>
-__global__ void sub_kernel(const T *__restrict__ a, const T *__restrict__ b, T *__restrict__ out, int64_t n, double fb)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) out[i] = (T)((a ? (double)a[i] : 0.0) - fb * (double)b[i]);
+    return by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        const T *s = (const T *)src;
+        T *d = (T *)dst;
+        return map_vec(n, st, [=] __device__(int64_t i) { d[i] = (T)((double)s[i] * f); });
+    });
 }
 
 static const int kJacGaussian[2] = {GPX_DK_DH, GPX_DK_DW};
@@ -240,14 +218,7 @@ static int deriv_vectors(DerivState &D)
     for (int i = 0; i < np; ++i)
         GPX_TRY(gpx_d_mean_member(g->dtype, g->kernel, jm[i], g->x, n, g->x, n, g->d, g->params, g->alpha, D.v(i),
                                   (void *)g->st));
-    const unsigned nblk = (unsigned)cdiv(n, 256);
-    if (g->dtype == GPX_F64)
-        hipLaunchKernelGGL((scale_copy_kernel<double>), dim3(nblk), dim3(256), 0, g->st, (const double *)g->alpha,
-                           (double *)D.v(np), n, 2.0 * g->s);
-    else
-        hipLaunchKernelGGL((scale_copy_kernel<float>), dim3(nblk), dim3(256), 0, g->st, (const float *)g->alpha,
-                           (float *)D.v(np), n, 2.0 * g->s);
-    GPX_LAUNCH_CHECK();
+    GPX_TRY(scale_copy(g->dtype, g->alpha, D.v(np), n, 2.0 * g->s, g->st));
     for (int i = 0; i <= np; ++i) {
         void *t0 = D.tmp.p, *t1 = (char *)D.tmp.p + (size_t)n * D.es;
         GPX_HIP(hipMemcpyAsync(t0, D.v(i), (size_t)n * D.es, hipMemcpyDeviceToDevice, g->st));
@@ -306,9 +277,8 @@ static int d2lh_t(gpx_gp *g, double *dlh_out, double *d2lh_out, double *d2loglh_
     for (int i = 0; i < P; ++i) GPX_TRY(dot(g->dtype, g->alpha, D.v(i), n, sc + slot++, st));
     for (int i = 0; i < P; ++i)
         for (int j = 0; j < P; ++j) GPX_TRY(dot(g->dtype, D.v(j), D.u(i), n, sc + slot++, st));
-    hipLaunchKernelGGL((strided_sum_kernel<T>), dim3(1), dim3(1024), 0, st, (const T *)D.W.p, n, lda + 1, sc + slot);
     const int slot_trW = slot++;
-    GPX_LAUNCH_CHECK();
+    GPX_TRY(diag_sum(g->dtype, D.W.p, n, lda, sc + slot_trW, st));
     // M_i = W dK_i (i < np), trace(M_i); D_i is built into X (free now), M_i kept
     std::vector<DevBuf> M(np);
     const int *jm = jac_members(g->kernel);
@@ -318,8 +288,7 @@ static int d2lh_t(gpx_gp *g, double *dlh_out, double *d2lh_out, double *d2loglh_
         GPX_TRY(kmat(g->dtype, g->kernel, jm[i], g->x, n, g->x, n, g->d, g->params, 0.0, GPX_FULL, X.p, lda, st));
         GPX_HIP(hipMemsetAsync(M[i].p, 0, (size_t)n * lda * sizeof(T), st));
         GPX_TRY(gemm_nt(g->dtype, n, n, n, D.W.p, lda, X.p, lda, M[i].p, lda, 1.0, GPX_FULL, 0, 0, st));   // W dK_i^T = W dK_i
-        hipLaunchKernelGGL((strided_sum_kernel<T>), dim3(1), dim3(1024), 0, st, (const T *)M[i].p, n, lda + 1, sc + slot++);
-        GPX_LAUNCH_CHECK();
+        GPX_TRY(diag_sum(g->dtype, M[i].p, n, lda, sc + slot++, st));
     }
     std::vector<double> hs(slot);
     GPX_HIP(hipMemcpyAsync(hs.data(), sc, (size_t)slot * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -421,7 +390,6 @@ static int dm_t(gpx_gp *g, const double *xo, int64_t m, double *out)
     GPX_TRY(res.alloc((size_t)P * m * sizeof(T)));
     GPX_TRY(upload_f64(g->dtype, dxo.p, m * g->d, xo, m * g->d, 1, m * g->d, st));
     const int *jm = jac_members(g->kernel);
-    const unsigned mb = (unsigned)cdiv(m, 256);
     for (int i = 0; i < P; ++i) {
         // dm_i = dK_i(xo, x) alpha - K(xo, x) u_i     (gp_c.pyx:121-131; dK_s(xo, x) = 0)
         if (i < np)
@@ -429,9 +397,9 @@ static int dm_t(gpx_gp *g, const double *xo, int64_t m, double *out)
                                       (void *)st));
         GPX_TRY(gpx_d_mean_member(g->dtype, g->kernel, GPX_K, dxo.p, m, g->x, n, g->d, g->params, D.u(i), o2.p,
                                   (void *)st));
-        hipLaunchKernelGGL((sub_kernel<T>), dim3(mb), dim3(256), 0, st, i < np ? (const T *)o1.p : (const T *)nullptr,
-                           (const T *)o2.p, (T *)res.p + (size_t)i * m, m, 1.0);
-        GPX_LAUNCH_CHECK();
+        const T *a = i < np ? (const T *)o1.p : (const T *)nullptr, *b = (const T *)o2.p;
+        T *dm = (T *)res.p + (size_t)i * m;
+        GPX_TRY(map_vec(m, st, [=] __device__(int64_t j) { dm[j] = (T)((a ? (double)a[j] : 0.0) - (double)b[j]); }));
     }
     return download_f64(g->dtype, out, P * m, res.p, P * m, 1, P * m, 0, st);
 }
@@ -452,24 +420,6 @@ static int dm_t(gpx_gp *g, const double *xo, int64_t m, double *out)
 //     [t1c = Kiy . dK_i dKi_j y]   = -k_i . r_j                   [trace(dKi_j dK_i)]     = -sum_ab N_j[a,b] N_i[b,a]
 //     [trace(Ki d2k)]              = sum_ab Ki[a,b] d2K_ij[b,a]   [dm_i]                  = dKxox_i w - Kxox r_i
 // Only the (n_p + 1) / (n_p + 1)^2 scalars, or the (n_p + 1) x m matrix of dm, return to the host.
-template <typename T>
-__global__ __launch_bounds__(256) void transpose_kernel(const T *__restrict__ src, int64_t lds, T *__restrict__ dst,
-                                                        int64_t ldd, int64_t n)
-{
-    __shared__ T tile[DR_T][DR_T + 1];
-    const int64_t r0 = (int64_t)blockIdx.y * DR_T, c0 = (int64_t)blockIdx.x * DR_T;
-    const int col = threadIdx.x & 63, rg = threadIdx.x >> 6;
-    for (int i = 0; i < 16; ++i) {
-        const int r = rg + 4 * i;
-        tile[r][col] = (r0 + r < n && c0 + col < n) ? src[(r0 + r) * lds + c0 + col] : (T)0;
-    }
-    __syncthreads();
-    for (int i = 0; i < 16; ++i) {
-        const int r = rg + 4 * i;
-        if (c0 + r < n && r0 + col < n) dst[(c0 + r) * ldd + r0 + col] = tile[col][r];
-    }
-}
-
 // partial[chunk][c] = sum over the chunk's rows r of M[r][c] v[r]   (M^T v in two passes, fixed summation order)
 template <typename T>
 __global__ __launch_bounds__(256) void gemv_t_partial_kernel(const T *__restrict__ M, int64_t ld, int64_t rows, int64_t cols,
@@ -538,10 +488,7 @@ struct Glue {
     }
     int scale(const void *src, void *dst, int64_t len, double f)
     {
-        hipLaunchKernelGGL((scale_copy_kernel<double>), dim3((unsigned)cdiv(len, 256)), dim3(256), 0, st, (const double *)src,
-                           (double *)dst, len, f);
-        GPX_LAUNCH_CHECK();
-        return GPX_OK;
+        return scale_copy(GPX_F64, src, dst, len, f, st);
     }
     // queue a . b; returns its slot (value in hsc after flush())
     int qdot(const void *a, const void *b, int64_t len, int *slot)
@@ -571,8 +518,7 @@ struct Glue {
     }
     int trace(const void *A, double *out)
     {
-        hipLaunchKernelGGL((strided_sum_kernel<double>), dim3(1), dim3(1024), 0, st, (const double *)A, n, ld + 1, (double *)part.p);
-        GPX_LAUNCH_CHECK();
+        GPX_TRY(diag_sum(GPX_F64, A, n, ld, (double *)part.p, st));
         GPX_HIP(hipMemcpyAsync(out, part.p, 8, hipMemcpyDeviceToHost, st));
         GPX_HIP(hipStreamSynchronize(st));
         return GPX_OK;
@@ -622,11 +568,7 @@ static int glue_d2lh(const double *y, const double *Ki, const double *Kj, const 
     auto at = [&](DevBuf &b, int i) { return (void *)((double *)b.p + (size_t)i * vs); };
     GPX_TRY(G.upload(dKi, Ki, n, n, ld));
     GPX_TRY(dKiT.alloc((size_t)n * ld * 8));
-    {
-        dim3 grid((unsigned)cdiv(n, DR_T), (unsigned)cdiv(n, DR_T));
-        hipLaunchKernelGGL((transpose_kernel<double>), grid, dim3(256), 0, G.st, (const double *)dKi.p, ld, (double *)dKiT.p, ld, n);
-        GPX_LAUNCH_CHECK();
-    }
+    GPX_TRY(transpose(GPX_F64, dKi.p, ld, n, n, dKiT.p, ld, 0, G.st));
     GPX_TRY(G.vec(dy, n)); GPX_TRY(G.vec(dKiy, n)); GPX_TRY(G.vec(dz, n)); GPX_TRY(G.vec(dw, n)); GPX_TRY(G.vec(dt, n));
     GPX_HIP(hipMemcpyAsync(dy.p, y, (size_t)n * 8, hipMemcpyHostToDevice, G.st));
     GPX_HIP(hipMemcpyAsync(dKiy.p, Kiy, (size_t)n * 8, hipMemcpyHostToDevice, G.st));
@@ -766,8 +708,7 @@ int gpx_gp_dlh_d2lh(gpx_gp_t *g, double *dlh, double *d2lh, double *d2loglh)
     GP_ENTER(g);
     GPX_ARG(g->fitted && (dlh || d2lh || d2loglh), "gp is not fitted / nothing requested");
     GPX_TRY(deriv_supported(g));
-    if (g->dtype == GPX_F64) return d2lh_t<double>(g, dlh, d2lh, d2loglh);
-    return d2lh_t<float>(g, dlh, d2lh, d2loglh);
+    return by_dtype(g->dtype, [&](auto t) { return d2lh_t<decltype(t)>(g, dlh, d2lh, d2loglh); });
 }
 
 int gpx_gp_dm_dtheta(gpx_gp_t *g, const double *xo, int64_t m, double *out)
@@ -777,8 +718,7 @@ int gpx_gp_dm_dtheta(gpx_gp_t *g, const double *xo, int64_t m, double *out)
     GPX_ARG(m >= 0 && (m == 0 || (xo && out)), "bad arguments");
     if (m == 0) return GPX_OK;
     GPX_TRY(deriv_supported(g));
-    if (g->dtype == GPX_F64) return dm_t<double>(g, xo, m, out);
-    return dm_t<float>(g, xo, m, out);
+    return by_dtype(g->dtype, [&](auto t) { return dm_t<decltype(t)>(g, xo, m, out); });
 }
 
 

@@ -8,7 +8,7 @@
 // complement and its factorisation, two single-rhs solves for the new alpha (n^2 flops each).  What nothing else in the
 // library does well is here: the re-pitched copy of the factor's lower trapezoid (copy_lower) and the Schur complement of
 // a FEW rows against MANY columns (schur_lower).
-#include "gpx_common.h"
+#include "gpx_small.h"
 #include <algorithm>
 
 #include "gpx_gp_internal.h"
@@ -38,16 +38,7 @@ __global__ __launch_bounds__(256) void copy_lower_kernel(const T *__restrict__ s
         if (aligned) {
             const VT *__restrict__ sv = reinterpret_cast<const VT *>(s);
             VT *__restrict__ dv = reinterpret_cast<VT *>(d);
-            const int64_t nv = row / VEC + 1;              // vectors up to the diagonal's
-            int64_t v = tid;
-            for (; v + 3 * 256 < nv; v += 4 * 256) {
-                VT t[4];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) t[u] = sv[v + u * 256];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) dv[v + u * 256] = t[u];
-            }
-            for (; v < nv; v += 256) dv[v] = sv[v];
+            copy_vecs(sv, dv, row / VEC + 1);              // vectors up to the diagonal's
         } else {
             for (int64_t c = tid; c <= row; c += 256) d[c] = s[c];
         }
@@ -63,19 +54,19 @@ int copy_lower(int dtype, const void *src, int64_t lds, void *dst, int64_t ldd, 
                         lds >= round_up(n, ch) && ldd >= round_up(n, ch);
     const dim3 grid((unsigned)cdiv(n, CL_ROWS)), block(256);
     ProfScope prof(PC_EXTEND, (double)n * (double)(n + 1) * (double)es, st);     // n (n + 1) / 2 elements read and written
-    if (dtype == GPX_F64)
-        hipLaunchKernelGGL((copy_lower_kernel<double>), grid, block, 0, st, (const double *)src, lds, (double *)dst, ldd, n, aligned);
-    else
-        hipLaunchKernelGGL((copy_lower_kernel<float>), grid, block, 0, st, (const float *)src, lds, (float *)dst, ldd, n, aligned);
-    GPX_LAUNCH_CHECK();
-    return GPX_OK;
+    return by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((copy_lower_kernel<T>), grid, block, 0, st, (const T *)src, lds, (T *)dst, ldd, n, aligned);
+        GPX_LAUNCH_CHECK();
+        return GPX_OK;
+    });
 }
 
 // ---- the Schur complement of few rows against many columns --------------------------------------------------------------
 // S (k x k) -= B B^T with B k x n.  As one product this is cdiv(k, 128)^2 tiles that each walk all n columns: k <= 128 and
 // n = 65536 is ONE workgroup with 2 * 128^2 * 65536 flops while every other CU idles.  B is cut into column slices; slice s
 // yields the partial Gram P_s = B[:, slice] B[:, slice]^T through the product kernel's batch form (count = whole slices,
-// sA = sB = slice width, beta = 0; the ragged last slice is a call of its own), and schur_reduce_kernel forms
+// sA = sB = slice width, beta = 0; the ragged last slice is a call of its own), and sum_slices_lower (gpx_sparse.hip) forms
 // S[i, j] - sum_s P_s[i, j] for j <= i in f64, s ascending, and stores once.  No atomics: the same bits every time.
 // The slice width: as many slices as give SCHUR_TARGET_WGS workgroups, but no slice narrower than SCHUR_MIN_SLICE
 // columns, rounded up to 128 columns (a multiple of the product kernel's k-step in both dtypes).  Measured on builds with
@@ -87,20 +78,6 @@ int copy_lower(int dtype, const void *src, int64_t lds, void *dst, int64_t ldd, 
 // One slice (n within a slice, or so many tiles that they fill the chip by themselves): no partials, no scratch, no
 // reduction -- one product S -= B B^T on the lower tiles.
 constexpr int64_t SCHUR_TARGET_WGS = 1024, SCHUR_MIN_SLICE = 256, SCHUR_SLICE_ALIGN = 128;
-
-template <typename T>
-__global__ __launch_bounds__(256) void schur_reduce_kernel(T *__restrict__ S, int64_t lds, const T *__restrict__ P, int64_t ldp,
-                                                           int64_t sP, int slices, int64_t k)
-{
-    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    for (int64_t i = blockIdx.y; i < k; i += gridDim.y) {
-        if (j > i) continue;
-        const T *__restrict__ p = P + i * ldp + j;
-        double acc = 0.0;
-        for (int s = 0; s < slices; ++s) acc += (double)p[(int64_t)s * sP];
-        S[i * lds + j] = (T)((double)S[i * lds + j] - acc);
-    }
-}
 
 static thread_local ThreadScratch g_schur_scr;      // the slices' partial Grams
 
@@ -133,13 +110,7 @@ int schur_lower(int dtype, const void *B, int64_t k, int64_t n, int64_t ldb, voi
     }
     const double elems = 0.5 * (double)k * (double)(k + 1);
     ProfScope prof(PC_EXTEND, elems * (double)(slices + 2) * (double)es, st);   // the partials and S read, S written
-    const dim3 grid((unsigned)cdiv(k, 256), (unsigned)std::min<int64_t>(k, 32768)), block(256);
-    if (dtype == GPX_F64)
-        hipLaunchKernelGGL((schur_reduce_kernel<double>), grid, block, 0, st, (double *)S, lds, (const double *)P, ldp, sP, (int)slices, k);
-    else
-        hipLaunchKernelGGL((schur_reduce_kernel<float>), grid, block, 0, st, (float *)S, lds, (const float *)P, ldp, sP, (int)slices, k);
-    GPX_LAUNCH_CHECK();
-    return GPX_OK;
+    return sum_slices_lower(dtype, P, ldp, sP, (int)slices, k, S, S, lds, st);
 }
 
 // ---- the handle ---------------------------------------------------------------------------------------------------------

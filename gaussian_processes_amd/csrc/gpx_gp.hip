@@ -10,7 +10,7 @@
 //   alpha  (n,)    K^-1 y
 //   t0,t1  (n,)    solve scratch
 //   scal   GpScal (gpx_gp_internal.h): logdet, y^T alpha, the non-finite flags, potrf's info
-#include "gpx_common.h"
+#include "gpx_small.h"
 #include <cmath>
 #include <vector>
 
@@ -19,27 +19,7 @@
 namespace gpx {
 
 // ---- the staging pair: host float64 <-> device arrays of a handle's dtype ---------------------------------------------------
-// Both kernels: grid (column blocks of 256, rows up to 32768), a row loop for what lies beyond.  (T)double rounds to nearest.
-template <typename T>
-__global__ void cvt_from_f64_2d(const double *__restrict__ src, int64_t lds, T *__restrict__ dst, int64_t ldd, int64_t rows, int64_t cols)
-{
-    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= cols) return;
-    for (int64_t r = blockIdx.y; r < rows; r += gridDim.y) dst[r * ldd + c] = (T)src[r * lds + c];
-}
-
-template <typename T>
-__global__ void cvt_to_f64_2d(const T *__restrict__ src, int64_t lds, double *__restrict__ dst,
-                              int64_t ldd, int64_t rows, int64_t cols, int lower_only)
-{
-    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= cols) return;
-    for (int64_t r = blockIdx.y; r < rows; r += gridDim.y) {
-        const double v = (double)src[r * lds + c];
-        dst[r * ldd + c] = (lower_only && c > r) ? 0.0 : v;
-    }
-}
-
+// The conversions are element maps (gpx_small.h); (T)double rounds to nearest.
 // a (rows x cols) block of float64 from host to device or back: a vector by a plain copy, a matrix by a pitched one -- also
 // where both sides are dense (n = 8192: the plain copy of 512 MiB took 9.50 ms, the pitched one 9.35)
 static int copy_rows(void *dst, int64_t ldd, const void *src, int64_t lds, int64_t rows, int64_t cols, hipMemcpyKind kind, hipStream_t st)
@@ -59,9 +39,9 @@ int upload_f64(int dtype, void *dst, int64_t ldd, const double *src, int64_t lds
         if (!stage) stage = &mine;
         if (!stage->p) GPX_TRY(stage->alloc((size_t)rows * cols * 8));
         GPX_TRY(copy_rows(stage->p, cols, src, lds, rows, cols, hipMemcpyHostToDevice, st));
-        const dim3 grid((unsigned)cdiv(cols, 256), (unsigned)std::min<int64_t>(rows, 32768)), block(256);
-        hipLaunchKernelGGL((cvt_from_f64_2d<float>), grid, block, 0, st, (const double *)stage->p, cols, (float *)dst, ldd, rows, cols);
-        GPX_LAUNCH_CHECK();
+        const double *src64 = (const double *)stage->p;
+        float *dst32 = (float *)dst;
+        GPX_TRY(map_rows(rows, cols, st, [=] __device__(int64_t r, int64_t c) { dst32[r * ldd + c] = (float)src64[r * cols + c]; }));
     }
     GPX_HIP(hipStreamSynchronize(st));
     return GPX_OK;
@@ -74,14 +54,13 @@ int download_f64(int dtype, double *dst, int64_t ldh, const void *src, int64_t l
     DevBuf buf;
     GPX_TRY(buf.alloc((size_t)rows * cols * 8));
     double *tmp = (double *)buf.p;
-    dim3 grid((unsigned)cdiv(cols, 256), (unsigned)std::min<int64_t>(rows, 32768)), block(256);
-    if (dtype == GPX_F64)
-        hipLaunchKernelGGL((cvt_to_f64_2d<double>), grid, block, 0, st, (const double *)src, lds, tmp,
-                           cols, rows, cols, lower_only);
-    else
-        hipLaunchKernelGGL((cvt_to_f64_2d<float>), grid, block, 0, st, (const float *)src, lds, tmp, cols,
-                           rows, cols, lower_only);
-    GPX_LAUNCH_CHECK();
+    GPX_TRY(by_dtype(dtype, [&](auto t) {
+        const decltype(t) *s = (const decltype(t) *)src;
+        return map_rows(rows, cols, st, [=] __device__(int64_t r, int64_t c) {
+            const double v = (double)s[r * lds + c];
+            tmp[r * cols + c] = (lower_only && c > r) ? 0.0 : v;
+        });
+    }));
     GPX_TRY(copy_rows(dst, ldh, tmp, cols, rows, cols, hipMemcpyDeviceToHost, st));
     GPX_HIP(hipStreamSynchronize(st));
     return GPX_OK;
@@ -175,14 +154,13 @@ int gp_scan_finite(gpx_gp *g)
     GPX_HIP(hipMemsetAsync(flags, 0, 2 * sizeof(int), g->st));
     const int64_t nx = g->n * g->d, ny = g->n;
     const unsigned bx = (unsigned)std::min<int64_t>(cdiv(nx, 256), 1024), by = (unsigned)std::min<int64_t>(cdiv(ny, 256), 1024);
-    if (g->dtype == GPX_F64) {
-        hipLaunchKernelGGL((nonfinite_kernel<double>), dim3(bx), dim3(256), 0, g->st, (const double *)g->x, nx, flags);
-        hipLaunchKernelGGL((nonfinite_kernel<double>), dim3(by), dim3(256), 0, g->st, (const double *)g->y, ny, flags + 1);
-    } else {
-        hipLaunchKernelGGL((nonfinite_kernel<float>), dim3(bx), dim3(256), 0, g->st, (const float *)g->x, nx, flags);
-        hipLaunchKernelGGL((nonfinite_kernel<float>), dim3(by), dim3(256), 0, g->st, (const float *)g->y, ny, flags + 1);
-    }
-    GPX_LAUNCH_CHECK();
+    GPX_TRY(by_dtype(g->dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((nonfinite_kernel<T>), dim3(bx), dim3(256), 0, g->st, (const T *)g->x, nx, flags);
+        hipLaunchKernelGGL((nonfinite_kernel<T>), dim3(by), dim3(256), 0, g->st, (const T *)g->y, ny, flags + 1);
+        GPX_LAUNCH_CHECK();
+        return GPX_OK;
+    }));
     int h[2] = {0, 0};
     GPX_HIP(hipMemcpyAsync(h, flags, sizeof(h), hipMemcpyDeviceToHost, g->st));
     GPX_HIP(hipStreamSynchronize(g->st));

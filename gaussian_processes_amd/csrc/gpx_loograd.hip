@@ -14,52 +14,12 @@
 // (gpx_gp_loo_grad_weights forms one, in float64, for the caller who asked for it).
 // k is read from the rows of X -- k_i = |row i of L^-T|^2, float64 sums, the very kernel gpx_gp_loo's sweep ends with --
 // rather than from the diagonal of W, so the value that comes out of this call is gpx_gp_loo's bit for bit, in fp32 too.
-#include "gpx_common.h"
+#include "gpx_small.h"
 #include <cmath>
 
 #include "gpx_gp_internal.h"
 
 namespace gpx {
-
-// u = alpha / k and sqrt(c), in the system's dtype; one thread per point.  k > 0 for every factor that exists.
-template <typename T>
-__global__ void loo_weights_kernel(const double *__restrict__ kii, const T *__restrict__ alpha, int64_t n, T *__restrict__ u,
-                                   T *__restrict__ sq)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const double k = kii[i], a = (double)alpha[i];
-    const double c = 0.5 * (1.0 + a * a / k) / k;
-    u[i] = (T)(a / k);
-    sq[i] = (T)sqrt(c);
-}
-
-// Y[r, c] = W[r, c] sq[c]: eye_kernel's grid (column blocks of 256, rows up to 32768 and a row loop beyond); columns < n only
-template <typename T>
-__global__ void col_scale_kernel(const T *__restrict__ W, const T *__restrict__ sq, T *__restrict__ Y, int64_t n, int64_t ld)
-{
-    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= n) return;
-    const T s = sq[c];
-    for (int64_t r = blockIdx.y; r < n; r += gridDim.y) Y[r * ld + c] = W[r * ld + c] * s;
-}
-
-// G (n x n float64, dense) from alpha, r and the lower triangle of Pm: entry (a, b) and its mirror from the same
-// expression in the same order of operands, so G is symmetric bit for bit
-template <typename T>
-__global__ void loo_g_kernel(const T *__restrict__ alpha, const T *__restrict__ rv, const T *__restrict__ Pm, int64_t ldp,
-                             double *__restrict__ G, int64_t n)
-{
-    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= n) return;
-    const double ac = (double)alpha[c], rc = (double)rv[c];
-    for (int64_t r = blockIdx.y; r < n; r += gridDim.y) {
-        const int64_t hi = r > c ? r : c, lo = r > c ? c : r;
-        const double ah = r > c ? (double)alpha[r] : ac, rh = r > c ? (double)rv[r] : rc;
-        const double al = r > c ? ac : (double)alpha[r], rl = r > c ? rc : (double)rv[r];
-        G[r * n + c] = 0.5 * (rh * al + ah * rl) - (double)Pm[hi * ldp + lo];
-    }
-}
 
 static inline size_t pad256(size_t b) { return (b + 255) / 256 * 256; }
 
@@ -88,20 +48,30 @@ int loo_weights_vectors(int dtype, const void *L, int64_t n, int64_t ldl, const 
     if (kii_have) GPX_TRY(loo_points(dtype, kii, y, alpha, n, nullptr, nullptr, v.logp, st));
     else GPX_TRY(loo_rows(dtype, X, n, n, ldl, 0, y, alpha, v.kii, nullptr, nullptr, v.logp, st));
     GPX_TRY(sum_f64(v.logp, n, v.sums, st));
-    const dim3 g1((unsigned)cdiv(n, 256)), block(256);
-    if (dtype == GPX_F64) hipLaunchKernelGGL((loo_weights_kernel<double>), g1, block, 0, st, kii, (const double *)alpha, n, (double *)v.u, (double *)v.sq);
-    else hipLaunchKernelGGL((loo_weights_kernel<float>), g1, block, 0, st, kii, (const float *)alpha, n, (float *)v.u, (float *)v.sq);
-    GPX_LAUNCH_CHECK();
+    // u = alpha / k and sqrt(c), in the system's dtype; one thread per point.  k > 0 for every factor that exists.
+    GPX_TRY(by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        const T *al = (const T *)alpha;
+        T *u = (T *)v.u, *sq = (T *)v.sq;
+        return map_vec(n, st, [=] __device__(int64_t i) {
+            const double k = kii[i], a = (double)al[i];
+            const double c = 0.5 * (1.0 + a * a / k) / k;
+            u[i] = (T)(a / k);
+            sq[i] = (T)sqrt(c);
+        });
+    }));
     // r = W (alpha / k) = L^-T (L^-1 u): two sweeps with the factor (its block operators where it has them), not a product with W
     GPX_TRY(trsv_lower(dtype, L, n, ldl, v.u, v.t, 0, st, nullptr, ops));
     GPX_TRY(trsv_lower(dtype, L, n, ldl, v.t, v.r, 1, st, nullptr, ops));
     GPX_TRY(dot(dtype, v.r, alpha, n, v.sums + 1, st));
     // Y = W diag(sqrt(c)) over X: X's rows have been read (k), nothing else needs L^-T
-    const dim3 g2((unsigned)cdiv(n, 256), (unsigned)std::min<int64_t>(n, 32768));
-    if (dtype == GPX_F64) hipLaunchKernelGGL((col_scale_kernel<double>), g2, block, 0, st, (const double *)W, (const double *)v.sq, (double *)X, n, ldl);
-    else hipLaunchKernelGGL((col_scale_kernel<float>), g2, block, 0, st, (const float *)W, (const float *)v.sq, (float *)X, n, ldl);
-    GPX_LAUNCH_CHECK();
-    return GPX_OK;
+    // Y[r, c] = W[r, c] sq[c]; columns < n only
+    return by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        const T *w = (const T *)W, *sq = (const T *)v.sq;
+        T *Y = (T *)X;
+        return map_rows(n, n, st, [=] __device__(int64_t r, int64_t c) { Y[r * ldl + c] = w[r * ldl + c] * sq[c]; });
+    });
 }
 
 // Pm = Y Y^T, lower triangle, over W (dead: k and Y exist).  gemm_nt on its triangular route: the tiles above the diagonal
@@ -199,14 +169,21 @@ int gpx_gp_loo_grad_weights(gpx_gp_t *g, double *G, int64_t ld)
     DevBuf Gd;
     GPX_TRY(Gd.alloc((size_t)n * n * sizeof(double)));
     GPX_TRY(loo_weights_of_handle(g, &w));
-    const dim3 grid((unsigned)cdiv(n, 256), (unsigned)std::min<int64_t>(n, 32768)), block(256);
-    if (g->dtype == GPX_F64)
-        hipLaunchKernelGGL((loo_g_kernel<double>), grid, block, 0, g->st, (const double *)g->alpha, (const double *)w.v.r,
-                           (const double *)w.W.p, g->lda, (double *)Gd.p, n);
-    else
-        hipLaunchKernelGGL((loo_g_kernel<float>), grid, block, 0, g->st, (const float *)g->alpha, (const float *)w.v.r,
-                           (const float *)w.W.p, g->lda, (double *)Gd.p, n);
-    GPX_LAUNCH_CHECK();
+    // G (n x n float64, dense) from alpha, r and the lower triangle of Pm: entry (a, b) and its mirror from the same
+    // expression in the same order of operands, so G is symmetric bit for bit
+    GPX_TRY(by_dtype(g->dtype, [&](auto t) {
+        using T = decltype(t);
+        const T *alpha = (const T *)g->alpha, *rv = (const T *)w.v.r, *Pm = (const T *)w.W.p;
+        const int64_t ldp = g->lda;
+        double *Gp = (double *)Gd.p;
+        return map_rows(n, n, g->st, [=] __device__(int64_t r, int64_t c) {
+            const double ac = (double)alpha[c], rc = (double)rv[c];
+            const int64_t hi = r > c ? r : c, lo = r > c ? c : r;
+            const double ah = r > c ? (double)alpha[r] : ac, rh = r > c ? (double)rv[r] : rc;
+            const double al = r > c ? ac : (double)alpha[r], rl = r > c ? rc : (double)rv[r];
+            Gp[r * n + c] = 0.5 * (rh * al + ah * rl) - (double)Pm[hi * ldp + lo];
+        });
+    }));
     return download_f64(GPX_F64, G, ld, Gd.p, n, n, n, 0, g->st);
 }
 

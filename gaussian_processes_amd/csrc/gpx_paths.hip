@@ -5,7 +5,7 @@
 // without materialising it (gpx_d_kmat_apply; its input-space gradient gpx_d_kmat_apply_grad is gpx_stream.hip's) -- and the
 // handle that owns one set of paths (gpx_gp_paths_create, gpx_paths_*).  include/gpx.h has the
 // definition of every random input; tests/_paths_helpers.py restates it in numpy.
-#include "gpx_common.h"
+#include "gpx_small.h"
 #include "gpx_kernels_dev.h"
 #include "gpx_gp_internal.h"
 #include <algorithm>
@@ -55,12 +55,12 @@ int rff_features(int dtype, const void *pts, int64_t m, int d, const double *ome
     if (m <= 0 || F <= 0) return GPX_OK;
     const dim3 grid((unsigned)cdiv(F, 256), (unsigned)std::min<int64_t>(m, 32768)), block(256);
     ProfScope prof(PC_RFF, 2.0 * (double)m * (double)F * (double)esize(dtype), st);
-    if (dtype == GPX_F64)
-        hipLaunchKernelGGL((rff_features_kernel<double>), grid, block, 0, st, (const double *)pts, m, d, omega_dev, F, scale, (double *)out, ld);
-    else
-        hipLaunchKernelGGL((rff_features_kernel<float>), grid, block, 0, st, (const float *)pts, m, d, omega_dev, F, scale, (float *)out, ld);
-    GPX_LAUNCH_CHECK();
-    return GPX_OK;
+    return by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((rff_features_kernel<T>), grid, block, 0, st, (const T *)pts, m, d, omega_dev, F, scale, (T *)out, ld);
+        GPX_LAUNCH_CHECK();
+        return GPX_OK;
+    });
 }
 
 // ---------------------------------------------------------------------------
@@ -101,12 +101,13 @@ int rff_features_grad(int dtype, const void *pts, int64_t m, int d, const double
     for (int k = 0; k < GPX_ARD_MAX_D; ++k) sd.w[k] = (col_div && k < d) ? scale / col_div[k] : scale;
     const dim3 grid((unsigned)cdiv(F, 256), (unsigned)std::min<int64_t>(m, 32768)), block(256);
     ProfScope prof(PC_RFF, 2.0 * (double)m * (double)d * (double)F * (double)esize(dtype), st);
-#define GPX_RFFG_LAUNCH(T, DIV) hipLaunchKernelGGL((rff_features_grad_kernel<T, DIV>), grid, block, 0, st, (const T *)pts, m, d, omega_dev, F, scale, sd, (T *)out, ld)
-    if (dtype == GPX_F64) { if (col_div) GPX_RFFG_LAUNCH(double, true); else GPX_RFFG_LAUNCH(double, false); }
-    else { if (col_div) GPX_RFFG_LAUNCH(float, true); else GPX_RFFG_LAUNCH(float, false); }
-#undef GPX_RFFG_LAUNCH
-    GPX_LAUNCH_CHECK();
-    return GPX_OK;
+    return by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        if (col_div) hipLaunchKernelGGL((rff_features_grad_kernel<T, true>), grid, block, 0, st, (const T *)pts, m, d, omega_dev, F, scale, sd, (T *)out, ld);
+        else hipLaunchKernelGGL((rff_features_grad_kernel<T, false>), grid, block, 0, st, (const T *)pts, m, d, omega_dev, F, scale, sd, (T *)out, ld);
+        GPX_LAUNCH_CHECK();
+        return GPX_OK;
+    });
 }
 
 // ---------------------------------------------------------------------------
@@ -150,29 +151,16 @@ int kmat_apply(int dtype, int kernel, const void *xo, int64_t m, const void *x, 
 }
 
 // ---- the handle's small kernels --------------------------------------------------------------------------------------
-// a[i] = a[i] / div for i < count (a true division: Omega = z / w_v as numpy divides)
-__global__ void paths_div_kernel(double *__restrict__ a, int64_t count, double div)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < count) a[i] = a[i] / div;
-}
-
-// R[s, j] = mul * R[s, j]  (alpha == null)   or   R[s, j] = alpha[j] - R[s, j];   grid (column blocks of 256, rows up to 32768)
-template <typename T>
-__global__ void paths_rows_kernel(T *__restrict__ R, int64_t ld, int64_t rows, int64_t cols, T mul, const T *__restrict__ alpha)
-{
-    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= cols) return;
-    for (int64_t r = blockIdx.y; r < rows; r += gridDim.y) R[r * ld + c] = alpha ? alpha[c] - R[r * ld + c] : mul * R[r * ld + c];
-}
-
+// R[s, j] = mul * R[s, j]  (alpha == null)   or   R[s, j] = alpha[j] - R[s, j];   mul in the rows' dtype
 static int paths_rows(int dtype, void *R, int64_t ld, int64_t rows, int64_t cols, double mul, const void *alpha, hipStream_t st)
 {
-    const dim3 grid((unsigned)cdiv(cols, 256), (unsigned)std::min<int64_t>(rows, 32768)), block(256);
-    if (dtype == GPX_F64) hipLaunchKernelGGL((paths_rows_kernel<double>), grid, block, 0, st, (double *)R, ld, rows, cols, mul, (const double *)alpha);
-    else hipLaunchKernelGGL((paths_rows_kernel<float>), grid, block, 0, st, (float *)R, ld, rows, cols, (float)mul, (const float *)alpha);
-    GPX_LAUNCH_CHECK();
-    return GPX_OK;
+    return by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        T *Rt = (T *)R;
+        const T *a = (const T *)alpha;
+        const T m = (T)mul;
+        return map_rows(rows, cols, st, [=] __device__(int64_t r, int64_t c) { Rt[r * ld + c] = a ? a[c] - Rt[r * ld + c] : m * Rt[r * ld + c]; });
+    });
 }
 
 // rows of a feature chunk: a multiple of 128 (the shifted C pointer of R += Theta Phi_c^T stays aligned), at most 4096, within
@@ -212,8 +200,11 @@ static int paths_build(gpx_gp *g, gpx_paths *p)
     GPX_HIP(hipMemcpyAsync(p->pts, v.x, (size_t)n * d * es, hipMemcpyDeviceToDevice, st));
     // Omega = z(seed, 1, .) / w_v
     GPX_TRY(randn(GPX_F64, p->omega, F, d, d, p->seed, 1, 0, st));
-    hipLaunchKernelGGL(paths_div_kernel, dim3((unsigned)cdiv(F * d, 256)), dim3(256), 0, st, p->omega, F * d, p->iso[1]);
-    GPX_LAUNCH_CHECK();
+    {                                                      // (a true division, as numpy divides)
+        double *omega = p->omega;
+        const double div = p->iso[1];
+        GPX_TRY(map_vec(F * d, st, [=] __device__(int64_t i) { omega[i] = omega[i] / div; }));
+    }
     if (S == 0) { GPX_HIP(hipStreamSynchronize(st)); return GPX_OK; }
     GPX_HIP(hipMemsetAsync(p->theta, 0, (size_t)S * p->ldt * es, st));
     GPX_HIP(hipMemsetAsync(p->V, 0, (size_t)S * p->ldv * es, st));

@@ -163,25 +163,6 @@ int trsm_rows(int dtype, void *X, int64_t ldx, int64_t rows, const void *Ljj, in
     return launch_trsm_rows<float>(X, ldx, rows, Ljj, ldl, jb, st, bt);
 }
 
-template <typename T>
-__global__ void tril_kernel(T *__restrict__ A, int64_t n, int64_t lda)
-{
-    for (int64_t i = blockIdx.y; i < n; i += gridDim.y)
-        for (int64_t c = i + 1 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; c < n;
-             c += (int64_t)gridDim.x * blockDim.x)
-            A[i * lda + c] = (T)0;
-}
-
-int tril(int dtype, void *A, int64_t n, int64_t lda, hipStream_t st)
-{
-    if (n <= 1) return GPX_OK;
-    dim3 grid((unsigned)std::min<int64_t>(cdiv(n, 256), 64), (unsigned)std::min<int64_t>(n, 32768)), block(256);
-    if (dtype == GPX_F64) hipLaunchKernelGGL((tril_kernel<double>), grid, block, 0, st, (double *)A, n, lda);
-    else hipLaunchKernelGGL((tril_kernel<float>), grid, block, 0, st, (float *)A, n, lda);
-    GPX_LAUNCH_CHECK();
-    return GPX_OK;
-}
-
 static int64_t outer_block(int64_t n, bool batched = false)
 {
     const int64_t forced = tune().potrf_nb;

@@ -14,7 +14,7 @@
 // carried by V alone: stream order is enough); inside a block groups of G (16 or 32) vectors outermost, then the block's columns,
 // then the group's vectors.  Within one column the b's of different vectors do not depend on each other (a rotation only
 // clears its own b), so the pivots are the partial sums a^2 + sum b_q^2 and all c, s of a (column, group) are formed at once.
-#include "gpx_common.h"
+#include "gpx_small.h"
 #include <algorithm>
 
 #include "gpx_gp_internal.h"
@@ -296,16 +296,8 @@ __global__ __launch_bounds__(256) void del_copy_rows_kernel(const T *__restrict_
         const int64_t nc = t + 1 < cols ? t + 1 : cols, nv = aligned ? nc / VEC : 0;
         const VT *__restrict__ sv = reinterpret_cast<const VT *>(s);
         VT *__restrict__ dv = reinterpret_cast<VT *>(d);
-        int64_t c = tid;
-        for (; c + 3 * 256 < nv; c += 4 * 256) {
-            VT w[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) w[u] = sv[c + u * 256];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) dv[c + u * 256] = w[u];
-        }
-        for (; c < nv; c += 256) dv[c] = sv[c];
-        for (c = nv * VEC + tid; c < nc; c += 256) d[c] = s[c];
+        copy_vecs(sv, dv, nv);
+        for (int64_t c = nv * VEC + tid; c < nc; c += 256) d[c] = s[c];
     }
 }
 
@@ -389,8 +381,7 @@ static int chol_delete_t(const T *L, int64_t n, int64_t ldl, const int64_t *idx_
 static int chol_delete_dev(int dtype, const void *L, int64_t n, int64_t ldl, const int64_t *idx_host, const int64_t *idx_dev, int64_t k,
                            void *V, void *out, int64_t ldo, hipStream_t st)
 {
-    if (dtype == GPX_F64) return chol_delete_t<double>((const double *)L, n, ldl, idx_host, idx_dev, k, (double *)V, (double *)out, ldo, st);
-    return chol_delete_t<float>((const float *)L, n, ldl, idx_host, idx_dev, k, (float *)V, (float *)out, ldo, st);
+    return by_dtype(dtype, [&](auto t) { using T = decltype(t); return chol_delete_t<T>((const T *)L, n, ldl, idx_host, idx_dev, k, (T *)V, (T *)out, ldo, st); });
 }
 
 int chol_delete(int dtype, const void *L, int64_t n, int64_t ldl, const int64_t *idx_host, int64_t k, void *out, int64_t ldo, hipStream_t st)
@@ -427,13 +418,12 @@ static int remove_impl(gpx_gp *g, const int64_t *idx, int64_t k, gpx_gp_t **out,
     GPX_TRY(del_scratch(g->dtype, n, idx, k, &idx_dev, &V, st));
     // 1. the kept points, gathered on the device
     const dim3 grid((unsigned)cdiv(n2 * (d + 1), 256)), block(256);
-    if (g->dtype == GPX_F64)
-        hipLaunchKernelGGL((del_gather_kernel<double>), grid, block, 0, st, (const double *)g->x, (const double *)g->y, d, idx_dev, k, n2,
-                           (double *)g2->x, (double *)g2->y);
-    else
-        hipLaunchKernelGGL((del_gather_kernel<float>), grid, block, 0, st, (const float *)g->x, (const float *)g->y, d, idx_dev, k, n2,
-                           (float *)g2->x, (float *)g2->y);
-    GPX_LAUNCH_CHECK();
+    GPX_TRY(by_dtype(g->dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((del_gather_kernel<T>), grid, block, 0, st, (const T *)g->x, (const T *)g->y, d, idx_dev, k, n2, (T *)g2->x, (T *)g2->y);
+        GPX_LAUNCH_CHECK();
+        return GPX_OK;
+    }));
     memcpy(g2->params, g->params, sizeof(g->params));
     g2->s = g->s;
     g2->have_data = true; g2->have_params = g->have_params; g2->have_K = false;    // (a fit has consumed the source's K, if it had one)

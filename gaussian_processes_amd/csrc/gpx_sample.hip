@@ -9,7 +9,7 @@
 // with the Philox constants and round of Random123 (Salmon et al., SC11).  Nothing else enters: not the grid, not the pitch, not
 // the way a caller cuts a matrix into calls -- element (i, j) of a rows x cols call is e = offset + i cols + j.  All of it is
 // fp64 for both dtypes; the one rounding to fp32 is the store.  tests/_sample_helpers.py restates it in numpy.
-#include "gpx_common.h"
+#include "gpx_small.h"
 #include <algorithm>
 
 namespace gpx {
@@ -63,47 +63,27 @@ int randn(int dtype, void *out, int64_t rows, int64_t cols, int64_t ld, uint64_t
     if (blocks > 0x7fffffff) { set_error("randn: %lld elements are more than one launch covers", (long long)total); return GPX_ERR_ARG; }
     ProfScope prof(PC_RANDN, (double)total * (double)esize(dtype), st);
     const dim3 grid((unsigned)blocks), block(256);
-    if (dtype == GPX_F64)
-        hipLaunchKernelGGL((randn_kernel<double>), grid, block, 0, st, (double *)out, cols, ld, total, q0, (int)(offset & 1), pairs, seed, stream);
-    else
-        hipLaunchKernelGGL((randn_kernel<float>), grid, block, 0, st, (float *)out, cols, ld, total, q0, (int)(offset & 1), pairs, seed, stream);
-    GPX_LAUNCH_CHECK();
-    return GPX_OK;
+    return by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((randn_kernel<T>), grid, block, 0, st, (T *)out, cols, ld, total, q0, (int)(offset & 1), pairs, seed, stream);
+        GPX_LAUNCH_CHECK();
+        return GPX_OK;
+    });
 }
 
 // ---- from a covariance to samples ---------------------------------------------------------------------------------------
 template <typename T>
-__global__ void add_diag_kernel(T *__restrict__ C, int64_t ldc, int64_t m, T v)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < m) C[i * ldc + i] += v;
-}
-
-// out[r, c] = mean[c] (null: 0) for r < rows, c < cols: grid (column blocks of 256, rows up to 32768), a row loop beyond
-template <typename T>
-__global__ void fill_rows_kernel(T *__restrict__ out, int64_t ldo, const T *__restrict__ mean, int64_t rows, int64_t cols)
-{
-    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= cols) return;
-    const T v = mean ? mean[c] : (T)0;
-    for (int64_t r = blockIdx.y; r < rows; r += gridDim.y) out[r * ldo + c] = v;
-}
-
-template <typename T>
 static int mvn_prepare_t(T *C, int64_t m, int64_t ldc, double jitter, hipStream_t st)
 {
-    hipLaunchKernelGGL((add_diag_kernel<T>), dim3((unsigned)cdiv(m, 256)), dim3(256), 0, st, C, ldc, m, (T)jitter);
-    GPX_LAUNCH_CHECK();
-    return GPX_OK;
+    const T v = (T)jitter;
+    return map_vec(m, st, [=] __device__(int64_t i) { C[i * ldc + i] += v; });
 }
 
+// out[r, c] = mean[c] (null: 0) for r < rows, c < cols
 template <typename T>
 static int fill_rows_t(T *out, int64_t ldo, const T *mean, int64_t rows, int64_t cols, hipStream_t st)
 {
-    const dim3 grid((unsigned)cdiv(cols, 256), (unsigned)std::min<int64_t>(rows, 32768)), block(256);
-    hipLaunchKernelGGL((fill_rows_kernel<T>), grid, block, 0, st, out, ldo, mean, rows, cols);
-    GPX_LAUNCH_CHECK();
-    return GPX_OK;
+    return map_rows(rows, cols, st, [=] __device__(int64_t r, int64_t c) { out[r * ldo + c] = mean ? mean[c] : (T)0; });
 }
 
 // out = 1 mean^T + Z Lc^T:  C + jitter I -> Lc in place (potrf, tril), Z = randn, then ONE full product against the
@@ -113,14 +93,12 @@ int mvn_sample(int dtype, void *C, int64_t m, int64_t ldc, const void *mean, dou
                void *Z, int64_t ldz, void *out, int64_t ldo, int *info_dev, hipStream_t st)
 {
     if (m <= 0) { GPX_HIP(hipMemsetAsync(info_dev, 0, sizeof(int), st)); return GPX_OK; }
-    if (dtype == GPX_F64) GPX_TRY(mvn_prepare_t<double>((double *)C, m, ldc, jitter, st));
-    else GPX_TRY(mvn_prepare_t<float>((float *)C, m, ldc, jitter, st));
+    GPX_TRY(by_dtype(dtype, [&](auto t) { using T = decltype(t); return mvn_prepare_t<T>((T *)C, m, ldc, jitter, st); }));
     GPX_TRY(potrf(dtype, C, m, ldc, info_dev, st));
     GPX_TRY(tril(dtype, C, m, ldc, st));
     if (S <= 0) return GPX_OK;
     GPX_TRY(randn(dtype, Z, S, m, ldz, seed, stream, 0, st));
-    if (dtype == GPX_F64) GPX_TRY(fill_rows_t<double>((double *)out, ldo, (const double *)mean, S, m, st));
-    else GPX_TRY(fill_rows_t<float>((float *)out, ldo, (const float *)mean, S, m, st));
+    GPX_TRY(by_dtype(dtype, [&](auto t) { using T = decltype(t); return fill_rows_t<T>((T *)out, ldo, (const T *)mean, S, m, st); }));
     return gemm_nt(dtype, S, m, m, Z, ldz, C, ldc, out, ldo, 1.0, GPX_FULL, 0, 0, st);
 }
 

@@ -12,7 +12,7 @@
 // trsv_fwd_fused / trsv_bwd_fused (steps), or trsv_op_kernel with per-block operators
 // built once per factor ("operator form" below; who may use them: ops_usable).
 // var_rows_kernel (the predictive variance's finishing pass) reads a solved m x n chunk once: rows n sizeof(T) bytes.
-#include "gpx_common.h"
+#include "gpx_small.h"
 #include "gpx_kernels_dev.h"
 #include "gpx_leaf.h"
 
@@ -778,9 +778,10 @@ int trsv_lower(int dtype, const void *L, int64_t n, int64_t ldl, void *b, void *
                hipStream_t st, const Batch *bt, TrsvOps *ops)
 {
     if (n <= 0) return GPX_OK;
-    if (dtype == GPX_F64)
-        return trsv_t<double>((const double *)L, n, ldl, (double *)b, (double *)x, transpose, st, -1, bt, ops);
-    return trsv_t<float>((const float *)L, n, ldl, (float *)b, (float *)x, transpose, st, -1, bt, ops);
+    return by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return trsv_t<T>((const T *)L, n, ldl, (T *)b, (T *)x, transpose, st, -1, bt, ops);
+    });
 }
 
 int trsv_ops_build(int dtype, const void *L, int64_t n, int64_t ldl, TrsvOps *ops, hipStream_t st)
@@ -788,8 +789,7 @@ int trsv_ops_build(int dtype, const void *L, int64_t n, int64_t ldl, TrsvOps *op
     if (!ops || !trsv_ops_whole_blocks(n) || !ops_usable(dtype, L, ldl)) return GPX_OK;   // the solve takes the step route
     GPX_TRY(ops->mem.reserve(trsv_ops_bytes(dtype, n), st));
     ops->invalidate();
-    if (dtype == GPX_F64) GPX_TRY(trsv_ops_prepare<double>((const double *)L, n, ldl, ops->mem.p, st));
-    else GPX_TRY(trsv_ops_prepare<float>((const float *)L, n, ldl, ops->mem.p, st));
+    GPX_TRY(by_dtype(dtype, [&](auto t) { using T = decltype(t); return trsv_ops_prepare<T>((const T *)L, n, ldl, ops->mem.p, st); }));
     ops->valid = true;
     ops->built = n / OB;
     return GPX_OK;
@@ -805,8 +805,7 @@ int trsv_ops_build_upto(int dtype, const void *L, int64_t n, int64_t ldl, TrsvOp
         ops->valid = false;
     }
     if (kend <= ops->built || !ops->mem.p) return GPX_OK;
-    if (dtype == GPX_F64) GPX_TRY(trsv_ops_prepare<double>((const double *)L, n, ldl, ops->mem.p, st, ops->built, kend));
-    else GPX_TRY(trsv_ops_prepare<float>((const float *)L, n, ldl, ops->mem.p, st, ops->built, kend));
+    GPX_TRY(by_dtype(dtype, [&](auto t) { using T = decltype(t); return trsv_ops_prepare<T>((const T *)L, n, ldl, ops->mem.p, st, ops->built, kend); }));
     ops->built = kend;
     if (kend == nfull) ops->valid = true;
     return GPX_OK;
@@ -816,9 +815,7 @@ int trsv_lower_cols(int dtype, const void *L, int64_t n, int64_t ldl, int64_t nc
                     hipStream_t st)
 {
     if (n <= 0 || ncols <= 0) return GPX_OK;
-    if (dtype == GPX_F64)
-        return trsv_t<double>((const double *)L, n, ldl, (double *)b, (double *)x, 0, st, ncols);
-    return trsv_t<float>((const float *)L, n, ldl, (float *)b, (float *)x, 0, st, ncols);
+    return by_dtype(dtype, [&](auto t) { using T = decltype(t); return trsv_t<T>((const T *)L, n, ldl, (T *)b, (T *)x, 0, st, ncols); });
 }
 
 // y[c] -= sum_r Lp[r, c] * x[r]   (c < ncols <= 1024, r < rows): the transposed
@@ -860,19 +857,15 @@ int panel_gemv_t(int dtype, const void *Lp, int64_t ldl, int64_t rows, int64_t n
     if (rows <= 0 || ncols <= 0) return GPX_OK;
     const int64_t nchunks = cdiv(rows, 256);
     ProfScope prof(PC_TRSV, (double)rows * ncols * esize(dtype), st);
-    if (dtype == GPX_F64) {
-        hipLaunchKernelGGL((panel_gemv_t_partial<double>), dim3((unsigned)nchunks), dim3(256), 0, st,
-                           (const double *)Lp, ldl, rows, (int)ncols, (const double *)x, work);
-        hipLaunchKernelGGL((panel_gemv_t_reduce<double>), dim3((unsigned)cdiv(ncols, 256)), dim3(256), 0, st,
-                           work, nchunks, (int)ncols, (double *)y);
-    } else {
-        hipLaunchKernelGGL((panel_gemv_t_partial<float>), dim3((unsigned)nchunks), dim3(256), 0, st,
-                           (const float *)Lp, ldl, rows, (int)ncols, (const float *)x, work);
-        hipLaunchKernelGGL((panel_gemv_t_reduce<float>), dim3((unsigned)cdiv(ncols, 256)), dim3(256), 0, st,
-                           work, nchunks, (int)ncols, (float *)y);
-    }
-    GPX_LAUNCH_CHECK();
-    return GPX_OK;
+    return by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((panel_gemv_t_partial<T>), dim3((unsigned)nchunks), dim3(256), 0, st,
+                           (const T *)Lp, ldl, rows, (int)ncols, (const T *)x, work);
+        hipLaunchKernelGGL((panel_gemv_t_reduce<T>), dim3((unsigned)cdiv(ncols, 256)), dim3(256), 0, st,
+                           work, nchunks, (int)ncols, (T *)y);
+        GPX_LAUNCH_CHECK();
+        return GPX_OK;
+    });
 }
 
 static thread_local ThreadScratch g_trsm_scr;   // the operator route: one m x 512 block of X per system
@@ -961,36 +954,6 @@ int trsm_right_lt(int dtype, const void *L, int64_t n, int64_t ldl, void *X, int
 }
 
 // ---- X <- X L^-1: the backward sweep over many right-hand sides -------------------------------------------
-// dst (cols x rows, ldd) <- src (rows x cols, lds)^T through 64 x 64 LDS tiles (transpose_subdiag_kernel's pattern for any
-// shape): loads and stores both run along a row, every index is checked against rows / cols.
-template <typename T>
-__global__ __launch_bounds__(256) void transpose_kernel(const T *__restrict__ src, int64_t lds, int64_t rows, int64_t cols,
-                                                        T *__restrict__ dst, int64_t ldd)
-{
-    __shared__ T tile[64][65];
-    const int64_t r0 = (int64_t)blockIdx.y * 64, c0 = (int64_t)blockIdx.x * 64;
-    for (int idx = threadIdx.x; idx < 64 * 64; idx += 256) {
-        const int r = idx >> 6, c = idx & 63;
-        if (r0 + r < rows && c0 + c < cols) tile[r][c] = src[(r0 + r) * lds + c0 + c];
-    }
-    __syncthreads();
-    for (int idx = threadIdx.x; idx < 64 * 64; idx += 256) {
-        const int c = idx >> 6, r = idx & 63;
-        if (r0 + r < rows && c0 + c < cols) dst[(c0 + c) * ldd + r0 + r] = tile[r][c];
-    }
-}
-
-static int transpose(int dtype, const void *src, int64_t lds, int64_t rows, int64_t cols, void *dst, int64_t ldd, hipStream_t st)
-{
-    if (rows <= 0 || cols <= 0) return GPX_OK;
-    const dim3 grid((unsigned)cdiv(cols, 64), (unsigned)cdiv(rows, 64)), block(256);
-    ProfScope prof(PC_TRANSPOSE, 2.0 * (double)rows * cols * esize(dtype), st);
-    if (dtype == GPX_F64) hipLaunchKernelGGL((transpose_kernel<double>), grid, block, 0, st, (const double *)src, lds, rows, cols, (double *)dst, ldd);
-    else hipLaunchKernelGGL((transpose_kernel<float>), grid, block, 0, st, (const float *)src, lds, rows, cols, (float *)dst, ldd);
-    GPX_LAUNCH_CHECK();
-    return GPX_OK;
-}
-
 // X[r, 0:jb] <- X[r, 0:jb] * Ljj^-1 for rows r < rows: trsm_rows (gpx_potrf.hip) mirrored, one lane per row, backward
 // substitution along the row:  x_c = (a_c - sum_{t > c} x_t L[t, c]) / L[c, c],  c = jb - 1 .. 0.  All lanes read the same
 // element of the staged block at the same time (an LDS broadcast).
@@ -1084,7 +1047,7 @@ int trsm_right_l(int dtype, const void *L, int64_t n, int64_t ldl, void *X, int6
                 GPX_TRY(gemm_nt(dtype, m, OB, OB, Xp(k0), ldx, Wtk, OB, scr, OB, 1.0, GPX_FULL, 0, 0, st, 1));
                 GPX_HIP(hipMemcpy2DAsync(Xp(k0), (size_t)ldx * es, scr, (size_t)OB * es, (size_t)OB * es, (size_t)m, hipMemcpyDeviceToDevice, st));
                 if (k0 > 0) {
-                    GPX_TRY(transpose(dtype, Lp(k0, 0), ldl, OB, k0, LT, OB, st));
+                    GPX_TRY(transpose(dtype, Lp(k0, 0), ldl, OB, k0, LT, OB, 0, st));
                     GPX_TRY(gemm_nt(dtype, m, k0, OB, Xp(k0), ldx, LT, OB, X, ldx, -1.0, GPX_FULL, 0, 0, st));
                 }
             }
@@ -1099,46 +1062,18 @@ int trsm_right_l(int dtype, const void *L, int64_t n, int64_t ldl, void *X, int6
     for (int64_t k0 = (n - 1) / NB * NB; k0 >= 0; k0 -= NB) {
         const int64_t kb = std::min(NB, n - k0), ke = k0 + kb;
         // LT[c][t] = L[k0 + t, c] for c < ke, t < kb (the block's own columns too: only what lies below a diagonal block is read)
-        GPX_TRY(transpose(dtype, Lp(k0, 0), ldl, kb, ke, LTv, ldt, st));
+        GPX_TRY(transpose(dtype, Lp(k0, 0), ldl, kb, ke, LTv, ldt, 0, st));
         for (int64_t j0 = k0 + (kb - 1) / SB * SB; j0 >= k0; j0 -= SB) {
             const int jb = (int)std::min<int64_t>(SB, ke - j0);
             const int64_t je = j0 + jb;
             if (je < ke)
                 GPX_TRY(gemm_nt(dtype, m, jb, ke - je, Xp(je), ldx, LT + (j0 * ldt + (je - k0)) * es, ldt, Xp(j0), ldx, -1.0,
                                 GPX_FULL, 0, 0, st));
-            if (dtype == GPX_F64) GPX_TRY(trsm_rows_l<double>(Xp(j0), ldx, m, Lp(j0, j0), ldl, jb, st));
-            else GPX_TRY(trsm_rows_l<float>(Xp(j0), ldx, m, Lp(j0, j0), ldl, jb, st));
+            GPX_TRY(by_dtype(dtype, [&](auto t) { return trsm_rows_l<decltype(t)>(Xp(j0), ldx, m, Lp(j0, j0), ldl, jb, st); }));
         }
         if (k0 > 0)
             GPX_TRY(gemm_nt(dtype, m, k0, kb, Xp(k0), ldx, LT, ldt, X, ldx, -1.0, GPX_FULL, 0, 0, st));
     }
-    return GPX_OK;
-}
-
-template <typename T>
-__global__ void eye_kernel(T *__restrict__ X, int64_t n, int64_t ld)
-{
-    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= ld) return;
-    for (int64_t r = blockIdx.y; r < n; r += gridDim.y) X[r * ld + c] = (c == r) ? (T)1 : (T)0;
-}
-
-// eye_kernel for a row chunk: X (rows x ld) <- rows [c0, c0 + rows) of the identity, columns [cz, ld) only (cz <= c0)
-template <typename T>
-__global__ void eye_rows_kernel(T *__restrict__ X, int64_t rows, int64_t ld, int64_t c0, int64_t cz)
-{
-    const int64_t c = cz + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= ld) return;
-    for (int64_t r = blockIdx.y; r < rows; r += gridDim.y) X[r * ld + c] = (c == c0 + r) ? (T)1 : (T)0;
-}
-
-int eye_rows(int dtype, void *X, int64_t rows, int64_t ld, int64_t c0, int64_t cz, hipStream_t st)
-{
-    if (rows <= 0 || cz >= ld) return GPX_OK;
-    const dim3 grid((unsigned)cdiv(ld - cz, 256), (unsigned)std::min<int64_t>(rows, 32768)), block(256);
-    if (dtype == GPX_F64) hipLaunchKernelGGL((eye_rows_kernel<double>), grid, block, 0, st, (double *)X, rows, ld, c0, cz);
-    else hipLaunchKernelGGL((eye_rows_kernel<float>), grid, block, 0, st, (float *)X, rows, ld, c0, cz);
-    GPX_LAUNCH_CHECK();
     return GPX_OK;
 }
 
@@ -1148,12 +1083,8 @@ int inv_from_factor(int dtype, const void *L, int64_t n, int64_t ldl, void *X, v
 {
     const size_t es = esize(dtype), nl = (size_t)n * ldl * es, ob = trsv_ops_bytes(dtype, n);
     if (count > 1 && !trsm_ops_ok(dtype, L, n, ldl)) { set_error("inv_from_factor: a lock-step group needs the operator route"); return GPX_ERR_ARG; }
-    dim3 grid((unsigned)cdiv(ldl, 256), (unsigned)std::min<int64_t>(n, 32768)), block(256);
     for (int i = 0; i < count; ++i) {
-        void *Xi = (char *)X + (size_t)i * nl;
-        if (dtype == GPX_F64) hipLaunchKernelGGL((eye_kernel<double>), grid, block, 0, st, (double *)Xi, n, ldl);
-        else hipLaunchKernelGGL((eye_kernel<float>), grid, block, 0, st, (float *)Xi, n, ldl);
-        GPX_LAUNCH_CHECK();
+        GPX_TRY(eye_rows(dtype, (char *)X + (size_t)i * nl, n, ldl, 0, 0, st));
         if (count > 1) {
             TrsvOps o = TrsvOps::view((char *)group_ops + (size_t)i * ob, ob);
             GPX_TRY(trsv_ops_build_upto(dtype, (const char *)L + (size_t)i * sL * es, n, ldl, &o, n / OB, st));
@@ -1165,70 +1096,6 @@ int inv_from_factor(int dtype, const void *L, int64_t n, int64_t ldl, void *X, v
     else GPX_TRY(trsm_right_lt(dtype, L, n, ldl, X, n, ldl, st, 1, ops));
     Batch bw; bw.count = count; bw.sA = bw.sB = bw.sC = sX;
     return gemm_nt(dtype, n, n, n, X, ldl, X, ldl, W, ldl, 1.0, tri, 0, 0, st, 0, 1, count > 1 ? &bw : nullptr);
-}
-
-// ---- reductions (single workgroup, fixed order => deterministic) ----------
-template <typename T, int MODE>   // MODE 0: sum a[i]*b[i]   1: 2*sum log a[i*stride]   2: sum a[i]
-__global__ __launch_bounds__(1024) void reduce_kernel(const T *__restrict__ a, const T *__restrict__ b,
-                                                      int64_t n, int64_t stride, double *__restrict__ out,
-                                                      int64_t sa, int64_t sb, int64_t so)
-{
-    // batched: workgroup blockIdx.x reduces vector pair blockIdx.x into out[blockIdx.x * so]
-    a += (int64_t)blockIdx.x * sa;
-    if (MODE == 0) b += (int64_t)blockIdx.x * sb;
-    out += (int64_t)blockIdx.x * so;
-    __shared__ double red[16];
-    const int tid = threadIdx.x;
-    double acc = 0.0;
-    for (int64_t i = tid; i < n; i += 1024) {
-        if (MODE == 0) acc = fma((double)a[i], (double)b[i], acc);
-        else if (MODE == 1) acc += log((double)a[i * stride]);
-        else acc += (double)a[i];
-    }
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
-    if ((tid & 63) == 0) red[tid >> 6] = acc;
-    __syncthreads();
-    if (tid == 0) {
-        double s = 0.0;
-        for (int w = 0; w < 16; ++w) s += red[w];
-        out[0] = (MODE == 1) ? 2.0 * s : s;
-    }
-}
-
-// count > 1: matrix i at L + i * sL, result in out_dev[i * so]
-int logdet_chol(int dtype, const void *L, int64_t n, int64_t ldl, double *out_dev, hipStream_t st, int count,
-                int64_t sL, int64_t so)
-{
-    if (dtype == GPX_F64)
-        hipLaunchKernelGGL((reduce_kernel<double, 1>), dim3(count), dim3(1024), 0, st, (const double *)L,
-                           (const double *)nullptr, n, ldl + 1, out_dev, sL, (int64_t)0, so);
-    else
-        hipLaunchKernelGGL((reduce_kernel<float, 1>), dim3(count), dim3(1024), 0, st, (const float *)L,
-                           (const float *)nullptr, n, ldl + 1, out_dev, sL, (int64_t)0, so);
-    GPX_LAUNCH_CHECK();
-    return GPX_OK;
-}
-
-// count > 1: pair i is (a + i * sa, b + i * sb), result in out_dev[i * so]
-int dot(int dtype, const void *a, const void *b, int64_t n, double *out_dev, hipStream_t st, int count, int64_t sa,
-        int64_t sb, int64_t so)
-{
-    if (dtype == GPX_F64)
-        hipLaunchKernelGGL((reduce_kernel<double, 0>), dim3(count), dim3(1024), 0, st, (const double *)a,
-                           (const double *)b, n, 1, out_dev, sa, sb, so);
-    else
-        hipLaunchKernelGGL((reduce_kernel<float, 0>), dim3(count), dim3(1024), 0, st, (const float *)a,
-                           (const float *)b, n, 1, out_dev, sa, sb, so);
-    GPX_LAUNCH_CHECK();
-    return GPX_OK;
-}
-
-int sum_f64(const double *a, int64_t n, double *out_dev, hipStream_t st)
-{
-    hipLaunchKernelGGL((reduce_kernel<double, 2>), dim3(1), dim3(1024), 0, st, a, (const double *)nullptr, n, 1, out_dev,
-                       (int64_t)0, (int64_t)0, (int64_t)0);
-    GPX_LAUNCH_CHECK();
-    return GPX_OK;
 }
 
 // ---- predictive variance: the finishing pass over a solved chunk X = K(xo_c, x) L^-T ---------------------------------
@@ -1330,8 +1197,7 @@ int var_rows(int dtype, int kernel, const void *X, int64_t rows, int64_t n, int6
     KParams kp;
     memset(&kp, 0, sizeof(kp));
     if (!accumulate && !kdiag_dev) GPX_TRY(make_kparams(kernel, GPX_K, params, 0.0, &kp));
-    if (dtype == GPX_F64) return launch_var_rows<double>(X, rows, n, ldx, xo, d, kp, kdiag_dev, accumulate, out_dev, st);
-    return launch_var_rows<float>(X, rows, n, ldx, xo, d, kp, kdiag_dev, accumulate, out_dev, st);
+    return by_dtype(dtype, [&](auto t) { return launch_var_rows<decltype(t)>(X, rows, n, ldx, xo, d, kp, kdiag_dev, accumulate, out_dev, st); });
 }
 
 int var_finish(int dtype, int kernel, const void *xo, int d, const double *params, const double *acc_dev, int64_t rows,
@@ -1341,12 +1207,12 @@ int var_finish(int dtype, int kernel, const void *xo, int d, const double *param
     KParams kp;
     GPX_TRY(make_kparams(kernel, GPX_K, params, 0.0, &kp));
     const dim3 grid((unsigned)cdiv(rows, 256)), block(256);
-    if (dtype == GPX_F64)
-        hipLaunchKernelGGL((var_finish_kernel<double>), grid, block, 0, st, (const double *)xo, d, kp, acc_dev, rows, out_dev);
-    else
-        hipLaunchKernelGGL((var_finish_kernel<float>), grid, block, 0, st, (const float *)xo, d, kp, acc_dev, rows, out_dev);
-    GPX_LAUNCH_CHECK();
-    return GPX_OK;
+    return by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((var_finish_kernel<T>), grid, block, 0, st, (const T *)xo, d, kp, acc_dev, rows, out_dev);
+        GPX_LAUNCH_CHECK();
+        return GPX_OK;
+    });
 }
 
 // ---- leave-one-out: the finishing pass over a solved chunk X = E_c L^-T (rows [c0, c0 + rows) of the identity) --------
@@ -1420,14 +1286,13 @@ int loo_rows(int dtype, const void *X, int64_t rows, int64_t n, int64_t ldx, int
     const int aligned = (ldx * (int64_t)es) % 16 == 0 && ((uintptr_t)X) % 16 == 0;
     const dim3 grid((unsigned)std::min<int64_t>(rows, 1 << 20)), block(256);
     ProfScope prof(PC_REDUCE, ((double)rows * (double)(n - c0) - 0.5 * (double)rows * (double)rows) * es, st);
-    if (dtype == GPX_F64)
-        hipLaunchKernelGGL((loo_rows_kernel<double>), grid, block, 0, st, (const double *)X, rows, n, ldx, c0, aligned,
-                           (const double *)y, (const double *)alpha, kii, mean, var, logp);
-    else
-        hipLaunchKernelGGL((loo_rows_kernel<float>), grid, block, 0, st, (const float *)X, rows, n, ldx, c0, aligned,
-                           (const float *)y, (const float *)alpha, kii, mean, var, logp);
-    GPX_LAUNCH_CHECK();
-    return GPX_OK;
+    return by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((loo_rows_kernel<T>), grid, block, 0, st, (const T *)X, rows, n, ldx, c0, aligned, (const T *)y, (const T *)alpha,
+                           kii, mean, var, logp);
+        GPX_LAUNCH_CHECK();
+        return GPX_OK;
+    });
 }
 
 int loo_points(int dtype, const double *kii, const void *y, const void *alpha, int64_t n, double *mean, double *var, double *logp,
@@ -1435,12 +1300,12 @@ int loo_points(int dtype, const double *kii, const void *y, const void *alpha, i
 {
     if (n <= 0) return GPX_OK;
     const dim3 grid((unsigned)cdiv(n, 256)), block(256);
-    if (dtype == GPX_F64)
-        hipLaunchKernelGGL((loo_point_kernel<double>), grid, block, 0, st, kii, (const double *)y, (const double *)alpha, n, mean, var, logp);
-    else
-        hipLaunchKernelGGL((loo_point_kernel<float>), grid, block, 0, st, kii, (const float *)y, (const float *)alpha, n, mean, var, logp);
-    GPX_LAUNCH_CHECK();
-    return GPX_OK;
+    return by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((loo_point_kernel<T>), grid, block, 0, st, kii, (const T *)y, (const T *)alpha, n, mean, var, logp);
+        GPX_LAUNCH_CHECK();
+        return GPX_OK;
+    });
 }
 
 }  // namespace gpx

@@ -11,10 +11,10 @@
 // multiplied by the product kernel of gpx_gemm.hip on the lower tiles.  Fusing the kernel evaluation into the product
 // would re-evaluate each operand panel once per output tile column (M / 128 times) in a build that is VALU-bound.
 // Phi is small and the depth enormous -- the opposite of a trailing update -- so the depth of a chunk is split over the
-// product's batch dimension: slice p of every chunk adds to partial accumulator p, and sum_slices_lower_kernel adds the
+// product's batch dimension: slice p of every chunk adds to partial accumulator p, and sum_slices_lower adds the
 // partials in slice order at the end.  No atomics: a repeated fit gives the same bits.
 // Everything after that is M x M: potrf, the triangular sweeps and the reductions the library already owns, plus the small
-// kernels of this file (mirror / transpose, B and the trace, the two-block variance rows).
+// kernels of this file (B and the trace, the two-block variance rows) and the transpose of gpx_small.hip, mirror mode included.
 //
 // Layout in HBM (dtype T, ldm = round_up(M, 16)):
 //   x (N, d)  y (N)  z (M, d)  [xs, zs: the ARD family's scaled copies]
@@ -22,7 +22,7 @@
 //   cvec, w, t0, t1        M each
 //   bacc                   M doubles
 //   work (grow-only)       G (M x cols) | the partial accumulators (slices x M x ldm)
-#include "gpx_common.h"
+#include "gpx_small.h"
 #include <algorithm>
 #include <cmath>
 #include <vector>
@@ -123,21 +123,6 @@ __device__ __forceinline__ double block256_sum(double v, double *red)
     return red[0];
 }
 
-// out[i, j] = sum_p P[p sP + i ldp + j], j <= i: the partial accumulators of the depth slices, p ascending, f64, one rounding
-template <typename T>
-__global__ __launch_bounds__(256) void sum_slices_lower_kernel(const T *__restrict__ P, int64_t ldp, int64_t sP, int slices, int64_t n,
-                                                               T *__restrict__ out, int64_t ldo)
-{
-    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    for (int64_t i = blockIdx.y; i < n; i += gridDim.y) {
-        if (j > i) continue;
-        const T *__restrict__ p = P + i * ldp + j;
-        double acc = 0.0;
-        for (int s = 0; s < slices; ++s) acc += (double)p[(int64_t)s * sP];
-        out[i * ldo + j] = (T)acc;
-    }
-}
-
 // acc[i] += sum_j G[i, j] y[j]: one workgroup per row (grid-stride), every lane its columns in index order, then the tree
 template <typename T>
 __global__ __launch_bounds__(256) void gemv_acc_kernel(const T *__restrict__ G, int64_t rows, int64_t cols, int64_t ldg,
@@ -150,26 +135,6 @@ __global__ __launch_bounds__(256) void gemv_acc_kernel(const T *__restrict__ G, 
         for (int64_t j = threadIdx.x; j < cols; j += 256) v = fma((double)g[j], (double)y[j], v);
         const double t = block256_sum(v, red);
         if (threadIdx.x == 0) acc[i] += t;
-    }
-}
-
-// out[j, i] = in[i, j] through a 32 x 32 tile in LDS.  mirror: in == out (no __restrict__), only the tiles at or below the
-// diagonal are read and only elements strictly above it are written -- nobody reads what another workgroup writes.
-template <typename T>
-__global__ __launch_bounds__(256) void transpose_kernel(const T *in, int64_t ldi, T *out, int64_t ldo, int64_t n, int mirror)
-{
-    __shared__ T tile[32][33];
-    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-    const int64_t bi = blockIdx.y, bj = blockIdx.x;        // tile row / tile column of `in`
-    if (mirror && bj > bi) return;
-    for (int r = ty; r < 32; r += 8) {
-        const int64_t i = bi * 32 + r, j = bj * 32 + tx;
-        if (i < n && j < n) tile[r][tx] = in[i * ldi + j];
-    }
-    __syncthreads();
-    for (int r = ty; r < 32; r += 8) {
-        const int64_t oi = bj * 32 + r, oj = bi * 32 + tx; // out[oi, oj] = in[oj, oi] = tile[tx][r]
-        if (oi < n && oj < n && (!mirror || oj > oi)) out[oi * ldo + oj] = tile[tx][r];
     }
 }
 
@@ -216,85 +181,64 @@ __global__ __launch_bounds__(256) void rows2_kernel(const T *__restrict__ V, con
 }
 
 // dst[i] = (T)(src[i] / div), src DOUBLE;  v[i] = (T)(v[i] / div)
-template <typename T>
-__global__ void cvt_div_kernel(const double *__restrict__ src, T *__restrict__ dst, int64_t n, double div)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) dst[i] = (T)(src[i] / div);
-}
-template <typename T>
-__global__ void div_kernel(T *__restrict__ v, int64_t n, double div)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) v[i] = (T)((double)v[i] / div);
-}
-
 static int cvt_div(int dtype, const double *src, void *dst, int64_t n, double div, hipStream_t st)
 {
-    const dim3 grid((unsigned)cdiv(n, 256)), block(256);
-    if (dtype == GPX_F64) hipLaunchKernelGGL((cvt_div_kernel<double>), grid, block, 0, st, src, (double *)dst, n, div);
-    else hipLaunchKernelGGL((cvt_div_kernel<float>), grid, block, 0, st, src, (float *)dst, n, div);
-    GPX_LAUNCH_CHECK();
-    return GPX_OK;
+    return by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        T *d = (T *)dst;
+        return map_vec(n, st, [=] __device__(int64_t i) { d[i] = (T)(src[i] / div); });
+    });
 }
 static int div_vec(int dtype, void *v, int64_t n, double div, hipStream_t st)
 {
-    const dim3 grid((unsigned)cdiv(n, 256)), block(256);
-    if (dtype == GPX_F64) hipLaunchKernelGGL((div_kernel<double>), grid, block, 0, st, (double *)v, n, div);
-    else hipLaunchKernelGGL((div_kernel<float>), grid, block, 0, st, (float *)v, n, div);
-    GPX_LAUNCH_CHECK();
-    return GPX_OK;
+    return by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        T *x = (T *)v;
+        return map_vec(n, st, [=] __device__(int64_t i) { x[i] = (T)((double)x[i] / div); });
+    });
 }
 
-static int sum_slices_lower(int dtype, const void *P, int64_t ldp, int64_t sP, int slices, int64_t n, void *out, int64_t ldo, hipStream_t st)
+// out[i, j] = sum_p P[p sP + i ldp + j], j <= i: the partial accumulators of the depth slices, p ascending, f64, one rounding.
+// minus_from (n x ldo, or null; may be out): out[i, j] = minus_from[i, j] - that sum, the subtraction in f64 before the rounding
+int sum_slices_lower(int dtype, const void *P, int64_t ldp, int64_t sP, int slices, int64_t n, const void *minus_from, void *out, int64_t ldo,
+                     hipStream_t st)
 {
-    if (n <= 0) return GPX_OK;
-    const dim3 grid((unsigned)cdiv(n, 256), (unsigned)std::min<int64_t>(n, 32768)), block(256);
-    if (dtype == GPX_F64)
-        hipLaunchKernelGGL((sum_slices_lower_kernel<double>), grid, block, 0, st, (const double *)P, ldp, sP, slices, n, (double *)out, ldo);
-    else
-        hipLaunchKernelGGL((sum_slices_lower_kernel<float>), grid, block, 0, st, (const float *)P, ldp, sP, slices, n, (float *)out, ldo);
-    GPX_LAUNCH_CHECK();
-    return GPX_OK;
+    return by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        const T *Pt = (const T *)P, *from = (const T *)minus_from;
+        T *o = (T *)out;
+        return map_rows(n, n, st, [=] __device__(int64_t i, int64_t j) {
+            if (j > i) return;
+            const T *p = Pt + i * ldp + j;
+            double acc = 0.0;
+            for (int s = 0; s < slices; ++s) acc += (double)p[(int64_t)s * sP];
+            o[i * ldo + j] = from ? (T)((double)from[i * ldo + j] - acc) : (T)acc;
+        });
+    });
 }
 
 static int gemv_acc(int dtype, const void *G, int64_t rows, int64_t cols, int64_t ldg, const void *y, double *acc, hipStream_t st)
 {
     if (rows <= 0 || cols <= 0) return GPX_OK;
     const dim3 grid((unsigned)std::min<int64_t>(rows, 1 << 20)), block(256);
-    if (dtype == GPX_F64)
-        hipLaunchKernelGGL((gemv_acc_kernel<double>), grid, block, 0, st, (const double *)G, rows, cols, ldg, (const double *)y, acc);
-    else
-        hipLaunchKernelGGL((gemv_acc_kernel<float>), grid, block, 0, st, (const float *)G, rows, cols, ldg, (const float *)y, acc);
-    GPX_LAUNCH_CHECK();
-    return GPX_OK;
-}
-
-static int transpose_sq(int dtype, const void *in, int64_t ldi, void *out, int64_t ldo, int64_t n, int mirror, hipStream_t st)
-{
-    if (n <= 0) return GPX_OK;
-    const int64_t t = cdiv(n, 32);
-    if (t > 65535) { set_error("transpose: n = %lld is beyond the grid", (long long)n); return GPX_ERR_ARG; }
-    const dim3 grid((unsigned)t, (unsigned)t), block(256);
-    ProfScope prof(PC_TRANSPOSE, (double)n * (double)n * (mirror ? 1.0 : 2.0) * (double)esize(dtype), st);
-    if (dtype == GPX_F64)
-        hipLaunchKernelGGL((transpose_kernel<double>), grid, block, 0, st, (const double *)in, ldi, (double *)out, ldo, n, mirror);
-    else
-        hipLaunchKernelGGL((transpose_kernel<float>), grid, block, 0, st, (const float *)in, ldi, (float *)out, ldo, n, mirror);
-    GPX_LAUNCH_CHECK();
-    return GPX_OK;
+    return by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((gemv_acc_kernel<T>), grid, block, 0, st, (const T *)G, rows, cols, ldg, (const T *)y, acc);
+        GPX_LAUNCH_CHECK();
+        return GPX_OK;
+    });
 }
 
 static int form_B(int dtype, const void *X, int64_t ldx, int64_t n, double s, void *B, int64_t ldb, double *trace_dev, hipStream_t st)
 {
     if (n <= 0) return GPX_OK;
     const dim3 grid((unsigned)cdiv(n, 256), (unsigned)std::min<int64_t>(n, 32768) + 1), block(256);
-    if (dtype == GPX_F64)
-        hipLaunchKernelGGL((form_B_kernel<double>), grid, block, 0, st, (const double *)X, ldx, n, s * s, (double *)B, ldb, trace_dev);
-    else
-        hipLaunchKernelGGL((form_B_kernel<float>), grid, block, 0, st, (const float *)X, ldx, n, s * s, (float *)B, ldb, trace_dev);
-    GPX_LAUNCH_CHECK();
-    return GPX_OK;
+    return by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((form_B_kernel<T>), grid, block, 0, st, (const T *)X, ldx, n, s * s, (T *)B, ldb, trace_dev);
+        GPX_LAUNCH_CHECK();
+        return GPX_OK;
+    });
 }
 
 // out_dev[i] = kdiag(i) - sum V^2 + sum W^2: the row sums here (into acc_dev, rows doubles), kdiag and the subtraction by var_finish (gpx_solve.hip), which
@@ -306,11 +250,12 @@ static int var_rows2(int dtype, int kernel, const void *V, const void *W, int64_
     {
         ProfScope prof(PC_REDUCE, 2.0 * (double)rows * (double)n * (double)esize(dtype), st);
         const dim3 grid((unsigned)std::min<int64_t>(rows, 1 << 20)), block(256);
-        if (dtype == GPX_F64)
-            hipLaunchKernelGGL((rows2_kernel<double>), grid, block, 0, st, (const double *)V, (const double *)W, rows, n, ldx, acc_dev);
-        else
-            hipLaunchKernelGGL((rows2_kernel<float>), grid, block, 0, st, (const float *)V, (const float *)W, rows, n, ldx, acc_dev);
-        GPX_LAUNCH_CHECK();
+        GPX_TRY(by_dtype(dtype, [&](auto t) {
+            using T = decltype(t);
+            hipLaunchKernelGGL((rows2_kernel<T>), grid, block, 0, st, (const T *)V, (const T *)W, rows, n, ldx, acc_dev);
+            GPX_LAUNCH_CHECK();
+            return GPX_OK;
+        }));
     }
     return var_finish(dtype, kernel, xo, d, params, acc_dev, rows, out_dev, st);
 }
@@ -400,16 +345,16 @@ static int sgp_fit(gpx_sgp *g, int64_t chunk_cols)
     }
     g->chunks_timed = chunks;
     GPX_HIP(hipMemsetAsync(g->Phi, 0, (size_t)M * ldm * es, st));
-    GPX_TRY(sum_slices_lower(dtype, Pacc, ldm, sP, slices, M, g->Phi, ldm, st));
+    GPX_TRY(sum_slices_lower(dtype, Pacc, ldm, sP, slices, M, nullptr, g->Phi, ldm, st));
     GPX_HIP(hipEventRecord(g->ev[2], st));
     // 3. the M x M tail
     GPX_TRY(dot(dtype, g->y, g->y, n, &g->scal->yy, st));
     // k(0): the first inducing point against itself, through the variance's finishing pass with a zero sum
     GPX_TRY(var_finish(dtype, v.kernel, v.z, g->d, v.params, &g->scal->zero, 1, &g->scal->k00, st));
     GPX_HIP(hipMemcpyAsync(g->Xf, g->Phi, (size_t)M * ldm * es, hipMemcpyDeviceToDevice, st));
-    GPX_TRY(transpose_sq(dtype, g->Xf, ldm, g->Xf, ldm, M, 1, st));                 // mirror: Phi, full
+    GPX_TRY(transpose(dtype, g->Xf, ldm, M, M, g->Xf, ldm, 1, st));               // mirror: Phi, full
     GPX_TRY(trsm_right_lt(dtype, g->Luu, M, ldm, g->Xf, M, ldm, st));               // Phi Luu^-T
-    GPX_TRY(transpose_sq(dtype, g->Xf, ldm, g->Xt, ldm, M, 0, st));                 // Luu^-1 Phi
+    GPX_TRY(transpose(dtype, g->Xf, ldm, M, M, g->Xt, ldm, 0, st));               // Luu^-1 Phi
     GPX_TRY(trsm_right_lt(dtype, g->Luu, M, ldm, g->Xt, M, ldm, st));               // X = Luu^-1 Phi Luu^-T
     GPX_TRY(form_B(dtype, g->Xt, ldm, M, g->s, g->LB, ldm, &g->scal->trX, st));
     GPX_TRY(potrf(dtype, g->LB, M, ldm, &g->scal->info2, st));
@@ -737,7 +682,7 @@ int gpx_d_sum_slices_lower(int dtype, const void *P, int64_t ldp, int64_t sP, in
     GPX_ARG(P && out && P != out, "NULL pointer or out == P");
     GPX_ARG(ldp >= n && ldo >= n && sP >= 0, "leading dimension too small");
     GPX_TRY(ensure_device());
-    return sum_slices_lower(dtype, P, ldp, sP, slices, n, out, ldo, S(stream));
+    return sum_slices_lower(dtype, P, ldp, sP, slices, n, nullptr, out, ldo, S(stream));
 }
 
 int gpx_d_gemv_acc(int dtype, const void *G, int64_t rows, int64_t cols, int64_t ldg, const void *y, double *acc_dev, void *stream)
@@ -758,7 +703,7 @@ int gpx_d_mirror_lower(int dtype, void *A, int64_t n, int64_t lda, void *stream)
     if (n == 0) return GPX_OK;
     GPX_ARG(A && lda >= n, "NULL pointer or leading dimension too small");
     GPX_TRY(ensure_device());
-    return transpose_sq(dtype, A, lda, A, lda, n, 1, S(stream));
+    return transpose(dtype, A, lda, n, n, A, lda, 1, S(stream));
 }
 
 int gpx_d_transpose(int dtype, const void *in, int64_t ldi, void *out, int64_t ldo, int64_t n, void *stream)
@@ -769,7 +714,7 @@ int gpx_d_transpose(int dtype, const void *in, int64_t ldi, void *out, int64_t l
     GPX_ARG(in && out && in != out, "NULL pointer or out == in");
     GPX_ARG(ldi >= n && ldo >= n, "leading dimension too small");
     GPX_TRY(ensure_device());
-    return transpose_sq(dtype, in, ldi, out, ldo, n, 0, S(stream));
+    return transpose(dtype, in, ldi, n, n, out, ldo, 0, S(stream));
 }
 
 int gpx_d_sgp_form_B(int dtype, const void *X, int64_t ldx, int64_t n, double s, void *B, int64_t ldb, double *trace_dev, void *stream)

@@ -172,7 +172,7 @@ int gpx_stream_wait_event(void *stream, void *event);
 #define GPX_PROF_GEMM_N64    10 /* gemm_nt_fast_kernel<T,64,1>: trailing updates of few tiles on 128 x 64 tiles; flops */
 #define GPX_PROF_TRANSPOSE   11 /* transpose_kernel: the row panels of L staged for X L^-1; bytes read + written */
 #define GPX_PROF_PRED_GRAD   12 /* pred_grad_kernel + its slice reduction; kernel evaluations m*n per window of dimensions */
-#define GPX_PROF_EXTEND      13 /* copy_lower_kernel + schur_reduce_kernel (gpx_gp_extend): bytes read + written */
+#define GPX_PROF_EXTEND      13 /* copy_lower_kernel + the fold of the Schur partials (gpx_gp_extend): bytes read + written */
 #define GPX_PROF_RANDN       14 /* randn_kernel (gpx_d_randn): bytes written */
 #define GPX_PROF_RFF         15 /* rff_features_kernel (gpx_d_rff_features): bytes written */
 #define GPX_PROF_KAPPLY      16 /* stream_apply_kernel + its slice reduction (gpx_d_kmat_apply, fused route): kernel evaluations m*n per group of weight vectors */

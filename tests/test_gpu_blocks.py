@@ -39,8 +39,8 @@ DTYPES = {"f64": (_lib.F64, np.float64, np.uint64, 2.0 ** -53), "f32": (_lib.F32
 _NAN_BITS = {np.float64: (0x7ff8000000a11ce5, 0x7ff80000000b0b00), np.float32: (0x7fc0a11c, 0x7fc00b0b)}
 
 
-def gamma(k):
-    return LD(k) * LD(U) / (LD(1) - LD(k) * LD(U))
+def gamma(k, u=U):
+    return LD(k) * LD(u) / (LD(1) - LD(k) * LD(u))
 
 
 def nan_in(npdt):
@@ -81,14 +81,15 @@ class Worst(object):
     def __init__(self, block, dtype):
         self.block, self.dtype, self.ratio, self.where = block, dtype, 0.0, ""
 
-    def check(self, got, ref, sum_abs, k, u_out, what):
-        """|got - ref| <= 4 (gamma_k sum_abs + u_out |ref|) componentwise; got must be finite."""
+    def check(self, got, ref, sum_abs, k, u_out, what, u_acc=U):
+        """|got - ref| <= 4 (gamma_k sum_abs + u_out |ref|) componentwise; got must be finite.  u_acc: the unit roundoff of
+        the accumulation (fp64 everywhere but in the product kernel behind schur_lower, which accumulates in T)."""
         got = np.asarray(got, dtype=np.float64)
         ref, sum_abs = np.asarray(ref, dtype=LD), np.asarray(sum_abs, dtype=LD)
         assert got.shape == ref.shape, what
         assert np.isfinite(got).all(), "%s: the result is not finite (something NaN was read)" % what
         err = np.abs(got.astype(LD) - ref)
-        tol = 4 * (gamma(k) * sum_abs + LD(u_out) * np.abs(ref))
+        tol = 4 * (gamma(k, u_acc) * sum_abs + LD(u_out) * np.abs(ref))
         with np.errstate(divide="ignore", invalid="ignore"):
             ratio = np.where(tol > 0, err / tol, np.where(err > 0, np.inf, 0.0))
         r = float(np.max(ratio)) if ratio.size else 0.0
@@ -188,7 +189,7 @@ def test_d_tril(dtype):
             assert same_bits(got[pad], A[pad]), what + ": padding"
 
 
-TRANSPOSE_N = (1, 31, 32, 33, 100, 300)
+TRANSPOSE_N = (1, 31, 32, 33, 63, 64, 65, 100, 130, 300)      # around one and two 32-wide tiles, several tiles, a ragged last one
 
 
 @pytest.mark.parametrize("dtype", ["f64", "f32"])
@@ -231,6 +232,44 @@ def test_d_mirror_lower(dtype):
             assert same_bits(got[low], A[low]), what + ": the lower triangle changed"
             assert np.array_equal(sq, np.tril(A[:n, :n]) + np.tril(A[:n, :n], -1).T), what
             assert same_bits(got[pad], A[pad]), what + ": padding"
+
+
+# ---- the Schur complement of few rows against many columns ---------------------------------------------------------------
+@pytest.mark.parametrize("dtype", ["f64", "f32"])
+def test_d_schur_lower(dtype):
+    """S (k x k, lower) -= B B^T, B k x n.  k = 70 is one 128-tile, so the slice width is round_up(max(256, cdiv(n, 1024)), 128)
+    = 256: n = 600 is two whole slices and a ragged one of 88 columns, their partial Grams folded by sum_slices_lower in its
+    subtracting mode (ldb = 608: the aligned product with beta = 0; ldb = 603: the cleared partials); n = 200 is ONE slice,
+    the product adds -B B^T straight into S and nothing is folded.
+    Bound: entry (i, j) is a sum of n + 1 terms -- S[i, j] and the n products -- whatever the slicing, and the rounding of a
+    partial Gram to T is one more node of that summation tree; the product kernel accumulates in T, so gamma_(n+1) is taken
+    with u_T (for T = double that is the file's gamma), and the one subtraction's result is rounded to T: u_T |ref|."""
+    did, npdt, _, ut = DTYPES[dtype]
+    lib, rng, worst = _lib.load(), np.random.RandomState(111), Worst("gpx_d_schur_lower", dtype)
+    k = 70
+    for n, ldb in ((600, 608), (600, 603), (200, 208)):
+        lds = round_up(k, 16) + 16
+        low, up, pad = _lower_upper(k, lds)
+        B = padded(rng, k, n, ldb, npdt)                                # NaN beyond column n
+        S0 = np.full((k + 1, lds), nan_in(npdt), dtype=npdt)            # NaN: the strict upper triangle, the pitch, the guard row
+        S0[low] = (rng.randn(int(low.sum())) * np.sqrt(n)).astype(npdt)
+        dB = DeviceBuffer.from_host(B)
+        got = []
+        for _ in range(2):
+            dS = DeviceBuffer.from_host(S0)
+            _lib.check(lib.gpx_d_schur_lower(did, dB.ptr, k, n, ldb, dS.ptr, lds, None))
+            sync()
+            got.append(dS.to_host())
+        what = "k = %d n = %d ldb = %d lds = %d" % (k, n, ldb, lds)
+        assert same_bits(got[0], got[1]), what + ": two runs differ"
+        assert same_bits(got[0][up | pad], S0[up | pad]), what + ": strict upper triangle / padding of S"
+        assert same_bits(dB.to_host(), B), what + ": the input"
+        Bl = B[:, :n].astype(LD)
+        il = np.tril_indices(k)
+        s0 = S0[:k, :k].astype(LD)[il]
+        prod = Bl[il[0]] * Bl[il[1]]                                    # (pairs, n): the n products of every entry
+        worst.check(got[0][:k, :k][il], s0 - prod.sum(1), np.abs(s0) + np.abs(prod).sum(1), n + 1, ut, what, u_acc=ut)
+    worst.report()
 
 
 # ---- the sparse fit's small kernels ---------------------------------------------------------------------------------------

@@ -177,11 +177,12 @@ def test_streamed_reductions_keep_one_copy_of_each_piece():
     assert sites(r"k -= \(?d\)?;\s*\+\+c") == {"gpx_kernels_dev.h": 1}
     assert sites(r"sqrt\(8\.0 \* \(double\)t") == {"gpx_kernels_dev.h": 1}
     assert sites(r"\bcdiv\(2048,") == {"gpx_stream.hip": 1}
-    # the 64-lane shuffle-down sum: the helper, the two sums that are no four-wave block sum (the 16-wave strided_sum_kernel
-    # and the one-value sum of gpx_solve.hip), and the one kernel that keeps the text written out because the helper changes
-    # its code: member_quad_trace_kernel's interleaved pair (22 more instructions) -- DESIGN "Streamed reductions".  The
-    # tile reductions of gpx_kmat.hip all go through the helper (one register array for S_0, the S_k and the trace)
-    assert sites(r"off = 32; off > 0; off >>= 1") == {"gpx_kernels_dev.h": 1, "gpx_deriv.hip": 2, "gpx_solve.hip": 1}
+    # the 64-lane shuffle-down sum: the helper, the one sum that is no four-wave block sum (the 16-wave reduce_kernel of
+    # gpx_small.hip, which the strided sum of gpx_deriv.hip has become a mode of), and the one kernel that keeps the text
+    # written out because the helper changes its code: member_quad_trace_kernel's interleaved pair (22 more instructions)
+    # -- DESIGN "Streamed reductions".  The tile reductions of gpx_kmat.hip all go through the helper (one register array
+    # for S_0, the S_k and the trace)
+    assert sites(r"off = 32; off > 0; off >>= 1") == {"gpx_kernels_dev.h": 1, "gpx_deriv.hip": 1, "gpx_small.hip": 1}
     # one tile walk for both hyper-parameter gradients: two kernels, one host summation of the partials
     kmat = code("gpx_kmat.hip")
     assert re.findall(r"__global__ __launch_bounds__\(256\) void (\w+_reduce\w*)\(", kmat) == ["tile_reduce_kernel", "tile_reduce_ard_kernel"]
@@ -197,6 +198,38 @@ def test_streamed_reductions_keep_one_copy_of_each_piece():
     assert len(re.findall(r"\bslice_plan\(", stream)) == 3          # the definition, the apply launcher, pred_grad
     for f in files:
         assert not re.search(r"\b(?:mean_kernel|kapply_fused_kernel|g_mean_scr|g_pgrad_scr)\b", code(f)), f
+
+
+def test_small_device_kernels_have_one_home():
+    """The element maps, the transposes and the single-workgroup sums were copied from file to file with every feature: ten
+    2-D maps with the same grid recipe, seven 1-D ones, three kernels called transpose_kernel, a second copy of the
+    single-workgroup sum, and the two-armed dtype dispatch in front of each.  They are now lambdas behind the two map
+    kernels of csrc/gpx_small.h, one transpose and one reduce_kernel in csrc/gpx_small.hip, and by_dtype; a new small
+    kernel that brings its own copy of either recipe back fails here.  (The files the consolidation left alone, and
+    gpx_potrf.hip, which only lost tril, still write the dispatch out.)"""
+    csrc = os.path.join(ROOT, "gaussian_processes_amd", "csrc")
+    files = [f for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".h"))]
+    src = {f: open(os.path.join(csrc, f)).read() for f in files}
+    assert "gpx_small.h" in files and "gpx_small.hip" in files
+
+    def defs(name):
+        return {f: n for f, n in ((f, len(re.findall(r"__global__(?:\s+__launch_bounds__\([^)]*\))?\s+void\s+%s\s*\(" % name, src[f]))) for f in files) if n}
+    assert defs("transpose_kernel") == {"gpx_small.hip": 1}
+    assert defs("map_rows_kernel") == {"gpx_small.h": 1}
+    assert defs("map_vec_kernel") == {"gpx_small.h": 1}
+    assert defs("reduce_kernel") == {"gpx_small.hip": 1}
+    gone = ("cvt_from_f64_2d", "cvt_to_f64_2d", "eye_kernel", "eye_rows_kernel", "col_scale_kernel", "loo_g_kernel", "fill_rows_kernel",
+            "paths_rows_kernel", "sum_slices_lower_kernel", "schur_reduce_kernel", "scale_copy_kernel", "sub_kernel", "cvt_div_kernel",
+            "div_kernel", "paths_div_kernel", "add_diag_kernel", "loo_weights_kernel", "strided_sum_kernel", "transpose_sq")
+    for f in files:
+        for name in gone:
+            assert not re.search(r"\b%s\b" % name, src[f]), (f, name)
+    untouched = ("gpx_gemm.hip", "gpx_panel.hip", "gpx_leaf.h", "gpx_kmat.hip", "gpx_stream.hip", "gpx_kernels_dev.h", "gpx_mg.hip",
+                 "gpx_runtime.hip", "gpx_potrf.hip")
+    for f in files:
+        if f not in untouched:
+            for line in src[f].splitlines():
+                assert not re.search(r"== GPX_F64\)\s*hipLaunchKernelGGL", line), (f, line)
 
 
 def test_no_cpu_fallback_without_gpu():
