@@ -91,7 +91,7 @@ struct EventPool {
 // ---- live per-kernel-class timing (HIP events around each launch; off by default) ----
 enum ProfClass { PC_KMAT = 0, PC_GEMM = 1, PC_POTRF_DIAG = 2, PC_TRSM_ROWS = 3, PC_TRSV = 4,
                  PC_MEAN = 5, PC_REDUCE = 6, PC_GEMM_SKINNY = 7, PC_GEMM_GENERIC = 8, PC_GEMM_PANEL = 9, PC_GEMM_N64 = 10,
-                 PC_TRANSPOSE = 11, PC_PRED_GRAD = 12, PC_EXTEND = 13, PC_RANDN = 14, PC_RFF = 15, PC_KAPPLY = 16, PC_KAPPLY_GRAD = 17, PC_CHOL_DELETE = 18, PC_SPARSE_GRAM = 19, PC_COUNT = 20 };
+                 PC_TRANSPOSE = 11, PC_PRED_GRAD = 12, PC_EXTEND = 13, PC_RANDN = 14, PC_RFF = 15, PC_KAPPLY = 16, PC_KAPPLY_GRAD = 17, PC_CHOL_DELETE = 18, PC_SPARSE_GRAM = 19, PC_SPARSE_GRAD = 20, PC_COUNT = 21 };
 extern bool g_prof_on;
 // the registry is shared by all host threads (mutex inside); a scope ends its OWN record
 int  prof_begin(int cls, double work, hipStream_t st);    // record index, -1 when nothing was recorded
@@ -321,6 +321,14 @@ int tile_reduce_ard(int dtype, const void *xs, int64_t n, int d, const double *i
                     int64_t ldm, double *partial_dev, double *out, hipStream_t st);
 void grad_from_sums(int kernel, int d, const double *params, const double *S, double quad, double noise_scale, double factor,
                     double *out);
+// Their rectangular sibling (gpx_kmat.hip), the N-sized pass of the sparse GP's gradient: rows x (n, d), columns z (m, d),
+//   sum_ji (P[j, i] + y_j w_i) dk_p(x_j, z_i)     P: n x ldp, the coefficient matrix, read once;  y: n;  w: m
+// with the kernel derivatives formed in the tile.  out (host): [P0, P1, P2, sum coef k] for GPX_KERNEL_GAUSSIAN /
+// GPX_KERNEL_PERIODIC (width 4), [S_0, S_1 .. S_d, 0] on the ARD family's scaled points (width d + 2; S_0 = sum coef k, S_k =
+// sum coef k t_k^2: tile_reduce_ard's sums).  partial_dev: dloglh_partial_doubles() DEVICE doubles.  One partial per workgroup and
+// quantity, added by the host in workgroup order: no atomics.  Synchronises `st`.
+int rect_reduce(int dtype, int kernel, const void *x, int64_t n, const void *z, int64_t m, int d, const double *params, const void *P,
+                int64_t ldp, const void *y, const void *w, double *partial_dev, double *out, hipStream_t st);
 // The Gaussian ARD family (gpx_kmat.hip): out <- x / w (w_host: d doubles; out may be x).
 // dloglh_partial_doubles: the DEVICE doubles either reduction needs for its per-workgroup partial sums.
 struct ArdWidths { double w[GPX_ARD_MAX_D]; };   // the widths as a kernel argument

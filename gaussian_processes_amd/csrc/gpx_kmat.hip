@@ -640,6 +640,215 @@ int tile_reduce_ard(int dtype, const void *xs, int64_t n, int d, const double *i
     return sum_partials(partial_dev, d + 2, out, st);
 }
 
+// ---------------------------------------------------------------------------
+// The rectangular sibling of the two passes above, for TWO point sets (the sparse GP's gradient, gpx_sparse.hip): rows x_j
+// (n of them, a column chunk of the data), columns z_i (m inducing points), a coefficient matrix P (n x ldp) that is in memory
+// and read once, and two staged vectors (y over the rows, w over the columns):
+//   coef_ji = P[j, i] + y_j w_i          out[p] = sum_ji coef_ji dk_p(x_j, z_i)          out[last] = sum_ji coef_ji k(x_j, z_i)
+// No symmetry, so no weights and no triangle: the tiles of the n x m rectangle row by row, the same 64 x 64 tile, thread
+// map (one column, 16 rows), LDS layout and fixed-order block sum as above; the slot that held tr M holds the sum against
+// the kernel itself (the ARD form has it as S_0 already and leaves the slot zero).  f64 sums for both dtypes, one partial per
+// workgroup and quantity, no atomics.
+// ---------------------------------------------------------------------------
+template <typename T>
+__global__ __launch_bounds__(256) void rect_tile_kernel(const T *__restrict__ x, int64_t n, const T *__restrict__ z, int64_t m, int d,
+                                                          const T *__restrict__ P, int64_t ldp, const T *__restrict__ y,
+                                                          const T *__restrict__ w, GradParams gp, double ck, int64_t ntiles_c,
+                                                          int64_t total, double *__restrict__ partial)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    T *s1 = reinterpret_cast<T *>(smem_raw);          // [GR_T][d]   rows (x)
+    T *s2 = s1 + (size_t)GR_T * d;                    // [d][GR_T]   columns (z), transposed
+    T *sy = s2 + (size_t)GR_T * d;                    // y rows
+    T *sw = sy + GR_T;                                // w cols
+    __shared__ double red[4][4];
+    const int tid = threadIdx.x, col = tid & 63, rg = tid >> 6;
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};             // up to 3 kernel params + the sum against k
+    for (int64_t t = blockIdx.x; t < total; t += gridDim.x) {
+        const int64_t tr = t / ntiles_c, tc = t - tr * ntiles_c;
+        const int64_t r0 = tr * GR_T, c0 = tc * GR_T;
+        __syncthreads();
+        for (int idx = tid; idx < GR_T * d; idx += 256) {
+            const int r = idx / d, k = idx - r * d;
+            s1[idx] = (r0 + r < n) ? x[(r0 + r) * d + k] : (T)0;
+            s2[(size_t)k * GR_T + r] = (c0 + r < m) ? z[(c0 + r) * d + k] : (T)0;
+        }
+        if (tid < GR_T) {
+            sy[tid] = (r0 + tid < n) ? y[r0 + tid] : (T)0;
+            sw[tid] = (c0 + tid < m) ? w[c0 + tid] : (T)0;
+        }
+        __syncthreads();
+        const int64_t gc = c0 + col;
+        const double wk = (double)sw[col];
+        for (int i = 0; i < 16; ++i) {
+            const int r = rg + 4 * i;
+            const int64_t gr = r0 + r;
+            if (gr >= n || gc >= m) continue;
+            const double coef = (double)P[gr * ldp + gc] + (double)sy[r] * wk;
+            if (gp.kernel == GPX_KERNEL_GAUSSIAN) {
+                T d2 = (T)0;
+                for (int k = 0; k < d; ++k) {
+                    const T tt = s1[r * d + k] - s2[(size_t)k * GR_T + col];
+                    d2 = fma(tt, tt, d2);
+                }
+                const double e = gp.c1 * (double)d2;
+                if (!(e < GPX_MIN_LOG)) {
+                    const double ex = exp(e);
+                    acc[0] += coef * (gp.c2h * ex);
+                    acc[1] += coef * (ex * (gp.c3w * (double)d2 - gp.c2w));
+                    acc[3] += coef * (ck * ex);
+                }
+            } else {
+                const T dd = s1[r] - s2[col];          // d == 1
+                acc[0] += coef * (double)periodic_entry<T>(GPX_DK_DH, dd, (T)gp.h, (T)gp.w, (T)gp.p);
+                acc[1] += coef * (double)periodic_entry<T>(GPX_DK_DW, dd, (T)gp.h, (T)gp.w, (T)gp.p);
+                acc[2] += coef * (double)periodic_entry<T>(GPX_DK_DP, dd, (T)gp.h, (T)gp.w, (T)gp.p);
+                acc[3] += coef * (double)periodic_entry<T>(GPX_K, dd, (T)gp.h, (T)gp.w, (T)gp.p);
+            }
+        }
+    }
+    block_sum_fixed(acc, red, tid);
+    __syncthreads();
+    if (tid < 4) partial[(int64_t)blockIdx.x * 4 + tid] = block_sum_final(red, tid);
+}
+
+// the ARD form on scaled points: S_0 = sum c_ji, S_k = sum c_ji t_k^2 with c_ji = coef_ji k_ji -- tile_reduce_ard_kernel's
+// two walks over the dimensions, its DMAX ladder and its register array
+template <typename T, int DMAX>
+__global__ __launch_bounds__(256) void rect_tile_ard_kernel(const T *__restrict__ xs, int64_t n, const T *__restrict__ zs, int64_t m,
+                                                              int d, const T *__restrict__ P, int64_t ldp, const T *__restrict__ y,
+                                                              const T *__restrict__ w, double c2, int64_t ntiles_c, int64_t total,
+                                                              double *__restrict__ partial)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    T *s1 = reinterpret_cast<T *>(smem_raw);          // [GR_T][DMAX]   rows (x)
+    T *s2 = s1 + (size_t)GR_T * DMAX;                 // [DMAX][GR_T]   columns (z), transposed
+    T *sy = s2 + (size_t)GR_T * DMAX;                 // y rows
+    T *sw = sy + GR_T;                                // w cols
+    __shared__ double red[4][DMAX + 2];
+    const int tid = threadIdx.x, col = tid & 63;
+    const int rg = __builtin_amdgcn_readfirstlane(tid >> 6);
+    double acc[DMAX + 2];                             // slot 0: S_0, 1 .. DMAX: S_k, DMAX + 1: stays 0
+#pragma unroll
+    for (int k = 0; k < DMAX + 2; ++k) acc[k] = 0.0;
+    for (int64_t t = blockIdx.x; t < total; t += gridDim.x) {
+        const int64_t tr = t / ntiles_c, tc = t - tr * ntiles_c;
+        const int64_t r0 = tr * GR_T, c0 = tc * GR_T;
+        __syncthreads();
+        for (int idx = tid; idx < GR_T * DMAX; idx += 256) {
+            const int r = idx / DMAX, k = idx - r * DMAX;
+            s1[idx] = (k < d && r0 + r < n) ? xs[(r0 + r) * d + k] : (T)0;
+            s2[(size_t)k * GR_T + r] = (k < d && c0 + r < m) ? zs[(c0 + r) * d + k] : (T)0;
+        }
+        if (tid < GR_T) {
+            sy[tid] = (r0 + tid < n) ? y[r0 + tid] : (T)0;
+            sw[tid] = (c0 + tid < m) ? w[c0 + tid] : (T)0;
+        }
+        __syncthreads();
+        const int64_t gc = c0 + col;
+        T r2[16];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) r2[i] = (T)0;
+#pragma unroll 2
+        for (int k = 0; k < d; ++k) {
+            const T b = s2[(size_t)k * GR_T + col];
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                const T tt = s1[(rg + 4 * i) * DMAX + k] - b;
+                r2[i] = fma(tt, tt, r2[i]);
+            }
+        }
+        double c[16];
+        const double wk = (double)sw[col];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const int r = rg + 4 * i;
+            const int64_t gr = r0 + r;
+            double ci = 0.0;
+            if (gr < n && gc < m) {
+                const double coef = (double)P[gr * ldp + gc] + (double)sy[r] * wk;
+                const double e = -0.5 * (double)r2[i];
+                if (!(e < GPX_MIN_LOG)) ci = coef * (c2 * exp(e));
+            }
+            c[i] = ci;
+            acc[0] += ci;
+        }
+#pragma unroll
+        for (int k = 0; k < DMAX; ++k) {
+            if (k < d) {
+                const T b = s2[(size_t)k * GR_T + col];
+                double a = 0.0;
+#pragma unroll
+                for (int i = 0; i < 16; ++i) {
+                    const double tt = (double)(s1[(rg + 4 * i) * DMAX + k] - b);
+                    a = fma(c[i], tt * tt, a);
+                }
+                acc[1 + k] += a;
+            }
+        }
+    }
+    block_sum_fixed(acc, red, tid);
+    __syncthreads();
+    if (tid < d + 2) partial[(int64_t)blockIdx.x * (d + 2) + tid] = block_sum_final(red, tid <= d ? tid : DMAX + 1);
+}
+
+template <typename T, int DMAX>
+static int launch_rect_reduce_ard(const void *xs, int64_t n, const void *zs, int64_t m, int d, const void *P, int64_t ldp, const void *y,
+                                  const void *w, double c2, double *partial_dev, hipStream_t st)
+{
+    const size_t smem = ((size_t)2 * GR_T * DMAX + 2 * GR_T) * sizeof(T);
+    if (smem > 48 * 1024) GPX_TRY(set_max_lds((const void *)rect_tile_ard_kernel<T, DMAX>, LDS_TILE_MAX));
+    const int64_t ntc = cdiv(m, GR_T), total = cdiv(n, GR_T) * ntc;
+    hipLaunchKernelGGL((rect_tile_ard_kernel<T, DMAX>), dim3((unsigned)std::min<int64_t>(GR_BLOCKS, total)), dim3(256), smem, st,
+                       (const T *)xs, n, (const T *)zs, m, d, (const T *)P, ldp, (const T *)y, (const T *)w, c2, ntc, total, partial_dev);
+    GPX_LAUNCH_CHECK();
+    return GPX_OK;
+}
+
+template <typename T>
+static int launch_rect_reduce(int kernel, const void *x, int64_t n, const void *z, int64_t m, int d, const double *params, const void *P,
+                              int64_t ldp, const void *y, const void *w, double *partial_dev, hipStream_t st)
+{
+    if (kernel == GPX_KERNEL_GAUSSIAN_ARD) {
+        const double c2 = 0.5 * sqrt(2.0 / M_PI) * params[0] * params[0] / params[1];     // make_kparams, GPX_K, of iso
+        if (d <= 8) return launch_rect_reduce_ard<T, 8>(x, n, z, m, d, P, ldp, y, w, c2, partial_dev, st);
+        if (d <= 16) return launch_rect_reduce_ard<T, 16>(x, n, z, m, d, P, ldp, y, w, c2, partial_dev, st);
+        if (d <= 32) return launch_rect_reduce_ard<T, 32>(x, n, z, m, d, P, ldp, y, w, c2, partial_dev, st);
+        return launch_rect_reduce_ard<T, 64>(x, n, z, m, d, P, ldp, y, w, c2, partial_dev, st);
+    }
+    GradParams gpar;
+    GPX_TRY(make_grad_params(kernel, d, params, &gpar));
+    const double ck = kernel == GPX_KERNEL_GAUSSIAN ? 0.5 * sqrt(2.0 / M_PI) * params[0] * params[0] / params[1] : 0.0;
+    const size_t smem = ((size_t)2 * GR_T * d + 2 * GR_T) * sizeof(T);
+    if (smem > 48 * 1024) GPX_TRY(set_max_lds((const void *)rect_tile_kernel<T>, LDS_TILE_MAX));
+    const int64_t ntc = cdiv(m, GR_T), total = cdiv(n, GR_T) * ntc;
+    hipLaunchKernelGGL((rect_tile_kernel<T>), dim3((unsigned)std::min<int64_t>(GR_BLOCKS, total)), dim3(256), smem, st, (const T *)x, n,
+                       (const T *)z, m, d, (const T *)P, ldp, (const T *)y, (const T *)w, gpar, ck, ntc, total, partial_dev);
+    GPX_LAUNCH_CHECK();
+    return GPX_OK;
+}
+
+// kernel == GPX_KERNEL_GAUSSIAN_ARD: x, z are the SCALED points and params = iso = (h / sqrt(wbar), 1)
+int rect_reduce(int dtype, int kernel, const void *x, int64_t n, const void *z, int64_t m, int d, const double *params, const void *P,
+                int64_t ldp, const void *y, const void *w, double *partial_dev, double *out, hipStream_t st)
+{
+    const bool ard = kernel == GPX_KERNEL_GAUSSIAN_ARD;
+    if (ard && (d < 1 || d > GPX_ARD_MAX_D)) { set_error("ARD gradient needs 1 <= d <= %d (got %d)", GPX_ARD_MAX_D, d); return GPX_ERR_ARG; }
+    if (n < 1 || m < 1 || ldp < m) { set_error("rect_reduce: need n, m >= 1 and ldp >= m"); return GPX_ERR_ARG; }
+    const int width = ard ? d + 2 : 4;
+    if ((size_t)2 * GR_T * (ard ? 64 : d) * esize(dtype) + 2 * GR_T * esize(dtype) > (size_t)LDS_TILE_MAX) {
+        set_error("rect_reduce: d = %d too large for the LDS-staged tile", d);
+        return GPX_ERR_UNSUPPORTED;
+    }
+    GPX_HIP(hipMemsetAsync(partial_dev, 0, (size_t)GR_BLOCKS * width * sizeof(double), st));
+    {
+        ProfScope prof(PC_SPARSE_GRAD, (double)n * (double)m, st);
+        if (dtype == GPX_F64) GPX_TRY(launch_rect_reduce<double>(kernel, x, n, z, m, d, params, P, ldp, y, w, partial_dev, st));
+        else GPX_TRY(launch_rect_reduce<float>(kernel, x, n, z, m, d, params, P, ldp, y, w, partial_dev, st));
+    }
+    return sum_partials(partial_dev, width, out, st);
+}
+
 // The host half of either gradient: the sums of a pass -> (d/d kernel params ..., d/ds).  factor: 1/2 for the marginal
 // likelihood (RW06 eq. 5.9), 1 for the leave-one-out criterion (dL = sum dK_ab G_ab); it enters only as a product by 1/2, 1 or
 // 2, all exact, so each output is bit for bit the expression its criterion always computed.  quad: the vectors' part of tr G (alpha .

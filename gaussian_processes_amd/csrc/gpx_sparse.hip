@@ -22,6 +22,12 @@
 //   cvec, w, t0, t1        M each
 //   bacc                   M doubles
 //   work (grow-only)       G (M x cols) | the partial accumulators (slices x M x ldm)
+//                          the gradient pass lays it out anew: reduction partials | three M x ldm blocks | K(x_c, z), P (c x ldm each)
+//
+// The gradient of the bound in the hyper-parameters (gpx_sgp_grad; include/gpx.h has the formulas): everything M x M from the
+// factors the fit left (Luu, LB, X in Xt, w) by the sweeps and products the library has, then a second pass over x in
+// column chunks: K(x_c, z), ONE product P = K(x_c, z) T, and the rectangular tile reduction of gpx_kmat.hip.  It writes
+// Xf, t0 and the work buffer only, so the fit's state -- elbo, the predictions, what gpx_sgp_get returns -- stays as it was.
 #include "gpx_small.h"
 #include <algorithm>
 #include <cmath>
@@ -58,6 +64,10 @@ struct gpx_sgp {
     bool have_x, have_y, have_z, fitted;
     int stage, pivot, split;
     SgpScal host;                      // the scalars of the last good fit
+    hipEvent_t gev[3];                 // the gradient pass: start, M x M part done, end
+    std::vector<hipEvent_t> gcev;      // four per chunk: before the build, behind it, behind the product, behind the reduction
+    float grad_ms[5];
+    bool have_grad;
 };
 
 namespace gpx {
@@ -291,7 +301,7 @@ static int sgp_fit(gpx_sgp *g, int64_t chunk_cols)
     const size_t es = esize(dtype);
     const int64_t n = g->n, M = g->m, ldm = g->ldm;
     hipStream_t st = g->st;
-    g->fitted = false; g->stage = 0; g->pivot = 0; g->chunks_timed = 0;
+    g->fitted = false; g->have_grad = false; g->stage = 0; g->pivot = 0; g->chunks_timed = 0;
     // the plan and its buffer, before anything is enqueued
     size_t freeb = 0, totalb = 0;
     GPX_HIP(hipMemGetInfo(&freeb, &totalb));
@@ -403,6 +413,147 @@ static int sgp_two_blocks(gpx_sgp *g, const void *xo_c, int64_t rows, void *V, v
     return trsm_right_lt(g->dtype, g->LB, M, ldm, W, rows, ldm, g->st);
 }
 
+// ---- the gradient of the bound in (kernel parameters..., s) -----------------------------------------------------------------
+// A[i, j] -= v[i] v[j], all of an n x n block
+static int sub_outer(int dtype, void *A, int64_t n, int64_t lda, const void *v, hipStream_t st)
+{
+    return by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        T *a = (T *)A;
+        const T *x = (const T *)v;
+        return map_rows(n, n, st, [=] __device__(int64_t i, int64_t j) { a[i * lda + j] = (T)((double)a[i * lda + j] - (double)x[i] * (double)x[j]); });
+    });
+}
+
+// C (m x n) = alpha A B^T: C is not read where the product kernel's aligned route can start from zero, cleared first elsewhere
+static int product_nt(int dtype, int64_t m, int64_t n, int64_t k, const void *A, const void *B, void *C, int64_t ld, double alpha,
+                      hipStream_t st)
+{
+    const bool beta0 = !tune().gemm_no_fast && k % (128 / (int64_t)esize(dtype)) == 0;
+    if (!beta0) GPX_HIP(hipMemsetAsync(C, 0, (size_t)m * ld * esize(dtype), st));
+    return gemm_nt(dtype, m, n, k, A, ld, B, ld, C, ld, alpha, GPX_FULL, 0, 0, st, beta0 ? 1 : 0);
+}
+
+static int sgp_grad_events(gpx_sgp *g, int64_t chunks)
+{
+    while ((int64_t)g->gcev.size() < 4 * chunks) {
+        hipEvent_t e;
+        GPX_HIP(hipEventCreate(&e));
+        g->gcev.push_back(e);
+    }
+    return GPX_OK;
+}
+
+static int sgp_grad(gpx_sgp *g, int64_t chunk_cols, double *grad)
+{
+    const int dtype = g->dtype, d = g->d, nkp = g->nparams;
+    const size_t es = esize(dtype);
+    const int64_t n = g->n, M = g->m, ldm = g->ldm;
+    hipStream_t st = g->st;
+    const bool ard = g->kernel == GPX_KERNEL_GAUSSIAN_ARD;
+    g->have_grad = false;
+    // the plan: the fit's, with two c x ldm blocks where the fit has one M x c
+    size_t freeb = 0, totalb = 0;
+    GPX_HIP(hipMemGetInfo(&freeb, &totalb));
+    int64_t cols = 0, chunks = 0;
+    GPX_TRY(sgp_plan(dtype, n, M, chunk_cols, g->split, freeb + g->work.bytes, &cols, &chunks, nullptr, nullptr));
+    const size_t budget = (freeb + g->work.bytes) / 4;
+    if ((size_t)2 * cols * ldm * es > budget) {
+        if (chunk_cols == 0) cols = std::max(SGP_CHUNK_ALIGN, cols / 2 / SGP_CHUNK_ALIGN * SGP_CHUNK_ALIGN);
+        if ((size_t)2 * cols * ldm * es > budget) {
+            set_error("sparse gradient: two blocks of %lld columns and %lld rows do not fit a quarter of the free device memory (%zu bytes free)",
+                      (long long)cols, (long long)M, freeb + g->work.bytes);
+            return GPX_ERR_NOMEM;
+        }
+        chunks = cdiv(n, cols);
+    }
+    const size_t part_doubles = dloglh_partial_doubles(g->kernel, d), part_bytes = (size_t)round_up((int64_t)(part_doubles + 8) * 8, 128);
+    const size_t mm = (size_t)M * ldm * es, blk = (size_t)cols * ldm * es;
+    GPX_TRY(g->work.reserve(part_bytes + 3 * mm + 2 * blk, st));
+    double *part = (double *)g->work.p, *wb_dev = part + part_doubles;
+    char *Y = (char *)g->work.p + part_bytes, *A = Y + mm, *Tm = A + mm, *G = Tm + mm, *P = G + blk;
+    char *Mm = Y;                                                                    // (Y is done with when Mm is formed)
+    void *X1 = g->Xf;                                                                // (work of the fit: nobody reads it afterwards)
+    GPX_TRY(sgp_grad_events(g, chunks));
+    const SgpView v = sgp_view(g);
+    const double s = g->s, s2 = s * s, N = (double)n;
+
+    // 1. the M x M part.  Neither Kuu^-1 - Sigma^-1 nor Gu is formed as a difference: in the directions the data do not
+    // reach (X ~ 0: those of Kuu's small eigenvalues, where Kuu^-1 is largest) the terms of both cancel, and in fp32 the
+    // difference of two inverses of size 1 / jitter is rounding error as large as what is left.  With B - I = X / s^2,
+    // Y = Luu^-T LB^-T and A = Luu^-T X LB^-T:
+    //   Kuu^-1 - Sigma^-1 = Luu^-T (I - B^-1) Luu^-1 = Luu^-T (X / s^2) B^-1 Luu^-1 = A Y^T / s^2
+    //   Gu = Luu^-T (I - B^-1 - X / s^2) Luu^-1 / 2 - w w^T / 2 = -(A A^T / s^4 + w w^T) / 2     (I - B^-1 - (B - I) = -(B - I)^2 B^-1)
+    GPX_HIP(hipEventRecord(g->gev[0], st));
+    GPX_TRY(eye_rows(dtype, X1, M, ldm, 0, 0, st));
+    GPX_TRY(trsm_right_lt(dtype, g->Luu, M, ldm, X1, M, ldm, st, 1));                 // X1 = Luu^-T
+    GPX_HIP(hipMemcpyAsync(Y, X1, mm, hipMemcpyDeviceToDevice, st));
+    GPX_TRY(trsm_right_lt(dtype, g->LB, M, ldm, Y, M, ldm, st));                      // Y = Luu^-T LB^-T
+    GPX_TRY(product_nt(dtype, M, M, M, X1, g->Xt, A, ldm, 1.0, st));                  // Luu^-T X  (X is symmetric)
+    GPX_TRY(trsm_right_lt(dtype, g->LB, M, ldm, A, M, ldm, st));                      // A = Luu^-T X LB^-T
+    GPX_TRY(product_nt(dtype, M, M, M, A, Y, Tm, ldm, 1.0 / s2, st));                 // Kuu^-1 - Sigma^-1
+    GPX_TRY(sub_outer(dtype, Tm, M, ldm, g->w, st));                                  // T
+    GPX_HIP(hipMemsetAsync(Mm, 0, mm, st));
+    GPX_TRY(gemm_nt(dtype, M, M, M, A, ldm, A, ldm, Mm, ldm, -1.0 / (s2 * s2), GPX_LOWER, 0, 0, st));   // w w^T - Mm = -2 Gu
+    GPX_TRY(cvt_div(dtype, g->bacc, g->t0, M, 1.0, st));
+    GPX_TRY(dot(dtype, g->w, g->t0, M, wb_dev, st));                                  // w . b
+    // sum (w w^T - Mm) o dKuu = -2 sum Gu o dKuu: the dense gradient's pass on z
+    double Suu[GPX_ARD_MAX_D + 2], Srect[GPX_ARD_MAX_D + 2], out[GPX_ARD_MAX_D + 2], wb = 0.0;
+    if (ard) GPX_TRY(tile_reduce_ard(dtype, g->zs, M, d, g->iso, g->w, nullptr, Mm, ldm, part, Suu, st));
+    else GPX_TRY(tile_reduce(dtype, g->kernel, g->z, M, d, g->params, g->w, nullptr, Mm, ldm, part, Suu, st));
+    GPX_HIP(hipMemcpyAsync(&wb, wb_dev, sizeof(double), hipMemcpyDeviceToHost, st));
+    GPX_HIP(hipEventRecord(g->gev[1], st));
+
+    // 2. the pass over x: sum_ji (P[j, i] + y_j w_i) dk(x_j, z_i), P = K(x_c, z) T
+    const int width = ard ? d + 2 : 4;
+    for (int q = 0; q < width; ++q) Srect[q] = 0.0;
+    for (int64_t c = 0; c < chunks; ++c) {
+        const int64_t c0 = c * cols, cc = std::min(cols, n - c0);
+        const char *xc = (const char *)v.x + (size_t)c0 * d * es;
+        route_hit(RT_SPARSE_CHUNK);
+        GPX_HIP(hipEventRecord(g->gcev[4 * c], st));
+        GPX_TRY(kmat(dtype, v.kernel, GPX_K, xc, cc, v.z, M, d, v.params, 0.0, GPX_FULL, G, ldm, st));
+        GPX_HIP(hipEventRecord(g->gcev[4 * c + 1], st));
+        GPX_TRY(product_nt(dtype, cc, M, M, G, Tm, P, ldm, 1.0, st));                 // (T is symmetric)
+        GPX_HIP(hipEventRecord(g->gcev[4 * c + 2], st));
+        GPX_TRY(rect_reduce(dtype, g->kernel, xc, cc, v.z, M, d, v.params, P, ldm, (const char *)g->y + (size_t)c0 * es, g->w, part, out, st));
+        GPX_HIP(hipEventRecord(g->gcev[4 * c + 3], st));
+        for (int q = 0; q < width; ++q) Srect[q] += out[q];
+    }
+    GPX_HIP(hipEventRecord(g->gev[2], st));
+    GPX_HIP(hipStreamSynchronize(st));
+
+    // 3. the gradient from the sums.  k(0) = k00 depends on h (and the Gaussian families' on the widths): dk(0)/dh = 2 k(0) / h,
+    // Gaussian dk(0)/dw = -k(0) / w; the ARD family's share is the term t = 0 of its sums
+    const double k00 = g->host.k00, h = g->params[0];
+    if (ard) {
+        double S[GPX_ARD_MAX_D + 2];
+        for (int q = 0; q <= d; ++q) S[q] = -0.5 * Suu[q] + Srect[q] / s2;
+        S[0] -= 0.5 * N * k00 / s2;
+        S[d + 1] = 0.0;
+        grad_from_sums(g->kernel, d, g->params, S, 0.0, 0.0, 1.0, grad);
+    } else {
+        for (int p = 0; p < nkp; ++p) grad[p] = -0.5 * Suu[p] + Srect[p] / s2;
+        grad[0] -= 0.5 * N * (2.0 * k00 / h) / s2;
+        if (g->kernel == GPX_KERNEL_GAUSSIAN) grad[1] += 0.5 * N * (k00 / g->params[1]) / s2;
+    }
+    const double sumk = ard ? Srect[0] : Srect[3];                                   // tr(T Phi) + w . b
+    grad[nkp] = -N / s + (((g->host.yy - wb) - sumk) + N * k00) / (s2 * s);
+
+    float *ms = g->grad_ms;
+    for (int i = 0; i < 5; ++i) ms[i] = 0.0f;
+    GPX_HIP(hipEventElapsedTime(&ms[0], g->gev[0], g->gev[1]));
+    for (int64_t c = 0; c < chunks; ++c)
+        for (int i = 0; i < 3; ++i) {
+            float t = 0.0f;
+            GPX_HIP(hipEventElapsedTime(&t, g->gcev[4 * c + i], g->gcev[4 * c + i + 1]));
+            ms[1 + i] += t;
+        }
+    GPX_HIP(hipEventElapsedTime(&ms[4], g->gev[0], g->gev[2]));
+    g->have_grad = true;
+    return GPX_OK;
+}
+
 }  // namespace gpx
 
 using namespace gpx;
@@ -462,6 +613,10 @@ int gpx_sgp_create(gpx_sgp_t **out, int dtype, int kernel, int64_t n, int64_t m_
         e = hipEventCreate(&g->ev[i]);
         if (e != hipSuccess) rc = hip_fail(e, "hipEventCreate", __FILE__, __LINE__);
     }
+    for (int i = 0; i < 3 && rc == GPX_OK; ++i) {
+        e = hipEventCreate(&g->gev[i]);
+        if (e != hipSuccess) rc = hip_fail(e, "hipEventCreate", __FILE__, __LINE__);
+    }
     if (rc != GPX_OK) { gpx_sgp_destroy(g); return rc; }
     *out = g;
     return GPX_OK;
@@ -478,7 +633,9 @@ int gpx_sgp_destroy(gpx_sgp_t *g)
         dev_free(b);
     g->work.release();
     for (int i = 0; i < 4; ++i) if (g->ev[i]) (void)hipEventDestroy(g->ev[i]);
+    for (int i = 0; i < 3; ++i) if (g->gev[i]) (void)hipEventDestroy(g->gev[i]);
     for (hipEvent_t e : g->cev) (void)hipEventDestroy(e);
+    for (hipEvent_t e : g->gcev) (void)hipEventDestroy(e);
     if (g->st) (void)hipStreamDestroy(g->st);
     delete g;
     return GPX_OK;
@@ -487,7 +644,7 @@ int gpx_sgp_destroy(gpx_sgp_t *g)
 int gpx_sgp_set_data(gpx_sgp_t *g, const double *x, const double *y, const double *z)
 {
     SGP_ENTER(g);
-    g->fitted = false;
+    g->fitted = false; g->have_grad = false;
     if (x) { GPX_TRY(upload_f64(g->dtype, g->x, g->n * g->d, x, g->n * g->d, 1, g->n * g->d, g->st)); g->have_x = true; }
     if (y) { GPX_TRY(upload_f64(g->dtype, g->y, g->n, y, g->n, 1, g->n, g->st)); g->have_y = true; }
     if (z) { GPX_TRY(upload_f64(g->dtype, g->z, g->m * g->d, z, g->m * g->d, 1, g->m * g->d, g->st)); g->have_z = true; }
@@ -654,12 +811,29 @@ int gpx_sgp_last_timing(gpx_sgp_t *g, float *ms5)
     return GPX_OK;
 }
 
+int gpx_sgp_grad(gpx_sgp_t *g, int64_t chunk_cols, double *grad)
+{
+    SGP_ENTER(g);
+    SGP_NEED_FIT(g);
+    GPX_ARG(grad, "NULL argument");
+    GPX_ARG(chunk_cols >= 0 && chunk_cols % SGP_CHUNK_ALIGN == 0, "chunk_cols must be 0 (automatic) or a multiple of 128");
+    return sgp_grad(g, chunk_cols, grad);
+}
+
+int gpx_sgp_last_grad_timing(gpx_sgp_t *g, float *ms5)
+{
+    GPX_ARG(g != nullptr && ms5, "NULL argument");
+    GPX_ARG(g->fitted && g->have_grad, "no gradient of the current fit (gpx_sgp_grad)");
+    for (int i = 0; i < 5; ++i) ms5[i] = g->grad_ms[i];
+    return GPX_OK;
+}
+
 int gpx_sgp_set_split(gpx_sgp_t *g, int slices)
 {
     GPX_ARG(g != nullptr, "handle is NULL");
     GPX_ARG(slices >= 0, "slices must be >= 0");
     g->split = slices;
-    g->fitted = false;
+    g->fitted = false; g->have_grad = false;
     return GPX_OK;
 }
 

@@ -11,6 +11,9 @@ The dense `GP` factors an n x n matrix; this class never forms one.  With induci
 O(N M^2) time, O(M^2 + M chunk) device memory: x passes through the device in column chunks (``gpx_sgp_fit``,
 include/gpx.h).  `elbo` is a LOWER BOUND on the log marginal likelihood of the dense GP, not that likelihood: there is no
 attribute called ``log_lh`` here, on purpose.
+
+`delbo_dtheta` is the gradient of the bound in ``(kernel parameters..., s)`` with `z` and the jitter held fixed
+(``gpx_sgp_grad``: a second pass over the chunks of `x`), `optimize` an L-BFGS-B on top of it.
 """
 import ctypes
 
@@ -306,6 +309,77 @@ class SparseGP(object):
         :math:`-\frac N2 \log 2\pi - N \log s`, ``fit`` :math:`-y^\top y / 2s^2`, ``quad`` :math:`c^\top c / 2s^2`,
         ``trace`` :math:`-(\sum_i k(x_i, x_i) - \mathrm{tr} X) / 2s^2`."""
         return dict(self._elbo_and_terms()[1])
+
+    # ---- the gradient of the bound and the optimiser on top of it ----
+    def _grad(self):
+        if "grad" not in self._memoized:
+            st = self._fit_pd()
+            out = np.empty(self.K.params.size + 1, dtype=DTYPE)
+            _lib.check(_lib.load().gpx_sgp_grad(st.handle, self._chunk_cols, _lib.dptr(out)))
+            self._memoized["grad"] = out
+        return self._memoized["grad"]
+
+    @property
+    def delbo_dtheta(self):
+        r"""Gradient of `elbo` in `params`, float64 ``(len(params),)`` in their order ``(kernel parameters..., s)``, with
+        the inducing inputs held fixed: one ``gpx_sgp_grad`` on the fitted handle (include/gpx.h has the closed form), a
+        second pass over `x` in the fit's column chunks.  The JITTER is held at the value in force: it is not
+        differentiated, even when ``jitter=None`` makes it follow the kernel's height.  Raises ``LinAlgError`` when a
+        factorisation of the fit failed."""
+        return self._grad().copy()
+
+    def elbo_and_grad(self):
+        r"""``(elbo, delbo_dtheta)``, the bits of the two properties; ``(-inf, array of NaN)`` when a factorisation failed
+        (it does not raise: this is what `optimize` calls at every trial point)."""
+        if self._fit().stage != 0:
+            return self.elbo, np.full(self.K.params.size + 1, np.nan, dtype=DTYPE)
+        return self.elbo, self.delbo_dtheta
+
+    def grad_timing(self):
+        """Milliseconds of the last gradient pass (HIP events on the handle's stream): the M x M part, the chunks' kernel
+        builds, their products K(x_c, z) T, their tile reductions, total."""
+        self._grad()
+        ms = (ctypes.c_float * 5)()
+        _lib.check(_lib.load().gpx_sgp_last_grad_timing(self._fit_pd().handle, ms))
+        return dict(zip(("mm", "build", "product", "reduce", "total"), list(ms)))
+
+    def optimize(self, maxiter=100, bounds=None):
+        r"""Maximise `elbo` over `params` (all positive) with scipy's L-BFGS-B in log-parameters, the inducing inputs held
+        fixed; one `elbo_and_grad` call per evaluation.  A trial point whose fit fails counts as a very poor one and the
+        line search backs off.  `bounds`: ``None``, or one ``(lo, hi)`` pair per parameter in the natural scale (``None``
+        for an open end).  The object is left at the best parameters evaluated.  Returns a dict: ``params``, ``elbo``,
+        ``nit``, ``nfev``, ``success``, ``message``."""
+        from scipy.optimize import minimize
+
+        x0 = np.log(self.params)
+        if bounds is not None:
+            bounds = list(bounds)
+            if len(bounds) != x0.size:
+                raise ValueError("bounds: one (lo, hi) pair per parameter (%d), got %d" % (x0.size, len(bounds)))
+            bounds = [tuple(None if b is None else float(np.log(b)) for b in pair) for pair in bounds]
+        best = {"elbo": -np.inf, "params": self.params}
+        state = {"worst": None}
+
+        def negative(u):
+            self.params = np.exp(u)
+            val, grad = self.elbo_and_grad()
+            if not (np.isfinite(val) and np.all(np.isfinite(grad))):
+                # a failed fit: worse than anything seen, flat -- the line search shortens its step
+                ref = state["worst"] if state["worst"] is not None else 0.0
+                return abs(ref) * 10.0 + 1e10, np.zeros_like(u)
+            if val > best["elbo"]:
+                best["elbo"], best["params"] = float(val), self.params
+            state["worst"] = -val if state["worst"] is None else max(state["worst"], -val)
+            return -float(val), -np.asarray(grad, dtype=DTYPE) * np.exp(u)           # d/d log theta = theta d/d theta
+
+        res = minimize(negative, x0, jac=True, method="L-BFGS-B", bounds=bounds, options={"maxiter": int(maxiter)})
+        self.params = best["params"]                 # (a refit there gives the bits of best["elbo"]: fits are repeatable)
+        if not np.isfinite(best["elbo"]):
+            return dict(params=self.params, elbo=DTYPE(-np.inf), nit=int(res.nit), nfev=int(res.nfev), success=False,
+                        message="no trial point had a positive definite fit")
+        msg = res.message.decode() if isinstance(res.message, bytes) else str(res.message)
+        return dict(params=self.params, elbo=DTYPE(best["elbo"]), nit=int(res.nit), nfev=int(res.nfev), success=bool(res.success),
+                    message=msg)
 
     def _get(self, which):
         if which not in self._memoized:

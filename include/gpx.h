@@ -179,6 +179,7 @@ int gpx_stream_wait_event(void *stream, void *event);
 #define GPX_PROF_KAPPLY_GRAD 17 /* stream_apply_grad_kernel + its slice reduction (gpx_d_kmat_apply_grad): kernel evaluations m*n per group of weight vectors and window of dimensions */
 #define GPX_PROF_CHOL_DELETE 18 /* del_copy_rows_kernel + del_block_kernel (gpx_d_chol_delete), ONE record per call around all of its launches: bytes read + written */
 #define GPX_PROF_SPARSE_GRAM 19 /* gpx_sgp_fit: the Gram product K(z, x_c) K(x_c, z) of ONE chunk, one record around all of its slice products; flops 2 c per element of the lower triangle.  (The product kernel's own launches are recorded under their classes as well.) */
+#define GPX_PROF_SPARSE_GRAD 20 /* rect_tile_kernel / rect_tile_ard_kernel (gpx_sgp_grad): the rectangular tile reduction of ONE chunk; kernel-derivative evaluations c * M */
 int gpx_prof_enable(int on);    /* also clears the registry */
 int gpx_prof_read(int cls, double *launches, double *total_ms, double *total_work);
 
@@ -811,6 +812,35 @@ int gpx_sgp_get(gpx_sgp_t *h, double *Luu, double *LB, double *c, double *Phi, d
 /* milliseconds of the last fit (HIP events on the handle's stream): [0] Kuu + its factor [1] the chunks' kernel builds
  * [2] the chunks' Gram products, b and the slice sum [3] the M x M tail [4] total */
 int gpx_sgp_last_timing(gpx_sgp_t *h, float *ms5);
+/* The gradient of the bound in the hyper-parameters, z held fixed: grad (HOST, nkp + 1 doubles) = d elbo / d (kernel
+ * parameters..., s), in the order of gpx_sgp_fit's params.  Needs a fit of stage 0 (GPX_ERR_ARG otherwise, as the predictions).
+ * With Sigma = Kuu + Phi / s^2 = Luu B Luu^T and w = Sigma^-1 b / s^2 (the mean's weights, on the device since the fit):
+ *   T  = Kuu^-1 - Sigma^-1 - w w^T                         Gu = T / 2 - Kuu^-1 Phi Kuu^-1 / (2 s^2)    = d elbo / d Kuu
+ *   Gf = (T K(z, x) + w y^T) / s^2                         = d elbo / d K(z, x)
+ *   d elbo / d theta_p = sum Gu o dKuu/dtheta_p + sum Gf o dK(z, x)/dtheta_p - N dk(0)/dtheta_p / (2 s^2)
+ *   d elbo / d s       = -N / s + (yy - 2 w.b + N k(0) - tr(T Phi)) / s^3
+ * (tr(T Phi) = tr X - tr((Sigma^-1 + w w^T) Phi): the N-sized pass sums it beside the derivatives).
+ * The JITTER is held at the value of the fit: it is not differentiated, even where the caller derived it from the kernel's
+ * parameters.  Three parts, all on the handle's stream:
+ *   1. M x M, O(M^3), blocks the library has (gpx_d_trsm_right_lt on the identity and on products, gpx_d_gemm_nt), from Luu, LB
+ *      and the fit's X.  No difference of inverses is formed -- where the data do not reach (X ~ 0, Kuu's small eigenvalues)
+ *      Kuu^-1 and Sigma^-1 agree and are of size 1 / jitter, and in fp32 their difference would be rounding error.  With
+ *      B - I = X / s^2, Y = Luu^-T LB^-T and A = Luu^-T X LB^-T:
+ *        Kuu^-1 - Sigma^-1 = Luu^-T (X / s^2) B^-1 Luu^-1 = A Y^T / s^2          Gu = -(A A^T / s^4 + w w^T) / 2
+ *      (I - B^-1 - X / s^2 = -(B - I)^2 B^-1).  The contraction of Gu with dKuu/dtheta is the dense gradient's tile reduction
+ *      on z with (a, M) = (w, -A A^T / s^4), for which a a^T - M = -2 Gu.
+ *   2. a second pass over x in column chunks -- the fit's plan and chunk_cols rule, but TWO c x M blocks in the work buffer:
+ *      an automatic width that does not fit twice is halved (to a multiple of 128) -- one GPX_ROUTE_SPARSE_CHUNK hit each:
+ *      K(x_c, z) by gpx_d_kmat;  P = K(x_c, z) T by gpx_d_gemm_nt (2 M^2 c flops);  the rectangular tile reduction
+ *      sum_ji (P[j, i] + y_j w_i) dk_p(x_j, z_i), derivatives formed in the tile from the staged points (GPX_PROF_SPARSE_GRAD),
+ *      f64 sums for both dtypes, one partial per workgroup and parameter.
+ *   3. the host adds the partials in workgroup order and the chunks in chunk order.  No floating-point atomics anywhere: a
+ *      repeated call returns the same bits.  Nothing the fit left behind is written: elbo and the predictions are unchanged. */
+int gpx_sgp_grad(gpx_sgp_t *h, int64_t chunk_cols, double *grad);
+/* milliseconds of the last gpx_sgp_grad (HIP events on the handle's stream): [0] the M x M part (with its reduction on z)
+ * [1] the chunks' kernel builds [2] the chunks' products K(x_c, z) T [3] the chunks' tile reductions (with the copy of their
+ * partials) [4] total.  GPX_ERR_ARG before the first gradient of the current fit. */
+int gpx_sgp_last_grad_timing(gpx_sgp_t *h, float *ms5);
 /* Depth slices per chunk for later fits of this handle: 0 = the plan's (the default), P >= 1 = exactly that many (1: one
  * plain product per chunk).  For measurements (tools/sparse_bench.py); results differ in the last bits between values. */
 int gpx_sgp_set_split(gpx_sgp_t *h, int slices);

@@ -8,7 +8,12 @@ the depth slices per chunk of the Gram product, 0 = the library's plan, P >= 1 =
 against one plain product per chunk is `--splits 0,1`.  Per (M, split): one warm-up fit, `repeats` fits whose
 gpx_sgp_last_timing entries are reported as medians (HIP events on the handle's stream), then one fit under gpx_prof for the
 Gram product's rate (GPX_PROF_SPARSE_GRAM: one pair of events around the products of each chunk; flops 2 c per element of
-the lower triangle) and the kernel build's.  Prediction (mean and var at `--predict` points) is timed by a host clock around
+the lower triangle) and the kernel build's.  With `--grad 1` (the default) the plan's row also carries the gradient of the
+bound: gpx_sgp_last_grad_timing medians of `repeats` passes on the fit that is there (M x M part, builds, products K(x_c, z) T,
+tile reductions, total), its ratio to the fit, the shares of the product and of the reduction, the product's TF/s
+(2 M^2 N flops), the reduction's rate under gpx_prof (GPX_PROF_SPARSE_GRAD: kernel-derivative evaluations), one
+`elbo_and_grad()` from new parameters by a host clock (what one optimize step costs) beside 2 (P + 1) fits (what central
+differences would).  Prediction (mean and var at `--predict` points) is timed by a host clock around
 the synchronous calls, once per M.  Every GPU step runs under a watchdog of its own (--step-timeout seconds): a step that
 overruns it ends the process with exit status 124, so nothing further is started on the device.
 """
@@ -30,6 +35,7 @@ from gaussian_processes_amd import _lib                  # noqa: E402
 from oracle import gp_oracle as orc                      # noqa: E402
 
 STAGES = ("kuu", "build", "gram", "tail", "total")
+GRAD_STAGES = ("mm", "build", "product", "reduce", "total")
 FP64_MFMA_PEAK_TFLOPS = 78.6
 
 
@@ -66,8 +72,16 @@ def _refit(sg):
     return elbo, sg.fit_timing()
 
 
+def _regrad(sg):
+    """The gradient pass alone, on the fit that is there."""
+    sg._memoized.pop("grad", None)
+    grad = sg.delbo_dtheta
+    return grad, sg.grad_timing()
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--grad", type=int, default=1)
     ap.add_argument("--n", type=int, default=1048576)
     ap.add_argument("--d", type=int, default=32)
     ap.add_argument("--m", default="1024,2048,4096")
@@ -112,6 +126,32 @@ def main():
                    "kmat_ms_prof": kmat_ms, "kmat_gentries_per_s": kmat_bytes / (8 if a.dtype == "float64" else 4) / kmat_ms / 1e6 if kmat_ms > 0 else None}
             if rec["gram_tflops"] and a.dtype == "float64":
                 rec["gram_fraction_of_fp64_mfma_peak"] = rec["gram_tflops"] / FP64_MFMA_PEAK_TFLOPS
+            if split == 0 and a.grad:
+                with Step("M = %d: warm-up gradient" % M, a.step_timeout):
+                    _regrad(sg)
+                gruns = []
+                with Step("M = %d: %d gradients" % (M, a.repeats), a.step_timeout):
+                    for _ in range(a.repeats):
+                        gruns.append(_regrad(sg)[1])
+                with Step("M = %d: one elbo_and_grad from new parameters (host clock)" % M, a.step_timeout):
+                    t0 = time.perf_counter()
+                    sg._invalidate()
+                    sg.elbo_and_grad()
+                    step_ms = 1e3 * (time.perf_counter() - t0)
+                with Step("M = %d: one gradient under gpx_prof" % M, a.step_timeout):
+                    _lib.check(lib.gpx_prof_enable(1))
+                    grad, _ = _regrad(sg)
+                    _, red_ms, red_evals = _prof(_lib.PROF_SPARSE_GRAD)
+                    _lib.check(lib.gpx_prof_enable(0))
+                fit_total = rec["fit_ms_median"]["total"]
+                gmed = {k: statistics.median(r[k] for r in gruns) for k in GRAD_STAGES}
+                nparams = len(sg.params)
+                rec.update({"grad": [float(v) for v in grad], "grad_ms_median": gmed, "grad_ms_total_all": [r["total"] for r in gruns],
+                            "grad_over_fit": gmed["total"] / fit_total if fit_total > 0 else None,
+                            "grad_share_product": gmed["product"] / gmed["total"], "grad_share_reduce": gmed["reduce"] / gmed["total"],
+                            "grad_product_tflops": 2.0 * M * M * a.n / gmed["product"] / 1e9 if gmed["product"] > 0 else None,
+                            "grad_reduce_ms_prof": red_ms, "grad_reduce_gevals_per_s": red_evals / red_ms / 1e6 if red_ms > 0 else None,
+                            "optimize_step_ms_host": step_ms, "finite_difference_step_ms": 2 * nparams * fit_total})   # nparams = P + 1: s is one
             if split == 0 and a.predict > 0:
                 with Step("M = %d: predict at %d points" % (M, a.predict), a.step_timeout):
                     sg.predict(Xo[:1024])                                    # warm-up
