@@ -309,26 +309,27 @@ int kmat_apply(int dtype, int kernel, const void *xo, int64_t m, const void *x, 
 // memory one chunk needs.  chunk_rows 0: the largest multiple of 128 (at most var_chunk_cap) whose buffers fit a quarter
 // of free_bytes.  GPX_ERR_ARG / GPX_ERR_NOMEM as gpx_debug_var_plan documents.
 int var_plan(int dtype, int64_t n, int64_t m, int64_t chunk_rows, size_t free_bytes, int64_t *rows, int64_t *chunks, size_t *bytes);
-// The fused hyper-parameter gradient pass (gpx_kmat.hip): sum_ab G_ab dK_p(x_a, x_b) with the kernel derivatives formed on
-// the fly, M's lower triangle read once; out4 (host) = [P0, P1, P2, trace M].  vec_b == nullptr: the marginal likelihood,
-// G = a a^T - M (a = alpha, M = K^-1); otherwise the leave-one-out criterion, G = (b a^T + a b^T) / 2 - M (b = r,
-// M = Pm = K^-1 diag(c) K^-1).  tile_reduce_ard: the same on the Gaussian ARD family's scaled points xs with
-// iso = (h / sqrt(wbar), 1): out (host, d + 2) = [S_0, S_1 .. S_d, trace M].
-// grad_from_sums: either pass's sums -> the gradient (kernel params ..., s); `factor` 1/2 (marginal likelihood) or 1 (LOO).
+// The fused tile reductions (gpx_kmat.hip; one kernel pair, two host entries): sum_ji coef_ji dk_p(row_j, col_i) with the
+// kernel derivatives formed in the tile and ONE matrix in memory, read once.
+//   tile_reduce, the symmetric pass over K(x, x), x (n, d): coef = G, M's lower triangle read.  vec_b == nullptr: the marginal
+//     likelihood, G = a a^T - M (a = alpha, M = K^-1); otherwise the leave-one-out criterion, G = (b a^T + a b^T) / 2 - M
+//     (b = r, M = Pm = K^-1 diag(c) K^-1).  last = trace M.
+//   rect_reduce, the rectangular pass over K(x, z), the N-sized pass of the sparse GP's gradient: rows x (n, d), columns
+//     z (m, d), coef_ji = P[j, i] + y_j w_i (P: n x ldp; y: n; w: m).  last = sum coef k (ARD: 0, S_0 is that sum).
+// kernel == GPX_KERNEL_GAUSSIAN_ARD for either: the points are the SCALED ones and params = iso = (h / sqrt(wbar), 1) --
+// reduce_params() hands a caller that pair (in iso2) for the family's own parameters, and `params` itself for the other kernels.
+// out (host): [P0, P1, P2, last] for GPX_KERNEL_GAUSSIAN / GPX_KERNEL_PERIODIC, [S_0, S_1 .. S_d, last] for the ARD family
+// (S_0 = sum coef k, S_k = sum coef k t_k^2): dloglh_partial_doubles() / 1024 values.  partial_dev: dloglh_partial_doubles()
+// DEVICE doubles.  One partial per workgroup and quantity, added by the host in workgroup order: no atomics.  Both
+// synchronise `st`.
+// grad_from_sums: a symmetric pass's sums -> the gradient (kernel params ..., s); `factor` 1/2 (marginal likelihood) or 1 (LOO).
 int tile_reduce(int dtype, int kernel, const void *x, int64_t n, int d, const double *params, const void *vec_a, const void *vec_b,
-                const void *M, int64_t ldm, double *partial_dev, double *out4, hipStream_t st);
-int tile_reduce_ard(int dtype, const void *xs, int64_t n, int d, const double *iso, const void *vec_a, const void *vec_b, const void *M,
-                    int64_t ldm, double *partial_dev, double *out, hipStream_t st);
-void grad_from_sums(int kernel, int d, const double *params, const double *S, double quad, double noise_scale, double factor,
-                    double *out);
-// Their rectangular sibling (gpx_kmat.hip), the N-sized pass of the sparse GP's gradient: rows x (n, d), columns z (m, d),
-//   sum_ji (P[j, i] + y_j w_i) dk_p(x_j, z_i)     P: n x ldp, the coefficient matrix, read once;  y: n;  w: m
-// with the kernel derivatives formed in the tile.  out (host): [P0, P1, P2, sum coef k] for GPX_KERNEL_GAUSSIAN /
-// GPX_KERNEL_PERIODIC (width 4), [S_0, S_1 .. S_d, 0] on the ARD family's scaled points (width d + 2; S_0 = sum coef k, S_k =
-// sum coef k t_k^2: tile_reduce_ard's sums).  partial_dev: dloglh_partial_doubles() DEVICE doubles.  One partial per workgroup and
-// quantity, added by the host in workgroup order: no atomics.  Synchronises `st`.
+                const void *M, int64_t ldm, double *partial_dev, double *out, hipStream_t st);
 int rect_reduce(int dtype, int kernel, const void *x, int64_t n, const void *z, int64_t m, int d, const double *params, const void *P,
                 int64_t ldp, const void *y, const void *w, double *partial_dev, double *out, hipStream_t st);
+const double *reduce_params(int kernel, int d, const double *params, double *iso2);
+void grad_from_sums(int kernel, int d, const double *params, const double *S, double quad, double noise_scale, double factor,
+                    double *out);
 // The Gaussian ARD family (gpx_kmat.hip): out <- x / w (w_host: d doubles; out may be x).
 // dloglh_partial_doubles: the DEVICE doubles either reduction needs for its per-workgroup partial sums.
 struct ArdWidths { double w[GPX_ARD_MAX_D]; };   // the widths as a kernel argument

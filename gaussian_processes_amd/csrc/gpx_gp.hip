@@ -884,14 +884,8 @@ static int grad_reduce(gpx_gp *g, const void *pts, const void *alpha, const doub
     const int64_t n = g->n;
     double *aa = part + dloglh_partial_doubles(g->kernel, g->d);
     GPX_TRY(dot(g->dtype, alpha, alpha, n, aa, g->st));
-    double S[GPX_ARD_MAX_D + 2], ata = 0.0;            // ARD: S_0, S_1 .. S_d, tr W; otherwise [P0, P1, P2, tr W]
-    if (g->kernel == GPX_KERNEL_GAUSSIAN_ARD) {
-        double iso[2];
-        ard_iso(params, g->d, iso);
-        GPX_TRY(tile_reduce_ard(g->dtype, pts, n, g->d, iso, alpha, nullptr, W, ldw, part, S, g->st));
-    } else {
-        GPX_TRY(tile_reduce(g->dtype, g->kernel, pts, n, g->d, params, alpha, nullptr, W, ldw, part, S, g->st));
-    }
+    double S[GPX_ARD_MAX_D + 2], iso[2], ata = 0.0;    // ARD: S_0, S_1 .. S_d, tr W; otherwise [P0, P1, P2, tr W]
+    GPX_TRY(tile_reduce(g->dtype, g->kernel, pts, n, g->d, reduce_params(g->kernel, g->d, params, iso), alpha, nullptr, W, ldw, part, S, g->st));
     GPX_HIP(hipMemcpyAsync(&ata, aa, sizeof(double), hipMemcpyDeviceToHost, g->st));
     GPX_HIP(hipStreamSynchronize(g->st));
     grad_from_sums(g->kernel, g->d, params, S, ata, s_noise, 0.5, out);

@@ -14,6 +14,8 @@
 // r = 0 that the reference keeps).
 #include "gpx_common.h"
 #include "gpx_kernels_dev.h"
+#include "gpx_small.h"
+#include <type_traits>
 #include <vector>
 
 namespace gpx {
@@ -301,30 +303,47 @@ int scale_points(int dtype, const void *x, int64_t n, int d, const double *w_hos
     ArdWidths aw;
     for (int k = 0; k < GPX_ARD_MAX_D; ++k) aw.w[k] = k < d ? w_host[k] : 1.0;
     const dim3 grid((unsigned)cdiv(n, 256)), block(256);
-    if (dtype == GPX_F64) hipLaunchKernelGGL((scale_points_kernel<double>), grid, block, 0, st, (const double *)x, n, d, aw, (double *)out);
-    else hipLaunchKernelGGL((scale_points_kernel<float>), grid, block, 0, st, (const float *)x, n, d, aw, (float *)out);
-    GPX_LAUNCH_CHECK();
-    return GPX_OK;
+    return by_dtype(dtype, [&](auto t) -> int {
+        using T = decltype(t);
+        hipLaunchKernelGGL((scale_points_kernel<T>), grid, block, 0, st, (const T *)x, n, d, aw, (T *)out);
+        GPX_LAUNCH_CHECK();
+        return GPX_OK;
+    });
 }
 
 static thread_local ThreadScratch g_ard_scr;    // gpx_d_kmat and gpx_d_pred_grad on the ARD family: the scaled copies of their two point sets
 int ard_scratch(size_t bytes, void **p) { return g_ard_scr.get(bytes, p); }
 
+const double *reduce_params(int kernel, int d, const double *params, double *iso2)
+{
+    if (kernel != GPX_KERNEL_GAUSSIAN_ARD) return params;
+    ard_iso(params, d, iso2);
+    return iso2;
+}
+
 // ---------------------------------------------------------------------------
-// Fused gradient reduction (gp/ext/gp_c.pyx:34-49 without its dense products):
-//   P[p]    = sum_{j,k} G_jk * dK_p(x_j, x_k)      p < n_kp
-//   P[last] = trace(M)
-// for a symmetric weight matrix G = (vectors) - M of which only M is in memory (lower triangle read; G and dK_p are
-// symmetric, so the sum runs over the lower triangle with weight 2 off the diagonal).  The kernel derivatives are
-// evaluated on the fly from the squared distance (no n x n Jacobian is materialised).  Deterministic: a fixed grid of
-// workgroups walks the tiles in a fixed order, per-workgroup partial sums are written out and added up by the host in
-// index order.  NV, the number of staged vector pairs, selects the criterion -- staging the second pair and the coefficient
-// are the ONLY text that differs, and each instantiation holds exactly one form of it:
-//   NV == 1  marginal likelihood:  G = a a^T - M,               a = alpha, M = W = K^-1
-//   NV == 2  leave-one-out (RW06 eq. 5.13 rearranged; gpx_loograd.hip has the derivation):
-//                                  G = (b a^T + a b^T) / 2 - M,  a = alpha, b = r, M = Pm = K^-1 diag(c) K^-1
-// (NV as a template parameter and not a __device__ helper around the shared text: the instantiations keep the resource
-// lines the four separate kernels had)
+// The tile reductions (gp/ext/gp_c.pyx:34-49 without its dense products): sums of a coefficient against the kernel's
+// derivatives over the entries of a kernel matrix,
+//   out[p] = sum_{j,i} coef_ji * dk_p(row_j, col_i)      p < n_kp,
+// with the derivatives evaluated on the fly from the squared distance (no Jacobian is materialised) and ONE matrix M that is
+// in memory and read once.  Deterministic: a fixed grid of workgroups walks the 64 x 64 tiles in a fixed order (a thread owns
+// one column and 16 rows of a tile), per-workgroup partial sums are written out and added up by the host in index order; f64
+// sums for both dtypes, no atomics.  FORM selects the pass.  It guards the tile decode, the column set, the staged vectors,
+// the entry guard, the coefficient and the last slot -- nothing else differs, and each instantiation holds exactly one form of
+// each:
+//   TILE_ML    marginal likelihood: K(x, x), symmetric.  G = a a^T - M, a = alpha, M = W = K^-1 (lower triangle read; G and
+//              dK_p are symmetric, so the sum runs over the lower triangle with weight wt = 2 off the diagonal):
+//              coef = wt (a_r a_c - M_rc); last slot tr M
+//   TILE_LOO   leave-one-out (RW06 eq. 5.13 rearranged; gpx_loograd.hip has the derivation): the same with
+//              G = (b a^T + a b^T) / 2 - M, a = alpha, b = r, M = Pm = K^-1 diag(c) K^-1
+//   TILE_RECT  the sparse GP's gradient (gpx_sparse.hip): K(x, z), rows x_j (n of them, a column chunk of the data), columns z_i
+//              (m inducing points); no symmetry, so no weights and no triangle: every tile of the rectangle, row by row.
+//              coef = M_ji + y_j w_i  (M = P, n x ldm; y over the rows, w over the columns); last slot sum coef k(x_j, z_i)
+//              (the ARD kernel has that as S_0 already and leaves the slot zero)
+// tile_reduce_ard_kernel is ONE text for the three forms; of the isotropic kernel only the two symmetric forms are one text,
+// tile_reduce_kernel, and the rectangular one is rect_tile_kernel (as a third form its fp32 instantiation was slower: DESIGN 3.3).
+// (FORM as a template parameter and not a __device__ helper around the shared text: the instantiations keep the resource
+// lines the separate kernels had)
 // ---------------------------------------------------------------------------
 struct GradParams {
     double c1, c2h, c2w, c3w;      // gaussian: e = c1*d2 ; dK_dh = c2h*exp(e) ; dK_dw = exp(e)*(c3w*d2 - c2w)
@@ -334,68 +353,86 @@ struct GradParams {
 
 constexpr int GR_T = 64;           // tile edge
 constexpr int GR_BLOCKS = 1024;
+enum { TILE_ML = 1, TILE_LOO = 2, TILE_RECT = 3 };
 
-// The staged vectors as ONE kernel argument of NV pointers.  The NV == 1 kernels take no second pointer (and reserve no LDS
-// for one), so every instantiation has the argument layout of the kernel it replaced: with an unused `vec_b` in the list the
-// isotropic marginal-likelihood kernel was scheduled differently and measured 2 - 6 % slower.
-template <typename T, int NV> struct TileVecs { const T *a, *b; };
-template <typename T> struct TileVecs<T, 1> { const T *a; };
-template <typename T, int NV>
-static TileVecs<T, NV> tile_vecs(const void *vec_a, const void *vec_b)
+// What only one form reads, as ONE kernel argument specialised per form: the staged vectors, and for TILE_RECT the second
+// point set and the tiles of a row.  No form carries a field it does not read (TILE_ML takes no second vector and reserves no
+// LDS for one), so the symmetric instantiations have the argument block of the kernels they replaced: with an unused `vec_b`
+// in the list the isotropic marginal-likelihood kernel was scheduled differently and measured 2 - 6 % slower.
+template <typename T, int FORM> struct TileArgs;
+template <typename T> struct TileArgs<T, TILE_ML> { const T *a; };
+template <typename T> struct TileArgs<T, TILE_LOO> { const T *a, *b; };
+template <typename T> struct TileArgs<T, TILE_RECT> { const T *z; int64_t m; const T *y, *w; int64_t ntiles_c; };
+
+// the origin of tile t: the lower triangle of the tiles of a symmetric pass (tri_tile), the rectangle's tiles row by row
+template <typename T, int FORM>
+__device__ __forceinline__ void tile_origin(const TileArgs<T, FORM> &a, int64_t t, int64_t *r0, int64_t *c0)
 {
-    TileVecs<T, NV> v;
-    v.a = (const T *)vec_a;
-    if constexpr (NV == 2) v.b = (const T *)vec_b;
-    return v;
+    int64_t tr, tc;
+    if constexpr (FORM == TILE_RECT) { tr = t / a.ntiles_c; tc = t - tr * a.ntiles_c; }
+    else tri_tile(t, &tr, &tc);
+    *r0 = tr * GR_T;
+    *c0 = tc * GR_T;
 }
 
-template <typename T, int NV>
-__global__ __launch_bounds__(256) void tile_reduce_kernel(const T *__restrict__ x, int64_t n, int d,
-                                                          TileVecs<T, NV> vec, const T *__restrict__ M, int64_t ldm,
-                                                          GradParams gp, int64_t ntiles_r,
+// the staged vectors of a tile, by the first GR_T threads: a over the rows (below n) and over the columns (below nc) -- y and w
+// for TILE_RECT -- and for TILE_LOO b behind them
+template <typename T, int FORM>
+__device__ __forceinline__ void stage_tile_vecs(const TileArgs<T, FORM> &a, T *sa1, int tid, int64_t r0, int64_t n, int64_t c0, int64_t nc)
+{
+    if (tid >= GR_T) return;
+    const T *vr, *vc;
+    if constexpr (FORM == TILE_RECT) { vr = a.y; vc = a.w; }
+    else { vr = a.a; vc = a.a; }
+    sa1[tid] = (r0 + tid < n) ? vr[r0 + tid] : (T)0;
+    sa1[GR_T + tid] = (c0 + tid < nc) ? vc[c0 + tid] : (T)0;
+    if constexpr (FORM == TILE_LOO) {
+        sa1[2 * GR_T + tid] = (r0 + tid < n) ? a.b[r0 + tid] : (T)0;
+        sa1[3 * GR_T + tid] = (c0 + tid < nc) ? a.b[c0 + tid] : (T)0;
+    }
+}
+
+// The isotropic kernel of the two SYMMETRIC forms (TILE_ML, TILE_LOO; the rectangular pass of these families is
+// rect_tile_kernel below).  nt: the tile rows; the pass walks nt (nt + 1) / 2 tiles
+template <typename T, int FORM>
+__global__ __launch_bounds__(256) void tile_reduce_kernel(const T *__restrict__ x, int64_t n, int d, TileArgs<T, FORM> a,
+                                                          const T *__restrict__ M, int64_t ldm, GradParams gp, int64_t nt,
                                                           double *__restrict__ partial)
 {
+    static_assert(FORM == TILE_ML || FORM == TILE_LOO, "the symmetric forms");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     T *s1 = reinterpret_cast<T *>(smem_raw);          // [GR_T][d]   rows
     T *s2 = s1 + (size_t)GR_T * d;                    // [d][GR_T]   columns, transposed
-    T *sa1 = s2 + (size_t)GR_T * d;                   // vec.a rows
-    T *sa2 = sa1 + GR_T;                              // vec.a cols
-    T *sb1 = sa2 + GR_T;                              // vec.b rows  (NV == 2)
-    T *sb2 = sb1 + GR_T;                              // vec.b cols
+    T *sa1 = s2 + (size_t)GR_T * d;                   // a rows
+    T *sa2 = sa1 + GR_T;                              // a cols
+    T *sb1 = sa2 + GR_T;                              // b rows  (TILE_LOO)
+    T *sb2 = sb1 + GR_T;                              // b cols
     __shared__ double red[4][4];
     const int tid = threadIdx.x, col = tid & 63, rg = tid >> 6;
     double acc[4] = {0.0, 0.0, 0.0, 0.0};             // up to 3 kernel params + trace
-    const int64_t total = ntiles_r * (ntiles_r + 1) / 2;
+    const int64_t total = nt * (nt + 1) / 2;
     for (int64_t t = blockIdx.x; t < total; t += gridDim.x) {
-        int64_t tr, tc;
-        tri_tile(t, &tr, &tc);
-        const int64_t r0 = tr * GR_T, c0 = tc * GR_T;
+        int64_t r0, c0;
+        tile_origin(a, t, &r0, &c0);
         __syncthreads();
         for (int idx = tid; idx < GR_T * d; idx += 256) {
             const int r = idx / d, k = idx - r * d;
             s1[idx] = (r0 + r < n) ? x[(r0 + r) * d + k] : (T)0;
             s2[(size_t)k * GR_T + r] = (c0 + r < n) ? x[(c0 + r) * d + k] : (T)0;
         }
-        if (tid < GR_T) {
-            sa1[tid] = (r0 + tid < n) ? vec.a[r0 + tid] : (T)0;
-            sa2[tid] = (c0 + tid < n) ? vec.a[c0 + tid] : (T)0;
-            if constexpr (NV == 2) {
-                sb1[tid] = (r0 + tid < n) ? vec.b[r0 + tid] : (T)0;
-                sb2[tid] = (c0 + tid < n) ? vec.b[c0 + tid] : (T)0;
-            }
-        }
+        stage_tile_vecs(a, sa1, tid, r0, n, c0, n);
         __syncthreads();
         const int64_t gc = c0 + col;
         const T ak = sa2[col];
-        const double bk = NV == 2 ? (double)sb2[col] : 0.0;
+        const double bk = FORM == TILE_LOO ? (double)sb2[col] : 0.0;
         for (int i = 0; i < 16; ++i) {
             const int r = rg + 4 * i;
             const int64_t gr = r0 + r;
             if (gr >= n || gc >= n || gc > gr) continue;
             const double wt = (gc == gr) ? 1.0 : 2.0;
             const double mjk = (double)M[gr * ldm + gc];
-            const double coef = NV == 1 ? wt * ((double)sa1[r] * (double)ak - mjk)
-                                        : wt * (0.5 * ((double)sb1[r] * (double)ak + (double)sa1[r] * bk) - mjk);
+            const double coef = FORM == TILE_ML ? wt * ((double)sa1[r] * (double)ak - mjk)
+                                                : wt * (0.5 * ((double)sb1[r] * (double)ak + (double)sa1[r] * bk) - mjk);
             if (gc == gr) acc[3] += mjk;
             if (gp.kernel == GPX_KERNEL_GAUSSIAN) {
                 T d2 = (T)0;
@@ -422,234 +459,10 @@ __global__ __launch_bounds__(256) void tile_reduce_kernel(const T *__restrict__ 
     if (tid < 4) partial[(int64_t)blockIdx.x * 4 + tid] = block_sum_final(red, tid);
 }
 
-// the partial sums of `width` quantities per workgroup, added on the host in workgroup order
-static int sum_partials(const double *partial_dev, int width, double *out, hipStream_t st)
-{
-    std::vector<double> host((size_t)GR_BLOCKS * width);
-    GPX_HIP(hipMemcpyAsync(host.data(), partial_dev, host.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-    GPX_HIP(hipStreamSynchronize(st));
-    for (int q = 0; q < width; ++q) {
-        double v = 0.0;
-        for (int b = 0; b < GR_BLOCKS; ++b) v += host[(size_t)b * width + q];
-        out[q] = v;
-    }
-    return GPX_OK;
-}
-
-// the workgroups of a pass over n points, and the launch's lower triangle of M read once as its byte count
-static inline int grad_blocks(int64_t n) { const int64_t ntr = cdiv(n, GR_T); return (int)std::min<int64_t>(GR_BLOCKS, ntr * (ntr + 1) / 2); }
-static inline double grad_bytes(int dtype, int64_t n) { return 0.5 * (double)n * (double)(n + 1) * (double)esize(dtype); }
-
-static int make_grad_params(int kernel, int d, const double *params, GradParams *gpar)
-{
-    memset(gpar, 0, sizeof(*gpar));
-    gpar->kernel = kernel;
-    if (kernel == GPX_KERNEL_GAUSSIAN) {
-        const double h = params[0], w = params[1], S = sqrt(2.0 / M_PI);
-        gpar->nkp = 2;
-        gpar->c1 = -0.5 / (w * w);
-        gpar->c2h = S * h / w;                         // gaussian_c.pyx:61
-        gpar->c2w = 0.5 * S * h * h / (w * w);         // :82
-        gpar->c3w = 0.5 * S * h * h / pow(w, 4);       // :83
-    } else {
-        if (d != 1) { set_error("periodic gradient needs d == 1"); return GPX_ERR_UNSUPPORTED; }
-        gpar->nkp = 3; gpar->h = params[0]; gpar->w = params[1]; gpar->p = params[2];
-    }
-    return GPX_OK;
-}
-
-template <typename T, int NV>
-static int launch_tile_reduce(const void *x, int64_t n, int d, const void *vec_a, const void *vec_b, const void *M, int64_t ldm,
-                              const GradParams &gpar, double *partial_dev, hipStream_t st)
-{
-    const size_t smem = ((size_t)2 * GR_T * d + 2 * NV * GR_T) * sizeof(T);
-    if (smem > 48 * 1024) GPX_TRY(set_max_lds((const void *)tile_reduce_kernel<T, NV>, LDS_TILE_MAX));
-    hipLaunchKernelGGL((tile_reduce_kernel<T, NV>), dim3(grad_blocks(n)), dim3(256), smem, st, (const T *)x, n, d,
-                       tile_vecs<T, NV>(vec_a, vec_b), (const T *)M, ldm, gpar, cdiv(n, GR_T), partial_dev);
-    GPX_LAUNCH_CHECK();
-    return GPX_OK;
-}
-
-// partial_dev: GR_BLOCKS * 4 doubles of DEVICE memory; out4: host, [P0, P1, P2, trace M]; vec_b == nullptr selects NV = 1
-int tile_reduce(int dtype, int kernel, const void *x, int64_t n, int d, const double *params, const void *vec_a, const void *vec_b,
-                const void *M, int64_t ldm, double *partial_dev, double *out4, hipStream_t st)
-{
-    GradParams gpar;
-    GPX_TRY(make_grad_params(kernel, d, params, &gpar));
-    GPX_HIP(hipMemsetAsync(partial_dev, 0, (size_t)GR_BLOCKS * 4 * sizeof(double), st));
-    {
-        ProfScope prof(PC_REDUCE, grad_bytes(dtype, n), st);
-        if (dtype == GPX_F64) {
-            if (vec_b) GPX_TRY((launch_tile_reduce<double, 2>(x, n, d, vec_a, vec_b, M, ldm, gpar, partial_dev, st)));
-            else GPX_TRY((launch_tile_reduce<double, 1>(x, n, d, vec_a, vec_b, M, ldm, gpar, partial_dev, st)));
-        } else {
-            if (vec_b) GPX_TRY((launch_tile_reduce<float, 2>(x, n, d, vec_a, vec_b, M, ldm, gpar, partial_dev, st)));
-            else GPX_TRY((launch_tile_reduce<float, 1>(x, n, d, vec_a, vec_b, M, ldm, gpar, partial_dev, st)));
-        }
-    }
-    return sum_partials(partial_dev, 4, out4, st);
-}
-
-// ---------------------------------------------------------------------------
-// The same pass for the Gaussian ARD family (d + 1 kernel parameters): with t_k = (a_k - b_k) / w_k (the difference of the
-// SCALED points) and c_ab = wt G_ab k_ab (G as above, by NV) it accumulates
-//   S_0 = sum c_ab,   S_k = sum c_ab t_k^2  (k = 1 .. d),   tr M
-// from which the host forms the gradient (dk/dh = 2k/h, dk/dw_k = k (t_k^2 - 1/d) / w_k: grad_from_sums).
-// One read of M, nothing n x n x d anywhere, no atomics; the same fixed grid, tile walk and host summation as above, f64
-// sums for both dtypes: bitwise repeatable.
-// Per tile a thread (one column, 16 rows) first forms its 16 weights c_ab -- squared distance in T as the matrix build
-// forms it, one exp each -- and keeps them in registers, then walks the dimensions once more: S_k += sum_i c_i t_ik^2.
-// d is a run-time value and d accumulators indexed by a loop variable would live in scratch memory, so the kernel is
-// compiled for DMAX = 8, 16, 32, 64 accumulators and that loop is unrolled over DMAX with a uniform `k < d` guard: every
-// acc[k] is a register (no scratch: see DESIGN 3.4 for the compiler's resource line).  The staged points are zero beyond d.
-// S_0, the S_k and the trace share ONE register array, so the block sum is the shared helper's.
-// ---------------------------------------------------------------------------
-template <typename T, int DMAX, int NV>
-__global__ __launch_bounds__(256) void tile_reduce_ard_kernel(const T *__restrict__ xs, int64_t n, int d,
-                                                              TileVecs<T, NV> vec, const T *__restrict__ M, int64_t ldm, double c2,
-                                                              int64_t ntiles_r, double *__restrict__ partial)
-{
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    T *s1 = reinterpret_cast<T *>(smem_raw);          // [GR_T][DMAX]   rows
-    T *s2 = s1 + (size_t)GR_T * DMAX;                 // [DMAX][GR_T]   columns, transposed
-    T *sa1 = s2 + (size_t)GR_T * DMAX;                // vec.a rows
-    T *sa2 = sa1 + GR_T;                              // vec.a cols
-    T *sb1 = sa2 + GR_T;                              // vec.b rows  (NV == 2)
-    T *sb2 = sb1 + GR_T;                              // vec.b cols
-    __shared__ double red[4][DMAX + 2];
-    const int tid = threadIdx.x, col = tid & 63;
-    const int rg = __builtin_amdgcn_readfirstlane(tid >> 6);      // (the wave's index: uniform, so the row reads broadcast)
-    double acc[DMAX + 2];                             // slot 0: S_0, 1 .. DMAX: S_k, DMAX + 1: tr M
-#pragma unroll
-    for (int k = 0; k < DMAX + 2; ++k) acc[k] = 0.0;
-    const int64_t total = ntiles_r * (ntiles_r + 1) / 2;
-    for (int64_t t = blockIdx.x; t < total; t += gridDim.x) {
-        int64_t tr, tc;
-        tri_tile(t, &tr, &tc);
-        const int64_t r0 = tr * GR_T, c0 = tc * GR_T;
-        __syncthreads();
-        for (int idx = tid; idx < GR_T * DMAX; idx += 256) {
-            const int r = idx / DMAX, k = idx - r * DMAX;
-            s1[idx] = (k < d && r0 + r < n) ? xs[(r0 + r) * d + k] : (T)0;
-            s2[(size_t)k * GR_T + r] = (k < d && c0 + r < n) ? xs[(c0 + r) * d + k] : (T)0;
-        }
-        if (tid < GR_T) {
-            sa1[tid] = (r0 + tid < n) ? vec.a[r0 + tid] : (T)0;
-            sa2[tid] = (c0 + tid < n) ? vec.a[c0 + tid] : (T)0;
-            if constexpr (NV == 2) {
-                sb1[tid] = (r0 + tid < n) ? vec.b[r0 + tid] : (T)0;
-                sb2[tid] = (c0 + tid < n) ? vec.b[c0 + tid] : (T)0;
-            }
-        }
-        __syncthreads();
-        const int64_t gc = c0 + col;
-        // the squared distances of this thread's 16 entries, accumulated as kmat_kernel accumulates them
-        T r2[16];
-#pragma unroll
-        for (int i = 0; i < 16; ++i) r2[i] = (T)0;
-#pragma unroll 2
-        for (int k = 0; k < d; ++k) {
-            const T b = s2[(size_t)k * GR_T + col];
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                const T tt = s1[(rg + 4 * i) * DMAX + k] - b;
-                r2[i] = fma(tt, tt, r2[i]);
-            }
-        }
-        // the weights c_ab (0 for an entry outside the matrix or above the diagonal: M is only read inside the lower triangle)
-        double c[16];
-        const double ak = (double)sa2[col], bk = NV == 2 ? (double)sb2[col] : 0.0;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            const int r = rg + 4 * i;
-            const int64_t gr = r0 + r;
-            double ci = 0.0;
-            if (gr < n && gc <= gr) {
-                const double mjk = (double)M[gr * ldm + gc];
-                const double wt = (gc == gr) ? 1.0 : 2.0;
-                const double coef = NV == 1 ? wt * ((double)sa1[r] * ak - mjk)
-                                            : wt * (0.5 * ((double)sb1[r] * ak + (double)sa1[r] * bk) - mjk);
-                if (gc == gr) acc[DMAX + 1] += mjk;
-                const double e = -0.5 * (double)r2[i];
-                if (!(e < GPX_MIN_LOG)) ci = coef * (c2 * exp(e));
-            }
-            c[i] = ci;
-            acc[0] += ci;
-        }
-#pragma unroll
-        for (int k = 0; k < DMAX; ++k) {
-            if (k < d) {
-                const T b = s2[(size_t)k * GR_T + col];
-                double a = 0.0;
-#pragma unroll
-                for (int i = 0; i < 16; ++i) {
-                    const double tt = (double)(s1[(rg + 4 * i) * DMAX + k] - b);
-                    a = fma(c[i], tt * tt, a);
-                }
-                acc[1 + k] += a;
-            }
-        }
-    }
-    block_sum_fixed(acc, red, tid);
-    __syncthreads();
-    if (tid < d + 2) partial[(int64_t)blockIdx.x * (d + 2) + tid] = block_sum_final(red, tid <= d ? tid : DMAX + 1);
-}
-
-template <typename T, int DMAX, int NV>
-static int launch_tile_reduce_ard(const void *xs, int64_t n, int d, const void *vec_a, const void *vec_b, const void *M, int64_t ldm,
-                                  double c2, double *partial_dev, hipStream_t st)
-{
-    const size_t smem = ((size_t)2 * GR_T * DMAX + 2 * NV * GR_T) * sizeof(T);
-    if (smem > 48 * 1024) GPX_TRY(set_max_lds((const void *)tile_reduce_ard_kernel<T, DMAX, NV>, LDS_TILE_MAX));
-    hipLaunchKernelGGL((tile_reduce_ard_kernel<T, DMAX, NV>), dim3(grad_blocks(n)), dim3(256), smem, st, (const T *)xs, n, d,
-                       tile_vecs<T, NV>(vec_a, vec_b), (const T *)M, ldm, c2, cdiv(n, GR_T), partial_dev);
-    GPX_LAUNCH_CHECK();
-    return GPX_OK;
-}
-
-template <typename T, int NV>
-static int launch_tile_reduce_ard_d(const void *xs, int64_t n, int d, const void *vec_a, const void *vec_b, const void *M, int64_t ldm,
-                                    double c2, double *partial_dev, hipStream_t st)
-{
-    if (d <= 8) return launch_tile_reduce_ard<T, 8, NV>(xs, n, d, vec_a, vec_b, M, ldm, c2, partial_dev, st);
-    if (d <= 16) return launch_tile_reduce_ard<T, 16, NV>(xs, n, d, vec_a, vec_b, M, ldm, c2, partial_dev, st);
-    if (d <= 32) return launch_tile_reduce_ard<T, 32, NV>(xs, n, d, vec_a, vec_b, M, ldm, c2, partial_dev, st);
-    return launch_tile_reduce_ard<T, 64, NV>(xs, n, d, vec_a, vec_b, M, ldm, c2, partial_dev, st);
-}
-
-size_t dloglh_partial_doubles(int kernel, int d) { return (size_t)GR_BLOCKS * (kernel == GPX_KERNEL_GAUSSIAN_ARD ? d + 2 : 4); }
-
-// xs: the SCALED points; iso: (h / sqrt(wbar), 1); partial_dev: dloglh_partial_doubles() of DEVICE memory;
-// out: host, d + 2 values [S_0, S_1 .. S_d, trace M]; vec_b == nullptr selects NV = 1
-int tile_reduce_ard(int dtype, const void *xs, int64_t n, int d, const double *iso, const void *vec_a, const void *vec_b, const void *M,
-                    int64_t ldm, double *partial_dev, double *out, hipStream_t st)
-{
-    if (d < 1 || d > GPX_ARD_MAX_D) { set_error("ARD gradient needs 1 <= d <= %d (got %d)", GPX_ARD_MAX_D, d); return GPX_ERR_ARG; }
-    const double c2 = 0.5 * sqrt(2.0 / M_PI) * iso[0] * iso[0] / iso[1];          // make_kparams, GPX_K
-    GPX_HIP(hipMemsetAsync(partial_dev, 0, (size_t)GR_BLOCKS * (d + 2) * sizeof(double), st));
-    {
-        ProfScope prof(PC_REDUCE, grad_bytes(dtype, n), st);
-        if (dtype == GPX_F64) {
-            if (vec_b) GPX_TRY((launch_tile_reduce_ard_d<double, 2>(xs, n, d, vec_a, vec_b, M, ldm, c2, partial_dev, st)));
-            else GPX_TRY((launch_tile_reduce_ard_d<double, 1>(xs, n, d, vec_a, vec_b, M, ldm, c2, partial_dev, st)));
-        } else {
-            if (vec_b) GPX_TRY((launch_tile_reduce_ard_d<float, 2>(xs, n, d, vec_a, vec_b, M, ldm, c2, partial_dev, st)));
-            else GPX_TRY((launch_tile_reduce_ard_d<float, 1>(xs, n, d, vec_a, vec_b, M, ldm, c2, partial_dev, st)));
-        }
-    }
-    return sum_partials(partial_dev, d + 2, out, st);
-}
-
-// ---------------------------------------------------------------------------
-// The rectangular sibling of the two passes above, for TWO point sets (the sparse GP's gradient, gpx_sparse.hip): rows x_j
-// (n of them, a column chunk of the data), columns z_i (m inducing points), a coefficient matrix P (n x ldp) that is in memory
-// and read once, and two staged vectors (y over the rows, w over the columns):
-//   coef_ji = P[j, i] + y_j w_i          out[p] = sum_ji coef_ji dk_p(x_j, z_i)          out[last] = sum_ji coef_ji k(x_j, z_i)
-// No symmetry, so no weights and no triangle: the tiles of the n x m rectangle row by row, the same 64 x 64 tile, thread
-// map (one column, 16 rows), LDS layout and fixed-order block sum as above; the slot that held tr M holds the sum against
-// the kernel itself (the ARD form has it as S_0 already and leaves the slot zero).  f64 sums for both dtypes, one partial per
-// workgroup and quantity, no atomics.
-// ---------------------------------------------------------------------------
+// The isotropic kernel of TILE_RECT: the text above with the rectangle's tile decode, column set, staged vectors, entry guard,
+// coefficient and last slot (ck: the Gaussian k's constant; total: the tiles).  It is a kernel of its own and not a third FORM
+// of tile_reduce_kernel because as one its fp32 instantiation measured 4 - 6 % slower on the MI355X with the same instructions in
+// the tile loop; the ARD kernel below serves all three forms.
 template <typename T>
 __global__ __launch_bounds__(256) void rect_tile_kernel(const T *__restrict__ x, int64_t n, const T *__restrict__ z, int64_t m, int d,
                                                           const T *__restrict__ P, int64_t ldp, const T *__restrict__ y,
@@ -712,40 +525,56 @@ __global__ __launch_bounds__(256) void rect_tile_kernel(const T *__restrict__ x,
     if (tid < 4) partial[(int64_t)blockIdx.x * 4 + tid] = block_sum_final(red, tid);
 }
 
-// the ARD form on scaled points: S_0 = sum c_ji, S_k = sum c_ji t_k^2 with c_ji = coef_ji k_ji -- tile_reduce_ard_kernel's
-// two walks over the dimensions, its DMAX ladder and its register array
-template <typename T, int DMAX>
-__global__ __launch_bounds__(256) void rect_tile_ard_kernel(const T *__restrict__ xs, int64_t n, const T *__restrict__ zs, int64_t m,
-                                                              int d, const T *__restrict__ P, int64_t ldp, const T *__restrict__ y,
-                                                              const T *__restrict__ w, double c2, int64_t ntiles_c, int64_t total,
+// ---------------------------------------------------------------------------
+// The same pass for the Gaussian ARD family (d + 1 kernel parameters): with t_k = (a_k - b_k) / w_k (the difference of the
+// SCALED points) and c_ab = coef_ab k_ab (coef as above, by FORM) it accumulates
+//   S_0 = sum c_ab,   S_k = sum c_ab t_k^2  (k = 1 .. d),   the last slot (tr M; TILE_RECT: 0)
+// from which the host forms the gradient (dk/dh = 2k/h, dk/dw_k = k (t_k^2 - 1/d) / w_k: grad_from_sums).
+// One read of M, nothing n x n x d anywhere, no atomics; the same fixed grid, tile walk and host summation as above, f64
+// sums for both dtypes: bitwise repeatable.
+// Per tile a thread (one column, 16 rows) first forms its 16 weights c_ab -- squared distance in T as the matrix build
+// forms it, one exp each -- and keeps them in registers, then walks the dimensions once more: S_k += sum_i c_i t_ik^2.
+// d is a run-time value and d accumulators indexed by a loop variable would live in scratch memory, so the kernel is
+// compiled for DMAX = 8, 16, 32, 64 accumulators and that loop is unrolled over DMAX with a uniform `k < d` guard: every
+// acc[k] is a register (no scratch: see DESIGN 3.4 for the compiler's resource line).  The staged points are zero beyond d.
+// S_0, the S_k and the last slot share ONE register array, so the block sum is the shared helper's.
+// ---------------------------------------------------------------------------
+template <typename T, int DMAX, int FORM>
+__global__ __launch_bounds__(256) void tile_reduce_ard_kernel(const T *__restrict__ xs, int64_t n, int d, TileArgs<T, FORM> a,
+                                                              const T *__restrict__ M, int64_t ldm, double c2, int64_t nt,
                                                               double *__restrict__ partial)
 {
+    constexpr bool RECT = FORM == TILE_RECT;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    T *s1 = reinterpret_cast<T *>(smem_raw);          // [GR_T][DMAX]   rows (x)
-    T *s2 = s1 + (size_t)GR_T * DMAX;                 // [DMAX][GR_T]   columns (z), transposed
-    T *sy = s2 + (size_t)GR_T * DMAX;                 // y rows
-    T *sw = sy + GR_T;                                // w cols
+    T *s1 = reinterpret_cast<T *>(smem_raw);          // [GR_T][DMAX]   rows
+    T *s2 = s1 + (size_t)GR_T * DMAX;                 // [DMAX][GR_T]   columns, transposed
+    T *sa1 = s2 + (size_t)GR_T * DMAX;                // a rows  (TILE_RECT: y)
+    T *sa2 = sa1 + GR_T;                              // a cols  (TILE_RECT: w)
+    T *sb1 = sa2 + GR_T;                              // b rows  (TILE_LOO)
+    T *sb2 = sb1 + GR_T;                              // b cols
     __shared__ double red[4][DMAX + 2];
     const int tid = threadIdx.x, col = tid & 63;
-    const int rg = __builtin_amdgcn_readfirstlane(tid >> 6);
-    double acc[DMAX + 2];                             // slot 0: S_0, 1 .. DMAX: S_k, DMAX + 1: stays 0
+    const int rg = __builtin_amdgcn_readfirstlane(tid >> 6);      // (the wave's index: uniform, so the row reads broadcast)
+    const T *xc = xs;                                 // the columns' points and their count
+    int64_t nc = n;
+    if constexpr (RECT) { xc = a.z; nc = a.m; }
+    double acc[DMAX + 2];                             // slot 0: S_0, 1 .. DMAX: S_k, DMAX + 1: the last slot
 #pragma unroll
     for (int k = 0; k < DMAX + 2; ++k) acc[k] = 0.0;
+    const int64_t total = RECT ? nt : nt * (nt + 1) / 2;
     for (int64_t t = blockIdx.x; t < total; t += gridDim.x) {
-        const int64_t tr = t / ntiles_c, tc = t - tr * ntiles_c;
-        const int64_t r0 = tr * GR_T, c0 = tc * GR_T;
+        int64_t r0, c0;
+        tile_origin(a, t, &r0, &c0);
         __syncthreads();
         for (int idx = tid; idx < GR_T * DMAX; idx += 256) {
             const int r = idx / DMAX, k = idx - r * DMAX;
             s1[idx] = (k < d && r0 + r < n) ? xs[(r0 + r) * d + k] : (T)0;
-            s2[(size_t)k * GR_T + r] = (k < d && c0 + r < m) ? zs[(c0 + r) * d + k] : (T)0;
+            s2[(size_t)k * GR_T + r] = (k < d && c0 + r < nc) ? xc[(c0 + r) * d + k] : (T)0;
         }
-        if (tid < GR_T) {
-            sy[tid] = (r0 + tid < n) ? y[r0 + tid] : (T)0;
-            sw[tid] = (c0 + tid < m) ? w[c0 + tid] : (T)0;
-        }
+        stage_tile_vecs(a, sa1, tid, r0, n, c0, nc);
         __syncthreads();
         const int64_t gc = c0 + col;
+        // the squared distances of this thread's 16 entries, accumulated as kmat_kernel accumulates them
         T r2[16];
 #pragma unroll
         for (int i = 0; i < 16; ++i) r2[i] = (T)0;
@@ -758,15 +587,25 @@ __global__ __launch_bounds__(256) void rect_tile_ard_kernel(const T *__restrict_
                 r2[i] = fma(tt, tt, r2[i]);
             }
         }
+        // the weights c_ab (0 for an entry outside the matrix or, in a symmetric pass, above the diagonal: M is only read inside)
         double c[16];
-        const double wk = (double)sw[col];
+        const double ak = (double)sa2[col], bk = FORM == TILE_LOO ? (double)sb2[col] : 0.0;
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
             const int r = rg + 4 * i;
             const int64_t gr = r0 + r;
             double ci = 0.0;
-            if (gr < n && gc < m) {
-                const double coef = (double)P[gr * ldp + gc] + (double)sy[r] * wk;
+            if (gr < n && (RECT ? gc < nc : gc <= gr)) {
+                const double mjk = (double)M[gr * ldm + gc];
+                double coef;
+                if constexpr (RECT) {
+                    coef = mjk + (double)sa1[r] * ak;
+                } else {
+                    const double wt = (gc == gr) ? 1.0 : 2.0;
+                    coef = FORM == TILE_ML ? wt * ((double)sa1[r] * ak - mjk)
+                                           : wt * (0.5 * ((double)sb1[r] * ak + (double)sa1[r] * bk) - mjk);
+                    if (gc == gr) acc[DMAX + 1] += mjk;
+                }
                 const double e = -0.5 * (double)r2[i];
                 if (!(e < GPX_MIN_LOG)) ci = coef * (c2 * exp(e));
             }
@@ -777,13 +616,13 @@ __global__ __launch_bounds__(256) void rect_tile_ard_kernel(const T *__restrict_
         for (int k = 0; k < DMAX; ++k) {
             if (k < d) {
                 const T b = s2[(size_t)k * GR_T + col];
-                double a = 0.0;
+                double a2 = 0.0;
 #pragma unroll
                 for (int i = 0; i < 16; ++i) {
                     const double tt = (double)(s1[(rg + 4 * i) * DMAX + k] - b);
-                    a = fma(c[i], tt * tt, a);
+                    a2 = fma(c[i], tt * tt, a2);
                 }
-                acc[1 + k] += a;
+                acc[1 + k] += a2;
             }
         }
     }
@@ -792,62 +631,145 @@ __global__ __launch_bounds__(256) void rect_tile_ard_kernel(const T *__restrict_
     if (tid < d + 2) partial[(int64_t)blockIdx.x * (d + 2) + tid] = block_sum_final(red, tid <= d ? tid : DMAX + 1);
 }
 
-template <typename T, int DMAX>
-static int launch_rect_reduce_ard(const void *xs, int64_t n, const void *zs, int64_t m, int d, const void *P, int64_t ldp, const void *y,
-                                  const void *w, double c2, double *partial_dev, hipStream_t st)
+// the partial sums of `width` quantities per workgroup, added on the host in workgroup order
+static int sum_partials(const double *partial_dev, int width, double *out, hipStream_t st)
 {
-    const size_t smem = ((size_t)2 * GR_T * DMAX + 2 * GR_T) * sizeof(T);
-    if (smem > 48 * 1024) GPX_TRY(set_max_lds((const void *)rect_tile_ard_kernel<T, DMAX>, LDS_TILE_MAX));
-    const int64_t ntc = cdiv(m, GR_T), total = cdiv(n, GR_T) * ntc;
-    hipLaunchKernelGGL((rect_tile_ard_kernel<T, DMAX>), dim3((unsigned)std::min<int64_t>(GR_BLOCKS, total)), dim3(256), smem, st,
-                       (const T *)xs, n, (const T *)zs, m, d, (const T *)P, ldp, (const T *)y, (const T *)w, c2, ntc, total, partial_dev);
-    GPX_LAUNCH_CHECK();
+    std::vector<double> host((size_t)GR_BLOCKS * width);
+    GPX_HIP(hipMemcpyAsync(host.data(), partial_dev, host.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    GPX_HIP(hipStreamSynchronize(st));
+    for (int q = 0; q < width; ++q) {
+        double v = 0.0;
+        for (int b = 0; b < GR_BLOCKS; ++b) v += host[(size_t)b * width + q];
+        out[q] = v;
+    }
     return GPX_OK;
 }
 
-template <typename T>
-static int launch_rect_reduce(int kernel, const void *x, int64_t n, const void *z, int64_t m, int d, const double *params, const void *P,
-                              int64_t ldp, const void *y, const void *w, double *partial_dev, hipStream_t st)
+// the Gaussian k's constant, make_kparams' c2 of GPX_K: h^2 sqrt(2 / pi) / (2 w).  (make_kparams multiplies h * h first, which
+// rounds differently in one pair of three: one spelling there would move either every entry of K or every gradient by an ulp)
+static inline double gaussian_k_const(double h, double w) { return 0.5 * sqrt(2.0 / M_PI) * h * h / w; }
+
+static int make_grad_params(int kernel, int d, const double *params, GradParams *gpar)
 {
+    memset(gpar, 0, sizeof(*gpar));
+    gpar->kernel = kernel;
+    if (kernel == GPX_KERNEL_GAUSSIAN) {
+        const double h = params[0], w = params[1], S = sqrt(2.0 / M_PI);
+        gpar->nkp = 2;
+        gpar->c1 = -0.5 / (w * w);
+        gpar->c2h = S * h / w;                         // gaussian_c.pyx:61
+        gpar->c2w = 0.5 * S * h * h / (w * w);         // :82
+        gpar->c3w = 0.5 * S * h * h / pow(w, 4);       // :83
+    } else {
+        if (d != 1) { set_error("periodic gradient needs d == 1"); return GPX_ERR_UNSUPPORTED; }
+        gpar->nkp = 3; gpar->h = params[0]; gpar->w = params[1]; gpar->p = params[2];
+    }
+    return GPX_OK;
+}
+
+// f(std::integral_constant<int, DMAX>()) for the rung of the ARD kernels' ladder that holds d: `decltype(dm)::value` names DMAX
+template <typename F>
+static inline int by_dmax(int d, F f)
+{
+    if (d <= 8) return f(std::integral_constant<int, 8>());
+    if (d <= 16) return f(std::integral_constant<int, 16>());
+    if (d <= 32) return f(std::integral_constant<int, 32>());
+    return f(std::integral_constant<int, 64>());
+}
+
+// the dynamic LDS of a tile: two staged point sets of dk coordinates (d, or the ARD kernels' DMAX) and nvec vectors
+static int tile_lds(int dk, int nvec, size_t es, size_t *bytes)
+{
+    *bytes = ((size_t)2 * GR_T * dk + (size_t)nvec * GR_T) * es;
+    if (*bytes <= (size_t)LDS_TILE_MAX) return GPX_OK;
+    set_error("tile reduction: d = %d too large for the LDS-staged tile", dk);
+    return GPX_ERR_UNSUPPORTED;
+}
+
+// one launch of the family's kernel for the form; kernel == GPX_KERNEL_GAUSSIAN_ARD: the points are the SCALED ones and params = iso
+template <typename T, int FORM>
+static int launch_tile_reduce(int kernel, const void *x, int64_t n, int d, const double *params, const TileArgs<T, FORM> &a, const void *M,
+                              int64_t ldm, int64_t nt, double *partial_dev, hipStream_t st)
+{
+    constexpr int NVEC = FORM == TILE_LOO ? 4 : 2;
+    const dim3 grid((unsigned)std::min<int64_t>(GR_BLOCKS, FORM == TILE_RECT ? nt : nt * (nt + 1) / 2)), block(256);
+    size_t smem = 0;
     if (kernel == GPX_KERNEL_GAUSSIAN_ARD) {
-        const double c2 = 0.5 * sqrt(2.0 / M_PI) * params[0] * params[0] / params[1];     // make_kparams, GPX_K, of iso
-        if (d <= 8) return launch_rect_reduce_ard<T, 8>(x, n, z, m, d, P, ldp, y, w, c2, partial_dev, st);
-        if (d <= 16) return launch_rect_reduce_ard<T, 16>(x, n, z, m, d, P, ldp, y, w, c2, partial_dev, st);
-        if (d <= 32) return launch_rect_reduce_ard<T, 32>(x, n, z, m, d, P, ldp, y, w, c2, partial_dev, st);
-        return launch_rect_reduce_ard<T, 64>(x, n, z, m, d, P, ldp, y, w, c2, partial_dev, st);
+        const double c2 = gaussian_k_const(params[0], params[1]);
+        return by_dmax(d, [&](auto dm) -> int {
+            constexpr int DMAX = decltype(dm)::value;
+            GPX_TRY(tile_lds(DMAX, NVEC, sizeof(T), &smem));
+            if (smem > 48 * 1024) GPX_TRY(set_max_lds((const void *)tile_reduce_ard_kernel<T, DMAX, FORM>, LDS_TILE_MAX));
+            hipLaunchKernelGGL((tile_reduce_ard_kernel<T, DMAX, FORM>), grid, block, smem, st, (const T *)x, n, d, a, (const T *)M, ldm,
+                               c2, nt, partial_dev);
+            GPX_LAUNCH_CHECK();
+            return GPX_OK;
+        });
     }
     GradParams gpar;
     GPX_TRY(make_grad_params(kernel, d, params, &gpar));
-    const double ck = kernel == GPX_KERNEL_GAUSSIAN ? 0.5 * sqrt(2.0 / M_PI) * params[0] * params[0] / params[1] : 0.0;
-    const size_t smem = ((size_t)2 * GR_T * d + 2 * GR_T) * sizeof(T);
-    if (smem > 48 * 1024) GPX_TRY(set_max_lds((const void *)rect_tile_kernel<T>, LDS_TILE_MAX));
-    const int64_t ntc = cdiv(m, GR_T), total = cdiv(n, GR_T) * ntc;
-    hipLaunchKernelGGL((rect_tile_kernel<T>), dim3((unsigned)std::min<int64_t>(GR_BLOCKS, total)), dim3(256), smem, st, (const T *)x, n,
-                       (const T *)z, m, d, (const T *)P, ldp, (const T *)y, (const T *)w, gpar, ck, ntc, total, partial_dev);
+    GPX_TRY(tile_lds(d, NVEC, sizeof(T), &smem));
+    if constexpr (FORM == TILE_RECT) {
+        const double ck = kernel == GPX_KERNEL_GAUSSIAN ? gaussian_k_const(params[0], params[1]) : 0.0;
+        if (smem > 48 * 1024) GPX_TRY(set_max_lds((const void *)rect_tile_kernel<T>, LDS_TILE_MAX));
+        hipLaunchKernelGGL((rect_tile_kernel<T>), grid, block, smem, st, (const T *)x, n, a.z, a.m, d, (const T *)M, ldm, a.y, a.w, gpar, ck,
+                           a.ntiles_c, nt, partial_dev);
+    } else {
+        if (smem > 48 * 1024) GPX_TRY(set_max_lds((const void *)tile_reduce_kernel<T, FORM>, LDS_TILE_MAX));
+        hipLaunchKernelGGL((tile_reduce_kernel<T, FORM>), grid, block, smem, st, (const T *)x, n, d, a, (const T *)M, ldm, gpar, nt,
+                           partial_dev);
+    }
     GPX_LAUNCH_CHECK();
     return GPX_OK;
 }
 
-// kernel == GPX_KERNEL_GAUSSIAN_ARD: x, z are the SCALED points and params = iso = (h / sqrt(wbar), 1)
-int rect_reduce(int dtype, int kernel, const void *x, int64_t n, const void *z, int64_t m, int d, const double *params, const void *P,
-                int64_t ldp, const void *y, const void *w, double *partial_dev, double *out, hipStream_t st)
+size_t dloglh_partial_doubles(int kernel, int d) { return (size_t)GR_BLOCKS * (kernel == GPX_KERNEL_GAUSSIAN_ARD ? d + 2 : 4); }
+
+// what both host entries do around their launch: the ARD family's range of d, the cleared partials, the profile scope, the
+// host's sum of the partials into out (dloglh_partial_doubles() / GR_BLOCKS values)
+template <typename L>
+static int tile_pass(int prof_class, double work, int kernel, int d, double *partial_dev, double *out, hipStream_t st, L launch)
 {
-    const bool ard = kernel == GPX_KERNEL_GAUSSIAN_ARD;
-    if (ard && (d < 1 || d > GPX_ARD_MAX_D)) { set_error("ARD gradient needs 1 <= d <= %d (got %d)", GPX_ARD_MAX_D, d); return GPX_ERR_ARG; }
-    if (n < 1 || m < 1 || ldp < m) { set_error("rect_reduce: need n, m >= 1 and ldp >= m"); return GPX_ERR_ARG; }
-    const int width = ard ? d + 2 : 4;
-    if ((size_t)2 * GR_T * (ard ? 64 : d) * esize(dtype) + 2 * GR_T * esize(dtype) > (size_t)LDS_TILE_MAX) {
-        set_error("rect_reduce: d = %d too large for the LDS-staged tile", d);
-        return GPX_ERR_UNSUPPORTED;
+    if (kernel == GPX_KERNEL_GAUSSIAN_ARD && (d < 1 || d > GPX_ARD_MAX_D)) {
+        set_error("ARD gradient needs 1 <= d <= %d (got %d)", GPX_ARD_MAX_D, d);
+        return GPX_ERR_ARG;
     }
+    const int width = (int)(dloglh_partial_doubles(kernel, d) / GR_BLOCKS);
     GPX_HIP(hipMemsetAsync(partial_dev, 0, (size_t)GR_BLOCKS * width * sizeof(double), st));
     {
-        ProfScope prof(PC_SPARSE_GRAD, (double)n * (double)m, st);
-        if (dtype == GPX_F64) GPX_TRY(launch_rect_reduce<double>(kernel, x, n, z, m, d, params, P, ldp, y, w, partial_dev, st));
-        else GPX_TRY(launch_rect_reduce<float>(kernel, x, n, z, m, d, params, P, ldp, y, w, partial_dev, st));
+        ProfScope prof(prof_class, work, st);
+        GPX_TRY(launch());
     }
     return sum_partials(partial_dev, width, out, st);
 }
+
+int tile_reduce(int dtype, int kernel, const void *x, int64_t n, int d, const double *params, const void *vec_a, const void *vec_b,
+                const void *M, int64_t ldm, double *partial_dev, double *out, hipStream_t st)
+{
+    // (the launch's lower triangle of M read once as its byte count)
+    return tile_pass(PC_REDUCE, 0.5 * (double)n * (double)(n + 1) * (double)esize(dtype), kernel, d, partial_dev, out, st, [&] {
+        return by_dtype(dtype, [&](auto t) -> int {
+            using T = decltype(t);
+            if (!vec_b) return launch_tile_reduce(kernel, x, n, d, params, TileArgs<T, TILE_ML>{(const T *)vec_a}, M, ldm, cdiv(n, GR_T), partial_dev, st);
+            return launch_tile_reduce(kernel, x, n, d, params, TileArgs<T, TILE_LOO>{(const T *)vec_a, (const T *)vec_b}, M, ldm, cdiv(n, GR_T), partial_dev, st);
+        });
+    });
+}
+
+int rect_reduce(int dtype, int kernel, const void *x, int64_t n, const void *z, int64_t m, int d, const double *params, const void *P,
+                int64_t ldp, const void *y, const void *w, double *partial_dev, double *out, hipStream_t st)
+{
+    if (n < 1 || m < 1 || ldp < m) { set_error("rect_reduce: need n, m >= 1 and ldp >= m"); return GPX_ERR_ARG; }
+    return tile_pass(PC_SPARSE_GRAD, (double)n * (double)m, kernel, d, partial_dev, out, st, [&] {
+        return by_dtype(dtype, [&](auto t) -> int {
+            using T = decltype(t);
+            const int64_t ntc = cdiv(m, GR_T);
+            return launch_tile_reduce(kernel, x, n, d, params, TileArgs<T, TILE_RECT>{(const T *)z, m, (const T *)y, (const T *)w, ntc}, P, ldp,
+                                      cdiv(n, GR_T) * ntc, partial_dev, st);
+        });
+    });
+}
+
 
 // The host half of either gradient: the sums of a pass -> (d/d kernel params ..., d/ds).  factor: 1/2 for the marginal
 // likelihood (RW06 eq. 5.9), 1 for the leave-one-out criterion (dL = sum dK_ab G_ab); it enters only as a product by 1/2, 1 or
@@ -904,8 +826,7 @@ int gpx_d_kmat(int dtype, int kernel, int member, const void *x1, int64_t n, con
     }
     KParams kp;
     GPX_TRY(make_kparams(kernel, member, params, diag_add, &kp));
-    if (dtype == GPX_F64) return launch_kmat<double>(x1, n, x2, m, d, kp, tri, out, ld, S(stream));
-    return launch_kmat<float>(x1, n, x2, m, d, kp, tri, out, ld, S(stream));
+    return by_dtype(dtype, [&](auto t) { return launch_kmat<decltype(t)>(x1, n, x2, m, d, kp, tri, out, ld, S(stream)); });
 }
 
 int gpx_d_scale_points(int dtype, const void *x, int64_t n, int d, const double *w_host, void *out, void *stream)

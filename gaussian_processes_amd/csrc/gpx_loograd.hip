@@ -99,14 +99,8 @@ int loo_grad_reduce(gpx_gp *g, const void *pts, const void *alpha, const double 
                     const void *Pm, int64_t ldp, double *part, double *value, double *out)
 {
     const int64_t n = g->n;
-    double S[GPX_ARD_MAX_D + 2], sums[2] = {0.0, 0.0};
-    if (g->kernel == GPX_KERNEL_GAUSSIAN_ARD) {
-        double iso[2];
-        ard_iso(params, g->d, iso);
-        GPX_TRY(tile_reduce_ard(g->dtype, pts, n, g->d, iso, alpha, v.r, Pm, ldp, part, S, g->st));
-    } else {
-        GPX_TRY(tile_reduce(g->dtype, g->kernel, pts, n, g->d, params, alpha, v.r, Pm, ldp, part, S, g->st));
-    }
+    double S[GPX_ARD_MAX_D + 2], iso[2], sums[2] = {0.0, 0.0};
+    GPX_TRY(tile_reduce(g->dtype, g->kernel, pts, n, g->d, reduce_params(g->kernel, g->d, params, iso), alpha, v.r, Pm, ldp, part, S, g->st));
     GPX_HIP(hipMemcpyAsync(sums, v.sums, sizeof(sums), hipMemcpyDeviceToHost, g->st));
     GPX_HIP(hipStreamSynchronize(g->st));
     grad_from_sums(g->kernel, g->d, params, S, sums[1], 2.0 * s_noise, 1.0, out);

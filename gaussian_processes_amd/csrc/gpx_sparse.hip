@@ -499,8 +499,7 @@ static int sgp_grad(gpx_sgp *g, int64_t chunk_cols, double *grad)
     GPX_TRY(dot(dtype, g->w, g->t0, M, wb_dev, st));                                  // w . b
     // sum (w w^T - Mm) o dKuu = -2 sum Gu o dKuu: the dense gradient's pass on z
     double Suu[GPX_ARD_MAX_D + 2], Srect[GPX_ARD_MAX_D + 2], out[GPX_ARD_MAX_D + 2], wb = 0.0;
-    if (ard) GPX_TRY(tile_reduce_ard(dtype, g->zs, M, d, g->iso, g->w, nullptr, Mm, ldm, part, Suu, st));
-    else GPX_TRY(tile_reduce(dtype, g->kernel, g->z, M, d, g->params, g->w, nullptr, Mm, ldm, part, Suu, st));
+    GPX_TRY(tile_reduce(dtype, g->kernel, v.z, M, d, v.params, g->w, nullptr, Mm, ldm, part, Suu, st));
     GPX_HIP(hipMemcpyAsync(&wb, wb_dev, sizeof(double), hipMemcpyDeviceToHost, st));
     GPX_HIP(hipEventRecord(g->gev[1], st));
 

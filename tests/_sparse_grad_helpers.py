@@ -75,11 +75,27 @@ def sgpr_grad_reference(kind, params, x, y, z, s, jitter, dtype=np.float64):
 
 
 # ---- the data of the edge shapes and the references of every GPU case, one evaluation each --------------------------------------
+# The ARD shapes beyond d = 3, one per rung of the kernel's DMAX ladder above the first (d = 9, 17, 33: DMAX = 16, 32, 64): the
+# widths of test_gpu_ard._widths(d) stretched by c(d).  Unstretched, the inputs (standard deviation ~ 5.8) put the median of
+# k(x_j, z_i) / k(0) over the rectangle at 1e-138 (d = 9): only coincident points would contribute, and there t_k = 0, so the S_k
+# sums would be exactly zero whatever the kernel computes.  tests/test_sparse_grad_cpu.py holds the median above 1e-5.
+ARD_STRETCH = {9: 6.0, 17: 8.0, 33: 12.0}
+ARD_RUNG_KEYS = [("ard", 129, d, 65) for d in sorted(ARD_STRETCH)]
+
+
 def edge_params(kind, d):
     if kind == "ard" and d != 3:
         from test_gpu_ard import _widths
-        return (1.0,) + tuple(_widths(d))
+        return (1.0,) + tuple(ARD_STRETCH[d] * _widths(d))
     return kernel_params(kind, d)
+
+
+def median_kernel_ratio(key):
+    """The median over the rectangle of k(x_j, z_i) / k(0) of a key."""
+    params, x, _, z = problem(key)
+    okind, op, xv, zv = oracle_view(key[0], params, x, z)
+    K = orc.kernel_matrix(okind, "K", xv, zv, op)
+    return float(np.median(K) / orc.kernel_matrix(okind, "K", zv[:1], zv[:1], op)[0, 0])
 
 
 def make_kernel(kind, params):

@@ -8,7 +8,8 @@ the terms that enter component p).  fp32 (automatic jitter): ORACLE_TOL["float32
 between the fp32 and the fp64 run of the restatement at the fp32 jitter: the rule of tests/test_gpu_sparse.py.  Every test
 prints error, bound and floor per component.
 Shapes: (N, M) at the edges of the 64-tile and of a 128-column chunk (chunk_cols = 128: 2 and 3 chunks with ragged last chunks
-of 1 and 44 columns), all three families, ARD at d = 9 (the DMAX = 16 rung) once; the six cases of tests/_sparse_helpers.py
+of 1 and 44 columns), all three families, ARD at d = 9, 17, 33 (the DMAX = 16, 32, 64 rungs of the rectangular pass; widths
+at which the rectangle's entries are not all zero: ARD_RUNG_KEYS) at 129 x 65; the six cases of tests/_sparse_helpers.py
 at automatic chunking, the first of them under its depth-slice plans as well."""
 import numpy as np
 import pytest
@@ -17,12 +18,12 @@ import gaussian_processes_amd as gp
 from gaussian_processes_amd import _lib
 from test_gpu_var import C_COND, ORACLE_TOL
 from _sparse_helpers import CASES, CASE_IDS, PLANS_N1000, S_NOISE, case_data, case_jitter
-from _sparse_grad_helpers import E32G, EDGE_PAIRS, grad_reference, make_kernel, problem
+from _sparse_grad_helpers import ARD_RUNG_KEYS, E32G, EDGE_PAIRS, grad_reference, make_kernel, problem
 
 pytestmark = pytest.mark.gpu
 
 _EPS = float(np.finfo(np.float64).eps)
-EDGE_KEYS = [(kind, N, d, M) for N, M in EDGE_PAIRS for kind, d in (("gaussian", 3), ("periodic", 1), ("ard", 3))] + [("ard", 129, 9, 65)]
+EDGE_KEYS = [(kind, N, d, M) for N, M in EDGE_PAIRS for kind, d in (("gaussian", 3), ("periodic", 1), ("ard", 3))] + ARD_RUNG_KEYS
 EDGE_IDS = ["%s-%d-%d-%d" % k for k in EDGE_KEYS]
 START = np.array([1.5, 0.7, 1.3])
 

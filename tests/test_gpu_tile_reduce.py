@@ -1,5 +1,5 @@
-"""GPU tests of the shared tile walk of the two hyper-parameter gradients (csrc/gpx_kmat.hip: tile_reduce_kernel<T, NV>,
-tile_reduce_ard_kernel<T, DMAX, NV>): GP.dloglh_dtheta (NV = 1) and GP.dloo_dtheta (NV = 2) on ONE fitted handle at the sizes
+"""GPU tests of the shared tile walk of the two hyper-parameter gradients (csrc/gpx_kmat.hip: tile_reduce_kernel<T, FORM>,
+tile_reduce_ard_kernel<T, DMAX, FORM>): GP.dloglh_dtheta (TILE_ML) and GP.dloo_dtheta (TILE_LOO) on ONE fitted handle at the sizes
 where a walk over 64 x 64 tiles of a lower triangle can go wrong -- N = 1 and 63 (one partial tile), 64 (exactly one tile),
 65 (the first off-diagonal tile, one row and one column of it), 129 (a 3 x 3 tile triangle with a ragged edge) -- for the
 Gaussian family (d = 3), the periodic family (d = 1) and the ARD family at d = 9 (DMAX = 16: zero padding past d).

@@ -183,9 +183,14 @@ def test_streamed_reductions_keep_one_copy_of_each_piece():
     # -- DESIGN "Streamed reductions".  The tile reductions of gpx_kmat.hip all go through the helper (one register array
     # for S_0, the S_k and the trace)
     assert sites(r"off = 32; off > 0; off >>= 1") == {"gpx_kernels_dev.h": 1, "gpx_deriv.hip": 1, "gpx_small.hip": 1}
-    # one tile walk for both hyper-parameter gradients: two kernels, one host summation of the partials
+    # one tile walk for the symmetric passes of both hyper-parameter gradients and, in the ARD kernel, the sparse gradient's
+    # rectangular pass: ALL kernels of the file are the build, the ARD scaling, the pair of tile reductions and the one
+    # rectangular kernel that measured slower as a third form of tile_reduce_kernel; one host summation of the partials
     kmat = code("gpx_kmat.hip")
-    assert re.findall(r"__global__ __launch_bounds__\(256\) void (\w+_reduce\w*)\(", kmat) == ["tile_reduce_kernel", "tile_reduce_ard_kernel"]
+    assert re.findall(r"__global__[^;{]*?\bvoid\s+(\w+)\s*\(", kmat) == ["kmat_kernel", "scale_points_kernel", "tile_reduce_kernel", "rect_tile_kernel",
+                                                                         "tile_reduce_ard_kernel"]
+    for f in files:
+        assert "rect_tile_ard" not in open(os.path.join(csrc, f)).read(), f
     assert len(re.findall(r"v \+= host\[", kmat)) == 1
     for f in ("gpx_kmat.hip", "gpx_deriv.hip", "gpx_stream.hip", "gpx_paths.hip"):
         assert "((red[0]" not in code(f), f
@@ -224,7 +229,7 @@ def test_small_device_kernels_have_one_home():
     for f in files:
         for name in gone:
             assert not re.search(r"\b%s\b" % name, src[f]), (f, name)
-    untouched = ("gpx_gemm.hip", "gpx_panel.hip", "gpx_leaf.h", "gpx_kmat.hip", "gpx_stream.hip", "gpx_kernels_dev.h", "gpx_mg.hip",
+    untouched = ("gpx_gemm.hip", "gpx_panel.hip", "gpx_leaf.h", "gpx_stream.hip", "gpx_kernels_dev.h", "gpx_mg.hip",
                  "gpx_runtime.hip", "gpx_potrf.hip")
     for f in files:
         if f not in untouched:

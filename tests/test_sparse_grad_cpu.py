@@ -15,7 +15,7 @@ import gaussian_processes_amd as gp
 from gaussian_processes_amd import _lib
 from conftest import ROOT
 from _sparse_helpers import CASES, CASE_IDS, S_NOISE, case_data, case_jitter, make_kernel, sgpr_reference
-from _sparse_grad_helpers import sgpr_grad_reference
+from _sparse_grad_helpers import ARD_RUNG_KEYS, median_kernel_ratio, sgpr_grad_reference
 
 
 @pytest.mark.parametrize("jitter_of", [np.float64, np.float32], ids=["jitter64", "jitter32"])
@@ -43,6 +43,17 @@ def test_closed_form_against_central_differences(case, jitter_of):
         print("theta[%d]: closed %+.9e  fd %+.9e  |closed - fd| / (1 + |closed|) = %.2e  (scale %.2e)" % (p, closed[p], fd, ratio, scale[p]))
         assert abs(closed[p] - fd) <= 1e-6 * (1.0 + abs(closed[p])), p
     print("%s jitter %.3e: largest ratio %.2e" % (CASE_IDS[CASES.index(case)], jitter, worst))
+
+
+def test_ard_rung_shapes_have_entries_that_count():
+    """The ARD shapes of the GPU test's DMAX = 16, 32, 64 rungs: half the rectangle's entries are at least 1e-5 k(0).  With
+    entries that underflow only coincident points contribute, their t_k are zero, and the S_k sums of the rectangular
+    pass would be exactly zero whatever the kernel computes."""
+    assert [k[2] for k in ARD_RUNG_KEYS] == [9, 17, 33]
+    for key in ARD_RUNG_KEYS:
+        med = median_kernel_ratio(key)
+        print("%s: median k / k(0) = %.2e" % (key, med))
+        assert med >= 1e-5, key
 
 
 # ---- optimize() with the numpy restatement in place of the device ----------------------------------------------------------
