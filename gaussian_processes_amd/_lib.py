@@ -87,6 +87,11 @@ _SIGNATURES = {
                                   c_void_p]),
     "gpx_d_syrk_bc": (c_int, [c_int, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int64, c_void_p,
                               c_int64, c_int64, c_int64, c_int64, c_int, c_int, c_void_p]),
+    "gpx_debug_gemm_nt": (c_int, [c_int, c_int64, c_int64, c_int64, c_double, c_void_p, c_int64, c_void_p, c_int64, c_void_p,
+                                  c_int64, c_int, c_int64, c_int64, c_int, c_int, c_int, c_int64, c_int64, c_int64, c_int,
+                                  c_int64, c_int64, c_int64, c_void_p]),
+    "gpx_debug_syrk_bc": (c_int, [c_int, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64,
+                                  c_int64, c_int64, c_int, c_int, c_void_p, c_int, c_int64, c_int64, c_void_p]),
     "gpx_d_tril": (c_int, [c_int, c_void_p, c_int64, c_int64, c_void_p]),
     "gpx_d_trsv_lower": (c_int, [c_int, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int,
                                  c_void_p]),

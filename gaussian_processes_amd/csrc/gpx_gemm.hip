@@ -961,6 +961,8 @@ int gemm_nt(int dtype, int64_t M, int64_t N, int64_t K, const void *A, int64_t l
             hipStream_t st, int beta0, int ktri, const Batch *bt, int wide_tiles)
 {
     if (M <= 0 || N <= 0 || K <= 0) return GPX_OK;
+    // the vector epilogue's lane pair that straddles the diagonal would store 0 (not C) into the first strictly upper element
+    if (beta0 && tri == GPX_LOWER) { set_error("gemm_nt: beta = 0 needs tri = GPX_FULL (the strict upper triangle would be written)"); return GPX_ERR_UNSUPPORTED; }
     const bool no_fast = tune().gemm_no_fast;
     const int64_t epk = 128 / (int64_t)esize(dtype), ch = 16 / (int64_t)esize(dtype);
     const bool fast = !no_fast && K % epk == 0 && lda % ch == 0 && ldb % ch == 0 &&
@@ -1041,6 +1043,11 @@ int syrk_bc(int dtype, int64_t n, int64_t row_begin, void *Cloc, int64_t ldc, in
         const int64_t pbr = cdiv(M, 1024), pbc = cdiv(Ncols, 1024);
         fm.a = P; fm.csh = 3;
         fm.b = (int)std::max<int64_t>(0, (G0 - row_begin) / 1024);
+        // Rows that begin BELOW the first column's diagonal (row_begin > G0): patch column pc still holds elements at or below
+        // the diagonal from patch row floor((G0 - row_begin) / 1024) + P * pc on, one (or more) above where the staircase
+        // starts it -- with more than one patch column the staircase dropped them (tests/test_gpu_gemm.py: kb < nb, or
+        // row_begin 64 below the panel).  The whole rectangle of patches then; tiles above the diagonal return at once.
+        if (G0 < row_begin && pbc > 1) fm.a = 0;
         fm.R = (int)pbr - fm.b;
         if (fm.R <= 0) return GPX_OK;
         int64_t np = 0;
@@ -1181,6 +1188,49 @@ extern "C" int gpx_d_syrk_bc(int dtype, int64_t n, int64_t row_begin, void *Cloc
     const int64_t ch = 16 / (int64_t)esize(dtype);
     GPX_ARG(ldp >= kb && ldp % ch == 0 && ((uintptr_t)Pb) % 16 == 0, "panel must be 16-byte aligned");
     return syrk_bc(dtype, n, row_begin, Cloc, ldc, cl0, cl1, Pb, ldp, k0, kb, nb, P, rank, S(stream));
+}
+
+// The two internal entries with the arguments the public ones hide (tests/test_gpu_gemm.py): host code only
+extern "C" int gpx_debug_gemm_nt(int dtype, int64_t M, int64_t N, int64_t K, double alpha, const void *A, int64_t lda,
+                                 const void *B, int64_t ldb, void *C, int64_t ldc, int tri, int64_t row0, int64_t col0,
+                                 int beta0, int ktri, int count, int64_t sA, int64_t sB, int64_t sC, int count2, int64_t tA,
+                                 int64_t tB, int64_t tC, void *stream)
+{
+    GPX_TRY(ensure_device());
+    GPX_ARG(dtype == GPX_F64 || dtype == GPX_F32, "dtype must be GPX_F64 or GPX_F32");
+    GPX_ARG(M >= 0 && N >= 0 && K >= 0, "negative dimension");
+    GPX_ARG((beta0 == 0 || beta0 == 1) && (ktri == 0 || ktri == 1), "beta0 and ktri must be 0 or 1");
+    GPX_ARG(count >= 1 && count2 >= 1 && count <= 65535 && count2 <= 65535, "batch counts must lie in [1, 65535]");
+    if (M == 0 || N == 0 || K == 0) return GPX_OK;
+    GPX_ARG(A && B && C, "NULL pointer");
+    const int64_t ch = 16 / (int64_t)esize(dtype);
+    GPX_ARG(lda >= K && ldb >= K && ldc >= N, "leading dimension too small");
+    GPX_ARG(lda % ch == 0 && ldb % ch == 0, "lda/ldb must be multiples of 16 bytes");
+    GPX_ARG(((uintptr_t)A) % 16 == 0 && ((uintptr_t)B) % 16 == 0, "A/B must be 16-byte aligned");
+    GPX_ARG(tri == GPX_FULL || tri == GPX_LOWER, "tri must be GPX_FULL or GPX_LOWER");
+    Batch bt; bt.count = count; bt.sA = sA; bt.sB = sB; bt.sC = sC;
+    bt.count2 = count2; bt.tA = tA; bt.tB = tB; bt.tC = tC;
+    return gemm_nt(dtype, M, N, K, A, lda, B, ldb, C, ldc, alpha, tri, row0, col0, S(stream), beta0, ktri,
+                   (int64_t)count * count2 > 1 ? &bt : nullptr);
+}
+
+extern "C" int gpx_debug_syrk_bc(int dtype, int64_t n, int64_t row_begin, void *Cloc, int64_t ldc, int64_t cl0, int64_t cl1,
+                                 const void *Pb, int64_t ldp, int64_t k0, int64_t kb, int64_t nb, int P, int rank,
+                                 const int *abort_flag_dev, int count, int64_t sP, int64_t sC, void *stream)
+{
+    GPX_TRY(ensure_device());
+    GPX_ARG(dtype == GPX_F64 || dtype == GPX_F32, "dtype must be GPX_F64 or GPX_F32");
+    GPX_ARG(n >= 0 && row_begin >= 0 && cl0 >= 0 && cl1 >= cl0 && kb >= 0, "bad dimensions");
+    GPX_ARG(P >= 1 && rank >= 0 && rank < P && nb >= 64 && nb % 64 == 0, "bad P / rank / nb");
+    GPX_ARG(k0 + kb <= row_begin, "row_begin must lie below the panel's diagonal block");
+    GPX_ARG(count >= 1 && count <= 65535, "batch count must lie in [1, 65535]");
+    if (n == 0 || cl1 == cl0 || kb == 0) return GPX_OK;
+    GPX_ARG(Cloc && Pb, "NULL pointer");
+    const int64_t ch = 16 / (int64_t)esize(dtype);
+    GPX_ARG(ldp >= kb && ldp % ch == 0 && ((uintptr_t)Pb) % 16 == 0, "panel must be 16-byte aligned");
+    Batch bt; bt.count = count; bt.sA = sP; bt.sB = sP; bt.sC = sC;      // both operands are rows of the panel
+    return syrk_bc(dtype, n, row_begin, Cloc, ldc, cl0, cl1, Pb, ldp, k0, kb, nb, P, rank, S(stream), abort_flag_dev,
+                   count > 1 ? &bt : nullptr);
 }
 
 // diagnostic hook (not declared in gpx.h): per-workgroup s_memtime stamps of the fast GEMM

@@ -317,6 +317,23 @@ int gpx_d_syrk_bc(int dtype, int64_t n, int64_t row_begin, void *Cloc, int64_t l
                   int64_t cl0, int64_t cl1, const void *Pb, int64_t ldp, int64_t k0,
                   int64_t kb, int64_t nb, int P, int rank, void *stream);
 
+/* The same two products with the arguments the public entries hide, for tests (tests/test_gpu_gemm.py); the argument checks
+ * of gpx_d_gemm_nt / gpx_d_syrk_bc apply.
+ * gpx_debug_gemm_nt: beta0 = 1: C = alpha A B^T, C is not read (aligned fast route and tri = GPX_FULL only, GPX_ERR_UNSUPPORTED
+ * otherwise); ktri = 1: A == B upper triangular in (row, k) and M == N == K, the k-loop of a tile row skips the zeros (ignored
+ * on the generic route); count x count2 products, member (y, z) at A + y sA + z tA (elements), B and C alike; a two-dimensional
+ * batch needs the fast route.  C == A is legal when N == K <= 64, beta0 = 1 and ldc == lda: each tile has read all K columns of
+ * its own rows before it stores them, and no other tile touches those rows.
+ * gpx_debug_syrk_bc: abort_flag_dev: DEVICE int per batch member (NULL: none), a member whose word is non-zero is left
+ * untouched (fast route only); count members, panels sP and matrices sC elements apart. */
+int gpx_debug_gemm_nt(int dtype, int64_t M, int64_t N, int64_t K, double alpha, const void *A, int64_t lda,
+                      const void *B, int64_t ldb, void *C, int64_t ldc, int tri, int64_t row0, int64_t col0,
+                      int beta0, int ktri, int count, int64_t sA, int64_t sB, int64_t sC, int count2, int64_t tA,
+                      int64_t tB, int64_t tC, void *stream);
+int gpx_debug_syrk_bc(int dtype, int64_t n, int64_t row_begin, void *Cloc, int64_t ldc, int64_t cl0, int64_t cl1,
+                      const void *Pb, int64_t ldp, int64_t k0, int64_t kb, int64_t nb, int P, int rank,
+                      const int *abort_flag_dev, int count, int64_t sP, int64_t sC, void *stream);
+
 /* Zero the strict upper triangle (scipy's cholesky returns a clean L). */
 int gpx_d_tril(int dtype, void *A, int64_t n, int64_t lda, void *stream);
 
