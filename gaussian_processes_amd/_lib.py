@@ -22,6 +22,7 @@ ERR_ARG, ERR_HIP, ERR_NO_DEVICE, ERR_NOMEM, ERR_UNSUPPORTED, ERR_INTERNAL = -1, 
  ROUTE_GRAD_CHUNK, ROUTE_EXTEND, ROUTE_SAMPLE, ROUTE_KAPPLY_FUSED, ROUTE_KAPPLY_GEMM, ROUTE_PATHS_GRAD_CHUNK,
  ROUTE_REMOVE, ROUTE_SPARSE_CHUNK) = range(26)
 PROF_RANDN, PROF_RFF, PROF_KAPPLY, PROF_KAPPLY_GRAD, PROF_CHOL_DELETE, PROF_SPARSE_GRAM, PROF_SPARSE_GRAD = 14, 15, 16, 17, 18, 19, 20
+PROF_SPARSE_ZGRAD = 21
 F64, F32 = 0, 1
 KERNEL_GAUSSIAN, KERNEL_PERIODIC, KERNEL_GAUSSIAN_ARD = 0, 1, 2
 ARD_MAX_D = 64
@@ -178,6 +179,8 @@ _SIGNATURES = {
     "gpx_sgp_set_split": (c_int, [c_void_p, c_int]),
     "gpx_sgp_grad": (c_int, [c_void_p, c_int64, c_double_p]),
     "gpx_sgp_last_grad_timing": (c_int, [c_void_p, POINTER(c_float)]),
+    "gpx_sgp_grad_z": (c_int, [c_void_p, c_int64, c_double_p, c_double_p]),
+    "gpx_sgp_last_zgrad_timing": (c_int, [c_void_p, POINTER(c_float)]),
     "gpx_debug_sgp_plan": (c_int, [c_int, c_int64, c_int64, c_int64, c_int, c_size_t, POINTER(c_int64), POINTER(c_int64),
                                    c_int_p, POINTER(c_int64)]),
     "gpx_d_sum_slices_lower": (c_int, [c_int, c_void_p, c_int64, c_int64, c_int, c_int64, c_void_p, c_int64, c_void_p]),
@@ -187,6 +190,9 @@ _SIGNATURES = {
     "gpx_d_sgp_form_B": (c_int, [c_int, c_void_p, c_int64, c_int64, c_double, c_void_p, c_int64, c_void_p, c_void_p]),
     "gpx_d_var_rows2": (c_int, [c_int, c_int, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int, c_double_p,
                                 c_void_p, c_void_p]),
+    "gpx_rect_zgrad_scratch": (c_int, [c_int, c_int64, c_int, POINTER(c_size_t)]),
+    "gpx_d_rect_zgrad": (c_int, [c_int, c_int, c_void_p, c_int64, c_void_p, c_int64, c_int, c_double_p, c_void_p, c_int64, c_void_p,
+                                 c_void_p, c_double, c_double_p, c_void_p, c_void_p, c_void_p]),
     "gpx_gp_get_Kxx": (c_int, [c_void_p, c_double_p, c_int64]),
     "gpx_gp_get_Lxx": (c_int, [c_void_p, c_double_p, c_int64]),
     "gpx_gp_get_alpha": (c_int, [c_void_p, c_double_p]),

@@ -91,7 +91,7 @@ struct EventPool {
 // ---- live per-kernel-class timing (HIP events around each launch; off by default) ----
 enum ProfClass { PC_KMAT = 0, PC_GEMM = 1, PC_POTRF_DIAG = 2, PC_TRSM_ROWS = 3, PC_TRSV = 4,
                  PC_MEAN = 5, PC_REDUCE = 6, PC_GEMM_SKINNY = 7, PC_GEMM_GENERIC = 8, PC_GEMM_PANEL = 9, PC_GEMM_N64 = 10,
-                 PC_TRANSPOSE = 11, PC_PRED_GRAD = 12, PC_EXTEND = 13, PC_RANDN = 14, PC_RFF = 15, PC_KAPPLY = 16, PC_KAPPLY_GRAD = 17, PC_CHOL_DELETE = 18, PC_SPARSE_GRAM = 19, PC_SPARSE_GRAD = 20, PC_COUNT = 21 };
+                 PC_TRANSPOSE = 11, PC_PRED_GRAD = 12, PC_EXTEND = 13, PC_RANDN = 14, PC_RFF = 15, PC_KAPPLY = 16, PC_KAPPLY_GRAD = 17, PC_CHOL_DELETE = 18, PC_SPARSE_GRAM = 19, PC_SPARSE_GRAD = 20, PC_SPARSE_ZGRAD = 21, PC_COUNT = 22 };
 extern bool g_prof_on;
 // the registry is shared by all host threads (mutex inside); a scope ends its OWN record
 int  prof_begin(int cls, double work, hipStream_t st);    // record index, -1 when nothing was recorded
@@ -328,6 +328,13 @@ int tile_reduce(int dtype, int kernel, const void *x, int64_t n, int d, const do
 int rect_reduce(int dtype, int kernel, const void *x, int64_t n, const void *z, int64_t m, int d, const double *params, const void *P,
                 int64_t ldp, const void *y, const void *w, double *partial_dev, double *out, hipStream_t st);
 const double *reduce_params(int kernel, int d, const double *params, double *iso2);
+// The rectangular pass whose result is per COLUMN point and dimension (gpx_zgrad.hip; the sparse GP's gradient in the inducing
+// inputs): gpx_d_rect_zgrad's arguments on GPX_KERNEL_GAUSSIAN / GPX_KERNEL_PERIODIC points (the ARD family: the scaled points,
+// iso and col_div = the widths).  partial_dev: rect_zgrad_partial_doubles(kernel, m, d) DEVICE doubles.  Enqueues and returns.
+size_t rect_zgrad_partial_doubles(int kernel, int64_t m, int d);
+int rect_zgrad(int dtype, int kernel, const void *r, int64_t n, const void *q, int64_t m, int d, const double *params, const void *C,
+               int64_t ldc, const void *u, const void *v, double scale, const double *col_div, double *partial_dev, double *out_dev,
+               hipStream_t st);
 void grad_from_sums(int kernel, int d, const double *params, const double *S, double quad, double noise_scale, double factor,
                     double *out);
 // The Gaussian ARD family (gpx_kmat.hip): out <- x / w (w_host: d doubles; out may be x).

@@ -13,6 +13,9 @@ template <> struct Vec<float>  { static constexpr int N = 4; typedef float4 type
 template <typename T> __device__ __forceinline__ T dev_exp(T x);
 template <> __device__ __forceinline__ double dev_exp<double>(double x) { return exp(x); }
 template <> __device__ __forceinline__ float  dev_exp<float>(float x)  { return expf(x); }
+template <typename T> __device__ __forceinline__ void dev_sincos(T x, T *s, T *c);
+template <> __device__ __forceinline__ void dev_sincos<double>(double x, double *s, double *c) { sincos(x, s, c); }
+template <> __device__ __forceinline__ void dev_sincos<float>(float x, float *s, float *c) { sincosf(x, s, c); }
 
 // one kernel-matrix entry from the accumulated squared distance (gaussian) --
 // FORM 0: c2*exp(e)   1: exp(e)*(c3*d2 - c2)   2: exp(e)*(c4*d2^2 - c3*d2 + c2)

@@ -205,7 +205,8 @@ const char *prof_class_name(int cls)
     static const char *names[PC_COUNT] = {"gpx:kernel_matrix", "gpx:gemm_trailing_update", "gpx:potrf_panel", "gpx:trsm_rows", "gpx:trsv",
                                           "gpx:mean", "gpx:reduce", "gpx:gemm_skinny", "gpx:gemm_generic", "gpx:gemm_panel", "gpx:gemm_n64",
                                           "gpx:transpose", "gpx:pred_grad", "gpx:extend", "gpx:randn", "gpx:rff_features", "gpx:kmat_apply",
-                                          "gpx:kmat_apply_grad", "gpx:chol_delete", "gpx:sparse_gram", "gpx:sparse_grad_reduce"};
+                                          "gpx:kmat_apply_grad", "gpx:chol_delete", "gpx:sparse_gram", "gpx:sparse_grad_reduce",
+                                          "gpx:sparse_zgrad"};
     return (cls >= 0 && cls < PC_COUNT) ? names[cls] : "gpx:other";
 }
 bool roctx_push(const char *name)

@@ -23,11 +23,15 @@
 //   bacc                   M doubles
 //   work (grow-only)       G (M x cols) | the partial accumulators (slices x M x ldm)
 //                          the gradient pass lays it out anew: reduction partials | three M x ldm blocks | K(x_c, z), P (c x ldm each)
+//                          and behind them, for the gradient in z: its M x d accumulator (f64) | -w | its slices' partials
 //
 // The gradient of the bound in the hyper-parameters (gpx_sgp_grad; include/gpx.h has the formulas): everything M x M from the
 // factors the fit left (Luu, LB, X in Xt, w) by the sweeps and products the library has, then a second pass over x in
 // column chunks: K(x_c, z), ONE product P = K(x_c, z) T, and the rectangular tile reduction of gpx_kmat.hip.  It writes
 // Xf, t0 and the work buffer only, so the fit's state -- elbo, the predictions, what gpx_sgp_get returns -- stays as it was.
+// The gradient in the inducing inputs (gpx_sgp_grad_z) rides on that pass: the same T, the same P and the same coefficients
+// P[j, i] + y_j w_i, contracted against dk/dz_ik by rect_zgrad (gpx_zgrad.hip) beside rect_reduce, and once more on z against
+// itself with the mirrored -A A^T / s^4 for Kuu's share.
 #include "gpx_small.h"
 #include <algorithm>
 #include <cmath>
@@ -68,6 +72,10 @@ struct gpx_sgp {
     std::vector<hipEvent_t> gcev;      // four per chunk: before the build, behind it, behind the product, behind the reduction
     float grad_ms[5];
     bool have_grad;
+    hipEvent_t zev;                    // the joint pass: behind the z-gradient's Kuu part
+    std::vector<hipEvent_t> zcev;      // one per chunk: behind the z-gradient's kernels
+    float zgrad_ms[2];
+    bool have_zgrad;
 };
 
 namespace gpx {
@@ -301,7 +309,7 @@ static int sgp_fit(gpx_sgp *g, int64_t chunk_cols)
     const size_t es = esize(dtype);
     const int64_t n = g->n, M = g->m, ldm = g->ldm;
     hipStream_t st = g->st;
-    g->fitted = false; g->have_grad = false; g->stage = 0; g->pivot = 0; g->chunks_timed = 0;
+    g->fitted = false; g->have_grad = false; g->have_zgrad = false; g->stage = 0; g->pivot = 0; g->chunks_timed = 0;
     // the plan and its buffer, before anything is enqueued
     size_t freeb = 0, totalb = 0;
     GPX_HIP(hipMemGetInfo(&freeb, &totalb));
@@ -434,24 +442,33 @@ static int product_nt(int dtype, int64_t m, int64_t n, int64_t k, const void *A,
     return gemm_nt(dtype, m, n, k, A, ld, B, ld, C, ld, alpha, GPX_FULL, 0, 0, st, beta0 ? 1 : 0);
 }
 
-static int sgp_grad_events(gpx_sgp *g, int64_t chunks)
+static int sgp_grad_events(gpx_sgp *g, int64_t chunks, bool with_z)
 {
     while ((int64_t)g->gcev.size() < 4 * chunks) {
         hipEvent_t e;
         GPX_HIP(hipEventCreate(&e));
         g->gcev.push_back(e);
     }
+    while (with_z && (int64_t)g->zcev.size() < chunks) {
+        hipEvent_t e;
+        GPX_HIP(hipEventCreate(&e));
+        g->zcev.push_back(e);
+    }
     return GPX_OK;
 }
 
-static int sgp_grad(gpx_sgp *g, int64_t chunk_cols, double *grad)
+// grad (may be null when grad_z is not): (kernel parameters..., s).  grad_z (HOST, M x d, or null): the gradient in the inducing
+// inputs from the same pass; null leaves the pass exactly the theta-only one -- the same launches, the same bits
+static int sgp_grad(gpx_sgp *g, int64_t chunk_cols, double *grad, double *grad_z)
 {
     const int dtype = g->dtype, d = g->d, nkp = g->nparams;
     const size_t es = esize(dtype);
     const int64_t n = g->n, M = g->m, ldm = g->ldm;
     hipStream_t st = g->st;
     const bool ard = g->kernel == GPX_KERNEL_GAUSSIAN_ARD;
-    g->have_grad = false;
+    g->have_grad = false; g->have_zgrad = false;
+    double grad_own[GPX_ARD_MAX_D + 2];
+    if (!grad) grad = grad_own;
     // the plan: the fit's, with two c x ldm blocks where the fit has one M x c
     size_t freeb = 0, totalb = 0;
     GPX_HIP(hipMemGetInfo(&freeb, &totalb));
@@ -469,12 +486,18 @@ static int sgp_grad(gpx_sgp *g, int64_t chunk_cols, double *grad)
     }
     const size_t part_doubles = dloglh_partial_doubles(g->kernel, d), part_bytes = (size_t)round_up((int64_t)(part_doubles + 8) * 8, 128);
     const size_t mm = (size_t)M * ldm * es, blk = (size_t)cols * ldm * es;
-    GPX_TRY(g->work.reserve(part_bytes + 3 * mm + 2 * blk, st));
+    // the gradient in z: its accumulator, -w and the slices' partials of its kernel (a function of M and d: the passes on x and on z share them)
+    const size_t zacc_bytes = grad_z ? (size_t)round_up(M * d * 8, 128) : 0, negw_bytes = grad_z ? (size_t)round_up(ldm * (int64_t)es, 128) : 0;
+    const size_t zpart_bytes = grad_z ? rect_zgrad_partial_doubles(sgp_view(g).kernel, M, d) * sizeof(double) : 0;
+    GPX_TRY(g->work.reserve(part_bytes + 3 * mm + 2 * blk + zacc_bytes + negw_bytes + zpart_bytes, st));
     double *part = (double *)g->work.p, *wb_dev = part + part_doubles;
     char *Y = (char *)g->work.p + part_bytes, *A = Y + mm, *Tm = A + mm, *G = Tm + mm, *P = G + blk;
     char *Mm = Y;                                                                    // (Y is done with when Mm is formed)
+    double *zacc = (double *)(P + blk), *zpart = (double *)(P + blk + zacc_bytes + negw_bytes);
+    char *negw = P + blk + zacc_bytes;
+    const double *col_div = ard ? g->params + 1 : nullptr;                           // (the scaled points: d/dz_ik = d/dzs_ik / w_k)
     void *X1 = g->Xf;                                                                // (work of the fit: nobody reads it afterwards)
-    GPX_TRY(sgp_grad_events(g, chunks));
+    GPX_TRY(sgp_grad_events(g, chunks, grad_z != nullptr));
     const SgpView v = sgp_view(g);
     const double s = g->s, s2 = s * s, N = (double)n;
 
@@ -502,6 +525,16 @@ static int sgp_grad(gpx_sgp *g, int64_t chunk_cols, double *grad)
     GPX_TRY(tile_reduce(dtype, g->kernel, v.z, M, d, v.params, g->w, nullptr, Mm, ldm, part, Suu, st));
     GPX_HIP(hipMemcpyAsync(&wb, wb_dev, sizeof(double), hipMemcpyDeviceToHost, st));
     GPX_HIP(hipEventRecord(g->gev[1], st));
+    if (grad_z) {
+        // Kuu's share, sum_i' 2 Gu[i, i'] dk(z_i, z_i')/dz_ik with 2 Gu = Mm - w w^T: the same kernel on z against itself, C = Mm
+        // mirrored to a full matrix, (u, v) = (-w, w).  The pair i' = i adds exactly 0: its difference is 0.
+        GPX_HIP(hipMemsetAsync(zacc, 0, (size_t)M * d * sizeof(double), st));
+        GPX_HIP(hipMemcpyAsync(negw, g->w, (size_t)M * es, hipMemcpyDeviceToDevice, st));
+        GPX_TRY(div_vec(dtype, negw, M, -1.0, st));
+        GPX_TRY(transpose(dtype, Mm, ldm, M, M, Mm, ldm, 1, st));
+        GPX_TRY(rect_zgrad(dtype, v.kernel, v.z, M, v.z, M, d, v.params, Mm, ldm, negw, g->w, 1.0, col_div, zpart, zacc, st));
+        GPX_HIP(hipEventRecord(g->zev, st));
+    }
 
     // 2. the pass over x: sum_ji (P[j, i] + y_j w_i) dk(x_j, z_i), P = K(x_c, z) T
     const int width = ard ? d + 2 : 4;
@@ -515,11 +548,19 @@ static int sgp_grad(gpx_sgp *g, int64_t chunk_cols, double *grad)
         GPX_HIP(hipEventRecord(g->gcev[4 * c + 1], st));
         GPX_TRY(product_nt(dtype, cc, M, M, G, Tm, P, ldm, 1.0, st));                 // (T is symmetric)
         GPX_HIP(hipEventRecord(g->gcev[4 * c + 2], st));
+        if (grad_z) {
+            // Gf's share on the same G, P: sum_j (P[j, i] + y_j w_i) dk(z_i, x_j)/dz_ik / s^2, ahead of the reduction, whose
+            // host sum waits for the stream
+            GPX_TRY(rect_zgrad(dtype, v.kernel, xc, cc, v.z, M, d, v.params, P, ldm, (const char *)g->y + (size_t)c0 * es, g->w, 1.0 / s2,
+                               col_div, zpart, zacc, st));
+            GPX_HIP(hipEventRecord(g->zcev[c], st));
+        }
         GPX_TRY(rect_reduce(dtype, g->kernel, xc, cc, v.z, M, d, v.params, P, ldm, (const char *)g->y + (size_t)c0 * es, g->w, part, out, st));
         GPX_HIP(hipEventRecord(g->gcev[4 * c + 3], st));
         for (int q = 0; q < width; ++q) Srect[q] += out[q];
     }
     GPX_HIP(hipEventRecord(g->gev[2], st));
+    if (grad_z) GPX_HIP(hipMemcpyAsync(grad_z, zacc, (size_t)M * d * sizeof(double), hipMemcpyDeviceToHost, st));
     GPX_HIP(hipStreamSynchronize(st));
 
     // 3. the gradient from the sums.  k(0) = k00 depends on h (and the Gaussian families' on the widths): dk(0)/dh = 2 k(0) / h,
@@ -544,12 +585,22 @@ static int sgp_grad(gpx_sgp *g, int64_t chunk_cols, double *grad)
     GPX_HIP(hipEventElapsedTime(&ms[0], g->gev[0], g->gev[1]));
     for (int64_t c = 0; c < chunks; ++c)
         for (int i = 0; i < 3; ++i) {
-            float t = 0.0f;
-            GPX_HIP(hipEventElapsedTime(&t, g->gcev[4 * c + i], g->gcev[4 * c + i + 1]));
+            float t = 0.0f;                                                          // (the reduction begins behind the z kernels)
+            GPX_HIP(hipEventElapsedTime(&t, (i == 2 && grad_z) ? g->zcev[c] : g->gcev[4 * c + i], g->gcev[4 * c + i + 1]));
             ms[1 + i] += t;
         }
     GPX_HIP(hipEventElapsedTime(&ms[4], g->gev[0], g->gev[2]));
     g->have_grad = true;
+    if (grad_z) {
+        g->zgrad_ms[0] = g->zgrad_ms[1] = 0.0f;
+        GPX_HIP(hipEventElapsedTime(&g->zgrad_ms[0], g->gev[1], g->zev));
+        for (int64_t c = 0; c < chunks; ++c) {
+            float t = 0.0f;
+            GPX_HIP(hipEventElapsedTime(&t, g->gcev[4 * c + 2], g->zcev[c]));
+            g->zgrad_ms[1] += t;
+        }
+        g->have_zgrad = true;
+    }
     return GPX_OK;
 }
 
@@ -616,6 +667,10 @@ int gpx_sgp_create(gpx_sgp_t **out, int dtype, int kernel, int64_t n, int64_t m_
         e = hipEventCreate(&g->gev[i]);
         if (e != hipSuccess) rc = hip_fail(e, "hipEventCreate", __FILE__, __LINE__);
     }
+    if (rc == GPX_OK) {
+        e = hipEventCreate(&g->zev);
+        if (e != hipSuccess) rc = hip_fail(e, "hipEventCreate", __FILE__, __LINE__);
+    }
     if (rc != GPX_OK) { gpx_sgp_destroy(g); return rc; }
     *out = g;
     return GPX_OK;
@@ -635,6 +690,8 @@ int gpx_sgp_destroy(gpx_sgp_t *g)
     for (int i = 0; i < 3; ++i) if (g->gev[i]) (void)hipEventDestroy(g->gev[i]);
     for (hipEvent_t e : g->cev) (void)hipEventDestroy(e);
     for (hipEvent_t e : g->gcev) (void)hipEventDestroy(e);
+    if (g->zev) (void)hipEventDestroy(g->zev);
+    for (hipEvent_t e : g->zcev) (void)hipEventDestroy(e);
     if (g->st) (void)hipStreamDestroy(g->st);
     delete g;
     return GPX_OK;
@@ -643,7 +700,7 @@ int gpx_sgp_destroy(gpx_sgp_t *g)
 int gpx_sgp_set_data(gpx_sgp_t *g, const double *x, const double *y, const double *z)
 {
     SGP_ENTER(g);
-    g->fitted = false; g->have_grad = false;
+    g->fitted = false; g->have_grad = false; g->have_zgrad = false;
     if (x) { GPX_TRY(upload_f64(g->dtype, g->x, g->n * g->d, x, g->n * g->d, 1, g->n * g->d, g->st)); g->have_x = true; }
     if (y) { GPX_TRY(upload_f64(g->dtype, g->y, g->n, y, g->n, 1, g->n, g->st)); g->have_y = true; }
     if (z) { GPX_TRY(upload_f64(g->dtype, g->z, g->m * g->d, z, g->m * g->d, 1, g->m * g->d, g->st)); g->have_z = true; }
@@ -816,7 +873,24 @@ int gpx_sgp_grad(gpx_sgp_t *g, int64_t chunk_cols, double *grad)
     SGP_NEED_FIT(g);
     GPX_ARG(grad, "NULL argument");
     GPX_ARG(chunk_cols >= 0 && chunk_cols % SGP_CHUNK_ALIGN == 0, "chunk_cols must be 0 (automatic) or a multiple of 128");
-    return sgp_grad(g, chunk_cols, grad);
+    return sgp_grad(g, chunk_cols, grad, nullptr);
+}
+
+int gpx_sgp_grad_z(gpx_sgp_t *g, int64_t chunk_cols, double *grad, double *grad_z)
+{
+    SGP_ENTER(g);
+    SGP_NEED_FIT(g);
+    GPX_ARG(grad_z, "NULL argument");
+    GPX_ARG(chunk_cols >= 0 && chunk_cols % SGP_CHUNK_ALIGN == 0, "chunk_cols must be 0 (automatic) or a multiple of 128");
+    return sgp_grad(g, chunk_cols, grad, grad_z);
+}
+
+int gpx_sgp_last_zgrad_timing(gpx_sgp_t *g, float *ms2)
+{
+    GPX_ARG(g != nullptr && ms2, "NULL argument");
+    GPX_ARG(g->fitted && g->have_zgrad, "no gradient in z of the current fit (gpx_sgp_grad_z)");
+    for (int i = 0; i < 2; ++i) ms2[i] = g->zgrad_ms[i];
+    return GPX_OK;
 }
 
 int gpx_sgp_last_grad_timing(gpx_sgp_t *g, float *ms5)
@@ -832,7 +906,7 @@ int gpx_sgp_set_split(gpx_sgp_t *g, int slices)
     GPX_ARG(g != nullptr, "handle is NULL");
     GPX_ARG(slices >= 0, "slices must be >= 0");
     g->split = slices;
-    g->fitted = false; g->have_grad = false;
+    g->fitted = false; g->have_grad = false; g->have_zgrad = false;
     return GPX_OK;
 }
 

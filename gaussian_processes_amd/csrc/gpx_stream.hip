@@ -345,9 +345,6 @@ int kapply_fused(int dtype, const void *xo, int64_t m, const void *x, int64_t n,
 // added by shuffles, waves through LDS, slices by pred_grad_reduce_kernel, all in a fixed order: no atomics, bitwise repeatable.
 // ---------------------------------------------------------------------------
 constexpr int PG_ACC = 16;         // f64 accumulators per lane
-template <typename T> __device__ __forceinline__ void dev_sincos(T x, T *s, T *c);
-template <> __device__ __forceinline__ void dev_sincos<double>(double x, double *s, double *c) { sincos(x, s, c); }
-template <> __device__ __forceinline__ void dev_sincos<float>(float x, float *s, float *c) { sincosf(x, s, c); }
 
 template <typename T, int KIND, int DP>
 __global__ __launch_bounds__(256) void pred_grad_kernel(const T *__restrict__ xo, int64_t m, const T *__restrict__ x, int64_t n,

@@ -13,7 +13,9 @@ include/gpx.h).  `elbo` is a LOWER BOUND on the log marginal likelihood of the d
 attribute called ``log_lh`` here, on purpose.
 
 `delbo_dtheta` is the gradient of the bound in ``(kernel parameters..., s)`` with `z` and the jitter held fixed
-(``gpx_sgp_grad``: a second pass over the chunks of `x`), `optimize` an L-BFGS-B on top of it.
+(``gpx_sgp_grad``: a second pass over the chunks of `x`), `delbo_dz` the gradient in the inducing inputs from the same pass
+(``gpx_sgp_grad_z``), `optimize` an L-BFGS-B on top of either: over the parameters, or with ``inducing=True`` over the
+parameters and `z` together.
 """
 import ctypes
 
@@ -34,7 +36,8 @@ class _SparseState(object):
     def __init__(self, dtype_id, kernel_id, n, m, d, device):
         self.key = (dtype_id, kernel_id, n, m, d, device)
         self.handle = ctypes.c_void_p()
-        self.data_version = -1
+        self.xy_version = -1
+        self.z_version = -1
         self.fit_version = -1
         self.stage = self.pivot = None
         lib = _lib.load()
@@ -93,6 +96,8 @@ class SparseGP(object):
         self._dev = None
         self._version = 0          # bumped by every invalidation
         self._data_version = 0     # bumped when x, y or z change
+        self._xy_version = 0       # ... when x or y change: everything is uploaded again
+        self._z_version = 0        # ... when z changes: only z is uploaded
         self._memoized = {}
         self._jitter = None
         self._chunk_cols = 0
@@ -104,11 +109,15 @@ class SparseGP(object):
         self.chunk_cols = chunk_cols
 
     # ---- invalidation: GP's scheme ----
-    def _invalidate(self, data=False):
+    def _invalidate(self, data=False, z=False):
         self._memoized = {}
         self._version += 1
-        if data:
+        if data or z:
             self._data_version += 1
+        if data:
+            self._xy_version += 1
+        if z:
+            self._z_version += 1
 
     @property
     def x(self):
@@ -155,7 +164,7 @@ class SparseGP(object):
             if arr.shape[0] < 1:
                 raise ValueError("need at least one inducing point (M >= 1)")
             _check_finite(arr)
-            self._invalidate(data=True)
+            self._invalidate(z=True)
             self._z = arr
             self._z.flags.writeable = False
 
@@ -260,10 +269,16 @@ class SparseGP(object):
                 self._dev.close()
             self._dev = _SparseState(*key)
         st = self._dev
-        if st.data_version != self._data_version:
+        if st.xy_version != self._xy_version:
             xs, ys, zs = (np.ascontiguousarray(a, dtype=DTYPE) for a in (self._x, self._y, self._z))
             _lib.check(_lib.load().gpx_sgp_set_data(st.handle, _lib.dptr(xs), _lib.dptr(ys), _lib.dptr(zs)))
-            st.data_version = self._data_version
+            st.xy_version, st.z_version = self._xy_version, self._z_version
+            st.fit_version = -1
+        elif st.z_version != self._z_version:
+            # only z moved (every step of a joint optimisation): x and y stay where they are on the device
+            zs = np.ascontiguousarray(self._z, dtype=DTYPE)
+            _lib.check(_lib.load().gpx_sgp_set_data(st.handle, None, None, _lib.dptr(zs)))
+            st.z_version = self._z_version
             st.fit_version = -1
         return st
 
@@ -319,6 +334,17 @@ class SparseGP(object):
             self._memoized["grad"] = out
         return self._memoized["grad"]
 
+    def _grad_z(self):
+        """One joint device call: the gradient in z, and the one in the parameters beside it (the bits `_grad` would give)."""
+        if "grad_z" not in self._memoized:
+            st = self._fit_pd()
+            out = np.empty(self.K.params.size + 1, dtype=DTYPE)
+            out_z = np.empty((self.n_inducing, self._d), dtype=DTYPE)
+            _lib.check(_lib.load().gpx_sgp_grad_z(st.handle, self._chunk_cols, _lib.dptr(out), _lib.dptr(out_z)))
+            self._memoized["grad"] = out
+            self._memoized["grad_z"] = out_z.reshape(self._z.shape)
+        return self._memoized["grad_z"]
+
     @property
     def delbo_dtheta(self):
         r"""Gradient of `elbo` in `params`, float64 ``(len(params),)`` in their order ``(kernel parameters..., s)``, with
@@ -328,11 +354,24 @@ class SparseGP(object):
         factorisation of the fit failed."""
         return self._grad().copy()
 
-    def elbo_and_grad(self):
+    @property
+    def delbo_dz(self):
+        r"""Gradient of `elbo` in the inducing inputs, float64 in the shape of `z` (``(M, d)`` or ``(M,)``), the parameters and
+        the jitter held fixed: one ``gpx_sgp_grad_z`` on the fitted handle, the pass over `x` that `delbo_dtheta` makes with
+        one more kernel per chunk -- it leaves `delbo_dtheta` behind too, in the same bits.  Raises ``LinAlgError`` when a
+        factorisation of the fit failed."""
+        return self._grad_z().copy()
+
+    def elbo_and_grad(self, inducing=False):
         r"""``(elbo, delbo_dtheta)``, the bits of the two properties; ``(-inf, array of NaN)`` when a factorisation failed
-        (it does not raise: this is what `optimize` calls at every trial point)."""
+        (it does not raise: this is what `optimize` calls at every trial point).  ``inducing=True``: ``(elbo, delbo_dtheta,
+        delbo_dz)`` from one joint device call, NaN arrays of both shapes after a failed fit."""
         if self._fit().stage != 0:
-            return self.elbo, np.full(self.K.params.size + 1, np.nan, dtype=DTYPE)
+            nan = np.full(self.K.params.size + 1, np.nan, dtype=DTYPE)
+            return (self.elbo, nan, np.full(self._z.shape, np.nan, dtype=DTYPE)) if inducing else (self.elbo, nan)
+        if inducing:
+            dz = self.delbo_dz                       # (first: the joint call serves delbo_dtheta)
+            return self.elbo, self.delbo_dtheta, dz
         return self.elbo, self.delbo_dtheta
 
     def grad_timing(self):
@@ -343,20 +382,30 @@ class SparseGP(object):
         _lib.check(_lib.load().gpx_sgp_last_grad_timing(self._fit_pd().handle, ms))
         return dict(zip(("mm", "build", "product", "reduce", "total"), list(ms)))
 
-    def optimize(self, maxiter=100, bounds=None):
+    def zgrad_timing(self):
+        """Milliseconds of the z-gradient's own kernels in the last joint pass: Kuu's share (the pass on `z` against itself),
+        the chunks' passes."""
+        self._grad_z()
+        ms = (ctypes.c_float * 2)()
+        _lib.check(_lib.load().gpx_sgp_last_zgrad_timing(self._fit_pd().handle, ms))
+        return dict(zip(("kuu", "chunks"), list(ms)))
+
+    def optimize(self, maxiter=100, bounds=None, inducing=False):
         r"""Maximise `elbo` over `params` (all positive) with scipy's L-BFGS-B in log-parameters, the inducing inputs held
         fixed; one `elbo_and_grad` call per evaluation.  A trial point whose fit fails counts as a very poor one and the
         line search backs off.  `bounds`: ``None``, or one ``(lo, hi)`` pair per parameter in the natural scale (``None``
         for an open end).  The object is left at the best parameters evaluated.  Returns a dict: ``params``, ``elbo``,
-        ``nit``, ``nfev``, ``success``, ``message``."""
+        ``nit``, ``nfev``, ``success``, ``message``.
+
+        ``inducing=True``: the inducing inputs move too -- L-BFGS-B over ``(log params, z.ravel())``, one joint device call
+        (`elbo_and_grad(inducing=True)`) per evaluation and only `z` uploaded between them.  `z` is unbounded (`bounds` is
+        still one pair per parameter), the object is left at the best ``(params, z)`` evaluated and the dict gains ``z``."""
         from scipy.optimize import minimize
 
+        if inducing:
+            return self._optimize_joint(minimize, maxiter, bounds)
         x0 = np.log(self.params)
-        if bounds is not None:
-            bounds = list(bounds)
-            if len(bounds) != x0.size:
-                raise ValueError("bounds: one (lo, hi) pair per parameter (%d), got %d" % (x0.size, len(bounds)))
-            bounds = [tuple(None if b is None else float(np.log(b)) for b in pair) for pair in bounds]
+        bounds = self._log_bounds(bounds, x0.size)
         best = {"elbo": -np.inf, "params": self.params}
         state = {"worst": None}
 
@@ -380,6 +429,47 @@ class SparseGP(object):
         msg = res.message.decode() if isinstance(res.message, bytes) else str(res.message)
         return dict(params=self.params, elbo=DTYPE(best["elbo"]), nit=int(res.nit), nfev=int(res.nfev), success=bool(res.success),
                     message=msg)
+
+    @staticmethod
+    def _log_bounds(bounds, nparams):
+        if bounds is None:
+            return None
+        bounds = list(bounds)
+        if len(bounds) != nparams:
+            raise ValueError("bounds: one (lo, hi) pair per parameter (%d), got %d" % (nparams, len(bounds)))
+        return [tuple(None if b is None else float(np.log(b)) for b in pair) for pair in bounds]
+
+    def _optimize_joint(self, minimize, maxiter, bounds):
+        """`optimize` over ``(log params, z.ravel())``."""
+        npar, zshape = self.params.size, self._z.shape
+        x0 = np.concatenate([np.log(self.params), self._z.ravel()])
+        bounds = self._log_bounds(bounds, npar)
+        if bounds is not None:
+            bounds = bounds + [(None, None)] * (x0.size - npar)
+        best = {"elbo": -np.inf, "params": self.params, "z": self._z}
+        state = {"worst": None}
+
+        def negative(u):
+            self.params = np.exp(u[:npar])
+            self.z = u[npar:].reshape(zshape)
+            val, grad, grad_z = self.elbo_and_grad(inducing=True)
+            if not (np.isfinite(val) and np.all(np.isfinite(grad)) and np.all(np.isfinite(grad_z))):
+                ref = state["worst"] if state["worst"] is not None else 0.0
+                return abs(ref) * 10.0 + 1e10, np.zeros_like(u)
+            if val > best["elbo"]:
+                best["elbo"], best["params"], best["z"] = float(val), self.params, self._z
+            state["worst"] = -val if state["worst"] is None else max(state["worst"], -val)
+            return -float(val), -np.concatenate([np.asarray(grad, dtype=DTYPE) * np.exp(u[:npar]), grad_z.ravel()])
+
+        res = minimize(negative, x0, jac=True, method="L-BFGS-B", bounds=bounds, options={"maxiter": int(maxiter)})
+        self.params = best["params"]
+        self.z = best["z"]
+        if not np.isfinite(best["elbo"]):
+            return dict(params=self.params, z=self._z, elbo=DTYPE(-np.inf), nit=int(res.nit), nfev=int(res.nfev), success=False,
+                        message="no trial point had a positive definite fit")
+        msg = res.message.decode() if isinstance(res.message, bytes) else str(res.message)
+        return dict(params=self.params, z=self._z, elbo=DTYPE(best["elbo"]), nit=int(res.nit), nfev=int(res.nfev),
+                    success=bool(res.success), message=msg)
 
     def _get(self, which):
         if which not in self._memoized:

@@ -180,6 +180,7 @@ int gpx_stream_wait_event(void *stream, void *event);
 #define GPX_PROF_CHOL_DELETE 18 /* del_copy_rows_kernel + del_block_kernel (gpx_d_chol_delete), ONE record per call around all of its launches: bytes read + written */
 #define GPX_PROF_SPARSE_GRAM 19 /* gpx_sgp_fit: the Gram product K(z, x_c) K(x_c, z) of ONE chunk, one record around all of its slice products; flops 2 c per element of the lower triangle.  (The product kernel's own launches are recorded under their classes as well.) */
 #define GPX_PROF_SPARSE_GRAD 20 /* rect_tile_kernel / tile_reduce_ard_kernel in its rectangular form (gpx_sgp_grad): the rectangular tile reduction of ONE chunk; kernel-derivative evaluations c * M */
+#define GPX_PROF_SPARSE_ZGRAD 21 /* rect_zgrad_kernel and its slice sum (gpx_sgp_grad_z, gpx_d_rect_zgrad): ONE pass of c rows against the M columns; kernel-derivative evaluations c * M per window of dimensions */
 int gpx_prof_enable(int on);    /* also clears the registry */
 int gpx_prof_read(int cls, double *launches, double *total_ms, double *total_work);
 
@@ -829,7 +830,7 @@ int gpx_sgp_get(gpx_sgp_t *h, double *Luu, double *LB, double *c, double *Phi, d
 /* milliseconds of the last fit (HIP events on the handle's stream): [0] Kuu + its factor [1] the chunks' kernel builds
  * [2] the chunks' Gram products, b and the slice sum [3] the M x M tail [4] total */
 int gpx_sgp_last_timing(gpx_sgp_t *h, float *ms5);
-/* The gradient of the bound in the hyper-parameters, z held fixed: grad (HOST, nkp + 1 doubles) = d elbo / d (kernel
+/* The gradient of the bound in the hyper-parameters, z held fixed (gpx_sgp_grad_z below: the one in z beside it): grad (HOST, nkp + 1 doubles) = d elbo / d (kernel
  * parameters..., s), in the order of gpx_sgp_fit's params.  Needs a fit of stage 0 (GPX_ERR_ARG otherwise, as the predictions).
  * With Sigma = Kuu + Phi / s^2 = Luu B Luu^T and w = Sigma^-1 b / s^2 (the mean's weights, on the device since the fit):
  *   T  = Kuu^-1 - Sigma^-1 - w w^T                         Gu = T / 2 - Kuu^-1 Phi Kuu^-1 / (2 s^2)    = d elbo / d Kuu
@@ -858,6 +859,25 @@ int gpx_sgp_grad(gpx_sgp_t *h, int64_t chunk_cols, double *grad);
  * [1] the chunks' kernel builds [2] the chunks' products K(x_c, z) T [3] the chunks' tile reductions (with the copy of their
  * partials) [4] total.  GPX_ERR_ARG before the first gradient of the current fit. */
 int gpx_sgp_last_grad_timing(gpx_sgp_t *h, float *ms5);
+/* The gradient of the bound in the inducing inputs, jointly with the one above: grad_z (HOST, M x d doubles, row i = z_i) =
+ * d elbo / d z, grad as gpx_sgp_grad's (it may be NULL here).  kff does not depend on z and the jitter is held fixed, so with Gu
+ * and Gf as above (Gf[i, j] = (P[j, i] + y_j w_i) / s^2, P = K(x, z) T):
+ *   d elbo / d z_ik = sum_i' 2 Gu[i, i'] dk(z_i, z_i')/dz_ik  +  sum_j Gf[i, j] dk(z_i, x_j)/dz_ik
+ *   gaussian families  dk(a, b)/da_k = -(a_k - b_k) / w_k^2 k(a, b)        periodic (d = 1)  -sin((a - b) / p) / (p w^2) k(a, b)
+ * (the term i' = i is zero: the kernels are stationary).  Both sums are ONE operation, gpx_d_rect_zgrad below:
+ *   over x, per chunk:  C = P, (u, v) = (y_c, w), rows x_c, columns z, scale 1 / s^2 -- beside the tile reduction of part 2, on
+ *     the same K(x_c, z) and P: one pass over x gives both gradients, at the same GPX_ROUTE_SPARSE_CHUNK hits;
+ *   over z, once:       C = -A A^T / s^4 (part 1's lower triangle, mirrored by gpx_d_mirror_lower), (u, v) = (-w, w), rows =
+ *     columns = z, scale 1:  C - w w^T = 2 Gu.
+ * The ARD family runs on the scaled points and divides column k by w_k.  The partials of the chunks add into ONE f64 M x d
+ * accumulator in chunk order on the handle's stream; no atomics: a repeated call returns the same bits, and grad is bit for
+ * bit gpx_sgp_grad's.  The work buffer grows by that accumulator, -w and the kernel's partials; the fit's state is untouched.
+ * No bounds on z are known to the library: an optimiser moves it freely. */
+int gpx_sgp_grad_z(gpx_sgp_t *h, int64_t chunk_cols, double *grad, double *grad_z);
+/* milliseconds of the z-gradient's own kernels in the last gpx_sgp_grad_z: [0] Kuu's share (the mirror and the pass on z) [1] the
+ * chunks' passes.  gpx_sgp_last_grad_timing's five stages keep their meaning ([3] begins behind these kernels, [4] includes
+ * them).  GPX_ERR_ARG before the first gpx_sgp_grad_z of the current fit. */
+int gpx_sgp_last_zgrad_timing(gpx_sgp_t *h, float *ms2);
 /* Depth slices per chunk for later fits of this handle: 0 = the plan's (the default), P >= 1 = exactly that many (1: one
  * plain product per chunk).  For measurements (tools/sparse_bench.py); results differ in the last bits between values. */
 int gpx_sgp_set_split(gpx_sgp_t *h, int slices);
@@ -887,6 +907,21 @@ int gpx_d_transpose(int dtype, const void *in, int64_t ldi, void *out, int64_t l
 int gpx_d_sgp_form_B(int dtype, const void *X, int64_t ldx, int64_t n, double s, void *B, int64_t ldb, double *trace_dev, void *stream);
 int gpx_d_var_rows2(int dtype, int kernel, const void *V, const void *W, int64_t rows, int64_t n, int64_t ldx, const void *xo, int d,
                     const double *params, double *out_dev, void *stream);
+/* gpx_d_rect_zgrad: the rectangular tile pass whose result is per column point and dimension,
+ *     out_dev[i, k] += scale * sum_j (C[j, i] + u_j v_i) dk(q_i, r_j)/dq_ik        i < m, k < d, j < n
+ *   rows r (n, d), columns q (m, d), C (n x ldc), u (n), v (m) in `dtype`; out_dev (m, d) DOUBLE, ADDED to; kernel
+ *   GPX_KERNEL_GAUSSIAN (any d the tile's LDS holds) or GPX_KERNEL_PERIODIC (d = 1), params the family's.  The ARD family: the
+ *   points scaled by gpx_d_scale_points, params = (h / sqrt(wbar), 1) and col_div (HOST, d doubles) = the widths -- column k
+ *   is divided by col_div[k]; NULL otherwise.  64 x 64 tiles; a workgroup keeps one column tile, walks a slice of the row
+ *   tiles and a window of dimensions (4, 16 or 32 wide; beyond d = 32 further windows evaluate k again); k is formed in `dtype` as
+ *   gpx_d_kmat forms it (a clamped pair adds exactly 0), the coefficient, the products and the sums in f64, the difference
+ *   r_jk - q_ik directly.  One partial per (slice, i, k) into partial_dev -- gpx_rect_zgrad_scratch doubles, a function of
+ *   (kernel, m, d) -- and a second kernel adds the slices in slice order.  No atomics; enqueues and returns.
+ * gpx_rect_zgrad_scratch: host arithmetic, the DOUBLES partial_dev must hold. */
+int gpx_rect_zgrad_scratch(int kernel, int64_t m, int d, size_t *doubles);
+int gpx_d_rect_zgrad(int dtype, int kernel, const void *r, int64_t n, const void *q, int64_t m, int d, const double *params,
+                     const void *C, int64_t ldc, const void *u, const void *v, double scale, const double *col_div,
+                     double *partial_dev, double *out_dev, void *stream);
 
 /* ------------------------------------------------------------- multi-GPU -- */
 /* One GP spread over the GPUs of a node, one PROCESS per GPU (north-star; SURVEY 8e -- the reference has

@@ -13,7 +13,10 @@ bound: gpx_sgp_last_grad_timing medians of `repeats` passes on the fit that is t
 tile reductions, total), its ratio to the fit, the shares of the product and of the reduction, the product's TF/s
 (2 M^2 N flops), the reduction's rate under gpx_prof (GPX_PROF_SPARSE_GRAD: kernel-derivative evaluations), one
 `elbo_and_grad()` from new parameters by a host clock (what one optimize step costs) beside 2 (P + 1) fits (what central
-differences would).  Prediction (mean and var at `--predict` points) is timed by a host clock around
+differences would).  Beside it the JOINT pass (gpx_sgp_grad_z: the gradient in the inducing inputs from the same pass): the same
+five stages with the z kernels' own two (gpx_sgp_last_zgrad_timing: Kuu's share, the chunks'), its ratio to the theta-only pass,
+the z kernels' rate under gpx_prof (GPX_PROF_SPARSE_ZGRAD: kernel-derivative evaluations, c M per window of dimensions) beside
+the reduction's on the same chunks, and one `elbo_and_grad(inducing=True)` after z moved (only z is uploaded).  Prediction (mean and var at `--predict` points) is timed by a host clock around
 the synchronous calls, once per M.  Every GPU step runs under a watchdog of its own (--step-timeout seconds): a step that
 overruns it ends the process with exit status 124, so nothing further is started on the device.
 """
@@ -77,6 +80,14 @@ def _regrad(sg):
     sg._memoized.pop("grad", None)
     grad = sg.delbo_dtheta
     return grad, sg.grad_timing()
+
+
+def _rejoint(sg):
+    """The joint pass alone, on the fit that is there: (grad_z, the five stages, the z kernels' two)."""
+    sg._memoized.pop("grad", None)
+    sg._memoized.pop("grad_z", None)
+    grad_z = sg.delbo_dz
+    return grad_z, sg.grad_timing(), sg.zgrad_timing()
 
 
 def main():
@@ -152,6 +163,32 @@ def main():
                             "grad_product_tflops": 2.0 * M * M * a.n / gmed["product"] / 1e9 if gmed["product"] > 0 else None,
                             "grad_reduce_ms_prof": red_ms, "grad_reduce_gevals_per_s": red_evals / red_ms / 1e6 if red_ms > 0 else None,
                             "optimize_step_ms_host": step_ms, "finite_difference_step_ms": 2 * nparams * fit_total})   # nparams = P + 1: s is one
+                with Step("M = %d: warm-up joint gradient" % M, a.step_timeout):
+                    _rejoint(sg)
+                jruns = []
+                with Step("M = %d: %d joint gradients" % (M, a.repeats), a.step_timeout):
+                    for _ in range(a.repeats):
+                        jruns.append(_rejoint(sg)[1:])
+                with Step("M = %d: one joint gradient under gpx_prof" % M, a.step_timeout):
+                    _lib.check(lib.gpx_prof_enable(1))
+                    grad_z = _rejoint(sg)[0]
+                    _, jred_ms, jred_evals = _prof(_lib.PROF_SPARSE_GRAD)
+                    zl, z_ms, z_evals = _prof(_lib.PROF_SPARSE_ZGRAD)
+                    _lib.check(lib.gpx_prof_enable(0))
+                with Step("M = %d: one joint elbo_and_grad after z moved (host clock)" % M, a.step_timeout):
+                    t0 = time.perf_counter()
+                    sg.z = np.array(sg.z) + 1e-3
+                    sg.elbo_and_grad(inducing=True)
+                    jstep_ms = 1e3 * (time.perf_counter() - t0)
+                    sg.z = z
+                jmed = {k: statistics.median(r[0][k] for r in jruns) for k in GRAD_STAGES}
+                zmed = {k: statistics.median(r[1][k] for r in jruns) for k in ("kuu", "chunks")}
+                rec.update({"joint_ms_median": jmed, "joint_zgrad_ms_median": zmed, "joint_ms_total_all": [r[0]["total"] for r in jruns],
+                            "joint_over_theta": jmed["total"] / gmed["total"] if gmed["total"] > 0 else None,
+                            "grad_z_absmax": float(np.abs(grad_z).max()), "zgrad_launches_prof": zl, "zgrad_ms_prof": z_ms,
+                            "zgrad_gevals_per_s": z_evals / z_ms / 1e6 if z_ms > 0 else None,
+                            "joint_reduce_gevals_per_s": jred_evals / jred_ms / 1e6 if jred_ms > 0 else None,
+                            "joint_optimize_step_ms_host": jstep_ms})
             if split == 0 and a.predict > 0:
                 with Step("M = %d: predict at %d points" % (M, a.predict), a.step_timeout):
                     sg.predict(Xo[:1024])                                    # warm-up
