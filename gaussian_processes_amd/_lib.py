@@ -93,6 +93,10 @@ _SIGNATURES = {
                                   c_int64, c_int64, c_int64, c_void_p]),
     "gpx_debug_syrk_bc": (c_int, [c_int, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64,
                                   c_int64, c_int64, c_int, c_int, c_void_p, c_int, c_int64, c_int64, c_void_p]),
+    "gpx_debug_potrf_panel": (c_int, [c_int, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int,
+                                      c_int, c_int64, c_void_p]),
+    "gpx_debug_potrf": (c_int, [c_int, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int, c_int64, c_void_p]),
+    "gpx_debug_panel_last": (c_int, [c_int_p, c_int_p, c_int_p, c_int_p]),
     "gpx_d_tril": (c_int, [c_int, c_void_p, c_int64, c_int64, c_void_p]),
     "gpx_d_trsv_lower": (c_int, [c_int, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int,
                                  c_void_p]),

@@ -571,6 +571,9 @@ struct ResScratch {
     GrowBuf mem; int nbatch = 0; int serial = 0;
     hipEvent_t ev = nullptr;        // after the last launch that was NOT on the look-ahead stream / recorded on demand on it
     hipStream_t last = nullptr; bool have_last = false, last_on_side = false;
+    // the last launch's instantiation (gpx_debug_panel_last): LV, LEAF_MFMA of the kernel that held the leaves, one launch or two,
+    // dynamic LDS; lv < 0: none yet
+    int last_lv = -1, last_leaf_mfma = 0, last_two_part = 0, last_pad_lds = 0;
 };
 static thread_local PerDevice<ResScratch> g_res_dev;
 #define RES_TRACE(...) do { if (tune().trace) { fprintf(stderr, "[gpx] " __VA_ARGS__); fputc('\n', stderr); fflush(stderr); } } while (0)
@@ -752,21 +755,29 @@ static int panel_res_t(T *A, int64_t lda, int64_t n, int64_t r0, int64_t c0, int
     const double res_rows = (double)rows;
     std::optional<ProfScope> prof;
     prof.emplace(PC_POTRF_DIAG, (kd * kd * kd / 3.0 + (res_rows - (double)kb) * kd * kd + 2.0 * res_rows * kd * (double)kpre) * nbatch, st);
+    // (which instantiation holds the leaves is also recorded on the host: the route counters cannot tell them apart)
+    auto ran = [&](int lv, bool leaf_mfma, bool two) {
+        scr->last_lv = lv; scr->last_leaf_mfma = leaf_mfma; scr->last_two_part = two; scr->last_pad_lds = lv == 4 ? (int)pad_lds : 0;
+    };
     if (two_part && (int64_t)grid.x > nsteps) {
         const bool mfma_chain = F64 || tune().leaf_mfma_f32_rows > 0;
         const dim3 gdiag((unsigned)nsteps, grid.y), grows(grid.x - (unsigned)nsteps, grid.y);
-        if (v4) GPX_PANEL_LAUNCH_LDS((panel_res_kernel<T, true, 4>), gdiag, 0, pad_lds);
-        else if (v5 && mfma_chain) GPX_PANEL_LAUNCH((panel_res_kernel<T, true, 5>), gdiag, 0);
-        else if (mfma_chain) GPX_PANEL_LAUNCH((panel_res_kernel<T, true>), gdiag, 0);
-        else GPX_PANEL_LAUNCH((panel_res_kernel<T, F64>), gdiag, 0);
+        if (v4) { ran(4, true, true); GPX_PANEL_LAUNCH_LDS((panel_res_kernel<T, true, 4>), gdiag, 0, pad_lds); }
+        else if (v5 && mfma_chain) { ran(5, true, true); GPX_PANEL_LAUNCH((panel_res_kernel<T, true, 5>), gdiag, 0); }
+        else if (mfma_chain) { ran(1, true, true); GPX_PANEL_LAUNCH((panel_res_kernel<T, true>), gdiag, 0); }
+        else { ran(1, F64, true); GPX_PANEL_LAUNCH((panel_res_kernel<T, F64>), gdiag, 0); }
         GPX_PANEL_LAUNCH((panel_res_kernel<T, F64>), grows, nsteps);          // (the rows never run a leaf: the lean instantiation)
     } else if (v4) {
+        ran(4, true, false);
         GPX_PANEL_LAUNCH_LDS((panel_res_kernel<T, true, 4>), grid, 0, pad_lds);
     } else if (v5 && mfma_single) {
+        ran(5, true, false);
         GPX_PANEL_LAUNCH((panel_res_kernel<T, true, 5>), grid, 0);
     } else if (mfma_single) {
+        ran(1, true, false);
         GPX_PANEL_LAUNCH((panel_res_kernel<T, true>), grid, 0);
     } else {
+        ran(1, F64, false);
         GPX_PANEL_LAUNCH((panel_res_kernel<T, F64>), grid, 0);
     }
 #undef GPX_PANEL_LAUNCH
@@ -905,6 +916,23 @@ extern "C" int gpx_debug_leaf_selfcheck(int run_now, int *state)
     GPX_HIP(hipGetDevice(&dev));
     std::lock_guard<std::mutex> lk(gpx::g_leaf_mu);
     *state = (dev >= 0 && dev < gpx::MAX_DEVICES) ? gpx::g_leaf_state[dev] : 0;
+    return GPX_OK;
+}
+
+// the instantiation of the calling thread's last resident panel launch on the current device (written on the host next to the
+// launch, panel_res_t): *lv, *leaf_mfma: the template arguments LV and LEAF_MFMA of the kernel that held the diagonal blocks'
+// leaves (LEAF_MFMA = 0: the lean kernel with the VALU leaf); *two_part: the rows below went out as a second launch;
+// *pad_lds_bytes: the dynamic LDS of an exclusive-CU launch.  GPX_ERR_ARG when the thread has launched none yet.
+extern "C" int gpx_debug_panel_last(int *lv, int *leaf_mfma, int *two_part, int *pad_lds_bytes)
+{
+    GPX_TRY(gpx::ensure_device());
+    gpx::ResScratch *scr = nullptr;
+    GPX_TRY(gpx::g_res_dev.current(&scr));
+    GPX_ARG(scr->last_lv >= 0, "no resident panel launch on this thread and device yet");
+    if (lv) *lv = scr->last_lv;
+    if (leaf_mfma) *leaf_mfma = scr->last_leaf_mfma;
+    if (two_part) *two_part = scr->last_two_part;
+    if (pad_lds_bytes) *pad_lds_bytes = scr->last_pad_lds;
     return GPX_OK;
 }
 

@@ -545,3 +545,45 @@ extern "C" int gpx_d_potrf_panel(int dtype, void *A, int64_t lda, int64_t n, int
     GPX_ARG(lda % 16 == 0 && ((uintptr_t)A) % 16 == 0 && c0 % 16 == 0, "A / lda / c0 must be 16-element aligned");
     return potrf_panel(dtype, A, lda, n, r0, c0, kb, info_dev, S(stream));
 }
+
+// The two internal entries with the arguments the public ones hide (tests/test_gpu_potrf.py): host code only
+extern "C" int gpx_debug_potrf_panel(int dtype, void *A, int64_t lda, int64_t n, int64_t r0, int64_t c0, int64_t kb,
+                                     int *info_dev, int64_t kpre, int idle_chip, int count, int64_t sA, void *stream)
+{
+    gpx::StreamTurn turn__((hipStream_t)stream);     // (this thread's scratch buffers: one stream at a time, gpx_mem.h)
+    GPX_TRY(ensure_device());
+    GPX_ARG(dtype == GPX_F64 || dtype == GPX_F32, "dtype must be GPX_F64 or GPX_F32");
+    GPX_ARG(n >= 0 && r0 >= 0 && c0 >= 0 && kb >= 0 && r0 + kb <= n, "bad dimensions");
+    GPX_ARG(info_dev, "info_dev is NULL");
+    GPX_ARG(idle_chip == 0 || idle_chip == 1, "idle_chip must be 0 or 1");
+    GPX_ARG(count >= 1 && count <= 65535, "batch count must lie in [1, 65535]");
+    if (kb == 0) return GPX_OK;
+    GPX_ARG(A, "A is NULL");
+    GPX_ARG(lda % 16 == 0 && ((uintptr_t)A) % 16 == 0 && c0 % 16 == 0, "A / lda / c0 must be 16-element aligned");
+    GPX_ARG(count == 1 || (sA % 16 == 0 && sA >= n * lda), "batch members must be whole matrices apart, 16-element aligned");
+    // what the factorisation itself ever folds into a panel launch (panel_res_fold): whole 64-column blocks that exist to the
+    // left of the panel, GPX_POTRF_FOLD_K of them at most
+    GPX_ARG(kpre >= 0 && kpre % IB == 0 && kpre <= c0 && kpre <= tune().fold_k, "kpre must be whole blocks left of the panel, at most GPX_POTRF_FOLD_K columns");
+    Batch bt; bt.count = count; bt.sA = bt.sB = bt.sC = sA;
+    PanelHints hints; hints.idle_chip = idle_chip != 0;
+    return potrf_panel(dtype, A, lda, n, r0, c0, kb, info_dev, S(stream), count > 1 ? &bt : nullptr, kpre, nullptr, hints);
+}
+
+extern "C" int gpx_debug_potrf(int dtype, void *A, int64_t n, int64_t lda, int *info_dev, int64_t xrows, int count, int64_t sA,
+                               void *stream)
+{
+    gpx::StreamTurn turn__((hipStream_t)stream);     // (this thread's scratch buffers: one stream at a time, gpx_mem.h)
+    GPX_TRY(ensure_device());
+    GPX_ARG(dtype == GPX_F64 || dtype == GPX_F32, "dtype must be GPX_F64 or GPX_F32");
+    GPX_ARG(n >= 0 && xrows >= 0, "n < 0 or xrows < 0");
+    GPX_ARG(info_dev, "info_dev is NULL");
+    GPX_ARG(count >= 1 && count <= 65535, "batch count must lie in [1, 65535]");
+    if (n == 0) { GPX_HIP(hipMemsetAsync(info_dev, 0, sizeof(int) * count, S(stream))); return GPX_OK; }
+    GPX_ARG(A, "A is NULL");
+    GPX_ARG(lda >= n, "lda < n");
+    GPX_ARG(lda % 16 == 0, "lda must be a multiple of 16 elements");
+    GPX_ARG(((uintptr_t)A) % 16 == 0, "A must be 16-byte aligned");
+    GPX_ARG(count == 1 || (sA % 16 == 0 && sA >= (n + xrows) * lda), "batch members must be whole matrices apart, 16-element aligned");
+    Batch bt; bt.count = count; bt.sA = bt.sB = bt.sC = sA;
+    return potrf(dtype, A, n, lda, info_dev, S(stream), count > 1 ? &bt : nullptr, xrows, /*may_block=*/false, nullptr);
+}

@@ -335,6 +335,27 @@ int gpx_debug_syrk_bc(int dtype, int64_t n, int64_t row_begin, void *Cloc, int64
                       const void *Pb, int64_t ldp, int64_t k0, int64_t kb, int64_t nb, int P, int rank,
                       const int *abort_flag_dev, int count, int64_t sP, int64_t sC, void *stream);
 
+/* The panel and the factorisation with the arguments the public entries hide, for tests (tests/test_gpu_potrf.py); host code
+ * only, the argument checks of gpx_d_potrf_panel / gpx_d_potrf apply.
+ * gpx_debug_potrf_panel: kpre: that many columns immediately to the left of the panel (rows [r0, n), whole 64-column blocks,
+ * <= c0 and <= GPX_POTRF_FOLD_K) hold finished columns of L that the launch applies to the panel first; only a panel the
+ * resident kernel takes in one launch can do that, any other kb with kpre != 0 is GPX_ERR_ARG.  idle_chip: the hint the
+ * factorisation gives a panel launched ahead of the update it runs beside (single matrices of up to GPX_PANEL_EXCL_ROWS rows:
+ * a CU of its own per workgroup).  count matrices sA elements apart (sA >= n lda, a multiple of 16) are factored in lock-step,
+ * info_dev then holds one word per matrix.
+ * gpx_debug_potrf: xrows further rows below the n x n matrix ride along: on return row n + i holds L^-1 applied to what was
+ * stored there; count and sA (>= (n + xrows) lda) as above; a pure enqueue, no progress hook.
+ * gpx_debug_panel_last: which instantiation of the resident panel kernel the calling thread's last launch on the current
+ * device was (recorded on the host next to the launch): *lv, *leaf_mfma: the kernel's LV and LEAF_MFMA (csrc/gpx_panel.hip;
+ * LEAF_MFMA = 0: the lean kernel with the VALU leaf) of the launch that held the diagonal blocks; *two_part: the rows below
+ * them went out as a second launch; *pad_lds_bytes: dynamic LDS of an exclusive-CU launch, else 0.  Any pointer may be NULL;
+ * GPX_ERR_ARG before the thread's first launch. */
+int gpx_debug_potrf_panel(int dtype, void *A, int64_t lda, int64_t n, int64_t r0, int64_t c0, int64_t kb,
+                          int *info_dev, int64_t kpre, int idle_chip, int count, int64_t sA, void *stream);
+int gpx_debug_potrf(int dtype, void *A, int64_t n, int64_t lda, int *info_dev, int64_t xrows, int count, int64_t sA,
+                    void *stream);
+int gpx_debug_panel_last(int *lv, int *leaf_mfma, int *two_part, int *pad_lds_bytes);
+
 /* Zero the strict upper triangle (scipy's cholesky returns a clean L). */
 int gpx_d_tril(int dtype, void *A, int64_t n, int64_t lda, void *stream);
 

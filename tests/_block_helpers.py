@@ -1,7 +1,9 @@
 """Helpers shared by the direct tests of device code (tests/test_gpu_blocks.py, tests/test_gpu_gemm.py): the dtype table, the
 two NaN payloads regions are padded with, bitwise comparison, and the derived error bound.  tests/test_gpu_blocks.py's
-docstring has the conventions and the derivation of the bound."""
+docstring has the conventions and the derivation of the bound.  For tests/test_gpu_potrf.py also the matrices with a known
+well-conditioned Cholesky factor and the componentwise backward-error check."""
 import ctypes
+import functools
 
 import numpy as np
 
@@ -74,3 +76,106 @@ class Worst(object):
 
     def report(self):
         print("%s %s: worst |got - ref| / (4 x derived bound) = %.3g  (%s)" % (self.block, self.dtype, self.ratio, self.where))
+
+
+# ---- Cholesky: matrices with a known well-conditioned factor, and the componentwise backward error ------------------------
+# (tests/test_gpu_potrf.py and its premise on the CPU, tests/test_potrf_premise_cpu.py)
+CHOL_GRID = 2.0 ** -19
+
+
+@functools.lru_cache(maxsize=None)
+def chol_l0(n, seed):
+    """L0: lower triangular, diagonal uniform in [1, 2], below it randn / sqrt(n), every entry rounded to a multiple of 2^-19.
+    The grid makes L0 L0^T EXACT in float64 in any summation order: every product is a multiple of 2^-38 and every partial sum
+    is below sum |a||b| <= |row_i| |row_j| < 2^15 (asserted), 53 bits at most -- so the BLAS product below IS the np.longdouble
+    product, bit for bit (test_potrf_premise_cpu.py checks that), at a thousandth of its cost at n = 2341."""
+    rng = np.random.RandomState(seed)
+    l0 = np.tril(rng.randn(n, n) / np.sqrt(n), -1)
+    l0[np.arange(n), np.arange(n)] = rng.uniform(1.0, 2.0, n)
+    l0 = np.round(l0 / CHOL_GRID) * CHOL_GRID
+    assert (np.abs(l0) ** 2).sum(1).max() < 2.0 ** 15
+    l0.setflags(write=False)
+    return l0
+
+
+@functools.lru_cache(maxsize=None)
+def chol_spd(n, seed, cols=None):
+    """A[:, :cols] = L0 L0^T exactly (float64 holds it), read-only; cond(A) is 20 - 30 and every 64-block of its factor is well
+    conditioned."""
+    l0 = chol_l0(n, seed)
+    cols = n if cols is None else cols
+    a = l0[:, :cols] @ l0[:cols, :cols].T
+    a.setflags(write=False)
+    return a
+
+
+@functools.lru_cache(maxsize=None)
+def chol_panel_input(n, seed, r0, cols, kpre=0):
+    """What a panel at row r0 of A = chol_spd(n, seed) finds: (S, pre), np.longdouble and float64, read-only.  S: rows r0 .. n
+    x `cols` columns from r0 on of the Schur complement of the leading r0 - kpre columns, taken in np.longdouble from the float64
+    LAPACK factor of A; pre: the kpre columns of that factor before r0, rows r0 .. n (the folded pre-update's operand)."""
+    import scipy.linalg
+    a = chol_spd(n, seed, r0 + cols)
+    s = a[r0:, r0:r0 + cols].astype(LD)
+    pre = np.zeros((n - r0, 0))
+    if r0 > 0:
+        l11 = scipy.linalg.cholesky(a[:r0, :r0], lower=True)
+        l21 = scipy.linalg.solve_triangular(l11, a[r0:, :r0].T, lower=True).T
+        done = l21[:, :r0 - kpre].astype(LD)
+        s = s - done @ done[:cols].T
+        pre = np.ascontiguousarray(l21[:, r0 - kpre:])
+    else:
+        assert kpre == 0
+    s.setflags(write=False)
+    pre.setflags(write=False)
+    return s, pre
+
+
+class WorstResidual(Worst):
+    """The worst |A - L L^T|_ij / (16 K_ij eps_T (|L||L|^T)_ij) of a route, printed at the end of its test."""
+
+    def factor(self, a_in, l_out, u, what, pre=None, exact=True):
+        """a_in: rows x kb as uploaded (dtype T; only row >= column is looked at), l_out: the same region afterwards, pre: rows x
+        kpre columns of L that the call applied first (as uploaded).  Every entry with column <= row must satisfy
+            |a_in - pre pre_d^T - L L_d^T|_ij <= 16 K_ij u (|pre||pre_d|^T + |L||L_d|^T)_ij,   K_ij = min(i, j) + 1 + kpre
+        (_d: the first kb rows; L = l_out with its strict upper part taken as zero).  exact: the residual in np.longdouble;
+        otherwise in float64 BLAS, and that product's own bound gamma_{K+1}(2^-53) (|L||L|^T) is added to the tolerance."""
+        rows, kb = a_in.shape
+        i, j = np.arange(rows)[:, None], np.arange(kb)[None, :]
+        low = j <= i
+        lo = np.where(low, np.asarray(l_out, dtype=np.float64), 0.0)
+        assert np.isfinite(lo).all(), "%s: the factor is not finite (something NaN was read)" % what
+        f = lo if pre is None or pre.shape[1] == 0 else np.hstack([np.asarray(pre, dtype=np.float64), lo])
+        kpre = f.shape[1] - kb
+        k = np.minimum(i, j) + 1 + kpre
+        sum_abs = (np.abs(f) @ np.abs(f[:kb]).T).astype(LD)
+        tol = 16 * k * LD(u) * sum_abs
+        if exact:
+            prod = f.astype(LD) @ f[:kb].astype(LD).T
+        else:
+            prod = (f @ f[:kb].T).astype(LD)
+            tol = tol + (k + 1) * LD(U) / (1 - (k + 1) * LD(U)) * sum_abs
+        err = np.abs(np.where(low, np.asarray(a_in).astype(LD), 0) - prod)
+        self.ratios(err[low], tol[low], what)
+
+    def ride(self, y_in, z_out, l_out, u, what):
+        """rows that rode along: |z L^T - y| <= 16 n u |z||L^T| for every row (y_in as uploaded, z_out afterwards, n columns)."""
+        n = l_out.shape[0]
+        lo = np.tril(np.asarray(l_out, dtype=np.float64)).astype(LD)
+        z = np.asarray(z_out, dtype=np.float64)
+        assert np.isfinite(z).all(), "%s: a ride-along row is not finite" % what
+        err = np.abs(z.astype(LD) @ lo.T - np.asarray(y_in).astype(LD))
+        tol = 16 * n * LD(u) * (np.abs(z).astype(LD) @ np.abs(lo).T)
+        self.ratios(err, tol, what)
+
+    def ratios(self, err, tol, what):
+        with np.errstate(divide="ignore", invalid="ignore"):
+            ratio = np.where(tol > 0, err / tol, np.where(err > 0, np.inf, 0.0))
+        r = float(np.max(ratio)) if ratio.size else 0.0
+        print("    %s: residual / bound = %.3g" % (what, r))
+        if r > self.ratio:
+            self.ratio, self.where = r, what
+        assert r <= 1.0, "%s: residual / asserted bound = %.3g" % (what, r)
+
+    def report(self):
+        print("%s %s: worst residual / (16 K eps (|L||L|^T)) = %.3g  (%s)" % (self.block, self.dtype, self.ratio, self.where))
