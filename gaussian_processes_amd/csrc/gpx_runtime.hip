@@ -160,6 +160,12 @@ void prof_end(int rec, hipStream_t st)
     if (b) (void)hipEventRecord(b, st);
 }
 
+void prof_set_work(int rec, double work)
+{
+    std::lock_guard<std::mutex> lk(g_prof_mu);
+    if (rec >= 0 && (size_t)rec < g_prof.size()) g_prof[rec].work = work;
+}
+
 static void prof_clear()
 {
     std::lock_guard<std::mutex> lk(g_prof_mu);
@@ -206,7 +212,7 @@ const char *prof_class_name(int cls)
                                           "gpx:mean", "gpx:reduce", "gpx:gemm_skinny", "gpx:gemm_generic", "gpx:gemm_panel", "gpx:gemm_n64",
                                           "gpx:transpose", "gpx:pred_grad", "gpx:extend", "gpx:randn", "gpx:rff_features", "gpx:kmat_apply",
                                           "gpx:kmat_apply_grad", "gpx:chol_delete", "gpx:sparse_gram", "gpx:sparse_grad_reduce",
-                                          "gpx:sparse_zgrad"};
+                                          "gpx:sparse_zgrad", "gpx:select"};
     return (cls >= 0 && cls < PC_COUNT) ? names[cls] : "gpx:other";
 }
 bool roctx_push(const char *name)

@@ -15,7 +15,8 @@ attribute called ``log_lh`` here, on purpose.
 `delbo_dtheta` is the gradient of the bound in ``(kernel parameters..., s)`` with `z` and the jitter held fixed
 (``gpx_sgp_grad``: a second pass over the chunks of `x`), `delbo_dz` the gradient in the inducing inputs from the same pass
 (``gpx_sgp_grad_z``), `optimize` an L-BFGS-B on top of either: over the parameters, or with ``inducing=True`` over the
-parameters and `z` together.
+parameters and `z` together.  `SparseGP.greedy_inducing` chooses the `z` to start from: greedy conditional-variance selection
+among the rows of `x` (``gpx_sgp_select``), which depends on the kernel and `x` alone.
 """
 import ctypes
 
@@ -80,7 +81,7 @@ class SparseGP(object):
     K : one of the built-in kernels (`GaussianKernel`, `PeriodicKernel`, `GaussianARDKernel`)
     x : ``(n,)`` or ``(n, d)`` input locations;  y : ``(n,)`` observations
     s : standard deviation of the observation noise, ``> 0`` (the bound divides by :math:`s^2`)
-    z : ``(M,)`` or ``(M, d)`` inducing inputs, ``M >= 1`` (`subset_inducing` picks rows of `x`)
+    z : ``(M,)`` or ``(M, d)`` inducing inputs, ``M >= 1`` (`greedy_inducing` selects rows of `x`, `subset_inducing` draws them)
     jitter : added to the diagonal of ``K(z, z)``; ``None`` is ``sqrt(eps_dtype) * k(0)``
     chunk_cols : columns of `x` per device chunk of the fit, 0 (automatic) or a multiple of 128
     """
@@ -257,6 +258,70 @@ class SparseGP(object):
         if M < 1 or M > x.shape[0]:
             raise ValueError("invalid value for M: %d (1 .. %d)" % (M, x.shape[0]))
         return np.array(x[np.random.RandomState(seed).permutation(x.shape[0])[:M]], dtype=DTYPE)
+
+    @staticmethod
+    def greedy_inducing(K, x, M, tol=None, first=None, dtype="float64", device=None, return_info=False, factor=False):
+        r"""Up to `M` rows of `x` chosen by greedy conditional-variance selection (Burt, Rasmussen and van der Wilk 2020; a
+        pivoted partial Cholesky of ``K(x, x)``, on the device: ``gpx_sgp_select``).  Every step takes the point whose prior
+        variance GIVEN the points already taken is largest (on a tie the smallest index; step 0 takes row `first` when it
+        is given).  The choice depends on the kernel and `x` alone -- not on `y` or `s` -- and is deterministic.
+
+        Returns ``x[index]`` as float64, ``(count, d)`` or ``(count,)`` for 1-D `x`: exact copies of rows of `x`, in the
+        order picked.  The selection stops early once no remaining point has a conditional variance above `tol`, so
+        ``count < M`` is NOT an error: the rest of `x` cannot be told apart from the set already picked.  ``tol=None`` is
+        ``sqrt(eps_dtype) * k(0)``, the automatic jitter of the constructor: below it a point is indistinguishable from
+        the set once the jitter is on ``K(z, z)``.
+
+        ``return_info=True``: ``(z, info)`` with ``index`` (int64), ``pivot`` (the conditional variance of each pick when
+        it was taken), ``trace`` (``count + 1`` values: ``trace[m]`` is :math:`\sum_i k(x_i, x_i) - \mathrm{tr} X` of the
+        bound at the first ``m`` picks and jitter 0 -- read it to choose `M`), ``count`` and ``tol``; ``factor=True`` adds
+        ``R`` ``(count, n)``, the partial Cholesky factor: ``R.T @ R`` reproduces the picked columns of ``K(x, x)``."""
+        if getattr(K, "_native_kernel", None) is None:
+            raise NotImplementedError("SparseGP needs a built-in kernel (GaussianKernel, PeriodicKernel, GaussianARDKernel): "
+                                      "plugin kernels are not supported")
+        x = np.asarray(x)
+        if x.ndim not in (1, 2) or x.shape[0] < 1:
+            raise ValueError("invalid shape for x: %s" % str(x.shape))
+        xs = np.ascontiguousarray(x, dtype=DTYPE)
+        _check_finite(xs)
+        n, d = xs.shape[0], (1 if xs.ndim == 1 else xs.shape[1])
+        M = int(M)
+        if M < 1 or M > n:
+            raise ValueError("invalid value for M: %d (1 .. %d)" % (M, n))
+        kid = K._native_kernel
+        if kid == _lib.KERNEL_GAUSSIAN_ARD and d != K.d:
+            raise ValueError("x has %d dimension(s), the kernel has %d width(s)" % (d, K.d))
+        dtype_id = _DTYPES[dtype]
+        if tol is not None:
+            tol = float(tol)
+            if not (tol >= 0.0) or not np.isfinite(tol):
+                raise ValueError("invalid value for tol: %s (None, or a finite number >= 0)" % tol)
+        if first is not None:
+            if int(first) != first or not 0 <= int(first) < n:
+                raise ValueError("invalid value for first: %s (None, or a row index 0 .. %d)" % (first, n - 1))
+            first = int(first)
+        if tol is None:
+            eps = np.finfo(np.float64 if dtype_id == _lib.F64 else np.float32).eps
+            tol = float(np.sqrt(eps) * np.max(K.diag(xs[:1])))
+        lib = _lib.load()
+        if device is not None:
+            _lib.check(lib.gpx_set_device(int(device)))
+        p = np.ascontiguousarray(K.params, dtype=DTYPE)
+        index, pivot, trace = np.empty(M, dtype=np.int64), np.empty(M, dtype=DTYPE), np.empty(M + 1, dtype=DTYPE)
+        R = np.empty((M, n), dtype=DTYPE) if factor else None
+        count = ctypes.c_int64(0)
+        _lib.check(lib.gpx_sgp_select(dtype_id, kid, _lib.dptr(xs), n, d, _lib.dptr(p), M, tol, -1 if first is None else first,
+                                      index.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), _lib.dptr(pivot), _lib.dptr(trace),
+                                      None if R is None else _lib.dptr(R), ctypes.byref(count)))
+        c = int(count.value)
+        index = index[:c].copy()
+        z = np.array(xs[index], dtype=DTYPE)
+        if not return_info:
+            return z
+        info = {"index": index, "pivot": pivot[:c].copy(), "trace": trace[:c + 1].copy(), "count": c, "tol": tol}
+        if factor:
+            info["R"] = R[:c].copy()
+        return z, info
 
     # ---- device plumbing ----
     def _state(self):

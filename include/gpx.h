@@ -181,6 +181,7 @@ int gpx_stream_wait_event(void *stream, void *event);
 #define GPX_PROF_SPARSE_GRAM 19 /* gpx_sgp_fit: the Gram product K(z, x_c) K(x_c, z) of ONE chunk, one record around all of its slice products; flops 2 c per element of the lower triangle.  (The product kernel's own launches are recorded under their classes as well.) */
 #define GPX_PROF_SPARSE_GRAD 20 /* rect_tile_kernel / tile_reduce_ard_kernel in its rectangular form (gpx_sgp_grad): the rectangular tile reduction of ONE chunk; kernel-derivative evaluations c * M */
 #define GPX_PROF_SPARSE_ZGRAD 21 /* rect_zgrad_kernel and its slice sum (gpx_sgp_grad_z, gpx_d_rect_zgrad): ONE pass of c rows against the M columns; kernel-derivative evaluations c * M per window of dimensions */
+#define GPX_PROF_SELECT      22 /* select_pick_kernel + select_step_kernel (gpx_sgp_select), ONE record per call around all of its launches: bytes of R read and written, sizeof(T) n count (count + 1) / 2 */
 int gpx_prof_enable(int on);    /* also clears the registry */
 int gpx_prof_read(int cls, double *launches, double *total_ms, double *total_work);
 
@@ -214,6 +215,7 @@ int gpx_prof_read(int cls, double *launches, double *total_ms, double *total_wor
 #define GPX_ROUTE_PATHS_GRAD_CHUNK 23 /* gpx_paths_grad: one hit per row chunk of xo                                                   */
 #define GPX_ROUTE_REMOVE         24   /* gpx_gp_remove: one hit per call                                               */
 #define GPX_ROUTE_SPARSE_CHUNK   25   /* gpx_sgp_fit: one hit per column chunk of x                                   */
+#define GPX_ROUTE_SELECT_STEP    26   /* gpx_sgp_select: one hit per step that picked a point                          */
 int gpx_debug_route_count(int route, int64_t *count);
 /* roctx ranges pushed so far (GPX_ROCTX=1: every gpx_gp_* call and every launch class below it is a nested host range for
  * `rocprofv3 --marker-trace`; libroctx64.so is loaded on first use; 0 while the switch is off) */
@@ -902,6 +904,28 @@ int gpx_sgp_last_zgrad_timing(gpx_sgp_t *h, float *ms2);
 /* Depth slices per chunk for later fits of this handle: 0 = the plan's (the default), P >= 1 = exactly that many (1: one
  * plain product per chunk).  For measurements (tools/sparse_bench.py); results differ in the last bits between values. */
 int gpx_sgp_set_split(gpx_sgp_t *h, int slices);
+/* Greedy conditional-variance selection of inducing points (Burt, Rasmussen and van der Wilk 2020): a pivoted partial
+ * Cholesky of K(x, x), which is never formed.  No handle: the call uploads x, runs on a stream of its own and is synchronous.
+ * All pointers are HOST.  x: (n, d) float64; params: the kernel's, as gpx_sgp_fit's.  All sums are f64 for both dtypes.
+ *   dres[i] = k(x_i, x_i), the element gpx_d_kmat would store (the ARD family: points scaled once by gpx_d_scale_points)
+ *   step m = 0, 1, ...:
+ *     1. p = the unpicked index with the largest dres; on a tie the SMALLEST index.  first >= 0: step 0 takes `first`.
+ *     2. dres[p] <= tol: stop, *count = m.
+ *     3. R[m, i] = (k(x_p, x_i) - sum_{j < m} R[j, p] R[j, i]) / sqrt(dres[p]) for every i, j ascending; R is kept in the dtype.
+ *     4. dres[i] -= R[m, i]^2 with R[m, i] as stored; p is picked and its residual counts as 0 from then on.
+ *     5. trace[m + 1] = sum_{i unpicked} dres[i].          trace[0]: that sum before any pick.
+ * trace[M] is kff - tr X of the bound at the M picks and jitter 0 -- the curve to choose M from.
+ * index, pivot: m_max entries, *count valid (pivot[m] = dres[p] at step m).  trace: m_max + 1 entries, *count + 1 valid.
+ * R: NULL, or m_max x n doubles, dense; the first *count rows are written.  On the device R is m_max x round_up(n, 128) in the
+ * dtype: GPX_ERR_NOMEM, with the bytes needed in gpx_last_error(), when that does not fit the free memory.
+ * Two launches per step (select_pick_kernel: one workgroup; select_step_kernel: one thread per 16 bytes of a row of R), all
+ * enqueued at once; stream order is the only dependency, no atomics: every output repeats bit for bit.
+ * GPX_ERR_ARG: n < 1, m_max outside 1 .. n, tol negative or not finite, first >= n, a kernel or d gpx_d_kmat refuses, NULL
+ * arguments, non-finite params; nothing is written then.  GPX_PROF_SELECT: one record per call.  GPX_ROUTE_SELECT_STEP: one
+ * hit per step that picked a point. */
+int gpx_sgp_select(int dtype, int kernel, const double *x, int64_t n, int d, const double *params,
+                   int64_t m_max, double tol, int64_t first,
+                   int64_t *index, double *pivot, double *trace, double *R, int64_t *count);
 /* host arithmetic only: the plan of a fit -- columns per chunk, chunks, depth slices per full chunk and their width.
  * chunk_cols 0: the largest multiple of 128, at most 16384, whose M x c block fits a quarter of free_bytes; one chunk of
  * round_up(n, 128) when n is within it.  slices: P = as many as make tiles x P cover 256 workgroups (tiles = the 128 x 128
