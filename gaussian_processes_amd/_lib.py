@@ -189,6 +189,7 @@ _SIGNATURES = {
                                POINTER(c_int64), c_double_p, c_double_p, c_double_p, POINTER(c_int64)]),
     "gpx_debug_sgp_plan": (c_int, [c_int, c_int64, c_int64, c_int64, c_int, c_size_t, POINTER(c_int64), POINTER(c_int64),
                                    c_int_p, POINTER(c_int64)]),
+    "gpx_debug_sgp_grad_plan": (c_int, [c_int, c_int64, c_int64, c_int64, c_int, c_size_t, POINTER(c_int64), POINTER(c_int64)]),
     "gpx_d_sum_slices_lower": (c_int, [c_int, c_void_p, c_int64, c_int64, c_int, c_int64, c_void_p, c_int64, c_void_p]),
     "gpx_d_gemv_acc": (c_int, [c_int, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
     "gpx_d_mirror_lower": (c_int, [c_int, c_void_p, c_int64, c_int64, c_void_p]),

@@ -59,8 +59,8 @@ int check_internal_info(int info);
 
 static inline hipStream_t S(void *s) { return (hipStream_t)s; }
 static inline size_t esize(int dtype) { return dtype == GPX_F64 ? 8 : 4; }
-static inline int64_t round_up(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
-static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
+static constexpr int64_t round_up(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
+static constexpr int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 // a "now" on `to` after everything enqueued so far on `from`, through an event the caller owns
 static inline int order(hipEvent_t e, hipStream_t from, hipStream_t to)

@@ -7,6 +7,8 @@
 //   GrowBuf                a grow-only block with ONE owner: a handle (fit_batch's workspaces, sag_tmp), a factor (the
 //                          TrsvOps below) or, through ThreadScratch, a host thread on one device
 //   ThreadScratch          one GrowBuf per device for the calling host thread
+//   Carve                  the byte layout of ONE block that holds several arrays: a pass declares it once, in a function
+//                          that returns its offsets and the total; the allocation takes the total, the pointers the offsets
 //
 // Every request is passed to hipMalloc byte for byte: nothing is rounded up, pooled or kept for a later caller.
 #pragma once
@@ -61,6 +63,19 @@ private:
         return GPX_OK;
     }
 };
+
+// A bump carver over byte offsets: take() returns where the next sub-block starts, total() the size of them all.  No
+// memory is touched, so a layout is a constexpr function of the shapes and can be asserted at compile time.
+struct Carve {
+    size_t end = 0;
+    constexpr size_t take(size_t bytes, size_t align = 128) { const size_t at = (end + align - 1) / align * align; end = at + bytes; return at; }
+    constexpr size_t total() const { return end; }
+};
+struct CarveCheck { size_t a, b, c, total; };
+constexpr CarveCheck carve_check() { Carve k; CarveCheck l{}; l.a = k.take(100); l.b = k.take(8, 256); l.c = k.take(24); l.total = k.total(); return l; }
+static_assert(carve_check().a == 0 && carve_check().b == 256 && carve_check().c == 384, "Carve: offsets ascend, each on its alignment");
+static_assert(carve_check().b >= carve_check().a + 100 && carve_check().c >= carve_check().b + 8, "Carve: sub-blocks do not overlap");
+static_assert(carve_check().total == carve_check().c + 24, "Carve: the total is the last offset plus its size");
 
 // One slot per device for per-thread state (`static thread_local PerDevice<...>`): a host thread that alternates between
 // GPUs finds each device's slot again, and no block is dropped unfreed.  HIP's current device is per host thread, and

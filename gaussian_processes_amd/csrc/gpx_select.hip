@@ -24,9 +24,10 @@
 // wave-uniform index, which the compiler turns into scalar loads (eight doubles per s_load in the unrolled loop) -- the route
 // the kernel-matrix build found faster than LDS broadcasts for its row points.
 //
-// Layout in HBM (dtype T, ldr = round_up(n, 128)):
-//   x (n, d)  [ARD: scaled in place]     R  m_max x ldr     dres  n doubles     picked  n bytes
-//   the partials: nwg doubles | nwg int64 | nwg doubles      index, pivot, trace, coef, the state word block
+// Layout in HBM (dtype T, ldr = round_up(n, 128)): ONE block, carved by sel_layout (gpx_mem.h's Carve, each sub-block on 128
+// bytes), whose total is also what the call tests against the free memory:
+//   x (n, d)  [ARD: scaled in place] | R  m_max x ldr | dres  n doubles | picked  n bytes
+//   | the partials: nwg doubles | nwg int64 | nwg doubles | index | pivot | trace | coef | the state word block
 #include "gpx_small.h"
 #include <algorithm>
 #include <cmath>
@@ -228,12 +229,39 @@ __global__ __launch_bounds__(256) void select_step_kernel(const T *__restrict__ 
     if (threadIdx.x == 0) { pmx[blockIdx.x] = mx; pix[blockIdx.x] = ix; psm[blockIdx.x] = sm; }
 }
 
+constexpr int64_t SEL_LD_ALIGN = 128;
+
+// Everything a selection holds on the device (the fp32 upload's f64 staging aside), ONE block: declared here, once.  The
+// allocation and the test against the free memory take `total`, SelBufs its pointers from the offsets.
+struct SelLayout { size_t x, R, dres, picked, pmx, pix, psm, index, pivot, trace, coef, st, total; };
+constexpr SelLayout sel_layout(int64_t n, int d, int64_t m_max, size_t es)
+{
+    const size_t nwg = (size_t)cdiv(n, 256 * (int64_t)(16 / es)), N = (size_t)n, M = (size_t)m_max;
+    Carve k;
+    const size_t x = k.take(N * d * es), R = k.take(M * (size_t)round_up(n, SEL_LD_ALIGN) * es), dres = k.take(N * 8), picked = k.take(N);
+    const size_t pmx = k.take(nwg * 8), pix = k.take(nwg * 8), psm = k.take(nwg * 8);
+    const size_t index = k.take(M * 8), pivot = k.take(M * 8), trace = k.take((M + 1) * 8), coef = k.take(M * 8), st = k.take(sizeof(SelState));
+    return {x, R, dres, picked, pmx, pix, psm, index, pivot, trace, coef, st, k.total()};
+}
+// the padding of the twelve sub-blocks: what the layout adds to the sum the twelve separate buffers of this file once made
+constexpr size_t sel_padding(int64_t n, int d, int64_t m_max, size_t es)
+{
+    return sel_layout(n, d, m_max, es).total - ((size_t)m_max * round_up(n, SEL_LD_ALIGN) * es + (size_t)n * d * es + (size_t)n * 9 +
+                                                (size_t)cdiv(n, 256 * (int64_t)(16 / es)) * 24 + (size_t)m_max * 32 + 8 + sizeof(SelState));
+}
+static_assert(sel_padding(1000, 3, 64, 8) <= 12 * 128 && sel_padding(1000, 3, 64, 4) <= 12 * 128, "the selection's layout (unsigned: never less)");
+
+// the pointers of a block laid out so
 struct SelBufs {
     void *x, *R;
     double *dres, *pmx, *psm, *pivot, *trace, *coef;
     int64_t *pix, *index;
     unsigned char *picked;
     SelState *st;
+    SelBufs(char *p, const SelLayout &l)
+        : x(p + l.x), R(p + l.R), dres((double *)(p + l.dres)), pmx((double *)(p + l.pmx)), psm((double *)(p + l.psm)),
+          pivot((double *)(p + l.pivot)), trace((double *)(p + l.trace)), coef((double *)(p + l.coef)), pix((int64_t *)(p + l.pix)),
+          index((int64_t *)(p + l.index)), picked((unsigned char *)(p + l.picked)), st((SelState *)(p + l.st)) {}
 };
 
 // every launch of a selection, enqueued on `st`: init, (pick, step) x m_max, the last trace entry
@@ -273,7 +301,6 @@ struct SelStream {
     }
 };
 
-constexpr int64_t SEL_LD_ALIGN = 128;
 constexpr size_t SEL_DOWNLOAD_BYTES = (size_t)256 << 20;       // the f64 staging copy of R's rows on their way to the host
 
 static int sgp_select(int dtype, int kernel, const double *x, int64_t n, int d, const double *params, int64_t m_max, double tol,
@@ -281,7 +308,6 @@ static int sgp_select(int dtype, int kernel, const double *x, int64_t n, int d, 
 {
     const size_t es = esize(dtype);
     const int64_t ldr = round_up(n, SEL_LD_ALIGN);
-    const int64_t nwg = cdiv(n, 256 * (int64_t)(16 / es));
     const bool ard = kernel == GPX_KERNEL_GAUSSIAN_ARD;
     double iso[2];
     const double *vparams = params;
@@ -290,9 +316,8 @@ static int sgp_select(int dtype, int kernel, const double *x, int64_t n, int d, 
     GPX_TRY(make_kparams(ard ? GPX_KERNEL_GAUSSIAN : kernel, GPX_K, vparams, 0.0, &kp));
 
     // everything the call holds on the device, against the free memory, before anything is allocated
-    const size_t r_bytes = (size_t)m_max * ldr * es, x_bytes = (size_t)n * d * es;
-    const size_t small = (size_t)n * 9 + (size_t)nwg * 24 + (size_t)m_max * 32 + 8 + sizeof(SelState);
-    const size_t need = r_bytes + x_bytes + (dtype == GPX_F32 ? (size_t)n * d * 8 : 0) + small;
+    const SelLayout lay = sel_layout(n, d, m_max, es);
+    const size_t r_bytes = (size_t)m_max * ldr * es, need = lay.total + (dtype == GPX_F32 ? (size_t)n * d * 8 : 0);
     size_t freeb = 0, totalb = 0;
     GPX_HIP(hipMemGetInfo(&freeb, &totalb));
     if (need > freeb) {
@@ -304,30 +329,12 @@ static int sgp_select(int dtype, int kernel, const double *x, int64_t n, int d, 
     GPX_TRY(own.create());
     hipStream_t st = own.st;
     StreamTurn turn(st);
-    DevBuf dx, dR, ddres, dpicked, dpmx, dpix, dpsm, dindex, dpivot, dtrace, dcoef, dstate;
-    GPX_TRY(dx.alloc(x_bytes));
-    GPX_TRY(dR.alloc(r_bytes));
-    GPX_TRY(ddres.alloc((size_t)n * 8));
-    GPX_TRY(dpicked.alloc((size_t)n));
-    GPX_TRY(dpmx.alloc((size_t)nwg * 8));
-    GPX_TRY(dpix.alloc((size_t)nwg * 8));
-    GPX_TRY(dpsm.alloc((size_t)nwg * 8));
-    GPX_TRY(dindex.alloc((size_t)m_max * 8));
-    GPX_TRY(dpivot.alloc((size_t)m_max * 8));
-    GPX_TRY(dtrace.alloc((size_t)(m_max + 1) * 8));
-    GPX_TRY(dcoef.alloc((size_t)m_max * 8));
-    GPX_TRY(dstate.alloc(sizeof(SelState)));
-    GPX_TRY(upload_f64(dtype, dx.p, n * d, x, n * d, 1, n * d, st));
-    if (ard) GPX_TRY(scale_points(dtype, dx.p, n, d, params + 1, dx.p, st));
-    GPX_HIP(hipMemsetAsync(dstate.p, 0, sizeof(SelState), st));
-
-    SelBufs b;
-    b.x = dx.p; b.R = dR.p;
-    b.dres = (double *)ddres.p; b.pmx = (double *)dpmx.p; b.psm = (double *)dpsm.p;
-    b.pivot = (double *)dpivot.p; b.trace = (double *)dtrace.p; b.coef = (double *)dcoef.p;
-    b.pix = (int64_t *)dpix.p; b.index = (int64_t *)dindex.p;
-    b.picked = (unsigned char *)dpicked.p;
-    b.st = (SelState *)dstate.p;
+    DevBuf dev;
+    GPX_TRY(dev.alloc(lay.total));
+    const SelBufs b((char *)dev.p, lay);
+    GPX_TRY(upload_f64(dtype, b.x, n * d, x, n * d, 1, n * d, st));
+    if (ard) GPX_TRY(scale_points(dtype, b.x, n, d, params + 1, b.x, st));
+    GPX_HIP(hipMemsetAsync(b.st, 0, sizeof(SelState), st));
 
     std::vector<int64_t> hindex((size_t)m_max);
     std::vector<double> hpivot((size_t)m_max), htrace((size_t)m_max + 1);
@@ -358,7 +365,7 @@ static int sgp_select(int dtype, int kernel, const double *x, int64_t n, int d, 
         const int64_t rows_per = std::max<int64_t>(1, (int64_t)(SEL_DOWNLOAD_BYTES / ((size_t)n * 8)));
         for (int64_t r0 = 0; r0 < cnt; r0 += rows_per) {
             const int64_t rows = std::min(rows_per, cnt - r0);
-            GPX_TRY(download_f64(dtype, R + r0 * n, n, (const char *)dR.p + (size_t)r0 * ldr * es, ldr, rows, n, 0, st));
+            GPX_TRY(download_f64(dtype, R + r0 * n, n, (const char *)b.R + (size_t)r0 * ldr * es, ldr, rows, n, 0, st));
         }
     }
     std::copy(hindex.begin(), hindex.begin() + cnt, index);

@@ -21,9 +21,12 @@
 //   Luu, Phi, Xf, Xt, LB   M x ldm each     (Xf, Xt: work; X ends up in Xt)
 //   cvec, w, t0, t1        M each
 //   bacc                   M doubles
-//   work (grow-only)       G (M x cols) | the partial accumulators (slices x M x ldm)
-//                          the gradient pass lays it out anew: reduction partials | three M x ldm blocks | K(x_c, z), P (c x ldm each)
+//   work (grow-only)       every pass lays it out anew, ONCE, with the carver of gpx_mem.h (each sub-block on 128 bytes):
+//                          sgp_fit_layout   G (M x cols) | the partial accumulators (slices x M x ldm)
+//                          sgp_grad_layout  reduction partials | three M x ldm blocks | K(x_c, z), P (c x ldm each)
 //                          and behind them, for the gradient in z: its M x d accumulator (f64) | -w | its slices' partials
+// Both passes take their chunks from sgp_plan (the gradient's: gpx_debug_sgp_grad_plan) and their times from the handle's one
+// SgpTimeline: a pass is a sequence of marks on the stream, resolved into fit_ms / grad_ms / zgrad_ms when it ends.
 //
 // The gradient of the bound in the hyper-parameters (gpx_sgp_grad; include/gpx.h has the formulas): everything M x M from the
 // factors the fit left (Luu, LB, X in Xt, w) by the sweeps and products the library has, then a second pass over x in
@@ -50,6 +53,40 @@ struct SgpScal {
     int info1, info2;  // potrf of Kuu, of B
 };
 
+// The times of one pass on the handle's stream.  A pass is a sequence of marks: mark() records the next event of a grow-only
+// pool and books the interval since the mark before it to a bucket, or to nobody (SGP_NOBODY); resolve(), behind the pass's
+// last synchronisation, adds the intervals up.  The fit and the gradient never overlap: they share the pool.
+constexpr int SGP_NOBODY = -1;
+struct SgpTimeline {
+    std::vector<hipEvent_t> pool;      // grow-only; gpx_sgp_destroy destroys them
+    std::vector<int> bucket;           // of the marks of the current pass
+    SgpTimeline &begin() { bucket.clear(); return *this; }
+    int mark(hipStream_t st, int b)
+    {
+        if (bucket.size() == pool.size()) {
+            hipEvent_t e;
+            GPX_HIP(hipEventCreate(&e));
+            pool.push_back(e);
+        }
+        GPX_HIP(hipEventRecord(pool[bucket.size()], st));
+        bucket.push_back(b);
+        return GPX_OK;
+    }
+    // ms[b] (b < count) = the sum of bucket b's intervals; ms[total] = the first mark to the last
+    int resolve(float *ms, int count, int total) const
+    {
+        for (int i = 0; i < count; ++i) ms[i] = 0.0f;
+        for (size_t i = 1; i < bucket.size(); ++i) {
+            if (bucket[i] == SGP_NOBODY) continue;
+            float t = 0.0f;
+            GPX_HIP(hipEventElapsedTime(&t, pool[i - 1], pool[i]));
+            ms[bucket[i]] += t;
+        }
+        if (bucket.size() > 1) GPX_HIP(hipEventElapsedTime(&ms[total], pool[0], pool[bucket.size() - 1]));
+        return GPX_OK;
+    }
+};
+
 struct gpx_sgp {
     int device, dtype, kernel, d, nparams;
     int64_t n, m, ldm;
@@ -60,22 +97,13 @@ struct gpx_sgp {
     SgpScal *scal;
     gpx::GrowBuf work;
     hipStream_t st;
-    hipEvent_t ev[4];                  // start, Kuu done, chunks done, tail done
-    std::vector<hipEvent_t> cev;       // three per chunk: before the build, behind it, behind the products
-    int64_t chunks_timed;
+    SgpTimeline tl;
     double params[1 + GPX_ARD_MAX_D], iso[2];
     double s, jitter;
-    bool have_x, have_y, have_z, fitted;
+    bool have_x, have_y, have_z, fitted, have_grad, have_zgrad;
     int stage, pivot, split;
     SgpScal host;                      // the scalars of the last good fit
-    hipEvent_t gev[3];                 // the gradient pass: start, M x M part done, end
-    std::vector<hipEvent_t> gcev;      // four per chunk: before the build, behind it, behind the product, behind the reduction
-    float grad_ms[5];
-    bool have_grad;
-    hipEvent_t zev;                    // the joint pass: behind the z-gradient's Kuu part
-    std::vector<hipEvent_t> zcev;      // one per chunk: behind the z-gradient's kernels
-    float zgrad_ms[2];
-    bool have_zgrad;
+    float fit_ms[5], grad_ms[5], zgrad_ms[2];      // the last passes' times, as gpx_sgp_last_{,grad_,zgrad_}timing return them
 };
 
 namespace gpx {
@@ -84,8 +112,12 @@ constexpr int64_t SGP_CHUNK_ALIGN = 128, SGP_CHUNK_CAP = 16384, SGP_TARGET_WGS =
                   SGP_ACC_BYTES = (int64_t)2 << 30;
 
 // ---- the plan: columns per chunk, depth slices ---------------------------------------------------------------------------
-static int sgp_plan(int dtype, int64_t n, int64_t M, int64_t chunk_cols, int split, size_t free_bytes, int64_t *cols, int64_t *chunks,
-                    int *slices, int64_t *slice_cols)
+struct SgpPlan { int64_t cols, chunks; int slices; int64_t slice_cols; };
+enum SgpPass { SGP_FIT, SGP_GRAD };
+
+// the one place chunk_cols is checked.  SGP_GRAD: the fit's columns, with two c x ldm blocks where the fit has one M x c
+// (slices and slice_cols stay the fit's: the gradient's product is not split)
+static int sgp_plan(SgpPass pass, int dtype, int64_t n, int64_t M, int64_t chunk_cols, int split, size_t free_bytes, SgpPlan *plan)
 {
     if (!(dtype == GPX_F64 || dtype == GPX_F32)) { set_error("sparse plan: dtype must be GPX_F64 or GPX_F32"); return GPX_ERR_ARG; }
     if (n < 1 || M < 1) { set_error("sparse plan: need n >= 1 and m_inducing >= 1"); return GPX_ERR_ARG; }
@@ -119,10 +151,17 @@ static int sgp_plan(int dtype, int64_t n, int64_t M, int64_t chunk_cols, int spl
     const int64_t planned = std::min(acc_fit, std::min(SGP_MAX_SLICES, std::max(SGP_MIN_SLICES, cdiv(SGP_TARGET_WGS, tiles))));
     const int64_t P = split > 0 ? split : planned;
     const int64_t W = round_up(std::max(cdiv(c, P), SGP_CHUNK_ALIGN), SGP_CHUNK_ALIGN);
-    if (cols) *cols = c;
-    if (chunks) *chunks = cdiv(n, c);
-    if (slices) *slices = (int)cdiv(c, W);
-    if (slice_cols) *slice_cols = W;
+    const int slices = (int)cdiv(c, W);
+    const size_t per_two = (size_t)2 * round_up(M, 16) * esize(dtype);
+    if (pass == SGP_GRAD && (size_t)c * per_two > budget) {
+        if (chunk_cols == 0) c = std::max(SGP_CHUNK_ALIGN, c / 2 / SGP_CHUNK_ALIGN * SGP_CHUNK_ALIGN);
+        if ((size_t)c * per_two > budget) {
+            set_error("sparse gradient: two blocks of %lld columns and %lld rows do not fit a quarter of the free device memory (%zu bytes free)",
+                      (long long)c, (long long)M, free_bytes);
+            return GPX_ERR_NOMEM;
+        }
+    }
+    *plan = {c, cdiv(n, c), slices, W};
     return GPX_OK;
 }
 
@@ -293,13 +332,25 @@ static int sgp_read_info(gpx_sgp *g, int which, int *info)
     return check_internal_info(*info);
 }
 
-static int sgp_chunk_events(gpx_sgp *g, int64_t chunks)
+static void sgp_unfit(gpx_sgp *g) { g->fitted = g->have_grad = g->have_zgrad = false; g->stage = g->pivot = 0; }
+
+// the work buffer of a fit: G (M x cols) | the partial accumulators (slices x M x ldm, p_bytes together)
+struct SgpFitLayout { size_t G, Pacc, p_bytes, total; };
+constexpr SgpFitLayout sgp_fit_layout(int64_t M, int64_t ldm, int64_t cols, int slices, size_t es)
 {
-    while ((int64_t)g->cev.size() < 3 * chunks) {
-        hipEvent_t e;
-        GPX_HIP(hipEventCreate(&e));
-        g->cev.push_back(e);
-    }
+    Carve k;
+    const size_t p_bytes = (size_t)slices * M * ldm * es, G = k.take((size_t)M * cols * es), Pacc = k.take(p_bytes);
+    return {G, Pacc, p_bytes, k.total()};
+}
+
+enum { FIT_KUU, FIT_BUILD, FIT_GRAM, FIT_TAIL, FIT_TOTAL };
+
+// a fit that ends here, its times with it: at the failed factorisation of `stage`, or at the end (stage 0)
+static int sgp_fit_ends(gpx_sgp *g, int stage, int pivot)
+{
+    GPX_HIP(hipStreamSynchronize(g->st));
+    GPX_TRY(g->tl.resolve(g->fit_ms, 5, FIT_TOTAL));
+    g->stage = stage; g->pivot = pivot; g->fitted = true;
     return GPX_OK;
 }
 
@@ -309,18 +360,17 @@ static int sgp_fit(gpx_sgp *g, int64_t chunk_cols)
     const size_t es = esize(dtype);
     const int64_t n = g->n, M = g->m, ldm = g->ldm;
     hipStream_t st = g->st;
-    g->fitted = false; g->have_grad = false; g->have_zgrad = false; g->stage = 0; g->pivot = 0; g->chunks_timed = 0;
+    SgpTimeline &tl = g->tl.begin();
+    sgp_unfit(g);
     // the plan and its buffer, before anything is enqueued
     size_t freeb = 0, totalb = 0;
     GPX_HIP(hipMemGetInfo(&freeb, &totalb));
-    int64_t cols = 0, chunks = 0, W = 0;
-    int slices = 0;
-    GPX_TRY(sgp_plan(dtype, n, M, chunk_cols, g->split, freeb + g->work.bytes, &cols, &chunks, &slices, &W));
-    const int64_t sP = M * ldm;
-    const size_t g_bytes = (size_t)M * cols * es, p_bytes = (size_t)slices * sP * es;
-    GPX_TRY(g->work.reserve(g_bytes + p_bytes, st));
-    char *G = (char *)g->work.p, *Pacc = G + g_bytes;      // (g_bytes is a multiple of 128 es: Pacc is 16-byte aligned)
-    GPX_TRY(sgp_chunk_events(g, chunks));
+    SgpPlan pl;
+    GPX_TRY(sgp_plan(SGP_FIT, dtype, n, M, chunk_cols, g->split, freeb + g->work.bytes, &pl));
+    const int64_t cols = pl.cols, chunks = pl.chunks, W = pl.slice_cols, sP = M * ldm;
+    const SgpFitLayout lay = sgp_fit_layout(M, ldm, cols, pl.slices, es);
+    GPX_TRY(g->work.reserve(lay.total, st));
+    char *G = (char *)g->work.p + lay.G, *Pacc = (char *)g->work.p + lay.Pacc;
     if (g->kernel == GPX_KERNEL_GAUSSIAN_ARD) {
         ard_iso(g->params, g->d, g->iso);
         GPX_TRY(scale_points(dtype, g->x, n, g->d, g->params + 1, g->xs, st));
@@ -328,24 +378,24 @@ static int sgp_fit(gpx_sgp *g, int64_t chunk_cols)
     }
     const SgpView v = sgp_view(g);
     GPX_HIP(hipMemsetAsync(g->scal, 0, sizeof(SgpScal), st));
-    GPX_HIP(hipEventRecord(g->ev[0], st));
+    GPX_TRY(tl.mark(st, SGP_NOBODY));
     // 1. Kuu and its factor
     GPX_TRY(kmat(dtype, v.kernel, GPX_K, v.z, M, v.z, M, g->d, v.params, g->jitter, GPX_LOWER, g->Luu, ldm, st));
     GPX_TRY(potrf(dtype, g->Luu, M, ldm, &g->scal->info1, st));
     GPX_TRY(tril(dtype, g->Luu, M, ldm, st));
-    GPX_HIP(hipEventRecord(g->ev[1], st));
+    GPX_TRY(tl.mark(st, FIT_KUU));
     int info = 0;
     GPX_TRY(sgp_read_info(g, 1, &info));
-    if (info != 0) { g->stage = 1; g->pivot = info; g->fitted = true; return GPX_OK; }
+    if (info != 0) return sgp_fit_ends(g, 1, info);        // (two marks: total == kuu, the rest 0)
     // 2. the chunk loop: Phi's partials, b
-    GPX_HIP(hipMemsetAsync(Pacc, 0, p_bytes, st));
+    GPX_HIP(hipMemsetAsync(Pacc, 0, lay.p_bytes, st));
     GPX_HIP(hipMemsetAsync(g->bacc, 0, (size_t)M * sizeof(double), st));
     for (int64_t c = 0; c < chunks; ++c) {
         const int64_t c0 = c * cols, cc = std::min(cols, n - c0);
         route_hit(RT_SPARSE_CHUNK);
-        GPX_HIP(hipEventRecord(g->cev[3 * c], st));
+        GPX_TRY(tl.mark(st, SGP_NOBODY));
         GPX_TRY(kmat(dtype, v.kernel, GPX_K, v.z, M, (const char *)v.x + (size_t)c0 * g->d * es, cc, g->d, v.params, 0.0, GPX_FULL, G, cols, st));
-        GPX_HIP(hipEventRecord(g->cev[3 * c + 1], st));
+        GPX_TRY(tl.mark(st, FIT_BUILD));
         const int64_t nfull = cc / W, tail = cc - nfull * W;
         {
             ProfScope prof(PC_SPARSE_GRAM, (double)cc * (double)M * (double)(M + 1), st);     // 2 cc flops per element of the lower triangle
@@ -359,12 +409,11 @@ static int sgp_fit(gpx_sgp *g, int64_t chunk_cols)
             }
         }
         GPX_TRY(gemv_acc(dtype, G, M, cc, cols, (const char *)g->y + (size_t)c0 * es, g->bacc, st));
-        GPX_HIP(hipEventRecord(g->cev[3 * c + 2], st));
+        GPX_TRY(tl.mark(st, FIT_GRAM));
     }
-    g->chunks_timed = chunks;
     GPX_HIP(hipMemsetAsync(g->Phi, 0, (size_t)M * ldm * es, st));
-    GPX_TRY(sum_slices_lower(dtype, Pacc, ldm, sP, slices, M, nullptr, g->Phi, ldm, st));
-    GPX_HIP(hipEventRecord(g->ev[2], st));
+    GPX_TRY(sum_slices_lower(dtype, Pacc, ldm, sP, pl.slices, M, nullptr, g->Phi, ldm, st));
+    GPX_TRY(tl.mark(st, FIT_GRAM));                         // (the slice sum)
     // 3. the M x M tail
     GPX_TRY(dot(dtype, g->y, g->y, n, &g->scal->yy, st));
     // k(0): the first inducing point against itself, through the variance's finishing pass with a zero sum
@@ -379,10 +428,8 @@ static int sgp_fit(gpx_sgp *g, int64_t chunk_cols)
     GPX_TRY(tril(dtype, g->LB, M, ldm, st));
     GPX_TRY(sgp_read_info(g, 2, &info));
     if (info != 0) {
-        GPX_HIP(hipEventRecord(g->ev[3], st));
-        GPX_HIP(hipStreamSynchronize(st));
-        g->stage = 2; g->pivot = info; g->fitted = true;
-        return GPX_OK;
+        GPX_TRY(tl.mark(st, FIT_TAIL));                     // (the tail up to the failed factorisation)
+        return sgp_fit_ends(g, 2, info);
     }
     // c = LB^-1 Luu^-1 b / s   (trsv_lower destroys its right-hand side)
     GPX_TRY(cvt_div(dtype, g->bacc, g->t0, M, 1.0, st));
@@ -396,17 +443,19 @@ static int sgp_fit(gpx_sgp *g, int64_t chunk_cols)
     GPX_TRY(div_vec(dtype, g->w, M, g->s, st));
     GPX_TRY(logdet_chol(dtype, g->LB, M, ldm, &g->scal->logdetB, st));
     GPX_TRY(dot(dtype, g->cvec, g->cvec, M, &g->scal->cc, st));
-    GPX_HIP(hipEventRecord(g->ev[3], st));
+    GPX_TRY(tl.mark(st, FIT_TAIL));
     GPX_HIP(hipMemcpyAsync(&g->host, g->scal, sizeof(SgpScal), hipMemcpyDeviceToHost, st));
-    GPX_HIP(hipStreamSynchronize(st));
-    g->fitted = true;
-    return GPX_OK;
+    return sgp_fit_ends(g, 0, 0);
 }
 
-static int sgp_upload_points(gpx_sgp *g, void *dst, const double *xo, int64_t m)
+// the test points of mean, var and cov on the device, scaled for the ARD family; m == 0: nothing to do
+static int sgp_stage_points(gpx_sgp *g, const double *xo, int64_t m, const double *out, DevBuf *dxo)
 {
-    GPX_TRY(upload_f64(g->dtype, dst, m * g->d, xo, m * g->d, 1, m * g->d, g->st));
-    if (g->kernel == GPX_KERNEL_GAUSSIAN_ARD) GPX_TRY(scale_points(g->dtype, dst, m, g->d, g->params + 1, dst, g->st));
+    if (!(m >= 0 && (m == 0 || (xo && out)))) { set_error("sparse prediction: bad arguments"); return GPX_ERR_ARG; }
+    if (m == 0) return GPX_OK;
+    GPX_TRY(dxo->alloc((size_t)m * g->d * esize(g->dtype)));
+    GPX_TRY(upload_f64(g->dtype, dxo->p, m * g->d, xo, m * g->d, 1, m * g->d, g->st));
+    if (g->kernel == GPX_KERNEL_GAUSSIAN_ARD) GPX_TRY(scale_points(g->dtype, dxo->p, m, g->d, g->params + 1, dxo->p, g->st));
     return GPX_OK;
 }
 
@@ -442,20 +491,22 @@ static int product_nt(int dtype, int64_t m, int64_t n, int64_t k, const void *A,
     return gemm_nt(dtype, m, n, k, A, ld, B, ld, C, ld, alpha, GPX_FULL, 0, 0, st, beta0 ? 1 : 0);
 }
 
-static int sgp_grad_events(gpx_sgp *g, int64_t chunks, bool with_z)
+// the work buffer of a gradient pass: the reduction's partials (part_doubles of them and the 8 w . b sits in) | Y A Tm
+// (M x ldm) | G P (cols x ldm), and with_z: the M x d accumulator (f64) | -w | zpart_doubles partials of the z kernel (a
+// function of M and d: the passes on x and on z share them).  Mm aliases Y, which is done with when Mm is formed.
+struct SgpGradLayout { size_t part, Y, A, Tm, G, P, zacc, negw, zpart, total; };
+constexpr SgpGradLayout sgp_grad_layout(int64_t M, int64_t ldm, int64_t cols, int d, size_t es, size_t part_doubles, bool with_z,
+                                        size_t zpart_doubles)
 {
-    while ((int64_t)g->gcev.size() < 4 * chunks) {
-        hipEvent_t e;
-        GPX_HIP(hipEventCreate(&e));
-        g->gcev.push_back(e);
-    }
-    while (with_z && (int64_t)g->zcev.size() < chunks) {
-        hipEvent_t e;
-        GPX_HIP(hipEventCreate(&e));
-        g->zcev.push_back(e);
-    }
-    return GPX_OK;
+    const size_t mm = (size_t)M * ldm * es, blk = (size_t)cols * ldm * es;
+    Carve k;
+    const size_t part = k.take((part_doubles + 8) * 8), Y = k.take(mm), A = k.take(mm), Tm = k.take(mm), G = k.take(blk), P = k.take(blk);
+    const size_t zacc = with_z ? k.take((size_t)M * d * 8) : 0, negw = with_z ? k.take((size_t)ldm * es) : 0;
+    const size_t zpart = with_z ? k.take(zpart_doubles * 8) : 0;
+    return {part, Y, A, Tm, G, P, zacc, negw, zpart, k.total()};
 }
+
+enum { GRAD_MM, GRAD_BUILD, GRAD_PRODUCT, GRAD_REDUCE, GRAD_TOTAL, ZGRAD_KUU, ZGRAD_CHUNKS, GRAD_BUCKETS };
 
 // grad (may be null when grad_z is not): (kernel parameters..., s).  grad_z (HOST, M x d, or null): the gradient in the inducing
 // inputs from the same pass; null leaves the pass exactly the theta-only one -- the same launches, the same bits
@@ -472,33 +523,21 @@ static int sgp_grad(gpx_sgp *g, int64_t chunk_cols, double *grad, double *grad_z
     // the plan: the fit's, with two c x ldm blocks where the fit has one M x c
     size_t freeb = 0, totalb = 0;
     GPX_HIP(hipMemGetInfo(&freeb, &totalb));
-    int64_t cols = 0, chunks = 0;
-    GPX_TRY(sgp_plan(dtype, n, M, chunk_cols, g->split, freeb + g->work.bytes, &cols, &chunks, nullptr, nullptr));
-    const size_t budget = (freeb + g->work.bytes) / 4;
-    if ((size_t)2 * cols * ldm * es > budget) {
-        if (chunk_cols == 0) cols = std::max(SGP_CHUNK_ALIGN, cols / 2 / SGP_CHUNK_ALIGN * SGP_CHUNK_ALIGN);
-        if ((size_t)2 * cols * ldm * es > budget) {
-            set_error("sparse gradient: two blocks of %lld columns and %lld rows do not fit a quarter of the free device memory (%zu bytes free)",
-                      (long long)cols, (long long)M, freeb + g->work.bytes);
-            return GPX_ERR_NOMEM;
-        }
-        chunks = cdiv(n, cols);
-    }
-    const size_t part_doubles = dloglh_partial_doubles(g->kernel, d), part_bytes = (size_t)round_up((int64_t)(part_doubles + 8) * 8, 128);
-    const size_t mm = (size_t)M * ldm * es, blk = (size_t)cols * ldm * es;
-    // the gradient in z: its accumulator, -w and the slices' partials of its kernel (a function of M and d: the passes on x and on z share them)
-    const size_t zacc_bytes = grad_z ? (size_t)round_up(M * d * 8, 128) : 0, negw_bytes = grad_z ? (size_t)round_up(ldm * (int64_t)es, 128) : 0;
-    const size_t zpart_bytes = grad_z ? rect_zgrad_partial_doubles(sgp_view(g).kernel, M, d) * sizeof(double) : 0;
-    GPX_TRY(g->work.reserve(part_bytes + 3 * mm + 2 * blk + zacc_bytes + negw_bytes + zpart_bytes, st));
-    double *part = (double *)g->work.p, *wb_dev = part + part_doubles;
-    char *Y = (char *)g->work.p + part_bytes, *A = Y + mm, *Tm = A + mm, *G = Tm + mm, *P = G + blk;
-    char *Mm = Y;                                                                    // (Y is done with when Mm is formed)
-    double *zacc = (double *)(P + blk), *zpart = (double *)(P + blk + zacc_bytes + negw_bytes);
-    char *negw = P + blk + zacc_bytes;
+    SgpPlan pl;
+    GPX_TRY(sgp_plan(SGP_GRAD, dtype, n, M, chunk_cols, g->split, freeb + g->work.bytes, &pl));
+    const int64_t cols = pl.cols, chunks = pl.chunks;
+    const SgpView v = sgp_view(g);
+    const size_t part_doubles = dloglh_partial_doubles(g->kernel, d), mm = (size_t)M * ldm * es;
+    const SgpGradLayout lay = sgp_grad_layout(M, ldm, cols, d, es, part_doubles, grad_z != nullptr,
+                                              grad_z ? rect_zgrad_partial_doubles(v.kernel, M, d) : 0);
+    GPX_TRY(g->work.reserve(lay.total, st));
+    char *base = (char *)g->work.p;
+    double *part = (double *)(base + lay.part), *wb_dev = part + part_doubles;
+    char *Y = base + lay.Y, *A = base + lay.A, *Tm = base + lay.Tm, *G = base + lay.G, *P = base + lay.P, *Mm = Y, *negw = base + lay.negw;
+    double *zacc = (double *)(base + lay.zacc), *zpart = (double *)(base + lay.zpart);
     const double *col_div = ard ? g->params + 1 : nullptr;                           // (the scaled points: d/dz_ik = d/dzs_ik / w_k)
     void *X1 = g->Xf;                                                                // (work of the fit: nobody reads it afterwards)
-    GPX_TRY(sgp_grad_events(g, chunks, grad_z != nullptr));
-    const SgpView v = sgp_view(g);
+    SgpTimeline &tl = g->tl.begin();
     const double s = g->s, s2 = s * s, N = (double)n;
 
     // 1. the M x M part.  Neither Kuu^-1 - Sigma^-1 nor Gu is formed as a difference: in the directions the data do not
@@ -507,7 +546,7 @@ static int sgp_grad(gpx_sgp *g, int64_t chunk_cols, double *grad, double *grad_z
     // Y = Luu^-T LB^-T and A = Luu^-T X LB^-T:
     //   Kuu^-1 - Sigma^-1 = Luu^-T (I - B^-1) Luu^-1 = Luu^-T (X / s^2) B^-1 Luu^-1 = A Y^T / s^2
     //   Gu = Luu^-T (I - B^-1 - X / s^2) Luu^-1 / 2 - w w^T / 2 = -(A A^T / s^4 + w w^T) / 2     (I - B^-1 - (B - I) = -(B - I)^2 B^-1)
-    GPX_HIP(hipEventRecord(g->gev[0], st));
+    GPX_TRY(tl.mark(st, SGP_NOBODY));
     GPX_TRY(eye_rows(dtype, X1, M, ldm, 0, 0, st));
     GPX_TRY(trsm_right_lt(dtype, g->Luu, M, ldm, X1, M, ldm, st, 1));                 // X1 = Luu^-T
     GPX_HIP(hipMemcpyAsync(Y, X1, mm, hipMemcpyDeviceToDevice, st));
@@ -524,7 +563,7 @@ static int sgp_grad(gpx_sgp *g, int64_t chunk_cols, double *grad, double *grad_z
     double Suu[GPX_ARD_MAX_D + 2], Srect[GPX_ARD_MAX_D + 2], out[GPX_ARD_MAX_D + 2], wb = 0.0;
     GPX_TRY(tile_reduce(dtype, g->kernel, v.z, M, d, v.params, g->w, nullptr, Mm, ldm, part, Suu, st));
     GPX_HIP(hipMemcpyAsync(&wb, wb_dev, sizeof(double), hipMemcpyDeviceToHost, st));
-    GPX_HIP(hipEventRecord(g->gev[1], st));
+    GPX_TRY(tl.mark(st, GRAD_MM));
     if (grad_z) {
         // Kuu's share, sum_i' 2 Gu[i, i'] dk(z_i, z_i')/dz_ik with 2 Gu = Mm - w w^T: the same kernel on z against itself, C = Mm
         // mirrored to a full matrix, (u, v) = (-w, w).  The pair i' = i adds exactly 0: its difference is 0.
@@ -533,7 +572,7 @@ static int sgp_grad(gpx_sgp *g, int64_t chunk_cols, double *grad, double *grad_z
         GPX_TRY(div_vec(dtype, negw, M, -1.0, st));
         GPX_TRY(transpose(dtype, Mm, ldm, M, M, Mm, ldm, 1, st));
         GPX_TRY(rect_zgrad(dtype, v.kernel, v.z, M, v.z, M, d, v.params, Mm, ldm, negw, g->w, 1.0, col_div, zpart, zacc, st));
-        GPX_HIP(hipEventRecord(g->zev, st));
+        GPX_TRY(tl.mark(st, ZGRAD_KUU));
     }
 
     // 2. the pass over x: sum_ji (P[j, i] + y_j w_i) dk(x_j, z_i), P = K(x_c, z) T
@@ -543,23 +582,23 @@ static int sgp_grad(gpx_sgp *g, int64_t chunk_cols, double *grad, double *grad_z
         const int64_t c0 = c * cols, cc = std::min(cols, n - c0);
         const char *xc = (const char *)v.x + (size_t)c0 * d * es;
         route_hit(RT_SPARSE_CHUNK);
-        GPX_HIP(hipEventRecord(g->gcev[4 * c], st));
+        GPX_TRY(tl.mark(st, SGP_NOBODY));
         GPX_TRY(kmat(dtype, v.kernel, GPX_K, xc, cc, v.z, M, d, v.params, 0.0, GPX_FULL, G, ldm, st));
-        GPX_HIP(hipEventRecord(g->gcev[4 * c + 1], st));
+        GPX_TRY(tl.mark(st, GRAD_BUILD));
         GPX_TRY(product_nt(dtype, cc, M, M, G, Tm, P, ldm, 1.0, st));                 // (T is symmetric)
-        GPX_HIP(hipEventRecord(g->gcev[4 * c + 2], st));
+        GPX_TRY(tl.mark(st, GRAD_PRODUCT));
         if (grad_z) {
             // Gf's share on the same G, P: sum_j (P[j, i] + y_j w_i) dk(z_i, x_j)/dz_ik / s^2, ahead of the reduction, whose
             // host sum waits for the stream
             GPX_TRY(rect_zgrad(dtype, v.kernel, xc, cc, v.z, M, d, v.params, P, ldm, (const char *)g->y + (size_t)c0 * es, g->w, 1.0 / s2,
                                col_div, zpart, zacc, st));
-            GPX_HIP(hipEventRecord(g->zcev[c], st));
+            GPX_TRY(tl.mark(st, ZGRAD_CHUNKS));
         }
         GPX_TRY(rect_reduce(dtype, g->kernel, xc, cc, v.z, M, d, v.params, P, ldm, (const char *)g->y + (size_t)c0 * es, g->w, part, out, st));
-        GPX_HIP(hipEventRecord(g->gcev[4 * c + 3], st));
+        GPX_TRY(tl.mark(st, GRAD_REDUCE));                                          // (behind the z kernels when they run)
         for (int q = 0; q < width; ++q) Srect[q] += out[q];
     }
-    GPX_HIP(hipEventRecord(g->gev[2], st));
+    GPX_TRY(tl.mark(st, SGP_NOBODY));
     if (grad_z) GPX_HIP(hipMemcpyAsync(grad_z, zacc, (size_t)M * d * sizeof(double), hipMemcpyDeviceToHost, st));
     GPX_HIP(hipStreamSynchronize(st));
 
@@ -580,27 +619,12 @@ static int sgp_grad(gpx_sgp *g, int64_t chunk_cols, double *grad, double *grad_z
     const double sumk = ard ? Srect[0] : Srect[3];                                   // tr(T Phi) + w . b
     grad[nkp] = -N / s + (((g->host.yy - wb) - sumk) + N * k00) / (s2 * s);
 
-    float *ms = g->grad_ms;
-    for (int i = 0; i < 5; ++i) ms[i] = 0.0f;
-    GPX_HIP(hipEventElapsedTime(&ms[0], g->gev[0], g->gev[1]));
-    for (int64_t c = 0; c < chunks; ++c)
-        for (int i = 0; i < 3; ++i) {
-            float t = 0.0f;                                                          // (the reduction begins behind the z kernels)
-            GPX_HIP(hipEventElapsedTime(&t, (i == 2 && grad_z) ? g->zcev[c] : g->gcev[4 * c + i], g->gcev[4 * c + i + 1]));
-            ms[1 + i] += t;
-        }
-    GPX_HIP(hipEventElapsedTime(&ms[4], g->gev[0], g->gev[2]));
+    float ms[GRAD_BUCKETS];
+    GPX_TRY(tl.resolve(ms, GRAD_BUCKETS, GRAD_TOTAL));
+    std::copy(ms, ms + 5, g->grad_ms);
+    std::copy(ms + ZGRAD_KUU, ms + GRAD_BUCKETS, g->zgrad_ms);
     g->have_grad = true;
-    if (grad_z) {
-        g->zgrad_ms[0] = g->zgrad_ms[1] = 0.0f;
-        GPX_HIP(hipEventElapsedTime(&g->zgrad_ms[0], g->gev[1], g->zev));
-        for (int64_t c = 0; c < chunks; ++c) {
-            float t = 0.0f;
-            GPX_HIP(hipEventElapsedTime(&t, g->gcev[4 * c + 2], g->zcev[c]));
-            g->zgrad_ms[1] += t;
-        }
-        g->have_zgrad = true;
-    }
+    g->have_zgrad = grad_z != nullptr;
     return GPX_OK;
 }
 
@@ -644,7 +668,6 @@ int gpx_sgp_create(gpx_sgp_t **out, int dtype, int kernel, int64_t n, int64_t m_
     g->ldm = round_up(m_inducing, 16);
     const size_t es = esize(dtype), mm = (size_t)m_inducing * g->ldm * es, mv = (size_t)g->ldm * es;
     int rc = GPX_OK;
-    hipError_t e;
 #define SGP_ALLOC(field, bytes) if (rc == GPX_OK) rc = dev_alloc((void **)&g->field, (bytes), "hipMalloc " #field)
     SGP_ALLOC(x, (size_t)n * d * es);
     SGP_ALLOC(y, (size_t)n * es);
@@ -655,21 +678,9 @@ int gpx_sgp_create(gpx_sgp_t **out, int dtype, int kernel, int64_t n, int64_t m_
     SGP_ALLOC(bacc, (size_t)m_inducing * sizeof(double));
     SGP_ALLOC(scal, sizeof(SgpScal));
 #undef SGP_ALLOC
-    if (rc == GPX_OK) {
-        e = hipStreamCreateWithFlags(&g->st, hipStreamNonBlocking);
+    if (rc == GPX_OK) {                                        // (the events: the timeline makes them as a pass first needs them)
+        const hipError_t e = hipStreamCreateWithFlags(&g->st, hipStreamNonBlocking);
         if (e != hipSuccess) rc = hip_fail(e, "hipStreamCreate", __FILE__, __LINE__);
-    }
-    for (int i = 0; i < 4 && rc == GPX_OK; ++i) {
-        e = hipEventCreate(&g->ev[i]);
-        if (e != hipSuccess) rc = hip_fail(e, "hipEventCreate", __FILE__, __LINE__);
-    }
-    for (int i = 0; i < 3 && rc == GPX_OK; ++i) {
-        e = hipEventCreate(&g->gev[i]);
-        if (e != hipSuccess) rc = hip_fail(e, "hipEventCreate", __FILE__, __LINE__);
-    }
-    if (rc == GPX_OK) {
-        e = hipEventCreate(&g->zev);
-        if (e != hipSuccess) rc = hip_fail(e, "hipEventCreate", __FILE__, __LINE__);
     }
     if (rc != GPX_OK) { gpx_sgp_destroy(g); return rc; }
     *out = g;
@@ -686,12 +697,7 @@ int gpx_sgp_destroy(gpx_sgp_t *g)
                     (void *)g->scal})
         dev_free(b);
     g->work.release();
-    for (int i = 0; i < 4; ++i) if (g->ev[i]) (void)hipEventDestroy(g->ev[i]);
-    for (int i = 0; i < 3; ++i) if (g->gev[i]) (void)hipEventDestroy(g->gev[i]);
-    for (hipEvent_t e : g->cev) (void)hipEventDestroy(e);
-    for (hipEvent_t e : g->gcev) (void)hipEventDestroy(e);
-    if (g->zev) (void)hipEventDestroy(g->zev);
-    for (hipEvent_t e : g->zcev) (void)hipEventDestroy(e);
+    for (hipEvent_t e : g->tl.pool) (void)hipEventDestroy(e);
     if (g->st) (void)hipStreamDestroy(g->st);
     delete g;
     return GPX_OK;
@@ -700,7 +706,7 @@ int gpx_sgp_destroy(gpx_sgp_t *g)
 int gpx_sgp_set_data(gpx_sgp_t *g, const double *x, const double *y, const double *z)
 {
     SGP_ENTER(g);
-    g->fitted = false; g->have_grad = false; g->have_zgrad = false;
+    sgp_unfit(g);
     if (x) { GPX_TRY(upload_f64(g->dtype, g->x, g->n * g->d, x, g->n * g->d, 1, g->n * g->d, g->st)); g->have_x = true; }
     if (y) { GPX_TRY(upload_f64(g->dtype, g->y, g->n, y, g->n, 1, g->n, g->st)); g->have_y = true; }
     if (z) { GPX_TRY(upload_f64(g->dtype, g->z, g->m * g->d, z, g->m * g->d, 1, g->m * g->d, g->st)); g->have_z = true; }
@@ -714,7 +720,6 @@ int gpx_sgp_fit(gpx_sgp_t *g, const double *params, double s, double jitter, int
     GPX_ARG(g->have_x && g->have_y && g->have_z, "no data in the handle (gpx_sgp_set_data)");
     GPX_ARG(s > 0.0 && s <= 1.79769313486231570e308, "s must be positive and finite (the bound divides by s^2)");
     GPX_ARG(jitter >= 0.0 && jitter <= 1.79769313486231570e308, "jitter must be >= 0 and finite");
-    GPX_ARG(chunk_cols >= 0 && chunk_cols % SGP_CHUNK_ALIGN == 0, "chunk_cols must be 0 (automatic) or a multiple of 128");
     for (int i = 0; i < g->nparams; ++i) {
         GPX_ARG(std::isfinite(params[i]), "array must not contain infs or NaNs (kernel parameters)");
         g->params[i] = params[i];
@@ -760,13 +765,10 @@ int gpx_sgp_mean(gpx_sgp_t *g, const double *xo, int64_t m, double *out)
 {
     SGP_ENTER(g);
     SGP_NEED_FIT(g);
-    GPX_ARG(m >= 0 && (m == 0 || (xo && out)), "bad arguments");
-    if (m == 0) return GPX_OK;
-    const size_t es = esize(g->dtype);
     DevBuf dxo, dout;
-    GPX_TRY(dxo.alloc((size_t)m * g->d * es));
-    GPX_TRY(dout.alloc((size_t)m * es));
-    GPX_TRY(sgp_upload_points(g, dxo.p, xo, m));
+    GPX_TRY(sgp_stage_points(g, xo, m, out, &dxo));
+    if (m == 0) return GPX_OK;
+    GPX_TRY(dout.alloc((size_t)m * esize(g->dtype)));
     const SgpView v = sgp_view(g);
     GPX_TRY(gpx_d_mean(g->dtype, v.kernel, dxo.p, m, v.z, g->m, g->d, v.params, g->w, dout.p, (void *)g->st));
     return download_f64(g->dtype, out, m, dout.p, m, 1, m, 0, g->st);
@@ -776,21 +778,19 @@ int gpx_sgp_var(gpx_sgp_t *g, const double *xo, int64_t m, int64_t chunk_rows, d
 {
     SGP_ENTER(g);
     SGP_NEED_FIT(g);
-    GPX_ARG(m >= 0 && (m == 0 || (xo && out)), "bad arguments");
     GPX_ARG(chunk_rows >= 0 && chunk_rows % 128 == 0, "chunk_rows must be 0 (automatic) or a multiple of 128");
+    size_t freeb = 0, totalb = 0;
+    GPX_HIP(hipMemGetInfo(&freeb, &totalb));                   // (the plan's: before the call allocates anything)
+    DevBuf dxo, V, W, dvar, dacc;
+    GPX_TRY(sgp_stage_points(g, xo, m, out, &dxo));
     if (m == 0) return GPX_OK;
     const size_t es = esize(g->dtype);
-    size_t freeb = 0, totalb = 0;
-    GPX_HIP(hipMemGetInfo(&freeb, &totalb));
     int64_t rows = 0, chunks = 0;
     GPX_TRY(var_plan(g->dtype, g->m, m, chunk_rows, freeb / 2, &rows, &chunks, nullptr));      // two blocks a chunk
-    DevBuf dxo, V, W, dvar, dacc;
-    GPX_TRY(dxo.alloc((size_t)m * g->d * es));
     GPX_TRY(V.alloc((size_t)rows * g->ldm * es));
     GPX_TRY(W.alloc((size_t)rows * g->ldm * es));
     GPX_TRY(dvar.alloc((size_t)m * sizeof(double)));
     GPX_TRY(dacc.alloc((size_t)rows * sizeof(double)));
-    GPX_TRY(sgp_upload_points(g, dxo.p, xo, m));
     const SgpView v = sgp_view(g);
     for (int64_t c = 0; c < chunks; ++c) {
         const int64_t r0 = c * rows, rc = std::min(rows, m - r0);
@@ -808,16 +808,14 @@ int gpx_sgp_cov(gpx_sgp_t *g, const double *xo, int64_t m, double *out)
 {
     SGP_ENTER(g);
     SGP_NEED_FIT(g);
-    GPX_ARG(m >= 0 && (m == 0 || (xo && out)), "bad arguments");
+    DevBuf dxo, V, W, C;
+    GPX_TRY(sgp_stage_points(g, xo, m, out, &dxo));
     if (m == 0) return GPX_OK;
     const size_t es = esize(g->dtype);
     const int64_t ldc = round_up(m, 16), ldm = g->ldm;
-    DevBuf dxo, V, W, C;
-    GPX_TRY(dxo.alloc((size_t)m * g->d * es));
     GPX_TRY(V.alloc((size_t)m * ldm * es));
     GPX_TRY(W.alloc((size_t)m * ldm * es));
     GPX_TRY(C.alloc((size_t)m * ldc * es));
-    GPX_TRY(sgp_upload_points(g, dxo.p, xo, m));
     const SgpView v = sgp_view(g);
     GPX_TRY(sgp_two_blocks(g, dxo.p, m, V.p, W.p));
     GPX_TRY(kmat(g->dtype, v.kernel, GPX_K, dxo.p, m, dxo.p, m, g->d, v.params, 0.0, GPX_FULL, C.p, ldc, g->st));
@@ -846,24 +844,7 @@ int gpx_sgp_last_timing(gpx_sgp_t *g, float *ms5)
 {
     GPX_ARG(g != nullptr && ms5, "NULL argument");
     GPX_ARG(g->fitted, "the sparse GP is not fitted");
-    gpx::DeviceGuard guard__(g->device);
-    if (guard__.rc != GPX_OK) return guard__.rc;
-    for (int i = 0; i < 5; ++i) ms5[i] = 0.0f;
-    GPX_HIP(hipEventElapsedTime(&ms5[0], g->ev[0], g->ev[1]));
-    if (g->stage == 1) { ms5[4] = ms5[0]; return GPX_OK; }
-    for (int64_t c = 0; c < g->chunks_timed; ++c) {
-        float a = 0.0f, b = 0.0f;
-        GPX_HIP(hipEventElapsedTime(&a, g->cev[3 * c], g->cev[3 * c + 1]));
-        GPX_HIP(hipEventElapsedTime(&b, g->cev[3 * c + 1], g->cev[3 * c + 2]));
-        ms5[1] += a; ms5[2] += b;
-    }
-    if (g->chunks_timed > 0) {
-        float r = 0.0f;
-        GPX_HIP(hipEventElapsedTime(&r, g->cev[3 * g->chunks_timed - 1], g->ev[2]));   // the slice sum
-        ms5[2] += r;
-    }
-    GPX_HIP(hipEventElapsedTime(&ms5[3], g->ev[2], g->ev[3]));
-    GPX_HIP(hipEventElapsedTime(&ms5[4], g->ev[0], g->ev[3]));
+    for (int i = 0; i < 5; ++i) ms5[i] = g->fit_ms[i];
     return GPX_OK;
 }
 
@@ -872,7 +853,6 @@ int gpx_sgp_grad(gpx_sgp_t *g, int64_t chunk_cols, double *grad)
     SGP_ENTER(g);
     SGP_NEED_FIT(g);
     GPX_ARG(grad, "NULL argument");
-    GPX_ARG(chunk_cols >= 0 && chunk_cols % SGP_CHUNK_ALIGN == 0, "chunk_cols must be 0 (automatic) or a multiple of 128");
     return sgp_grad(g, chunk_cols, grad, nullptr);
 }
 
@@ -881,7 +861,6 @@ int gpx_sgp_grad_z(gpx_sgp_t *g, int64_t chunk_cols, double *grad, double *grad_
     SGP_ENTER(g);
     SGP_NEED_FIT(g);
     GPX_ARG(grad_z, "NULL argument");
-    GPX_ARG(chunk_cols >= 0 && chunk_cols % SGP_CHUNK_ALIGN == 0, "chunk_cols must be 0 (automatic) or a multiple of 128");
     return sgp_grad(g, chunk_cols, grad, grad_z);
 }
 
@@ -906,14 +885,30 @@ int gpx_sgp_set_split(gpx_sgp_t *g, int slices)
     GPX_ARG(g != nullptr, "handle is NULL");
     GPX_ARG(slices >= 0, "slices must be >= 0");
     g->split = slices;
-    g->fitted = false; g->have_grad = false; g->have_zgrad = false;
+    sgp_unfit(g);
     return GPX_OK;
 }
 
 int gpx_debug_sgp_plan(int dtype, int64_t n, int64_t m_inducing, int64_t chunk_cols, int split, size_t free_bytes, int64_t *cols,
                        int64_t *chunks, int *slices, int64_t *slice_cols)
 {
-    return sgp_plan(dtype, n, m_inducing, chunk_cols, split, free_bytes, cols, chunks, slices, slice_cols);
+    SgpPlan pl;
+    GPX_TRY(sgp_plan(SGP_FIT, dtype, n, m_inducing, chunk_cols, split, free_bytes, &pl));
+    if (slices) *slices = pl.slices;
+    if (slice_cols) *slice_cols = pl.slice_cols;
+    if (cols) *cols = pl.cols;
+    if (chunks) *chunks = pl.chunks;
+    return GPX_OK;
+}
+
+int gpx_debug_sgp_grad_plan(int dtype, int64_t n, int64_t m_inducing, int64_t chunk_cols, int split, size_t free_bytes, int64_t *cols,
+                            int64_t *chunks)
+{
+    SgpPlan pl;
+    GPX_TRY(sgp_plan(SGP_GRAD, dtype, n, m_inducing, chunk_cols, split, free_bytes, &pl));
+    if (cols) *cols = pl.cols;
+    if (chunks) *chunks = pl.chunks;
+    return GPX_OK;
 }
 
 // ---- the building blocks ---------------------------------------------------------------------------------------------------

@@ -73,6 +73,36 @@ def _chunk_arg(name, val):
     return val
 
 
+def _native_id(K, d=None):
+    """The library's id of a built-in kernel (a plugin kernel has none); with `d`, an ARD kernel must have that many widths."""
+    kid = getattr(K, "_native_kernel", None)
+    if kid is None:
+        raise NotImplementedError("SparseGP needs a built-in kernel (GaussianKernel, PeriodicKernel, GaussianARDKernel): "
+                                  "plugin kernels are not supported")
+    if d is not None and kid == _lib.KERNEL_GAUSSIAN_ARD and d != K.d:
+        raise ValueError("x has %d dimension(s), the kernel has %d width(s)" % (d, K.d))
+    return kid
+
+
+def _points(name, val, K=None, copy=False):
+    """``(array, d)``: `val` as finite float64 points ``(n,)`` or ``(n, d)``, ``n >= 1`` (`copy`: never a view of `val`); with
+    `K`, checked against it (`_native_id`)."""
+    arr = np.array(val, copy=True, dtype=DTYPE) if copy else np.ascontiguousarray(val, dtype=DTYPE)
+    if arr.ndim not in (1, 2) or arr.shape[0] < 1:
+        raise ValueError("invalid shape for %s: %s" % (name, str(arr.shape)))
+    _check_finite(arr)
+    d = 1 if arr.ndim == 1 else arr.shape[1]
+    if K is not None:
+        _native_id(K, d)
+    return arr, d
+
+
+def _k0_jitter(K, point, dtype_id):
+    """``sqrt(eps_dtype) * k(0)`` at `point` (one row): the automatic jitter, and `greedy_inducing`'s automatic `tol`."""
+    eps = np.finfo(np.float64 if dtype_id == _lib.F64 else np.float32).eps
+    return float(np.sqrt(eps) * np.max(K.diag(point)))
+
+
 class SparseGP(object):
     r"""Sparse GP regression on inducing points.
 
@@ -87,9 +117,7 @@ class SparseGP(object):
     """
 
     def __init__(self, K, x, y, s, z, jitter=None, dtype="float64", device=None, chunk_cols=0):
-        if getattr(K, "_native_kernel", None) is None:
-            raise NotImplementedError("SparseGP needs a built-in kernel (GaussianKernel, PeriodicKernel, GaussianARDKernel): "
-                                      "plugin kernels are not supported")
+        _native_id(K)
         self.K = K
         self._x = self._y = self._z = self._s = None
         self._dtype = _DTYPES[dtype]
@@ -127,10 +155,7 @@ class SparseGP(object):
     @x.setter
     def x(self, val):
         if _changed(val, self._x):
-            arr = np.array(val, copy=True, dtype=DTYPE)
-            if arr.ndim not in (1, 2) or arr.shape[0] < 1:
-                raise ValueError("invalid shape for x: %s" % str(arr.shape))
-            _check_finite(arr)
+            arr = _points("x", val, copy=True)[0]    # (an ARD kernel's widths: `_state`, with the kernel as it is then)
             self._invalidate(data=True)
             self._x = arr
             self._x.flags.writeable = False
@@ -184,7 +209,7 @@ class SparseGP(object):
     @property
     def jitter(self):
         r"""The value in force: the one given, or ``sqrt(eps_dtype) * k(0)`` from the kernel's current parameters."""
-        return self._auto_jitter() if self._jitter is None else self._jitter
+        return _k0_jitter(self.K, self._z[:1], self._dtype) if self._jitter is None else self._jitter
 
     @jitter.setter
     def jitter(self, val):
@@ -243,10 +268,6 @@ class SparseGP(object):
     def _d(self):
         return 1 if self._x.ndim == 1 else self._x.shape[1]
 
-    def _auto_jitter(self):
-        eps = np.finfo(np.float64 if self._dtype == _lib.F64 else np.float32).eps
-        return float(np.sqrt(eps) * np.max(self.K.diag(self._z[:1])))
-
     @staticmethod
     def subset_inducing(x, M, seed=0):
         r"""`M` distinct rows of `x`, in the order ``numpy.random.RandomState(seed).permutation(n)[:M]`` gives: a pure
@@ -276,21 +297,11 @@ class SparseGP(object):
         it was taken), ``trace`` (``count + 1`` values: ``trace[m]`` is :math:`\sum_i k(x_i, x_i) - \mathrm{tr} X` of the
         bound at the first ``m`` picks and jitter 0 -- read it to choose `M`), ``count`` and ``tol``; ``factor=True`` adds
         ``R`` ``(count, n)``, the partial Cholesky factor: ``R.T @ R`` reproduces the picked columns of ``K(x, x)``."""
-        if getattr(K, "_native_kernel", None) is None:
-            raise NotImplementedError("SparseGP needs a built-in kernel (GaussianKernel, PeriodicKernel, GaussianARDKernel): "
-                                      "plugin kernels are not supported")
-        x = np.asarray(x)
-        if x.ndim not in (1, 2) or x.shape[0] < 1:
-            raise ValueError("invalid shape for x: %s" % str(x.shape))
-        xs = np.ascontiguousarray(x, dtype=DTYPE)
-        _check_finite(xs)
-        n, d = xs.shape[0], (1 if xs.ndim == 1 else xs.shape[1])
-        M = int(M)
+        kid = _native_id(K)
+        xs, d = _points("x", x, K)
+        n, M = xs.shape[0], int(M)
         if M < 1 or M > n:
             raise ValueError("invalid value for M: %d (1 .. %d)" % (M, n))
-        kid = K._native_kernel
-        if kid == _lib.KERNEL_GAUSSIAN_ARD and d != K.d:
-            raise ValueError("x has %d dimension(s), the kernel has %d width(s)" % (d, K.d))
         dtype_id = _DTYPES[dtype]
         if tol is not None:
             tol = float(tol)
@@ -301,8 +312,7 @@ class SparseGP(object):
                 raise ValueError("invalid value for first: %s (None, or a row index 0 .. %d)" % (first, n - 1))
             first = int(first)
         if tol is None:
-            eps = np.finfo(np.float64 if dtype_id == _lib.F64 else np.float32).eps
-            tol = float(np.sqrt(eps) * np.max(K.diag(xs[:1])))
+            tol = _k0_jitter(K, xs[:1], dtype_id)
         lib = _lib.load()
         if device is not None:
             _lib.check(lib.gpx_set_device(int(device)))
@@ -325,10 +335,7 @@ class SparseGP(object):
 
     # ---- device plumbing ----
     def _state(self):
-        kid = self.K._native_kernel
-        if kid == _lib.KERNEL_GAUSSIAN_ARD and self._d != self.K.d:
-            raise ValueError("x has %d dimension(s), the kernel has %d width(s)" % (self._d, self.K.d))
-        key = (self._dtype, kid, self._n, self.n_inducing, self._d, self._device)
+        key = (self._dtype, _native_id(self.K, self._d), self._n, self.n_inducing, self._d, self._device)
         if self._dev is None or self._dev.key != key:
             if self._dev is not None:
                 self._dev.close()
@@ -439,21 +446,22 @@ class SparseGP(object):
             return self.elbo, self.delbo_dtheta, dz
         return self.elbo, self.delbo_dtheta
 
+    def _timing(self, entry, st, names):
+        ms = (ctypes.c_float * len(names))()
+        _lib.check(getattr(_lib.load(), entry)(st.handle, ms))
+        return dict(zip(names, list(ms)))
+
     def grad_timing(self):
         """Milliseconds of the last gradient pass (HIP events on the handle's stream): the M x M part, the chunks' kernel
         builds, their products K(x_c, z) T, their tile reductions, total."""
         self._grad()
-        ms = (ctypes.c_float * 5)()
-        _lib.check(_lib.load().gpx_sgp_last_grad_timing(self._fit_pd().handle, ms))
-        return dict(zip(("mm", "build", "product", "reduce", "total"), list(ms)))
+        return self._timing("gpx_sgp_last_grad_timing", self._fit_pd(), ("mm", "build", "product", "reduce", "total"))
 
     def zgrad_timing(self):
         """Milliseconds of the z-gradient's own kernels in the last joint pass: Kuu's share (the pass on `z` against itself),
         the chunks' passes."""
         self._grad_z()
-        ms = (ctypes.c_float * 2)()
-        _lib.check(_lib.load().gpx_sgp_last_zgrad_timing(self._fit_pd().handle, ms))
-        return dict(zip(("kuu", "chunks"), list(ms)))
+        return self._timing("gpx_sgp_last_zgrad_timing", self._fit_pd(), ("kuu", "chunks"))
 
     def optimize(self, maxiter=100, bounds=None, inducing=False):
         r"""Maximise `elbo` over `params` (all positive) with scipy's L-BFGS-B in log-parameters, the inducing inputs held
@@ -467,74 +475,42 @@ class SparseGP(object):
         still one pair per parameter), the object is left at the best ``(params, z)`` evaluated and the dict gains ``z``."""
         from scipy.optimize import minimize
 
-        if inducing:
-            return self._optimize_joint(minimize, maxiter, bounds)
-        x0 = np.log(self.params)
-        bounds = self._log_bounds(bounds, x0.size)
-        best = {"elbo": -np.inf, "params": self.params}
-        state = {"worst": None}
-
-        def negative(u):
-            self.params = np.exp(u)
-            val, grad = self.elbo_and_grad()
-            if not (np.isfinite(val) and np.all(np.isfinite(grad))):
-                # a failed fit: worse than anything seen, flat -- the line search shortens its step
-                ref = state["worst"] if state["worst"] is not None else 0.0
-                return abs(ref) * 10.0 + 1e10, np.zeros_like(u)
-            if val > best["elbo"]:
-                best["elbo"], best["params"] = float(val), self.params
-            state["worst"] = -val if state["worst"] is None else max(state["worst"], -val)
-            return -float(val), -np.asarray(grad, dtype=DTYPE) * np.exp(u)           # d/d log theta = theta d/d theta
-
-        res = minimize(negative, x0, jac=True, method="L-BFGS-B", bounds=bounds, options={"maxiter": int(maxiter)})
-        self.params = best["params"]                 # (a refit there gives the bits of best["elbo"]: fits are repeatable)
-        if not np.isfinite(best["elbo"]):
-            return dict(params=self.params, elbo=DTYPE(-np.inf), nit=int(res.nit), nfev=int(res.nfev), success=False,
-                        message="no trial point had a positive definite fit")
-        msg = res.message.decode() if isinstance(res.message, bytes) else str(res.message)
-        return dict(params=self.params, elbo=DTYPE(best["elbo"]), nit=int(res.nit), nfev=int(res.nfev), success=bool(res.success),
-                    message=msg)
-
-    @staticmethod
-    def _log_bounds(bounds, nparams):
-        if bounds is None:
-            return None
-        bounds = list(bounds)
-        if len(bounds) != nparams:
-            raise ValueError("bounds: one (lo, hi) pair per parameter (%d), got %d" % (nparams, len(bounds)))
-        return [tuple(None if b is None else float(np.log(b)) for b in pair) for pair in bounds]
-
-    def _optimize_joint(self, minimize, maxiter, bounds):
-        """`optimize` over ``(log params, z.ravel())``."""
         npar, zshape = self.params.size, self._z.shape
-        x0 = np.concatenate([np.log(self.params), self._z.ravel()])
-        bounds = self._log_bounds(bounds, npar)
+        x0 = np.concatenate([np.log(self.params), self._z.ravel()]) if inducing else np.log(self.params)
         if bounds is not None:
-            bounds = bounds + [(None, None)] * (x0.size - npar)
+            bounds = list(bounds)
+            if len(bounds) != npar:
+                raise ValueError("bounds: one (lo, hi) pair per parameter (%d), got %d" % (npar, len(bounds)))
+            bounds = [tuple(None if b is None else float(np.log(b)) for b in pair) for pair in bounds] + [(None, None)] * (x0.size - npar)
         best = {"elbo": -np.inf, "params": self.params, "z": self._z}
         state = {"worst": None}
 
         def negative(u):
             self.params = np.exp(u[:npar])
-            self.z = u[npar:].reshape(zshape)
-            val, grad, grad_z = self.elbo_and_grad(inducing=True)
-            if not (np.isfinite(val) and np.all(np.isfinite(grad)) and np.all(np.isfinite(grad_z))):
+            if inducing:
+                self.z = u[npar:].reshape(zshape)
+            val, *grads = self.elbo_and_grad(inducing=True) if inducing else self.elbo_and_grad()
+            if not (np.isfinite(val) and all(np.all(np.isfinite(g)) for g in grads)):
+                # a failed fit: worse than anything seen, flat -- the line search shortens its step
                 ref = state["worst"] if state["worst"] is not None else 0.0
                 return abs(ref) * 10.0 + 1e10, np.zeros_like(u)
             if val > best["elbo"]:
                 best["elbo"], best["params"], best["z"] = float(val), self.params, self._z
             state["worst"] = -val if state["worst"] is None else max(state["worst"], -val)
-            return -float(val), -np.concatenate([np.asarray(grad, dtype=DTYPE) * np.exp(u[:npar]), grad_z.ravel()])
+            grads[0] = np.asarray(grads[0], dtype=DTYPE) * np.exp(u[:npar])             # d/d log theta = theta d/d theta
+            return -float(val), -np.concatenate([np.ravel(g) for g in grads])
 
         res = minimize(negative, x0, jac=True, method="L-BFGS-B", bounds=bounds, options={"maxiter": int(maxiter)})
-        self.params = best["params"]
-        self.z = best["z"]
-        if not np.isfinite(best["elbo"]):
-            return dict(params=self.params, z=self._z, elbo=DTYPE(-np.inf), nit=int(res.nit), nfev=int(res.nfev), success=False,
-                        message="no trial point had a positive definite fit")
+        self.params = best["params"]                 # (a refit there gives the bits of best["elbo"]: fits are repeatable)
+        if inducing:
+            self.z = best["z"]
+        found = bool(np.isfinite(best["elbo"]))
         msg = res.message.decode() if isinstance(res.message, bytes) else str(res.message)
-        return dict(params=self.params, z=self._z, elbo=DTYPE(best["elbo"]), nit=int(res.nit), nfev=int(res.nfev),
-                    success=bool(res.success), message=msg)
+        out = dict(params=self.params, elbo=DTYPE(best["elbo"]), nit=int(res.nit), nfev=int(res.nfev), success=found and bool(res.success),
+                   message=msg if found else "no trial point had a positive definite fit")
+        if inducing:
+            out["z"] = self._z
+        return out
 
     def _get(self, which):
         if which not in self._memoized:
@@ -615,10 +591,7 @@ class SparseGP(object):
     def fit_timing(self):
         """Milliseconds of the last device fit (HIP events on the handle's stream): Kuu and its factor, the chunks' kernel
         builds, the chunks' Gram products (with b and the slice sum), the M x M tail, total."""
-        st = self._fit()
-        ms = (ctypes.c_float * 5)()
-        _lib.check(_lib.load().gpx_sgp_last_timing(st.handle, ms))
-        return dict(zip(("kuu", "build", "gram", "tail", "total"), list(ms)))
+        return self._timing("gpx_sgp_last_timing", self._fit(), ("kuu", "build", "gram", "tail", "total"))
 
 
 def _check_finite(a):

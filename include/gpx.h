@@ -934,6 +934,12 @@ int gpx_sgp_select(int dtype, int kernel, const double *x, int64_t n, int d, con
  * chunk's share cols / P rounded up to 128, *slices = cdiv(cols, width) <= P. */
 int gpx_debug_sgp_plan(int dtype, int64_t n, int64_t m_inducing, int64_t chunk_cols, int split, size_t free_bytes,
                        int64_t *cols, int64_t *chunks, int *slices, int64_t *slice_cols);
+/* the same for the gradient pass (gpx_sgp_grad, gpx_sgp_grad_z), which holds two cols x ldm blocks (ldm = m_inducing rounded
+ * up to 16) where the fit holds one m_inducing x cols: the fit's cols; when the two blocks exceed a quarter of free_bytes an
+ * automatic plan (chunk_cols 0) halves them once, rounded down to 128 and never below 128; what still does not fit is
+ * GPX_ERR_NOMEM.  *chunks = cdiv(n, *cols).  chunk_cols is checked here and in gpx_debug_sgp_plan alike: GPX_ERR_ARG. */
+int gpx_debug_sgp_grad_plan(int dtype, int64_t n, int64_t m_inducing, int64_t chunk_cols, int split, size_t free_bytes,
+                            int64_t *cols, int64_t *chunks);
 /* The new kernels, one building block each (DEVICE pointers, `dtype` unless said otherwise; fixed order, no atomics).
  * gpx_d_sum_slices_lower: out[i, j] = sum_p P[p sP + i ldp + j] for j <= i < n, p ascending, summed in f64, rounded once;
  *   the strict upper triangle of out is not written.

@@ -253,6 +253,53 @@ def test_failed_factorisation():
     assert _lib.load().gpx_sgp_last_zgrad_timing(st.handle, zt()) == _lib.ERR_ARG
 
 
+def _assert_timings(sg, joint):
+    for t, stages in ((sg.fit_timing(), ("kuu", "build", "gram", "tail")), (sg.grad_timing(), ("mm", "build", "product", "reduce"))):
+        assert set(t) == set(stages) | {"total"} and all(v >= 0 for v in t.values()), t
+        assert t["total"] >= max(t[k] for k in stages), t
+    if joint:
+        tz = sg.zgrad_timing()
+        assert set(tz) == {"kuu", "chunks"} and all(v >= 0 for v in tz.values()), tz
+        assert sg.grad_timing()["total"] >= tz["chunks"]
+
+
+@pytest.mark.parametrize("dtype", ["float64", "float32"])
+def test_one_handle_through_alternating_passes_and_chunkings(dtype):
+    """The handle's one pool of events grows (8 chunks), is reused at a smaller size (1 chunk) and grows no further; the work
+    buffer is laid out anew by the fit and by the gradient in turn.  Nothing of that may show in a result."""
+    case = CASES[0]
+    assert case == ("gaussian", 1000, 3, 128)
+    params, x, y, z, _, _ = case_data(case)
+
+    def fresh(chunk_cols):
+        return gp.SparseGP(case_kernel(case[0], params), x, y, S_NOISE, z, jitter=1e-6 if dtype == "float64" else None, dtype=dtype,
+                           chunk_cols=chunk_cols)
+    want8, want1 = fresh(128), fresh(0)
+    sg = fresh(128)
+    assert sg.elbo == want8.elbo and np.isfinite(sg.elbo)                              # 1. a fit in 8 chunks
+    assert same_bits(sg.delbo_dz, want8.delbo_dz) and same_bits(sg.delbo_dtheta, want8.delbo_dtheta)      # 2.
+    _assert_timings(sg, joint=True)
+    sg.chunk_cols = 0                                                                  # 3. one chunk
+    assert sg.elbo == want1.elbo and same_bits(sg.delbo_dtheta, want1.delbo_dtheta)    # 4.
+    assert same_bits(sg.Luu, want1.Luu) and same_bits(sg.LB, want1.LB) and same_bits(sg.c, want1.c)
+    _assert_timings(sg, joint=False)
+    sg.chunk_cols = 128                                                                # 5.
+    assert same_bits(sg.delbo_dz, want8.delbo_dz) and same_bits(sg.delbo_dtheta, want8.delbo_dtheta)      # 6.
+    assert sg.elbo == want8.elbo and same_bits(sg.Luu, want8.Luu) and same_bits(sg.c, want8.c)
+    _assert_timings(sg, joint=True)
+    # a failed fit on the same handle: the rank-deficient z of test_failed_factorisation
+    zz = np.array(z)
+    zz[64:] = zz[:64]
+    sg.jitter, sg.z = 0.0, zz
+    st = sg._fit()
+    assert st.stage == 1
+    t = sg.fit_timing()
+    assert t["total"] == t["kuu"] and t["kuu"] >= 0 and t["build"] == t["gram"] == t["tail"] == 0, t
+    lib = _lib.load()
+    assert lib.gpx_sgp_last_grad_timing(st.handle, (ctypes.c_float * 5)()) == _lib.ERR_ARG
+    assert lib.gpx_sgp_last_zgrad_timing(st.handle, (ctypes.c_float * 2)()) == _lib.ERR_ARG
+
+
 def test_joint_optimize_on_the_device():
     case = CASES[0]
     params, x, y, z, _, _ = case_data(case)

@@ -5,7 +5,7 @@ binding of the new symbols.
 Measured ratios |closed - fd| / (1 + |closed|) (bound 1e-6; step 1e-5 theta_p, fp64), the largest over both jitters:
 gaussian cases <= 2.2e-9, periodic (777, 1, 64) 1.0e-7, ard (1000, 3, 200) 3.4e-10 -- the rectangular ARD derivative is new
 here and agrees as the oracle's Jacobians do."""
-from ctypes import POINTER, c_double, c_float, c_int, c_int64, c_void_p
+from ctypes import POINTER, byref, c_double, c_float, c_int, c_int64, c_size_t, c_void_p
 import re
 
 import numpy as np
@@ -141,3 +141,41 @@ def test_gradient_symbols_are_bound():
     for name in ("delbo_dtheta", "elbo_and_grad", "grad_timing", "optimize"):
         assert hasattr(gp.SparseGP, name)
     assert "optimize" not in gp.__all__ and not hasattr(gp, "delbo_dtheta")
+
+
+# ---- the plan of a gradient pass: host arithmetic (no GPU) ----
+def _plans(n, M, chunk_cols=0, free=1 << 36, dtype=_lib.F64):
+    """(rc, (cols, chunks)) of the gradient's plan and of the fit's, for the same arguments."""
+    lib, out = _lib.load(), []
+    for entry, extra in ((lib.gpx_debug_sgp_plan, (None, None)), (lib.gpx_debug_sgp_grad_plan, ())):
+        cols, chunks = c_int64(0), c_int64(0)
+        rc = entry(dtype, n, M, chunk_cols, 0, free, byref(cols), byref(chunks), *extra)
+        out.append((rc, (cols.value, chunks.value)))
+    return out[::-1]                                                  # (the gradient's ran last: last_error() is its)
+
+
+def test_plan_of_a_gradient_pass():
+    """Two cols x ldm blocks where the fit holds one M x cols: fp64, n = 2^20, M = ldm = 4096."""
+    n, M = 1 << 20, 4096
+    assert _plans(n, M, free=1 << 36) == [(_lib.OK, (16384, 64))] * 2                 # 2^30 bytes within the quarter: the fit's plan
+    # the fit takes 8192 columns; two blocks of 8192 x 4096 doubles are 2^29 bytes, the quarter 2^28: halved once, 2^28 fits
+    assert _plans(n, M, free=1 << 30) == [(_lib.OK, (4096, 256)), (_lib.OK, (8192, 128))]
+    grad, fit = _plans(n, M, chunk_cols=8192, free=1 << 30)                            # explicit chunks are never halved
+    assert grad[0] == _lib.ERR_NOMEM and "two blocks of 8192 columns" in _lib.last_error()
+    assert fit == (_lib.OK, (8192, 128))
+    assert _plans(1000, 128, chunk_cols=128) == [(_lib.OK, (128, 8))] * 2
+    for bad in (100, 129, -128):
+        for rc, _ in _plans(1000, 128, chunk_cols=bad):
+            assert rc == _lib.ERR_ARG and "chunk_cols" in _lib.last_error()
+
+
+def test_gradient_plan_symbol_is_bound():
+    want = (c_int, [c_int, c_int64, c_int64, c_int64, c_int, c_size_t, POINTER(c_int64), POINTER(c_int64)])
+    assert "gpx_debug_sgp_grad_plan" in _lib.EXPORTED_SYMBOLS
+    assert _lib._SIGNATURES["gpx_debug_sgp_grad_plan"][0] is want[0]
+    assert list(_lib._SIGNATURES["gpx_debug_sgp_grad_plan"][1]) == want[1]
+    with open(ROOT + "/include/gpx.h") as f:
+        hdr = f.read()
+    assert re.search(r"int gpx_debug_sgp_grad_plan\(int dtype, int64_t n, int64_t m_inducing, int64_t chunk_cols, int split, "
+                     r"size_t free_bytes,\s+int64_t \*cols, int64_t \*chunks\);", hdr)
+    assert _lib.load().gpx_debug_sgp_grad_plan.argtypes == want[1]
