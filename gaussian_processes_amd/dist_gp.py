@@ -16,6 +16,7 @@ process (`save_fitted`, copy, pickle) raises NotImplementedError: `GP` has them.
 import numpy as np
 
 from . import _lib, multi_gpu
+from ._facade import FAMILIES, native_id
 from .gp import GP, DTYPE, memoprop
 
 __all__ = ["DistributedGP"]
@@ -33,11 +34,11 @@ def _unsupported(name, why="it needs an n x n host copy of a matrix that stays d
 
 
 def _native_kernel_id(K):
-    kid = getattr(K, "_native_kernel", None)
+    kid = native_id(K)
     if kid is None:
         raise TypeError("DistributedGP needs a built-in kernel (GaussianKernel or PeriodicKernel); %s is a Python "
                         "kernel plugin, which gp.GP supports on one GPU" % type(K).__name__)
-    if kid == _lib.KERNEL_GAUSSIAN_ARD:
+    if not FAMILIES[kid].multi_gpu:
         raise NotImplementedError("DistributedGP does not support %s: the multi-GPU fit knows GaussianKernel and "
                                   "PeriodicKernel only; gp.GP has the ARD family on one GPU" % type(K).__name__)
     return kid

@@ -22,6 +22,9 @@ from copy import copy, deepcopy
 import numpy as np
 
 from . import _lib
+from ._facade import (FAMILIES, Handle, ParamsMixin, check_finite, chunk_arg, count_arg, device_grad, device_hessian,
+                      dtype_eps, dtype_id, dtype_name, has_paths, kernel_class, native_id, nonneg_float_arg, points_arg, seed_arg,
+                      select_device, timing)
 from .ext import gp_c
 
 __all__ = ["GP"]
@@ -31,9 +34,6 @@ logger = logging.getLogger("gp.gp")
 DTYPE = np.float64
 EPS = np.finfo(DTYPE).eps
 MIN = np.log(np.exp2(DTYPE(np.finfo(DTYPE).minexp + 4)))   # gp/gp.py:17
-
-_DTYPES = {"float64": _lib.F64, "f64": _lib.F64, np.float64: _lib.F64,
-           "float32": _lib.F32, "f32": _lib.F32, np.float32: _lib.F32}
 
 
 def memoprop(f):
@@ -53,44 +53,21 @@ def memoprop(f):
     return property(fget=fget, fdel=fdel, doc=f.__doc__)
 
 
-class _DeviceState(object):
-    """Owns the gpx_gp handle of one GP; rebuilt whenever shape/dtype change."""
+class _DeviceState(Handle):
+    """Owns the gpx_gp handle of one GP; rebuilt whenever shape/dtype change.  `handle`: an existing fitted gpx_gp handle to
+    wrap (gpx_gp_load, gpx_gp_extend, gpx_gp_remove) instead of a new one."""
+    _destroy = "gpx_gp_destroy"
 
-    def __init__(self, dtype_id, kernel_id, n, d, device):
+    def __init__(self, dtype_id, kernel_id, n, d, device, handle=None):
+        Handle.__init__(self, ptr=handle)
         self.key = (dtype_id, kernel_id, n, d, device)
-        self.handle = ctypes.c_void_p()
-        self.data_version = -1
-        self.params_version = -1
-        self.fit_version = -1
+        self.data_version = self.params_version = self.fit_version = -1
         self.info = None
-        lib = _lib.load()
-        if device is not None:
-            _lib.check(lib.gpx_set_device(int(device)))
-        _lib.check(lib.gpx_gp_create(ctypes.byref(self.handle), dtype_id, kernel_id, n, d))
-
-    @classmethod
-    def adopt(cls, handle, key):
-        """Wrap an existing fitted gpx_gp handle (gpx_gp_load)."""
-        st = cls.__new__(cls)
-        st.key = key
-        st.handle = handle
-        st.data_version = st.params_version = st.fit_version = -1
-        st.info = None
-        return st
-
-    def close(self):
-        if self.handle:
-            _lib.load().gpx_gp_destroy(self.handle)
-            self.handle = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:   # interpreter shutdown
-            pass
+        if handle is None:
+            _lib.check(select_device(device).gpx_gp_create(ctypes.byref(self.handle), dtype_id, kernel_id, n, d))
 
 
-class GP(object):
+class GP(ParamsMixin):
     r"""Gaussian process regression object.
 
     Parameters
@@ -111,7 +88,7 @@ class GP(object):
         self._y = None
         self._s = None
         self._memoized = {}
-        self._dtype = _DTYPES[dtype]
+        self._dtype = dtype_id(dtype)
         self._device = device
         self._dev = None          # _DeviceState, created lazily
         self._version = 0         # bumped by every invalidation
@@ -209,32 +186,8 @@ class GP(object):
             self._invalidate()
             self._s = DTYPE(val)
 
-    @property
-    def params(self):
-        r"""``(kernel parameters..., s)`` (gp/gp.py:199-214)."""
-        kp = self.K.params
-        out = np.empty(kp.size + 1)
-        out[:-1] = kp
-        out[-1] = self._s
-        return out
-
-    @params.setter
-    def params(self, val):
-        if np.any(self.params != val):
-            self._invalidate()
-            self.K.params = val[:-1]
-            self.s = val[-1]
-
     def get_param(self, name):
         return self.s if name == "s" else getattr(self.K, name)
-
-    def set_param(self, name, val):
-        if name == "s":
-            self.s = val
-            return
-        if getattr(self.K, name) != val:      # AttributeError for an unknown name
-            self._invalidate()
-            self.K.set_param(name, val)
 
     # ---- device plumbing ----
     @property
@@ -245,13 +198,8 @@ class GP(object):
     def _d(self):
         return 1 if self._x.ndim == 1 else self._x.shape[1]
 
-    def _is_ard(self):
-        return getattr(self.K, "_native_kernel", None) == _lib.KERNEL_GAUSSIAN_ARD
-
     def _state(self):
-        kid = getattr(self.K, "_native_kernel", None)
-        if kid == _lib.KERNEL_GAUSSIAN_ARD and self._d != self.K.d:
-            raise ValueError("x has %d dimension(s), the kernel has %d width(s)" % (self._d, self.K.d))
+        kid = native_id(self.K, self._d)
         key = (self._dtype, _lib.KERNEL_GAUSSIAN if kid is None else kid, self._n, self._d,
                self._device)
         if self._dev is None or self._dev.key != key:
@@ -282,13 +230,12 @@ class GP(object):
         if st.fit_version == self._version:
             return st
         lib = _lib.load()
-        native = getattr(self.K, "_native_kernel", None) is not None
-        if native:
+        if native_id(self.K) is not None:
             self._sync_params(st)
         else:
             # plugin kernel: its own Python K() on the host, matrix uploaded
             Kxx = np.ascontiguousarray(self.Kxx, dtype=DTYPE)
-            _check_finite(Kxx)
+            check_finite(Kxx)
             _lib.check(lib.gpx_gp_set_K(st.handle, _lib.dptr(Kxx), Kxx.shape[1]))
         info = ctypes.c_int(0)
         _lib.check(lib.gpx_gp_fit(st.handle, ctypes.byref(info)))
@@ -306,7 +253,7 @@ class GP(object):
     @memoprop
     def Kxx(self):
         r"""Kernel covariance matrix :math:`K(x, x) + s^2 I` (gp/gp.py:242-266)."""
-        if getattr(self.K, "_native_kernel", None) is None:
+        if native_id(self.K) is None:
             K = self.K(self._x, self._x)
             K[np.diag_indices_from(K)] += self._s ** 2
             return K
@@ -384,8 +331,7 @@ class GP(object):
         kernels: computed entirely on the device (K^-1 never leaves HBM, the kernel Jacobian
         is never materialised); plugin kernels: the reference's formula with device products."""
         npar = len(self.params)
-        native = getattr(self.K, "_native_kernel", None) is not None
-        if native and (self._d == 1 or self.K._native_kernel in (_lib.KERNEL_GAUSSIAN, _lib.KERNEL_GAUSSIAN_ARD)):
+        if device_grad(native_id(self.K), self._d):
             st = self._fit()
             out = np.empty(npar, dtype=DTYPE)
             _lib.check(_lib.load().gpx_gp_dloglh_dtheta(st.handle, _lib.dptr(out)))
@@ -397,17 +343,17 @@ class GP(object):
 
     def _native_derivs(self):
         """True when the derivative stack can stay on the device (built-in kernel; periodic: 1-D)."""
-        kid = getattr(self.K, "_native_kernel", None)
-        return kid is not None and kid != _lib.KERNEL_GAUSSIAN_ARD and (self._d == 1 or kid == _lib.KERNEL_GAUSSIAN)
+        return device_hessian(native_id(self.K), self._d)
 
     def _no_ard(self, name):
-        if self._is_ard():
+        kid = native_id(self.K)
+        if kid is not None and not FAMILIES[kid].hessian:
             raise NotImplementedError("%s is not implemented for GaussianARDKernel (dloglh_dtheta and dlh_dtheta are)" % name)
 
     @memoprop
     def dlh_dtheta(self):
         r"""Gradient of the marginal likelihood (gp/gp.py:435-465).  Native kernels: device resident."""
-        if self._native_derivs() or self._is_ard():
+        if device_grad(native_id(self.K), self._d):
             # gp_c.pyx:52-67 is lh times gp_c.pyx:34-49 term by term: 0.5 lh (y^T K^-1 dK K^-1 y - tr(K^-1 dK))
             return np.asarray(self.lh * self.dloglh_dtheta, dtype=DTYPE)
         out, Ki = self._nan_or(len(self.params))
@@ -464,11 +410,7 @@ class GP(object):
         return self.K(xo, self._x)
 
     def _xo(self, xo):
-        xo = np.ascontiguousarray(xo, dtype=DTYPE)
-        d = 1 if xo.ndim == 1 else xo.shape[1]
-        if xo.ndim not in (1, 2) or d != self._d:
-            raise ValueError("invalid shape for xo: %s" % str(xo.shape))
-        return xo, xo.shape[0]
+        return points_arg("xo", xo, self._d)
 
     def mean(self, xo):
         r"""Predictive mean :math:`K(x^*, x) K_{xx}^{-1} y`, RW06 eq. 2.23 (gp/gp.py:574-597).
@@ -477,7 +419,7 @@ class GP(object):
         xo, m = self._xo(xo)
         out = np.empty(m, dtype=DTYPE)
         lib = _lib.load()
-        if getattr(self.K, "_native_kernel", None) is not None:
+        if native_id(self.K) is not None:
             _lib.check(lib.gpx_gp_mean(st.handle, _lib.dptr(xo), m, _lib.dptr(out)))
         else:
             Kxox = np.ascontiguousarray(self.Kxox(xo), dtype=DTYPE)
@@ -492,7 +434,7 @@ class GP(object):
         xo, m = self._xo(xo)
         out = np.empty((m, m), dtype=DTYPE)
         lib = _lib.load()
-        if getattr(self.K, "_native_kernel", None) is not None:
+        if native_id(self.K) is not None:
             _lib.check(lib.gpx_gp_cov(st.handle, _lib.dptr(xo), m, _lib.dptr(out)))
         else:
             Kxox = np.ascontiguousarray(self.Kxox(xo), dtype=DTYPE)
@@ -513,13 +455,11 @@ class GP(object):
         result is NOT clamped at zero: where the posterior variance is below the rounding error of the two terms it
         may come out slightly negative."""
         xo, m = self._xo(xo)                         # a bad shape raises before the library is touched
-        chunk_rows = int(chunk_rows)
-        if chunk_rows < 0 or chunk_rows % 128:
-            raise ValueError("invalid value for chunk_rows: %d (0, or a multiple of 128)" % chunk_rows)
+        chunk_rows = chunk_arg("chunk_rows", chunk_rows)
         st = self._fit_pd()
         out = np.empty(m, dtype=DTYPE)
         lib = _lib.load()
-        if getattr(self.K, "_native_kernel", None) is not None:
+        if native_id(self.K) is not None:
             _lib.check(lib.gpx_gp_var(st.handle, _lib.dptr(xo), m, chunk_rows, _lib.dptr(out)))
         else:
             step = max(1, self._VAR_HOST_CHUNK_BYTES // (8 * self._n))
@@ -542,10 +482,8 @@ class GP(object):
     def _grad_args(self, xo, chunk_rows, name):
         """(xo, m, chunk_rows, the fitted state) of a gradient call; every refusal comes before the library is touched."""
         xo, m = self._xo(xo)
-        chunk_rows = int(chunk_rows)
-        if chunk_rows < 0 or chunk_rows % 128:
-            raise ValueError("invalid value for chunk_rows: %d (0, or a multiple of 128)" % chunk_rows)
-        if getattr(self.K, "_native_kernel", None) is None:
+        chunk_rows = chunk_arg("chunk_rows", chunk_rows)
+        if native_id(self.K) is None:
             raise NotImplementedError("%s needs a built-in kernel: the kernel plugin contract (K, jacobian, hessian) has no "
                                       "derivative with respect to the inputs, dk/dx" % name)
         return xo, m, chunk_rows, self._fit_pd()
@@ -601,9 +539,7 @@ class GP(object):
         :math:`\log p_i = \tfrac12 \log k_i - \tfrac12 \alpha_i^2 / k_i - \tfrac12 \log 2\pi`.
         :math:`\sigma_i^2` is the variance of the left-out OBSERVATION, noise included: ``var(x_i, noise=True)`` of the GP
         fitted without point i.  Fills `loo_mean`, `loo_var` and `loo_log_lh`.  ``chunk_rows`` as for `var`."""
-        chunk_rows = int(chunk_rows)
-        if chunk_rows < 0 or chunk_rows % 128:
-            raise ValueError("invalid value for chunk_rows: %d (0, or a multiple of 128)" % chunk_rows)
+        chunk_rows = chunk_arg("chunk_rows", chunk_rows)
         st = self._fit_pd()
         mean, var, log_p = (np.empty(self._n, dtype=DTYPE) for _ in range(3))
         total = ctypes.c_double(0.0)
@@ -658,8 +594,7 @@ class GP(object):
         if st.info != 0:
             out.fill(np.nan)
             return out
-        native = getattr(self.K, "_native_kernel", None) is not None
-        if native and (self._d == 1 or self.K._native_kernel in (_lib.KERNEL_GAUSSIAN, _lib.KERNEL_GAUSSIAN_ARD)):
+        if device_grad(native_id(self.K), self._d):
             total = ctypes.c_double(0.0)
             _lib.check(_lib.load().gpx_gp_loo_grad(st.handle, ctypes.byref(total), _lib.dptr(out)))
             self._memoized.setdefault("loo_log_lh", DTYPE(total.value))
@@ -703,13 +638,11 @@ class GP(object):
         """A GP restored from `save_fitted`: the factor goes straight back into HBM and nothing is
         recomputed (`log_lh`, `mean`, `cov`, ... are served from the loaded state).  `K`: the kernel
         object for a plugin kernel; built-in kernels are rebuilt from the file."""
-        lib = _lib.load()
-        if device is not None:
-            _lib.check(lib.gpx_set_device(int(device)))
+        lib = select_device(device)
         h = ctypes.c_void_p()
         _lib.check(lib.gpx_gp_load(ctypes.byref(h), str(path).encode()))
         try:
-            dt, kid, n, d = ctypes.c_int(), ctypes.c_int(), ctypes.c_int64(), ctypes.c_int()
+            dt, kid, n, d, info = ctypes.c_int(), ctypes.c_int(), ctypes.c_int64(), ctypes.c_int(), ctypes.c_int(0)
             prm = np.zeros(3)
             s = ctypes.c_double()
             _lib.check(lib.gpx_gp_describe(h, ctypes.byref(dt), ctypes.byref(kid), ctypes.byref(n), ctypes.byref(d),
@@ -717,24 +650,31 @@ class GP(object):
             x = np.empty((n.value, d.value), dtype=DTYPE)
             y = np.empty(n.value, dtype=DTYPE)
             _lib.check(lib.gpx_gp_get_xy(h, _lib.dptr(x), _lib.dptr(y)))
-            if K is None:
-                from .kernels import GaussianKernel, PeriodicKernel, GaussianARDKernel
-                if kid.value == _lib.KERNEL_GAUSSIAN_ARD:
-                    full, cnt = np.zeros(1 + _lib.ARD_MAX_D), ctypes.c_int(0)
-                    _lib.check(lib.gpx_gp_get_params(h, _lib.dptr(full), full.size, ctypes.byref(cnt)))
-                    K = GaussianARDKernel(full[0], full[1:cnt.value])
-                else:
-                    K = GaussianKernel(*prm[:2]) if kid.value == _lib.KERNEL_GAUSSIAN else PeriodicKernel(*prm[:3])
-            obj = cls(K, x.ravel() if (d.value == 1 and kid.value != _lib.KERNEL_GAUSSIAN_ARD) else x, y, s=s.value,
-                      dtype="float64" if dt.value == _lib.F64 else "float32", device=device)
-            key = (obj._dtype, kid.value, obj._n, obj._d, obj._device)
-            st = _DeviceState.adopt(h, key)
+            _lib.check(lib.gpx_gp_info(h, ctypes.byref(info)))
+            if K is None and kid.value == _lib.KERNEL_GAUSSIAN_ARD:
+                full, cnt = np.zeros(1 + _lib.ARD_MAX_D), ctypes.c_int(0)
+                _lib.check(lib.gpx_gp_get_params(h, _lib.dptr(full), full.size, ctypes.byref(cnt)))
+                K = kernel_class(kid.value)(full[0], full[1:cnt.value])
+            elif K is None:
+                K = kernel_class(kid.value)(*prm[:FAMILIES[kid.value].nparams(d.value)])
+            if d.value == 1 and kid.value != _lib.KERNEL_GAUSSIAN_ARD:
+                x = x.ravel()
         except Exception:
             lib.gpx_gp_destroy(h)
             raise
-        info = ctypes.c_int(0)
-        _lib.check(lib.gpx_gp_info(st.handle, ctypes.byref(info)))
-        st.info = info.value
+        return cls._adopt_fitted(h, kid.value, info.value, K, x, y, s.value, dt.value, device)
+
+    @classmethod
+    def _adopt_fitted(cls, handle, kid, info, K, x, y, s, dtype_id, device):
+        """A GP on ``(K, x, y, s)`` whose device state is the fitted gpx_gp `handle` (family `kid`, fit status `info`): nothing
+        is uploaded or refitted until an input changes.  The handle is destroyed when the object cannot be built."""
+        try:
+            obj = cls(K, x, y, s=s, dtype=dtype_name(dtype_id), device=device)
+            st = _DeviceState(obj._dtype, kid, obj._n, obj._d, obj._device, handle=handle)
+        except Exception:
+            _lib.load().gpx_gp_destroy(handle)
+            raise
+        st.info = info
         st.data_version = obj._data_version
         st.params_version = st.fit_version = obj._version
         obj._dev = st
@@ -744,9 +684,8 @@ class GP(object):
     def _auto_jitter(self, xo, Kxoxo=None):
         """``sqrt(eps_dtype) * k(0)``: the prior variance from the kernel's closed form, or -- a plugin kernel -- the largest
         diagonal entry of the `Kxoxo` it evaluated."""
-        eps = np.finfo(np.float64 if self._dtype == _lib.F64 else np.float32).eps
         k0 = np.max(self.K.diag(xo[:1])) if Kxoxo is None else np.max(np.diag(Kxoxo))
-        return float(np.sqrt(eps) * k0)
+        return float(np.sqrt(dtype_eps(self._dtype)) * k0)
 
     def sample(self, xo, size=None, seed=None, noise=False, jitter=None):
         r"""Draws from the joint posterior of the function values at `xo`, on the device:
@@ -765,29 +704,15 @@ class GP(object):
         names the pivot and the jitter -- nothing is retried with a larger one.  Memory: ``(m, n)``, ``(m, m)`` and two
         ``(size, m)`` blocks on the device; `m` is bounded by HBM."""
         xo, m = self._xo(xo)                         # every refusal comes before the library is touched
-        if size is None:
-            S = 1
-        else:
-            if isinstance(size, bool) or not isinstance(size, (int, np.integer)) or size < 0:
-                raise ValueError("invalid value for size: %r (None, or an int >= 0)" % (size,))
-            S = int(size)
-        if seed is None:
-            seed = int(np.random.randint(0, 2 ** 32)) << 32 | int(np.random.randint(0, 2 ** 32))
-        elif isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 2 ** 64:
-            raise ValueError("invalid value for seed: %r (None, or an int in [0, 2**64))" % (seed,))
-        seed = int(seed)
-        if jitter is not None:
-            try:
-                jitter = float(jitter)
-            except (TypeError, ValueError):
-                raise ValueError("invalid value for jitter: %r (None, or a float >= 0)" % (jitter,))
-            if not (np.isfinite(jitter) and jitter >= 0):
-                raise ValueError("invalid value for jitter: %r (None, or a finite float >= 0)" % (jitter,))
+        size = count_arg("size", size, 0, none_ok=True)
+        S = 1 if size is None else size
+        seed = seed_arg(seed)
+        jitter = nonneg_float_arg("jitter", jitter, sample_wording=True)
         st = self._fit_pd()
         lib = _lib.load()
         out = np.empty((S, m), dtype=DTYPE)
         info = ctypes.c_int(0)
-        if getattr(self.K, "_native_kernel", None) is not None:
+        if native_id(self.K) is not None:
             _lib.check(lib.gpx_gp_sample(st.handle, _lib.dptr(xo), m, S, seed, int(bool(noise)), -1.0 if jitter is None else jitter,
                                          _lib.dptr(out), ctypes.byref(info)))
             if info.value != 0 and jitter is None:
@@ -832,19 +757,12 @@ class GP(object):
         fused pass, so a draw can be maximised by a gradient-based multi-start optimiser rather than by central differences.
         Not offered: second derivatives, `DistributedGP`, persistence of paths."""
         from .paths import PosteriorPaths
-        if isinstance(size, bool) or not isinstance(size, (int, np.integer)) or size < 0:    # every refusal comes before the library is touched
-            raise ValueError("invalid value for size: %r (an int >= 0)" % (size,))
-        if isinstance(features, bool) or not isinstance(features, (int, np.integer)) or features < 1:
-            raise ValueError("invalid value for features: %r (an int >= 1)" % (features,))
-        if seed is None:
-            seed = int(np.random.randint(0, 2 ** 32)) << 32 | int(np.random.randint(0, 2 ** 32))
-        elif isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 2 ** 64:
-            raise ValueError("invalid value for seed: %r (None, or an int in [0, 2**64))" % (seed,))
-        kid = getattr(self.K, "_native_kernel", None)
-        if kid not in (_lib.KERNEL_GAUSSIAN, _lib.KERNEL_GAUSSIAN_ARD):
+        size = count_arg("size", size, 0)            # every refusal comes before the library is touched
+        features = count_arg("features", features, 1)
+        seed = seed_arg(seed)
+        if not has_paths(native_id(self.K)):
             raise NotImplementedError("sample_paths supports GaussianKernel and GaussianARDKernel (a random-feature prior needs "
                                       "the kernel's spectral density); %s is not supported" % type(self.K).__name__)
-        size, features, seed = int(size), int(features), int(seed)
         st = self._fit_pd()
         h = ctypes.c_void_p()
         _lib.check(_lib.load().gpx_gp_paths_create(st.handle, size, features, seed, ctypes.byref(h)))
@@ -873,31 +791,21 @@ class GP(object):
             raise ValueError("extend needs at least one new point (k = %d)" % k)
         if y_new.shape != (k,):
             raise ValueError("invalid shape for y_new: %s" % str(y_new.shape))
+        K, x, y = deepcopy(self.K), np.concatenate([self._x, x_new]), np.concatenate([self._y, y_new])
         st = self._fit_pd()
         lib = _lib.load()
         h, info = ctypes.c_void_p(), ctypes.c_int(0)
-        if getattr(self.K, "_native_kernel", None) is not None:
+        if native_id(self.K) is not None:
             _lib.check(lib.gpx_gp_extend(st.handle, _lib.dptr(x_new), _lib.dptr(y_new), k, ctypes.byref(h), ctypes.byref(info)))
         else:
             Kno = np.ascontiguousarray(self.K(x_new, self._x), dtype=DTYPE)
             Knn = np.array(self.K(x_new, x_new), dtype=DTYPE, order="C")
             Knn[np.diag_indices_from(Knn)] += self._s ** 2
-            _check_finite(Kno)
-            _check_finite(Knn)
+            check_finite(Kno)
+            check_finite(Knn)
             _lib.check(lib.gpx_gp_extend_from_K(st.handle, _lib.dptr(x_new), _lib.dptr(y_new), k, _lib.dptr(Kno),
                                                 _lib.dptr(Knn), ctypes.byref(h), ctypes.byref(info)))
-        try:
-            obj = type(self)(deepcopy(self.K), np.concatenate([self._x, x_new]), np.concatenate([self._y, y_new]),
-                             s=self._s, dtype="float64" if self._dtype == _lib.F64 else "float32", device=self._device)
-            new =_DeviceState.adopt(h, (obj._dtype, st.key[1], obj._n, obj._d, obj._device))
-        except Exception:
-            lib.gpx_gp_destroy(h)
-            raise
-        new.info = info.value
-        new.data_version = obj._data_version
-        new.params_version = new.fit_version = obj._version
-        obj._dev = new
-        return obj
+        return self._adopt_fitted(h, st.key[1], info.value, K, x, y, self._s, self._dtype, self._device)
 
     # ---- shrinking a fitted GP ----
     def _removal_indices(self, idx):
@@ -946,32 +854,17 @@ class GP(object):
         the source is dropped; ``g = g.remove(i)`` releases it.  A sliding window is
         ``g = g.extend(xn, yn).remove(range(k))``."""
         rm = self._removal_indices(idx)                        # every refusal comes before the library is touched
-        k = int(rm.size)
+        K, x, y = deepcopy(self.K), np.delete(self._x, rm, axis=0), np.delete(self._y, rm)
         st = self._fit_pd()
-        lib = _lib.load()
         h, info = ctypes.c_void_p(), ctypes.c_int(0)
-        _lib.check(lib.gpx_gp_remove(st.handle, rm.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), k, ctypes.byref(h),
-                                     ctypes.byref(info)))
-        try:
-            obj = type(self)(deepcopy(self.K), np.delete(self._x, rm, axis=0), np.delete(self._y, rm),
-                             s=self._s, dtype="float64" if self._dtype == _lib.F64 else "float32", device=self._device)
-            new = _DeviceState.adopt(h, (obj._dtype, st.key[1], obj._n, obj._d, obj._device))
-        except Exception:
-            lib.gpx_gp_destroy(h)
-            raise
-        new.info = info.value
-        new.data_version = obj._data_version
-        new.params_version = new.fit_version = obj._version
-        obj._dev = new
-        return obj
+        _lib.check(_lib.load().gpx_gp_remove(st.handle, rm.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), int(rm.size), ctypes.byref(h),
+                                             ctypes.byref(info)))
+        return self._adopt_fitted(h, st.key[1], info.value, K, x, y, self._s, self._dtype, self._device)
 
     def fit_timing(self):
         """Milliseconds of the last device fit: kernel build, potrf, solve, reductions, total
         (HIP events on the handle's stream)."""
-        st = self._fit()
-        ms = (ctypes.c_float * 5)()
-        _lib.check(_lib.load().gpx_gp_last_timing(st.handle, ms))
-        return dict(zip(("kernel_build", "potrf", "solve", "reduce", "total"), list(ms)))
+        return timing("gpx_gp_last_timing", self._fit().handle, ("kernel_build", "potrf", "solve", "reduce", "total"))
 
     def plot(self, ax=None, xlim=None, color="k", markercolor="r"):
         """Plot the predictive mean +/- one standard deviation (gp/gp.py:664-700)."""
@@ -993,9 +886,3 @@ class GP(object):
 def _c(a):
     """float64 C-contiguous view / copy (what the ext modules' buffer arguments require)."""
     return np.ascontiguousarray(a, dtype=DTYPE)
-
-
-def _check_finite(a):
-    # scipy.linalg.cholesky(..., check_finite=True) (gp/gp.py:294)
-    if not np.isfinite(a).all():
-        raise ValueError("array must not contain infs or NaNs")

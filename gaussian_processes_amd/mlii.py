@@ -16,22 +16,18 @@ import ctypes
 import numpy as np
 
 from . import _lib
+from ._facade import FAMILIES, FAMILY_IDS, Handle, dtype_id, select_device
 
 __all__ = ["log_lh_batch", "best_restart", "BatchEvaluator", "optimize"]
-
-_KERNEL_IDS = {"gaussian": (_lib.KERNEL_GAUSSIAN, 2), "periodic": (_lib.KERNEL_PERIODIC, 3),
-               "gaussian_ard": (_lib.KERNEL_GAUSSIAN_ARD, None)}     # None: (h, w_1 ... w_d), the count comes from x
 
 
 def _kernel_id(kernel, x):
     """(GPX_KERNEL_* id, number of kernel parameters) of a family name for inputs x: (n,) or (n, d)."""
-    kid, nkp = _KERNEL_IDS[kernel]
-    if nkp is None:
-        d = 1 if x.ndim == 1 else x.shape[1]
-        if not 1 <= d <= _lib.ARD_MAX_D:
-            raise ValueError("kernel %r needs between 1 and %d input dimensions (got %d)" % (kernel, _lib.ARD_MAX_D, d))
-        nkp = d + 1
-    return kid, nkp
+    kid = FAMILY_IDS[kernel]
+    d = 1 if x.ndim == 1 else x.shape[1]
+    if kid == _lib.KERNEL_GAUSSIAN_ARD and not 1 <= d <= _lib.ARD_MAX_D:      # (h, w_1 ... w_d): the count comes from x
+        raise ValueError("kernel %r needs between 1 and %d input dimensions (got %d)" % (kernel, _lib.ARD_MAX_D, d))
+    return kid, FAMILIES[kid].nparams(d)
 
 
 CRITERIA = ("log_lh", "loo")
@@ -42,10 +38,11 @@ def _check_criterion(criterion):
         raise ValueError("invalid value for criterion: %r (one of %s)" % (criterion, ", ".join(repr(c) for c in CRITERIA)))
 
 
-class BatchEvaluator(object):
+class BatchEvaluator(Handle):
     """One resident data set, many sweeps: keeps the ``gpx_gp`` handle (x, y and the lock-step
     workspace in HBM) alive between calls, so that an outer optimiser pays the upload and the
     tens-of-GB workspace allocation once.  ``ev(thetas)`` -> log_lh of every row."""
+    _pointer, _destroy = "h", "gpx_gp_destroy"
 
     def __init__(self, x, y, kernel="gaussian", dtype="float64", device=None):
         x = np.ascontiguousarray(x, dtype=np.float64)
@@ -55,11 +52,9 @@ class BatchEvaluator(object):
         d = 1 if x.ndim == 1 else x.shape[1]
         if y.shape != (n,):
             raise ValueError("invalid shape for y: %s" % str(y.shape))
-        self.lib = _lib.load()
-        if device is not None:
-            _lib.check(self.lib.gpx_set_device(int(device)))
-        dt = _lib.F64 if dtype in ("float64", "f64") else _lib.F32
-        self.h = ctypes.c_void_p()
+        dt = dtype_id(dtype)
+        self.lib = select_device(device)
+        Handle.__init__(self)
         self.n = n
         _lib.check(self.lib.gpx_gp_create(ctypes.byref(self.h), dt, self.kid, n, d))
         try:
@@ -109,22 +104,11 @@ class BatchEvaluator(object):
         """loo_log_lh of every row: the values of ``value_and_grad(thetas, criterion="loo")``, from the same call."""
         return self.value_and_grad(thetas, criterion="loo")[0]
 
-    def close(self):
-        if self.h:
-            self.lib.gpx_gp_destroy(self.h)
-            self.h = ctypes.c_void_p()
-
     def __enter__(self):
         return self
 
     def __exit__(self, *exc):
         self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def log_lh_batch(x, y, thetas, kernel="gaussian", dtype="float64", dist=None, device=None, concurrency=None,
@@ -158,10 +142,8 @@ def log_lh_batch(x, y, thetas, kernel="gaussian", dtype="float64", dist=None, de
     if y.shape != (n,):
         raise ValueError("invalid shape for y: %s" % str(y.shape))
     rank, world = (dist.get_rank(), dist.get_world_size()) if dist is not None else (0, 1)
-    lib = _lib.load()
-    if device is not None:
-        _lib.check(lib.gpx_set_device(int(device)))
-    dt = _lib.F64 if dtype in ("float64", "f64") else _lib.F32
+    dt = dtype_id(dtype)
+    lib = select_device(device)
     out = np.zeros(thetas.shape[0], dtype=np.float64)
     eps = np.finfo(np.float64).eps
     mine = list(range(rank, thetas.shape[0], world))
@@ -170,9 +152,9 @@ def log_lh_batch(x, y, thetas, kernel="gaussian", dtype="float64", dist=None, de
     concurrency = max(1, min(int(concurrency), len(mine) or 1))
 
     def work(rows):
-        if device is not None:
-            _lib.check(lib.gpx_set_device(int(device)))         # the current device is per host thread
-        h = ctypes.c_void_p()
+        select_device(device)                                   # the current device is per host thread
+        owner = Handle("gpx_gp_destroy")
+        h = owner.handle
         _lib.check(lib.gpx_gp_create(ctypes.byref(h), dt, kid, n, d))
         try:
             _lib.check(lib.gpx_gp_set_data(h, _lib.dptr(x), _lib.dptr(y)))
@@ -188,11 +170,9 @@ def log_lh_batch(x, y, thetas, kernel="gaussian", dtype="float64", dist=None, de
                 _lib.check(lib.gpx_gp_log_lh(h, ctypes.byref(v)))
                 out[i] = v.value
         finally:
-            lib.gpx_gp_destroy(h)
+            owner.close()
 
     if batched and concurrency == 1:
-        if device is not None:
-            _lib.check(lib.gpx_set_device(int(device)))
         if mine:
             with BatchEvaluator(x, y, kernel=kernel, dtype=dtype, device=device) as ev:
                 out[mine] = ev(thetas[mine])

@@ -35,40 +35,35 @@ group of paths and window of dimensions, where ``2 d + 1`` calls of the paths fo
 Out of scope: second derivatives, the periodic family (an exact Fourier-series prior exists for it), plugin kernels,
 `DistributedGP`, and persistence -- a paths object is regenerated from its seed, not copied or pickled.
 """
-import ctypes
-
 import numpy as np
 
 from . import _lib
+from ._facade import DTYPE, Handle, chunk_arg, points_arg, timing
 
 __all__ = ["PosteriorPaths"]
 
-DTYPE = np.float64
 
-
-class PosteriorPaths(object):
+class PosteriorPaths(Handle):
     """`size` posterior function draws of a fitted `GP` (made by `GP.sample_paths`); call it with test points.
 
     Attributes: ``size``, ``features``, ``seed``, ``n``, ``d``.  The object owns its device state and does not refer to the
-    `GP` again: the GP may be modified, refitted or deleted."""
+    `GP` again: the GP may be modified, refitted or deleted.  `close` releases the device state now (`__del__` does it
+    otherwise)."""
+    _pointer, _destroy = "_handle", "gpx_paths_destroy"
 
     def __init__(self, handle, size, features, seed, n, d, ndim):
-        self._handle = handle
+        Handle.__init__(self, ptr=handle)
         self.size, self.features, self.seed, self.n, self.d = size, features, seed, n, d
         self._ndim = ndim              # of the GP's x: 1 -> xo is (m,), 2 -> (m, d)
 
     def _checked(self, xo, chunk_rows):
         """`xo` as a contiguous float64 array and its number of points, after the refusals `__call__`, `grad` and
         `value_and_grad` share -- every one of them comes before the library is touched."""
-        xo = np.ascontiguousarray(xo, dtype=DTYPE)
-        d = 1 if xo.ndim == 1 else xo.shape[1] if xo.ndim == 2 else -1
-        if xo.ndim not in (1, 2) or d != self.d or (xo.ndim == 1 and self._ndim == 2):
-            raise ValueError("invalid shape for xo: %s" % str(xo.shape))
-        if isinstance(chunk_rows, bool) or not isinstance(chunk_rows, (int, np.integer)) or chunk_rows < 0 or chunk_rows % 128:
-            raise ValueError("invalid value for chunk_rows: %r (0, or a multiple of 128)" % (chunk_rows,))
+        xo, m = points_arg("xo", xo, self.d, self._ndim)
+        chunk_arg("chunk_rows", chunk_rows, strict=True)
         if not self._handle:
             raise ValueError("the paths have been closed")
-        return xo, xo.shape[0]
+        return xo, m
 
     def __call__(self, xo, chunk_rows=0):
         """The draws at `xo` (``(m,)`` for 1-D inputs or ``(m, d)``): ``(size, m)`` float64.  ``chunk_rows``: test points per
@@ -110,21 +105,7 @@ class PosteriorPaths(object):
         sweeps, the rest, total."""
         if not self._handle:
             raise ValueError("the paths have been closed")
-        ms = (ctypes.c_float * 4)()
-        _lib.check(_lib.load().gpx_debug_paths_timing(self._handle, ms))
-        return dict(zip(("features_products", "sweeps", "rest", "total"), list(ms)))
-
-    def close(self):
-        """Release the device state now (`__del__` does it otherwise)."""
-        if self._handle:
-            _lib.load().gpx_paths_destroy(self._handle)
-            self._handle = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:   # interpreter shutdown
-            pass
+        return timing("gpx_debug_paths_timing", self._handle, ("features_products", "sweeps", "rest", "total"))
 
     def _no_copy(self, *args, **kwargs):
         raise NotImplementedError("PosteriorPaths holds device state and is not copied or pickled: regenerate it from the seed, "

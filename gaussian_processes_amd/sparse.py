@@ -23,7 +23,8 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from .gp import DTYPE, _DTYPES
+from ._facade import (DTYPE, Handle, ParamsMixin, check_finite, chunk_arg, dtype_eps, dtype_id, native_id, nonneg_float_arg,
+                      points_arg, select_device, timing)
 
 __all__ = ["SparseGP"]
 
@@ -31,31 +32,16 @@ ELBO_TERMS = ("logdet", "noise", "fit", "quad", "trace")
 _STAGE_NAMES = {1: "Kuu = K(z, z) + jitter I", 2: "B = I + Luu^-1 Phi Luu^-T / s^2"}
 
 
-class _SparseState(object):
+class _SparseState(Handle):
     """Owns the gpx_sgp handle of one SparseGP; rebuilt whenever a shape, the dtype or the kernel family changes."""
+    _destroy = "gpx_sgp_destroy"
 
     def __init__(self, dtype_id, kernel_id, n, m, d, device):
+        Handle.__init__(self)
         self.key = (dtype_id, kernel_id, n, m, d, device)
-        self.handle = ctypes.c_void_p()
-        self.xy_version = -1
-        self.z_version = -1
-        self.fit_version = -1
+        self.xy_version = self.z_version = self.fit_version = -1
         self.stage = self.pivot = None
-        lib = _lib.load()
-        if device is not None:
-            _lib.check(lib.gpx_set_device(int(device)))
-        _lib.check(lib.gpx_sgp_create(ctypes.byref(self.handle), dtype_id, kernel_id, n, m, d))
-
-    def close(self):
-        if self.handle:
-            _lib.load().gpx_sgp_destroy(self.handle)
-            self.handle = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:   # interpreter shutdown
-            pass
+        _lib.check(select_device(device).gpx_sgp_create(ctypes.byref(self.handle), dtype_id, kernel_id, n, m, d))
 
 
 def _changed(val, cur):
@@ -66,21 +52,12 @@ def _changed(val, cur):
     return val.shape != cur.shape or bool(np.any(val != cur))
 
 
-def _chunk_arg(name, val):
-    val = int(val)
-    if val < 0 or val % 128:
-        raise ValueError("invalid value for %s: %d (0, or a multiple of 128)" % (name, val))
-    return val
-
-
 def _native_id(K, d=None):
     """The library's id of a built-in kernel (a plugin kernel has none); with `d`, an ARD kernel must have that many widths."""
-    kid = getattr(K, "_native_kernel", None)
+    kid = native_id(K, d)
     if kid is None:
         raise NotImplementedError("SparseGP needs a built-in kernel (GaussianKernel, PeriodicKernel, GaussianARDKernel): "
                                   "plugin kernels are not supported")
-    if d is not None and kid == _lib.KERNEL_GAUSSIAN_ARD and d != K.d:
-        raise ValueError("x has %d dimension(s), the kernel has %d width(s)" % (d, K.d))
     return kid
 
 
@@ -90,7 +67,7 @@ def _points(name, val, K=None, copy=False):
     arr = np.array(val, copy=True, dtype=DTYPE) if copy else np.ascontiguousarray(val, dtype=DTYPE)
     if arr.ndim not in (1, 2) or arr.shape[0] < 1:
         raise ValueError("invalid shape for %s: %s" % (name, str(arr.shape)))
-    _check_finite(arr)
+    check_finite(arr)
     d = 1 if arr.ndim == 1 else arr.shape[1]
     if K is not None:
         _native_id(K, d)
@@ -99,11 +76,10 @@ def _points(name, val, K=None, copy=False):
 
 def _k0_jitter(K, point, dtype_id):
     """``sqrt(eps_dtype) * k(0)`` at `point` (one row): the automatic jitter, and `greedy_inducing`'s automatic `tol`."""
-    eps = np.finfo(np.float64 if dtype_id == _lib.F64 else np.float32).eps
-    return float(np.sqrt(eps) * np.max(K.diag(point)))
+    return float(np.sqrt(dtype_eps(dtype_id)) * np.max(K.diag(point)))
 
 
-class SparseGP(object):
+class SparseGP(ParamsMixin):
     r"""Sparse GP regression on inducing points.
 
     Parameters
@@ -120,7 +96,7 @@ class SparseGP(object):
         _native_id(K)
         self.K = K
         self._x = self._y = self._z = self._s = None
-        self._dtype = _DTYPES[dtype]
+        self._dtype = dtype_id(dtype)
         self._device = device
         self._dev = None
         self._version = 0          # bumped by every invalidation
@@ -170,7 +146,7 @@ class SparseGP(object):
             arr = np.array(val, copy=True, dtype=DTYPE)
             if arr.shape != (self._x.shape[0],):
                 raise ValueError("invalid shape for y: %s" % str(arr.shape))
-            _check_finite(arr)
+            check_finite(arr)
             self._invalidate(data=True)
             self._y = arr
             self._y.flags.writeable = False
@@ -189,7 +165,7 @@ class SparseGP(object):
                 raise ValueError("invalid shape for z: %s (x has %d dimension(s))" % (str(arr.shape), self._d))
             if arr.shape[0] < 1:
                 raise ValueError("need at least one inducing point (M >= 1)")
-            _check_finite(arr)
+            check_finite(arr)
             self._invalidate(z=True)
             self._z = arr
             self._z.flags.writeable = False
@@ -213,10 +189,7 @@ class SparseGP(object):
 
     @jitter.setter
     def jitter(self, val):
-        if val is not None:
-            val = float(val)
-            if not (val >= 0.0) or not np.isfinite(val):
-                raise ValueError("invalid value for jitter: %s (None, or a finite number >= 0)" % val)
+        val = nonneg_float_arg("jitter", val)
         if val != self._jitter:
             self._invalidate()
             self._jitter = val
@@ -227,34 +200,10 @@ class SparseGP(object):
 
     @chunk_cols.setter
     def chunk_cols(self, val):
-        val = _chunk_arg("chunk_cols", val)
+        val = chunk_arg("chunk_cols", val)
         if val != self._chunk_cols:
             self._invalidate()
             self._chunk_cols = val
-
-    @property
-    def params(self):
-        r"""``(kernel parameters..., s)``, as `GP.params`."""
-        kp = self.K.params
-        out = np.empty(kp.size + 1)
-        out[:-1] = kp
-        out[-1] = self._s
-        return out
-
-    @params.setter
-    def params(self, val):
-        if np.any(self.params != val):
-            self._invalidate()
-            self.K.params = val[:-1]
-            self.s = val[-1]
-
-    def set_param(self, name, val):
-        if name == "s":
-            self.s = val
-            return
-        if getattr(self.K, name) != val:
-            self._invalidate()
-            self.K.set_param(name, val)
 
     @property
     def n_inducing(self):
@@ -302,25 +251,20 @@ class SparseGP(object):
         n, M = xs.shape[0], int(M)
         if M < 1 or M > n:
             raise ValueError("invalid value for M: %d (1 .. %d)" % (M, n))
-        dtype_id = _DTYPES[dtype]
-        if tol is not None:
-            tol = float(tol)
-            if not (tol >= 0.0) or not np.isfinite(tol):
-                raise ValueError("invalid value for tol: %s (None, or a finite number >= 0)" % tol)
+        dt = dtype_id(dtype)
+        tol = nonneg_float_arg("tol", tol)
         if first is not None:
             if int(first) != first or not 0 <= int(first) < n:
                 raise ValueError("invalid value for first: %s (None, or a row index 0 .. %d)" % (first, n - 1))
             first = int(first)
         if tol is None:
-            tol = _k0_jitter(K, xs[:1], dtype_id)
-        lib = _lib.load()
-        if device is not None:
-            _lib.check(lib.gpx_set_device(int(device)))
+            tol = _k0_jitter(K, xs[:1], dt)
+        lib = select_device(device)
         p = np.ascontiguousarray(K.params, dtype=DTYPE)
         index, pivot, trace = np.empty(M, dtype=np.int64), np.empty(M, dtype=DTYPE), np.empty(M + 1, dtype=DTYPE)
         R = np.empty((M, n), dtype=DTYPE) if factor else None
         count = ctypes.c_int64(0)
-        _lib.check(lib.gpx_sgp_select(dtype_id, kid, _lib.dptr(xs), n, d, _lib.dptr(p), M, tol, -1 if first is None else first,
+        _lib.check(lib.gpx_sgp_select(dt, kid, _lib.dptr(xs), n, d, _lib.dptr(p), M, tol, -1 if first is None else first,
                                       index.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), _lib.dptr(pivot), _lib.dptr(trace),
                                       None if R is None else _lib.dptr(R), ctypes.byref(count)))
         c = int(count.value)
@@ -446,22 +390,17 @@ class SparseGP(object):
             return self.elbo, self.delbo_dtheta, dz
         return self.elbo, self.delbo_dtheta
 
-    def _timing(self, entry, st, names):
-        ms = (ctypes.c_float * len(names))()
-        _lib.check(getattr(_lib.load(), entry)(st.handle, ms))
-        return dict(zip(names, list(ms)))
-
     def grad_timing(self):
         """Milliseconds of the last gradient pass (HIP events on the handle's stream): the M x M part, the chunks' kernel
         builds, their products K(x_c, z) T, their tile reductions, total."""
         self._grad()
-        return self._timing("gpx_sgp_last_grad_timing", self._fit_pd(), ("mm", "build", "product", "reduce", "total"))
+        return timing("gpx_sgp_last_grad_timing", self._fit_pd().handle, ("mm", "build", "product", "reduce", "total"))
 
     def zgrad_timing(self):
         """Milliseconds of the z-gradient's own kernels in the last joint pass: Kuu's share (the pass on `z` against itself),
         the chunks' passes."""
         self._grad_z()
-        return self._timing("gpx_sgp_last_zgrad_timing", self._fit_pd(), ("kuu", "chunks"))
+        return timing("gpx_sgp_last_zgrad_timing", self._fit_pd().handle, ("kuu", "chunks"))
 
     def optimize(self, maxiter=100, bounds=None, inducing=False):
         r"""Maximise `elbo` over `params` (all positive) with scipy's L-BFGS-B in log-parameters, the inducing inputs held
@@ -549,11 +488,7 @@ class SparseGP(object):
 
     # ---- predictions ----
     def _xo(self, xo):
-        xo = np.ascontiguousarray(xo, dtype=DTYPE)
-        d = 1 if xo.ndim == 1 else (xo.shape[1] if xo.ndim == 2 else -1)
-        if xo.ndim not in (1, 2) or d != self._d:
-            raise ValueError("invalid shape for xo: %s" % str(xo.shape))
-        return xo, xo.shape[0]
+        return points_arg("xo", xo, self._d)
 
     def mean(self, xo):
         r"""Predictive mean :math:`k(x^*, z) L_{uu}^{-\top} L_B^{-\top} c / s`, ``(m,)``: one fused device pass."""
@@ -567,7 +502,7 @@ class SparseGP(object):
         r"""Predictive variance, the diagonal of `cov(xo)`, ``(m,)``, in row chunks of `xo` (``chunk_rows``: 0 or a
         multiple of 128).  ``noise=True`` adds :math:`s^2`.  Not clamped at zero."""
         xo, m = self._xo(xo)
-        chunk_rows = _chunk_arg("chunk_rows", chunk_rows)
+        chunk_rows = chunk_arg("chunk_rows", chunk_rows)
         st = self._fit_pd()
         out = np.empty(m, dtype=DTYPE)
         _lib.check(_lib.load().gpx_sgp_var(st.handle, _lib.dptr(xo), m, chunk_rows, _lib.dptr(out)))
@@ -591,9 +526,4 @@ class SparseGP(object):
     def fit_timing(self):
         """Milliseconds of the last device fit (HIP events on the handle's stream): Kuu and its factor, the chunks' kernel
         builds, the chunks' Gram products (with b and the slice sum), the M x M tail, total."""
-        return self._timing("gpx_sgp_last_timing", self._fit(), ("kuu", "build", "gram", "tail", "total"))
-
-
-def _check_finite(a):
-    if not np.isfinite(a).all():
-        raise ValueError("array must not contain infs or NaNs")
+        return timing("gpx_sgp_last_timing", self._fit().handle, ("kuu", "build", "gram", "tail", "total"))

@@ -1033,6 +1033,20 @@ def test_save_load_fitted_roundtrip(tmp_path, dtype, monkeypatch):
         gp.GP.load_fitted(bad)
 
 
+def test_extend_and_remove_adopt_the_fitted_handle():
+    """The results of `extend` and `remove` carry a handle that is current (what `load_fitted` asserts above): reading
+    `log_lh` does not refit."""
+    n, d, k = 200, 2, 3
+    X, y, _ = orc.synth_inputs(n + k, d, 1)
+    g = gp.GP(gp.GaussianKernel(1.1, 0.9), X[:n], y[:n], s=0.8)
+    for h, rows in ((g.extend(X[n:], y[n:]), n + k), (g.remove([0, 7, n - 1]), n - k)):
+        assert h._dev.fit_version == h._version and h._dev.info == 0 and h.x.shape == (rows, d)
+        assert h._dev.data_version == h._data_version and h._dev.params_version == h._version
+        dev, fit_version = h._dev, h._dev.fit_version
+        assert np.isfinite(h.log_lh)
+        assert h._dev is dev and h._dev.fit_version == fit_version
+
+
 def test_out_of_core_kernel_build_into_memmap(tmp_path, monkeypatch):
     """gpx_kmat_host streams row panels (panel size forced to 64 rows: 11 panels, ragged last) into the
     caller's buffer -- here a numpy.memmap, i.e. a matrix that never has to fit in HBM or host RAM."""
