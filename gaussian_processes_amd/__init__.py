@@ -15,12 +15,13 @@ import logging
 from . import ext
 from .gp import GP
 from .sparse import SparseGP
+from .iterative import IterativeGP
 from .paths import PosteriorPaths
 from .dist_gp import DistributedGP
 from .kernels import Kernel, GaussianKernel, PeriodicKernel, GaussianARDKernel
 from . import kernels
 
-__all__ = ["ext", "GP", "SparseGP", "DistributedGP", "PosteriorPaths", "Kernel", "PeriodicKernel", "GaussianKernel", "GaussianARDKernel"]
+__all__ = ["ext", "GP", "SparseGP", "IterativeGP", "DistributedGP", "PosteriorPaths", "Kernel", "PeriodicKernel", "GaussianKernel", "GaussianARDKernel"]
 
 logger = logging.getLogger("gp")
 logger.setLevel("INFO")

@@ -49,7 +49,7 @@ int  ensure_device();   // GPX_OK when a GPU is usable
 enum Route { RT_TRSV_OPS = 0, RT_TRSV_STEPS = 1, RT_PANEL_RES = 2, RT_PANEL_CHAIN = 3, RT_FIT_RIDE = 4,
              RT_FIT_TWO_SOLVES = 5, RT_GEMM_FAST = 6, RT_GEMM_GENERIC = 7, RT_SYRK_EXACT = 8, RT_SYRK_PATCH = 9,
              RT_MG_BCAST_ONE = 10, RT_MG_BCAST_SAG = 11, RT_FIT_OPS_AHEAD = 12, RT_TRSM_OPS = 13, RT_POTRF_PAIR = 14, RT_VAR_CHUNK = 15, RT_LOO_CHUNK = 16,
-             RT_TRSM_L_OPS = 17, RT_GRAD_CHUNK = 18, RT_EXTEND = 19, RT_SAMPLE = 20, RT_KAPPLY_FUSED = 21, RT_KAPPLY_GEMM = 22, RT_PATHS_GRAD_CHUNK = 23, RT_REMOVE = 24, RT_SPARSE_CHUNK = 25, RT_SELECT_STEP = 26, RT_COUNT = 27 };
+             RT_TRSM_L_OPS = 17, RT_GRAD_CHUNK = 18, RT_EXTEND = 19, RT_SAMPLE = 20, RT_KAPPLY_FUSED = 21, RT_KAPPLY_GEMM = 22, RT_PATHS_GRAD_CHUNK = 23, RT_REMOVE = 24, RT_SPARSE_CHUNK = 25, RT_SELECT_STEP = 26, RT_CG_ITER = 27, RT_COUNT = 28 };
 void route_hit(int route);
 
 // LAPACK-style info of a factorisation as the host sees it: > 0 "not positive definite" (the caller's business),
@@ -91,7 +91,7 @@ struct EventPool {
 // ---- live per-kernel-class timing (HIP events around each launch; off by default) ----
 enum ProfClass { PC_KMAT = 0, PC_GEMM = 1, PC_POTRF_DIAG = 2, PC_TRSM_ROWS = 3, PC_TRSV = 4,
                  PC_MEAN = 5, PC_REDUCE = 6, PC_GEMM_SKINNY = 7, PC_GEMM_GENERIC = 8, PC_GEMM_PANEL = 9, PC_GEMM_N64 = 10,
-                 PC_TRANSPOSE = 11, PC_PRED_GRAD = 12, PC_EXTEND = 13, PC_RANDN = 14, PC_RFF = 15, PC_KAPPLY = 16, PC_KAPPLY_GRAD = 17, PC_CHOL_DELETE = 18, PC_SPARSE_GRAM = 19, PC_SPARSE_GRAD = 20, PC_SPARSE_ZGRAD = 21, PC_SELECT = 22, PC_COUNT = 23 };
+                 PC_TRANSPOSE = 11, PC_PRED_GRAD = 12, PC_EXTEND = 13, PC_RANDN = 14, PC_RFF = 15, PC_KAPPLY = 16, PC_KAPPLY_GRAD = 17, PC_CHOL_DELETE = 18, PC_SPARSE_GRAM = 19, PC_SPARSE_GRAD = 20, PC_SPARSE_ZGRAD = 21, PC_SELECT = 22, PC_CG = 23, PC_COUNT = 24 };
 extern bool g_prof_on;
 // the registry is shared by all host threads (mutex inside); a scope ends its OWN record
 int  prof_begin(int cls, double work, hipStream_t st);    // record index, -1 when nothing was recorded

@@ -1,4 +1,4 @@
-// gpx_gp_internal.h -- the fitted-GP handle, shared by gpx_gp.hip and gpx_deriv.hip (not part of the ABI).
+// gpx_gp_internal.h -- the fitted-GP handle, shared by gpx_gp.hip and gpx_deriv.hip, and what the other handles share (not part of the ABI).
 #pragma once
 #include "gpx_common.h"
 #include <cstddef>
@@ -64,6 +64,62 @@ static inline void gp_unfit(gpx_gp *g) { g->fitted = false; g->have_kii = false;
 // backward sweep is left; otherwise both sweeps from y), logdet, y^T alpha, ev[3], ev[4], fitted.  info (may be null):
 // waits for all of it and takes potrf's verdict to the host
 int gp_finish_fit(gpx_gp *g, bool rhs_is_row_n, int *info);
+// The times of one pass on the handle's stream.  A pass is a sequence of marks: mark() records the next event of a grow-only
+// pool and books the interval since the mark before it to a bucket, or to nobody (TL_NOBODY); resolve(), behind the pass's
+// last synchronisation, adds the intervals up.  The passes of one handle never overlap: they share the pool
+// (the sparse GP's fit and gradient, the iterative GP's solves).
+constexpr int TL_NOBODY = -1;
+struct PassTimeline {
+    std::vector<hipEvent_t> pool;      // grow-only; the handle's destroy destroys them
+    std::vector<int> bucket;           // of the marks of the current pass
+    PassTimeline &begin() { bucket.clear(); return *this; }
+    int mark(hipStream_t st, int b)
+    {
+        if (bucket.size() == pool.size()) {
+            hipEvent_t e;
+            GPX_HIP(hipEventCreate(&e));
+            pool.push_back(e);
+        }
+        GPX_HIP(hipEventRecord(pool[bucket.size()], st));
+        bucket.push_back(b);
+        return GPX_OK;
+    }
+    // ms[b] (b < count) = the sum of bucket b's intervals; ms[total] = the first mark to the last
+    int resolve(float *ms, int count, int total) const
+    {
+        for (int i = 0; i < count; ++i) ms[i] = 0.0f;
+        for (size_t i = 1; i < bucket.size(); ++i) {
+            if (bucket[i] == TL_NOBODY) continue;
+            float t = 0.0f;
+            GPX_HIP(hipEventElapsedTime(&t, pool[i - 1], pool[i]));
+            ms[bucket[i]] += t;
+        }
+        if (bucket.size() > 1) GPX_HIP(hipEventElapsedTime(&ms[total], pool[0], pool[bucket.size() - 1]));
+        return GPX_OK;
+    }
+    // For a pass of many marks: behind a synchronisation, ADD the intervals so far to acc[b] (TL_NOBODY's only to acc[total], which
+    // gets every interval) and begin again from the last mark, so that the pass never holds more events than lie between two folds
+    int fold(float *acc, int total)
+    {
+        for (size_t i = 1; i < bucket.size(); ++i) {
+            float t = 0.0f;
+            GPX_HIP(hipEventElapsedTime(&t, pool[i - 1], pool[i]));
+            if (bucket[i] != TL_NOBODY) acc[bucket[i]] += t;
+            acc[total] += t;
+        }
+        if (bucket.size() > 1) { std::swap(pool[0], pool[bucket.size() - 1]); bucket.resize(1); }
+        return GPX_OK;
+    }
+};
+// The greedy selection of gpx_sgp_select on points that are ALREADY on the device, for a caller that keeps R there (gpx_select.hip;
+// the iterative GP's preconditioner).  kernel: GPX_KERNEL_GAUSSIAN or GPX_KERNEL_PERIODIC with `params` (HOST) -- the ARD family
+// passes its scaled points and isotropic constants.  block: select_block_bytes() of device memory, the caller's; *R: where the
+// factor lies inside it, m_max x *ldr in the dtype (*ldr = round_up(n, 128); columns [n, *ldr) are never written), *count rows
+// valid.  The launches, their order and therefore every bit are gpx_sgp_select's with first = -1.  Synchronises `st`; the
+// profile record and the route hits are gpx_sgp_select's.
+size_t select_block_bytes(int dtype, int64_t n, int64_t m_max);
+int select_on_device(int dtype, int kernel, const void *x_dev, int64_t n, int d, const double *params, int64_t m_max, double tol, void *block,
+                     hipStream_t st, int64_t *count, void **R, int64_t *ldr);
 // kernel parameters of a family at dimension d
 static inline int nparams_of(int kernel, int d) { return kernel == GPX_KERNEL_GAUSSIAN_ARD ? 1 + d : (kernel == GPX_KERNEL_PERIODIC ? 3 : 2); }
 // The points and the two isotropic constants this handle's launches use: its own (x, params), or for the ARD family the

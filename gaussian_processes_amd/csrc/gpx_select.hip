@@ -28,6 +28,10 @@
 // bytes), whose total is also what the call tests against the free memory:
 //   x (n, d)  [ARD: scaled in place] | R  m_max x ldr | dres  n doubles | picked  n bytes
 //   | the partials: nwg doubles | nwg int64 | nwg doubles | index | pivot | trace | coef | the state word block
+//
+// Two callers, ONE launch sequence (select_run): gpx_sgp_select, which uploads x and downloads the results, and
+// select_on_device (gpx_gp_internal.h) for a handle whose points are resident and which keeps R on the device -- the iterative
+// GP's preconditioner (gpx_cg.hip); its block is the same layout without x.
 #include "gpx_small.h"
 #include <algorithm>
 #include <cmath>
@@ -288,6 +292,51 @@ static int select_enqueue(const SelBufs &b, int64_t n, int d, const KParams &kp,
     return GPX_OK;
 }
 
+// One selection on a block laid out by sel_layout whose points (b.x) are in place: the state word cleared, every launch, one
+// profile record around them (its work -- the bytes of R read and written -- is known at the end), the count on the host and a
+// route hit per pick.  Synchronises `st`.
+static int select_run(int dtype, bool periodic, const SelBufs &b, int64_t n, int d, const KParams &kp, int64_t m_max, double tol,
+                      int64_t first, int64_t ldr, hipStream_t st, int64_t *count)
+{
+    GPX_HIP(hipMemsetAsync(b.st, 0, sizeof(SelState), st));
+    SelState hs;
+    {
+        RoctxRange range(prof_class_name(PC_SELECT));
+        const int rec = (g_prof_on && g_prof_mute == 0) ? prof_begin(PC_SELECT, 0.0, st) : -1;
+        const int rc = by_dtype(dtype, [&](auto t) {
+            using T = decltype(t);
+            return periodic ? select_enqueue<T, GPX_KERNEL_PERIODIC>(b, n, d, kp, m_max, tol, first, ldr, st)
+                            : select_enqueue<T, GPX_KERNEL_GAUSSIAN>(b, n, d, kp, m_max, tol, first, ldr, st);
+        });
+        if (rec >= 0) prof_end(rec, st);
+        GPX_TRY(rc);
+        GPX_HIP(hipMemcpyAsync(&hs, b.st, sizeof(SelState), hipMemcpyDeviceToHost, st));
+        GPX_HIP(hipStreamSynchronize(st));
+        if (rec >= 0) prof_set_work(rec, (double)esize(dtype) * (double)n * (double)hs.count * (double)(hs.count + 1) / 2.0);
+    }
+    const int64_t cnt = hs.count;
+    if (cnt < 0 || cnt > m_max) { set_error("gpx_sgp_select: the device reported %lld picks of at most %lld", (long long)cnt, (long long)m_max); return GPX_ERR_INTERNAL; }
+    for (int64_t i = 0; i < cnt; ++i) route_hit(RT_SELECT_STEP);
+    *count = cnt;
+    return GPX_OK;
+}
+
+// The device-pointer entry (gpx_gp_internal.h): the same launches on points the caller keeps in HBM.  The block is sel_layout's
+// with no room for x; R stays where it is, for the caller.
+size_t select_block_bytes(int dtype, int64_t n, int64_t m_max) { return sel_layout(n, 0, m_max, esize(dtype)).total; }
+
+int select_on_device(int dtype, int kernel, const void *x_dev, int64_t n, int d, const double *params, int64_t m_max, double tol, void *block,
+                     hipStream_t st, int64_t *count, void **R, int64_t *ldr)
+{
+    KParams kp;
+    GPX_TRY(make_kparams(kernel, GPX_K, params, 0.0, &kp));
+    SelBufs b((char *)block, sel_layout(n, 0, m_max, esize(dtype)));
+    b.x = const_cast<void *>(x_dev);
+    *ldr = round_up(n, SEL_LD_ALIGN);
+    *R = b.R;
+    return select_run(dtype, kernel == GPX_KERNEL_PERIODIC, b, n, d, kp, m_max, tol, -1, *ldr, st, count);
+}
+
 // a stream of the call's own, gone with it
 struct SelStream {
     hipStream_t st = nullptr;
@@ -334,33 +383,14 @@ static int sgp_select(int dtype, int kernel, const double *x, int64_t n, int d, 
     const SelBufs b((char *)dev.p, lay);
     GPX_TRY(upload_f64(dtype, b.x, n * d, x, n * d, 1, n * d, st));
     if (ard) GPX_TRY(scale_points(dtype, b.x, n, d, params + 1, b.x, st));
-    GPX_HIP(hipMemsetAsync(b.st, 0, sizeof(SelState), st));
-
     std::vector<int64_t> hindex((size_t)m_max);
     std::vector<double> hpivot((size_t)m_max), htrace((size_t)m_max + 1);
-    SelState hs;
-    {
-        // one record around all of the call's launches; its work -- the bytes of R read and written -- is known at the end
-        RoctxRange range(prof_class_name(PC_SELECT));
-        const int rec = (g_prof_on && g_prof_mute == 0) ? prof_begin(PC_SELECT, 0.0, st) : -1;
-        const bool periodic = kernel == GPX_KERNEL_PERIODIC;
-        const int rc = by_dtype(dtype, [&](auto t) {
-            using T = decltype(t);
-            return periodic ? select_enqueue<T, GPX_KERNEL_PERIODIC>(b, n, d, kp, m_max, tol, first, ldr, st)
-                            : select_enqueue<T, GPX_KERNEL_GAUSSIAN>(b, n, d, kp, m_max, tol, first, ldr, st);
-        });
-        if (rec >= 0) prof_end(rec, st);
-        GPX_TRY(rc);
-        GPX_HIP(hipMemcpyAsync(&hs, b.st, sizeof(SelState), hipMemcpyDeviceToHost, st));
-        GPX_HIP(hipMemcpyAsync(hindex.data(), b.index, (size_t)m_max * 8, hipMemcpyDeviceToHost, st));
-        GPX_HIP(hipMemcpyAsync(hpivot.data(), b.pivot, (size_t)m_max * 8, hipMemcpyDeviceToHost, st));
-        GPX_HIP(hipMemcpyAsync(htrace.data(), b.trace, (size_t)(m_max + 1) * 8, hipMemcpyDeviceToHost, st));
-        GPX_HIP(hipStreamSynchronize(st));
-        if (rec >= 0) prof_set_work(rec, (double)es * (double)n * (double)hs.count * (double)(hs.count + 1) / 2.0);
-    }
-    const int64_t cnt = hs.count;
-    if (cnt < 0 || cnt > m_max) { set_error("gpx_sgp_select: the device reported %lld picks of at most %lld", (long long)cnt, (long long)m_max); return GPX_ERR_INTERNAL; }
-    for (int64_t i = 0; i < cnt; ++i) route_hit(RT_SELECT_STEP);
+    int64_t cnt = 0;
+    GPX_TRY(select_run(dtype, kernel == GPX_KERNEL_PERIODIC, b, n, d, kp, m_max, tol, first, ldr, st, &cnt));
+    GPX_HIP(hipMemcpyAsync(hindex.data(), b.index, (size_t)m_max * 8, hipMemcpyDeviceToHost, st));
+    GPX_HIP(hipMemcpyAsync(hpivot.data(), b.pivot, (size_t)m_max * 8, hipMemcpyDeviceToHost, st));
+    GPX_HIP(hipMemcpyAsync(htrace.data(), b.trace, (size_t)(m_max + 1) * 8, hipMemcpyDeviceToHost, st));
+    GPX_HIP(hipStreamSynchronize(st));
     if (R && cnt > 0) {
         const int64_t rows_per = std::max<int64_t>(1, (int64_t)(SEL_DOWNLOAD_BYTES / ((size_t)n * 8)));
         for (int64_t r0 = 0; r0 < cnt; r0 += rows_per) {

@@ -53,39 +53,9 @@ struct SgpScal {
     int info1, info2;  // potrf of Kuu, of B
 };
 
-// The times of one pass on the handle's stream.  A pass is a sequence of marks: mark() records the next event of a grow-only
-// pool and books the interval since the mark before it to a bucket, or to nobody (SGP_NOBODY); resolve(), behind the pass's
-// last synchronisation, adds the intervals up.  The fit and the gradient never overlap: they share the pool.
-constexpr int SGP_NOBODY = -1;
-struct SgpTimeline {
-    std::vector<hipEvent_t> pool;      // grow-only; gpx_sgp_destroy destroys them
-    std::vector<int> bucket;           // of the marks of the current pass
-    SgpTimeline &begin() { bucket.clear(); return *this; }
-    int mark(hipStream_t st, int b)
-    {
-        if (bucket.size() == pool.size()) {
-            hipEvent_t e;
-            GPX_HIP(hipEventCreate(&e));
-            pool.push_back(e);
-        }
-        GPX_HIP(hipEventRecord(pool[bucket.size()], st));
-        bucket.push_back(b);
-        return GPX_OK;
-    }
-    // ms[b] (b < count) = the sum of bucket b's intervals; ms[total] = the first mark to the last
-    int resolve(float *ms, int count, int total) const
-    {
-        for (int i = 0; i < count; ++i) ms[i] = 0.0f;
-        for (size_t i = 1; i < bucket.size(); ++i) {
-            if (bucket[i] == SGP_NOBODY) continue;
-            float t = 0.0f;
-            GPX_HIP(hipEventElapsedTime(&t, pool[i - 1], pool[i]));
-            ms[bucket[i]] += t;
-        }
-        if (bucket.size() > 1) GPX_HIP(hipEventElapsedTime(&ms[total], pool[0], pool[bucket.size() - 1]));
-        return GPX_OK;
-    }
-};
+// the times of a pass: the handle's one PassTimeline (gpx_gp_internal.h)
+constexpr int SGP_NOBODY = gpx::TL_NOBODY;
+using SgpTimeline = gpx::PassTimeline;
 
 struct gpx_sgp {
     int device, dtype, kernel, d, nparams;

@@ -182,6 +182,7 @@ int gpx_stream_wait_event(void *stream, void *event);
 #define GPX_PROF_SPARSE_GRAD 20 /* rect_tile_kernel / tile_reduce_ard_kernel in its rectangular form (gpx_sgp_grad): the rectangular tile reduction of ONE chunk; kernel-derivative evaluations c * M */
 #define GPX_PROF_SPARSE_ZGRAD 21 /* rect_zgrad_kernel and its slice sum (gpx_sgp_grad_z, gpx_d_rect_zgrad): ONE pass of c rows against the M columns; kernel-derivative evaluations c * M per window of dimensions */
 #define GPX_PROF_SELECT      22 /* select_pick_kernel + select_step_kernel (gpx_sgp_select), ONE record per call around all of its launches: bytes of R read and written, sizeof(T) n count (count + 1) / 2 */
+#define GPX_PROF_CG          23 /* gpx_cg_solve, gpx_cg_var: ONE record per call around all of its launches (the product's and the blocks' own launches are recorded under their classes as well); kernel evaluations n^2 x iterations, summed over the groups of columns */
 int gpx_prof_enable(int on);    /* also clears the registry */
 int gpx_prof_read(int cls, double *launches, double *total_ms, double *total_work);
 
@@ -216,6 +217,7 @@ int gpx_prof_read(int cls, double *launches, double *total_ms, double *total_wor
 #define GPX_ROUTE_REMOVE         24   /* gpx_gp_remove: one hit per call                                               */
 #define GPX_ROUTE_SPARSE_CHUNK   25   /* gpx_sgp_fit: one hit per column chunk of x                                   */
 #define GPX_ROUTE_SELECT_STEP    26   /* gpx_sgp_select: one hit per step that picked a point                          */
+#define GPX_ROUTE_CG_ITER        27   /* gpx_cg_solve, gpx_cg_var: one hit per iteration of a group of columns         */
 int gpx_debug_route_count(int route, int64_t *count);
 /* roctx ranges pushed so far (GPX_ROCTX=1: every gpx_gp_* call and every launch class below it is a nested host range for
  * `rocprofv3 --marker-trace`; libroctx64.so is loaded on first use; 0 while the switch is off) */
@@ -973,6 +975,63 @@ int gpx_rect_zgrad_scratch(int kernel, int64_t m, int d, size_t *doubles);
 int gpx_d_rect_zgrad(int dtype, int kernel, const void *r, int64_t n, const void *q, int64_t m, int d, const double *params,
                      const void *C, int64_t ldc, const void *u, const void *v, double scale, const double *col_div,
                      double *partial_dev, double *out_dev, void *stream);
+
+/* ------------------------------------- exact GP past the n x n factor: CG -- */
+/* (K + s^2 I) X^T = B^T by batched preconditioned conjugate gradients; K(x, x) is never formed (Gardner et al. 2018; Wang et
+ * al. 2019).  Device memory is n (d + 2 rank + 6 S + 2) doubles and small change, S = min(columns, 32): nothing scales with
+ * n^2 (DESIGN 3.3 "Exact GP past the factor").  GPX_F64 only: GPX_F32 is GPX_ERR_UNSUPPORTED, and so is a d beyond the fused
+ * route of gpx_d_kmat_apply (d <= 47), the only product the solver uses: with GPX_KAPPLY_FUSED_MAX lowered by
+ * gpx_debug_kapply_fused_max the groups shrink to that many columns, and at 0 a solve is GPX_ERR_UNSUPPORTED.  All three kernel families (the
+ * ARD family on points scaled once by gpx_d_scale_points).  The handle keeps x (n, d) and y (n) in HBM, has one stream, makes
+ * its device current in every call as gpx_gp_t does, and every call is synchronous.  All pointers below are HOST.
+ *   preconditioner  P = R^T R + s^2 I, R (k x n) the pivoted partial Cholesky of gpx_sgp_select on the resident x
+ *   one iteration   q = s^2 p, then gpx_d_kmat_apply(x_rows, x, p -> q) on row blocks of x (at most 32 columns at a time: the
+ *                   fused route);  delta = p.q, alpha = rho / delta, x += alpha p, r -= alpha q, rr = r.r;
+ *                   z = P^-1 r, rho' = r.z, beta = rho' / rho, p = z + beta p
+ * Every dot is f64, summed per workgroup and then in ascending workgroup order by a second launch, which also forms alpha,
+ * beta and the flags on the device; no atomics: a repeated solve gives the same bits.
+ * Freezing: a column whose rr <= tol^2 b.b (|r| <= tol |b|) is frozen at that iteration -- its x, r and p no longer change
+ * whatever its batch companions do, and that iteration is its count.  b = 0: frozen from the start, x = 0, 0 iterations,
+ * relres 0.  delta <= 0 or not finite (positive definiteness lost to rounding): frozen, the count is MINUS the iteration.
+ * The host reads the group's residual norms and flags once per iteration, in one copy, and stops when every column is frozen
+ * or at maxiter.  Not converged at maxiter is not an error: relres holds what was reached. */
+typedef struct gpx_cg gpx_cg_t;
+int gpx_cg_create(gpx_cg_t **h, int dtype, int kernel, int64_t n, int d);
+int gpx_cg_destroy(gpx_cg_t *h);
+/* x: (n, d), y: (n,) float64; either may be NULL: that array is kept.  A new x forgets the preconditioner, either forgets
+ * the solution for y. */
+int gpx_cg_set_data(gpx_cg_t *h, const double *x, const double *y);
+/* The preconditioner of (params, s) -- params as gpx_gp_set_params, s > 0 -- which every later solve must name again.
+ * rank in 0 .. n; 0: none (P = I).  The selection (tol: its stop rule, as gpx_sgp_select's) runs on the resident x and R stays
+ * on the device; *count <= rank rows are used (count < rank is not an error: the selection stopped at tol).  Then
+ * C = s^2 I + R R^T (gpx_d_gemm_nt on the lower triangle), C = Lc Lc^T (gpx_d_potrf) and R^T (gpx_d_transpose's kernel).
+ * GPX_ERR_ARG naming the pivot when that factorisation fails (it cannot for s > 0 in exact arithmetic).
+ * GPX_PROF_SELECT and GPX_ROUTE_SELECT_STEP as gpx_sgp_select. */
+int gpx_cg_precond(gpx_cg_t *h, const double *params, double s, int64_t rank, double tol, int64_t *count);
+/* out = P^-1 V for S vectors (V, out: S x n dense), by Woodbury: (V - (V R^T) C^-1 R) / s^2 -- two gpx_d_gemm_nt, gpx_d_trsm_right_lt
+ * and gpx_d_trsm_right_l on the S x k block, one map.  The block the solver applies, alone. */
+int gpx_cg_precond_apply(gpx_cg_t *h, const double *V, int64_t S, double *out);
+/* B: S right-hand sides, S x n dense, or NULL with S == 1: the handle's y (that solution stays on the device for gpx_cg_mean).
+ * X: S x n (may be NULL with B == NULL).  iters, relres: S entries; relres = sqrt(rr / b.b) of the recurrence.  More than 32
+ * columns go in groups of 32 through one set of buffers.  tol >= 0 (the relative residual), maxiter >= 0.  GPX_ERR_ARG when
+ * (params, s) are not the preconditioner's.  GPX_PROF_CG: one record per call; GPX_ROUTE_CG_ITER: one hit per iteration of a
+ * group. */
+int gpx_cg_solve(gpx_cg_t *h, const double *params, double s, const double *B, int64_t S, double tol, int64_t maxiter, double *X,
+                 int *iters, double *relres);
+/* out[i] = sum_j k(xo_i, x_j) alpha_j, xo (m, d): gpx_d_mean with the last solution for y.  GPX_ERR_ARG if there is none, or
+ * if it belongs to other parameters. */
+int gpx_cg_mean(gpx_cg_t *h, const double *params, const double *xo, int64_t m, double *out);
+/* Predictive variance at xo (m, d), in groups of at most 32 test points: B = K(xo_c, x) (gpx_d_kmat), one batched solve,
+ * out[i] = k(xo_i, xo_i) - b_i . x_i (f64, fixed order).  m / 32 solves: for hundreds of points, not millions.  *worst_relres
+ * (may be NULL): the largest relres over all columns.  Not clamped at zero. */
+int gpx_cg_var(gpx_cg_t *h, const double *params, double s, const double *xo, int64_t m, double tol, int64_t maxiter, double *out,
+               double *worst_relres);
+/* milliseconds (HIP events on the handle's stream): [0] the last gpx_cg_precond; of the last gpx_cg_solve / gpx_cg_var:
+ * [1] the products [2] the preconditioner applies (with rho' = r.z) [3] the vector kernels [4] total [5] the status reads --
+ * from the end of an iteration's vector kernels to the first launch the host makes once it has the status */
+int gpx_cg_last_timing(gpx_cg_t *h, float *ms6);
+/* bytes of device memory the handle owns now (this host thread's scratch blocks, which the products use, are not the handle's) */
+int gpx_cg_device_bytes(gpx_cg_t *h, size_t *bytes);
 
 /* ------------------------------------------------------------- multi-GPU -- */
 /* One GP spread over the GPUs of a node, one PROCESS per GPU (north-star; SURVEY 8e -- the reference has
