@@ -20,9 +20,9 @@ ERR_ARG, ERR_HIP, ERR_NO_DEVICE, ERR_NOMEM, ERR_UNSUPPORTED, ERR_INTERNAL = -1, 
  ROUTE_GEMM_FAST, ROUTE_GEMM_GENERIC, ROUTE_SYRK_EXACT, ROUTE_SYRK_PATCH, ROUTE_MG_BCAST_ONE, ROUTE_MG_BCAST_SAG,
  ROUTE_FIT_OPS_AHEAD, ROUTE_TRSM_OPS, ROUTE_POTRF_PAIR, ROUTE_VAR_CHUNK, ROUTE_LOO_CHUNK, ROUTE_TRSM_L_OPS,
  ROUTE_GRAD_CHUNK, ROUTE_EXTEND, ROUTE_SAMPLE, ROUTE_KAPPLY_FUSED, ROUTE_KAPPLY_GEMM, ROUTE_PATHS_GRAD_CHUNK,
- ROUTE_REMOVE, ROUTE_SPARSE_CHUNK, ROUTE_SELECT_STEP, ROUTE_CG_ITER) = range(28)
+ ROUTE_REMOVE, ROUTE_SPARSE_CHUNK, ROUTE_SELECT_STEP, ROUTE_CG_ITER, ROUTE_LOWRANK) = range(29)
 PROF_RANDN, PROF_RFF, PROF_KAPPLY, PROF_KAPPLY_GRAD, PROF_CHOL_DELETE, PROF_SPARSE_GRAM, PROF_SPARSE_GRAD = 14, 15, 16, 17, 18, 19, 20
-PROF_SPARSE_ZGRAD, PROF_SELECT, PROF_CG = 21, 22, 23
+PROF_SPARSE_ZGRAD, PROF_SELECT, PROF_CG, PROF_LOWRANK = 21, 22, 23, 24
 F64, F32 = 0, 1
 KERNEL_GAUSSIAN, KERNEL_PERIODIC, KERNEL_GAUSSIAN_ARD = 0, 1, 2
 ARD_MAX_D = 64
@@ -195,6 +195,11 @@ _SIGNATURES = {
     "gpx_cg_solve": (c_int, [c_void_p, c_double_p, c_double, c_double_p, c_int64, c_double, c_int64, c_double_p, c_int_p, c_double_p]),
     "gpx_cg_mean": (c_int, [c_void_p, c_double_p, c_double_p, c_int64, c_double_p]),
     "gpx_cg_var": (c_int, [c_void_p, c_double_p, c_double, c_double_p, c_int64, c_double, c_int64, c_double_p, c_double_p]),
+    "gpx_cg_probes": (c_int, [c_void_p, c_int64, c_uint64, c_double_p]),
+    "gpx_cg_lh": (c_int, [c_void_p, c_double_p, c_double, c_double_p, c_int64, c_uint64, c_double, c_int64, c_int, c_double_p, c_int_p,
+                          c_double_p, c_double_p, c_double_p, c_double_p, c_double_p]),
+    "gpx_d_lowrank_reduce": (c_int, [c_int, c_int, c_void_p, c_int64, c_int, c_double_p, c_void_p, c_void_p, c_int64, c_int64, c_double_p,
+                                     c_void_p]),
     "gpx_cg_last_timing": (c_int, [c_void_p, POINTER(c_float)]),
     "gpx_cg_device_bytes": (c_int, [c_void_p, POINTER(c_size_t)]),
     "gpx_debug_sgp_plan": (c_int, [c_int, c_int64, c_int64, c_int64, c_int, c_size_t, POINTER(c_int64), POINTER(c_int64),

@@ -20,7 +20,16 @@
 //   sel   (grow-only) the selection's block (sel_layout without x): R  rank x ldn | its residuals, partials and state
 //   pre   (grow-only) cg_pre_layout:    C  k x ldk | Rt  n x ldk (R^T: the library's product is the NT form) | W  32 x ldk
 //   state (grow-only) cg_state_layout:  the scalars | the partials  32 x nwg | B, X, Rv, Z, P, Q  S x ldn each
-// Nothing scales with n^2: n (d + 2 rank + 6 S + 2) doubles and small change.
+//   lh    (grow-only) cg_lh_layout, allocated by the first gpx_cg_lh:  the coefficient history  maxiter x 2 x 32 | rho0  32 |
+//         Zt  32 x ldn, the first preconditioned residuals | the tile reduction's partials
+// Nothing scales with n^2: n (d + 2 rank + 6 S + 2) doubles and small change (7 S with the estimate's block).
+//
+// The marginal likelihood (gpx_cg_lh): CG's alpha_j, beta_j ARE the Lanczos coefficients of P^-1/2 (K + s^2 I) P^-1/2 started
+// at P^-1/2 z, so with probes z ~ N(0, P)  log det (K + s^2 I) = log det P + E[rho0 e1^T log(T) e1], rho0 = z . P^-1 z
+// (stochastic Lanczos quadrature; the tridiagonal's eigenproblem is the host's).  cg_fin_kernel writes the coefficients of
+// every iteration into the history block -- through a pointer that is null in every other solve -- and the group's history is
+// downloaded once.  The gradient's trace term uses E[P^-1 z z^T] = I: tr(K^-1 dK) = E[(K^-1 z)^T dK (P^-1 z)], contracted
+// against the kernel derivatives by lowrank_reduce (gpx_lrgrad.hip) with U = -W / T, V = Zt, and once more with U = V = alpha.
 #include "gpx_small.h"
 #include <algorithm>
 #include <cmath>
@@ -48,13 +57,20 @@ struct CgScal {
     CgStatus stat;
 };
 
+// what a solve leaves behind for the likelihood estimate (null: nothing recorded)
+struct CgRecord {
+    double *hist;              // [it - 1][0: alpha, 1: beta][CG_GROUP], cleared by the caller; a frozen column's entries stay 0
+    double *rho0;              // CG_GROUP: r0 . P^-1 r0
+    double *Zt;                // S x ldn: P^-1 r0 (b.Z is overwritten at every iteration)
+};
+
 enum { CG_T_BUILD, CG_T_PRODUCT, CG_T_APPLY, CG_T_VECTOR, CG_T_TOTAL, CG_T_READ, CG_T_COUNT };
 
 struct gpx_cg {
     int device, dtype, kernel, d, nparams;
     int64_t n, ldn;
     void *x, *xs, *y, *alpha;
-    gpx::GrowBuf sel, pre, state;
+    gpx::GrowBuf sel, pre, state, lh;
     void *R;                   // inside sel
     int64_t rank, k, ldk;      // rank asked for, rows of R in use, round_up(k, 16)
     hipStream_t st;
@@ -125,7 +141,7 @@ __global__ __launch_bounds__(256) void cg_update_kernel(double *__restrict__ x, 
 // The second launch of every reduction: thread s adds column s's partials in ascending workgroup order and does what the sum is for.
 enum { CG_FIN_BB, CG_FIN_RHO0, CG_FIN_DELTA, CG_FIN_RR, CG_FIN_RHO, CG_FIN_ACC };
 __global__ __launch_bounds__(64) void cg_fin_kernel(int mode, const double *__restrict__ partial, int64_t nwg, int S, int it, double tol2,
-                                                    int rho_is_rr, CgScal *sc)
+                                                    int rho_is_rr, CgScal *sc, double *hist)
 {
     const int s = threadIdx.x;
     if (s >= S) return;
@@ -146,6 +162,7 @@ __global__ __launch_bounds__(64) void cg_fin_kernel(int mode, const double *__re
         if (frozen) sc->alpha[s] = 0.0;
         else if (!(sum > 0.0) || !isfinite(sum)) { sc->stat.frozen[s] = 1; sc->stat.iters[s] = -it; sc->alpha[s] = 0.0; }
         else sc->alpha[s] = sc->rho[s] / sum;
+        if (hist) hist[(int64_t)(it - 1) * 2 * CG_GROUP + s] = sc->alpha[s];
         break;
     case CG_FIN_RR:
         if (!frozen) {
@@ -160,6 +177,7 @@ __global__ __launch_bounds__(64) void cg_fin_kernel(int mode, const double *__re
             sc->beta[s] = rho != 0.0 ? sum / rho : 0.0;
             sc->rho[s] = sum;
         }
+        if (hist) hist[(int64_t)(it - 1) * 2 * CG_GROUP + CG_GROUP + s] = sc->beta[s];
         break;
     default: sc->acc[s] = sum; break;
     }
@@ -194,6 +212,15 @@ struct CgBufs {
           Q((double *)(p + l.Q)), part((double *)(p + l.part)), sc((CgScal *)(p + l.scal)) {}
 };
 
+struct CgLhLayout { size_t hist, rho0, Zt, part, total; };
+static CgLhLayout cg_lh_layout(int64_t ldn, int64_t maxiter, size_t partial_doubles)
+{
+    Carve c;
+    const size_t hist = c.take((size_t)std::max<int64_t>(maxiter, 1) * 2 * CG_GROUP * 8), rho0 = c.take(CG_GROUP * 8);
+    const size_t Zt = c.take((size_t)CG_GROUP * ldn * 8), part = c.take(partial_doubles * 8);
+    return {hist, rho0, Zt, part, c.total()};
+}
+
 static inline int64_t cg_nwg(int64_t n) { return cdiv(n, CG_WG); }
 
 // the state block for groups of S columns; a block that grew is cleared (the columns [n, ldn) of every array stay zero from
@@ -223,9 +250,9 @@ static int cg_dot(const double *a, double *b, int64_t S, const gpx_cg *g, double
     GPX_LAUNCH_CHECK();
     return GPX_OK;
 }
-static int cg_fin(int mode, int64_t S, int it, double tol2, const gpx_cg *g, const CgBufs &b)
+static int cg_fin(int mode, int64_t S, int it, double tol2, const gpx_cg *g, const CgBufs &b, double *hist = nullptr)
 {
-    hipLaunchKernelGGL(cg_fin_kernel, dim3(1), dim3(64), 0, g->st, mode, b.part, cg_nwg(g->n), (int)S, it, tol2, g->k > 0 ? 0 : 1, b.sc);
+    hipLaunchKernelGGL(cg_fin_kernel, dim3(1), dim3(64), 0, g->st, mode, b.part, cg_nwg(g->n), (int)S, it, tol2, g->k > 0 ? 0 : 1, b.sc, hist);
     GPX_LAUNCH_CHECK();
     return GPX_OK;
 }
@@ -265,7 +292,9 @@ static bool cg_all_frozen(const CgStatus &h, int64_t S)
 }
 
 // One group: the right-hand sides are in b.B (S x ldn); the solution is left in b.X.  iters, relres: S entries (host).
-static int cg_solve_group(gpx_cg *g, const CgBufs &b, int64_t S, double tol, int64_t maxiter, int *iters, double *relres, int64_t *its_done)
+// rec (may be null): the coefficient history, rho0 and the first preconditioned residual are kept for gpx_cg_lh.
+static int cg_solve_group(gpx_cg *g, const CgBufs &b, int64_t S, double tol, int64_t maxiter, int *iters, double *relres, int64_t *its_done,
+                          const CgRecord *rec = nullptr)
 {
     const int64_t n = g->n, ldn = g->ldn;
     const size_t vb = (size_t)S * ldn * 8;
@@ -288,6 +317,12 @@ static int cg_solve_group(gpx_cg *g, const CgBufs &b, int64_t S, double tol, int
     }
     GPX_TRY(cg_fin(CG_FIN_RHO0, S, 0, tol2, g, b));
     GPX_HIP(hipMemcpyAsync(b.P, Z, vb, hipMemcpyDeviceToDevice, st));
+    double *hist = nullptr;
+    if (rec) {
+        hist = rec->hist;
+        GPX_HIP(hipMemcpyAsync(rec->Zt, Z, vb, hipMemcpyDeviceToDevice, st));
+        GPX_HIP(hipMemcpyAsync(rec->rho0, b.sc->rho, sizeof(double) * CG_GROUP, hipMemcpyDeviceToDevice, st));
+    }
     GPX_TRY(tl.mark(st, CG_T_VECTOR));
     CgStatus host;
     GPX_TRY(cg_read_status(g, b, &host));
@@ -308,7 +343,7 @@ static int cg_solve_group(gpx_cg *g, const CgBufs &b, int64_t S, double tol, int
         }
         GPX_TRY(tl.mark(st, CG_T_PRODUCT));
         GPX_TRY(cg_dot<false>(b.P, b.Q, S, g, 1.0, b.part));
-        GPX_TRY(cg_fin(CG_FIN_DELTA, S, (int)it, tol2, g, b));
+        GPX_TRY(cg_fin(CG_FIN_DELTA, S, (int)it, tol2, g, b, hist));
         hipLaunchKernelGGL(cg_update_kernel, dim3((unsigned)cg_nwg(n), (unsigned)S), dim3(256), 0, st, b.X, b.Rv, b.P, b.Q, ldn, n, b.sc, b.part,
                            cg_nwg(n));
         GPX_LAUNCH_CHECK();
@@ -322,7 +357,7 @@ static int cg_solve_group(gpx_cg *g, const CgBufs &b, int64_t S, double tol, int
             GPX_TRY(cg_dot<true>(b.Rv, b.Z, S, g, s2, b.part));
             GPX_TRY(tl.mark(st, CG_T_APPLY));
         }
-        GPX_TRY(cg_fin(CG_FIN_RHO, S, (int)it, tol2, g, b));
+        GPX_TRY(cg_fin(CG_FIN_RHO, S, (int)it, tol2, g, b, hist));
         {
             double *P = b.P;
             const double *Zc = Z;
@@ -463,6 +498,59 @@ static int cg_precond(gpx_cg *g, const double *params, double s, int64_t rank, d
     return GPX_OK;
 }
 
+// The handle's solution for y: one group of one column; it stays on the device for gpx_cg_mean and gpx_cg_lh.
+static int cg_solve_y(gpx_cg *g, const CgBufs &b, double tol, int64_t maxiter, int *iters, double *relres, int64_t *its)
+{
+    const int64_t ldn = g->ldn;
+    GPX_HIP(hipMemcpyAsync(b.B, g->y, (size_t)ldn * 8, hipMemcpyDeviceToDevice, g->st));
+    GPX_TRY(g->tl.mark(g->st, TL_NOBODY));
+    GPX_TRY(cg_solve_group(g, b, 1, tol, maxiter, iters, relres, its));
+    GPX_HIP(hipMemcpyAsync(g->alpha, b.X, (size_t)ldn * 8, hipMemcpyDeviceToDevice, g->st));
+    for (int i = 0; i < g->nparams; ++i) g->alpha_params[i] = g->params[i];
+    g->have_alpha = true;
+    return GPX_OK;
+}
+
+// Rows [t0, t0 + S) of the probes z ~ N(0, P) into dst (S x ldn, its pads zero): z = g1 R + s g2 with g2 = randn(T x n; seed,
+// stream 4) and g1 = randn(T x k; seed, stream 5); rank 0 (P = I): z = g2.  Row t depends on (seed, t) alone: fewer probes are a
+// prefix of more, and a group is generated where it is solved.
+static int cg_make_probes(gpx_cg *g, int64_t t0, int64_t S, uint64_t seed, double *dst)
+{
+    const int64_t n = g->n, ldn = g->ldn, k = g->k, ldk = g->ldk;
+    hipStream_t st = g->st;
+    GPX_TRY(randn(GPX_F64, dst, S, n, ldn, seed, 4, (uint64_t)t0 * (uint64_t)n, st));
+    if (k == 0) return GPX_OK;
+    const double sd = g->s;
+    GPX_TRY(map_rows(S, n, st, [=] __device__(int64_t r, int64_t c) { dst[r * ldn + c] = sd * dst[r * ldn + c]; }));
+    const CgPreLayout lay = cg_pre_layout(n, k, ldk);
+    char *base = (char *)g->pre.p;
+    void *Rt = base + lay.Rt, *W = base + lay.W;
+    GPX_HIP(hipMemsetAsync(W, 0, (size_t)S * ldk * 8, st));
+    GPX_TRY(randn(GPX_F64, W, S, k, ldk, seed, 5, (uint64_t)t0 * (uint64_t)k, st));
+    // dst += g1 R, as W Rt^T over the padded depth ldk (W's and Rt's columns [k, ldk) are zero)
+    return gemm_nt(GPX_F64, S, n, ldk, W, ldk, Rt, ldk, dst, ldn, 1.0, GPX_FULL, 0, 0, st);
+}
+
+// log det P = 2 sum log diag(Lc) + (n - k) log s^2; 0 without a preconditioner (P = I).  Synchronises the stream.
+static int cg_logdet_precond(gpx_cg *g, double *out)
+{
+    *out = 0.0;
+    const int64_t k = g->k, ldk = g->ldk;
+    if (k == 0) return GPX_OK;
+    const CgPreLayout lay = cg_pre_layout(g->n, k, ldk);
+    const double *C = (const double *)((char *)g->pre.p + lay.C);
+    double *W = (double *)((char *)g->pre.p + lay.W);
+    GPX_TRY(map_vec(k, g->st, [=] __device__(int64_t i) { W[i] = C[i * ldk + i]; }));
+    std::vector<double> diag((size_t)k);
+    GPX_HIP(hipMemcpyAsync(diag.data(), W, (size_t)k * 8, hipMemcpyDeviceToHost, g->st));
+    GPX_HIP(hipStreamSynchronize(g->st));
+    GPX_HIP(hipMemsetAsync(W, 0, (size_t)k * 8, g->st));         // (W's columns [k, ldk) of every row stay zero for the products)
+    double sum = 0.0;
+    for (int64_t i = 0; i < k; ++i) sum += log(diag[i]);
+    *out = 2.0 * sum + (double)(g->n - k) * log(g->s * g->s);
+    return GPX_OK;
+}
+
 }  // namespace gpx
 
 using namespace gpx;
@@ -533,7 +621,7 @@ int gpx_cg_destroy(gpx_cg_t *g)
     if (g->st) (void)hipStreamSynchronize(g->st);
     stream_epoch_bump();                                       // (StreamTurn: a later stream at this one's address is a different stream)
     for (void *b : {g->x, g->xs, g->y, g->alpha}) dev_free(b);
-    g->sel.release(); g->pre.release(); g->state.release();
+    g->sel.release(); g->pre.release(); g->state.release(); g->lh.release();
     for (hipEvent_t e : g->tl.pool) (void)hipEventDestroy(e);
     if (g->st) (void)hipStreamDestroy(g->st);
     delete g;
@@ -603,17 +691,13 @@ int gpx_cg_solve(gpx_cg_t *g, const double *params, double s, const double *B, i
         const int64_t S = std::min<int64_t>(G, Sn - s0);
         CgBufs b;
         GPX_TRY(cg_state(g, std::min<int64_t>(G, Sn), &b));
-        if (B) GPX_TRY(upload_f64(g->dtype, b.B, ldn, B + s0 * n, n, S, n, g->st));
-        else GPX_HIP(hipMemcpyAsync(b.B, g->y, (size_t)ldn * 8, hipMemcpyDeviceToDevice, g->st));
-        GPX_TRY(g->tl.mark(g->st, TL_NOBODY));
         int64_t its = 0;
-        GPX_TRY(cg_solve_group(g, b, S, tol, maxiter, iters + s0, relres + s0, &its));
+        if (B) {
+            GPX_TRY(upload_f64(g->dtype, b.B, ldn, B + s0 * n, n, S, n, g->st));
+            GPX_TRY(g->tl.mark(g->st, TL_NOBODY));
+            GPX_TRY(cg_solve_group(g, b, S, tol, maxiter, iters + s0, relres + s0, &its));
+        } else GPX_TRY(cg_solve_y(g, b, tol, maxiter, iters, relres, &its));     // the solution for y stays, for gpx_cg_mean
         pass.group(its);
-        if (!B) {                                               // the solution for y stays, for gpx_cg_mean
-            GPX_HIP(hipMemcpyAsync(g->alpha, b.X, (size_t)ldn * 8, hipMemcpyDeviceToDevice, g->st));
-            for (int i = 0; i < g->nparams; ++i) g->alpha_params[i] = g->params[i];
-            g->have_alpha = true;
-        }
         GPX_TRY(g->tl.mark(g->st, CG_T_VECTOR));
         if (X) GPX_TRY(download_f64(g->dtype, X + s0 * n, n, b.X, ldn, S, n, 0, g->st));
         GPX_TRY(g->tl.mark(g->st, TL_NOBODY));
@@ -689,6 +773,109 @@ int gpx_cg_var(gpx_cg_t *g, const double *params, double s, const double *xo, in
     return GPX_OK;
 }
 
+int gpx_cg_probes(gpx_cg_t *g, int64_t T, uint64_t seed, double *out)
+{
+    CG_ENTER(g);
+    GPX_ARG(g->have_precond, "there is no preconditioner (gpx_cg_precond)");
+    GPX_ARG(T >= 1, "need T >= 1");
+    GPX_ARG(T <= INT64_MAX / g->n, "T * n overflows");
+    for (int64_t t0 = 0; t0 < T; t0 += CG_GROUP) {
+        const int64_t S = std::min<int64_t>(CG_GROUP, T - t0);
+        CgBufs b;
+        GPX_TRY(cg_state(g, std::min<int64_t>(CG_GROUP, T), &b));
+        GPX_TRY(cg_make_probes(g, t0, S, seed, b.B));
+        if (out) GPX_TRY(download_f64(g->dtype, out + t0 * g->n, g->n, b.B, g->ldn, S, g->n, 0, g->st));
+    }
+    GPX_HIP(hipStreamSynchronize(g->st));
+    return GPX_OK;
+}
+
+int gpx_cg_lh(gpx_cg_t *g, const double *params, double s, const double *Z, int64_t T, uint64_t seed, double tol, int64_t maxiter,
+              int want_grad, double *rho0, int *iters, double *relres, double *coef, double *scalars, double *sums, double *grad)
+{
+    CG_ENTER(g);
+    CG_NEED_PRECOND(g, params, s);
+    GPX_ARG(T >= 1, "need T >= 1");
+    GPX_ARG(tol >= 0.0 && tol <= 1.79769313486231570e308, "tol must be >= 0 and finite");
+    GPX_ARG(maxiter >= 0 && maxiter <= 0x7fffffff, "maxiter must lie in 0 .. 2^31 - 1");
+    GPX_ARG(rho0 && iters && relres && coef && scalars && (!want_grad || (sums && grad)), "NULL argument");
+    GPX_ARG(T <= INT64_MAX / std::max<int64_t>(g->n, 2 * maxiter), "T * n overflows");
+    const int64_t n = g->n, ldn = g->ldn;
+    hipStream_t st = g->st;
+    int64_t G = 0;
+    GPX_TRY(cg_group_now(&G));
+    const size_t pdoubles = want_grad ? dloglh_partial_doubles(g->kernel, g->d) : 0;
+    const int width = (int)(dloglh_partial_doubles(g->kernel, g->d) / GR_BLOCKS);
+    const CgLhLayout lay = cg_lh_layout(ldn, maxiter, pdoubles);
+    bool grew = false;
+    GPX_TRY(g->lh.reserve(lay.total, st, &grew));
+    if (grew) GPX_HIP(hipMemsetAsync(g->lh.p, 0, g->lh.bytes, st));      // (Zt's columns [n, ldn) stay zero: the copies bring zeros)
+    char *lb = (char *)g->lh.p;
+    const CgRecord rec = {(double *)(lb + lay.hist), (double *)(lb + lay.rho0), (double *)(lb + lay.Zt)};
+    double *part = (double *)(lb + lay.part);
+    CgPass pass(g);
+    GPX_TRY(pass.begin());
+    CgBufs b;
+    GPX_TRY(cg_state(g, std::min<int64_t>(G, T), &b));
+    if (!g->have_alpha) {                                         // by gpx_cg_solve's rules for B == NULL
+        int it1 = 0;
+        double rr1 = 0.0;
+        int64_t its = 0;
+        GPX_TRY(cg_solve_y(g, b, tol, maxiter, &it1, &rr1, &its));
+        pass.group(its);
+    }
+    GPX_TRY(cg_dot<false>((const double *)g->y, (double *)g->alpha, 1, g, 1.0, b.part));
+    GPX_TRY(cg_fin(CG_FIN_ACC, 1, 0, 0.0, g, b));
+    GPX_HIP(hipMemcpyAsync(&scalars[1], b.sc->acc, sizeof(double), hipMemcpyDeviceToHost, st));
+    GPX_TRY(cg_logdet_precond(g, &scalars[0]));                   // (synchronises: y . alpha has arrived)
+    GPX_TRY(g->tl.mark(st, CG_T_VECTOR));
+    const CgView v = cg_view(g);
+    double launch[GPX_ARD_MAX_D + 2];
+    if (want_grad) for (int q = 0; q < width; ++q) sums[q] = 0.0;
+    for (int64_t i = 0; i < T * maxiter * 2; ++i) coef[i] = 0.0;
+    std::vector<double> hh;
+    double hrho[CG_GROUP];
+    for (int64_t t0 = 0; t0 < T; t0 += G) {
+        const int64_t S = std::min<int64_t>(G, T - t0);
+        if (Z) GPX_TRY(upload_f64(g->dtype, b.B, ldn, Z + t0 * n, n, S, n, st));
+        else GPX_TRY(cg_make_probes(g, t0, S, seed, b.B));
+        GPX_HIP(hipMemsetAsync(rec.hist, 0, (size_t)maxiter * 2 * CG_GROUP * 8, st));
+        GPX_TRY(g->tl.mark(st, TL_NOBODY));
+        int64_t its = 0;
+        GPX_TRY(cg_solve_group(g, b, S, tol, maxiter, iters + t0, relres + t0, &its, &rec));
+        pass.group(its);
+        // ONE download of the group's history
+        hh.resize((size_t)std::max<int64_t>(its, 1) * 2 * CG_GROUP);
+        if (its > 0) GPX_HIP(hipMemcpyAsync(hh.data(), rec.hist, (size_t)its * 2 * CG_GROUP * 8, hipMemcpyDeviceToHost, st));
+        GPX_HIP(hipMemcpyAsync(hrho, rec.rho0, sizeof(hrho), hipMemcpyDeviceToHost, st));
+        GPX_HIP(hipStreamSynchronize(st));
+        for (int64_t c = 0; c < S; ++c) {
+            rho0[t0 + c] = hrho[c];
+            for (int64_t it = 0; it < its; ++it) {
+                coef[((t0 + c) * maxiter + it) * 2] = hh[(size_t)it * 2 * CG_GROUP + c];
+                coef[((t0 + c) * maxiter + it) * 2 + 1] = hh[(size_t)it * 2 * CG_GROUP + CG_GROUP + c];
+            }
+        }
+        if (want_grad) {                                          // U = -W / T (in place: b.X is the group's), V = Zt
+            double *X = b.X;
+            const double scale = -1.0 / (double)T;
+            GPX_TRY(map_rows(S, n, st, [=] __device__(int64_t r, int64_t c) { X[r * ldn + c] = scale * X[r * ldn + c]; }));
+            GPX_TRY(lowrank_reduce(g->kernel, v.x, n, g->d, v.params, b.X, rec.Zt, ldn, S, part, launch, st));
+            for (int q = 0; q < width; ++q) sums[q] += launch[q];
+        }
+        GPX_TRY(g->tl.mark(st, TL_NOBODY));
+    }
+    if (want_grad) {
+        GPX_TRY(lowrank_reduce(g->kernel, v.x, n, g->d, v.params, (const double *)g->alpha, (const double *)g->alpha, ldn, 1, part, launch, st));
+        for (int q = 0; q < width; ++q) sums[q] += launch[q];
+        // last = alpha . alpha - the trace's estimate: d/ds = s * last (dK/ds = 2 s I)
+        grad_from_sums(g->kernel, g->d, g->params, sums, 0.0, -g->s, 0.5, grad);
+        GPX_TRY(g->tl.mark(st, TL_NOBODY));
+    }
+    GPX_TRY(pass.end());
+    return GPX_OK;
+}
+
 int gpx_cg_last_timing(gpx_cg_t *g, float *ms6)
 {
     GPX_ARG(g != nullptr && ms6, "NULL argument");
@@ -701,7 +888,7 @@ int gpx_cg_device_bytes(gpx_cg_t *g, size_t *bytes)
 {
     GPX_ARG(g != nullptr && bytes, "NULL argument");
     const size_t pts = (size_t)g->n * g->d * 8;
-    *bytes = pts + (g->xs ? pts : 0) + 2 * (size_t)g->ldn * 8 + g->sel.bytes + g->pre.bytes + g->state.bytes;
+    *bytes = pts + (g->xs ? pts : 0) + 2 * (size_t)g->ldn * 8 + g->sel.bytes + g->pre.bytes + g->state.bytes + g->lh.bytes;
     return GPX_OK;
 }
 

@@ -6,6 +6,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <math.h>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/gpx.h"
@@ -49,7 +50,7 @@ int  ensure_device();   // GPX_OK when a GPU is usable
 enum Route { RT_TRSV_OPS = 0, RT_TRSV_STEPS = 1, RT_PANEL_RES = 2, RT_PANEL_CHAIN = 3, RT_FIT_RIDE = 4,
              RT_FIT_TWO_SOLVES = 5, RT_GEMM_FAST = 6, RT_GEMM_GENERIC = 7, RT_SYRK_EXACT = 8, RT_SYRK_PATCH = 9,
              RT_MG_BCAST_ONE = 10, RT_MG_BCAST_SAG = 11, RT_FIT_OPS_AHEAD = 12, RT_TRSM_OPS = 13, RT_POTRF_PAIR = 14, RT_VAR_CHUNK = 15, RT_LOO_CHUNK = 16,
-             RT_TRSM_L_OPS = 17, RT_GRAD_CHUNK = 18, RT_EXTEND = 19, RT_SAMPLE = 20, RT_KAPPLY_FUSED = 21, RT_KAPPLY_GEMM = 22, RT_PATHS_GRAD_CHUNK = 23, RT_REMOVE = 24, RT_SPARSE_CHUNK = 25, RT_SELECT_STEP = 26, RT_CG_ITER = 27, RT_COUNT = 28 };
+             RT_TRSM_L_OPS = 17, RT_GRAD_CHUNK = 18, RT_EXTEND = 19, RT_SAMPLE = 20, RT_KAPPLY_FUSED = 21, RT_KAPPLY_GEMM = 22, RT_PATHS_GRAD_CHUNK = 23, RT_REMOVE = 24, RT_SPARSE_CHUNK = 25, RT_SELECT_STEP = 26, RT_CG_ITER = 27, RT_LOWRANK = 28, RT_COUNT = 29 };
 void route_hit(int route);
 
 // LAPACK-style info of a factorisation as the host sees it: > 0 "not positive definite" (the caller's business),
@@ -91,7 +92,7 @@ struct EventPool {
 // ---- live per-kernel-class timing (HIP events around each launch; off by default) ----
 enum ProfClass { PC_KMAT = 0, PC_GEMM = 1, PC_POTRF_DIAG = 2, PC_TRSM_ROWS = 3, PC_TRSV = 4,
                  PC_MEAN = 5, PC_REDUCE = 6, PC_GEMM_SKINNY = 7, PC_GEMM_GENERIC = 8, PC_GEMM_PANEL = 9, PC_GEMM_N64 = 10,
-                 PC_TRANSPOSE = 11, PC_PRED_GRAD = 12, PC_EXTEND = 13, PC_RANDN = 14, PC_RFF = 15, PC_KAPPLY = 16, PC_KAPPLY_GRAD = 17, PC_CHOL_DELETE = 18, PC_SPARSE_GRAM = 19, PC_SPARSE_GRAD = 20, PC_SPARSE_ZGRAD = 21, PC_SELECT = 22, PC_CG = 23, PC_COUNT = 24 };
+                 PC_TRANSPOSE = 11, PC_PRED_GRAD = 12, PC_EXTEND = 13, PC_RANDN = 14, PC_RFF = 15, PC_KAPPLY = 16, PC_KAPPLY_GRAD = 17, PC_CHOL_DELETE = 18, PC_SPARSE_GRAM = 19, PC_SPARSE_GRAD = 20, PC_SPARSE_ZGRAD = 21, PC_SELECT = 22, PC_CG = 23, PC_LOWRANK = 24, PC_COUNT = 25 };
 extern bool g_prof_on;
 // the registry is shared by all host threads (mutex inside); a scope ends its OWN record
 int  prof_begin(int cls, double work, hipStream_t st);    // record index, -1 when nothing was recorded
@@ -329,6 +330,33 @@ int tile_reduce(int dtype, int kernel, const void *x, int64_t n, int d, const do
 int rect_reduce(int dtype, int kernel, const void *x, int64_t n, const void *z, int64_t m, int d, const double *params, const void *P,
                 int64_t ldp, const void *y, const void *w, double *partial_dev, double *out, hipStream_t st);
 const double *reduce_params(int kernel, int d, const double *params, double *iso2);
+// What the tile reductions of both files (gpx_kmat.hip, gpx_lrgrad.hip) share: the tile edge and the fixed grid, the derivative
+// constants of a family (make_grad_params: GPX_KERNEL_GAUSSIAN or GPX_KERNEL_PERIODIC; the latter needs d == 1), the Gaussian
+// k's constant and the ladder of the ARD kernels' accumulator counts.
+constexpr int GR_T = 64;           // tile edge
+constexpr int GR_BLOCKS = 1024;
+struct GradParams {
+    double c1, c2h, c2w, c3w;      // gaussian: e = c1*d2 ; dK_dh = c2h*exp(e) ; dK_dw = exp(e)*(c3w*d2 - c2w)
+    double h, w, p;                // periodic
+    int kernel, nkp;
+};
+int make_grad_params(int kernel, int d, const double *params, GradParams *gpar);
+// the Gaussian k's constant, make_kparams' c2 of GPX_K: h^2 sqrt(2 / pi) / (2 w).  (make_kparams multiplies h * h first, which
+// rounds differently in one pair of three: one spelling there would move either every entry of K or every gradient by an ulp)
+static inline double gaussian_k_const(double h, double w) { return 0.5 * sqrt(2.0 / M_PI) * h * h / w; }
+// f(std::integral_constant<int, DMAX>()) for the rung of the ARD kernels' ladder that holds d: `decltype(dm)::value` names DMAX
+template <typename F>
+static inline int by_dmax(int d, F f)
+{
+    if (d <= 8) return f(std::integral_constant<int, 8>());
+    if (d <= 16) return f(std::integral_constant<int, 16>());
+    if (d <= 32) return f(std::integral_constant<int, 32>());
+    return f(std::integral_constant<int, 64>());
+}
+// The low-rank tile reduction (gpx_lrgrad.hip): gpx_d_lowrank_reduce's arguments behind its checks; partial_dev:
+// dloglh_partial_doubles() DEVICE doubles.  Synchronises `st`.
+int lowrank_reduce(int kernel, const void *x, int64_t n, int d, const double *params, const double *U, const double *V, int64_t ld,
+                   int64_t T, double *partial_dev, double *out, hipStream_t st);
 // The rectangular pass whose result is per COLUMN point and dimension (gpx_zgrad.hip; the sparse GP's gradient in the inducing
 // inputs): gpx_d_rect_zgrad's arguments on GPX_KERNEL_GAUSSIAN / GPX_KERNEL_PERIODIC points (the ARD family: the scaled points,
 // iso and col_div = the widths).  partial_dev: rect_zgrad_partial_doubles(kernel, m, d) DEVICE doubles.  Enqueues and returns.

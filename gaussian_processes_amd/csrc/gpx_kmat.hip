@@ -345,14 +345,6 @@ const double *reduce_params(int kernel, int d, const double *params, double *iso
 // (FORM as a template parameter and not a __device__ helper around the shared text: the instantiations keep the resource
 // lines the separate kernels had)
 // ---------------------------------------------------------------------------
-struct GradParams {
-    double c1, c2h, c2w, c3w;      // gaussian: e = c1*d2 ; dK_dh = c2h*exp(e) ; dK_dw = exp(e)*(c3w*d2 - c2w)
-    double h, w, p;                // periodic
-    int kernel, nkp;
-};
-
-constexpr int GR_T = 64;           // tile edge
-constexpr int GR_BLOCKS = 1024;
 enum { TILE_ML = 1, TILE_LOO = 2, TILE_RECT = 3 };
 
 // What only one form reads, as ONE kernel argument specialised per form: the staged vectors, and for TILE_RECT the second
@@ -645,11 +637,7 @@ static int sum_partials(const double *partial_dev, int width, double *out, hipSt
     return GPX_OK;
 }
 
-// the Gaussian k's constant, make_kparams' c2 of GPX_K: h^2 sqrt(2 / pi) / (2 w).  (make_kparams multiplies h * h first, which
-// rounds differently in one pair of three: one spelling there would move either every entry of K or every gradient by an ulp)
-static inline double gaussian_k_const(double h, double w) { return 0.5 * sqrt(2.0 / M_PI) * h * h / w; }
-
-static int make_grad_params(int kernel, int d, const double *params, GradParams *gpar)
+int make_grad_params(int kernel, int d, const double *params, GradParams *gpar)
 {
     memset(gpar, 0, sizeof(*gpar));
     gpar->kernel = kernel;
@@ -665,16 +653,6 @@ static int make_grad_params(int kernel, int d, const double *params, GradParams 
         gpar->nkp = 3; gpar->h = params[0]; gpar->w = params[1]; gpar->p = params[2];
     }
     return GPX_OK;
-}
-
-// f(std::integral_constant<int, DMAX>()) for the rung of the ARD kernels' ladder that holds d: `decltype(dm)::value` names DMAX
-template <typename F>
-static inline int by_dmax(int d, F f)
-{
-    if (d <= 8) return f(std::integral_constant<int, 8>());
-    if (d <= 16) return f(std::integral_constant<int, 16>());
-    if (d <= 32) return f(std::integral_constant<int, 32>());
-    return f(std::integral_constant<int, 64>());
 }
 
 // the dynamic LDS of a tile: two staged point sets of dk coordinates (d, or the ARD kernels' DMAX) and nvec vectors

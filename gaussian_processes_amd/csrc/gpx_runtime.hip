@@ -212,7 +212,7 @@ const char *prof_class_name(int cls)
                                           "gpx:mean", "gpx:reduce", "gpx:gemm_skinny", "gpx:gemm_generic", "gpx:gemm_panel", "gpx:gemm_n64",
                                           "gpx:transpose", "gpx:pred_grad", "gpx:extend", "gpx:randn", "gpx:rff_features", "gpx:kmat_apply",
                                           "gpx:kmat_apply_grad", "gpx:chol_delete", "gpx:sparse_gram", "gpx:sparse_grad_reduce",
-                                          "gpx:sparse_zgrad", "gpx:select", "gpx:cg_solve"};
+                                          "gpx:sparse_zgrad", "gpx:select", "gpx:cg_solve", "gpx:lowrank_reduce"};
     return (cls >= 0 && cls < PC_COUNT) ? names[cls] : "gpx:other";
 }
 bool roctx_push(const char *name)

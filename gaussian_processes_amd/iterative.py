@@ -10,8 +10,10 @@ product with K is one fused pass over the points (``gpx_d_kmat_apply``), and the
 is ``8 n (d + 2 rank + 6 S + 2)`` bytes and small change for ``S <= 32`` simultaneous right-hand sides -- nothing scales
 with ``n^2`` (``gpx_cg_*``, include/gpx.h; DESIGN 3.3 "Exact GP past the factor").
 
-The intended workflow: choose the hyper-parameters with `SparseGP.optimize`, or with `mlii` / `GP` on a subset of the data,
-then predict exactly at the full N with this class.
+Model selection stays on the same route: `log_lh_estimate` and `log_lh_and_grad` estimate the marginal likelihood and its
+gradient from the CG coefficients of a few random probes (stochastic Lanczos quadrature), the gradient's n^2 contraction runs
+in one fused tile reduction whose low-rank coefficients are formed inside the tile (``gpx_d_lowrank_reduce``), and `optimize`
+is L-BFGS-B on them with common random numbers.
 """
 import ctypes
 import warnings
@@ -31,6 +33,29 @@ __all__ = ["IterativeGP"]
 #: 32 - 128 pays at once (61 iterations against 4 on the tests' problem A): ask for it.
 DEFAULT_PRECOND_RANK = 0
 MAXITER_CAP = 1000
+#: probes=None: one group of CG columns, the unit of cost of a pass (DESIGN 3.3 "Marginal likelihood by Lanczos quadrature")
+DEFAULT_PROBES = 32
+
+
+def lanczos_quadrature(alpha, beta):
+    r""":math:`e_1^\top \log(T) e_1` for the Lanczos tridiagonal of one CG run with step lengths `alpha` (``m``) and ratios
+    `beta` (the first ``m - 1`` are used): ``T[j, j] = 1 / alpha_j + beta_{j-1} / alpha_{j-1}``, ``T[j, j+1] = sqrt(beta_j) /
+    alpha_j``.  ``m = 0`` (a zero probe) gives 0.  The eigenproblem goes to LAPACK's QL / QR driver: a long CG run loses
+    orthogonality and its tridiagonal has clusters of near-copies of converged eigenvalues, on which the default driver
+    (``stemr``) reports "did not converge"; for the quadrature the copies are harmless -- their weights add up."""
+    from scipy.linalg import eigh_tridiagonal
+
+    a = np.asarray(alpha, dtype=DTYPE)
+    m = a.size
+    if m == 0:
+        return 0.0
+    b = np.asarray(beta, dtype=DTYPE)[:m - 1]
+    diag = 1.0 / a
+    diag[1:] += b / a[:-1]
+    if m == 1:
+        return float(np.log(diag[0]))
+    w, v = eigh_tridiagonal(diag, np.sqrt(b) / a[:-1], lapack_driver="stev")
+    return float(np.sum(v[0] ** 2 * np.log(w)))
 
 
 class _CgState(Handle):
@@ -70,10 +95,11 @@ class IterativeGP(ParamsMixin):
     maxiter : iterations at most, ``>= 1``; ``None`` is ``min(n, 1000)``
     dtype : ``"float64"`` only (an fp32-product, fp64-recurrence solver is not implemented)
 
-    There is deliberately no `log_lh`, `cov`, `sample`, derivative, pickling or `DistributedGP` counterpart here: the log
-    determinant needs stochastic Lanczos quadrature on the CG coefficients, which is not built.  The hyper-parameters are
-    expected to come from elsewhere -- `SparseGP.optimize` on inducing points, or `mlii` / `GP` on a subset -- and this class
-    to predict exactly with them at the full N.
+    There is deliberately no exact `log_lh`, and no `cov`, `sample`, pickling or `DistributedGP` counterpart here.  The
+    marginal likelihood is available as a STOCHASTIC ESTIMATE -- `log_lh_estimate`, `log_lh_and_grad` and `optimize`, named
+    so because the log determinant comes from Lanczos quadrature on the CG coefficients of random probes (Gardner et al.
+    2018): its `info` carries the standard error, and given probes (``probes=sqrt(n) * np.eye(n)`` at rank 0 is the exact
+    trace) make it deterministic.  Nothing n x n is formed for it either.
     """
 
     def __init__(self, K, x, y, s, precond_rank=None, tol=None, maxiter=None, dtype="float64", device=None):
@@ -317,9 +343,148 @@ class IterativeGP(ParamsMixin):
         xo, _ = self._xo(xo)
         return self.mean(xo), self.var(xo, noise=noise)
 
+    # ---- the marginal likelihood: stochastic Lanczos quadrature ----
+    def _probes_arg(self, probes, seed):
+        """(Z or None, T, seed) of a `probes` argument, checked before the library is touched."""
+        if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not (0 <= int(seed) < 2 ** 64):
+            raise ValueError("invalid value for seed: %r (an int in 0 .. 2^64 - 1)" % (seed,))
+        if probes is None:
+            return None, DEFAULT_PROBES, int(seed)
+        if isinstance(probes, np.ndarray) or isinstance(probes, (list, tuple)):
+            Z = np.ascontiguousarray(probes, dtype=DTYPE)
+            if Z.ndim != 2 or Z.shape[1] != self._n or Z.shape[0] < 1:
+                raise ValueError("invalid shape for probes: %s (n = %d: None, an int >= 1 or a (T, n) array)" % (str(Z.shape), self._n))
+            check_finite(Z)
+            return Z, Z.shape[0], int(seed)
+        return None, count_arg("probes", probes, 1), int(seed)
+
+    def probes(self, T, seed=0):
+        r"""The `T` probe rows the device generates for `seed`, ``(T, n)``: :math:`z \sim N(0, P)` with the preconditioner
+        :math:`P = R^\top R + s^2 I` of the current parameters -- ``z = g1 R + s g2`` from the counter-based normal sequence
+        (``gpx_d_randn``; `g2` is stream 4, `g1` stream 5), and ``z = g2`` at rank 0 (:math:`P = I`).  Row `t` depends on
+        ``(seed, t)`` alone: fewer probes are a prefix of more."""
+        _, T, seed = self._probes_arg(count_arg("T", T, 1), seed)
+        st = self._state()
+        out = np.empty((T, self._n), dtype=DTYPE)
+        _lib.check(_lib.load().gpx_cg_probes(st.handle, T, seed, _lib.dptr(out)))
+        return out
+
+    def _lh(self, probes, seed, want_grad):
+        """One device pass (memoized per argument set): the record `log_lh_estimate` and `log_lh_and_grad` are read from."""
+        Z, T, seed = self._probes_arg(probes, seed)
+        key = ("lh", T if Z is None else Z.tobytes(), seed)
+        have = self._memoized.get(key)
+        if have is not None and (have["grad"] is not None or not want_grad):
+            return have
+        alpha, fit = self._solve_y()                  # (memoized; warns once when y's own solve stopped at maxiter)
+        st = self._state()
+        n, maxiter = self._n, self.maxiter
+        npar = self.K.params.size
+        rho0, relres = np.empty(T, dtype=DTYPE), np.empty(T, dtype=DTYPE)
+        iters = np.zeros(T, dtype=np.int32)
+        coef = np.empty((T, maxiter, 2), dtype=DTYPE)
+        scalars = np.empty(2, dtype=DTYPE)
+        sums, grad = np.empty(max(4, self._d + 2), dtype=DTYPE), np.empty(npar + 1, dtype=DTYPE)
+        p = np.ascontiguousarray(self.K.params, dtype=DTYPE)
+        _lib.check(_lib.load().gpx_cg_lh(st.handle, _lib.dptr(p), float(self._s), None if Z is None else _lib.dptr(Z), T, seed, self.tol,
+                                         maxiter, 1 if want_grad else 0, _lib.dptr(rho0), iters.ctypes.data_as(ctypes.POINTER(ctypes.c_int)),
+                                         _lib.dptr(relres), _lib.dptr(coef), _lib.dptr(scalars), _lib.dptr(sums), _lib.dptr(grad)))
+        st.alpha_version = self._version
+        its = iters.astype(np.int64)
+        lost = its < 0                                # positive definiteness lost to rounding in that column
+        quad = np.array([np.nan if lost[t] else rho0[t] * lanczos_quadrature(coef[t, :its[t], 0], coef[t, :its[t], 1]) for t in range(T)])
+        converged = ~lost & (relres <= self.tol * (1.0 + 4.0 * np.finfo(DTYPE).eps))
+        logdet = float(scalars[0] + quad.mean()) if not lost.any() else np.inf
+        value = -0.5 * float(scalars[1]) - 0.5 * logdet - 0.5 * n * np.log(2.0 * np.pi)
+        if not converged[~lost].all():
+            warnings.warn("IterativeGP: %d of %d probe solves stopped above tol %.3e after maxiter = %d iterations (worst relative "
+                          "residual %.3e); the quadrature of the shorter Lanczos runs is returned"
+                          % (int((~converged & ~lost).sum()), T, self.tol, maxiter, float(relres[~lost].max())), RuntimeWarning, stacklevel=3)
+        if want_grad and lost.any():
+            grad = np.full(npar + 1, np.nan)
+        info = {"logdet": logdet, "logdet_precond": float(scalars[0]), "quad": quad,
+                "stderr": float(quad.std(ddof=1) / np.sqrt(T)) if T > 1 else float("nan"), "fit": -0.5 * float(scalars[1]),
+                "iterations": its, "relres": relres, "converged": converged, "rank": st.rank}
+        rec = {"value": float(value), "grad": grad if want_grad else None, "info": info}
+        self._memoized[key] = rec
+        return rec
+
+    def log_lh_estimate(self, probes=None, seed=0, return_info=False):
+        r"""A stochastic estimate of the log marginal likelihood,
+
+        .. math:: -\tfrac12 y^\top \alpha - \tfrac12 \Big(\log\det P + \tfrac1T \sum_t \rho_t\, e_1^\top \log(T_t)\, e_1\Big) - \tfrac n2 \log 2\pi
+
+        with :math:`T_t` the Lanczos tridiagonal of probe `t` read off its CG coefficients (``T[j, j] = 1 / a_j + b_{j-1} /
+        a_{j-1}``, ``T[j, j+1] = sqrt(b_j) / a_j``) and :math:`\rho_t = z_t^\top P^{-1} z_t`; the eigenproblem of the small
+        tridiagonals is the host's (``scipy.linalg.eigh_tridiagonal``).  `probes`: ``None`` (32: one group of columns, the unit
+        of cost), an int ``>= 1`` (that many, generated on the device from `seed`: `probes`), or a ``(T, n)`` array used as
+        given -- the caller answers for its distribution: the rows' second moment ``Z.T @ Z / T`` must be `P` in expectation
+        (at rank 0 the identity; ``sqrt(n) * np.eye(n)`` has it exactly, and the estimate is then the exact trace).  The same arguments give the same bits, and the result is memoized.
+
+        ``return_info=True``: ``(value, info)`` with ``logdet``, ``logdet_precond``, ``quad`` (the `T` per-probe terms),
+        ``stderr`` (their standard error: that of ``logdet``), ``fit`` (:math:`-y^\top\alpha / 2`), per probe
+        ``iterations`` / ``relres`` / ``converged``, and ``rank``.  A probe column whose recurrence lost positive
+        definiteness (negative count) makes the value ``-inf`` without raising; a column that stopped at `maxiter` warns
+        (``RuntimeWarning``) and the value is still returned: the quadrature of a shorter Lanczos run is still a quadrature."""
+        rec = self._lh(probes, seed, False)
+        return (rec["value"], dict(rec["info"])) if return_info else rec["value"]
+
+    def log_lh_and_grad(self, probes=None, seed=0):
+        r"""``(value, grad)``: `log_lh_estimate` and the estimate of its gradient over `params`, (kernel parameters..., s),
+
+        .. math:: \tfrac12 \alpha^\top \partial K \alpha - \tfrac12 \tfrac1T \sum_t w_t^\top \partial K\, \tilde z_t,
+                  \qquad w_t = (K + s^2 I)^{-1} z_t, \quad \tilde z_t = P^{-1} z_t
+
+        which uses :math:`E[\tilde z z^\top] = I` for :math:`z \sim N(0, P)`.  Both contractions run in one fused tile
+        reduction per group of 32 probes that forms the low-rank coefficients inside the tile (``gpx_d_lowrank_reduce``): no
+        n x n matrix exists.  The noise component comes from the reduction's trace slot.  ``NaN`` gradients (and ``-inf``)
+        when a probe column lost positive definiteness."""
+        rec = self._lh(probes, seed, True)
+        return rec["value"], np.array(rec["grad"], copy=True)
+
+    def optimize(self, maxiter=50, bounds=None, probes=None, seed=0):
+        r"""Maximise `log_lh_estimate` over `params` (all positive) with scipy's L-BFGS-B in log-parameters; one
+        `log_lh_and_grad` call per evaluation, all with the same `probes` and `seed` (common random numbers: the objective is
+        one smooth function of the parameters, not a fresh draw per evaluation).  With generated probes the gradient is that of
+        the EXPECTATION over probes, not of the fixed-probe estimate (the probes' distribution moves with the preconditioner,
+        and its derivative is not taken), so the line search sees a slightly inconsistent pair; with given probes at rank 0
+        the two agree up to the solves' tolerance.  `bounds`: ``None``, or one ``(lo, hi)`` pair per parameter in the natural
+        scale.  The object is left at the best parameters evaluated.  Returns a dict: ``params``, ``log_lh_estimate``,
+        ``evaluations``, ``nit``, ``success``, ``message``."""
+        from scipy.optimize import minimize
+
+        self._probes_arg(probes, seed)
+        npar = self.params.size
+        if bounds is not None:
+            bounds = list(bounds)
+            if len(bounds) != npar:
+                raise ValueError("bounds: one (lo, hi) pair per parameter (%d), got %d" % (npar, len(bounds)))
+            bounds = [tuple(None if b is None else float(np.log(b)) for b in pair) for pair in bounds]
+        best = {"value": -np.inf, "params": self.params}
+        state = {"worst": None, "evaluations": 0}
+
+        def negative(u):
+            self.params = np.exp(u)
+            state["evaluations"] += 1
+            val, grad = self.log_lh_and_grad(probes=probes, seed=seed)
+            if not (np.isfinite(val) and np.all(np.isfinite(grad))):
+                ref = state["worst"] if state["worst"] is not None else 0.0
+                return abs(ref) * 10.0 + 1e10, np.zeros_like(u)
+            if val > best["value"]:
+                best["value"], best["params"] = float(val), self.params
+            state["worst"] = -val if state["worst"] is None else max(state["worst"], -val)
+            return -float(val), -grad * np.exp(u)                 # d/d log theta = theta d/d theta
+
+        res = minimize(negative, np.log(self.params), jac=True, method="L-BFGS-B", bounds=bounds, options={"maxiter": int(maxiter)})
+        self.params = best["params"]
+        found = bool(np.isfinite(best["value"]))
+        msg = res.message.decode() if isinstance(res.message, bytes) else str(res.message)
+        return dict(params=self.params, log_lh_estimate=DTYPE(best["value"]), evaluations=state["evaluations"], nit=int(res.nit),
+                    success=found and bool(res.success), message=msg if found else "no trial point had a finite estimate")
+
     def timing(self):
         """Milliseconds (HIP events on the handle's stream): ``precond`` the last preconditioner build; of the last solve
-        (`inv_Kxx_y`, `solve` or `var`): ``product`` the products with K, ``apply`` the preconditioner applies, ``vector`` the
+        (`inv_Kxx_y`, `solve`, `var` or an estimate's pass): ``product`` the products with K, ``apply`` the preconditioner applies, ``vector`` the
         dots and updates, ``total``, and ``read`` the per-iteration status reads."""
         return timing("gpx_cg_last_timing", self._state().handle, ("precond", "product", "apply", "vector", "total", "read"))
 

@@ -183,6 +183,7 @@ int gpx_stream_wait_event(void *stream, void *event);
 #define GPX_PROF_SPARSE_ZGRAD 21 /* rect_zgrad_kernel and its slice sum (gpx_sgp_grad_z, gpx_d_rect_zgrad): ONE pass of c rows against the M columns; kernel-derivative evaluations c * M per window of dimensions */
 #define GPX_PROF_SELECT      22 /* select_pick_kernel + select_step_kernel (gpx_sgp_select), ONE record per call around all of its launches: bytes of R read and written, sizeof(T) n count (count + 1) / 2 */
 #define GPX_PROF_CG          23 /* gpx_cg_solve, gpx_cg_var: ONE record per call around all of its launches (the product's and the blocks' own launches are recorded under their classes as well); kernel evaluations n^2 x iterations, summed over the groups of columns */
+#define GPX_PROF_LOWRANK     24 /* lowrank_tile_kernel (gpx_d_lowrank_reduce, gpx_cg_lh): ONE launch of at most 32 rows of U and V; kernel-derivative evaluations n^2 */
 int gpx_prof_enable(int on);    /* also clears the registry */
 int gpx_prof_read(int cls, double *launches, double *total_ms, double *total_work);
 
@@ -218,6 +219,7 @@ int gpx_prof_read(int cls, double *launches, double *total_ms, double *total_wor
 #define GPX_ROUTE_SPARSE_CHUNK   25   /* gpx_sgp_fit: one hit per column chunk of x                                   */
 #define GPX_ROUTE_SELECT_STEP    26   /* gpx_sgp_select: one hit per step that picked a point                          */
 #define GPX_ROUTE_CG_ITER        27   /* gpx_cg_solve, gpx_cg_var: one hit per iteration of a group of columns         */
+#define GPX_ROUTE_LOWRANK        28   /* gpx_d_lowrank_reduce, gpx_cg_lh: one hit per launch of the low-rank tile reduction      */
 int gpx_debug_route_count(int route, int64_t *count);
 /* roctx ranges pushed so far (GPX_ROCTX=1: every gpx_gp_* call and every launch class below it is a nested host range for
  * `rocprofv3 --marker-trace`; libroctx64.so is loaded on first use; 0 while the switch is off) */
@@ -760,7 +762,7 @@ int gpx_gp_device_ptrs(gpx_gp_t *gp, void **A, int64_t *lda, void **x, void **y,
  *   f_s(a) = phi(a) . Theta_s + sum_j k(a, x_j) V[s, j],    V_s = alpha - Kxx^-1 (Phi(x) Theta_s + sigma E_s)
  * GPX_KERNEL_GAUSSIAN and GPX_KERNEL_GAUSSIAN_ARD only.  On the handle's view -- points p = x (Gaussian) or x / w (ARD),
  * isotropic constants (h_v, w_v) = (h, w) or (h / sqrt(wbar), 1), k0 = h_v^2 / (w_v sqrt(2 pi)) -- and with z the sequence
- * of gpx_d_randn (stream 0 stays gpx_gp_sample's):
+ * of gpx_d_randn (stream 0 stays gpx_gp_sample's; streams 4 and 5 are gpx_cg_probes'):
  *   Omega[f, k] = z(seed, 1, f d + k) / w_v     f < F, k < d    spectral frequencies, DOUBLE for both dtypes
  *   Theta[s, q] = z(seed, 2, s 2F + q)          s < S, q < 2F   feature weights, handle dtype
  *   E[s, j]     = z(seed, 3, s n + j)           j < n           the observation-noise draw; sigma = the GP's s
@@ -976,6 +978,21 @@ int gpx_d_rect_zgrad(int dtype, int kernel, const void *r, int64_t n, const void
                      const void *C, int64_t ldc, const void *u, const void *v, double scale, const double *col_div,
                      double *partial_dev, double *out_dev, void *stream);
 
+/* gpx_d_lowrank_reduce: the tile reduction whose coefficient is low rank and formed inside the tile (csrc/gpx_lrgrad.hip),
+ *     S_p = sum_{j,i} c_ji dk(x_j, x_i)/dtheta_p,   c_ji = sum_{t<T} U[t, j] V[t, i],   last = sum_j c_jj       j, i < n
+ *   x (n, d), U and V (T x ld, ld >= n; the columns [n, ld) are never read) DEVICE float64; out HOST doubles:
+ *   [P0, P1, P2, last] for GPX_KERNEL_GAUSSIAN (d up to what the tile's LDS holds) and GPX_KERNEL_PERIODIC (d = 1), params the
+ *   family's; [S_0, S_1 .. S_d, last] (S_0 = sum c k, S_k = sum c k t_k^2) for GPX_KERNEL_GAUSSIAN_ARD, where x are the points
+ *   scaled by gpx_d_scale_points and params = (h / sqrt(wbar), 1) -- the slots of the dense gradient's reduction.  No n x n
+ *   object exists: 64 x 64 tiles of the whole square; a tile stages its 64 + 64 points and the T x 64 slices of U (rows) and V
+ *   (columns) in LDS, a pair forms its coefficient by a T-long dot and its distance and derivatives once; everything f64.  At
+ *   most 32 rows of U and V go per launch (GPX_ROUTE_LOWRANK, GPX_PROF_LOWRANK: one each); a larger T is several launches whose
+ *   sums are added in launch order.  One partial per workgroup and quantity, added by the host in workgroup order: no atomics,
+ *   two calls give the same bits.  Synchronous.  GPX_F32 is GPX_ERR_UNSUPPORTED ("float64 only"); GPX_ERR_ARG for NULL
+ *   pointers, T < 1, n < 1, ld < n. */
+int gpx_d_lowrank_reduce(int dtype, int kernel, const void *x, int64_t n, int d, const double *params, const void *U, const void *V,
+                         int64_t ld, int64_t T, double *out, void *stream);
+
 /* ------------------------------------- exact GP past the n x n factor: CG -- */
 /* (K + s^2 I) X^T = B^T by batched preconditioned conjugate gradients; K(x, x) is never formed (Gardner et al. 2018; Wang et
  * al. 2019).  Device memory is n (d + 2 rank + 6 S + 2) doubles and small change, S = min(columns, 32): nothing scales with
@@ -1026,6 +1043,29 @@ int gpx_cg_mean(gpx_cg_t *h, const double *params, const double *xo, int64_t m, 
  * (may be NULL): the largest relres over all columns.  Not clamped at zero. */
 int gpx_cg_var(gpx_cg_t *h, const double *params, double s, const double *xo, int64_t m, double tol, int64_t maxiter, double *out,
                double *worst_relres);
+/* T probe rows z ~ N(0, P) of the preconditioner in force, made on the device: with g2 = gpx_d_randn(T x n; seed, stream 4)
+ * and g1 = gpx_d_randn(T x k; seed, stream 5), z = g1 R + s g2 (one gpx_d_gemm_nt against the resident R^T); rank 0 (P = I):
+ * z = g2.  Row t depends on (seed, t) alone: fewer probes are a prefix of more.  out: T x n HOST, or NULL (generated and dropped). */
+int gpx_cg_probes(gpx_cg_t *h, int64_t T, uint64_t seed, double *out);
+/* One pass of the stochastic estimate of the marginal likelihood and, with want_grad != 0, of its gradient (Gardner et al.
+ * 2018): CG's alpha_j, beta_j are the Lanczos coefficients of P^-1/2 (K + s^2 I) P^-1/2 started at P^-1/2 z, so for probes
+ * z ~ N(0, P):  log det(K + s^2 I) = log det P + E[rho0 e1^T log(T_z) e1],  rho0 = z . P^-1 z, and
+ * tr((K + s^2 I)^-1 dK) = E[w^T dK zt],  w = (K + s^2 I)^-1 z,  zt = P^-1 z  (E[zt z^T] = I).
+ * Z: T x n probes (HOST), or NULL: gpx_cg_probes(T, seed).  The handle's solution alpha for y is solved first if it is absent,
+ * by the rules of gpx_cg_solve(B == NULL) with this tol and maxiter, and stays.  Per group of at most 32 probes: one solve whose
+ * coefficient history cg_fin_kernel records on the device (one download per group; a frozen column's entries are 0) and which
+ * keeps W = (K + s^2 I)^-1 Z and Zt; with want_grad one gpx_d_lowrank_reduce over U = -W / T, V = Zt; at the end one for
+ * U = V = alpha.  Results (HOST):
+ *   rho0, iters, relres  T entries (iters, relres as gpx_cg_solve's)
+ *   coef      T x maxiter x 2: coef[t][j] = (alpha_j, beta_j) of probe t, 0 from its last iteration on (beta of the last is 0)
+ *   scalars   [0] log det P = 2 sum log diag(Lc) + (n - k) log s^2 (0 at rank 0)   [1] y . alpha
+ *   sums      the reduction's slots summed over all launches: G = alpha alpha^T - (1/T) sum_t w_t zt_t^T against dk/dtheta_p
+ *   grad      (kernel parameters ..., s) of the estimate: the dense gradient's host half on `sums`; d/ds = s * last
+ * sums and grad may be NULL without want_grad.  The estimate's block (history, rho0, Zt, the reduction's partials) is
+ * allocated by the first call and only grows: a handle that never asks has the device bytes it had.  GPX_PROF_CG: one record
+ * per call; GPX_ROUTE_CG_ITER per iteration of a group; GPX_ROUTE_LOWRANK per launch of the reduction. */
+int gpx_cg_lh(gpx_cg_t *h, const double *params, double s, const double *Z, int64_t T, uint64_t seed, double tol, int64_t maxiter,
+              int want_grad, double *rho0, int *iters, double *relres, double *coef, double *scalars, double *sums, double *grad);
 /* milliseconds (HIP events on the handle's stream): [0] the last gpx_cg_precond; of the last gpx_cg_solve / gpx_cg_var:
  * [1] the products [2] the preconditioner applies (with rho' = r.z) [3] the vector kernels [4] total [5] the status reads --
  * from the end of an iteration's vector kernels to the first launch the host makes once it has the status */

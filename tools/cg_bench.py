@@ -1,10 +1,10 @@
 """tools/cg_bench.py -- time the iterative exact GP ("Exact GP past the factor: preconditioned CG").
 
     python tools/cg_bench.py [--sweep 65536] [--ranks 0,32,128,512] [--large 262144] [--predict 65536] [--read 8192,65536]
-                             [--d 32] [--dense 1] [--step-timeout 300]
+                             [--d 32] [--dense 1] [--lh 65536,262144] [--probes 32] [--step-timeout 300]
 
 One process, one JSON object per measurement on stdout; Gaussian kernel (h = 1, w = sqrt(d) / 2, s = 1), synthetic inputs of
-oracle.synth_inputs -- the benchmark's data.  Three measurements, each skipped with 0:
+oracle.synth_inputs -- the benchmark's data.  Four measurements, each skipped with 0 (--lh: with an empty list, its default):
   --sweep N    IterativeGP.inv_Kxx_y at N for every rank of --ranks: iterations to tol, gpx_cg_last_timing (the preconditioner's
                build; of the solve: products, preconditioner applies, vector kernels, status reads, total), milliseconds per
                iteration, build + solve, a host clock around the whole call, device bytes; beside it the dense gp.GP fit at the
@@ -13,6 +13,11 @@ oracle.synth_inputs -- the benchmark's data.  Three measurements, each skipped w
                bytes and the drop in free device memory; gp.GP's refusal at the same N is the comparison.
   --read LIST  the per-iteration status read's share of an iteration at each N: rank 0, maxiter 20 and a tolerance of 1e-300, so
                that the solve runs on to 20 iterations or to a residual of exactly 0.
+  --lh LIST    the marginal-likelihood pass at each N, default rank, for every probe count of --probes: the solve for y first (its
+               iterations and time), then one IterativeGP.log_lh_estimate and one log_lh_and_grad (a fresh pass each: the memo is
+               dropped) by a host clock, with the probes' iteration counts, the estimate's standard error, and from the live
+               profile the launches and milliseconds of the low-rank tile reduction (GPX_PROF_LOWRANK) next to its flop model
+               n^2 (d + T) FMAs per launch.
 Every GPU step runs under a watchdog of its own (--step-timeout seconds): a step that overruns it ends the process with exit
 status 124, so nothing further is started on the device.
 """
@@ -84,6 +89,44 @@ def solve_record(g, n, d):
             "model_product_ms": model_ms(n, d), "device_bytes": g.device_bytes}
 
 
+def prof_lowrank():
+    """(launches, milliseconds) of the low-rank tile reduction since the profile was enabled."""
+    import ctypes
+    a, b, c = ctypes.c_double(0), ctypes.c_double(0), ctypes.c_double(0)
+    _lib.check(_lib.load().gpx_prof_read(_lib.PROF_LOWRANK, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)))
+    return int(a.value), b.value
+
+
+def lh_record(g, n, d, probes):
+    """One estimate and one estimate with gradient, each a fresh pass, after the solve for y."""
+    lib = _lib.load()
+    rec = {"measurement": "lh", "n": n, "d": d, "probes": probes, "rank": int(g.solve_info["rank"]),
+           "y_iterations": int(g.solve_info["iterations"][0])}
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore", RuntimeWarning)
+        for name, call in (("estimate", lambda: g.log_lh_estimate(probes=probes, return_info=True)),
+                           ("gradient", lambda: g.log_lh_and_grad(probes=probes))):
+            for key in [k for k in g._memoized if isinstance(k, tuple) and k[0] == "lh"]:
+                del g._memoized[key]
+            _lib.check(lib.gpx_prof_enable(1))
+            t0 = time.perf_counter()
+            out = call()
+            rec[name + "_host_ms"] = 1e3 * (time.perf_counter() - t0)
+            launches, ms = prof_lowrank()
+            _lib.check(lib.gpx_prof_enable(0))
+            rec[name + "_total_ms"] = g.timing()["total"]
+            if name == "estimate":
+                info = out[1]
+                rec.update(value=float(out[0]), stderr=info["stderr"], probe_iterations_max=int(np.abs(info["iterations"]).max()),
+                           probe_iterations_mean=float(np.abs(info["iterations"]).mean()), converged=bool(info["converged"].all()))
+            else:
+                rec.update(reduce_launches=launches, reduce_ms=ms, grad=[float(v) for v in out[1]],
+                           reduce_model_ms=(float(n) * n * 2 * (d + min(probes, 32)) * (launches - 1) + float(n) * n * 2 * (d + 1))
+                           / (FP64_VECTOR_PEAK_TFLOPS * 1e12) * 1e3)
+    rec["device_bytes"] = g.device_bytes
+    return rec
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sweep", type=int, default=65536)
@@ -93,6 +136,8 @@ def main():
     ap.add_argument("--read", default="8192,65536")
     ap.add_argument("--d", type=int, default=32)
     ap.add_argument("--dense", type=int, default=1)
+    ap.add_argument("--lh", default="")
+    ap.add_argument("--probes", default="32")
     ap.add_argument("--step-timeout", type=int, default=300)
     a = ap.parse_args()
     _lib.load()
@@ -152,6 +197,15 @@ def main():
             rec = solve_record(g, n, d)
         rec["measurement"] = "read"
         emit(rec)
+        g._dev.close()
+    for n in [int(v) for v in a.lh.split(",") if v]:
+        X, y, _ = orc.synth_inputs(n, d, 1)
+        g = gp.IterativeGP(gp.GaussianKernel(h, w), X, y, s)
+        with Step("lh N = %d: the solve for y" % n, a.step_timeout):
+            g.inv_Kxx_y
+        for probes in [int(v) for v in a.probes.split(",")]:
+            with Step("lh N = %d, %d probes" % (n, probes), a.step_timeout):
+                emit(lh_record(g, n, d, probes))
         g._dev.close()
 
 
